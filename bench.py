@@ -13,11 +13,19 @@ replicas; the only collective is the final logits all-gather).  A "step" = one 2
 all 36 layers (27 Gated DeltaNet + 9 SWA mixers on the gfx950 kernels of this repo, the projections/MLP
 on stock rocBLAS/hipBLASLt).  Untimed setup streams 131072 - K*256 tokens (at least the 17 steps that fill the SWA window), so that the K
 timed steps are steady-state full-window steps that END at exactly 128K tokens of context whatever K is.
-After the timed prefill region a decode leg (graph-captured greedy single-token steps at that context)
-is timed separately and reported as `decode_tok_s`.
+A plain run does only that: set-up, the untimed and warm-up steps, the K timed steps, then rank 0 prints ONE JSON
+line (`value` = prefill tok/s of the timed steps, `ms_per_step`).
 
-Rank 0 prints ONE JSON line.  Extra objects: `roofline` (dominant hot-path kernel, measured live with
-HIP events on the launch stream), `kernels` (all hot-path kernels), `cpu_baseline` (oracle on host cores).
+    --dump-outputs DIR   after the timed steps, rank 0 writes what the last timed step returned to its caller as
+                         float32 DIR/hidden.npy (B, chunk, 2048) and DIR/logits.npy (B, 1, 151936); the inputs are
+                         seeded, so two builds can be compared output for output at the same arguments
+    --full               everything beyond the headline, in the same line: a decode leg (graph-captured greedy
+                         single-token steps at the reached context, `decode_tok_s`), `roofline` (dominant hot-path
+                         kernel, measured live with HIP events on the launch stream), `kernels` (all hot-path
+                         kernels), `cpu_baseline` (oracle on host cores), `fp8_e4m3` (configs[4]),
+                         `cfg1_4k_prefill_decode` (configs[1]), `cfg3_512k_prefill` (configs[3]) and, at N > 1,
+                         `dist` (what the collective ran on + the sequence-parallel leg); the --no-* options drop
+                         single legs of it
 """
 import argparse
 import json
@@ -77,7 +85,23 @@ def parse():
                          "sequence of N tokens per rank in 4096-token calls from position 0 (524288 = the full configs[3] sequence, 128 calls)")
     ap.add_argument("--sp-tokens", type=int, default=4096, help="N > 1: tokens per rank of the sequence-parallel prefill leg")
     ap.add_argument("--no-sp", action="store_true", help="N > 1: skip the sequence-parallel prefill leg (SURVEY.md 8f-4)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run the decode leg, kernel timings / roofline, CPU baseline, fp8, configs[1] / configs[3] legs and, "
+                         "at N > 1, the collective checks and the sequence-parallel leg (the --no-* options apply to these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as float32 DIR/hidden.npy and DIR/logits.npy (rank 0)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+def dump_outputs(out_dir, arrays):
+    """Write each tensor of `arrays` as float32 `out_dir/<name>.npy` (--dump-outputs)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.detach().float().cpu().numpy())
 
 
 def event_time_ms(fn, iters, stream):
@@ -568,21 +592,24 @@ def main():
     elapsed = ivd.max_over_ranks(elapsed, device)
     tokens_global = args.steps * T * B_local * world
     ctx_tokens = cache.get_seq_length()
+    if args.dump_outputs and rank == 0:
+        # what GraphedStep.step returns to its caller: 2.7 MB at the default shapes
+        dump_outputs(args.dump_outputs, {"hidden": step.hidden, "logits": step.logits})
 
     # the path's only collective: gather the last-position logits of every sequence
     _, logits = step.hidden, step.logits
     last = logits[:, -1].float().contiguous()
     all_logits = ivd.gather_last_logits(last, [B_local] * world)              # first call: communicator set-up included
-    torch.cuda.synchronize()
-    tg = time.perf_counter()
-    all_logits = ivd.gather_last_logits(last, [B_local] * world)
-    torch.cuda.synchronize()
-    allgather_ms = ivd.max_over_ranks((time.perf_counter() - tg) * 1e3, device)
     finite = bool(torch.isfinite(all_logits).all())
     # what the collective actually ran on (N > 1): backend, one record per rank, the gathered shape.  Ranks must sit on
     # distinct GPUs under RCCL (the gloo debug mode IVL_DIST_BACKEND=gloo may stack ranks on one device).
     dist_info = None
-    if world > 1:
+    if world > 1 and args.full:
+        torch.cuda.synchronize()
+        tg = time.perf_counter()
+        all_logits = ivd.gather_last_logits(last, [B_local] * world)
+        torch.cuda.synchronize()
+        allgather_ms = ivd.max_over_ranks((time.perf_counter() - tg) * 1e3, device)
         dist_info = ivd.describe_ranks(device)
         dist_info.update(gathered_logits_shape=list(all_logits.shape), allgather_ms=allgather_ms,
                          logits_rows_differ_across_ranks=bool(world < 2 or not torch.equal(all_logits[0], all_logits[1])))
@@ -592,31 +619,32 @@ def main():
 
     # per-kernel durations inside the real step, live (rank 0; outside the timed region; the cache advances like in a step)
     live_prefill = live_decode = None
-    if rank == 0 and not args.no_kernel_timing:
+    if rank == 0 and args.full and not args.no_kernel_timing:
         try:
             live_prefill = profile_replays(lambda: step.step(frames[0]))
         except Exception as e:                       # profiler unavailable: the committed rocprofv3 trace is used instead
             print(f"[bench] torch.profiler unavailable ({type(e).__name__}: {e})", file=sys.stderr)
 
     # ---- decode leg (separately timed) ------------------------------------------------------------
-    dec = GraphedDecode(model, cache, B_local)
-    dec.token.copy_(logits[:, -1].argmax(-1, keepdim=True))
-    dec.capture()
-    for _ in range(4):
-        dec.step()
-    ivd.barrier()
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    for _ in range(args.decode_steps):
-        dec.step()
-    torch.cuda.synchronize()
-    ivd.barrier()
-    dec_elapsed = ivd.max_over_ranks(time.perf_counter() - t1, device)
-    if rank == 0 and live_prefill is not None:
-        try:
-            live_decode = profile_replays(dec.step, n=8)
-        except Exception as e:
-            print(f"[bench] torch.profiler unavailable for the decode graph ({type(e).__name__}: {e})", file=sys.stderr)
+    if args.full:
+        dec = GraphedDecode(model, cache, B_local)
+        dec.token.copy_(logits[:, -1].argmax(-1, keepdim=True))
+        dec.capture()
+        for _ in range(4):
+            dec.step()
+        ivd.barrier()
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        for _ in range(args.decode_steps):
+            dec.step()
+        torch.cuda.synchronize()
+        ivd.barrier()
+        dec_elapsed = ivd.max_over_ranks(time.perf_counter() - t1, device)
+        if rank == 0 and live_prefill is not None:
+            try:
+                live_decode = profile_replays(dec.step, n=8)
+            except Exception as e:
+                print(f"[bench] torch.profiler unavailable for the decode graph ({type(e).__name__}: {e})", file=sys.stderr)
     mem_gb = torch.cuda.max_memory_allocated(device) / 2 ** 30
 
     # ---- sequence-parallel prefill leg (N > 1; reported beside the headline, never mixed into `value`): ONE
@@ -624,7 +652,7 @@ def main():
     #      every layer's carried state to rank r + 1 (point-to-point: device tensors over xGMI under RCCL, host-staged under the
     #      gloo debug backend).  Checked on the last rank against its own single-rank run of the same call sequence.
     sp = None
-    if world > 1 and not args.no_sp:
+    if world > 1 and args.full and not args.no_sp:
         # Every stage that can fail on ONE rank (allocations, the last rank's single-rank reference run) ends in an exchange of
         # an ok flag (all_reduce MIN) BEFORE the next collective, so a rank that raised does not leave the others blocked in a
         # barrier / broadcast: all ranks then skip the rest of the leg and the error is recorded.  The headline above is
@@ -703,7 +731,7 @@ def main():
     # ---- fp8 leg (rank 0, reported beside the headline, never mixed into `value`): BASELINE.json configs[4] -- the same
     #      steady-state streaming step and decode step with e4m3 operands in the GDN chunk scan / SWA decode step
     fp8 = None
-    if rank == 0 and not args.no_fp8:
+    if rank == 0 and args.full and not args.no_fp8:
         model.set_mma_dtype("fp8_e4m3")
         cache8 = cache.clone()
         step8 = GraphedStep(model, cache8, B_local, T, logits_to_keep=1)
@@ -745,7 +773,7 @@ def main():
     #      tokens over that time, and the last-position logits of all sequences are gathered ONCE at the end (the path's only
     #      collective).
     cfg3 = None
-    if not args.no_cfg3:
+    if args.full and not args.no_cfg3:
         Tb = 4096
         fresh = args.cfg3_tokens > 0
         n_warm, n_timed = (1, max(1, args.cfg3_tokens // Tb)) if fresh else (2, 8)
@@ -869,7 +897,7 @@ def main():
     #      4096-token prefill call on a fresh cache (chunk path over 64 chunks; SWA purely causal) + 128 graphed decode steps;
     #      the slowest rank defines both times (MAX over ranks), aggregates are all ranks' tokens over them
     cfg1 = None
-    if not args.no_cfg1:
+    if args.full and not args.no_cfg1:
         del step, dec
         Tp, reps = 4096, 3
         err1, pf, tdec, fin1 = None, None, None, None
@@ -915,9 +943,9 @@ def main():
                     "decode_ms_per_token": tdec / 128 * 1e3, "logits_finite": fin1}
 
     kernels, cpu = None, None
-    if rank == 0 and not args.no_kernel_timing:
+    if rank == 0 and args.full and not args.no_kernel_timing:
         kernels = kernel_timings(device, T, args.window, live_prefill=live_prefill, live_decode=live_decode)
-    if rank == 0 and not args.no_cpu_baseline:          # rank 0 at any N (the other ranks wait in the barrier below)
+    if rank == 0 and args.full and not args.no_cpu_baseline:          # rank 0 at any N (the other ranks wait in the barrier below)
         cpu = cpu_baseline(T, args.window)
     ivd.barrier()
 
@@ -927,15 +955,16 @@ def main():
             "value": tokens_global / elapsed, "unit": "tok/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
-            "decode_tok_s": args.decode_steps * B_local * world / dec_elapsed,
-            "decode_ms_per_token": dec_elapsed / args.decode_steps * 1e3,
+            **({"decode_tok_s": args.decode_steps * B_local * world / dec_elapsed,
+                "decode_ms_per_token": dec_elapsed / args.decode_steps * 1e3} if args.full else {}),
             "config": {
                 "workload": f"InfiniteVL-3B ({args.layers} layers: 9 SWA + 27 Gated DeltaNet, random-init bf16) streaming "
-                            f"prefill, {T}-token hipGraph chunk steps, SWA window {args.window} (full), then greedy decode "
-                            f"at the reached context",
+                            f"prefill, {T}-token hipGraph chunk steps, SWA window {args.window} (full)"
+                            + (", then greedy decode at the reached context" if args.full else ""),
                 "global_batch": B_local * world, "seq_len": ctx_tokens, "tokens_timed": tokens_global,
                 "parallelism": f"dp{world} (batch-sharded replicas, one logits all-gather)",
-                "decode_steps": args.decode_steps, "untimed_steps_before_timed_region": fill + args.warmup,
+                **({"decode_steps": args.decode_steps} if args.full else {}),
+                "untimed_steps_before_timed_region": fill + args.warmup,
             },
             "logits_finite": finite, "peak_mem_gib": round(mem_gb, 2),
         }

@@ -1712,7 +1712,7 @@ def test_sequence_parallel_prefill_two_ranks_bit_exact():
 
 
 def test_bench_two_ranks_reports_what_the_collective_ran_on():
-    """bench.py --gpus 2 (self-spawned under torch.distributed.run) with the gloo debug backend, both ranks on this GPU: the
+    """bench.py --gpus 2 --full (self-spawned under torch.distributed.run) with the gloo debug backend, both ranks on this GPU: the
     JSON line carries a `dist` object (backend, world, one record per rank with device index and PCI bus id, the gathered
     logits' shape, the all-gather time) - the fields that make a driver-run multi-GPU line checkable from its output.  Under
     RCCL the same code asserts that the ranks sit on distinct devices."""
@@ -1723,7 +1723,7 @@ def test_bench_two_ranks_reports_what_the_collective_ran_on():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", IVL_DIST_BACKEND="gloo", IVL_NO_TUNABLEOP="1")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([_sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+    r = subprocess.run([_sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--full", "--steps", "2", "--warmup", "1",
                         "--layers", "4", "--context", "8192", "--decode-steps", "2",
                         "--no-fp8", "--no-kernel-timing", "--sp-tokens", "1024"], capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
@@ -1757,6 +1757,33 @@ def test_bench_two_ranks_reports_what_the_collective_ran_on():
     assert c1["n_gpus"] == 2 and c1["prefill_tok_s"] > 0 and c1["decode_tok_s"] > 0 and c1["logits_finite"]
     cb = out["cpu_baseline"]
     assert cb["kind"] == "port" and cb["value"] > 0 and cb["cores"] >= 1 and "oracle/model.py" in cb["sample"]
+
+
+def test_bench_plain_run_and_dumped_outputs(tmp_path):
+    """bench.py without --full: the line carries the headline (`value` = tok/s of the --steps timed steps, `ms_per_step`) and
+    none of the --full legs; --dump-outputs writes the last timed step's hidden states and logits as float32 .npy files."""
+    import json as _json
+    import subprocess
+    import sys as _sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, IVL_NO_TUNABLEOP="1")
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    dump = tmp_path / "outputs"
+    r = subprocess.run([_sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--layers", "4", "--context", "8192", "--dump-outputs", str(dump)],
+                       capture_output=True, text=True, timeout=600, env=env)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
+    out = _json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert out["metric"] == "prefill tok/s + decode tok/s, InfiniteVL-3B @128K seq" and out["unit"] == "tok/s"
+    assert out["higher_is_better"] is True and out["dtype"] == "bf16" and out["steps"] == 3 and out["warmup"] == 1
+    assert out["config"]["tokens_timed"] == 3 * 256 and out["config"]["seq_len"] == 8192
+    assert out["ms_per_step"] > 0 and abs(out["value"] - 256 / (out["ms_per_step"] * 1e-3)) < 1e-6 * out["value"]
+    assert not set(out) & {"decode_tok_s", "roofline", "kernels", "cpu_baseline", "fp8_e4m3", "cfg1_4k_prefill_decode",
+                           "cfg3_512k_prefill", "dist"}
+    h, lg = np.load(dump / "hidden.npy"), np.load(dump / "logits.npy")
+    assert h.dtype == np.float32 and h.shape == (1, 256, 2048) and lg.dtype == np.float32 and lg.shape == (1, 1, 151936)
+    assert np.isfinite(h).all() and np.isfinite(lg).all() and np.abs(h).max() > 0 and np.abs(lg).max() > 0
 
 
 def test_full_attention_layer_with_dynamic_cache_equals_one_causal_call():

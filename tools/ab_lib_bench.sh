@@ -1,20 +1,20 @@
 #!/bin/bash
-# Same-box A/B of the default bench line with another build of the library (developer use):
-#   tools/ab_lib_bench.sh tools/ab/libivl_other.so [rounds]      -> gpurun_out/ab_lib/{base,other}_N.json, one summary line each
-lib=$1; rounds=${2:-2}
-mkdir -p gpurun_out/ab_lib
+# Same-box A/B of the full bench line with another build of the library (developer use):
+#   tools/ab_lib_bench.sh tools/ab/libivl_other.so [rounds] [outdir]   -> outdir/{base,other}_N.json, one summary line each
+lib=$1; rounds=${2:-2}; out=${3:-$(mktemp -d)}
+mkdir -p "$out"
 for r in $(seq 1 $rounds); do
-  python bench.py > gpurun_out/ab_lib/base_$r.json 2>/dev/null
+  python bench.py --full > "$out/base_$r.json" 2>/dev/null
   python -c "
 import runpy, sys
 from infinitevl_amd import _lib
 _lib.load('$lib')
-sys.argv = ['bench.py']
-runpy.run_path('bench.py', run_name='__main__')" > gpurun_out/ab_lib/other_$r.json 2>/dev/null
+sys.argv = ['bench.py', '--full']
+runpy.run_path('bench.py', run_name='__main__')" > "$out/other_$r.json" 2>/dev/null
 done
-python - <<'PY'
-import json, glob
-for f in sorted(glob.glob('gpurun_out/ab_lib/*.json')):
+python - "$out" <<'PY'
+import json, glob, sys
+for f in sorted(glob.glob(sys.argv[1] + '/*.json')):
     try:
         d = json.loads(open(f).read().strip().splitlines()[-1])
     except Exception as e:

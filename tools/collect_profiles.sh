@@ -13,7 +13,7 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/prof_bench /tmp/pmc_FETCH_SIZE /tmp/pmc_WRITE_SIZE
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_bench -o bench -- \
-    python $REPO/bench.py --steps 64 --warmup 4 --decode-steps 32 --no-cpu-baseline > $OUT/${TAG}_bench_under_rocprof.json 2>/dev/null
+    python $REPO/bench.py --full --steps 64 --warmup 4 --decode-steps 32 --no-cpu-baseline > $OUT/${TAG}_bench_under_rocprof.json 2>/dev/null
 cp /tmp/prof_bench/bench_kernel_stats.csv $OUT/${TAG}_bench_kernel_stats.csv
 # the same trace keyed by (kernel, grid): one row per launch SHAPE, so the 256-token step's launches are not mixed with the
 # decode / 4096-token / batched shapes of the same kernel name (avg_ns of gdn_chunk_prepare@32768 + gdn_chunk_scan<2>@49152
