@@ -254,6 +254,15 @@ IVL_API size_t ivl_swa_workspace_bytes(int B, int T, int Hq, int d);
 /* Workspace of the 256-row form of a long call over a full ring (see ivl_swa_args.pos_min); 0: the shape does not qualify. */
 IVL_API size_t ivl_swa_ring256_workspace_bytes(int B, int T, int Hq, int Hkv, int d, int cache_capacity);
 IVL_API int ivl_swa_fwd(const ivl_swa_args* args, void* stream);
+/* The packed decode step of ivl_swa_fwd with ONE RING POSITION PER BATCH ROW (independent streams in the rows of one
+ * cache).  pos_rows: device int64[B]; row b attends exactly as ivl_swa_fwd does at pos = pos_rows[b] (n_ring =
+ * min(pos_rows[b], C), key 0 in ring slot (pos_rows[b] - n_ring) mod C, same band), and with append_new its tokens go to
+ * slots (pos_rows[b] + t) % C.  args->pos, pos_dev and pos_min are ignored; pos_rows is never written (advancing the
+ * positions is the caller's job).  Scope: a ring cache, T_new == T, T * Hq/Hkv <= 64, mma_dtype IVL_BF16; fused rope and
+ * append_new as in ivl_swa_fwd.  Workspace: ivl_swa_workspace_bytes(B, T, Hq, d).  Two launches (split-KV attention, then the
+ * combine with the append folded in), with the split count of ivl_swa_fwd: a row's output and ring are bit-identical to a
+ * B = 1 ivl_swa_fwd of that row.  Other shapes: IVL_ERR_UNSUPPORTED; NULL pos_rows: IVL_ERR_INVALID_ARG. */
+IVL_API int ivl_swa_decode_rows_fwd(const ivl_swa_args* args, const int64_t* pos_rows, void* stream);
 
 /* Append the T new tokens to the ring (slot (pos+t) % C) -- after ivl_swa_fwd of the same call.
  * Replaces the tail copy-back of std:146-172.  k_new,v_new bf16 with the strides given.  With rope_cos / rope_sin

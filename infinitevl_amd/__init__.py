@@ -11,14 +11,14 @@ Layout
     dist.py      batch-sharded multi-GPU driver (RCCL all-gather of the last-token logits)
 """
 from . import _lib
-from .cache import StaticCachePrealloc, StaticLinearLayerPrealloc, StaticSlidingWindowLayerPrealloc
+from .cache import MultiStreamCache, StaticCachePrealloc, StaticLinearLayerPrealloc, StaticSlidingWindowLayerPrealloc
 from .modules import GatedDeltaNet, InfiniteVLRotaryEmbedding, InfiniteVLSelfAttention
 from .ops import (FusedRMSNormGated, RMSNorm, ShortConvolution, apply_mrope_inplace, chunk_gated_delta_rule,
                   fused_recurrent_gated_delta_rule, gdn_gate, get_unpad_data, index_first_axis, pad_input,
                   swa_attention_interface, swa_forward)
 
 __all__ = [
-    "StaticCachePrealloc", "StaticLinearLayerPrealloc", "StaticSlidingWindowLayerPrealloc",
+    "MultiStreamCache", "StaticCachePrealloc", "StaticLinearLayerPrealloc", "StaticSlidingWindowLayerPrealloc",
     "GatedDeltaNet", "InfiniteVLSelfAttention", "InfiniteVLRotaryEmbedding",
     "FusedRMSNormGated", "RMSNorm", "ShortConvolution", "get_unpad_data", "index_first_axis", "pad_input", "chunk_gated_delta_rule", "fused_recurrent_gated_delta_rule",
     "gdn_gate", "apply_mrope_inplace", "swa_attention_interface", "swa_forward", "load_library",

@@ -30,6 +30,7 @@ EXPORTED_SYMBOLS = (
     "ivl_gdn_sync_status", "ivl_gdn_sync_reset", "ivl_gdn_resident_blocks",
     "ivl_short_conv_bias_fwd", "ivl_rmsnorm_swish_gate_res_fwd", "ivl_gdn_recurrent_f16_fwd",
     "ivl_gdn_decode_split_fwd", "ivl_gdn_out_linear_small_m_fwd", "ivl_swa_ring256_workspace_bytes",
+    "ivl_swa_decode_rows_fwd",
 )
 
 
@@ -120,6 +121,9 @@ def load(path: str = None) -> ctypes.CDLL:
     lib.ivl_swa_ring256_workspace_bytes.argtypes = [i, i, i, i, i, i]
     lib.ivl_swa_fwd.restype = i
     lib.ivl_swa_fwd.argtypes = [POINTER(SwaArgs), vp]
+    if path is None or hasattr(lib, "ivl_swa_decode_rows_fwd"):   # (a developer A/B against an older build lacks it)
+        lib.ivl_swa_decode_rows_fwd.restype = i
+        lib.ivl_swa_decode_rows_fwd.argtypes = [POINTER(SwaArgs), vp, vp]
     lib.ivl_swa_cache_append.restype = i
     lib.ivl_swa_cache_append.argtypes = [vp, vp, i64, i64, i64, vp, vp, i, i, i, i, i, i64, vp, vp, vp, i, i, vp]
     lib.ivl_counter_add.restype = i

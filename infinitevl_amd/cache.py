@@ -481,6 +481,7 @@ class DynamicLayer(_HFLayer):
 class StaticCachePrealloc(_HFCache):
     """Aggregate cache: one pre-allocated layer object per decoder layer, dispatched by
     `config.layer_types` (std:366-443)."""
+    _sliding_layer_cls = StaticSlidingWindowLayerPrealloc
 
     def __init__(self, *, config, batch_size: int = 1, device="cpu", dtype: torch.dtype = torch.float32,
                  zero_init: bool = False, recurrent_state_shape: Optional[Tuple[int, ...]] = None,
@@ -494,8 +495,8 @@ class StaticCachePrealloc(_HFCache):
             layer_types = layer_types[: -int(getattr(cfg, "num_kv_shared_layers"))]
         for lt in layer_types:
             if lt in ("sliding_attention", "chunked_attention"):
-                layers.append(StaticSlidingWindowLayerPrealloc(config=cfg, batch_size=batch_size, device=device,
-                                                               dtype=dtype, zero_init=zero_init))
+                layers.append(self._sliding_layer_cls(config=cfg, batch_size=batch_size, device=device,
+                                                      dtype=dtype, zero_init=zero_init))
             elif lt in ("linear_attention", "delta_net", "retnet", "state_space"):
                 layers.append(StaticLinearLayerPrealloc(config=cfg, batch_size=batch_size, device=device, dtype=dtype,
                                                         zero_init=zero_init,
@@ -563,3 +564,163 @@ class StaticCachePrealloc(_HFCache):
                 if torch.is_tensor(t):
                     total += t.numel() * t.element_size()
         return total
+
+
+# ---- independent streams in the rows of one cache ------------------------------------------------------------------
+
+
+def _retype(obj, cls):
+    """A shallow copy of `obj` as an instance of `cls` (same attributes; tensors shared until reassigned)."""
+    new = cls.__new__(cls)
+    new.__dict__.update(vars(obj))
+    return new
+
+
+class MultiStreamSlidingLayer(StaticSlidingWindowLayerPrealloc):
+    """Sliding layer of a MultiStreamCache: row b of the ring belongs to slot b, which has its own position
+    `_pos_rows[b]` (device int64 [n_slots], shared by all sliding layers of the cache; `_lengths` is its host mirror).
+    Decode steps of one token only: a prompt is prefilled on MultiStreamCache.slot_view."""
+
+    def __init__(self, **kw):
+        super().__init__(**kw)
+        self._pos_rows = torch.zeros(self.batch_size, dtype=torch.int64, device=self.device)
+        self._lengths = [0] * self.batch_size
+
+    def attend(self, q, k_new, v_new, scaling, window, mma_dtype=None, rope=None):
+        B, T, Hkv, D = k_new.shape
+        if T != 1:
+            raise ValueError(f"MultiStreamCache decodes one token per slot and step (got T={T}); prefill a slot through "
+                             "MultiStreamCache.slot_view(slot)")
+        if mma_dtype is not None and ops.mma_code(mma_dtype) != ops.IVL_BF16:
+            raise ValueError("MultiStreamCache: the fp8 decode step is not supported (bf16 only)")
+        if B != self.batch_size:
+            raise ValueError(f"MultiStreamCache has {self.batch_size} slots, but got B={B}")
+        o = ops.swa_forward(q, k_new, v_new, window=window, scaling=scaling, k_cache=self._buf_keys,
+                            v_cache=self._buf_values, pos_rows=self._pos_rows, rope=rope, append=True)
+        if self._advances_counter:
+            self._pos_rows.add_(1)
+        self.advance(1)
+        return o
+
+    def advance(self, T: int) -> None:
+        if self._advances_counter:
+            for i in range(len(self._lengths)):
+                self._lengths[i] += int(T)
+
+    def get_seq_length(self, *a, **k) -> int:
+        raise ValueError("MultiStreamCache: every slot has its own length (MultiStreamCache.get_seq_length(slot=...))")
+
+    def reset(self) -> None:
+        super().reset()
+        self._pos_rows.zero_()
+        self._lengths[:] = [0] * len(self._lengths)
+
+    def clone(self) -> "MultiStreamSlidingLayer":
+        new = super().clone()
+        new._pos_rows = self._pos_rows.clone()
+        new._lengths = list(self._lengths)
+        return new
+
+    def copy_from(self, other: "MultiStreamSlidingLayer") -> None:
+        super().copy_from(other)
+        self._pos_rows.copy_(other._pos_rows)
+        self._lengths[:] = other._lengths
+
+
+class _SlotSlidingLayer(StaticSlidingWindowLayerPrealloc):
+    """Sliding layer of a slot view: B = 1 aliases of one ring row and of its position; the counting layer reports
+    the slot's length back to the host mirror of the multi-stream cache."""
+
+    def advance(self, T: int) -> None:
+        super().advance(T)
+        if self._advances_counter:
+            self._lengths[self._slot] = self.cumulative_length
+
+
+class MultiStreamCache(StaticCachePrealloc):
+    """A StaticCachePrealloc whose batch rows are SLOTS: independent streams that join (admit) and leave (release) between
+    decode steps.  Every slot has its own ring position (`pos_rows`, device int64 [n_slots], shared by all sliding layers;
+    `slot_lengths` is its host mirror).  A decode step advances every slot by one token in one launch (idle slots compute
+    on zeros; their outputs are ignored).  A prompt is prefilled on `slot_view(slot)`, a B = 1 cache aliasing the slot's
+    row, through the unchanged stack forward.  bf16 only; a stack forward needs explicit position_ids."""
+    _sliding_layer_cls = MultiStreamSlidingLayer
+
+    def __init__(self, *, config, n_slots: int, device="cpu", dtype: torch.dtype = torch.float32):
+        super().__init__(config=config, batch_size=n_slots, device=device, dtype=dtype, zero_init=True)
+        self.n_slots = int(n_slots)
+        if not any(isinstance(l, MultiStreamSlidingLayer) for l in self.layers):
+            raise ValueError("MultiStreamCache needs at least one sliding-window layer")
+        self.ensure_started()                # zero history in every GDN layer: the decode graph always reads the tensors
+
+    def _share_position_counter(self) -> None:
+        super()._share_position_counter()
+        sliding = [l for l in self.layers if isinstance(l, MultiStreamSlidingLayer)]
+        for layer in sliding[1:]:
+            layer._pos_rows, layer._lengths = sliding[0]._pos_rows, sliding[0]._lengths
+
+    def _sliding(self):
+        return [l for l in self.layers if isinstance(l, MultiStreamSlidingLayer)]
+
+    @property
+    def pos_rows(self) -> torch.Tensor:
+        return self._sliding()[0]._pos_rows
+
+    @property
+    def slot_lengths(self):
+        return self._sliding()[0]._lengths
+
+    def get_seq_length(self, layer_idx: int = 0, *a, slot: Optional[int] = None, **k) -> int:
+        if slot is None:
+            raise ValueError("MultiStreamCache: the slots have different lengths; pass position_ids to the forward "
+                             "(or get_seq_length(slot=...))")
+        return int(self.slot_lengths[slot])
+
+    def _check_slot(self, slot: int) -> int:
+        slot = int(slot)
+        if not 0 <= slot < self.n_slots:
+            raise IndexError(f"slot {slot} out of range [0, {self.n_slots})")
+        return slot
+
+    def admit(self, slot: int) -> None:
+        """Empty slot `slot` for a new stream: its GDN states are zeroed and its position restarts at 0 (the ring row is
+        not read below the position).  In-place writes only: valid between replays of a captured graph."""
+        slot = self._check_slot(slot)
+        for layer in self.layers:
+            if isinstance(layer, StaticLinearLayerPrealloc):
+                for t in layer.carried_tensors():
+                    t[slot].zero_()
+        self.pos_rows[slot:slot + 1].zero_()
+        self.slot_lengths[slot] = 0
+
+    release = admit
+
+    def slot_view(self, slot: int) -> StaticCachePrealloc:
+        """A B = 1 StaticCachePrealloc whose tensors alias row `slot` (ring, conv and recurrent states, position): a prompt
+        runs through the unchanged stack forward on it (chunked GDN, 128 / 256-row attention, in-place state)."""
+        slot = self._check_slot(slot)
+        n = self.slot_lengths[slot]
+        layers = []
+        for layer in self.layers:
+            if isinstance(layer, MultiStreamSlidingLayer):
+                v = _retype(layer, _SlotSlidingLayer)
+                v.batch_size = 1
+                if layer._buf_keys is not None:
+                    v._buf_keys, v._buf_values = layer._buf_keys[slot:slot + 1], layer._buf_values[slot:slot + 1]
+                v._pos_dev = layer._pos_rows[slot:slot + 1]
+                v._slot = slot
+                v.size, v.cumulative_length = int(min(layer.capacity, n)), int(n)
+            elif isinstance(layer, StaticLinearLayerPrealloc):
+                v = copy.copy(layer)
+                v.batch_size = 1
+                for name in ("conv_state_q", "conv_state_k", "conv_state_v", "recurrent_state"):
+                    t = getattr(layer, name)
+                    if t is not None:
+                        setattr(v, name, t[slot:slot + 1])
+                v.start, v.seq_len = True, int(n)
+            else:
+                raise ValueError(f"MultiStreamCache.slot_view: unsupported layer type {type(layer).__name__}")
+            layers.append(v)
+        view = _retype(self, StaticCachePrealloc)      # the aggregate's own bookkeeping, with per-slot layers
+        view.layers = layers
+        view._share_position_counter()
+        return view

@@ -62,352 +62,18 @@ __device__ __forceinline__ float group_sum(float x) {
 
 template <bool PACK, int QG>
 __global__ __launch_bounds__(256, 2) void swa_fwd_kernel(const long long* pos_dev, SwaParams p) {   // (pos_dev: see swa_prefill_kernel)
-  __shared__ __attribute__((aligned(16))) unsigned char smem[SWA_LDS_BYTES];
-  constexpr int QT = SWA_QT * QG;      // query rows per workgroup
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int l15 = lane & 15, g = lane >> 4;
-  const int G = p.Hq / p.Hkv;
-  // 1-D grid with an XCD-aware (bijective) remap: hardware block id i runs on XCD i % 8; logical ids are
-  // ordered (b, split, kv-head, head-in-group, q-tile) so the workgroups that read the SAME K/V range are
-  // consecutive and therefore land on the same XCD / L2 (they re-read each K/V tile up to 8 x n_qtiles times).
-  const int heads_y = PACK ? p.Hkv : p.Hq;
-  int bx, rest;                      // q-tile, and (b * nsplit + split) * heads_y + head
-  {
-    const int nwg = gridDim.x, xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int qn = nwg >> 3, rn = nwg & 7;
-    if (rn == 0 && qn % p.n_qtiles == 0) {
-      // every XCD owns whole (batch, split, head) rows.  Inside an XCD the workgroups are issued heaviest first
-      // (the work of a q-tile grows with its index: causal / window not yet full), so the long workgroups no
-      // longer form the tail.  When all of them are co-resident (<= 2 per CU) the upper half goes first in
-      // descending order and the lower half follows in ascending order: a heavy one shares its CU with a light one.
-      const int hx = qn / p.n_qtiles;                       // rows per XCD
-      const int r = slot / hx, half = (p.n_qtiles + 1) >> 1;
-      bx = qn > 64 ? p.n_qtiles - 1 - r : (r < half ? p.n_qtiles - 1 - r : r - half);
-      rest = xcd * hx + slot % hx;
-    } else {
-      const int lid = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + slot;
-      bx = lid % p.n_qtiles;
-      rest = lid / p.n_qtiles;
-    }
-  }
-  const int by = rest % heads_y;                         // q head (or kv head when PACK); heads of one group adjacent
-  const int bz = rest / heads_y;                         // b * nsplit + split
-  const int b = bz / p.nsplit, split = bz % p.nsplit;
-  const int hk = PACK ? by : by / G;
-  IVL_T(tr_start);
-#ifdef IVL_TRACE
-  const long long rt_start = (long long)__builtin_amdgcn_s_memrealtime();
-#endif
-  IVL_TVAR(tr_b1); IVL_TVAR(tr_st); IVL_TVAR(tr_qk); IVL_TVAR(tr_sm); IVL_TVAR(tr_pv);
+#define SWA_ROWS 0
+#include "swa_fwd_body.inc"
+#undef SWA_ROWS
+}
 
-  const long long pos = pos_dev ? *pos_dev : p.pos;
-  const int n_ring = p.C > 0 ? (int)(pos < (long long)p.C ? pos : (long long)p.C) : 0;
-  const int n_extra = p.T_new - p.T;
-  const int n_prev = n_ring + n_extra;
-  const int S = n_prev + p.T;
-  const int s0 = p.C > 0 ? mod_pos(pos - n_ring, p.C) : 0;      // ring slot of call-local key 0
-
-  // ---- rows of this workgroup / wave / lane ----------------------------------------------------
-  const int total_rows = PACK ? p.T * G : p.T;
-  const int tile_row0 = bx * QT;
-  int t_row[QG], hq[QG], hi[QG], lo[QG];
-  bool row_ok[QG];
-#pragma unroll
-  for (int qg = 0; qg < QG; ++qg) {
-    const int row = tile_row0 + (wave * QG + qg) * 16 + l15;
-    row_ok[qg] = row < total_rows;
-    t_row[qg] = PACK ? row / G : row;
-    hq[qg] = PACK ? hk * G + row % G : by;
-    hi[qg] = n_prev + t_row[qg];
-    lo[qg] = p.W > 0 ? max(0, n_prev + t_row[qg] - p.W + 1) : 0;
-  }
-
-  // band extremes over the rows of THIS wave (rows are consecutive; lo/hi are monotone in the row index)
-  int w_lo_max, w_hi_min;
-  {
-    const int wr0 = tile_row0 + wave * 16 * QG;
-    const int wr1 = min(wr0 + 16 * QG - 1, total_rows - 1);
-    const int t_first = PACK ? wr0 / G : wr0;
-    const int t_last = PACK ? max(wr1, wr0) / G : max(wr1, wr0);
-    w_hi_min = n_prev + t_first;
-    w_lo_max = p.W > 0 ? max(0, n_prev + t_last - p.W + 1) : 0;
-  }
-
-  // workgroup key-tile range
-  const int last_row = min(tile_row0 + QT, total_rows) - 1;
-  const int t_min = PACK ? tile_row0 / G : tile_row0;
-  const int t_max = PACK ? last_row / G : last_row;
-  const int lo_min = p.W > 0 ? max(0, n_prev + t_min - p.W + 1) : 0;
-  const int kt0 = lo_min / SWA_KT, kt1 = (n_prev + t_max) / SWA_KT + 1;
-  const int per = (kt1 - kt0 + p.nsplit - 1) / p.nsplit;
-  const int kt_begin = kt0 + split * per;
-  const int kt_end = min(kt1, kt_begin + per);
-
-  // ---- Q fragments (B operand of S^T = K Q^T): lane = query row, k-slots 8g..8g+7 of each 32-chunk ----
-  u32x4 qf[QG][4];
-#pragma unroll
-  for (int qg = 0; qg < QG; ++qg) {
-    const bf16_t* qp = p.q + (long long)b * p.q_sb + (long long)t_row[qg] * p.q_st + (long long)hq[qg] * p.q_sh;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      if (row_ok[qg]) qf[qg][ks] = *(const u32x4*)(qp + 32 * ks + 8 * g);
-      else qf[qg][ks] = u32x4{0u, 0u, 0u, 0u};
-    }
-  }
-
-  const long long rplane = (long long)p.B * p.T * SWA_D;
-  if (p.rcos != nullptr) {
-#pragma unroll
-    for (int qg = 0; qg < QG; ++qg) {
-      const long long row_off = ((long long)b * p.T + min(t_row[qg], p.T - 1)) * SWA_D;
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) rope_pair(qf[qg][ks], qf[qg][ks + 2], p.rcos, p.rsin, rplane, row_off, 32 * ks + 8 * g, p.rs0, p.rs1);
-    }
-  }
-  float m_run[QG], l_run[QG];
-  f32x4 oacc[QG][8];
-#pragma unroll
-  for (int qg = 0; qg < QG; ++qg) {
-    m_run[qg] = -INFINITY;
-    l_run[qg] = 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) oacc[qg][i] = f32x4{0.f, 0.f, 0.f, 0.f};
-  }
-
-  // ---- staging: thread -> rows (tid>>4) + 16 i, 16-byte chunk tid&15 ------------------------------
-  const int srow = tid >> 4, schunk = tid & 15;
-  u32x4 kreg[4], vreg[4];
-  // per-(batch, kv-head) base pointers; rows are addressed with 32-bit element offsets from them
-  const bf16_t* kb_ring = p.C > 0 ? p.k_cache + (((long long)b * p.Hkv + hk) * p.C) * SWA_D + schunk * 8 : p.k_new;
-  const bf16_t* vb_ring = p.C > 0 ? p.v_cache + (((long long)b * p.Hkv + hk) * p.C) * SWA_D + schunk * 8 : p.v_new;
-  const bf16_t* kb_new = p.k_new + (long long)b * p.kn_sb + (long long)hk * p.kn_sh + schunk * 8;
-  const bf16_t* vb_new = p.v_new + (long long)b * p.kn_sb + (long long)hk * p.kn_sh + schunk * 8;
-  const unsigned int kn_st32 = (unsigned int)p.kn_st;
-  // the call's new keys arrive un-rotated when the rope is fused: thread (row, 16-byte chunk) fetches the partner chunk
-  // (channels +-64) and the row's cos / sin and rotates its chunk in place (only the few tiles that hold new keys pay this)
-  auto rope_new_key = [&](u32x4& kv, int jn /* index among the new keys */) {
-    const int lo_ch = (schunk & 7) * 8;                    // channel block of the "lo" half of the pair
-    const u32x4 part = *(const u32x4*)(kb_new - schunk * 8 + (unsigned int)jn * kn_st32 + (schunk ^ 8) * 8);
-    u32x4 lo = schunk < 8 ? kv : part, hi = schunk < 8 ? part : kv;
-    rope_pair(lo, hi, p.rcos, p.rsin, rplane, ((long long)b * p.T + jn) * SWA_D, lo_ch, p.rs0, p.rs1);
-    kv = schunk < 8 ? lo : hi;
-  };
-  auto load_tile = [&](int kt) {
-    const int j0 = kt * SWA_KT;
-    const int slot0 = s0 + j0;
-    if (j0 + SWA_KT <= n_ring && (slot0 + SWA_KT <= p.C || slot0 >= p.C)) {
-      // wave-uniform fast path (almost every tile of a full window): 64 consecutive ring slots, no wrap inside
-      const unsigned int off = (unsigned int)((slot0 >= p.C ? slot0 - p.C : slot0) + srow) * SWA_D;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        kreg[i] = *(const u32x4*)(kb_ring + off + 16 * i * SWA_D);
-        vreg[i] = *(const u32x4*)(vb_ring + off + 16 * i * SWA_D);
-      }
-      return;
-    }
-    if (j0 >= n_ring && j0 + SWA_KT <= S) {
-      // wave-uniform fast path: 64 keys of this call
-      const unsigned int off = (unsigned int)(j0 - n_ring + srow) * kn_st32;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        kreg[i] = *(const u32x4*)(kb_new + off + 16 * i * kn_st32);
-        vreg[i] = *(const u32x4*)(vb_new + off + 16 * i * kn_st32);
-      }
-      if (p.rcos != nullptr) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) rope_new_key(kreg[i], j0 - n_ring + srow + 16 * i);
-      }
-      return;
-    }
-    // generic tile (ring wrap, ring/new seam or tail).  Branch-free per row: every row issues its two 16-byte
-    // loads (clamped address); a conditional load per row would serialise one memory round trip per row.
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int j = j0 + srow + 16 * i;
-      const int jc = min(j, S - 1);
-      const bool in_ring = jc < n_ring;
-      int slot = s0 + jc;
-      slot = slot >= p.C ? slot - p.C : slot;
-      const unsigned int off = in_ring ? (unsigned int)slot * SWA_D : (unsigned int)(jc - n_ring) * kn_st32;
-      const bf16_t* kp = (in_ring ? kb_ring : kb_new) + off;
-      const bf16_t* vp = (in_ring ? vb_ring : vb_new) + off;
-      kreg[i] = *(const u32x4*)kp;
-      vreg[i] = *(const u32x4*)vp;
-      if (p.rcos != nullptr && !in_ring) rope_new_key(kreg[i], jc - n_ring);
-    }
-    if (j0 + SWA_KT > S) {          // wave-uniform: tail tile, rows >= S are zeroed
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        if (j0 + srow + 16 * i >= S) {
-          kreg[i] = u32x4{0u, 0u, 0u, 0u};
-          vreg[i] = u32x4{0u, 0u, 0u, 0u};
-        }
-    }
-  };
-  auto store_tile = [&]() {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int r = srow + 16 * i;
-      *(u32x4*)(smem + r * SWA_KSTRIDE + ((schunk ^ (r & 15)) << 4)) = kreg[i];
-      *(u32x4*)(smem + SWA_LDS_K + r * SWA_VSTRIDE + schunk * 16) = vreg[i];
-    }
-  };
-
-  if (kt_begin < kt_end) load_tile(kt_begin);
-  const float sc = p.scaling * LOG2E;
-  IVL_T(tr_loop);
-
-  for (int kt = kt_begin; kt < kt_end; ++kt) {
-    IVL_T(tr0);
-    __syncthreads();
-    IVL_T(tr1);
-    store_tile();
-    __syncthreads();
-    IVL_T(tr2);
-
-    // ---- S^T = K Q^T : 4 key sub-tiles x 4 d-steps; d-step outermost so that consecutive MFMAs go to
-    //      independent accumulators (no back-to-back dependent issue) -------------------------------------
-    f32x4 sacc[QG][4];
-#pragma unroll
-    for (int qg = 0; qg < QG; ++qg)
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt) sacc[qg][mt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt) {
-        // piece' = piece ^ (row & 15): ds_read_b128 is serviced in the lane groups {0-3,12-15,20-27}, {4-11,16-19,28-31},
-        // ... (MI355X_MICROARCH.md, LDS); a padded 272-byte stride puts two lanes of every group on the same banks
-        // (SQ_LDS_BANK_CONFLICT = 25 % of the LDS cycles), the XOR image is conflict-free for this fragment shape
-        const u32x4 kf = *(const u32x4*)(smem + (16 * mt + l15) * SWA_KSTRIDE + (((4 * ks + g) ^ l15) << 4));
-#pragma unroll
-        for (int qg = 0; qg < QG; ++qg)
-          sacc[qg][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_mfma(kf), as_mfma(qf[qg][ks]), sacc[qg][mt], 0, 0, 0);
-      }
-    }
-    // next tile's global loads are issued behind the first MFMA batch (their address arithmetic no longer
-    // delays it); they have the softmax + PV phases to land before store_tile of the next iteration
-    if (kt + 1 < kt_end) load_tile(kt + 1);
-    IVL_T(tr3);
-    // ---- band mask + online softmax (lane-local rows) -----------------------------------------
-    // Interior tiles (every key visible to every row of this wave) skip the per-element band test.
-    const int jbase = kt * SWA_KT + 4 * g;
-    const bool interior = kt * SWA_KT >= w_lo_max && kt * SWA_KT + SWA_KT - 1 <= w_hi_min;
-    u32x4 pf[QG][2];
-#pragma unroll
-    for (int qg = 0; qg < QG; ++qg) {
-      // scores stay raw; the softmax scale is folded into the exponent: p = 2^(s*sc - m), m tracked in scaled units
-      if (!interior) {
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int j = jbase + 16 * mt + r;
-            const bool vis = row_ok[qg] && j >= lo[qg] && j <= hi[qg];
-            sacc[qg][mt][r] = vis ? sacc[qg][mt][r] : -INFINITY;
-          }
-      }
-      // the FIRST reader of the MFMA results must be an instruction the compiler sees: its hazard recognizer inserts the
-      // wait states between an MFMA and a dependent VALU read, but does not look inside inline asm (on an interior tile
-      // the asm v_max3 would otherwise follow the last MFMA directly and read the accumulators too early)
-      float rmax = vmax2(__builtin_fmaxf(sacc[qg][0][0], sacc[qg][0][1]), sacc[qg][0][2]);
-      rmax = vmax3(rmax, sacc[qg][0][3], sacc[qg][1][0]);
-      rmax = vmax3(rmax, sacc[qg][1][1], sacc[qg][1][2]);
-      rmax = vmax3(rmax, sacc[qg][1][3], sacc[qg][2][0]);
-      rmax = vmax3(rmax, sacc[qg][2][1], sacc[qg][2][2]);
-      rmax = vmax3(rmax, sacc[qg][2][3], sacc[qg][3][0]);
-      rmax = vmax3(rmax, sacc[qg][3][1], sacc[qg][3][2]);
-      rmax = vmax2(rmax, sacc[qg][3][3]);
-      rmax = group_max(rmax) * sc;                             // sc > 0: max commutes with the scale
-      const float m_new = vmax2(m_run[qg], rmax);
-      const float m_use = m_new == -INFINITY ? 0.f : m_new;
-      float rsum = 0.f;
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float pv = __builtin_amdgcn_exp2f(__builtin_fmaf(sacc[qg][mt][r], sc, -m_use));   // argument <= 0
-          sacc[qg][mt][r] = pv;
-          rsum += pv;
-        }
-      rsum = group_sum(rsum);
-      if (__any(m_new > m_run[qg])) {                        // some row's running max moved: rescale (exact)
-        const float alpha = __builtin_amdgcn_exp2f(m_run[qg] - m_use);      // m_run = -inf -> 0
-        l_run[qg] = l_run[qg] * alpha + rsum;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) oacc[qg][i] *= alpha;
-      } else {
-        l_run[qg] += rsum;
-      }
-      m_run[qg] = m_new;
-      // P^T fragments (B operand): slots 8g+e <-> keys 32ks2+4g+e | 32ks2+16+4g+(e-4)
-#pragma unroll
-      for (int ks2 = 0; ks2 < 2; ++ks2) {
-        pf[qg][ks2].x = pack2bf(sacc[qg][2 * ks2][0], sacc[qg][2 * ks2][1]);
-        pf[qg][ks2].y = pack2bf(sacc[qg][2 * ks2][2], sacc[qg][2 * ks2][3]);
-        pf[qg][ks2].z = pack2bf(sacc[qg][2 * ks2 + 1][0], sacc[qg][2 * ks2 + 1][1]);
-        pf[qg][ks2].w = pack2bf(sacc[qg][2 * ks2 + 1][2], sacc[qg][2 * ks2 + 1][3]);
-      }
-    }
-    IVL_T(tr4);
-    // ---- O^T += V^T P^T : 8 d sub-tiles x 2 key-steps ------------------------------------------
-    const unsigned char* vbase = smem + SWA_LDS_K;
-#pragma unroll
-    for (int mt2 = 0; mt2 < 8; ++mt2) {
-#pragma unroll
-      for (int ks2 = 0; ks2 < 2; ++ks2) {
-        // 16-lane group g reads the 4x16 block rows (32ks2 [+16] + 4g .. +3), cols 16mt2..+15;
-        // lane i supplies the address of row (i>>2), cols 4(i&3)..+3 and receives column i.
-        const int r0 = 32 * ks2 + 4 * g + (l15 >> 2);
-        const int cb = (16 * mt2 + 4 * (l15 & 3)) * 2;
-        typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-        const s16x4 a0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(vbase + r0 * SWA_VSTRIDE + cb));
-        const s16x4 a1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(vbase + (r0 + 16) * SWA_VSTRIDE + cb));
-        u32x2 w0, w1;
-        __builtin_memcpy(&w0, &a0, 8);
-        __builtin_memcpy(&w1, &a1, 8);
-        const u32x4 vf = u32x4{w0.x, w0.y, w1.x, w1.y};
-#pragma unroll
-        for (int qg = 0; qg < QG; ++qg)
-          oacc[qg][mt2] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_mfma(vf), as_mfma(pf[qg][ks2]), oacc[qg][mt2], 0, 0, 0);
-      }
-    }
-    IVL_T(tr5);
-    IVL_TACC(tr_b1, tr1, tr0); IVL_TACC(tr_st, tr2, tr1); IVL_TACC(tr_qk, tr3, tr2); IVL_TACC(tr_sm, tr4, tr3); IVL_TACC(tr_pv, tr5, tr4);
-  }
-  IVL_T(tr_end);
-
-  // ---- epilogue: lane owns its rows, d = 16 mt2 + 4g + r ----------------------------------------
-#pragma unroll
-  for (int qg = 0; qg < QG; ++qg) {
-    if (!row_ok[qg]) continue;
-    if (p.nsplit == 1) {
-      const float inv = l_run[qg] > 0.f ? 1.0f / l_run[qg] : 0.f;
-      bf16_t* op = p.o + (((long long)b * p.T + t_row[qg]) * p.Hq + hq[qg]) * SWA_D + 4 * g;
-#pragma unroll
-      for (int mt2 = 0; mt2 < 8; ++mt2) {
-        u32x2 w;
-        w.x = pack2bf(oacc[qg][mt2][0] * inv, oacc[qg][mt2][1] * inv);
-        w.y = pack2bf(oacc[qg][mt2][2] * inv, oacc[qg][mt2][3] * inv);
-        *(u32x2*)(op + 16 * mt2) = w;
-      }
-    } else {
-      const long long prow = (((long long)b * p.nsplit + split) * p.T + t_row[qg]) * p.Hq + hq[qg];
-      float* po = p.part_o + prow * SWA_D + 4 * g;
-#pragma unroll
-      for (int mt2 = 0; mt2 < 8; ++mt2) *(f32x4*)(po + 16 * mt2) = oacc[qg][mt2];
-      if (g == 0) {
-        p.part_ml[prow * 2] = m_run[qg];
-        p.part_ml[prow * 2 + 1] = l_run[qg];
-      }
-    }
-  }
-  IVL_T(tr_fin);
-  IVL_TOUT(32, tr_loop - tr_start); IVL_TOUT(33, tr_b1); IVL_TOUT(34, tr_st); IVL_TOUT(35, tr_qk); IVL_TOUT(36, tr_sm);
-#ifdef IVL_TRACE
-  IVL_TOUT(41, (long long)__builtin_amdgcn_s_memrealtime() - rt_start);
-#endif
-  IVL_TOUT(37, tr_pv); IVL_TOUT(38, tr_fin - tr_end); IVL_TOUT(39, tr_fin - tr_start); IVL_TOUT(40, kt_end - kt_begin);
+// packed decode step with one ring position per batch row (pos_rows: int64[B], ivl_swa_decode_rows_fwd)
+__global__ __launch_bounds__(256, 2) void swa_rows_decode_kernel(const long long* pos_dev, SwaParams p) {
+  constexpr bool PACK = true;
+  constexpr int QG = 1;
+#define SWA_ROWS 1
+#include "swa_fwd_body.inc"
+#undef SWA_ROWS
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -1114,18 +780,21 @@ struct AppendArgs {
   int first_block;          // index of the first append block in the grid; < 0: no append
 };
 // token t of the call -> slot (pos + t) % C ; only the last min(T, C) tokens are written
+// ROWS (ivl_swa_decode_rows_fwd): a.pos_dev is an int64[B], batch row b appends at its own pos_dev[b]
+template <bool ROWS = false>
 __device__ __forceinline__ void ring_append(const AppendArgs& a, long long block, long long nblocks) {
-  const long long pos = a.pos_dev ? *a.pos_dev : a.pos;
+  const long long pos = ROWS ? 0 : (a.pos_dev ? *a.pos_dev : a.pos);
   const int t_first = a.T > a.C ? a.T - a.C : 0;
   const int nt = a.T - t_first;
   const long long total = (long long)a.B * nt * a.Hkv * (SWA_D / 8);
-  const int pos_slot = mod_pos(pos, a.C);
+  const int pos_slot0 = mod_pos(pos, a.C);
   for (long long idx = block * blockDim.x + threadIdx.x; idx < total; idx += nblocks * blockDim.x) {
     const int ch = (int)(idx & (SWA_D / 8 - 1));
     int hk, tt;
     const long long bt = divmod_idx(idx >> 4, a.Hkv, hk);          // SWA_D / 8 = 16 pieces per row
     const int b = (int)divmod_idx(bt, nt, tt);
     tt += t_first;
+    const int pos_slot = ROWS ? mod_pos(a.pos_dev[b], a.C) : pos_slot0;
     const int slot = (int)(((unsigned int)pos_slot + (unsigned int)tt) % (unsigned int)a.C);      // (pos + tt) % C; pos_slot, tt < 2^31
     const long long src = (long long)b * a.kn_sb + (long long)tt * a.kn_st + (long long)hk * a.kn_sh + ch * 8;
     const long long dst = (((long long)b * a.Hkv + hk) * a.C + slot) * SWA_D + ch * 8;
@@ -1149,48 +818,21 @@ __device__ __forceinline__ void ring_append(const AppendArgs& a, long long block
 template <int NS, bool BF16P>
 __global__ __launch_bounds__(256) void swa_combine_kernel(const float* __restrict__ part_o, const float* __restrict__ part_ml,
                                                          bf16_t* __restrict__ o, int B, int rows_per_b, int nsplit, AppendArgs ap) {
-  if (ap.first_block >= 0 && (int)blockIdx.x >= ap.first_block) {
-    ring_append(ap, (long long)blockIdx.x - ap.first_block, (long long)gridDim.x - ap.first_block);
-    return;
-  }
-  const int ncb = ap.first_block >= 0 ? ap.first_block : (int)gridDim.x;       // combine blocks
-  const int lane = threadIdx.x & 63;
-  const long long wid = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const long long nw = ((long long)ncb * blockDim.x) >> 6;
-  for (long long r = wid; r < (long long)B * rows_per_b; r += nw) {
-    int rr_;
-    const long long b = divmod_idx(r, rows_per_b, rr_), rr = rr_;
-    float ms[NS], ls[NS];
-    float2 ov[NS];
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-      const bool on = s < nsplit;
-      const long long pr = (b * nsplit + (on ? s : 0)) * rows_per_b + rr;
-      const float2 ml = *(const float2*)(part_ml + pr * 2);
-      ms[s] = on ? ml.x : -INFINITY;
-      ls[s] = on ? ml.y : 0.f;
-      if (BF16P) {
-        const unsigned int w2 = *(const unsigned int*)((const bf16_t*)part_o + pr * SWA_D + 2 * lane);
-        ov[s] = float2{bflo(w2), bfhi(w2)};
-      } else {
-        ov[s] = *(const float2*)(part_o + pr * SWA_D + 2 * lane);
-      }
-    }
-    float m = -INFINITY;
-#pragma unroll
-    for (int s = 0; s < NS; ++s) m = fmaxf(m, ms[s]);
-    float l = 0.f, a0 = 0.f, a1 = 0.f;
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-      float w = ms[s] == -INFINITY ? 0.f : exp2f(ms[s] - m);
-      if (BF16P) w *= ls[s];
-      l = BF16P ? l + w : fmaf(w, ls[s], l);
-      a0 = fmaf(w, ov[s].x, a0);
-      a1 = fmaf(w, ov[s].y, a1);
-    }
-    const float inv = l > 0.f ? 1.0f / l : 0.f;
-    *(unsigned int*)(o + r * SWA_D + 2 * lane) = pack2bf(a0 * inv, a1 * inv);
-  }
+#define SWA_WIDE 0
+#define SWA_ROWS 0
+#include "swa_combine_body.inc"
+#undef SWA_ROWS
+#undef SWA_WIDE
+}
+template <int NS>
+__global__ __launch_bounds__(256) void swa_rows_combine_kernel(const float* __restrict__ part_o, const float* __restrict__ part_ml,
+                                                              bf16_t* __restrict__ o, int B, int rows_per_b, int nsplit, AppendArgs ap) {
+  constexpr bool BF16P = false;
+#define SWA_WIDE 0
+#define SWA_ROWS 1
+#include "swa_combine_body.inc"
+#undef SWA_ROWS
+#undef SWA_WIDE
 }
 
 // merge up to 64 split-KV partials (packed decode): one wavefront per (b, t, head) row.  Lane s first owns split s
@@ -1198,49 +840,19 @@ __global__ __launch_bounds__(256) void swa_combine_kernel(const float* __restric
 // v_readlane while every lane accumulates its 2 d-values; loads are issued 8 splits at a time.
 __global__ __launch_bounds__(256) void swa_combine_wide_kernel(const float* __restrict__ part_o, const float* __restrict__ part_ml,
                                                               bf16_t* __restrict__ o, int B, int rows_per_b, int nsplit, AppendArgs ap) {
-  if (ap.first_block >= 0 && (int)blockIdx.x >= ap.first_block) {
-    ring_append(ap, (long long)blockIdx.x - ap.first_block, (long long)gridDim.x - ap.first_block);
-    return;
-  }
-  // one WORKGROUP per row: wave w merges the splits 16w .. 16w + 15 (all 16 partial rows requested at once: one memory
-  // round trip instead of nsplit / 8), the four partial sums meet in LDS
-  __shared__ float2 red[4][64];
-  const int ncb = ap.first_block >= 0 ? ap.first_block : (int)gridDim.x;       // combine blocks
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (long long r = blockIdx.x; r < (long long)B * rows_per_b; r += ncb) {
-    int rr_;
-    const long long b = divmod_idx(r, rows_per_b, rr_), rr = rr_;
-    const bool on = lane < nsplit;
-    const float2 ml = *(const float2*)(part_ml + ((b * nsplit + (on ? lane : 0)) * rows_per_b + rr) * 2);
-    float2 ov[16];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-      const int s2 = min(16 * wave + j, nsplit - 1);
-      ov[j] = *(const float2*)(part_o + ((b * nsplit + s2) * rows_per_b + rr) * SWA_D + 2 * lane);
-    }
-    const float ms = on ? ml.x : -INFINITY;
-    float m = ms;
-#pragma unroll
-    for (int ofs = 32; ofs > 0; ofs >>= 1) m = fmaxf(m, __shfl_xor(m, ofs, 64));
-    const float w = ms == -INFINITY ? 0.f : exp2f(ms - m);
-    const float l = wave_sum(w * (on ? ml.y : 0.f));
-    float a0 = 0.f, a1 = 0.f;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-      const int s2 = 16 * wave + j;
-      const float ws = s2 < nsplit ? __shfl(w, s2, 64) : 0.f;
-      a0 = fmaf(ws, ov[j].x, a0);
-      a1 = fmaf(ws, ov[j].y, a1);
-    }
-    red[wave][lane] = float2{a0, a1};
-    __syncthreads();
-    if (wave == 0) {
-      const float2 p1 = red[1][lane], p2 = red[2][lane], p3 = red[3][lane];
-      const float inv = l > 0.f ? 1.0f / l : 0.f;
-      *(unsigned int*)(o + r * SWA_D + 2 * lane) = pack2bf((a0 + p1.x + p2.x + p3.x) * inv, (a1 + p1.y + p2.y + p3.y) * inv);
-    }
-    __syncthreads();
-  }
+#define SWA_WIDE 1
+#define SWA_ROWS 0
+#include "swa_combine_body.inc"
+#undef SWA_ROWS
+#undef SWA_WIDE
+}
+__global__ __launch_bounds__(256) void swa_rows_combine_wide_kernel(const float* __restrict__ part_o, const float* __restrict__ part_ml,
+                                                                   bf16_t* __restrict__ o, int B, int rows_per_b, int nsplit, AppendArgs ap) {
+#define SWA_WIDE 1
+#define SWA_ROWS 1
+#include "swa_combine_body.inc"
+#undef SWA_ROWS
+#undef SWA_WIDE
 }
 
 // stand-alone ring append (ivl_swa_cache_append, and ivl_swa_fwd with append_new when no combine launch follows)
@@ -1267,6 +879,39 @@ static int swa_base_nsplit(int B, int T, int Hq) {
 }
 
 int swa_ring256_launch(const ivl_swa_args* a, hipStream_t st);      // swa_ring256.hip
+
+// worst-case number of key tiles a workgroup walks (n_prev unknown under graph replay -> capacity)
+static int swa_max_tiles(const ivl_swa_args* a) {
+  const long long max_prev = (long long)a->cache_capacity + (a->T_new - a->T);
+  long long span = a->window > 0 ? (long long)a->window + 2 * SWA_QT : max_prev + a->T;
+  if (span > max_prev + a->T) span = max_prev + a->T;
+  return (int)(span / SWA_KT) + 2;
+}
+
+static SwaParams swa_params(const ivl_swa_args* a, int nsplit) {
+  SwaParams p;
+  p.q = (const bf16_t*)a->q; p.k_new = (const bf16_t*)a->k_new; p.v_new = (const bf16_t*)a->v_new;
+  p.k_cache = (const bf16_t*)a->k_cache; p.v_cache = (const bf16_t*)a->v_cache; p.o = (bf16_t*)a->o;
+  p.q_sb = a->q_sb; p.q_st = a->q_st; p.q_sh = a->q_sh; p.kn_sb = a->kn_sb; p.kn_st = a->kn_st; p.kn_sh = a->kn_sh;
+  p.vn_sb = a->kn_sb; p.vn_st = a->kn_st; p.vn_sh = a->kn_sh;
+  p.B = a->B; p.T = a->T; p.T_new = a->T_new; p.Hq = a->Hq; p.Hkv = a->Hkv; p.C = a->cache_capacity; p.W = a->window;
+  p.nsplit = nsplit; p.pos = a->pos; p.pos_dev = (const long long*)a->pos_dev; p.scaling = a->scaling;
+  p.part_o = nullptr; p.part_ml = nullptr;
+  p.rcos = (const bf16_t*)a->rope_cos; p.rsin = (const bf16_t*)a->rope_sin; p.rs0 = a->rope_s0; p.rs1 = a->rope_s1;
+  return p;
+}
+
+// the ring append of a call (ivl_swa_args.append_new) with the (possibly rotated-copy) keys of p; returns its block count
+static int swa_append_args(const ivl_swa_args* a, const SwaParams& p, AppendArgs& ap) {
+  ap.k_new = p.k_new; ap.v_new = p.v_new; ap.kn_sb = p.kn_sb; ap.kn_st = p.kn_st; ap.kn_sh = p.kn_sh;
+  ap.vn_sb = p.vn_sb; ap.vn_st = p.vn_st; ap.vn_sh = p.vn_sh;
+  ap.k_cache = (bf16_t*)a->k_cache; ap.v_cache = (bf16_t*)a->v_cache;
+  ap.B = a->B; ap.T = a->T; ap.Hkv = a->Hkv; ap.C = a->cache_capacity; ap.pos = a->pos; ap.pos_dev = p.pos_dev;
+  ap.rcos = p.rcos; ap.rsin = p.rsin; ap.rs0 = p.rs0; ap.rs1 = p.rs1;
+  const int nt = a->T > a->cache_capacity ? a->cache_capacity : a->T;
+  long long ab = ((long long)a->B * nt * a->Hkv * (SWA_D / 8) + 255) / 256;
+  return (int)(ab > 2048 ? 2048 : ab);
+}
 
 }  // namespace ivl
 
@@ -1316,11 +961,7 @@ extern "C" int ivl_swa_fwd(const ivl_swa_args* a, void* stream) {
   }
   const int G = a->Hq / a->Hkv;
   const bool pack = (long long)a->T * G <= SWA_QT && G <= 16;
-  // worst-case number of key tiles a workgroup walks (n_prev unknown under graph replay -> capacity)
-  const long long max_prev = (long long)a->cache_capacity + (a->T_new - a->T);
-  long long span = a->window > 0 ? (long long)a->window + 2 * SWA_QT : max_prev + a->T;
-  if (span > max_prev + a->T) span = max_prev + a->T;
-  const int max_tiles = (int)(span / SWA_KT) + 2;
+  const int max_tiles = swa_max_tiles(a);
   int nsplit = 1;
   if (pack) {
     nsplit = max_tiles;                    // decode: one key tile per workgroup (the K/V read is the whole cost)
@@ -1332,15 +973,7 @@ extern "C" int ivl_swa_fwd(const ivl_swa_args* a, void* stream) {
   }
   if (nsplit < 1) nsplit = 1;
 
-  SwaParams p;
-  p.q = (const bf16_t*)a->q; p.k_new = (const bf16_t*)a->k_new; p.v_new = (const bf16_t*)a->v_new;
-  p.k_cache = (const bf16_t*)a->k_cache; p.v_cache = (const bf16_t*)a->v_cache; p.o = (bf16_t*)a->o;
-  p.q_sb = a->q_sb; p.q_st = a->q_st; p.q_sh = a->q_sh; p.kn_sb = a->kn_sb; p.kn_st = a->kn_st; p.kn_sh = a->kn_sh;
-  p.vn_sb = a->kn_sb; p.vn_st = a->kn_st; p.vn_sh = a->kn_sh;
-  p.B = a->B; p.T = a->T; p.T_new = a->T_new; p.Hq = a->Hq; p.Hkv = a->Hkv; p.C = a->cache_capacity; p.W = a->window;
-  p.nsplit = nsplit; p.pos = a->pos; p.pos_dev = (const long long*)a->pos_dev; p.scaling = a->scaling;
-  p.part_o = nullptr; p.part_ml = nullptr;
-  p.rcos = (const bf16_t*)a->rope_cos; p.rsin = (const bf16_t*)a->rope_sin; p.rs0 = a->rope_s0; p.rs1 = a->rope_s1;
+  SwaParams p = swa_params(a, nsplit);
   if (nsplit > 1) {
     const size_t n_o = (size_t)a->B * nsplit * a->T * a->Hq * SWA_D;
     const size_t need = (n_o + (size_t)a->B * nsplit * a->T * a->Hq * 2) * sizeof(float);
@@ -1394,16 +1027,7 @@ extern "C" int ivl_swa_fwd(const ivl_swa_args* a, void* stream) {
   AppendArgs ap;
   ap.first_block = -1;
   int append_blocks = 0;
-  if (a->append_new) {
-    ap.k_new = p.k_new; ap.v_new = p.v_new; ap.kn_sb = p.kn_sb; ap.kn_st = p.kn_st; ap.kn_sh = p.kn_sh;
-    ap.vn_sb = p.vn_sb; ap.vn_st = p.vn_st; ap.vn_sh = p.vn_sh;
-    ap.k_cache = (bf16_t*)a->k_cache; ap.v_cache = (bf16_t*)a->v_cache;
-    ap.B = a->B; ap.T = a->T; ap.Hkv = a->Hkv; ap.C = a->cache_capacity; ap.pos = a->pos; ap.pos_dev = p.pos_dev;
-    ap.rcos = p.rcos; ap.rsin = p.rsin; ap.rs0 = p.rs0; ap.rs1 = p.rs1;
-    const int nt = a->T > a->cache_capacity ? a->cache_capacity : a->T;
-    long long ab = ((long long)a->B * nt * a->Hkv * (SWA_D / 8) + 255) / 256;
-    append_blocks = (int)(ab > 2048 ? 2048 : ab);
-  }
+  if (a->append_new) append_blocks = swa_append_args(a, p, ap);
   if (nsplit > 1) {
     const long long nrows = (long long)a->B * a->T * a->Hq;
     long long gb = (nrows * 64 + 255) / 256;
@@ -1429,6 +1053,69 @@ extern "C" int ivl_swa_fwd(const ivl_swa_args* a, void* stream) {
     rc = check_launch("ivl_swa_fwd(append)");
   }
   return rc;
+}
+
+extern "C" int ivl_swa_decode_rows_fwd(const ivl_swa_args* a, const int64_t* pos_rows, void* stream) {
+  IVL_REQUIRE(a != nullptr, IVL_ERR_INVALID_ARG, "ivl_swa_decode_rows_fwd: NULL args");
+  IVL_REQUIRE(pos_rows != nullptr, IVL_ERR_INVALID_ARG, "ivl_swa_decode_rows_fwd: NULL pos_rows");
+  IVL_REQUIRE(a->q && a->k_new && a->v_new && a->o, IVL_ERR_INVALID_ARG, "ivl_swa_decode_rows_fwd: NULL q/k_new/v_new/o");
+  IVL_REQUIRE(a->B > 0 && a->T > 0 && a->Hq > 0 && a->Hkv > 0, IVL_ERR_INVALID_ARG,
+              "ivl_swa_decode_rows_fwd: bad sizes B=%d T=%d Hq=%d Hkv=%d", a->B, a->T, a->Hq, a->Hkv);
+  IVL_REQUIRE(a->d == SWA_D, IVL_ERR_UNSUPPORTED, "ivl_swa_decode_rows_fwd: head_dim %d unsupported (built for 128)", a->d);
+  IVL_REQUIRE(a->Hq % a->Hkv == 0, IVL_ERR_INVALID_ARG, "ivl_swa_decode_rows_fwd: Hq=%d not a multiple of Hkv=%d", a->Hq, a->Hkv);
+  IVL_REQUIRE(a->cache_capacity > 0 && a->k_cache && a->v_cache, IVL_ERR_UNSUPPORTED,
+              "ivl_swa_decode_rows_fwd: needs a ring cache (cache_capacity=%d)", a->cache_capacity);
+  IVL_REQUIRE(a->T_new == a->T, IVL_ERR_UNSUPPORTED, "ivl_swa_decode_rows_fwd: needs T_new == T (got %d, %d)", a->T_new, a->T);
+  const int G = a->Hq / a->Hkv;
+  IVL_REQUIRE((long long)a->T * G <= SWA_QT && G <= 16, IVL_ERR_UNSUPPORTED,
+              "ivl_swa_decode_rows_fwd: packed decode rows only: T * Hq/Hkv = %lld > %d", (long long)a->T * G, SWA_QT);
+  IVL_REQUIRE(a->mma_dtype == IVL_BF16, IVL_ERR_UNSUPPORTED, "ivl_swa_decode_rows_fwd: mma_dtype must be IVL_BF16 (got %d)",
+              a->mma_dtype);
+  IVL_REQUIRE((a->rope_cos == nullptr) == (a->rope_sin == nullptr), IVL_ERR_INVALID_ARG,
+              "ivl_swa_decode_rows_fwd: rope_cos and rope_sin go together");
+  IVL_REQUIRE(a->rope_cos == nullptr || (a->rope_s0 % 8 == 0 && a->rope_s1 % 8 == 0 && a->rope_s0 >= 0 && a->rope_s1 >= 0 &&
+                                          a->rope_s0 + a->rope_s1 <= 64),
+              IVL_ERR_UNSUPPORTED, "ivl_swa_decode_rows_fwd: mrope sections must be multiples of 8 (got %d, %d)", a->rope_s0, a->rope_s1);
+  IVL_REQUIRE((long long)a->T_new * a->kn_st < (1LL << 32) && a->kn_st >= 0, IVL_ERR_UNSUPPORTED,
+              "ivl_swa_decode_rows_fwd: T_new * kn_st = %lld elements exceeds the 32-bit row addressing of the kernel",
+              (long long)a->T_new * a->kn_st);
+  // the same split count as ivl_swa_fwd's packed decode step (capacity and window only): row b of this call and a B = 1
+  // ivl_swa_fwd at pos = pos_rows[b] run the same workgroups and the same combine, bit for bit
+  int nsplit = swa_max_tiles(a);
+  if (nsplit > SWA_MAX_SPLIT_PACK) nsplit = SWA_MAX_SPLIT_PACK;
+  IVL_REQUIRE(nsplit > 1, IVL_ERR_UNSUPPORTED, "ivl_swa_decode_rows_fwd: single-split shape (window %d)", a->window);
+  SwaParams p = swa_params(a, nsplit);
+  p.pos = 0; p.pos_dev = (const long long*)pos_rows;
+  const size_t n_o = (size_t)a->B * nsplit * a->T * a->Hq * SWA_D;
+  const size_t need = (n_o + (size_t)a->B * nsplit * a->T * a->Hq * 2) * sizeof(float);
+  IVL_REQUIRE(a->workspace != nullptr && a->workspace_bytes >= need, IVL_ERR_WORKSPACE,
+              "ivl_swa_decode_rows_fwd: workspace %zu bytes < required %zu (nsplit=%d)", a->workspace_bytes, need, nsplit);
+  p.part_o = (float*)a->workspace;
+  p.part_ml = p.part_o + n_o;
+  p.n_qtiles = 1;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(swa_rows_decode_kernel, dim3(a->Hkv * a->B * nsplit), dim3(256), 0, st, p.pos_dev, p);
+  int rc = check_launch("ivl_swa_decode_rows_fwd");
+  if (rc != IVL_OK) return rc;
+  AppendArgs ap;
+  ap.first_block = -1;
+  const int append_blocks = a->append_new ? swa_append_args(a, p, ap) : 0;
+  const long long nrows = (long long)a->B * a->T * a->Hq;
+  if (nsplit > 16) {
+    const long long wb = nrows > 4096 ? 4096 : nrows;             // one workgroup per row
+    if (append_blocks > 0) ap.first_block = (int)wb;
+    hipLaunchKernelGGL(swa_rows_combine_wide_kernel, dim3((int)wb + append_blocks), dim3(256), 0, st, p.part_o, p.part_ml, p.o, a->B,
+                       a->T * a->Hq, nsplit, ap);
+  } else {
+    long long gb = (nrows * 64 + 255) / 256;
+    if (gb > 4096) gb = 4096;
+    if (append_blocks > 0) ap.first_block = (int)gb;
+    const dim3 cg((int)gb + append_blocks);
+    if (nsplit <= 4) hipLaunchKernelGGL((swa_rows_combine_kernel<4>), cg, dim3(256), 0, st, p.part_o, p.part_ml, p.o, a->B, a->T * a->Hq, nsplit, ap);
+    else if (nsplit <= 8) hipLaunchKernelGGL((swa_rows_combine_kernel<8>), cg, dim3(256), 0, st, p.part_o, p.part_ml, p.o, a->B, a->T * a->Hq, nsplit, ap);
+    else hipLaunchKernelGGL((swa_rows_combine_kernel<16>), cg, dim3(256), 0, st, p.part_o, p.part_ml, p.o, a->B, a->T * a->Hq, nsplit, ap);
+  }
+  return check_launch("ivl_swa_decode_rows_fwd(combine)");
 }
 
 extern "C" int ivl_swa_cache_append(const void* k_new, const void* v_new, int64_t kn_sb, int64_t kn_st, int64_t kn_sh,

@@ -18,7 +18,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
-from .cache import StaticCachePrealloc
+from .cache import MultiStreamCache, StaticCachePrealloc
 
 import os as _os
 
@@ -437,6 +437,89 @@ class GraphedDecode:
         if self.graph is None:
             self.capture()
         self.cache.ensure_started()
+        self.graph.replay()
+        self.cache.advance(1)
+        return self.token
+
+
+class GraphedMultiStreamDecode:
+    """Greedy decode of independent streams in the slots of a MultiStreamCache: ONE captured graph advances every slot by
+    one token (embed -> stack -> argmax -> token buffer, per-slot positions +1).  Streams join with admit() (the prompt runs
+    eagerly on the slot's B = 1 view) and leave with release(), both between replays and without a recapture."""
+
+    PREFILL_CHUNK = 4096
+
+    def __init__(self, model: InfiniteVLTextStack, cache: MultiStreamCache, warmup: int = 2):
+        if any(getattr(l.self_attn, "mma_dtype", None) is not None for l in model.layers):
+            raise ValueError("GraphedMultiStreamDecode: the fp8 decode step is not supported (bf16 only)")
+        p_ = next(model.parameters())
+        self.model, self.cache, self.S = model, cache, cache.n_slots
+        self.token = torch.zeros(self.S, 1, dtype=torch.int64, device=p_.device)
+        self.position_ids = torch.zeros(3, self.S, 1, dtype=torch.int64, device=p_.device)
+        self.logits = None
+        self.graph: Optional[torch.cuda.CUDAGraph] = None
+        self._warmup = warmup
+
+    def _run(self):
+        _, lg = self.model(input_ids=self.token, position_ids=self.position_ids, past_key_values=self.cache,
+                           logits_to_keep=1)
+        self.token.copy_(lg[:, -1].argmax(-1, keepdim=True))
+        self.position_ids.add_(1)
+        return lg
+
+    def capture(self) -> None:
+        """Warm up and capture; every slot's ring, state, position and token are restored afterwards."""
+        saved, saved_pos, saved_tok = self.cache.clone(), self.position_ids.clone(), self.token.clone()
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s), torch.no_grad():
+            for _ in range(self._warmup):
+                self._run()
+        torch.cuda.current_stream().wait_stream(s)
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.no_grad(), torch.cuda.graph(self.graph):
+            self.logits = self._run()
+        self.cache.copy_from(saved)
+        self.position_ids.copy_(saved_pos)
+        self.token.copy_(saved_tok)
+
+    @torch.no_grad()
+    def admit(self, slot: int, inputs_embeds: torch.Tensor, position_ids: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Start a stream in `slot` with a prompt inputs_embeds [1,T,hidden] (M-RoPE position_ids [3,1,T]; default: text
+        positions 0..T-1).  Its first generated token is written to token[slot] and returned."""
+        if inputs_embeds.dim() != 3 or inputs_embeds.shape[0] != 1:
+            raise ValueError(f"admit: inputs_embeds must be [1,T,hidden]; got {tuple(inputs_embeds.shape)}")
+        T = inputs_embeds.shape[1]
+        if position_ids is None:
+            position_ids = torch.arange(T, device=inputs_embeds.device, dtype=torch.int64)[None, None, :].expand(3, 1, T)
+        if tuple(position_ids.shape) != (3, 1, T):
+            raise ValueError(f"admit: position_ids must be [3,1,{T}]; got {tuple(position_ids.shape)}")
+        self.cache.admit(slot)
+        view = self.cache.slot_view(slot)
+        lg = None
+        for a in range(0, T, self.PREFILL_CHUNK):
+            b = min(T, a + self.PREFILL_CHUNK)
+            _, lg = self.model(inputs_embeds=inputs_embeds[:, a:b], position_ids=position_ids[:, :, a:b],
+                               past_key_values=view, logits_to_keep=1)
+        self.token[slot].copy_(lg[0, -1].argmax(-1, keepdim=True))
+        self.position_ids[:, slot].fill_(int(position_ids.max()) + 1)        # the next M-RoPE text position
+        return self.token[slot]
+
+    def release(self, slot: int) -> None:
+        """End the stream in `slot`: its state is zeroed (the slot keeps computing on zeros until the next admit)."""
+        self.cache.release(slot)
+        self.token[slot].zero_()
+        self.position_ids[:, slot].zero_()
+
+    def step(self, graph: bool = True) -> torch.Tensor:
+        """One decode step of every slot; the new tokens are left in self.token [S,1] (device).  graph=False runs the
+        same step eagerly (the reference the captured graph is checked against)."""
+        if not graph:
+            with torch.no_grad():
+                self.logits = self._run()
+            return self.token
+        if self.graph is None:
+            self.capture()
         self.graph.replay()
         self.cache.advance(1)
         return self.token

@@ -1009,6 +1009,7 @@ def swa_forward(
     k_cache: Optional[torch.Tensor] = None, v_cache: Optional[torch.Tensor] = None,
     pos: int = 0, pos_dev: Optional[torch.Tensor] = None, n_query: Optional[int] = None,
     layout: str = "bthd", mma_dtype=None, rope=None, append: bool = False, pos_min: int = 0, pos_min_holds_in_graph: bool = False,
+    pos_rows: Optional[torch.Tensor] = None,
 ) -> torch.Tensor:
     """Sliding-window GQA attention over (ring cache ++ new keys); returns o [B,T,Hq,d] bf16.
 
@@ -1022,8 +1023,11 @@ def swa_forward(
     `pos_min`: a lower bound of the position the caller vouches for (the host-side counter of the cache) when the position
     itself is read from `pos_dev`: a long call over a FULL ring (pos_min >= C) takes the 256-row kernel on a linear copy of the
     keys (ivl_swa_args.pos_min).  Ignored while a stream capture is recording (a replay may start from an earlier position)
-    unless `pos_min_holds_in_graph` says the bound holds for every replay (the kernel micro-benchmarks replay one position)."""
-    _need_gpu(q, k_new, v_new, k_cache, v_cache, pos_dev)
+    unless `pos_min_holds_in_graph` says the bound holds for every replay (the kernel micro-benchmarks replay one position).
+    `pos_rows` (device int64 [B]): one ring position per batch row -- independent streams in the rows of one cache
+    (ivl_swa_decode_rows_fwd).  Row b attends as this call would at B = 1 with pos = pos_rows[b]; pos_rows is not advanced.
+    Packed decode steps only (ring cache, T_new == T, T * Hq/Hkv <= 64, bf16); excludes pos / pos_dev / pos_min."""
+    _need_gpu(q, k_new, v_new, k_cache, v_cache, pos_dev, pos_rows)
     if q.dtype != torch.bfloat16 or k_new.dtype != torch.bfloat16 or v_new.dtype != torch.bfloat16:
         raise ValueError("swa_forward is built for bf16")
     if layout == "bhtd":
@@ -1032,6 +1036,19 @@ def swa_forward(
     T_new, Hkv = k_new.shape[1], k_new.shape[2]
     if n_query is not None:
         assert n_query == T
+    if pos_rows is not None:
+        if pos_dev is not None or pos != 0 or pos_min != 0:
+            raise ValueError("swa_forward: pos_rows excludes pos / pos_dev / pos_min")
+        if pos_rows.dtype != torch.int64 or tuple(pos_rows.shape) != (B,) or not pos_rows.is_contiguous():
+            raise ValueError(f"swa_forward: pos_rows must be a contiguous int64 [B] = [{B}] tensor; got {pos_rows.dtype} "
+                             f"{tuple(pos_rows.shape)}")
+        if k_cache is None:
+            raise ValueError("swa_forward: pos_rows needs a ring cache (k_cache / v_cache)")
+        if T_new != T or T * (Hq // Hkv) > 64:
+            raise ValueError(f"swa_forward: pos_rows serves packed decode steps only: T_new == T and T * Hq/Hkv <= 64 "
+                             f"(got T={T}, T_new={T_new}, Hq/Hkv={Hq // Hkv})")
+        if mma_code(mma_dtype) != IVL_BF16:
+            raise ValueError("swa_forward: pos_rows runs in bf16 only (no fp8 decode step)")
     if q.stride(-1) != 1:
         q = q.contiguous()
     if k_new.stride(-1) != 1 or v_new.stride() != k_new.stride():
@@ -1045,7 +1062,7 @@ def swa_forward(
     lib = _lib.load()
     nbytes = lib.ivl_swa_workspace_bytes(B, T, Hq, d)
     pos_min = int(pos_min) if pos_dev is not None else int(pos)
-    if not (SWA_RING256 and C > 0 and pos_min >= C and T >= 256 and T_new == T and window == C + 1) or (
+    if pos_rows is not None or not (SWA_RING256 and C > 0 and pos_min >= C and T >= 256 and T_new == T and window == C + 1) or (
             torch.cuda.is_current_stream_capturing() and not pos_min_holds_in_graph):
         pos_min = 0
     else:
@@ -1074,7 +1091,10 @@ def swa_forward(
     if rope is not None:
         cos, sin, sec = _rope_args(rope, B, T, d)
         a.rope_cos, a.rope_sin, a.rope_s0, a.rope_s1 = cos.data_ptr(), sin.data_ptr(), int(sec[0]), int(sec[1])
-    _lib.check(lib.ivl_swa_fwd(ctypes.byref(a), _stream(q)))
+    if pos_rows is not None:
+        _lib.check(lib.ivl_swa_decode_rows_fwd(ctypes.byref(a), pos_rows.data_ptr(), _stream(q)))
+    else:
+        _lib.check(lib.ivl_swa_fwd(ctypes.byref(a), _stream(q)))
     return o
 
 
