@@ -396,6 +396,14 @@ IVL_API int ivl_linear_swiglu_small_m_fwd(const void* x, const void* w_gate_up, 
 IVL_API int ivl_norm_linear_small_m_fwd(const void* x, const void* residual, const void* norm_weight, float eps, void* h_out,
                                 const void* w, const void* bias, void* y, int M, int N, int K, int glu, void* stream);
 
+/* nn.Linear for the wide projections of a prefill chunk of up to 256 rows: y[M,N] = bf16(x[M,K] W[N,K]^T + bias[N]), or with
+ * glu != 0 the SwiGLU MLP head on the fused gate|up weight [2N,K] (N = I):
+ *   y[M,I] = bf16( bf16(silu(bf16(x Wg^T + bg))) * bf16(x Wu^T + bu) ),  Wg = w[:I], Wu = w[I:], bias [2I] or NULL
+ * = the glu == 0 call on the fused weight followed by ivl_silu_mul_fwd, bit for bit.  One workgroup per column range with all rows
+ * (no K split: the same bits on every run).  x, W, bias, y bf16 row-major contiguous, fp32 accumulation, one rounding.
+ * 1 <= M <= 256, K % 64 == 0 and K <= 16384, N % 4 == 0, x / W 16-byte aligned: else IVL_ERR_UNSUPPORTED / IVL_ERR_INVALID_ARG. */
+IVL_API int ivl_linear_m256_fwd(const void* x, const void* w, const void* bias, void* y, int M, int N, int K, int glu, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -30,7 +30,7 @@ EXPORTED_SYMBOLS = (
     "ivl_gdn_sync_status", "ivl_gdn_sync_reset", "ivl_gdn_resident_blocks",
     "ivl_short_conv_bias_fwd", "ivl_rmsnorm_swish_gate_res_fwd", "ivl_gdn_recurrent_f16_fwd",
     "ivl_gdn_decode_split_fwd", "ivl_gdn_out_linear_small_m_fwd", "ivl_swa_ring256_workspace_bytes",
-    "ivl_swa_decode_rows_fwd",
+    "ivl_swa_decode_rows_fwd", "ivl_linear_m256_fwd",
 )
 
 
@@ -153,6 +153,8 @@ def load(path: str = None) -> ctypes.CDLL:
     lib.ivl_linear_swiglu_small_m_fwd.argtypes = [vp, vp, vp, vp, i, i, i, vp]
     lib.ivl_norm_linear_small_m_fwd.restype = i
     lib.ivl_norm_linear_small_m_fwd.argtypes = [vp, vp, vp, f, vp, vp, vp, vp, i, i, i, i, vp]
+    lib.ivl_linear_m256_fwd.restype = i
+    lib.ivl_linear_m256_fwd.argtypes = [vp, vp, vp, vp, i, i, i, i, vp]
     _lib = lib
     # the one environment switch, on the Python side: IVL_GDN_RESIDENT_BLOCKS=0 forces the two-launch form of the fused GDN call
     env = os.environ.get("IVL_GDN_RESIDENT_BLOCKS", "")

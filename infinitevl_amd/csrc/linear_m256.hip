@@ -1,0 +1,251 @@
+// y[M,N] = x[M,K] W[N,K]^T (+ bias), bf16 in / fp32 accumulate / bf16 out, for M <= 256 rows: the wide projections of a
+// 256-token prefill chunk.  The package dispatches the GLU form -- the fused MLP gate|up with the SwiGLU gate in the epilogue,
+// 32.5 us against 39.7 for library GEMM + silu_mul at 256 x 22016 x 2048 (tools/ab_linear_m256.py, same box).  The plain
+// form on the GDN in-projection (256 x 12320 x 2048) loses to the library (22.6 against 20.7 us) and is not dispatched.
+//
+// Decomposition: ONE workgroup per column range with ALL (up to 256) rows -- no K split, no reduction across workgroups, no
+// workspace, no inter-workgroup signalling; the same bits on every run.  The column range is chosen so that the grid is one
+// wave of workgroups over the 256 CUs: the plain form takes 64 weight rows (N = 12320: 193 workgroups), the GLU form 48 output
+// columns = 48 gate rows + the 48 matching up rows (I = 11008: 230 workgroups; the fused [2I, K] weight is not re-packed).
+//
+// Every workgroup re-reads all of x (1 MB at K = 2048, served by L2) beside its own 0.39 MB of weights.  Both operands are
+// k-contiguous and are staged the same way: per K-tile of 64, 1 KB LDS-DMA pieces (global_load_lds_dwordx4: 8 rows x one full
+// 128-byte line, no VGPR round trip) into a [rows][128 B] image whose 16-byte chunks are XOR-swizzled on the SOURCE side (chunk c of
+// row r stored at c ^ ((r >> 1) & 7): the ds_read_b128 fragment reads of 16 consecutive rows hit 16 distinct bank slots).  A ring of
+// L256_STAGES stages; one barrier per tile, behind a counted vmcnt that leaves the later tiles' pieces in flight.  The DMA is inline asm
+// the compiler does not track, and the loop holds no other vector-memory load, so no compiler-inserted vmcnt(0) drains the ring.
+// Counters: HBM 0.46, MFMA 0.27, TA ~0.42 busy -- no unit saturated; latency-bound with two tiles in flight.
+// L256_WG_ROWS / L256_STAGES / L256_W_NT select the variants measured there (developer A/B builds; the defaults are what ships).
+//
+// ROWS / 32 waves: wave w owns x rows 32w .. 32w + 31 (the B operand, two 16-row fragments) and every weight row of the workgroup (the A
+// operand), v_mfma_f32_16x16x32_bf16.  With the weight rows on the MFMA's row axis a lane ends up holding 4 CONSECUTIVE output
+// columns of one x row: one 8-byte store per lane and fragment, written through (store_out8: the consumer is the next kernel).
+//
+// GLU epilogue: act = bf16( bf16(silu(g)) * u ) with g, u the accumulators rounded to bf16 -- the arithmetic of silu_mul_kernel
+// (and of linear_small_m_kernel's GLU form), so the fused output is bit-equal to the plain output followed by ivl_silu_mul_fwd.
+#include "ivl_common.h"
+
+namespace ivl {
+
+constexpr int L256_ROWS = 256;                 // x rows of a call (at most)
+constexpr int L256_BK = 64;                    // K-tile: one 128-byte line per row
+constexpr int L256_KMAX = 16384;
+#ifndef L256_WG_ROWS
+#define L256_WG_ROWS 256                       // x rows per workgroup: 256 (all) or 128 (two workgroups per column range, one XCD)
+#endif
+#ifndef L256_STAGES
+#define L256_STAGES 3                          // ring stages (tiles requested STAGES - 1 ahead)
+#endif
+#ifndef L256_W_NT
+#define L256_W_NT 1                            // the GLU form requests its weight pieces non-temporal (each weight byte is read once):
+#endif                                         // 33.9 -> 32.5 us; the plain form keeps the default policy (nt: 22.6 -> 25.3 us)
+
+template <bool GLU, int ROWS, int NST>
+struct L256Cfg {
+  static constexpr int NCOL = GLU ? 48 : 64;                   // output columns per workgroup
+  static constexpr int NW = GLU ? 2 * NCOL : NCOL;             // weight rows per workgroup
+  static constexpr int NT = NW / 16;                           // 16-row weight fragments
+  static constexpr int WAVES = ROWS / 32;                      // a wave owns 32 x rows
+  static constexpr int PIECES = (ROWS + NW) / 8;               // 1 KB DMA pieces per K-tile (x image first, then the weight rows)
+  static constexpr int PW_MAX = (PIECES + WAVES - 1) / WAVES;  // pieces per wave: waves < PIECES % WAVES take one more
+  static constexpr int STAGE = (ROWS + NW) * 128;              // bytes per ring stage
+  static constexpr int LDS = NST * STAGE;
+};
+
+template <int N>
+__device__ __forceinline__ void l256_vmcnt() {
+  static_assert(N >= 0 && N < 64, "vmcnt immediate");
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+
+// wait until at most `ahead` (< 3) tiles of this wave's pieces are still in flight; PW: this wave's pieces per tile
+template <int PW>
+__device__ __forceinline__ void l256_wait_tiles(int ahead) {
+  if (ahead <= 0) l256_vmcnt<0>();
+  else if (ahead == 1) l256_vmcnt<PW>();
+  else l256_vmcnt<2 * PW>();
+}
+
+__device__ __forceinline__ const bf16_t* l256_uniform(const bf16_t* p) {
+  const unsigned long long v = (unsigned long long)p;
+  const unsigned int lo = __builtin_amdgcn_readfirstlane((unsigned int)v), hi = __builtin_amdgcn_readfirstlane((unsigned int)(v >> 32));
+  return (const bf16_t*)(((unsigned long long)hi << 32) | lo);
+}
+
+template <bool GLU, int ROWS, int NST, bool WNT>
+__global__ __launch_bounds__(ROWS * 2) void linear_m256_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ w,
+                                                               const bf16_t* __restrict__ bias, bf16_t* __restrict__ y, int M, int N, int K) {
+  using C = L256Cfg<GLU, ROWS, NST>;
+  static_assert(NST >= 2 && NST <= 3, "ring of 2 or 3 stages");
+  constexpr int AHEAD = NST - 1;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  // workgroup -> (column range, row block).  ROWS < 256: the row blocks of a column range are workgroups b and b + 8 of a group of
+  // 16 -- the same XCD under round-robin placement (a speed choice only), so the second reads the weight rows from that XCD's L2
+  int colblk = (int)blockIdx.x, r0 = 0;
+  if constexpr (ROWS < L256_ROWS) {
+    const int b = (int)blockIdx.x;
+    colblk = (b >> 4) * 8 + (b & 7);
+    r0 = ((b >> 3) & 1) * ROWS;
+    if (colblk * C::NCOL >= N || r0 >= M) return;    // (whole workgroup, before any barrier)
+  }
+  const int n0 = colblk * C::NCOL;
+  const int nkt = K / L256_BK;
+  const unsigned int lds_base = (unsigned int)(size_t)smem;
+
+  // ---- DMA pieces of this wave: p = wave + WAVES i.  Lane l moves the 16-byte chunk (l & 7) of row 8p + (l >> 3) of the stage
+  // image; the chunk it stores there is logical chunk (l & 7) ^ swz(row).  Source offsets are relative to the K-tile's first
+  // column and are the same for every tile (the tile advances the uniform base pointer).
+  const bool pw_full = wave < C::PIECES % C::WAVES || C::PIECES % C::WAVES == 0;
+  unsigned int src_off[C::PW_MAX];
+#pragma unroll
+  for (int i = 0; i < C::PW_MAX; ++i) {
+    const int p = min(wave + C::WAVES * i, C::PIECES - 1);
+    const int r = 8 * p + (lane >> 3);                           // row of the stage image
+    const int c = (lane & 7) ^ ((r >> 1) & 7);                   // logical chunk stored at (lane & 7)
+    long long grow;                                              // row of x / of w
+    if (r < ROWS) {
+      grow = min(r0 + r, M - 1);
+    } else {
+      const int j = r - ROWS;                                    // weight row of the workgroup
+      if (GLU) grow = j < C::NCOL ? min(n0 + j, N - 1) : (long long)N + min(n0 + j - C::NCOL, N - 1);
+      else grow = min(n0 + j, N - 1);
+    }
+    src_off[i] = (unsigned int)(grow * K * 2 + c * 16);
+  }
+  auto dma_tile = [&](int t) __attribute__((always_inline)) {
+    const unsigned int dst0 = lds_base + (unsigned int)(t % NST) * C::STAGE;
+    const bf16_t* xb = l256_uniform(x + (size_t)t * L256_BK);
+    const bf16_t* wb = l256_uniform(w + (size_t)t * L256_BK);
+#pragma unroll
+    for (int i = 0; i < C::PW_MAX; ++i) {
+      const int p = wave + C::WAVES * i;
+      if (i == C::PW_MAX - 1 && p >= C::PIECES) break;            // (wave-uniform)
+      const unsigned int dst = __builtin_amdgcn_readfirstlane(dst0 + 1024u * p);
+      unsigned int keep;
+      if (p < ROWS / 8 || !WNT)
+        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3\n\ts_mov_b32 m0, %0"
+                     : "=&s"(keep) : "v"(src_off[i]), "s"(dst), "s"(p < ROWS / 8 ? xb : wb) : "memory");
+      else
+        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3 nt\n\ts_mov_b32 m0, %0"
+                     : "=&s"(keep) : "v"(src_off[i]), "s"(dst), "s"(wb) : "memory");
+    }
+  };
+
+  // ---- fragment reads: lane l reads row (l & 15) of a 16-row fragment, chunk 4 s + (l >> 4) of k32-step s
+  unsigned int frag_off[2];
+#pragma unroll
+  for (int s = 0; s < 2; ++s) frag_off[s] = (unsigned int)((lane & 15) * 128 + (((4 * s + (lane >> 4)) ^ ((lane >> 1) & 7)) << 4));
+
+  f32x4 acc[C::NT][2];
+#pragma unroll
+  for (int j = 0; j < C::NT; ++j)
+#pragma unroll
+    for (int i = 0; i < 2; ++i) acc[j][i] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+#pragma unroll
+  for (int t = 0; t < AHEAD; ++t)
+    if (t < nkt) dma_tile(t);
+  for (int t = 0; t < nkt; ++t) {
+    // tile t has landed for this wave's pieces; the barrier makes every wave's pieces visible and retires every wave's reads of
+    // tile t - 1, whose stage tile t + AHEAD then reuses
+    const int ahead = min(AHEAD - 1, nkt - 1 - t);
+    if (pw_full) l256_wait_tiles<C::PW_MAX>(ahead);
+    else l256_wait_tiles<C::PW_MAX - 1>(ahead);
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    if (t + AHEAD < nkt) dma_tile(t + AHEAD);
+    const unsigned char* st = smem + (t % NST) * C::STAGE;
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      bf16x8 xf[2], wf[C::NT];
+#pragma unroll
+      for (int i = 0; i < 2; ++i) xf[i] = *(const bf16x8*)(st + (32 * wave + 16 * i) * 128 + frag_off[s]);
+#pragma unroll
+      for (int j = 0; j < C::NT; ++j) wf[j] = *(const bf16x8*)(st + (ROWS + 16 * j) * 128 + frag_off[s]);
+#pragma unroll
+      for (int j = 0; j < C::NT; ++j)
+#pragma unroll
+        for (int i = 0; i < 2; ++i) acc[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[j], xf[i], acc[j][i], 0, 0, 0);
+    }
+  }
+
+  // ---- epilogue: acc[j][i][r] = y[row r0 + 32 wave + 16 i + (l & 15)][col n0 + 16 j + 4 (l >> 4) + r]
+  const int cq = 4 * (lane >> 4);
+  if constexpr (GLU) {
+#pragma unroll
+    for (int j = 0; j < C::NT / 2; ++j) {
+      const int col = n0 + 16 * j + cq;
+      float bg[4] = {0.f, 0.f, 0.f, 0.f}, bu[4] = {0.f, 0.f, 0.f, 0.f};
+      if (bias != nullptr && col < N)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) { bg[r] = bf2f(bias[col + r]); bu[r] = bf2f(bias[N + col + r]); }
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const int row = r0 + 32 * wave + 16 * i + (lane & 15);
+        float o[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float g = bf_round(acc[j][i][r] + bg[r]), u = bf_round(acc[j + C::NT / 2][i][r] + bu[r]);
+          o[r] = bf_round(g * sigmoidf_(g)) * u;
+        }
+        if (row < M && col < N) store_out8(y + (size_t)row * N + col, u32x2{pack2bf(o[0], o[1]), pack2bf(o[2], o[3])});
+      }
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < C::NT; ++j) {
+      const int col = n0 + 16 * j + cq;
+      float bb[4] = {0.f, 0.f, 0.f, 0.f};
+      if (bias != nullptr && col < N)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) bb[r] = bf2f(bias[col + r]);
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const int row = r0 + 32 * wave + 16 * i + (lane & 15);
+        if (row < M && col < N)
+          store_out8(y + (size_t)row * N + col,
+                     u32x2{pack2bf(acc[j][i][0] + bb[0], acc[j][i][1] + bb[1]), pack2bf(acc[j][i][2] + bb[2], acc[j][i][3] + bb[3])});
+      }
+    }
+  }
+}
+
+template <bool GLU>
+static int launch_l256(const void* x, const void* w, const void* bias, void* y, int M, int N, int K, hipStream_t st) {
+  constexpr int ROWS = L256_WG_ROWS, NST = L256_STAGES;
+  using C = L256Cfg<GLU, ROWS, NST>;
+  constexpr bool WNT = GLU && L256_W_NT != 0;
+  const void* fn = (const void*)linear_m256_kernel<GLU, ROWS, NST, WNT>;
+  static bool attr_set[64];                        // per device: a function attribute belongs to the device's copy of the code object
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  if (!__atomic_load_n(&attr_set[dev & 63], __ATOMIC_ACQUIRE)) {
+    (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
+    __atomic_store_n(&attr_set[dev & 63], true, __ATOMIC_RELEASE);
+  }
+  const int ncol = (N + C::NCOL - 1) / C::NCOL;
+  const dim3 grid(ROWS < L256_ROWS ? (ncol + 7) / 8 * 16 : ncol);
+  hipLaunchKernelGGL((linear_m256_kernel<GLU, ROWS, NST, WNT>), grid, dim3(ROWS * 2), C::LDS, st, (const bf16_t*)x,
+                     (const bf16_t*)w, (const bf16_t*)bias, (bf16_t*)y, M, N, K);
+  return check_launch("ivl_linear_m256_fwd");
+}
+
+}  // namespace ivl
+
+using namespace ivl;
+
+extern "C" int ivl_linear_m256_fwd(const void* x, const void* w, const void* bias, void* y, int M, int N, int K, int glu, void* stream) {
+  IVL_REQUIRE(x && w && y, IVL_ERR_INVALID_ARG, "ivl_linear_m256_fwd: NULL pointer");
+  IVL_REQUIRE(M > 0 && N > 0 && K > 0, IVL_ERR_INVALID_ARG, "ivl_linear_m256_fwd: M=%d N=%d K=%d", M, N, K);
+  IVL_REQUIRE(M <= L256_ROWS, IVL_ERR_UNSUPPORTED, "ivl_linear_m256_fwd: M=%d (built for at most %d rows)", M, L256_ROWS);
+  IVL_REQUIRE(K % L256_BK == 0 && K <= L256_KMAX, IVL_ERR_UNSUPPORTED,
+              "ivl_linear_m256_fwd: K=%d (a multiple of %d, at most %d)", K, L256_BK, L256_KMAX);
+  IVL_REQUIRE(N % 4 == 0, IVL_ERR_UNSUPPORTED, "ivl_linear_m256_fwd: N=%d (a multiple of 4: 8-byte output pieces)", N);
+  // every source offset of the DMA is a 32-bit byte offset from the weight (x) base
+  IVL_REQUIRE((long long)(glu ? 2 : 1) * N * K * 2 < (1ll << 32), IVL_ERR_UNSUPPORTED,
+              "ivl_linear_m256_fwd: weight of %d x %d rows does not fit 32-bit offsets", glu ? 2 * N : N, K);
+  IVL_REQUIRE((((size_t)x | (size_t)w) & 15) == 0 && ((size_t)y & 7) == 0 && ((size_t)bias & 1) == 0, IVL_ERR_INVALID_ARG,
+              "ivl_linear_m256_fwd: x / w must be 16-byte aligned, y 8-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  return glu ? launch_l256<true>(x, w, bias, y, M, N, K, st) : launch_l256<false>(x, w, bias, y, M, N, K, st);
+}

@@ -918,6 +918,24 @@ def silu_mul(gate_up: torch.Tensor) -> torch.Tensor:
     return y
 
 
+def _m256_swiglu_applies(x: torch.Tensor, w_gate_up: torch.Tensor, rows: int, I: int, K: int) -> bool:
+    """ivl_linear_m256_fwd takes the SwiGLU MLP head of a 256-row prefill chunk (the fused gate|up weight, 48 output columns per
+    workgroup: 6144 < I <= 12288 makes one wave of workgroups over the chip's 256 CUs) when the kernel's layout admits it.
+    Measured against the library GEMM at the bench shapes (tools/ab_linear_m256.py, same box): gate|up + silu_mul 39.7 -> 32.5 us;
+    the plain form on the GDN in-projection (256 x 12320 x 2048) 22.6 us against the library's 20.7, so plain projections, like
+    the narrow N = 2048 / 2560 ones and every 4096-row call, stay on the library GEMM."""
+    return (x.is_cuda and rows == 256 and 6144 < I <= 12288 and I % 4 == 0 and K % 64 == 0 and 64 <= K <= 16384
+            and x.dtype == torch.bfloat16 and w_gate_up.dtype == torch.bfloat16 and w_gate_up.dim() == 2
+            and w_gate_up.is_contiguous() and x.is_contiguous() and x.shape[-1] == K and x.data_ptr() % 16 == 0
+            and w_gate_up.data_ptr() % 16 == 0)
+
+
+def _linear_swiglu_m256(x: torch.Tensor, w_gate_up: torch.Tensor, rows: int, I: int, K: int) -> torch.Tensor:
+    y = torch.empty(*x.shape[:-1], I, dtype=torch.bfloat16, device=x.device)
+    _lib.check(_lib.load().ivl_linear_m256_fwd(_p(x), _p(w_gate_up), None, _p(y), rows, I, K, 1, _stream(x)))
+    return y
+
+
 def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
     """nn.Linear forward.  A single-token decode step (<= 4 rows) is a pure weight stream and goes through
     ivl_linear_small_m_fwd; longer calls are stock library GEMMs (hipBLASLt / rocBLAS through torch), which
@@ -943,7 +961,8 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] =
 
 def linear_swiglu(x: torch.Tensor, w_gate_up: torch.Tensor) -> torch.Tensor:
     """silu(gate_proj(x)) * up_proj(x) with the fused gate|up weight [2I, K] (std:945).  Decode steps (<= 4 rows)
-    apply the gate in the epilogue of the weight-stream kernel; longer calls are a library GEMM + silu_mul."""
+    apply the gate in the epilogue of the weight-stream kernel, and so does the 256-row kernel of a prefill chunk
+    (ivl_linear_m256_fwd); other calls are a library GEMM + silu_mul."""
     if isinstance(x, PreNorm):
         y = _prenorm_linear(x, w_gate_up, None, True)
         if y is not None:
@@ -958,6 +977,8 @@ def linear_swiglu(x: torch.Tensor, w_gate_up: torch.Tensor) -> torch.Tensor:
         y = torch.empty(*x.shape[:-1], I, dtype=torch.bfloat16, device=x.device)
         _lib.check(_lib.load().ivl_linear_swiglu_small_m_fwd(_p(xc), _p(w_gate_up), None, _p(y), rows, I, K, _stream(x)))
         return y
+    if _m256_swiglu_applies(x, w_gate_up, rows, I, K):
+        return _linear_swiglu_m256(x, w_gate_up, rows, I, K)
     return silu_mul(linear(x, w_gate_up))
 
 
