@@ -3,7 +3,7 @@ hybrid-attention hot path (Gated DeltaNet chunk/recurrent rule + sliding-window 
 
 Layout
     csrc/        hand-written HIP kernels + the C ABI (include/ivl_hip.h) -> libivl_hip.so
-    _lib.py      ctypes binding (no fallback: a missing library raises)
+    _lib.py      ctypes binding, derived from include/ivl_hip.h at import (no fallback: a missing library raises)
     ops.py       operator-level API with the reference's operator names
     cache.py     StaticCachePrealloc & friends (ring-buffer / device-counter redesign)
     modules.py   GatedDeltaNet, InfiniteVLSelfAttention drop-in nn.Modules

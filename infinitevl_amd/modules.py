@@ -418,17 +418,12 @@ class InfiniteVLVisionAttention(nn.Module):
 def _conv_into(mod: "ops.ShortConvolution", x: torch.Tensor, prev: Optional[torch.Tensor], dst: torch.Tensor):
     """Run the short conv reading history from `prev` (None = zero history, the reference's first call,
     std:298-300) and writing the new state into the pre-allocated cache tensor `dst` (may alias prev)."""
-    from . import _lib
-    from .ops import _p, _stream
     if dst.dtype != torch.bfloat16:
         # non-bf16 cache: run on a bf16 copy of the history; cache.update(op="set") copies the result back
         tmp = prev.to(torch.bfloat16) if prev is not None else None
         return mod(x, cache=tmp, output_final_state=True)
     B, T, D = x.shape
-    W = mod.kernel_size[0]
     x = x.contiguous()
     y = torch.empty_like(x)
-    w = mod.weight if mod.weight.dtype == torch.bfloat16 else mod.weight.to(torch.bfloat16)
-    _lib.check(_lib.load().ivl_short_conv_fwd(_p(x), _p(w.contiguous()), _p(prev), _p(y), _p(dst), B, T, D, W,
-                                              int(mod.activation is not None), _stream(x)))
+    mod._launch(x, y, prev, dst, B, T, D, mod.kernel_size[0])
     return y, dst

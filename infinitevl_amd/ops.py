@@ -44,6 +44,11 @@ def _p(t: Optional[torch.Tensor]):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
+def _pd(t: Optional[torch.Tensor], default: int = IVL_F32):
+    """(pointer, dtype code) of an optional state / residual tensor; `default` is the code handed over with a NULL pointer."""
+    return _p(t), _DT_CODE[t.dtype] if t is not None else default
+
+
 def _stream(t: torch.Tensor):
     return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
 
@@ -202,8 +207,7 @@ def fused_recurrent_gated_delta_rule(
     def entry(q_, k_, v_, g_, b_, o_, hi, ho, Tn, H_, K_, V_, sc, l2):
         _lib.check(rec_fwd(
             _p(q_), _p(k_), _p(v_), _p(g_), _p(b_), _p(o_),
-            _p(hi), _DT_CODE[hi.dtype] if hi is not None else IVL_F32,
-            _p(ho), _DT_CODE[ho.dtype] if ho is not None else IVL_F32,
+            *_pd(hi), *_pd(ho),
             q_.shape[0], Tn, H_, K_, V_, sc, l2, _stream(q_)))
     if cu_seqlens is not None:
         _gdn_varlen(entry, q, k, v, g, beta, o, h0, ht, _varlen_segments(cu_seqlens, T), H, K, V, scale,
@@ -248,8 +252,7 @@ def chunk_gated_delta_rule(
     def entry(q_, k_, v_, g_, b_, o_, hi, ho, Tn, H_, K_, V_, sc, l2):
         _lib.check(lib.ivl_gdn_chunk_fwd(
             _p(q_), _p(k_), _p(v_), _p(g_), _p(b_), _p(o_),
-            _p(hi), _DT_CODE[hi.dtype] if hi is not None else IVL_F32,
-            _p(ho), _DT_CODE[ho.dtype] if ho is not None else IVL_F32,
+            *_pd(hi), *_pd(ho),
             q_.shape[0], Tn, H_, K_, V_, sc, l2, mma, _p(ws), ws.numel(), _stream(q_)))
     if segs is not None:
         _gdn_varlen(entry, q, k, v, g, beta, o, h0, ht, segs, H, K, V, scale, int(bool(use_qk_l2norm_in_kernel)), ())
@@ -466,7 +469,7 @@ def gdn_chunk_fused(proj: torch.Tensor, cols, conv_weights, conv_states_in, conv
     _lib.check(lib.ivl_gdn_chunk_fused_fwd(
         _p(proj), ld, cols[0], cols[1], cols[2], cols[3], cols[4], _p(wq), _p(wk), _p(wv),
         _p(si[0]), _p(si[1]), _p(si[2]), _p(so[0]), _p(so[1]), _p(so[2]), _p(A_log32), _p(dt_bias32), _p(o),
-        _p(h0), _DT_CODE[h0.dtype] if h0 is not None else IVL_F32, _p(ht), _DT_CODE[ht.dtype] if ht is not None else IVL_F32,
+        *_pd(h0), *_pd(ht),
         B, T, H, K, V, wq.shape[-1], float(K ** -0.5 if scale is None else scale), mma_code(mma_dtype), _p(ws), ws.numel(),
         _p(area) if _GDN_SINGLE_LAUNCH else None, _stream(proj)))
     return o
@@ -671,8 +674,8 @@ class FusedRMSNormGated(nn.Module):
             res_dt = residual.dtype if residual is not None else (torch.float32 if residual_in_fp32 else None)
             res_out = torch.empty(x.shape, dtype=res_dt, device=x.device) if res_dt is not None and (residual is not None or res_dt != x.dtype) else None
             _lib.check(_lib.load().ivl_rmsnorm_swish_gate_res_fwd(
-                _p(x), _p(g), _p(w.contiguous()), _p(residual), _DT_CODE[residual.dtype] if residual is not None else IVL_BF16,
-                _p(res_out), _DT_CODE[res_out.dtype] if res_out is not None else IVL_BF16, _p(y), x.numel() // N, N, float(self.eps), _stream(x)))
+                _p(x), _p(g), _p(w.contiguous()), *_pd(residual, IVL_BF16), *_pd(res_out, IVL_BF16),
+                _p(y), x.numel() // N, N, float(self.eps), _stream(x)))
             return y if not prenorm else (y, res_out if res_out is not None else x)
         _lib.check(_lib.load().ivl_rmsnorm_swish_gate_fwd(_p(x), _p(g), _p(w.contiguous()), _p(y),
                                                           x.numel() // N, N, float(self.eps), _stream(x)))

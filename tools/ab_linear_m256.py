@@ -42,10 +42,7 @@ def main():
     libs = {"m256": _lib.load()}
     for v in args.variant:
         vname, path = v.split("=", 1)
-        lib = ctypes.CDLL(os.path.abspath(path))
-        lib.ivl_linear_m256_fwd.restype = ctypes.c_int
-        lib.ivl_linear_m256_fwd.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_int] * 4 + [ctypes.c_void_p]
-        libs[vname] = lib
+        libs[vname] = _lib.bind(ctypes.CDLL(os.path.abspath(path)), require_all=False)
     res = {}
     for name, (N, K, glu) in SHAPES.items():
         rows_w = 2 * N if glu else N
