@@ -18,16 +18,10 @@ typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 
 // 16-byte store of a kernel OUTPUT that the next kernel (a GEMM on all eight dies) reads.  The lines have to reach the memory
 // side before that kernel starts whatever the policy; written through (`sc0 sc1`) they leave while the kernel still runs instead
-// of in its end-of-kernel write-back.  IVL_OUT_STORE: 0 = plain, 1 = non-temporal, 2 = write-through (default).  Same-box ABAB
-// of the default bench line for the add+norm / gated norm / SwiGLU-gate kernels (136 launches of a step): plain 5.261 / 5.297
-// -> write-through 5.230 / 5.266 ms per step (their in-step time 1.431 / 1.425 -> 1.392 / 1.368 ms); non-temporal: no change.
-#ifndef IVL_OUT_STORE
-#define IVL_OUT_STORE 2
-#endif
+// of in its end-of-kernel write-back.  Why write-through and nothing else: same-box ABAB of the default bench line for the
+// add+norm / gated norm / SwiGLU-gate kernels (136 launches of a step): plain stores 5.261 / 5.297 -> write-through 5.230 / 5.266 ms
+// per step (their in-step time 1.431 / 1.425 -> 1.392 / 1.368 ms); non-temporal stores: no change against plain.
 __device__ __forceinline__ void store_out16(void* p, u32x4 v) {
-#if IVL_OUT_STORE == 1
-  __builtin_nontemporal_store(v, (u32x4*)p);
-#elif IVL_OUT_STORE == 2
   // (the s_nop: a store of more than 8 bytes reads its data registers after issue, and hipcc does not pad an asm statement --
   //  without it the next instruction may overwrite them first: cdna_hip_programming.md section 5.7)
   // CONTRACT for callers: hipcc inserts no wait states in FRONT of an asm statement either -- `v` and `p` must be the
@@ -35,17 +29,10 @@ __device__ __forceinline__ void store_out16(void* p, u32x4 v) {
   // of an MFMA / v_dot or a freshly written SGPR-derived VGPR pair; every caller today passes a pack2bf / cvt_pk result or an LDS
   // read behind its s_waitcnt.  A new call site that stores an accumulator register as is must copy it through a VALU move first.
   asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
-#else
-  *(u32x4*)p = v;
-#endif
 }
 typedef __attribute__((ext_vector_type(2))) unsigned int ivl_u32x2_t;
 __device__ __forceinline__ void store_out8(void* p, ivl_u32x2_t v) {
-#if IVL_OUT_STORE == 2
   asm volatile("global_store_dwordx2 %0, %1, off sc0 sc1" ::"v"(p), "v"(v) : "memory");
-#else
-  *(ivl_u32x2_t*)p = v;
-#endif
 }
 
 typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;

@@ -41,9 +41,10 @@ struct SwaParams {
   const bf16_t* rcos; const bf16_t* rsin; int rs0, rs1;
 };
 
-// QG = 16-row query groups per wave (1: 64 rows per workgroup, decode / short calls; 2: 128 rows per workgroup).
-// With QG = 2 every K / V^T fragment read from LDS feeds two MFMAs: at QG = 1 the 4 waves of a workgroup pull
-// 128 KB through the 128 B/clk LDS port per 64-key tile (1024 clk) for 512 clk of MFMA work per SIMD.
+// QG = 16-row query groups per wave.  Only QG = 1 (64 rows per workgroup, decode / short calls) is instantiated: there the 4 waves
+// of a workgroup pull 128 KB through the 128 B/clk LDS port per 64-key tile (1024 clk) for 512 clk of MFMA work per SIMD.  QG = 2
+// (128 rows per workgroup, every K / V^T fragment read from LDS feeding two MFMAs) was round 2a's answer to that; swa_prefill_kernel
+// superseded it and it is no longer instantiated.
 // butterfly over the four 16-lane groups of a wave (the lanes that share a query row) on the gfx950 lane-swap
 // instructions: v_permlane16_swap exchanges odd rows of one operand with even rows of the other, v_permlane32_swap
 // the upper half with the lower half; with both operands = x the two results hold x and its partner.
@@ -858,21 +859,13 @@ __global__ __launch_bounds__(256) void swa_rows_combine_wide_kernel(const float*
 // stand-alone ring append (ivl_swa_cache_append, and ivl_swa_fwd with append_new when no combine launch follows)
 __global__ __launch_bounds__(256) void swa_cache_append_kernel(AppendArgs ap) { ring_append(ap, blockIdx.x, gridDim.x); }
 
-// The 64-row kernel (QG = 1) serves decode / T <= 64 calls; longer calls run swa_prefill_kernel (the QG = 2 instantiation of
-// round 2a - two 16-row groups per wave - is superseded by it and no longer launched).
-static int swa_qg(int, int, int) { return 1; }
-
+// The 64-row kernel (QG = 1) serves decode / T <= 64 calls; longer calls run swa_prefill_kernel.  The QG = 2 form of round 2a (two
+// 16-row groups per wave) is superseded by it and not instantiated; QG stays a template parameter of swa_fwd_kernel.
 static int swa_base_nsplit(int B, int T, int Hq) {
-  if (T > SWA_QT) {
-    const long long base = (long long)B * ((T + PF_QT - 1) / PF_QT) * Hq;
-    long long ns = (256 + base - 1) / base;
-    if (ns < 1) ns = 1;
-    if (ns > SWA_MAX_SPLIT) ns = SWA_MAX_SPLIT;
-    return (int)ns;
-  }
-  const int qt = SWA_QT * swa_qg(B, T, Hq);
+  const bool prefill = T > SWA_QT;
+  const int qt = prefill ? PF_QT : SWA_QT;
   const long long base = (long long)B * ((T + qt - 1) / qt) * Hq;
-  long long ns = (512 + base - 1) / base;
+  long long ns = ((prefill ? 256 : 512) + base - 1) / base;
   if (ns < 1) ns = 1;
   if (ns > SWA_MAX_SPLIT) ns = SWA_MAX_SPLIT;
   return (int)ns;
@@ -888,6 +881,40 @@ static int swa_max_tiles(const ivl_swa_args* a) {
   return (int)(span / SWA_KT) + 2;
 }
 
+// packed decode rows (T * Hq/Hkv <= 64): one key tile per workgroup, the K / V read is the whole cost.  ivl_swa_fwd and
+// ivl_swa_decode_rows_fwd both take their split count from here (capacity and window only), and their combine from
+// swa_combine_append: that is why row b of a pos_rows call and a B = 1 ivl_swa_fwd at pos = pos_rows[b] run the same
+// workgroups and the same merge, bit for bit
+static int swa_pack_nsplit(const ivl_swa_args* a) {
+  const int nsplit = swa_max_tiles(a);
+  return nsplit > SWA_MAX_SPLIT_PACK ? SWA_MAX_SPLIT_PACK : nsplit;
+}
+
+// ---- argument rules shared by ivl_swa_fwd and ivl_swa_decode_rows_fwd (`fn`: the entry point's name for the message).  One function
+// per run of rules that sit together in both: every entry point calls them between its own rules, in its own order.
+static int swa_check_pointers(const ivl_swa_args* a, const char* fn) {
+  IVL_REQUIRE(a != nullptr, IVL_ERR_INVALID_ARG, "%s: NULL args", fn);
+  IVL_REQUIRE(a->q && a->k_new && a->v_new && a->o, IVL_ERR_INVALID_ARG, "%s: NULL q/k_new/v_new/o", fn);
+  return IVL_OK;
+}
+static int swa_check_heads(const ivl_swa_args* a, const char* fn) {      // behind the entry point's size rule (Hkv > 0)
+  IVL_REQUIRE(a->d == SWA_D, IVL_ERR_UNSUPPORTED, "%s: head_dim %d unsupported (built for 128)", fn, a->d);
+  IVL_REQUIRE(a->Hq % a->Hkv == 0, IVL_ERR_INVALID_ARG, "%s: Hq=%d not a multiple of Hkv=%d", fn, a->Hq, a->Hkv);
+  return IVL_OK;
+}
+static int swa_check_rope_tables(const ivl_swa_args* a, const char* fn) {
+  IVL_REQUIRE((a->rope_cos == nullptr) == (a->rope_sin == nullptr), IVL_ERR_INVALID_ARG, "%s: rope_cos and rope_sin go together", fn);
+  return IVL_OK;
+}
+// the mrope sections the fused rotation takes (rope_pair rotates 8-channel blocks)
+static bool swa_rope_sections_ok(int s0, int s1) { return s0 % 8 == 0 && s1 % 8 == 0 && s0 >= 0 && s1 >= 0 && s0 + s1 <= 64; }
+// new-key rows are addressed with 32-bit element offsets from the (batch, kv-head) base
+static int swa_check_key_rows(const ivl_swa_args* a, const char* fn, const char* hint) {
+  IVL_REQUIRE((long long)a->T_new * a->kn_st < (1LL << 32) && a->kn_st >= 0, IVL_ERR_UNSUPPORTED,
+              "%s: T_new * kn_st = %lld elements exceeds the 32-bit row addressing of the kernel%s", fn, (long long)a->T_new * a->kn_st, hint);
+  return IVL_OK;
+}
+
 static SwaParams swa_params(const ivl_swa_args* a, int nsplit) {
   SwaParams p;
   p.q = (const bf16_t*)a->q; p.k_new = (const bf16_t*)a->k_new; p.v_new = (const bf16_t*)a->v_new;
@@ -901,16 +928,62 @@ static SwaParams swa_params(const ivl_swa_args* a, int nsplit) {
   return p;
 }
 
-// the ring append of a call (ivl_swa_args.append_new) with the (possibly rotated-copy) keys of p; returns its block count
-static int swa_append_args(const ivl_swa_args* a, const SwaParams& p, AppendArgs& ap) {
-  ap.k_new = p.k_new; ap.v_new = p.v_new; ap.kn_sb = p.kn_sb; ap.kn_st = p.kn_st; ap.kn_sh = p.kn_sh;
-  ap.vn_sb = p.vn_sb; ap.vn_st = p.vn_st; ap.vn_sh = p.vn_sh;
-  ap.k_cache = (bf16_t*)a->k_cache; ap.v_cache = (bf16_t*)a->v_cache;
-  ap.B = a->B; ap.T = a->T; ap.Hkv = a->Hkv; ap.C = a->cache_capacity; ap.pos = a->pos; ap.pos_dev = p.pos_dev;
-  ap.rcos = p.rcos; ap.rsin = p.rsin; ap.rs0 = p.rs0; ap.rs1 = p.rs1;
-  const int nt = a->T > a->cache_capacity ? a->cache_capacity : a->T;
-  long long ab = ((long long)a->B * nt * a->Hkv * (SWA_D / 8) + 255) / 256;
-  return (int)(ab > 2048 ? 2048 : ab);
+// split-KV partials of p.nsplit > 1 splits at the head of the workspace: part_o [B, nsplit, T, Hq, 128] and, behind it, the
+// (m, l) pairs part_ml [B, nsplit, T, Hq, 2], both sized as fp32
+static size_t swa_partials_bytes(const SwaParams& p) { return (size_t)p.B * p.nsplit * p.T * p.Hq * (SWA_D + 2) * sizeof(float); }
+static int swa_carve_partials(const ivl_swa_args* a, const char* fn, SwaParams& p) {
+  const size_t need = swa_partials_bytes(p);
+  IVL_REQUIRE(a->workspace != nullptr && a->workspace_bytes >= need, IVL_ERR_WORKSPACE, "%s: workspace %zu bytes < required %zu (nsplit=%d)",
+              fn, a->workspace_bytes, need, p.nsplit);
+  p.part_o = (float*)a->workspace;
+  p.part_ml = p.part_o + (size_t)p.B * p.nsplit * p.T * p.Hq * SWA_D;
+  return IVL_OK;
+}
+
+// the ring append of T new tokens (keys k_new with strides kn_*, values v_new with strides vn_*) into a ring of C slots; returns
+// its block count.  first_block is the caller's.
+static int swa_append_args(AppendArgs& ap, const bf16_t* k_new, long long kn_sb, long long kn_st, long long kn_sh, const bf16_t* v_new,
+                           long long vn_sb, long long vn_st, long long vn_sh, const void* k_cache, const void* v_cache, int B, int T, int Hkv,
+                           int C, long long pos, const long long* pos_dev, const bf16_t* rcos, const bf16_t* rsin, int rs0, int rs1) {
+  ap.k_new = k_new; ap.kn_sb = kn_sb; ap.kn_st = kn_st; ap.kn_sh = kn_sh;
+  ap.v_new = v_new; ap.vn_sb = vn_sb; ap.vn_st = vn_st; ap.vn_sh = vn_sh;
+  ap.k_cache = (bf16_t*)k_cache; ap.v_cache = (bf16_t*)v_cache;
+  ap.B = B; ap.T = T; ap.Hkv = Hkv; ap.C = C; ap.pos = pos; ap.pos_dev = pos_dev;
+  ap.rcos = rcos; ap.rsin = rsin; ap.rs0 = rs0; ap.rs1 = rs1;
+  const int nt = T > C ? C : T;
+  return blocks256((long long)B * nt * Hkv * (SWA_D / 8), 2048);
+}
+
+// What follows the attention launch: the merge of the split-KV partials (p.nsplit > 1) with the ring append (`append`) in the
+// blocks behind the combine blocks, or the stand-alone append launch when there is nothing to merge.  `rows`: the pos_rows forms;
+// `bf16p`: the partials are swa_prefill_kernel's.  The append uses the (possibly rotated-copy) keys of p.
+typedef void (*swa_combine_fn)(const float*, const float*, bf16_t*, int, int, int, AppendArgs);
+static swa_combine_fn swa_combine_for(int nsplit, bool rows, bool bf16p) {
+  if (nsplit > 16) return rows ? swa_rows_combine_wide_kernel : swa_combine_wide_kernel;
+  if (rows) return nsplit <= 4 ? swa_rows_combine_kernel<4> : nsplit <= 8 ? swa_rows_combine_kernel<8> : swa_rows_combine_kernel<16>;
+  if (bf16p) return nsplit <= 4 ? swa_combine_kernel<4, true> : nsplit <= 8 ? swa_combine_kernel<8, true> : swa_combine_kernel<16, true>;
+  return nsplit <= 4 ? swa_combine_kernel<4, false> : nsplit <= 8 ? swa_combine_kernel<8, false> : swa_combine_kernel<16, false>;
+}
+static int swa_combine_append(const SwaParams& p, bool rows, bool bf16p, bool append, hipStream_t st) {
+  AppendArgs ap;
+  ap.first_block = -1;
+  const int append_blocks = !append ? 0 : swa_append_args(ap, p.k_new, p.kn_sb, p.kn_st, p.kn_sh, p.v_new, p.vn_sb, p.vn_st, p.vn_sh, p.k_cache,
+                                                          p.v_cache, p.B, p.T, p.Hkv, p.C, p.pos, p.pos_dev, p.rcos, p.rsin, p.rs0, p.rs1);
+  if (p.nsplit > 1) {
+    const long long nrows = (long long)p.B * p.T * p.Hq;
+    const int blocks = p.nsplit > 16 ? (int)(nrows > 4096 ? 4096 : nrows)        // wide: one workgroup per row
+                                     : blocks256(nrows * 64, 4096);              // one wavefront per row
+    if (append_blocks > 0) ap.first_block = blocks;
+    hipLaunchKernelGGL(swa_combine_for(p.nsplit, rows, bf16p), dim3(blocks + append_blocks), dim3(256), 0, st, p.part_o, p.part_ml, p.o,
+                       p.B, p.T * p.Hq, p.nsplit, ap);
+    return check_launch(rows ? "ivl_swa_decode_rows_fwd(combine)" : "ivl_swa_fwd(combine)");
+  }
+  if (append_blocks > 0) {                     // ivl_swa_fwd only: the pos_rows form always has splits to merge
+    ap.first_block = 0;
+    hipLaunchKernelGGL(swa_cache_append_kernel, dim3(append_blocks), dim3(256), 0, st, ap);
+    return check_launch("ivl_swa_fwd(append)");
+  }
+  return IVL_OK;
 }
 
 }  // namespace ivl
@@ -928,20 +1001,17 @@ extern "C" size_t ivl_swa_workspace_bytes(int B, int T, int Hq, int d) {
 }
 
 extern "C" int ivl_swa_fwd(const ivl_swa_args* a, void* stream) {
-  IVL_REQUIRE(a != nullptr, IVL_ERR_INVALID_ARG, "ivl_swa_fwd: NULL args");
-  IVL_REQUIRE(a->q && a->k_new && a->v_new && a->o, IVL_ERR_INVALID_ARG, "ivl_swa_fwd: NULL q/k_new/v_new/o");
+  static const char fn[] = "ivl_swa_fwd";
+  if (const int rc = swa_check_pointers(a, fn); rc != IVL_OK) return rc;
   IVL_REQUIRE(a->B > 0 && a->T > 0 && a->T_new >= a->T && a->Hq > 0 && a->Hkv > 0, IVL_ERR_INVALID_ARG,
               "ivl_swa_fwd: bad sizes B=%d T=%d T_new=%d Hq=%d Hkv=%d", a->B, a->T, a->T_new, a->Hq, a->Hkv);
-  IVL_REQUIRE(a->d == SWA_D, IVL_ERR_UNSUPPORTED, "ivl_swa_fwd: head_dim %d unsupported (built for 128)", a->d);
-  IVL_REQUIRE(a->Hq % a->Hkv == 0, IVL_ERR_INVALID_ARG, "ivl_swa_fwd: Hq=%d not a multiple of Hkv=%d", a->Hq, a->Hkv);
+  if (const int rc = swa_check_heads(a, fn); rc != IVL_OK) return rc;
   IVL_REQUIRE(a->cache_capacity >= 0 && (a->cache_capacity == 0 || (a->k_cache && a->v_cache)), IVL_ERR_INVALID_ARG,
               "ivl_swa_fwd: cache_capacity=%d needs k_cache/v_cache", a->cache_capacity);
   IVL_REQUIRE(a->pos_dev != nullptr || a->pos >= 0, IVL_ERR_INVALID_ARG, "ivl_swa_fwd: negative pos");
-  IVL_REQUIRE((a->rope_cos == nullptr) == (a->rope_sin == nullptr), IVL_ERR_INVALID_ARG, "ivl_swa_fwd: rope_cos and rope_sin go together");
-  IVL_REQUIRE(a->rope_cos == nullptr || (a->T_new == a->T && a->rope_s0 % 8 == 0 && a->rope_s1 % 8 == 0 && a->rope_s0 >= 0 &&
-                                          a->rope_s1 >= 0 && a->rope_s0 + a->rope_s1 <= 64),
-              IVL_ERR_UNSUPPORTED, "ivl_swa_fwd: fused rope needs T_new == T and mrope sections that are multiples of 8 (got %d, %d)",
-              a->rope_s0, a->rope_s1);
+  if (const int rc = swa_check_rope_tables(a, fn); rc != IVL_OK) return rc;
+  IVL_REQUIRE(a->rope_cos == nullptr || (a->T_new == a->T && swa_rope_sections_ok(a->rope_s0, a->rope_s1)), IVL_ERR_UNSUPPORTED,
+              "ivl_swa_fwd: fused rope needs T_new == T and mrope sections that are multiples of 8 (got %d, %d)", a->rope_s0, a->rope_s1);
   IVL_REQUIRE(a->rope_cos == nullptr || a->mma_dtype == IVL_BF16 || !((long long)a->T * (a->Hq / a->Hkv) <= SWA_QT),
               IVL_ERR_UNSUPPORTED, "ivl_swa_fwd: the fp8 decode step takes rotated q / k (apply ivl_mrope_fwd first)");
   IVL_REQUIRE(a->mma_dtype == IVL_BF16 || a->mma_dtype == IVL_FP8_E4M3, IVL_ERR_INVALID_ARG,
@@ -949,10 +1019,7 @@ extern "C" int ivl_swa_fwd(const ivl_swa_args* a, void* stream) {
   IVL_REQUIRE(!a->append_new || (a->cache_capacity > 0 && a->T_new == a->T), IVL_ERR_INVALID_ARG,
               "ivl_swa_fwd: append_new needs a ring cache and T_new == T (got capacity %d, T_new %d, T %d)", a->cache_capacity,
               a->T_new, a->T);
-  // new-key rows are addressed with 32-bit element offsets from the (batch, kv-head) base
-  IVL_REQUIRE((long long)a->T_new * a->kn_st < (1LL << 32) && a->kn_st >= 0, IVL_ERR_UNSUPPORTED,
-              "ivl_swa_fwd: T_new * kn_st = %lld elements exceeds the 32-bit row addressing of the kernel (split the call)",
-              (long long)a->T_new * a->kn_st);
+  if (const int rc = swa_check_key_rows(a, fn, " (split the call)"); rc != IVL_OK) return rc;
   // a long call over a FULL ring (the caller vouches for pos >= C): the 256-row form on a linear copy of the keys (swa_ring256.hip)
   if (a->pos_min >= a->cache_capacity && a->cache_capacity > 0 && a->window == a->cache_capacity + 1 && a->T_new == a->T &&
       a->mma_dtype == IVL_BF16 && a->pos_min >= 0 && (a->pos_dev != nullptr || a->pos >= a->cache_capacity)) {
@@ -961,29 +1028,20 @@ extern "C" int ivl_swa_fwd(const ivl_swa_args* a, void* stream) {
   }
   const int G = a->Hq / a->Hkv;
   const bool pack = (long long)a->T * G <= SWA_QT && G <= 16;
-  const int max_tiles = swa_max_tiles(a);
-  int nsplit = 1;
+  int nsplit;
   if (pack) {
-    nsplit = max_tiles;                    // decode: one key tile per workgroup (the K/V read is the whole cost)
-    if (nsplit > SWA_MAX_SPLIT_PACK) nsplit = SWA_MAX_SPLIT_PACK;
+    nsplit = swa_pack_nsplit(a);
   } else {
+    const int max_tiles = swa_max_tiles(a);
     nsplit = swa_base_nsplit(a->B, a->T, a->Hq);
     if (nsplit > max_tiles / 4) nsplit = max_tiles / 4;
-    if (nsplit > SWA_MAX_SPLIT) nsplit = SWA_MAX_SPLIT;
   }
   if (nsplit < 1) nsplit = 1;
 
   SwaParams p = swa_params(a, nsplit);
-  if (nsplit > 1) {
-    const size_t n_o = (size_t)a->B * nsplit * a->T * a->Hq * SWA_D;
-    const size_t need = (n_o + (size_t)a->B * nsplit * a->T * a->Hq * 2) * sizeof(float);
-    IVL_REQUIRE(a->workspace != nullptr && a->workspace_bytes >= need, IVL_ERR_WORKSPACE,
-                "ivl_swa_fwd: workspace %zu bytes < required %zu (nsplit=%d)", a->workspace_bytes, need, nsplit);
-    p.part_o = (float*)a->workspace;
-    p.part_ml = p.part_o + n_o;
-  }
+  if (nsplit > 1)
+    if (const int rc = swa_carve_partials(a, fn, p); rc != IVL_OK) return rc;
   const int rows = pack ? a->T * G : a->T;
-  const int qg = pack ? 1 : swa_qg(a->B, a->T, a->Hq);
   const bool prefill = !pack && a->T > SWA_QT;
   hipStream_t st = (hipStream_t)stream;
   // Fused M-RoPE of a prefill call: with split KV every split of a q-tile would rotate the same query rows, and in a long call
@@ -998,71 +1056,39 @@ extern "C" int ivl_swa_fwd(const ivl_swa_args* a, void* stream) {
     // rounded up to 16 bytes: the pre-pass, the attention kernel and the ring append move q_rot / k_rot as 16-byte vectors
     // (B * nsplit * T * Hq * 130 floats is only 8-byte aligned for an odd row count; the +256 slack of
     // ivl_swa_workspace_bytes covers the padding)
-    const size_t n_part = nsplit > 1 ? (((size_t)a->B * nsplit * a->T * a->Hq * (SWA_D + 2)) * sizeof(float) + 15) & ~(size_t)15 : 0;
+    const size_t n_part = nsplit > 1 ? (swa_partials_bytes(p) + 15) & ~(size_t)15 : 0;
     const size_t n_q = (size_t)a->B * a->T * a->Hq * SWA_D, n_k = (size_t)a->B * a->T * a->Hkv * SWA_D;
     IVL_REQUIRE(a->workspace != nullptr && a->workspace_bytes >= n_part + (n_q + n_k) * sizeof(bf16_t), IVL_ERR_WORKSPACE,
                 "ivl_swa_fwd: workspace %zu bytes < required %zu (rope pre-pass)", a->workspace_bytes, n_part + (n_q + n_k) * sizeof(bf16_t));
     bf16_t* q_rot = (bf16_t*)((unsigned char*)a->workspace + n_part);
     bf16_t* k_rot = q_rot + n_q;
-    const long long items = (long long)a->B * a->T * (a->Hq + a->Hkv) * 8;
-    long long gb = (items + 255) / 256;
-    if (gb > 2048) gb = 2048;
-    hipLaunchKernelGGL(swa_rope_prepass_kernel, dim3((int)gb), dim3(256), 0, st, p.q, p.q_sb, p.q_st, p.q_sh, p.k_new, p.kn_sb, p.kn_st,
-                       p.kn_sh, q_rot, k_rot, a->B, a->T, a->Hq, a->Hkv, p.rcos, p.rsin, p.rs0, p.rs1);
-    int rc0 = check_launch("ivl_swa_fwd(rope pre-pass)");
-    if (rc0 != IVL_OK) return rc0;
+    hipLaunchKernelGGL(swa_rope_prepass_kernel, dim3(blocks256((long long)a->B * a->T * (a->Hq + a->Hkv) * 8, 2048)), dim3(256), 0, st, p.q,
+                       p.q_sb, p.q_st, p.q_sh, p.k_new, p.kn_sb, p.kn_st, p.kn_sh, q_rot, k_rot, a->B, a->T, a->Hq, a->Hkv, p.rcos, p.rsin,
+                       p.rs0, p.rs1);
+    if (const int rc = check_launch("ivl_swa_fwd(rope pre-pass)"); rc != IVL_OK) return rc;
     p.q = q_rot; p.q_sb = (long long)a->T * a->Hq * SWA_D; p.q_st = (long long)a->Hq * SWA_D; p.q_sh = SWA_D;
     p.k_new = k_rot; p.kn_sb = (long long)a->T * a->Hkv * SWA_D; p.kn_st = (long long)a->Hkv * SWA_D; p.kn_sh = SWA_D;
     p.rcos = nullptr; p.rsin = nullptr;
   }
-  p.n_qtiles = prefill ? (rows + PF_QT - 1) / PF_QT : (rows + SWA_QT * qg - 1) / (SWA_QT * qg);
+  p.n_qtiles = prefill ? (rows + PF_QT - 1) / PF_QT : (rows + SWA_QT - 1) / SWA_QT;
   dim3 grid(p.n_qtiles * (pack ? a->Hkv : a->Hq) * a->B * nsplit);
   if (prefill) hipLaunchKernelGGL(swa_prefill_kernel, grid, dim3(P8_THREADS), 0, st, p.pos_dev, p);
   else if (pack && a->mma_dtype == IVL_FP8_E4M3)
     hipLaunchKernelGGL(swa_decode_fp8_kernel, dim3(a->Hkv * a->B * nsplit), dim3(256), 0, st, p.pos_dev, p);
   else if (pack) hipLaunchKernelGGL((swa_fwd_kernel<true, 1>), grid, dim3(256), 0, st, p.pos_dev, p);
   else hipLaunchKernelGGL((swa_fwd_kernel<false, 1>), grid, dim3(256), 0, st, p.pos_dev, p);
-  int rc = check_launch("ivl_swa_fwd");
-  if (rc != IVL_OK) return rc;
-  AppendArgs ap;
-  ap.first_block = -1;
-  int append_blocks = 0;
-  if (a->append_new) append_blocks = swa_append_args(a, p, ap);
-  if (nsplit > 1) {
-    const long long nrows = (long long)a->B * a->T * a->Hq;
-    long long gb = (nrows * 64 + 255) / 256;
-    if (gb > 4096) gb = 4096;
-    if (append_blocks > 0) ap.first_block = (int)gb;
-    const dim3 cg((int)gb + append_blocks);
-    if (nsplit > 16) {
-      long long wb = nrows > 4096 ? 4096 : nrows;                 // one workgroup per row
-      if (append_blocks > 0) ap.first_block = (int)wb;
-      hipLaunchKernelGGL(swa_combine_wide_kernel, dim3((int)wb + append_blocks), dim3(256), 0, st, p.part_o, p.part_ml, p.o, a->B,
-                         a->T * a->Hq, nsplit, ap);
-    }
-    else if (prefill && nsplit <= 4) hipLaunchKernelGGL((swa_combine_kernel<4, true>), cg, dim3(256), 0, st, p.part_o, p.part_ml, p.o, a->B, a->T * a->Hq, nsplit, ap);
-    else if (prefill && nsplit <= 8) hipLaunchKernelGGL((swa_combine_kernel<8, true>), cg, dim3(256), 0, st, p.part_o, p.part_ml, p.o, a->B, a->T * a->Hq, nsplit, ap);
-    else if (prefill) hipLaunchKernelGGL((swa_combine_kernel<16, true>), cg, dim3(256), 0, st, p.part_o, p.part_ml, p.o, a->B, a->T * a->Hq, nsplit, ap);
-    else if (nsplit <= 4) hipLaunchKernelGGL((swa_combine_kernel<4, false>), cg, dim3(256), 0, st, p.part_o, p.part_ml, p.o, a->B, a->T * a->Hq, nsplit, ap);
-    else if (nsplit <= 8) hipLaunchKernelGGL((swa_combine_kernel<8, false>), cg, dim3(256), 0, st, p.part_o, p.part_ml, p.o, a->B, a->T * a->Hq, nsplit, ap);
-    else hipLaunchKernelGGL((swa_combine_kernel<16, false>), cg, dim3(256), 0, st, p.part_o, p.part_ml, p.o, a->B, a->T * a->Hq, nsplit, ap);
-    rc = check_launch("ivl_swa_fwd(combine)");
-  } else if (append_blocks > 0) {
-    ap.first_block = 0;
-    hipLaunchKernelGGL(swa_cache_append_kernel, dim3(append_blocks), dim3(256), 0, st, ap);
-    rc = check_launch("ivl_swa_fwd(append)");
-  }
-  return rc;
+  if (const int rc = check_launch(fn); rc != IVL_OK) return rc;
+  return swa_combine_append(p, false, prefill, a->append_new != 0, st);
 }
 
 extern "C" int ivl_swa_decode_rows_fwd(const ivl_swa_args* a, const int64_t* pos_rows, void* stream) {
-  IVL_REQUIRE(a != nullptr, IVL_ERR_INVALID_ARG, "ivl_swa_decode_rows_fwd: NULL args");
-  IVL_REQUIRE(pos_rows != nullptr, IVL_ERR_INVALID_ARG, "ivl_swa_decode_rows_fwd: NULL pos_rows");
-  IVL_REQUIRE(a->q && a->k_new && a->v_new && a->o, IVL_ERR_INVALID_ARG, "ivl_swa_decode_rows_fwd: NULL q/k_new/v_new/o");
+  static const char fn[] = "ivl_swa_decode_rows_fwd";
+  // (a NULL struct is refused first, by the shared rule behind this one)
+  IVL_REQUIRE(a == nullptr || pos_rows != nullptr, IVL_ERR_INVALID_ARG, "ivl_swa_decode_rows_fwd: NULL pos_rows");
+  if (const int rc = swa_check_pointers(a, fn); rc != IVL_OK) return rc;
   IVL_REQUIRE(a->B > 0 && a->T > 0 && a->Hq > 0 && a->Hkv > 0, IVL_ERR_INVALID_ARG,
               "ivl_swa_decode_rows_fwd: bad sizes B=%d T=%d Hq=%d Hkv=%d", a->B, a->T, a->Hq, a->Hkv);
-  IVL_REQUIRE(a->d == SWA_D, IVL_ERR_UNSUPPORTED, "ivl_swa_decode_rows_fwd: head_dim %d unsupported (built for 128)", a->d);
-  IVL_REQUIRE(a->Hq % a->Hkv == 0, IVL_ERR_INVALID_ARG, "ivl_swa_decode_rows_fwd: Hq=%d not a multiple of Hkv=%d", a->Hq, a->Hkv);
+  if (const int rc = swa_check_heads(a, fn); rc != IVL_OK) return rc;
   IVL_REQUIRE(a->cache_capacity > 0 && a->k_cache && a->v_cache, IVL_ERR_UNSUPPORTED,
               "ivl_swa_decode_rows_fwd: needs a ring cache (cache_capacity=%d)", a->cache_capacity);
   IVL_REQUIRE(a->T_new == a->T, IVL_ERR_UNSUPPORTED, "ivl_swa_decode_rows_fwd: needs T_new == T (got %d, %d)", a->T_new, a->T);
@@ -1071,51 +1097,20 @@ extern "C" int ivl_swa_decode_rows_fwd(const ivl_swa_args* a, const int64_t* pos
               "ivl_swa_decode_rows_fwd: packed decode rows only: T * Hq/Hkv = %lld > %d", (long long)a->T * G, SWA_QT);
   IVL_REQUIRE(a->mma_dtype == IVL_BF16, IVL_ERR_UNSUPPORTED, "ivl_swa_decode_rows_fwd: mma_dtype must be IVL_BF16 (got %d)",
               a->mma_dtype);
-  IVL_REQUIRE((a->rope_cos == nullptr) == (a->rope_sin == nullptr), IVL_ERR_INVALID_ARG,
-              "ivl_swa_decode_rows_fwd: rope_cos and rope_sin go together");
-  IVL_REQUIRE(a->rope_cos == nullptr || (a->rope_s0 % 8 == 0 && a->rope_s1 % 8 == 0 && a->rope_s0 >= 0 && a->rope_s1 >= 0 &&
-                                          a->rope_s0 + a->rope_s1 <= 64),
-              IVL_ERR_UNSUPPORTED, "ivl_swa_decode_rows_fwd: mrope sections must be multiples of 8 (got %d, %d)", a->rope_s0, a->rope_s1);
-  IVL_REQUIRE((long long)a->T_new * a->kn_st < (1LL << 32) && a->kn_st >= 0, IVL_ERR_UNSUPPORTED,
-              "ivl_swa_decode_rows_fwd: T_new * kn_st = %lld elements exceeds the 32-bit row addressing of the kernel",
-              (long long)a->T_new * a->kn_st);
-  // the same split count as ivl_swa_fwd's packed decode step (capacity and window only): row b of this call and a B = 1
-  // ivl_swa_fwd at pos = pos_rows[b] run the same workgroups and the same combine, bit for bit
-  int nsplit = swa_max_tiles(a);
-  if (nsplit > SWA_MAX_SPLIT_PACK) nsplit = SWA_MAX_SPLIT_PACK;
+  if (const int rc = swa_check_rope_tables(a, fn); rc != IVL_OK) return rc;
+  IVL_REQUIRE(a->rope_cos == nullptr || swa_rope_sections_ok(a->rope_s0, a->rope_s1), IVL_ERR_UNSUPPORTED,
+              "ivl_swa_decode_rows_fwd: mrope sections must be multiples of 8 (got %d, %d)", a->rope_s0, a->rope_s1);
+  if (const int rc = swa_check_key_rows(a, fn, ""); rc != IVL_OK) return rc;
+  const int nsplit = swa_pack_nsplit(a);
   IVL_REQUIRE(nsplit > 1, IVL_ERR_UNSUPPORTED, "ivl_swa_decode_rows_fwd: single-split shape (window %d)", a->window);
   SwaParams p = swa_params(a, nsplit);
   p.pos = 0; p.pos_dev = (const long long*)pos_rows;
-  const size_t n_o = (size_t)a->B * nsplit * a->T * a->Hq * SWA_D;
-  const size_t need = (n_o + (size_t)a->B * nsplit * a->T * a->Hq * 2) * sizeof(float);
-  IVL_REQUIRE(a->workspace != nullptr && a->workspace_bytes >= need, IVL_ERR_WORKSPACE,
-              "ivl_swa_decode_rows_fwd: workspace %zu bytes < required %zu (nsplit=%d)", a->workspace_bytes, need, nsplit);
-  p.part_o = (float*)a->workspace;
-  p.part_ml = p.part_o + n_o;
+  if (const int rc = swa_carve_partials(a, fn, p); rc != IVL_OK) return rc;
   p.n_qtiles = 1;
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(swa_rows_decode_kernel, dim3(a->Hkv * a->B * nsplit), dim3(256), 0, st, p.pos_dev, p);
-  int rc = check_launch("ivl_swa_decode_rows_fwd");
-  if (rc != IVL_OK) return rc;
-  AppendArgs ap;
-  ap.first_block = -1;
-  const int append_blocks = a->append_new ? swa_append_args(a, p, ap) : 0;
-  const long long nrows = (long long)a->B * a->T * a->Hq;
-  if (nsplit > 16) {
-    const long long wb = nrows > 4096 ? 4096 : nrows;             // one workgroup per row
-    if (append_blocks > 0) ap.first_block = (int)wb;
-    hipLaunchKernelGGL(swa_rows_combine_wide_kernel, dim3((int)wb + append_blocks), dim3(256), 0, st, p.part_o, p.part_ml, p.o, a->B,
-                       a->T * a->Hq, nsplit, ap);
-  } else {
-    long long gb = (nrows * 64 + 255) / 256;
-    if (gb > 4096) gb = 4096;
-    if (append_blocks > 0) ap.first_block = (int)gb;
-    const dim3 cg((int)gb + append_blocks);
-    if (nsplit <= 4) hipLaunchKernelGGL((swa_rows_combine_kernel<4>), cg, dim3(256), 0, st, p.part_o, p.part_ml, p.o, a->B, a->T * a->Hq, nsplit, ap);
-    else if (nsplit <= 8) hipLaunchKernelGGL((swa_rows_combine_kernel<8>), cg, dim3(256), 0, st, p.part_o, p.part_ml, p.o, a->B, a->T * a->Hq, nsplit, ap);
-    else hipLaunchKernelGGL((swa_rows_combine_kernel<16>), cg, dim3(256), 0, st, p.part_o, p.part_ml, p.o, a->B, a->T * a->Hq, nsplit, ap);
-  }
-  return check_launch("ivl_swa_decode_rows_fwd(combine)");
+  if (const int rc = check_launch(fn); rc != IVL_OK) return rc;
+  return swa_combine_append(p, true, false, a->append_new != 0, st);
 }
 
 extern "C" int ivl_swa_cache_append(const void* k_new, const void* v_new, int64_t kn_sb, int64_t kn_st, int64_t kn_sh,
@@ -1127,18 +1122,13 @@ extern "C" int ivl_swa_cache_append(const void* k_new, const void* v_new, int64_
   IVL_REQUIRE(d == SWA_D, IVL_ERR_UNSUPPORTED, "ivl_swa_cache_append: head_dim %d unsupported", d);
   IVL_REQUIRE(pos_dev != nullptr || pos >= 0, IVL_ERR_INVALID_ARG, "ivl_swa_cache_append: negative pos");
   IVL_REQUIRE((rope_cos == nullptr) == (rope_sin == nullptr), IVL_ERR_INVALID_ARG, "ivl_swa_cache_append: rope_cos and rope_sin go together");
-  IVL_REQUIRE(rope_cos == nullptr || (rope_s0 % 8 == 0 && rope_s1 % 8 == 0 && rope_s0 >= 0 && rope_s1 >= 0 && rope_s0 + rope_s1 <= 64),
-              IVL_ERR_UNSUPPORTED, "ivl_swa_cache_append: mrope sections must be multiples of 8 (got %d, %d)", rope_s0, rope_s1);
-  const int nt = T > cache_capacity ? cache_capacity : T;
-  long long items = (long long)B * nt * Hkv * (SWA_D / 8);
-  long long gb = (items + 255) / 256;
-  if (gb > 2048) gb = 2048;
+  IVL_REQUIRE(rope_cos == nullptr || swa_rope_sections_ok(rope_s0, rope_s1), IVL_ERR_UNSUPPORTED,
+              "ivl_swa_cache_append: mrope sections must be multiples of 8 (got %d, %d)", rope_s0, rope_s1);
   AppendArgs ap;
-  ap.k_new = (const bf16_t*)k_new; ap.v_new = (const bf16_t*)v_new; ap.kn_sb = kn_sb; ap.kn_st = kn_st; ap.kn_sh = kn_sh;
-  ap.vn_sb = kn_sb; ap.vn_st = kn_st; ap.vn_sh = kn_sh;
-  ap.k_cache = (bf16_t*)k_cache; ap.v_cache = (bf16_t*)v_cache; ap.B = B; ap.T = T; ap.Hkv = Hkv; ap.C = cache_capacity;
-  ap.pos = (long long)pos; ap.pos_dev = (const long long*)pos_dev;
-  ap.rcos = (const bf16_t*)rope_cos; ap.rsin = (const bf16_t*)rope_sin; ap.rs0 = rope_s0; ap.rs1 = rope_s1; ap.first_block = 0;
-  hipLaunchKernelGGL(swa_cache_append_kernel, dim3((int)gb), dim3(256), 0, (hipStream_t)stream, ap);
+  const int blocks = swa_append_args(ap, (const bf16_t*)k_new, kn_sb, kn_st, kn_sh, (const bf16_t*)v_new, kn_sb, kn_st, kn_sh, k_cache, v_cache, B, T,
+                                     Hkv, cache_capacity, pos, (const long long*)pos_dev, (const bf16_t*)rope_cos, (const bf16_t*)rope_sin,
+                                     rope_s0, rope_s1);
+  ap.first_block = 0;
+  hipLaunchKernelGGL(swa_cache_append_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, ap);
   return check_launch("ivl_swa_cache_append");
 }

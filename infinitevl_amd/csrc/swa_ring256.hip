@@ -18,6 +18,9 @@
 //      g ^ (r & 3)), 32 one-KB pieces per tile issued by the compute waves 0-3 (eight each) between their row maximum and their
 //      exponentials, a 4-stage ring filled three tiles ahead, one barrier per tile; waves 4-7 (the SIMD partners of 0-3) request
 //      nothing and run their phases rotated by one (softmax(t), PV(t), QK^T(t + 1)); no static priority (it costs 3-35 x here).
+//      The forms that were measured and dropped (every wave requesting four pieces, the rotated half requesting, requests behind the
+//      exponentials or split around them, static priority on either half, no rotation) are recorded in
+//      profiles/r06_swa_ring256_ab.txt.
 #include "ivl_common.h"
 #include "swa_shared.h"
 #include <type_traits>
@@ -30,13 +33,6 @@ constexpr int R2_STAGE = 2 * R2_KT * 256;    // K image + V image = 32 KB
 constexpr int R2_NST = 4;                    // stages
 constexpr int R2_AHEAD = 3;                  // tiles requested ahead
 constexpr int R2_LDS = R2_NST * R2_STAGE;    // 128 KB
-#ifndef R2_DMA_BY
-#define R2_DMA_BY 2                          // who requests the tiles of the loop: 0 every wave four pieces per tile; 1 / 2 only waves
-                                             // 4-7 / 0-3, eight each (2 = default: -3 ... -6 % against 0 on three boxes; 1: +1.5 %)
-#endif
-#ifndef R2_DMA_AT
-#define R2_DMA_AT 0                          // where the four DMA pieces of a tile are issued: 0 behind the row maximum, 1 behind the
-#endif                                       // exponentials, 2 two and two
 constexpr int R2_PAD_ROWS = 64;              // zero rows behind the linear keys (the last tile of the last q-tile ends 1 key late)
 
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
@@ -175,18 +171,18 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                      : "=&s"(keep) : "v"(isv ? v_src : k_src), "s"(dst), "s"(base) : "memory");
       }
   };
-#if R2_DMA_BY
-  // role split: only one half of the waves (R2_DMA_BY 1: the rotated half 4-7, 2: waves 0-3) requests the tiles of the loop, eight pieces
-  // per wave and tile: wave w' = wave & 3 moves chunks w', w' + 4, w' + 8, w' + 12 of both images
-  const bool dma_role = R2_DMA_BY == 1 ? wave >= 4 : wave < 4;       // (3: as 2, the K pieces behind the row maximum, the V pieces behind the exponentials)
+  // role split: only waves 0-3 (the half that is NOT rotated) request the tiles of the loop, eight pieces per wave and tile: wave w
+  // moves chunks w, w + 4, w + 8, w + 12 of both images.  Measured -3 ... -6 % per launch on three boxes against every wave
+  // requesting four pieces; the rotated half 4-7 as the requester instead: +1.5 %.
+  const bool dma_role = wave < 4;
   const unsigned int k_src8 = (unsigned int)(r_in * 256 + ((pp ^ ((4 * (wave & 3) + r_in) & 15)) << 4));
-  auto dma_tile8 = [&](int jt, int v0 = 0, int v1 = 2) __attribute__((always_inline)) {
+  auto dma_tile8 = [&](int jt) __attribute__((always_inline)) {
     const unsigned int dst0 = lds_base + (unsigned int)(jt & (R2_NST - 1)) * R2_STAGE + 1024u * (wave & 3);
     const long long wofs = (long long)jt * (R2_KT * 256) + ((wave & 3) - wave) * 1024;      // kbase / vbase carry wave * 1024
 #pragma unroll
     for (int j = 0; j < 4; ++j)
 #pragma unroll
-      for (int isv = v0; isv < v1; ++isv) {
+      for (int isv = 0; isv < 2; ++isv) {
         const unsigned char* base = uniform_ptr((isv ? vbase : kbase) + wofs + j * 4096);
         const unsigned int dst = __builtin_amdgcn_readfirstlane(dst0 + (isv ? 16384u : 0u) + 4096u * j);
         unsigned int keep;
@@ -194,7 +190,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                      : "=&s"(keep) : "v"(isv ? v_src : k_src8), "s"(dst), "s"(base) : "memory");
       }
   };
-#endif
   dma_tile(0, 0, 2);
   dma_tile(1, 0, 2);
   dma_tile(2, 0, 2);
@@ -353,64 +348,27 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       smax(mask_tag, t);
     }
     const bool more = !MASK || t + R2_AHEAD < NT;
-#if R2_DMA_BY == 3
-    if (more && dma_role) dma_tile8(t + R2_AHEAD, 0, 1);
-#elif R2_DMA_BY
-    if (more && dma_role) dma_tile8(t + R2_AHEAD);
-#elif !defined(R2_NO_DMA) && R2_DMA_AT == 0
-    if (more) dma_tile(t + R2_AHEAD, 0, 2);
-#elif !defined(R2_NO_DMA) && R2_DMA_AT == 2
-    if (more) dma_tile(t + R2_AHEAD, 0, 1);
-#endif
+    if (more && dma_role) dma_tile8(t + R2_AHEAD);      // behind the row maximum, in front of the exponentials
     if (on) sexp(mask_tag);
-#if R2_DMA_BY == 3
-    if (more && dma_role) dma_tile8(t + R2_AHEAD, 1, 2);
-#endif
-#if !defined(R2_NO_DMA) && R2_DMA_AT == 1
-    if (more) dma_tile(t + R2_AHEAD, 0, 2);
-#elif !defined(R2_NO_DMA) && R2_DMA_AT == 2
-    if (more) dma_tile(t + R2_AHEAD, 1, 2);
-#endif
     if (on) pv(t);
     if (ROT && t + 1 < NT && vis(t + 1)) qk(t + 1);
-#if R2_DMA_BY
-    if (more && dma_role) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+    if (more && dma_role) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");      // the eight newest requests may fly
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#else
-    if (more) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
     tile_barrier();
   };
   auto run = [&](auto rot_tag) __attribute__((always_inline)) {
     constexpr bool ROT = decltype(rot_tag)::value;
-    if (ROT) {
-#ifdef R2_PRIO      // static priority 1 for the rotated half (what swa_prefill_kernel does) makes THIS kernel 35x slower (5.57 ms
-      __builtin_amdgcn_s_setprio(1);      // vs 157 us per launch, same box): the prio-0 waves also issue the LDS-DMA the others wait for
-#endif
-      if (vis(0)) qk(0);
-    }
-#ifdef R2_PRIO0
-    if (!ROT) __builtin_amdgcn_s_setprio(1);
-#endif
+    // no s_setprio: static priority 1 for the rotated half (what swa_prefill_kernel does) made THIS kernel 35x slower (5.57 ms vs
+    // 157 us per launch, same box) -- the priority-0 waves also issue the LDS-DMA the others wait for
+    if (ROT && vis(0)) qk(0);
     const int n_lo = NT < 4 ? NT : 4;
     int t = 0;
     for (; t < n_lo; ++t) body(rot_tag, std::true_type{}, t);
     for (; t < j_hi; ++t) body(rot_tag, std::false_type{}, t);
     for (; t < NT; ++t) body(rot_tag, std::true_type{}, t);
-#ifdef R2_PRIO
-    if (ROT) __builtin_amdgcn_s_setprio(0);
-#endif
-#ifdef R2_PRIO0
-    if (!ROT) __builtin_amdgcn_s_setprio(0);
-#endif
   };
-#ifdef R2_NO_ROT
-  run(std::false_type{});
-#else
   if (wave < 4) run(std::false_type{});
   else run(std::true_type{});
-#endif
 
   // ---- normalise and store O [B,T,Hq,128]: lane (row l31, half hi5) owns d = 32 mt + 8 qd + 4 hi5 .. +3
   {
@@ -471,9 +429,7 @@ int swa_ring256_launch(const ivl_swa_args* a, hipStream_t st) {
   la.rcos = (const bf16_t*)a->rope_cos; la.rsin = (const bf16_t*)a->rope_sin; la.rs0 = a->rope_s0; la.rs1 = a->rope_s1;
   la.append = a->append_new ? 1 : 0;
   const long long items = ((long long)a->B * a->T * (a->Hkv + (q_rot ? a->Hq : 0)) + (long long)a->B * a->Hkv * (a->cache_capacity + R2_PAD_ROWS)) * 8;
-  long long gb = (items + 255) / 256;
-  if (gb > 4096) gb = 4096;
-  hipLaunchKernelGGL(swa_linearize_kernel, dim3((int)gb), dim3(256), 0, st, la);
+  hipLaunchKernelGGL(swa_linearize_kernel, dim3(blocks256(items, 4096)), dim3(256), 0, st, la);
   int rc = check_launch("ivl_swa_fwd(linearize pre-pass)");
   if (rc != IVL_OK) return rc;
   Ring256Params p;

@@ -25,6 +25,13 @@ __device__ __forceinline__ mfma_bf16x8 as_mfma(u32x4 v) {
   return r;
 }
 
+// host side (the launchers of swa.hip and swa_ring256.hip): the grid of a grid-stride kernel, blocks of 256 threads for n work
+// items, at most `cap` of them
+inline int blocks256(long long n, int cap) {
+  const long long blocks = (n + 255) / 256;
+  return (int)(blocks > cap ? cap : blocks);
+}
+
 // single-instruction max helpers (a plain fmaxf on MFMA results draws a canonicalising v_max per operand)
 __device__ __forceinline__ float vmax3(float a, float b, float c) {
   float r;
