@@ -89,6 +89,31 @@ __device__ __forceinline__ float wave_sum(float v) {
 // v_rcp_f32 (1 ulp) instead of an IEEE division (~10 instructions): every SiLU / swish gate of the package goes through
 // here (the results are rounded to bf16 right after), so all paths stay bit-identical to each other
 __device__ __forceinline__ float sigmoidf_(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
+// a * sigmoid(a) of the SwiGLU paths (ivl_silu_mul_fwd and the GEMM epilogues that equal it bit for bit).  Below a = -87.3 the
+// reciprocal of 1 + e^-a is an fp32 subnormal, which v_rcp_f32 returns as 0 (and e^-a itself overflows at -88.7), although
+// bf16(silu(a)) is a normal number down to a = -91.5 (-5.3e-37 at a = -88) and a subnormal one down to -97.  Down there
+// 1 + e^-a = e^-a to one part in 2^115, so silu(a) = a e^a, evaluated as (a 2^(a log2 e + 64)) 2^-64 to keep the exponential and
+// the product out of the subnormal range.
+// N values share ONE test and branch (a branch per element cost the 256-row gate|up kernel 3 %): as bit patterns, the floats
+// below -80 are the unsigned integers above that of -80.
+__device__ __forceinline__ float silu_deep_(float a) {
+  return ldexpf(a * __builtin_amdgcn_exp2f(fmaf(a, 1.44269504088896341f, 64.f)), -64);
+}
+template <int N_>
+__device__ __forceinline__ void siluf_n_(const float (&a)[N_], float (&o)[N_]) {
+  unsigned int top = 0u;
+#pragma unroll
+  for (int i = 0; i < N_; ++i) {
+    o[i] = a[i] * sigmoidf_(a[i]);
+    const unsigned int bits = __float_as_uint(a[i]);
+    top = bits > top ? bits : top;
+  }
+  if (__builtin_expect(top > 0xC2A00000u, 0)) {
+#pragma unroll
+    for (int i = 0; i < N_; ++i)
+      if (a[i] < -80.f) o[i] = silu_deep_(a[i]);
+  }
+}
 // beta = sigmoid(b) (std:1293) keeps the IEEE division and expf: it is H values per token, and a 1-ulp fp32 difference can
 // flip the bf16 rounding against the reference's `b.sigmoid()`
 __device__ __forceinline__ float sigmoid_exact_(float x) { return 1.0f / (1.0f + expf(-x)); }

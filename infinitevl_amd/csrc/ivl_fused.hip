@@ -286,8 +286,9 @@ __global__ __launch_bounds__(256) void silu_mul_kernel(const bf16_t* __restrict_
     float a[8], b[8], o[8];
     unpack8(*(const u32x4*)(gu + r * 2 * I + v * 8), a);
     unpack8(*(const u32x4*)(gu + r * 2 * I + I + v * 8), b);
+    siluf_n_(a, o);
 #pragma unroll
-    for (int i = 0; i < 8; ++i) o[i] = bf_round(a[i] * sigmoidf_(a[i])) * b[i];
+    for (int i = 0; i < 8; ++i) o[i] = bf_round(o[i]) * b[i];
     if (write_through) store_out16(y + r * I + v * 8, pack8(o));
     else *(u32x4*)(y + r * I + v * 8) = pack8(o);
   }

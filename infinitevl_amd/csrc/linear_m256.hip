@@ -182,12 +182,12 @@ __global__ __launch_bounds__(ROWS * 2) void linear_m256_kernel(const bf16_t* __r
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
         const int row = r0 + 32 * wave + 16 * i + (lane & 15);
-        float o[4];
+        float g[4], o[4];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float g = bf_round(acc[j][i][r] + bg[r]), u = bf_round(acc[j + C::NT / 2][i][r] + bu[r]);
-          o[r] = bf_round(g * sigmoidf_(g)) * u;
-        }
+        for (int r = 0; r < 4; ++r) g[r] = bf_round(acc[j][i][r] + bg[r]);
+        siluf_n_(g, o);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) o[r] = bf_round(o[r]) * bf_round(acc[j + C::NT / 2][i][r] + bu[r]);
         if (row < M && col < N) store_out8(y + (size_t)row * N + col, u32x2{pack2bf(o[0], o[1]), pack2bf(o[2], o[3])});
       }
     }

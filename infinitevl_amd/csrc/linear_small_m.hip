@@ -168,7 +168,10 @@ __global__ __launch_bounds__(256, (NORM && M == 1) ? 3 : 1) void linear_small_m_
         if (GLU) {
           const float gt = bf_round(s + (bias != nullptr ? bf2f(bias[row0 + r]) : 0.f));          // gate_proj output
           const float up = bf_round(s2 + (bias != nullptr ? bf2f(bias[N + row0 + r]) : 0.f));     // up_proj output
-          y[(size_t)m * N + row0 + r] = f2bf(bf_round(gt * sigmoidf_(gt)) * up);                  // = silu_mul_kernel
+          const float g1[1] = {gt};
+          float s1[1];
+          siluf_n_(g1, s1);
+          y[(size_t)m * N + row0 + r] = f2bf(bf_round(s1[0]) * up);                              // = silu_mul_kernel
         } else {
           y[(size_t)m * N + row0 + r] = f2bf(s + (bias != nullptr ? bf2f(bias[row0 + r]) : 0.f));
         }

@@ -831,24 +831,45 @@ def rmsnorm_swish_gate_strided(x: torch.Tensor, gate_base: torch.Tensor, gate_ld
                                eps: float) -> torch.Tensor:
     """Gated RMSNorm with the gate read in place from a fused projection buffer.  x [B,T,H,256] bf16
     contiguous; gate_base = view whose data_ptr is the gate block's first element, row stride gate_ld."""
-    _need_gpu(x, gate_base)
+    _need_gpu(x, gate_base, weight)
+    if x.dim() != 4 or x.dtype != torch.bfloat16 or gate_base.dtype != torch.bfloat16:
+        raise ValueError(f"rmsnorm_swish_gate_strided: x must be bf16 [B,T,H,256] and the gate bf16; got {x.dtype} {tuple(x.shape)}, "
+                         f"{gate_base.dtype}")
     B, T, H, N = x.shape
+    # the kernel reads 16-byte vectors at gate + token * gate_ld + head * 256: the view's rows must be the buffer's rows
+    rows_ok, step = gate_base.stride(-1) == 1, gate_ld
+    for i in range(gate_base.dim() - 2, -1, -1):                   # [.., T, cols]: token t of batch row b at (b * T + t) * gate_ld
+        rows_ok = rows_ok and (gate_base.shape[i] == 1 or gate_base.stride(i) == step)
+        step *= gate_base.shape[i]
+    if gate_ld % 8 or gate_base.shape[-1] < H * N or gate_base.shape[-1] > gate_ld or gate_base.data_ptr() % 16 or not rows_ok:
+        raise ValueError(f"rmsnorm_swish_gate_strided: gate view (shape {tuple(gate_base.shape)}, strides {tuple(gate_base.stride())}, "
+                         f"gate_ld={gate_ld}) must start 16-byte aligned, hold the H*{N} = {H * N} gate columns of a token within "
+                         f"one row of the buffer, and have unit column stride and a row stride gate_ld that is a multiple of 8")
+    if weight.numel() != N:
+        raise ValueError(f"rmsnorm_swish_gate_strided: weight has {weight.numel()} elements, rows have {N}")
+    x = x.contiguous()
+    w = weight.detach().to(torch.bfloat16).contiguous()
     y = torch.empty_like(x)
-    _lib.check(_lib.load().ivl_rmsnorm_swish_gate_strided_fwd(_p(x), _p(gate_base), gate_ld, H, _p(weight), _p(y),
+    _lib.check(_lib.load().ivl_rmsnorm_swish_gate_strided_fwd(_p(x), _p(gate_base), gate_ld, H, _p(w), _p(y),
                                                               B * T * H, N, float(eps), _stream(x)))
     return y
 
 
 def add_rmsnorm(x: torch.Tensor, residual: Optional[torch.Tensor], weight: torch.Tensor, eps: float):
     """h = x + residual (bf16) ; y = RMSNorm(h) * weight, one launch.  Returns (y, h); with residual=None, h is x."""
-    _need_gpu(x, residual)
+    _need_gpu(x, residual, weight)
     if x.dtype != torch.bfloat16:
         raise ValueError("add_rmsnorm is built for bf16")
     N = x.shape[-1]
+    if weight.numel() != N:
+        raise ValueError(f"add_rmsnorm: weight has {weight.numel()} elements, rows have {N}")
+    if residual is not None and (residual.dtype != torch.bfloat16 or tuple(residual.shape) != tuple(x.shape)):
+        raise ValueError(f"add_rmsnorm: residual must be a bf16 tensor of x's shape {tuple(x.shape)}; got {residual.dtype} "
+                         f"{tuple(residual.shape)}")
     x = x.contiguous()
     y = torch.empty_like(x)
     h = torch.empty_like(x) if residual is not None else None
-    w = weight if weight.dtype == torch.bfloat16 else weight.to(torch.bfloat16)
+    w = weight.detach().to(torch.bfloat16).contiguous()
     _lib.check(_lib.load().ivl_add_rmsnorm_fwd(_p(x), _p(residual.contiguous()) if residual is not None else None,
                                                _p(w), _p(y), _p(h), x.numel() // N, N, float(eps), _stream(x)))
     return y, (h if h is not None else x)
