@@ -404,6 +404,35 @@ IVL_API int ivl_norm_linear_small_m_fwd(const void* x, const void* residual, con
  * 1 <= M <= 256, K % 64 == 0 and K <= 16384, N % 4 == 0, x / W 16-byte aligned: else IVL_ERR_UNSUPPORTED / IVL_ERR_INVALID_ARG. */
 IVL_API int ivl_linear_m256_fwd(const void* x, const void* w, const void* bias, void* y, int M, int N, int K, int glu, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Next-token sampling over lm_head logits: temperature, top-k, top-p, one random stream per row, one launch.
+ * Replaces the logits warpers + multinomial of HF generate, which the reference drives with do_sample / temperature / top_p /
+ * top_k (src/llamafactory/api/chat.py:160-162, api/protocol.py:99-101, webui/runner.py:231-232,
+ * webui/components/chatbot.py:78-79).  Row s (a batch row or a decode slot) = the V bf16 logits at logits + s*ld.
+ *   1 a NaN logit counts as -inf; order = numeric order of the bf16 values; m = max x.
+ *   2 temperature[s] <= 0: token = the LOWEST index with x == m, n_kept = 1, prob = 1, counter[s] unchanged.
+ *   3 top-k (0 < top_k[s] < V): K = {i : x_i >= the k-th largest value} (ties at the threshold stay, TopKLogitsWarper); else all.
+ *   4 w_i = exp((x_i - m) / temperature), exactly 1 where x_i == m (also m = +-inf), 0 for x_i = -inf < m.  Evaluated as the
+ *     integer q_i = floor(exp2f((x_i - m) * (log2e / temperature)) * 2^40): a token more than 40 ln 2 = 27.7 nats (after the
+ *     temperature) below the maximum has weight 0 and is never drawn.
+ *   5 top-p (top_p[s] < 1): with A(v) = sum{w_i : i in K, x_i > v} / sum{w_i : i in K}, P = {i in K : A(x_i) < p}
+ *     (TopPLogitsWarper behind temperature and top-k: the top class always survives) -- except that tokens with EQUAL logits
+ *     are kept or dropped together, where HF's cut inside a tie follows its sort order; else P = K.
+ *   6 u64 = mix(mix(seed[s]) + (counter[s] + 1) * 0x9E3779B97F4A7C15) mod 2^64, mix = splitmix64's finaliser
+ *     (z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31);
+ *     token = the first i in P, in vocabulary order, whose inclusive sum of q over P exceeds floor(u64 * Z_P / 2^64);
+ *     then counter[s] += 1.
+ * All sums are integer adds: the token is a pure function of (x, temperature, top_k, top_p, seed, counter) -- the same bits on
+ * every run, eager or in a replayed graph, whichever row of a larger call the logits sit in.
+ * token[s * token_stride] int64 is written; n_kept [S] int32 (= |P|) and prob [S] fp32 (= q_token / Z_P) may be NULL.
+ * Any V >= 1 and ld >= V, any alignment (16-byte loads from the boundary at or below each row).  V >= 2^23: IVL_ERR_UNSUPPORTED.
+ * ------------------------------------------------------------------------------------------- */
+IVL_API int ivl_sample_rows_fwd(const void* logits, int64_t ld, int S, int V,
+                                const float* temperature, const int32_t* top_k, const float* top_p,
+                                const int64_t* seed, int64_t* counter,
+                                int64_t* token, int64_t token_stride,
+                                int32_t* n_kept, float* prob, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

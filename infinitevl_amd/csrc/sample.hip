@@ -1,0 +1,417 @@
+// Token sampling over the lm_head logits of a decode step: temperature, top-k and top-p per row, one launch, one workgroup per
+// row (a row = a batch row of GraphedDecode or a slot of GraphedMultiStreamDecode).  Serves the generation arguments the
+// reference hands to HF generate (src/llamafactory/api/chat.py:160-162, api/protocol.py:99-101, webui/runner.py:231-232,
+// webui/components/chatbot.py:78-79); the semantics are written out at ivl_sample_rows_fwd in include/ivl_hip.h.
+//
+// No sort: bf16 has 65,536 values, so the top-k and the top-p thresholds come EXACTLY from histograms of an order-preserving
+// 16-bit key -- a coarse level over the high 12 bits (4096 bins in LDS: real logits sit in a few binades, 8 bins each), then the 16
+// keys of the one boundary bin.  No float sums: a weight is the integer q = floor(2^(( x - m) log2e / tau) 2^40) (Q40; a token more
+// than 40 ln 2 = 27.7 nats below the maximum has weight 0), every histogram, sum and prefix is an integer add, so the token is the
+// same bits whatever the order the waves arrive in, eager or replayed, alone or beside other rows.  Z <= V 2^40: below 2^58 at the
+// model's V = 151936; the host refuses V >= 2^23, so every sum stays below 2^63.
+//
+// Passes over the row (304 KB at V = 151936, written by lm_head just before: L2 hits), only those the row's parameters need:
+//   1  maximum and its lowest index (+ coarse counts if top-k)      greedy rows end here
+//   2  top-k: counts of the 16 keys of the bin that holds the k-th largest value                -> t_k
+//   3  top-p: coarse masses of the keys >= t_k                                                  -> Z_K, boundary bin
+//   4  top-p: counts of the 16 keys of that bin (mass = count x weight)                         -> t_p
+//   5  kept count and mass per wave (a wave owns a contiguous index range)                      -> |P|, Z_P, target = hi64(u64 Z_P)
+//   6  the one wave whose range holds the target scans it again and walks the tile that holds it -> token
+// Rows are read in 16-byte tiles from the 16-byte boundary at or below the row start, whatever `ld` and the base: the (at most 7)
+// elements in front of and behind the row inside its first and last tile are masked out -- they lie in the same 16 bytes as row
+// elements, so the loads stay inside the caller's allocation granule.
+#include "ivl_common.h"
+
+namespace ivl {
+
+typedef unsigned long long u64;
+
+constexpr int SMP_THREADS = 1024;
+constexpr int SMP_WAVES = SMP_THREADS / 64;
+constexpr int SMP_BINS = 4096;                 // coarse level: key >> 4
+constexpr int SMP_SUB = 16;                    // keys per coarse bin
+constexpr unsigned SMP_KEY_NINF = 0x007Fu;     // key of -inf (and of NaN): the lowest key that occurs
+constexpr u64 SMP_ONE = 1ull << 40;            // weight of the maximum
+
+// bf16 bits -> a 16-bit key whose unsigned order is the numeric order; NaN counts as -inf, -0 as +0
+__device__ __forceinline__ unsigned smp_key(unsigned b) {
+  if ((b & 0x7FFFu) > 0x7F80u) b = 0xFF80u;
+  if (b == 0x8000u) b = 0u;
+  return (b & 0x8000u) ? (~b & 0xFFFFu) : (b | 0x8000u);
+}
+__device__ __forceinline__ float smp_key_value(unsigned k) {
+  const unsigned b = (k & 0x8000u) ? (k & 0x7FFFu) : (~k & 0xFFFFu);
+  return __uint_as_float(b << 16);
+}
+
+// Q40 weight of a key: 2^40 exactly at the maximum (also m = +-inf), 0 for -inf below it and below 2^-40
+__device__ __forceinline__ u64 smp_weight(unsigned key, unsigned mkey, float xm, float c) {
+  if (key == mkey) return SMP_ONE;
+  if (key <= SMP_KEY_NINF) return 0ull;
+  const float a = (smp_key_value(key) - xm) * c;
+  if (!(a > -41.f)) return 0ull;               // also a NaN (0 x inf at a temperature outside what the host admits)
+  return (u64)(__builtin_amdgcn_exp2f(a) * 0x1p40f);
+}
+
+struct SmpRow {
+  const u32x4* base;     // 16-byte boundary at or below the row start
+  long long nt;          // tiles of 8 elements
+  int off;               // row element 0 is element `off` of tile 0
+  int V;
+};
+
+// keys of tile j; returns the mask of the elements that belong to the row
+__device__ __forceinline__ unsigned smp_load(const SmpRow& r, long long j, unsigned (&key)[8]) {
+  const u32x4 v = r.base[j];
+  const unsigned w[4] = {v.x, v.y, v.z, v.w};
+  const long long i0 = j * 8 - r.off;
+  unsigned valid = 0u;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    key[e] = smp_key((w[e >> 1] >> ((e & 1) * 16)) & 0xFFFFu);
+    const long long i = i0 + e;
+    if (i >= 0 && i < r.V) valid |= 1u << e;
+  }
+  return valid;
+}
+
+__device__ __forceinline__ u64 smp_wave_sum(u64 v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ u64 smp_wave_incl_scan(u64 v, int lane) {
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const u64 t = __shfl_up(v, o, 64);
+    if (lane >= o) v += t;
+  }
+  return v;
+}
+
+// hist[bin[e]] += val[e] for the elements of `mask`, called by every lane of a wave.  A wave whose elements all fall into one
+// bin (a row of equal logits, a masked vocabulary range) adds once per wave, a thread whose elements do once per thread: all the
+// row's atomics on one LDS word would otherwise run one after the other.
+__device__ __forceinline__ void smp_hist_add(u64* hist, const unsigned (&bin)[8], const u64 (&val)[8], unsigned mask, int lane) {
+  unsigned tb = 0xFFFFFFFFu;
+  u64 tsum = 0ull;
+  bool same = true;
+#pragma unroll
+  for (int e = 0; e < 8; ++e)
+    if (mask >> e & 1u) {
+      if (tb == 0xFFFFFFFFu) tb = bin[e];
+      if (bin[e] == tb) tsum += val[e]; else same = false;
+    }
+  const u64 have = __ballot(mask != 0u);
+  if (have == 0ull) return;
+  const unsigned wb = (unsigned)__shfl((int)tb, __ffsll((long long)have) - 1, 64);
+  if (__all(mask == 0u || (same && tb == wb))) {
+    const u64 s = smp_wave_sum(tsum);
+    if (lane == 0 && s != 0ull) atomicAdd(&hist[wb], s);
+  } else if (mask != 0u) {
+    if (same) {
+      if (tsum != 0ull) atomicAdd(&hist[tb], tsum);
+    } else {
+#pragma unroll
+      for (int e = 0; e < 8; ++e)
+        if ((mask >> e & 1u) && val[e] != 0ull) atomicAdd(&hist[bin[e]], val[e]);
+    }
+  }
+}
+
+// Walk of the coarse bins from the top: thread t owns bins 4095-4t .. 4092-4t.  E_b = the sum of the bins above b.  Returns the
+// total; `locate` then finds the lowest bin with E_b < T (the bin where the running sum crosses T) and leaves (bin, E_bin) in sh[].
+struct SmpScan { u64 c[4]; u64 excl; u64 total; };
+__device__ __forceinline__ void smp_scan(const u64* hist, u64* wsum, int tid, SmpScan& s) {
+  const int lane = tid & 63, wave = tid >> 6;
+  u64 local = 0ull;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) { s.c[i] = hist[SMP_BINS - 1 - 4 * tid - i]; local += s.c[i]; }
+  const u64 incl = smp_wave_incl_scan(local, lane);
+  if (lane == 63) wsum[wave] = incl;
+  __syncthreads();
+  u64 woff = 0ull, total = 0ull;
+#pragma unroll
+  for (int w = 0; w < SMP_WAVES; ++w) { const u64 x = wsum[w]; if (w < wave) woff += x; total += x; }
+  s.excl = woff + incl - local;
+  s.total = total;
+}
+__device__ __forceinline__ void smp_locate(const SmpScan& s, u64 T, int tid, unsigned* sh_bin, u64* sh_E) {
+  u64 E = s.excl;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    if (E < T && E + s.c[i] >= T) { *sh_bin = (unsigned)(SMP_BINS - 1 - 4 * tid - i); *sh_E = E; }
+    E += s.c[i];
+  }
+}
+
+__global__ void __launch_bounds__(SMP_THREADS)
+sample_rows_kernel(const bf16_t* __restrict__ logits, long long ld, int V, const float* __restrict__ temperature,
+                   const int* __restrict__ top_k, const float* __restrict__ top_p, const long long* __restrict__ seed,
+                   long long* __restrict__ counter, long long* __restrict__ token, long long token_stride,
+                   int* __restrict__ n_kept, float* __restrict__ prob) {
+  __shared__ u64 hist[SMP_BINS];
+  __shared__ u64 sub[SMP_SUB];
+  __shared__ u64 wsum[SMP_WAVES];
+  __shared__ u64 wbest[SMP_WAVES];
+  __shared__ unsigned wcnt[SMP_WAVES];
+  __shared__ unsigned sh_bin;
+  __shared__ u64 sh_E;
+  __shared__ unsigned sh_key;
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const long long s = blockIdx.x;
+  const bf16_t* row = logits + s * ld;
+  SmpRow r;
+  r.off = (int)(((uintptr_t)row & 15u) >> 1);
+  r.base = (const u32x4*)(row - r.off);
+  r.V = V;
+  r.nt = ((long long)r.off + V + 7) >> 3;
+
+  const float tau = temperature[s];
+  const bool greedy = !(tau > 0.f);
+  const int k = top_k[s];
+  const float p = top_p[s];
+  const bool use_k = !greedy && k > 0 && k < V;
+  const bool use_p = !greedy && p < 1.f;
+
+  if (use_k) {
+#pragma unroll
+    for (int i = 0; i < SMP_BINS / SMP_THREADS; ++i) hist[tid + i * SMP_THREADS] = 0ull;
+    __syncthreads();
+  }
+
+  // ---- pass 1: the maximum and its lowest index; coarse counts for top-k
+  unsigned bkey = 0u, bidx = 0u;
+  bool got = false;
+  for (long long j0 = (long long)wave * 64; j0 < r.nt; j0 += SMP_THREADS) {
+    const long long j = j0 + lane;
+    unsigned key[8] = {}, valid = 0u;
+    if (j < r.nt) valid = smp_load(r, j, key);
+#pragma unroll
+    for (int e = 0; e < 8; ++e)
+      if ((valid >> e & 1u) && (!got || key[e] > bkey)) { bkey = key[e]; bidx = (unsigned)(j * 8 - r.off + e); got = true; }
+    if (use_k) {
+      unsigned bin[8];
+      u64 val[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) { bin[e] = key[e] >> 4; val[e] = 1ull; }
+      smp_hist_add(hist, bin, val, valid, lane);
+    }
+  }
+  // (key, lowest index) as one ordered word: the larger key wins, then the smaller index
+  u64 best = got ? ((u64)(bkey + 1u) << 32) | (u64)(0xFFFFFFFFu - bidx) : 0ull;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { const u64 t = __shfl_xor(best, o, 64); best = t > best ? t : best; }
+  if (lane == 0) wbest[wave] = best;
+  __syncthreads();
+  best = 0ull;
+#pragma unroll
+  for (int w = 0; w < SMP_WAVES; ++w) best = wbest[w] > best ? wbest[w] : best;
+  const unsigned mkey = (unsigned)(best >> 32) - 1u;
+  const unsigned midx = 0xFFFFFFFFu - (unsigned)(best & 0xFFFFFFFFull);
+
+  if (greedy) {
+    if (tid == 0) {
+      token[s * token_stride] = (long long)midx;
+      if (n_kept) n_kept[s] = 1;
+      if (prob) prob[s] = 1.f;
+    }
+    return;
+  }
+  const float xm = smp_key_value(mkey);
+  const float c = 1.44269504088896341f / tau;
+
+  // ---- top-k: the bin where the count from the top reaches k, then the key inside it
+  unsigned tk = 0u;
+  if (use_k) {
+    SmpScan sc;
+    smp_scan(hist, wsum, tid, sc);
+    smp_locate(sc, (u64)k, tid, &sh_bin, &sh_E);
+    if (tid < SMP_SUB) sub[tid] = 0ull;
+    __syncthreads();
+    const unsigned B = sh_bin;
+    for (long long j0 = (long long)wave * 64; j0 < r.nt; j0 += SMP_THREADS) {
+      const long long j = j0 + lane;
+      unsigned key[8] = {}, valid = 0u;
+      if (j < r.nt) valid = smp_load(r, j, key);
+      unsigned bin[8], m = 0u;
+      u64 val[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) { bin[e] = key[e] & 15u; val[e] = 1ull; if ((key[e] >> 4) == B) m |= 1u << e; }
+      if (__any((valid & m) != 0u)) smp_hist_add(sub, bin, val, valid & m, lane);
+    }
+    __syncthreads();
+    if (tid == 0) {
+      u64 E = sh_E;
+      unsigned res = mkey;
+      for (int i = SMP_SUB - 1; i >= 0; --i) {
+        if (E < (u64)k) res = B * SMP_SUB + i;
+        E += sub[i];
+      }
+      sh_key = res;
+    }
+    __syncthreads();
+    tk = sh_key;
+    __syncthreads();
+  }
+
+  // ---- top-p: keep a class while the mass strictly above it is below p Z_K
+  unsigned tp = 0u;
+  if (use_p) {
+#pragma unroll
+    for (int i = 0; i < SMP_BINS / SMP_THREADS; ++i) hist[tid + i * SMP_THREADS] = 0ull;
+    __syncthreads();
+    for (long long j0 = (long long)wave * 64; j0 < r.nt; j0 += SMP_THREADS) {
+      const long long j = j0 + lane;
+      unsigned key[8] = {}, valid = 0u;
+      if (j < r.nt) valid = smp_load(r, j, key);
+      unsigned m = 0u;
+#pragma unroll
+      for (int e = 0; e < 8; ++e)
+        if (key[e] >= tk) m |= 1u << e;
+      m &= valid;
+      if (__any(m != 0u)) {
+        unsigned bin[8];
+        u64 val[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { bin[e] = key[e] >> 4; val[e] = (m >> e & 1u) ? smp_weight(key[e], mkey, xm, c) : 0ull; }
+        smp_hist_add(hist, bin, val, m, lane);
+      }
+    }
+    __syncthreads();
+    SmpScan sc;
+    smp_scan(hist, wsum, tid, sc);
+    // mass above < p Z  <=>  mass above < ceil(p Z) for an integer mass; p Z in float64 (Z < 2^64: 2^-53 relative)
+    const double pz = (double)p * (double)sc.total;
+    const u64 T = pz > 0.0 ? (u64)ceil(pz) : 0ull;
+    if (tid == 0) { sh_bin = mkey >> 4; sh_E = 0ull; }        // T == 0 (p <= 0): the top class alone
+    __syncthreads();
+    smp_locate(sc, T, tid, &sh_bin, &sh_E);
+    if (tid < SMP_SUB) sub[tid] = 0ull;
+    __syncthreads();
+    const unsigned B = sh_bin;
+    for (long long j0 = (long long)wave * 64; j0 < r.nt; j0 += SMP_THREADS) {
+      const long long j = j0 + lane;
+      unsigned key[8] = {}, valid = 0u;
+      if (j < r.nt) valid = smp_load(r, j, key);
+      unsigned bin[8], m = 0u;
+      u64 val[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) { bin[e] = key[e] & 15u; val[e] = 1ull; if ((key[e] >> 4) == B && key[e] >= tk) m |= 1u << e; }
+      if (__any((valid & m) != 0u)) smp_hist_add(sub, bin, val, valid & m, lane);
+    }
+    __syncthreads();
+    if (tid == 0) {
+      u64 E = sh_E;
+      unsigned res = mkey;
+      for (int i = SMP_SUB - 1; i >= 0; --i) {
+        const unsigned key = B * SMP_SUB + i;
+        if (E < T) res = key;
+        E += sub[i] * smp_weight(key, mkey, xm, c);
+      }
+      sh_key = res < mkey ? res : mkey;
+    }
+    __syncthreads();
+    tp = sh_key;
+  }
+  const unsigned t = tk > tp ? tk : tp;
+
+  // ---- pass 5: kept count and mass; wave w owns the tiles [w tpw, (w+1) tpw), its lanes interleaved
+  const long long tpw = (r.nt + SMP_WAVES - 1) / SMP_WAVES;
+  const long long jbeg = wave * tpw, jend = (jbeg + tpw < r.nt) ? jbeg + tpw : r.nt;
+  unsigned cnt = 0u;
+  u64 mass = 0ull;
+  for (long long j0 = jbeg; j0 < jend; j0 += 64) {
+    const long long j = j0 + lane;
+    if (j < jend) {
+      unsigned key[8];
+      const unsigned valid = smp_load(r, j, key);
+#pragma unroll
+      for (int e = 0; e < 8; ++e)
+        if ((valid >> e & 1u) && key[e] >= t) { ++cnt; mass += smp_weight(key[e], mkey, xm, c); }
+    }
+  }
+  mass = smp_wave_sum(mass);
+  cnt = (unsigned)smp_wave_sum((u64)cnt);
+  __syncthreads();                              // wsum of the last scan has been read by every thread
+  if (lane == 0) { wsum[wave] = mass; wcnt[wave] = cnt; }
+  __syncthreads();
+  u64 Z = 0ull;
+  unsigned kept = 0u;
+#pragma unroll
+  for (int w = 0; w < SMP_WAVES; ++w) { Z += wsum[w]; kept += wcnt[w]; }
+
+  // ---- the draw: splitmix64 finaliser over (seed, counter + 1)
+  const long long ctr = counter[s];
+  auto mix = [](u64 z) {
+    z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
+    z ^= z >> 27; z *= 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+  };
+  const u64 u = mix(mix((u64)seed[s]) + ((u64)ctr + 1ull) * 0x9E3779B97F4A7C15ull);
+  const u64 target = __umul64hi(u, Z);          // < Z
+  u64 before = 0ull;
+  int wstar = SMP_WAVES - 1;
+#pragma unroll
+  for (int w = SMP_WAVES - 1; w >= 0; --w) {
+    u64 pre = 0ull;
+#pragma unroll
+    for (int v = 0; v < SMP_WAVES; ++v) if (v < w) pre += wsum[v];
+    if (target >= pre && target < pre + wsum[w]) { wstar = w; before = pre; }
+  }
+  if (wave != wstar) return;
+
+  // ---- pass 6: the wave that holds the target finds the tile, one lane walks it
+  u64 rem = target - before;
+  for (long long j0 = jbeg; j0 < jend; j0 += 64) {
+    const long long j = j0 + lane;
+    unsigned key[8] = {}, valid = 0u;
+    u64 q[8];
+    u64 m = 0ull;
+    if (j < jend) valid = smp_load(r, j, key);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      q[e] = ((valid >> e & 1u) && key[e] >= t) ? smp_weight(key[e], mkey, xm, c) : 0ull;
+      m += q[e];
+    }
+    const u64 incl = smp_wave_incl_scan(m, lane);
+    const u64 tot = __shfl(incl, 63, 64);
+    if (rem < tot) {
+      const u64 hit = __ballot(rem < incl);
+      if (lane == __ffsll((long long)hit) - 1) {
+        u64 x = rem - (incl - m);
+        int e = 0;
+#pragma unroll
+        for (int i = 0; i < 7; ++i)
+          if (e == i && x >= q[i]) { x -= q[i]; e = i + 1; }
+        u64 qe = q[0];
+#pragma unroll
+        for (int i = 1; i < 8; ++i) if (e == i) qe = q[i];
+        token[s * token_stride] = j * 8 - r.off + e;
+        if (n_kept) n_kept[s] = (int)kept;
+        if (prob) prob[s] = (float)((double)qe / (double)Z);
+        counter[s] = ctr + 1;
+      }
+      return;
+    }
+    rem -= tot;
+  }
+}
+
+}  // namespace ivl
+
+extern "C" int ivl_sample_rows_fwd(const void* logits, int64_t ld, int S, int V, const float* temperature, const int32_t* top_k,
+                                   const float* top_p, const int64_t* seed, int64_t* counter, int64_t* token,
+                                   int64_t token_stride, int32_t* n_kept, float* prob, void* stream) {
+  using namespace ivl;
+  IVL_REQUIRE(logits && temperature && top_k && top_p && seed && counter && token, IVL_ERR_INVALID_ARG,
+              "ivl_sample_rows_fwd: NULL pointer");
+  IVL_REQUIRE(S >= 1 && V >= 1 && ld >= (int64_t)V, IVL_ERR_INVALID_ARG, "ivl_sample_rows_fwd: S=%d V=%d ld=%lld", S, V,
+              (long long)ld);
+  IVL_REQUIRE(V < (1 << 23), IVL_ERR_UNSUPPORTED, "ivl_sample_rows_fwd: V=%d (the Q40 sums are sized for V < 2^23)", V);
+  hipLaunchKernelGGL(sample_rows_kernel, dim3((unsigned)S), dim3(SMP_THREADS), 0, (hipStream_t)stream, (const bf16_t*)logits,
+                     (long long)ld, V, temperature, (const int*)top_k, top_p, (const long long*)seed, (long long*)counter,
+                     (long long*)token, (long long)token_stride, (int*)n_kept, prob);
+  return check_launch("ivl_sample_rows_fwd");
+}

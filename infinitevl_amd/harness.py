@@ -10,6 +10,7 @@ stock PyTorch-ROCm (rocBLAS/hipBLASLt GEMMs): callers of the path, kept as-is.
 """
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass, field, fields
 from typing import Dict, List, Optional, Tuple
 
@@ -395,13 +396,75 @@ class GraphedStep:
         return self.hidden, self.logits
 
 
-class GraphedDecode:
-    """hipGraph-captured greedy single-token step: embed(token) -> stack -> argmax -> token buffer
-    (the demo's eager loop, demo:399-422, made replayable: token and position stay on the device)."""
+class Sampler:
+    """Per-row sampling parameters and random streams of a decode step, resident on the device: temperature / top_k / top_p /
+    seed / counter of ops.sample_tokens, one row per batch row (GraphedDecode) or slot (GraphedMultiStreamDecode).  A captured
+    step reads the table at replay, so a row set between replays samples with its new parameters on the next one, without a
+    recapture -- like the per-slot ring positions.  Rows start greedy (temperature 0: the lowest-index arg-max, no draw).
+    The generation arguments of the reference (do_sample / temperature / top_p / top_k: api/chat.py:160-162) map onto set()."""
 
-    def __init__(self, model: InfiniteVLTextStack, cache: StaticCachePrealloc, batch_size: int, warmup: int = 2):
+    def __init__(self, n_rows: int, device):
+        if n_rows < 1:
+            raise ValueError(f"Sampler: n_rows must be >= 1; got {n_rows}")
+        self.n_rows = int(n_rows)
+        self.temperature = torch.zeros(n_rows, dtype=torch.float32, device=device)
+        self.top_k = torch.zeros(n_rows, dtype=torch.int32, device=device)
+        self.top_p = torch.ones(n_rows, dtype=torch.float32, device=device)
+        self.seed = torch.zeros(n_rows, dtype=torch.int64, device=device)
+        self.counter = torch.zeros(n_rows, dtype=torch.int64, device=device)      # draws made so far; the kernel advances it
+
+    def _row(self, row: int) -> int:
+        if not isinstance(row, int) or not 0 <= row < self.n_rows:
+            raise ValueError(f"Sampler: row must be an int in [0, {self.n_rows}); got {row!r}")
+        return row
+
+    def set(self, row: int, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0) -> None:
+        """Parameters and a fresh random stream (counter 0) for `row`.  temperature 0 = greedy; top_k 0 and top_p 1 = off."""
+        row = self._row(row)
+        temperature, top_p = float(temperature), float(top_p)
+        if not (math.isfinite(temperature) and temperature >= 0.0):
+            raise ValueError(f"Sampler.set: temperature must be finite and >= 0; got {temperature}")
+        if isinstance(top_k, bool) or not isinstance(top_k, int) or not 0 <= top_k < 2 ** 31:
+            raise ValueError(f"Sampler.set: top_k must be an int >= 0 (0 = off); got {top_k!r}")
+        if not 0.0 < top_p <= 1.0:
+            raise ValueError(f"Sampler.set: top_p must be in (0, 1]; got {top_p}")
+        if isinstance(seed, bool) or not isinstance(seed, int) or not -2 ** 63 <= seed < 2 ** 64:
+            raise ValueError(f"Sampler.set: seed must be a 64-bit int; got {seed!r}")
+        self.temperature[row] = temperature
+        self.top_k[row] = top_k
+        self.top_p[row] = top_p
+        self.seed[row] = seed - 2 ** 64 if seed >= 2 ** 63 else seed
+        self.counter[row] = 0
+
+    def reset(self, row: int) -> None:
+        """Back to greedy."""
+        self.set(row)
+
+    def state(self) -> torch.Tensor:
+        """The counters (what a step changes), for a save around a capture's warm-up."""
+        return self.counter.clone()
+
+    def load_state(self, state: torch.Tensor) -> None:
+        self.counter.copy_(state)
+
+    def sample(self, logits: torch.Tensor, out: torch.Tensor, row: Optional[int] = None) -> torch.Tensor:
+        """Tokens of every row (logits [n_rows,V]) or of the one `row` (logits [1,V]; views of the table, no copy) into `out`."""
+        sl = slice(None) if row is None else slice(row, row + 1)
+        return ops.sample_tokens(logits, self.temperature[sl], self.top_k[sl], self.top_p[sl], self.seed[sl], self.counter[sl],
+                                 out=out)
+
+
+class GraphedDecode:
+    """hipGraph-captured single-token step: embed(token) -> stack -> argmax -> token buffer
+    (the demo's eager loop, demo:399-422, made replayable: token and position stay on the device).  With a `sampler` (a
+    Sampler of batch_size rows) the arg-max and the copy are ONE ops.sample_tokens launch on the sampler's table."""
+
+    def __init__(self, model: InfiniteVLTextStack, cache: StaticCachePrealloc, batch_size: int, warmup: int = 2,
+                 sampler: Optional["Sampler"] = None):
         p_ = next(model.parameters())
-        self.model, self.cache, self.B = model, cache, batch_size
+        if sampler is not None and sampler.n_rows != batch_size:
+            raise ValueError(f"GraphedDecode: the sampler has {sampler.n_rows} rows for batch_size {batch_size}")
+        self.model, self.cache, self.B, self.sampler = model, cache, batch_size, sampler
         self.token = torch.zeros(batch_size, 1, dtype=torch.int64, device=p_.device)
         start = cache.get_seq_length()
         self.position_ids = torch.full((3, batch_size, 1), start, dtype=torch.int64, device=p_.device)
@@ -412,13 +475,17 @@ class GraphedDecode:
     def _run(self):
         _, lg = self.model(input_ids=self.token, position_ids=self.position_ids, past_key_values=self.cache,
                            logits_to_keep=1)
-        self.token.copy_(lg[:, -1].argmax(-1, keepdim=True))
+        if self.sampler is None:
+            self.token.copy_(lg[:, -1].argmax(-1, keepdim=True))
+        else:
+            self.sampler.sample(lg[:, -1], self.token)
         self.position_ids.add_(1)
         return lg
 
     def capture(self) -> None:
         self.cache.ensure_started()
         saved, saved_pos, saved_tok = self.cache.clone(), self.position_ids.clone(), self.token.clone()
+        saved_smp = self.sampler.state() if self.sampler is not None else None
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s), torch.no_grad():
@@ -431,6 +498,8 @@ class GraphedDecode:
         self.cache.copy_from(saved)
         self.position_ids.copy_(saved_pos)
         self.token.copy_(saved_tok)
+        if self.sampler is not None:
+            self.sampler.load_state(saved_smp)          # the warm-up and the capture itself made draws
 
     def step(self):
         """One decode step; the new token is left in self.token (device)."""
@@ -443,33 +512,43 @@ class GraphedDecode:
 
 
 class GraphedMultiStreamDecode:
-    """Greedy decode of independent streams in the slots of a MultiStreamCache: ONE captured graph advances every slot by
+    """Decode of independent streams in the slots of a MultiStreamCache: ONE captured graph advances every slot by
     one token (embed -> stack -> argmax -> token buffer, per-slot positions +1).  Streams join with admit() (the prompt runs
-    eagerly on the slot's B = 1 view) and leave with release(), both between replays and without a recapture."""
+    eagerly on the slot's B = 1 view) and leave with release(), both between replays and without a recapture.
+    Greedy by default; with a `sampler` (a Sampler of n_slots rows) every slot draws its token with its own temperature /
+    top-k / top-p and its own random stream in one ops.sample_tokens launch (a slot left at temperature 0 stays greedy)."""
 
     PREFILL_CHUNK = 4096
 
-    def __init__(self, model: InfiniteVLTextStack, cache: MultiStreamCache, warmup: int = 2):
+    def __init__(self, model: InfiniteVLTextStack, cache: MultiStreamCache, warmup: int = 2,
+                 sampler: Optional["Sampler"] = None):
+        if sampler is not None and sampler.n_rows != cache.n_slots:
+            raise ValueError(f"GraphedMultiStreamDecode: the sampler has {sampler.n_rows} rows for {cache.n_slots} slots")
+        self.sampler = sampler
         if any(getattr(l.self_attn, "mma_dtype", None) is not None for l in model.layers):
             raise ValueError("GraphedMultiStreamDecode: the fp8 decode step is not supported (bf16 only)")
         p_ = next(model.parameters())
         self.model, self.cache, self.S = model, cache, cache.n_slots
         self.token = torch.zeros(self.S, 1, dtype=torch.int64, device=p_.device)
         self.position_ids = torch.zeros(3, self.S, 1, dtype=torch.int64, device=p_.device)
-        self.logits = None
+        self.logits = self.admit_logits = None
         self.graph: Optional[torch.cuda.CUDAGraph] = None
         self._warmup = warmup
 
     def _run(self):
         _, lg = self.model(input_ids=self.token, position_ids=self.position_ids, past_key_values=self.cache,
                            logits_to_keep=1)
-        self.token.copy_(lg[:, -1].argmax(-1, keepdim=True))
+        if self.sampler is None:
+            self.token.copy_(lg[:, -1].argmax(-1, keepdim=True))
+        else:
+            self.sampler.sample(lg[:, -1], self.token)
         self.position_ids.add_(1)
         return lg
 
     def capture(self) -> None:
         """Warm up and capture; every slot's ring, state, position and token are restored afterwards."""
         saved, saved_pos, saved_tok = self.cache.clone(), self.position_ids.clone(), self.token.clone()
+        saved_smp = self.sampler.state() if self.sampler is not None else None
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s), torch.no_grad():
@@ -482,11 +561,17 @@ class GraphedMultiStreamDecode:
         self.cache.copy_from(saved)
         self.position_ids.copy_(saved_pos)
         self.token.copy_(saved_tok)
+        if self.sampler is not None:
+            self.sampler.load_state(saved_smp)          # the warm-up and the capture itself made draws
 
     @torch.no_grad()
-    def admit(self, slot: int, inputs_embeds: torch.Tensor, position_ids: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def admit(self, slot: int, inputs_embeds: torch.Tensor, position_ids: Optional[torch.Tensor] = None,
+              sampling: Optional[dict] = None) -> torch.Tensor:
         """Start a stream in `slot` with a prompt inputs_embeds [1,T,hidden] (M-RoPE position_ids [3,1,T]; default: text
-        positions 0..T-1).  Its first generated token is written to token[slot] and returned."""
+        positions 0..T-1).  Its first generated token is written to token[slot] and returned.  `sampling`: the keyword
+        arguments of Sampler.set for this stream (needs a sampler), applied before that first token is drawn."""
+        if sampling is not None and self.sampler is None:
+            raise ValueError("admit: sampling parameters need a GraphedMultiStreamDecode built with a sampler")
         if inputs_embeds.dim() != 3 or inputs_embeds.shape[0] != 1:
             raise ValueError(f"admit: inputs_embeds must be [1,T,hidden]; got {tuple(inputs_embeds.shape)}")
         T = inputs_embeds.shape[1]
@@ -494,6 +579,8 @@ class GraphedMultiStreamDecode:
             position_ids = torch.arange(T, device=inputs_embeds.device, dtype=torch.int64)[None, None, :].expand(3, 1, T)
         if tuple(position_ids.shape) != (3, 1, T):
             raise ValueError(f"admit: position_ids must be [3,1,{T}]; got {tuple(position_ids.shape)}")
+        if sampling is not None:
+            self.sampler.set(slot, **sampling)
         self.cache.admit(slot)
         view = self.cache.slot_view(slot)
         lg = None
@@ -501,13 +588,19 @@ class GraphedMultiStreamDecode:
             b = min(T, a + self.PREFILL_CHUNK)
             _, lg = self.model(inputs_embeds=inputs_embeds[:, a:b], position_ids=position_ids[:, :, a:b],
                                past_key_values=view, logits_to_keep=1)
-        self.token[slot].copy_(lg[0, -1].argmax(-1, keepdim=True))
+        self.admit_logits = lg                          # [1,1,vocab]: what the latest admission's first token was taken from
+        if self.sampler is None:
+            self.token[slot].copy_(lg[0, -1].argmax(-1, keepdim=True))
+        else:
+            self.sampler.sample(lg[:, -1], self.token[slot:slot + 1], row=slot)
         self.position_ids[:, slot].fill_(int(position_ids.max()) + 1)        # the next M-RoPE text position
         return self.token[slot]
 
     def release(self, slot: int) -> None:
         """End the stream in `slot`: its state is zeroed (the slot keeps computing on zeros until the next admit)."""
         self.cache.release(slot)
+        if self.sampler is not None:
+            self.sampler.reset(slot)
         self.token[slot].zero_()
         self.position_ids[:, slot].zero_()
 

@@ -1189,3 +1189,40 @@ def swa_attention_interface(module, query, key, value, attention_mask=None, drop
         scaling = query.shape[-1] ** -0.5
     out = swa_forward(query, key, value, window=sliding_window, scaling=scaling, layout="bhtd")
     return out, None
+
+
+# ---------------------------------------------------------------------------------------------
+# sampling
+# ---------------------------------------------------------------------------------------------
+def sample_tokens(logits: torch.Tensor, temperature: torch.Tensor, top_k: torch.Tensor, top_p: torch.Tensor, seed: torch.Tensor,
+                  counter: torch.Tensor, out: Optional[torch.Tensor] = None, n_kept: Optional[torch.Tensor] = None,
+                  prob: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One next token per row of lm_head logits [S,V] or [S,1,V] (bf16, last dim contiguous) in one launch: temperature,
+    top-k, top-p and the draw, per row (ivl_sample_rows_fwd states the semantics; HF generate's warpers + multinomial,
+    api/chat.py:160-162 of the reference).  temperature / top_k / top_p / seed / counter: [S] fp32 / int32 / fp32 / int64 /
+    int64; a row with temperature <= 0 takes the lowest-index arg-max.  counter[s] (draws made so far) is advanced by the
+    kernel for every row that draws: the token is a pure function of (logits, parameters, seed, counter).  `out`: int64 [S]
+    or [S,1], written in place and returned (default: a new [S]); n_kept [S] int32 and prob [S] fp32 are optional outputs."""
+    if logits.dim() == 3 and logits.shape[1] == 1:
+        logits = logits[:, 0]
+    if logits.dim() != 2 or logits.dtype != torch.bfloat16 or logits.shape[0] < 1 or logits.shape[1] < 1:
+        raise ValueError(f"sample_tokens: logits must be bf16 [S,V] or [S,1,V]; got {logits.dtype} {tuple(logits.shape)}")
+    S, V = logits.shape
+    if logits.stride(1) != 1 or (S > 1 and logits.stride(0) < V):
+        raise ValueError(f"sample_tokens: the last dim of logits must be contiguous and the rows apart (strides {logits.stride()})")
+    for name, t, dt in (("temperature", temperature, torch.float32), ("top_k", top_k, torch.int32),
+                        ("top_p", top_p, torch.float32), ("seed", seed, torch.int64), ("counter", counter, torch.int64),
+                        ("n_kept", n_kept, torch.int32), ("prob", prob, torch.float32)):
+        if t is None:
+            continue
+        if t.dtype != dt or tuple(t.shape) != (S,) or not t.is_contiguous():
+            raise ValueError(f"sample_tokens: {name} must be a contiguous {dt} tensor of [{S}]; got {t.dtype} {tuple(t.shape)}")
+    if out is None:
+        out = torch.empty(S, dtype=torch.int64, device=logits.device)
+    if out.dtype != torch.int64 or tuple(out.shape) not in ((S,), (S, 1)):
+        raise ValueError(f"sample_tokens: out must be int64 [{S}] or [{S},1]; got {out.dtype} {tuple(out.shape)}")
+    _need_gpu(logits, temperature, top_k, top_p, seed, counter, out, n_kept, prob)
+    _lib.check(_lib.load().ivl_sample_rows_fwd(
+        _p(logits), logits.stride(0) if S > 1 else V, S, V, _p(temperature), _p(top_k), _p(top_p), _p(seed), _p(counter),
+        _p(out), out.stride(0) if S > 1 else 1, _p(n_kept), _p(prob), _stream(logits)))
+    return out

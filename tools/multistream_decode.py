@@ -7,6 +7,14 @@ prefills.  1, 2 and 4 slots are timed alternately with the B = 1 reference in th
 `--steps` graph replays); the median over `--rounds` rounds is reported.  Prints one JSON line (and writes it to --out).
 
     python tools/multistream_decode.py [--steps 64] [--rounds 5] [--out profiles/multistream_decode.json]
+
+--sampling measures the sampled step instead (harness.Sampler, ops.sample_tokens in place of argmax + copy_): per slot count the
+greedy step as it is without a sampler (A), the same step with every row greedy inside the kernel (B) and with every row
+sampling at temperature 0.7 / top-k 50 / top-p 0.9 (C), timed A B A C per round in one process; and the operator alone at the
+model's vocabulary (random logits and a row of equal logits, which sends every histogram update to one bin) beside torch's
+argmax + copy_.  The bar for B and C is A + 2 %.
+
+    python tools/multistream_decode.py --sampling --slots 1,4 [--out profiles/sampling_decode.json]
 """
 import argparse
 import json
@@ -26,6 +34,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--slots", default="1,2,4")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--sampling", action="store_true", help="time the sampled step against the greedy one (see above)")
     args = ap.parse_args()
     import torch
     from infinitevl_amd.cache import MultiStreamCache
@@ -51,6 +60,9 @@ def main():
                 pid = torch.arange(a, b, device=dev)[None, None, :].expand(3, 1, b - a)
                 _, lg = model(inputs_embeds=x[:, a:b], position_ids=pid, past_key_values=cache)
         return lg
+
+    if args.sampling:
+        return sampling_legs(args, torch, model, cfg, prompts, dev)
 
     # reference: one stream on the existing B = 1 graphed decode step
     c1 = model.allocate_inference_cache(1)
@@ -95,6 +107,80 @@ def main():
         res[f"slots{n}"] = {"ms_per_step": round(ms, 4), "aggregate_tok_s": round(1000.0 * n / ms, 1),
                             "per_stream_tok_s": round(1000.0 / ms, 1), "aggregate_vs_b1": round(n * ref_ms / ms, 3),
                             "spread_ms": [round(min(times[f"slots{n}"]), 4), round(max(times[f"slots{n}"]), 4)]}
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+SAMPLED = {"temperature": 0.7, "top_k": 50, "top_p": 0.9}
+
+
+def sampling_legs(args, torch, model, cfg, prompts, dev):
+    from infinitevl_amd import ops
+    from infinitevl_amd.cache import MultiStreamCache
+    from infinitevl_amd.harness import GraphedMultiStreamDecode, Sampler
+    stream = torch.cuda.current_stream()
+
+    def timed(fn, n):
+        for _ in range(4):
+            fn()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        for _ in range(n):
+            fn()
+        e1.record(stream)
+        e1.synchronize()
+        return e0.elapsed_time(e1) / n
+
+    slots = [int(s) for s in args.slots.split(",")]
+    res = {"tool": "multistream_decode --sampling", "layers": cfg.num_hidden_layers, "window": 4096, "steps": args.steps,
+           "rounds": args.rounds, "sampled": SAMPLED, "bar": "greedy ms_per_step + 2 %"}
+    for n in slots:
+        legs = {}
+        for name in ("greedy", "kernel_greedy", "sampled"):
+            cache = MultiStreamCache(config=cfg, n_slots=n, device=dev, dtype=torch.bfloat16)
+            smp = None if name == "greedy" else Sampler(n, dev)
+            dec = GraphedMultiStreamDecode(model, cache, sampler=smp)
+            for s in range(n):
+                dec.admit(s, prompts[s], sampling=dict(SAMPLED, seed=s + 1) if name == "sampled" else None)
+            dec.capture()
+            legs[name] = dec.step
+        times = {k: [] for k in legs}
+        for _ in range(args.rounds):                            # A B A C
+            for name in ("kernel_greedy", "sampled"):
+                times["greedy"].append(timed(legs["greedy"], args.steps))
+                times[name].append(timed(legs[name], args.steps))
+        a = statistics.median(times["greedy"])
+        res[f"slots{n}"] = {"greedy_ms_per_step": round(a, 4), "greedy_spread_ms": [round(min(times["greedy"]), 4),
+                                                                                     round(max(times["greedy"]), 4)]}
+        for name in ("kernel_greedy", "sampled"):
+            b = statistics.median(times[name])
+            res[f"slots{n}"][name] = {"ms_per_step": round(b, 4), "vs_greedy": round(b / a, 4), "delta_us": round(1000 * (b - a), 1),
+                                      "spread_ms": [round(min(times[name]), 4), round(max(times[name]), 4)],
+                                      "within_bar": bool(b <= 1.02 * a)}
+        del legs
+    # the operator alone, back to back on one stream (launch-bound figures include the launch gap)
+    V = cfg.vocab_size
+    gen = torch.Generator(device=dev).manual_seed(1)
+    op = {}
+    for S in (1, 4):
+        rows = {"random": (torch.randn(S, V, generator=gen, device=dev) * 3.0).to(torch.bfloat16),
+                "all_equal": torch.full((S, V), 0.75, dtype=torch.bfloat16, device=dev)}
+        tok = torch.zeros(S, 1, dtype=torch.int64, device=dev)
+        for rname, lg in rows.items():
+            def torch_greedy():
+                tok.copy_(lg.argmax(-1, keepdim=True))
+            op[f"S{S}_{rname}_torch_argmax_copy_us"] = round(1000 * timed(torch_greedy, 200), 2)
+            for pname, kw in (("kernel_greedy", {}), ("sampled", SAMPLED), ("temperature_only", {"temperature": 1.0}),
+                              ("top_p_only", {"temperature": 0.7, "top_p": 0.9}), ("top_k_only", {"temperature": 0.7, "top_k": 50})):
+                smp = Sampler(S, dev)
+                for s in range(S):
+                    smp.set(s, seed=s, **kw)
+                op[f"S{S}_{rname}_{pname}_us"] = round(1000 * timed(lambda: smp.sample(lg, tok), 200), 2)
+    res["operator_V%d" % V] = op
     line = json.dumps(res)
     print(line)
     if args.out:
