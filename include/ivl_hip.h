@@ -433,6 +433,47 @@ IVL_API int ivl_sample_rows_fwd(const void* logits, int64_t ld, int S, int V,
                                 int64_t* token, int64_t token_stride,
                                 int32_t* n_kept, float* prob, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * ivl_sample_rows_fwd with the generation controls the reference hands to HF generate beside the sampling arguments
+ * (src/llamafactory/chat/hf_engine.py:128-156: repetition_penalty, eos_token_id, max_new_tokens), inside the same one launch.
+ * Every control group may be NULL (off); with all of them NULL the call IS ivl_sample_rows_fwd, bit for bit.  Per row s, in order:
+ *   A finished row.  done[s] != 0 on entry: token = fill[s] (0 when fill == NULL), n_kept = 0, prob = 0, and nothing else of the
+ *     row is read or written -- not the counter, seen, n_new or the history; the workgroup returns before its first pass.
+ *   B repetition penalty (HF RepetitionPenaltyLogitsProcessor, which runs before the warpers).  seen: a bitmap of uint32 words,
+ *     row s at seen + s*seen_ld; bit (i & 31) of word (i >> 5) = token i has occurred.  For a seen token and
+ *     r = rep_penalty[s] != 1:   x' = bf16_rne(x < 0 ? x * r : x / r),
+ *     fp32 arithmetic on the widened bf16 value, a true IEEE division, one rounding to bf16.  NaN stays NaN (= -inf), +-inf stay,
+ *     -0 stays in the class of +0.  Unseen tokens and rows with r == 1 (or rep_penalty == NULL) use x unchanged.  Steps 1-6 of
+ *     ivl_sample_rows_fwd then run on x' (the greedy arg-max is that of x'); because x' is a bf16 value again, the histograms,
+ *     the integer weights and the bit-reproducible draw are what they are for any other row.  HF keeps the penalised logit in
+ *     fp32; here it is rounded to bf16: half a bf16 ulp, at most 2^-8 relative, on a penalised logit.
+ *   C bookkeeping after the draw, by the one lane that writes the token:
+ *       seen != NULL: the token's bit is set (also at r == 1);
+ *       history != NULL: history[s*hist_ld + n_new[s] % hist_ld] = token  (int64; a ring of the last hist_ld tokens);
+ *       n_new != NULL: n_new[s] += 1;
+ *       done[s] = 1 if the token equals any of stop_ids[s*n_stop .. +n_stop) (int64; entries < 0 are unused);
+ *       else done[s] = 2 if budget[s] >= 0 and n_new[s] >= budget[s] (after the increment).  A stop id wins over the budget.
+ *   D bounds.  Bits at or above V in a row's last word, the words between ceil(V/32) and seen_ld and other rows are never
+ *     modified and never influence a result; nothing outside a row's seen_ld words is read.
+ * done codes: 0 running, 1 ended on a stop id, 2 ended on its budget; the host clears done[s] to restart a row.
+ * IVL_ERR_INVALID_ARG (before anything is launched): rep_penalty without seen; seen with seen_ld*32 < V; n_stop outside 0..16;
+ * n_stop > 0 without stop_ids or done; budget without n_new or done; history without n_new or with hist_ld < 1; and whatever
+ * ivl_sample_rows_fwd refuses.
+ * ------------------------------------------------------------------------------------------- */
+IVL_API int ivl_sample_rows_ctl_fwd(const void* logits, int64_t ld, int S, int V,
+                                    const float* temperature, const int32_t* top_k, const float* top_p,
+                                    const int64_t* seed, int64_t* counter,
+                                    int64_t* token, int64_t token_stride,
+                                    int32_t* n_kept, float* prob,
+                                    const float* rep_penalty, uint32_t* seen, int64_t seen_ld,
+                                    const int64_t* stop_ids, int n_stop, const int64_t* budget, const int64_t* fill,
+                                    int64_t* n_new, int32_t* done, int64_t* history, int64_t hist_ld, void* stream);
+
+/* Sets the bits of ids[0..n) (int64, device) in ONE row of a seen bitmap: the prompt's tokens, before the first draw.  Ids outside
+ * [0, V) are ignored, duplicates are fine; n == 0 is a no-op.  seen_row NULL, V < 1, n < 0 or ids NULL with n > 0:
+ * IVL_ERR_INVALID_ARG. */
+IVL_API int ivl_token_mark_fwd(uint32_t* seen_row, int64_t V, const int64_t* ids, int64_t n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,7 +20,15 @@
 // Rows are read in 16-byte tiles from the 16-byte boundary at or below the row start, whatever `ld` and the base: the (at most 7)
 // elements in front of and behind the row inside its first and last tile are masked out -- they lie in the same 16 bytes as row
 // elements, so the loads stay inside the caller's allocation granule.
+//
+// Generation controls (ivl_sample_rows_ctl_fwd; the kernel is a template on them, the entry point above instantiates the form
+// without): a finished row returns its fill token before the first pass; the repetition penalty re-keys the seen elements of a
+// tile where it is loaded (a bitmap of seen tokens, 8 bits a tile from two bytes), rounded back to bf16, so every pass sees the same
+// penalised keys and nothing behind the key changes; the lane that writes the token then sets its bit, logs it, counts it and
+// decides `done` from the stop ids and the budget.  ivl_token_mark_fwd marks a prompt's tokens in a row of the bitmap.
 #include "ivl_common.h"
+
+#include <type_traits>
 
 namespace ivl {
 
@@ -60,8 +68,53 @@ struct SmpRow {
   int V;
 };
 
+// The repetition penalty of the controlled form: the row's bitmap of seen tokens as bytes (bit i & 7 of byte i >> 3 = bit i & 31 of
+// word i >> 5) and the row's r; bits == NULL when r == 1 (uniform per workgroup: nothing is fetched then).  SmpNoPen: the
+// control-free form, whose smp_load is the one it always had.
+struct SmpNoPen {};
+struct SmpPen {
+  const unsigned char* bits;
+  float r;
+  float inv;             // RN(1 / r)
+  bool fast;             // 2^-20 <= r < 2^21: smp_penalise_fast serves the logits of ordinary size
+};
+
+// bf16 bits of a seen logit -> bf16_rne(x < 0 ? x * r : x / r) in fp32 (a true division, one rounding); NaN stays NaN
+__device__ __forceinline__ unsigned smp_penalise(unsigned b, float r) {
+  const float x = __uint_as_float(b << 16);
+  const float y = x < 0.f ? x * r : __fdiv_rn(x, r);
+  unsigned u = __float_as_uint(y);
+  if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (u >> 16) | 0x40u;
+  u += 0x7FFFu + ((u >> 16) & 1u);
+  return u >> 16;
+}
+// The same value without a division or a branch, for a logit of ordinary size (2^-30 <= |x| < 2^31, checked by the caller) and
+// 2^-20 <= r < 2^21: with y = RN(1 / r), q = RN(x y) is within an ulp of x / r, e = x - q r is exact in one fma, and
+// RN(q + e y) = RN(x / r) (Markstein's theorem; the ranges keep q, e and every product away from overflow and underflow).  The
+// passes are bound by their vector instructions, and a division costs about as many as the rest of an element's work.
+__device__ __forceinline__ unsigned smp_penalise_fast(unsigned b, float r, float inv) {
+  const float x = __uint_as_float(b << 16);
+  const float q = __fmul_rn(x, inv);
+  const float e = __fmaf_rn(-q, r, x);
+  const float y = x < 0.f ? __fmul_rn(x, r) : __fmaf_rn(e, inv, q);
+  unsigned u = __float_as_uint(y);
+  u += 0x7FFFu + ((u >> 16) & 1u);
+  return u >> 16;
+}
+
+// the seen bits of the 8 elements of tile j (bit e = element e).  The tile starts `off` elements before a byte boundary of the
+// bitmap, so they come from bytes j - 1 and j.  Both indices are clamped into the ceil(V/8) bytes that hold a bit below V (no
+// branch: the two loads leave with the tile's own); what a clamped byte contributes belongs to elements outside the row, which
+// the caller masks out.
+__device__ __forceinline__ unsigned smp_seen_bits(const SmpRow& r, const unsigned char* bits, long long j) {
+  const long long last = ((long long)r.V - 1) >> 3;
+  const unsigned lo = bits[j > 0 ? j - 1 : 0];
+  const unsigned hi = bits[j < last ? j : last];
+  return ((lo >> (8 - r.off)) | (hi << r.off)) & 0xFFu;
+}
+
 // keys of tile j; returns the mask of the elements that belong to the row
-__device__ __forceinline__ unsigned smp_load(const SmpRow& r, long long j, unsigned (&key)[8]) {
+__device__ __forceinline__ unsigned smp_load(const SmpRow& r, const SmpNoPen&, long long j, unsigned (&key)[8]) {
   const u32x4 v = r.base[j];
   const unsigned w[4] = {v.x, v.y, v.z, v.w};
   const long long i0 = j * 8 - r.off;
@@ -72,6 +125,40 @@ __device__ __forceinline__ unsigned smp_load(const SmpRow& r, long long j, unsig
     const long long i = i0 + e;
     if (i >= 0 && i < r.V) valid |= 1u << e;
   }
+  return valid;
+}
+// the same with the seen elements re-keyed to their penalised value: every pass sees the same keys
+__device__ __forceinline__ unsigned smp_load(const SmpRow& r, const SmpPen& pen, long long j, unsigned (&key)[8]) {
+  const u32x4 v = r.base[j];
+  const unsigned w[4] = {v.x, v.y, v.z, v.w};
+  const long long i0 = j * 8 - r.off;
+  unsigned valid = 0u;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const long long i = i0 + e;
+    if (i >= 0 && i < r.V) valid |= 1u << e;
+  }
+  if (pen.bits) {                                // uniform per workgroup
+    const unsigned seen = smp_seen_bits(r, pen.bits, j) & valid;
+    unsigned odd = pen.fast ? 0u : seen;         // seen elements outside the fast form's range: zeros, infinities, NaN, tiny, huge
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const unsigned b = (w[e >> 1] >> ((e & 1) * 16)) & 0xFFFFu;
+      const unsigned pb = smp_penalise_fast(b, pen.r, pen.inv);
+      if (((b & 0x7F80u) - (97u << 7)) > (60u << 7)) odd |= seen & (1u << e);
+      key[e] = (seen >> e & 1u) ? pb : b;
+    }
+    if (__any(odd != 0u)) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e)
+        if (odd >> e & 1u) key[e] = smp_penalise((w[e >> 1] >> ((e & 1) * 16)) & 0xFFFFu, pen.r);
+    }
+  } else {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) key[e] = (w[e >> 1] >> ((e & 1) * 16)) & 0xFFFFu;
+  }
+#pragma unroll
+  for (int e = 0; e < 8; ++e) key[e] = smp_key(key[e]);
   return valid;
 }
 
@@ -145,11 +232,75 @@ __device__ __forceinline__ void smp_locate(const SmpScan& s, u64 T, int tid, uns
   }
 }
 
+// The controls of ivl_sample_rows_ctl_fwd; every group may be NULL (off)
+struct SmpCtl {
+  const float* rep_penalty;
+  unsigned* seen;
+  long long seen_ld;
+  const long long* stop_ids;
+  int n_stop;
+  const long long* budget;
+  const long long* fill;
+  long long* n_new;
+  int* done;
+  long long* history;
+  long long hist_ld;
+};
+
+// Bookkeeping of row s after its draw, by the one lane that wrote the token (no other thread touches the row's state: every
+// read of `seen` by the passes lies before the barrier or the wave-wide shuffle in front of the token write)
+__device__ __forceinline__ void smp_after(const SmpCtl& c, long long s, long long tok) {
+  if (c.seen) {
+    unsigned* w = c.seen + s * c.seen_ld + (tok >> 5);
+    *w = *w | (1u << (tok & 31));
+  }
+  long long n = 0;
+  if (c.n_new) {
+    n = c.n_new[s];
+    if (c.history) c.history[s * c.hist_ld + n % c.hist_ld] = tok;
+    c.n_new[s] = ++n;
+  }
+  if (c.done) {
+    int d = 0;
+    for (int i = 0; i < c.n_stop; ++i) {
+      const long long id = c.stop_ids[s * c.n_stop + i];
+      if (id >= 0 && id == tok) d = 1;
+    }
+    if (d == 0 && c.budget) {
+      const long long b = c.budget[s];
+      if (b >= 0 && n >= b) d = 2;
+    }
+    if (d != 0) c.done[s] = d;
+  }
+}
+
+// CTL: no type (the control-free form, with the parameter list it always had) or SmpCtl
+__device__ __forceinline__ const SmpCtl& smp_first(const SmpCtl& c) { return c; }
+
+template <typename... CTL>
 __global__ void __launch_bounds__(SMP_THREADS)
 sample_rows_kernel(const bf16_t* __restrict__ logits, long long ld, int V, const float* __restrict__ temperature,
                    const int* __restrict__ top_k, const float* __restrict__ top_p, const long long* __restrict__ seed,
                    long long* __restrict__ counter, long long* __restrict__ token, long long token_stride,
-                   int* __restrict__ n_kept, float* __restrict__ prob) {
+                   int* __restrict__ n_kept, float* __restrict__ prob, const CTL... ctl_) {
+  constexpr bool kCtl = sizeof...(CTL) == 1;
+  typename std::conditional<kCtl, SmpPen, SmpNoPen>::type pen;
+  if constexpr (kCtl) {
+    const SmpCtl& ctl = smp_first(ctl_...);
+    const long long s = blockIdx.x;
+    if (ctl.done && ctl.done[s] != 0) {                 // a finished row: the fill token, nothing else read or written
+      if (threadIdx.x == 0) {
+        token[s * token_stride] = ctl.fill ? ctl.fill[s] : 0ll;
+        if (n_kept) n_kept[s] = 0;
+        if (prob) prob[s] = 0.f;
+      }
+      return;
+    }
+    pen.r = ctl.rep_penalty ? ctl.rep_penalty[s] : 1.f;
+    pen.bits = pen.r != 1.f ? (const unsigned char*)(ctl.seen + s * ctl.seen_ld) : nullptr;
+    pen.inv = __fdiv_rn(1.f, pen.r);
+    pen.fast = ((__float_as_uint(pen.r) >> 23) & 0x1FFu) - 107u <= 40u;      // positive, exponent -20 .. 20
+  }
   __shared__ u64 hist[SMP_BINS];
   __shared__ u64 sub[SMP_SUB];
   __shared__ u64 wsum[SMP_WAVES];
@@ -187,7 +338,7 @@ sample_rows_kernel(const bf16_t* __restrict__ logits, long long ld, int V, const
   for (long long j0 = (long long)wave * 64; j0 < r.nt; j0 += SMP_THREADS) {
     const long long j = j0 + lane;
     unsigned key[8] = {}, valid = 0u;
-    if (j < r.nt) valid = smp_load(r, j, key);
+    if (j < r.nt) valid = smp_load(r, pen, j, key);
 #pragma unroll
     for (int e = 0; e < 8; ++e)
       if ((valid >> e & 1u) && (!got || key[e] > bkey)) { bkey = key[e]; bidx = (unsigned)(j * 8 - r.off + e); got = true; }
@@ -216,6 +367,7 @@ sample_rows_kernel(const bf16_t* __restrict__ logits, long long ld, int V, const
       token[s * token_stride] = (long long)midx;
       if (n_kept) n_kept[s] = 1;
       if (prob) prob[s] = 1.f;
+      if constexpr (kCtl) smp_after(smp_first(ctl_...), s, (long long)midx);
     }
     return;
   }
@@ -234,7 +386,7 @@ sample_rows_kernel(const bf16_t* __restrict__ logits, long long ld, int V, const
     for (long long j0 = (long long)wave * 64; j0 < r.nt; j0 += SMP_THREADS) {
       const long long j = j0 + lane;
       unsigned key[8] = {}, valid = 0u;
-      if (j < r.nt) valid = smp_load(r, j, key);
+      if (j < r.nt) valid = smp_load(r, pen, j, key);
       unsigned bin[8], m = 0u;
       u64 val[8];
 #pragma unroll
@@ -265,7 +417,7 @@ sample_rows_kernel(const bf16_t* __restrict__ logits, long long ld, int V, const
     for (long long j0 = (long long)wave * 64; j0 < r.nt; j0 += SMP_THREADS) {
       const long long j = j0 + lane;
       unsigned key[8] = {}, valid = 0u;
-      if (j < r.nt) valid = smp_load(r, j, key);
+      if (j < r.nt) valid = smp_load(r, pen, j, key);
       unsigned m = 0u;
 #pragma unroll
       for (int e = 0; e < 8; ++e)
@@ -294,7 +446,7 @@ sample_rows_kernel(const bf16_t* __restrict__ logits, long long ld, int V, const
     for (long long j0 = (long long)wave * 64; j0 < r.nt; j0 += SMP_THREADS) {
       const long long j = j0 + lane;
       unsigned key[8] = {}, valid = 0u;
-      if (j < r.nt) valid = smp_load(r, j, key);
+      if (j < r.nt) valid = smp_load(r, pen, j, key);
       unsigned bin[8], m = 0u;
       u64 val[8];
 #pragma unroll
@@ -326,7 +478,7 @@ sample_rows_kernel(const bf16_t* __restrict__ logits, long long ld, int V, const
     const long long j = j0 + lane;
     if (j < jend) {
       unsigned key[8];
-      const unsigned valid = smp_load(r, j, key);
+      const unsigned valid = smp_load(r, pen, j, key);
 #pragma unroll
       for (int e = 0; e < 8; ++e)
         if ((valid >> e & 1u) && key[e] >= t) { ++cnt; mass += smp_weight(key[e], mkey, xm, c); }
@@ -369,7 +521,7 @@ sample_rows_kernel(const bf16_t* __restrict__ logits, long long ld, int V, const
     unsigned key[8] = {}, valid = 0u;
     u64 q[8];
     u64 m = 0ull;
-    if (j < jend) valid = smp_load(r, j, key);
+    if (j < jend) valid = smp_load(r, pen, j, key);
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       q[e] = ((valid >> e & 1u) && key[e] >= t) ? smp_weight(key[e], mkey, xm, c) : 0ull;
@@ -392,6 +544,7 @@ sample_rows_kernel(const bf16_t* __restrict__ logits, long long ld, int V, const
         if (n_kept) n_kept[s] = (int)kept;
         if (prob) prob[s] = (float)((double)qe / (double)Z);
         counter[s] = ctr + 1;
+        if constexpr (kCtl) smp_after(smp_first(ctl_...), s, j * 8 - r.off + e);
       }
       return;
     }
@@ -399,19 +552,83 @@ sample_rows_kernel(const bf16_t* __restrict__ logits, long long ld, int V, const
   }
 }
 
+// seen_row |= the bits of ids[0..n) that lie in [0, V)
+__global__ void __launch_bounds__(256)
+token_mark_kernel(unsigned* __restrict__ seen_row, long long V, const long long* __restrict__ ids, long long n) {
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+    const long long id = ids[i];
+    if (id >= 0 && id < V) atomicOr(&seen_row[id >> 5], 1u << (id & 31));
+  }
+}
+
 }  // namespace ivl
+
+static int sample_rows_check(const char* fn, const void* logits, int64_t ld, int S, int V, const float* temperature,
+                             const int32_t* top_k, const float* top_p, const int64_t* seed, int64_t* counter, int64_t* token) {
+  IVL_REQUIRE(logits && temperature && top_k && top_p && seed && counter && token, IVL_ERR_INVALID_ARG, "%s: NULL pointer", fn);
+  IVL_REQUIRE(S >= 1 && V >= 1 && ld >= (int64_t)V, IVL_ERR_INVALID_ARG, "%s: S=%d V=%d ld=%lld", fn, S, V, (long long)ld);
+  IVL_REQUIRE(V < (1 << 23), IVL_ERR_UNSUPPORTED, "%s: V=%d (the Q40 sums are sized for V < 2^23)", fn, V);
+  return IVL_OK;
+}
 
 extern "C" int ivl_sample_rows_fwd(const void* logits, int64_t ld, int S, int V, const float* temperature, const int32_t* top_k,
                                    const float* top_p, const int64_t* seed, int64_t* counter, int64_t* token,
                                    int64_t token_stride, int32_t* n_kept, float* prob, void* stream) {
   using namespace ivl;
-  IVL_REQUIRE(logits && temperature && top_k && top_p && seed && counter && token, IVL_ERR_INVALID_ARG,
-              "ivl_sample_rows_fwd: NULL pointer");
-  IVL_REQUIRE(S >= 1 && V >= 1 && ld >= (int64_t)V, IVL_ERR_INVALID_ARG, "ivl_sample_rows_fwd: S=%d V=%d ld=%lld", S, V,
-              (long long)ld);
-  IVL_REQUIRE(V < (1 << 23), IVL_ERR_UNSUPPORTED, "ivl_sample_rows_fwd: V=%d (the Q40 sums are sized for V < 2^23)", V);
-  hipLaunchKernelGGL(sample_rows_kernel, dim3((unsigned)S), dim3(SMP_THREADS), 0, (hipStream_t)stream, (const bf16_t*)logits,
-                     (long long)ld, V, temperature, (const int*)top_k, top_p, (const long long*)seed, (long long*)counter,
-                     (long long*)token, (long long)token_stride, (int*)n_kept, prob);
+  const int rc = sample_rows_check("ivl_sample_rows_fwd", logits, ld, S, V, temperature, top_k, top_p, seed, counter, token);
+  if (rc != IVL_OK) return rc;
+  hipLaunchKernelGGL(sample_rows_kernel<>, dim3((unsigned)S), dim3(SMP_THREADS), 0, (hipStream_t)stream,
+                     (const bf16_t*)logits, (long long)ld, V, temperature, (const int*)top_k, top_p, (const long long*)seed,
+                     (long long*)counter, (long long*)token, (long long)token_stride, (int*)n_kept, prob);
   return check_launch("ivl_sample_rows_fwd");
+}
+
+extern "C" int ivl_sample_rows_ctl_fwd(const void* logits, int64_t ld, int S, int V, const float* temperature,
+                                       const int32_t* top_k, const float* top_p, const int64_t* seed, int64_t* counter,
+                                       int64_t* token, int64_t token_stride, int32_t* n_kept, float* prob,
+                                       const float* rep_penalty, uint32_t* seen, int64_t seen_ld, const int64_t* stop_ids,
+                                       int n_stop, const int64_t* budget, const int64_t* fill, int64_t* n_new, int32_t* done,
+                                       int64_t* history, int64_t hist_ld, void* stream) {
+  using namespace ivl;
+  const char* fn = "ivl_sample_rows_ctl_fwd";
+  const int rc = sample_rows_check(fn, logits, ld, S, V, temperature, top_k, top_p, seed, counter, token);
+  if (rc != IVL_OK) return rc;
+  IVL_REQUIRE(!rep_penalty || seen, IVL_ERR_INVALID_ARG, "%s: rep_penalty needs seen", fn);
+  IVL_REQUIRE(!seen || seen_ld * 32 >= (int64_t)V, IVL_ERR_INVALID_ARG, "%s: seen_ld=%lld words hold fewer than V=%d bits", fn,
+              (long long)seen_ld, V);
+  IVL_REQUIRE(n_stop >= 0 && n_stop <= 16, IVL_ERR_INVALID_ARG, "%s: n_stop=%d outside 0..16", fn, n_stop);
+  IVL_REQUIRE(n_stop == 0 || (stop_ids && done), IVL_ERR_INVALID_ARG, "%s: n_stop=%d needs stop_ids and done", fn, n_stop);
+  IVL_REQUIRE(!budget || (n_new && done), IVL_ERR_INVALID_ARG, "%s: budget needs n_new and done", fn);
+  IVL_REQUIRE(!history || (n_new && hist_ld >= 1), IVL_ERR_INVALID_ARG, "%s: history needs n_new and hist_ld >= 1 (%lld)", fn,
+              (long long)hist_ld);
+  if (!rep_penalty && !seen && n_stop == 0 && !budget && !n_new && !done && !history)      // no control: the control-free kernel
+    return ivl_sample_rows_fwd(logits, ld, S, V, temperature, top_k, top_p, seed, counter, token, token_stride, n_kept, prob,
+                               stream);
+  SmpCtl c;
+  c.rep_penalty = rep_penalty;
+  c.seen = seen;
+  c.seen_ld = seen_ld;
+  c.stop_ids = (const long long*)stop_ids;
+  c.n_stop = n_stop;
+  c.budget = (const long long*)budget;
+  c.fill = (const long long*)fill;
+  c.n_new = (long long*)n_new;
+  c.done = done;
+  c.history = (long long*)history;
+  c.hist_ld = hist_ld;
+  hipLaunchKernelGGL(sample_rows_kernel<SmpCtl>, dim3((unsigned)S), dim3(SMP_THREADS), 0, (hipStream_t)stream,
+                     (const bf16_t*)logits, (long long)ld, V, temperature, (const int*)top_k, top_p, (const long long*)seed,
+                     (long long*)counter, (long long*)token, (long long)token_stride, (int*)n_kept, prob, c);
+  return check_launch(fn);
+}
+
+extern "C" int ivl_token_mark_fwd(uint32_t* seen_row, int64_t V, const int64_t* ids, int64_t n, void* stream) {
+  using namespace ivl;
+  IVL_REQUIRE(seen_row && V >= 1 && n >= 0 && (n == 0 || ids), IVL_ERR_INVALID_ARG, "ivl_token_mark_fwd: seen_row=%p V=%lld n=%lld",
+              (void*)seen_row, (long long)V, (long long)n);
+  if (n == 0) return IVL_OK;
+  const long long blocks = (n + 255) / 256;
+  hipLaunchKernelGGL(token_mark_kernel, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(256), 0, (hipStream_t)stream,
+                     (unsigned*)seen_row, (long long)V, (const long long*)ids, (long long)n);
+  return check_launch("ivl_token_mark_fwd");
 }

@@ -401,27 +401,55 @@ class Sampler:
     seed / counter of ops.sample_tokens, one row per batch row (GraphedDecode) or slot (GraphedMultiStreamDecode).  A captured
     step reads the table at replay, so a row set between replays samples with its new parameters on the next one, without a
     recapture -- like the per-slot ring positions.  Rows start greedy (temperature 0: the lowest-index arg-max, no draw).
-    The generation arguments of the reference (do_sample / temperature / top_p / top_k: api/chat.py:160-162) map onto set()."""
+    The generation arguments of the reference (do_sample / temperature / top_p / top_k: api/chat.py:160-162) map onto set().
 
-    def __init__(self, n_rows: int, device):
+    Generation controls (repetition_penalty / eos_token_id / max_new_tokens of chat/hf_engine.py:128-156) live in the same
+    table and act inside the same launch (ivl_sample_rows_ctl_fwd): a sampler built with `vocab_size` (the bitmap of seen
+    tokens the penalty needs) or `history` (a ring of the last `history` tokens per row) uses the controlled launch; one
+    built without either samples exactly as before, until a row is given stop ids or a budget -- set that before the step is
+    captured (the graphed classes recapture when they see the switch).  The kernel keeps n_new (tokens generated) and done
+    (0 running, 1 stop id, 2 budget) per row; a finished row gets its fill token until it is set or reset again."""
+
+    def __init__(self, n_rows: int, device, vocab_size: Optional[int] = None, max_stop: int = 8, history: int = 0):
         if n_rows < 1:
             raise ValueError(f"Sampler: n_rows must be >= 1; got {n_rows}")
+        if vocab_size is not None and (isinstance(vocab_size, bool) or not isinstance(vocab_size, int) or vocab_size < 1):
+            raise ValueError(f"Sampler: vocab_size must be an int >= 1; got {vocab_size!r}")
+        if isinstance(max_stop, bool) or not isinstance(max_stop, int) or not 0 <= max_stop <= 16:
+            raise ValueError(f"Sampler: max_stop must be an int in [0, 16]; got {max_stop!r}")
+        if isinstance(history, bool) or not isinstance(history, int) or history < 0:
+            raise ValueError(f"Sampler: history must be an int >= 0; got {history!r}")
         self.n_rows = int(n_rows)
         self.temperature = torch.zeros(n_rows, dtype=torch.float32, device=device)
         self.top_k = torch.zeros(n_rows, dtype=torch.int32, device=device)
         self.top_p = torch.ones(n_rows, dtype=torch.float32, device=device)
         self.seed = torch.zeros(n_rows, dtype=torch.int64, device=device)
         self.counter = torch.zeros(n_rows, dtype=torch.int64, device=device)      # draws made so far; the kernel advances it
+        self.vocab_size, self.max_stop, self.history_len = vocab_size, max_stop, history
+        self.controlled = vocab_size is not None or history > 0
+        self.rep_penalty = torch.ones(n_rows, dtype=torch.float32, device=device)
+        self.seen = None if vocab_size is None else torch.zeros(n_rows, (vocab_size + 31) // 32, dtype=torch.int32, device=device)
+        self.stop_ids = torch.full((n_rows, max_stop), -1, dtype=torch.int64, device=device) if max_stop else None
+        self.budget = torch.full((n_rows,), -1, dtype=torch.int64, device=device)
+        self.fill = torch.zeros(n_rows, dtype=torch.int64, device=device)
+        self.n_new = torch.zeros(n_rows, dtype=torch.int64, device=device)        # tokens generated; the kernel advances it
+        self.done = torch.zeros(n_rows, dtype=torch.int32, device=device)         # 0 running, 1 stop id, 2 budget
+        self.history = torch.zeros(n_rows, history, dtype=torch.int64, device=device) if history else None
+        self._ends = [False] * n_rows                    # rows with a stop id or a budget (host copy, for run_until_done)
 
     def _row(self, row: int) -> int:
         if not isinstance(row, int) or not 0 <= row < self.n_rows:
             raise ValueError(f"Sampler: row must be an int in [0, {self.n_rows}); got {row!r}")
         return row
 
-    def set(self, row: int, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0) -> None:
-        """Parameters and a fresh random stream (counter 0) for `row`.  temperature 0 = greedy; top_k 0 and top_p 1 = off."""
+    def set(self, row: int, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0,
+            repetition_penalty: float = 1.0, stop_token_ids=(), max_new_tokens: Optional[int] = None, fill_token: int = 0) -> None:
+        """Parameters and a fresh stream for `row`: counter 0, and the row's bitmap, n_new, done and history cleared.
+        temperature 0 = greedy; top_k 0 and top_p 1 = off; repetition_penalty 1 = off (else finite and > 0: needs a sampler
+        built with vocab_size); stop_token_ids: at most max_stop ints >= 0; max_new_tokens: None or an int >= 1; fill_token:
+        what the row's token becomes once it is done."""
         row = self._row(row)
-        temperature, top_p = float(temperature), float(top_p)
+        temperature, top_p, repetition_penalty = float(temperature), float(top_p), float(repetition_penalty)
         if not (math.isfinite(temperature) and temperature >= 0.0):
             raise ValueError(f"Sampler.set: temperature must be finite and >= 0; got {temperature}")
         if isinstance(top_k, bool) or not isinstance(top_k, int) or not 0 <= top_k < 2 ** 31:
@@ -430,28 +458,98 @@ class Sampler:
             raise ValueError(f"Sampler.set: top_p must be in (0, 1]; got {top_p}")
         if isinstance(seed, bool) or not isinstance(seed, int) or not -2 ** 63 <= seed < 2 ** 64:
             raise ValueError(f"Sampler.set: seed must be a 64-bit int; got {seed!r}")
+        if not (math.isfinite(repetition_penalty) and repetition_penalty > 0.0):
+            raise ValueError(f"Sampler.set: repetition_penalty must be finite and > 0; got {repetition_penalty}")
+        if repetition_penalty != 1.0 and self.seen is None:
+            raise ValueError("Sampler.set: a repetition_penalty needs a Sampler built with vocab_size (the bitmap of seen tokens)")
+        stop = list(stop_token_ids)
+        if len(stop) > self.max_stop or any(isinstance(t, bool) or not isinstance(t, int) or not 0 <= t < 2 ** 63 for t in stop):
+            raise ValueError(f"Sampler.set: stop_token_ids must be at most {self.max_stop} ints >= 0; got {stop_token_ids!r}")
+        if max_new_tokens is not None and (isinstance(max_new_tokens, bool) or not isinstance(max_new_tokens, int)
+                                           or not 1 <= max_new_tokens < 2 ** 63):
+            raise ValueError(f"Sampler.set: max_new_tokens must be None or an int >= 1; got {max_new_tokens!r}")
+        if isinstance(fill_token, bool) or not isinstance(fill_token, int) or not 0 <= fill_token < 2 ** 63:
+            raise ValueError(f"Sampler.set: fill_token must be an int >= 0; got {fill_token!r}")
         self.temperature[row] = temperature
         self.top_k[row] = top_k
         self.top_p[row] = top_p
         self.seed[row] = seed - 2 ** 64 if seed >= 2 ** 63 else seed
         self.counter[row] = 0
+        self.rep_penalty[row] = repetition_penalty
+        if self.stop_ids is not None:
+            self.stop_ids[row] = torch.tensor(stop + [-1] * (self.max_stop - len(stop)), dtype=torch.int64)
+        self.budget[row] = -1 if max_new_tokens is None else max_new_tokens
+        self.fill[row] = fill_token
+        self.n_new[row] = 0
+        self.done[row] = 0
+        if self.seen is not None:
+            self.seen[row].zero_()
+        if self.history is not None:
+            self.history[row].zero_()
+        self._ends[row] = bool(stop) or max_new_tokens is not None
+        if self._ends[row]:
+            self.controlled = True
 
     def reset(self, row: int) -> None:
-        """Back to greedy."""
+        """Back to greedy, with every control off and the row's state cleared."""
         self.set(row)
 
-    def state(self) -> torch.Tensor:
-        """The counters (what a step changes), for a save around a capture's warm-up."""
-        return self.counter.clone()
+    def mark(self, row: int, ids: torch.Tensor) -> None:
+        """Mark the prompt's tokens `ids` (int64 [T] or [1,T], on the sampler's device) as seen by `row`: after set(), before
+        the row's first draw."""
+        row = self._row(row)
+        if self.seen is None:
+            raise ValueError("Sampler.mark: needs a Sampler built with vocab_size (the bitmap of seen tokens)")
+        if ids.dtype != torch.int64 or not (ids.dim() == 1 or (ids.dim() == 2 and ids.shape[0] == 1)):
+            raise ValueError(f"Sampler.mark: ids must be int64 [T] or [1,T]; got {ids.dtype} {tuple(ids.shape)}")
+        ops.mark_tokens(self.seen[row], ids, self.vocab_size)
 
-    def load_state(self, state: torch.Tensor) -> None:
-        self.counter.copy_(state)
+    def _stateful(self):
+        return {k: t for k, t in (("counter", self.counter), ("seen", self.seen), ("n_new", self.n_new), ("done", self.done),
+                                  ("history", self.history)) if t is not None}
+
+    def state(self) -> Dict[str, torch.Tensor]:
+        """Everything a step changes (counter, seen, n_new, done, history), for a save around a capture's warm-up."""
+        return {k: t.clone() for k, t in self._stateful().items()}
+
+    def load_state(self, state: Dict[str, torch.Tensor]) -> None:
+        mine = self._stateful()
+        if set(state) != set(mine):
+            raise ValueError(f"Sampler.load_state: the state holds {sorted(state)}, this sampler {sorted(mine)}")
+        for k, t in mine.items():
+            t.copy_(state[k])
+
+    def poll(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(done, n_new) of every row on the host, int64 [n_rows] each, in one copy (it waits for the steps queued so far)."""
+        both = torch.stack([self.done.to(torch.int64), self.n_new]).cpu()
+        return both[0], both[1]
+
+    def tokens(self, row: int) -> torch.Tensor:
+        """The tokens `row` has generated, from its history (host, int64): the first min(n_new, history) entries in order; of a
+        row that generated more than `history` tokens, the last `history` of them, oldest first."""
+        row = self._row(row)
+        if self.history is None:
+            raise ValueError("Sampler.tokens: needs a Sampler built with history > 0")
+        h, n = self.history[row].cpu(), int(self.n_new[row].item())
+        if n <= self.history_len:
+            return h[:n].clone()
+        a = n % self.history_len
+        return torch.cat([h[a:], h[:a]])
 
     def sample(self, logits: torch.Tensor, out: torch.Tensor, row: Optional[int] = None) -> torch.Tensor:
         """Tokens of every row (logits [n_rows,V]) or of the one `row` (logits [1,V]; views of the table, no copy) into `out`."""
         sl = slice(None) if row is None else slice(row, row + 1)
+        if not self.controlled:
+            return ops.sample_tokens(logits, self.temperature[sl], self.top_k[sl], self.top_p[sl], self.seed[sl], self.counter[sl],
+                                     out=out)
+        if self.seen is not None and logits.shape[-1] != self.vocab_size:
+            raise ValueError(f"Sampler.sample: logits of {logits.shape[-1]} tokens for a sampler of vocab_size {self.vocab_size}")
         return ops.sample_tokens(logits, self.temperature[sl], self.top_k[sl], self.top_p[sl], self.seed[sl], self.counter[sl],
-                                 out=out)
+                                 out=out, rep_penalty=self.rep_penalty[sl] if self.seen is not None else None,
+                                 seen=self.seen[sl] if self.seen is not None else None,
+                                 stop_ids=self.stop_ids[sl] if self.stop_ids is not None else None, budget=self.budget[sl],
+                                 fill=self.fill[sl], n_new=self.n_new[sl], done=self.done[sl],
+                                 history=self.history[sl] if self.history is not None else None)
 
 
 class GraphedDecode:
@@ -471,6 +569,7 @@ class GraphedDecode:
         self.logits = None
         self.graph: Optional[torch.cuda.CUDAGraph] = None
         self._warmup = warmup
+        self._captured_controlled = False
 
     def _run(self):
         _, lg = self.model(input_ids=self.token, position_ids=self.position_ids, past_key_values=self.cache,
@@ -500,10 +599,11 @@ class GraphedDecode:
         self.token.copy_(saved_tok)
         if self.sampler is not None:
             self.sampler.load_state(saved_smp)          # the warm-up and the capture itself made draws
+            self._captured_controlled = self.sampler.controlled
 
     def step(self):
         """One decode step; the new token is left in self.token (device)."""
-        if self.graph is None:
+        if self.graph is None or (self.sampler is not None and self.sampler.controlled != self._captured_controlled):
             self.capture()
         self.cache.ensure_started()
         self.graph.replay()
@@ -534,6 +634,8 @@ class GraphedMultiStreamDecode:
         self.logits = self.admit_logits = None
         self.graph: Optional[torch.cuda.CUDAGraph] = None
         self._warmup = warmup
+        self._captured_controlled = False
+        self._live = set()                               # slots between admit and release
 
     def _run(self):
         _, lg = self.model(input_ids=self.token, position_ids=self.position_ids, past_key_values=self.cache,
@@ -563,15 +665,21 @@ class GraphedMultiStreamDecode:
         self.token.copy_(saved_tok)
         if self.sampler is not None:
             self.sampler.load_state(saved_smp)          # the warm-up and the capture itself made draws
+            self._captured_controlled = self.sampler.controlled
 
     @torch.no_grad()
     def admit(self, slot: int, inputs_embeds: torch.Tensor, position_ids: Optional[torch.Tensor] = None,
-              sampling: Optional[dict] = None) -> torch.Tensor:
+              sampling: Optional[dict] = None, prompt_ids: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Start a stream in `slot` with a prompt inputs_embeds [1,T,hidden] (M-RoPE position_ids [3,1,T]; default: text
         positions 0..T-1).  Its first generated token is written to token[slot] and returned.  `sampling`: the keyword
-        arguments of Sampler.set for this stream (needs a sampler), applied before that first token is drawn."""
+        arguments of Sampler.set for this stream (needs a sampler), applied before that first token is drawn.  `prompt_ids`
+        (int64 [T] or [1,T]): the prompt's tokens, marked as seen for the repetition penalty after the row is set and before the
+        first token is drawn; that token goes through the same controlled launch as every later one, so it is counted, logged
+        and may already end the stream."""
         if sampling is not None and self.sampler is None:
             raise ValueError("admit: sampling parameters need a GraphedMultiStreamDecode built with a sampler")
+        if prompt_ids is not None and self.sampler is None:
+            raise ValueError("admit: prompt_ids need a GraphedMultiStreamDecode built with a sampler")
         if inputs_embeds.dim() != 3 or inputs_embeds.shape[0] != 1:
             raise ValueError(f"admit: inputs_embeds must be [1,T,hidden]; got {tuple(inputs_embeds.shape)}")
         T = inputs_embeds.shape[1]
@@ -581,7 +689,10 @@ class GraphedMultiStreamDecode:
             raise ValueError(f"admit: position_ids must be [3,1,{T}]; got {tuple(position_ids.shape)}")
         if sampling is not None:
             self.sampler.set(slot, **sampling)
+        if prompt_ids is not None:
+            self.sampler.mark(slot, prompt_ids.to(inputs_embeds.device))
         self.cache.admit(slot)
+        self._live.add(slot)
         view = self.cache.slot_view(slot)
         lg = None
         for a in range(0, T, self.PREFILL_CHUNK):
@@ -599,6 +710,7 @@ class GraphedMultiStreamDecode:
     def release(self, slot: int) -> None:
         """End the stream in `slot`: its state is zeroed (the slot keeps computing on zeros until the next admit)."""
         self.cache.release(slot)
+        self._live.discard(slot)
         if self.sampler is not None:
             self.sampler.reset(slot)
         self.token[slot].zero_()
@@ -611,11 +723,31 @@ class GraphedMultiStreamDecode:
             with torch.no_grad():
                 self.logits = self._run()
             return self.token
-        if self.graph is None:
+        if self.graph is None or (self.sampler is not None and self.sampler.controlled != self._captured_controlled):
             self.capture()
         self.graph.replay()
         self.cache.advance(1)
         return self.token
+
+    def run_until_done(self, max_steps: int, poll_every: int = 16) -> Dict[int, torch.Tensor]:
+        """Replay up to `max_steps` steps without a host round trip per token: the sampler's done flags are polled every
+        `poll_every` steps, and the loop ends once every live slot that has a stop id or a budget is done (or at max_steps; it
+        runs to max_steps when no live slot has either).  Returns {slot: the slot's generated tokens} of the live slots, from
+        the sampler's history.  A finished slot keeps computing on its fill token until it is released."""
+        if self.sampler is None or self.sampler.history is None:
+            raise ValueError("run_until_done: needs a sampler built with history > 0")
+        if max_steps < 0 or poll_every < 1:
+            raise ValueError(f"run_until_done: max_steps >= 0 and poll_every >= 1; got {max_steps}, {poll_every}")
+        watched = [s for s in sorted(self._live) if self.sampler._ends[s]]
+        steps = 0
+        while steps < max_steps:
+            if watched and bool((self.sampler.poll()[0][watched] != 0).all()):
+                break
+            n = min(poll_every, max_steps - steps)
+            for _ in range(n):
+                self.step()
+            steps += n
+        return {s: self.sampler.tokens(s) for s in sorted(self._live)}
 
 
 @torch.no_grad()

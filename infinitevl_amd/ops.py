@@ -1196,13 +1196,24 @@ def swa_attention_interface(module, query, key, value, attention_mask=None, drop
 # ---------------------------------------------------------------------------------------------
 def sample_tokens(logits: torch.Tensor, temperature: torch.Tensor, top_k: torch.Tensor, top_p: torch.Tensor, seed: torch.Tensor,
                   counter: torch.Tensor, out: Optional[torch.Tensor] = None, n_kept: Optional[torch.Tensor] = None,
-                  prob: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  prob: Optional[torch.Tensor] = None, *, rep_penalty: Optional[torch.Tensor] = None,
+                  seen: Optional[torch.Tensor] = None, stop_ids: Optional[torch.Tensor] = None,
+                  budget: Optional[torch.Tensor] = None, fill: Optional[torch.Tensor] = None,
+                  n_new: Optional[torch.Tensor] = None, done: Optional[torch.Tensor] = None,
+                  history: Optional[torch.Tensor] = None) -> torch.Tensor:
     """One next token per row of lm_head logits [S,V] or [S,1,V] (bf16, last dim contiguous) in one launch: temperature,
     top-k, top-p and the draw, per row (ivl_sample_rows_fwd states the semantics; HF generate's warpers + multinomial,
     api/chat.py:160-162 of the reference).  temperature / top_k / top_p / seed / counter: [S] fp32 / int32 / fp32 / int64 /
     int64; a row with temperature <= 0 takes the lowest-index arg-max.  counter[s] (draws made so far) is advanced by the
     kernel for every row that draws: the token is a pure function of (logits, parameters, seed, counter).  `out`: int64 [S]
-    or [S,1], written in place and returned (default: a new [S]); n_kept [S] int32 and prob [S] fp32 are optional outputs."""
+    or [S,1], written in place and returned (default: a new [S]); n_kept [S] int32 and prob [S] fp32 are optional outputs.
+
+    The keyword-only generation controls (ivl_sample_rows_ctl_fwd states the semantics; repetition_penalty / eos_token_id /
+    max_new_tokens of the reference's chat/hf_engine.py:128-156), each optional: rep_penalty [S] fp32 with seen [S,W] int32
+    (a bitmap of W >= ceil(V/32) words per row, updated by the kernel); stop_ids [S,n] int64 (n <= 16, entries < 0 unused),
+    budget [S] int64 (< 0: none) and fill [S] int64 with the state n_new [S] int64, done [S] int32 (0 running, 1 stop id,
+    2 budget; a finished row gets its fill token and nothing else of it is touched) and history [S,H] int64 (a ring of the
+    last H tokens).  With none given this is the control-free launch."""
     if logits.dim() == 3 and logits.shape[1] == 1:
         logits = logits[:, 0]
     if logits.dim() != 2 or logits.dtype != torch.bfloat16 or logits.shape[0] < 1 or logits.shape[1] < 1:
@@ -1212,17 +1223,62 @@ def sample_tokens(logits: torch.Tensor, temperature: torch.Tensor, top_k: torch.
         raise ValueError(f"sample_tokens: the last dim of logits must be contiguous and the rows apart (strides {logits.stride()})")
     for name, t, dt in (("temperature", temperature, torch.float32), ("top_k", top_k, torch.int32),
                         ("top_p", top_p, torch.float32), ("seed", seed, torch.int64), ("counter", counter, torch.int64),
-                        ("n_kept", n_kept, torch.int32), ("prob", prob, torch.float32)):
+                        ("n_kept", n_kept, torch.int32), ("prob", prob, torch.float32), ("rep_penalty", rep_penalty, torch.float32),
+                        ("budget", budget, torch.int64), ("fill", fill, torch.int64), ("n_new", n_new, torch.int64),
+                        ("done", done, torch.int32)):
         if t is None:
             continue
         if t.dtype != dt or tuple(t.shape) != (S,) or not t.is_contiguous():
             raise ValueError(f"sample_tokens: {name} must be a contiguous {dt} tensor of [{S}]; got {t.dtype} {tuple(t.shape)}")
+    for name, t, dt in (("seen", seen, torch.int32), ("stop_ids", stop_ids, torch.int64), ("history", history, torch.int64)):
+        if t is None:
+            continue
+        if t.dtype != dt or t.dim() != 2 or t.shape[0] != S or t.stride(1) != 1 or (S > 1 and t.stride(0) < t.shape[1]):
+            raise ValueError(f"sample_tokens: {name} must be a {dt} tensor of [{S},n] with contiguous rows; got {t.dtype} "
+                             f"{tuple(t.shape)} strides {t.stride()}")
+    if seen is not None and seen.shape[1] * 32 < V:
+        raise ValueError(f"sample_tokens: seen has {seen.shape[1]} words per row for V = {V} (needs {(V + 31) // 32})")
+    if rep_penalty is not None and seen is None:
+        raise ValueError("sample_tokens: rep_penalty needs the seen bitmap")
+    n_stop = 0 if stop_ids is None else stop_ids.shape[1]
+    if n_stop > 16 or (stop_ids is not None and (n_stop < 1 or not stop_ids.is_contiguous())):
+        raise ValueError(f"sample_tokens: stop_ids must be contiguous [{S},n] with 1 <= n <= 16; got {tuple(stop_ids.shape)}")
+    if n_stop > 0 and done is None:
+        raise ValueError("sample_tokens: stop_ids needs done")
+    if budget is not None and (n_new is None or done is None):
+        raise ValueError("sample_tokens: budget needs n_new and done")
+    if history is not None and (n_new is None or history.shape[1] < 1):
+        raise ValueError("sample_tokens: history needs n_new and at least one entry per row")
     if out is None:
         out = torch.empty(S, dtype=torch.int64, device=logits.device)
     if out.dtype != torch.int64 or tuple(out.shape) not in ((S,), (S, 1)):
         raise ValueError(f"sample_tokens: out must be int64 [{S}] or [{S},1]; got {out.dtype} {tuple(out.shape)}")
-    _need_gpu(logits, temperature, top_k, top_p, seed, counter, out, n_kept, prob)
-    _lib.check(_lib.load().ivl_sample_rows_fwd(
+    controls = (rep_penalty, seen, stop_ids, budget, fill, n_new, done, history)
+    _need_gpu(logits, temperature, top_k, top_p, seed, counter, out, n_kept, prob, *controls)
+    if all(t is None for t in controls):
+        _lib.check(_lib.load().ivl_sample_rows_fwd(
+            _p(logits), logits.stride(0) if S > 1 else V, S, V, _p(temperature), _p(top_k), _p(top_p), _p(seed), _p(counter),
+            _p(out), out.stride(0) if S > 1 else 1, _p(n_kept), _p(prob), _stream(logits)))
+        return out
+    _lib.check(_lib.load().ivl_sample_rows_ctl_fwd(
         _p(logits), logits.stride(0) if S > 1 else V, S, V, _p(temperature), _p(top_k), _p(top_p), _p(seed), _p(counter),
-        _p(out), out.stride(0) if S > 1 else 1, _p(n_kept), _p(prob), _stream(logits)))
+        _p(out), out.stride(0) if S > 1 else 1, _p(n_kept), _p(prob), _p(rep_penalty), _p(seen),
+        0 if seen is None else (seen.stride(0) if S > 1 else seen.shape[1]), _p(stop_ids), n_stop, _p(budget), _p(fill), _p(n_new),
+        _p(done), _p(history), 0 if history is None else (history.stride(0) if S > 1 else history.shape[1]), _stream(logits)))
     return out
+
+
+def mark_tokens(seen_row: torch.Tensor, ids: torch.Tensor, vocab_size: int) -> None:
+    """Set the bits of `ids` (int64, any shape) in ONE row of a seen bitmap (int32 [W], W * 32 >= vocab_size): the prompt's
+    tokens, before the first draw of a row with a repetition penalty (ivl_token_mark_fwd).  Ids outside [0, vocab_size) are
+    ignored; duplicates and an empty `ids` are fine."""
+    if seen_row.dtype != torch.int32 or seen_row.dim() != 1 or not seen_row.is_contiguous():
+        raise ValueError(f"mark_tokens: seen_row must be a contiguous int32 [W]; got {seen_row.dtype} {tuple(seen_row.shape)}")
+    if isinstance(vocab_size, bool) or not isinstance(vocab_size, int) or not 1 <= vocab_size <= seen_row.shape[0] * 32:
+        raise ValueError(f"mark_tokens: vocab_size must be an int in [1, {seen_row.shape[0] * 32}]; got {vocab_size!r}")
+    if ids.dtype != torch.int64:
+        raise ValueError(f"mark_tokens: ids must be int64; got {ids.dtype}")
+    _need_gpu(seen_row, ids)
+    ids = ids.reshape(-1).contiguous()
+    _lib.check(_lib.load().ivl_token_mark_fwd(_p(seen_row), vocab_size, _p(ids) if ids.numel() else None, ids.numel(),
+                                              _stream(seen_row)))

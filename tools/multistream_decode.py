@@ -15,6 +15,14 @@ model's vocabulary (random logits and a row of equal logits, which sends every h
 argmax + copy_.  The bar for B and C is A + 2 %.
 
     python tools/multistream_decode.py --sampling --slots 1,4 [--out profiles/sampling_decode.json]
+
+--generation measures the generation controls of the same launch (repetition penalty, stop ids, token budget, history): per slot
+count the greedy step without a sampler (A), the sampled step (0.7 / 50 / 0.9) without controls (B) and the same with a
+repetition penalty of 1.3, two stop ids, a budget and a 256-entry history, the bitmap of seen tokens about 5 % full (C), timed
+A B A C per round; and the operator alone at the model's vocabulary with and without the controls.  C may exceed B by no more
+than the 2 % of A the sampling launch is granted as a whole.
+
+    python tools/multistream_decode.py --generation --slots 1,4 [--out profiles/generation_decode.json]
 """
 import argparse
 import json
@@ -35,6 +43,7 @@ def main():
     ap.add_argument("--slots", default="1,2,4")
     ap.add_argument("--out", default=None)
     ap.add_argument("--sampling", action="store_true", help="time the sampled step against the greedy one (see above)")
+    ap.add_argument("--generation", action="store_true", help="time the step with the generation controls (see above)")
     args = ap.parse_args()
     import torch
     from infinitevl_amd.cache import MultiStreamCache
@@ -63,6 +72,8 @@ def main():
 
     if args.sampling:
         return sampling_legs(args, torch, model, cfg, prompts, dev)
+    if args.generation:
+        return generation_legs(args, torch, model, cfg, prompts, dev)
 
     # reference: one stream on the existing B = 1 graphed decode step
     c1 = model.allocate_inference_cache(1)
@@ -180,6 +191,105 @@ def sampling_legs(args, torch, model, cfg, prompts, dev):
                 for s in range(S):
                     smp.set(s, seed=s, **kw)
                 op[f"S{S}_{rname}_{pname}_us"] = round(1000 * timed(lambda: smp.sample(lg, tok), 200), 2)
+    res["operator_V%d" % V] = op
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+CONTROLS = {"repetition_penalty": 1.3, "max_new_tokens": 1 << 40}     # + two stop ids; a budget no run reaches
+HISTORY = 256
+SEEN_FRACTION = 0.05
+
+
+def generation_legs(args, torch, model, cfg, prompts, dev):
+    from infinitevl_amd.cache import MultiStreamCache
+    from infinitevl_amd.harness import GraphedMultiStreamDecode, Sampler
+    stream = torch.cuda.current_stream()
+    V = cfg.vocab_size
+
+    def timed(fn, n):
+        for _ in range(4):
+            fn()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        for _ in range(n):
+            fn()
+        e1.record(stream)
+        e1.synchronize()
+        return e0.elapsed_time(e1) / n
+
+    def seen_ids(s):
+        g = torch.Generator().manual_seed(100 + s)
+        return torch.randperm(V, generator=g)[:int(SEEN_FRACTION * V)].to(dev)
+
+    def controls(s):
+        # a stop id the random model happens to draw would end the stream, and the rest of C would time the finished-row exit:
+        # the done flags are read back after the timing and reported (controlled_rows_still_live)
+        return dict(SAMPLED, seed=s + 1, stop_token_ids=[V - 1 - s, V - 9 - s], **CONTROLS)
+
+    slots = [int(s) for s in args.slots.split(",")]
+    res = {"tool": "multistream_decode --generation", "layers": cfg.num_hidden_layers, "window": 4096, "steps": args.steps,
+           "rounds": args.rounds, "sampled": SAMPLED, "controls": dict(CONTROLS, stop_ids=2, history=HISTORY,
+                                                                        seen_fraction=SEEN_FRACTION),
+           "bar": "controlled ms_per_step <= sampled ms_per_step + 2 % of greedy ms_per_step"}
+    for n in slots:
+        legs, samplers = {}, {}
+        for name in ("greedy", "sampled", "controlled"):
+            cache = MultiStreamCache(config=cfg, n_slots=n, device=dev, dtype=torch.bfloat16)
+            smp = None if name == "greedy" else (Sampler(n, dev) if name == "sampled" else Sampler(n, dev, vocab_size=V, history=HISTORY))
+            dec = GraphedMultiStreamDecode(model, cache, sampler=smp)
+            for s in range(n):
+                if name == "greedy":
+                    dec.admit(s, prompts[s])
+                elif name == "sampled":
+                    dec.admit(s, prompts[s], sampling=dict(SAMPLED, seed=s + 1))
+                else:
+                    dec.admit(s, prompts[s], sampling=controls(s), prompt_ids=seen_ids(s))
+            dec.capture()
+            legs[name], samplers[name] = dec.step, smp
+        times = {k: [] for k in legs}
+        for _ in range(args.rounds):                            # A B A C
+            for name in ("sampled", "controlled"):
+                times["greedy"].append(timed(legs["greedy"], args.steps))
+                times[name].append(timed(legs[name], args.steps))
+        a = statistics.median(times["greedy"])
+        b = statistics.median(times["sampled"])
+        c = statistics.median(times["controlled"])
+        done, n_new = samplers["controlled"].poll()
+        row = {"greedy_ms_per_step": round(a, 4), "greedy_spread_ms": [round(min(times["greedy"]), 4), round(max(times["greedy"]), 4)]}
+        for name, t in (("sampled", b), ("controlled", c)):
+            row[name] = {"ms_per_step": round(t, 4), "vs_greedy": round(t / a, 4), "delta_us": round(1000 * (t - a), 1),
+                         "spread_ms": [round(min(times[name]), 4), round(max(times[name]), 4)], "within_greedy_bar": bool(t <= 1.02 * a)}
+        row["controlled_minus_sampled_us"] = round(1000 * (c - b), 1)
+        row["allowance_us"] = round(1000 * 0.02 * a, 1)
+        row["controlled_within_allowance"] = bool(c - b <= 0.02 * a)
+        row["controlled_rows_still_live"] = bool((done == 0).all())          # else part of C timed the finished-row exit
+        row["controlled_tokens_per_row"] = n_new.tolist()
+        res[f"slots{n}"] = row
+        del legs, samplers
+    # the operator alone, back to back on one stream (launch-bound figures include the launch gap)
+    gen = torch.Generator(device=dev).manual_seed(1)
+    op = {}
+    for S in (1, 4):
+        lg = (torch.randn(S, V, generator=gen, device=dev) * 3.0).to(torch.bfloat16)
+        tok = torch.zeros(S, 1, dtype=torch.int64, device=dev)
+        for pname, kw in (("kernel_greedy", {}), ("sampled", SAMPLED)):
+            plain = Sampler(S, dev)
+            ctl = Sampler(S, dev, vocab_size=V, history=HISTORY)
+            r1 = Sampler(S, dev, vocab_size=V, history=HISTORY)
+            for s in range(S):
+                plain.set(s, seed=s, **kw)
+                ctl.set(s, seed=s, stop_token_ids=[V - 1 - s, V - 9 - s], **CONTROLS, **kw)
+                ctl.mark(s, seen_ids(s))
+                r1.set(s, seed=s, stop_token_ids=[V - 1 - s, V - 9 - s], max_new_tokens=1 << 40, **kw)
+            op[f"S{S}_{pname}_us"] = round(1000 * timed(lambda: plain.sample(lg, tok), 200), 2)
+            op[f"S{S}_{pname}_controls_penalty_off_us"] = round(1000 * timed(lambda: r1.sample(lg, tok), 200), 2)
+            op[f"S{S}_{pname}_controls_us"] = round(1000 * timed(lambda: ctl.sample(lg, tok), 200), 2)
+            op[f"S{S}_{pname}_controls_rows_still_live"] = bool((ctl.poll()[0] == 0).all() and (r1.poll()[0] == 0).all())
     res["operator_V%d" % V] = op
     line = json.dumps(res)
     print(line)
