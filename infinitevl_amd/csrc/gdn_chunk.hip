@@ -34,7 +34,7 @@
 // the DMA that fills it is a plain linear copy of the record.
 #include <mutex>
 
-#include "ivl_common.h"
+#include "ivl_rowwise.h"
 #include <type_traits>
 
 namespace ivl {
@@ -205,8 +205,8 @@ __device__ __forceinline__ u32x4 frag_tr32(const bf16_t* X, int ld, int k0, int 
 // Fused front end (FUSED = true): the pre-pass reads the mixer's ONE projection buffer itself and applies the three causal
 // short convolutions (kernel 4, + SiLU, carry-in from / carry-out to the conv states, fla:modules/convolution.py via
 // std:1253-1283) and the gate math (std:1293-1294) on the way in - the q / k / v / g / beta tensors of the unfused path never
-// exist in HBM and the separate prologue launch disappears.  Same arithmetic, same bf16 rounding points as
-// ivl_gdn_prologue_fwd followed by the plain pre-pass: the two paths agree bit for bit.
+// exist in HBM and the separate prologue launch disappears.  The bf16 rounding points are those of ivl_gdn_prologue_fwd
+// followed by the plain pre-pass (gate math: gdn_gate_; conv: conv4_silu): the two paths agree bit for bit.
 struct PrepFused {
   const bf16_t* proj; long long ld;                 // [B*T, ld] bf16
   int col_q, col_k, col_v, col_a, col_b;            // first column of q / k / v (head 0) and of the a / b gate inputs
@@ -218,7 +218,7 @@ struct PrepFused {
 
 // causal 4-tap conv + SiLU of NR consecutive tokens x 8 channels: xr[0..2] = the three tokens before the run, xr[3..] the
 // run; taps of channel c = (w[c / 2] .x/.y | .z/.w).  fp32 accumulation in tap order, output rounded to bf16 (the unfused
-// path's tensors are bf16).
+// path's tensors are bf16).  Must agree with the scalar conv4_taps_ + a * sigmoidf_(a) (ivl_rowwise.h) bit for bit.
 template <int NR>
 __device__ __forceinline__ void conv4_silu(const u32x4* xr, const u32x4* w, u32x4* out) {
   // two channels per instruction (v_pk_mul_f32 / v_pk_fma_f32 / v_pk_add_f32; component-wise IEEE, so the results are those
@@ -347,11 +347,9 @@ __device__ __forceinline__ void gdn_chunk_prepare_body(
   // wave 1 the last arrival at B1 by its whole length (~1,800 cycles).
   auto p1a = [&]() {
     float g_ld, b_ld;
-    if constexpr (FUSED) {                           // g = -exp(A_log) softplus(a + dt_bias), beta = bf16(sigmoid(b)) (std:1293-1294)
-      const float av = p1_g + p1_dt;
-      const float sp = av > 20.f ? av : log1pf(expf(av));
-      g_ld = -expf(p1_A) * sp;
-      b_ld = bf2f(f2bf(sigmoid_exact_(p1_b)));
+    if constexpr (FUSED) {                           // beta is a bf16 tensor in the unfused path
+      gdn_gate_(p1_g, p1_dt, p1_b, &p1_A, g_ld, b_ld);
+      b_ld = bf_round(b_ld);
     } else {
       g_ld = p1_g;
       b_ld = p1_b;

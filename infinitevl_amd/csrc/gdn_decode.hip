@@ -8,7 +8,7 @@
 //
 // One workgroup per (batch, head), 8 waves.  State S[128][256] lives in registers: wave w owns rows 16w..16w+15,
 // lane l owns columns 4l..4l+3 (a wave reads/writes one whole 512-byte state row per instruction).
-#include "ivl_common.h"
+#include "ivl_rowwise.h"
 
 namespace ivl {
 
@@ -28,17 +28,15 @@ struct DecParams {
   int H; float scale;
 };
 
-// one channel of a width-4 causal conv at T == 1: taps over (state[1], state[2], state[3], x); new state = those 4
+// one channel of a width-4 causal conv + SiLU at T == 1: taps over (state[1], state[2], state[3], x), rounded to bf16 as the
+// prologue stores it; SHIFT: the state becomes those 4 (in place)
+template <bool SHIFT = true>
 __device__ __forceinline__ float conv1(const bf16_t* xrow, int col, const bf16_t* w, int wch, bf16_t* st, size_t ch) {
   const u32x2 wv = *(const u32x2*)(w + (size_t)wch * 4);      // taps of channel wch
   const u32x2 sv = *(const u32x2*)(st + ch * 4);              // state of (batch, channel)
   const bf16_t xr = xrow[col];
-  const float x = bf2f(xr);
-  float a = bflo(wv.x) * bfhi(sv.x);
-  a = fmaf(bfhi(wv.x), bflo(sv.y), a);
-  a = fmaf(bflo(wv.y), bfhi(sv.y), a);
-  a = fmaf(bfhi(wv.y), x, a);
-  *(u32x2*)(st + ch * 4) = u32x2{(sv.x >> 16) | (sv.y << 16), (sv.y >> 16) | ((unsigned int)xr << 16)};
+  const float a = conv4_taps_(bflo(wv.x), bfhi(wv.x), bflo(wv.y), bfhi(wv.y), bfhi(sv.x), bflo(sv.y), bfhi(sv.y), bf2f(xr));
+  if constexpr (SHIFT) *(u32x2*)(st + ch * 4) = conv_state_shift1_(sv, xr);
   return bf_round(a * sigmoidf_(a));
 }
 
@@ -99,13 +97,10 @@ __global__ __launch_bounds__(64 * DNW) void gdn_decode_step_kernel(DEC_HEAD_PARA
     if (lane == 0) s_part[wave][0] = ss;
   }
   if (tid == 0) {
-    // gate math (std:1293-1294) at the prologue kernel's rounding points
-    const float av = bf2f(xrow[p.col_a + h]) + p.dt_bias[h];
-    const float bv = bf2f(xrow[p.col_b + h]);
-    const float sp = av > 20.f ? av : log1pf(expf(av));
-    const float g = -expf(p.A_log[h]) * sp;
+    float g, beta;
+    gdn_gate_(bf2f(xrow[p.col_a + h]), p.dt_bias[h], bf2f(xrow[p.col_b + h]), p.A_log + h, g, beta);
     s_sc[0] = __expf(g);
-    s_sc[1] = bf_round(sigmoid_exact_(bv));
+    s_sc[1] = bf_round(beta);                                           // the prologue stores beta in bf16
   }
   __syncthreads();
   if (tid < 2 * DK) {
@@ -173,14 +168,13 @@ __global__ __launch_bounds__(64 * DNW) void gdn_decode_step_kernel(DEC_HEAD_PARA
   // ---- gated RMSNorm over the head's 256 outputs (every wave holds all of them, 4 per lane) -----------
   if (wave == 0) {
     const float ss = wave_sum(o4[0] * o4[0] + o4[1] * o4[1] + o4[2] * o4[2] + o4[3] * o4[3]);
-    const float rstd = 1.0f / sqrtf(ss * (1.0f / 256.0f) + p.eps);
+    const float rstd = rms256_rstd_(ss, p.eps);
     const u32x2 wv = *(const u32x2*)(p.norm_w + 4 * lane);
     const u32x2 gv = *(const u32x2*)(xrow + p.col_g + h * DV + 4 * lane);
     const float wf[4] = {bflo(wv.x), bfhi(wv.x), bflo(wv.y), bfhi(wv.y)};
     const float gf[4] = {bflo(gv.x), bfhi(gv.x), bflo(gv.y), bfhi(gv.y)};
     float y4[4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) y4[c] = o4[c] * rstd * wf[c] * gf[c] * sigmoidf_(gf[c]);
+    gated_norm_n_(o4, rstd, wf, gf, y4);
     *(u32x2*)(p.y + ((size_t)b * p.H + h) * DV + 4 * lane) = u32x2{pack2bf(y4[0], y4[1]), pack2bf(y4[2], y4[3])};
   }
 }
@@ -199,16 +193,6 @@ __global__ __launch_bounds__(64 * DNW) void gdn_decode_step_kernel(DEC_HEAD_PARA
 // bit-identical to it.
 constexpr int DSQ = 4;                 // column quarters per head
 constexpr int DSC = DV / DSQ;          // 64 columns per workgroup
-__device__ __forceinline__ float conv1_ro(const bf16_t* xrow, int col, const bf16_t* w, int wch, const bf16_t* st, size_t ch) {
-  const u32x2 wv = *(const u32x2*)(w + (size_t)wch * 4);
-  const u32x2 sv = *(const u32x2*)(st + ch * 4);
-  const float x = bf2f(xrow[col]);
-  float a = bflo(wv.x) * bfhi(sv.x);
-  a = fmaf(bfhi(wv.x), bflo(sv.y), a);
-  a = fmaf(bflo(wv.y), bfhi(sv.y), a);
-  a = fmaf(bfhi(wv.y), x, a);
-  return bf_round(a * sigmoidf_(a));
-}
 
 __global__ __launch_bounds__(256) void gdn_decode_split_kernel(DEC_HEAD_PARAMS, DecParams p) {
   DEC_HEAD_APPLY(p);
@@ -243,20 +227,18 @@ __global__ __launch_bounds__(256) void gdn_decode_split_kernel(DEC_HEAD_PARAMS, 
   // v channel 64 qt + tid (tid < 64): column-local, shifted in place
   const int Dq = p.H * DK, Dv = p.H * DV;
   float qk;
-  if (tid < DK) qk = conv1_ro(xrow, p.col_q + h * DK + tid, p.wq, h * DK + tid, p.cq, (size_t)b * Dq + h * DK + tid);
-  else qk = conv1_ro(xrow, p.col_k + h * DK + (tid - DK), p.wk, h * DK + tid - DK, p.ck, (size_t)b * Dq + h * DK + (tid - DK));
+  if (tid < DK) qk = conv1<false>(xrow, p.col_q + h * DK + tid, p.wq, h * DK + tid, p.cq, (size_t)b * Dq + h * DK + tid);
+  else qk = conv1<false>(xrow, p.col_k + h * DK + (tid - DK), p.wk, h * DK + tid - DK, p.ck, (size_t)b * Dq + h * DK + (tid - DK));
   if (tid < DSC) s_v[tid] = conv1(xrow, p.col_v + h * DV + DSC * qt + tid, p.wv, h * DV + DSC * qt + tid, p.cv, (size_t)b * Dv + h * DV + DSC * qt + tid);
   {
     const float ss = wave_sum(qk * qk);
     if (lane == 0) s_part[wave][0] = ss;
   }
   if (tid == 0) {
-    const float av = bf2f(xrow[p.col_a + h]) + p.dt_bias[h];
-    const float bv = bf2f(xrow[p.col_b + h]);
-    const float sp = av > 20.f ? av : log1pf(expf(av));
-    const float g = -expf(p.A_log[h]) * sp;
+    float g, beta;
+    gdn_gate_(bf2f(xrow[p.col_a + h]), p.dt_bias[h], bf2f(xrow[p.col_b + h]), p.A_log + h, g, beta);
     s_sc[0] = __expf(g);
-    s_sc[1] = bf_round(sigmoid_exact_(bv));
+    s_sc[1] = bf_round(beta);                                           // the prologue stores beta in bf16
   }
   __syncthreads();
   {

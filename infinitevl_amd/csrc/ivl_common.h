@@ -85,6 +85,12 @@ __device__ __forceinline__ float wave_sum(float v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+// the sum over the 32 lanes of the caller's half of the wavefront
+__device__ __forceinline__ float half_wave_sum(float v) {
+#pragma unroll
+  for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
 
 // v_rcp_f32 (1 ulp) instead of an IEEE division (~10 instructions): every SiLU / swish gate of the package goes through
 // here (the results are rounded to bf16 right after), so all paths stay bit-identical to each other
@@ -170,6 +176,14 @@ __device__ __forceinline__ long long divmod_idx(long long x, int d, int& rem) {
 // ---- host side -------------------------------------------------------------------------------
 void set_error(const char* fmt, ...);
 int check_launch(const char* what);
+
+// workgroups of a grid-stride kernel: one thread per item, at most `cap` workgroups
+static inline int grid_cap(long long items, int block = 256, int cap = 2048) {
+  long long g = (items + block - 1) / block;
+  if (g < 1) g = 1;
+  if (g > cap) g = cap;
+  return (int)g;
+}
 
 #define IVL_REQUIRE(cond, code, ...)        \
   do {                                      \

@@ -8,11 +8,10 @@
 //   ivl_add_rmsnorm_fwd      (residual add +) RMSNorm of the decoder layer in one pass
 //   ivl_silu_mul_fwd         SwiGLU gate: silu(a) * b over the two halves of a fused gate|up projection
 // All HBM-bound, 16-byte vector accesses, rounding points identical to the unfused torch bf16 ops.
-#include "ivl_common.h"
+#include "ivl_rowwise.h"
 
 namespace ivl {
 
-constexpr int FC_W = 4;       // conv taps
 // tokens per conv thread: 8 for long calls (3 halo rows re-read per 8 tokens); 4 for the 256-token step, where 8
 // would leave half the chip idle (128 workgroups; 7.8 -> 6.0 us).  Not below 4: only the thread of chunk 0 may touch
 // the carried state (it is updated in place), so chunk 1 must start at a token >= 3.
@@ -40,18 +39,17 @@ struct ProParams {
 template <int FC_TCH>      // >= 3 (see above)
 __global__ __launch_bounds__(256) void gdn_prologue_kernel(ProParams p) {
   if ((int)blockIdx.x >= p.conv_blocks) {
-    // ---- gate math: beta = sigmoid(b) ; g = -exp(A_log) softplus(a + dt_bias) (std:1293-1294) ---------
+    // ---- gate math (gdn_gate_) ----------------------------------------------------------------------
     const long long n = (long long)p.B * p.T * p.H;
     const long long i0 = ((long long)blockIdx.x - p.conv_blocks) * blockDim.x + threadIdx.x;
     const long long step = ((long long)gridDim.x - p.conv_blocks) * blockDim.x;
     for (long long i = i0; i < n; i += step) {
       const int h = (int)(i % p.H);
       const long long row = i / p.H;
-      const float av = bf2f(p.proj[row * p.ld + p.col_a + h]) + p.dt_bias[h];
-      const float bv = bf2f(p.proj[row * p.ld + p.col_b + h]);
-      const float sp = av > 20.f ? av : log1pf(expf(av));
-      p.g[i] = -expf(p.A_log[h]) * sp;
-      p.beta[i] = f2bf(sigmoid_exact_(bv));
+      float gv, bv;
+      gdn_gate_(bf2f(p.proj[row * p.ld + p.col_a + h]), p.dt_bias[h], bf2f(p.proj[row * p.ld + p.col_b + h]), p.A_log + h, gv, bv);
+      p.g[i] = gv;
+      p.beta[i] = f2bf(bv);
     }
     return;
   }
@@ -74,7 +72,7 @@ __global__ __launch_bounds__(256) void gdn_prologue_kernel(ProParams p) {
     const bf16_t* xb = p.proj + (long long)b * T * p.ld + sg.col0 + d0;     // row t at xb + t*ld
 
     // issue every load first (branch-free): taps, up to 3 halo rows, the chunk's rows, the state
-    const u32x4* wp = (const u32x4*)(sg.w + (size_t)d0 * FC_W);
+    const u32x4* wp = (const u32x4*)(sg.w + (size_t)d0 * CONV_W);
     const u32x4 w0 = wp[0], w1 = wp[1], w2 = wp[2], w3 = wp[3];
     u32x4 xr[FC_TCH + 3];
 #pragma unroll
@@ -85,72 +83,26 @@ __global__ __launch_bounds__(256) void gdn_prologue_kernel(ProParams p) {
     }
     u32x4 s0 = u32x4{0u, 0u, 0u, 0u}, s1 = s0, s2 = s0, s3 = s0;
     if (ch == 0 && sg.state_in != nullptr) {
-      const u32x4* sp = (const u32x4*)(sg.state_in + ((size_t)b * sg.D + d0) * FC_W);
+      const u32x4* sp = (const u32x4*)(sg.state_in + ((size_t)b * sg.D + d0) * CONV_W);
       s0 = sp[0]; s1 = sp[1]; s2 = sp[2]; s3 = sp[3];
     }
-    float wf[8][FC_W], st[8][FC_W];
-    {
-      const unsigned int ww[16] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w, w2.x, w2.y, w2.z, w2.w, w3.x, w3.y, w3.z, w3.w};
-      const unsigned int ss[16] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w, s2.x, s2.y, s2.z, s2.w, s3.x, s3.y, s3.z, s3.w};
-#pragma unroll
-      for (int c = 0; c < 8; ++c) {
-        wf[c][0] = bflo(ww[2 * c]); wf[c][1] = bfhi(ww[2 * c]); wf[c][2] = bflo(ww[2 * c + 1]); wf[c][3] = bfhi(ww[2 * c + 1]);
-        st[c][0] = bflo(ss[2 * c]); st[c][1] = bfhi(ss[2 * c]); st[c][2] = bflo(ss[2 * c + 1]); st[c][3] = bfhi(ss[2 * c + 1]);
-      }
-    }
+    float wf[8][CONV_W], st[8][CONV_W];
+    unpack_taps8_(w0, w1, w2, w3, wf);
+    unpack_taps8_(s0, s1, s2, s3, st);
     float win[3][8];
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      unpack8(xr[k], win[k]);
-      if (ch == 0) {
-#pragma unroll
-        for (int c = 0; c < 8; ++c) win[k][c] = st[c][k + 1];    // times -3,-2,-1 = state[...,1..3]
-      }
-    }
+    for (int k = 0; k < 3; ++k) unpack8(xr[k], win[k]);
+    if (ch == 0) conv_window_from_state_(st, win);
     bf16_t* yb = sg.y + ((size_t)b * T) * sg.D + d0;
 #pragma unroll
     for (int k = 0; k < FC_TCH; ++k) {
       const int t = t0 + k;
       float cur[8], out[8];
       unpack8(xr[k + 3], cur);
-#pragma unroll
-      for (int c = 0; c < 8; ++c) {
-        float a = wf[c][0] * win[0][c];
-        a = fmaf(wf[c][1], win[1][c], a);
-        a = fmaf(wf[c][2], win[2][c], a);
-        a = fmaf(wf[c][3], cur[c], a);
-        if (p.apply_silu) a = a * sigmoidf_(a);
-        out[c] = a;
-        win[0][c] = win[1][c]; win[1][c] = win[2][c]; win[2][c] = cur[c];
-      }
+      conv4_step8_(wf, win, cur, p.apply_silu != 0, out);
       if (t < T) *(u32x4*)(yb + (size_t)t * sg.D) = pack8(out);
     }
-    if (ch == 0 && sg.state_out != nullptr) {
-      // new_state[c][j] = ext[T + j], ext = [state(4), x(T)]
-      float ns[8][FC_W];
-#pragma unroll
-      for (int j = 0; j < FC_W; ++j) {
-        const int e = T + j;
-        if (e >= FC_W) {
-          float xv[8];
-          unpack8(*(const u32x4*)(xb + (long long)(e - FC_W) * p.ld), xv);
-#pragma unroll
-          for (int c = 0; c < 8; ++c) ns[c][j] = xv[c];
-        } else {
-#pragma unroll
-          for (int e2 = 0; e2 < FC_W; ++e2)
-            if (e == e2) {
-#pragma unroll
-              for (int c = 0; c < 8; ++c) ns[c][j] = st[c][e2];
-            }
-        }
-      }
-      u32x4* op = (u32x4*)(sg.state_out + ((size_t)b * sg.D + d0) * FC_W);
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        op[i] = u32x4{pack2bf(ns[2 * i][0], ns[2 * i][1]), pack2bf(ns[2 * i][2], ns[2 * i][3]),
-                      pack2bf(ns[2 * i + 1][0], ns[2 * i + 1][1]), pack2bf(ns[2 * i + 1][2], ns[2 * i + 1][3])};
-    }
+    if (ch == 0 && sg.state_out != nullptr) conv_store_state8_(st, xb, p.ld, T, sg.state_out + ((size_t)b * sg.D + d0) * CONV_W);
   }
 }
 
@@ -169,14 +121,7 @@ __global__ __launch_bounds__(256) void rmsnorm_gate_strided_kernel(
     float xf[8], gf[8], o8[8];
     unpack8(*(const u32x4*)(x + r * 256 + lane32 * 8), xf);
     unpack8(*(const u32x4*)(gate + tok * gate_ld + h * 256 + lane32 * 8), gf);
-    float ss = 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) ss = fmaf(xf[i], xf[i], ss);
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
-    const float rstd = 1.0f / sqrtf(ss * (1.0f / 256.0f) + eps);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) o8[i] = xf[i] * rstd * wf[i] * gf[i] * sigmoidf_(gf[i]);
+    gated_norm_n_(xf, rms256_rstd_(half_wave_sum(sumsq8_(xf, 0.f)), eps), wf, gf, o8);
     store_out16(y + r * 256 + lane32 * 8, pack8(o8));
   }
 }
@@ -219,7 +164,7 @@ __global__ __launch_bounds__(256) void mrope_strided_kernel(
 
 // (residual add +) RMSNorm, one 256-thread workgroup per row, N % 8 == 0, N <= 8192.
 //   h = bf16(x + residual)            (written to h_out when residual != NULL)
-//   y = bf16(weight * bf16(h * rsqrt(mean(h^2) + eps)))        (Qwen2RMSNorm rounding points)
+//   y = bf16(weight * bf16(h * rsqrt(mean(h^2) + eps)))        (Qwen2RMSNorm rounding points: add_round_, sumsq8_, qwen_norm_)
 __global__ __launch_bounds__(256) void add_rmsnorm_kernel(
     const bf16_t* __restrict__ x, const bf16_t* __restrict__ residual, const bf16_t* __restrict__ weight,
     bf16_t* __restrict__ y, bf16_t* __restrict__ h_out, int N, float eps) {
@@ -246,18 +191,17 @@ __global__ __launch_bounds__(256) void add_rmsnorm_kernel(
         float rv[8];
         unpack8(*(const u32x4*)(residual + row * N + v * 8), rv);
 #pragma unroll
-        for (int i = 0; i < 8; ++i) hv[it][i] = bf_round(hv[it][i] + rv[i]);
+        for (int i = 0; i < 8; ++i) hv[it][i] = add_round_(hv[it][i], rv[i]);
         store_out16(h_out + row * N + v * 8, pack8(hv[it]));
       }
-#pragma unroll
-      for (int i = 0; i < 8; ++i) ss = fmaf(hv[it][i], hv[it][i], ss);
+      ss = sumsq8_(hv[it], ss);
     }
   }
   ss = wave_sum(ss);
   if (lane == 0) s_part[wave] = ss;
   __syncthreads();
   const float tot = s_part[0] + s_part[1] + s_part[2] + s_part[3];
-  const float rstd = rsqrtf(tot / (float)N + eps);
+  const float rstd = qwen_rstd_(tot, N, eps);
 #pragma unroll
   for (int it = 0; it < 4; ++it) {
     const int v = tid + it * 256;
@@ -265,7 +209,7 @@ __global__ __launch_bounds__(256) void add_rmsnorm_kernel(
       float wv[8], o8[8];
       unpack8(wraw[it], wv);
 #pragma unroll
-      for (int i = 0; i < 8; ++i) o8[i] = wv[i] * bf_round(hv[it][i] * rstd);
+      for (int i = 0; i < 8; ++i) o8[i] = qwen_norm_(hv[it][i], rstd, wv[i]);
       store_out16(y + row * N + v * 8, pack8(o8));
     }
   }
@@ -294,13 +238,6 @@ __global__ __launch_bounds__(256) void silu_mul_kernel(const bf16_t* __restrict_
   }
 }
 
-static inline int grid_cap(long long items, int block = 256, int cap = 2048) {
-  long long g = (items + block - 1) / block;
-  if (g < 1) g = 1;
-  if (g > cap) g = cap;
-  return (int)g;
-}
-
 }  // namespace ivl
 
 using namespace ivl;
@@ -315,7 +252,7 @@ extern "C" int ivl_gdn_prologue_fwd(const void* proj, int64_t ld, int col_q, int
   IVL_REQUIRE(proj && w_q && w_k && w_v && A_log && dt_bias && q && k && v && g && beta, IVL_ERR_INVALID_ARG,
               "ivl_gdn_prologue_fwd: NULL pointer");
   IVL_REQUIRE(B > 0 && T > 0 && H > 0 && Dq > 0 && Dk > 0 && Dv > 0, IVL_ERR_INVALID_ARG, "ivl_gdn_prologue_fwd: bad sizes");
-  IVL_REQUIRE(W == FC_W, IVL_ERR_UNSUPPORTED, "ivl_gdn_prologue_fwd: kernel size %d unsupported (built for 4)", W);
+  IVL_REQUIRE(W == CONV_W, IVL_ERR_UNSUPPORTED, "ivl_gdn_prologue_fwd: kernel size %d unsupported (built for 4)", W);
   IVL_REQUIRE(Dq % 8 == 0 && Dk % 8 == 0 && Dv % 8 == 0 && ld % 8 == 0 && col_q % 8 == 0 && col_k % 8 == 0 && col_v % 8 == 0,
               IVL_ERR_UNSUPPORTED, "ivl_gdn_prologue_fwd: channel counts / offsets / row stride must be multiples of 8");
   ProParams p;

@@ -3,7 +3,7 @@
 // device-side position counter.  All are HBM-bound: 16-byte vector loads, one pass.
 #include <stdarg.h>
 
-#include "ivl_common.h"
+#include "ivl_rowwise.h"
 
 namespace ivl {
 
@@ -30,7 +30,6 @@ int check_launch(const char* what) {
 // One thread = 8 channels x TCH consecutive tokens; the thread of token-chunk 0 is the only reader
 // of state_in for its channels and also the writer of state_out, so state_out may alias state_in.
 // ------------------------------------------------------------------------------------------------
-constexpr int CONV_W = 4;
 constexpr int CONV_TCH = 8;
 
 // bias (fla's ShortConvolution(bias=True), not used by InfiniteVL): the accumulator starts from it, as in causal_conv1d.
@@ -48,114 +47,41 @@ __global__ __launch_bounds__(256) void short_conv_kernel(
     const int d0 = dg * 8;
     const int t0 = ch * CONV_TCH;
 
-    // weights: 8 channels x 4 taps
     float wf[8][CONV_W];
     {
       const u32x4* wp = (const u32x4*)(w + (size_t)d0 * CONV_W);
-      u32x4 w0 = wp[0], w1 = wp[1], w2 = wp[2], w3 = wp[3];
-      unsigned int ww[16] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w,
-                             w2.x, w2.y, w2.z, w2.w, w3.x, w3.y, w3.z, w3.w};
-#pragma unroll
-      for (int c = 0; c < 8; ++c) {
-        wf[c][0] = bflo(ww[2 * c]);
-        wf[c][1] = bfhi(ww[2 * c]);
-        wf[c][2] = bflo(ww[2 * c + 1]);
-        wf[c][3] = bfhi(ww[2 * c + 1]);
-      }
+      unpack_taps8_(wp[0], wp[1], wp[2], wp[3], wf);
     }
     // history state for these 8 channels (only needed by chunk 0)
     float st[8][CONV_W];
     if (ch == 0) {
+      const u32x4 z = u32x4{0u, 0u, 0u, 0u};
       if (state_in != nullptr) {
         const u32x4* sp = (const u32x4*)(state_in + ((size_t)b * D + d0) * CONV_W);
-        u32x4 s0 = sp[0], s1 = sp[1], s2 = sp[2], s3 = sp[3];
-        unsigned int ss[16] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w,
-                               s2.x, s2.y, s2.z, s2.w, s3.x, s3.y, s3.z, s3.w};
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-          st[c][0] = bflo(ss[2 * c]);
-          st[c][1] = bfhi(ss[2 * c]);
-          st[c][2] = bflo(ss[2 * c + 1]);
-          st[c][3] = bfhi(ss[2 * c + 1]);
-        }
+        unpack_taps8_(sp[0], sp[1], sp[2], sp[3], st);
       } else {
-#pragma unroll
-        for (int c = 0; c < 8; ++c)
-#pragma unroll
-          for (int j = 0; j < CONV_W; ++j) st[c][j] = 0.f;
+        unpack_taps8_(z, z, z, z, st);
       }
     }
     // sliding window of the last 3 inputs: win[k][c] = input at time (t0-3+k)
     float win[3][8];
     const bf16_t* xb = x + (size_t)b * T * D + d0;
     if (ch == 0) {
-      // times -3,-2,-1 come from the carried state (newest last): state[...,1..3]
-#pragma unroll
-      for (int k = 0; k < 3; ++k)
-#pragma unroll
-        for (int c = 0; c < 8; ++c) win[k][c] = st[c][k + 1];
+      conv_window_from_state_(st, win);
     } else {
 #pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        u32x4 v = *(const u32x4*)(xb + (size_t)(t0 - 3 + k) * D);
-        win[k][0] = bflo(v.x); win[k][1] = bfhi(v.x); win[k][2] = bflo(v.y); win[k][3] = bfhi(v.y);
-        win[k][4] = bflo(v.z); win[k][5] = bfhi(v.z); win[k][6] = bflo(v.w); win[k][7] = bfhi(v.w);
-      }
+      for (int k = 0; k < 3; ++k) unpack8(*(const u32x4*)(xb + (size_t)(t0 - 3 + k) * D), win[k]);
     }
     float bf[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     if (bias != nullptr) unpack8(*(const u32x4*)(bias + d0), bf);
     const int tend = min(t0 + CONV_TCH, T);
     for (int t = t0; t < tend; ++t) {
-      u32x4 v = *(const u32x4*)(xb + (size_t)t * D);
-      float cur[8] = {bflo(v.x), bfhi(v.x), bflo(v.y), bfhi(v.y), bflo(v.z), bfhi(v.z), bflo(v.w), bfhi(v.w)};
-      float out[8];
-#pragma unroll
-      for (int c = 0; c < 8; ++c) {
-        float a = bias != nullptr ? fmaf(wf[c][0], win[0][c], bf[c]) : wf[c][0] * win[0][c];
-        a = fmaf(wf[c][1], win[1][c], a);
-        a = fmaf(wf[c][2], win[2][c], a);
-        a = fmaf(wf[c][3], cur[c], a);
-        if (apply_silu) a = a * sigmoidf_(a);
-        out[c] = a;
-        win[0][c] = win[1][c];
-        win[1][c] = win[2][c];
-        win[2][c] = cur[c];
-      }
-      u32x4 o;
-      o.x = pack2bf(out[0], out[1]); o.y = pack2bf(out[2], out[3]);
-      o.z = pack2bf(out[4], out[5]); o.w = pack2bf(out[6], out[7]);
-      *(u32x4*)(y + ((size_t)b * T + t) * D + d0) = o;
+      float cur[8], out[8];
+      unpack8(*(const u32x4*)(xb + (size_t)t * D), cur);
+      conv4_step8_(wf, win, cur, apply_silu != 0, out, bias != nullptr, bf);
+      *(u32x4*)(y + ((size_t)b * T + t) * D + d0) = pack8(out);
     }
-    if (ch == 0 && state_out != nullptr) {
-      // new_state[c][j] = ext[T + j], ext = [state(4), x(T)]
-      float ns[8][CONV_W];
-#pragma unroll
-      for (int j = 0; j < CONV_W; ++j) {
-        const int e = T + j;            // index into ext
-        if (e >= CONV_W) {
-          u32x4 v = *(const u32x4*)(xb + (size_t)(e - CONV_W) * D);
-          ns[0][j] = bflo(v.x); ns[1][j] = bfhi(v.x); ns[2][j] = bflo(v.y); ns[3][j] = bfhi(v.y);
-          ns[4][j] = bflo(v.z); ns[5][j] = bfhi(v.z); ns[6][j] = bflo(v.w); ns[7][j] = bfhi(v.w);
-        } else {
-#pragma unroll
-          for (int e2 = 0; e2 < CONV_W; ++e2)
-            if (e == e2) {
-#pragma unroll
-              for (int c = 0; c < 8; ++c) ns[c][j] = st[c][e2];
-            }
-        }
-      }
-      u32x4* op = (u32x4*)(state_out + ((size_t)b * D + d0) * CONV_W);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        u32x4 o;
-        o.x = pack2bf(ns[2 * i][0], ns[2 * i][1]);
-        o.y = pack2bf(ns[2 * i][2], ns[2 * i][3]);
-        o.z = pack2bf(ns[2 * i + 1][0], ns[2 * i + 1][1]);
-        o.w = pack2bf(ns[2 * i + 1][2], ns[2 * i + 1][3]);
-        op[i] = o;
-      }
-    }
+    if (ch == 0 && state_out != nullptr) conv_store_state8_(st, xb, D, T, state_out + ((size_t)b * D + d0) * CONV_W);
   }
 }
 
@@ -208,35 +134,30 @@ __global__ __launch_bounds__(256) void rmsnorm_gate_kernel(
         }
       }
     }
-    float ss = 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) ss = fmaf(xf[i], xf[i], ss);
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
-    const float rstd = 1.0f / sqrtf(ss * (1.0f / 256.0f) + eps);
+    const float rstd = rms256_rstd_(half_wave_sum(sumsq8_(xf, 0.f)), eps);
     float o8[8];
+    if constexpr (GATED) {
+      gated_norm_n_(xf, rstd, wf, gf, o8);
+    } else {
 #pragma unroll
-    for (int i = 0; i < 8; ++i) o8[i] = GATED ? xf[i] * rstd * wf[i] * gf[i] * sigmoidf_(gf[i]) : xf[i] * rstd * wf[i];
-    u32x4 ov;
-    ov.x = pack2bf(o8[0], o8[1]); ov.y = pack2bf(o8[2], o8[3]);
-    ov.z = pack2bf(o8[4], o8[5]); ov.w = pack2bf(o8[6], o8[7]);
-    *(u32x4*)(y + r * 256 + lane32 * 8) = ov;
+      for (int i = 0; i < 8; ++i) o8[i] = xf[i] * rstd * wf[i];
+    }
+    *(u32x4*)(y + r * 256 + lane32 * 8) = pack8(o8);
   }
 }
 
 // ------------------------------------------------------------------------------------------------
-// gate math: beta = sigmoid(b) -> bf16 ; g = -exp(A_log[h]) * softplus(a + dt_bias[h]) -> fp32
-// softplus follows torch (threshold 20).
+// gate math (gdn_gate_): beta = sigmoid(b) -> bf16 ; g = -exp(A_log[h]) * softplus(a + dt_bias[h]) -> fp32
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void gdn_gate_kernel(
     const bf16_t* __restrict__ a, const bf16_t* __restrict__ b, const float* __restrict__ A_log,
     const float* __restrict__ dt_bias, float* __restrict__ g, bf16_t* __restrict__ beta, long long n, int H) {
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
     const int h = (int)(i % H);
-    const float av = bf2f(a[i]) + dt_bias[h];
-    const float sp = av > 20.f ? av : log1pf(expf(av));
-    g[i] = -expf(A_log[h]) * sp;
-    beta[i] = f2bf(sigmoid_exact_(bf2f(b[i])));
+    float gv, bv;
+    gdn_gate_(bf2f(a[i]), dt_bias[h], bf2f(b[i]), A_log + h, gv, bv);
+    g[i] = gv;
+    beta[i] = f2bf(bv);
   }
 }
 
@@ -306,13 +227,6 @@ __global__ void counter_add_kernel(long long* c, long long delta) {
   if (threadIdx.x == 0 && blockIdx.x == 0) *c += delta;
 }
 
-static inline int grid_for(long long work_items, int block = 256, int cap = 256 * 8) {
-  long long g = (work_items + block - 1) / block;
-  if (g < 1) g = 1;
-  if (g > cap) g = cap;
-  return (int)g;
-}
-
 }  // namespace ivl
 
 using namespace ivl;
@@ -343,7 +257,7 @@ extern "C" int ivl_short_conv_fwd(const void* x, const void* weight, const void*
   IVL_REQUIRE(W == CONV_W, IVL_ERR_UNSUPPORTED, "ivl_short_conv_fwd: kernel size %d unsupported (built for 4)", W);
   IVL_REQUIRE(D % 8 == 0, IVL_ERR_UNSUPPORTED, "ivl_short_conv_fwd: D=%d must be a multiple of 8", D);
   const long long items = (long long)B * ((T + CONV_TCH - 1) / CONV_TCH) * (D / 8);
-  hipLaunchKernelGGL(short_conv_kernel, dim3(grid_for(items)), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(short_conv_kernel, dim3(grid_cap(items)), dim3(256), 0, (hipStream_t)stream,
                      (const bf16_t*)x, (const bf16_t*)weight, (const bf16_t*)nullptr, (const bf16_t*)state_in, (bf16_t*)y, (bf16_t*)state_out,
                      B, T, D, apply_silu);
   return check_launch("ivl_short_conv_fwd");
@@ -355,10 +269,10 @@ extern "C" int ivl_rmsnorm_swish_gate_fwd(const void* x, const void* gate, const
   IVL_REQUIRE(rows > 0, IVL_ERR_INVALID_ARG, "ivl_rmsnorm_swish_gate_fwd: rows=%d", rows);
   IVL_REQUIRE(N == 256, IVL_ERR_UNSUPPORTED, "ivl_rmsnorm_swish_gate_fwd: N=%d unsupported (built for head_v_dim 256)", N);
   if (gate != nullptr)
-    hipLaunchKernelGGL(rmsnorm_gate_kernel<true>, dim3(grid_for((long long)rows * 32)), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(rmsnorm_gate_kernel<true>, dim3(grid_cap((long long)rows * 32)), dim3(256), 0, (hipStream_t)stream,
                        (const bf16_t*)x, (const bf16_t*)gate, (const bf16_t*)weight, (bf16_t*)y, rows, eps);
   else
-    hipLaunchKernelGGL(rmsnorm_gate_kernel<false>, dim3(grid_for((long long)rows * 32)), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(rmsnorm_gate_kernel<false>, dim3(grid_cap((long long)rows * 32)), dim3(256), 0, (hipStream_t)stream,
                        (const bf16_t*)x, (const bf16_t*)nullptr, (const bf16_t*)weight, (bf16_t*)y, rows, eps);
   return check_launch("ivl_rmsnorm_swish_gate_fwd");
 }
@@ -371,7 +285,7 @@ extern "C" int ivl_rmsnorm_swish_gate_res_fwd(const void* x, const void* gate, c
   IVL_REQUIRE((residual == nullptr || residual_dtype == IVL_F32 || residual_dtype == IVL_BF16) &&
               (residual_out == nullptr || residual_out_dtype == IVL_F32 || residual_out_dtype == IVL_BF16),
               IVL_ERR_INVALID_ARG, "ivl_rmsnorm_swish_gate_res_fwd: residual dtype must be IVL_F32 or IVL_BF16");
-  hipLaunchKernelGGL((rmsnorm_gate_kernel<true, true>), dim3(grid_for((long long)rows * 32)), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL((rmsnorm_gate_kernel<true, true>), dim3(grid_cap((long long)rows * 32)), dim3(256), 0, (hipStream_t)stream,
                      (const bf16_t*)x, (const bf16_t*)gate, (const bf16_t*)weight, (bf16_t*)y, rows, eps,
                      NormRes{residual, residual_dtype, residual_out, residual_out_dtype});
   return check_launch("ivl_rmsnorm_swish_gate_res_fwd");
@@ -384,7 +298,7 @@ extern "C" int ivl_short_conv_bias_fwd(const void* x, const void* weight, const 
   IVL_REQUIRE(W == CONV_W, IVL_ERR_UNSUPPORTED, "ivl_short_conv_bias_fwd: kernel size %d unsupported (built for 4)", W);
   IVL_REQUIRE(D % 8 == 0, IVL_ERR_UNSUPPORTED, "ivl_short_conv_bias_fwd: D=%d must be a multiple of 8", D);
   const long long items = (long long)B * ((T + CONV_TCH - 1) / CONV_TCH) * (D / 8);
-  hipLaunchKernelGGL(short_conv_kernel, dim3(grid_for(items)), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(short_conv_kernel, dim3(grid_cap(items)), dim3(256), 0, (hipStream_t)stream,
                      (const bf16_t*)x, (const bf16_t*)weight, (const bf16_t*)bias, (const bf16_t*)state_in, (bf16_t*)y, (bf16_t*)state_out,
                      B, T, D, apply_silu);
   return check_launch("ivl_short_conv_bias_fwd");
@@ -395,7 +309,7 @@ extern "C" int ivl_gdn_gate_fwd(const void* a, const void* b, const float* A_log
   IVL_REQUIRE(a && b && A_log && dt_bias && g && beta, IVL_ERR_INVALID_ARG, "ivl_gdn_gate_fwd: NULL pointer");
   IVL_REQUIRE(rows > 0 && H > 0, IVL_ERR_INVALID_ARG, "ivl_gdn_gate_fwd: rows=%d H=%d", rows, H);
   const long long n = (long long)rows * H;
-  hipLaunchKernelGGL(gdn_gate_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(gdn_gate_kernel, dim3(grid_cap(n)), dim3(256), 0, (hipStream_t)stream,
                      (const bf16_t*)a, (const bf16_t*)b, A_log, dt_bias, g, (bf16_t*)beta, n, H);
   return check_launch("ivl_gdn_gate_fwd");
 }
@@ -407,7 +321,7 @@ extern "C" int ivl_mrope_fwd(void* q, void* k, const void* cos, const void* sin,
   IVL_REQUIRE(d % 16 == 0 && s0 + s1 + s2 == d / 2, IVL_ERR_UNSUPPORTED,
               "ivl_mrope_fwd: need d%%16==0 and s0+s1+s2==d/2 (d=%d, sections %d,%d,%d)", d, s0, s1, s2);
   const long long items = (long long)B * T * (Hq + Hkv) * (d / 16);
-  hipLaunchKernelGGL(mrope_kernel, dim3(grid_for(items)), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(mrope_kernel, dim3(grid_cap(items)), dim3(256), 0, (hipStream_t)stream,
                      (bf16_t*)q, (bf16_t*)k, (const bf16_t*)cos, (const bf16_t*)sin, B, T, Hq, Hkv, d, s0, s1);
   return check_launch("ivl_mrope_fwd");
 }

@@ -13,10 +13,11 @@
 // NORM variant (round 3): the RMSNorm in front of the projection -- (residual add +) Qwen2RMSNorm, 73 one-row launches of
 // ivl_add_rmsnorm_fwd per decode token, each ~4.2 us inside the token's graph: 15 % of the token -- runs in the prologue of
 // the weight stream.  Every workgroup forms the normalised rows itself (M x K <= 4 x 4096 elements: 8 KB of L2-resident
-// input per row, the same thread -> element mapping, summation order and rounding points as add_rmsnorm_kernel: the rows
-// are bit-identical to that kernel's) into LDS while its first weight pieces are in flight, and reads x from there;
+// input per row, the same thread -> element mapping and summation order as add_rmsnorm_kernel, through the same
+// add_round_ / sumsq8_ / qwen_norm_: the rows are bit-identical to that kernel's) into LDS while its first weight pieces are in
+// flight, and reads x from there;
 // workgroup 0 also writes the new residual stream h = bf16(x + residual).
-#include "ivl_common.h"
+#include "ivl_rowwise.h"
 
 namespace ivl {
 
@@ -96,11 +97,10 @@ __global__ __launch_bounds__(256, (NORM && M == 1) ? 3 : 1) void linear_small_m_
             float rv[8];
             unpack8(rraw[m][it], rv);
 #pragma unroll
-            for (int i = 0; i < 8; ++i) hv[m][it][i] = bf_round(hv[m][it][i] + rv[i]);
+            for (int i = 0; i < 8; ++i) hv[m][it][i] = add_round_(hv[m][it][i], rv[i]);
             if (blockIdx.x == 0) *(u32x4*)(na.h_out + (size_t)m * K + v * 8) = pack8(hv[m][it]);
           }
-#pragma unroll
-          for (int i = 0; i < 8; ++i) ss = fmaf(hv[m][it][i], hv[m][it][i], ss);
+          ss = sumsq8_(hv[m][it], ss);
         }
       }
       ss = wave_sum(ss);
@@ -110,7 +110,7 @@ __global__ __launch_bounds__(256, (NORM && M == 1) ? 3 : 1) void linear_small_m_
 #pragma unroll
     for (int m = 0; m < M; ++m) {
       const float tot = s_part[m][0] + s_part[m][1] + s_part[m][2] + s_part[m][3];
-      const float rstd = rsqrtf(tot / (float)K + na.eps);
+      const float rstd = qwen_rstd_(tot, K, na.eps);
 #pragma unroll
       for (int it = 0; it < NIT; ++it) {
         const int v = tid + it * 256;
@@ -118,7 +118,7 @@ __global__ __launch_bounds__(256, (NORM && M == 1) ? 3 : 1) void linear_small_m_
           float wv8[8], o8[8];
           unpack8(wraw[it], wv8);
 #pragma unroll
-          for (int i = 0; i < 8; ++i) o8[i] = wv8[i] * bf_round(hv[m][it][i] * rstd);
+          for (int i = 0; i < 8; ++i) o8[i] = qwen_norm_(hv[m][it][i], rstd, wv8[i]);
           s_x[m * (LSM_NORM_KMAX / 8) + v] = pack8(o8);
         }
       }
@@ -225,8 +225,8 @@ static int lsm_dispatch(const void* x, const void* w, const void* bias, void* y,
 // ------------------------------------------------------------------------------------------------------------------------------
 // GDN output projection of a decode step with the GATED RMSNorm in its prologue (round 5): x = o_norm(o, gate) is
 // formed by every workgroup itself -- per head a 256-wide statistic of the un-normalised bf16 delta-rule output (8 KB per row,
-// L2-resident) and the gate columns of the projection row -- with the arithmetic of gdn_decode_step_kernel's last block (lane l of
-// a wave holds elements 4l .. 4l + 3 of a head: same sums, same roundings: bit-identical), staged in LDS, then the o_proj weight
+// L2-resident) and the gate columns of the projection row -- through gated_norm_n_ with the element layout of
+// gdn_decode_step_kernel's last block (lane l of a wave holds elements 4l .. 4l + 3 of a head), staged in LDS, then the o_proj weight
 // stream reads x from there.  What makes it worth a kernel: the decode step itself can then run on 4 x as many workgroups
 // (gdn_decode_split_kernel) because nothing spans a head any more.  The first workgroups also shift the conv states of q and k
 // (new state = taps 1..3 + the step's raw projection value): every quarter workgroup of the split step READS those states, so
@@ -253,7 +253,7 @@ __global__ __launch_bounds__(256) void linear_gdn_out_kernel(const bf16_t* __res
       bf16_t* st = (isk ? ga.ck : ga.cq) + ((size_t)m * ga.Dq + ch) * 4;
       const u32x2 sv = *(const u32x2*)st;
       const bf16_t xr = ga.proj[(size_t)m * ga.proj_ld + (isk ? ga.col_k : ga.col_q) + ch];
-      *(u32x2*)st = u32x2{(sv.x >> 16) | (sv.y << 16), (sv.y >> 16) | ((unsigned int)xr << 16)};
+      *(u32x2*)st = conv_state_shift1_(sv, xr);
     }
   }
   // ---- the rows' pieces first (o, gate, norm weight: 4 heads per wave), then the first weight batch, then the norm ----
@@ -287,10 +287,8 @@ __global__ __launch_bounds__(256) void linear_gdn_out_kernel(const bf16_t* __res
           const float o4[4] = {bflo(oraw[m][i].x), bfhi(oraw[m][i].x), bflo(oraw[m][i].y), bfhi(oraw[m][i].y)};
           const float gf[4] = {bflo(graw[m][i].x), bfhi(graw[m][i].x), bflo(graw[m][i].y), bfhi(graw[m][i].y)};
           const float ss = wave_sum(o4[0] * o4[0] + o4[1] * o4[1] + o4[2] * o4[2] + o4[3] * o4[3]);
-          const float rstd = 1.0f / sqrtf(ss * (1.0f / 256.0f) + ga.eps);
           float y4[4];
-#pragma unroll
-          for (int c = 0; c < 4; ++c) y4[c] = o4[c] * rstd * wf[c] * gf[c] * sigmoidf_(gf[c]);
+          gated_norm_n_(o4, rms256_rstd_(ss, ga.eps), wf, gf, y4);
           if (hh < ga.H)
             *(u32x2*)((bf16_t*)s_x + (size_t)m * LSM_NORM_KMAX + hh * 256 + 4 * lane) = u32x2{pack2bf(y4[0], y4[1]), pack2bf(y4[2], y4[3])};
         }
