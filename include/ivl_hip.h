@@ -469,6 +469,51 @@ IVL_API int ivl_sample_rows_ctl_fwd(const void* logits, int64_t ld, int S, int V
                                     const int64_t* stop_ids, int n_stop, const int64_t* budget, const int64_t* fill,
                                     int64_t* n_new, int32_t* done, int64_t* history, int64_t hist_ld, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * ivl_sample_rows_ctl_fwd with the scores of what it generates, inside the same one launch: the log-probability of the token, the
+ * n_top most likely alternatives, a running sum and rings beside the token history (`logprobs` / `top_logprobs` of the OpenAI
+ * protocol the reference's api/ serves; output_scores of HF generate).  Every new argument may be NULL / 0 (off); with all of them
+ * off the call IS ivl_sample_rows_ctl_fwd.  With any of them on, token, counter, seen, n_new, done, history, n_kept and prob are
+ * bit for bit those of ivl_sample_rows_ctl_fwd on the same inputs.  Per row s:
+ *   L1 the scored distribution.  x' = the row as the kernel keys it: after the repetition penalty of step B, before temperature,
+ *      top-k and top-p (HF's processed scores in front of the warpers; with r == 1 the raw model distribution).  NaN counts as
+ *      -inf (step 1); m = max x'.
+ *        Z1  = sum_i floor(exp2f((x'_i - m) * log2e) * 2^40),  log2e = 1.44269504088896341f, the product rounded to fp32;
+ *              an integer sum, exact in any order.  The weight is exactly 2^40 where x'_i == m (also at m = +-inf), 0 for
+ *              x'_i = -inf < m and for (x'_i - m) * log2e <= -41 (step 4 at temperature 1).  2^40 <= Z1 <= V 2^40 < 2^63.
+ *        lse = logf(RN_fp32(Z1) * 2^-40): the uint64 -> fp32 conversion rounds to nearest even, the scaling by 2^-40 is exact,
+ *              logf is the device library's fp32 logarithm (1 ulp).  0 <= lse <= ln V.
+ *        lp(i) = (x'_i - m) - lse, two fp32 subtractions in this order; lp(i) = -lse where x'_i == m; lp(i) = -inf where
+ *              x'_i = -inf < m.  A token below the 27.7-nat weight floor of step 4 still gets its finite lp from this formula.
+ *              A row of nothing but -inf / NaN gives every token -logf((float)V).
+ *   L2 logprob[s] = lp(token written), for greedy and drawn rows alike (a greedy row makes the Z1 pass too, in this form only).
+ *   L3 top-N.  The min(n_top, V) tokens with the largest x', ties to the lowest index, listed by (x' descending, index ascending):
+ *      top_ids[s*n_top + j] int64, top_logprobs[s*n_top + j] = lp(top_ids[..]) fp32, bit-equal to what logprob would hold for that
+ *      token; entries j >= V are id -1 / lp -inf.  Selected by the 4096 + 16 histogram threshold of top-k, no sort of the row.
+ *   L4 bookkeeping, by the one lane that writes the token, in front of step C, at the ring index of the token history
+ *      a = s*hist_ld + n_new[s] % hist_ld (n_new before its increment):
+ *        lp_history[a] = logprob;  top_hist_ids[a*n_top + j] = top_ids[j];  top_hist_lp[a*n_top + j] = top_logprobs[j];
+ *        cum_logprob[s] += (double)logprob  (float64; one add per step, in step order).
+ *   L5 a finished row (done[s] != 0 on entry): logprob = 0, top_ids = -1, top_logprobs = -inf; no ring or cum_logprob write, and
+ *      nothing else of the row is touched, as in step A.
+ * logprob [S] fp32; n_top 0..20; top_ids / top_logprobs [S, n_top]; cum_logprob [S] float64; lp_history [S, hist_ld] fp32;
+ * top_hist_ids int64 / top_hist_lp fp32 [S, hist_ld, n_top].  hist_ld is the one of `history` (which may itself be NULL).
+ * The scores are a pure function of (x, rep_penalty, seen) and the token: the same bits eager or in a replayed graph, alone or as
+ * any row of a larger call.
+ * IVL_ERR_INVALID_ARG (before anything is launched): n_top outside 0..20; n_top > 0 without top_ids or top_logprobs; lp_history
+ * or a top ring without n_new or with hist_ld < 1; a top ring with n_top == 0; and whatever ivl_sample_rows_ctl_fwd refuses.
+ * ------------------------------------------------------------------------------------------- */
+IVL_API int ivl_sample_rows_lp_fwd(const void* logits, int64_t ld, int S, int V,
+                                   const float* temperature, const int32_t* top_k, const float* top_p,
+                                   const int64_t* seed, int64_t* counter,
+                                   int64_t* token, int64_t token_stride,
+                                   int32_t* n_kept, float* prob,
+                                   const float* rep_penalty, uint32_t* seen, int64_t seen_ld,
+                                   const int64_t* stop_ids, int n_stop, const int64_t* budget, const int64_t* fill,
+                                   int64_t* n_new, int32_t* done, int64_t* history, int64_t hist_ld,
+                                   float* logprob, int n_top, int64_t* top_ids, float* top_logprobs, double* cum_logprob,
+                                   float* lp_history, int64_t* top_hist_ids, float* top_hist_lp, void* stream);
+
 /* Sets the bits of ids[0..n) (int64, device) in ONE row of a seen bitmap: the prompt's tokens, before the first draw.  Ids outside
  * [0, V) are ignored, duplicates are fine; n == 0 is a no-op.  seen_row NULL, V < 1, n < 0 or ids NULL with n > 0:
  * IVL_ERR_INVALID_ARG. */

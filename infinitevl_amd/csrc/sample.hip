@@ -26,6 +26,15 @@
 // tile where it is loaded (a bitmap of seen tokens, 8 bits a tile from two bytes), rounded back to bf16, so every pass sees the same
 // penalised keys and nothing behind the key changes; the lane that writes the token then sets its bit, logs it, counts it and
 // decides `done` from the stop ids and the budget.  ivl_token_mark_fwd marks a prompt's tokens in a row of the bitmap.
+//
+// Log-probabilities (ivl_sample_rows_lp_fwd; a third form of the template, the two others are compiled without a line of it): the
+// row's log-partition from the integer sum Z1 of the Q40 weights at temperature 1 and the n_top <= 20 largest keys, in three more
+// passes placed where `hist` is free -- behind top-k's scan, in front of top-p's masses, or in front of a greedy row's write:
+//   L1  Z1 and the coarse counts (a top-k row has them from pass 1)     L2  counts of the 16 keys of the bin that holds the n_top-th largest value -> t_N
+//       (skipped where that bin and the bins above it hold at most 20 keys: they are all collected)
+//   L3  collect: every key > t_N (fewer than n_top), and per wave (a wave owns a contiguous index range) its first ties == t_N
+// then wave 0 takes the ties in wave = index order, ranks the <= 20 survivors against each other (no sort of the row) and leaves
+// the ordered list in LDS for the lane that writes the token: it scores the token, logs and adds it up beside smp_after.
 #include "ivl_common.h"
 
 #include <type_traits>
@@ -274,8 +283,217 @@ __device__ __forceinline__ void smp_after(const SmpCtl& c, long long s, long lon
   }
 }
 
-// CTL: no type (the control-free form, with the parameter list it always had) or SmpCtl
+// The log-probability group of ivl_sample_rows_lp_fwd; every pointer may be NULL (off)
+constexpr int SMP_TOP_MAX = 20;
+struct SmpLp {
+  float* logprob;
+  int n_top;
+  long long* top_ids;
+  float* top_lp;
+  double* cum;
+  float* lp_hist;
+  long long* top_hist_ids;
+  float* top_hist_lp;
+};
+struct SmpLpLds {
+  u64 cand[SMP_TOP_MAX];                   // the survivors in output order, as (key + 1) << 32 | ~index
+  u64 gt[SMP_TOP_MAX];                     // keys above t_N, in the order the waves met them
+  unsigned tie[SMP_WAVES][SMP_TOP_MAX];    // per wave: the lowest indices of its keys == t_N
+  unsigned ntie[SMP_WAVES];
+  unsigned ngt;
+};
+struct SmpNoLds {};
+
+// lp of a key: (x' - m) - lse in fp32; -lse at the maximum (also m = +-inf), -inf for -inf < m
+__device__ __forceinline__ float smp_lp(unsigned key, unsigned mkey, float xm, float lse) {
+  if (key == mkey) return -lse;
+  if (key <= SMP_KEY_NINF) return -__builtin_inff();
+  return (smp_key_value(key) - xm) - lse;
+}
+
+// Passes L1-L3, by every thread of the workgroup, while `hist`, `sub`, `wsum` and the sh_ words are free; returns lse and leaves
+// the min(n_top, V) survivors in L.cand.  Ends on a barrier.  counted: hist already holds the row's coarse counts (pass 1 made
+// them for top-k, whose scan only read them).
+template <typename PEN>
+__device__ __forceinline__ float smp_lp_phase(const SmpRow& r, const PEN& pen, unsigned mkey, float xm, int n_top, bool counted, int tid,
+                                              u64* hist, u64* sub, u64* wsum, unsigned* sh_bin, u64* sh_E, unsigned* sh_key,
+                                              SmpLpLds& L) {
+  const int lane = tid & 63, wave = tid >> 6;
+  const unsigned nsel = (unsigned)(n_top < r.V ? n_top : r.V);
+  const bool count = nsel > 0u && !counted;
+  if (nsel > 0u) {
+    if (count) {
+#pragma unroll
+      for (int i = 0; i < SMP_BINS / SMP_THREADS; ++i) hist[tid + i * SMP_THREADS] = 0ull;
+    }
+    if (tid < SMP_WAVES) L.ntie[tid] = 0u;
+    if (tid == 0) L.ngt = 0u;
+  }
+  __syncthreads();
+  // ---- L1: Z1 = the sum of the Q40 weights at temperature 1; coarse counts
+  u64 z = 0ull;
+  for (long long j0 = (long long)wave * 64; j0 < r.nt; j0 += SMP_THREADS) {
+    const long long j = j0 + lane;
+    unsigned key[8] = {}, valid = 0u;
+    if (j < r.nt) valid = smp_load(r, pen, j, key);
+#pragma unroll
+    for (int e = 0; e < 8; ++e)
+      if (valid >> e & 1u) z += smp_weight(key[e], mkey, xm, 1.44269504088896341f);
+    if (count) {
+      unsigned bin[8];
+      u64 val[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) { bin[e] = key[e] >> 4; val[e] = 1ull; }
+      smp_hist_add(hist, bin, val, valid, lane);
+    }
+  }
+  z = smp_wave_sum(z);
+  if (lane == 0) wsum[wave] = z;
+  __syncthreads();
+  u64 Z1 = 0ull;
+#pragma unroll
+  for (int w = 0; w < SMP_WAVES; ++w) Z1 += wsum[w];
+  const float lse = logf((float)Z1 * 0x1p-40f);        // 2^40 <= Z1 < 2^63: the conversion rounds to nearest even, the scaling is exact
+  if (nsel == 0u) { __syncthreads(); return lse; }
+  __syncthreads();                                     // wsum has been read by every thread
+  // ---- the bin where the count from the top reaches nsel, then L2: the key inside it
+  SmpScan sc;
+  smp_scan(hist, wsum, tid, sc);
+  smp_locate(sc, (u64)nsel, tid, sh_bin, sh_E);
+  if (tid < SMP_SUB) sub[tid] = 0ull;
+  __syncthreads();
+  const unsigned B = *sh_bin;
+  // The boundary bin and the bins above it hold `upto` >= nsel keys.  If they all fit the list (the usual case: the head of a
+  // row of logits is sparse), L2 is skipped: every key of these bins is collected and the ranking keeps the first nsel.
+  const u64 upto = *sh_E + hist[B];
+  const bool whole = upto <= (u64)SMP_TOP_MAX;         // uniform over the workgroup
+  unsigned tN, need;
+  if (whole) {
+    tN = B * SMP_SUB - 1u;                             // B >= 7 (the bin of -inf): every key of bin B is above it
+    need = 0u;
+  } else {
+    for (long long j0 = (long long)wave * 64; j0 < r.nt; j0 += SMP_THREADS) {
+      const long long j = j0 + lane;
+      unsigned key[8] = {}, valid = 0u;
+      if (j < r.nt) valid = smp_load(r, pen, j, key);
+      unsigned bin[8], m = 0u;
+      u64 val[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) { bin[e] = key[e] & 15u; val[e] = 1ull; if ((key[e] >> 4) == B) m |= 1u << e; }
+      if (__any((valid & m) != 0u)) smp_hist_add(sub, bin, val, valid & m, lane);
+    }
+    __syncthreads();
+    if (tid == 0) {
+      u64 E = *sh_E, above = 0ull;
+      unsigned res = mkey;
+      for (int i = SMP_SUB - 1; i >= 0; --i) {
+        if (E < (u64)nsel) { res = B * SMP_SUB + i; above = E; }
+        E += sub[i];
+      }
+      *sh_key = res;
+      *sh_E = above;                                   // keys above t_N: fewer than nsel
+    }
+    __syncthreads();
+    tN = *sh_key;
+    need = nsel - (unsigned)*sh_E;                     // ties at t_N to take, lowest indices first: 1 .. nsel
+  }
+  // ---- L3: collect; wave w owns the tiles [w tpw, (w+1) tpw), its lanes interleaved: lane order = index order
+  const long long tpw = (r.nt + SMP_WAVES - 1) / SMP_WAVES;
+  const long long jbeg = wave * tpw, jend = (jbeg + tpw < r.nt) ? jbeg + tpw : r.nt;
+  unsigned mytie = 0u;                                 // ties of this wave so far (uniform over the wave)
+  for (long long j0 = jbeg; j0 < jend; j0 += 64) {
+    const long long j = j0 + lane;
+    unsigned key[8] = {}, valid = 0u;
+    if (j < jend) valid = smp_load(r, pen, j, key);
+    unsigned gm = 0u, tm = 0u;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      if (key[e] > tN) gm |= 1u << e;
+      if (key[e] == tN) tm |= 1u << e;
+    }
+    gm &= valid;
+    tm &= valid;
+    if (gm != 0u) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e)
+        if (gm >> e & 1u) {
+          const unsigned at = atomicAdd(&L.ngt, 1u);
+          if (at < (unsigned)SMP_TOP_MAX) L.gt[at] = ((u64)(key[e] + 1u) << 32) | (u64)(0xFFFFFFFFu - (unsigned)(j * 8 - r.off + e));
+        }
+    }
+    if (mytie < need && __any(tm != 0u)) {
+      const unsigned c = (unsigned)__popc(tm);
+      const unsigned incl = (unsigned)smp_wave_incl_scan((u64)c, lane);
+      unsigned pos = mytie + incl - c;
+#pragma unroll
+      for (int e = 0; e < 8; ++e)
+        if (tm >> e & 1u) {
+          if (pos < need) L.tie[wave][pos] = (unsigned)(j * 8 - r.off + e);
+          ++pos;
+        }
+      mytie += (unsigned)__shfl((int)incl, 63, 64);
+    }
+  }
+  if (lane == 0) L.ntie[wave] = mytie < need ? mytie : need;
+  __syncthreads();
+  // ---- wave 0: lane i holds candidate i, its rank = the candidates in front of it by (key descending, index ascending)
+  if (wave == 0) {
+    const unsigned ngt = L.ngt;                        // the keys above t_N; with `need` ties: the candidates
+    const unsigned ncand = ngt + need;
+    u64 mine = 0ull;
+    if ((unsigned)lane < ngt) {
+      mine = L.gt[lane];
+    } else if ((unsigned)lane < ncand) {
+      unsigned t = (unsigned)lane - ngt;
+      bool found = false;
+#pragma unroll
+      for (int w = 0; w < SMP_WAVES; ++w) {
+        const unsigned n = L.ntie[w];
+        if (!found) {
+          if (t < n) { mine = ((u64)(tN + 1u) << 32) | (u64)(0xFFFFFFFFu - L.tie[w][t]); found = true; }
+          else t -= n;
+        }
+      }
+    }
+    unsigned rank = 0u;
+    for (unsigned i = 0u; i < ncand; ++i) {
+      const u64 other = __shfl(mine, (int)i, 64);
+      if (other > mine) ++rank;
+    }
+    if ((unsigned)lane < ncand) L.cand[rank] = mine;
+  }
+  __syncthreads();
+  return lse;
+}
+
+// Scores of row s, by the lane that writes the token, in front of smp_after (the ring index is n_new before its increment)
+__device__ __forceinline__ void smp_lp_after(const SmpLp& lp, const SmpCtl& c, long long s, int V, unsigned tkey, unsigned mkey,
+                                             float xm, float lse, const SmpLpLds& L) {
+  const float v = smp_lp(tkey, mkey, xm, lse);
+  if (lp.logprob) lp.logprob[s] = v;
+  long long at = 0;
+  if (lp.lp_hist || lp.top_hist_ids || lp.top_hist_lp) at = s * c.hist_ld + c.n_new[s] % c.hist_ld;
+  if (lp.lp_hist) lp.lp_hist[at] = v;
+  for (int j = 0; j < lp.n_top; ++j) {
+    long long id = -1ll;
+    float l = -__builtin_inff();
+    if (j < V) {
+      const u64 w = L.cand[j];
+      id = (long long)(0xFFFFFFFFu - (unsigned)(w & 0xFFFFFFFFull));
+      l = smp_lp((unsigned)(w >> 32) - 1u, mkey, xm, lse);
+    }
+    lp.top_ids[s * lp.n_top + j] = id;
+    lp.top_lp[s * lp.n_top + j] = l;
+    if (lp.top_hist_ids) lp.top_hist_ids[at * lp.n_top + j] = id;
+    if (lp.top_hist_lp) lp.top_hist_lp[at * lp.n_top + j] = l;
+  }
+  if (lp.cum) lp.cum[s] += (double)v;
+}
+
+// CTL: no type (the control-free form, with the parameter list it always had), SmpCtl, or SmpCtl and SmpLp
 __device__ __forceinline__ const SmpCtl& smp_first(const SmpCtl& c) { return c; }
+__device__ __forceinline__ const SmpCtl& smp_first(const SmpCtl& c, const SmpLp&) { return c; }
+__device__ __forceinline__ const SmpLp& smp_second(const SmpCtl&, const SmpLp& l) { return l; }
 
 template <typename... CTL>
 __global__ void __launch_bounds__(SMP_THREADS)
@@ -283,7 +501,7 @@ sample_rows_kernel(const bf16_t* __restrict__ logits, long long ld, int V, const
                    const int* __restrict__ top_k, const float* __restrict__ top_p, const long long* __restrict__ seed,
                    long long* __restrict__ counter, long long* __restrict__ token, long long token_stride,
                    int* __restrict__ n_kept, float* __restrict__ prob, const CTL... ctl_) {
-  constexpr bool kCtl = sizeof...(CTL) == 1;
+  constexpr bool kCtl = sizeof...(CTL) >= 1, kLp = sizeof...(CTL) == 2;
   typename std::conditional<kCtl, SmpPen, SmpNoPen>::type pen;
   if constexpr (kCtl) {
     const SmpCtl& ctl = smp_first(ctl_...);
@@ -293,6 +511,14 @@ sample_rows_kernel(const bf16_t* __restrict__ logits, long long ld, int V, const
         token[s * token_stride] = ctl.fill ? ctl.fill[s] : 0ll;
         if (n_kept) n_kept[s] = 0;
         if (prob) prob[s] = 0.f;
+      }
+      if constexpr (kLp) {                              // no score: logprob 0, no alternatives, no ring or sum write
+        const SmpLp& lp = smp_second(ctl_...);
+        if (threadIdx.x == 0 && lp.logprob) lp.logprob[s] = 0.f;
+        if ((int)threadIdx.x < lp.n_top) {
+          lp.top_ids[s * lp.n_top + threadIdx.x] = -1ll;
+          lp.top_lp[s * lp.n_top + threadIdx.x] = -__builtin_inff();
+        }
       }
       return;
     }
@@ -309,6 +535,8 @@ sample_rows_kernel(const bf16_t* __restrict__ logits, long long ld, int V, const
   __shared__ unsigned sh_bin;
   __shared__ u64 sh_E;
   __shared__ unsigned sh_key;
+  __shared__ typename std::conditional<kLp, SmpLpLds, SmpNoLds>::type lpl;
+  [[maybe_unused]] float lse = 0.f;
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const long long s = blockIdx.x;
@@ -363,10 +591,15 @@ sample_rows_kernel(const bf16_t* __restrict__ logits, long long ld, int V, const
   const unsigned midx = 0xFFFFFFFFu - (unsigned)(best & 0xFFFFFFFFull);
 
   if (greedy) {
+    if constexpr (kLp)
+      lse = smp_lp_phase(r, pen, mkey, smp_key_value(mkey), smp_second(ctl_...).n_top, false, tid, hist, sub, wsum, &sh_bin, &sh_E,
+                         &sh_key, lpl);
     if (tid == 0) {
       token[s * token_stride] = (long long)midx;
       if (n_kept) n_kept[s] = 1;
       if (prob) prob[s] = 1.f;
+      if constexpr (kLp)
+        smp_lp_after(smp_second(ctl_...), smp_first(ctl_...), s, V, mkey, mkey, smp_key_value(mkey), lse, lpl);
       if constexpr (kCtl) smp_after(smp_first(ctl_...), s, (long long)midx);
     }
     return;
@@ -407,6 +640,8 @@ sample_rows_kernel(const bf16_t* __restrict__ logits, long long ld, int V, const
     tk = sh_key;
     __syncthreads();
   }
+  if constexpr (kLp)                             // hist is free here: top-k has read its counts, top-p has not begun
+    lse = smp_lp_phase(r, pen, mkey, xm, smp_second(ctl_...).n_top, use_k, tid, hist, sub, wsum, &sh_bin, &sh_E, &sh_key, lpl);
 
   // ---- top-p: keep a class while the mass strictly above it is below p Z_K
   unsigned tp = 0u;
@@ -544,6 +779,12 @@ sample_rows_kernel(const bf16_t* __restrict__ logits, long long ld, int V, const
         if (n_kept) n_kept[s] = (int)kept;
         if (prob) prob[s] = (float)((double)qe / (double)Z);
         counter[s] = ctr + 1;
+        if constexpr (kLp) {
+          unsigned ke = key[0];
+#pragma unroll
+          for (int i = 1; i < 8; ++i) if (e == i) ke = key[i];
+          smp_lp_after(smp_second(ctl_...), smp_first(ctl_...), s, V, ke, mkey, xm, lse, lpl);
+        }
         if constexpr (kCtl) smp_after(smp_first(ctl_...), s, j * 8 - r.off + e);
       }
       return;
@@ -571,6 +812,20 @@ static int sample_rows_check(const char* fn, const void* logits, int64_t ld, int
   return IVL_OK;
 }
 
+static int sample_rows_ctl_check(const char* fn, int V, const float* rep_penalty, const uint32_t* seen, int64_t seen_ld,
+                                 const int64_t* stop_ids, int n_stop, const int64_t* budget, const int64_t* n_new,
+                                 const int32_t* done, const int64_t* history, int64_t hist_ld) {
+  IVL_REQUIRE(!rep_penalty || seen, IVL_ERR_INVALID_ARG, "%s: rep_penalty needs seen", fn);
+  IVL_REQUIRE(!seen || seen_ld * 32 >= (int64_t)V, IVL_ERR_INVALID_ARG, "%s: seen_ld=%lld words hold fewer than V=%d bits", fn,
+              (long long)seen_ld, V);
+  IVL_REQUIRE(n_stop >= 0 && n_stop <= 16, IVL_ERR_INVALID_ARG, "%s: n_stop=%d outside 0..16", fn, n_stop);
+  IVL_REQUIRE(n_stop == 0 || (stop_ids && done), IVL_ERR_INVALID_ARG, "%s: n_stop=%d needs stop_ids and done", fn, n_stop);
+  IVL_REQUIRE(!budget || (n_new && done), IVL_ERR_INVALID_ARG, "%s: budget needs n_new and done", fn);
+  IVL_REQUIRE(!history || (n_new && hist_ld >= 1), IVL_ERR_INVALID_ARG, "%s: history needs n_new and hist_ld >= 1 (%lld)", fn,
+              (long long)hist_ld);
+  return IVL_OK;
+}
+
 extern "C" int ivl_sample_rows_fwd(const void* logits, int64_t ld, int S, int V, const float* temperature, const int32_t* top_k,
                                    const float* top_p, const int64_t* seed, int64_t* counter, int64_t* token,
                                    int64_t token_stride, int32_t* n_kept, float* prob, void* stream) {
@@ -583,28 +838,10 @@ extern "C" int ivl_sample_rows_fwd(const void* logits, int64_t ld, int S, int V,
   return check_launch("ivl_sample_rows_fwd");
 }
 
-extern "C" int ivl_sample_rows_ctl_fwd(const void* logits, int64_t ld, int S, int V, const float* temperature,
-                                       const int32_t* top_k, const float* top_p, const int64_t* seed, int64_t* counter,
-                                       int64_t* token, int64_t token_stride, int32_t* n_kept, float* prob,
-                                       const float* rep_penalty, uint32_t* seen, int64_t seen_ld, const int64_t* stop_ids,
-                                       int n_stop, const int64_t* budget, const int64_t* fill, int64_t* n_new, int32_t* done,
-                                       int64_t* history, int64_t hist_ld, void* stream) {
-  using namespace ivl;
-  const char* fn = "ivl_sample_rows_ctl_fwd";
-  const int rc = sample_rows_check(fn, logits, ld, S, V, temperature, top_k, top_p, seed, counter, token);
-  if (rc != IVL_OK) return rc;
-  IVL_REQUIRE(!rep_penalty || seen, IVL_ERR_INVALID_ARG, "%s: rep_penalty needs seen", fn);
-  IVL_REQUIRE(!seen || seen_ld * 32 >= (int64_t)V, IVL_ERR_INVALID_ARG, "%s: seen_ld=%lld words hold fewer than V=%d bits", fn,
-              (long long)seen_ld, V);
-  IVL_REQUIRE(n_stop >= 0 && n_stop <= 16, IVL_ERR_INVALID_ARG, "%s: n_stop=%d outside 0..16", fn, n_stop);
-  IVL_REQUIRE(n_stop == 0 || (stop_ids && done), IVL_ERR_INVALID_ARG, "%s: n_stop=%d needs stop_ids and done", fn, n_stop);
-  IVL_REQUIRE(!budget || (n_new && done), IVL_ERR_INVALID_ARG, "%s: budget needs n_new and done", fn);
-  IVL_REQUIRE(!history || (n_new && hist_ld >= 1), IVL_ERR_INVALID_ARG, "%s: history needs n_new and hist_ld >= 1 (%lld)", fn,
-              (long long)hist_ld);
-  if (!rep_penalty && !seen && n_stop == 0 && !budget && !n_new && !done && !history)      // no control: the control-free kernel
-    return ivl_sample_rows_fwd(logits, ld, S, V, temperature, top_k, top_p, seed, counter, token, token_stride, n_kept, prob,
-                               stream);
-  SmpCtl c;
+static ivl::SmpCtl sample_rows_ctl(const float* rep_penalty, uint32_t* seen, int64_t seen_ld, const int64_t* stop_ids, int n_stop,
+                                   const int64_t* budget, const int64_t* fill, int64_t* n_new, int32_t* done, int64_t* history,
+                                   int64_t hist_ld) {
+  ivl::SmpCtl c;
   c.rep_penalty = rep_penalty;
   c.seen = seen;
   c.seen_ld = seen_ld;
@@ -616,9 +853,67 @@ extern "C" int ivl_sample_rows_ctl_fwd(const void* logits, int64_t ld, int S, in
   c.done = done;
   c.history = (long long*)history;
   c.hist_ld = hist_ld;
+  return c;
+}
+
+extern "C" int ivl_sample_rows_ctl_fwd(const void* logits, int64_t ld, int S, int V, const float* temperature,
+                                       const int32_t* top_k, const float* top_p, const int64_t* seed, int64_t* counter,
+                                       int64_t* token, int64_t token_stride, int32_t* n_kept, float* prob,
+                                       const float* rep_penalty, uint32_t* seen, int64_t seen_ld, const int64_t* stop_ids,
+                                       int n_stop, const int64_t* budget, const int64_t* fill, int64_t* n_new, int32_t* done,
+                                       int64_t* history, int64_t hist_ld, void* stream) {
+  using namespace ivl;
+  const char* fn = "ivl_sample_rows_ctl_fwd";
+  int rc = sample_rows_check(fn, logits, ld, S, V, temperature, top_k, top_p, seed, counter, token);
+  if (rc != IVL_OK) return rc;
+  rc = sample_rows_ctl_check(fn, V, rep_penalty, seen, seen_ld, stop_ids, n_stop, budget, n_new, done, history, hist_ld);
+  if (rc != IVL_OK) return rc;
+  if (!rep_penalty && !seen && n_stop == 0 && !budget && !n_new && !done && !history)      // no control: the control-free kernel
+    return ivl_sample_rows_fwd(logits, ld, S, V, temperature, top_k, top_p, seed, counter, token, token_stride, n_kept, prob,
+                               stream);
+  const SmpCtl c = sample_rows_ctl(rep_penalty, seen, seen_ld, stop_ids, n_stop, budget, fill, n_new, done, history, hist_ld);
   hipLaunchKernelGGL(sample_rows_kernel<SmpCtl>, dim3((unsigned)S), dim3(SMP_THREADS), 0, (hipStream_t)stream,
                      (const bf16_t*)logits, (long long)ld, V, temperature, (const int*)top_k, top_p, (const long long*)seed,
                      (long long*)counter, (long long*)token, (long long)token_stride, (int*)n_kept, prob, c);
+  return check_launch(fn);
+}
+
+extern "C" int ivl_sample_rows_lp_fwd(const void* logits, int64_t ld, int S, int V, const float* temperature,
+                                      const int32_t* top_k, const float* top_p, const int64_t* seed, int64_t* counter,
+                                      int64_t* token, int64_t token_stride, int32_t* n_kept, float* prob,
+                                      const float* rep_penalty, uint32_t* seen, int64_t seen_ld, const int64_t* stop_ids,
+                                      int n_stop, const int64_t* budget, const int64_t* fill, int64_t* n_new, int32_t* done,
+                                      int64_t* history, int64_t hist_ld, float* logprob, int n_top, int64_t* top_ids,
+                                      float* top_logprobs, double* cum_logprob, float* lp_history, int64_t* top_hist_ids,
+                                      float* top_hist_lp, void* stream) {
+  using namespace ivl;
+  const char* fn = "ivl_sample_rows_lp_fwd";
+  int rc = sample_rows_check(fn, logits, ld, S, V, temperature, top_k, top_p, seed, counter, token);
+  if (rc != IVL_OK) return rc;
+  rc = sample_rows_ctl_check(fn, V, rep_penalty, seen, seen_ld, stop_ids, n_stop, budget, n_new, done, history, hist_ld);
+  if (rc != IVL_OK) return rc;
+  IVL_REQUIRE(n_top >= 0 && n_top <= SMP_TOP_MAX, IVL_ERR_INVALID_ARG, "%s: n_top=%d outside 0..%d", fn, n_top, SMP_TOP_MAX);
+  IVL_REQUIRE(n_top == 0 || (top_ids && top_logprobs), IVL_ERR_INVALID_ARG, "%s: n_top=%d needs top_ids and top_logprobs", fn, n_top);
+  IVL_REQUIRE(!(top_hist_ids || top_hist_lp) || n_top > 0, IVL_ERR_INVALID_ARG, "%s: the top rings need n_top > 0", fn);
+  IVL_REQUIRE(!(lp_history || top_hist_ids || top_hist_lp) || (n_new && hist_ld >= 1), IVL_ERR_INVALID_ARG,
+              "%s: lp_history and the top rings need n_new and hist_ld >= 1 (%lld)", fn, (long long)hist_ld);
+  if (!logprob && n_top == 0 && !top_ids && !top_logprobs && !cum_logprob && !lp_history && !top_hist_ids && !top_hist_lp)
+    return ivl_sample_rows_ctl_fwd(logits, ld, S, V, temperature, top_k, top_p, seed, counter, token, token_stride, n_kept, prob,
+                                   rep_penalty, seen, seen_ld, stop_ids, n_stop, budget, fill, n_new, done, history, hist_ld,
+                                   stream);
+  const SmpCtl c = sample_rows_ctl(rep_penalty, seen, seen_ld, stop_ids, n_stop, budget, fill, n_new, done, history, hist_ld);
+  SmpLp l;
+  l.logprob = logprob;
+  l.n_top = n_top;
+  l.top_ids = (long long*)top_ids;
+  l.top_lp = top_logprobs;
+  l.cum = cum_logprob;
+  l.lp_hist = lp_history;
+  l.top_hist_ids = (long long*)top_hist_ids;
+  l.top_hist_lp = top_hist_lp;
+  hipLaunchKernelGGL((sample_rows_kernel<SmpCtl, SmpLp>), dim3((unsigned)S), dim3(SMP_THREADS), 0, (hipStream_t)stream,
+                     (const bf16_t*)logits, (long long)ld, V, temperature, (const int*)top_k, top_p, (const long long*)seed,
+                     (long long*)counter, (long long*)token, (long long)token_stride, (int*)n_kept, prob, c, l);
   return check_launch(fn);
 }
 

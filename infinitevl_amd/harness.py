@@ -408,9 +408,17 @@ class Sampler:
     tokens the penalty needs) or `history` (a ring of the last `history` tokens per row) uses the controlled launch; one
     built without either samples exactly as before, until a row is given stop ids or a budget -- set that before the step is
     captured (the graphed classes recapture when they see the switch).  The kernel keeps n_new (tokens generated) and done
-    (0 running, 1 stop id, 2 budget) per row; a finished row gets its fill token until it is set or reset again."""
+    (0 running, 1 stop id, 2 budget) per row; a finished row gets its fill token until it is set or reset again.
 
-    def __init__(self, n_rows: int, device, vocab_size: Optional[int] = None, max_stop: int = 8, history: int = 0):
+    Scores (`logprobs` / `top_logprobs` of the reference's api/protocol.py, output_scores of HF generate): a sampler built
+    with `logprobs` = 0 (the emitted token's log-probability) or 1..20 (that plus the N most likely alternatives) uses the
+    scoring launch (ivl_sample_rows_lp_fwd) from construction on, so no recapture is involved: `logprob`, `top_ids`,
+    `top_logprob` hold the latest step's scores, `cum_logprob` (float64) their sum per row since set(), and with `history`
+    logprobs() / top_logprobs() return them token for token beside tokens().  The scored distribution is the one after the
+    repetition penalty and before temperature / top-k / top-p.  None = off: the sampler launches what it always did."""
+
+    def __init__(self, n_rows: int, device, vocab_size: Optional[int] = None, max_stop: int = 8, history: int = 0,
+                 logprobs: Optional[int] = None):
         if n_rows < 1:
             raise ValueError(f"Sampler: n_rows must be >= 1; got {n_rows}")
         if vocab_size is not None and (isinstance(vocab_size, bool) or not isinstance(vocab_size, int) or vocab_size < 1):
@@ -419,6 +427,8 @@ class Sampler:
             raise ValueError(f"Sampler: max_stop must be an int in [0, 16]; got {max_stop!r}")
         if isinstance(history, bool) or not isinstance(history, int) or history < 0:
             raise ValueError(f"Sampler: history must be an int >= 0; got {history!r}")
+        if logprobs is not None and (isinstance(logprobs, bool) or not isinstance(logprobs, int) or not 0 <= logprobs <= 20):
+            raise ValueError(f"Sampler: logprobs must be None or an int in [0, 20]; got {logprobs!r}")
         self.n_rows = int(n_rows)
         self.temperature = torch.zeros(n_rows, dtype=torch.float32, device=device)
         self.top_k = torch.zeros(n_rows, dtype=torch.int32, device=device)
@@ -436,6 +446,21 @@ class Sampler:
         self.done = torch.zeros(n_rows, dtype=torch.int32, device=device)         # 0 running, 1 stop id, 2 budget
         self.history = torch.zeros(n_rows, history, dtype=torch.int64, device=device) if history else None
         self._ends = [False] * n_rows                    # rows with a stop id or a budget (host copy, for run_until_done)
+        self.n_logprobs = logprobs
+        self.logprob = self.cum_logprob = self.top_ids = self.top_logprob = None
+        self.lp_history = self.top_hist_ids = self.top_hist_lp = None
+        if logprobs is not None:
+            self.controlled = True
+            self.logprob = torch.zeros(n_rows, dtype=torch.float32, device=device)
+            self.cum_logprob = torch.zeros(n_rows, dtype=torch.float64, device=device)
+            if history:
+                self.lp_history = torch.zeros(n_rows, history, dtype=torch.float32, device=device)
+            if logprobs:
+                self.top_ids = torch.full((n_rows, logprobs), -1, dtype=torch.int64, device=device)
+                self.top_logprob = torch.full((n_rows, logprobs), -math.inf, dtype=torch.float32, device=device)
+                if history:
+                    self.top_hist_ids = torch.full((n_rows, history, logprobs), -1, dtype=torch.int64, device=device)
+                    self.top_hist_lp = torch.full((n_rows, history, logprobs), -math.inf, dtype=torch.float32, device=device)
 
     def _row(self, row: int) -> int:
         if not isinstance(row, int) or not 0 <= row < self.n_rows:
@@ -444,7 +469,7 @@ class Sampler:
 
     def set(self, row: int, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0,
             repetition_penalty: float = 1.0, stop_token_ids=(), max_new_tokens: Optional[int] = None, fill_token: int = 0) -> None:
-        """Parameters and a fresh stream for `row`: counter 0, and the row's bitmap, n_new, done and history cleared.
+        """Parameters and a fresh stream for `row`: counter 0, and the row's bitmap, n_new, done, history and scores cleared.
         temperature 0 = greedy; top_k 0 and top_p 1 = off; repetition_penalty 1 = off (else finite and > 0: needs a sampler
         built with vocab_size); stop_token_ids: at most max_stop ints >= 0; max_new_tokens: None or an int >= 1; fill_token:
         what the row's token becomes once it is done."""
@@ -486,6 +511,10 @@ class Sampler:
             self.seen[row].zero_()
         if self.history is not None:
             self.history[row].zero_()
+        for t, v in ((self.logprob, 0.0), (self.cum_logprob, 0.0), (self.lp_history, 0.0), (self.top_ids, -1),
+                     (self.top_logprob, -math.inf), (self.top_hist_ids, -1), (self.top_hist_lp, -math.inf)):
+            if t is not None:
+                t[row] = v
         self._ends[row] = bool(stop) or max_new_tokens is not None
         if self._ends[row]:
             self.controlled = True
@@ -506,10 +535,13 @@ class Sampler:
 
     def _stateful(self):
         return {k: t for k, t in (("counter", self.counter), ("seen", self.seen), ("n_new", self.n_new), ("done", self.done),
-                                  ("history", self.history)) if t is not None}
+                                  ("history", self.history), ("logprob", self.logprob), ("cum_logprob", self.cum_logprob),
+                                  ("top_ids", self.top_ids), ("top_logprob", self.top_logprob), ("lp_history", self.lp_history),
+                                  ("top_hist_ids", self.top_hist_ids), ("top_hist_lp", self.top_hist_lp)) if t is not None}
 
     def state(self) -> Dict[str, torch.Tensor]:
-        """Everything a step changes (counter, seen, n_new, done, history), for a save around a capture's warm-up."""
+        """Everything a step changes (counter, seen, n_new, done, history, and the scores of a sampler built with logprobs), for
+        a save around a capture's warm-up."""
         return {k: t.clone() for k, t in self._stateful().items()}
 
     def load_state(self, state: Dict[str, torch.Tensor]) -> None:
@@ -536,6 +568,26 @@ class Sampler:
         a = n % self.history_len
         return torch.cat([h[a:], h[:a]])
 
+    def _ring(self, row: int, ring: Optional[torch.Tensor], what: str) -> torch.Tensor:
+        row = self._row(row)
+        if ring is None:
+            raise ValueError(f"Sampler.{what}: needs a Sampler built with history > 0 and logprobs"
+                             + (" >= 1" if what == "top_logprobs" else ""))
+        h, n = ring[row].cpu(), int(self.n_new[row].item())
+        if n <= self.history_len:
+            return h[:n].clone()
+        a = n % self.history_len
+        return torch.cat([h[a:], h[:a]])
+
+    def logprobs(self, row: int) -> torch.Tensor:
+        """The log-probabilities of the tokens `row` has generated (host, fp32 [n]): entry i belongs to tokens(row)[i]."""
+        return self._ring(row, self.lp_history, "logprobs")
+
+    def top_logprobs(self, row: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(ids int64 [n,N], log-probabilities fp32 [n,N]) of the N most likely tokens at each step of `row`, most likely
+        first: entry i belongs to tokens(row)[i]."""
+        return self._ring(row, self.top_hist_ids, "top_logprobs"), self._ring(row, self.top_hist_lp, "top_logprobs")
+
     def sample(self, logits: torch.Tensor, out: torch.Tensor, row: Optional[int] = None) -> torch.Tensor:
         """Tokens of every row (logits [n_rows,V]) or of the one `row` (logits [1,V]; views of the table, no copy) into `out`."""
         sl = slice(None) if row is None else slice(row, row + 1)
@@ -549,7 +601,11 @@ class Sampler:
                                  seen=self.seen[sl] if self.seen is not None else None,
                                  stop_ids=self.stop_ids[sl] if self.stop_ids is not None else None, budget=self.budget[sl],
                                  fill=self.fill[sl], n_new=self.n_new[sl], done=self.done[sl],
-                                 history=self.history[sl] if self.history is not None else None)
+                                 history=self.history[sl] if self.history is not None else None,
+                                 **{k: t[sl] for k, t in (("logprob", self.logprob), ("top_ids", self.top_ids),
+                                                          ("top_logprobs", self.top_logprob), ("cum_logprob", self.cum_logprob),
+                                                          ("lp_history", self.lp_history), ("top_hist_ids", self.top_hist_ids),
+                                                          ("top_hist_lp", self.top_hist_lp)) if t is not None})
 
 
 class GraphedDecode:

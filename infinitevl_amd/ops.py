@@ -1200,7 +1200,10 @@ def sample_tokens(logits: torch.Tensor, temperature: torch.Tensor, top_k: torch.
                   seen: Optional[torch.Tensor] = None, stop_ids: Optional[torch.Tensor] = None,
                   budget: Optional[torch.Tensor] = None, fill: Optional[torch.Tensor] = None,
                   n_new: Optional[torch.Tensor] = None, done: Optional[torch.Tensor] = None,
-                  history: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  history: Optional[torch.Tensor] = None, logprob: Optional[torch.Tensor] = None,
+                  top_ids: Optional[torch.Tensor] = None, top_logprobs: Optional[torch.Tensor] = None,
+                  cum_logprob: Optional[torch.Tensor] = None, lp_history: Optional[torch.Tensor] = None,
+                  top_hist_ids: Optional[torch.Tensor] = None, top_hist_lp: Optional[torch.Tensor] = None) -> torch.Tensor:
     """One next token per row of lm_head logits [S,V] or [S,1,V] (bf16, last dim contiguous) in one launch: temperature,
     top-k, top-p and the draw, per row (ivl_sample_rows_fwd states the semantics; HF generate's warpers + multinomial,
     api/chat.py:160-162 of the reference).  temperature / top_k / top_p / seed / counter: [S] fp32 / int32 / fp32 / int64 /
@@ -1213,7 +1216,15 @@ def sample_tokens(logits: torch.Tensor, temperature: torch.Tensor, top_k: torch.
     (a bitmap of W >= ceil(V/32) words per row, updated by the kernel); stop_ids [S,n] int64 (n <= 16, entries < 0 unused),
     budget [S] int64 (< 0: none) and fill [S] int64 with the state n_new [S] int64, done [S] int32 (0 running, 1 stop id,
     2 budget; a finished row gets its fill token and nothing else of it is touched) and history [S,H] int64 (a ring of the
-    last H tokens).  With none given this is the control-free launch."""
+    last H tokens).  With none given this is the control-free launch.
+
+    The keyword-only scores (ivl_sample_rows_lp_fwd states the semantics; `logprobs` / `top_logprobs` of the reference's
+    api/protocol.py, output_scores of HF generate), each optional, of the distribution after the repetition penalty and before
+    temperature / top-k / top-p: logprob [S] fp32 (of the token written); top_ids [S,N] int64 with top_logprobs [S,N] fp32
+    (0 < N <= 20: the N most likely tokens, most likely first, ties to the lowest id; id -1 / -inf past V); cum_logprob [S]
+    float64 (the kernel adds logprob to it); and, with n_new, rings at the index of `history`: lp_history [S,H] fp32,
+    top_hist_ids [S,H,N] int64 and top_hist_lp [S,H,N] fp32 (the H of `history` when that is given too).  With any of them
+    given the launch is the scoring form; the token and every control's state are those of the call without them."""
     if logits.dim() == 3 and logits.shape[1] == 1:
         logits = logits[:, 0]
     if logits.dim() != 2 or logits.dtype != torch.bfloat16 or logits.shape[0] < 1 or logits.shape[1] < 1:
@@ -1225,7 +1236,8 @@ def sample_tokens(logits: torch.Tensor, temperature: torch.Tensor, top_k: torch.
                         ("top_p", top_p, torch.float32), ("seed", seed, torch.int64), ("counter", counter, torch.int64),
                         ("n_kept", n_kept, torch.int32), ("prob", prob, torch.float32), ("rep_penalty", rep_penalty, torch.float32),
                         ("budget", budget, torch.int64), ("fill", fill, torch.int64), ("n_new", n_new, torch.int64),
-                        ("done", done, torch.int32)):
+                        ("done", done, torch.int32), ("logprob", logprob, torch.float32),
+                        ("cum_logprob", cum_logprob, torch.float64)):
         if t is None:
             continue
         if t.dtype != dt or tuple(t.shape) != (S,) or not t.is_contiguous():
@@ -1249,12 +1261,50 @@ def sample_tokens(logits: torch.Tensor, temperature: torch.Tensor, top_k: torch.
         raise ValueError("sample_tokens: budget needs n_new and done")
     if history is not None and (n_new is None or history.shape[1] < 1):
         raise ValueError("sample_tokens: history needs n_new and at least one entry per row")
+    scores = (logprob, top_ids, top_logprobs, cum_logprob, lp_history, top_hist_ids, top_hist_lp)
+    n_top, hist_ld = 0, (0 if history is None else history.shape[1])
+    if any(t is not None for t in scores):
+        if (top_ids is None) != (top_logprobs is None):
+            raise ValueError("sample_tokens: top_ids and top_logprobs come together")
+        if top_ids is not None:
+            n_top = top_ids.shape[1] if top_ids.dim() == 2 else -1
+            if not 1 <= n_top <= 20:
+                raise ValueError(f"sample_tokens: top_ids must be [{S},N] with 1 <= N <= 20; got {tuple(top_ids.shape)}")
+        for name, t, dt in (("top_ids", top_ids, torch.int64), ("top_logprobs", top_logprobs, torch.float32)):
+            if t is not None and (t.dtype != dt or tuple(t.shape) != (S, n_top) or not t.is_contiguous()):
+                raise ValueError(f"sample_tokens: {name} must be a contiguous {dt} tensor of [{S},{n_top}]; got {t.dtype} "
+                                 f"{tuple(t.shape)}")
+        rings = (("lp_history", lp_history, torch.float32, 2), ("top_hist_ids", top_hist_ids, torch.int64, 3),
+                 ("top_hist_lp", top_hist_lp, torch.float32, 3))
+        for name, t, dt, nd in rings:
+            if t is None:
+                continue
+            if n_new is None:
+                raise ValueError(f"sample_tokens: {name} needs n_new")
+            if nd == 3 and n_top == 0:
+                raise ValueError(f"sample_tokens: {name} needs top_ids and top_logprobs")
+            if hist_ld == 0 and t.dim() == nd:
+                hist_ld = t.shape[1]
+            want = (S, hist_ld) if nd == 2 else (S, hist_ld, n_top)
+            if t.dtype != dt or tuple(t.shape) != want or hist_ld < 1 or not t.is_contiguous():
+                raise ValueError(f"sample_tokens: {name} must be a contiguous {dt} tensor of {list(want)} (the history's "
+                                 f"length, at least 1); got {t.dtype} {tuple(t.shape)}")
+        if history is not None and any(t is not None for _, t, _, _ in rings) and S > 1 and history.stride(0) != hist_ld:
+            raise ValueError("sample_tokens: with lp_history or the top rings, history must be contiguous")
     if out is None:
         out = torch.empty(S, dtype=torch.int64, device=logits.device)
     if out.dtype != torch.int64 or tuple(out.shape) not in ((S,), (S, 1)):
         raise ValueError(f"sample_tokens: out must be int64 [{S}] or [{S},1]; got {out.dtype} {tuple(out.shape)}")
     controls = (rep_penalty, seen, stop_ids, budget, fill, n_new, done, history)
-    _need_gpu(logits, temperature, top_k, top_p, seed, counter, out, n_kept, prob, *controls)
+    _need_gpu(logits, temperature, top_k, top_p, seed, counter, out, n_kept, prob, *controls, *scores)
+    if any(t is not None for t in scores):
+        _lib.check(_lib.load().ivl_sample_rows_lp_fwd(
+            _p(logits), logits.stride(0) if S > 1 else V, S, V, _p(temperature), _p(top_k), _p(top_p), _p(seed), _p(counter),
+            _p(out), out.stride(0) if S > 1 else 1, _p(n_kept), _p(prob), _p(rep_penalty), _p(seen),
+            0 if seen is None else (seen.stride(0) if S > 1 else seen.shape[1]), _p(stop_ids), n_stop, _p(budget), _p(fill),
+            _p(n_new), _p(done), _p(history), hist_ld, _p(logprob), n_top, _p(top_ids), _p(top_logprobs), _p(cum_logprob),
+            _p(lp_history), _p(top_hist_ids), _p(top_hist_lp), _stream(logits)))
+        return out
     if all(t is None for t in controls):
         _lib.check(_lib.load().ivl_sample_rows_fwd(
             _p(logits), logits.stride(0) if S > 1 else V, S, V, _p(temperature), _p(top_k), _p(top_p), _p(seed), _p(counter),

@@ -23,6 +23,14 @@ A B A C per round; and the operator alone at the model's vocabulary with and wit
 than the 2 % of A the sampling launch is granted as a whole.
 
     python tools/multistream_decode.py --generation --slots 1,4 [--out profiles/generation_decode.json]
+
+--logprobs measures the scores of the same launch (Sampler(logprobs=)): per slot count the greedy step without a sampler (A), the
+sampled step (0.7 / 50 / 0.9) without scores (B) and the same with logprobs=5 and a 256-entry history (C: the log-probability of
+every token, the 5 most likely alternatives, their rings and the running sum), timed A B A C per round; and the operator alone at
+the model's vocabulary, greedy and sampled, with and without the scores.  No bar is asserted: C - B is reported beside the
+2 % of A the sampling launch is granted as a whole.
+
+    python tools/multistream_decode.py --logprobs --slots 1,4 [--out profiles/logprobs_decode.json]
 """
 import argparse
 import json
@@ -44,6 +52,7 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--sampling", action="store_true", help="time the sampled step against the greedy one (see above)")
     ap.add_argument("--generation", action="store_true", help="time the step with the generation controls (see above)")
+    ap.add_argument("--logprobs", action="store_true", help="time the step with logprobs and top-5 alternatives (see above)")
     args = ap.parse_args()
     import torch
     from infinitevl_amd.cache import MultiStreamCache
@@ -74,6 +83,8 @@ def main():
         return sampling_legs(args, torch, model, cfg, prompts, dev)
     if args.generation:
         return generation_legs(args, torch, model, cfg, prompts, dev)
+    if args.logprobs:
+        return logprobs_legs(args, torch, model, cfg, prompts, dev)
 
     # reference: one stream on the existing B = 1 graphed decode step
     c1 = model.allocate_inference_cache(1)
@@ -290,6 +301,79 @@ def generation_legs(args, torch, model, cfg, prompts, dev):
             op[f"S{S}_{pname}_controls_penalty_off_us"] = round(1000 * timed(lambda: r1.sample(lg, tok), 200), 2)
             op[f"S{S}_{pname}_controls_us"] = round(1000 * timed(lambda: ctl.sample(lg, tok), 200), 2)
             op[f"S{S}_{pname}_controls_rows_still_live"] = bool((ctl.poll()[0] == 0).all() and (r1.poll()[0] == 0).all())
+    res["operator_V%d" % V] = op
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+N_LOGPROBS = 5
+
+
+def logprobs_legs(args, torch, model, cfg, prompts, dev):
+    from infinitevl_amd.cache import MultiStreamCache
+    from infinitevl_amd.harness import GraphedMultiStreamDecode, Sampler
+    stream = torch.cuda.current_stream()
+    V = cfg.vocab_size
+
+    def timed(fn, n):
+        for _ in range(4):
+            fn()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        for _ in range(n):
+            fn()
+        e1.record(stream)
+        e1.synchronize()
+        return e0.elapsed_time(e1) / n
+
+    slots = [int(s) for s in args.slots.split(",")]
+    res = {"tool": "multistream_decode --logprobs", "layers": cfg.num_hidden_layers, "window": 4096, "steps": args.steps,
+           "rounds": args.rounds, "sampled": SAMPLED, "scored": {"logprobs": N_LOGPROBS, "history": HISTORY},
+           "bar": "none asserted; allowance_us = 2 % of greedy ms_per_step"}
+    for n in slots:
+        legs = {}
+        for name in ("greedy", "sampled", "scored"):
+            cache = MultiStreamCache(config=cfg, n_slots=n, device=dev, dtype=torch.bfloat16)
+            smp = None if name == "greedy" else (Sampler(n, dev) if name == "sampled" else
+                                                 Sampler(n, dev, history=HISTORY, logprobs=N_LOGPROBS))
+            dec = GraphedMultiStreamDecode(model, cache, sampler=smp)
+            for s in range(n):
+                dec.admit(s, prompts[s], sampling=None if name == "greedy" else dict(SAMPLED, seed=s + 1))
+            dec.capture()
+            legs[name] = dec.step
+        times = {k: [] for k in legs}
+        for _ in range(args.rounds):                            # A B A C
+            for name in ("sampled", "scored"):
+                times["greedy"].append(timed(legs["greedy"], args.steps))
+                times[name].append(timed(legs[name], args.steps))
+        a, b, c = (statistics.median(times[k]) for k in ("greedy", "sampled", "scored"))
+        row = {"greedy_ms_per_step": round(a, 4), "greedy_spread_ms": [round(min(times["greedy"]), 4), round(max(times["greedy"]), 4)]}
+        for name, t in (("sampled", b), ("scored", c)):
+            row[name] = {"ms_per_step": round(t, 4), "vs_greedy": round(t / a, 4), "delta_us": round(1000 * (t - a), 1),
+                         "spread_ms": [round(min(times[name]), 4), round(max(times[name]), 4)], "within_greedy_bar": bool(t <= 1.02 * a)}
+        print(f"slots{n}: A {a:.4f} B {b:.4f} C {c:.4f} ms", file=sys.stderr, flush=True)
+        row["scored_minus_sampled_us"] = round(1000 * (c - b), 1)
+        row["allowance_us"] = round(1000 * 0.02 * a, 1)
+        res[f"slots{n}"] = row
+        del legs
+    # the operator alone, back to back on one stream (launch-bound figures include the launch gap)
+    gen = torch.Generator(device=dev).manual_seed(1)
+    op = {}
+    for S in (1, 4):
+        lg = (torch.randn(S, V, generator=gen, device=dev) * 3.0).to(torch.bfloat16)
+        tok = torch.zeros(S, 1, dtype=torch.int64, device=dev)
+        for pname, kw in (("kernel_greedy", {}), ("sampled", SAMPLED)):
+            forms = {"": Sampler(S, dev), "_logprob_only": Sampler(S, dev, history=HISTORY, logprobs=0),
+                     "_logprobs5": Sampler(S, dev, history=HISTORY, logprobs=N_LOGPROBS),
+                     "_logprobs20": Sampler(S, dev, history=HISTORY, logprobs=20)}
+            for fname, smp in forms.items():
+                for s in range(S):
+                    smp.set(s, seed=s, **kw)
+                op[f"S{S}_{pname}{fname}_us"] = round(1000 * timed(lambda: smp.sample(lg, tok), 200), 2)
     res["operator_V%d" % V] = op
     line = json.dumps(res)
     print(line)
