@@ -4,26 +4,21 @@
 // Formulation (everything per query row stays inside one lane group; no P round trip through LDS):
 //   S^T = K Q^T      A = K tile rows (keys)      B = Q^T            -> lane owns ONE query row
 //   O^T = V^T P^T    A = V^T (LDS transpose read) B = P^T (in regs) -> same lane owns that row's O
-// A 64-key tile is staged once per workgroup (4 waves x 16 query rows) into LDS: K rows padded to 272 B
-// (ds_read_b128 of MFMA A fragments from ONE base register + immediates), V rows padded to 288 B
-// (conflict-free ds_read_b64_tr_b16).  The key -> MFMA k-slot map of the PV product is permuted so the
-// probabilities produced by the first MFMA feed the second one without any cross-lane movement:
-//   slot 8g+e  <->  key 32*ks + 4g + e (e<4)  |  key 32*ks + 16 + 4g + (e-4) (e>=4).
+// A 64-key tile is staged once per workgroup (4 waves x 16 query rows) into LDS; the tile itself (LDS image, QK^T, online
+// softmax, the permuted key -> k-slot map of the PV product, row store) is attn_tile64.h, shared with vision_attn.hip.
 // Band (bit-exact contract): row with token index t sees call-local keys
 //   lo = max(0, n_prev + t - W + 1) .. hi = n_prev + t.
 // Long key ranges are optionally split across workgroups (flash-decoding); a combine kernel merges.
 #include "ivl_common.h"
-#include "swa_shared.h"
+#include "attn_tile64.h"
 #include <type_traits>
 
 namespace ivl {
 
 constexpr int SWA_QT = 64;           // query rows per workgroup
-constexpr int SWA_KT = 64;           // keys per tile
-constexpr int SWA_KSTRIDE = 256;     // bytes per K row in LDS; 16-byte pieces XOR-swizzled by the row (see below)
-constexpr int SWA_VSTRIDE = 288;     // bytes per V row in LDS (padded)
-constexpr int SWA_LDS_K = SWA_KT * SWA_KSTRIDE;
-constexpr int SWA_LDS_BYTES = SWA_LDS_K + SWA_KT * SWA_VSTRIDE;
+constexpr int SWA_KT = TILE64_KT;    // keys per tile
+constexpr int SWA_VSTRIDE = tile64_v_stride(SWA_D);      // LDS image: attn_tile64.h
+constexpr int SWA_LDS_BYTES = tile64_lds_bytes(SWA_D);
 constexpr int SWA_MAX_SPLIT = 16;        // prefill / split-KV with register-resident combine
 constexpr int SWA_MAX_SPLIT_PACK = 64;   // packed decode rows: one 64-key tile per workgroup
 IVL_TRACE_DECL(swa)
@@ -41,26 +36,7 @@ struct SwaParams {
   const bf16_t* rcos; const bf16_t* rsin; int rs0, rs1;
 };
 
-// QG = 16-row query groups per wave.  Only QG = 1 (64 rows per workgroup, decode / short calls) is instantiated: there the 4 waves
-// of a workgroup pull 128 KB through the 128 B/clk LDS port per 64-key tile (1024 clk) for 512 clk of MFMA work per SIMD.  QG = 2
-// (128 rows per workgroup, every K / V^T fragment read from LDS feeding two MFMAs) was round 2a's answer to that; swa_prefill_kernel
-// superseded it and it is no longer instantiated.
-// butterfly over the four 16-lane groups of a wave (the lanes that share a query row) on the gfx950 lane-swap
-// instructions: v_permlane16_swap exchanges odd rows of one operand with even rows of the other, v_permlane32_swap
-// the upper half with the lower half; with both operands = x the two results hold x and its partner.
-__device__ __forceinline__ float group_max(float x) {
-  auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-  x = vmax2(__uint_as_float(a[0]), __uint_as_float(a[1]));
-  auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-  return vmax2(__uint_as_float(b[0]), __uint_as_float(b[1]));
-}
-__device__ __forceinline__ float group_sum(float x) {
-  auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-  x = __uint_as_float(a[0]) + __uint_as_float(a[1]);
-  auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-  return __uint_as_float(b[0]) + __uint_as_float(b[1]);
-}
-
+// QG = 16-row query groups per wave; only QG = 1 is instantiated (decode / T <= 64 calls), longer calls run swa_prefill_kernel.
 template <bool PACK, int QG>
 __global__ __launch_bounds__(256, 2) void swa_fwd_kernel(const long long* pos_dev, SwaParams p) {   // (pos_dev: see swa_prefill_kernel)
 #define SWA_ROWS 0
@@ -407,7 +383,6 @@ __global__ __launch_bounds__(P8_THREADS, 1) void swa_prefill_kernel(const long l
     for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
       for (int mt = 0; mt < 4; ++mt) {
-        typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
         const unsigned char* vp = smem + (av[mt] + so) + 16 * ks * 256;
         const s16x4 a0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)vp);
         const s16x4 a1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(vp + 8 * 256));
@@ -725,20 +700,10 @@ __global__ __launch_bounds__(256, 2) void swa_decode_fp8_kernel(const long long*
 
   if (!row_ok) return;
   if (p.nsplit == 1) {
-    const float inv = l_run > 0.f ? 1.0f / l_run : 0.f;
-    bf16_t* op = p.o + (((long long)b * p.T + t_row) * p.Hq + hq) * SWA_D + 4 * g;
-#pragma unroll
-    for (int mt2 = 0; mt2 < 8; ++mt2)
-      *(u32x2*)(op + 16 * mt2) = u32x2{pack2bf(oacc[mt2][0] * inv, oacc[mt2][1] * inv), pack2bf(oacc[mt2][2] * inv, oacc[mt2][3] * inv)};
+    tile64_store_row<8, true>(p.o + (((long long)b * p.T + t_row) * p.Hq + hq) * SWA_D + 4 * g, oacc, l_run);
   } else {
     const long long prow = (((long long)b * p.nsplit + split) * p.T + t_row) * p.Hq + hq;
-    float* po = p.part_o + prow * SWA_D + 4 * g;
-#pragma unroll
-    for (int mt2 = 0; mt2 < 8; ++mt2) *(f32x4*)(po + 16 * mt2) = oacc[mt2];
-    if (g == 0) {
-      p.part_ml[prow * 2] = m_run;
-      p.part_ml[prow * 2 + 1] = l_run;
-    }
+    tile64_store_partial(p.part_o + prow * SWA_D + 4 * g, p.part_ml + prow * 2, g, oacc, m_run, l_run);
   }
 }
 
@@ -859,8 +824,6 @@ __global__ __launch_bounds__(256) void swa_rows_combine_wide_kernel(const float*
 // stand-alone ring append (ivl_swa_cache_append, and ivl_swa_fwd with append_new when no combine launch follows)
 __global__ __launch_bounds__(256) void swa_cache_append_kernel(AppendArgs ap) { ring_append(ap, blockIdx.x, gridDim.x); }
 
-// The 64-row kernel (QG = 1) serves decode / T <= 64 calls; longer calls run swa_prefill_kernel.  The QG = 2 form of round 2a (two
-// 16-row groups per wave) is superseded by it and not instantiated; QG stays a template parameter of swa_fwd_kernel.
 static int swa_base_nsplit(int B, int T, int Hq) {
   const bool prefill = T > SWA_QT;
   const int qt = prefill ? PF_QT : SWA_QT;

@@ -35,7 +35,6 @@ constexpr int R2_AHEAD = 3;                  // tiles requested ahead
 constexpr int R2_LDS = R2_NST * R2_STAGE;    // 128 KB
 constexpr int R2_PAD_ROWS = 64;              // zero rows behind the linear keys (the last tile of the last q-tile ends 1 key late)
 
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 
 // a wave-uniform pointer the compiler has lost track of (derived from blockIdx through divisions): back into SGPRs for the
 // scalar-base operand of the LDS-DMA instruction

@@ -7,7 +7,7 @@
 //     patches; 16 heads x 80 channels in the 3B model (window layers: <= 64 patches per segment, the four "full"
 //     layers: one segment per frame).
 //
-// Same construction as the 64-row sliding-window kernel (swa.hip: S^T = K Q^T and O^T = V^T P^T on
+// The 64-key tile of the 64-row sliding-window kernel (attn_tile64.h: S^T = K Q^T and O^T = V^T P^T on
 // v_mfma_f32_16x16x32_bf16, online softmax with lane-local rows, P^T packed in place), minus everything a ViT does not
 // have (ring cache, band, GQA, split-KV), plus a head dimension that is not a multiple of 32:
 //   D = 80 : the QK contraction runs over 96 channels (the 16-byte pieces 10, 11 of every K row in LDS and of every Q
@@ -16,17 +16,13 @@
 // ceil(max_seqlen / 64) tiles per segment (tiles beyond a segment's length exit at once: the host never reads
 // cu_seqlens, so the call is graph-capturable), mapped onto the XCDs so that the tiles of one (segment, head) share an L2.
 #include "ivl_common.h"
+#include "attn_tile64.h"
 
 namespace ivl {
 
-typedef __bf16 mfma_bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-
 IVL_TRACE_DECL(vis)
 
-constexpr float VA_LOG2E = 1.4426950408889634f;
-constexpr int VA_QT = 64, VA_KT = 64;
+constexpr int VA_QT = 64, VA_KT = TILE64_KT;
 
 struct VisionAttnParams {
   const bf16_t* q; const bf16_t* k; const bf16_t* v; bf16_t* o;
@@ -36,35 +32,6 @@ struct VisionAttnParams {
   int k_rotated;                                                 // the keys come from the rotary pre-pass: only q is rotated in the kernel
   float scaling;
 };
-
-__device__ __forceinline__ mfma_bf16x8 va_mfma(u32x4 v) {
-  mfma_bf16x8 r;
-  __builtin_memcpy(&r, &v, 16);
-  return r;
-}
-__device__ __forceinline__ float va_max2(float a, float b) {
-  float r;
-  asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
-__device__ __forceinline__ float va_max3(float a, float b, float c) {
-  float r;
-  asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-  return r;
-}
-// butterflies over the four 16-lane groups of a wave (the lanes that share a query row)
-__device__ __forceinline__ float va_group_max(float x) {
-  auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-  x = va_max2(__uint_as_float(a[0]), __uint_as_float(a[1]));
-  auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-  return va_max2(__uint_as_float(b[0]), __uint_as_float(b[1]));
-}
-__device__ __forceinline__ float va_group_sum(float x) {
-  auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-  x = __uint_as_float(a[0]) + __uint_as_float(a[1]);
-  auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-  return __uint_as_float(b[0]) + __uint_as_float(b[1]);
-}
 
 // apply_rotary_pos_emb_vision on one 16-byte piece (8 channels c0..c0+7 of one token and head):
 //   out = x * cos + rotate_half(x) * sin,  rotate_half(x)[c] = -x[c + D/2] (c < D/2) | x[c - D/2] (c >= D/2)
@@ -100,14 +67,8 @@ __global__ __launch_bounds__(256, 2) void vision_attn_kernel(VisionAttnParams p)
   constexpr int DK = (D + 31) / 32 * 32;       // contraction length of the QK product (zero padded)
   constexpr int NKS = DK / 32;                 // QK MFMA steps
   constexpr int NDT = D / 16;                  // PV output column tiles
-  // K rows of 256 B with the 16-byte pieces XOR-swizzled by the row (piece' = piece ^ (row & 15), as in swa.hip: the
-  // ds_read_b128 lane groups {0-3,12-15,20-27}, ... see distinct banks; a padded 208-byte row measured 37 % of the LDS
-  // cycles as bank conflicts).  V rows: ds_read_b64_tr_b16 serves 8 rows x 32 B per 32-lane group, conflict-free when the
-  // row stride is an odd multiple of 32 B: 160 B (D = 80) as it is, 128 / 256 B rows get 32 B of padding.
-  constexpr int KS = 256;
-  constexpr int VS = (D * 2 / 32) % 2 == 1 ? D * 2 : D * 2 + 32;
-  constexpr int LDS_K = VA_KT * KS;
-  __shared__ __attribute__((aligned(16))) unsigned char smem[LDS_K + VA_KT * VS];
+  constexpr int VS = tile64_v_stride(D);       // LDS image: attn_tile64.h
+  __shared__ __attribute__((aligned(16))) unsigned char smem[tile64_lds_bytes(D)];
 
   IVL_T(tv_start);
   IVL_TVAR(tv_b1); IVL_TVAR(tv_st); IVL_TVAR(tv_qk); IVL_TVAR(tv_sm); IVL_TVAR(tv_pv);
@@ -157,7 +118,7 @@ __global__ __launch_bounds__(256, 2) void vision_attn_kernel(VisionAttnParams p)
   if constexpr (DK > D) {
     constexpr int NPAD = DK / 8 - NCH;
     for (int i = tid; i < VA_KT * NPAD; i += 256)
-      *(u32x4*)(smem + (i / NPAD) * KS + (((NCH + i % NPAD) ^ ((i / NPAD) & 15)) << 4)) = u32x4{0u, 0u, 0u, 0u};
+      *(u32x4*)(smem + tile64_k_off(i / NPAD, NCH + i % NPAD)) = u32x4{0u, 0u, 0u, 0u};
   }
 
   float m_run[QG], l_run[QG];
@@ -213,44 +174,21 @@ __global__ __launch_bounds__(256, 2) void vision_attn_kernel(VisionAttnParams p)
       }
     }
   };
-  auto store_tile = [&]() {
-    if (!s_act) return;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int r = srow + 16 * i;
-      *(u32x4*)(smem + r * KS + ((schunk ^ (r & 15)) << 4)) = kreg[i];
-      *(u32x4*)(smem + LDS_K + r * VS + schunk * 16) = vreg[i];
-    }
-  };
-
   const int n_kt = (len + VA_KT - 1) / VA_KT;
   load_tile(0);
-  const float sc = p.scaling * VA_LOG2E;
+  const float sc = p.scaling * LOG2E;
 
   IVL_T(tv_loop);
   for (int kt = 0; kt < n_kt; ++kt) {
     IVL_T(t0);
     __syncthreads();
     IVL_T(t1);
-    store_tile();
+    if (s_act) tile64_stage<VS>(smem, srow, schunk, kreg, vreg);
     __syncthreads();
     IVL_T(t2);
 
-    // ---- S^T = K Q^T : 4 key sub-tiles x NKS channel steps -----------------------------------------------------
     f32x4 sacc[QG][4];
-#pragma unroll
-    for (int qg = 0; qg < QG; ++qg)
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt) sacc[qg][mt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int ks = 0; ks < NKS; ++ks)
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt) {
-        const u32x4 kf = *(const u32x4*)(smem + (16 * mt + l15) * KS + (((4 * ks + g) ^ l15) << 4));
-#pragma unroll
-        for (int qg = 0; qg < QG; ++qg)
-          sacc[qg][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(va_mfma(kf), va_mfma(qf[qg][ks]), sacc[qg][mt], 0, 0, 0);
-      }
+    tile64_qk<NKS, QG>(smem, l15, g, qf, sacc);
     if (kt + 1 < n_kt) load_tile(kt + 1);      // lands under the softmax and the PV product
     IVL_T(t3);
 
@@ -265,67 +203,11 @@ __global__ __launch_bounds__(256, 2) void vision_attn_kernel(VisionAttnParams p)
 #pragma unroll
           for (int r = 0; r < 4; ++r) sacc[qg][mt][r] = jbase + 16 * mt + r < len ? sacc[qg][mt][r] : -INFINITY;
       }
-      // the FIRST reader of the MFMA results is an instruction the compiler sees (its hazard recognizer does not look
-      // inside inline asm; see swa.hip)
-      float rmax = va_max2(__builtin_fmaxf(sacc[qg][0][0], sacc[qg][0][1]), sacc[qg][0][2]);
-      rmax = va_max3(rmax, sacc[qg][0][3], sacc[qg][1][0]);
-      rmax = va_max3(rmax, sacc[qg][1][1], sacc[qg][1][2]);
-      rmax = va_max3(rmax, sacc[qg][1][3], sacc[qg][2][0]);
-      rmax = va_max3(rmax, sacc[qg][2][1], sacc[qg][2][2]);
-      rmax = va_max3(rmax, sacc[qg][2][3], sacc[qg][3][0]);
-      rmax = va_max3(rmax, sacc[qg][3][1], sacc[qg][3][2]);
-      rmax = va_max2(rmax, sacc[qg][3][3]);
-      rmax = va_group_max(rmax) * sc;                          // sc > 0: max commutes with the scale
-      const float m_new = va_max2(m_run[qg], rmax);            // every tile holds at least one valid key: finite
-      float rsum = 0.f;
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float pv = __builtin_amdgcn_exp2f(__builtin_fmaf(sacc[qg][mt][r], sc, -m_new));   // argument <= 0
-          sacc[qg][mt][r] = pv;
-          rsum += pv;
-        }
-      rsum = va_group_sum(rsum);
-      if (__any(m_new > m_run[qg])) {                          // some row's running maximum moved: rescale (exact)
-        const float alpha = __builtin_amdgcn_exp2f(m_run[qg] - m_new);      // m_run = -inf -> 0
-        l_run[qg] = l_run[qg] * alpha + rsum;
-#pragma unroll
-        for (int i = 0; i < NDT; ++i) oacc[qg][i] *= alpha;
-      } else {
-        l_run[qg] += rsum;
-      }
-      m_run[qg] = m_new;
-      // P^T fragments (B operand): slots 8g+e <-> keys 32 ks2 + 4g + e | 32 ks2 + 16 + 4g + (e - 4)
-#pragma unroll
-      for (int ks2 = 0; ks2 < 2; ++ks2) {
-        pf[qg][ks2].x = pack2bf(sacc[qg][2 * ks2][0], sacc[qg][2 * ks2][1]);
-        pf[qg][ks2].y = pack2bf(sacc[qg][2 * ks2][2], sacc[qg][2 * ks2][3]);
-        pf[qg][ks2].z = pack2bf(sacc[qg][2 * ks2 + 1][0], sacc[qg][2 * ks2 + 1][1]);
-        pf[qg][ks2].w = pack2bf(sacc[qg][2 * ks2 + 1][2], sacc[qg][2 * ks2 + 1][3]);
-      }
+      const Tile64Probs t = tile64_probs<false>(sacc[qg][0], sacc[qg][1], sacc[qg][2], sacc[qg][3], sc, m_run[qg]);
+#include "attn_tile64_rescale.inc"
     }
     IVL_T(t4);
-    // ---- O^T += V^T P^T : NDT column tiles x 2 key steps ------------------------------------------------------
-    const unsigned char* vbase = smem + LDS_K;
-#pragma unroll
-    for (int mt2 = 0; mt2 < NDT; ++mt2)
-#pragma unroll
-      for (int ks2 = 0; ks2 < 2; ++ks2) {
-        // 16-lane group g reads the 4x16 block rows (32 ks2 [+16] + 4g .. +3), columns 16 mt2 .. +15; lane i supplies
-        // the address of row (i >> 2), columns 4 (i & 3) .. +3 and receives column i
-        const int r0 = 32 * ks2 + 4 * g + (l15 >> 2);
-        const int cb = (16 * mt2 + 4 * (l15 & 3)) * 2;
-        const s16x4 a0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(vbase + r0 * VS + cb));
-        const s16x4 a1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(vbase + (r0 + 16) * VS + cb));
-        u32x2 w0, w1;
-        __builtin_memcpy(&w0, &a0, 8);
-        __builtin_memcpy(&w1, &a1, 8);
-        const u32x4 vf = u32x4{w0.x, w0.y, w1.x, w1.y};
-#pragma unroll
-        for (int qg = 0; qg < QG; ++qg)
-          oacc[qg][mt2] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(va_mfma(vf), va_mfma(pf[qg][ks2]), oacc[qg][mt2], 0, 0, 0);
-      }
+    tile64_pv<NDT, QG, VS>(smem, l15, g, pf, oacc);
     IVL_T(t5);
     IVL_TACC(tv_b1, t1, t0); IVL_TACC(tv_st, t2, t1); IVL_TACC(tv_qk, t3, t2); IVL_TACC(tv_sm, t4, t3); IVL_TACC(tv_pv, t5, t4);
   }
@@ -337,11 +219,7 @@ __global__ __launch_bounds__(256, 2) void vision_attn_kernel(VisionAttnParams p)
 #pragma unroll
   for (int qg = 0; qg < QG; ++qg) {
     if (!row_ok[qg]) continue;
-    const float inv = 1.0f / l_run[qg];        // l_run >= 1 term: the row's own maximum contributes 2^0
-    bf16_t* op = p.o + tok_q[qg] * p.o_st + (long long)h * p.o_sh + 4 * g;
-#pragma unroll
-    for (int mt2 = 0; mt2 < NDT; ++mt2)
-      *(u32x2*)(op + 16 * mt2) = u32x2{pack2bf(oacc[qg][mt2][0] * inv, oacc[qg][mt2][1] * inv), pack2bf(oacc[qg][mt2][2] * inv, oacc[qg][mt2][3] * inv)};
+    tile64_store_row<NDT, false>(p.o + tok_q[qg] * p.o_st + (long long)h * p.o_sh + 4 * g, oacc[qg], l_run[qg]);
   }
 }
 
