@@ -519,6 +519,29 @@ IVL_API int ivl_sample_rows_lp_fwd(const void* logits, int64_t ld, int S, int V,
  * IVL_ERR_INVALID_ARG. */
 IVL_API int ivl_token_mark_fwd(uint32_t* seen_row, int64_t V, const int64_t* ids, int64_t n, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Row fork: row `src_row` of every tensor of a table goes to a set of rows of the partner tensors, in one launch.  The state of
+ * a stream (ring rows, conv and recurrent states, position, sampler rows) is one row each of many tensors: this is the clone of
+ * the reference's streaming demo (inference_examples/demo_streaming_inference.py:357-398) and the fan-out behind
+ * num_return_sequences (src/llamafactory/api/chat.py:164), between two replays of a captured step.
+ * table: DEVICE int64 [n_entries][6], built once by the caller and kept:
+ *     {src_base, dst_base, src_row_stride_bytes, dst_row_stride_bytes, row_bytes, first_piece}
+ *   Row r of an entry is the row_bytes >= 1 bytes at base + r * row_stride_bytes.  A row is cut into pieces of 16384 bytes;
+ *   first_piece is the number of pieces of all entries before this one (entry 0: 0), which makes the pieces of the table one
+ *   flat work list that the workgroups share evenly, whatever the mix of entry sizes.
+ * dst_mask: bit r set = row r of every entry's destination tensor is written.  Every source byte is read once and stored to
+ *   every destination; 16-byte accesses where the source and all destinations of a piece sit at the same offset in a 16-byte
+ *   line (bytes before and after), single bytes otherwise; no byte outside a destination row is written, none outside the source
+ *   row read.  An entry whose src_base == dst_base never copies src_row onto itself (that bit is skipped in the kernel; a caller
+ *   that can see the table refuses it: the host side of this call cannot, the table is device memory).  Overlapping source and
+ *   destination rows are the caller's to exclude.
+ * max_row_bytes: the largest row_bytes of the table (it bounds the grid).  No allocation, copy or synchronisation: capturable.
+ * IVL_ERR_INVALID_ARG: NULL table, n_entries < 1, max_row_bytes < 1, src_row < 0, dst_mask == 0.
+ * IVL_ERR_UNSUPPORTED: src_row >= 63 or bit 63 of dst_mask (rows 0..62 only).
+ * ------------------------------------------------------------------------------------------- */
+IVL_API int ivl_rows_copy_fwd(const int64_t* table, int n_entries, int64_t max_row_bytes, int src_row, int64_t dst_mask,
+                              void* stream);
+
 #ifdef __cplusplus
 }
 #endif

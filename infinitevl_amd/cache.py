@@ -642,7 +642,9 @@ class MultiStreamCache(StaticCachePrealloc):
     decode steps.  Every slot has its own ring position (`pos_rows`, device int64 [n_slots], shared by all sliding layers;
     `slot_lengths` is its host mirror).  A decode step advances every slot by one token in one launch (idle slots compute
     on zeros; their outputs are ignored).  A prompt is prefilled on `slot_view(slot)`, a B = 1 cache aliasing the slot's
-    row, through the unchanged stack forward.  bf16 only; a stack forward needs explicit position_ids."""
+    row, through the unchanged stack forward.  bf16 only; a stack forward needs explicit position_ids.
+    A slot's history is one row of every tensor: fork() copies it to other slots, load() / store() exchange it with another
+    cache, each in one launch (ops.RowCopyPlan)."""
     _sliding_layer_cls = MultiStreamSlidingLayer
 
     def __init__(self, *, config, n_slots: int, device="cpu", dtype: torch.dtype = torch.float32):
@@ -693,6 +695,123 @@ class MultiStreamCache(StaticCachePrealloc):
         self.slot_lengths[slot] = 0
 
     release = admit
+
+    # ---- a slot's state as one row: fork inside the cache, load from / store to another cache ------------------------
+    def row_tensors(self):
+        """Every tensor that holds one row per slot: the carried tensors of every layer, then the ring positions."""
+        out = []
+        for i, layer in enumerate(self.layers):
+            if not isinstance(layer, (MultiStreamSlidingLayer, StaticLinearLayerPrealloc)):
+                raise ValueError(f"MultiStreamCache: layer {i}: unsupported layer type {type(layer).__name__}")
+            out += layer.carried_tensors()
+        return out + [self.pos_rows]
+
+    def _other_rows(self, other: StaticCachePrealloc, what: str):
+        """(row tensors of `other` in the order of row_tensors(), its number of rows): layer types, shapes after the row and
+        dtypes checked against this cache's."""
+        if not isinstance(other, StaticCachePrealloc) or len(other.layers) != len(self.layers):
+            raise ValueError(f"MultiStreamCache.{what}: needs a StaticCachePrealloc or MultiStreamCache of the same config "
+                             f"({len(self.layers)} layers); got {type(other).__name__}"
+                             + (f" of {len(other.layers)} layers" if hasattr(other, "layers") else ""))
+        out = []
+        for i, (mine, theirs) in enumerate(zip(self.layers, other.layers)):
+            sliding = isinstance(mine, StaticSlidingWindowLayerPrealloc)
+            if sliding != isinstance(theirs, StaticSlidingWindowLayerPrealloc) or \
+                    (not sliding and not isinstance(theirs, StaticLinearLayerPrealloc)):
+                raise ValueError(f"MultiStreamCache.{what}: layer {i}: {type(theirs).__name__} does not match "
+                                 f"{type(mine).__name__}")
+            a, b = mine.carried_tensors(), theirs.carried_tensors()
+            if len(a) != len(b):
+                raise ValueError(f"MultiStreamCache.{what}: layer {i}: {len(b)} carried tensors for {len(a)}")
+            for ta, tb in zip(a, b):
+                if tuple(ta.shape[1:]) != tuple(tb.shape[1:]) or ta.dtype != tb.dtype:
+                    raise ValueError(f"MultiStreamCache.{what}: layer {i}: {tb.dtype} {tuple(tb.shape)} does not match "
+                                     f"{ta.dtype} {tuple(ta.shape)} after the row")
+            out += b
+        n_rows = other.layers[0].batch_size
+        if isinstance(other, MultiStreamCache):
+            pos = other.pos_rows
+        else:                                   # one counter for all rows of a StaticCachePrealloc: every row reads it
+            sl = [l for l in other.layers if isinstance(l, StaticSlidingWindowLayerPrealloc)][0]
+            pos = sl._pos_dev if n_rows == 1 else sl._pos_dev.expand(n_rows)
+        return out + [pos], n_rows
+
+    def _other_length(self, other: StaticCachePrealloc, row: int) -> int:
+        if isinstance(other, MultiStreamCache):
+            return int(other.slot_lengths[row])
+        return int([l for l in other.layers if isinstance(l, StaticSlidingWindowLayerPrealloc)][0].cumulative_length)
+
+    def _plan(self, kind: str, other: Optional[StaticCachePrealloc] = None) -> "ops.RowCopyPlan":
+        """The copy plan of fork / load / store, built once per (source, destination) identity.  A shallow copy of this cache
+        (clone()) or another `other` at a recycled address never reuses a plan: it holds the tensors' addresses."""
+        import weakref
+        plans = self.__dict__.get("_row_plans")
+        if plans is None or plans[0] != id(self):
+            plans = self._row_plans = (id(self), {})
+        key = (kind, id(other))
+        hit = plans[1].get(key)
+        if hit is not None and (other is None or hit[0]() is other):
+            return hit[1]
+        for k in [k for k, v in plans[1].items() if v[0] is not None and v[0]() is None]:
+            del plans[1][k]
+        if kind == "fork":
+            plan = ops.RowCopyPlan([(t, t) for t in self.row_tensors()])
+        else:
+            theirs, _ = self._other_rows(other, kind)
+            mine = self.row_tensors()
+            plan = ops.RowCopyPlan(list(zip(theirs, mine)) if kind == "load" else list(zip(mine, theirs)))
+        plans[1][key] = (None if other is None else weakref.ref(other), plan)
+        return plan
+
+    def _check_dsts(self, dsts):
+        dsts = [self._check_slot(d) for d in dsts]
+        if not dsts or len(set(dsts)) != len(dsts):
+            raise ValueError(f"MultiStreamCache: the destination slots must be distinct and at least one; got {dsts}")
+        return dsts
+
+    def fork(self, src: int, dsts) -> None:
+        """Slots `dsts` become copies of slot `src`: every carried tensor of every layer and the ring position, in ONE launch
+        (ops.RowCopyPlan).  In-place writes only: valid between replays of a captured graph."""
+        src, dsts = self._check_slot(src), self._check_dsts(dsts)
+        self._plan("fork").run(src, dsts)
+        for d in dsts:
+            self.slot_lengths[d] = self.slot_lengths[src]
+
+    def load(self, dsts, cache: StaticCachePrealloc, row: int = 0) -> None:
+        """Slots `dsts` become copies of row `row` of another cache of the same config and dtype (a StaticCachePrealloc -- the
+        B = 1 cache of a running video stream -- or a MultiStreamCache), ring position included, in one launch.  The source is
+        only read (a GDN layer it never used is first zeroed, as its first call would read it)."""
+        dsts = self._check_dsts(dsts)
+        _, n_rows = self._other_rows(cache, "load")
+        if isinstance(row, bool) or not isinstance(row, int) or not 0 <= row < n_rows:
+            raise ValueError(f"MultiStreamCache.load: row must be an int in [0, {n_rows}); got {row!r}")
+        cache.ensure_started()
+        self._plan("load", cache).run(row, dsts)
+        n = self._other_length(cache, row)
+        for d in dsts:
+            self.slot_lengths[d] = n
+
+    def store(self, slot: int, cache: StaticCachePrealloc, row: int = 0) -> None:
+        """The reverse of load: row `row` of `cache` becomes a copy of slot `slot`, its device counter in the same launch;
+        its host counters are left as import_carried(length) leaves them.  A StaticCachePrealloc target has one row (its
+        rows share one position counter)."""
+        slot = self._check_slot(slot)
+        _, n_rows = self._other_rows(cache, "store")
+        if not isinstance(cache, MultiStreamCache) and n_rows != 1:
+            raise ValueError(f"MultiStreamCache.store: a StaticCachePrealloc target must have batch_size 1 (its rows share one "
+                             f"position counter); got {n_rows}")
+        if isinstance(row, bool) or not isinstance(row, int) or not 0 <= row < n_rows:
+            raise ValueError(f"MultiStreamCache.store: row must be an int in [0, {n_rows}); got {row!r}")
+        self._plan("store", cache).run(slot, [row])
+        n = int(self.slot_lengths[slot])
+        if isinstance(cache, MultiStreamCache):
+            cache.slot_lengths[row] = n
+            return
+        for layer in cache.layers:
+            if isinstance(layer, StaticSlidingWindowLayerPrealloc):
+                layer.size, layer.cumulative_length = int(min(layer.capacity, n)), n
+            else:
+                layer.seq_len, layer.start = n, True
 
     def slot_view(self, slot: int) -> StaticCachePrealloc:
         """A B = 1 StaticCachePrealloc whose tensors alias row `slot` (ring, conv and recurrent states, position): a prompt

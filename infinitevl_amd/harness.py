@@ -467,6 +467,75 @@ class Sampler:
             raise ValueError(f"Sampler: row must be an int in [0, {self.n_rows}); got {row!r}")
         return row
 
+    _FORK_KEYS = ("temperature", "top_k", "top_p", "seed")
+
+    def _checked(self, who: str, params: dict) -> dict:
+        """The keyword arguments of set() that `params` holds, validated and normalised (no device work)."""
+        p = dict(params)
+        if "temperature" in p:
+            p["temperature"] = temperature = float(p["temperature"])
+            if not (math.isfinite(temperature) and temperature >= 0.0):
+                raise ValueError(f"{who}: temperature must be finite and >= 0; got {temperature}")
+        if "top_k" in p:
+            top_k = p["top_k"]
+            if isinstance(top_k, bool) or not isinstance(top_k, int) or not 0 <= top_k < 2 ** 31:
+                raise ValueError(f"{who}: top_k must be an int >= 0 (0 = off); got {top_k!r}")
+        if "top_p" in p:
+            p["top_p"] = top_p = float(p["top_p"])
+            if not 0.0 < top_p <= 1.0:
+                raise ValueError(f"{who}: top_p must be in (0, 1]; got {top_p}")
+        if "seed" in p:
+            seed = p["seed"]
+            if isinstance(seed, bool) or not isinstance(seed, int) or not -2 ** 63 <= seed < 2 ** 64:
+                raise ValueError(f"{who}: seed must be a 64-bit int; got {seed!r}")
+        if "repetition_penalty" in p:
+            p["repetition_penalty"] = repetition_penalty = float(p["repetition_penalty"])
+            if not (math.isfinite(repetition_penalty) and repetition_penalty > 0.0):
+                raise ValueError(f"{who}: repetition_penalty must be finite and > 0; got {repetition_penalty}")
+            if repetition_penalty != 1.0 and self.seen is None:
+                raise ValueError(f"{who}: a repetition_penalty needs a Sampler built with vocab_size (the bitmap of seen tokens)")
+        if "stop_token_ids" in p:
+            stop = list(p["stop_token_ids"])
+            if len(stop) > self.max_stop or any(isinstance(t, bool) or not isinstance(t, int) or not 0 <= t < 2 ** 63 for t in stop):
+                raise ValueError(f"{who}: stop_token_ids must be at most {self.max_stop} ints >= 0; got {p['stop_token_ids']!r}")
+            p["stop_token_ids"] = stop
+        if "max_new_tokens" in p:
+            max_new_tokens = p["max_new_tokens"]
+            if max_new_tokens is not None and (isinstance(max_new_tokens, bool) or not isinstance(max_new_tokens, int)
+                                               or not 1 <= max_new_tokens < 2 ** 63):
+                raise ValueError(f"{who}: max_new_tokens must be None or an int >= 1; got {max_new_tokens!r}")
+        if "fill_token" in p:
+            fill_token = p["fill_token"]
+            if isinstance(fill_token, bool) or not isinstance(fill_token, int) or not 0 <= fill_token < 2 ** 63:
+                raise ValueError(f"{who}: fill_token must be an int >= 0; got {fill_token!r}")
+        return p
+
+    def _write(self, row: int, p: dict) -> None:
+        """Writes the checked parameters `p` into `row` and leaves the row's state alone, except that a seed restarts its
+        counter.  The host's note of a stop id or a budget follows when `p` holds both."""
+        if "temperature" in p:
+            self.temperature[row] = p["temperature"]
+        if "top_k" in p:
+            self.top_k[row] = p["top_k"]
+        if "top_p" in p:
+            self.top_p[row] = p["top_p"]
+        if "seed" in p:
+            self.seed[row] = p["seed"] - 2 ** 64 if p["seed"] >= 2 ** 63 else p["seed"]
+            self.counter[row] = 0
+        if "repetition_penalty" in p:
+            self.rep_penalty[row] = p["repetition_penalty"]
+        if "stop_token_ids" in p and self.stop_ids is not None:
+            stop = p["stop_token_ids"]
+            self.stop_ids[row] = torch.tensor(stop + [-1] * (self.max_stop - len(stop)), dtype=torch.int64)
+        if "max_new_tokens" in p:
+            self.budget[row] = -1 if p["max_new_tokens"] is None else p["max_new_tokens"]
+        if "fill_token" in p:
+            self.fill[row] = p["fill_token"]
+        if "stop_token_ids" in p and "max_new_tokens" in p:
+            self._ends[row] = bool(p["stop_token_ids"]) or p["max_new_tokens"] is not None
+            if self._ends[row]:
+                self.controlled = True
+
     def set(self, row: int, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0,
             repetition_penalty: float = 1.0, stop_token_ids=(), max_new_tokens: Optional[int] = None, fill_token: int = 0) -> None:
         """Parameters and a fresh stream for `row`: counter 0, and the row's bitmap, n_new, done, history and scores cleared.
@@ -474,37 +543,9 @@ class Sampler:
         built with vocab_size); stop_token_ids: at most max_stop ints >= 0; max_new_tokens: None or an int >= 1; fill_token:
         what the row's token becomes once it is done."""
         row = self._row(row)
-        temperature, top_p, repetition_penalty = float(temperature), float(top_p), float(repetition_penalty)
-        if not (math.isfinite(temperature) and temperature >= 0.0):
-            raise ValueError(f"Sampler.set: temperature must be finite and >= 0; got {temperature}")
-        if isinstance(top_k, bool) or not isinstance(top_k, int) or not 0 <= top_k < 2 ** 31:
-            raise ValueError(f"Sampler.set: top_k must be an int >= 0 (0 = off); got {top_k!r}")
-        if not 0.0 < top_p <= 1.0:
-            raise ValueError(f"Sampler.set: top_p must be in (0, 1]; got {top_p}")
-        if isinstance(seed, bool) or not isinstance(seed, int) or not -2 ** 63 <= seed < 2 ** 64:
-            raise ValueError(f"Sampler.set: seed must be a 64-bit int; got {seed!r}")
-        if not (math.isfinite(repetition_penalty) and repetition_penalty > 0.0):
-            raise ValueError(f"Sampler.set: repetition_penalty must be finite and > 0; got {repetition_penalty}")
-        if repetition_penalty != 1.0 and self.seen is None:
-            raise ValueError("Sampler.set: a repetition_penalty needs a Sampler built with vocab_size (the bitmap of seen tokens)")
-        stop = list(stop_token_ids)
-        if len(stop) > self.max_stop or any(isinstance(t, bool) or not isinstance(t, int) or not 0 <= t < 2 ** 63 for t in stop):
-            raise ValueError(f"Sampler.set: stop_token_ids must be at most {self.max_stop} ints >= 0; got {stop_token_ids!r}")
-        if max_new_tokens is not None and (isinstance(max_new_tokens, bool) or not isinstance(max_new_tokens, int)
-                                           or not 1 <= max_new_tokens < 2 ** 63):
-            raise ValueError(f"Sampler.set: max_new_tokens must be None or an int >= 1; got {max_new_tokens!r}")
-        if isinstance(fill_token, bool) or not isinstance(fill_token, int) or not 0 <= fill_token < 2 ** 63:
-            raise ValueError(f"Sampler.set: fill_token must be an int >= 0; got {fill_token!r}")
-        self.temperature[row] = temperature
-        self.top_k[row] = top_k
-        self.top_p[row] = top_p
-        self.seed[row] = seed - 2 ** 64 if seed >= 2 ** 63 else seed
-        self.counter[row] = 0
-        self.rep_penalty[row] = repetition_penalty
-        if self.stop_ids is not None:
-            self.stop_ids[row] = torch.tensor(stop + [-1] * (self.max_stop - len(stop)), dtype=torch.int64)
-        self.budget[row] = -1 if max_new_tokens is None else max_new_tokens
-        self.fill[row] = fill_token
+        self._write(row, self._checked("Sampler.set", dict(
+            temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, repetition_penalty=repetition_penalty,
+            stop_token_ids=stop_token_ids, max_new_tokens=max_new_tokens, fill_token=fill_token)))
         self.n_new[row] = 0
         self.done[row] = 0
         if self.seen is not None:
@@ -515,9 +556,49 @@ class Sampler:
                      (self.top_logprob, -math.inf), (self.top_hist_ids, -1), (self.top_hist_lp, -math.inf)):
             if t is not None:
                 t[row] = v
-        self._ends[row] = bool(stop) or max_new_tokens is not None
-        if self._ends[row]:
-            self.controlled = True
+
+    # ---- a row's parameters and state as one row of every tensor: fork ---------------------------------------------------
+    def row_tensors(self) -> List[torch.Tensor]:
+        """Every per-row tensor of the table, parameters and state."""
+        return [t for t in (self.temperature, self.top_k, self.top_p, self.seed, self.counter, self.rep_penalty, self.seen,
+                            self.stop_ids, self.budget, self.fill, self.n_new, self.done, self.history, self.logprob,
+                            self.cum_logprob, self.top_ids, self.top_logprob, self.lp_history, self.top_hist_ids,
+                            self.top_hist_lp) if t is not None]
+
+    def _check_fork(self, who: str, src: int, dsts, sampling, keys=None) -> Tuple[int, List[int], List[dict]]:
+        """(src, dsts, one checked override dict per destination) of a fork; no device work."""
+        src = self._row(src)
+        dsts = [self._row(d) for d in dsts]
+        if not dsts or len(set(dsts)) != len(dsts) or src in dsts:
+            raise ValueError(f"{who}: the destination rows must be distinct, at least one and without the source row {src}; "
+                             f"got {dsts}")
+        if sampling is None:
+            sampling = [{}] * len(dsts)
+        sampling = list(sampling)
+        if len(sampling) != len(dsts) or not all(isinstance(d, dict) for d in sampling):
+            raise ValueError(f"{who}: sampling must be one dict per destination row ({len(dsts)}); got {sampling!r}")
+        keys = self._FORK_KEYS if keys is None else keys
+        for d in sampling:
+            if set(d) - set(keys):
+                raise ValueError(f"{who}: sampling may hold {', '.join(keys)}; got {sorted(set(d) - set(keys))}")
+        return src, dsts, [self._checked(who, d) for d in sampling]
+
+    def _forked(self, src: int, dsts, overrides) -> None:
+        """After the rows were copied: the host's notes follow, then the overrides (the state stays as copied)."""
+        for d, p in zip(dsts, overrides):
+            self._ends[d] = self._ends[src]
+            self._write(d, p)
+
+    def fork(self, src: int, dsts, sampling=None) -> None:
+        """Rows `dsts` become copies of row `src`: every per-row tensor, parameters and state (seen bitmap, counters, history,
+        score rings) in one launch, and the host's note of a stop id or budget.  `sampling`: one dict per destination with any
+        of temperature / top_k / top_p / seed, checked as in set() and applied WITHOUT clearing the copied state; a given
+        seed restarts that row's counter at 0 (an independent random stream over the same history)."""
+        src, dsts, overrides = self._check_fork("Sampler.fork", src, dsts, sampling)
+        if self.__dict__.get("_fork_plan") is None:
+            self._fork_plan = ops.RowCopyPlan([(t, t) for t in self.row_tensors()])
+        self._fork_plan.run(src, dsts)
+        self._forked(src, dsts, overrides)
 
     def reset(self, row: int) -> None:
         """Back to greedy, with every control off and the row's state cleared."""
@@ -672,7 +753,10 @@ class GraphedMultiStreamDecode:
     one token (embed -> stack -> argmax -> token buffer, per-slot positions +1).  Streams join with admit() (the prompt runs
     eagerly on the slot's B = 1 view) and leave with release(), both between replays and without a recapture.
     Greedy by default; with a `sampler` (a Sampler of n_slots rows) every slot draws its token with its own temperature /
-    top-k / top-p and its own random stream in one ops.sample_tokens launch (a slot left at temperature 0 stays greedy)."""
+    top-k / top-p and its own random stream in one ops.sample_tokens launch (a slot left at temperature 0 stays greedy).
+    A slot's whole state is one row of every tensor, so a stream also branches: fork() copies a live slot into others in one
+    launch, load() brings in the state of an external stream cache, extend() feeds a live slot more prompt tokens, and
+    admit_n() prefills a prompt once for several independently sampled answers -- all between replays, never a recapture."""
 
     PREFILL_CHUNK = 4096
 
@@ -749,19 +833,177 @@ class GraphedMultiStreamDecode:
             self.sampler.mark(slot, prompt_ids.to(inputs_embeds.device))
         self.cache.admit(slot)
         self._live.add(slot)
+        lg = self._prefill(slot, inputs_embeds, position_ids)
+        self.admit_logits = lg                          # [1,1,vocab]: what the latest admission's first token was taken from
+        self._draw(slot, lg)
+        self.position_ids[:, slot].fill_(int(position_ids.max()) + 1)        # the next M-RoPE text position
+        return self.token[slot]
+
+    def _prefill(self, slot: int, inputs_embeds: torch.Tensor, position_ids: torch.Tensor) -> torch.Tensor:
+        """Runs prompt tokens through the stack on the slot's B = 1 view, in calls of PREFILL_CHUNK; the last call's logits."""
         view = self.cache.slot_view(slot)
+        T = inputs_embeds.shape[1]
         lg = None
         for a in range(0, T, self.PREFILL_CHUNK):
             b = min(T, a + self.PREFILL_CHUNK)
             _, lg = self.model(inputs_embeds=inputs_embeds[:, a:b], position_ids=position_ids[:, :, a:b],
                                past_key_values=view, logits_to_keep=1)
-        self.admit_logits = lg                          # [1,1,vocab]: what the latest admission's first token was taken from
+        return lg
+
+    def _draw(self, slot: int, lg: torch.Tensor) -> None:
+        """token[slot] from the logits lg [1,1,vocab], in the slot's own sampler row."""
         if self.sampler is None:
             self.token[slot].copy_(lg[0, -1].argmax(-1, keepdim=True))
         else:
             self.sampler.sample(lg[:, -1], self.token[slot:slot + 1], row=slot)
-        self.position_ids[:, slot].fill_(int(position_ids.max()) + 1)        # the next M-RoPE text position
+
+    def _check_prompt(self, who: str, inputs_embeds, position_ids, prompt_ids) -> int:
+        if prompt_ids is not None and self.sampler is None:
+            raise ValueError(f"{who}: prompt_ids need a GraphedMultiStreamDecode built with a sampler")
+        if inputs_embeds.dim() != 3 or inputs_embeds.shape[0] != 1 or inputs_embeds.shape[1] < 1:
+            raise ValueError(f"{who}: inputs_embeds must be [1,T,hidden]; got {tuple(inputs_embeds.shape)}")
+        T = inputs_embeds.shape[1]
+        if position_ids is not None and tuple(position_ids.shape) != (3, 1, T):
+            raise ValueError(f"{who}: position_ids must be [3,1,{T}]; got {tuple(position_ids.shape)}")
+        return T
+
+    def _slots(self, who: str, slots) -> List[int]:
+        slots = list(slots)
+        if not slots or len(set(slots)) != len(slots) or \
+                any(isinstance(s, bool) or not isinstance(s, int) or not 0 <= s < self.S for s in slots):
+            raise ValueError(f"{who}: slots must be distinct ints in [0, {self.S}), at least one; got {slots!r}")
+        return slots
+
+    def _row_plan(self) -> "ops.RowCopyPlan":
+        """ONE plan over everything a slot owns here: the cache's rows, its token, its three M-RoPE positions and the sampler's
+        rows.  Built at the first fork and kept (the tensors never move)."""
+        if self.__dict__.get("_fork_plan") is None:
+            ts = self.cache.row_tensors() + [self.token] + [self.position_ids[i] for i in range(3)]
+            if self.sampler is not None:
+                ts += self.sampler.row_tensors()
+            self._fork_plan = ops.RowCopyPlan([(t, t) for t in ts])
+        return self._fork_plan
+
+    def _fork_rows(self, src: int, dsts: List[int]) -> None:
+        self._row_plan().run(src, dsts)
+        for d in dsts:
+            self.cache.slot_lengths[d] = self.cache.slot_lengths[src]
+            self._live.add(d)
+
+    @torch.no_grad()
+    def fork(self, src: int, dsts, sampling=None) -> None:
+        """Slots `dsts` become copies of the live slot `src` -- cache rows, pending token, M-RoPE positions and sampler rows in
+        one launch -- and live: the branch of the reference's streaming demo (demo:357-398) on the serving path.  `sampling`:
+        one dict per destination as in Sampler.fork (temperature / top_k / top_p / seed; the copied state is kept, a seed
+        starts an independent random stream).  In-place writes only, between replays: never a recapture."""
+        src = self._slots("fork", [src])[0]
+        dsts = self._slots("fork", dsts)
+        if src in dsts:
+            raise ValueError(f"fork: the destination slots {dsts} contain the source slot {src}")
+        if src not in self._live:
+            raise ValueError(f"fork: slot {src} holds no stream (admit or load it first)")
+        if sampling is not None and self.sampler is None:
+            raise ValueError("fork: sampling parameters need a GraphedMultiStreamDecode built with a sampler")
+        overrides = None
+        if self.sampler is not None:
+            _, _, overrides = self.sampler._check_fork("fork", src, dsts, sampling)
+        self._fork_rows(src, dsts)
+        if self.sampler is not None:
+            self.sampler._forked(src, dsts, overrides)
+
+    @torch.no_grad()
+    def extend(self, slot: int, inputs_embeds: torch.Tensor, position_ids: Optional[torch.Tensor] = None,
+               prompt_ids: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Continue the live slot `slot` with more prompt tokens inputs_embeds [1,T,hidden] -- a question, the next video
+        frame -- on its B = 1 view.  position_ids [3,1,T]; default: each of the slot's three positions counts on from
+        position_ids[:, slot].  The slot's next token is drawn from the last logits (in the sampler's launch, after
+        `prompt_ids` were marked as seen) and REPLACES the pending one, which was never fed to the model.  admit_logits is set."""
+        slot = self._slots("extend", [slot])[0]
+        if slot not in self._live:
+            raise ValueError(f"extend: slot {slot} holds no stream (admit or load it first)")
+        T = self._check_prompt("extend", inputs_embeds, position_ids, prompt_ids)
+        if position_ids is None:
+            position_ids = self.position_ids[:, slot:slot + 1] + torch.arange(T, device=self.position_ids.device, dtype=torch.int64)
+        if prompt_ids is not None:
+            self.sampler.mark(slot, prompt_ids.to(inputs_embeds.device))
+        lg = self._prefill(slot, inputs_embeds, position_ids)
+        self.admit_logits = lg
+        self._draw(slot, lg)
+        self.position_ids[:, slot].copy_(position_ids.max() + 1)
         return self.token[slot]
+
+    @torch.no_grad()
+    def admit_n(self, slots, inputs_embeds: torch.Tensor, position_ids: Optional[torch.Tensor] = None,
+                sampling=None, prompt_ids: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Several answers to one prompt (num_return_sequences of the reference's api/chat.py:164): the prompt is prefilled
+        ONCE, into slots[0]; its cache and sampler rows are forked to slots[1:] before any token is drawn; then every slot
+        draws its own first token from the same logits, in its own sampler row.  `sampling`: one dict of Sampler.set
+        keyword arguments per slot (e.g. one seed each); every slot ends up as admit(slot, ..., sampling=that dict,
+        prompt_ids=prompt_ids) would leave it.  Returns token[slots]."""
+        slots = self._slots("admit_n", slots)
+        if sampling is not None and self.sampler is None:
+            raise ValueError("admit_n: sampling parameters need a GraphedMultiStreamDecode built with a sampler")
+        T = self._check_prompt("admit_n", inputs_embeds, position_ids, prompt_ids)
+        if position_ids is None:
+            position_ids = torch.arange(T, device=inputs_embeds.device, dtype=torch.int64)[None, None, :].expand(3, 1, T)
+        checked = None
+        if sampling is not None:
+            sampling = list(sampling)
+            if len(sampling) != len(slots) or not all(isinstance(d, dict) for d in sampling):
+                raise ValueError(f"admit_n: sampling must be one dict per slot ({len(slots)}); got {sampling!r}")
+            names = ("temperature", "top_k", "top_p", "seed", "repetition_penalty", "stop_token_ids", "max_new_tokens", "fill_token")
+            for d in sampling:
+                if set(d) - set(names):
+                    raise TypeError(f"admit_n: unknown sampling arguments {sorted(set(d) - set(names))}")
+            defaults = dict(temperature=0.0, top_k=0, top_p=1.0, seed=0, repetition_penalty=1.0, stop_token_ids=(),
+                            max_new_tokens=None, fill_token=0)
+            checked = [self.sampler._checked("admit_n", {**defaults, **d}) for d in sampling]
+        first, rest = slots[0], slots[1:]
+        if sampling is not None:
+            self.sampler.set(first, **sampling[0])
+        if prompt_ids is not None:
+            self.sampler.mark(first, prompt_ids.to(inputs_embeds.device))
+        self.cache.admit(first)
+        self._live.add(first)
+        lg = self._prefill(first, inputs_embeds, position_ids)
+        self.admit_logits = lg
+        self.position_ids[:, first].fill_(int(position_ids.max()) + 1)
+        if rest:
+            self._fork_rows(first, rest)                # the marked bitmap and the fresh state travel with the row
+            if self.sampler is not None:
+                for i, d in enumerate(rest):
+                    self.sampler._ends[d] = self.sampler._ends[first]
+                    if checked is not None:
+                        self.sampler._write(d, checked[i + 1])
+        for s in slots:
+            self._draw(s, lg)
+        return self.token[slots]
+
+    @torch.no_grad()
+    def load(self, slots, cache: StaticCachePrealloc, row: int = 0, next_position: Optional[int] = None, sampling=None) -> None:
+        """The demo's branch (demo:363-365) on the serving path: the state of row `row` of an external cache -- the B = 1
+        StaticCachePrealloc of a running video stream -- goes into `slots` in one launch, and they become live.  The source is
+        only read, so questions never pollute the video's history.  Each slot's three M-RoPE positions are set to
+        `next_position` (default: the source's length); `sampling`: one dict of Sampler.set keyword arguments per slot, applied
+        as in admit.  No token is pending afterwards: extend(slot, question) follows."""
+        slots = self._slots("load", slots)
+        if sampling is not None:
+            if self.sampler is None:
+                raise ValueError("load: sampling parameters need a GraphedMultiStreamDecode built with a sampler")
+            sampling = list(sampling)
+            if len(sampling) != len(slots) or not all(isinstance(d, dict) for d in sampling):
+                raise ValueError(f"load: sampling must be one dict per slot ({len(slots)}); got {sampling!r}")
+        if next_position is not None and (isinstance(next_position, bool) or not isinstance(next_position, int) or next_position < 0):
+            raise ValueError(f"load: next_position must be None or an int >= 0; got {next_position!r}")
+        self.cache.load(slots, cache, row)
+        if next_position is None:
+            next_position = self.cache.slot_lengths[slots[0]]
+        for i, s in enumerate(slots):
+            if sampling is not None:
+                self.sampler.set(s, **sampling[i])
+            self.token[s].zero_()
+            self.position_ids[:, s].fill_(next_position)
+            self._live.add(s)
 
     def release(self, slot: int) -> None:
         """End the stream in `slot`: its state is zeroed (the slot keeps computing on zeros until the next admit)."""

@@ -1332,3 +1332,106 @@ def mark_tokens(seen_row: torch.Tensor, ids: torch.Tensor, vocab_size: int) -> N
     ids = ids.reshape(-1).contiguous()
     _lib.check(_lib.load().ivl_token_mark_fwd(_p(seen_row), vocab_size, _p(ids) if ids.numel() else None, ids.numel(),
                                               _stream(seen_row)))
+
+
+# ---------------------------------------------------------------------------------------------
+# row fork: one row of many tensors to other rows, one launch
+# ---------------------------------------------------------------------------------------------
+def _byte_extent(t: torch.Tensor) -> Tuple[int, int]:
+    """[first, past-the-last) byte addresses a tensor's elements can occupy."""
+    span = sum((n - 1) * s for n, s in zip(t.shape, t.stride())) + 1
+    return t.data_ptr(), t.data_ptr() + span * t.element_size()
+
+
+class RowCopyPlan:
+    """`pairs`: a list of (src, dst) tensors with the row on dim 0.  run(src_row, dst_rows) copies row `src_row` of every src to
+    the rows `dst_rows` of its dst, all pairs in ONE launch (ivl_rows_copy_fwd) on the current stream: each source byte is read
+    once for all destinations.  The device table is built here, once; run() allocates and copies nothing, so it may be captured
+    and is valid between replays of a captured graph.  The plan keeps the tensors alive.
+
+    Of a pair: same dtype, same shape after dim 0, every row contiguous (any row stride for src; the rows of dst must not
+    overlap each other), one device for the whole plan, at most 63 rows on either side, and src and dst are either the same
+    storage and view (rows move inside one tensor) or do not overlap at all."""
+
+    MAX_ROWS = 63
+    PIECE_BYTES = 16384          # RC_CHUNK of csrc/rows_copy.hip: the work list of the table's sixth column is cut this way
+
+    def __init__(self, pairs):
+        pairs = list(pairs)
+        if not pairs:
+            raise ValueError("RowCopyPlan: no pairs")
+        rows, first_piece, device = [], 0, None
+        self.same = []
+        for i, pair in enumerate(pairs):
+            if not (isinstance(pair, (tuple, list)) and len(pair) == 2 and all(torch.is_tensor(t) for t in pair)):
+                raise ValueError(f"RowCopyPlan: pair {i} must be (src_tensor, dst_tensor)")
+            src, dst = pair
+            if src.dim() < 1 or dst.dim() < 1 or src.shape[0] < 1 or dst.shape[0] < 1:
+                raise ValueError(f"RowCopyPlan: pair {i}: both tensors need at least one row on dim 0; got {tuple(src.shape)} "
+                                 f"and {tuple(dst.shape)}")
+            if src.dtype != dst.dtype:
+                raise ValueError(f"RowCopyPlan: pair {i}: dtypes differ ({src.dtype} and {dst.dtype})")
+            if tuple(src.shape[1:]) != tuple(dst.shape[1:]):
+                raise ValueError(f"RowCopyPlan: pair {i}: shapes after dim 0 differ ({tuple(src.shape)} and {tuple(dst.shape)})")
+            if not (src[0].is_contiguous() and dst[0].is_contiguous()):
+                raise ValueError(f"RowCopyPlan: pair {i}: every row must be contiguous (strides {src.stride()} and {dst.stride()})")
+            if src.device != dst.device or (device is not None and src.device != device):
+                raise ValueError(f"RowCopyPlan: pair {i}: all tensors must be on one device ({src.device}, {dst.device}"
+                                 + (f"; the plan's: {device})" if device is not None else ")"))
+            device = src.device
+            if src.shape[0] > self.MAX_ROWS or dst.shape[0] > self.MAX_ROWS:
+                raise ValueError(f"RowCopyPlan: pair {i}: at most {self.MAX_ROWS} rows per tensor; got {src.shape[0]} and "
+                                 f"{dst.shape[0]}")
+            row_bytes = src[0].numel() * src.element_size()
+            if row_bytes < 1:
+                raise ValueError(f"RowCopyPlan: pair {i}: empty rows ({tuple(src.shape)})")
+            if dst.shape[0] > 1 and dst.stride(0) * dst.element_size() < row_bytes:
+                raise ValueError(f"RowCopyPlan: pair {i}: the rows of the destination overlap each other (row stride "
+                                 f"{dst.stride(0)} elements, {row_bytes} bytes per row)")
+            same = (src.data_ptr() == dst.data_ptr() and tuple(src.shape) == tuple(dst.shape) and src.stride() == dst.stride())
+            if not same:
+                (a0, a1), (b0, b1) = _byte_extent(src), _byte_extent(dst)
+                if a0 < b1 and b0 < a1:
+                    raise ValueError(f"RowCopyPlan: pair {i}: source and destination overlap partially (they must be the same "
+                                     "storage and view, or not overlap at all)")
+            self.same.append(same)
+            rows.append([src.data_ptr(), dst.data_ptr(), src.stride(0) * src.element_size(), dst.stride(0) * dst.element_size(),
+                         row_bytes, first_piece])
+            first_piece += (row_bytes + self.PIECE_BYTES - 1) // self.PIECE_BYTES
+        self.pairs = pairs
+        self.device = device
+        self.n_entries = len(rows)
+        self.n_pieces = first_piece
+        self.max_row_bytes = max(r[4] for r in rows)
+        self.row_bytes = sum(r[4] for r in rows)                    # bytes of one row over all pairs
+        self.n_src_rows = min(p[0].shape[0] for p in pairs)
+        self.n_dst_rows = min(p[1].shape[0] for p in pairs)
+        self.any_same = any(self.same)
+        self.table = torch.tensor(rows, dtype=torch.int64).to(device) if device.type == "cuda" else None
+
+    def check_rows(self, src_row, dst_rows) -> int:
+        """Validates the rows of a run (no device work) and returns the destination mask."""
+        if isinstance(src_row, bool) or not isinstance(src_row, int) or not 0 <= src_row < self.n_src_rows:
+            raise ValueError(f"RowCopyPlan.run: src_row must be an int in [0, {self.n_src_rows}); got {src_row!r}")
+        dst_rows = list(dst_rows)
+        if not dst_rows:
+            raise ValueError("RowCopyPlan.run: dst_rows is empty")
+        mask = 0
+        for r in dst_rows:
+            if isinstance(r, bool) or not isinstance(r, int) or not 0 <= r < self.n_dst_rows:
+                raise ValueError(f"RowCopyPlan.run: dst_rows must be ints in [0, {self.n_dst_rows}); got {r!r}")
+            if mask >> r & 1:
+                raise ValueError(f"RowCopyPlan.run: row {r} is repeated in dst_rows {dst_rows}")
+            mask |= 1 << r
+        if self.any_same and mask >> src_row & 1:
+            raise ValueError(f"RowCopyPlan.run: dst_rows {dst_rows} contains src_row {src_row} of a plan that copies inside "
+                             "one tensor")
+        return mask
+
+    def run(self, src_row: int, dst_rows) -> None:
+        mask = self.check_rows(src_row, dst_rows)
+        if self.table is None:
+            raise ValueError("RowCopyPlan.run: the tensors are on the CPU; the row copy runs only on an MI355X (ROCm) device "
+                             "(there is deliberately no CPU fallback)")
+        _lib.check(_lib.load().ivl_rows_copy_fwd(_p(self.table), self.n_entries, self.max_row_bytes, src_row, mask,
+                                                 _stream(self.table)))

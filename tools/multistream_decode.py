@@ -31,6 +31,16 @@ the model's vocabulary, greedy and sampled, with and without the scores.  No bar
 2 % of A the sampling launch is granted as a whole.
 
     python tools/multistream_decode.py --logprobs --slots 1,4 [--out profiles/logprobs_decode.json]
+
+--fork measures the slot fork (MultiStreamCache.fork: ops.RowCopyPlan, one ivl_rows_copy_fwd launch): a 4-slot cache with slot 0
+admitted with 4096 + 700 tokens; per round, interleaved: the fork to 1 and to 3 slots, the per-tensor `t[d].copy_(t[0])` loop
+doing the same copies (127 and 381 launches), one torch copy of a single buffer of the same number of bytes, and the
+re-admission of the prompt that a fork saves.  Each figure is the median over --rounds of device events around one call (the
+fork, the loop, the re-admission) or around --steps calls queued back to back (the single-buffer copy, and the fork again: one
+call between two events on an empty stream also counts the host's way to the launch).  The rates and the share of the 6.3 TB/s
+copy rate are taken from the queued calls and count bytes read once and written once per destination.
+
+    python tools/multistream_decode.py --fork [--out profiles/slot_fork.json]
 """
 import argparse
 import json
@@ -53,6 +63,7 @@ def main():
     ap.add_argument("--sampling", action="store_true", help="time the sampled step against the greedy one (see above)")
     ap.add_argument("--generation", action="store_true", help="time the step with the generation controls (see above)")
     ap.add_argument("--logprobs", action="store_true", help="time the step with logprobs and top-5 alternatives (see above)")
+    ap.add_argument("--fork", action="store_true", help="time the slot fork against the copy_ loop and a re-admission (see above)")
     args = ap.parse_args()
     import torch
     from infinitevl_amd.cache import MultiStreamCache
@@ -85,6 +96,8 @@ def main():
         return generation_legs(args, torch, model, cfg, prompts, dev)
     if args.logprobs:
         return logprobs_legs(args, torch, model, cfg, prompts, dev)
+    if args.fork:
+        return fork_legs(args, torch, model, cfg, prompts, dev)
 
     # reference: one stream on the existing B = 1 graphed decode step
     c1 = model.allocate_inference_cache(1)
@@ -381,6 +394,79 @@ def logprobs_legs(args, torch, model, cfg, prompts, dev):
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
             f.write(line + "\n")
+
+
+COPY_ROOF_TBS = 6.3
+
+
+def fork_legs(args, torch, model, cfg, prompts, dev):
+    from infinitevl_amd.cache import MultiStreamCache
+    from infinitevl_amd.harness import GraphedMultiStreamDecode
+    stream = torch.cuda.current_stream()
+    cache = MultiStreamCache(config=cfg, n_slots=4, device=dev, dtype=torch.bfloat16)
+    dec = GraphedMultiStreamDecode(model, cache)
+    x = prompts[1]                                              # 4096 + 700 tokens
+    dec.admit(0, x)
+    rows = cache.row_tensors()
+    row_bytes = sum(t[0].numel() * t.element_size() for t in rows)
+    flat = {n: (torch.empty(n * row_bytes, dtype=torch.uint8, device=dev), torch.empty(n * row_bytes, dtype=torch.uint8, device=dev))
+            for n in (1, 3)}
+
+    def timed(fn, n=1):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        for _ in range(n):
+            fn()
+        e1.record(stream)
+        e1.synchronize()
+        return e0.elapsed_time(e1) / n
+
+    def loop(dsts):
+        for t in rows:
+            for d in dsts:
+                t[d].copy_(t[0])
+
+    dsts = {1: [1], 3: [1, 2, 3]}
+    legs = {}
+    for n in (1, 3):
+        legs[f"fork_to{n}"] = (lambda n=n: cache.fork(0, dsts[n]), 1)
+        legs[f"fork_to{n}_queued"] = (lambda n=n: cache.fork(0, dsts[n]), args.steps)
+        legs[f"copy_loop_to{n}"] = (lambda n=n: loop(dsts[n]), 1)
+        legs[f"single_buffer_copy_{n}x"] = (lambda n=n: flat[n][1].copy_(flat[n][0]), args.steps)
+    legs["readmit"] = (lambda: dec.admit(0, x), 1)
+    for fn, _ in legs.values():                                 # warm-up: plans, kernels, allocator
+        fn()
+    torch.cuda.synchronize()
+    times = {k: [] for k in legs}
+    for _ in range(args.rounds):
+        for k, (fn, n) in legs.items():
+            times[k].append(timed(fn, n))
+    for d in (1, 2, 3):                                         # the measured forks were real ones
+        assert all(torch.equal(t[0], t[d]) for t in rows)
+    med = {k: statistics.median(v) for k, v in times.items()}
+    res = {"tool": "multistream_decode --fork", "layers": cfg.num_hidden_layers, "window": 4096, "prompt_tokens": x.shape[1],
+           "rounds": args.rounds, "row_tensors": len(rows), "row_bytes": row_bytes, "copy_roof_TBs": COPY_ROOF_TBS,
+           "readmit_ms": round(med["readmit"], 3), "readmit_spread_ms": [round(min(times["readmit"]), 3), round(max(times["readmit"]), 3)]}
+    for n in (1, 3):
+        # a single call between two events also counts the host's way to the launch (the stream is empty by then); --steps
+        # calls queued back to back, like the single-buffer copy, count the kernel: the rates are taken from those
+        f1, l, c = med[f"fork_to{n}"], med[f"copy_loop_to{n}"], med[f"single_buffer_copy_{n}x"]
+        f = med[f"fork_to{n}_queued"]
+        moved = row_bytes * (1 + n)                             # read once, written n times
+        res[f"to{n}"] = {"fork_us": round(1000 * f1, 1), "fork_queued_us": round(1000 * f, 1), "fork_spread_us": [round(1000 * min(times[f"fork_to{n}"]), 1),
+                                                                           round(1000 * max(times[f"fork_to{n}"]), 1)],
+                         "copy_loop_us": round(1000 * l, 1), "copy_loop_launches": len(rows) * n, "loop_over_fork": round(l / f1, 2),
+                         "single_buffer_copy_us": round(1000 * c, 1), "single_buffer_bytes_moved": 2 * n * row_bytes,
+                         "fork_TBs": round(moved / (f * 1e-3) / 1e12, 3), "fork_share_of_roof": round(moved / (f * 1e-3) / 1e12 / COPY_ROOF_TBS, 3),
+                         "single_buffer_TBs": round(2 * n * row_bytes / (c * 1e-3) / 1e12, 3),
+                         "fork_share_of_single_buffer_rate": round((moved / f) / (2 * n * row_bytes / c), 3),
+                         "readmit_over_fork": round(med["readmit"] / f1, 1)}
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f_:
+            f_.write(line + "\n")
 
 
 if __name__ == "__main__":
