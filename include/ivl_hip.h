@@ -542,6 +542,100 @@ IVL_API int ivl_token_mark_fwd(uint32_t* seen_row, int64_t V, const int64_t* ids
 IVL_API int ivl_rows_copy_fwd(const int64_t* table, int n_entries, int64_t max_row_bytes, int src_row, int64_t dst_mask,
                               void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Row gather: the rows [row0, row0 + n_rows) of every tensor of a table are permuted / duplicated IN PLACE by a map that lives on
+ * the device -- the reorder of a beam search step (HF generate's cache reorder by beam_idx; num_beams of the reference's
+ * hparams/generating_args.py), whose parents are decided inside the captured step.
+ * table: the format of ivl_rows_copy_fwd, every entry with src_base == dst_base and equal strides (only dst_base, the destination
+ *   stride, row_bytes and first_piece are read).
+ * parent: DEVICE int32 [n_rows].  For every entry and every d < n_rows at once:
+ *     row row0 + d  <-  the OLD row row0 + parent[d].
+ *   Rows with parent[d] == d are neither loaded nor stored (an identity map moves no byte); a parent[d] outside [0, n_rows) counts
+ *   as d: nothing outside the group is ever read or written.
+ * No shadow copy and no barrier: for its own 16-byte lanes of a piece (and its edge bytes) a thread first loads that lane from
+ *   every row some d != parent[d] names, and only then stores to every such d.  A thread only overwrites bytes it has itself
+ *   already loaded, and one offset of a row belongs to one thread, so cycles ([1,2,3,0]), swaps and fan-out ([0,0,0,0], the fork)
+ *   need no ordering between threads.  16-byte accesses where the row stride is a multiple of 16 (bytes at the unaligned head and
+ *   tail of a piece), single bytes otherwise, in the same load-all-then-store order.  n_rows <= 4: 16384-byte pieces, 4 x 4
+ *   16-byte registers; n_rows 5..8: the piece is walked in two halves, 8 x 2 registers.  No LDS.
+ * 1 <= n_rows <= 8, row0 >= 0, row0 + n_rows <= 63.  No allocation, copy or synchronisation: capturable, and a replay follows the
+ * current contents of `parent`.
+ * IVL_ERR_INVALID_ARG: NULL table or parent, n_entries < 1, max_row_bytes < 1, row0 < 0, n_rows outside 1..8.
+ * IVL_ERR_UNSUPPORTED: row0 + n_rows > 63.
+ * ------------------------------------------------------------------------------------------- */
+IVL_API int ivl_rows_gather_fwd(const int64_t* table, int n_entries, int64_t max_row_bytes, int row0, int n_rows,
+                                const int32_t* parent, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * The scores of ivl_sample_rows_lp_fwd without a token: per row s, steps A (a finished row), B (the repetition penalty on `seen`),
+ * L1 and L3 of that call, and nothing else -- the candidate lists of a beam search step.
+ *   top_ids[s*n_top + j] / top_logprobs[s*n_top + j]: the min(n_top, V) tokens with the largest x', ties to the lowest index,
+ *   by (x' descending, index ascending), with lp of L1; entries j >= V are -1 / -inf.  Bit-equal to what ivl_sample_rows_lp_fwd
+ *   writes to its top_ids / top_logprobs for the same (logits, rep_penalty, seen), whatever that call's sampling parameters.
+ *   A row with done[s] != 0 gets ids -1 and lp -inf (L5).  done may be NULL (no row is finished).
+ * Nothing is committed: no token, counter, n_kept or prob; `seen` and `done` are const and no n_new, history or ring exists here.
+ * IVL_ERR_INVALID_ARG: NULL logits / top_ids / top_logprobs, S < 1, V < 1, ld < V, rep_penalty without seen, seen with
+ * seen_ld*32 < V, n_top outside 1..20.  IVL_ERR_UNSUPPORTED: V >= 2^23.
+ * ------------------------------------------------------------------------------------------- */
+IVL_API int ivl_sample_rows_score_fwd(const void* logits, int64_t ld, int S, int V,
+                                      const float* rep_penalty, const uint32_t* seen, int64_t seen_ld, const int32_t* done,
+                                      int n_top, int64_t* top_ids, float* top_logprobs, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Beam search (num_beams / length_penalty / early_stopping of HF generate, which the reference sets through
+ * hparams/generating_args.py and train/sft/workflow.py:94): G groups of B beams; group g owns the rows (slots) [g B, (g+1) B) of
+ * every per-slot tensor.  One step = score (ivl_sample_rows_score_fwd with n_top = K) -> ivl_beam_select_fwd ->
+ * ivl_rows_gather_fwd(parent + g B) over everything a slot owns -> ivl_beam_commit_fwd.  Both calls here process group g only if
+ * bit g of the HOST group_mask is set and beam_done[g] == 0; a skipped group has nothing read or written.
+ * Per slot: top_ids int64 / top_logprobs fp32 [S,K]; cum_logprob float64 [S], the beam's sum of log-probabilities, -inf = no beam
+ *   here; n_new int64 [S]; history int64 [S,L] (L = hist_ld; token i of a beam at history[s*L + i % L]); seen uint32 [S,seen_ld];
+ *   token int64 at token + s*token_stride.
+ * Per group: length_penalty float64 [G]; early_stopping int32 [G]; budget int64 [G] (< 0: none); stop_ids int64 [G,n_stop]
+ *   (entries < 0 unused); beam_done int32 [G] (0 running, 1 finished by the stopping rule, 2 by its budget); n_hyp int32 [G];
+ *   hyp_score / hyp_sum float64 [G,B]; hyp_len int64 [G,B]; hyp_tokens int64 [G,B,L]; parent int32, next_token int64 and next_score
+ *   float64 [G,B].  The first n_hyp entries of the hyp_* tables are the group's finished hypotheses in insertion order.
+ *
+ * ivl_beam_select_fwd (HF BeamSearchScorer.process, BeamHypotheses.add / is_done):
+ *   S1 candidates: (beam b, rank j < K) with top_ids >= 0, of beams with a finite cum_logprob; score = cum_logprob[b] + (double)lp,
+ *      one float64 add of an fp32 value.
+ *   S2 they are ranked by (score descending, beam ascending, rank ascending) -- a total order -- and the first K are walked:
+ *        a stop id at walk position >= B is skipped;
+ *        a stop id at walk position < B becomes a hypothesis: tokens = the parent's history (as it is BEFORE the gather) followed
+ *          by the stop token, length n = n_new[parent] + 1, sum = the candidate's score, score = hyp(sum, n);
+ *        any other candidate becomes the next beam d = 0, 1, ...: parent[d] = b, next_token[d], next_score[d]; the walk ends when
+ *          B beams are taken.  Beams left over (fewer candidates than needed) get parent d, token 0, score -inf.
+ *   S3 hyp(sum, n) = sum / n^length_penalty in float64: length_penalty == 1 is a plain IEEE division, == 0 the sum itself, anything
+ *      else sum / pow((double)n, length_penalty).
+ *   S4 insert: if n_hyp < B or score > the worst score; over B, the worst (the lowest score, the earliest inserted of equals) leaves
+ *      and the later entries move up.
+ *   S5 done, evaluated after the walk: never while n_hyp < B; with early_stopping once n_hyp == B; else when
+ *      worst >= hyp(the best candidate's score, n_new + 1).  A done group gets beam_done = 1 and parent = the identity; it is
+ *      not committed, so its tokens and scores freeze while its slots go on computing.
+ * ivl_beam_commit_fwd, after the gather, for every beam d of a running group: token = next_token[d]; its bit of `seen` is set (seen
+ *   may be NULL); history[n_new % L] = token; n_new += 1; cum_logprob = next_score[d].  Then, if budget[g] >= 0 and n_new has
+ *   reached it: every beam with a finite sum becomes a hypothesis in beam order by S4 (tokens = its history, n = n_new; HF
+ *   finalize), beam_done = 2 and parent = the identity.  Whichever way a group ends, its parent row is the identity from then
+ *   on: the gather of a later step, which runs for every group, moves none of its rows.
+ * K = max(2, 1 + n_stop) B makes the first K candidates hold B that are no stop id; the host computes it and refuses K > 20.
+ * Deliberate differences from HF: the scores are those of the penalised bf16 row x' (L1; HF penalises log-softmax values; with
+ * r == 1 the two agree); the tie order of S2 (torch.topk leaves it open); a hypothesis includes its stop token;
+ * early_stopping = "never" and beam sampling are not offered.
+ * IVL_ERR_INVALID_ARG (before anything is launched): G outside 1..63, B outside 1..8, K outside 1..20, n_stop outside 0..16 or
+ * without stop_ids, hist_ld < 1, token_stride < 1, seen with seen_ld*32 < V, a NULL pointer other than seen and stop_ids.
+ * ------------------------------------------------------------------------------------------- */
+IVL_API int ivl_beam_select_fwd(int G, int B, int K, int64_t group_mask,
+                                const int64_t* top_ids, const float* top_logprobs, const double* cum_logprob,
+                                const int64_t* n_new, const int64_t* history, int64_t hist_ld,
+                                const int64_t* stop_ids, int n_stop, const double* length_penalty, const int32_t* early_stopping,
+                                int32_t* beam_done, int32_t* n_hyp, double* hyp_score, double* hyp_sum, int64_t* hyp_len,
+                                int64_t* hyp_tokens, int32_t* parent, int64_t* next_token, double* next_score, void* stream);
+IVL_API int ivl_beam_commit_fwd(int G, int B, int64_t group_mask,
+                                const int64_t* next_token, const double* next_score, int64_t* token, int64_t token_stride,
+                                uint32_t* seen, int64_t seen_ld, int64_t V, int64_t* history, int64_t hist_ld, int64_t* n_new,
+                                double* cum_logprob, const int64_t* budget, const double* length_penalty,
+                                int32_t* beam_done, int32_t* n_hyp, double* hyp_score, double* hyp_sum, int64_t* hyp_len,
+                                int64_t* hyp_tokens, int32_t* parent, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -35,6 +35,10 @@
 //   L3  collect: every key > t_N (fewer than n_top), and per wave (a wave owns a contiguous index range) its first ties == t_N
 // then wave 0 takes the ties in wave = index order, ranks the <= 20 survivors against each other (no sort of the row) and leaves
 // the ordered list in LDS for the lane that writes the token: it scores the token, logs and adds it up beside smp_after.
+//
+// Score only (ivl_sample_rows_score_fwd; a fourth form, the three others are compiled without a line of it): a beam search step
+// needs every beam's candidate list and no token.  The form takes the greedy row's path -- pass 1 for the maximum, L1-L3 -- writes
+// the list and stops: no token, counter, seen bit, n_new, done, history or ring; its sampling parameters are not even read.
 #include "ivl_common.h"
 
 #include <type_traits>
@@ -490,10 +494,14 @@ __device__ __forceinline__ void smp_lp_after(const SmpLp& lp, const SmpCtl& c, l
   if (lp.cum) lp.cum[s] += (double)v;
 }
 
-// CTL: no type (the control-free form, with the parameter list it always had), SmpCtl, or SmpCtl and SmpLp
+// CTL: no type (the control-free form, with the parameter list it always had), SmpCtl, SmpCtl and SmpLp, or these two and
+// SmpScore (the score-only form of ivl_sample_rows_score_fwd: steps A, B, L1 and L3, nothing committed)
+struct SmpScore {};
 __device__ __forceinline__ const SmpCtl& smp_first(const SmpCtl& c) { return c; }
 __device__ __forceinline__ const SmpCtl& smp_first(const SmpCtl& c, const SmpLp&) { return c; }
+__device__ __forceinline__ const SmpCtl& smp_first(const SmpCtl& c, const SmpLp&, const SmpScore&) { return c; }
 __device__ __forceinline__ const SmpLp& smp_second(const SmpCtl&, const SmpLp& l) { return l; }
+__device__ __forceinline__ const SmpLp& smp_second(const SmpCtl&, const SmpLp& l, const SmpScore&) { return l; }
 
 template <typename... CTL>
 __global__ void __launch_bounds__(SMP_THREADS)
@@ -501,16 +509,18 @@ sample_rows_kernel(const bf16_t* __restrict__ logits, long long ld, int V, const
                    const int* __restrict__ top_k, const float* __restrict__ top_p, const long long* __restrict__ seed,
                    long long* __restrict__ counter, long long* __restrict__ token, long long token_stride,
                    int* __restrict__ n_kept, float* __restrict__ prob, const CTL... ctl_) {
-  constexpr bool kCtl = sizeof...(CTL) >= 1, kLp = sizeof...(CTL) == 2;
+  constexpr bool kCtl = sizeof...(CTL) >= 1, kLp = sizeof...(CTL) >= 2, kScore = sizeof...(CTL) == 3;
   typename std::conditional<kCtl, SmpPen, SmpNoPen>::type pen;
   if constexpr (kCtl) {
     const SmpCtl& ctl = smp_first(ctl_...);
     const long long s = blockIdx.x;
     if (ctl.done && ctl.done[s] != 0) {                 // a finished row: the fill token, nothing else read or written
-      if (threadIdx.x == 0) {
-        token[s * token_stride] = ctl.fill ? ctl.fill[s] : 0ll;
-        if (n_kept) n_kept[s] = 0;
-        if (prob) prob[s] = 0.f;
+      if constexpr (!kScore) {
+        if (threadIdx.x == 0) {
+          token[s * token_stride] = ctl.fill ? ctl.fill[s] : 0ll;
+          if (n_kept) n_kept[s] = 0;
+          if (prob) prob[s] = 0.f;
+        }
       }
       if constexpr (kLp) {                              // no score: logprob 0, no alternatives, no ring or sum write
         const SmpLp& lp = smp_second(ctl_...);
@@ -547,10 +557,10 @@ sample_rows_kernel(const bf16_t* __restrict__ logits, long long ld, int V, const
   r.V = V;
   r.nt = ((long long)r.off + V + 7) >> 3;
 
-  const float tau = temperature[s];
+  float tau = 0.f, p = 1.f;                             // the score-only form has no sampling parameters: it takes the greedy
+  int k = 0;                                            // row's path to the scores and writes no token
+  if constexpr (!kScore) { tau = temperature[s]; k = top_k[s]; p = top_p[s]; }
   const bool greedy = !(tau > 0.f);
-  const int k = top_k[s];
-  const float p = top_p[s];
   const bool use_k = !greedy && k > 0 && k < V;
   const bool use_p = !greedy && p < 1.f;
 
@@ -595,12 +605,14 @@ sample_rows_kernel(const bf16_t* __restrict__ logits, long long ld, int V, const
       lse = smp_lp_phase(r, pen, mkey, smp_key_value(mkey), smp_second(ctl_...).n_top, false, tid, hist, sub, wsum, &sh_bin, &sh_E,
                          &sh_key, lpl);
     if (tid == 0) {
-      token[s * token_stride] = (long long)midx;
-      if (n_kept) n_kept[s] = 1;
-      if (prob) prob[s] = 1.f;
+      if constexpr (!kScore) {
+        token[s * token_stride] = (long long)midx;
+        if (n_kept) n_kept[s] = 1;
+        if (prob) prob[s] = 1.f;
+      }
       if constexpr (kLp)
         smp_lp_after(smp_second(ctl_...), smp_first(ctl_...), s, V, mkey, mkey, smp_key_value(mkey), lse, lpl);
-      if constexpr (kCtl) smp_after(smp_first(ctl_...), s, (long long)midx);
+      if constexpr (kCtl && !kScore) smp_after(smp_first(ctl_...), s, (long long)midx);
     }
     return;
   }
@@ -914,6 +926,37 @@ extern "C" int ivl_sample_rows_lp_fwd(const void* logits, int64_t ld, int S, int
   hipLaunchKernelGGL((sample_rows_kernel<SmpCtl, SmpLp>), dim3((unsigned)S), dim3(SMP_THREADS), 0, (hipStream_t)stream,
                      (const bf16_t*)logits, (long long)ld, V, temperature, (const int*)top_k, top_p, (const long long*)seed,
                      (long long*)counter, (long long*)token, (long long)token_stride, (int*)n_kept, prob, c, l);
+  return check_launch(fn);
+}
+
+extern "C" int ivl_sample_rows_score_fwd(const void* logits, int64_t ld, int S, int V, const float* rep_penalty, const uint32_t* seen,
+                                         int64_t seen_ld, const int32_t* done, int n_top, int64_t* top_ids, float* top_logprobs,
+                                         void* stream) {
+  using namespace ivl;
+  const char* fn = "ivl_sample_rows_score_fwd";
+  IVL_REQUIRE(logits && top_ids && top_logprobs, IVL_ERR_INVALID_ARG, "%s: NULL pointer", fn);
+  IVL_REQUIRE(S >= 1 && V >= 1 && ld >= (int64_t)V, IVL_ERR_INVALID_ARG, "%s: S=%d V=%d ld=%lld", fn, S, V, (long long)ld);
+  IVL_REQUIRE(V < (1 << 23), IVL_ERR_UNSUPPORTED, "%s: V=%d (the Q40 sums are sized for V < 2^23)", fn, V);
+  IVL_REQUIRE(!rep_penalty || seen, IVL_ERR_INVALID_ARG, "%s: rep_penalty needs seen", fn);
+  IVL_REQUIRE(!seen || seen_ld * 32 >= (int64_t)V, IVL_ERR_INVALID_ARG, "%s: seen_ld=%lld words hold fewer than V=%d bits", fn,
+              (long long)seen_ld, V);
+  IVL_REQUIRE(n_top >= 1 && n_top <= SMP_TOP_MAX, IVL_ERR_INVALID_ARG, "%s: n_top=%d outside 1..%d", fn, n_top, SMP_TOP_MAX);
+  // the kernel of this form reads `seen` and `done` and writes neither (smp_after is not part of it)
+  const SmpCtl c = sample_rows_ctl(rep_penalty, const_cast<uint32_t*>(seen), seen_ld, nullptr, 0, nullptr, nullptr, nullptr,
+                                   const_cast<int32_t*>(done), nullptr, 0);
+  SmpLp l;
+  l.logprob = nullptr;
+  l.n_top = n_top;
+  l.top_ids = (long long*)top_ids;
+  l.top_lp = top_logprobs;
+  l.cum = nullptr;
+  l.lp_hist = nullptr;
+  l.top_hist_ids = nullptr;
+  l.top_hist_lp = nullptr;
+  hipLaunchKernelGGL((sample_rows_kernel<SmpCtl, SmpLp, SmpScore>), dim3((unsigned)S), dim3(SMP_THREADS), 0, (hipStream_t)stream,
+                     (const bf16_t*)logits, (long long)ld, V, (const float*)nullptr, (const int*)nullptr, (const float*)nullptr,
+                     (const long long*)nullptr, (long long*)nullptr, (long long*)nullptr, 0ll, (int*)nullptr, (float*)nullptr, c, l,
+                     SmpScore{});
   return check_launch(fn);
 }
 

@@ -1048,6 +1048,185 @@ class GraphedMultiStreamDecode:
         return {s: self.sampler.tokens(s) for s in sorted(self._live)}
 
 
+class GraphedBeamDecode(GraphedMultiStreamDecode):
+    """Beam search on the serving path (num_beams / length_penalty / early_stopping of HF generate, which the reference sets in
+    hparams/generating_args.py and train/sft/workflow.py:94): the slots of a MultiStreamCache form G = n_slots / num_beams
+    independent groups of num_beams beams, group g in the slots [g B, (g+1) B).  ONE captured step advances every group:
+    model forward -> score-only launch (ops.score_tokens: every beam's K candidates) -> ops.beam_select (parents, next tokens,
+    finished hypotheses, the done rule) -> one row gather per group by the device-resident parents (ops.RowGatherPlan over
+    everything a slot owns) -> ops.beam_commit.  No host round trip per token, and no recapture when a group is admitted,
+    finishes or is released: length_penalty, early_stopping, stop ids and budgets are device tensors read at replay.
+    ivl_beam_select_fwd in include/ivl_hip.h states the semantics and the differences from HF."""
+
+    def __init__(self, model: InfiniteVLTextStack, cache: MultiStreamCache, num_beams: int, vocab_size: int, history: int,
+                 max_stop: int = 1, warmup: int = 2):
+        if isinstance(num_beams, bool) or not isinstance(num_beams, int) or not 1 <= num_beams <= 8:
+            raise ValueError(f"GraphedBeamDecode: num_beams must be an int in [1, 8]; got {num_beams!r}")
+        if cache.n_slots % num_beams:
+            raise ValueError(f"GraphedBeamDecode: the cache's {cache.n_slots} slots are no multiple of num_beams = {num_beams}")
+        if isinstance(history, bool) or not isinstance(history, int) or history < 1:
+            raise ValueError(f"GraphedBeamDecode: history must be an int >= 1; got {history!r}")
+        if isinstance(max_stop, bool) or not isinstance(max_stop, int) or not 0 <= max_stop <= 16:
+            raise ValueError(f"GraphedBeamDecode: max_stop must be an int in [0, 16]; got {max_stop!r}")
+        K = ops.beam_width(num_beams, max_stop)          # refuses K > 20
+        device = next(model.parameters()).device
+        sampler = Sampler(cache.n_slots, device, vocab_size=vocab_size, max_stop=0, history=history, logprobs=K)
+        sampler.lp_history = sampler.top_hist_ids = sampler.top_hist_lp = None      # a beam keeps tokens, not per-token scores
+        super().__init__(model, cache, warmup=warmup, sampler=sampler)
+        self.B, self.G, self.K, self.L, self.max_stop = num_beams, cache.n_slots // num_beams, K, history, max_stop
+        G, B, L = self.G, self.B, self.L
+        z = lambda dt, *shape: torch.zeros(*shape, dtype=dt, device=device)
+        self.beam = dict(length_penalty=torch.ones(G, dtype=torch.float64, device=device), early_stopping=z(torch.int32, G),
+                         budget=torch.full((G,), -1, dtype=torch.int64, device=device),
+                         beam_done=torch.ones(G, dtype=torch.int32, device=device),       # an idle group counts as finished
+                         n_hyp=z(torch.int32, G), hyp_score=z(torch.float64, G, B), hyp_sum=z(torch.float64, G, B),
+                         hyp_len=z(torch.int64, G, B), hyp_tokens=z(torch.int64, G, B, L),
+                         parent=torch.arange(B, dtype=torch.int32, device=device).repeat(G, 1),
+                         next_token=z(torch.int64, G, B), next_score=z(torch.float64, G, B))
+        self.stop_ids = torch.full((G, max_stop), -1, dtype=torch.int64, device=device) if max_stop else None
+        self._groups = set()                             # groups between admit and release
+        self._gather_plan = None
+
+    def _group(self, who: str, group) -> int:
+        if isinstance(group, bool) or not isinstance(group, int) or not 0 <= group < self.G:
+            raise ValueError(f"{who}: group must be an int in [0, {self.G}); got {group!r}")
+        return group
+
+    def _plan(self) -> "ops.RowGatherPlan":
+        """ONE plan over everything a slot owns: the cache's rows, its token, its M-RoPE positions, the sampler's rows."""
+        if self._gather_plan is None:
+            ts = self.cache.row_tensors() + [self.token] + [self.position_ids[i] for i in range(3)] + self.sampler.row_tensors()
+            self._gather_plan = ops.RowGatherPlan(ts)
+        return self._gather_plan
+
+    def _beam_tail(self, logits: torch.Tensor, row0: int, groups) -> None:
+        """Score, select, gather and commit of `groups` from the logits [n,V] of the rows row0 .. row0 + n."""
+        smp, n = self.sampler, logits.shape[0]
+        sl = slice(row0, row0 + n)
+        mask = sum(1 << g for g in groups)
+        ops.score_tokens(logits, smp.top_ids[sl], smp.top_logprob[sl], rep_penalty=smp.rep_penalty[sl], seen=smp.seen[sl],
+                         done=smp.done[sl])
+        ops.beam_select(self.B, mask, smp.top_ids, smp.top_logprob, smp.cum_logprob, smp.n_new, smp.history, self.stop_ids,
+                        self.beam)
+        plan = self._plan()
+        for g in groups:
+            plan.run(g * self.B, self.B, self.beam["parent"][g])
+        ops.beam_commit(self.B, mask, self.token, smp.seen, smp.vocab_size, smp.history, smp.n_new, smp.cum_logprob, self.beam)
+
+    def _run(self):
+        _, lg = self.model(input_ids=self.token, position_ids=self.position_ids, past_key_values=self.cache,
+                           logits_to_keep=1)
+        self._beam_tail(lg[:, -1], 0, range(self.G))
+        self.position_ids.add_(1)
+        return lg
+
+    def capture(self) -> None:
+        """As GraphedMultiStreamDecode.capture; the beam tensors are saved and restored around the warm-up too."""
+        saved = {k: t.clone() for k, t in self.beam.items()}
+        super().capture()
+        for k, t in self.beam.items():
+            t.copy_(saved[k])
+
+    @torch.no_grad()
+    def admit(self, group: int, inputs_embeds: torch.Tensor, position_ids: Optional[torch.Tensor] = None,
+              prompt_ids: Optional[torch.Tensor] = None, *, max_new_tokens: int, stop_token_ids=(),
+              repetition_penalty: float = 1.0, length_penalty: float = 1.0, early_stopping: bool = False) -> torch.Tensor:
+        """Start a beam search in `group` with a prompt inputs_embeds [1,T,hidden].  The prompt is prefilled ONCE, into the
+        group's first slot; then score, select, gather and commit run on this group alone: the beams' sums start as
+        [0, -inf, ...], so every parent is beam 0 and the gather is the fork.  Returns the group's first tokens token[g B:(g+1) B].
+        max_new_tokens <= history (a hypothesis is read from the token history, which must not wrap); stop_token_ids: at most
+        max_stop ints >= 0."""
+        g = self._group("admit", group)
+        T = self._check_prompt("admit", inputs_embeds, position_ids, prompt_ids)
+        stop = list(stop_token_ids)
+        if any(isinstance(t, bool) or not isinstance(t, int) or not 0 <= t < 2 ** 63 for t in stop):
+            raise ValueError(f"admit: stop_token_ids must be ints >= 0; got {stop_token_ids!r}")
+        if ops.beam_width(self.B, len(stop)) > self.K:
+            raise ValueError(f"admit: {len(stop)} stop ids need K = {ops.beam_width(self.B, len(stop))} candidates per beam; this "
+                             f"decoder was built with max_stop = {self.max_stop} (K = {self.K})")
+        if isinstance(max_new_tokens, bool) or not isinstance(max_new_tokens, int) or max_new_tokens < 1:
+            raise ValueError(f"admit: max_new_tokens must be an int >= 1; got {max_new_tokens!r}")
+        if max_new_tokens > self.L:
+            raise ValueError(f"admit: max_new_tokens = {max_new_tokens} exceeds the token history of {self.L} a hypothesis is "
+                             "read from")
+        length_penalty = float(length_penalty)
+        if not math.isfinite(length_penalty):
+            raise ValueError(f"admit: length_penalty must be finite; got {length_penalty}")
+        if not isinstance(early_stopping, bool):
+            raise ValueError(f"admit: early_stopping must be a bool (\"never\" is not offered); got {early_stopping!r}")
+        checked = self.sampler._checked("admit", dict(repetition_penalty=repetition_penalty))
+        if position_ids is None:
+            position_ids = torch.arange(T, device=inputs_embeds.device, dtype=torch.int64)[None, None, :].expand(3, 1, T)
+        B, s0 = self.B, g * self.B
+        for s in range(s0, s0 + B):
+            self.sampler.set(s, repetition_penalty=checked["repetition_penalty"])
+        if B > 1:
+            self.sampler.cum_logprob[s0 + 1:s0 + B] = -math.inf
+        if prompt_ids is not None:
+            self.sampler.mark(s0, prompt_ids.to(inputs_embeds.device))
+        bm = self.beam
+        bm["length_penalty"][g] = length_penalty
+        bm["early_stopping"][g] = int(early_stopping)
+        bm["budget"][g] = max_new_tokens
+        bm["beam_done"][g] = 0
+        bm["n_hyp"][g] = 0
+        if self.stop_ids is not None:
+            self.stop_ids[g] = torch.tensor(stop + [-1] * (self.max_stop - len(stop)), dtype=torch.int64)
+        self.cache.admit(s0)
+        lg = self._prefill(s0, inputs_embeds, position_ids)
+        self.admit_logits = lg
+        self.position_ids[:, s0].fill_(int(position_ids.max()) + 1)
+        self._beam_tail(lg[:, -1], s0, [g])
+        for s in range(s0, s0 + B):
+            self.cache.slot_lengths[s] = self.cache.slot_lengths[s0]
+            self._live.add(s)
+        self._groups.add(g)
+        return self.token[s0:s0 + B]
+
+    def release(self, group: int) -> None:
+        """End the search in `group`: its slots are zeroed and the group counts as finished until the next admit."""
+        g = self._group("release", group)
+        for s in range(g * self.B, (g + 1) * self.B):
+            super().release(s)
+        self.beam["beam_done"][g] = 1
+        self.beam["n_hyp"][g] = 0
+        self.beam["parent"][g] = torch.arange(self.B, dtype=torch.int32)
+        self._groups.discard(g)
+
+    def result(self, group: int, n: int = 1):
+        """The n best finished hypotheses of `group` as (tokens int64 [len] on the host, score, sum of log-probabilities), best
+        first, ties to the earlier insertion."""
+        g = self._group("result", group)
+        if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+            raise ValueError(f"result: n must be an int >= 1; got {n!r}")
+        nh = int(self.beam["n_hyp"][g].item())
+        score, sums = self.beam["hyp_score"][g].cpu(), self.beam["hyp_sum"][g].cpu()
+        lens, toks = self.beam["hyp_len"][g].cpu(), self.beam["hyp_tokens"][g].cpu()
+        order = sorted(range(nh), key=lambda i: (-float(score[i]), i))[:n]
+        return [(toks[i, :int(lens[i])].clone(), float(score[i]), float(sums[i])) for i in order]
+
+    def run_until_done(self, max_steps: int, poll_every: int = 16):
+        """Replay up to `max_steps` steps; beam_done is polled every `poll_every` steps and the loop ends once every admitted
+        group is finished.  Returns {group: result(group)} of the admitted groups."""
+        if max_steps < 0 or poll_every < 1:
+            raise ValueError(f"run_until_done: max_steps >= 0 and poll_every >= 1; got {max_steps}, {poll_every}")
+        groups = sorted(self._groups)
+        steps = 0
+        while steps < max_steps:
+            if groups and bool((self.beam["beam_done"].cpu()[groups] != 0).all()):
+                break
+            n = min(poll_every, max_steps - steps)
+            for _ in range(n):
+                self.step()
+            steps += n
+        return {g: self.result(g) for g in groups}
+
+    def _per_slot(self, *a, **k):
+        raise ValueError("GraphedBeamDecode: a slot of a beam group is not a stream of its own (admit / release a group)")
+
+    fork = extend = admit_n = load = _per_slot
+
+
 @torch.no_grad()
 def greedy_decode(model: InfiniteVLTextStack, cache: StaticCachePrealloc, first_token: torch.Tensor, steps: int,
                   start_pos: Optional[int] = None) -> torch.Tensor:

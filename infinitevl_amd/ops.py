@@ -1435,3 +1435,198 @@ class RowCopyPlan:
                              "(there is deliberately no CPU fallback)")
         _lib.check(_lib.load().ivl_rows_copy_fwd(_p(self.table), self.n_entries, self.max_row_bytes, src_row, mask,
                                                  _stream(self.table)))
+
+
+# ---------------------------------------------------------------------------------------------
+# beam search: score without a token, row gather by a device map, select / commit
+# ---------------------------------------------------------------------------------------------
+def score_tokens(logits: torch.Tensor, top_ids: torch.Tensor, top_logprobs: torch.Tensor, *,
+                 rep_penalty: Optional[torch.Tensor] = None, seen: Optional[torch.Tensor] = None,
+                 done: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The N most likely tokens per row of lm_head logits [S,V] or [S,1,V] (bf16) with their log-probabilities, and NOTHING
+    else: no token, no counter, no seen bit (ivl_sample_rows_score_fwd; the candidate lists of a beam search step).  top_ids
+    int64 / top_logprobs fp32 [S,N], 1 <= N <= 20, written in place and returned: bit-equal to what sample_tokens(...,
+    top_ids=, top_logprobs=) writes for the same (logits, rep_penalty, seen).  rep_penalty [S] fp32 with seen [S,W] int32
+    (read only); done [S] int32 (read only): a row with done != 0 gets ids -1 and -inf."""
+    if logits.dim() == 3 and logits.shape[1] == 1:
+        logits = logits[:, 0]
+    if logits.dim() != 2 or logits.dtype != torch.bfloat16 or logits.shape[0] < 1 or logits.shape[1] < 1:
+        raise ValueError(f"score_tokens: logits must be bf16 [S,V] or [S,1,V]; got {logits.dtype} {tuple(logits.shape)}")
+    S, V = logits.shape
+    if logits.stride(1) != 1 or (S > 1 and logits.stride(0) < V):
+        raise ValueError(f"score_tokens: the last dim of logits must be contiguous and the rows apart (strides {logits.stride()})")
+    n_top = top_ids.shape[1] if top_ids.dim() == 2 else -1
+    if not 1 <= n_top <= 20:
+        raise ValueError(f"score_tokens: top_ids must be [{S},N] with 1 <= N <= 20; got {tuple(top_ids.shape)}")
+    for name, t, dt in (("top_ids", top_ids, torch.int64), ("top_logprobs", top_logprobs, torch.float32)):
+        if t.dtype != dt or tuple(t.shape) != (S, n_top) or not t.is_contiguous():
+            raise ValueError(f"score_tokens: {name} must be a contiguous {dt} tensor of [{S},{n_top}]; got {t.dtype} {tuple(t.shape)}")
+    for name, t, dt in (("rep_penalty", rep_penalty, torch.float32), ("done", done, torch.int32)):
+        if t is not None and (t.dtype != dt or tuple(t.shape) != (S,) or not t.is_contiguous()):
+            raise ValueError(f"score_tokens: {name} must be a contiguous {dt} tensor of [{S}]; got {t.dtype} {tuple(t.shape)}")
+    if seen is not None:
+        if seen.dtype != torch.int32 or seen.dim() != 2 or seen.shape[0] != S or seen.stride(1) != 1 or \
+                (S > 1 and seen.stride(0) < seen.shape[1]):
+            raise ValueError(f"score_tokens: seen must be an int32 tensor of [{S},W] with contiguous rows; got {seen.dtype} "
+                             f"{tuple(seen.shape)} strides {seen.stride()}")
+        if seen.shape[1] * 32 < V:
+            raise ValueError(f"score_tokens: seen has {seen.shape[1]} words per row for V = {V} (needs {(V + 31) // 32})")
+    if rep_penalty is not None and seen is None:
+        raise ValueError("score_tokens: rep_penalty needs the seen bitmap")
+    _need_gpu(logits, top_ids, top_logprobs, rep_penalty, seen, done)
+    _lib.check(_lib.load().ivl_sample_rows_score_fwd(
+        _p(logits), logits.stride(0) if S > 1 else V, S, V, _p(rep_penalty), _p(seen),
+        0 if seen is None else (seen.stride(0) if S > 1 else seen.shape[1]), _p(done), n_top, _p(top_ids), _p(top_logprobs),
+        _stream(logits)))
+    return top_ids, top_logprobs
+
+
+class RowGatherPlan:
+    """`tensors`: tensors with the row on dim 0.  run(row0, n_rows, parent) makes row row0 + d of every tensor the OLD row
+    row0 + parent[d], for all d < n_rows at once, in place and in ONE launch (ivl_rows_gather_fwd).  `parent` is a DEVICE
+    int32 [n_rows]: the launch may be captured, and a replay follows the tensor's current contents.  Rows with parent[d] == d
+    are not touched; a parent[d] outside [0, n_rows) counts as d.  The tensors are validated as RowCopyPlan validates a
+    (t, t) pair, and the device table is that plan's."""
+
+    MAX_GROUP = 8
+
+    def __init__(self, tensors):
+        tensors = list(tensors)
+        if not tensors or not all(torch.is_tensor(t) for t in tensors):
+            raise ValueError("RowGatherPlan: needs a non-empty list of tensors")
+        self.plan = RowCopyPlan([(t, t) for t in tensors])
+        self.n_rows = self.plan.n_dst_rows
+
+    def check(self, row0, n_rows, parent: torch.Tensor) -> None:
+        for name, v in (("row0", row0), ("n_rows", n_rows)):
+            if isinstance(v, bool) or not isinstance(v, int):
+                raise ValueError(f"RowGatherPlan.run: {name} must be an int; got {v!r}")
+        if not 1 <= n_rows <= self.MAX_GROUP:
+            raise ValueError(f"RowGatherPlan.run: n_rows must be in [1, {self.MAX_GROUP}]; got {n_rows}")
+        if row0 < 0 or row0 + n_rows > self.n_rows:
+            raise ValueError(f"RowGatherPlan.run: rows [{row0}, {row0 + n_rows}) are outside the plan's {self.n_rows} rows")
+        if not torch.is_tensor(parent) or parent.dtype != torch.int32 or tuple(parent.shape) != (n_rows,) or \
+                not parent.is_contiguous():
+            raise ValueError(f"RowGatherPlan.run: parent must be a contiguous int32 tensor of [{n_rows}]; got "
+                             + (f"{parent.dtype} {tuple(parent.shape)}" if torch.is_tensor(parent) else repr(parent)))
+        if parent.device != self.plan.device:
+            raise ValueError(f"RowGatherPlan.run: parent is on {parent.device}, the plan's tensors on {self.plan.device}")
+
+    def run(self, row0: int, n_rows: int, parent: torch.Tensor) -> None:
+        self.check(row0, n_rows, parent)
+        if self.plan.table is None:
+            raise ValueError("RowGatherPlan.run: the tensors are on the CPU; the row gather runs only on an MI355X (ROCm) device "
+                             "(there is deliberately no CPU fallback)")
+        _lib.check(_lib.load().ivl_rows_gather_fwd(_p(self.plan.table), self.plan.n_entries, self.plan.max_row_bytes, row0, n_rows,
+                                                   _p(parent), _stream(self.plan.table)))
+
+
+def beam_width(num_beams: int, n_stop: int) -> int:
+    """K of a beam step: the candidates every beam offers and the length of the walk, max(2, 1 + n_stop) * num_beams -- enough
+    for the first K ranked candidates to hold num_beams that are no stop id.  ValueError above 20 (the scoring launch's limit)."""
+    if isinstance(num_beams, bool) or not isinstance(num_beams, int) or not 1 <= num_beams <= 8:
+        raise ValueError(f"beam_width: num_beams must be an int in [1, 8]; got {num_beams!r}")
+    if isinstance(n_stop, bool) or not isinstance(n_stop, int) or n_stop < 0:
+        raise ValueError(f"beam_width: n_stop must be an int >= 0; got {n_stop!r}")
+    K = max(2, 1 + n_stop) * num_beams
+    if K > 20:
+        raise ValueError(f"beam_width: K = max(2, 1 + {n_stop}) * {num_beams} = {K} candidates per beam exceed the 20 the scoring "
+                         "launch returns (fewer beams or fewer stop ids)")
+    return K
+
+
+_BEAM_GROUP = (("length_penalty", torch.float64, 1), ("early_stopping", torch.int32, 1), ("budget", torch.int64, 1),
+               ("beam_done", torch.int32, 1), ("n_hyp", torch.int32, 1), ("hyp_score", torch.float64, 2),
+               ("hyp_sum", torch.float64, 2), ("hyp_len", torch.int64, 2), ("hyp_tokens", torch.int64, 3),
+               ("parent", torch.int32, 2), ("next_token", torch.int64, 2), ("next_score", torch.float64, 2))
+
+
+def _beam_check(who: str, G: int, B: int, L: int, group_mask, st: dict, names) -> int:
+    if isinstance(group_mask, bool) or not isinstance(group_mask, int) or not 0 <= group_mask < (1 << G):
+        raise ValueError(f"{who}: group_mask must be an int in [0, 2^{G}); got {group_mask!r}")
+    for name, dt, nd in _BEAM_GROUP:
+        if name not in names:
+            continue
+        t = st[name]
+        want = (G,) if nd == 1 else ((G, B) if nd == 2 else (G, B, L))
+        if not torch.is_tensor(t) or t.dtype != dt or tuple(t.shape) != want or not t.is_contiguous():
+            raise ValueError(f"{who}: {name} must be a contiguous {dt} tensor of {list(want)}; got "
+                             + (f"{t.dtype} {tuple(t.shape)}" if torch.is_tensor(t) else repr(t)))
+    return group_mask
+
+
+def beam_select(B: int, group_mask: int, top_ids: torch.Tensor, top_logprobs: torch.Tensor, cum_logprob: torch.Tensor,
+                n_new: torch.Tensor, history: torch.Tensor, stop_ids: Optional[torch.Tensor], state: dict) -> None:
+    """The decision of a beam search step for the groups of `group_mask` (ivl_beam_select_fwd states the semantics; HF
+    BeamSearchScorer.process): from every slot's candidate list top_ids / top_logprobs [S,K] and sum cum_logprob [S] float64 to
+    state["parent"] / ["next_token"] / ["next_score"] [G,B], the hypothesis tables state["n_hyp"], ["hyp_score"], ["hyp_sum"],
+    ["hyp_len"], ["hyp_tokens"] and state["beam_done"].  S = G * B slots; n_new [S] int64, history [S,L] int64, stop_ids [G,n]
+    int64 or None; state also holds length_penalty [G] float64 and early_stopping [G] int32."""
+    if isinstance(B, bool) or not isinstance(B, int) or not 1 <= B <= 8:
+        raise ValueError(f"beam_select: B must be an int in [1, 8]; got {B!r}")
+    if top_ids.dim() != 2 or top_ids.shape[0] % B or not 1 <= top_ids.shape[1] <= 20:
+        raise ValueError(f"beam_select: top_ids must be [G*{B},K] with 1 <= K <= 20; got {tuple(top_ids.shape)}")
+    S, K = top_ids.shape
+    G = S // B
+    if history.dim() != 2:
+        raise ValueError(f"beam_select: history must be [{S},L]; got {tuple(history.shape)}")
+    L = history.shape[1]
+    for name, t, dt, want in (("top_ids", top_ids, torch.int64, (S, K)), ("top_logprobs", top_logprobs, torch.float32, (S, K)),
+                              ("cum_logprob", cum_logprob, torch.float64, (S,)), ("n_new", n_new, torch.int64, (S,)),
+                              ("history", history, torch.int64, (S, L))):
+        if t.dtype != dt or tuple(t.shape) != want or not t.is_contiguous() or L < 1:
+            raise ValueError(f"beam_select: {name} must be a contiguous {dt} tensor of {list(want)}; got {t.dtype} {tuple(t.shape)}")
+    n_stop = 0
+    if stop_ids is not None:
+        if stop_ids.dtype != torch.int64 or stop_ids.dim() != 2 or stop_ids.shape[0] != G or not 1 <= stop_ids.shape[1] <= 16 or \
+                not stop_ids.is_contiguous():
+            raise ValueError(f"beam_select: stop_ids must be a contiguous int64 [{G},n], 1 <= n <= 16; got {stop_ids.dtype} "
+                             f"{tuple(stop_ids.shape)}")
+        n_stop = stop_ids.shape[1]
+    names = ("length_penalty", "early_stopping", "beam_done", "n_hyp", "hyp_score", "hyp_sum", "hyp_len", "hyp_tokens", "parent",
+             "next_token", "next_score")
+    mask = _beam_check("beam_select", G, B, L, group_mask, state, names)
+    _need_gpu(top_ids, top_logprobs, cum_logprob, n_new, history, stop_ids, *(state[k] for k in names))
+    _lib.check(_lib.load().ivl_beam_select_fwd(
+        G, B, K, mask, _p(top_ids), _p(top_logprobs), _p(cum_logprob), _p(n_new), _p(history), L, _p(stop_ids), n_stop,
+        _p(state["length_penalty"]), _p(state["early_stopping"]), _p(state["beam_done"]), _p(state["n_hyp"]),
+        _p(state["hyp_score"]), _p(state["hyp_sum"]), _p(state["hyp_len"]), _p(state["hyp_tokens"]), _p(state["parent"]),
+        _p(state["next_token"]), _p(state["next_score"]), _stream(top_ids)))
+
+
+def beam_commit(B: int, group_mask: int, token: torch.Tensor, seen: Optional[torch.Tensor], vocab_size: Optional[int],
+                history: torch.Tensor, n_new: torch.Tensor, cum_logprob: torch.Tensor, state: dict) -> None:
+    """The bookkeeping of a beam search step after the row gather, for the running groups of `group_mask`
+    (ivl_beam_commit_fwd): token [S] or [S,1] int64 <- state["next_token"], the token's bit of seen [S,W] int32 (or None), its
+    place in history [S,L], n_new += 1, cum_logprob <- state["next_score"]; a group whose n_new reaches state["budget"] files
+    its beams as hypotheses and ends with beam_done = 2 and state["parent"] = the identity."""
+    if isinstance(B, bool) or not isinstance(B, int) or not 1 <= B <= 8:
+        raise ValueError(f"beam_commit: B must be an int in [1, 8]; got {B!r}")
+    if history.dim() != 2 or history.shape[0] % B or history.shape[1] < 1:
+        raise ValueError(f"beam_commit: history must be [G*{B},L]; got {tuple(history.shape)}")
+    S, L = history.shape
+    G = S // B
+    if token.dtype != torch.int64 or tuple(token.shape) not in ((S,), (S, 1)):
+        raise ValueError(f"beam_commit: token must be int64 [{S}] or [{S},1]; got {token.dtype} {tuple(token.shape)}")
+    for name, t, dt, want in (("history", history, torch.int64, (S, L)), ("n_new", n_new, torch.int64, (S,)),
+                              ("cum_logprob", cum_logprob, torch.float64, (S,))):
+        if t.dtype != dt or tuple(t.shape) != want or not t.is_contiguous():
+            raise ValueError(f"beam_commit: {name} must be a contiguous {dt} tensor of {list(want)}; got {t.dtype} {tuple(t.shape)}")
+    V = 0
+    if seen is not None:
+        if isinstance(vocab_size, bool) or not isinstance(vocab_size, int) or vocab_size < 1:
+            raise ValueError(f"beam_commit: seen needs vocab_size, an int >= 1; got {vocab_size!r}")
+        V = vocab_size
+        if seen.dtype != torch.int32 or tuple(seen.shape[:1]) != (S,) or seen.dim() != 2 or not seen.is_contiguous() or \
+                seen.shape[1] * 32 < V:
+            raise ValueError(f"beam_commit: seen must be a contiguous int32 [{S},W] with W * 32 >= {V}; got {seen.dtype} "
+                             f"{tuple(seen.shape)}")
+    names = ("length_penalty", "budget", "beam_done", "n_hyp", "hyp_score", "hyp_sum", "hyp_len", "hyp_tokens", "next_token",
+             "next_score", "parent")
+    mask = _beam_check("beam_commit", G, B, L, group_mask, state, names)
+    _need_gpu(token, seen, history, n_new, cum_logprob, *(state[k] for k in names))
+    _lib.check(_lib.load().ivl_beam_commit_fwd(
+        G, B, mask, _p(state["next_token"]), _p(state["next_score"]), _p(token), token.stride(0) if S > 1 else 1, _p(seen),
+        0 if seen is None else seen.shape[1], V, _p(history), L, _p(n_new), _p(cum_logprob), _p(state["budget"]),
+        _p(state["length_penalty"]), _p(state["beam_done"]), _p(state["n_hyp"]), _p(state["hyp_score"]), _p(state["hyp_sum"]),
+        _p(state["hyp_len"]), _p(state["hyp_tokens"]), _p(state["parent"]), _stream(history)))

@@ -41,6 +41,14 @@ call between two events on an empty stream also counts the host's way to the lau
 copy rate are taken from the queued calls and count bytes read once and written once per destination.
 
     python tools/multistream_decode.py --fork [--out profiles/slot_fork.json]
+
+--beam: the cost of beam search (harness.GraphedBeamDecode) in the captured step, by the A B A C protocol above: the 4-slot
+greedy step (A), the step of one group of 4 beams (B) and of two groups of 2 beams (C), median of --rounds rounds of --steps
+replays, with the 2 % allowance of A beside them; then the row gather alone (ops.RowGatherPlan over everything a slot owns, at
+the model's real row table, 4 rows) for three maps -- the identity, a 4-cycle and all-from-0 -- against the per-tensor
+index_select + copy_ loop on the same map, single calls and calls queued back to back.
+
+    python tools/multistream_decode.py --beam [--out profiles/beam_decode.json]
 """
 import argparse
 import json
@@ -64,6 +72,7 @@ def main():
     ap.add_argument("--generation", action="store_true", help="time the step with the generation controls (see above)")
     ap.add_argument("--logprobs", action="store_true", help="time the step with logprobs and top-5 alternatives (see above)")
     ap.add_argument("--fork", action="store_true", help="time the slot fork against the copy_ loop and a re-admission (see above)")
+    ap.add_argument("--beam", action="store_true", help="time the beam search step and the row gather (see above)")
     args = ap.parse_args()
     import torch
     from infinitevl_amd.cache import MultiStreamCache
@@ -98,6 +107,8 @@ def main():
         return logprobs_legs(args, torch, model, cfg, prompts, dev)
     if args.fork:
         return fork_legs(args, torch, model, cfg, prompts, dev)
+    if args.beam:
+        return beam_legs(args, torch, model, cfg, prompts, dev)
 
     # reference: one stream on the existing B = 1 graphed decode step
     c1 = model.allocate_inference_cache(1)
@@ -467,6 +478,92 @@ def fork_legs(args, torch, model, cfg, prompts, dev):
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f_:
             f_.write(line + "\n")
+
+
+def beam_legs(args, torch, model, cfg, prompts, dev):
+    from infinitevl_amd.cache import MultiStreamCache
+    from infinitevl_amd.harness import GraphedBeamDecode, GraphedMultiStreamDecode
+    stream = torch.cuda.current_stream()
+    L = 2048                                                    # the budget: no leg finishes while it is timed
+
+    def timed(fn, n, warm=4):
+        for _ in range(warm):
+            fn()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        for _ in range(n):
+            fn()
+        e1.record(stream)
+        e1.synchronize()
+        return e0.elapsed_time(e1) / n
+
+    legs, decs = {}, {}
+    cache = MultiStreamCache(config=cfg, n_slots=4, device=dev, dtype=torch.bfloat16)
+    dec = GraphedMultiStreamDecode(model, cache)
+    for s in range(4):
+        dec.admit(s, prompts[s])
+    dec.capture()
+    legs["greedy"] = dec.step
+    for name, B in (("beam4", 4), ("beam2x2", 2)):
+        cache = MultiStreamCache(config=cfg, n_slots=4, device=dev, dtype=torch.bfloat16)
+        bd = GraphedBeamDecode(model, cache, B, cfg.vocab_size, L, max_stop=0)
+        for g in range(4 // B):
+            bd.admit(g, prompts[g], max_new_tokens=L)
+        bd.capture()
+        legs[name], decs[name] = bd.step, bd
+    times = {k: [] for k in legs}
+    for _ in range(args.rounds):                                # A B A C
+        for name in ("beam4", "beam2x2"):
+            times["greedy"].append(timed(legs["greedy"], args.steps))
+            times[name].append(timed(legs[name], args.steps))
+    a = statistics.median(times["greedy"])
+    res = {"tool": "multistream_decode --beam", "layers": cfg.num_hidden_layers, "window": 4096, "steps": args.steps,
+           "rounds": args.rounds, "history": L, "bar": "A + 2 %",
+           "greedy_ms_per_step": round(a, 4), "greedy_spread_ms": [round(min(times["greedy"]), 4), round(max(times["greedy"]), 4)],
+           "allowance_us": round(1000 * 0.02 * a, 1)}
+    for name in ("beam4", "beam2x2"):
+        t = statistics.median(times[name])
+        bd = decs[name]
+        assert int(bd.beam["beam_done"].sum()) == 0 and int(bd.sampler.n_new.min()) > args.rounds * args.steps      # it did run
+        res[name] = {"ms_per_step": round(t, 4), "vs_greedy": round(t / a, 4), "delta_us": round(1000 * (t - a), 1),
+                     "spread_ms": [round(min(times[name]), 4), round(max(times[name]), 4)], "within_greedy_bar": bool(t <= 1.02 * a),
+                     "K": bd.K, "launches_after_forward": 3 + bd.G}
+        print(f"{name}: A {a:.4f} ms, beam {t:.4f} ms", file=sys.stderr, flush=True)
+    # the gather alone, on everything a slot owns in the 4-beam decoder
+    bd = decs["beam4"]
+    plan = bd._plan()
+    rows = [p[0] for p in plan.plan.pairs]
+    row_bytes = plan.plan.row_bytes
+    maps = {"identity": [0, 1, 2, 3], "cycle4": [1, 2, 3, 0], "all_from_0": [0, 0, 0, 0]}
+    gat = {"row_tensors": len(rows), "row_bytes": row_bytes, "copy_roof_TBs": COPY_ROOF_TBS}
+    for name, m in maps.items():
+        par = torch.tensor(m, dtype=torch.int32, device=dev)
+        idx = par.to(torch.int64)
+
+        def loop():
+            for t in rows:
+                t.copy_(t.index_select(0, idx))
+
+        one, many, lp = [], [], []
+        for _ in range(args.rounds):
+            one.append(timed(lambda: plan.run(0, 4, par), 1, warm=1))
+            many.append(timed(lambda: plan.run(0, 4, par), args.steps, warm=1))
+            lp.append(timed(loop, 1, warm=1))
+        moved = sum(1 for d, p in enumerate(m) if p != d)       # rows written; the rows read: the distinct parents of those
+        read = len({p for d, p in enumerate(m) if p != d})
+        q = statistics.median(many)
+        gat[name] = {"gather_us": round(1000 * statistics.median(one), 1), "gather_queued_us": round(1000 * q, 1),
+                     "index_select_copy_loop_us": round(1000 * statistics.median(lp), 1), "loop_launches": 2 * len(rows),
+                     "loop_over_gather": round(statistics.median(lp) / statistics.median(one), 2),
+                     "bytes_moved": (moved + read) * row_bytes,
+                     "gather_TBs": round((moved + read) * row_bytes / (q * 1e-3) / 1e12, 3)}
+    res["gather"] = gat
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
 
 
 if __name__ == "__main__":
