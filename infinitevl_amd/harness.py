@@ -10,9 +10,11 @@ stock PyTorch-ROCm (rocBLAS/hipBLASLt GEMMs): callers of the path, kept as-is.
 """
 from __future__ import annotations
 
+import contextlib
+import inspect
 import math
 from dataclasses import dataclass, field, fields
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import torch
 import torch.nn as nn
@@ -329,7 +331,56 @@ def clone_inference_cache(cache: StaticCachePrealloc) -> StaticCachePrealloc:
     return cache.clone()
 
 
-class GraphedStep:
+class _Graphed:
+    """What the graphed classes share: ONE capture recipe, the rule for a recapture, and the single-token step."""
+
+    sampler: Optional["Sampler"] = None                 # (GraphedStep has none)
+    _captured_controlled = False
+
+    def _capture(self, tensors: List[torch.Tensor], scope=None):
+        """Captures one self._run() into self.graph and returns what it returned.  The cache, `tensors` and the sampler's state
+        are cloned first (before the capture begins) and restored last, so neither the `_warmup` runs on a side stream nor
+        the captured run leave a trace; `scope`: a context manager around the warm-up and the capture."""
+        saved_cache, saved = self.cache.clone(), [t.clone() for t in tensors]
+        saved_smp = self.sampler.state() if self.sampler is not None else None
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with scope if scope is not None else contextlib.nullcontext():
+            with torch.cuda.stream(s), torch.no_grad():
+                for _ in range(self._warmup):
+                    self._run()
+            torch.cuda.current_stream().wait_stream(s)
+            self.graph = torch.cuda.CUDAGraph()
+            with torch.no_grad(), torch.cuda.graph(self.graph):
+                out = self._run()
+        self.cache.copy_from(saved_cache)
+        for t, was in zip(tensors, saved):
+            t.copy_(was)
+        if self.sampler is not None:
+            self.sampler.load_state(saved_smp)          # the warm-up and the capture itself made draws
+            self._captured_controlled = self.sampler.controlled
+        return out
+
+    def _stale(self) -> bool:
+        """No graph yet, or one captured before the sampler switched to the controlled launch."""
+        return self.graph is None or (self.sampler is not None and self.sampler.controlled != self._captured_controlled)
+
+    def _run(self):
+        """The T = 1 step: forward of every row's token, its next token, positions + 1."""
+        _, lg = self.model(input_ids=self.token, position_ids=self.position_ids, past_key_values=self.cache,
+                           logits_to_keep=1)
+        self._next_token(lg[:, -1])
+        self.position_ids.add_(1)
+        return lg
+
+    def _next_token(self, logits: torch.Tensor) -> None:
+        if self.sampler is None:
+            self.token.copy_(logits.argmax(-1, keepdim=True))
+        else:
+            self.sampler.sample(logits, self.token)
+
+
+class GraphedStep(_Graphed):
     """One hipGraph-captured forward of fixed length T over static input buffers
     (demo:262-269, 473-489).  The cache carries device-resident counters, so the same graph is valid
     for every step; positions advance inside the graph."""
@@ -358,24 +409,11 @@ class GraphedStep:
         """Warm up on a side stream with a throw-away clone of the cache state (demo:285-315), then
         capture.  The live cache is restored afterwards, so capture has no side effects on it."""
         self.cache.ensure_started()          # a replayed graph always reads the cache tensors
-        saved = self.cache.clone()
-        saved_pos = self.position_ids.clone()
         # the graph owns the flag words of its single-launch GDN calls (ops.gdn_sync_scope): it may be replayed beside eager
         # calls or other graphs without sharing them
         if self._sync is None:
             self._sync = ops.new_gdn_sync_area(self.inputs_embeds.device)
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with ops.gdn_sync_scope(self._sync):
-            with torch.cuda.stream(s), torch.no_grad():
-                for _ in range(self._warmup):
-                    self._run()
-            torch.cuda.current_stream().wait_stream(s)
-            self.graph = torch.cuda.CUDAGraph()
-            with torch.no_grad(), torch.cuda.graph(self.graph):
-                self.hidden, self.logits = self._run()
-        self.cache.copy_from(saved)
-        self.position_ids.copy_(saved_pos)
+        self.hidden, self.logits = self._capture([self.position_ids], ops.gdn_sync_scope(self._sync))
 
     def reset(self) -> None:
         """Start a new sequence on the same graph: cache counters and state tensors back to empty, positions to 0."""
@@ -394,6 +432,53 @@ class GraphedStep:
         self.cache.advance(self.T)
         ops.gdn_sync_check(self.inputs_embeds.device)    # free (a host word): a failed in-launch wait of an EARLIER replay raises here
         return self.hidden, self.logits
+
+
+class _RowField(NamedTuple):
+    """One per-row tensor of a Sampler (Sampler._TABLE)."""
+    name: str                   # the attribute
+    dtype: torch.dtype
+    shape: Tuple[str, ...]      # after the row, as named extents: "words" of the seen bitmap (vocab_size), "max_stop", "history",
+    #                             "top" (logprobs >= 1), "ring" (history, of a sampler with score rings).  The tensor exists when
+    #                             every extent is non-zero
+    init: float                 # of a fresh row, and what set() clears a state tensor to
+    state: bool = False         # a step changes it (state() saves it); else a parameter
+    kw: Optional[str] = None    # the keyword under which ops.sample_tokens takes it; None: positional
+    score: bool = False         # ... and only in a sampler built with logprobs
+
+
+def _stop_ids(who: str, ids, at_most: Optional[int] = None) -> List[int]:
+    """`ids` as a list of ints in [0, 2^63), at most `at_most` of them (None: the caller bounds their number)."""
+    stop = list(ids)
+    if (at_most is not None and len(stop) > at_most) or \
+            any(isinstance(t, bool) or not isinstance(t, int) or not 0 <= t < 2 ** 63 for t in stop):
+        raise ValueError(f"{who}: stop_token_ids must be {'' if at_most is None else f'at most {at_most} '}ints >= 0; got {ids!r}")
+    return stop
+
+
+def _write_stop_ids(table: torch.Tensor, row: int, stop: List[int]) -> None:
+    """`stop` into row `row` of an int64 [n, max_stop] table, padded with -1 (unused)."""
+    table[row] = torch.tensor(stop + [-1] * (table.shape[1] - len(stop)), dtype=torch.int64)
+
+
+def _sampling_dicts(who: str, sampling, n: int, per: str, keys=None) -> List[dict]:
+    """`sampling` as a list of one dict per `per` (n of them) that hold only `keys` (None: whatever Sampler.set will take).
+    A key outside all of Sampler.set's is a TypeError, as from set() itself; one outside a narrower list a ValueError."""
+    sampling = list(sampling)
+    if len(sampling) != n or not all(isinstance(d, dict) for d in sampling):
+        raise ValueError(f"{who}: sampling must be one dict per {per} ({n}); got {sampling!r}")
+    for d in sampling:
+        extra = sorted(set(d) - set(d if keys is None else keys))
+        if extra and set(keys) >= set(Sampler._SET_DEFAULTS):
+            raise TypeError(f"{who}: unknown sampling arguments {extra}")
+        if extra:
+            raise ValueError(f"{who}: sampling may hold {', '.join(keys)}; got {extra}")
+    return sampling
+
+
+def _text_positions(T: int, device) -> torch.Tensor:
+    """The M-RoPE positions [3,1,T] of a text prompt: 0..T-1 on all three axes."""
+    return torch.arange(T, device=device, dtype=torch.int64)[None, None, :].expand(3, 1, T)
 
 
 class Sampler:
@@ -417,8 +502,35 @@ class Sampler:
     logprobs() / top_logprobs() return them token for token beside tokens().  The scored distribution is the one after the
     repetition penalty and before temperature / top-k / top-p.  None = off: the sampler launches what it always did."""
 
+    # THE list of the per-row tensors: each is an attribute of its name, [n_rows, *shape], or None when the sampler does not hold
+    # it.  row_tensors() (so every fork and beam gather), state() / load_state(), what set() clears and the keywords of
+    # sample() all follow from here, in this order (the row plans' work lists are built in it).
+    _TABLE = (
+        _RowField("temperature", torch.float32, (), 0.0),
+        _RowField("top_k", torch.int32, (), 0),
+        _RowField("top_p", torch.float32, (), 1.0),
+        _RowField("seed", torch.int64, (), 0),
+        _RowField("counter", torch.int64, (), 0, state=True),                       # draws made so far
+        _RowField("rep_penalty", torch.float32, (), 1.0, kw="rep_penalty"),
+        _RowField("seen", torch.int32, ("words",), 0, state=True, kw="seen"),       # the bitmap of a sampler built with vocab_size
+        _RowField("stop_ids", torch.int64, ("max_stop",), -1, kw="stop_ids"),
+        _RowField("budget", torch.int64, (), -1, kw="budget"),
+        _RowField("fill", torch.int64, (), 0, kw="fill"),
+        _RowField("n_new", torch.int64, (), 0, state=True, kw="n_new"),             # tokens generated
+        _RowField("done", torch.int32, (), 0, state=True, kw="done"),               # 0 running, 1 stop id, 2 budget
+        _RowField("history", torch.int64, ("history",), 0, state=True, kw="history"),
+        _RowField("logprob", torch.float32, (), 0.0, state=True, kw="logprob", score=True),
+        _RowField("cum_logprob", torch.float64, (), 0.0, state=True, kw="cum_logprob", score=True),
+        _RowField("top_ids", torch.int64, ("top",), -1, state=True, kw="top_ids", score=True),
+        _RowField("top_logprob", torch.float32, ("top",), -math.inf, state=True, kw="top_logprobs", score=True),
+        _RowField("lp_history", torch.float32, ("ring",), 0.0, state=True, kw="lp_history", score=True),
+        _RowField("top_hist_ids", torch.int64, ("ring", "top"), -1, state=True, kw="top_hist_ids", score=True),
+        _RowField("top_hist_lp", torch.float32, ("ring", "top"), -math.inf, state=True, kw="top_hist_lp", score=True),
+    )
+
     def __init__(self, n_rows: int, device, vocab_size: Optional[int] = None, max_stop: int = 8, history: int = 0,
-                 logprobs: Optional[int] = None):
+                 logprobs: Optional[int] = None, *, score_rings: bool = True):
+        """score_rings=False: no per-token score rings (lp_history, top_hist_ids, top_hist_lp) beside the token history."""
         if n_rows < 1:
             raise ValueError(f"Sampler: n_rows must be >= 1; got {n_rows}")
         if vocab_size is not None and (isinstance(vocab_size, bool) or not isinstance(vocab_size, int) or vocab_size < 1):
@@ -430,37 +542,19 @@ class Sampler:
         if logprobs is not None and (isinstance(logprobs, bool) or not isinstance(logprobs, int) or not 0 <= logprobs <= 20):
             raise ValueError(f"Sampler: logprobs must be None or an int in [0, 20]; got {logprobs!r}")
         self.n_rows = int(n_rows)
-        self.temperature = torch.zeros(n_rows, dtype=torch.float32, device=device)
-        self.top_k = torch.zeros(n_rows, dtype=torch.int32, device=device)
-        self.top_p = torch.ones(n_rows, dtype=torch.float32, device=device)
-        self.seed = torch.zeros(n_rows, dtype=torch.int64, device=device)
-        self.counter = torch.zeros(n_rows, dtype=torch.int64, device=device)      # draws made so far; the kernel advances it
-        self.vocab_size, self.max_stop, self.history_len = vocab_size, max_stop, history
-        self.controlled = vocab_size is not None or history > 0
-        self.rep_penalty = torch.ones(n_rows, dtype=torch.float32, device=device)
-        self.seen = None if vocab_size is None else torch.zeros(n_rows, (vocab_size + 31) // 32, dtype=torch.int32, device=device)
-        self.stop_ids = torch.full((n_rows, max_stop), -1, dtype=torch.int64, device=device) if max_stop else None
-        self.budget = torch.full((n_rows,), -1, dtype=torch.int64, device=device)
-        self.fill = torch.zeros(n_rows, dtype=torch.int64, device=device)
-        self.n_new = torch.zeros(n_rows, dtype=torch.int64, device=device)        # tokens generated; the kernel advances it
-        self.done = torch.zeros(n_rows, dtype=torch.int32, device=device)         # 0 running, 1 stop id, 2 budget
-        self.history = torch.zeros(n_rows, history, dtype=torch.int64, device=device) if history else None
+        self.vocab_size, self.max_stop, self.history_len, self.n_logprobs = vocab_size, max_stop, history, logprobs
+        self.controlled = vocab_size is not None or history > 0 or logprobs is not None
+        extent = {"words": (vocab_size + 31) // 32 if vocab_size is not None else 0, "max_stop": max_stop, "history": history,
+                  "top": logprobs or 0, "ring": history if score_rings else 0}
+        self._fields = []                                # the entries of _TABLE this sampler holds, in the table's order
+        for f in self._TABLE:
+            shape = [extent[e] for e in f.shape]
+            held = all(shape) and (logprobs is not None or not f.score)
+            setattr(self, f.name, torch.full((n_rows, *shape), f.init, dtype=f.dtype, device=device) if held else None)
+            if held:
+                self._fields.append(f)
         self._ends = [False] * n_rows                    # rows with a stop id or a budget (host copy, for run_until_done)
-        self.n_logprobs = logprobs
-        self.logprob = self.cum_logprob = self.top_ids = self.top_logprob = None
-        self.lp_history = self.top_hist_ids = self.top_hist_lp = None
-        if logprobs is not None:
-            self.controlled = True
-            self.logprob = torch.zeros(n_rows, dtype=torch.float32, device=device)
-            self.cum_logprob = torch.zeros(n_rows, dtype=torch.float64, device=device)
-            if history:
-                self.lp_history = torch.zeros(n_rows, history, dtype=torch.float32, device=device)
-            if logprobs:
-                self.top_ids = torch.full((n_rows, logprobs), -1, dtype=torch.int64, device=device)
-                self.top_logprob = torch.full((n_rows, logprobs), -math.inf, dtype=torch.float32, device=device)
-                if history:
-                    self.top_hist_ids = torch.full((n_rows, history, logprobs), -1, dtype=torch.int64, device=device)
-                    self.top_hist_lp = torch.full((n_rows, history, logprobs), -math.inf, dtype=torch.float32, device=device)
+        self._fork_plan = None                           # built at the first fork()
 
     def _row(self, row: int) -> int:
         if not isinstance(row, int) or not 0 <= row < self.n_rows:
@@ -495,10 +589,7 @@ class Sampler:
             if repetition_penalty != 1.0 and self.seen is None:
                 raise ValueError(f"{who}: a repetition_penalty needs a Sampler built with vocab_size (the bitmap of seen tokens)")
         if "stop_token_ids" in p:
-            stop = list(p["stop_token_ids"])
-            if len(stop) > self.max_stop or any(isinstance(t, bool) or not isinstance(t, int) or not 0 <= t < 2 ** 63 for t in stop):
-                raise ValueError(f"{who}: stop_token_ids must be at most {self.max_stop} ints >= 0; got {p['stop_token_ids']!r}")
-            p["stop_token_ids"] = stop
+            p["stop_token_ids"] = _stop_ids(who, p["stop_token_ids"], at_most=self.max_stop)
         if "max_new_tokens" in p:
             max_new_tokens = p["max_new_tokens"]
             if max_new_tokens is not None and (isinstance(max_new_tokens, bool) or not isinstance(max_new_tokens, int)
@@ -525,8 +616,7 @@ class Sampler:
         if "repetition_penalty" in p:
             self.rep_penalty[row] = p["repetition_penalty"]
         if "stop_token_ids" in p and self.stop_ids is not None:
-            stop = p["stop_token_ids"]
-            self.stop_ids[row] = torch.tensor(stop + [-1] * (self.max_stop - len(stop)), dtype=torch.int64)
+            _write_stop_ids(self.stop_ids, row, p["stop_token_ids"])
         if "max_new_tokens" in p:
             self.budget[row] = -1 if p["max_new_tokens"] is None else p["max_new_tokens"]
         if "fill_token" in p:
@@ -543,44 +633,26 @@ class Sampler:
         built with vocab_size); stop_token_ids: at most max_stop ints >= 0; max_new_tokens: None or an int >= 1; fill_token:
         what the row's token becomes once it is done."""
         row = self._row(row)
-        self._write(row, self._checked("Sampler.set", dict(
-            temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, repetition_penalty=repetition_penalty,
-            stop_token_ids=stop_token_ids, max_new_tokens=max_new_tokens, fill_token=fill_token)))
-        self.n_new[row] = 0
-        self.done[row] = 0
-        if self.seen is not None:
-            self.seen[row].zero_()
-        if self.history is not None:
-            self.history[row].zero_()
-        for t, v in ((self.logprob, 0.0), (self.cum_logprob, 0.0), (self.lp_history, 0.0), (self.top_ids, -1),
-                     (self.top_logprob, -math.inf), (self.top_hist_ids, -1), (self.top_hist_lp, -math.inf)):
-            if t is not None:
-                t[row] = v
+        given = locals()                                 # every keyword of the signature, by the names of _SET_DEFAULTS
+        self._write(row, self._checked("Sampler.set", {k: given[k] for k in self._SET_DEFAULTS}))
+        for f in self._fields:
+            if f.state:
+                getattr(self, f.name)[row] = f.init
 
     # ---- a row's parameters and state as one row of every tensor: fork ---------------------------------------------------
     def row_tensors(self) -> List[torch.Tensor]:
         """Every per-row tensor of the table, parameters and state."""
-        return [t for t in (self.temperature, self.top_k, self.top_p, self.seed, self.counter, self.rep_penalty, self.seen,
-                            self.stop_ids, self.budget, self.fill, self.n_new, self.done, self.history, self.logprob,
-                            self.cum_logprob, self.top_ids, self.top_logprob, self.lp_history, self.top_hist_ids,
-                            self.top_hist_lp) if t is not None]
+        return [getattr(self, f.name) for f in self._fields]
 
-    def _check_fork(self, who: str, src: int, dsts, sampling, keys=None) -> Tuple[int, List[int], List[dict]]:
+    def _check_fork(self, who: str, src: int, dsts, sampling) -> Tuple[int, List[int], List[dict]]:
         """(src, dsts, one checked override dict per destination) of a fork; no device work."""
         src = self._row(src)
         dsts = [self._row(d) for d in dsts]
         if not dsts or len(set(dsts)) != len(dsts) or src in dsts:
             raise ValueError(f"{who}: the destination rows must be distinct, at least one and without the source row {src}; "
                              f"got {dsts}")
-        if sampling is None:
-            sampling = [{}] * len(dsts)
-        sampling = list(sampling)
-        if len(sampling) != len(dsts) or not all(isinstance(d, dict) for d in sampling):
-            raise ValueError(f"{who}: sampling must be one dict per destination row ({len(dsts)}); got {sampling!r}")
-        keys = self._FORK_KEYS if keys is None else keys
-        for d in sampling:
-            if set(d) - set(keys):
-                raise ValueError(f"{who}: sampling may hold {', '.join(keys)}; got {sorted(set(d) - set(keys))}")
+        sampling = _sampling_dicts(who, [{}] * len(dsts) if sampling is None else sampling, len(dsts), "destination row",
+                                   self._FORK_KEYS)
         return src, dsts, [self._checked(who, d) for d in sampling]
 
     def _forked(self, src: int, dsts, overrides) -> None:
@@ -595,7 +667,7 @@ class Sampler:
         of temperature / top_k / top_p / seed, checked as in set() and applied WITHOUT clearing the copied state; a given
         seed restarts that row's counter at 0 (an independent random stream over the same history)."""
         src, dsts, overrides = self._check_fork("Sampler.fork", src, dsts, sampling)
-        if self.__dict__.get("_fork_plan") is None:
+        if self._fork_plan is None:
             self._fork_plan = ops.RowCopyPlan([(t, t) for t in self.row_tensors()])
         self._fork_plan.run(src, dsts)
         self._forked(src, dsts, overrides)
@@ -615,10 +687,7 @@ class Sampler:
         ops.mark_tokens(self.seen[row], ids, self.vocab_size)
 
     def _stateful(self):
-        return {k: t for k, t in (("counter", self.counter), ("seen", self.seen), ("n_new", self.n_new), ("done", self.done),
-                                  ("history", self.history), ("logprob", self.logprob), ("cum_logprob", self.cum_logprob),
-                                  ("top_ids", self.top_ids), ("top_logprob", self.top_logprob), ("lp_history", self.lp_history),
-                                  ("top_hist_ids", self.top_hist_ids), ("top_hist_lp", self.top_hist_lp)) if t is not None}
+        return {f.name: getattr(self, f.name) for f in self._fields if f.state}
 
     def state(self) -> Dict[str, torch.Tensor]:
         """Everything a step changes (counter, seen, n_new, done, history, and the scores of a sampler built with logprobs), for
@@ -640,20 +709,13 @@ class Sampler:
     def tokens(self, row: int) -> torch.Tensor:
         """The tokens `row` has generated, from its history (host, int64): the first min(n_new, history) entries in order; of a
         row that generated more than `history` tokens, the last `history` of them, oldest first."""
-        row = self._row(row)
-        if self.history is None:
-            raise ValueError("Sampler.tokens: needs a Sampler built with history > 0")
-        h, n = self.history[row].cpu(), int(self.n_new[row].item())
-        if n <= self.history_len:
-            return h[:n].clone()
-        a = n % self.history_len
-        return torch.cat([h[a:], h[:a]])
+        return self._ring(row, self.history, "tokens", "history > 0")
 
-    def _ring(self, row: int, ring: Optional[torch.Tensor], what: str) -> torch.Tensor:
+    def _ring(self, row: int, ring: Optional[torch.Tensor], what: str, needs: str) -> torch.Tensor:
+        """The entries of one of the history-long rings that `row` has written, oldest first."""
         row = self._row(row)
         if ring is None:
-            raise ValueError(f"Sampler.{what}: needs a Sampler built with history > 0 and logprobs"
-                             + (" >= 1" if what == "top_logprobs" else ""))
+            raise ValueError(f"Sampler.{what}: needs a Sampler built with {needs}")
         h, n = ring[row].cpu(), int(self.n_new[row].item())
         if n <= self.history_len:
             return h[:n].clone()
@@ -662,34 +724,34 @@ class Sampler:
 
     def logprobs(self, row: int) -> torch.Tensor:
         """The log-probabilities of the tokens `row` has generated (host, fp32 [n]): entry i belongs to tokens(row)[i]."""
-        return self._ring(row, self.lp_history, "logprobs")
+        return self._ring(row, self.lp_history, "logprobs", "history > 0 and logprobs")
 
     def top_logprobs(self, row: int) -> Tuple[torch.Tensor, torch.Tensor]:
         """(ids int64 [n,N], log-probabilities fp32 [n,N]) of the N most likely tokens at each step of `row`, most likely
         first: entry i belongs to tokens(row)[i]."""
-        return self._ring(row, self.top_hist_ids, "top_logprobs"), self._ring(row, self.top_hist_lp, "top_logprobs")
+        return tuple(self._ring(row, ring, "top_logprobs", "history > 0 and logprobs >= 1")
+                     for ring in (self.top_hist_ids, self.top_hist_lp))
 
     def sample(self, logits: torch.Tensor, out: torch.Tensor, row: Optional[int] = None) -> torch.Tensor:
         """Tokens of every row (logits [n_rows,V]) or of the one `row` (logits [1,V]; views of the table, no copy) into `out`."""
         sl = slice(None) if row is None else slice(row, row + 1)
-        if not self.controlled:
-            return ops.sample_tokens(logits, self.temperature[sl], self.top_k[sl], self.top_p[sl], self.seed[sl], self.counter[sl],
-                                     out=out)
-        if self.seen is not None and logits.shape[-1] != self.vocab_size:
-            raise ValueError(f"Sampler.sample: logits of {logits.shape[-1]} tokens for a sampler of vocab_size {self.vocab_size}")
+        kw = {}
+        if self.controlled:
+            if self.seen is not None and logits.shape[-1] != self.vocab_size:
+                raise ValueError(f"Sampler.sample: logits of {logits.shape[-1]} tokens for a sampler of vocab_size {self.vocab_size}")
+            kw = {f.kw: getattr(self, f.name)[sl] for f in self._fields if f.kw is not None}
+            if self.seen is None:
+                del kw["rep_penalty"]                    # the penalty reads the bitmap: without one the launch takes neither
         return ops.sample_tokens(logits, self.temperature[sl], self.top_k[sl], self.top_p[sl], self.seed[sl], self.counter[sl],
-                                 out=out, rep_penalty=self.rep_penalty[sl] if self.seen is not None else None,
-                                 seen=self.seen[sl] if self.seen is not None else None,
-                                 stop_ids=self.stop_ids[sl] if self.stop_ids is not None else None, budget=self.budget[sl],
-                                 fill=self.fill[sl], n_new=self.n_new[sl], done=self.done[sl],
-                                 history=self.history[sl] if self.history is not None else None,
-                                 **{k: t[sl] for k, t in (("logprob", self.logprob), ("top_ids", self.top_ids),
-                                                          ("top_logprobs", self.top_logprob), ("cum_logprob", self.cum_logprob),
-                                                          ("lp_history", self.lp_history), ("top_hist_ids", self.top_hist_ids),
-                                                          ("top_hist_lp", self.top_hist_lp)) if t is not None})
+                                 out=out, **kw)
 
 
-class GraphedDecode:
+# the names and defaults of set()'s keywords are stated once, in its signature: set() and admit_n read them from here
+Sampler._SET_DEFAULTS = {k: p.default for k, p in inspect.signature(Sampler.set).parameters.items()
+                         if p.default is not inspect.Parameter.empty}
+
+
+class GraphedDecode(_Graphed):
     """hipGraph-captured single-token step: embed(token) -> stack -> argmax -> token buffer
     (the demo's eager loop, demo:399-422, made replayable: token and position stay on the device).  With a `sampler` (a
     Sampler of batch_size rows) the arg-max and the copy are ONE ops.sample_tokens launch on the sampler's table."""
@@ -706,41 +768,14 @@ class GraphedDecode:
         self.logits = None
         self.graph: Optional[torch.cuda.CUDAGraph] = None
         self._warmup = warmup
-        self._captured_controlled = False
-
-    def _run(self):
-        _, lg = self.model(input_ids=self.token, position_ids=self.position_ids, past_key_values=self.cache,
-                           logits_to_keep=1)
-        if self.sampler is None:
-            self.token.copy_(lg[:, -1].argmax(-1, keepdim=True))
-        else:
-            self.sampler.sample(lg[:, -1], self.token)
-        self.position_ids.add_(1)
-        return lg
 
     def capture(self) -> None:
         self.cache.ensure_started()
-        saved, saved_pos, saved_tok = self.cache.clone(), self.position_ids.clone(), self.token.clone()
-        saved_smp = self.sampler.state() if self.sampler is not None else None
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s), torch.no_grad():
-            for _ in range(self._warmup):
-                self._run()
-        torch.cuda.current_stream().wait_stream(s)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.no_grad(), torch.cuda.graph(self.graph):
-            self.logits = self._run()
-        self.cache.copy_from(saved)
-        self.position_ids.copy_(saved_pos)
-        self.token.copy_(saved_tok)
-        if self.sampler is not None:
-            self.sampler.load_state(saved_smp)          # the warm-up and the capture itself made draws
-            self._captured_controlled = self.sampler.controlled
+        self.logits = self._capture([self.position_ids, self.token])
 
     def step(self):
         """One decode step; the new token is left in self.token (device)."""
-        if self.graph is None or (self.sampler is not None and self.sampler.controlled != self._captured_controlled):
+        if self._stale():
             self.capture()
         self.cache.ensure_started()
         self.graph.replay()
@@ -748,7 +783,7 @@ class GraphedDecode:
         return self.token
 
 
-class GraphedMultiStreamDecode:
+class GraphedMultiStreamDecode(_Graphed):
     """Decode of independent streams in the slots of a MultiStreamCache: ONE captured graph advances every slot by
     one token (embed -> stack -> argmax -> token buffer, per-slot positions +1).  Streams join with admit() (the prompt runs
     eagerly on the slot's B = 1 view) and leave with release(), both between replays and without a recapture.
@@ -774,38 +809,12 @@ class GraphedMultiStreamDecode:
         self.logits = self.admit_logits = None
         self.graph: Optional[torch.cuda.CUDAGraph] = None
         self._warmup = warmup
-        self._captured_controlled = False
         self._live = set()                               # slots between admit and release
-
-    def _run(self):
-        _, lg = self.model(input_ids=self.token, position_ids=self.position_ids, past_key_values=self.cache,
-                           logits_to_keep=1)
-        if self.sampler is None:
-            self.token.copy_(lg[:, -1].argmax(-1, keepdim=True))
-        else:
-            self.sampler.sample(lg[:, -1], self.token)
-        self.position_ids.add_(1)
-        return lg
+        self._fork_plan = None                           # built at the first fork
 
     def capture(self) -> None:
         """Warm up and capture; every slot's ring, state, position and token are restored afterwards."""
-        saved, saved_pos, saved_tok = self.cache.clone(), self.position_ids.clone(), self.token.clone()
-        saved_smp = self.sampler.state() if self.sampler is not None else None
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s), torch.no_grad():
-            for _ in range(self._warmup):
-                self._run()
-        torch.cuda.current_stream().wait_stream(s)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.no_grad(), torch.cuda.graph(self.graph):
-            self.logits = self._run()
-        self.cache.copy_from(saved)
-        self.position_ids.copy_(saved_pos)
-        self.token.copy_(saved_tok)
-        if self.sampler is not None:
-            self.sampler.load_state(saved_smp)          # the warm-up and the capture itself made draws
-            self._captured_controlled = self.sampler.controlled
+        self.logits = self._capture([self.position_ids, self.token])
 
     @torch.no_grad()
     def admit(self, slot: int, inputs_embeds: torch.Tensor, position_ids: Optional[torch.Tensor] = None,
@@ -818,15 +827,9 @@ class GraphedMultiStreamDecode:
         and may already end the stream."""
         if sampling is not None and self.sampler is None:
             raise ValueError("admit: sampling parameters need a GraphedMultiStreamDecode built with a sampler")
-        if prompt_ids is not None and self.sampler is None:
-            raise ValueError("admit: prompt_ids need a GraphedMultiStreamDecode built with a sampler")
-        if inputs_embeds.dim() != 3 or inputs_embeds.shape[0] != 1:
-            raise ValueError(f"admit: inputs_embeds must be [1,T,hidden]; got {tuple(inputs_embeds.shape)}")
-        T = inputs_embeds.shape[1]
+        T = self._check_prompt("admit", inputs_embeds, position_ids, prompt_ids)
         if position_ids is None:
-            position_ids = torch.arange(T, device=inputs_embeds.device, dtype=torch.int64)[None, None, :].expand(3, 1, T)
-        if tuple(position_ids.shape) != (3, 1, T):
-            raise ValueError(f"admit: position_ids must be [3,1,{T}]; got {tuple(position_ids.shape)}")
+            position_ids = _text_positions(T, inputs_embeds.device)
         if sampling is not None:
             self.sampler.set(slot, **sampling)
         if prompt_ids is not None:
@@ -874,14 +877,18 @@ class GraphedMultiStreamDecode:
             raise ValueError(f"{who}: slots must be distinct ints in [0, {self.S}), at least one; got {slots!r}")
         return slots
 
+    def _slot_tensors(self) -> List[torch.Tensor]:
+        """Everything a slot owns here, the slot on dim 0: the cache's rows, its token, its three M-RoPE positions and the
+        sampler's rows."""
+        ts = self.cache.row_tensors() + [self.token] + [self.position_ids[i] for i in range(3)]
+        if self.sampler is not None:
+            ts += self.sampler.row_tensors()
+        return ts
+
     def _row_plan(self) -> "ops.RowCopyPlan":
-        """ONE plan over everything a slot owns here: the cache's rows, its token, its three M-RoPE positions and the sampler's
-        rows.  Built at the first fork and kept (the tensors never move)."""
-        if self.__dict__.get("_fork_plan") is None:
-            ts = self.cache.row_tensors() + [self.token] + [self.position_ids[i] for i in range(3)]
-            if self.sampler is not None:
-                ts += self.sampler.row_tensors()
-            self._fork_plan = ops.RowCopyPlan([(t, t) for t in ts])
+        """ONE plan over everything a slot owns.  Built at the first fork and kept (the tensors never move)."""
+        if self._fork_plan is None:
+            self._fork_plan = ops.RowCopyPlan([(t, t) for t in self._slot_tensors()])
         return self._fork_plan
 
     def _fork_rows(self, src: int, dsts: List[int]) -> None:
@@ -945,19 +952,11 @@ class GraphedMultiStreamDecode:
             raise ValueError("admit_n: sampling parameters need a GraphedMultiStreamDecode built with a sampler")
         T = self._check_prompt("admit_n", inputs_embeds, position_ids, prompt_ids)
         if position_ids is None:
-            position_ids = torch.arange(T, device=inputs_embeds.device, dtype=torch.int64)[None, None, :].expand(3, 1, T)
+            position_ids = _text_positions(T, inputs_embeds.device)
         checked = None
         if sampling is not None:
-            sampling = list(sampling)
-            if len(sampling) != len(slots) or not all(isinstance(d, dict) for d in sampling):
-                raise ValueError(f"admit_n: sampling must be one dict per slot ({len(slots)}); got {sampling!r}")
-            names = ("temperature", "top_k", "top_p", "seed", "repetition_penalty", "stop_token_ids", "max_new_tokens", "fill_token")
-            for d in sampling:
-                if set(d) - set(names):
-                    raise TypeError(f"admit_n: unknown sampling arguments {sorted(set(d) - set(names))}")
-            defaults = dict(temperature=0.0, top_k=0, top_p=1.0, seed=0, repetition_penalty=1.0, stop_token_ids=(),
-                            max_new_tokens=None, fill_token=0)
-            checked = [self.sampler._checked("admit_n", {**defaults, **d}) for d in sampling]
+            sampling = _sampling_dicts("admit_n", sampling, len(slots), "slot", tuple(Sampler._SET_DEFAULTS))
+            checked = [self.sampler._checked("admit_n", {**Sampler._SET_DEFAULTS, **d}) for d in sampling]
         first, rest = slots[0], slots[1:]
         if sampling is not None:
             self.sampler.set(first, **sampling[0])
@@ -990,9 +989,7 @@ class GraphedMultiStreamDecode:
         if sampling is not None:
             if self.sampler is None:
                 raise ValueError("load: sampling parameters need a GraphedMultiStreamDecode built with a sampler")
-            sampling = list(sampling)
-            if len(sampling) != len(slots) or not all(isinstance(d, dict) for d in sampling):
-                raise ValueError(f"load: sampling must be one dict per slot ({len(slots)}); got {sampling!r}")
+            sampling = _sampling_dicts("load", sampling, len(slots), "slot")      # (the keys: set() checks them, slot by slot)
         if next_position is not None and (isinstance(next_position, bool) or not isinstance(next_position, int) or next_position < 0):
             raise ValueError(f"load: next_position must be None or an int >= 0; got {next_position!r}")
         self.cache.load(slots, cache, row)
@@ -1021,11 +1018,23 @@ class GraphedMultiStreamDecode:
             with torch.no_grad():
                 self.logits = self._run()
             return self.token
-        if self.graph is None or (self.sampler is not None and self.sampler.controlled != self._captured_controlled):
+        if self._stale():
             self.capture()
         self.graph.replay()
         self.cache.advance(1)
         return self.token
+
+    def _replay_until(self, finished, max_steps: int, poll_every: int) -> None:
+        """Up to `max_steps` replays; finished() -- a host read, so it waits for the steps queued so far -- is asked before the
+        first and after every `poll_every` of them, and ends the loop."""
+        if max_steps < 0 or poll_every < 1:
+            raise ValueError(f"run_until_done: max_steps >= 0 and poll_every >= 1; got {max_steps}, {poll_every}")
+        steps = 0
+        while steps < max_steps and not finished():
+            n = min(poll_every, max_steps - steps)
+            for _ in range(n):
+                self.step()
+            steps += n
 
     def run_until_done(self, max_steps: int, poll_every: int = 16) -> Dict[int, torch.Tensor]:
         """Replay up to `max_steps` steps without a host round trip per token: the sampler's done flags are polled every
@@ -1034,17 +1043,8 @@ class GraphedMultiStreamDecode:
         the sampler's history.  A finished slot keeps computing on its fill token until it is released."""
         if self.sampler is None or self.sampler.history is None:
             raise ValueError("run_until_done: needs a sampler built with history > 0")
-        if max_steps < 0 or poll_every < 1:
-            raise ValueError(f"run_until_done: max_steps >= 0 and poll_every >= 1; got {max_steps}, {poll_every}")
         watched = [s for s in sorted(self._live) if self.sampler._ends[s]]
-        steps = 0
-        while steps < max_steps:
-            if watched and bool((self.sampler.poll()[0][watched] != 0).all()):
-                break
-            n = min(poll_every, max_steps - steps)
-            for _ in range(n):
-                self.step()
-            steps += n
+        self._replay_until(lambda: bool(watched) and bool((self.sampler.poll()[0][watched] != 0).all()), max_steps, poll_every)
         return {s: self.sampler.tokens(s) for s in sorted(self._live)}
 
 
@@ -1070,8 +1070,8 @@ class GraphedBeamDecode(GraphedMultiStreamDecode):
             raise ValueError(f"GraphedBeamDecode: max_stop must be an int in [0, 16]; got {max_stop!r}")
         K = ops.beam_width(num_beams, max_stop)          # refuses K > 20
         device = next(model.parameters()).device
-        sampler = Sampler(cache.n_slots, device, vocab_size=vocab_size, max_stop=0, history=history, logprobs=K)
-        sampler.lp_history = sampler.top_hist_ids = sampler.top_hist_lp = None      # a beam keeps tokens, not per-token scores
+        sampler = Sampler(cache.n_slots, device, vocab_size=vocab_size, max_stop=0, history=history, logprobs=K,
+                          score_rings=False)                                        # a beam keeps tokens, not per-token scores
         super().__init__(model, cache, warmup=warmup, sampler=sampler)
         self.B, self.G, self.K, self.L, self.max_stop = num_beams, cache.n_slots // num_beams, K, history, max_stop
         G, B, L = self.G, self.B, self.L
@@ -1095,8 +1095,7 @@ class GraphedBeamDecode(GraphedMultiStreamDecode):
     def _plan(self) -> "ops.RowGatherPlan":
         """ONE plan over everything a slot owns: the cache's rows, its token, its M-RoPE positions, the sampler's rows."""
         if self._gather_plan is None:
-            ts = self.cache.row_tensors() + [self.token] + [self.position_ids[i] for i in range(3)] + self.sampler.row_tensors()
-            self._gather_plan = ops.RowGatherPlan(ts)
+            self._gather_plan = ops.RowGatherPlan(self._slot_tensors())
         return self._gather_plan
 
     def _beam_tail(self, logits: torch.Tensor, row0: int, groups) -> None:
@@ -1113,19 +1112,12 @@ class GraphedBeamDecode(GraphedMultiStreamDecode):
             plan.run(g * self.B, self.B, self.beam["parent"][g])
         ops.beam_commit(self.B, mask, self.token, smp.seen, smp.vocab_size, smp.history, smp.n_new, smp.cum_logprob, self.beam)
 
-    def _run(self):
-        _, lg = self.model(input_ids=self.token, position_ids=self.position_ids, past_key_values=self.cache,
-                           logits_to_keep=1)
-        self._beam_tail(lg[:, -1], 0, range(self.G))
-        self.position_ids.add_(1)
-        return lg
+    def _next_token(self, logits: torch.Tensor) -> None:
+        self._beam_tail(logits, 0, range(self.G))
 
     def capture(self) -> None:
         """As GraphedMultiStreamDecode.capture; the beam tensors are saved and restored around the warm-up too."""
-        saved = {k: t.clone() for k, t in self.beam.items()}
-        super().capture()
-        for k, t in self.beam.items():
-            t.copy_(saved[k])
+        self.logits = self._capture([self.position_ids, self.token, *self.beam.values()])
 
     @torch.no_grad()
     def admit(self, group: int, inputs_embeds: torch.Tensor, position_ids: Optional[torch.Tensor] = None,
@@ -1138,9 +1130,7 @@ class GraphedBeamDecode(GraphedMultiStreamDecode):
         max_stop ints >= 0."""
         g = self._group("admit", group)
         T = self._check_prompt("admit", inputs_embeds, position_ids, prompt_ids)
-        stop = list(stop_token_ids)
-        if any(isinstance(t, bool) or not isinstance(t, int) or not 0 <= t < 2 ** 63 for t in stop):
-            raise ValueError(f"admit: stop_token_ids must be ints >= 0; got {stop_token_ids!r}")
+        stop = _stop_ids("admit", stop_token_ids)        # (how many: the K of this decoder bounds them, next)
         if ops.beam_width(self.B, len(stop)) > self.K:
             raise ValueError(f"admit: {len(stop)} stop ids need K = {ops.beam_width(self.B, len(stop))} candidates per beam; this "
                              f"decoder was built with max_stop = {self.max_stop} (K = {self.K})")
@@ -1156,7 +1146,7 @@ class GraphedBeamDecode(GraphedMultiStreamDecode):
             raise ValueError(f"admit: early_stopping must be a bool (\"never\" is not offered); got {early_stopping!r}")
         checked = self.sampler._checked("admit", dict(repetition_penalty=repetition_penalty))
         if position_ids is None:
-            position_ids = torch.arange(T, device=inputs_embeds.device, dtype=torch.int64)[None, None, :].expand(3, 1, T)
+            position_ids = _text_positions(T, inputs_embeds.device)
         B, s0 = self.B, g * self.B
         for s in range(s0, s0 + B):
             self.sampler.set(s, repetition_penalty=checked["repetition_penalty"])
@@ -1171,7 +1161,7 @@ class GraphedBeamDecode(GraphedMultiStreamDecode):
         bm["beam_done"][g] = 0
         bm["n_hyp"][g] = 0
         if self.stop_ids is not None:
-            self.stop_ids[g] = torch.tensor(stop + [-1] * (self.max_stop - len(stop)), dtype=torch.int64)
+            _write_stop_ids(self.stop_ids, g, stop)
         self.cache.admit(s0)
         lg = self._prefill(s0, inputs_embeds, position_ids)
         self.admit_logits = lg
@@ -1208,17 +1198,8 @@ class GraphedBeamDecode(GraphedMultiStreamDecode):
     def run_until_done(self, max_steps: int, poll_every: int = 16):
         """Replay up to `max_steps` steps; beam_done is polled every `poll_every` steps and the loop ends once every admitted
         group is finished.  Returns {group: result(group)} of the admitted groups."""
-        if max_steps < 0 or poll_every < 1:
-            raise ValueError(f"run_until_done: max_steps >= 0 and poll_every >= 1; got {max_steps}, {poll_every}")
         groups = sorted(self._groups)
-        steps = 0
-        while steps < max_steps:
-            if groups and bool((self.beam["beam_done"].cpu()[groups] != 0).all()):
-                break
-            n = min(poll_every, max_steps - steps)
-            for _ in range(n):
-                self.step()
-            steps += n
+        self._replay_until(lambda: bool(groups) and bool((self.beam["beam_done"].cpu()[groups] != 0).all()), max_steps, poll_every)
         return {g: self.result(g) for g in groups}
 
     def _per_slot(self, *a, **k):

@@ -8,7 +8,9 @@
   5. admit_n: one prefill, n independent sampled answers == n admissions;
   6. the streaming demo's branch: load from a B = 1 stream cache, extend with a question, decode; the source stays untouched;
   7. store + load == fork;
-  8. the model's real width: one launch is not slower than the per-tensor copy_ loop."""
+  8. the model's real width: one launch is not slower than the per-tensor copy_ loop;
+  9. admit refuses an empty prompt before any state is touched;
+ 10. capture() of each of the four graphed classes leaves every tensor the object owns as it was."""
 import statistics
 
 import pytest
@@ -271,6 +273,116 @@ def test_store_then_load_equals_fork(small):
     assert b1.get_seq_length() == n + 1 and b1.layers[0]._pos_dev.tolist() == [n + 1]
     dec.step(graph=False)                                         # the same token in the slot it came from
     assert rms_rel(lg[0, -1].float().cpu(), dec.logits[0, -1].float().cpu()) < 4e-3
+
+
+# ---------------------------------------------------------------------------------------------
+# 9. a refused admission
+# ---------------------------------------------------------------------------------------------
+def test_admit_refuses_an_empty_prompt_before_it_touches_anything(small):
+    _, hc = small
+    dec, cache = _decoder(small, 2)
+    dec.admit(0, fk.prompt(hc, 5, 81, DEV)[0])
+    rows = [t.clone() for t in cache.row_tensors()]
+    with pytest.raises(ValueError, match=r"admit: inputs_embeds must be \[1,T,hidden\]"):
+        dec.admit(1, torch.zeros(1, 0, hc.hidden_size, dtype=torch.bfloat16, device=DEV))
+    assert cache.slot_lengths == [5, 0] and dec._live == {0}
+    for t, was in zip(cache.row_tensors(), rows):
+        assert torch.equal(t, was)
+
+
+# ---------------------------------------------------------------------------------------------
+# 10. capture() has no side effects
+# ---------------------------------------------------------------------------------------------
+def _graphed_step(small):
+    """The T and the once-fed B = 1 cache of the capture test in tests/test_gpu_parity.py."""
+    from infinitevl_amd.harness import GraphedStep
+    stack, hc = small
+    T = 70
+    cache = stack.allocate_inference_cache(1, zero_init=True)
+    with torch.no_grad():
+        stack(inputs_embeds=fk.prompt(hc, T, 91, DEV)[0], past_key_values=cache)
+    gs = GraphedStep(stack, cache, 1, T)
+    gs.inputs_embeds.copy_(fk.prompt(hc, T, 92, DEV)[0])
+    return gs
+
+
+def _graphed_decode(small):
+    from infinitevl_amd.harness import GraphedDecode, Sampler
+    stack, hc = small
+    cache = stack.allocate_inference_cache(2, zero_init=True)
+    with torch.no_grad():
+        stack(inputs_embeds=torch.cat([fk.prompt(hc, 5, 93 + b, DEV)[0] for b in range(2)]), past_key_values=cache)
+    smp = Sampler(2, DEV, vocab_size=hc.vocab_size, history=8)
+    for b in range(2):
+        smp.set(b, temperature=0.8, seed=b + 1, repetition_penalty=1.3)
+    dec = GraphedDecode(stack, cache, 2, sampler=smp)
+    dec.token.copy_(torch.tensor([[7], [300]]))
+    return dec
+
+
+def _graphed_multistream(small):
+    from infinitevl_amd.harness import Sampler
+    _, hc = small
+    dec, _ = _decoder(small, 4, sampler=Sampler(4, DEV, vocab_size=hc.vocab_size, history=8, logprobs=2))
+    for slot, T in ((0, 5), (2, 100)):                 # below the window of 96 and past it: that slot's ring has wrapped
+        x, ids = fk.prompt(hc, T, 95 + slot, DEV)
+        dec.admit(slot, x, sampling=dict(temperature=0.8, seed=slot + 1, repetition_penalty=1.3), prompt_ids=ids)
+    return dec
+
+
+def _graphed_beam(small):
+    from infinitevl_amd.cache import MultiStreamCache
+    from infinitevl_amd.harness import GraphedBeamDecode
+    stack, hc = small
+    cache = MultiStreamCache(config=hc, n_slots=4, device=DEV, dtype=torch.bfloat16)
+    dec = GraphedBeamDecode(stack, cache, 2, hc.vocab_size, 16)
+    x, ids = fk.prompt(hc, 100, 99, DEV)
+    dec.admit(1, x, prompt_ids=ids, max_new_tokens=12, stop_token_ids=[3], repetition_penalty=1.3)
+    return dec
+
+
+def _owned(obj):
+    """Every tensor the graphed object owns on the host, by name, and the host counters of its cache."""
+    out, cache = {}, obj.cache
+    if hasattr(cache, "row_tensors"):
+        out.update({f"cache.{i}": t for i, t in enumerate(cache.row_tensors())})
+        host = list(cache.slot_lengths)
+    else:
+        snap = _source_snapshot(cache)
+        out.update({f"cache.{i}.{j}": t for i, (ts, _, _) in enumerate(snap) for j, t in enumerate(ts)})
+        out.update({f"cache.{i}.pos": pos for i, (_, _, pos) in enumerate(snap) if pos is not None})
+        host = [h for _, h, _ in snap]
+    out["position_ids"] = obj.position_ids
+    for name in ("token", "stop_ids"):
+        if getattr(obj, name, None) is not None:
+            out[name] = getattr(obj, name)
+    if getattr(obj, "sampler", None) is not None:
+        out.update({f"sampler.{i}": t for i, t in enumerate(obj.sampler.row_tensors())})
+    out.update({f"beam.{k}": t for k, t in getattr(obj, "beam", {}).items()})
+    return {k: t.cpu() for k, t in out.items()}, host
+
+
+@pytest.mark.parametrize("build, eager", [(_graphed_step, False), (_graphed_decode, False), (_graphed_multistream, True),
+                                          (_graphed_beam, True)], ids=["step", "decode", "multistream", "beam"])
+def test_capture_leaves_every_tensor_as_it_was(small, build, eager):
+    """The warm-up runs and the captured run themselves advance the cache, the positions, the token, the sampler's state and
+    the beam tables: all of it is back afterwards, bit for bit, and the graph then steps as the eager step does (where the
+    class offers one; the other two have their own graph-against-eager tests)."""
+    obj = build(small)
+    torch.cuda.synchronize()
+    before, host = _owned(obj)
+    obj.capture()
+    torch.cuda.synchronize()
+    after, host_after = _owned(obj)
+    assert obj.graph is not None and host_after == host and after.keys() == before.keys()
+    for k, was in before.items():
+        assert torch.equal(after[k], was), k
+    if eager:
+        ref = build(small)
+        for i in range(3):
+            obj.step()
+            ref.step(graph=False)
+            assert torch.equal(obj.token, ref.token), i
 
 
 # ---------------------------------------------------------------------------------------------

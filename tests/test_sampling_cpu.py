@@ -190,3 +190,67 @@ def test_entry_point_validates_and_is_exported(lib):
     assert "ivl_sample_rows_fwd" in _lib.EXPORTED_SYMBOLS
     out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
     assert "ivl_sample_rows_fwd" in {ln.split()[-1] for ln in out.splitlines() if ln.strip()}
+
+
+@pytest.mark.parametrize("logprobs", [None, 0, 2])
+@pytest.mark.parametrize("history", [0, 5])
+@pytest.mark.parametrize("max_stop", [0, 3])
+@pytest.mark.parametrize("vocab_size", [None, 70])
+def test_sampler_table_follows_its_configuration(monkeypatch, vocab_size, max_stop, history, logprobs):
+    """Which per-row tensors a Sampler holds, which of them are state, what set() clears them to and under which keyword
+    sample() hands each to ops.sample_tokens, as rules over the constructor's arguments."""
+    from infinitevl_amd import ops
+    from infinitevl_amd.harness import Sampler
+    s = Sampler(3, "cpu", vocab_size=vocab_size, max_stop=max_stop, history=history, logprobs=logprobs)
+    bitmap, ring, scored, top = vocab_size is not None, history > 0, logprobs is not None, bool(logprobs)
+    inf = float("inf")
+    # name: (exists, value of a fresh or cleared row, a step changes it, keyword of ops.sample_tokens), in row_tensors() order
+    rules = {"temperature": (True, 0, False, None), "top_k": (True, 0, False, None), "top_p": (True, 1, False, None),
+             "seed": (True, 0, False, None), "counter": (True, 0, True, None),
+             "rep_penalty": (True, 1, False, "rep_penalty" if bitmap else None), "seen": (bitmap, 0, True, "seen"),
+             "stop_ids": (max_stop > 0, -1, False, "stop_ids"), "budget": (True, -1, False, "budget"),
+             "fill": (True, 0, False, "fill"), "n_new": (True, 0, True, "n_new"), "done": (True, 0, True, "done"),
+             "history": (ring, 0, True, "history"), "logprob": (scored, 0, True, "logprob"),
+             "cum_logprob": (scored, 0, True, "cum_logprob"), "top_ids": (top, -1, True, "top_ids"),
+             "top_logprob": (top, -inf, True, "top_logprobs"), "lp_history": (scored and ring, 0, True, "lp_history"),
+             "top_hist_ids": (top and ring, -1, True, "top_hist_ids"), "top_hist_lp": (top and ring, -inf, True, "top_hist_lp")}
+    have = [n for n, r in rules.items() if r[0]]
+    assert all(getattr(s, n) is None for n in rules if n not in have)
+    assert len(have) == 10 + bitmap + (max_stop > 0) + ring + 2 * scored + 2 * top + (scored and ring) + 2 * (top and ring)
+    assert [t.data_ptr() for t in s.row_tensors()] == [getattr(s, n).data_ptr() for n in have]
+    for n in have:
+        t = getattr(s, n)
+        assert t.shape[0] == 3 and torch.equal(t, torch.full_like(t, rules[n][1])), n
+    state = s.state()
+    assert sorted(state) == sorted(n for n in have if rules[n][2])
+    assert all(state[n].data_ptr() != getattr(s, n).data_ptr() for n in state)
+
+    calls = []
+    monkeypatch.setattr(ops, "sample_tokens", lambda *a, **k: calls.append((a, k)) or k["out"])
+    V = vocab_size or 70
+    token = torch.zeros(3, 1, dtype=torch.int64)
+    assert s.sample(torch.zeros(3, V, dtype=torch.bfloat16), token) is token
+    s.sample(torch.zeros(1, V, dtype=torch.bfloat16), token[1:2], row=1)
+    assert s.controlled == (bitmap or ring or scored) and len(calls) == 2
+    for (args, kw), rows, row0 in zip(calls, (3, 1), (0, 1)):
+        def is_rows_of(t, name):
+            whole = getattr(s, name)
+            return tuple(t.shape) == (rows, *whole.shape[1:]) and \
+                t.data_ptr() == whole.data_ptr() + row0 * whole.stride(0) * whole.element_size()
+        assert len(args) == 6 and tuple(args[0].shape) == (rows, V)
+        for t, n in zip(args[1:], ("temperature", "top_k", "top_p", "seed", "counter")):
+            assert is_rows_of(t, n), n
+        assert kw["out"].data_ptr() == token[row0:].data_ptr()
+        given = {k: t for k, t in kw.items() if t is not None and k != "out"}
+        want = {r[3]: n for n, r in rules.items() if r[0] and r[3] is not None} if s.controlled else {}
+        assert sorted(given) == sorted(want)
+        for k, t in given.items():
+            assert is_rows_of(t, want[k]), k
+
+    for n in have:
+        if rules[n][2]:
+            getattr(s, n)[1] = 7
+    s.set(1)
+    for n in have:
+        t = getattr(s, n)
+        assert torch.equal(t, torch.full_like(t, rules[n][1])), n
