@@ -514,6 +514,57 @@ IVL_API int ivl_sample_rows_lp_fwd(const void* logits, int64_t ld, int S, int V,
                                    float* logprob, int n_top, int64_t* top_ids, float* top_logprobs, double* cum_logprob,
                                    float* lp_history, int64_t* top_hist_ids, float* top_hist_lp, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * ivl_sample_rows_lp_fwd under a token-level finite state machine per row, inside the same one launch: constrained decoding (what
+ * HF generate takes as prefix_allowed_tokens_fn or a logits processor, with the token on the host after every step) without a
+ * host round trip per token.  The arguments of ivl_sample_rows_lp_fwd, then the constraint group:
+ *   fsm_state int32 [S]: per row a state index q >= 0, or -1 = an unconstrained row;
+ *   fsm_mask uint32 [n_states, mask_ld], mask_ld*32 >= V: bit (i & 31) of word (i >> 5) of row q = token i is allowed in state q
+ *     (the layout of `seen`);
+ *   fsm_desc int64 [n_states, 2] = {trans_off, cls_off} of state q's grammar;  fsm_cls int32, flat: the class of token i in that
+ *     grammar = fsm_cls[cls_off + i];  fsm_trans int32, flat: next = fsm_trans[trans_off + class]: a state >= 0, -1 = the row
+ *     becomes unconstrained, -2 = no transition.  States are global indices: several grammars share the tables.
+ * Per row s, with q = fsm_state[s] read ONCE at kernel entry (behind step A: a finished row is not looked at):
+ *   F0 group off or row free.  fsm_state == NULL: the call IS ivl_sample_rows_lp_fwd, bit for bit.  A row with q < 0 behaves as
+ *      in that call and its state stays as it is.
+ *   F1 the row is its allowed sub-vocabulary.  A = {i < V : bit i of mask row q}.  Steps 1-6, B and L1-L3 run over i in A only: a
+ *      token outside A is not keyed to -inf, it is ABSENT -- no part in the maximum, the counts, the masses, Z1, the top-N or the
+ *      walk -- and can never be emitted or listed, also when every allowed logit is -inf or NaN and a disallowed one is +inf.
+ *      Bits at or above V in a mask row's last word and the words between ceil(V/32) and mask_ld are ignored.
+ *   F2 what follows: |A| takes V's place throughout.  top_k >= |A| keeps all of A; entries j >= |A| of the top-N list are -1 /
+ *      -inf; a set A whose logits are all -inf or NaN gives each of its tokens -logf((float)|A|) (Z1 = |A| 2^40); n_kept, prob
+ *      and logprob are those of the distribution renormalised over A.
+ *   F3 all sums are integers and the draw is the first index in vocabulary order, so every output equals, bit for bit, that of
+ *      ivl_sample_rows_lp_fwd on the gathered row x[A] (A ascending) with the gathered seen bits: token and top_ids (mapped back
+ *      through A), counter, n_kept, prob, logprob, top_logprobs, the rings and cum_logprob.
+ *   F4 advance, by the lane that writes the token, behind step C:  c = fsm_cls[cls_off + token];
+ *      fsm_state[s] = fsm_trans[trans_off + c].  `done` is decided by step C as before: a stop id that an accepting state allows
+ *      ends the row through the stop rule.
+ *   F5 dead end: done[s] = 3.
+ *      A is empty, or q >= n_states (then no word of the tables is read): token = fill[s] (0 without fill), n_kept = 0, prob = 0,
+ *      logprob = 0, top_ids = -1, top_logprobs = -inf; the counter, seen, n_new, the history, the rings, cum_logprob and the
+ *      state stay unchanged (step A's treatment).  "A is empty" is decided uniformly for the workgroup after pass 1.
+ *      The transition read in F4 is -2 (tables whose mask and transitions disagree): the token stands as drawn with step C's
+ *      bookkeeping, the state stays unchanged, and done[s] = 3 replaces what step C decided.
+ * Tables are the caller's to keep consistent (bit set <=> transition != -2) and in bounds: cls_off + i and trans_off + class are
+ * not checked on the device.
+ * done codes: 0 running, 1 stop id, 2 budget, 3 dead end.
+ * IVL_ERR_INVALID_ARG (before anything is launched): fsm_state with fsm_mask, fsm_desc, fsm_cls, fsm_trans or done NULL;
+ * mask_ld*32 < V; n_states < 1; and whatever ivl_sample_rows_lp_fwd refuses.
+ * ------------------------------------------------------------------------------------------- */
+IVL_API int ivl_sample_rows_fsm_fwd(const void* logits, int64_t ld, int S, int V,
+                                    const float* temperature, const int32_t* top_k, const float* top_p,
+                                    const int64_t* seed, int64_t* counter,
+                                    int64_t* token, int64_t token_stride,
+                                    int32_t* n_kept, float* prob,
+                                    const float* rep_penalty, uint32_t* seen, int64_t seen_ld,
+                                    const int64_t* stop_ids, int n_stop, const int64_t* budget, const int64_t* fill,
+                                    int64_t* n_new, int32_t* done, int64_t* history, int64_t hist_ld,
+                                    float* logprob, int n_top, int64_t* top_ids, float* top_logprobs, double* cum_logprob,
+                                    float* lp_history, int64_t* top_hist_ids, float* top_hist_lp,
+                                    int32_t* fsm_state, const uint32_t* fsm_mask, int64_t mask_ld, int n_states,
+                                    const int64_t* fsm_desc, const int32_t* fsm_cls, const int32_t* fsm_trans, void* stream);
+
 /* Sets the bits of ids[0..n) (int64, device) in ONE row of a seen bitmap: the prompt's tokens, before the first draw.  Ids outside
  * [0, V) are ignored, duplicates are fine; n == 0 is a no-op.  seen_row NULL, V < 1, n < 0 or ids NULL with n > 0:
  * IVL_ERR_INVALID_ARG. */

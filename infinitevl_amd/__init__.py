@@ -8,6 +8,7 @@ Layout
     cache.py     StaticCachePrealloc & friends (ring-buffer / device-counter redesign)
     modules.py   GatedDeltaNet, InfiniteVLSelfAttention drop-in nn.Modules
     harness.py   decoder stack, hipGraph streaming step, greedy decode, cache clone
+    grammar.py   TokenFsm: token-level state machines for constrained decoding (host side, numpy)
     dist.py      batch-sharded multi-GPU driver (RCCL all-gather of the last-token logits)
 """
 from . import _lib

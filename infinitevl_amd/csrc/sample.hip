@@ -39,6 +39,12 @@
 // Score only (ivl_sample_rows_score_fwd; a fourth form, the three others are compiled without a line of it): a beam search step
 // needs every beam's candidate list and no token.  The form takes the greedy row's path -- pass 1 for the maximum, L1-L3 -- writes
 // the list and stops: no token, counter, seen bit, n_new, done, history or ring; its sampling parameters are not even read.
+//
+// Constrained (ivl_sample_rows_fsm_fwd; a fifth form, the four others are compiled without a line of it): a row in state q >= 0 of
+// a token-level finite state machine IS its allowed sub-vocabulary.  The allowed-token bitmap of q has the layout of `seen` and
+// comes through the same helper, and it is ANDed into the `valid` mask of smp_load: a disallowed token is absent from every pass,
+// exactly as the elements in front of and behind the row are.  Pass 1 counts |A| beside the maximum (it takes V's place in top-k's
+// switch and in the length of the top-N list); the lane that writes the token then advances the state by three dependent loads.
 #include "ivl_common.h"
 
 #include <type_traits>
@@ -172,6 +178,17 @@ __device__ __forceinline__ unsigned smp_load(const SmpRow& r, const SmpPen& pen,
   }
 #pragma unroll
   for (int e = 0; e < 8; ++e) key[e] = smp_key(key[e]);
+  return valid;
+}
+
+// The constrained form: the penalty's view plus the allowed-token bitmap of the row's state, bytes in the layout of `bits`
+// (allow == NULL for a free row, uniform per workgroup).  A disallowed element leaves the mask: no pass ever looks at its key.
+struct SmpPenFsm : SmpPen {
+  const unsigned char* allow;
+};
+__device__ __forceinline__ unsigned smp_load(const SmpRow& r, const SmpPenFsm& pen, long long j, unsigned (&key)[8]) {
+  unsigned valid = smp_load(r, static_cast<const SmpPen&>(pen), j, key);
+  if (pen.allow) valid &= smp_seen_bits(r, pen.allow, j);
   return valid;
 }
 
@@ -316,14 +333,14 @@ __device__ __forceinline__ float smp_lp(unsigned key, unsigned mkey, float xm, f
 }
 
 // Passes L1-L3, by every thread of the workgroup, while `hist`, `sub`, `wsum` and the sh_ words are free; returns lse and leaves
-// the min(n_top, V) survivors in L.cand.  Ends on a barrier.  counted: hist already holds the row's coarse counts (pass 1 made
-// them for top-k, whose scan only read them).
+// the min(n_top, nrow) survivors in L.cand (nrow: the tokens of the row, V or a constrained row's |A|).  Ends on a barrier.
+// counted: hist already holds the row's coarse counts (pass 1 made them for top-k, whose scan only read them).
 template <typename PEN>
-__device__ __forceinline__ float smp_lp_phase(const SmpRow& r, const PEN& pen, unsigned mkey, float xm, int n_top, bool counted, int tid,
+__device__ __forceinline__ float smp_lp_phase(const SmpRow& r, const PEN& pen, int nrow, unsigned mkey, float xm, int n_top, bool counted, int tid,
                                               u64* hist, u64* sub, u64* wsum, unsigned* sh_bin, u64* sh_E, unsigned* sh_key,
                                               SmpLpLds& L) {
   const int lane = tid & 63, wave = tid >> 6;
-  const unsigned nsel = (unsigned)(n_top < r.V ? n_top : r.V);
+  const unsigned nsel = (unsigned)(n_top < nrow ? n_top : nrow);
   const bool count = nsel > 0u && !counted;
   if (nsel > 0u) {
     if (count) {
@@ -494,14 +511,56 @@ __device__ __forceinline__ void smp_lp_after(const SmpLp& lp, const SmpCtl& c, l
   if (lp.cum) lp.cum[s] += (double)v;
 }
 
+// The constraint group of ivl_sample_rows_fsm_fwd
+struct SmpFsm {
+  int* state;
+  const unsigned* mask;
+  long long mask_ld;
+  int n_states;
+  const long long* desc;
+  const int* cls;
+  const int* trans;
+};
+
+// A dead end in front of the draw (F5: no such state, or a state that allows nothing), by every thread of the workgroup: step
+// A's outputs and done = 3; the counter, seen, n_new, the history, the scores' sums and rings and the state stay as they are
+__device__ __forceinline__ void smp_fsm_dead(const SmpCtl& c, const SmpLp& lp, long long s, long long* token, long long token_stride,
+                                             int* n_kept, float* prob) {
+  if (threadIdx.x == 0) {
+    token[s * token_stride] = c.fill ? c.fill[s] : 0ll;
+    if (n_kept) n_kept[s] = 0;
+    if (prob) prob[s] = 0.f;
+    if (lp.logprob) lp.logprob[s] = 0.f;
+    c.done[s] = 3;
+  }
+  if ((int)threadIdx.x < lp.n_top) {
+    lp.top_ids[s * lp.n_top + threadIdx.x] = -1ll;
+    lp.top_lp[s * lp.n_top + threadIdx.x] = -__builtin_inff();
+  }
+}
+
+// F4, by the one lane that wrote the token, behind smp_after: the state advances by the token's class; no transition (-2) is
+// a dead end behind the draw: the token stands, the state stays, done = 3
+__device__ __forceinline__ void smp_fsm_after(const SmpFsm& f, const SmpCtl& c, long long s, int q, long long tok) {
+  if (q < 0) return;
+  const long long trans_off = f.desc[2 * q], cls_off = f.desc[2 * q + 1];
+  const int next = f.trans[trans_off + f.cls[cls_off + tok]];
+  if (next < -1) c.done[s] = 3; else f.state[s] = next;
+}
+
 // CTL: no type (the control-free form, with the parameter list it always had), SmpCtl, SmpCtl and SmpLp, or these two and
-// SmpScore (the score-only form of ivl_sample_rows_score_fwd: steps A, B, L1 and L3, nothing committed)
+// SmpScore (the score-only form of ivl_sample_rows_score_fwd: steps A, B, L1 and L3, nothing committed) or SmpFsm (the
+// constrained form of ivl_sample_rows_fsm_fwd)
 struct SmpScore {};
+template <typename T, typename... U> constexpr bool smp_has = (std::is_same<T, U>::value || ...);
 __device__ __forceinline__ const SmpCtl& smp_first(const SmpCtl& c) { return c; }
 __device__ __forceinline__ const SmpCtl& smp_first(const SmpCtl& c, const SmpLp&) { return c; }
 __device__ __forceinline__ const SmpCtl& smp_first(const SmpCtl& c, const SmpLp&, const SmpScore&) { return c; }
 __device__ __forceinline__ const SmpLp& smp_second(const SmpCtl&, const SmpLp& l) { return l; }
 __device__ __forceinline__ const SmpLp& smp_second(const SmpCtl&, const SmpLp& l, const SmpScore&) { return l; }
+__device__ __forceinline__ const SmpCtl& smp_first(const SmpCtl& c, const SmpLp&, const SmpFsm&) { return c; }
+__device__ __forceinline__ const SmpLp& smp_second(const SmpCtl&, const SmpLp& l, const SmpFsm&) { return l; }
+__device__ __forceinline__ const SmpFsm& smp_third(const SmpCtl&, const SmpLp&, const SmpFsm& f) { return f; }
 
 template <typename... CTL>
 __global__ void __launch_bounds__(SMP_THREADS)
@@ -509,8 +568,11 @@ sample_rows_kernel(const bf16_t* __restrict__ logits, long long ld, int V, const
                    const int* __restrict__ top_k, const float* __restrict__ top_p, const long long* __restrict__ seed,
                    long long* __restrict__ counter, long long* __restrict__ token, long long token_stride,
                    int* __restrict__ n_kept, float* __restrict__ prob, const CTL... ctl_) {
-  constexpr bool kCtl = sizeof...(CTL) >= 1, kLp = sizeof...(CTL) >= 2, kScore = sizeof...(CTL) == 3;
-  typename std::conditional<kCtl, SmpPen, SmpNoPen>::type pen;
+  constexpr bool kCtl = sizeof...(CTL) >= 1, kLp = sizeof...(CTL) >= 2, kScore = smp_has<SmpScore, CTL...>;
+  constexpr bool kFsm = smp_has<SmpFsm, CTL...>;
+  typename std::conditional<kFsm, SmpPenFsm, typename std::conditional<kCtl, SmpPen, SmpNoPen>::type>::type pen;
+  [[maybe_unused]] int fsm_q = -1;                      // the row's state, read once: the lane that advances it writes last
+  [[maybe_unused]] bool lp_on = true;                   // (the constrained form is launched with the score group off, too)
   if constexpr (kCtl) {
     const SmpCtl& ctl = smp_first(ctl_...);
     const long long s = blockIdx.x;
@@ -536,6 +598,17 @@ sample_rows_kernel(const bf16_t* __restrict__ logits, long long ld, int V, const
     pen.bits = pen.r != 1.f ? (const unsigned char*)(ctl.seen + s * ctl.seen_ld) : nullptr;
     pen.inv = __fdiv_rn(1.f, pen.r);
     pen.fast = ((__float_as_uint(pen.r) >> 23) & 0x1FFu) - 107u <= 40u;      // positive, exponent -20 .. 20
+    if constexpr (kFsm) {
+      const SmpFsm& f = smp_third(ctl_...);
+      const SmpLp& lp = smp_second(ctl_...);
+      lp_on = lp.logprob || lp.n_top > 0 || lp.cum || lp.lp_hist;
+      fsm_q = f.state[s];
+      if (fsm_q >= f.n_states) {                        // no such state: a dead end, before a word of the tables is read
+        smp_fsm_dead(ctl, lp, s, token, token_stride, n_kept, prob);
+        return;
+      }
+      pen.allow = fsm_q >= 0 ? (const unsigned char*)(f.mask + (long long)fsm_q * f.mask_ld) : nullptr;
+    }
   }
   __shared__ u64 hist[SMP_BINS];
   __shared__ u64 sub[SMP_SUB];
@@ -561,10 +634,10 @@ sample_rows_kernel(const bf16_t* __restrict__ logits, long long ld, int V, const
   int k = 0;                                            // row's path to the scores and writes no token
   if constexpr (!kScore) { tau = temperature[s]; k = top_k[s]; p = top_p[s]; }
   const bool greedy = !(tau > 0.f);
-  const bool use_k = !greedy && k > 0 && k < V;
+  const bool count_k = !greedy && k > 0 && k < V;      // pass 1 counts for top-k (a constrained row may still turn it off: k >= |A|)
   const bool use_p = !greedy && p < 1.f;
 
-  if (use_k) {
+  if (count_k) {
 #pragma unroll
     for (int i = 0; i < SMP_BINS / SMP_THREADS; ++i) hist[tid + i * SMP_THREADS] = 0ull;
     __syncthreads();
@@ -573,14 +646,16 @@ sample_rows_kernel(const bf16_t* __restrict__ logits, long long ld, int V, const
   // ---- pass 1: the maximum and its lowest index; coarse counts for top-k
   unsigned bkey = 0u, bidx = 0u;
   bool got = false;
+  [[maybe_unused]] unsigned na = 0u;                    // the constrained form: this thread's share of |A|
   for (long long j0 = (long long)wave * 64; j0 < r.nt; j0 += SMP_THREADS) {
     const long long j = j0 + lane;
     unsigned key[8] = {}, valid = 0u;
     if (j < r.nt) valid = smp_load(r, pen, j, key);
+    if constexpr (kFsm) na += (unsigned)__popc(valid);
 #pragma unroll
     for (int e = 0; e < 8; ++e)
       if ((valid >> e & 1u) && (!got || key[e] > bkey)) { bkey = key[e]; bidx = (unsigned)(j * 8 - r.off + e); got = true; }
-    if (use_k) {
+    if (count_k) {
       unsigned bin[8];
       u64 val[8];
 #pragma unroll
@@ -593,17 +668,33 @@ sample_rows_kernel(const bf16_t* __restrict__ logits, long long ld, int V, const
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) { const u64 t = __shfl_xor(best, o, 64); best = t > best ? t : best; }
   if (lane == 0) wbest[wave] = best;
+  if constexpr (kFsm) {
+    na = (unsigned)smp_wave_sum((u64)na);
+    if (lane == 0) wcnt[wave] = na;                     // (pass 5 writes wcnt again, behind barriers)
+  }
   __syncthreads();
   best = 0ull;
 #pragma unroll
   for (int w = 0; w < SMP_WAVES; ++w) best = wbest[w] > best ? wbest[w] : best;
   const unsigned mkey = (unsigned)(best >> 32) - 1u;
   const unsigned midx = 0xFFFFFFFFu - (unsigned)(best & 0xFFFFFFFFull);
+  int nrow = V;                                         // the tokens of the row: V, or |A| of a constrained row
+  if constexpr (kFsm) {
+    nrow = 0;
+#pragma unroll
+    for (int w = 0; w < SMP_WAVES; ++w) nrow += (int)wcnt[w];
+    if (nrow == 0) {                                    // the state allows nothing (uniform: every thread sums the same words)
+      smp_fsm_dead(smp_first(ctl_...), smp_second(ctl_...), s, token, token_stride, n_kept, prob);
+      return;
+    }
+  }
+  const bool use_k = count_k && k < nrow;
 
   if (greedy) {
     if constexpr (kLp)
-      lse = smp_lp_phase(r, pen, mkey, smp_key_value(mkey), smp_second(ctl_...).n_top, false, tid, hist, sub, wsum, &sh_bin, &sh_E,
-                         &sh_key, lpl);
+      if (lp_on)
+        lse = smp_lp_phase(r, pen, nrow, mkey, smp_key_value(mkey), smp_second(ctl_...).n_top, false, tid, hist, sub, wsum, &sh_bin,
+                           &sh_E, &sh_key, lpl);
     if (tid == 0) {
       if constexpr (!kScore) {
         token[s * token_stride] = (long long)midx;
@@ -611,8 +702,9 @@ sample_rows_kernel(const bf16_t* __restrict__ logits, long long ld, int V, const
         if (prob) prob[s] = 1.f;
       }
       if constexpr (kLp)
-        smp_lp_after(smp_second(ctl_...), smp_first(ctl_...), s, V, mkey, mkey, smp_key_value(mkey), lse, lpl);
+        smp_lp_after(smp_second(ctl_...), smp_first(ctl_...), s, nrow, mkey, mkey, smp_key_value(mkey), lse, lpl);
       if constexpr (kCtl && !kScore) smp_after(smp_first(ctl_...), s, (long long)midx);
+      if constexpr (kFsm) smp_fsm_after(smp_third(ctl_...), smp_first(ctl_...), s, fsm_q, (long long)midx);
     }
     return;
   }
@@ -653,7 +745,9 @@ sample_rows_kernel(const bf16_t* __restrict__ logits, long long ld, int V, const
     __syncthreads();
   }
   if constexpr (kLp)                             // hist is free here: top-k has read its counts, top-p has not begun
-    lse = smp_lp_phase(r, pen, mkey, xm, smp_second(ctl_...).n_top, use_k, tid, hist, sub, wsum, &sh_bin, &sh_E, &sh_key, lpl);
+    if (lp_on)
+      lse = smp_lp_phase(r, pen, nrow, mkey, xm, smp_second(ctl_...).n_top, count_k, tid, hist, sub, wsum, &sh_bin, &sh_E, &sh_key,
+                         lpl);
 
   // ---- top-p: keep a class while the mass strictly above it is below p Z_K
   unsigned tp = 0u;
@@ -795,9 +889,10 @@ sample_rows_kernel(const bf16_t* __restrict__ logits, long long ld, int V, const
           unsigned ke = key[0];
 #pragma unroll
           for (int i = 1; i < 8; ++i) if (e == i) ke = key[i];
-          smp_lp_after(smp_second(ctl_...), smp_first(ctl_...), s, V, ke, mkey, xm, lse, lpl);
+          smp_lp_after(smp_second(ctl_...), smp_first(ctl_...), s, nrow, ke, mkey, xm, lse, lpl);
         }
         if constexpr (kCtl) smp_after(smp_first(ctl_...), s, j * 8 - r.off + e);
+        if constexpr (kFsm) smp_fsm_after(smp_third(ctl_...), smp_first(ctl_...), s, fsm_q, j * 8 - r.off + e);
       }
       return;
     }
@@ -835,6 +930,18 @@ static int sample_rows_ctl_check(const char* fn, int V, const float* rep_penalty
   IVL_REQUIRE(!budget || (n_new && done), IVL_ERR_INVALID_ARG, "%s: budget needs n_new and done", fn);
   IVL_REQUIRE(!history || (n_new && hist_ld >= 1), IVL_ERR_INVALID_ARG, "%s: history needs n_new and hist_ld >= 1 (%lld)", fn,
               (long long)hist_ld);
+  return IVL_OK;
+}
+
+static int sample_rows_lp_check(const char* fn, const int64_t* n_new, int64_t hist_ld, int n_top, const int64_t* top_ids,
+                                const float* top_logprobs, const float* lp_history, const int64_t* top_hist_ids,
+                                const float* top_hist_lp) {
+  using ivl::SMP_TOP_MAX;
+  IVL_REQUIRE(n_top >= 0 && n_top <= SMP_TOP_MAX, IVL_ERR_INVALID_ARG, "%s: n_top=%d outside 0..%d", fn, n_top, SMP_TOP_MAX);
+  IVL_REQUIRE(n_top == 0 || (top_ids && top_logprobs), IVL_ERR_INVALID_ARG, "%s: n_top=%d needs top_ids and top_logprobs", fn, n_top);
+  IVL_REQUIRE(!(top_hist_ids || top_hist_lp) || n_top > 0, IVL_ERR_INVALID_ARG, "%s: the top rings need n_top > 0", fn);
+  IVL_REQUIRE(!(lp_history || top_hist_ids || top_hist_lp) || (n_new && hist_ld >= 1), IVL_ERR_INVALID_ARG,
+              "%s: lp_history and the top rings need n_new and hist_ld >= 1 (%lld)", fn, (long long)hist_ld);
   return IVL_OK;
 }
 
@@ -890,6 +997,20 @@ extern "C" int ivl_sample_rows_ctl_fwd(const void* logits, int64_t ld, int S, in
   return check_launch(fn);
 }
 
+static ivl::SmpLp sample_rows_lp(float* logprob, int n_top, int64_t* top_ids, float* top_logprobs, double* cum_logprob,
+                                 float* lp_history, int64_t* top_hist_ids, float* top_hist_lp) {
+  ivl::SmpLp l;
+  l.logprob = logprob;
+  l.n_top = n_top;
+  l.top_ids = (long long*)top_ids;
+  l.top_lp = top_logprobs;
+  l.cum = cum_logprob;
+  l.lp_hist = lp_history;
+  l.top_hist_ids = (long long*)top_hist_ids;
+  l.top_hist_lp = top_hist_lp;
+  return l;
+}
+
 extern "C" int ivl_sample_rows_lp_fwd(const void* logits, int64_t ld, int S, int V, const float* temperature,
                                       const int32_t* top_k, const float* top_p, const int64_t* seed, int64_t* counter,
                                       int64_t* token, int64_t token_stride, int32_t* n_kept, float* prob,
@@ -904,28 +1025,63 @@ extern "C" int ivl_sample_rows_lp_fwd(const void* logits, int64_t ld, int S, int
   if (rc != IVL_OK) return rc;
   rc = sample_rows_ctl_check(fn, V, rep_penalty, seen, seen_ld, stop_ids, n_stop, budget, n_new, done, history, hist_ld);
   if (rc != IVL_OK) return rc;
-  IVL_REQUIRE(n_top >= 0 && n_top <= SMP_TOP_MAX, IVL_ERR_INVALID_ARG, "%s: n_top=%d outside 0..%d", fn, n_top, SMP_TOP_MAX);
-  IVL_REQUIRE(n_top == 0 || (top_ids && top_logprobs), IVL_ERR_INVALID_ARG, "%s: n_top=%d needs top_ids and top_logprobs", fn, n_top);
-  IVL_REQUIRE(!(top_hist_ids || top_hist_lp) || n_top > 0, IVL_ERR_INVALID_ARG, "%s: the top rings need n_top > 0", fn);
-  IVL_REQUIRE(!(lp_history || top_hist_ids || top_hist_lp) || (n_new && hist_ld >= 1), IVL_ERR_INVALID_ARG,
-              "%s: lp_history and the top rings need n_new and hist_ld >= 1 (%lld)", fn, (long long)hist_ld);
+  rc = sample_rows_lp_check(fn, n_new, hist_ld, n_top, top_ids, top_logprobs, lp_history, top_hist_ids, top_hist_lp);
+  if (rc != IVL_OK) return rc;
   if (!logprob && n_top == 0 && !top_ids && !top_logprobs && !cum_logprob && !lp_history && !top_hist_ids && !top_hist_lp)
     return ivl_sample_rows_ctl_fwd(logits, ld, S, V, temperature, top_k, top_p, seed, counter, token, token_stride, n_kept, prob,
                                    rep_penalty, seen, seen_ld, stop_ids, n_stop, budget, fill, n_new, done, history, hist_ld,
                                    stream);
   const SmpCtl c = sample_rows_ctl(rep_penalty, seen, seen_ld, stop_ids, n_stop, budget, fill, n_new, done, history, hist_ld);
-  SmpLp l;
-  l.logprob = logprob;
-  l.n_top = n_top;
-  l.top_ids = (long long*)top_ids;
-  l.top_lp = top_logprobs;
-  l.cum = cum_logprob;
-  l.lp_hist = lp_history;
-  l.top_hist_ids = (long long*)top_hist_ids;
-  l.top_hist_lp = top_hist_lp;
+  const SmpLp l = sample_rows_lp(logprob, n_top, top_ids, top_logprobs, cum_logprob, lp_history, top_hist_ids, top_hist_lp);
   hipLaunchKernelGGL((sample_rows_kernel<SmpCtl, SmpLp>), dim3((unsigned)S), dim3(SMP_THREADS), 0, (hipStream_t)stream,
                      (const bf16_t*)logits, (long long)ld, V, temperature, (const int*)top_k, top_p, (const long long*)seed,
                      (long long*)counter, (long long*)token, (long long)token_stride, (int*)n_kept, prob, c, l);
+  return check_launch(fn);
+}
+
+extern "C" int ivl_sample_rows_fsm_fwd(const void* logits, int64_t ld, int S, int V, const float* temperature,
+                                       const int32_t* top_k, const float* top_p, const int64_t* seed, int64_t* counter,
+                                       int64_t* token, int64_t token_stride, int32_t* n_kept, float* prob,
+                                       const float* rep_penalty, uint32_t* seen, int64_t seen_ld, const int64_t* stop_ids,
+                                       int n_stop, const int64_t* budget, const int64_t* fill, int64_t* n_new, int32_t* done,
+                                       int64_t* history, int64_t hist_ld, float* logprob, int n_top, int64_t* top_ids,
+                                       float* top_logprobs, double* cum_logprob, float* lp_history, int64_t* top_hist_ids,
+                                       float* top_hist_lp, int32_t* fsm_state, const uint32_t* fsm_mask, int64_t mask_ld,
+                                       int n_states, const int64_t* fsm_desc, const int32_t* fsm_cls, const int32_t* fsm_trans,
+                                       void* stream) {
+  using namespace ivl;
+  const char* fn = "ivl_sample_rows_fsm_fwd";
+  if (!fsm_state)                                        // the group is off: the scoring call, bit for bit
+    return ivl_sample_rows_lp_fwd(logits, ld, S, V, temperature, top_k, top_p, seed, counter, token, token_stride, n_kept, prob,
+                                  rep_penalty, seen, seen_ld, stop_ids, n_stop, budget, fill, n_new, done, history, hist_ld, logprob,
+                                  n_top, top_ids, top_logprobs, cum_logprob, lp_history, top_hist_ids, top_hist_lp, stream);
+  int rc = sample_rows_check(fn, logits, ld, S, V, temperature, top_k, top_p, seed, counter, token);
+  if (rc != IVL_OK) return rc;
+  rc = sample_rows_ctl_check(fn, V, rep_penalty, seen, seen_ld, stop_ids, n_stop, budget, n_new, done, history, hist_ld);
+  if (rc != IVL_OK) return rc;
+  rc = sample_rows_lp_check(fn, n_new, hist_ld, n_top, top_ids, top_logprobs, lp_history, top_hist_ids, top_hist_lp);
+  if (rc != IVL_OK) return rc;
+  IVL_REQUIRE(fsm_mask, IVL_ERR_INVALID_ARG, "%s: fsm_state needs fsm_mask", fn);
+  IVL_REQUIRE(fsm_desc, IVL_ERR_INVALID_ARG, "%s: fsm_state needs fsm_desc", fn);
+  IVL_REQUIRE(fsm_cls, IVL_ERR_INVALID_ARG, "%s: fsm_state needs fsm_cls", fn);
+  IVL_REQUIRE(fsm_trans, IVL_ERR_INVALID_ARG, "%s: fsm_state needs fsm_trans", fn);
+  IVL_REQUIRE(done, IVL_ERR_INVALID_ARG, "%s: fsm_state needs done (a dead end is reported there)", fn);
+  IVL_REQUIRE(mask_ld * 32 >= (int64_t)V, IVL_ERR_INVALID_ARG, "%s: mask_ld=%lld words hold fewer than V=%d bits", fn,
+              (long long)mask_ld, V);
+  IVL_REQUIRE(n_states >= 1, IVL_ERR_INVALID_ARG, "%s: n_states=%d", fn, n_states);
+  const SmpCtl c = sample_rows_ctl(rep_penalty, seen, seen_ld, stop_ids, n_stop, budget, fill, n_new, done, history, hist_ld);
+  const SmpLp l = sample_rows_lp(logprob, n_top, top_ids, top_logprobs, cum_logprob, lp_history, top_hist_ids, top_hist_lp);
+  SmpFsm f;
+  f.state = fsm_state;
+  f.mask = fsm_mask;
+  f.mask_ld = mask_ld;
+  f.n_states = n_states;
+  f.desc = (const long long*)fsm_desc;
+  f.cls = fsm_cls;
+  f.trans = fsm_trans;
+  hipLaunchKernelGGL((sample_rows_kernel<SmpCtl, SmpLp, SmpFsm>), dim3((unsigned)S), dim3(SMP_THREADS), 0, (hipStream_t)stream,
+                     (const bf16_t*)logits, (long long)ld, V, temperature, (const int*)top_k, top_p, (const long long*)seed,
+                     (long long*)counter, (long long*)token, (long long)token_stride, (int*)n_kept, prob, c, l, f);
   return check_launch(fn);
 }
 

@@ -445,6 +445,7 @@ class _RowField(NamedTuple):
     state: bool = False         # a step changes it (state() saves it); else a parameter
     kw: Optional[str] = None    # the keyword under which ops.sample_tokens takes it; None: positional
     score: bool = False         # ... and only in a sampler built with logprobs
+    grammar: bool = False       # ... and only in a sampler built with grammar_states
 
 
 def _stop_ids(who: str, ids, at_most: Optional[int] = None) -> List[int]:
@@ -500,7 +501,15 @@ class Sampler:
     scoring launch (ivl_sample_rows_lp_fwd) from construction on, so no recapture is involved: `logprob`, `top_ids`,
     `top_logprob` hold the latest step's scores, `cum_logprob` (float64) their sum per row since set(), and with `history`
     logprobs() / top_logprobs() return them token for token beside tokens().  The scored distribution is the one after the
-    repetition penalty and before temperature / top-k / top-p.  None = off: the sampler launches what it always did."""
+    repetition penalty and before temperature / top-k / top-p.  None = off: the sampler launches what it always did.
+
+    Constrained decoding (what HF generate takes as prefix_allowed_tokens_fn, without the token on the host): a sampler built
+    with `grammar_states` > 0 (and vocab_size) owns an ops.FsmTables arena of that many states and one more per-row tensor,
+    `fsm_state` (-1 = unconstrained), and uses the constrained launch (ivl_sample_rows_fsm_fwd) from construction on, so no
+    recapture is involved: load_grammar() puts a grammar.TokenFsm into the arena, set_grammar() points a row at it, and the
+    kernel restricts the row's draw to the tokens its state allows and advances the state with the token it emits.  A grammar
+    loaded and set between two replays of a captured step is obeyed by the next one.  A row whose state allows nothing ends with
+    done code 3.  Fork and state() follow the table: a forked row continues from its parent's grammar state."""
 
     # THE list of the per-row tensors: each is an attribute of its name, [n_rows, *shape], or None when the sampler does not hold
     # it.  row_tensors() (so every fork and beam gather), state() / load_state(), what set() clears and the keywords of
@@ -526,11 +535,15 @@ class Sampler:
         _RowField("lp_history", torch.float32, ("ring",), 0.0, state=True, kw="lp_history", score=True),
         _RowField("top_hist_ids", torch.int64, ("ring", "top"), -1, state=True, kw="top_hist_ids", score=True),
         _RowField("top_hist_lp", torch.float32, ("ring", "top"), -math.inf, state=True, kw="top_hist_lp", score=True),
+        _RowField("fsm_state", torch.int32, (), -1, state=True, kw="fsm_state", grammar=True),      # -1 = unconstrained
     )
 
     def __init__(self, n_rows: int, device, vocab_size: Optional[int] = None, max_stop: int = 8, history: int = 0,
-                 logprobs: Optional[int] = None, *, score_rings: bool = True):
-        """score_rings=False: no per-token score rings (lp_history, top_hist_ids, top_hist_lp) beside the token history."""
+                 logprobs: Optional[int] = None, *, score_rings: bool = True, grammar_states: int = 0,
+                 grammar_slots: Optional[int] = None, grammar_trans: Optional[int] = None):
+        """score_rings=False: no per-token score rings (lp_history, top_hist_ids, top_hist_lp) beside the token history.
+        grammar_states: the states of all grammars loaded at a time; grammar_slots: how many grammars (default: one per row);
+        grammar_trans: their transition entries, n_states x n_classes each (default: 256 per state)."""
         if n_rows < 1:
             raise ValueError(f"Sampler: n_rows must be >= 1; got {n_rows}")
         if vocab_size is not None and (isinstance(vocab_size, bool) or not isinstance(vocab_size, int) or vocab_size < 1):
@@ -541,15 +554,24 @@ class Sampler:
             raise ValueError(f"Sampler: history must be an int >= 0; got {history!r}")
         if logprobs is not None and (isinstance(logprobs, bool) or not isinstance(logprobs, int) or not 0 <= logprobs <= 20):
             raise ValueError(f"Sampler: logprobs must be None or an int in [0, 20]; got {logprobs!r}")
+        if isinstance(grammar_states, bool) or not isinstance(grammar_states, int) or grammar_states < 0:
+            raise ValueError(f"Sampler: grammar_states must be an int >= 0; got {grammar_states!r}")
+        if grammar_states == 0 and (grammar_slots is not None or grammar_trans is not None):
+            raise ValueError("Sampler: grammar_slots and grammar_trans need grammar_states > 0")
+        if grammar_states > 0 and vocab_size is None:
+            raise ValueError("Sampler: grammar_states needs vocab_size (the allowed-token bitmaps)")
         self.n_rows = int(n_rows)
+        # the arena of the grammars' tables (its own checks refuse what is left of the three sizes)
+        self.grammars = ops.FsmTables(device, vocab_size, grammar_states, n_rows if grammar_slots is None else grammar_slots,
+                                      256 * grammar_states if grammar_trans is None else grammar_trans) if grammar_states else None
         self.vocab_size, self.max_stop, self.history_len, self.n_logprobs = vocab_size, max_stop, history, logprobs
-        self.controlled = vocab_size is not None or history > 0 or logprobs is not None
+        self.controlled = vocab_size is not None or history > 0 or logprobs is not None      # (a grammar needs vocab_size)
         extent = {"words": (vocab_size + 31) // 32 if vocab_size is not None else 0, "max_stop": max_stop, "history": history,
                   "top": logprobs or 0, "ring": history if score_rings else 0}
         self._fields = []                                # the entries of _TABLE this sampler holds, in the table's order
         for f in self._TABLE:
             shape = [extent[e] for e in f.shape]
-            held = all(shape) and (logprobs is not None or not f.score)
+            held = all(shape) and (logprobs is not None or not f.score) and (self.grammars is not None or not f.grammar)
             setattr(self, f.name, torch.full((n_rows, *shape), f.init, dtype=f.dtype, device=device) if held else None)
             if held:
                 self._fields.append(f)
@@ -686,6 +708,47 @@ class Sampler:
             raise ValueError(f"Sampler.mark: ids must be int64 [T] or [1,T]; got {ids.dtype} {tuple(ids.shape)}")
         ops.mark_tokens(self.seen[row], ids, self.vocab_size)
 
+    # ---- constrained decoding ------------------------------------------------------------------------------------------------
+    def _arena(self, who: str) -> "ops.FsmTables":
+        if self.grammars is None:
+            raise ValueError(f"Sampler.{who}: needs a Sampler built with grammar_states > 0")
+        return self.grammars
+
+    def load_grammar(self, fsm) -> "ops.FsmHandle":
+        """Puts a grammar.TokenFsm into the sampler's arena (between replays: no recapture); ValueError when it is full."""
+        return self._arena("load_grammar").load(fsm)
+
+    def unload_grammar(self, handle: "ops.FsmHandle") -> None:
+        """Frees the grammar's room.  A row still in one of its states meets a dead end (done code 3) at its next draw."""
+        self._arena("unload_grammar").unload(handle)
+
+    def set_grammar(self, row: int, handle: Optional["ops.FsmHandle"], state: Optional[int] = None) -> None:
+        """`row` continues under the grammar `handle`, from its start state or from the local `state`; None: unconstrained.
+        Call it after set(), which clears the row to unconstrained."""
+        row, arena = self._row(row), self._arena("set_grammar")
+        if handle is None:
+            if state is not None:
+                raise ValueError("Sampler.set_grammar: a state needs a grammar")
+            self.fsm_state[row] = -1
+            return
+        if handle not in arena.handles():
+            raise ValueError(f"Sampler.set_grammar: {handle!r} is not loaded in this sampler")
+        local = handle.start if state is None else state
+        if isinstance(local, bool) or not isinstance(local, int) or not 0 <= local < handle.n_states:
+            raise ValueError(f"Sampler.set_grammar: state must be in [0, {handle.n_states}); got {state!r}")
+        self.fsm_state[row] = handle.base + local
+
+    def grammar_state(self, row: int) -> Optional[int]:
+        """The row's state, local to its grammar (host; it waits for the steps queued so far); None: the row is unconstrained."""
+        row, arena = self._row(row), self._arena("grammar_state")
+        g = int(self.fsm_state[row].item())
+        if g < 0:
+            return None
+        found = arena.local(g)
+        if found is None:
+            raise ValueError(f"Sampler.grammar_state: row {row} is in state {g}, which no loaded grammar owns")
+        return found[1]
+
     def _stateful(self):
         return {f.name: getattr(self, f.name) for f in self._fields if f.state}
 
@@ -702,7 +765,8 @@ class Sampler:
             t.copy_(state[k])
 
     def poll(self) -> Tuple[torch.Tensor, torch.Tensor]:
-        """(done, n_new) of every row on the host, int64 [n_rows] each, in one copy (it waits for the steps queued so far)."""
+        """(done, n_new) of every row on the host, int64 [n_rows] each, in one copy (it waits for the steps queued so far).
+        done: 0 running, 1 stop id, 2 budget, 3 a dead end of the row's grammar."""
         both = torch.stack([self.done.to(torch.int64), self.n_new]).cpu()
         return both[0], both[1]
 
@@ -742,6 +806,8 @@ class Sampler:
             kw = {f.kw: getattr(self, f.name)[sl] for f in self._fields if f.kw is not None}
             if self.seen is None:
                 del kw["rep_penalty"]                    # the penalty reads the bitmap: without one the launch takes neither
+            if self.grammars is not None:
+                kw["fsm"] = self.grammars
         return ops.sample_tokens(logits, self.temperature[sl], self.top_k[sl], self.top_p[sl], self.seed[sl], self.counter[sl],
                                  out=out, **kw)
 
@@ -818,20 +884,24 @@ class GraphedMultiStreamDecode(_Graphed):
 
     @torch.no_grad()
     def admit(self, slot: int, inputs_embeds: torch.Tensor, position_ids: Optional[torch.Tensor] = None,
-              sampling: Optional[dict] = None, prompt_ids: Optional[torch.Tensor] = None) -> torch.Tensor:
+              sampling: Optional[dict] = None, prompt_ids: Optional[torch.Tensor] = None, grammar=None) -> torch.Tensor:
         """Start a stream in `slot` with a prompt inputs_embeds [1,T,hidden] (M-RoPE position_ids [3,1,T]; default: text
         positions 0..T-1).  Its first generated token is written to token[slot] and returned.  `sampling`: the keyword
         arguments of Sampler.set for this stream (needs a sampler), applied before that first token is drawn.  `prompt_ids`
         (int64 [T] or [1,T]): the prompt's tokens, marked as seen for the repetition penalty after the row is set and before the
         first token is drawn; that token goes through the same controlled launch as every later one, so it is counted, logged
-        and may already end the stream."""
+        and may already end the stream.  `grammar` (a handle of Sampler.load_grammar): the stream starts in the grammar's start
+        state, set after the row's parameters and before the first draw, so the first token is constrained too."""
         if sampling is not None and self.sampler is None:
             raise ValueError("admit: sampling parameters need a GraphedMultiStreamDecode built with a sampler")
+        self._check_grammar("admit", grammar)
         T = self._check_prompt("admit", inputs_embeds, position_ids, prompt_ids)
         if position_ids is None:
             position_ids = _text_positions(T, inputs_embeds.device)
         if sampling is not None:
             self.sampler.set(slot, **sampling)
+        if grammar is not None:
+            self.sampler.set_grammar(slot, grammar)
         if prompt_ids is not None:
             self.sampler.mark(slot, prompt_ids.to(inputs_embeds.device))
         self.cache.admit(slot)
@@ -859,6 +929,12 @@ class GraphedMultiStreamDecode(_Graphed):
             self.token[slot].copy_(lg[0, -1].argmax(-1, keepdim=True))
         else:
             self.sampler.sample(lg[:, -1], self.token[slot:slot + 1], row=slot)
+
+    def _check_grammar(self, who: str, grammar) -> None:
+        if grammar is not None and (self.sampler is None or self.sampler.grammars is None):
+            raise ValueError(f"{who}: a grammar needs a GraphedMultiStreamDecode whose sampler was built with grammar_states")
+        if grammar is not None and grammar not in self.sampler.grammars.handles():
+            raise ValueError(f"{who}: {grammar!r} is not loaded in the sampler (Sampler.load_grammar)")
 
     def _check_prompt(self, who: str, inputs_embeds, position_ids, prompt_ids) -> int:
         if prompt_ids is not None and self.sampler is None:
@@ -920,15 +996,19 @@ class GraphedMultiStreamDecode(_Graphed):
 
     @torch.no_grad()
     def extend(self, slot: int, inputs_embeds: torch.Tensor, position_ids: Optional[torch.Tensor] = None,
-               prompt_ids: Optional[torch.Tensor] = None) -> torch.Tensor:
+               prompt_ids: Optional[torch.Tensor] = None, grammar=None) -> torch.Tensor:
         """Continue the live slot `slot` with more prompt tokens inputs_embeds [1,T,hidden] -- a question, the next video
         frame -- on its B = 1 view.  position_ids [3,1,T]; default: each of the slot's three positions counts on from
         position_ids[:, slot].  The slot's next token is drawn from the last logits (in the sampler's launch, after
-        `prompt_ids` were marked as seen) and REPLACES the pending one, which was never fed to the model.  admit_logits is set."""
+        `prompt_ids` were marked as seen) and REPLACES the pending one, which was never fed to the model.  admit_logits is set.
+        `grammar`: the slot goes to that grammar's start state before the draw (default: it stays in the state it is in)."""
         slot = self._slots("extend", [slot])[0]
         if slot not in self._live:
             raise ValueError(f"extend: slot {slot} holds no stream (admit or load it first)")
+        self._check_grammar("extend", grammar)
         T = self._check_prompt("extend", inputs_embeds, position_ids, prompt_ids)
+        if grammar is not None:
+            self.sampler.set_grammar(slot, grammar)
         if position_ids is None:
             position_ids = self.position_ids[:, slot:slot + 1] + torch.arange(T, device=self.position_ids.device, dtype=torch.int64)
         if prompt_ids is not None:
@@ -941,13 +1021,14 @@ class GraphedMultiStreamDecode(_Graphed):
 
     @torch.no_grad()
     def admit_n(self, slots, inputs_embeds: torch.Tensor, position_ids: Optional[torch.Tensor] = None,
-                sampling=None, prompt_ids: Optional[torch.Tensor] = None) -> torch.Tensor:
+                sampling=None, prompt_ids: Optional[torch.Tensor] = None, grammar=None) -> torch.Tensor:
         """Several answers to one prompt (num_return_sequences of the reference's api/chat.py:164): the prompt is prefilled
         ONCE, into slots[0]; its cache and sampler rows are forked to slots[1:] before any token is drawn; then every slot
         draws its own first token from the same logits, in its own sampler row.  `sampling`: one dict of Sampler.set
         keyword arguments per slot (e.g. one seed each); every slot ends up as admit(slot, ..., sampling=that dict,
-        prompt_ids=prompt_ids) would leave it.  Returns token[slots]."""
+        prompt_ids=prompt_ids) would leave it.  `grammar`: every slot starts in that grammar's start state.  Returns token[slots]."""
         slots = self._slots("admit_n", slots)
+        self._check_grammar("admit_n", grammar)
         if sampling is not None and self.sampler is None:
             raise ValueError("admit_n: sampling parameters need a GraphedMultiStreamDecode built with a sampler")
         T = self._check_prompt("admit_n", inputs_embeds, position_ids, prompt_ids)
@@ -960,6 +1041,8 @@ class GraphedMultiStreamDecode(_Graphed):
         first, rest = slots[0], slots[1:]
         if sampling is not None:
             self.sampler.set(first, **sampling[0])
+        if grammar is not None:
+            self.sampler.set_grammar(first, grammar)    # (it travels to the other slots with the row)
         if prompt_ids is not None:
             self.sampler.mark(first, prompt_ids.to(inputs_embeds.device))
         self.cache.admit(first)
@@ -979,13 +1062,16 @@ class GraphedMultiStreamDecode(_Graphed):
         return self.token[slots]
 
     @torch.no_grad()
-    def load(self, slots, cache: StaticCachePrealloc, row: int = 0, next_position: Optional[int] = None, sampling=None) -> None:
+    def load(self, slots, cache: StaticCachePrealloc, row: int = 0, next_position: Optional[int] = None, sampling=None,
+             grammar=None) -> None:
         """The demo's branch (demo:363-365) on the serving path: the state of row `row` of an external cache -- the B = 1
         StaticCachePrealloc of a running video stream -- goes into `slots` in one launch, and they become live.  The source is
         only read, so questions never pollute the video's history.  Each slot's three M-RoPE positions are set to
         `next_position` (default: the source's length); `sampling`: one dict of Sampler.set keyword arguments per slot, applied
-        as in admit.  No token is pending afterwards: extend(slot, question) follows."""
+        as in admit; `grammar`: every slot is put into that grammar's start state, for the draw of the extend that follows.
+        No token is pending afterwards: extend(slot, question) follows."""
         slots = self._slots("load", slots)
+        self._check_grammar("load", grammar)
         if sampling is not None:
             if self.sampler is None:
                 raise ValueError("load: sampling parameters need a GraphedMultiStreamDecode built with a sampler")
@@ -998,6 +1084,8 @@ class GraphedMultiStreamDecode(_Graphed):
         for i, s in enumerate(slots):
             if sampling is not None:
                 self.sampler.set(s, **sampling[i])
+            if grammar is not None:
+                self.sampler.set_grammar(s, grammar)
             self.token[s].zero_()
             self.position_ids[:, s].fill_(next_position)
             self._live.add(s)
@@ -1059,7 +1147,12 @@ class GraphedBeamDecode(GraphedMultiStreamDecode):
     ivl_beam_select_fwd in include/ivl_hip.h states the semantics and the differences from HF."""
 
     def __init__(self, model: InfiniteVLTextStack, cache: MultiStreamCache, num_beams: int, vocab_size: int, history: int,
-                 max_stop: int = 1, warmup: int = 2):
+                 max_stop: int = 1, warmup: int = 2, sampler: Optional["Sampler"] = None):
+        """sampler: the slots' sampler, where the caller wants to keep it (default: built here); it must be what this class
+        builds -- n_slots rows, vocab_size, max_stop 0, history, logprobs = K, no score rings -- and hold no grammars."""
+        if sampler is not None and sampler.grammars is not None:
+            raise ValueError("GraphedBeamDecode: the sampler was built with grammar_states: constrained beam search is not "
+                             "supported (a beam's candidates come from the score-only launch, which reads no grammar)")
         if isinstance(num_beams, bool) or not isinstance(num_beams, int) or not 1 <= num_beams <= 8:
             raise ValueError(f"GraphedBeamDecode: num_beams must be an int in [1, 8]; got {num_beams!r}")
         if cache.n_slots % num_beams:
@@ -1070,8 +1163,13 @@ class GraphedBeamDecode(GraphedMultiStreamDecode):
             raise ValueError(f"GraphedBeamDecode: max_stop must be an int in [0, 16]; got {max_stop!r}")
         K = ops.beam_width(num_beams, max_stop)          # refuses K > 20
         device = next(model.parameters()).device
-        sampler = Sampler(cache.n_slots, device, vocab_size=vocab_size, max_stop=0, history=history, logprobs=K,
-                          score_rings=False)                                        # a beam keeps tokens, not per-token scores
+        if sampler is None:
+            sampler = Sampler(cache.n_slots, device, vocab_size=vocab_size, max_stop=0, history=history, logprobs=K,
+                              score_rings=False)                                    # a beam keeps tokens, not per-token scores
+        elif (sampler.n_rows, sampler.vocab_size, sampler.max_stop, sampler.history_len, sampler.n_logprobs,
+              sampler.lp_history is None) != (cache.n_slots, vocab_size, 0, history, K, True):
+            raise ValueError(f"GraphedBeamDecode: the sampler must be Sampler({cache.n_slots}, device, vocab_size={vocab_size}, "
+                             f"max_stop=0, history={history}, logprobs={K}, score_rings=False)")
         super().__init__(model, cache, warmup=warmup, sampler=sampler)
         self.B, self.G, self.K, self.L, self.max_stop = num_beams, cache.n_slots // num_beams, K, history, max_stop
         G, B, L = self.G, self.B, self.L

@@ -18,8 +18,9 @@ import ctypes
 import os
 import threading
 import weakref
-from typing import Dict, Optional, Tuple
+from typing import Dict, List, NamedTuple, Optional, Tuple
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -1203,7 +1204,8 @@ def sample_tokens(logits: torch.Tensor, temperature: torch.Tensor, top_k: torch.
                   history: Optional[torch.Tensor] = None, logprob: Optional[torch.Tensor] = None,
                   top_ids: Optional[torch.Tensor] = None, top_logprobs: Optional[torch.Tensor] = None,
                   cum_logprob: Optional[torch.Tensor] = None, lp_history: Optional[torch.Tensor] = None,
-                  top_hist_ids: Optional[torch.Tensor] = None, top_hist_lp: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  top_hist_ids: Optional[torch.Tensor] = None, top_hist_lp: Optional[torch.Tensor] = None,
+                  fsm_state: Optional[torch.Tensor] = None, fsm=None) -> torch.Tensor:
     """One next token per row of lm_head logits [S,V] or [S,1,V] (bf16, last dim contiguous) in one launch: temperature,
     top-k, top-p and the draw, per row (ivl_sample_rows_fwd states the semantics; HF generate's warpers + multinomial,
     api/chat.py:160-162 of the reference).  temperature / top_k / top_p / seed / counter: [S] fp32 / int32 / fp32 / int64 /
@@ -1224,7 +1226,14 @@ def sample_tokens(logits: torch.Tensor, temperature: torch.Tensor, top_k: torch.
     (0 < N <= 20: the N most likely tokens, most likely first, ties to the lowest id; id -1 / -inf past V); cum_logprob [S]
     float64 (the kernel adds logprob to it); and, with n_new, rings at the index of `history`: lp_history [S,H] fp32,
     top_hist_ids [S,H,N] int64 and top_hist_lp [S,H,N] fp32 (the H of `history` when that is given too).  With any of them
-    given the launch is the scoring form; the token and every control's state are those of the call without them."""
+    given the launch is the scoring form; the token and every control's state are those of the call without them.
+
+    The keyword-only constraint (ivl_sample_rows_fsm_fwd states the semantics; HF generate's prefix_allowed_tokens_fn without
+    the token on the host): fsm_state [S] int32, per row a state of the tables `fsm` or -1 = unconstrained, advanced by the
+    kernel with the token it emits; `fsm`: an FsmTables, or any holder of mask int32 [n_states, mask_ld] (mask_ld * 32 >= V),
+    desc int64 [n_states, 2], cls int32 and trans int32 (flat), with mask_ld and n_states.  A row in state q draws from the
+    tokens of q's bitmap alone, and its scores are those of the distribution over them.  Needs `done` (3 = a dead end).  With
+    fsm_state given the launch is the constrained form; the two come together."""
     if logits.dim() == 3 and logits.shape[1] == 1:
         logits = logits[:, 0]
     if logits.dim() != 2 or logits.dtype != torch.bfloat16 or logits.shape[0] < 1 or logits.shape[1] < 1:
@@ -1236,7 +1245,7 @@ def sample_tokens(logits: torch.Tensor, temperature: torch.Tensor, top_k: torch.
                         ("top_p", top_p, torch.float32), ("seed", seed, torch.int64), ("counter", counter, torch.int64),
                         ("n_kept", n_kept, torch.int32), ("prob", prob, torch.float32), ("rep_penalty", rep_penalty, torch.float32),
                         ("budget", budget, torch.int64), ("fill", fill, torch.int64), ("n_new", n_new, torch.int64),
-                        ("done", done, torch.int32), ("logprob", logprob, torch.float32),
+                        ("done", done, torch.int32), ("logprob", logprob, torch.float32), ("fsm_state", fsm_state, torch.int32),
                         ("cum_logprob", cum_logprob, torch.float64)):
         if t is None:
             continue
@@ -1291,19 +1300,39 @@ def sample_tokens(logits: torch.Tensor, temperature: torch.Tensor, top_k: torch.
                                  f"length, at least 1); got {t.dtype} {tuple(t.shape)}")
         if history is not None and any(t is not None for _, t, _, _ in rings) and S > 1 and history.stride(0) != hist_ld:
             raise ValueError("sample_tokens: with lp_history or the top rings, history must be contiguous")
+    tables = ()
+    if (fsm_state is None) != (fsm is None):
+        raise ValueError("sample_tokens: fsm_state and fsm come together")
+    if fsm is not None:
+        if done is None:
+            raise ValueError("sample_tokens: fsm_state needs done (a dead end is reported there)")
+        tables = (fsm.mask, fsm.desc, fsm.cls, fsm.trans)
+        n_states, mask_ld = int(fsm.n_states), int(fsm.mask_ld)
+        for name, t, dt in zip(("mask", "desc", "cls", "trans"), tables, (torch.int32, torch.int64, torch.int32, torch.int32)):
+            if not isinstance(t, torch.Tensor) or t.dtype != dt or not t.is_contiguous():
+                raise ValueError(f"sample_tokens: fsm.{name} must be a contiguous {dt} tensor")
+        if n_states < 1 or tuple(fsm.mask.shape) != (n_states, mask_ld) or tuple(fsm.desc.shape) != (n_states, 2):
+            raise ValueError(f"sample_tokens: fsm.mask must be [n_states, mask_ld] = [{n_states}, {mask_ld}] and fsm.desc "
+                             f"[{n_states}, 2]; got {tuple(fsm.mask.shape)} and {tuple(fsm.desc.shape)}")
+        if mask_ld * 32 < V:
+            raise ValueError(f"sample_tokens: fsm.mask has {mask_ld} words per state for V = {V} (needs {(V + 31) // 32})")
     if out is None:
         out = torch.empty(S, dtype=torch.int64, device=logits.device)
     if out.dtype != torch.int64 or tuple(out.shape) not in ((S,), (S, 1)):
         raise ValueError(f"sample_tokens: out must be int64 [{S}] or [{S},1]; got {out.dtype} {tuple(out.shape)}")
     controls = (rep_penalty, seen, stop_ids, budget, fill, n_new, done, history)
-    _need_gpu(logits, temperature, top_k, top_p, seed, counter, out, n_kept, prob, *controls, *scores)
-    if any(t is not None for t in scores):
-        _lib.check(_lib.load().ivl_sample_rows_lp_fwd(
-            _p(logits), logits.stride(0) if S > 1 else V, S, V, _p(temperature), _p(top_k), _p(top_p), _p(seed), _p(counter),
-            _p(out), out.stride(0) if S > 1 else 1, _p(n_kept), _p(prob), _p(rep_penalty), _p(seen),
-            0 if seen is None else (seen.stride(0) if S > 1 else seen.shape[1]), _p(stop_ids), n_stop, _p(budget), _p(fill),
-            _p(n_new), _p(done), _p(history), hist_ld, _p(logprob), n_top, _p(top_ids), _p(top_logprobs), _p(cum_logprob),
-            _p(lp_history), _p(top_hist_ids), _p(top_hist_lp), _stream(logits)))
+    _need_gpu(logits, temperature, top_k, top_p, seed, counter, out, n_kept, prob, *controls, *scores, fsm_state, *tables)
+    if fsm is not None or any(t is not None for t in scores):
+        args = (_p(logits), logits.stride(0) if S > 1 else V, S, V, _p(temperature), _p(top_k), _p(top_p), _p(seed), _p(counter),
+                _p(out), out.stride(0) if S > 1 else 1, _p(n_kept), _p(prob), _p(rep_penalty), _p(seen),
+                0 if seen is None else (seen.stride(0) if S > 1 else seen.shape[1]), _p(stop_ids), n_stop, _p(budget), _p(fill),
+                _p(n_new), _p(done), _p(history), hist_ld, _p(logprob), n_top, _p(top_ids), _p(top_logprobs), _p(cum_logprob),
+                _p(lp_history), _p(top_hist_ids), _p(top_hist_lp))
+        if fsm is not None:
+            _lib.check(_lib.load().ivl_sample_rows_fsm_fwd(*args, _p(fsm_state), _p(fsm.mask), mask_ld, n_states, _p(fsm.desc),
+                                                           _p(fsm.cls), _p(fsm.trans), _stream(logits)))
+        else:
+            _lib.check(_lib.load().ivl_sample_rows_lp_fwd(*args, _stream(logits)))
         return out
     if all(t is None for t in controls):
         _lib.check(_lib.load().ivl_sample_rows_fwd(
@@ -1316,6 +1345,92 @@ def sample_tokens(logits: torch.Tensor, temperature: torch.Tensor, top_k: torch.
         0 if seen is None else (seen.stride(0) if S > 1 else seen.shape[1]), _p(stop_ids), n_stop, _p(budget), _p(fill), _p(n_new),
         _p(done), _p(history), 0 if history is None else (history.stride(0) if S > 1 else history.shape[1]), _stream(logits)))
     return out
+
+
+class FsmHandle(NamedTuple):
+    """A grammar loaded into an FsmTables: its states are the global states [base, base + n_states), `start` is local."""
+    base: int
+    start: int
+    n_states: int
+    slot: int                   # which of the arena's class tables it holds
+    trans_off: int
+    trans_len: int
+
+
+class FsmTables:
+    """The device tables of ivl_sample_rows_fsm_fwd as ONE arena for several grammars (grammar.TokenFsm), allocated once: room
+    for `states` states in all, `grammars` grammars at a time (one class table of vocab_size entries each) and `trans`
+    transition entries (a grammar takes n_states x n_classes of them).  load() writes a grammar at a free range, its transition
+    targets rebased to global state indices; unload() frees the range and clears its bitmaps, so a row left in one of its
+    states meets a dead end instead of another grammar's tokens.  The tensors never move: a captured step sees a grammar that
+    was loaded after its capture.  mask / desc / cls / trans with mask_ld and n_states are what ops.sample_tokens(fsm=) takes."""
+
+    def __init__(self, device, vocab_size: int, states: int, grammars: int, trans: int, mask_ld: Optional[int] = None):
+        for name, v in (("vocab_size", vocab_size), ("states", states), ("grammars", grammars), ("trans", trans)):
+            if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+                raise ValueError(f"FsmTables: {name} must be an int >= 1; got {v!r}")
+        words = (vocab_size + 31) // 32
+        if mask_ld is not None and (isinstance(mask_ld, bool) or not isinstance(mask_ld, int) or mask_ld < words):
+            raise ValueError(f"FsmTables: mask_ld must be an int >= {words} (the words of vocab_size {vocab_size}); got {mask_ld!r}")
+        self.vocab_size, self.n_states, self.mask_ld = vocab_size, states, words if mask_ld is None else mask_ld
+        self.mask = torch.zeros(states, self.mask_ld, dtype=torch.int32, device=device)
+        self.desc = torch.zeros(states, 2, dtype=torch.int64, device=device)
+        self.cls = torch.zeros(grammars * vocab_size, dtype=torch.int32, device=device)
+        self.trans = torch.full((trans,), -2, dtype=torch.int32, device=device)
+        self._slots: List[Optional[FsmHandle]] = [None] * grammars
+
+    def handles(self) -> List[FsmHandle]:
+        return [h for h in self._slots if h is not None]
+
+    @staticmethod
+    def _first_fit(taken, need: int, room: int) -> Optional[int]:
+        at = 0
+        for a, n in sorted(taken):
+            if a - at >= need:
+                break
+            at = a + n
+        return at if at + need <= room else None
+
+    def load(self, fsm) -> FsmHandle:
+        """Writes `fsm` (a grammar.TokenFsm) into free ranges of the arena and returns its handle.  ValueError: another
+        vocabulary, or no room left (states, grammars or transition entries)."""
+        if fsm.vocab_size != self.vocab_size:
+            raise ValueError(f"FsmTables.load: a grammar over {fsm.vocab_size} tokens for tables of vocab_size {self.vocab_size}")
+        held = self.handles()
+        n, n_trans = fsm.n_states, fsm.n_states * fsm.n_classes
+        base = self._first_fit([(h.base, h.n_states) for h in held], n, self.n_states)
+        off = self._first_fit([(h.trans_off, h.trans_len) for h in held], n_trans, self.trans.shape[0])
+        if None not in self._slots or base is None or off is None:
+            raise ValueError(f"FsmTables.load: the arena is full: {len(held)} of {len(self._slots)} grammars, "
+                             f"{sum(h.n_states for h in held)} of {self.n_states} states and {sum(h.trans_len for h in held)} of "
+                             f"{self.trans.shape[0]} transition entries are taken; this grammar needs {n} states and {n_trans} "
+                             f"entries, each in one piece")
+        slot = self._slots.index(None)
+        dev = self.mask.device
+        t = fsm.trans.astype(np.int32)
+        self.trans[off:off + n_trans] = torch.from_numpy(np.where(t >= 0, t + base, t).astype(np.int32).reshape(-1)).to(dev)
+        self.cls[slot * self.vocab_size:(slot + 1) * self.vocab_size] = torch.from_numpy(fsm.cls.astype(np.int32)).to(dev)
+        desc = np.stack([off + np.arange(n, dtype=np.int64) * fsm.n_classes, np.full(n, slot * self.vocab_size, dtype=np.int64)], 1)
+        self.desc[base:base + n] = torch.from_numpy(desc).to(dev)
+        words = fsm.mask.shape[1]
+        self.mask[base:base + n, :words] = torch.from_numpy(np.ascontiguousarray(fsm.mask).view(np.int32)).to(dev)
+        self._slots[slot] = h = FsmHandle(base, fsm.start, n, slot, off, n_trans)
+        return h
+
+    def unload(self, handle: FsmHandle) -> None:
+        """Frees the grammar's ranges; its states allow nothing from now on."""
+        if handle.slot >= len(self._slots) or self._slots[handle.slot] != handle:
+            raise ValueError(f"FsmTables.unload: {handle!r} is not loaded here")
+        self.mask[handle.base:handle.base + handle.n_states].zero_()
+        self.trans[handle.trans_off:handle.trans_off + handle.trans_len] = -2
+        self._slots[handle.slot] = None
+
+    def local(self, state: int) -> Optional[Tuple[FsmHandle, int]]:
+        """(handle, local state) of a global state, or None where no loaded grammar owns it."""
+        for h in self.handles():
+            if h.base <= state < h.base + h.n_states:
+                return h, state - h.base
+        return None
 
 
 def mark_tokens(seen_row: torch.Tensor, ids: torch.Tensor, vocab_size: int) -> None:

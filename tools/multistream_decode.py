@@ -49,6 +49,16 @@ the model's real row table, 4 rows) for three maps -- the identity, a 4-cycle an
 index_select + copy_ loop on the same map, single calls and calls queued back to back.
 
     python tools/multistream_decode.py --beam [--out profiles/beam_decode.json]
+
+--grammar: the cost of constrained decoding (Sampler(grammar_states=), ivl_sample_rows_fsm_fwd) in the captured 4-slot step.  A:
+the sampled step (0.7 / 50 / 0.9) with logprobs=0, the launch the constrained form extends; B: the same with a 5-label
+grammar.TokenFsm.from_choices grammar on every slot; C: with a 64-state TokenFsm.from_byte_dfa grammar (hh:mm:ss, repeated, over
+a synthetic byte vocabulary of the model's size) on every slot.  Timed A B A C per round.  Every leg restores one int32 per
+slot before each replay (B and C: the slots' start states, so a label grammar never runs out; A: a word nobody reads), so that
+copy cancels in the differences.  Then the operator alone on 4 rows of the model's vocabulary.  No bar is asserted: B - A and
+C - A are reported beside the 2 % of the greedy step the sampling launch is granted as a whole.
+
+    python tools/multistream_decode.py --grammar [--out profiles/grammar_decode.json]
 """
 import argparse
 import json
@@ -73,6 +83,7 @@ def main():
     ap.add_argument("--logprobs", action="store_true", help="time the step with logprobs and top-5 alternatives (see above)")
     ap.add_argument("--fork", action="store_true", help="time the slot fork against the copy_ loop and a re-admission (see above)")
     ap.add_argument("--beam", action="store_true", help="time the beam search step and the row gather (see above)")
+    ap.add_argument("--grammar", action="store_true", help="time the constrained step against the scored one (see above)")
     args = ap.parse_args()
     import torch
     from infinitevl_amd.cache import MultiStreamCache
@@ -109,6 +120,8 @@ def main():
         return fork_legs(args, torch, model, cfg, prompts, dev)
     if args.beam:
         return beam_legs(args, torch, model, cfg, prompts, dev)
+    if args.grammar:
+        return grammar_legs(args, torch, model, cfg, prompts, dev)
 
     # reference: one stream on the existing B = 1 graphed decode step
     c1 = model.allocate_inference_cache(1)
@@ -398,6 +411,112 @@ def logprobs_legs(args, torch, model, cfg, prompts, dev):
                 for s in range(S):
                     smp.set(s, seed=s, **kw)
                 op[f"S{S}_{pname}{fname}_us"] = round(1000 * timed(lambda: smp.sample(lg, tok), 200), 2)
+    res["operator_V%d" % V] = op
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+def timing_grammars(V):
+    """(a 5-label from_choices grammar, a 64-state from_byte_dfa grammar that never ends) over V tokens"""
+    import numpy as np
+    from infinitevl_amd.grammar import TokenFsm
+    labels = [[V // 7, V // 3], [V // 7, V // 5, 11], [V // 2], [V - 2, 3, 3, 9], [1000 % V, 0]]
+    choices = TokenFsm.from_choices(V, labels, stop_token_ids=[V - 1])
+    rng = np.random.default_rng(0)
+    alphabet = np.frombuffer(b"0123456789::,ab ", dtype=np.uint8)
+    vocab = [bytes(rng.choice(alphabet, size=rng.integers(1, 6))) for _ in range(V)]
+    # "dd:dd:dd," is 9 bytes = 9 states; seven copies in a ring and one start state: 64 states, none of them final
+    n = 64
+    bt = np.full((n, 256), -1, dtype=np.int32)
+    step = [b"0123456789", b"0123456789", b":", b"0123456789", b"0123456789", b":", b"0123456789", b"0123456789", b","]
+    bt[0, list(step[0])] = 2
+    for q in range(1, n):
+        bt[q, list(step[(q - 1) % 9])] = q + 1 if q + 1 < n else 1
+    return choices, TokenFsm.from_byte_dfa(vocab, bt, 0, [])
+
+
+def grammar_legs(args, torch, model, cfg, prompts, dev):
+    from infinitevl_amd.cache import MultiStreamCache
+    from infinitevl_amd.harness import GraphedMultiStreamDecode, Sampler
+    stream = torch.cuda.current_stream()
+    V, n = cfg.vocab_size, 4
+
+    def timed(fn, reps):
+        for _ in range(4):
+            fn()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        for _ in range(reps):
+            fn()
+        e1.record(stream)
+        e1.synchronize()
+        return e0.elapsed_time(e1) / reps
+
+    fsms = dict(zip(("choices", "dfa64"), timing_grammars(V)))
+    res = {"tool": "multistream_decode --grammar", "layers": cfg.num_hidden_layers, "window": 4096, "steps": args.steps,
+           "rounds": args.rounds, "slots": n, "sampled": SAMPLED, "baseline": "sampled, logprobs=0, vocab_size (the same build)",
+           "grammars": {k: {"states": f.n_states, "classes": f.n_classes, "allowed_at_start": int(f.allowed(f.start).sum())}
+                        for k, f in fsms.items()},
+           "bar": "none asserted; allowance_us = 2 % of greedy ms_per_step"}
+
+    def restoring(dec, word, value):
+        def fn():
+            word.copy_(value)
+            dec.step()
+        return fn
+
+    legs = {}
+    for name in ("greedy", "scored", "choices", "dfa64"):
+        cache = MultiStreamCache(config=cfg, n_slots=n, device=dev, dtype=torch.bfloat16)
+        smp = None if name == "greedy" else Sampler(n, dev, vocab_size=V, logprobs=0,
+                                                    grammar_states=fsms[name].n_states if name in fsms else 0)
+        dec = GraphedMultiStreamDecode(model, cache, sampler=smp)
+        handle = smp.load_grammar(fsms[name]) if name in fsms else None
+        for s in range(n):
+            dec.admit(s, prompts[s], sampling=None if name == "greedy" else dict(SAMPLED, seed=s + 1), grammar=handle)
+        dec.capture()
+        if name == "greedy":
+            legs[name] = dec.step
+        elif handle is None:
+            legs[name] = restoring(dec, torch.zeros(n, dtype=torch.int32, device=dev), torch.zeros(n, dtype=torch.int32, device=dev))
+        else:
+            legs[name] = restoring(dec, smp.fsm_state, torch.full((n,), handle.base + handle.start, dtype=torch.int32, device=dev))
+    times = {k: [] for k in legs}
+    for _ in range(args.rounds):                                # A B A C, the greedy step once per round
+        times["greedy"].append(timed(legs["greedy"], args.steps))
+        for name in ("choices", "dfa64"):
+            times["scored"].append(timed(legs["scored"], args.steps))
+            times[name].append(timed(legs[name], args.steps))
+    med = {k: statistics.median(v) for k, v in times.items()}
+    res["greedy_ms_per_step"] = round(med["greedy"], 4)
+    res["allowance_us"] = round(1000 * 0.02 * med["greedy"], 1)
+    for name in ("scored", "choices", "dfa64"):
+        res[name] = {"ms_per_step": round(med[name], 4), "spread_ms": [round(min(times[name]), 4), round(max(times[name]), 4)]}
+        if name != "scored":
+            res[name]["minus_scored_us"] = round(1000 * (med[name] - med["scored"]), 1)
+    print(" ".join(f"{k} {v:.4f}" for k, v in med.items()), file=sys.stderr, flush=True)
+    del legs
+    # the operator alone, 4 rows back to back on one stream (launch-bound figures include the launch gap)
+    gen = torch.Generator(device=dev).manual_seed(1)
+    lg = (torch.randn(n, V, generator=gen, device=dev) * 3.0).to(torch.bfloat16)
+    tok = torch.zeros(n, 1, dtype=torch.int64, device=dev)
+    op = {}
+    for name in ("scored", "choices", "dfa64"):
+        smp = Sampler(n, dev, vocab_size=V, logprobs=0, grammar_states=fsms[name].n_states if name in fsms else 0)
+        handle = smp.load_grammar(fsms[name]) if name in fsms else None
+        word = smp.fsm_state if handle else torch.zeros(n, dtype=torch.int32, device=dev)
+        value = torch.full((n,), handle.base + handle.start if handle else 0, dtype=torch.int32, device=dev)
+        for s in range(n):
+            smp.set(s, seed=s, **SAMPLED)
+
+        def fn():
+            word.copy_(value)
+            smp.sample(lg, tok)
+        op[f"S{n}_{name}_us"] = round(1000 * timed(fn, 200), 2)
     res["operator_V%d" % V] = op
     line = json.dumps(res)
     print(line)
