@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define IVL_ABI_VERSION 11
+#define IVL_ABI_VERSION 12
 
 /* The library is built with -fvisibility=hidden: the entry points declared here are its ONLY exported symbols. */
 #define IVL_API __attribute__((visibility("default")))
@@ -426,55 +426,48 @@ IVL_API int ivl_linear_m256_fwd(const void* x, const void* w, const void* bias, 
  * every run, eager or in a replayed graph, whichever row of a larger call the logits sit in.
  * token[s * token_stride] int64 is written; n_kept [S] int32 (= |P|) and prob [S] fp32 (= q_token / Z_P) may be NULL.
  * Any V >= 1 and ld >= V, any alignment (16-byte loads from the boundary at or below each row).  V >= 2^23: IVL_ERR_UNSUPPORTED.
- * ------------------------------------------------------------------------------------------- */
-IVL_API int ivl_sample_rows_fwd(const void* logits, int64_t ld, int S, int V,
-                                const float* temperature, const int32_t* top_k, const float* top_p,
-                                const int64_t* seed, int64_t* counter,
-                                int64_t* token, int64_t token_stride,
-                                int32_t* n_kept, float* prob, void* stream);
-
-/* ---------------------------------------------------------------------------------------------
- * ivl_sample_rows_fwd with the generation controls the reference hands to HF generate beside the sampling arguments
+ *
+ * The call takes ONE struct, ivl_sample_args: the row and the sampling arguments above, then three optional groups and the
+ * score-only switch.  Every field of a group may be NULL / 0 (off).  THE FORM of the launch follows from what is set:
+ *     score_only != 0                                                                          -> the score-only form
+ *     else fsm_state                                                                           -> the constrained form
+ *     else any of logprob, n_top > 0, top_ids, top_logprobs, cum_logprob, lp_history, top_hist_ids, top_hist_lp
+ *                                                                                              -> the scoring form
+ *     else any of rep_penalty, seen, n_stop > 0, budget, n_new, done, history                  -> the controlled form
+ *     else                                                                                     -> the control-free form
+ *   `fill` alone and the scalars (seen_ld, hist_ld, mask_ld, n_states) select nothing.  Turning a group on never changes the
+ *   outputs of the groups below it: with the scores on, token, counter, seen, n_new, done, history, n_kept and prob are bit for bit
+ *   those of the same call without them; a row with fsm_state[s] < 0 behaves as in the call without the constraint group; and with
+ *   every group off the outputs are those of steps 1-6 alone.
+ *
+ * CONTROLS: the generation controls the reference hands to HF generate beside the sampling arguments
  * (src/llamafactory/chat/hf_engine.py:128-156: repetition_penalty, eos_token_id, max_new_tokens), inside the same one launch.
- * Every control group may be NULL (off); with all of them NULL the call IS ivl_sample_rows_fwd, bit for bit.  Per row s, in order:
+ * Per row s, in order:
  *   A finished row.  done[s] != 0 on entry: token = fill[s] (0 when fill == NULL), n_kept = 0, prob = 0, and nothing else of the
  *     row is read or written -- not the counter, seen, n_new or the history; the workgroup returns before its first pass.
  *   B repetition penalty (HF RepetitionPenaltyLogitsProcessor, which runs before the warpers).  seen: a bitmap of uint32 words,
  *     row s at seen + s*seen_ld; bit (i & 31) of word (i >> 5) = token i has occurred.  For a seen token and
  *     r = rep_penalty[s] != 1:   x' = bf16_rne(x < 0 ? x * r : x / r),
  *     fp32 arithmetic on the widened bf16 value, a true IEEE division, one rounding to bf16.  NaN stays NaN (= -inf), +-inf stay,
- *     -0 stays in the class of +0.  Unseen tokens and rows with r == 1 (or rep_penalty == NULL) use x unchanged.  Steps 1-6 of
- *     ivl_sample_rows_fwd then run on x' (the greedy arg-max is that of x'); because x' is a bf16 value again, the histograms,
+ *     -0 stays in the class of +0.  Unseen tokens and rows with r == 1 (or rep_penalty == NULL) use x unchanged.  Steps 1-6
+ *     then run on x' (the greedy arg-max is that of x'); because x' is a bf16 value again, the histograms,
  *     the integer weights and the bit-reproducible draw are what they are for any other row.  HF keeps the penalised logit in
  *     fp32; here it is rounded to bf16: half a bf16 ulp, at most 2^-8 relative, on a penalised logit.
  *   C bookkeeping after the draw, by the one lane that writes the token:
  *       seen != NULL: the token's bit is set (also at r == 1);
- *       history != NULL: history[s*hist_ld + n_new[s] % hist_ld] = token  (int64; a ring of the last hist_ld tokens);
+ *       history != NULL: history[s*hist_ld + n_new[s] % hist_ld] = token  (int64; a ring of the last hist_ld tokens: hist_ld is
+ *         both the ring's length and its row pitch);
  *       n_new != NULL: n_new[s] += 1;
  *       done[s] = 1 if the token equals any of stop_ids[s*n_stop .. +n_stop) (int64; entries < 0 are unused);
  *       else done[s] = 2 if budget[s] >= 0 and n_new[s] >= budget[s] (after the increment).  A stop id wins over the budget.
  *   D bounds.  Bits at or above V in a row's last word, the words between ceil(V/32) and seen_ld and other rows are never
  *     modified and never influence a result; nothing outside a row's seen_ld words is read.
- * done codes: 0 running, 1 ended on a stop id, 2 ended on its budget; the host clears done[s] to restart a row.
- * IVL_ERR_INVALID_ARG (before anything is launched): rep_penalty without seen; seen with seen_ld*32 < V; n_stop outside 0..16;
- * n_stop > 0 without stop_ids or done; budget without n_new or done; history without n_new or with hist_ld < 1; and whatever
- * ivl_sample_rows_fwd refuses.
- * ------------------------------------------------------------------------------------------- */
-IVL_API int ivl_sample_rows_ctl_fwd(const void* logits, int64_t ld, int S, int V,
-                                    const float* temperature, const int32_t* top_k, const float* top_p,
-                                    const int64_t* seed, int64_t* counter,
-                                    int64_t* token, int64_t token_stride,
-                                    int32_t* n_kept, float* prob,
-                                    const float* rep_penalty, uint32_t* seen, int64_t seen_ld,
-                                    const int64_t* stop_ids, int n_stop, const int64_t* budget, const int64_t* fill,
-                                    int64_t* n_new, int32_t* done, int64_t* history, int64_t hist_ld, void* stream);
-
-/* ---------------------------------------------------------------------------------------------
- * ivl_sample_rows_ctl_fwd with the scores of what it generates, inside the same one launch: the log-probability of the token, the
+ * done codes: 0 running, 1 ended on a stop id, 2 ended on its budget, 3 a dead end of the constraint; the host clears done[s] to
+ * restart a row.
+ *
+ * SCORES: the scores of what the call generates, inside the same one launch: the log-probability of the token, the
  * n_top most likely alternatives, a running sum and rings beside the token history (`logprobs` / `top_logprobs` of the OpenAI
- * protocol the reference's api/ serves; output_scores of HF generate).  Every new argument may be NULL / 0 (off); with all of them
- * off the call IS ivl_sample_rows_ctl_fwd.  With any of them on, token, counter, seen, n_new, done, history, n_kept and prob are
- * bit for bit those of ivl_sample_rows_ctl_fwd on the same inputs.  Per row s:
+ * protocol the reference's api/ serves; output_scores of HF generate).  Per row s:
  *   L1 the scored distribution.  x' = the row as the kernel keys it: after the repetition penalty of step B, before temperature,
  *      top-k and top-p (HF's processed scores in front of the warpers; with r == 1 the raw model distribution).  NaN counts as
  *      -inf (step 1); m = max x'.
@@ -500,24 +493,10 @@ IVL_API int ivl_sample_rows_ctl_fwd(const void* logits, int64_t ld, int S, int V
  * top_hist_ids int64 / top_hist_lp fp32 [S, hist_ld, n_top].  hist_ld is the one of `history` (which may itself be NULL).
  * The scores are a pure function of (x, rep_penalty, seen) and the token: the same bits eager or in a replayed graph, alone or as
  * any row of a larger call.
- * IVL_ERR_INVALID_ARG (before anything is launched): n_top outside 0..20; n_top > 0 without top_ids or top_logprobs; lp_history
- * or a top ring without n_new or with hist_ld < 1; a top ring with n_top == 0; and whatever ivl_sample_rows_ctl_fwd refuses.
- * ------------------------------------------------------------------------------------------- */
-IVL_API int ivl_sample_rows_lp_fwd(const void* logits, int64_t ld, int S, int V,
-                                   const float* temperature, const int32_t* top_k, const float* top_p,
-                                   const int64_t* seed, int64_t* counter,
-                                   int64_t* token, int64_t token_stride,
-                                   int32_t* n_kept, float* prob,
-                                   const float* rep_penalty, uint32_t* seen, int64_t seen_ld,
-                                   const int64_t* stop_ids, int n_stop, const int64_t* budget, const int64_t* fill,
-                                   int64_t* n_new, int32_t* done, int64_t* history, int64_t hist_ld,
-                                   float* logprob, int n_top, int64_t* top_ids, float* top_logprobs, double* cum_logprob,
-                                   float* lp_history, int64_t* top_hist_ids, float* top_hist_lp, void* stream);
-
-/* ---------------------------------------------------------------------------------------------
- * ivl_sample_rows_lp_fwd under a token-level finite state machine per row, inside the same one launch: constrained decoding (what
+ *
+ * CONSTRAINT: a token-level finite state machine per row, inside the same one launch: constrained decoding (what
  * HF generate takes as prefix_allowed_tokens_fn or a logits processor, with the token on the host after every step) without a
- * host round trip per token.  The arguments of ivl_sample_rows_lp_fwd, then the constraint group:
+ * host round trip per token.
  *   fsm_state int32 [S]: per row a state index q >= 0, or -1 = an unconstrained row;
  *   fsm_mask uint32 [n_states, mask_ld], mask_ld*32 >= V: bit (i & 31) of word (i >> 5) of row q = token i is allowed in state q
  *     (the layout of `seen`);
@@ -525,8 +504,8 @@ IVL_API int ivl_sample_rows_lp_fwd(const void* logits, int64_t ld, int S, int V,
  *     grammar = fsm_cls[cls_off + i];  fsm_trans int32, flat: next = fsm_trans[trans_off + class]: a state >= 0, -1 = the row
  *     becomes unconstrained, -2 = no transition.  States are global indices: several grammars share the tables.
  * Per row s, with q = fsm_state[s] read ONCE at kernel entry (behind step A: a finished row is not looked at):
- *   F0 group off or row free.  fsm_state == NULL: the call IS ivl_sample_rows_lp_fwd, bit for bit.  A row with q < 0 behaves as
- *      in that call and its state stays as it is.
+ *   F0 group off or row free.  fsm_state == NULL: the form rule above decides, as if the group's fields did not exist.  A row with
+ *      q < 0 behaves as in the call without the group and its state stays as it is.
  *   F1 the row is its allowed sub-vocabulary.  A = {i < V : bit i of mask row q}.  Steps 1-6, B and L1-L3 run over i in A only: a
  *      token outside A is not keyed to -inf, it is ABSENT -- no part in the maximum, the counts, the masses, Z1, the top-N or the
  *      walk -- and can never be emitted or listed, also when every allowed logit is -inf or NaN and a disallowed one is +inf.
@@ -535,7 +514,7 @@ IVL_API int ivl_sample_rows_lp_fwd(const void* logits, int64_t ld, int S, int V,
  *      -inf; a set A whose logits are all -inf or NaN gives each of its tokens -logf((float)|A|) (Z1 = |A| 2^40); n_kept, prob
  *      and logprob are those of the distribution renormalised over A.
  *   F3 all sums are integers and the draw is the first index in vocabulary order, so every output equals, bit for bit, that of
- *      ivl_sample_rows_lp_fwd on the gathered row x[A] (A ascending) with the gathered seen bits: token and top_ids (mapped back
+ *      the unconstrained call on the gathered row x[A] (A ascending) with the gathered seen bits: token and top_ids (mapped back
  *      through A), counter, n_kept, prob, logprob, top_logprobs, the rings and cum_logprob.
  *   F4 advance, by the lane that writes the token, behind step C:  c = fsm_cls[cls_off + token];
  *      fsm_state[s] = fsm_trans[trans_off + c].  `done` is decided by step C as before: a stop id that an accepting state allows
@@ -548,22 +527,45 @@ IVL_API int ivl_sample_rows_lp_fwd(const void* logits, int64_t ld, int S, int V,
  *      bookkeeping, the state stays unchanged, and done[s] = 3 replaces what step C decided.
  * Tables are the caller's to keep consistent (bit set <=> transition != -2) and in bounds: cls_off + i and trans_off + class are
  * not checked on the device.
- * done codes: 0 running, 1 stop id, 2 budget, 3 dead end.
- * IVL_ERR_INVALID_ARG (before anything is launched): fsm_state with fsm_mask, fsm_desc, fsm_cls, fsm_trans or done NULL;
- * mask_ld*32 < V; n_states < 1; and whatever ivl_sample_rows_lp_fwd refuses.
+ *
+ * SCORE ONLY (score_only != 0): the scores without a token: per row s, steps A (a finished row), B (the repetition penalty on
+ * `seen`), L1 and L3, and nothing else -- the candidate lists of a beam search step.
+ *   top_ids[s*n_top + j] / top_logprobs[s*n_top + j]: the min(n_top, V) tokens with the largest x', ties to the lowest index,
+ *   by (x' descending, index ascending), with lp of L1; entries j >= V are -1 / -inf.  Bit-equal to what the scoring form
+ *   writes to its top_ids / top_logprobs for the same (logits, rep_penalty, seen), whatever that call's sampling parameters.
+ *   A row with done[s] != 0 gets ids -1 and lp -inf (L5).  done may be NULL (no row is finished).
+ * Nothing is committed: no token, counter, n_kept or prob; `seen` and `done` are only read and no n_new, history or ring exists here.
+ * The form takes logits, ld, S, V, rep_penalty, seen, seen_ld, done, n_top (1..20), top_ids and top_logprobs; any other field that
+ * is set is refused, not ignored.
+ *
+ * Refused before anything is launched, checked in the order base, controls, scores, constraint.
+ * IVL_ERR_INVALID_ARG: NULL args, logits, temperature, top_k, top_p, seed, counter or token (score only: logits, top_ids or
+ * top_logprobs); S < 1, V < 1, ld < V; score_only with a field outside its list; rep_penalty without seen; seen with
+ * seen_ld*32 < V; n_stop outside 0..16; n_stop > 0 without stop_ids or done; budget without n_new or done; history without n_new or
+ * with hist_ld < 1; n_top outside 0..20 (score only: 1..20); n_top > 0 without top_ids or top_logprobs; lp_history or a top ring
+ * without n_new or with hist_ld < 1; a top ring with n_top == 0; fsm_state with fsm_mask, fsm_desc, fsm_cls, fsm_trans or done NULL,
+ * mask_ld*32 < V or n_states < 1.  IVL_ERR_UNSUPPORTED: V >= 2^23.
  * ------------------------------------------------------------------------------------------- */
-IVL_API int ivl_sample_rows_fsm_fwd(const void* logits, int64_t ld, int S, int V,
-                                    const float* temperature, const int32_t* top_k, const float* top_p,
-                                    const int64_t* seed, int64_t* counter,
-                                    int64_t* token, int64_t token_stride,
-                                    int32_t* n_kept, float* prob,
-                                    const float* rep_penalty, uint32_t* seen, int64_t seen_ld,
-                                    const int64_t* stop_ids, int n_stop, const int64_t* budget, const int64_t* fill,
-                                    int64_t* n_new, int32_t* done, int64_t* history, int64_t hist_ld,
-                                    float* logprob, int n_top, int64_t* top_ids, float* top_logprobs, double* cum_logprob,
-                                    float* lp_history, int64_t* top_hist_ids, float* top_hist_lp,
-                                    int32_t* fsm_state, const uint32_t* fsm_mask, int64_t mask_ld, int n_states,
-                                    const int64_t* fsm_desc, const int32_t* fsm_cls, const int32_t* fsm_trans, void* stream);
+typedef struct ivl_sample_args {
+  /* row */
+  const void* logits; int64_t ld; int S, V;
+  /* sampling */
+  const float* temperature; const int32_t* top_k; const float* top_p; const int64_t* seed; int64_t* counter;
+  int64_t* token; int64_t token_stride; int32_t* n_kept; float* prob;
+  /* controls */
+  const float* rep_penalty; uint32_t* seen; int64_t seen_ld;
+  const int64_t* stop_ids; int n_stop; const int64_t* budget; const int64_t* fill;
+  int64_t* n_new; int32_t* done; int64_t* history; int64_t hist_ld;
+  /* scores */
+  float* logprob; int n_top; int64_t* top_ids; float* top_logprobs; double* cum_logprob;
+  float* lp_history; int64_t* top_hist_ids; float* top_hist_lp;
+  /* constraint */
+  int32_t* fsm_state; const uint32_t* fsm_mask; int64_t mask_ld; int n_states;
+  const int64_t* fsm_desc; const int32_t* fsm_cls; const int32_t* fsm_trans;
+  int score_only;
+} ivl_sample_args;
+
+IVL_API int ivl_sample_rows_fwd(const ivl_sample_args* args, void* stream);
 
 /* Sets the bits of ids[0..n) (int64, device) in ONE row of a seen bitmap: the prompt's tokens, before the first draw.  Ids outside
  * [0, V) are ignored, duplicates are fine; n == 0 is a no-op.  seen_row NULL, V < 1, n < 0 or ids NULL with n > 0:
@@ -618,24 +620,9 @@ IVL_API int ivl_rows_gather_fwd(const int64_t* table, int n_entries, int64_t max
                                 const int32_t* parent, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
- * The scores of ivl_sample_rows_lp_fwd without a token: per row s, steps A (a finished row), B (the repetition penalty on `seen`),
- * L1 and L3 of that call, and nothing else -- the candidate lists of a beam search step.
- *   top_ids[s*n_top + j] / top_logprobs[s*n_top + j]: the min(n_top, V) tokens with the largest x', ties to the lowest index,
- *   by (x' descending, index ascending), with lp of L1; entries j >= V are -1 / -inf.  Bit-equal to what ivl_sample_rows_lp_fwd
- *   writes to its top_ids / top_logprobs for the same (logits, rep_penalty, seen), whatever that call's sampling parameters.
- *   A row with done[s] != 0 gets ids -1 and lp -inf (L5).  done may be NULL (no row is finished).
- * Nothing is committed: no token, counter, n_kept or prob; `seen` and `done` are const and no n_new, history or ring exists here.
- * IVL_ERR_INVALID_ARG: NULL logits / top_ids / top_logprobs, S < 1, V < 1, ld < V, rep_penalty without seen, seen with
- * seen_ld*32 < V, n_top outside 1..20.  IVL_ERR_UNSUPPORTED: V >= 2^23.
- * ------------------------------------------------------------------------------------------- */
-IVL_API int ivl_sample_rows_score_fwd(const void* logits, int64_t ld, int S, int V,
-                                      const float* rep_penalty, const uint32_t* seen, int64_t seen_ld, const int32_t* done,
-                                      int n_top, int64_t* top_ids, float* top_logprobs, void* stream);
-
-/* ---------------------------------------------------------------------------------------------
  * Beam search (num_beams / length_penalty / early_stopping of HF generate, which the reference sets through
  * hparams/generating_args.py and train/sft/workflow.py:94): G groups of B beams; group g owns the rows (slots) [g B, (g+1) B) of
- * every per-slot tensor.  One step = score (ivl_sample_rows_score_fwd with n_top = K) -> ivl_beam_select_fwd ->
+ * every per-slot tensor.  One step = score (ivl_sample_rows_fwd with score_only and n_top = K) -> ivl_beam_select_fwd ->
  * ivl_rows_gather_fwd(parent + g B) over everything a slot owns -> ivl_beam_commit_fwd.  Both calls here process group g only if
  * bit g of the HOST group_mask is set and beam_done[g] == 0; a skipped group has nothing read or written.
  * Per slot: top_ids int64 / top_logprobs fp32 [S,K]; cum_logprob float64 [S], the beam's sum of log-probabilities, -inf = no beam

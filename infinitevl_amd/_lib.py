@@ -1,7 +1,8 @@
 """ctypes binding of libivl_hip.so, derived from the C ABI's one declaration: include/ivl_hip.h.
 
-The header is read at import (no library needed): its `#define IVL_*` integers become module attributes, `struct
-ivl_swa_args` becomes `SwaArgs`, and every `IVL_API` prototype an entry of `PROTOTYPES`, which `bind` applies to a CDLL.
+The header is read at import (no library needed): its `#define IVL_*` integers become module attributes, every `struct
+ivl_<x>_args` a ctypes class (`SwaArgs`, `SampleArgs`), and every `IVL_API` prototype an entry of `PROTOTYPES`, which `bind`
+applies to a CDLL.
 The library is built in-tree by `__graft_entry__.build()` / `make -C infinitevl_amd/csrc`.
 There is NO fallback: if the shared object is missing, importing an operator raises.
 """
@@ -59,23 +60,26 @@ def _int_expr(expr: str, where: str) -> int:
         raise ImportError(f"ivl_hip.h: {where}: not an integer expression: {expr!r}") from None
 
 
-def parse_header(text: str):
-    """(constants {name: int}, the SwaArgs class, prototypes {name: (restype, [argument types])}) of a header text."""
+def parse_header(text: str, structs: dict = None):
+    """(constants {name: int}, the SwaArgs class, prototypes {name: (restype, [argument types])}) of a header text.  `structs`,
+    when given, receives every `typedef struct ivl_<x>_args` of the header as {"ivl_<x>_args": its ctypes class}."""
     text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
     defines = re.findall(r"^[ \t]*#[ \t]*define[ \t]+(IVL_\w+)[ \t]+(\S[^\n]*)", text, re.M)     # (the include guard has no value)
     consts = {name: _int_expr(expr, "#define " + name) for name, expr in defines if name != "IVL_API"}
     text = re.sub(r"^[ \t]*#[^\n]*", " ", text, flags=re.M)
-    struct = re.search(r"typedef\s+struct\s+ivl_swa_args\s*\{(.*?)\}\s*ivl_swa_args\s*;", text, re.S)
-    if struct is None:
+    structs = {} if structs is None else structs
+    for tag, body in re.findall(r"typedef\s+struct\s+(ivl_\w+_args)\s*\{(.*?)\}\s*\1\s*;", text, re.S):
+        fields = []
+        for decl in filter(None, (d.strip() for d in body.split(";"))):
+            m = re.fullmatch(_DECL + r"(\w+(?:\s*,\s*\w+)*)", decl, re.S)
+            if m is None:
+                raise ImportError(f"ivl_hip.h: {tag}: cannot read the field declaration {decl!r}")
+            fields += [(name, _ctype(m.group(1), f"{tag}.{name}", _C_TYPES)) for name in re.split(r"\s*,\s*", m.group(2))]
+        cls = "".join(w.capitalize() for w in tag.split("_")[1:])                                  # ivl_swa_args -> SwaArgs
+        structs[tag] = type(cls, (Structure,), {"_fields_": fields, "__doc__": f"struct {tag} (include/ivl_hip.h)."})
+    if "ivl_swa_args" not in structs:
         raise ImportError("ivl_hip.h: struct ivl_swa_args not found")
-    fields = []
-    for decl in filter(None, (d.strip() for d in struct.group(1).split(";"))):
-        m = re.fullmatch(_DECL + r"(\w+(?:\s*,\s*\w+)*)", decl, re.S)
-        if m is None:
-            raise ImportError(f"ivl_hip.h: ivl_swa_args: cannot read the field declaration {decl!r}")
-        fields += [(name, _ctype(m.group(1), "ivl_swa_args." + name, _C_TYPES)) for name in re.split(r"\s*,\s*", m.group(2))]
-    swa_args = type("SwaArgs", (Structure,), {"_fields_": fields, "__doc__": "struct ivl_swa_args (include/ivl_hip.h)."})
-    known = {**_C_TYPES, "const ivl_swa_args*": POINTER(swa_args)}
+    known = {**_C_TYPES, **{f"const {tag}*": POINTER(cls) for tag, cls in structs.items()}}
     protos = {}
     for ret, name, params in re.findall(r"\bIVL_API\s+" + _DECL + r"(\w+)\s*\(([^()]*)\)\s*;", text, re.S):
         types = []
@@ -86,13 +90,15 @@ def parse_header(text: str):
     if len(protos) != len(re.findall(r"\bIVL_API\b", text)):
         raise ImportError(f"ivl_hip.h: only {len(protos)} of its IVL_API declarations are readable prototypes (the last one "
                           f"read: {list(protos)[-1:]})")
-    return consts, swa_args, protos
+    return consts, structs["ivl_swa_args"], protos
 
 
 if not os.path.exists(HEADER_PATH):
     raise ImportError(f"{HEADER_PATH} not found: the package is used in-tree and reads the C ABI from the header at import.")
+STRUCTS = {}                                                 # {"ivl_swa_args": SwaArgs, "ivl_sample_args": SampleArgs}
 with open(HEADER_PATH) as _f:
-    CONSTANTS, SwaArgs, PROTOTYPES = parse_header(_f.read())
+    CONSTANTS, SwaArgs, PROTOTYPES = parse_header(_f.read(), STRUCTS)
+SampleArgs = STRUCTS["ivl_sample_args"]
 globals().update(CONSTANTS)                                  # IVL_ABI_VERSION, IVL_BF16, ..., IVL_OK, IVL_ERR_*, IVL_GDN_*
 EXPORTED_SYMBOLS = tuple(PROTOTYPES)
 

@@ -21,13 +21,13 @@
 // elements in front of and behind the row inside its first and last tile are masked out -- they lie in the same 16 bytes as row
 // elements, so the loads stay inside the caller's allocation granule.
 //
-// Generation controls (ivl_sample_rows_ctl_fwd; the kernel is a template on them, the entry point above instantiates the form
-// without): a finished row returns its fill token before the first pass; the repetition penalty re-keys the seen elements of a
+// Generation controls (the kernel is a template on them; the entry point launches the form without when none is given): a
+// finished row returns its fill token before the first pass; the repetition penalty re-keys the seen elements of a
 // tile where it is loaded (a bitmap of seen tokens, 8 bits a tile from two bytes), rounded back to bf16, so every pass sees the same
 // penalised keys and nothing behind the key changes; the lane that writes the token then sets its bit, logs it, counts it and
 // decides `done` from the stop ids and the budget.  ivl_token_mark_fwd marks a prompt's tokens in a row of the bitmap.
 //
-// Log-probabilities (ivl_sample_rows_lp_fwd; a third form of the template, the two others are compiled without a line of it): the
+// Log-probabilities (a third form of the template, the two others are compiled without a line of it): the
 // row's log-partition from the integer sum Z1 of the Q40 weights at temperature 1 and the n_top <= 20 largest keys, in three more
 // passes placed where `hist` is free -- behind top-k's scan, in front of top-p's masses, or in front of a greedy row's write:
 //   L1  Z1 and the coarse counts (a top-k row has them from pass 1)     L2  counts of the 16 keys of the bin that holds the n_top-th largest value -> t_N
@@ -36,11 +36,11 @@
 // then wave 0 takes the ties in wave = index order, ranks the <= 20 survivors against each other (no sort of the row) and leaves
 // the ordered list in LDS for the lane that writes the token: it scores the token, logs and adds it up beside smp_after.
 //
-// Score only (ivl_sample_rows_score_fwd; a fourth form, the three others are compiled without a line of it): a beam search step
+// Score only (score_only != 0; a fourth form, the three others are compiled without a line of it): a beam search step
 // needs every beam's candidate list and no token.  The form takes the greedy row's path -- pass 1 for the maximum, L1-L3 -- writes
 // the list and stops: no token, counter, seen bit, n_new, done, history or ring; its sampling parameters are not even read.
 //
-// Constrained (ivl_sample_rows_fsm_fwd; a fifth form, the four others are compiled without a line of it): a row in state q >= 0 of
+// Constrained (fsm_state != NULL; a fifth form, the four others are compiled without a line of it): a row in state q >= 0 of
 // a token-level finite state machine IS its allowed sub-vocabulary.  The allowed-token bitmap of q has the layout of `seen` and
 // comes through the same helper, and it is ANDed into the `valid` mask of smp_load: a disallowed token is absent from every pass,
 // exactly as the elements in front of and behind the row are.  Pass 1 counts |A| beside the maximum (it takes V's place in top-k's
@@ -262,7 +262,7 @@ __device__ __forceinline__ void smp_locate(const SmpScan& s, u64 T, int tid, uns
   }
 }
 
-// The controls of ivl_sample_rows_ctl_fwd; every group may be NULL (off)
+// The control group of ivl_sample_args; every group may be NULL (off)
 struct SmpCtl {
   const float* rep_penalty;
   unsigned* seen;
@@ -304,7 +304,7 @@ __device__ __forceinline__ void smp_after(const SmpCtl& c, long long s, long lon
   }
 }
 
-// The log-probability group of ivl_sample_rows_lp_fwd; every pointer may be NULL (off)
+// The score group of ivl_sample_args; every pointer may be NULL (off)
 constexpr int SMP_TOP_MAX = 20;
 struct SmpLp {
   float* logprob;
@@ -511,7 +511,7 @@ __device__ __forceinline__ void smp_lp_after(const SmpLp& lp, const SmpCtl& c, l
   if (lp.cum) lp.cum[s] += (double)v;
 }
 
-// The constraint group of ivl_sample_rows_fsm_fwd
+// The constraint group of ivl_sample_args
 struct SmpFsm {
   int* state;
   const unsigned* mask;
@@ -549,18 +549,14 @@ __device__ __forceinline__ void smp_fsm_after(const SmpFsm& f, const SmpCtl& c, 
 }
 
 // CTL: no type (the control-free form, with the parameter list it always had), SmpCtl, SmpCtl and SmpLp, or these two and
-// SmpScore (the score-only form of ivl_sample_rows_score_fwd: steps A, B, L1 and L3, nothing committed) or SmpFsm (the
-// constrained form of ivl_sample_rows_fsm_fwd)
+// SmpScore (the score-only form: steps A, B, L1 and L3, nothing committed) or SmpFsm (the constrained form)
 struct SmpScore {};
 template <typename T, typename... U> constexpr bool smp_has = (std::is_same<T, U>::value || ...);
-__device__ __forceinline__ const SmpCtl& smp_first(const SmpCtl& c) { return c; }
-__device__ __forceinline__ const SmpCtl& smp_first(const SmpCtl& c, const SmpLp&) { return c; }
-__device__ __forceinline__ const SmpCtl& smp_first(const SmpCtl& c, const SmpLp&, const SmpScore&) { return c; }
-__device__ __forceinline__ const SmpLp& smp_second(const SmpCtl&, const SmpLp& l) { return l; }
-__device__ __forceinline__ const SmpLp& smp_second(const SmpCtl&, const SmpLp& l, const SmpScore&) { return l; }
-__device__ __forceinline__ const SmpCtl& smp_first(const SmpCtl& c, const SmpLp&, const SmpFsm&) { return c; }
-__device__ __forceinline__ const SmpLp& smp_second(const SmpCtl&, const SmpLp& l, const SmpFsm&) { return l; }
-__device__ __forceinline__ const SmpFsm& smp_third(const SmpCtl&, const SmpLp&, const SmpFsm& f) { return f; }
+// the group of type T among the kernel's trailing parameters
+template <typename T, typename H, typename... R>
+__device__ __forceinline__ const T& smp_get(const H& h, const R&... r) {
+  if constexpr (std::is_same<T, H>::value) return h; else return smp_get<T>(r...);
+}
 
 template <typename... CTL>
 __global__ void __launch_bounds__(SMP_THREADS)
@@ -574,7 +570,7 @@ sample_rows_kernel(const bf16_t* __restrict__ logits, long long ld, int V, const
   [[maybe_unused]] int fsm_q = -1;                      // the row's state, read once: the lane that advances it writes last
   [[maybe_unused]] bool lp_on = true;                   // (the constrained form is launched with the score group off, too)
   if constexpr (kCtl) {
-    const SmpCtl& ctl = smp_first(ctl_...);
+    const SmpCtl& ctl = smp_get<SmpCtl>(ctl_...);
     const long long s = blockIdx.x;
     if (ctl.done && ctl.done[s] != 0) {                 // a finished row: the fill token, nothing else read or written
       if constexpr (!kScore) {
@@ -585,7 +581,7 @@ sample_rows_kernel(const bf16_t* __restrict__ logits, long long ld, int V, const
         }
       }
       if constexpr (kLp) {                              // no score: logprob 0, no alternatives, no ring or sum write
-        const SmpLp& lp = smp_second(ctl_...);
+        const SmpLp& lp = smp_get<SmpLp>(ctl_...);
         if (threadIdx.x == 0 && lp.logprob) lp.logprob[s] = 0.f;
         if ((int)threadIdx.x < lp.n_top) {
           lp.top_ids[s * lp.n_top + threadIdx.x] = -1ll;
@@ -599,8 +595,8 @@ sample_rows_kernel(const bf16_t* __restrict__ logits, long long ld, int V, const
     pen.inv = __fdiv_rn(1.f, pen.r);
     pen.fast = ((__float_as_uint(pen.r) >> 23) & 0x1FFu) - 107u <= 40u;      // positive, exponent -20 .. 20
     if constexpr (kFsm) {
-      const SmpFsm& f = smp_third(ctl_...);
-      const SmpLp& lp = smp_second(ctl_...);
+      const SmpFsm& f = smp_get<SmpFsm>(ctl_...);
+      const SmpLp& lp = smp_get<SmpLp>(ctl_...);
       lp_on = lp.logprob || lp.n_top > 0 || lp.cum || lp.lp_hist;
       fsm_q = f.state[s];
       if (fsm_q >= f.n_states) {                        // no such state: a dead end, before a word of the tables is read
@@ -684,7 +680,7 @@ sample_rows_kernel(const bf16_t* __restrict__ logits, long long ld, int V, const
 #pragma unroll
     for (int w = 0; w < SMP_WAVES; ++w) nrow += (int)wcnt[w];
     if (nrow == 0) {                                    // the state allows nothing (uniform: every thread sums the same words)
-      smp_fsm_dead(smp_first(ctl_...), smp_second(ctl_...), s, token, token_stride, n_kept, prob);
+      smp_fsm_dead(smp_get<SmpCtl>(ctl_...), smp_get<SmpLp>(ctl_...), s, token, token_stride, n_kept, prob);
       return;
     }
   }
@@ -693,7 +689,7 @@ sample_rows_kernel(const bf16_t* __restrict__ logits, long long ld, int V, const
   if (greedy) {
     if constexpr (kLp)
       if (lp_on)
-        lse = smp_lp_phase(r, pen, nrow, mkey, smp_key_value(mkey), smp_second(ctl_...).n_top, false, tid, hist, sub, wsum, &sh_bin,
+        lse = smp_lp_phase(r, pen, nrow, mkey, smp_key_value(mkey), smp_get<SmpLp>(ctl_...).n_top, false, tid, hist, sub, wsum, &sh_bin,
                            &sh_E, &sh_key, lpl);
     if (tid == 0) {
       if constexpr (!kScore) {
@@ -702,9 +698,9 @@ sample_rows_kernel(const bf16_t* __restrict__ logits, long long ld, int V, const
         if (prob) prob[s] = 1.f;
       }
       if constexpr (kLp)
-        smp_lp_after(smp_second(ctl_...), smp_first(ctl_...), s, nrow, mkey, mkey, smp_key_value(mkey), lse, lpl);
-      if constexpr (kCtl && !kScore) smp_after(smp_first(ctl_...), s, (long long)midx);
-      if constexpr (kFsm) smp_fsm_after(smp_third(ctl_...), smp_first(ctl_...), s, fsm_q, (long long)midx);
+        smp_lp_after(smp_get<SmpLp>(ctl_...), smp_get<SmpCtl>(ctl_...), s, nrow, mkey, mkey, smp_key_value(mkey), lse, lpl);
+      if constexpr (kCtl && !kScore) smp_after(smp_get<SmpCtl>(ctl_...), s, (long long)midx);
+      if constexpr (kFsm) smp_fsm_after(smp_get<SmpFsm>(ctl_...), smp_get<SmpCtl>(ctl_...), s, fsm_q, (long long)midx);
     }
     return;
   }
@@ -746,7 +742,7 @@ sample_rows_kernel(const bf16_t* __restrict__ logits, long long ld, int V, const
   }
   if constexpr (kLp)                             // hist is free here: top-k has read its counts, top-p has not begun
     if (lp_on)
-      lse = smp_lp_phase(r, pen, nrow, mkey, xm, smp_second(ctl_...).n_top, count_k, tid, hist, sub, wsum, &sh_bin, &sh_E, &sh_key,
+      lse = smp_lp_phase(r, pen, nrow, mkey, xm, smp_get<SmpLp>(ctl_...).n_top, count_k, tid, hist, sub, wsum, &sh_bin, &sh_E, &sh_key,
                          lpl);
 
   // ---- top-p: keep a class while the mass strictly above it is below p Z_K
@@ -889,10 +885,10 @@ sample_rows_kernel(const bf16_t* __restrict__ logits, long long ld, int V, const
           unsigned ke = key[0];
 #pragma unroll
           for (int i = 1; i < 8; ++i) if (e == i) ke = key[i];
-          smp_lp_after(smp_second(ctl_...), smp_first(ctl_...), s, nrow, ke, mkey, xm, lse, lpl);
+          smp_lp_after(smp_get<SmpLp>(ctl_...), smp_get<SmpCtl>(ctl_...), s, nrow, ke, mkey, xm, lse, lpl);
         }
-        if constexpr (kCtl) smp_after(smp_first(ctl_...), s, j * 8 - r.off + e);
-        if constexpr (kFsm) smp_fsm_after(smp_third(ctl_...), smp_first(ctl_...), s, fsm_q, j * 8 - r.off + e);
+        if constexpr (kCtl) smp_after(smp_get<SmpCtl>(ctl_...), s, j * 8 - r.off + e);
+        if constexpr (kFsm) smp_fsm_after(smp_get<SmpFsm>(ctl_...), smp_get<SmpCtl>(ctl_...), s, fsm_q, j * 8 - r.off + e);
       }
       return;
     }
@@ -911,208 +907,83 @@ token_mark_kernel(unsigned* __restrict__ seen_row, long long V, const long long*
 
 }  // namespace ivl
 
-static int sample_rows_check(const char* fn, const void* logits, int64_t ld, int S, int V, const float* temperature,
-                             const int32_t* top_k, const float* top_p, const int64_t* seed, int64_t* counter, int64_t* token) {
-  IVL_REQUIRE(logits && temperature && top_k && top_p && seed && counter && token, IVL_ERR_INVALID_ARG, "%s: NULL pointer", fn);
-  IVL_REQUIRE(S >= 1 && V >= 1 && ld >= (int64_t)V, IVL_ERR_INVALID_ARG, "%s: S=%d V=%d ld=%lld", fn, S, V, (long long)ld);
-  IVL_REQUIRE(V < (1 << 23), IVL_ERR_UNSUPPORTED, "%s: V=%d (the Q40 sums are sized for V < 2^23)", fn, V);
-  return IVL_OK;
-}
-
-static int sample_rows_ctl_check(const char* fn, int V, const float* rep_penalty, const uint32_t* seen, int64_t seen_ld,
-                                 const int64_t* stop_ids, int n_stop, const int64_t* budget, const int64_t* n_new,
-                                 const int32_t* done, const int64_t* history, int64_t hist_ld) {
-  IVL_REQUIRE(!rep_penalty || seen, IVL_ERR_INVALID_ARG, "%s: rep_penalty needs seen", fn);
-  IVL_REQUIRE(!seen || seen_ld * 32 >= (int64_t)V, IVL_ERR_INVALID_ARG, "%s: seen_ld=%lld words hold fewer than V=%d bits", fn,
-              (long long)seen_ld, V);
-  IVL_REQUIRE(n_stop >= 0 && n_stop <= 16, IVL_ERR_INVALID_ARG, "%s: n_stop=%d outside 0..16", fn, n_stop);
-  IVL_REQUIRE(n_stop == 0 || (stop_ids && done), IVL_ERR_INVALID_ARG, "%s: n_stop=%d needs stop_ids and done", fn, n_stop);
-  IVL_REQUIRE(!budget || (n_new && done), IVL_ERR_INVALID_ARG, "%s: budget needs n_new and done", fn);
-  IVL_REQUIRE(!history || (n_new && hist_ld >= 1), IVL_ERR_INVALID_ARG, "%s: history needs n_new and hist_ld >= 1 (%lld)", fn,
-              (long long)hist_ld);
-  return IVL_OK;
-}
-
-static int sample_rows_lp_check(const char* fn, const int64_t* n_new, int64_t hist_ld, int n_top, const int64_t* top_ids,
-                                const float* top_logprobs, const float* lp_history, const int64_t* top_hist_ids,
-                                const float* top_hist_lp) {
-  using ivl::SMP_TOP_MAX;
-  IVL_REQUIRE(n_top >= 0 && n_top <= SMP_TOP_MAX, IVL_ERR_INVALID_ARG, "%s: n_top=%d outside 0..%d", fn, n_top, SMP_TOP_MAX);
-  IVL_REQUIRE(n_top == 0 || (top_ids && top_logprobs), IVL_ERR_INVALID_ARG, "%s: n_top=%d needs top_ids and top_logprobs", fn, n_top);
-  IVL_REQUIRE(!(top_hist_ids || top_hist_lp) || n_top > 0, IVL_ERR_INVALID_ARG, "%s: the top rings need n_top > 0", fn);
-  IVL_REQUIRE(!(lp_history || top_hist_ids || top_hist_lp) || (n_new && hist_ld >= 1), IVL_ERR_INVALID_ARG,
-              "%s: lp_history and the top rings need n_new and hist_ld >= 1 (%lld)", fn, (long long)hist_ld);
-  return IVL_OK;
-}
-
-extern "C" int ivl_sample_rows_fwd(const void* logits, int64_t ld, int S, int V, const float* temperature, const int32_t* top_k,
-                                   const float* top_p, const int64_t* seed, int64_t* counter, int64_t* token,
-                                   int64_t token_stride, int32_t* n_kept, float* prob, void* stream) {
+// one launch statement for the five forms: the groups G follow the twelve parameters that every form takes
+template <typename... G>
+static void sample_rows_launch(const ivl_sample_args& a, void* stream, const G&... g) {
   using namespace ivl;
-  const int rc = sample_rows_check("ivl_sample_rows_fwd", logits, ld, S, V, temperature, top_k, top_p, seed, counter, token);
-  if (rc != IVL_OK) return rc;
-  hipLaunchKernelGGL(sample_rows_kernel<>, dim3((unsigned)S), dim3(SMP_THREADS), 0, (hipStream_t)stream,
-                     (const bf16_t*)logits, (long long)ld, V, temperature, (const int*)top_k, top_p, (const long long*)seed,
-                     (long long*)counter, (long long*)token, (long long)token_stride, (int*)n_kept, prob);
-  return check_launch("ivl_sample_rows_fwd");
+  hipLaunchKernelGGL((sample_rows_kernel<G...>), dim3((unsigned)a.S), dim3(SMP_THREADS), 0, (hipStream_t)stream,
+                     (const bf16_t*)a.logits, (long long)a.ld, a.V, a.temperature, (const int*)a.top_k, a.top_p,
+                     (const long long*)a.seed, (long long*)a.counter, (long long*)a.token, (long long)a.token_stride,
+                     (int*)a.n_kept, a.prob, g...);
 }
 
-static ivl::SmpCtl sample_rows_ctl(const float* rep_penalty, uint32_t* seen, int64_t seen_ld, const int64_t* stop_ids, int n_stop,
-                                   const int64_t* budget, const int64_t* fill, int64_t* n_new, int32_t* done, int64_t* history,
-                                   int64_t hist_ld) {
-  ivl::SmpCtl c;
-  c.rep_penalty = rep_penalty;
-  c.seen = seen;
-  c.seen_ld = seen_ld;
-  c.stop_ids = (const long long*)stop_ids;
-  c.n_stop = n_stop;
-  c.budget = (const long long*)budget;
-  c.fill = (const long long*)fill;
-  c.n_new = (long long*)n_new;
-  c.done = done;
-  c.history = (long long*)history;
-  c.hist_ld = hist_ld;
-  return c;
-}
-
-extern "C" int ivl_sample_rows_ctl_fwd(const void* logits, int64_t ld, int S, int V, const float* temperature,
-                                       const int32_t* top_k, const float* top_p, const int64_t* seed, int64_t* counter,
-                                       int64_t* token, int64_t token_stride, int32_t* n_kept, float* prob,
-                                       const float* rep_penalty, uint32_t* seen, int64_t seen_ld, const int64_t* stop_ids,
-                                       int n_stop, const int64_t* budget, const int64_t* fill, int64_t* n_new, int32_t* done,
-                                       int64_t* history, int64_t hist_ld, void* stream) {
+// Checks in the order base, controls, scores, constraint; then the form rule of include/ivl_hip.h, written once.
+extern "C" int ivl_sample_rows_fwd(const ivl_sample_args* args, void* stream) {
   using namespace ivl;
-  const char* fn = "ivl_sample_rows_ctl_fwd";
-  int rc = sample_rows_check(fn, logits, ld, S, V, temperature, top_k, top_p, seed, counter, token);
-  if (rc != IVL_OK) return rc;
-  rc = sample_rows_ctl_check(fn, V, rep_penalty, seen, seen_ld, stop_ids, n_stop, budget, n_new, done, history, hist_ld);
-  if (rc != IVL_OK) return rc;
-  if (!rep_penalty && !seen && n_stop == 0 && !budget && !n_new && !done && !history)      // no control: the control-free kernel
-    return ivl_sample_rows_fwd(logits, ld, S, V, temperature, top_k, top_p, seed, counter, token, token_stride, n_kept, prob,
-                               stream);
-  const SmpCtl c = sample_rows_ctl(rep_penalty, seen, seen_ld, stop_ids, n_stop, budget, fill, n_new, done, history, hist_ld);
-  hipLaunchKernelGGL(sample_rows_kernel<SmpCtl>, dim3((unsigned)S), dim3(SMP_THREADS), 0, (hipStream_t)stream,
-                     (const bf16_t*)logits, (long long)ld, V, temperature, (const int*)top_k, top_p, (const long long*)seed,
-                     (long long*)counter, (long long*)token, (long long)token_stride, (int*)n_kept, prob, c);
-  return check_launch(fn);
-}
-
-static ivl::SmpLp sample_rows_lp(float* logprob, int n_top, int64_t* top_ids, float* top_logprobs, double* cum_logprob,
-                                 float* lp_history, int64_t* top_hist_ids, float* top_hist_lp) {
-  ivl::SmpLp l;
-  l.logprob = logprob;
-  l.n_top = n_top;
-  l.top_ids = (long long*)top_ids;
-  l.top_lp = top_logprobs;
-  l.cum = cum_logprob;
-  l.lp_hist = lp_history;
-  l.top_hist_ids = (long long*)top_hist_ids;
-  l.top_hist_lp = top_hist_lp;
-  return l;
-}
-
-extern "C" int ivl_sample_rows_lp_fwd(const void* logits, int64_t ld, int S, int V, const float* temperature,
-                                      const int32_t* top_k, const float* top_p, const int64_t* seed, int64_t* counter,
-                                      int64_t* token, int64_t token_stride, int32_t* n_kept, float* prob,
-                                      const float* rep_penalty, uint32_t* seen, int64_t seen_ld, const int64_t* stop_ids,
-                                      int n_stop, const int64_t* budget, const int64_t* fill, int64_t* n_new, int32_t* done,
-                                      int64_t* history, int64_t hist_ld, float* logprob, int n_top, int64_t* top_ids,
-                                      float* top_logprobs, double* cum_logprob, float* lp_history, int64_t* top_hist_ids,
-                                      float* top_hist_lp, void* stream) {
-  using namespace ivl;
-  const char* fn = "ivl_sample_rows_lp_fwd";
-  int rc = sample_rows_check(fn, logits, ld, S, V, temperature, top_k, top_p, seed, counter, token);
-  if (rc != IVL_OK) return rc;
-  rc = sample_rows_ctl_check(fn, V, rep_penalty, seen, seen_ld, stop_ids, n_stop, budget, n_new, done, history, hist_ld);
-  if (rc != IVL_OK) return rc;
-  rc = sample_rows_lp_check(fn, n_new, hist_ld, n_top, top_ids, top_logprobs, lp_history, top_hist_ids, top_hist_lp);
-  if (rc != IVL_OK) return rc;
-  if (!logprob && n_top == 0 && !top_ids && !top_logprobs && !cum_logprob && !lp_history && !top_hist_ids && !top_hist_lp)
-    return ivl_sample_rows_ctl_fwd(logits, ld, S, V, temperature, top_k, top_p, seed, counter, token, token_stride, n_kept, prob,
-                                   rep_penalty, seen, seen_ld, stop_ids, n_stop, budget, fill, n_new, done, history, hist_ld,
-                                   stream);
-  const SmpCtl c = sample_rows_ctl(rep_penalty, seen, seen_ld, stop_ids, n_stop, budget, fill, n_new, done, history, hist_ld);
-  const SmpLp l = sample_rows_lp(logprob, n_top, top_ids, top_logprobs, cum_logprob, lp_history, top_hist_ids, top_hist_lp);
-  hipLaunchKernelGGL((sample_rows_kernel<SmpCtl, SmpLp>), dim3((unsigned)S), dim3(SMP_THREADS), 0, (hipStream_t)stream,
-                     (const bf16_t*)logits, (long long)ld, V, temperature, (const int*)top_k, top_p, (const long long*)seed,
-                     (long long*)counter, (long long*)token, (long long)token_stride, (int*)n_kept, prob, c, l);
-  return check_launch(fn);
-}
-
-extern "C" int ivl_sample_rows_fsm_fwd(const void* logits, int64_t ld, int S, int V, const float* temperature,
-                                       const int32_t* top_k, const float* top_p, const int64_t* seed, int64_t* counter,
-                                       int64_t* token, int64_t token_stride, int32_t* n_kept, float* prob,
-                                       const float* rep_penalty, uint32_t* seen, int64_t seen_ld, const int64_t* stop_ids,
-                                       int n_stop, const int64_t* budget, const int64_t* fill, int64_t* n_new, int32_t* done,
-                                       int64_t* history, int64_t hist_ld, float* logprob, int n_top, int64_t* top_ids,
-                                       float* top_logprobs, double* cum_logprob, float* lp_history, int64_t* top_hist_ids,
-                                       float* top_hist_lp, int32_t* fsm_state, const uint32_t* fsm_mask, int64_t mask_ld,
-                                       int n_states, const int64_t* fsm_desc, const int32_t* fsm_cls, const int32_t* fsm_trans,
-                                       void* stream) {
-  using namespace ivl;
-  const char* fn = "ivl_sample_rows_fsm_fwd";
-  if (!fsm_state)                                        // the group is off: the scoring call, bit for bit
-    return ivl_sample_rows_lp_fwd(logits, ld, S, V, temperature, top_k, top_p, seed, counter, token, token_stride, n_kept, prob,
-                                  rep_penalty, seen, seen_ld, stop_ids, n_stop, budget, fill, n_new, done, history, hist_ld, logprob,
-                                  n_top, top_ids, top_logprobs, cum_logprob, lp_history, top_hist_ids, top_hist_lp, stream);
-  int rc = sample_rows_check(fn, logits, ld, S, V, temperature, top_k, top_p, seed, counter, token);
-  if (rc != IVL_OK) return rc;
-  rc = sample_rows_ctl_check(fn, V, rep_penalty, seen, seen_ld, stop_ids, n_stop, budget, n_new, done, history, hist_ld);
-  if (rc != IVL_OK) return rc;
-  rc = sample_rows_lp_check(fn, n_new, hist_ld, n_top, top_ids, top_logprobs, lp_history, top_hist_ids, top_hist_lp);
-  if (rc != IVL_OK) return rc;
-  IVL_REQUIRE(fsm_mask, IVL_ERR_INVALID_ARG, "%s: fsm_state needs fsm_mask", fn);
-  IVL_REQUIRE(fsm_desc, IVL_ERR_INVALID_ARG, "%s: fsm_state needs fsm_desc", fn);
-  IVL_REQUIRE(fsm_cls, IVL_ERR_INVALID_ARG, "%s: fsm_state needs fsm_cls", fn);
-  IVL_REQUIRE(fsm_trans, IVL_ERR_INVALID_ARG, "%s: fsm_state needs fsm_trans", fn);
-  IVL_REQUIRE(done, IVL_ERR_INVALID_ARG, "%s: fsm_state needs done (a dead end is reported there)", fn);
-  IVL_REQUIRE(mask_ld * 32 >= (int64_t)V, IVL_ERR_INVALID_ARG, "%s: mask_ld=%lld words hold fewer than V=%d bits", fn,
-              (long long)mask_ld, V);
-  IVL_REQUIRE(n_states >= 1, IVL_ERR_INVALID_ARG, "%s: n_states=%d", fn, n_states);
-  const SmpCtl c = sample_rows_ctl(rep_penalty, seen, seen_ld, stop_ids, n_stop, budget, fill, n_new, done, history, hist_ld);
-  const SmpLp l = sample_rows_lp(logprob, n_top, top_ids, top_logprobs, cum_logprob, lp_history, top_hist_ids, top_hist_lp);
-  SmpFsm f;
-  f.state = fsm_state;
-  f.mask = fsm_mask;
-  f.mask_ld = mask_ld;
-  f.n_states = n_states;
-  f.desc = (const long long*)fsm_desc;
-  f.cls = fsm_cls;
-  f.trans = fsm_trans;
-  hipLaunchKernelGGL((sample_rows_kernel<SmpCtl, SmpLp, SmpFsm>), dim3((unsigned)S), dim3(SMP_THREADS), 0, (hipStream_t)stream,
-                     (const bf16_t*)logits, (long long)ld, V, temperature, (const int*)top_k, top_p, (const long long*)seed,
-                     (long long*)counter, (long long*)token, (long long)token_stride, (int*)n_kept, prob, c, l, f);
-  return check_launch(fn);
-}
-
-extern "C" int ivl_sample_rows_score_fwd(const void* logits, int64_t ld, int S, int V, const float* rep_penalty, const uint32_t* seen,
-                                         int64_t seen_ld, const int32_t* done, int n_top, int64_t* top_ids, float* top_logprobs,
-                                         void* stream) {
-  using namespace ivl;
-  const char* fn = "ivl_sample_rows_score_fwd";
-  IVL_REQUIRE(logits && top_ids && top_logprobs, IVL_ERR_INVALID_ARG, "%s: NULL pointer", fn);
-  IVL_REQUIRE(S >= 1 && V >= 1 && ld >= (int64_t)V, IVL_ERR_INVALID_ARG, "%s: S=%d V=%d ld=%lld", fn, S, V, (long long)ld);
-  IVL_REQUIRE(V < (1 << 23), IVL_ERR_UNSUPPORTED, "%s: V=%d (the Q40 sums are sized for V < 2^23)", fn, V);
-  IVL_REQUIRE(!rep_penalty || seen, IVL_ERR_INVALID_ARG, "%s: rep_penalty needs seen", fn);
-  IVL_REQUIRE(!seen || seen_ld * 32 >= (int64_t)V, IVL_ERR_INVALID_ARG, "%s: seen_ld=%lld words hold fewer than V=%d bits", fn,
-              (long long)seen_ld, V);
-  IVL_REQUIRE(n_top >= 1 && n_top <= SMP_TOP_MAX, IVL_ERR_INVALID_ARG, "%s: n_top=%d outside 1..%d", fn, n_top, SMP_TOP_MAX);
-  // the kernel of this form reads `seen` and `done` and writes neither (smp_after is not part of it)
-  const SmpCtl c = sample_rows_ctl(rep_penalty, const_cast<uint32_t*>(seen), seen_ld, nullptr, 0, nullptr, nullptr, nullptr,
-                                   const_cast<int32_t*>(done), nullptr, 0);
-  SmpLp l;
-  l.logprob = nullptr;
-  l.n_top = n_top;
-  l.top_ids = (long long*)top_ids;
-  l.top_lp = top_logprobs;
-  l.cum = nullptr;
-  l.lp_hist = nullptr;
-  l.top_hist_ids = nullptr;
-  l.top_hist_lp = nullptr;
-  hipLaunchKernelGGL((sample_rows_kernel<SmpCtl, SmpLp, SmpScore>), dim3((unsigned)S), dim3(SMP_THREADS), 0, (hipStream_t)stream,
-                     (const bf16_t*)logits, (long long)ld, V, (const float*)nullptr, (const int*)nullptr, (const float*)nullptr,
-                     (const long long*)nullptr, (long long*)nullptr, (long long*)nullptr, 0ll, (int*)nullptr, (float*)nullptr, c, l,
-                     SmpScore{});
+  static const char fn[] = "ivl_sample_rows_fwd";
+  IVL_REQUIRE(args, IVL_ERR_INVALID_ARG, "%s: NULL args", fn);
+  const ivl_sample_args& a = *args;
+  const bool score = a.score_only != 0;
+  const bool ring = a.lp_history || a.top_hist_ids || a.top_hist_lp;
+  // ---- base
+  IVL_REQUIRE(a.logits && (score ? a.top_ids && a.top_logprobs
+                                 : a.temperature && a.top_k && a.top_p && a.seed && a.counter && a.token),
+              IVL_ERR_INVALID_ARG, "%s: NULL pointer", fn);
+  IVL_REQUIRE(a.S >= 1 && a.V >= 1 && a.ld >= (int64_t)a.V, IVL_ERR_INVALID_ARG, "%s: S=%d V=%d ld=%lld", fn, a.S, a.V,
+              (long long)a.ld);
+  IVL_REQUIRE(a.V < (1 << 23), IVL_ERR_UNSUPPORTED, "%s: V=%d (the Q40 sums are sized for V < 2^23)", fn, a.V);
+  if (score)                                             // nothing is committed: a field that says otherwise is refused
+    IVL_REQUIRE(!a.temperature && !a.top_k && !a.top_p && !a.seed && !a.counter && !a.token && a.token_stride == 0 && !a.n_kept &&
+                    !a.prob && !a.stop_ids && a.n_stop == 0 && !a.budget && !a.fill && !a.n_new && !a.history && a.hist_ld == 0 &&
+                    !a.logprob && !a.cum_logprob && !ring && !a.fsm_state && !a.fsm_mask && a.mask_ld == 0 && a.n_states == 0 &&
+                    !a.fsm_desc && !a.fsm_cls && !a.fsm_trans,
+                IVL_ERR_INVALID_ARG, "%s: score_only takes logits, rep_penalty, seen, done and the top-N list alone", fn);
+  // ---- controls
+  IVL_REQUIRE(!a.rep_penalty || a.seen, IVL_ERR_INVALID_ARG, "%s: rep_penalty needs seen", fn);
+  IVL_REQUIRE(!a.seen || a.seen_ld * 32 >= (int64_t)a.V, IVL_ERR_INVALID_ARG, "%s: seen_ld=%lld words hold fewer than V=%d bits", fn,
+              (long long)a.seen_ld, a.V);
+  IVL_REQUIRE(a.n_stop >= 0 && a.n_stop <= 16, IVL_ERR_INVALID_ARG, "%s: n_stop=%d outside 0..16", fn, a.n_stop);
+  IVL_REQUIRE(a.n_stop == 0 || (a.stop_ids && a.done), IVL_ERR_INVALID_ARG, "%s: n_stop=%d needs stop_ids and done", fn, a.n_stop);
+  IVL_REQUIRE(!a.budget || (a.n_new && a.done), IVL_ERR_INVALID_ARG, "%s: budget needs n_new and done", fn);
+  IVL_REQUIRE(!a.history || (a.n_new && a.hist_ld >= 1), IVL_ERR_INVALID_ARG, "%s: history needs n_new and hist_ld >= 1 (%lld)", fn,
+              (long long)a.hist_ld);
+  // ---- scores
+  IVL_REQUIRE(a.n_top >= (score ? 1 : 0) && a.n_top <= SMP_TOP_MAX, IVL_ERR_INVALID_ARG, "%s: n_top=%d outside %d..%d", fn, a.n_top,
+              score ? 1 : 0, SMP_TOP_MAX);
+  IVL_REQUIRE(a.n_top == 0 || (a.top_ids && a.top_logprobs), IVL_ERR_INVALID_ARG, "%s: n_top=%d needs top_ids and top_logprobs", fn,
+              a.n_top);
+  IVL_REQUIRE(!(a.top_hist_ids || a.top_hist_lp) || a.n_top > 0, IVL_ERR_INVALID_ARG, "%s: the top rings need n_top > 0", fn);
+  IVL_REQUIRE(!ring || (a.n_new && a.hist_ld >= 1), IVL_ERR_INVALID_ARG,
+              "%s: lp_history and the top rings need n_new and hist_ld >= 1 (%lld)", fn, (long long)a.hist_ld);
+  // ---- constraint
+  if (a.fsm_state) {
+    IVL_REQUIRE(a.fsm_mask, IVL_ERR_INVALID_ARG, "%s: fsm_state needs fsm_mask", fn);
+    IVL_REQUIRE(a.fsm_desc, IVL_ERR_INVALID_ARG, "%s: fsm_state needs fsm_desc", fn);
+    IVL_REQUIRE(a.fsm_cls, IVL_ERR_INVALID_ARG, "%s: fsm_state needs fsm_cls", fn);
+    IVL_REQUIRE(a.fsm_trans, IVL_ERR_INVALID_ARG, "%s: fsm_state needs fsm_trans", fn);
+    IVL_REQUIRE(a.done, IVL_ERR_INVALID_ARG, "%s: fsm_state needs done (a dead end is reported there)", fn);
+    IVL_REQUIRE(a.mask_ld * 32 >= (int64_t)a.V, IVL_ERR_INVALID_ARG, "%s: mask_ld=%lld words hold fewer than V=%d bits", fn,
+                (long long)a.mask_ld, a.V);
+    IVL_REQUIRE(a.n_states >= 1, IVL_ERR_INVALID_ARG, "%s: n_states=%d", fn, a.n_states);
+  }
+  // ---- the device structs, each filled here and nowhere else, in the order of their fields (the score-only form reads seen
+  //      and done and writes neither)
+  const SmpCtl c = {a.rep_penalty, a.seen, a.seen_ld, (const long long*)a.stop_ids, a.n_stop, (const long long*)a.budget,
+                    (const long long*)a.fill, (long long*)a.n_new, a.done, (long long*)a.history, a.hist_ld};
+  const SmpLp l = {a.logprob, a.n_top, (long long*)a.top_ids, a.top_logprobs, a.cum_logprob, a.lp_history,
+                   (long long*)a.top_hist_ids, a.top_hist_lp};
+  const SmpFsm f = {a.fsm_state, a.fsm_mask, a.mask_ld, a.n_states, (const long long*)a.fsm_desc, a.fsm_cls, a.fsm_trans};
+  // ---- the form: `fill` and the scalars (seen_ld, hist_ld, mask_ld, n_states) select nothing
+  if (score)
+    sample_rows_launch(a, stream, c, l, SmpScore{});
+  else if (a.fsm_state)
+    sample_rows_launch(a, stream, c, l, f);
+  else if (a.logprob || a.n_top > 0 || a.top_ids || a.top_logprobs || a.cum_logprob || ring)
+    sample_rows_launch(a, stream, c, l);
+  else if (a.rep_penalty || a.seen || a.n_stop > 0 || a.budget || a.n_new || a.done || a.history)
+    sample_rows_launch(a, stream, c);
+  else
+    sample_rows_launch(a, stream);
   return check_launch(fn);
 }
 

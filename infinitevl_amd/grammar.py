@@ -1,7 +1,7 @@
 """Token-level finite state machines for constrained decoding: the host side (numpy only, no device work).
 
 A `TokenFsm` says, per state, which tokens a stream may emit and where each of them leads.  The sampling launch
-(ivl_sample_rows_fsm_fwd in include/ivl_hip.h) reads its compact tables on the device: the allowed-token bitmap of the row's
+(ivl_sample_rows_fwd in include/ivl_hip.h) reads its compact tables on the device: the allowed-token bitmap of the row's
 state restricts the draw, and the emitted token advances the state, with no host round trip per token.  This is what HF
 generate's `prefix_allowed_tokens_fn` serves (INTEGRATION.md maps one onto the other).
 

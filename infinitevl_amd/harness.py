@@ -490,7 +490,7 @@ class Sampler:
     The generation arguments of the reference (do_sample / temperature / top_p / top_k: api/chat.py:160-162) map onto set().
 
     Generation controls (repetition_penalty / eos_token_id / max_new_tokens of chat/hf_engine.py:128-156) live in the same
-    table and act inside the same launch (ivl_sample_rows_ctl_fwd): a sampler built with `vocab_size` (the bitmap of seen
+    table and act inside the same launch (ivl_sample_rows_fwd): a sampler built with `vocab_size` (the bitmap of seen
     tokens the penalty needs) or `history` (a ring of the last `history` tokens per row) uses the controlled launch; one
     built without either samples exactly as before, until a row is given stop ids or a budget -- set that before the step is
     captured (the graphed classes recapture when they see the switch).  The kernel keeps n_new (tokens generated) and done
@@ -498,14 +498,14 @@ class Sampler:
 
     Scores (`logprobs` / `top_logprobs` of the reference's api/protocol.py, output_scores of HF generate): a sampler built
     with `logprobs` = 0 (the emitted token's log-probability) or 1..20 (that plus the N most likely alternatives) uses the
-    scoring launch (ivl_sample_rows_lp_fwd) from construction on, so no recapture is involved: `logprob`, `top_ids`,
+    scoring form of that launch from construction on, so no recapture is involved: `logprob`, `top_ids`,
     `top_logprob` hold the latest step's scores, `cum_logprob` (float64) their sum per row since set(), and with `history`
     logprobs() / top_logprobs() return them token for token beside tokens().  The scored distribution is the one after the
     repetition penalty and before temperature / top-k / top-p.  None = off: the sampler launches what it always did.
 
     Constrained decoding (what HF generate takes as prefix_allowed_tokens_fn, without the token on the host): a sampler built
     with `grammar_states` > 0 (and vocab_size) owns an ops.FsmTables arena of that many states and one more per-row tensor,
-    `fsm_state` (-1 = unconstrained), and uses the constrained launch (ivl_sample_rows_fsm_fwd) from construction on, so no
+    `fsm_state` (-1 = unconstrained), and uses the constrained form of that launch from construction on, so no
     recapture is involved: load_grammar() puts a grammar.TokenFsm into the arena, set_grammar() points a row at it, and the
     kernel restricts the row's draw to the tokens its state allows and advances the state with the token it emits.  A grammar
     loaded and set between two replays of a captured step is obeyed by the next one.  A row whose state allows nothing ends with

@@ -25,7 +25,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from ._lib import IVL_BF16, IVL_F32, IVL_FP8_E4M3, SwaArgs
+from ._lib import IVL_BF16, IVL_F32, IVL_FP8_E4M3, SampleArgs, SwaArgs
 
 _DT_CODE = {torch.bfloat16: IVL_BF16, torch.float32: IVL_F32}
 _MMA_CODE = {None: IVL_BF16, "bf16": IVL_BF16, torch.bfloat16: IVL_BF16, "fp8": IVL_FP8_E4M3, "fp8_e4m3": IVL_FP8_E4M3,
@@ -1195,6 +1195,21 @@ def swa_attention_interface(module, query, key, value, attention_mask=None, drop
 # ---------------------------------------------------------------------------------------------
 # sampling
 # ---------------------------------------------------------------------------------------------
+def _sample_args(logits: torch.Tensor, tensors: dict, **scalars) -> SampleArgs:
+    """ivl_sample_args of a call over logits [S,V]: the row, the tensors that are given (by field name; None = NULL = off) and
+    the scalar fields; what is not named stays 0."""
+    S, V = logits.shape
+    a = SampleArgs(ld=logits.stride(0) if S > 1 else V, S=S, V=V, **scalars)
+    a.logits = logits.data_ptr()
+    for name, t in tensors.items():
+        if t is not None:
+            setattr(a, name, t.data_ptr())
+    seen = tensors.get("seen")
+    if seen is not None:
+        a.seen_ld = seen.stride(0) if S > 1 else seen.shape[1]
+    return a
+
+
 def sample_tokens(logits: torch.Tensor, temperature: torch.Tensor, top_k: torch.Tensor, top_p: torch.Tensor, seed: torch.Tensor,
                   counter: torch.Tensor, out: Optional[torch.Tensor] = None, n_kept: Optional[torch.Tensor] = None,
                   prob: Optional[torch.Tensor] = None, *, rep_penalty: Optional[torch.Tensor] = None,
@@ -1213,14 +1228,14 @@ def sample_tokens(logits: torch.Tensor, temperature: torch.Tensor, top_k: torch.
     kernel for every row that draws: the token is a pure function of (logits, parameters, seed, counter).  `out`: int64 [S]
     or [S,1], written in place and returned (default: a new [S]); n_kept [S] int32 and prob [S] fp32 are optional outputs.
 
-    The keyword-only generation controls (ivl_sample_rows_ctl_fwd states the semantics; repetition_penalty / eos_token_id /
+    The keyword-only generation controls (CONTROLS of ivl_sample_rows_fwd; repetition_penalty / eos_token_id /
     max_new_tokens of the reference's chat/hf_engine.py:128-156), each optional: rep_penalty [S] fp32 with seen [S,W] int32
     (a bitmap of W >= ceil(V/32) words per row, updated by the kernel); stop_ids [S,n] int64 (n <= 16, entries < 0 unused),
     budget [S] int64 (< 0: none) and fill [S] int64 with the state n_new [S] int64, done [S] int32 (0 running, 1 stop id,
     2 budget; a finished row gets its fill token and nothing else of it is touched) and history [S,H] int64 (a ring of the
     last H tokens).  With none given this is the control-free launch.
 
-    The keyword-only scores (ivl_sample_rows_lp_fwd states the semantics; `logprobs` / `top_logprobs` of the reference's
+    The keyword-only scores (SCORES of ivl_sample_rows_fwd; `logprobs` / `top_logprobs` of the reference's
     api/protocol.py, output_scores of HF generate), each optional, of the distribution after the repetition penalty and before
     temperature / top-k / top-p: logprob [S] fp32 (of the token written); top_ids [S,N] int64 with top_logprobs [S,N] fp32
     (0 < N <= 20: the N most likely tokens, most likely first, ties to the lowest id; id -1 / -inf past V); cum_logprob [S]
@@ -1228,7 +1243,7 @@ def sample_tokens(logits: torch.Tensor, temperature: torch.Tensor, top_k: torch.
     top_hist_ids [S,H,N] int64 and top_hist_lp [S,H,N] fp32 (the H of `history` when that is given too).  With any of them
     given the launch is the scoring form; the token and every control's state are those of the call without them.
 
-    The keyword-only constraint (ivl_sample_rows_fsm_fwd states the semantics; HF generate's prefix_allowed_tokens_fn without
+    The keyword-only constraint (CONSTRAINT of ivl_sample_rows_fwd; HF generate's prefix_allowed_tokens_fn without
     the token on the host): fsm_state [S] int32, per row a state of the tables `fsm` or -1 = unconstrained, advanced by the
     kernel with the token it emits; `fsm`: an FsmTables, or any holder of mask int32 [n_states, mask_ld] (mask_ld * 32 >= V),
     desc int64 [n_states, 2], cls int32 and trans int32 (flat), with mask_ld and n_states.  A row in state q draws from the
@@ -1270,6 +1285,8 @@ def sample_tokens(logits: torch.Tensor, temperature: torch.Tensor, top_k: torch.
         raise ValueError("sample_tokens: budget needs n_new and done")
     if history is not None and (n_new is None or history.shape[1] < 1):
         raise ValueError("sample_tokens: history needs n_new and at least one entry per row")
+    if history is not None and S > 1 and history.stride(0) != history.shape[1]:      # hist_ld is the ring's length AND its row pitch
+        raise ValueError(f"sample_tokens: history must be contiguous; got {tuple(history.shape)} strides {history.stride()}")
     scores = (logprob, top_ids, top_logprobs, cum_logprob, lp_history, top_hist_ids, top_hist_lp)
     n_top, hist_ld = 0, (0 if history is None else history.shape[1])
     if any(t is not None for t in scores):
@@ -1298,17 +1315,14 @@ def sample_tokens(logits: torch.Tensor, temperature: torch.Tensor, top_k: torch.
             if t.dtype != dt or tuple(t.shape) != want or hist_ld < 1 or not t.is_contiguous():
                 raise ValueError(f"sample_tokens: {name} must be a contiguous {dt} tensor of {list(want)} (the history's "
                                  f"length, at least 1); got {t.dtype} {tuple(t.shape)}")
-        if history is not None and any(t is not None for _, t, _, _ in rings) and S > 1 and history.stride(0) != hist_ld:
-            raise ValueError("sample_tokens: with lp_history or the top rings, history must be contiguous")
-    tables = ()
     if (fsm_state is None) != (fsm is None):
         raise ValueError("sample_tokens: fsm_state and fsm come together")
     if fsm is not None:
         if done is None:
             raise ValueError("sample_tokens: fsm_state needs done (a dead end is reported there)")
-        tables = (fsm.mask, fsm.desc, fsm.cls, fsm.trans)
         n_states, mask_ld = int(fsm.n_states), int(fsm.mask_ld)
-        for name, t, dt in zip(("mask", "desc", "cls", "trans"), tables, (torch.int32, torch.int64, torch.int32, torch.int32)):
+        for name, t, dt in (("mask", fsm.mask, torch.int32), ("desc", fsm.desc, torch.int64), ("cls", fsm.cls, torch.int32),
+                            ("trans", fsm.trans, torch.int32)):
             if not isinstance(t, torch.Tensor) or t.dtype != dt or not t.is_contiguous():
                 raise ValueError(f"sample_tokens: fsm.{name} must be a contiguous {dt} tensor")
         if n_states < 1 or tuple(fsm.mask.shape) != (n_states, mask_ld) or tuple(fsm.desc.shape) != (n_states, 2):
@@ -1320,30 +1334,17 @@ def sample_tokens(logits: torch.Tensor, temperature: torch.Tensor, top_k: torch.
         out = torch.empty(S, dtype=torch.int64, device=logits.device)
     if out.dtype != torch.int64 or tuple(out.shape) not in ((S,), (S, 1)):
         raise ValueError(f"sample_tokens: out must be int64 [{S}] or [{S},1]; got {out.dtype} {tuple(out.shape)}")
-    controls = (rep_penalty, seen, stop_ids, budget, fill, n_new, done, history)
-    _need_gpu(logits, temperature, top_k, top_p, seed, counter, out, n_kept, prob, *controls, *scores, fsm_state, *tables)
-    if fsm is not None or any(t is not None for t in scores):
-        args = (_p(logits), logits.stride(0) if S > 1 else V, S, V, _p(temperature), _p(top_k), _p(top_p), _p(seed), _p(counter),
-                _p(out), out.stride(0) if S > 1 else 1, _p(n_kept), _p(prob), _p(rep_penalty), _p(seen),
-                0 if seen is None else (seen.stride(0) if S > 1 else seen.shape[1]), _p(stop_ids), n_stop, _p(budget), _p(fill),
-                _p(n_new), _p(done), _p(history), hist_ld, _p(logprob), n_top, _p(top_ids), _p(top_logprobs), _p(cum_logprob),
-                _p(lp_history), _p(top_hist_ids), _p(top_hist_lp))
-        if fsm is not None:
-            _lib.check(_lib.load().ivl_sample_rows_fsm_fwd(*args, _p(fsm_state), _p(fsm.mask), mask_ld, n_states, _p(fsm.desc),
-                                                           _p(fsm.cls), _p(fsm.trans), _stream(logits)))
-        else:
-            _lib.check(_lib.load().ivl_sample_rows_lp_fwd(*args, _stream(logits)))
-        return out
-    if all(t is None for t in controls):
-        _lib.check(_lib.load().ivl_sample_rows_fwd(
-            _p(logits), logits.stride(0) if S > 1 else V, S, V, _p(temperature), _p(top_k), _p(top_p), _p(seed), _p(counter),
-            _p(out), out.stride(0) if S > 1 else 1, _p(n_kept), _p(prob), _stream(logits)))
-        return out
-    _lib.check(_lib.load().ivl_sample_rows_ctl_fwd(
-        _p(logits), logits.stride(0) if S > 1 else V, S, V, _p(temperature), _p(top_k), _p(top_p), _p(seed), _p(counter),
-        _p(out), out.stride(0) if S > 1 else 1, _p(n_kept), _p(prob), _p(rep_penalty), _p(seen),
-        0 if seen is None else (seen.stride(0) if S > 1 else seen.shape[1]), _p(stop_ids), n_stop, _p(budget), _p(fill), _p(n_new),
-        _p(done), _p(history), 0 if history is None else (history.stride(0) if S > 1 else history.shape[1]), _stream(logits)))
+    tensors = dict(temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, counter=counter, token=out, n_kept=n_kept, prob=prob,
+                   rep_penalty=rep_penalty, seen=seen, stop_ids=stop_ids, budget=budget, fill=fill, n_new=n_new, done=done,
+                   history=history, logprob=logprob, top_ids=top_ids, top_logprobs=top_logprobs, cum_logprob=cum_logprob,
+                   lp_history=lp_history, top_hist_ids=top_hist_ids, top_hist_lp=top_hist_lp, fsm_state=fsm_state)
+    if fsm is not None:
+        tensors.update(fsm_mask=fsm.mask, fsm_desc=fsm.desc, fsm_cls=fsm.cls, fsm_trans=fsm.trans)
+    _need_gpu(logits, *tensors.values())
+    a = _sample_args(logits, tensors, token_stride=out.stride(0) if S > 1 else 1, n_stop=n_stop, hist_ld=hist_ld, n_top=n_top)
+    if fsm is not None:
+        a.mask_ld, a.n_states = mask_ld, n_states
+    _lib.check(_lib.load().ivl_sample_rows_fwd(ctypes.byref(a), _stream(logits)))
     return out
 
 
@@ -1358,7 +1359,7 @@ class FsmHandle(NamedTuple):
 
 
 class FsmTables:
-    """The device tables of ivl_sample_rows_fsm_fwd as ONE arena for several grammars (grammar.TokenFsm), allocated once: room
+    """The device tables of ivl_sample_args' constraint group as ONE arena for several grammars (grammar.TokenFsm), allocated once: room
     for `states` states in all, `grammars` grammars at a time (one class table of vocab_size entries each) and `trans`
     transition entries (a grammar takes n_states x n_classes of them).  load() writes a grammar at a free range, its transition
     targets rebased to global state indices; unload() frees the range and clears its bitmaps, so a row left in one of its
@@ -1559,7 +1560,7 @@ def score_tokens(logits: torch.Tensor, top_ids: torch.Tensor, top_logprobs: torc
                  rep_penalty: Optional[torch.Tensor] = None, seen: Optional[torch.Tensor] = None,
                  done: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """The N most likely tokens per row of lm_head logits [S,V] or [S,1,V] (bf16) with their log-probabilities, and NOTHING
-    else: no token, no counter, no seen bit (ivl_sample_rows_score_fwd; the candidate lists of a beam search step).  top_ids
+    else: no token, no counter, no seen bit (ivl_sample_rows_fwd, score_only; the candidate lists of a beam search step).  top_ids
     int64 / top_logprobs fp32 [S,N], 1 <= N <= 20, written in place and returned: bit-equal to what sample_tokens(...,
     top_ids=, top_logprobs=) writes for the same (logits, rep_penalty, seen).  rep_penalty [S] fp32 with seen [S,W] int32
     (read only); done [S] int32 (read only): a row with done != 0 gets ids -1 and -inf."""
@@ -1589,10 +1590,9 @@ def score_tokens(logits: torch.Tensor, top_ids: torch.Tensor, top_logprobs: torc
     if rep_penalty is not None and seen is None:
         raise ValueError("score_tokens: rep_penalty needs the seen bitmap")
     _need_gpu(logits, top_ids, top_logprobs, rep_penalty, seen, done)
-    _lib.check(_lib.load().ivl_sample_rows_score_fwd(
-        _p(logits), logits.stride(0) if S > 1 else V, S, V, _p(rep_penalty), _p(seen),
-        0 if seen is None else (seen.stride(0) if S > 1 else seen.shape[1]), _p(done), n_top, _p(top_ids), _p(top_logprobs),
-        _stream(logits)))
+    a = _sample_args(logits, dict(rep_penalty=rep_penalty, seen=seen, done=done, top_ids=top_ids, top_logprobs=top_logprobs),
+                     n_top=n_top, score_only=1)
+    _lib.check(_lib.load().ivl_sample_rows_fwd(ctypes.byref(a), _stream(logits)))
     return top_ids, top_logprobs
 
 

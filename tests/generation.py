@@ -1,4 +1,4 @@
-"""Reference, input builders and the judge for the generation controls of ivl_sample_rows_ctl_fwd / ops.sample_tokens (CPU only,
+"""Reference, input builders and the judge for the generation controls of ivl_sample_rows_fwd / ops.sample_tokens (CPU only,
 numpy / torch): repetition penalty, stop ids, token budget.
 
 The penalty is evaluated with exactly the header's arithmetic: fp32 on the widened bf16 logit, x < 0 ? x * r : x / r, one

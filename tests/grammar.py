@@ -1,4 +1,4 @@
-"""Reference, input builders and the judge for constrained decoding: ivl_sample_rows_fsm_fwd / ops.sample_tokens(fsm_state=, fsm=)
+"""Reference, input builders and the judge for constrained decoding: ivl_sample_rows_fwd / ops.sample_tokens(fsm_state=, fsm=)
 (CPU only, numpy / torch).
 
 A constrained row IS its allowed sub-vocabulary A (F1 of the header), so nothing new is judged by a new rule: `gather` takes

@@ -1,4 +1,4 @@
-"""Reference and judge for the scores of ivl_sample_rows_lp_fwd / ops.sample_tokens(logprob=, top_ids=, ...) (CPU only, numpy /
+"""Reference and judge for the scores of ivl_sample_rows_fwd / ops.sample_tokens(logprob=, top_ids=, ...) (CPU only, numpy /
 torch): the log-probability of the emitted token and the N most likely alternatives.
 
 The scored distribution is the row as the kernel keys it: the bf16 row after generation.penalise (where a penalty applies), NaN as

@@ -26,6 +26,7 @@ What is judged, and why the bounds are what they are (none is fitted to the kern
 """
 from __future__ import annotations
 
+import ctypes
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence
 
@@ -287,3 +288,28 @@ def hf_kept(x: torch.Tensor, tau: float, k: int, p: float) -> np.ndarray:
         remove[-1:] = False
         s = s.masked_fill(torch.zeros(V, dtype=torch.bool).scatter(0, idx, remove), -float("inf"))
     return (s > -float("inf")).numpy()
+
+
+# ---------------------------------------------------------------------------------------------
+# the C entry point on pointers that are never dereferenced (validation fails first)
+# ---------------------------------------------------------------------------------------------
+ONE = 0x1000
+ARG_FIELDS = ("logits ld S V "
+              "temperature top_k top_p seed counter token token_stride n_kept prob "
+              "rep_penalty seen seen_ld stop_ids n_stop budget fill n_new done history hist_ld "
+              "logprob n_top top_ids top_logprobs cum_logprob lp_history top_hist_ids top_hist_lp "
+              "fsm_state fsm_mask mask_ld n_states fsm_desc fsm_cls fsm_trans score_only").split()
+
+
+def c_call(lib, V: int = 64, **fields) -> int:
+    """ivl_sample_rows_fwd on an ivl_sample_args that holds what the control-free call requires (S = 1, ld = V, token_stride = 1,
+    every required pointer ONE) with `fields` on top (None = NULL); everything else is 0 / NULL."""
+    from infinitevl_amd import _lib
+    base = dict(logits=ONE, ld=V, S=1, V=V, temperature=ONE, top_k=ONE, top_p=ONE, seed=ONE, counter=ONE, token=ONE, token_stride=1)
+    return lib.ivl_sample_rows_fwd(ctypes.byref(_lib.SampleArgs(**{**base, **fields})), None)
+
+
+def c_refused(lib, code: int, word: bytes, **fields) -> bool:
+    """c_call(**fields) returns `code` and ivl_last_error() names the entry point and `word`"""
+    rc, err = c_call(lib, **fields), lib.ivl_last_error()
+    return rc == code and b"ivl_sample_rows_fwd" in err and word in err

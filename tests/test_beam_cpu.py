@@ -12,9 +12,10 @@ import torch
 
 import beam
 import fork as fk
+import sampling
 from conftest import ROOT
 
-NEW = ("ivl_sample_rows_score_fwd", "ivl_rows_gather_fwd", "ivl_beam_select_fwd", "ivl_beam_commit_fwd")
+NEW = ("ivl_rows_gather_fwd", "ivl_beam_select_fwd", "ivl_beam_commit_fwd")      # (the score-only form: ivl_sample_rows_fwd)
 
 
 @pytest.fixture(scope="module")
@@ -152,14 +153,16 @@ def test_the_synthetic_cases_stay_under_the_contested_cap_and_cover_the_rules():
 # ---------------------------------------------------------------------------------------------
 # header, binding, library
 # ---------------------------------------------------------------------------------------------
-def test_header_yields_the_four_prototypes_and_the_abi_stays_11(lib):
+def test_header_yields_the_prototypes_and_the_abi_version(lib):
     from infinitevl_amd import _lib
     hdr = open(os.path.join(ROOT, "include", "ivl_hip.h")).read()
-    consts, _, protos = _lib.parse_header(hdr)
-    assert consts["IVL_ABI_VERSION"] == 11 and lib.ivl_abi_version() == 11
+    structs = {}
+    consts, _, protos = _lib.parse_header(hdr, structs)
+    assert consts["IVL_ABI_VERSION"] == 12 and lib.ivl_abi_version() == 12
     vp, i, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
     assert protos["ivl_rows_gather_fwd"] == (i, [vp, i, i64, i, i, vp, vp])
-    assert protos["ivl_sample_rows_score_fwd"] == (i, [vp, i64, i, i, vp, vp, i64, vp, i, vp, vp, vp])
+    assert protos["ivl_sample_rows_fwd"] == (i, [ctypes.POINTER(structs["ivl_sample_args"]), vp])
+    assert structs["ivl_sample_args"]._fields_[-1] == ("score_only", i)
     assert protos["ivl_beam_select_fwd"] == (i, [i, i, i, i64, vp, vp, vp, vp, vp, i64, vp, i, vp, vp] + [vp] * 9 + [vp])
     assert protos["ivl_beam_commit_fwd"] == (i, [i, i, i64, vp, vp, vp, i64, vp, i64, i64, vp, i64, vp, vp, vp, vp] + [vp] * 7 + [vp])
     out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
@@ -191,17 +194,24 @@ def test_gather_entry_point_refuses_bad_arguments(lib):
 def test_score_entry_point_refuses_bad_arguments(lib):
     from infinitevl_amd import _lib
     INV, UNS = _lib.IVL_ERR_INVALID_ARG, _lib.IVL_ERR_UNSUPPORTED
-    one = ctypes.c_void_p(0x1000)
-    good = dict(logits=one, ld=1000, S=2, V=1000, rep=one, seen=one, seen_ld=32, done=one, n_top=8, ids=one, lps=one)
-    for kw, code, word in (({"logits": None}, INV, b"NULL"), ({"ids": None}, INV, b"NULL"), ({"lps": None}, INV, b"NULL"),
+    one = sampling.ONE
+    sampled = dict.fromkeys(("temperature", "top_k", "top_p", "seed", "counter", "token"))             # NULL in this form
+    good = dict(sampled, token_stride=0, score_only=1, ld=1000, S=2, V=1000, rep_penalty=one, seen=one, seen_ld=32, done=one,
+                n_top=8, top_ids=one, top_logprobs=one)
+    for kw, code, word in (({"logits": None}, INV, b"NULL"), ({"top_ids": None}, INV, b"NULL"),
+                           ({"top_logprobs": None}, INV, b"NULL"),
                            ({"S": 0}, INV, b"S=0"), ({"V": 0}, INV, b"V=0"), ({"ld": 999}, INV, b"ld=999"),
                            ({"seen": None}, INV, b"rep_penalty needs seen"), ({"seen_ld": 31}, INV, b"seen_ld"),
                            ({"n_top": 0}, INV, b"n_top"), ({"n_top": 21}, INV, b"n_top"),
                            ({"V": 1 << 23, "ld": 1 << 23, "seen_ld": 1 << 18}, UNS, b"2^23")):
-        a = dict(good, **kw)
-        rc = lib.ivl_sample_rows_score_fwd(a["logits"], a["ld"], a["S"], a["V"], a["rep"], a["seen"], a["seen_ld"], a["done"],
-                                           a["n_top"], a["ids"], a["lps"], None)
-        _expect(lib, rc, code, b"ivl_sample_rows_score_fwd", word, kw)
+        assert sampling.c_refused(lib, code, word, **dict(good, **kw)), kw
+    # a field outside the form's list that is set is refused, not ignored: pointers and scalars alike
+    own = ("logits", "ld", "S", "V", "rep_penalty", "seen", "seen_ld", "done", "n_top", "top_ids", "top_logprobs", "score_only")
+    foreign = [n for n in sampling.ARG_FIELDS if n not in own]
+    assert len(foreign) == 28
+    for name in foreign:
+        assert sampling.c_refused(lib, INV, b"score_only", **dict(good, **{name: one})), name
+    assert sampling.c_refused(lib, INV, b"NULL", **dict(good, score_only=0))                # the sampling forms' required pointers
 
 
 def test_beam_entry_points_refuse_bad_arguments(lib):

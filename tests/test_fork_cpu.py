@@ -26,13 +26,13 @@ def test_header_still_parses_and_the_symbol_is_declared_and_exported(lib):
     from infinitevl_amd import _lib
     hdr = open(os.path.join(ROOT, "include", "ivl_hip.h")).read()
     consts, _, protos = _lib.parse_header(hdr)
-    assert consts["IVL_ABI_VERSION"] == 11 and "ivl_rows_copy_fwd" in protos
+    assert consts["IVL_ABI_VERSION"] == 12 and "ivl_rows_copy_fwd" in protos
     assert "IVL_API int ivl_rows_copy_fwd(" in hdr and "ivl_rows_copy_fwd" in _lib.EXPORTED_SYMBOLS
     vp = ctypes.c_void_p
     assert _lib.PROTOTYPES["ivl_rows_copy_fwd"] == (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, vp])
     out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
     assert "ivl_rows_copy_fwd" in {ln.split()[-1] for ln in out.splitlines() if ln.strip()}
-    assert lib.ivl_abi_version() == 11
+    assert lib.ivl_abi_version() == 12
 
 
 def test_entry_point_refuses_bad_arguments(lib):

@@ -232,46 +232,57 @@ def test_ops_refuse_cpu_tensors_and_bad_control_arguments():
             ops.mark_tokens(*a)
 
 
+def test_ops_refuse_a_padded_history_with_and_without_scores():
+    """hist_ld is the ring's length AND its row pitch on the device (smp_after: history[s * hist_ld + n_new % hist_ld]), so a
+    history whose rows lie further apart than they are long is refused on every path, before the device is looked at."""
+    from infinitevl_amd import ops
+    S, V, H = 2, 40, 4
+    lg = torch.zeros(S, V, dtype=torch.bfloat16)
+    tab = (torch.zeros(S), torch.zeros(S, dtype=torch.int32), torch.ones(S), torch.zeros(S, dtype=torch.int64),
+           torch.zeros(S, dtype=torch.int64))
+    n_new, padded = torch.zeros(S, dtype=torch.int64), torch.zeros(S, H + 2, dtype=torch.int64)[:, :H]
+    assert padded.stride() == (H + 2, 1)
+    for scores in ({}, {"logprob": torch.zeros(S)}, {"lp_history": torch.zeros(S, H)}):
+        with pytest.raises(ValueError, match="history must be contiguous"):
+            ops.sample_tokens(lg, *tab, n_new=n_new, history=padded, **scores)
+        with pytest.raises(RuntimeError, match="no CPU fallback"):                # one row, or rows that touch: nothing to refuse
+            ops.sample_tokens(lg[:1], *(t[:1] for t in tab), n_new=n_new[:1], history=padded[:1],
+                              **{k: v[:1] for k, v in scores.items()})
+        with pytest.raises(RuntimeError, match="no CPU fallback"):
+            ops.sample_tokens(lg, *tab, n_new=n_new, history=padded.contiguous(), **scores)
+
+
 # ---------------------------------------------------------------------------------------------
 # the C entry points
 # ---------------------------------------------------------------------------------------------
 def test_entry_points_validate_and_are_exported(lib):
     from infinitevl_amd import _lib
-    one = ctypes.c_void_p(0x1000)       # never dereferenced: validation fails first
-    INV = _lib.IVL_ERR_INVALID_ARG
-    base = [one, 64, 1, 64, one, one, one, one, one, one, 1, None, None]
-    # rep_penalty, seen, seen_ld, stop_ids, n_stop, budget, fill, n_new, done, history, hist_ld, stream
-    off = [None, None, 0, None, 0, None, None, None, None, None, 0, None]
+    one, INV = sampling.ONE, _lib.IVL_ERR_INVALID_ARG
+    assert sampling.ARG_FIELDS[13:24] == ["rep_penalty", "seen", "seen_ld", "stop_ids", "n_stop", "budget", "fill", "n_new", "done",
+                                          "history", "hist_ld"]
 
-    def call(**kw):
-        names = ("rep_penalty", "seen", "seen_ld", "stop_ids", "n_stop", "budget", "fill", "n_new", "done", "history", "hist_ld")
-        ctl = list(off)
-        for n, v in kw.items():
-            ctl[names.index(n)] = v
-        return lib.ivl_sample_rows_ctl_fwd(*(base + ctl))
+    def refused(word, **kw):
+        return sampling.c_refused(lib, INV, word, **kw)
 
-    assert call(rep_penalty=one) == INV and b"seen" in lib.ivl_last_error()
-    assert call(rep_penalty=one, seen=one, seen_ld=1) == INV and b"seen_ld" in lib.ivl_last_error()      # 32 bits for V = 64
-    assert call(seen=one, seen_ld=1) == INV
-    assert call(n_stop=-1) == INV and call(n_stop=17, stop_ids=one, done=one) == INV and b"n_stop" in lib.ivl_last_error()
-    assert call(n_stop=2, done=one) == INV and call(n_stop=2, stop_ids=one) == INV
-    assert call(budget=one, done=one) == INV and call(budget=one, n_new=one) == INV and b"budget" in lib.ivl_last_error()
-    assert call(history=one, hist_ld=4) == INV
-    assert call(history=one, n_new=one, hist_ld=0) == INV and b"history" in lib.ivl_last_error()
-    for i in (0, 4, 5, 6, 7, 8, 9):     # every required pointer of the control-free call
-        args = list(base + off)
-        args[i] = None
-        assert lib.ivl_sample_rows_ctl_fwd(*args) == INV and b"NULL" in lib.ivl_last_error(), i
-    args = list(base + off)
-    args[1], args[3] = 1 << 24, 1 << 23
-    assert lib.ivl_sample_rows_ctl_fwd(*args) == _lib.IVL_ERR_UNSUPPORTED
+    assert refused(b"rep_penalty needs seen", rep_penalty=one)
+    assert refused(b"seen_ld", rep_penalty=one, seen=one, seen_ld=1)                                    # 32 bits for V = 64
+    assert refused(b"seen_ld", seen=one, seen_ld=1)
+    assert refused(b"n_stop=", n_stop=-1) and refused(b"n_stop=", n_stop=17, stop_ids=one, done=one)
+    assert refused(b"n_stop=", n_stop=2, done=one) and refused(b"n_stop=", n_stop=2, stop_ids=one)
+    assert refused(b"budget", budget=one, done=one) and refused(b"budget", budget=one, n_new=one)
+    assert refused(b"history", history=one, hist_ld=4)
+    assert refused(b"history", history=one, n_new=one, hist_ld=0)
+    for name in ("logits", "temperature", "top_k", "top_p", "seed", "counter", "token"):               # with a control on
+        assert refused(b"NULL", done=one, **{name: None}), name
+    assert sampling.c_refused(lib, _lib.IVL_ERR_UNSUPPORTED, b"2^23", V=1 << 23, ld=1 << 24, done=one)
+    one = ctypes.c_void_p(one)
     assert lib.ivl_token_mark_fwd(None, 64, one, 1, None) == INV
     assert lib.ivl_token_mark_fwd(one, 0, one, 1, None) == INV
     assert lib.ivl_token_mark_fwd(one, 64, one, -1, None) == INV
     assert lib.ivl_token_mark_fwd(one, 64, None, 1, None) == INV and b"ivl_token_mark_fwd" in lib.ivl_last_error()
     assert lib.ivl_token_mark_fwd(one, 64, None, 0, None) == _lib.IVL_OK                                 # n == 0: nothing launched
-    assert lib.ivl_abi_version() == _lib.IVL_ABI_VERSION == 11
+    assert lib.ivl_abi_version() == _lib.IVL_ABI_VERSION == 12
     out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
     exported = {ln.split()[-1] for ln in out.splitlines() if ln.strip()}
-    for name in ("ivl_sample_rows_ctl_fwd", "ivl_token_mark_fwd"):
+    for name in ("ivl_sample_rows_fwd", "ivl_token_mark_fwd"):
         assert name in _lib.EXPORTED_SYMBOLS and name in exported, name

@@ -1,6 +1,6 @@
 """GPU (-m gpu): beam search in the graphed multi-stream decode.
 
-  1. ops.score_tokens (ivl_sample_rows_score_fwd): the candidate lists are bit-equal to the scoring launch's, nothing is committed;
+  1. ops.score_tokens (ivl_sample_rows_fwd, score_only): the candidate lists are bit-equal to the scoring launch's, nothing is committed;
   2. ops.RowGatherPlan (ivl_rows_gather_fwd) against torch indexing, bit for bit: identity, swap, cycle, fan-out, B = 2, 3, 4, 8,
      row0 = 2, an out-of-range parent, and one captured graph replayed with two maps;
   3. ops.beam_select / ops.beam_commit against the plain-Python reference of tests/beam.py on ~200 seeded cases;

@@ -1,4 +1,4 @@
-"""GPU (-m gpu): the generation controls of the sampling launch (ops.sample_tokens keywords / ivl_sample_rows_ctl_fwd,
+"""GPU (-m gpu): the generation controls of the sampling launch (ops.sample_tokens keywords / the controls of ivl_sample_rows_fwd,
 ops.mark_tokens) and their use in the graphed decode steps, judged by tests/generation.py: the float64 reference and the bounds
 of tests/sampling.py on the penalised bf16 row, integer bookkeeping compared exactly.
 
@@ -7,7 +7,7 @@ of tests/sampling.py on the penalised bf16 row, integer bookkeeping compared exa
     words whose guard word and bits >= V are preset to ones; 32 draws per row, each judged; the bitmap after a call = before + the
     token's bit;
   * evolving bitmaps: a greedy chain of 16 distinct tokens, 32 sampled draws judged against the host-tracked set;
-  * equivalence: r = 1 with a bitmap, and every control NULL, against ivl_sample_rows_fwd bit for bit; a row alone and as row 3
+  * equivalence: r = 1 with a bitmap, and every group off, against the control-free call bit for bit; a row alone and as row 3
     of 4; the same call twice;
   * stop ids, budget, n_new, the history ring and its wrap, finished rows; mark_tokens;
   * GraphedMultiStreamDecode / GraphedDecode with a controlled Sampler: eager == replayed graph across a capture, capture() leaves
@@ -180,8 +180,8 @@ def test_evolving_bitmap_sampled_draws():
 # 3. equivalence and determinism
 # ---------------------------------------------------------------------------------------------
 def _plain_draws(cases, ld, shift, n, how):
-    """how: "old" = ops.sample_tokens without controls, "r1" = rep_penalty 1 with a bitmap, "null" = the controlled entry point
-    with every control NULL"""
+    """how: "old" = ops.sample_tokens without controls, "r1" = rep_penalty 1 with a bitmap, "null" = the entry point on an
+    ivl_sample_args whose three groups are off -- every pointer NULL but `fill`, every scalar of theirs set all the same"""
     from infinitevl_amd import _lib, ops
     S, V = len(cases), cases[0]["x"].shape[0]
     _, lg = _place([c["x"] for c in cases], ld, shift)
@@ -191,18 +191,18 @@ def _plain_draws(cases, ld, shift, n, how):
     pr = torch.full((n, S), -1.0, dtype=torch.float32, device=DEV)
     seen, _ = _bitmap([np.ones(V, dtype=bool)] * S, V)
     rp = torch.ones(S, dtype=torch.float32, device=DEV)
-    p_ = lambda t: ctypes.c_void_p(t.data_ptr())
+    fill = torch.full((S,), 7, dtype=torch.int64, device=DEV)
     for d in range(n):
         if how == "old":
             ops.sample_tokens(lg, *tab, out=tok[d], n_kept=nk[d], prob=pr[d])
         elif how == "r1":
             ops.sample_tokens(lg, *tab, out=tok[d], n_kept=nk[d], prob=pr[d], rep_penalty=rp, seen=seen)
         else:
-            rc = _lib.load().ivl_sample_rows_ctl_fwd(
-                p_(lg), lg.stride(0) if S > 1 else V, S, V, *[p_(t) for t in tab], p_(tok[d]), 1, p_(nk[d]), p_(pr[d]),
-                None, None, 0, None, 0, None, None, None, None, None, 0,
-                ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-            assert rc == 0
+            ptrs = dict(zip(("temperature", "top_k", "top_p", "seed", "counter"), tab), logits=lg, token=tok[d], n_kept=nk[d],
+                        prob=pr[d], fill=fill)
+            a = _lib.SampleArgs(ld=lg.stride(0) if S > 1 else V, S=S, V=V, token_stride=1, seen_ld=generation.words_for(V), hist_ld=4,
+                                mask_ld=generation.words_for(V), n_states=3, **{k: t.data_ptr() for k, t in ptrs.items()})
+            assert _lib.load().ivl_sample_rows_fwd(ctypes.byref(a), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)) == 0
     torch.cuda.synchronize()
     return tok.cpu().numpy(), nk.cpu().numpy(), pr.cpu().numpy(), tab[4].cpu().tolist()
 

@@ -1,4 +1,4 @@
-"""GPU (-m gpu): constrained decoding inside the sampling launch (ops.sample_tokens fsm_state= / fsm= -> ivl_sample_rows_fsm_fwd)
+"""GPU (-m gpu): constrained decoding inside the sampling launch (ops.sample_tokens fsm_state= / fsm= -> ivl_sample_rows_fwd)
 and its use in the graphed decode steps, judged by tests/grammar.py.
 
   * operator: V in {1, 97, 4099} and one row of 151936; calls of 1 .. 4 rows in a +inf surround at odd ld, shifted bases and

@@ -1,4 +1,4 @@
-"""GPU (-m gpu): the scores of the sampling launch (ops.sample_tokens logprob= / top_ids= / ... -> ivl_sample_rows_lp_fwd) and
+"""GPU (-m gpu): the scores of the sampling launch (ops.sample_tokens logprob= / top_ids= / ... -> ivl_sample_rows_fwd) and
 their use in the graphed decode steps, judged by tests/logprobs.py: float64 log-softmax of the (penalised) bf16 row, exact ids.
 
   * operator: V in {1, 97, 4099} and one row of 151936, n_top in {0, 1, 5, 20} (also > V), calls of 1 .. 4 rows in a +inf
@@ -222,12 +222,12 @@ def test_group_all_null_is_the_controlled_entry():
     n_new, done = torch.zeros(S, dtype=torch.int64, device=DEV), torch.zeros(S, dtype=torch.int32, device=DEV)
     tok = torch.full((S,), -1, dtype=torch.int64, device=DEV)
     nk, pr = torch.full((S,), -1, dtype=torch.int32, device=DEV), torch.full((S,), -1.0, device=DEV)
-    p_ = lambda t: ctypes.c_void_p(t.data_ptr())
-    rc = _lib.load().ivl_sample_rows_lp_fwd(
-        p_(lg), lg.stride(0), S, V, *[p_(t) for t in tab], p_(tok), 1, p_(nk), p_(pr), p_(rp), p_(seen), W, None, 0, None, p_(fill),
-        p_(n_new), p_(done), None, 0, None, 0, None, None, None, None, None, None,
-        ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    assert rc == 0
+    # the score and constraint groups off: their pointers NULL, their scalars (and hist_ld, without a history) set all the same
+    ptrs = dict(zip(("temperature", "top_k", "top_p", "seed", "counter"), tab), logits=lg, token=tok, n_kept=nk, prob=pr,
+                rep_penalty=rp, seen=seen, fill=fill, n_new=n_new, done=done)
+    a = _lib.SampleArgs(ld=lg.stride(0), S=S, V=V, token_stride=1, seen_ld=W, hist_ld=4, mask_ld=W, n_states=3,
+                        **{k: t.data_ptr() for k, t in ptrs.items()})
+    assert _lib.load().ivl_sample_rows_fwd(ctypes.byref(a), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)) == 0
     torch.cuda.synchronize()
     got = ([{"token": tok.cpu().numpy(), "n_kept": nk.cpu().numpy(), "prob": pr.cpu().numpy()}],
            {"counter": tab[4].cpu().numpy(), "seen": seen.cpu().numpy(), "n_new": n_new.cpu().numpy(), "done": done.cpu().numpy()})

@@ -1,10 +1,9 @@
 """CPU (-m "not gpu"): the host side of constrained decoding -- grammar.TokenFsm's three builders against tables written by hand,
-its token classes, tails and refusals; the header's declaration and the library's export of ivl_sample_rows_fsm_fwd with its
-error codes on pointers that are never dereferenced; the ABI version; ops.FsmTables, ops.sample_tokens' and Sampler's new
+its token classes, tails and refusals; the constraint group of ivl_sample_args and ivl_sample_rows_fwd's
+error codes for it on pointers that are never dereferenced; the ABI version; ops.FsmTables, ops.sample_tokens' and Sampler's new
 arguments; what the graphed classes refuse before any device work; and the builders of tests/grammar.py."""
 import ctypes
 import os
-import subprocess
 import types
 
 import numpy as np
@@ -211,56 +210,36 @@ def test_the_gpu_tests_cases_are_well_formed():
 # ---------------------------------------------------------------------------------------------
 def test_entry_point_is_declared_exported_and_validates(lib):
     from infinitevl_amd import _lib
-    hdr = open(os.path.join(ROOT, "include", "ivl_hip.h")).read()
-    assert "IVL_API int ivl_sample_rows_fsm_fwd(" in hdr
-    assert "ivl_sample_rows_fsm_fwd" in _lib.EXPORTED_SYMBOLS
-    ret, args = _lib.PROTOTYPES["ivl_sample_rows_fsm_fwd"]
-    lp = _lib.PROTOTYPES["ivl_sample_rows_lp_fwd"][1]
-    assert ret is ctypes.c_int and args[:len(lp) - 1] == lp[:-1] and len(args) == len(lp) + 7
-    assert args[len(lp) - 1:] == [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int] + [ctypes.c_void_p] * 4
-    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
-    assert "ivl_sample_rows_fsm_fwd" in {ln.split()[-1] for ln in out.splitlines() if ln.strip()}
-    assert lib.ivl_abi_version() == _lib.IVL_ABI_VERSION == 11
+    assert _lib.PROTOTYPES["ivl_sample_rows_fwd"] == (ctypes.c_int, [ctypes.POINTER(_lib.SampleArgs), ctypes.c_void_p])
+    assert [(n, t) for n, t in _lib.SampleArgs._fields_ if n in sampling.ARG_FIELDS[32:39]] == list(zip(
+        ("fsm_state", "fsm_mask", "mask_ld", "n_states", "fsm_desc", "fsm_cls", "fsm_trans"),
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int] + [ctypes.c_void_p] * 3))
+    assert lib.ivl_abi_version() == _lib.IVL_ABI_VERSION == 12
 
-    one = ctypes.c_void_p(0x1000)       # never dereferenced: validation fails first
-    INV = _lib.IVL_ERR_INVALID_ARG
-    V = 64
-    base = [one, V, 1, V, one, one, one, one, one, one, 1, None, None]
-    ctl = {"rep_penalty": None, "seen": None, "seen_ld": 0, "stop_ids": None, "n_stop": 0, "budget": None, "fill": None,
-           "n_new": None, "done": one, "history": None, "hist_ld": 0}
-    lpg = {"logprob": None, "n_top": 0, "top_ids": None, "top_logprobs": None, "cum_logprob": None, "lp_history": None,
-           "top_hist_ids": None, "top_hist_lp": None}
-    fsm = {"fsm_state": one, "fsm_mask": one, "mask_ld": 2, "n_states": 3, "fsm_desc": one, "fsm_cls": one, "fsm_trans": one}
+    one, INV = sampling.ONE, _lib.IVL_ERR_INVALID_ARG
+    fsm = {"done": one, "fsm_state": one, "fsm_mask": one, "mask_ld": 2, "n_states": 3, "fsm_desc": one, "fsm_cls": one,
+           "fsm_trans": one}
 
-    def call(**kw):
-        groups = [dict(ctl), dict(lpg), dict(fsm)]
-        for n, v in kw.items():
-            [g for g in groups if n in g][0][n] = v
-        return lib.ivl_sample_rows_fsm_fwd(*(base + [v for g in groups for v in g.values()] + [None]))
+    def refused(word, **kw):
+        return sampling.c_refused(lib, INV, word, **{**fsm, **kw})
 
     for name in ("fsm_mask", "fsm_desc", "fsm_cls", "fsm_trans", "done"):
-        assert call(**{name: None}) == INV and name.encode() in lib.ivl_last_error(), name
-    assert call(mask_ld=1) == INV and b"mask_ld" in lib.ivl_last_error()
-    assert call(mask_ld=0) == INV and call(mask_ld=-1) == INV
-    assert call(n_states=0) == INV and b"n_states" in lib.ivl_last_error()
-    assert call(n_states=-4) == INV
-    # whatever the scoring entry refuses
-    assert call(n_top=21, top_ids=one, top_logprobs=one) == INV and b"n_top" in lib.ivl_last_error()
-    assert call(n_top=5) == INV and b"top_ids" in lib.ivl_last_error()
-    assert call(lp_history=one, hist_ld=4) == INV and b"n_new" in lib.ivl_last_error()
-    assert call(rep_penalty=one) == INV and b"seen" in lib.ivl_last_error()
-    assert call(n_stop=17, stop_ids=one) == INV and call(budget=one) == INV and call(history=one, hist_ld=4) == INV
-    assert b"ivl_sample_rows_fsm_fwd" in lib.ivl_last_error()
-    for i in (0, 4, 5, 6, 7, 8, 9):     # every required pointer of the control-free call
-        a = base + list(ctl.values()) + list(lpg.values()) + list(fsm.values()) + [None]
-        a[i] = None
-        assert lib.ivl_sample_rows_fsm_fwd(*a) == INV and b"NULL" in lib.ivl_last_error(), i
-    a = base + list(ctl.values()) + list(lpg.values()) + list(fsm.values()) + [None]
-    a[1], a[3] = 1 << 24, 1 << 23
-    assert lib.ivl_sample_rows_fsm_fwd(*a) == _lib.IVL_ERR_UNSUPPORTED
-    # the group off: the scoring entry's own refusals, under its own name
-    assert call(fsm_state=None, done=None, n_top=21, top_ids=one, top_logprobs=one) == INV
-    assert b"ivl_sample_rows_lp_fwd" in lib.ivl_last_error()
+        assert refused(name.encode(), **{name: None}), name
+    assert refused(b"mask_ld", mask_ld=1) and refused(b"mask_ld", mask_ld=0) and refused(b"mask_ld", mask_ld=-1)
+    assert refused(b"n_states", n_states=0) and refused(b"n_states", n_states=-4)
+    # whatever the scores and the controls refuse
+    assert refused(b"n_top", n_top=21, top_ids=one, top_logprobs=one)
+    assert refused(b"top_ids", n_top=5)
+    assert refused(b"n_new", lp_history=one, hist_ld=4)
+    assert refused(b"rep_penalty needs seen", rep_penalty=one)
+    assert refused(b"n_stop=", n_stop=17, stop_ids=one) and refused(b"budget", budget=one)
+    assert refused(b"history", history=one, hist_ld=4)
+    for name in ("logits", "temperature", "top_k", "top_p", "seed", "counter", "token"):          # with the constraint on
+        assert refused(b"NULL", **{name: None}), name
+    assert sampling.c_refused(lib, _lib.IVL_ERR_UNSUPPORTED, b"2^23", **{**fsm, "V": 1 << 23, "ld": 1 << 24, "mask_ld": 1 << 18})
+    # the group off: its own checks do not apply (scalars alone select nothing), the others do
+    assert refused(b"n_top", fsm_state=None, done=None, n_top=21, top_ids=one, top_logprobs=one)
+    assert refused(b"n_top", fsm_state=None, fsm_mask=None, mask_ld=0, n_states=0, n_top=21, top_ids=one, top_logprobs=one)
 
 
 # ---------------------------------------------------------------------------------------------

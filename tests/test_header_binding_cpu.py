@@ -1,7 +1,7 @@
 """CPU (-m "not gpu"): the ctypes binding is what include/ivl_hip.h declares.  The header reader of infinitevl_amd/_lib.py on
 small synthetic headers (every type form the real header uses; an unknown type is an error that names it), on the real header
-(prototype count, constants), against a host C compiler (sizeof / offsetof of ivl_swa_args, the values of the constants),
-and `bind` on the built library and on a stand-in object that lacks a symbol."""
+(prototype count, constants), against a host C compiler (sizeof / offsetof of ivl_swa_args and ivl_sample_args, the values of the
+constants), and `bind` on the built library and on a stand-in object that lacks a symbol."""
 import ctypes
 import os
 import re
@@ -30,16 +30,24 @@ typedef struct ivl_swa_args {
   size_t workspace_bytes;
 } ivl_swa_args;
 """
+STRUCT2 = """
+typedef struct ivl_pick_args {
+  /* a group */
+  const float* w; int32_t* out;
+  int n, k;
+  int64_t ld;
+} ivl_pick_args;
+"""
 SYNTHETIC = """
 #ifndef IVL_HIP_H
 #define IVL_HIP_H
 #include <stddef.h>
 #define IVL_API __attribute__((visibility("default")))
-#define IVL_ABI_VERSION 11
+#define IVL_ABI_VERSION 12
 #define IVL_ERR_SYNC (-5)   /* a wait ran out (see ivl_f) */
 #define IVL_QUERY (-2147483647 - 1)
   #  define IVL_SUM (1 + (2 - -3))
-""" + STRUCT + """
+""" + STRUCT + STRUCT2 + """
 IVL_API int ivl_version(void);
 IVL_API const char* ivl_last_error(void);
 /* IVL_API int ivl_commented_out(int x); */
@@ -49,23 +57,29 @@ IVL_API int ivl_f(const void* x, void* y, const float* g, /* between, arguments 
           int n, float scale, size_t bytes, int64_t delta,   // trailing
           const int32_t *cu, void* stream);
 IVL_API int ivl_swa(const ivl_swa_args* args, void* stream);
+IVL_API int ivl_pick(const ivl_pick_args *args, const ivl_swa_args* other, void* stream);
 #endif
 """
 
 
 def test_reader_on_synthetic_headers():
-    consts, swa, protos = _lib.parse_header(SYNTHETIC)
-    assert consts == {"IVL_ABI_VERSION": 11, "IVL_ERR_SYNC": -5, "IVL_QUERY": -2 ** 31, "IVL_SUM": 6}
-    assert issubclass(swa, ctypes.Structure)
+    structs = {}
+    consts, swa, protos = _lib.parse_header(SYNTHETIC, structs)
+    assert consts == {"IVL_ABI_VERSION": 12, "IVL_ERR_SYNC": -5, "IVL_QUERY": -2 ** 31, "IVL_SUM": 6}
+    assert issubclass(swa, ctypes.Structure) and list(structs) == ["ivl_swa_args", "ivl_pick_args"] and structs["ivl_swa_args"] is swa
+    pick = structs["ivl_pick_args"]
+    assert issubclass(pick, ctypes.Structure) and pick.__name__ == "PickArgs"
+    assert pick._fields_ == [("w", c_void_p), ("out", c_void_p), ("n", c_int), ("k", c_int), ("ld", c_int64)]
     assert swa._fields_ == [("q", c_void_p), ("o", c_void_p), ("q_sb", c_int64), ("q_st", c_int64), ("q_sh", c_int64), ("B", c_int),
                             ("T", c_int), ("pos_dev", c_void_p), ("scaling", c_float), ("workspace_bytes", c_size_t)]
     vp = c_void_p
-    assert list(protos) == ["ivl_version", "ivl_last_error", "ivl_bytes", "ivl_f", "ivl_swa"]          # header order
+    assert list(protos) == ["ivl_version", "ivl_last_error", "ivl_bytes", "ivl_f", "ivl_swa", "ivl_pick"]          # header order
     assert protos["ivl_version"] == (c_int, [])
     assert protos["ivl_last_error"] == (c_char_p, [])
     assert protos["ivl_bytes"] == (c_size_t, [c_int, c_int64])
     assert protos["ivl_f"] == (c_int, [vp, vp, vp, vp, vp, c_int, c_float, c_size_t, c_int64, vp, vp])
     assert protos["ivl_swa"] == (c_int, [POINTER(swa), vp])
+    assert protos["ivl_pick"] == (c_int, [POINTER(pick), POINTER(swa), vp])
 
 
 @pytest.mark.parametrize("decl, named", [
@@ -89,8 +103,13 @@ def test_reader_refuses_what_it_does_not_know(decl, named):
 def test_reader_refuses_an_unknown_struct_field_type():
     with pytest.raises(ImportError, match=r"ivl_swa_args\.ratio.*'double'"):
         _lib.parse_header(STRUCT.replace("float scaling;", "float scaling; double ratio;"))
-    with pytest.raises(ImportError, match="ivl_swa_args"):
-        _lib.parse_header("IVL_API int ivl_first(void);")
+    with pytest.raises(ImportError, match=r"ivl_pick_args\.k.*'unsigned'"):
+        _lib.parse_header(STRUCT + STRUCT2.replace("int n, k;", "int n; unsigned k;"))
+    with pytest.raises(ImportError, match=r"ivl_pick_args: cannot read"):
+        _lib.parse_header(STRUCT + STRUCT2.replace("int n, k;", "int n, k[2];"))
+    for text in ("IVL_API int ivl_first(void);", STRUCT2):               # a header without ivl_swa_args
+        with pytest.raises(ImportError, match="ivl_swa_args not found"):
+            _lib.parse_header(text)
 
 
 def test_real_header_prototype_count_and_constants():
@@ -101,9 +120,12 @@ def test_real_header_prototype_count_and_constants():
     assert set(_lib.CONSTANTS) == CONSTANT_NAMES
     for name, value in _lib.CONSTANTS.items():
         assert getattr(_lib, name) == value and type(value) is int
-    assert (_lib.IVL_ABI_VERSION, _lib.IVL_BF16, _lib.IVL_F32, _lib.IVL_FP8_E4M3, _lib.IVL_OK) == (11, 0, 2, 3, 0)
+    assert (_lib.IVL_ABI_VERSION, _lib.IVL_BF16, _lib.IVL_F32, _lib.IVL_FP8_E4M3, _lib.IVL_OK) == (12, 0, 2, 3, 0)
     assert _lib.SwaArgs.__name__ == "SwaArgs" and issubclass(_lib.SwaArgs, ctypes.Structure)
     assert _lib.PROTOTYPES["ivl_swa_fwd"] == (c_int, [POINTER(_lib.SwaArgs), c_void_p])
+    assert _lib.SampleArgs.__name__ == "SampleArgs" and issubclass(_lib.SampleArgs, ctypes.Structure)
+    assert _lib.STRUCTS == {"ivl_swa_args": _lib.SwaArgs, "ivl_sample_args": _lib.SampleArgs}
+    assert _lib.PROTOTYPES["ivl_sample_rows_fwd"] == (c_int, [POINTER(_lib.SampleArgs), c_void_p])
     assert _lib.PROTOTYPES["ivl_last_error"] == (c_char_p, [])
 
 
@@ -120,9 +142,10 @@ def _host_cc():
 def test_struct_layout_and_constants_against_the_c_compiler(tmp_path):
     fields = [name for name, _ in _lib.SwaArgs._fields_]
     assert len(fields) >= 32 and {"pos", "scaling", "workspace", "pos_min"} <= set(fields)
-    lines = ['#include <stdio.h>', '#include "ivl_hip.h"', 'int main(void) {',
-             '  printf("sizeof %zu\\n", sizeof(ivl_swa_args));']
-    lines += [f'  printf("offsetof {f} %zu\\n", offsetof(ivl_swa_args, {f}));' for f in fields]
+    lines = ['#include <stdio.h>', '#include "ivl_hip.h"', 'int main(void) {']
+    for tag, cls in _lib.STRUCTS.items():
+        lines += [f'  printf("sizeof {tag} %zu\\n", sizeof({tag}));']
+        lines += [f'  printf("offsetof {tag} {f} %zu\\n", offsetof({tag}, {f}));' for f, _ in cls._fields_]
     lines += [f'  printf("const {c} %lld\\n", (long long)({c}));' for c in sorted(CONSTANT_NAMES)]
     lines += ['  return 0;', '}']
     src = tmp_path / "layout.c"
@@ -131,10 +154,15 @@ def test_struct_layout_and_constants_against_the_c_compiler(tmp_path):
     subprocess.run([_host_cc(), "-I", os.path.dirname(HEADER), str(src), "-o", exe], check=True, capture_output=True, text=True)
     out = subprocess.run([exe], check=True, capture_output=True, text=True).stdout
     got = {tuple(ln.split()[:-1]): int(ln.split()[-1]) for ln in out.splitlines()}
-    assert got[("sizeof",)] == ctypes.sizeof(_lib.SwaArgs) == 208
-    for f in fields:
-        assert got[("offsetof", f)] == getattr(_lib.SwaArgs, f).offset, f
-    assert [got[("offsetof", f)] for f in ("pos", "scaling", "workspace", "pos_min")] == [128, 144, 152, 200]
+    assert got[("sizeof", "ivl_swa_args")] == ctypes.sizeof(_lib.SwaArgs) == 208
+    assert got[("sizeof", "ivl_sample_args")] == ctypes.sizeof(_lib.SampleArgs) == 312
+    for tag, cls in _lib.STRUCTS.items():
+        assert len(cls._fields_) >= 32
+        for f, _ in cls._fields_:
+            assert got[("offsetof", tag, f)] == getattr(cls, f).offset, (tag, f)
+    assert [got[("offsetof", "ivl_swa_args", f)] for f in ("pos", "scaling", "workspace", "pos_min")] == [128, 144, 152, 200]
+    assert [got[("offsetof", "ivl_sample_args", f)] for f in ("temperature", "hist_ld", "n_states", "score_only")] == \
+        [24, 176, 272, 304]
     for c in CONSTANT_NAMES:
         assert got[("const", c)] == getattr(_lib, c), c
     assert got[("const", "IVL_GDN_RESIDENT_QUERY")] == -2 ** 31 and got[("const", "IVL_GDN_SYNC_BYTES")] == 16384
@@ -151,7 +179,7 @@ def test_load_declares_every_symbol_of_the_product_library():
         fn = getattr(lib, name)
         assert fn.restype is restype and list(fn.argtypes) == argtypes, name
     fresh = _lib.bind(ctypes.CDLL(so))                                                             # the product rule on a new handle
-    assert fresh.ivl_abi_version() == _lib.IVL_ABI_VERSION == 11
+    assert fresh.ivl_abi_version() == _lib.IVL_ABI_VERSION == 12
 
 
 class _Fn:

@@ -1,11 +1,10 @@
 """CPU (-m "not gpu"): the scores' reference (tests/logprobs.py) stands on its own -- against torch.log_softmax in float64 and the
-special rows by hand -- and the host side of the feature: the header's declaration and the library's export of
-ivl_sample_rows_lp_fwd, its error codes on pointers that are never dereferenced, the ABI version, ops.sample_tokens' and
+special rows by hand -- and the host side of the feature: the header's declaration of the score group of
+ivl_sample_args, the entry point's error codes on pointers that are never dereferenced, the ABI version, ops.sample_tokens' and
 Sampler's new arguments."""
 import ctypes
 import math
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -102,53 +101,35 @@ def test_judge_accepts_the_reference_and_refuses_what_is_off():
 def test_entry_point_is_declared_exported_and_validates(lib):
     from infinitevl_amd import _lib
     hdr = open(os.path.join(ROOT, "include", "ivl_hip.h")).read()
-    assert "IVL_API int ivl_sample_rows_lp_fwd(" in hdr
-    assert "ivl_sample_rows_lp_fwd" in _lib.EXPORTED_SYMBOLS
-    ret, args = _lib.PROTOTYPES["ivl_sample_rows_lp_fwd"]
-    ctl = _lib.PROTOTYPES["ivl_sample_rows_ctl_fwd"][1]
-    assert ret is ctypes.c_int and args[:len(ctl) - 1] == ctl[:-1] and len(args) == len(ctl) + 8 and args[len(ctl)] is ctypes.c_int
-    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
-    assert "ivl_sample_rows_lp_fwd" in {ln.split()[-1] for ln in out.splitlines() if ln.strip()}
-    assert lib.ivl_abi_version() == _lib.IVL_ABI_VERSION == 11
+    assert "IVL_API int ivl_sample_rows_fwd(const ivl_sample_args* args, void* stream);" in hdr
+    assert _lib.PROTOTYPES["ivl_sample_rows_fwd"] == (ctypes.c_int, [ctypes.POINTER(_lib.SampleArgs), ctypes.c_void_p])
+    fields = dict(_lib.SampleArgs._fields_)
+    assert sampling.ARG_FIELDS[24:32] == ["logprob", "n_top", "top_ids", "top_logprobs", "cum_logprob", "lp_history", "top_hist_ids",
+                                          "top_hist_lp"]
+    assert fields["n_top"] is ctypes.c_int and fields["cum_logprob"] is ctypes.c_void_p
+    assert lib.ivl_abi_version() == _lib.IVL_ABI_VERSION == 12
 
-    one = ctypes.c_void_p(0x1000)       # never dereferenced: validation fails first
-    INV = _lib.IVL_ERR_INVALID_ARG
-    base = [one, 64, 1, 64, one, one, one, one, one, one, 1, None, None]
-    ctl_names = ("rep_penalty", "seen", "seen_ld", "stop_ids", "n_stop", "budget", "fill", "n_new", "done", "history", "hist_ld")
-    ctl_off = [None, None, 0, None, 0, None, None, None, None, None, 0]
-    lp_names = ("logprob", "n_top", "top_ids", "top_logprobs", "cum_logprob", "lp_history", "top_hist_ids", "top_hist_lp")
-    lp_off = [None, 0, None, None, None, None, None, None]
+    one, INV = sampling.ONE, _lib.IVL_ERR_INVALID_ARG
 
-    def call(**kw):
-        c, l = list(ctl_off), list(lp_off)
-        for n, v in kw.items():
-            if n in ctl_names:
-                c[ctl_names.index(n)] = v
-            else:
-                l[lp_names.index(n)] = v
-        return lib.ivl_sample_rows_lp_fwd(*(base + c + l + [None]))
+    def refused(word, **kw):
+        return sampling.c_refused(lib, INV, word, **kw)
 
-    assert call(n_top=-1) == INV and call(n_top=21, top_ids=one, top_logprobs=one) == INV and b"n_top" in lib.ivl_last_error()
-    assert call(n_top=5) == INV and call(n_top=5, top_ids=one) == INV and call(n_top=5, top_logprobs=one) == INV
-    assert b"top_ids" in lib.ivl_last_error()
-    assert call(lp_history=one, hist_ld=4) == INV and b"n_new" in lib.ivl_last_error()             # no n_new
-    assert call(lp_history=one, n_new=one, hist_ld=0) == INV
+    assert refused(b"n_top", n_top=-1) and refused(b"n_top", n_top=21, top_ids=one, top_logprobs=one)
+    assert refused(b"top_ids", n_top=5) and refused(b"top_ids", n_top=5, top_ids=one)
+    assert refused(b"top_ids", n_top=5, top_logprobs=one)
+    assert refused(b"n_new", lp_history=one, hist_ld=4)                                            # no n_new
+    assert refused(b"hist_ld", lp_history=one, n_new=one, hist_ld=0)
     for ring in ("top_hist_ids", "top_hist_lp"):
-        assert call(**{ring: one}, n_top=5, top_ids=one, top_logprobs=one, hist_ld=4) == INV       # no n_new
-        assert call(**{ring: one}, n_top=5, top_ids=one, top_logprobs=one, n_new=one, hist_ld=0) == INV
-        assert call(**{ring: one}, n_new=one, hist_ld=4) == INV and b"n_top" in lib.ivl_last_error()   # n_top == 0
-    # whatever the controlled entry refuses
-    assert call(logprob=one, rep_penalty=one) == INV and b"seen" in lib.ivl_last_error()
-    assert call(logprob=one, n_stop=17, stop_ids=one, done=one) == INV
-    assert call(logprob=one, budget=one, done=one) == INV and call(logprob=one, history=one, hist_ld=4) == INV
-    assert b"ivl_sample_rows_lp_fwd" in lib.ivl_last_error()
-    for i in (0, 4, 5, 6, 7, 8, 9):     # every required pointer of the control-free call
-        a = list(base + ctl_off + lp_off + [None])
-        a[i] = None
-        assert lib.ivl_sample_rows_lp_fwd(*a) == INV and b"NULL" in lib.ivl_last_error(), i
-    a = list(base + ctl_off + lp_off + [None])
-    a[1], a[3] = 1 << 24, 1 << 23
-    assert lib.ivl_sample_rows_lp_fwd(*a) == _lib.IVL_ERR_UNSUPPORTED
+        assert refused(b"n_new", **{ring: one}, n_top=5, top_ids=one, top_logprobs=one, hist_ld=4)       # no n_new
+        assert refused(b"hist_ld", **{ring: one}, n_top=5, top_ids=one, top_logprobs=one, n_new=one, hist_ld=0)
+        assert refused(b"n_top", **{ring: one}, n_new=one, hist_ld=4)                              # n_top == 0
+    # whatever the controls refuse
+    assert refused(b"rep_penalty needs seen", logprob=one, rep_penalty=one)
+    assert refused(b"n_stop=", logprob=one, n_stop=17, stop_ids=one, done=one)
+    assert refused(b"budget", logprob=one, budget=one, done=one) and refused(b"history", logprob=one, history=one, hist_ld=4)
+    for name in ("logits", "temperature", "top_k", "top_p", "seed", "counter", "token"):          # with a score on
+        assert refused(b"NULL", logprob=one, **{name: None}), name
+    assert sampling.c_refused(lib, _lib.IVL_ERR_UNSUPPORTED, b"2^23", V=1 << 23, ld=1 << 24, logprob=one)
 
 
 # ---------------------------------------------------------------------------------------------

@@ -176,17 +176,16 @@ def test_sample_tokens_refuses_cpu_tensors_and_bad_arguments():
 
 def test_entry_point_validates_and_is_exported(lib):
     from infinitevl_amd import _lib
-    one = ctypes.c_void_p(0x1000)       # never dereferenced: validation fails first
-    ok = [one, 16, 1, 16, one, one, one, one, one, one, 1, None, None, None]
-    for i in (0, 4, 5, 6, 7, 8, 9):     # every required pointer
-        args = list(ok)
-        args[i] = None
-        assert lib.ivl_sample_rows_fwd(*args) == _lib.IVL_ERR_INVALID_ARG and b"NULL" in lib.ivl_last_error(), i
-    assert lib.ivl_sample_rows_fwd(one, 16, 0, 16, one, one, one, one, one, one, 1, None, None, None) == _lib.IVL_ERR_INVALID_ARG
-    assert lib.ivl_sample_rows_fwd(one, 16, 1, 0, one, one, one, one, one, one, 1, None, None, None) == _lib.IVL_ERR_INVALID_ARG
-    assert lib.ivl_sample_rows_fwd(one, 15, 1, 16, one, one, one, one, one, one, 1, None, None, None) == _lib.IVL_ERR_INVALID_ARG
-    assert lib.ivl_sample_rows_fwd(one, 1 << 24, 1, 1 << 23, one, one, one, one, one, one, 1, None, None,
-                                   None) == _lib.IVL_ERR_UNSUPPORTED
+    INV, UNS = _lib.IVL_ERR_INVALID_ARG, _lib.IVL_ERR_UNSUPPORTED
+    assert _lib.PROTOTYPES["ivl_sample_rows_fwd"] == (ctypes.c_int, [ctypes.POINTER(_lib.SampleArgs), ctypes.c_void_p])
+    assert [n for n, _ in _lib.SampleArgs._fields_] == sampling.ARG_FIELDS
+    assert lib.ivl_sample_rows_fwd(None, None) == INV and b"NULL" in lib.ivl_last_error()
+    for name in ("logits", "temperature", "top_k", "top_p", "seed", "counter", "token"):     # every required pointer
+        assert sampling.c_refused(lib, INV, b"NULL", V=16, **{name: None}), name
+    assert sampling.c_refused(lib, INV, b"S=0", V=16, S=0)
+    assert sampling.c_refused(lib, INV, b"V=0", V=0, ld=16)
+    assert sampling.c_refused(lib, INV, b"ld=15", V=16, ld=15)
+    assert sampling.c_refused(lib, UNS, b"2^23", V=1 << 23, ld=1 << 24)
     assert "ivl_sample_rows_fwd" in _lib.EXPORTED_SYMBOLS
     out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
     assert "ivl_sample_rows_fwd" in {ln.split()[-1] for ln in out.splitlines() if ln.strip()}

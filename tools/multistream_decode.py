@@ -50,8 +50,8 @@ index_select + copy_ loop on the same map, single calls and calls queued back to
 
     python tools/multistream_decode.py --beam [--out profiles/beam_decode.json]
 
---grammar: the cost of constrained decoding (Sampler(grammar_states=), ivl_sample_rows_fsm_fwd) in the captured 4-slot step.  A:
-the sampled step (0.7 / 50 / 0.9) with logprobs=0, the launch the constrained form extends; B: the same with a 5-label
+--grammar: the cost of constrained decoding (Sampler(grammar_states=), ivl_sample_rows_fwd's constraint) in the captured 4-slot
+step.  A: the sampled step (0.7 / 50 / 0.9) with logprobs=0, the launch the constrained form extends; B: the same with a 5-label
 grammar.TokenFsm.from_choices grammar on every slot; C: with a 64-state TokenFsm.from_byte_dfa grammar (hh:mm:ss, repeated, over
 a synthetic byte vocabulary of the model's size) on every slot.  Timed A B A C per round.  Every leg restores one int32 per
 slot before each replay (B and C: the slots' start states, so a label grammar never runs out; A: a word nobody reads), so that
