@@ -405,6 +405,39 @@ IVL_API int ivl_norm_linear_small_m_fwd(const void* x, const void* residual, con
 IVL_API int ivl_linear_m256_fwd(const void* x, const void* w, const void* bias, void* y, int M, int N, int K, int glu, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Scoring GIVEN tokens under lm_head: the log-probability of target[r] in the distribution of row r, the [M,N] logits never
+ * written anywhere.  Replaces logits -> float log_softmax -> gather (HF `labels=`, CrossEntropyLoss(reduction="none") of
+ * scripts/stat_utils/cal_ppl.py:111-124, `echo` + `logprobs` of the OpenAI protocol, likelihood ranking of candidate answers).
+ * x [M,K], w [N,K], bias [N] or NULL: bf16, the shapes and alignments of the plain form of ivl_linear_m256_fwd (1 <= M <= 256,
+ * K % 64 == 0 and K <= 16384, N % 4 == 0, 32-bit weight offsets, x / w 16-byte aligned).  target int64 [M]; logprob fp32 [M];
+ * top1 int64 [M] and lse fp32 [M] may be NULL.  Per row r:
+ *   S1 the logits.  xl[c] = bf16(x[r] . W[c] + bias[c]): the bits ivl_linear_m256_fwd (glu == 0) writes for that element -- the
+ *      same K order, one rounding.  A NaN counts as -inf (step 1 of the sampling contract below).  m = max_c xl[c].
+ *   S2 the partition sum.  Z = sum_c w_c, w_c = exp(xl[c] - m): exactly 1 where xl[c] == m (also at m = +-inf), 0 where
+ *      xl[c] = -inf < m.  The real-valued definition behind L1 of the sampling launch's scores, without its 2^-40 weight floor.
+ *      A row of nothing but -inf / NaN has Z = N.
+ *   S3 lse[r] = m + logf(Z); lse[r] = m when m is infinite.
+ *   S4 logprob[r] = (xl[target[r]] - m) - logf(Z): -logf(Z) where the target's logit equals m, -inf where it is -inf < m,
+ *      -logf((float)N) in the all -inf row.  A target outside [0, N) -- IGNORE_INDEX = -100 -- is not scored: logprob[r] = 0.0f.
+ *   S5 top1[r] = the lowest index with xl == m (the greedy token of step 2); written for ignored rows too; 0 in the all -inf row.
+ * Two launches.  (1) linear_m256's kernel with a SCORE epilogue, 64 columns x all rows per workgroup: per (column block j, row)
+ * one partial {m_j, z_j = sum exp(xl - m_j) in fp32, idx_j = the lowest index attaining m_j} goes to the workspace as one
+ * 16-byte store, and the one lane that owns column target[r] stores that logit; no atomics.  (2) one workgroup per row:
+ * M_r = max_j m_j, top1 = the smallest idx_j among m_j == M_r, Z = sum_j z_j exp(m_j - M_r) in float64 in a fixed order (blocks
+ * with m_j == M_r unscaled, blocks at -inf nothing).  Every output is a pure function of (x[r], W, bias, target[r]): the same
+ * bits on every run, eager or in a replayed graph, for any M and whichever row of the call the row sits in.
+ * Error against the real number, from the bf16 logits on: |err| <= 1e-5 + 2^-22 |value| for logprob and lse (<= 2 ulp per expf,
+ * 64-term fp32 partial sums, a float64 combine, 1 ulp of logf, one rounding of the difference).
+ * workspace: ivl_linear_logprob_workspace_bytes(M, N) = ceil(N/64) * M * 16 + M * 4 bytes rounded up to 256 (0 for M < 1 or
+ * N < 1), 16-byte aligned; its contents are scratch.  No allocation, no synchronisation, capturable.
+ * Errors as ivl_linear_m256_fwd; IVL_ERR_INVALID_ARG also for NULL target, logprob or workspace; IVL_ERR_WORKSPACE: too small.
+ * ------------------------------------------------------------------------------------------- */
+IVL_API size_t ivl_linear_logprob_workspace_bytes(int M, int N);
+IVL_API int ivl_linear_logprob_m256_fwd(const void* x, const void* w, const void* bias, const int64_t* target, float* logprob,
+                                int64_t* top1, float* lse, int M, int N, int K, void* workspace, size_t workspace_bytes,
+                                void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Next-token sampling over lm_head logits: temperature, top-k, top-p, one random stream per row, one launch.
  * Replaces the logits warpers + multinomial of HF generate, which the reference drives with do_sample / temperature / top_p /
  * top_k (src/llamafactory/api/chat.py:160-162, api/protocol.py:99-101, webui/runner.py:231-232,

@@ -23,6 +23,14 @@
 //
 // GLU epilogue: act = bf16( bf16(silu(g)) * u ) with g, u the accumulators rounded to bf16 -- the arithmetic of silu_mul_kernel
 // (and of linear_small_m_kernel's GLU form), so the fused output is bit-equal to the plain output followed by ivl_silu_mul_fwd.
+//
+// SCORE epilogue (ivl_linear_logprob_m256_fwd: the log-probability of a GIVEN token under lm_head, the logits never written): the
+// plain form's configuration; the accumulators are rounded to the bf16 logits the plain form would store, and the 64 columns of a
+// row -- 16 in each of the lanes l, l + 16, l + 32, l + 48 -- are reduced in registers and by two xor-shuffles to one partial
+// {max, sum exp(x - max), lowest index of the max} per (column block, row), one 16-byte store; the lane that owns column
+// target[row] stores that logit.  logprob_combine_kernel (one workgroup per row) merges the ceil(N / 64) partials in float64 in a
+// fixed order.  No atomics, no LDS beyond the ring; the plain and GLU
+// instantiations are untouched by it.
 #include "ivl_common.h"
 
 namespace ivl {
@@ -72,9 +80,14 @@ __device__ __forceinline__ const bf16_t* l256_uniform(const bf16_t* p) {
   return (const bf16_t*)(((unsigned long long)hi << 32) | lo);
 }
 
-template <bool GLU, int ROWS, int NST, bool WNT>
+// TARGET: empty (y = the bf16 output [M,N]), or one `const long long*` = the SCORE form: `target`, and y is the workspace
+// (ceil(N/64) x M partials of 16 bytes, then M target logits).  The plain and GLU instantiations have the signature they always had.
+template <bool GLU, int ROWS, int NST, bool WNT, typename... TARGET>
 __global__ __launch_bounds__(ROWS * 2) void linear_m256_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ w,
-                                                               const bf16_t* __restrict__ bias, bf16_t* __restrict__ y, int M, int N, int K) {
+                                                               const bf16_t* __restrict__ bias, bf16_t* __restrict__ y, int M, int N, int K,
+                                                               TARGET... target_arg) {
+  constexpr bool SCORE = sizeof...(TARGET) != 0;
+  static_assert(!(SCORE && GLU) && sizeof...(TARGET) <= 1, "the SCORE epilogue is a plain-form epilogue");
   using C = L256Cfg<GLU, ROWS, NST>;
   static_assert(NST >= 2 && NST <= 3, "ring of 2 or 3 stages");
   constexpr int AHEAD = NST - 1;
@@ -191,6 +204,60 @@ __global__ __launch_bounds__(ROWS * 2) void linear_m256_kernel(const bf16_t* __r
         if (row < M && col < N) store_out8(y + (size_t)row * N + col, u32x2{pack2bf(o[0], o[1]), pack2bf(o[2], o[3])});
       }
     }
+  } else if constexpr (SCORE) {
+    const long long* __restrict__ target = (target_arg, ...);
+    // xl = the bf16 logit the plain form stores (NaN = -inf; columns >= N are absent).  Per row: m = the maximum over the
+    // workgroup's 64 columns, z = sum of exp(xl - m) (exactly 1 where xl == m, also at m = +-inf), idx = the lowest column with xl == m
+    constexpr float NEG_INF = -__builtin_huge_valf();
+    u32x4* part = (u32x4*)y;
+    float* tlogit = (float*)(part + (size_t)((N + C::NCOL - 1) / C::NCOL) * M);
+    float bb[C::NT][4];
+#pragma unroll
+    for (int j = 0; j < C::NT; ++j) {
+      const int col = n0 + 16 * j + cq;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) bb[j][r] = bias != nullptr && col < N ? bf2f(bias[col + r]) : 0.f;
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int row = r0 + 32 * wave + 16 * i + (lane & 15);
+      const long long t = row < M ? target[row] : -1ll;
+      const int tc = t >= 0 && t < (long long)N ? (int)t : -1;       // the scored column (any workgroup's), -1: none
+      float xl[C::NT][4], m = NEG_INF;
+#pragma unroll
+      for (int j = 0; j < C::NT; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float v = bf_round(acc[j][i][r] + bb[j][r]);
+          xl[j][r] = (n0 + 16 * j + cq < N && v == v) ? v : NEG_INF;
+          m = fmaxf(m, xl[j][r]);
+        }
+      m = fmaxf(m, __shfl_xor(m, 16, 64));
+      m = fmaxf(m, __shfl_xor(m, 32, 64));
+      float z = 0.f, tv = 0.f;
+      int idx = 0x7fffffff;
+      bool hit = false;
+#pragma unroll
+      for (int j = 0; j < C::NT; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int col = n0 + 16 * j + cq + r;
+          const bool top = xl[j][r] == m;
+          if (n0 + 16 * j + cq < N) {
+            z += top ? 1.f : expf(xl[j][r] - m);
+            if (top) idx = min(idx, col);
+            if (col == tc) { tv = xl[j][r]; hit = true; }
+          }
+        }
+      z += __shfl_xor(z, 16, 64);
+      z += __shfl_xor(z, 32, 64);
+      idx = min(idx, __shfl_xor(idx, 16, 64));
+      idx = min(idx, __shfl_xor(idx, 32, 64));
+      if (row < M) {
+        if (lane < 16) part[(size_t)colblk * M + row] = u32x4{__float_as_uint(m), __float_as_uint(z), (unsigned int)idx, 0u};
+        if (hit) tlogit[row] = tv;
+      }
+    }
   } else {
 #pragma unroll
     for (int j = 0; j < C::NT; ++j) {
@@ -208,6 +275,99 @@ __global__ __launch_bounds__(ROWS * 2) void linear_m256_kernel(const bf16_t* __r
       }
     }
   }
+}
+
+// Launch 2 of ivl_linear_logprob_m256_fwd: one workgroup per row merges the row's nblk partials {m_j, z_j, idx_j}.
+//   M_r = max m_j;  top1 = the smallest idx_j among m_j == M_r;  Z = sum_j z_j exp(m_j - M_r) in float64 (unscaled where m_j == M_r,
+//   nothing from a block at -inf below M_r).  Thread t adds blocks t, t + 256, ... in that order, then a fixed xor tree over the wave and
+//   the four wave sums in wave order: the same bits for any M and whichever row of a call the logits sit in.
+constexpr int LPC_THREADS = 256;
+__global__ __launch_bounds__(LPC_THREADS) void logprob_combine_kernel(const u32x4* __restrict__ part, const float* __restrict__ tlogit,
+                                                                      const long long* __restrict__ target, float* __restrict__ logprob,
+                                                                      long long* __restrict__ top1, float* __restrict__ lse, int M,
+                                                                      int N, int nblk) {
+  __shared__ float s_m[LPC_THREADS / 64];
+  __shared__ int s_i[LPC_THREADS / 64];
+  __shared__ double s_z[LPC_THREADS / 64];
+  const int row = (int)blockIdx.x, tid = threadIdx.x;
+  const float NEG_INF = -__builtin_huge_valf();
+  float m = NEG_INF;
+  int idx = 0x7fffffff;
+  for (int j = tid; j < nblk; j += LPC_THREADS) {
+    const u32x4 p = part[(size_t)j * M + row];
+    const float mj = __uint_as_float(p.x);
+    const int ij = (int)p.z;
+    if (mj > m || (mj == m && ij < idx)) { m = mj; idx = ij; }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float mo = __shfl_xor(m, o, 64);
+    const int io = __shfl_xor(idx, o, 64);
+    if (mo > m || (mo == m && io < idx)) { m = mo; idx = io; }
+  }
+  if ((tid & 63) == 0) { s_m[tid >> 6] = m; s_i[tid >> 6] = idx; }
+  __syncthreads();
+  m = s_m[0];
+  idx = s_i[0];
+#pragma unroll
+  for (int v = 1; v < LPC_THREADS / 64; ++v)
+    if (s_m[v] > m || (s_m[v] == m && s_i[v] < idx)) { m = s_m[v]; idx = s_i[v]; }
+  double z = 0.0;
+  for (int j = tid; j < nblk; j += LPC_THREADS) {
+    const u32x4 p = part[(size_t)j * M + row];
+    const float mj = __uint_as_float(p.x), zj = __uint_as_float(p.y);
+    if (mj == m) z += (double)zj;
+    else if (mj > NEG_INF) z += (double)zj * exp((double)mj - (double)m);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) z += __shfl_xor(z, o, 64);
+  if ((tid & 63) == 0) s_z[tid >> 6] = z;
+  __syncthreads();
+  if (tid == 0) {
+    z = s_z[0];
+#pragma unroll
+    for (int v = 1; v < LPC_THREADS / 64; ++v) z += s_z[v];
+    const float lz = logf((float)z);
+    const long long t = target[row];
+    float lp = 0.f;                                            // a target outside [0, N) is not scored
+    if (t >= 0 && t < (long long)N) {
+      const float xt = tlogit[row];
+      lp = (xt == m ? 0.f : xt - m) - lz;
+    }
+    logprob[row] = lp;
+    if (top1 != nullptr) top1[row] = (long long)idx;
+    if (lse != nullptr) lse[row] = (m == NEG_INF || m == -NEG_INF) ? m : m + lz;
+  }
+}
+
+static size_t logprob_workspace_bytes(int M, int N) {
+  const size_t nblk = ((size_t)N + 63) / 64;
+  return (nblk * (size_t)M * 16 + (size_t)M * 4 + 255) & ~(size_t)255;
+}
+
+static int launch_l256_score(const void* x, const void* w, const void* bias, const int64_t* target, float* logprob, int64_t* top1,
+                             float* lse, int M, int N, int K, void* ws, hipStream_t st) {
+  constexpr int ROWS = L256_WG_ROWS, NST = L256_STAGES;
+  using C = L256Cfg<false, ROWS, NST>;
+  static_assert(C::NCOL == 64, "the workspace formula and the combine count 64-column blocks");
+  const void* fn = (const void*)linear_m256_kernel<false, ROWS, NST, false, const long long*>;
+  static bool attr_set[64];                        // per device, as in launch_l256
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  if (!__atomic_load_n(&attr_set[dev & 63], __ATOMIC_ACQUIRE)) {
+    (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
+    __atomic_store_n(&attr_set[dev & 63], true, __ATOMIC_RELEASE);
+  }
+  const int ncol = (N + C::NCOL - 1) / C::NCOL;
+  const dim3 grid(ROWS < L256_ROWS ? (ncol + 7) / 8 * 16 : ncol);
+  hipLaunchKernelGGL((linear_m256_kernel<false, ROWS, NST, false, const long long*>), grid, dim3(ROWS * 2), C::LDS, st,
+                     (const bf16_t*)x, (const bf16_t*)w, (const bf16_t*)bias, (bf16_t*)ws, M, N, K, (const long long*)target);
+  const int rc = check_launch("ivl_linear_logprob_m256_fwd");
+  if (rc != IVL_OK) return rc;
+  const u32x4* part = (const u32x4*)ws;
+  hipLaunchKernelGGL(logprob_combine_kernel, dim3(M), dim3(LPC_THREADS), 0, st, part, (const float*)(part + (size_t)ncol * M),
+                     (const long long*)target, logprob, (long long*)top1, lse, M, N, ncol);
+  return check_launch("ivl_linear_logprob_m256_fwd (combine)");
 }
 
 template <bool GLU>
@@ -248,4 +408,32 @@ extern "C" int ivl_linear_m256_fwd(const void* x, const void* w, const void* bia
               "ivl_linear_m256_fwd: x / w must be 16-byte aligned, y 8-byte aligned");
   hipStream_t st = (hipStream_t)stream;
   return glu ? launch_l256<true>(x, w, bias, y, M, N, K, st) : launch_l256<false>(x, w, bias, y, M, N, K, st);
+}
+
+extern "C" size_t ivl_linear_logprob_workspace_bytes(int M, int N) {
+  if (M < 1 || N < 1) return 0;
+  return logprob_workspace_bytes(M, N);
+}
+
+extern "C" int ivl_linear_logprob_m256_fwd(const void* x, const void* w, const void* bias, const int64_t* target, float* logprob,
+                                           int64_t* top1, float* lse, int M, int N, int K, void* workspace, size_t workspace_bytes,
+                                           void* stream) {
+  IVL_REQUIRE(x && w, IVL_ERR_INVALID_ARG, "ivl_linear_logprob_m256_fwd: NULL pointer (x / w)");
+  IVL_REQUIRE(target && logprob, IVL_ERR_INVALID_ARG, "ivl_linear_logprob_m256_fwd: NULL pointer (target / logprob)");
+  IVL_REQUIRE(workspace, IVL_ERR_INVALID_ARG, "ivl_linear_logprob_m256_fwd: NULL workspace");
+  IVL_REQUIRE(M > 0 && N > 0 && K > 0, IVL_ERR_INVALID_ARG, "ivl_linear_logprob_m256_fwd: M=%d N=%d K=%d", M, N, K);
+  IVL_REQUIRE(M <= L256_ROWS, IVL_ERR_UNSUPPORTED, "ivl_linear_logprob_m256_fwd: M=%d (built for at most %d rows)", M, L256_ROWS);
+  IVL_REQUIRE(K % L256_BK == 0 && K <= L256_KMAX, IVL_ERR_UNSUPPORTED,
+              "ivl_linear_logprob_m256_fwd: K=%d (a multiple of %d, at most %d)", K, L256_BK, L256_KMAX);
+  IVL_REQUIRE(N % 4 == 0, IVL_ERR_UNSUPPORTED, "ivl_linear_logprob_m256_fwd: N=%d (a multiple of 4, as the plain form)", N);
+  IVL_REQUIRE((long long)N * K * 2 < (1ll << 32), IVL_ERR_UNSUPPORTED,
+              "ivl_linear_logprob_m256_fwd: weight of %d x %d rows does not fit 32-bit offsets", N, K);
+  IVL_REQUIRE((((size_t)x | (size_t)w | (size_t)workspace) & 15) == 0 && ((size_t)bias & 1) == 0 && ((size_t)target & 7) == 0 &&
+                  ((size_t)top1 & 7) == 0 && (((size_t)logprob | (size_t)lse) & 3) == 0,
+              IVL_ERR_INVALID_ARG, "ivl_linear_logprob_m256_fwd: x / w / workspace must be 16-byte aligned (x=%p w=%p workspace=%p)", x,
+              w, workspace);
+  const size_t need = logprob_workspace_bytes(M, N);
+  IVL_REQUIRE(workspace_bytes >= need, IVL_ERR_WORKSPACE, "ivl_linear_logprob_m256_fwd: workspace of %zu bytes, %zu needed", workspace_bytes,
+              need);
+  return launch_l256_score(x, w, bias, target, logprob, top1, lse, M, N, K, workspace, (hipStream_t)stream);
 }

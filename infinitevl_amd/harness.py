@@ -1020,6 +1020,28 @@ class GraphedMultiStreamDecode(_Graphed):
         return self.token[slot]
 
     @torch.no_grad()
+    def score(self, slot: int, inputs_embeds: torch.Tensor, labels: torch.Tensor, position_ids: Optional[torch.Tensor] = None,
+              next_label: Optional[int] = None) -> "ScoreResult":
+        """Teacher-forced scoring on the live slot `slot`: score_sequence on its B = 1 view, in calls of PREFILL_CHUNK --
+        the log-probability of labels (HF convention: the input's length, shifted inside; -100 = not scored; the last position
+        against `next_label`) as a continuation of what the slot holds.  The slot's state and its three M-RoPE positions advance
+        as in extend (position_ids [3,1,T]; default: counting on from position_ids[:, slot]).  No token is drawn: token[slot]
+        is zeroed as after load, so an extend (or another score) follows before the slot is stepped.
+        Ranking candidate answers by likelihood without polluting the stream: fork(src, dsts) -> score(dst, candidate) for
+        each -> release(dst); `src` is only read by the fork."""
+        slot = self._slots("score", [slot])[0]
+        if slot not in self._live:
+            raise ValueError(f"score: slot {slot} holds no stream (admit or load it first)")
+        T = self._check_prompt("score", inputs_embeds, position_ids, None)
+        if position_ids is None:
+            position_ids = self.position_ids[:, slot:slot + 1] + torch.arange(T, device=self.position_ids.device, dtype=torch.int64)
+        res = score_sequence(self.model, self.cache.slot_view(slot), inputs_embeds=inputs_embeds, labels=labels,
+                             position_ids=position_ids, chunk=self.PREFILL_CHUNK, next_label=next_label)
+        self.token[slot].zero_()
+        self.position_ids[:, slot].copy_(position_ids.max() + 1)
+        return res
+
+    @torch.no_grad()
     def admit_n(self, slots, inputs_embeds: torch.Tensor, position_ids: Optional[torch.Tensor] = None,
                 sampling=None, prompt_ids: Optional[torch.Tensor] = None, grammar=None) -> torch.Tensor:
         """Several answers to one prompt (num_return_sequences of the reference's api/chat.py:164): the prompt is prefilled
@@ -1303,7 +1325,86 @@ class GraphedBeamDecode(GraphedMultiStreamDecode):
     def _per_slot(self, *a, **k):
         raise ValueError("GraphedBeamDecode: a slot of a beam group is not a stream of its own (admit / release a group)")
 
-    fork = extend = admit_n = load = _per_slot
+    fork = extend = score = admit_n = load = _per_slot
+
+
+IGNORE_INDEX = -100
+
+
+def shift_labels(labels: torch.Tensor, next_label: Optional[int] = None) -> torch.Tensor:
+    """The target of every position of a teacher-forced sequence, from HF-style labels (the same length as the input, NOT
+    shifted: scripts/stat_utils/cal_ppl.py:111-124): position t is scored against labels[..., t + 1], the last position against
+    `next_label` -- or not at all (IGNORE_INDEX) when that is None.  Pure tensor code on the labels' device (CPU included);
+    chunks of a long sequence take slices of the result, so the shift also holds across chunk boundaries."""
+    if labels.dtype != torch.int64 or labels.dim() not in (1, 2) or labels.shape[-1] < 1:
+        raise ValueError(f"shift_labels: labels must be int64 [T] or [B,T] with T >= 1; got {tuple(labels.shape)} {labels.dtype}")
+    if next_label is not None and (isinstance(next_label, bool) or not isinstance(next_label, int)):
+        raise ValueError(f"shift_labels: next_label must be None or an int; got {next_label!r}")
+    out = torch.empty_like(labels)
+    out[..., :-1] = labels[..., 1:]
+    out[..., -1] = IGNORE_INDEX if next_label is None else next_label
+    return out
+
+
+class ScoreResult(NamedTuple):
+    """What score_sequence returns; every field is a device tensor (nothing was read on the host)."""
+    logprobs: torch.Tensor       # fp32, the labels' shape: log p(target) at every position, 0 where not scored
+    top1: torch.Tensor           # int64: the greedy token of every position (not scored ones included)
+    targets: torch.Tensor        # int64: the shifted labels the positions were scored against
+    n_scored: torch.Tensor       # int64 scalar: positions with a target inside the vocabulary
+    nll: torch.Tensor            # float64 scalar: -sum(logprobs)
+
+    @property
+    def perplexity(self) -> torch.Tensor:
+        return torch.exp(self.nll / self.n_scored)
+
+    @property
+    def accuracy(self) -> torch.Tensor:
+        """eval_accuracy of the reference's train/sft: greedy token == label over the scored positions (top1 is a token of
+        the vocabulary, so it never equals a target that was not scored)."""
+        return (self.top1 == self.targets).sum().double() / self.n_scored
+
+
+@torch.no_grad()
+def score_sequence(model: InfiniteVLTextStack, cache: StaticCachePrealloc, *, input_ids: Optional[torch.Tensor] = None,
+                   inputs_embeds: Optional[torch.Tensor] = None, labels: torch.Tensor,
+                   position_ids: Optional[torch.Tensor] = None, chunk: int = 4096,
+                   next_label: Optional[int] = None) -> ScoreResult:
+    """Teacher-forced scoring of a sequence that continues whatever `cache` already holds: the log-probability of every label
+    under the model, position by position, in constant memory -- perplexity at any depth of a stream, HF's `labels=` loss,
+    eval_loss / eval_accuracy, the likelihood of a candidate answer, `echo` + `logprobs`.
+    The sequence runs as prefill calls of `chunk` tokens with logits_to_keep=0; each call's hidden states go through
+    ops.linear_logprob against the tied embed_tokens.weight, so no [T, vocab] logits exist at any time.
+    `labels` (int64, [T] or [B,T]) follow the HF convention: the same length as the input, shifted here (shift_labels) --
+    position t is scored against labels[t + 1], across chunk boundaries too; the last position against `next_label`, or not at
+    all when that is None; -100 entries (and anything else outside the vocabulary) are not scored.  The cache advances by T."""
+    if (input_ids is None) == (inputs_embeds is None):
+        raise ValueError("score_sequence: exactly one of input_ids and inputs_embeds")
+    if isinstance(chunk, bool) or not isinstance(chunk, int) or chunk < 1:
+        raise ValueError(f"score_sequence: chunk must be an int >= 1; got {chunk!r}")
+    src = input_ids if inputs_embeds is None else inputs_embeds
+    B, T = int(src.shape[0]), int(src.shape[1])
+    if tuple(labels.shape) not in ((B, T),) + (((T,),) if B == 1 else ()):
+        raise ValueError(f"score_sequence: labels must have the input's shape [{B},{T}]"
+                         f"{' or [' + str(T) + ']' if B == 1 else ''}; got {tuple(labels.shape)}")
+    if position_ids is not None and tuple(position_ids.shape) != (3, B, T):
+        raise ValueError(f"score_sequence: position_ids must be [3,{B},{T}]; got {tuple(position_ids.shape)}")
+    targets = shift_labels(labels.to(src.device), next_label)
+    tg = targets.view(B, T)
+    logprobs = torch.empty(B, T, dtype=torch.float32, device=src.device)
+    top1 = torch.empty(B, T, dtype=torch.int64, device=src.device)
+    weight = model.embed_tokens.weight                                           # tied lm_head (std:2091-2092)
+    for a in range(0, T, chunk):
+        b = min(T, a + chunk)
+        h, _ = model(input_ids=None if input_ids is None else input_ids[:, a:b],
+                     inputs_embeds=None if inputs_embeds is None else inputs_embeds[:, a:b],
+                     position_ids=None if position_ids is None else position_ids[:, :, a:b],
+                     past_key_values=cache, logits_to_keep=0)
+        lp, t1 = ops.linear_logprob(h.contiguous(), weight, tg[:, a:b].contiguous(), top1=True)
+        logprobs[:, a:b] = lp
+        top1[:, a:b] = t1
+    n_scored = ((tg >= 0) & (tg < weight.shape[0])).sum()
+    return ScoreResult(logprobs.view(labels.shape), top1.view(labels.shape), targets, n_scored, -logprobs.double().sum())
 
 
 @torch.no_grad()

@@ -1007,6 +1007,46 @@ def linear_swiglu(x: torch.Tensor, w_gate_up: torch.Tensor) -> torch.Tensor:
     return silu_mul(linear(x, w_gate_up))
 
 
+def linear_logprob(x: torch.Tensor, weight: torch.Tensor, target: torch.Tensor, bias: Optional[torch.Tensor] = None, *,
+                   top1: bool = False, lse: bool = False):
+    """log-probability of target[...] under softmax(bf16(x @ weight.T + bias)), row by row, without the logits ever reaching
+    memory (ivl_linear_logprob_m256_fwd: the 256-row GEMM with a log-sum-exp epilogue + a per-row combine).  x [..., K] bf16,
+    weight [N, K] bf16, bias [N] bf16 or None, target int64 with x's leading shape; a target outside [0, N) (-100) is not scored
+    and gives 0.0.  Returns logprob fp32 with x's leading shape -- and, when asked, top1 int64 (the greedy token of every row,
+    ignored rows included) and / or lse fp32, in that order.  Any number of rows, in pieces of 256; nothing is read on the host.
+    Inputs that are not CUDA bf16 contiguous, or a shape the kernel refuses, raise ValueError: there is no other path."""
+    lead = tuple(x.shape[:-1])
+    K = x.shape[-1] if x.dim() else 0
+    ok = (x.is_cuda and weight.is_cuda and target.is_cuda and x.dtype == torch.bfloat16 and weight.dtype == torch.bfloat16
+          and x.is_contiguous() and weight.is_contiguous() and weight.dim() == 2 and weight.shape[1] == K
+          and target.dtype == torch.int64 and target.is_contiguous() and tuple(target.shape) == lead
+          and (bias is None or (bias.is_cuda and bias.dtype == torch.bfloat16 and bias.is_contiguous()
+                                and tuple(bias.shape) == (weight.shape[0],))))
+    if not ok:
+        raise ValueError("linear_logprob: x [..., K] and weight [N, K] (bias [N]) must be contiguous bf16 CUDA tensors and target "
+                         f"a contiguous int64 CUDA tensor of x's leading shape; got x {tuple(x.shape)} {x.dtype} {x.device}, weight "
+                         f"{tuple(weight.shape)} {weight.dtype}, target {tuple(target.shape)} {target.dtype}")
+    N = weight.shape[0]
+    rows = x.numel() // K if K else 0
+    lib = _lib.load()
+    out_lp = torch.empty(lead, dtype=torch.float32, device=x.device)
+    out_top = torch.empty(lead, dtype=torch.int64, device=x.device) if top1 else None
+    out_lse = torch.empty(lead, dtype=torch.float32, device=x.device) if lse else None
+    if rows:
+        nbytes = lib.ivl_linear_logprob_workspace_bytes(min(rows, 256), N)
+        ws = get_workspace(nbytes, x.device, "logprob")
+        x2, tg, lp = x.view(rows, K), target.view(rows), out_lp.view(rows)
+        tp = out_top.view(rows) if top1 else None
+        ls = out_lse.view(rows) if lse else None
+        for a in range(0, rows, 256):
+            m = min(256, rows - a)
+            _lib.check(lib.ivl_linear_logprob_m256_fwd(
+                _p(x2[a:a + m]), _p(weight), _p(bias), _p(tg[a:a + m]), _p(lp[a:a + m]), _p(tp[a:a + m]) if top1 else None,
+                _p(ls[a:a + m]) if lse else None, m, N, K, _p(ws), ws.numel(), _stream(x)))
+    outs = (out_lp,) + ((out_top,) if top1 else ()) + ((out_lse,) if lse else ())
+    return outs if len(outs) > 1 else out_lp
+
+
 def apply_mrope_strided_inplace(q: torch.Tensor, k: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, mrope_section):
     """M-RoPE in place on q [B,T,Hq,d] / k [B,T,Hkv,d] VIEWS into a fused qkv projection (row = token)."""
     _need_gpu(q, k, cos, sin)
