@@ -369,7 +369,8 @@ IVL_API int ivl_gdn_decode_split_fwd(const void* proj, int64_t ld, int col_q, in
  * with FusedRMSNormGated (fla:modules/fused_norm_gate.py:778-796; 256-wide heads, eps) in the prologue of the weight stream.
  * gate = first gate element of row 0 of the fused projection (row stride gate_ld elements); norm_weight bf16 [256].  Also shifts
  * the conv states [M, H*128, 4] of q and k by the step's raw projection values (proj + col_q / col_k, row stride proj_ld): the
- * second half of ivl_gdn_decode_split_fwd's state update.  M <= 4, H <= 16. */
+ * second half of ivl_gdn_decode_split_fwd's state update.  M <= 4, 2 <= H <= 16 (IVL_ERR_UNSUPPORTED otherwise: at H = 1 half of
+ * every wave would skip the weight loop whose first trip holds the norm). */
 IVL_API int ivl_gdn_out_linear_small_m_fwd(const void* o_raw, const void* gate, int64_t gate_ld, const void* norm_weight, float eps,
                                    int H, const void* proj, int64_t proj_ld, int col_q, int col_k, void* conv_state_q,
                                    void* conv_state_k, const void* w, const void* bias, void* y, int M, int N, int K, void* stream);

@@ -352,8 +352,11 @@ extern "C" int ivl_gdn_out_linear_small_m_fwd(const void* o_raw, const void* gat
   IVL_REQUIRE(o_raw && gate && norm_weight && proj && conv_state_q && conv_state_k && w && y, IVL_ERR_INVALID_ARG,
               "ivl_gdn_out_linear_small_m_fwd: NULL pointer");
   IVL_REQUIRE(M >= 1 && M <= 4, IVL_ERR_UNSUPPORTED, "ivl_gdn_out_linear_small_m_fwd: M=%d (built for 1..4 rows)", M);
-  IVL_REQUIRE(H >= 1 && H <= 16 && K == H * 256 && K <= LSM_NORM_KMAX && N > 0, IVL_ERR_UNSUPPORTED,
-              "ivl_gdn_out_linear_small_m_fwd: H=%d K=%d N=%d (K = H * 256 <= %d)", H, K, N, LSM_NORM_KMAX);
+  // (H >= 2, i.e. K >= 512: every lane of a wave must enter the weight loop, whose first trip holds the gated norm and its
+  // workgroup barrier -- as in the NORM form)
+  IVL_REQUIRE(H >= 2 && H <= 16 && K == H * 256 && K <= LSM_NORM_KMAX && N > 0, IVL_ERR_UNSUPPORTED,
+              "ivl_gdn_out_linear_small_m_fwd: H=%d K=%d N=%d (2 <= H <= 16, K = H * 256 <= %d: every lane must enter the weight loop, "
+              "whose first trip holds the gated norm, as in the NORM form)", H, K, N, LSM_NORM_KMAX);
   IVL_REQUIRE(gate_ld % 4 == 0 && ((size_t)gate & 7) == 0 && ((size_t)o_raw & 7) == 0, IVL_ERR_INVALID_ARG,
               "ivl_gdn_out_linear_small_m_fwd: o_raw / gate rows must be 8-byte aligned");
   GdnOutArgs ga;

@@ -272,7 +272,7 @@ class GatedDeltaNet(nn.Module):
         if (T == 1 and layer is not None and prev[0] is not None and h0 is not None and Dk == Dq
                 and h0.data_ptr() == layer.recurrent_state.data_ptr() and K == 128 and V == 256):
             ow, ob = self.o_proj.weight, self.o_proj.bias
-            if (ops._SPLIT_DECODE and B <= 4 and H <= 16 and ow.dtype == torch.bfloat16 and ow.is_contiguous() and cg % 4 == 0
+            if (ops._SPLIT_DECODE and B <= 4 and 2 <= H <= 16 and ow.dtype == torch.bfloat16 and ow.is_contiguous() and cg % 4 == 0
                     and ld % 4 == 0 and (ob is None or (ob.dtype == torch.bfloat16 and ob.is_contiguous()))):
                 # decode step on 64 workgroups (sequence x head x column quarter); the gated norm and the q / k conv-state shift ride
                 # in the o_proj launch: the same two launches, 4 x the memory parallelism for the 2 MB of state (bit-identical)

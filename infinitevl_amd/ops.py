@@ -814,7 +814,7 @@ def gdn_out_linear(o_raw: torch.Tensor, proj: torch.Tensor, col_g: int, col_q: i
                    H: int) -> torch.Tensor:
     """o_proj(o_norm(o_raw, gate)) for a decode step, one launch: the gated RMSNorm runs in the prologue of the weight stream, and
     the launch shifts the q / k conv states (the second half of gdn_decode_split's state update).  proj [B,1,ld] is the step's
-    fused projection (gate columns at col_g, raw q / k columns at col_q / col_k)."""
+    fused projection (gate columns at col_g, raw q / k columns at col_q / col_k).  2 <= H <= 16 heads (the kernel refuses others)."""
     _need_gpu(o_raw, proj, weight)
     B, T, ld = proj.shape
     K = o_raw.shape[-1]
