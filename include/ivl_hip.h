@@ -397,6 +397,33 @@ IVL_API int ivl_linear_swiglu_small_m_fwd(const void* x, const void* w_gate_up, 
 IVL_API int ivl_norm_linear_small_m_fwd(const void* x, const void* residual, const void* norm_weight, float eps, void* h_out,
                                 const void* w, const void* bias, void* y, int M, int N, int K, int glu, void* stream);
 
+/* WEIGHT-ONLY E4M3: the e4m3 twins of the four decode projections above -- the same argument lists, with
+ *   wq     uint8 [N,K] row-major, 16-byte aligned (GLU: [2I,K]): OCP e4m3fn codes (the gfx950 encoding, not e4m3fnuz) in place of w,
+ *   scale  fp32 [N] (GLU: [2I]): one scale per weight row.
+ *   y[m,n] = bf16(scale[n] * acc[m,n] + bias[n]),   acc[m,n] = the fp32 sum of float(code) * x (the decode of a code is exact).
+ * The summation ORDER is that of the bf16 kernels (linear_small_m_kernel / linear_gdn_out_kernel are ONE template over the weight
+ * element): per (weight row, x row) lane l of a wave adds the 8 products of chunk l + 64 i (8 elements = 8 bytes here) in element
+ * order with fmaf, i ascending, from 0; pieces past the row end add fmaf(w, 0, acc); then wave_sum.  scale * acc + bias is
+ * formed in fp32 (the product is exact for a power of two).  GLU, NORM and the gated norm with the conv-state shift are those of the bf16 forms;
+ * the x side is untouched.
+ * THE CONTRACT: with every scale[n] a power of two, each entry point equals its bf16 twin called on W' = dequantize(wq, scale)
+ * (W'[n,k] = float(code) * scale[n], exact in bf16) BIT FOR BIT -- y, h_out and the conv states -- because scaling an fp32 fmaf chain
+ * by a power of two commutes with every rounding in it (short of underflow / overflow).  The ABI does not check that a scale is a
+ * power of two: a general scale computes the formula above and loses the equality.  No e4m3 NaN code (0x7F / 0xFF) is expected.
+ * Ranges and refusals are those of the twins (M 1..4, K % 8 == 0, 512 <= K <= 4096 for NORM, 2 <= H <= 16 for the GDN form), NULL
+ * scale: IVL_ERR_INVALID_ARG; every check runs before anything is launched. */
+IVL_API int ivl_linear_small_m_w8_fwd(const void* x, const void* wq, const float* scale, const void* bias, void* y, int M, int N,
+                              int K, void* stream);
+IVL_API int ivl_linear_swiglu_small_m_w8_fwd(const void* x, const void* wq_gate_up, const float* scale, const void* bias, void* y,
+                                     int M, int I, int K, void* stream);
+IVL_API int ivl_norm_linear_small_m_w8_fwd(const void* x, const void* residual, const void* norm_weight, float eps, void* h_out,
+                                   const void* wq, const float* scale, const void* bias, void* y, int M, int N, int K, int glu,
+                                   void* stream);
+IVL_API int ivl_gdn_out_linear_small_m_w8_fwd(const void* o_raw, const void* gate, int64_t gate_ld, const void* norm_weight,
+                                      float eps, int H, const void* proj, int64_t proj_ld, int col_q, int col_k,
+                                      void* conv_state_q, void* conv_state_k, const void* wq, const float* scale,
+                                      const void* bias, void* y, int M, int N, int K, void* stream);
+
 /* nn.Linear for the wide projections of a prefill chunk of up to 256 rows: y[M,N] = bf16(x[M,K] W[N,K]^T + bias[N]), or with
  * glu != 0 the SwiGLU MLP head on the fused gate|up weight [2N,K] (N = I):
  *   y[M,I] = bf16( bf16(silu(bf16(x Wg^T + bg))) * bf16(x Wu^T + bu) ),  Wg = w[:I], Wu = w[I:], bias [2I] or NULL

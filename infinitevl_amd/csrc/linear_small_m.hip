@@ -17,6 +17,10 @@
 // add_round_ / sumsq8_ / qwen_norm_: the rows are bit-identical to that kernel's) into LDS while its first weight pieces are in
 // flight, and reads x from there;
 // workgroup 0 also writes the new residual stream h = bf16(x + residual).
+//
+// WEIGHT-ONLY E4M3 (the *_w8 entry points): the same kernels instantiated on 1-byte OCP e4m3fn codes with one fp32 scale
+// per weight row -- half the bytes of the stream, the x side untouched, and with power-of-two scales the bf16 kernels' output on the
+// dequantised weight bit for bit.
 #include "ivl_rowwise.h"
 
 namespace ivl {
@@ -31,6 +35,43 @@ __device__ __forceinline__ float dot8(u32x4 a, u32x4 b, float acc) {
 
 constexpr int LSM_U = 4;          // 16-byte pieces per lane per row in flight
 
+// e4m3 (OCP e4m3fn, the gfx950 encoding) piece of 8 weights = 8 bytes: v_cvt_pk_f32_fp8 decodes two bytes per instruction, exactly;
+// the products and their order are dot8's
+__device__ __forceinline__ float dot8_e4m3(u32x2 a, u32x4 b, float acc) {
+  const auto w01 = __builtin_amdgcn_cvt_pk_f32_fp8((int)a.x, false), w23 = __builtin_amdgcn_cvt_pk_f32_fp8((int)a.x, true);
+  const auto w45 = __builtin_amdgcn_cvt_pk_f32_fp8((int)a.y, false), w67 = __builtin_amdgcn_cvt_pk_f32_fp8((int)a.y, true);
+  acc = fmaf(w01[0], bflo(b.x), acc); acc = fmaf(w01[1], bfhi(b.x), acc);
+  acc = fmaf(w23[0], bflo(b.y), acc); acc = fmaf(w23[1], bfhi(b.y), acc);
+  acc = fmaf(w45[0], bflo(b.z), acc); acc = fmaf(w45[1], bfhi(b.z), acc);
+  acc = fmaf(w67[0], bflo(b.w), acc); acc = fmaf(w67[1], bfhi(b.w), acc);
+  return acc;
+}
+
+// WEIGHT-ELEMENT POLICIES.  The kernels below are written once; a policy says what a lane's piece of 8 weights is, how a row is
+// found and how a piece meets its 8 x values.  The lane -> chunk mapping, the fmaf chain and wave_sum -- the summation ORDER -- are
+// the kernels', so the e4m3 stream has the bf16 stream's order by construction.  Both keep LSM_U pieces per row in flight: an e4m3
+// piece is half the bytes, but 8 (and 16) of them per row measured SLOWER at M = 1 than 4 (lm_head 73 and 123 us against 47, gate|up
+// 14.5 against 12.3: DESIGN 4.13) -- the registers they take cost more occupancy than the bytes in flight buy.
+struct WBf16 {                                     // bf16 [N,K]: 16-byte pieces
+  using piece = u32x4;
+  using arg = const bf16_t* __restrict__;
+  static constexpr bool SCALED = false;
+  static bool null(arg w) { return w == nullptr; }
+  static __device__ __forceinline__ const piece* row(arg w, size_t r, int K) { return (const piece*)(w + r * K); }
+  static __device__ __forceinline__ float scale(arg, int) { return 1.f; }
+  static __device__ __forceinline__ float dot(piece a, u32x4 b, float acc) { return dot8(a, b, acc); }
+};
+struct W8Arg { const unsigned char* q; const float* scale; };
+struct WE4m3 {                                     // e4m3 codes [N,K] + one fp32 scale per row: 8-byte pieces
+  using piece = u32x2;
+  using arg = W8Arg;
+  static constexpr bool SCALED = true;
+  static bool null(arg w) { return w.q == nullptr || w.scale == nullptr; }
+  static __device__ __forceinline__ const piece* row(arg w, size_t r, int K) { return (const piece*)(w.q + r * K); }
+  static __device__ __forceinline__ float scale(arg w, int r) { return w.scale[r]; }
+  static __device__ __forceinline__ float dot(piece a, u32x4 b, float acc) { return dot8_e4m3(a, b, acc); }
+};
+
 struct NormArgs {
   const bf16_t* residual;          // NULL: plain norm of x
   const bf16_t* weight;            // RMSNorm weight [K]
@@ -43,22 +84,25 @@ constexpr int LSM_NORM_KMAX = 4096;
 // NIT: 16-byte pieces of a row per thread in the norm prologue (1: K <= 2048 -- the hidden size of the model; 2: K <= 4096);
 // the prologue's registers are live while the first weight batch is in flight, and 218 VGPRs meant 2 workgroups per CU: the M = 1
 // instances (the decode token) are capped at 168 (three workgroups per CU); M >= 2 would spill there and keeps the default
-template <int RPW, int M, bool GLU, bool NORM, int NIT = 2>
-__global__ __launch_bounds__(256, (NORM && M == 1) ? 3 : 1) void linear_small_m_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ w,
+template <class WT, int RPW, int M, bool GLU, bool NORM, int NIT = 2>
+__global__ __launch_bounds__(256, (NORM && M == 1) ? 3 : 1) void linear_small_m_kernel(const bf16_t* __restrict__ x, typename WT::arg w,
                                                             const bf16_t* __restrict__ bias, bf16_t* __restrict__ y,
                                                             int N, int K, NormArgs na) {
   constexpr int NR = GLU ? 2 * RPW : RPW;          // weight rows per wave
+  using piece_t = typename WT::piece;
   __shared__ __attribute__((aligned(16))) u32x4 s_x[NORM ? M * (LSM_NORM_KMAX / 8) : 1];
   __shared__ float s_part[NORM ? M : 1][4];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int nchunk = K >> 3;
   const int row0 = (blockIdx.x * 4 + wave) * RPW;
   if (!NORM && row0 >= N) return;                  // (NORM: every wave takes part in the barriers; its rows are clamped, its stores guarded)
-  const u32x4* wrow[NR];
+  const piece_t* wrow[NR];
+  float wscale[WT::SCALED ? NR : 1];               // (e4m3: the rows' scales, requested ahead of the stream -- the epilogue would wait for them)
 #pragma unroll
   for (int r = 0; r < NR; ++r) {
     const int rr = min(row0 + (r % RPW), N - 1) + (r >= RPW ? N : 0);      // GLU: rows [RPW, 2RPW) are the "up" rows
-    wrow[r] = (const u32x4*)(w + (size_t)rr * K);
+    wrow[r] = WT::row(w, (size_t)rr, K);
+    if constexpr (WT::SCALED) wscale[r] = WT::scale(w, __builtin_amdgcn_readfirstlane(rr));      // (wave-uniform: SGPRs)
   }
   float acc[NR][M];
 #pragma unroll
@@ -127,7 +171,8 @@ __global__ __launch_bounds__(256, (NORM && M == 1) ? 3 : 1) void linear_small_m_
   };
   bool first = true;
   for (int c0 = lane; c0 < nchunk; c0 += 64 * LSM_U) {
-    u32x4 wv[LSM_U][NR], xv[LSM_U][M];
+    piece_t wv[LSM_U][NR];
+    u32x4 xv[LSM_U][M];
 #pragma unroll
     for (int u = 0; u < LSM_U; ++u) {
       const int cc = min(c0 + 64 * u, nchunk - 1);
@@ -155,7 +200,7 @@ __global__ __launch_bounds__(256, (NORM && M == 1) ? 3 : 1) void linear_small_m_
 #pragma unroll
       for (int r = 0; r < NR; ++r)
 #pragma unroll
-        for (int m = 0; m < M; ++m) acc[r][m] = dot8(wv[u][r], xv[u][m], acc[r][m]);
+        for (int m = 0; m < M; ++m) acc[r][m] = WT::dot(wv[u][r], xv[u][m], acc[r][m]);
   }
 #pragma unroll
   for (int r = 0; r < RPW; ++r)
@@ -164,6 +209,10 @@ __global__ __launch_bounds__(256, (NORM && M == 1) ? 3 : 1) void linear_small_m_
       float s = wave_sum(acc[r][m]);
       float s2 = 0.f;
       if (GLU) s2 = wave_sum(acc[RPW + r][m]);
+      if constexpr (WT::SCALED) {                  // y = bf16(scale * acc + bias): the product is exact for a scale 2^e
+        s = wscale[r] * s;
+        if (GLU) s2 = wscale[RPW + r] * s2;
+      }
       if (lane == 0 && row0 + r < N) {
         if (GLU) {
           const float gt = bf_round(s + (bias != nullptr ? bf2f(bias[row0 + r]) : 0.f));          // gate_proj output
@@ -179,45 +228,45 @@ __global__ __launch_bounds__(256, (NORM && M == 1) ? 3 : 1) void linear_small_m_
     }
 }
 
-template <int RPW, bool GLU, bool NORM>
-static void launch_lsm(const bf16_t* x, const bf16_t* w, const bf16_t* bias, bf16_t* y, int M, int N, int K, const NormArgs& na,
+template <class WT, int RPW, bool GLU, bool NORM>
+static void launch_lsm(const bf16_t* x, typename WT::arg w, const bf16_t* bias, bf16_t* y, int M, int N, int K, const NormArgs& na,
                        hipStream_t st) {
   const int rows_per_wg = 4 * RPW;
   dim3 grid((N + rows_per_wg - 1) / rows_per_wg);
   if (NORM && K <= 2048) {
     switch (M) {
-      case 1: hipLaunchKernelGGL((linear_small_m_kernel<RPW, 1, GLU, NORM, 1>), grid, dim3(256), 0, st, x, w, bias, y, N, K, na); break;
-      case 2: hipLaunchKernelGGL((linear_small_m_kernel<RPW, 2, GLU, NORM, 1>), grid, dim3(256), 0, st, x, w, bias, y, N, K, na); break;
-      case 3: hipLaunchKernelGGL((linear_small_m_kernel<RPW, 3, GLU, NORM, 1>), grid, dim3(256), 0, st, x, w, bias, y, N, K, na); break;
-      default: hipLaunchKernelGGL((linear_small_m_kernel<RPW, 4, GLU, NORM, 1>), grid, dim3(256), 0, st, x, w, bias, y, N, K, na); break;
+      case 1: hipLaunchKernelGGL((linear_small_m_kernel<WT, RPW, 1, GLU, NORM, 1>), grid, dim3(256), 0, st, x, w, bias, y, N, K, na); break;
+      case 2: hipLaunchKernelGGL((linear_small_m_kernel<WT, RPW, 2, GLU, NORM, 1>), grid, dim3(256), 0, st, x, w, bias, y, N, K, na); break;
+      case 3: hipLaunchKernelGGL((linear_small_m_kernel<WT, RPW, 3, GLU, NORM, 1>), grid, dim3(256), 0, st, x, w, bias, y, N, K, na); break;
+      default: hipLaunchKernelGGL((linear_small_m_kernel<WT, RPW, 4, GLU, NORM, 1>), grid, dim3(256), 0, st, x, w, bias, y, N, K, na); break;
     }
     return;
   }
   switch (M) {
-    case 1: hipLaunchKernelGGL((linear_small_m_kernel<RPW, 1, GLU, NORM>), grid, dim3(256), 0, st, x, w, bias, y, N, K, na); break;
-    case 2: hipLaunchKernelGGL((linear_small_m_kernel<RPW, 2, GLU, NORM>), grid, dim3(256), 0, st, x, w, bias, y, N, K, na); break;
-    case 3: hipLaunchKernelGGL((linear_small_m_kernel<RPW, 3, GLU, NORM>), grid, dim3(256), 0, st, x, w, bias, y, N, K, na); break;
-    default: hipLaunchKernelGGL((linear_small_m_kernel<RPW, 4, GLU, NORM>), grid, dim3(256), 0, st, x, w, bias, y, N, K, na); break;
+    case 1: hipLaunchKernelGGL((linear_small_m_kernel<WT, RPW, 1, GLU, NORM>), grid, dim3(256), 0, st, x, w, bias, y, N, K, na); break;
+    case 2: hipLaunchKernelGGL((linear_small_m_kernel<WT, RPW, 2, GLU, NORM>), grid, dim3(256), 0, st, x, w, bias, y, N, K, na); break;
+    case 3: hipLaunchKernelGGL((linear_small_m_kernel<WT, RPW, 3, GLU, NORM>), grid, dim3(256), 0, st, x, w, bias, y, N, K, na); break;
+    default: hipLaunchKernelGGL((linear_small_m_kernel<WT, RPW, 4, GLU, NORM>), grid, dim3(256), 0, st, x, w, bias, y, N, K, na); break;
   }
 }
 
-template <bool NORM>
-static int lsm_dispatch(const void* x, const void* w, const void* bias, void* y, int M, int N, int K, bool glu, const NormArgs& na,
+template <class WT, bool NORM>
+static int lsm_dispatch(const void* x, typename WT::arg wp, const void* bias, void* y, int M, int N, int K, bool glu, const NormArgs& na,
                         void* stream, const char* who) {
-  IVL_REQUIRE(x && w && y, IVL_ERR_INVALID_ARG, "%s: NULL pointer", who);
+  IVL_REQUIRE(x && !WT::null(wp) && y, IVL_ERR_INVALID_ARG, "%s: NULL pointer", who);
   IVL_REQUIRE(M >= 1 && M <= 4, IVL_ERR_UNSUPPORTED, "%s: M=%d (built for 1..4 rows; use a GEMM)", who, M);
   IVL_REQUIRE(N > 0 && K > 0 && K % 8 == 0, IVL_ERR_INVALID_ARG, "%s: N=%d K=%d (K must be a multiple of 8)", who, N, K);
   hipStream_t st = (hipStream_t)stream;
-  const bf16_t *xp = (const bf16_t*)x, *wp = (const bf16_t*)w, *bp = (const bf16_t*)bias;
+  const bf16_t *xp = (const bf16_t*)x, *bp = (const bf16_t*)bias;
   bf16_t* yp = (bf16_t*)y;
   // rows per wave: enough workgroups to cover the chip (>= ~2 per CU) before amortising the x reads over more rows
   if (glu) {
-    if (N >= 4096) launch_lsm<2, true, NORM>(xp, wp, bp, yp, M, N, K, na, st);       // 4 weight rows per wave
-    else launch_lsm<1, true, NORM>(xp, wp, bp, yp, M, N, K, na, st);
+    if (N >= 4096) launch_lsm<WT, 2, true, NORM>(xp, wp, bp, yp, M, N, K, na, st);       // 4 weight rows per wave
+    else launch_lsm<WT, 1, true, NORM>(xp, wp, bp, yp, M, N, K, na, st);
   } else {
-    if (N >= 8192) launch_lsm<4, false, NORM>(xp, wp, bp, yp, M, N, K, na, st);
-    else if (N >= 4096) launch_lsm<2, false, NORM>(xp, wp, bp, yp, M, N, K, na, st);
-    else launch_lsm<1, false, NORM>(xp, wp, bp, yp, M, N, K, na, st);
+    if (N >= 8192) launch_lsm<WT, 4, false, NORM>(xp, wp, bp, yp, M, N, K, na, st);
+    else if (N >= 4096) launch_lsm<WT, 2, false, NORM>(xp, wp, bp, yp, M, N, K, na, st);
+    else launch_lsm<WT, 1, false, NORM>(xp, wp, bp, yp, M, N, K, na, st);
   }
   return check_launch(who);
 }
@@ -237,14 +286,17 @@ struct GdnOutArgs {
   const bf16_t* proj; long long proj_ld; int col_q, col_k;
   bf16_t* cq; bf16_t* ck; int Dq;                  // conv states [M, Dq, 4] of q and k
 };
-template <int M>
-__global__ __launch_bounds__(256) void linear_gdn_out_kernel(const bf16_t* __restrict__ o_raw, const bf16_t* __restrict__ w,
+template <class WT, int M>
+__global__ __launch_bounds__(256) void linear_gdn_out_kernel(const bf16_t* __restrict__ o_raw, typename WT::arg w,
                                                              const bf16_t* __restrict__ bias, bf16_t* __restrict__ y, int N, int K, GdnOutArgs ga) {
   __shared__ __attribute__((aligned(16))) u32x4 s_x[M * (LSM_NORM_KMAX / 8)];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, tid = threadIdx.x;
   const int nchunk = K >> 3;
+  using piece_t = typename WT::piece;
   const int row = min((int)blockIdx.x * 4 + wave, N - 1);
-  const u32x4* wrow = (const u32x4*)(w + (size_t)row * K);
+  const piece_t* wrow = WT::row(w, (size_t)row, K);
+  float wscale = 1.f;
+  if constexpr (WT::SCALED) wscale = WT::scale(w, __builtin_amdgcn_readfirstlane(row));
   // ---- conv-state shift of q and k (a few items per workgroup; independent of everything else here) ----
   {
     const int total = M * 2 * ga.Dq;
@@ -274,7 +326,7 @@ __global__ __launch_bounds__(256) void linear_gdn_out_kernel(const bf16_t* __res
   for (int m = 0; m < M; ++m) acc[m] = 0.f;
   bool first = true;
   for (int c0 = lane; c0 < nchunk; c0 += 64 * LSM_U) {
-    u32x4 wvv[LSM_U];
+    piece_t wvv[LSM_U];
 #pragma unroll
     for (int u = 0; u < LSM_U; ++u) wvv[u] = __builtin_nontemporal_load(wrow + min(c0 + 64 * u, nchunk - 1));
     if (first) {                                   // (workgroup-uniform trip count)
@@ -303,13 +355,14 @@ __global__ __launch_bounds__(256) void linear_gdn_out_kernel(const bf16_t* __res
 #pragma unroll
       for (int m = 0; m < M; ++m) {
         const u32x4 xl = c < nchunk ? s_x[m * (LSM_NORM_KMAX / 8) + cc] : u32x4{0u, 0u, 0u, 0u};
-        acc[m] = dot8(wvv[u], xl, acc[m]);
+        acc[m] = WT::dot(wvv[u], xl, acc[m]);
       }
     }
   }
 #pragma unroll
   for (int m = 0; m < M; ++m) {
-    const float sum = wave_sum(acc[m]);
+    float sum = wave_sum(acc[m]);
+    if constexpr (WT::SCALED) sum = wscale * sum;
     if (lane == 0 && (int)blockIdx.x * 4 + wave < N)
       y[(size_t)m * N + row] = f2bf(sum + (bias != nullptr ? bf2f(bias[row]) : 0.f));
   }
@@ -319,58 +372,102 @@ __global__ __launch_bounds__(256) void linear_gdn_out_kernel(const bf16_t* __res
 
 using namespace ivl;
 
+// ---- the bf16 entry points -------------------------------------------------------------------------------------------------
 extern "C" int ivl_linear_small_m_fwd(const void* x, const void* w, const void* bias, void* y, int M, int N, int K,
                                       void* stream) {
-  return lsm_dispatch<false>(x, w, bias, y, M, N, K, false, NormArgs{}, stream, "ivl_linear_small_m_fwd");
+  return lsm_dispatch<WBf16, false>(x, (const bf16_t*)w, bias, y, M, N, K, false, NormArgs{}, stream, "ivl_linear_small_m_fwd");
 }
 
 extern "C" int ivl_linear_swiglu_small_m_fwd(const void* x, const void* w_gate_up, const void* bias, void* y, int M, int I,
                                              int K, void* stream) {
-  return lsm_dispatch<false>(x, w_gate_up, bias, y, M, I, K, true, NormArgs{}, stream, "ivl_linear_swiglu_small_m_fwd");
+  return lsm_dispatch<WBf16, false>(x, (const bf16_t*)w_gate_up, bias, y, M, I, K, true, NormArgs{}, stream, "ivl_linear_swiglu_small_m_fwd");
+}
+
+template <class WT>
+static int norm_linear(const void* x, const void* residual, const void* norm_weight, float eps, void* h_out, typename WT::arg w,
+                       const void* bias, void* y, int M, int N, int K, int glu, void* stream, const char* who) {
+  IVL_REQUIRE(norm_weight != nullptr, IVL_ERR_INVALID_ARG, "%s: NULL norm weight", who);
+  IVL_REQUIRE(residual == nullptr || h_out != nullptr, IVL_ERR_INVALID_ARG, "%s: residual needs h_out", who);
+  // (K >= 512: every lane of a wave must enter the weight loop, whose first trip holds the workgroup barriers of the norm)
+  IVL_REQUIRE(K >= 512 && K <= LSM_NORM_KMAX, IVL_ERR_UNSUPPORTED,
+              "%s: K=%d (the normalised rows are staged in LDS by the whole workgroup: 512 <= K <= %d)", who, K, LSM_NORM_KMAX);
+  NormArgs na;
+  na.residual = (const bf16_t*)residual; na.weight = (const bf16_t*)norm_weight; na.h_out = (bf16_t*)h_out; na.eps = eps;
+  return lsm_dispatch<WT, true>(x, w, bias, y, M, N, K, glu != 0, na, stream, who);
 }
 
 extern "C" int ivl_norm_linear_small_m_fwd(const void* x, const void* residual, const void* norm_weight, float eps, void* h_out,
                                            const void* w, const void* bias, void* y, int M, int N, int K, int glu, void* stream) {
-  IVL_REQUIRE(norm_weight != nullptr, IVL_ERR_INVALID_ARG, "ivl_norm_linear_small_m_fwd: NULL norm weight");
-  IVL_REQUIRE(residual == nullptr || h_out != nullptr, IVL_ERR_INVALID_ARG, "ivl_norm_linear_small_m_fwd: residual needs h_out");
-  // (K >= 512: every lane of a wave must enter the weight loop, whose first trip holds the workgroup barriers of the norm)
-  IVL_REQUIRE(K >= 512 && K <= LSM_NORM_KMAX, IVL_ERR_UNSUPPORTED,
-              "ivl_norm_linear_small_m_fwd: K=%d (the normalised rows are staged in LDS by the whole workgroup: 512 <= K <= %d)", K, LSM_NORM_KMAX);
-  NormArgs na;
-  na.residual = (const bf16_t*)residual; na.weight = (const bf16_t*)norm_weight; na.h_out = (bf16_t*)h_out; na.eps = eps;
-  return lsm_dispatch<true>(x, w, bias, y, M, N, K, glu != 0, na, stream, "ivl_norm_linear_small_m_fwd");
+  return norm_linear<WBf16>(x, residual, norm_weight, eps, h_out, (const bf16_t*)w, bias, y, M, N, K, glu, stream,
+                            "ivl_norm_linear_small_m_fwd");
 }
 
 // o_proj of a GDN decode step with the gated RMSNorm in the prologue and the q / k conv-state shift riding along (see
 // linear_gdn_out_kernel; pairs with ivl_gdn_decode_split_fwd).  o_raw bf16 [M, H*256] (un-normalised delta-rule output), gate =
 // first gate element of row 0 (row stride gate_ld elements), proj = the step's projection rows (row stride proj_ld), conv states
 // [M, Dq, 4] of q and k (updated in place).  y[M, N] = o_norm(o_raw, gate) W^T (+ bias).
-extern "C" int ivl_gdn_out_linear_small_m_fwd(const void* o_raw, const void* gate, int64_t gate_ld, const void* norm_weight, float eps,
-                                              int H, const void* proj, int64_t proj_ld, int col_q, int col_k, void* conv_state_q,
-                                              void* conv_state_k, const void* w, const void* bias, void* y, int M, int N, int K,
-                                              void* stream) {
-  IVL_REQUIRE(o_raw && gate && norm_weight && proj && conv_state_q && conv_state_k && w && y, IVL_ERR_INVALID_ARG,
-              "ivl_gdn_out_linear_small_m_fwd: NULL pointer");
-  IVL_REQUIRE(M >= 1 && M <= 4, IVL_ERR_UNSUPPORTED, "ivl_gdn_out_linear_small_m_fwd: M=%d (built for 1..4 rows)", M);
+template <class WT>
+static int gdn_out_linear(const void* o_raw, const void* gate, int64_t gate_ld, const void* norm_weight, float eps, int H,
+                          const void* proj, int64_t proj_ld, int col_q, int col_k, void* conv_state_q, void* conv_state_k,
+                          typename WT::arg w, const void* bias, void* y, int M, int N, int K, void* stream, const char* who) {
+  IVL_REQUIRE(o_raw && gate && norm_weight && proj && conv_state_q && conv_state_k && !WT::null(w) && y, IVL_ERR_INVALID_ARG,
+              "%s: NULL pointer", who);
+  IVL_REQUIRE(M >= 1 && M <= 4, IVL_ERR_UNSUPPORTED, "%s: M=%d (built for 1..4 rows)", who, M);
   // (H >= 2, i.e. K >= 512: every lane of a wave must enter the weight loop, whose first trip holds the gated norm and its
   // workgroup barrier -- as in the NORM form)
   IVL_REQUIRE(H >= 2 && H <= 16 && K == H * 256 && K <= LSM_NORM_KMAX && N > 0, IVL_ERR_UNSUPPORTED,
-              "ivl_gdn_out_linear_small_m_fwd: H=%d K=%d N=%d (2 <= H <= 16, K = H * 256 <= %d: every lane must enter the weight loop, "
-              "whose first trip holds the gated norm, as in the NORM form)", H, K, N, LSM_NORM_KMAX);
+              "%s: H=%d K=%d N=%d (2 <= H <= 16, K = H * 256 <= %d: every lane must enter the weight loop, "
+              "whose first trip holds the gated norm, as in the NORM form)", who, H, K, N, LSM_NORM_KMAX);
   IVL_REQUIRE(gate_ld % 4 == 0 && ((size_t)gate & 7) == 0 && ((size_t)o_raw & 7) == 0, IVL_ERR_INVALID_ARG,
-              "ivl_gdn_out_linear_small_m_fwd: o_raw / gate rows must be 8-byte aligned");
+              "%s: o_raw / gate rows must be 8-byte aligned", who);
   GdnOutArgs ga;
   ga.gate = (const bf16_t*)gate; ga.gate_ld = gate_ld; ga.norm_w = (const bf16_t*)norm_weight; ga.eps = eps; ga.H = H;
   ga.proj = (const bf16_t*)proj; ga.proj_ld = proj_ld; ga.col_q = col_q; ga.col_k = col_k;
   ga.cq = (bf16_t*)conv_state_q; ga.ck = (bf16_t*)conv_state_k; ga.Dq = H * 128;
   const dim3 grid((N + 3) / 4);
   hipStream_t st = (hipStream_t)stream;
-  const bf16_t *op = (const bf16_t*)o_raw, *wp = (const bf16_t*)w, *bp = (const bf16_t*)bias;
+  const bf16_t *op = (const bf16_t*)o_raw, *bp = (const bf16_t*)bias;
   switch (M) {
-    case 1: hipLaunchKernelGGL((linear_gdn_out_kernel<1>), grid, dim3(256), 0, st, op, wp, bp, (bf16_t*)y, N, K, ga); break;
-    case 2: hipLaunchKernelGGL((linear_gdn_out_kernel<2>), grid, dim3(256), 0, st, op, wp, bp, (bf16_t*)y, N, K, ga); break;
-    case 3: hipLaunchKernelGGL((linear_gdn_out_kernel<3>), grid, dim3(256), 0, st, op, wp, bp, (bf16_t*)y, N, K, ga); break;
-    default: hipLaunchKernelGGL((linear_gdn_out_kernel<4>), grid, dim3(256), 0, st, op, wp, bp, (bf16_t*)y, N, K, ga); break;
+    case 1: hipLaunchKernelGGL((linear_gdn_out_kernel<WT, 1>), grid, dim3(256), 0, st, op, w, bp, (bf16_t*)y, N, K, ga); break;
+    case 2: hipLaunchKernelGGL((linear_gdn_out_kernel<WT, 2>), grid, dim3(256), 0, st, op, w, bp, (bf16_t*)y, N, K, ga); break;
+    case 3: hipLaunchKernelGGL((linear_gdn_out_kernel<WT, 3>), grid, dim3(256), 0, st, op, w, bp, (bf16_t*)y, N, K, ga); break;
+    default: hipLaunchKernelGGL((linear_gdn_out_kernel<WT, 4>), grid, dim3(256), 0, st, op, w, bp, (bf16_t*)y, N, K, ga); break;
   }
-  return check_launch("ivl_gdn_out_linear_small_m_fwd");
+  return check_launch(who);
+}
+
+extern "C" int ivl_gdn_out_linear_small_m_fwd(const void* o_raw, const void* gate, int64_t gate_ld, const void* norm_weight, float eps,
+                                              int H, const void* proj, int64_t proj_ld, int col_q, int col_k, void* conv_state_q,
+                                              void* conv_state_k, const void* w, const void* bias, void* y, int M, int N, int K,
+                                              void* stream) {
+  return gdn_out_linear<WBf16>(o_raw, gate, gate_ld, norm_weight, eps, H, proj, proj_ld, col_q, col_k, conv_state_q, conv_state_k,
+                               (const bf16_t*)w, bias, y, M, N, K, stream, "ivl_gdn_out_linear_small_m_fwd");
+}
+
+// ---- the e4m3 twins: wq uint8 [N,K] (GLU: [2I,K]) OCP e4m3fn codes, scale fp32 [N] / [2I]; everything else as above --------------
+extern "C" int ivl_linear_small_m_w8_fwd(const void* x, const void* wq, const float* scale, const void* bias, void* y, int M, int N,
+                                         int K, void* stream) {
+  return lsm_dispatch<WE4m3, false>(x, W8Arg{(const unsigned char*)wq, scale}, bias, y, M, N, K, false, NormArgs{}, stream,
+                                    "ivl_linear_small_m_w8_fwd");
+}
+
+extern "C" int ivl_linear_swiglu_small_m_w8_fwd(const void* x, const void* wq, const float* scale, const void* bias, void* y, int M,
+                                                int I, int K, void* stream) {
+  return lsm_dispatch<WE4m3, false>(x, W8Arg{(const unsigned char*)wq, scale}, bias, y, M, I, K, true, NormArgs{}, stream,
+                                    "ivl_linear_swiglu_small_m_w8_fwd");
+}
+
+extern "C" int ivl_norm_linear_small_m_w8_fwd(const void* x, const void* residual, const void* norm_weight, float eps, void* h_out,
+                                              const void* wq, const float* scale, const void* bias, void* y, int M, int N, int K,
+                                              int glu, void* stream) {
+  return norm_linear<WE4m3>(x, residual, norm_weight, eps, h_out, W8Arg{(const unsigned char*)wq, scale}, bias, y, M, N, K, glu, stream,
+                            "ivl_norm_linear_small_m_w8_fwd");
+}
+
+extern "C" int ivl_gdn_out_linear_small_m_w8_fwd(const void* o_raw, const void* gate, int64_t gate_ld, const void* norm_weight,
+                                                 float eps, int H, const void* proj, int64_t proj_ld, int col_q, int col_k,
+                                                 void* conv_state_q, void* conv_state_k, const void* wq, const float* scale,
+                                                 const void* bias, void* y, int M, int N, int K, void* stream) {
+  return gdn_out_linear<WE4m3>(o_raw, gate, gate_ld, norm_weight, eps, H, proj, proj_ld, col_q, col_k, conv_state_q, conv_state_k,
+                               W8Arg{(const unsigned char*)wq, scale}, bias, y, M, N, K, stream, "ivl_gdn_out_linear_small_m_w8_fwd");
 }

@@ -112,6 +112,17 @@ class InfiniteVLTextMLP(nn.Module):
         self.down_proj = nn.Linear(config.intermediate_size, config.hidden_size, bias=False)
 
         self._fused_w = None
+        self._w8_gu = self._w8_down = None  # ops.PackedWeight of the fused gate|up weight and of down_proj (quantize_weights_)
+        self._w8_on = False
+
+    @torch.no_grad()
+    def quantize_weights_(self) -> "InfiniteVLTextMLP":
+        """Round the fused gate|up weight and down_proj onto the e4m3 x 2^e grid IN PLACE and keep the packed copies."""
+        if self._fused_w is None:
+            raise RuntimeError("quantize_weights_: call fuse_() first")
+        self._w8_gu = ops.PackedWeight.of(self._fused_w, also=(self.gate_proj.weight, self.up_proj.weight))
+        self._w8_down = ops.PackedWeight.of(self.down_proj.weight)
+        return self
 
     @torch.no_grad()
     def fuse_(self) -> "InfiniteVLTextMLP":
@@ -125,7 +136,8 @@ class InfiniteVLTextMLP(nn.Module):
     def forward(self, x):
         if (self._fused_w is not None and x.is_cuda and x.dtype == torch.bfloat16
                 and self.gate_proj.weight.data_ptr() == self._fused_w.data_ptr()):
-            return ops.linear(ops.linear_swiglu(x, self._fused_w), self.down_proj.weight)
+            w8_gu, w8_down = ops.w8_kwargs(self._w8_gu, self._w8_on), ops.w8_kwargs(self._w8_down, self._w8_on)
+            return ops.linear(ops.linear_swiglu(x, self._fused_w, **w8_gu), self.down_proj.weight, **w8_down)
         if isinstance(x, ops.PreNorm):
             x = x.materialize()
         return self.down_proj(F.silu(self.gate_proj(x)) * self.up_proj(x))
@@ -168,6 +180,8 @@ class InfiniteVLTextStack(nn.Module):
         self.layers = nn.ModuleList([InfiniteVLDecoderLayer(config, i) for i in range(config.num_hidden_layers)])
         self.norm = InfiniteVLRMSNorm(config.hidden_size, eps=config.rms_norm_eps)
         self.rotary_emb = InfiniteVLRotaryEmbedding(config)
+        self._w8_lm_head = None                 # ops.PackedWeight of the tied embed_tokens.weight (quantize_weights_(lm_head=True))
+        self._w8_on = False
 
     @torch.no_grad()
     def init_weights_(self, seed: int = 0, std: float = 0.02) -> "InfiniteVLTextStack":
@@ -201,6 +215,32 @@ class InfiniteVLTextStack(nn.Module):
         for layer in self.layers:
             layer.self_attn.fuse_()
             layer.mlp.fuse_()
+        return self
+
+    @torch.no_grad()
+    def quantize_weights_(self, lm_head: bool = False) -> "InfiniteVLTextStack":
+        """Weight-only e4m3 for the decode step (call after fuse_()).  THIS CHANGES THE MODEL'S WEIGHTS: every
+        projection weight -- the fused q|k|v, the attention o_proj, the fused GDN in-projection, the GDN o_proj, the fused gate|up,
+        down_proj, and with lm_head=True the tied embed_tokens.weight (the embedding lookup then reads the rounded weight too) --
+        is rounded IN PLACE to W' = e4m3 code x 2^e, one power of two per row (ops.quantize_rows_e4m3), and keeps a packed
+        copy of the codes (+1 byte per weight on top of the bf16 weight, which prefill and every M > 4 call still read).
+        Biases, norm and conv weights stay bf16.  From then on every path computes the same function bit for bit whether the
+        packed copies are used (decode steps of <= 4 rows stream 1 byte per weight) or not: use_packed_weights() switches.
+        Writing the weights afterwards (load_state_dict) makes the packed copies stale -- the next call raises; quantise again."""
+        for layer in self.layers:
+            layer.self_attn.quantize_weights_()
+            layer.mlp.quantize_weights_()
+        self._w8_lm_head = ops.PackedWeight.of(self.embed_tokens.weight) if lm_head else None
+        return self.use_packed_weights(True)
+
+    def use_packed_weights(self, on: bool = True) -> "InfiniteVLTextStack":
+        """Stream the packed e4m3 copies in decode steps (True) or the bf16 weights, which hold the same values (False); the
+        weights are not touched.  Call it before a capture: a graphed class recaptures when the switch changed after its capture."""
+        if on and any(m._w8_o is None for m in (layer.self_attn for layer in self.layers)):
+            raise RuntimeError("use_packed_weights(True): call quantize_weights_() first")
+        self._w8_on = bool(on)
+        for layer in self.layers:
+            layer.self_attn._w8_on = layer.mlp._w8_on = self._w8_on
         return self
 
     def set_mma_dtype(self, mma_dtype) -> "InfiniteVLTextStack":
@@ -272,7 +312,8 @@ class InfiniteVLTextStack(nn.Module):
             _, h = self.norm.add_and_norm(pend, resid)
         logits = None
         if logits_to_keep:
-            logits = ops.linear(h[:, -logits_to_keep:, :], self.embed_tokens.weight)  # tied lm_head (std:2091-2092)
+            logits = ops.linear(h[:, -logits_to_keep:, :], self.embed_tokens.weight,  # tied lm_head (std:2091-2092)
+                                **ops.w8_kwargs(self._w8_lm_head, self._w8_on))
         return h, logits
 
 
@@ -336,6 +377,7 @@ class _Graphed:
 
     sampler: Optional["Sampler"] = None                 # (GraphedStep has none)
     _captured_controlled = False
+    _captured_w8 = False
 
     def _capture(self, tensors: List[torch.Tensor], scope=None):
         """Captures one self._run() into self.graph and returns what it returned.  The cache, `tensors` and the sampler's state
@@ -359,11 +401,17 @@ class _Graphed:
         if self.sampler is not None:
             self.sampler.load_state(saved_smp)          # the warm-up and the capture itself made draws
             self._captured_controlled = self.sampler.controlled
+        self._captured_w8 = self._w8_on()
         return out
 
+    def _w8_on(self) -> bool:
+        return bool(getattr(self.model, "_w8_on", False))
+
     def _stale(self) -> bool:
-        """No graph yet, or one captured before the sampler switched to the controlled launch."""
-        return self.graph is None or (self.sampler is not None and self.sampler.controlled != self._captured_controlled)
+        """No graph yet, or one captured before the sampler switched to the controlled launch or before the model switched
+        between its bf16 weights and their packed e4m3 copies (use_packed_weights)."""
+        return (self.graph is None or (self.sampler is not None and self.sampler.controlled != self._captured_controlled)
+                or self._w8_on() != self._captured_w8)
 
     def _run(self):
         """The T = 1 step: forward of every row's token, its next token, positions + 1."""
@@ -423,7 +471,7 @@ class GraphedStep(_Graphed):
                                 .expand(3, self.B, self.T))
 
     def step(self, inputs_embeds: Optional[torch.Tensor] = None):
-        if self.graph is None:
+        if self._stale():
             self.capture()
         self.cache.ensure_started()          # a replayed graph always reads the cache tensors (no-op once started)
         if inputs_embeds is not None:

@@ -77,6 +77,8 @@ class InfiniteVLSelfAttention(nn.Module):
                                if config.layer_types[self.layer_idx] == "sliding_attention" else None)
         self.rotary_emb = InfiniteVLRotaryEmbedding(config=config)
         self._fused_w = self._fused_b = None
+        self._w8_qkv = self._w8_o = None    # ops.PackedWeight of the fused q|k|v weight and of o_proj (quantize_weights_)
+        self._w8_on = False
         self.mma_dtype = None           # None = bf16 operands; "fp8_e4m3": single-token decode products on e4m3 (configs[4])
 
     @torch.no_grad()
@@ -120,7 +122,7 @@ class InfiniteVLSelfAttention(nn.Module):
                      and not (self.mma_dtype is not None and q_len * self.num_key_value_groups <= 64))
         if self._fused_ok(hidden_states):
             nq, nkv = self.num_heads * self.head_dim, self.num_key_value_heads * self.head_dim
-            qkv = ops.linear(hidden_states, self._fused_w, self._fused_b)                     # [B,T,nq+2nkv]
+            qkv = ops.linear(hidden_states, self._fused_w, self._fused_b, **ops.w8_kwargs(self._w8_qkv, self._w8_on))  # [B,T,nq+2nkv]
             q = qkv[..., :nq].unflatten(-1, (self.num_heads, self.head_dim))
             k = qkv[..., nq:nq + nkv].unflatten(-1, (self.num_key_value_heads, self.head_dim))
             v = qkv[..., nq + nkv:].unflatten(-1, (self.num_key_value_heads, self.head_dim))
@@ -145,7 +147,16 @@ class InfiniteVLSelfAttention(nn.Module):
             attn, _ = ops.swa_attention_interface(self, q.transpose(1, 2), fk, fv, None, scaling=self.scaling,
                                                   sliding_window=self.sliding_window)
         attn = attn.reshape(bsz, q_len, -1)
-        return ops.linear(attn, self.o_proj.weight, self.o_proj.bias), None
+        return ops.linear(attn, self.o_proj.weight, self.o_proj.bias, **ops.w8_kwargs(self._w8_o, self._w8_on)), None
+
+    @torch.no_grad()
+    def quantize_weights_(self) -> "InfiniteVLSelfAttention":
+        """Round the fused q|k|v weight and o_proj onto the e4m3 x 2^e grid IN PLACE and keep the packed copies (after fuse_())."""
+        if self._fused_w is None:
+            raise RuntimeError("quantize_weights_: call fuse_() first")
+        self._w8_qkv = ops.PackedWeight.of(self._fused_w, also=(self.q_proj.weight, self.k_proj.weight, self.v_proj.weight))
+        self._w8_o = ops.PackedWeight.of(self.o_proj.weight)
+        return self
 
 
 class GatedDeltaNet(nn.Module):
@@ -208,6 +219,8 @@ class GatedDeltaNet(nn.Module):
         self._fused_w = None
         self._fused_cols = None
         self._gate32 = None
+        self._w8_in = self._w8_o = None     # ops.PackedWeight of the fused in-projection and of o_proj (quantize_weights_)
+        self._w8_on = False
         self.mma_dtype = None           # None = the reference's bf16 operands; "fp8_e4m3" = BASELINE.json configs[4]
 
     @torch.no_grad()
@@ -234,6 +247,16 @@ class GatedDeltaNet(nn.Module):
         self._gate32 = None
         return self
 
+    @torch.no_grad()
+    def quantize_weights_(self) -> "GatedDeltaNet":
+        """Round the fused q|k|v|g|a|b weight and o_proj onto the e4m3 x 2^e grid IN PLACE and keep the packed copies."""
+        if self._fused_w is None:
+            raise RuntimeError("quantize_weights_: call fuse_() first (the Gated DeltaNet needs use_gate)")
+        self._w8_in = ops.PackedWeight.of(self._fused_w, also=(self.q_proj.weight, self.k_proj.weight, self.v_proj.weight,
+                                                              self.g_proj.weight, self.a_proj.weight, self.b_proj.weight))
+        self._w8_o = ops.PackedWeight.of(self.o_proj.weight)
+        return self
+
     def _gate_params32(self):
         """fp32 copies of A_log / dt_bias for the gate math (std:1294 upcasts them per call); cached and
         refreshed whenever the parameters are modified in place (e.g. load_state_dict after fuse_)."""
@@ -255,7 +278,8 @@ class GatedDeltaNet(nn.Module):
         H, K, V = self.num_heads, self.head_dim, self.head_v_dim
         Dq, Dk, Dv = H * K, self.key_dim, self.value_dim
         cq, ck, cv, cg, ca, cb = self._fused_cols
-        proj = ops.linear(hidden_states, self._fused_w)                               # [B,T,ld]
+        w8_in, w8_o = ops.w8_kwargs(self._w8_in, self._w8_on), ops.w8_kwargs(self._w8_o, self._w8_on)
+        proj = ops.linear(hidden_states, self._fused_w, **w8_in)                      # [B,T,ld]
         ld = proj.shape[-1]
         prev = (None, None, None)
         h0 = None
@@ -279,7 +303,7 @@ class GatedDeltaNet(nn.Module):
                 o_raw = ops.gdn_decode_split(proj, (cq, ck, cv, ca, cb),
                                              (self.q_conv1d.weight, self.k_conv1d.weight, self.v_conv1d.weight), outs, A32, dt32,
                                              layer.recurrent_state, H, K, V, K ** -0.5)
-                y = ops.gdn_out_linear(o_raw, proj, cg, cq, ck, w, self.norm_eps, outs[0], outs[1], ow, ob, H)
+                y = ops.gdn_out_linear(o_raw, proj, cg, cq, ck, w, self.norm_eps, outs[0], outs[1], ow, ob, H, **w8_o)
                 past_key_values.update(layer_idx=self.layer_idx, key_states=None, value_states=None, conv_state=outs,
                                        recurrent_state=layer.recurrent_state,
                                        cache_kwargs={"op": "set", "delta_len": T, "cache_position": cache_position})
@@ -291,7 +315,7 @@ class GatedDeltaNet(nn.Module):
             past_key_values.update(layer_idx=self.layer_idx, key_states=None, value_states=None, conv_state=outs,
                                    recurrent_state=layer.recurrent_state,
                                    cache_kwargs={"op": "set", "delta_len": T, "cache_position": cache_position})
-            return ops.linear(o, self.o_proj.weight, self.o_proj.bias), None
+            return ops.linear(o, self.o_proj.weight, self.o_proj.bias, **w8_o), None
         convs = (self.q_conv1d.weight, self.k_conv1d.weight, self.v_conv1d.weight)
         if mode == "chunk" and Dk == Dq and K == 128 and V == 256 and convs[0].shape[-1] == 4:
             # convs + gates inside the chunk kernel's pre-pass: q / k / v / g / beta never reach HBM, one launch less
@@ -310,7 +334,7 @@ class GatedDeltaNet(nn.Module):
                                    recurrent_state=layer.recurrent_state,
                                    cache_kwargs={"op": "set", "delta_len": T, "cache_position": cache_position})
         o = ops.rmsnorm_swish_gate_strided(o, proj[..., cg:], ld, w, self.norm_eps)
-        return ops.linear(o.reshape(B, T, -1), self.o_proj.weight, self.o_proj.bias), None
+        return ops.linear(o.reshape(B, T, -1), self.o_proj.weight, self.o_proj.bias, **w8_o), None
 
     def forward(self, hidden_states: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
                 past_key_values=None, cache_position: Optional[torch.LongTensor] = None, **kwargs):

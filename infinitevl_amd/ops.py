@@ -811,7 +811,7 @@ def gdn_decode_split(proj: torch.Tensor, cols, conv_weights, conv_states, A_log3
 
 def gdn_out_linear(o_raw: torch.Tensor, proj: torch.Tensor, col_g: int, col_q: int, col_k: int, norm_weight: torch.Tensor, eps: float,
                    conv_state_q: torch.Tensor, conv_state_k: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor],
-                   H: int) -> torch.Tensor:
+                   H: int, w8: Optional["PackedWeight"] = None) -> torch.Tensor:
     """o_proj(o_norm(o_raw, gate)) for a decode step, one launch: the gated RMSNorm runs in the prologue of the weight stream, and
     the launch shifts the q / k conv states (the second half of gdn_decode_split's state update).  proj [B,1,ld] is the step's
     fused projection (gate columns at col_g, raw q / k columns at col_q / col_k).  2 <= H <= 16 heads (the kernel refuses others)."""
@@ -822,6 +822,14 @@ def gdn_out_linear(o_raw: torch.Tensor, proj: torch.Tensor, col_g: int, col_q: i
     assert T == 1 and o_raw.is_contiguous() and weight.is_contiguous() and weight.dtype == torch.bfloat16
     y = torch.empty(B, 1, N, dtype=torch.bfloat16, device=o_raw.device)
     gate = proj.view(B, ld)[:, col_g:]
+    if w8 is not None:                                   # the e4m3 twin on the packed copy of `weight` (see `linear`)
+        w8.check(weight)
+        _lib.check(_lib.load().ivl_gdn_out_linear_small_m_w8_fwd(
+            _p(o_raw), ctypes.c_void_p(gate.data_ptr()), ld, _p(norm_weight), float(eps), H, _p(proj), ld, col_q, col_k,
+            _p(conv_state_q), _p(conv_state_k), _p(w8.codes), _p(w8.scale), _p(bias) if bias is not None else None, _p(y), B, N, K,
+            _stream(o_raw)))
+        W8_CALLS["gdn_out_linear"] += 1
+        return y
     _lib.check(_lib.load().ivl_gdn_out_linear_small_m_fwd(
         _p(o_raw), ctypes.c_void_p(gate.data_ptr()), ld, _p(norm_weight), float(eps), H, _p(proj), ld, col_q, col_k,
         _p(conv_state_q), _p(conv_state_k), _p(weight), _p(bias) if bias is not None else None, _p(y), B, N, K, _stream(o_raw)))
@@ -916,8 +924,86 @@ class PreNorm:
         return self._y
 
 
-def _prenorm_linear(pn: "PreNorm", weight: torch.Tensor, bias: Optional[torch.Tensor], glu: bool) -> Optional[torch.Tensor]:
-    """The fused launch when it applies (decode step, bf16, K <= 4096), else None."""
+# ---- weight-only e4m3 for the decode step's weight streams ------------------------------------------------------------
+E4M3_MAX = 448.0
+W8_EXP_LIMIT = 100
+# calls that took a w8 entry point, per entry point (tests read it to know which kernel a call ran on)
+W8_CALLS = {"linear": 0, "linear_swiglu": 0, "norm_linear": 0, "gdn_out_linear": 0}
+
+
+def quantize_rows_e4m3(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """bf16 [N,K] -> (codes uint8 [N,K], exp int32 [N], scale fp32 [N]): per row the SMALLEST power of two 2^e with
+    max|w[n,:]| <= 448 * 2^e (e = 0 for a zero row; |e| > 100 and non-finite weights are refused) and codes =
+    RNE_e4m3fn(w / 2^e), OCP e4m3fn.  The exponent comes from frexp (amax = m 2^x, 0.5 <= m < 1: e = x - 9 up to m = 0.875 =
+    448 / 512, else x - 8), never from a floating log2; w / 2^e is exact and at most 448, so the cast meets neither its
+    saturation nor a NaN code.  Pure torch: CPU and GPU tensors."""
+    if w.dim() != 2 or w.dtype != torch.bfloat16:
+        raise ValueError(f"quantize_rows_e4m3: a bf16 [N,K] weight is expected; got {w.dtype} {tuple(w.shape)}")
+    wf = w.detach().float()
+    if not bool(torch.isfinite(wf).all()):
+        raise ValueError("quantize_rows_e4m3: non-finite weights")
+    amax = wf.abs().amax(1)
+    m, x = torch.frexp(amax)
+    exp = torch.where(m <= 0.875, x - 9, x - 8)
+    exp = torch.where(amax == 0, torch.zeros_like(exp), exp).to(torch.int32)
+    if bool((exp.abs() > W8_EXP_LIMIT).any()):
+        raise ValueError(f"quantize_rows_e4m3: a row scale 2^e with |e| > {W8_EXP_LIMIT}")
+    scale = torch.ldexp(torch.ones_like(amax), exp)
+    codes = (wf / scale[:, None]).to(torch.float8_e4m3fn).view(torch.uint8)
+    return codes, exp, scale
+
+
+def dequantize_rows_e4m3(codes: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """W' = float(code) * scale[n] as bf16: exact for a power-of-two scale (an e4m3 value has 4 significant bits)."""
+    return (codes.view(torch.float8_e4m3fn).float() * scale[:, None].float()).to(torch.bfloat16)
+
+
+class PackedWeight:
+    """The e4m3 copy of a bf16 weight that HOLDS W' = dequantize(codes, scale): codes uint8 [N,K], scale fp32 [N] (powers of two),
+    and what identifies the bf16 weight it was made from -- its data pointer and `_version` (and those of `also`: parameters that
+    are views of a fused weight carry version counters of their own, and load_state_dict writes through THEM).  A packed copy whose
+    weight has moved or been written since is stale: `check` raises, nothing falls back silently."""
+
+    __slots__ = ("codes", "scale", "exp", "ptr", "version", "_watch")
+
+    def __init__(self, weight: torch.Tensor, codes: torch.Tensor, scale: torch.Tensor, exp: Optional[torch.Tensor] = None, also=()):
+        self.codes, self.scale, self.exp = codes.contiguous(), scale.to(torch.float32).contiguous(), exp
+        self.ptr, self.version = weight.data_ptr(), weight._version
+        self._watch = [(t, t.data_ptr(), t._version) for t in also]
+
+    @classmethod
+    def of(cls, weight: torch.Tensor, also=()) -> "PackedWeight":
+        """Quantise `weight` (bf16 [N,K], contiguous), write W' back IN PLACE (views and data pointers keep holding) and pack it."""
+        codes, exp, scale = quantize_rows_e4m3(weight)
+        with torch.no_grad():
+            weight.copy_(dequantize_rows_e4m3(codes, scale))
+        return cls(weight, codes, scale, exp, also)
+
+    def stale(self, weight: torch.Tensor) -> bool:
+        return (weight.data_ptr() != self.ptr or weight._version != self.version
+                or any(t.data_ptr() != p or t._version != v for t, p, v in self._watch))
+
+    def check(self, weight: torch.Tensor) -> "PackedWeight":
+        if self.stale(weight):
+            raise RuntimeError("PackedWeight is stale: the bf16 weight it was quantised from has moved or been written since "
+                               "(load_state_dict, an in-place update); call quantize_weights_() again")
+        if tuple(self.codes.shape) != tuple(weight.shape) or self.codes.device != weight.device:
+            raise RuntimeError(f"PackedWeight {tuple(self.codes.shape)} on {self.codes.device} does not belong to a weight "
+                               f"{tuple(weight.shape)} on {weight.device}")
+        return self
+
+
+def w8_kwargs(packed: Optional[PackedWeight], on: bool) -> dict:
+    """The `w8=` argument of linear / linear_swiglu / gdn_out_linear for a module: nothing at all unless a packed copy is in use, so
+    a model that never called quantize_weights_ makes the calls it always made."""
+    return {"w8": packed} if on and packed is not None else {}
+
+
+def _prenorm_linear(pn: "PreNorm", weight: torch.Tensor, bias: Optional[torch.Tensor], glu: bool,
+                    w8: Optional[PackedWeight] = None) -> Optional[torch.Tensor]:
+    """The fused launch when it applies (decode step, bf16, K <= 4096), else None.  w8: the e4m3 twin on the packed copy."""
+    if w8 is not None:
+        w8.check(weight)
     K = weight.shape[-1]
     rows = pn.numel() // K if K else 0
     if not (pn.is_cuda and 1 <= rows <= 4 and pn.dtype == torch.bfloat16 and weight.dtype == torch.bfloat16 and weight.dim() == 2
@@ -926,6 +1012,13 @@ def _prenorm_linear(pn: "PreNorm", weight: torch.Tensor, bias: Optional[torch.Te
         return None
     N = weight.shape[0] // 2 if glu else weight.shape[0]
     y = torch.empty(*pn.shape[:-1], N, dtype=torch.bfloat16, device=pn.device)
+    if w8 is not None:
+        _lib.check(_lib.load().ivl_norm_linear_small_m_w8_fwd(
+            _p(pn.x), _p(pn.residual), _p(pn.weight), pn.eps, _p(pn.h) if pn.residual is not None else None,
+            _p(w8.codes), _p(w8.scale), _p(bias) if bias is not None else None, _p(y), rows, N, K, 1 if glu else 0, _stream(pn.x)))
+        W8_CALLS["norm_linear"] += 1
+        pn.done = True
+        return y
     _lib.check(_lib.load().ivl_norm_linear_small_m_fwd(
         _p(pn.x), _p(pn.residual), _p(pn.weight), pn.eps, _p(pn.h) if pn.residual is not None else None,
         _p(weight), _p(bias) if bias is not None else None, _p(y), rows, N, K, 1 if glu else 0, _stream(pn.x)))
@@ -961,12 +1054,15 @@ def _linear_swiglu_m256(x: torch.Tensor, w_gate_up: torch.Tensor, rows: int, I: 
     return y
 
 
-def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, w8: Optional[PackedWeight] = None) -> torch.Tensor:
     """nn.Linear forward.  A single-token decode step (<= 4 rows) is a pure weight stream and goes through
     ivl_linear_small_m_fwd; longer calls are stock library GEMMs (hipBLASLt / rocBLAS through torch), which
-    SURVEY.md 8(d) keeps outside the hot path."""
+    SURVEY.md 8(d) keeps outside the hot path.  w8: the packed e4m3 copy of `weight` (which then holds W'): the weight stream
+    reads it in place of the bf16 weight -- the same bits, half the bytes; every other path reads `weight` as ever."""
+    if w8 is not None:
+        w8.check(weight)
     if isinstance(x, PreNorm):
-        y = _prenorm_linear(x, weight, bias, False)
+        y = _prenorm_linear(x, weight, bias, False, w8)
         if y is not None:
             return y
         x = x.materialize()
@@ -978,18 +1074,25 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] =
         xc = x if x.is_contiguous() else x.contiguous()
         N = weight.shape[0]
         y = torch.empty(*x.shape[:-1], N, dtype=torch.bfloat16, device=x.device)
+        if w8 is not None:
+            _lib.check(_lib.load().ivl_linear_small_m_w8_fwd(_p(xc), _p(w8.codes), _p(w8.scale), _p(bias) if bias is not None else None,
+                                                             _p(y), rows, N, K, _stream(x)))
+            W8_CALLS["linear"] += 1
+            return y
         _lib.check(_lib.load().ivl_linear_small_m_fwd(_p(xc), _p(weight), _p(bias) if bias is not None else None,
                                                       _p(y), rows, N, K, _stream(x)))
         return y
     return torch.nn.functional.linear(x, weight, bias)
 
 
-def linear_swiglu(x: torch.Tensor, w_gate_up: torch.Tensor) -> torch.Tensor:
+def linear_swiglu(x: torch.Tensor, w_gate_up: torch.Tensor, w8: Optional[PackedWeight] = None) -> torch.Tensor:
     """silu(gate_proj(x)) * up_proj(x) with the fused gate|up weight [2I, K] (std:945).  Decode steps (<= 4 rows)
     apply the gate in the epilogue of the weight-stream kernel, and so does the 256-row kernel of a prefill chunk
-    (ivl_linear_m256_fwd); other calls are a library GEMM + silu_mul."""
+    (ivl_linear_m256_fwd); other calls are a library GEMM + silu_mul.  w8: as in `linear`."""
+    if w8 is not None:
+        w8.check(w_gate_up)
     if isinstance(x, PreNorm):
-        y = _prenorm_linear(x, w_gate_up, None, True)
+        y = _prenorm_linear(x, w_gate_up, None, True, w8)
         if y is not None:
             return y
         x = x.materialize()
@@ -1000,6 +1103,11 @@ def linear_swiglu(x: torch.Tensor, w_gate_up: torch.Tensor) -> torch.Tensor:
             and w_gate_up.is_contiguous() and K % 8 == 0):
         xc = x if x.is_contiguous() else x.contiguous()
         y = torch.empty(*x.shape[:-1], I, dtype=torch.bfloat16, device=x.device)
+        if w8 is not None:
+            _lib.check(_lib.load().ivl_linear_swiglu_small_m_w8_fwd(_p(xc), _p(w8.codes), _p(w8.scale), None, _p(y), rows, I, K,
+                                                                    _stream(x)))
+            W8_CALLS["linear_swiglu"] += 1
+            return y
         _lib.check(_lib.load().ivl_linear_swiglu_small_m_fwd(_p(xc), _p(w_gate_up), None, _p(y), rows, I, K, _stream(x)))
         return y
     if _m256_swiglu_applies(x, w_gate_up, rows, I, K):

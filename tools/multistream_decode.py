@@ -59,6 +59,17 @@ copy cancels in the differences.  Then the operator alone on 4 rows of the model
 C - A are reported beside the 2 % of the greedy step the sampling launch is granted as a whole.
 
     python tools/multistream_decode.py --grammar [--out profiles/grammar_decode.json]
+
+--w8: weight-only e4m3 in the decode step (InfiniteVLTextStack.quantize_weights_(lm_head=True)).  A: the captured greedy step on
+the bf16 weights (use_packed_weights(False): the bf16 kernels, whose code does not depend on the values); B: the same step
+streaming the packed e4m3 copies, timed A B A B per slot count, median of --rounds rounds.  Then every weight stream of a decode
+token alone, bf16 against w8 through the entry points the model reaches them by, at M = 1 and M = 4: us per call and achieved
+GB/s of weight bytes, cycling through enough copies of the weight (>= 1 GB of bf16) that no call finds its weight in a cache,
+the calls of a leg captured in one graph.
+For information: how far the logits of the rounded random-init model sit from the unrounded one's over 16 teacher-forced decode
+steps (max and rms of the difference beside the rms of the logits).  Nothing is asserted.
+
+    python tools/multistream_decode.py --w8 --slots 1,4 [--out profiles/w8_decode.json]
 """
 import argparse
 import json
@@ -84,6 +95,7 @@ def main():
     ap.add_argument("--fork", action="store_true", help="time the slot fork against the copy_ loop and a re-admission (see above)")
     ap.add_argument("--beam", action="store_true", help="time the beam search step and the row gather (see above)")
     ap.add_argument("--grammar", action="store_true", help="time the constrained step against the scored one (see above)")
+    ap.add_argument("--w8", action="store_true", help="time the step on packed e4m3 weights against the bf16 step (see above)")
     args = ap.parse_args()
     import torch
     from infinitevl_amd.cache import MultiStreamCache
@@ -122,6 +134,8 @@ def main():
         return beam_legs(args, torch, model, cfg, prompts, dev)
     if args.grammar:
         return grammar_legs(args, torch, model, cfg, prompts, dev)
+    if args.w8:
+        return w8_legs(args, torch, model, cfg, prompts, dev)
 
     # reference: one stream on the existing B = 1 graphed decode step
     c1 = model.allocate_inference_cache(1)
@@ -518,6 +532,147 @@ def grammar_legs(args, torch, model, cfg, prompts, dev):
             smp.sample(lg, tok)
         op[f"S{n}_{name}_us"] = round(1000 * timed(fn, 200), 2)
     res["operator_V%d" % V] = op
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+def w8_operator_legs(args, torch, cfg, dev, timed):
+    """every weight stream of a decode token alone: {name: {M: {bf16_us, w8_us, bf16_GBs, w8_GBs}}}"""
+    from infinitevl_amd import _lib, ops
+    lib = _lib.load()
+    hd, I, V = cfg.hidden_size, cfg.intermediate_size, cfg.vocab_size
+    # (name, weight rows, K, form): the forms the model reaches them by in a decode step
+    shapes = [("qkv", 2560, hd, "norm"), ("gdn_in", 12320, hd, "norm"), ("attn_o_proj", hd, 2048, "plain"),
+              ("gdn_o_proj", hd, 4096, "plain"), ("gate_up", 2 * I, hd, "norm_glu"), ("down", hd, I, "plain"),
+              ("lm_head", V, hd, "plain")]
+    gen = torch.Generator(device=dev).manual_seed(2)
+    out = {}
+    for name, R, K, form in shapes:
+        copies = max(2, -(-(1 << 30) // (R * K * 2)))
+        w = (torch.randn(R, K, generator=gen, device=dev) * 0.02).to(torch.bfloat16)
+        codes, _, scale = ops.quantize_rows_e4m3(w)
+        wb = ops.dequantize_rows_e4m3(codes, scale)[None].expand(copies, R, K).contiguous()
+        wq = codes[None].expand(copies, R, K).contiguous()
+        del w
+        N = R // 2 if form == "norm_glu" else R
+        nw = torch.ones(K, dtype=torch.bfloat16, device=dev)
+        row = {"weight_rows": R, "K": K, "form": form, "copies": copies}
+        for M in (1, 4):
+            x = (torch.randn(M, K, generator=gen, device=dev) * 0.5).to(torch.bfloat16)
+            y = torch.empty(M, N, dtype=torch.bfloat16, device=dev)
+            state = {"i": 0}
+
+            def call(packed):
+                i = state["i"] = (state["i"] + 1) % copies
+                st = ops._stream(x)
+                wp = ops._p(wq[i]) if packed else ops._p(wb[i])
+                if form == "plain":
+                    rc = (lib.ivl_linear_small_m_w8_fwd(ops._p(x), wp, ops._p(scale), None, ops._p(y), M, N, K, st) if packed else
+                          lib.ivl_linear_small_m_fwd(ops._p(x), wp, None, ops._p(y), M, N, K, st))
+                else:
+                    glu = 1 if form == "norm_glu" else 0
+                    rc = (lib.ivl_norm_linear_small_m_w8_fwd(ops._p(x), None, ops._p(nw), 1e-6, None, wp, ops._p(scale), None, ops._p(y),
+                                                             M, N, K, glu, st) if packed else
+                          lib.ivl_norm_linear_small_m_fwd(ops._p(x), None, ops._p(nw), 1e-6, None, wp, None, ops._p(y), M, N, K, glu, st))
+                _lib.check(rc)
+
+            # `reps` calls in ONE captured graph per leg: from Python a call costs more than the small streams take
+            reps = max(8, min(128, 2 * copies))
+            graphs = {}
+            for packed in (False, True):
+                call(packed)
+                torch.cuda.synchronize()
+                graphs[packed] = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graphs[packed]):
+                    for _ in range(reps):
+                        call(packed)
+            t = {False: [], True: []}
+            for _ in range(args.rounds):                        # A B A B
+                for packed in (False, True, False, True):
+                    t[packed].append(timed(graphs[packed].replay, 4) / reps)
+            a, b = statistics.median(t[False]), statistics.median(t[True])
+            del graphs
+            row[f"M{M}"] = {"bf16_us": round(1000 * a, 2), "w8_us": round(1000 * b, 2), "w8_over_bf16": round(b / a, 3),
+                            "bf16_GBs": round(R * K * 2 / (a * 1e-3) / 1e9, 1), "w8_GBs": round(R * K / (b * 1e-3) / 1e9, 1)}
+        out[name] = row
+        print(name, row, file=sys.stderr, flush=True)
+        del wb, wq
+    return out
+
+
+def w8_legs(args, torch, model, cfg, prompts, dev):
+    from infinitevl_amd.cache import MultiStreamCache
+    from infinitevl_amd.harness import GraphedMultiStreamDecode
+    stream = torch.cuda.current_stream()
+
+    def timed(fn, n):
+        for _ in range(4):
+            fn()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        for _ in range(n):
+            fn()
+        e1.record(stream)
+        e1.synchronize()
+        return e0.elapsed_time(e1) / n
+
+    def forced_logits(tokens=None):
+        """16 eager decode steps behind a 512-token prompt; tokens: the ones to feed (None: greedy) -> (tokens, logits fp32)"""
+        with torch.no_grad():
+            cache = model.allocate_inference_cache(1)
+            _, lg = model(inputs_embeds=prompts[0][:, :512], past_key_values=cache)
+            toks, out = [], []
+            tok = lg[:, -1].argmax(-1, keepdim=True)
+            for i in range(16):
+                if tokens is not None:
+                    tok = tokens[i]
+                toks.append(tok)
+                _, lg = model(input_ids=tok, past_key_values=cache)
+                out.append(lg[0, -1].float())
+                tok = lg[:, -1].argmax(-1, keepdim=True)
+        return toks, torch.stack(out)
+
+    toks, ref = forced_logits()
+    model.quantize_weights_(lm_head=True)
+    _, got = forced_logits(toks)
+    diff = got - ref
+    slots = [int(s) for s in args.slots.split(",")]
+    res = {"tool": "multistream_decode --w8", "layers": cfg.num_hidden_layers, "window": 4096, "steps": args.steps, "rounds": args.rounds,
+           "quantised": "q|k|v, attention o_proj, GDN in-projection, GDN o_proj, gate|up, down_proj, lm_head",
+           "bar": "none asserted",
+           "rounded_vs_unrounded_logits_16_steps": {"max_abs_diff": round(float(diff.abs().max()), 4),
+                                                    "rms_diff": round(float(diff.pow(2).mean().sqrt()), 5),
+                                                    "rms_logits": round(float(ref.pow(2).mean().sqrt()), 5),
+                                                    "same_argmax_steps": int((got.argmax(-1) == ref.argmax(-1)).sum())}}
+    for n in slots:
+        decs = {}
+        for name, on in (("bf16", False), ("w8", True)):
+            model.use_packed_weights(on)
+            cache = MultiStreamCache(config=cfg, n_slots=n, device=dev, dtype=torch.bfloat16)
+            dec = GraphedMultiStreamDecode(model, cache)
+            for s in range(n):
+                dec.admit(s, prompts[s])
+            dec.capture()
+            decs[name] = (dec, on)
+        times = {k: [] for k in decs}
+        for _ in range(args.rounds):                            # A B A B
+            for name in ("bf16", "w8", "bf16", "w8"):
+                dec, on = decs[name]
+                model.use_packed_weights(on)                    # (a host flag: the step would recapture on a mismatch)
+                times[name].append(timed(dec.step, args.steps))
+        a, b = statistics.median(times["bf16"]), statistics.median(times["w8"])
+        res[f"slots{n}"] = {"bf16_ms_per_step": round(a, 4), "w8_ms_per_step": round(b, 4), "w8_over_bf16": round(b / a, 4),
+                            "delta_us": round(1000 * (b - a), 1),
+                            "bf16_spread_ms": [round(min(times["bf16"]), 4), round(max(times["bf16"]), 4)],
+                            "w8_spread_ms": [round(min(times["w8"]), 4), round(max(times["w8"]), 4)]}
+        print(f"slots{n}: bf16 {a:.4f} w8 {b:.4f} ms", file=sys.stderr, flush=True)
+        del decs
+    model.use_packed_weights(True)
+    res["operators"] = w8_operator_legs(args, torch, cfg, dev, timed)
     line = json.dumps(res)
     print(line)
     if args.out:
