@@ -424,6 +424,42 @@ IVL_API int ivl_gdn_out_linear_small_m_w8_fwd(const void* o_raw, const void* gat
                                       void* conv_state_q, void* conv_state_k, const void* wq, const float* scale,
                                       const void* bias, void* y, int M, int N, int K, void* stream);
 
+/* WEIGHT-ONLY MXFP4: the 4-bit twins of the four decode projections -- the argument lists of the *_w8 twins, with
+ *   wq   uint8 [N, Kp/2] (GLU: [2I, Kp/2]), 16-byte aligned: OCP microscaling FP4 codes (e2m1: sign, 2 exponent bits, 1 mantissa
+ *        bit -- the magnitudes 0, .5, 1, 1.5, 2, 3, 4, 6 --, two per byte, the element of the lower index in the LOW nibble),
+ *   sq   uint8 [N, Kp/32] (GLU: [2I, Kp/32]), 4-byte aligned: one e8m0 scale byte b per block of 32 consecutive K elements,
+ *        the scale 2^(b - 127),
+ * both in the SHUFFLED layout the kernels read (below), Kp = 2048 ceil(K / 2048).  K % 32 == 0.
+ *   W'[n,k] = e2m1(code[n,k]) * 2^(b[n, k/32] - 127)        (2 significant bits: exact in bf16)
+ *   y[m,n]  = bf16(acc[m,n] + bias[n]),   acc[m,n] = the fp32 sum of W'[n,k] * x[m,k] in the bf16 kernels' ORDER (see the w8 twins: one
+ *             template over the weight element): v_cvt_scalef32_pk_f32_fp4 decodes two codes and applies the block scale, exactly.
+ * THE CONTRACT: each entry point equals its bf16 twin called on W' BIT FOR BIT -- y, h_out and the conv states.  There is no per-row
+ * scale and no scaled epilogue: the block scale is part of the weight.
+ * THE LAYOUT (ops.mxfp4_shuffle / mxfp4_unshuffle convert from / to plain row-major OCP, where byte j of a row holds elements 2j, 2j + 1
+ * and scale byte i belongs to elements 32i .. 32i + 31).  A CHUNK is 8 consecutive K elements = 4 bytes; TILE t of a row is the chunks
+ * [256t, 256t + 256) = one trip of the weight loop of a wave.  In a row of wq (Kp/2 bytes) the chunk 256t + l + 64u (l in 0..63, u in
+ * 0..3) sits at byte 1024t + 16l + 4u: lane l fetches the four pieces of a trip with ONE 16-byte load, in the order it adds them.  In a
+ * row of sq (Kp/32 bytes) the scale of block 64t + (l >> 2) + 16u -- the block of that chunk -- sits at byte 64t + 4(l >> 2) + u: one
+ * dword per lane holds the scales of its four pieces.  Chunks and blocks past K are padding: code 0x0, scale byte 127; they meet
+ * x = 0 like every piece past the row end.  A scale byte is used as the fp32 bit pattern b << 23: b = 0 and b = 255 are not expected
+ * (ops.quantize_rows_mxfp4 keeps |b - 127| <= 100).
+ * The exponent rule is the producer's business: ops.quantize_rows_mxfp4 takes the SMALLEST e with amax(block) <= 6 * 2^e, which never
+ * saturates; the OCP reference rule, e = floor(log2 amax) - 2, is one smaller where amax > 6 * 2^e and then clamps such elements to +-6.
+ * Codes made by either rule (any e8m0 in 1..254) are decoded the same way here.
+ * Ranges and refusals are those of the twins, plus K % 32 == 0, wq 16-byte and sq 4-byte aligned (IVL_ERR_INVALID_ARG); NULL sq:
+ * IVL_ERR_INVALID_ARG; every check runs before anything is launched. */
+IVL_API int ivl_linear_small_m_w4_fwd(const void* x, const void* wq, const void* sq, const void* bias, void* y, int M, int N,
+                              int K, void* stream);
+IVL_API int ivl_linear_swiglu_small_m_w4_fwd(const void* x, const void* wq_gate_up, const void* sq, const void* bias, void* y,
+                                     int M, int I, int K, void* stream);
+IVL_API int ivl_norm_linear_small_m_w4_fwd(const void* x, const void* residual, const void* norm_weight, float eps, void* h_out,
+                                   const void* wq, const void* sq, const void* bias, void* y, int M, int N, int K, int glu,
+                                   void* stream);
+IVL_API int ivl_gdn_out_linear_small_m_w4_fwd(const void* o_raw, const void* gate, int64_t gate_ld, const void* norm_weight,
+                                      float eps, int H, const void* proj, int64_t proj_ld, int col_q, int col_k,
+                                      void* conv_state_q, void* conv_state_k, const void* wq, const void* sq,
+                                      const void* bias, void* y, int M, int N, int K, void* stream);
+
 /* nn.Linear for the wide projections of a prefill chunk of up to 256 rows: y[M,N] = bf16(x[M,K] W[N,K]^T + bias[N]), or with
  * glu != 0 the SwiGLU MLP head on the fused gate|up weight [2N,K] (N = I):
  *   y[M,I] = bf16( bf16(silu(bf16(x Wg^T + bg))) * bf16(x Wu^T + bu) ),  Wg = w[:I], Wu = w[I:], bias [2I] or NULL

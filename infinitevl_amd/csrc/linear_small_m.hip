@@ -21,6 +21,10 @@
 // WEIGHT-ONLY E4M3 (the *_w8 entry points): the same kernels instantiated on 1-byte OCP e4m3fn codes with one fp32 scale
 // per weight row -- half the bytes of the stream, the x side untouched, and with power-of-two scales the bf16 kernels' output on the
 // dequantised weight bit for bit.
+//
+// WEIGHT-ONLY MXFP4 (the *_w4 entry points): the same kernels on OCP e2m1 codes, two per byte, with one e8m0 power-of-two
+// scale per 32 weights, in a pre-shuffled layout (include/ivl_hip.h) that hands a lane the four pieces of a loop trip in one 16-byte
+// load -- a quarter of the bytes, and again the bf16 kernels' output on the dequantised weight bit for bit.
 #include "ivl_rowwise.h"
 
 namespace ivl {
@@ -52,10 +56,14 @@ __device__ __forceinline__ float dot8_e4m3(u32x2 a, u32x4 b, float acc) {
 // the kernels', so the e4m3 stream has the bf16 stream's order by construction.  Both keep LSM_U pieces per row in flight: an e4m3
 // piece is half the bytes, but 8 (and 16) of them per row measured SLOWER at M = 1 than 4 (lm_head 73 and 123 us against 47, gate|up
 // 14.5 against 12.3: DESIGN 4.13) -- the registers they take cost more occupancy than the bytes in flight buy.
+//
+// WMxfp4 (the *_w4 entry points) replaces the LSM_U piece loads of a trip by ONE 16-byte load of codes and one 4-byte load
+// of block scales per weight row (PACKED: the shuffled layout of include/ivl_hip.h puts a lane's four pieces of a trip side by side);
+// the block scale is part of the weight, so there is no scaled epilogue.
 struct WBf16 {                                     // bf16 [N,K]: 16-byte pieces
   using piece = u32x4;
   using arg = const bf16_t* __restrict__;
-  static constexpr bool SCALED = false;
+  static constexpr bool SCALED = false, PACKED = false;
   static bool null(arg w) { return w == nullptr; }
   static __device__ __forceinline__ const piece* row(arg w, size_t r, int K) { return (const piece*)(w + r * K); }
   static __device__ __forceinline__ float scale(arg, int) { return 1.f; }
@@ -65,11 +73,47 @@ struct W8Arg { const unsigned char* q; const float* scale; };
 struct WE4m3 {                                     // e4m3 codes [N,K] + one fp32 scale per row: 8-byte pieces
   using piece = u32x2;
   using arg = W8Arg;
-  static constexpr bool SCALED = true;
+  static constexpr bool SCALED = true, PACKED = false;
   static bool null(arg w) { return w.q == nullptr || w.scale == nullptr; }
   static __device__ __forceinline__ const piece* row(arg w, size_t r, int K) { return (const piece*)(w.q + r * K); }
   static __device__ __forceinline__ float scale(arg w, int r) { return w.scale[r]; }
   static __device__ __forceinline__ float dot(piece a, u32x4 b, float acc) { return dot8_e4m3(a, b, acc); }
+};
+struct W4Arg { const unsigned char* q; const unsigned char* s; };
+struct WMxfp4 {                                    // e2m1 codes, two per byte, + one e8m0 scale per 32 weights, shuffled: 4-byte pieces
+  using piece = unsigned int;
+  using arg = W4Arg;
+  static constexpr bool SCALED = false, PACKED = true;
+  static bool null(arg w) { return w.q == nullptr || w.s == nullptr; }
+  static __host__ __device__ __forceinline__ int kp(int K) { return (K + 2047) & ~2047; }      // a row is whole tiles of 2048 weights
+  static __device__ __forceinline__ const piece* row(arg w, size_t r, int K) { return (const piece*)(w.q + r * (size_t)(kp(K) >> 1)); }
+  static __device__ __forceinline__ const unsigned int* srow(arg w, size_t r, int K) {
+    return (const unsigned int*)(w.s + r * (size_t)(kp(K) >> 5));
+  }
+  static __device__ __forceinline__ float scale(arg, int) { return 1.f; }
+  // trip t of a row (chunks 256t + lane + 64u): the lane's four pieces are dwords 4 (64t + lane) .. + 3 of the row, their four scale
+  // bytes dword 16t + (lane >> 2) of the scale row
+  static __device__ __forceinline__ u32x4 load_codes(const piece* row, int t, int lane) {
+    return __builtin_nontemporal_load((const u32x4*)row + t * 64 + lane);
+  }
+  static __device__ __forceinline__ unsigned int load_scales(const unsigned int* srow, int t, int lane) {
+    return __builtin_nontemporal_load(srow + t * 16 + (lane >> 2));
+  }
+  // piece a (element 2j in the low nibble of byte j) with the e8m0 byte sb: v_cvt_scalef32_pk_f32_fp4 decodes two codes and multiplies
+  // by 2^(sb - 127), exactly; the products and their order are dot8's
+  static __device__ __forceinline__ void decode(piece a, unsigned int sb, float (&w)[8]) {
+    const float s = __builtin_bit_cast(float, sb << 23);
+    const auto w01 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(a, s, 0), w23 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(a, s, 1);
+    const auto w45 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(a, s, 2), w67 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(a, s, 3);
+    w[0] = w01[0]; w[1] = w01[1]; w[2] = w23[0]; w[3] = w23[1]; w[4] = w45[0]; w[5] = w45[1]; w[6] = w67[0]; w[7] = w67[1];
+  }
+  static __device__ __forceinline__ float dot(const float (&w)[8], u32x4 b, float acc) {
+    acc = fmaf(w[0], bflo(b.x), acc); acc = fmaf(w[1], bfhi(b.x), acc);
+    acc = fmaf(w[2], bflo(b.y), acc); acc = fmaf(w[3], bfhi(b.y), acc);
+    acc = fmaf(w[4], bflo(b.z), acc); acc = fmaf(w[5], bfhi(b.z), acc);
+    acc = fmaf(w[6], bflo(b.w), acc); acc = fmaf(w[7], bfhi(b.w), acc);
+    return acc;
+  }
 };
 
 struct NormArgs {
@@ -103,6 +147,11 @@ __global__ __launch_bounds__(256, (NORM && M == 1) ? 3 : 1) void linear_small_m_
     const int rr = min(row0 + (r % RPW), N - 1) + (r >= RPW ? N : 0);      // GLU: rows [RPW, 2RPW) are the "up" rows
     wrow[r] = WT::row(w, (size_t)rr, K);
     if constexpr (WT::SCALED) wscale[r] = WT::scale(w, __builtin_amdgcn_readfirstlane(rr));      // (wave-uniform: SGPRs)
+  }
+  const unsigned int* wsrow[WT::PACKED ? NR : 1];  // (mxfp4: the rows' block scales)
+  if constexpr (WT::PACKED) {
+#pragma unroll
+    for (int r = 0; r < NR; ++r) wsrow[r] = WT::srow(w, (size_t)(min(row0 + (r % RPW), N - 1) + (r >= RPW ? N : 0)), K);
   }
   float acc[NR][M];
 #pragma unroll
@@ -170,14 +219,48 @@ __global__ __launch_bounds__(256, (NORM && M == 1) ? 3 : 1) void linear_small_m_
     __syncthreads();
   };
   bool first = true;
+  // mxfp4: a trip is 20 bytes per lane and row, so the plain and GLU forms of M >= 2 keep TWO trips in flight -- the next trip's codes
+  // and scales are requested before this trip's are used.  Measured: at M = 4 down K = 11008 19.6 -> 14.7 us, GDN o_proj
+  // 7.6 -> 6.3, lm_head 93 -> 84 (its one trip is requested ahead of the x rows); at M = 1 nothing gains and the 4-rows-per-wave
+  // instance goes from 71 to 131 VGPRs (lm_head 38 -> 44 us).  Not the NORM form: its K <= 4096 is two trips at most, and its
+  // M = 1 instances (capped at 168 VGPRs) would spill.
+  constexpr bool AHEAD = WT::PACKED && !NORM && M > 1;
+  u32x4 qnext[WT::PACKED ? NR : 1];
+  unsigned int snext[WT::PACKED ? NR : 1];
+  auto load_trip = [&](int t) {                    // (a padded row holds whole trips: no clamp)
+    if constexpr (WT::PACKED) {
+#pragma unroll
+      for (int r = 0; r < NR; ++r) {
+        qnext[r] = WT::load_codes(wrow[r], t, lane);
+        snext[r] = WT::load_scales(wsrow[r], t, lane);
+      }
+    }
+  };
+  if constexpr (AHEAD) {
+    if (lane < nchunk) load_trip(0);
+  }
   for (int c0 = lane; c0 < nchunk; c0 += 64 * LSM_U) {
     piece_t wv[LSM_U][NR];
     u32x4 xv[LSM_U][M];
+    unsigned int wsb[WT::PACKED ? NR : 1];         // (mxfp4: byte u = the block scale of piece u)
+    if constexpr (WT::PACKED) {
+      static_assert(LSM_U == 4, "a 16-byte load holds the four pieces of a trip");
+      if constexpr (!AHEAD) load_trip(c0 >> 8);    // (c0 = lane + 256 t)
 #pragma unroll
-    for (int u = 0; u < LSM_U; ++u) {
-      const int cc = min(c0 + 64 * u, nchunk - 1);
+      for (int r = 0; r < NR; ++r) {
+        wv[0][r] = qnext[r].x; wv[1][r] = qnext[r].y; wv[2][r] = qnext[r].z; wv[3][r] = qnext[r].w;
+        wsb[r] = snext[r];
+      }
+      if constexpr (AHEAD) {
+        if (c0 + 64 * LSM_U < nchunk) load_trip((c0 >> 8) + 1);
+      }
+    } else {
 #pragma unroll
-      for (int r = 0; r < NR; ++r) wv[u][r] = __builtin_nontemporal_load(wrow[r] + cc);
+      for (int u = 0; u < LSM_U; ++u) {
+        const int cc = min(c0 + 64 * u, nchunk - 1);
+#pragma unroll
+        for (int r = 0; r < NR; ++r) wv[u][r] = __builtin_nontemporal_load(wrow[r] + cc);
+      }
     }
     if constexpr (NORM) {
       if (first) norm_rows();                      // (the loop trip count is workgroup-uniform)
@@ -195,12 +278,24 @@ __global__ __launch_bounds__(256, (NORM && M == 1) ? 3 : 1) void linear_small_m_
         xv[u][m] = c < nchunk ? xl : u32x4{0u, 0u, 0u, 0u};      // pieces past the row end contribute nothing
       }
     }
+    if constexpr (WT::PACKED) {
 #pragma unroll
-    for (int u = 0; u < LSM_U; ++u)
+      for (int u = 0; u < LSM_U; ++u)
 #pragma unroll
-      for (int r = 0; r < NR; ++r)
+        for (int r = 0; r < NR; ++r) {
+          float wf[8];
+          WT::decode(wv[u][r], (wsb[r] >> (8 * u)) & 0xffu, wf);
 #pragma unroll
-        for (int m = 0; m < M; ++m) acc[r][m] = WT::dot(wv[u][r], xv[u][m], acc[r][m]);
+          for (int m = 0; m < M; ++m) acc[r][m] = WT::dot(wf, xv[u][m], acc[r][m]);
+        }
+    } else {
+#pragma unroll
+      for (int u = 0; u < LSM_U; ++u)
+#pragma unroll
+        for (int r = 0; r < NR; ++r)
+#pragma unroll
+          for (int m = 0; m < M; ++m) acc[r][m] = WT::dot(wv[u][r], xv[u][m], acc[r][m]);
+    }
   }
 #pragma unroll
   for (int r = 0; r < RPW; ++r)
@@ -256,10 +351,16 @@ static int lsm_dispatch(const void* x, typename WT::arg wp, const void* bias, vo
   IVL_REQUIRE(x && !WT::null(wp) && y, IVL_ERR_INVALID_ARG, "%s: NULL pointer", who);
   IVL_REQUIRE(M >= 1 && M <= 4, IVL_ERR_UNSUPPORTED, "%s: M=%d (built for 1..4 rows; use a GEMM)", who, M);
   IVL_REQUIRE(N > 0 && K > 0 && K % 8 == 0, IVL_ERR_INVALID_ARG, "%s: N=%d K=%d (K must be a multiple of 8)", who, N, K);
+  if constexpr (WT::PACKED) {
+    IVL_REQUIRE(K % 32 == 0, IVL_ERR_INVALID_ARG, "%s: K=%d (one block scale per 32 weights: K must be a multiple of 32)", who, K);
+    IVL_REQUIRE(((size_t)wp.q & 15) == 0 && ((size_t)wp.s & 3) == 0, IVL_ERR_INVALID_ARG,
+                "%s: wq must be 16-byte aligned and sq 4-byte aligned", who);
+  }
   hipStream_t st = (hipStream_t)stream;
   const bf16_t *xp = (const bf16_t*)x, *bp = (const bf16_t*)bias;
   bf16_t* yp = (bf16_t*)y;
-  // rows per wave: enough workgroups to cover the chip (>= ~2 per CU) before amortising the x reads over more rows
+  // rows per wave: enough workgroups to cover the chip (>= ~2 per CU) before amortising the x reads over more rows (mxfp4 keeps the
+  // rule: 8 rows per wave from N = 32768 measured lm_head at 48 us against 44 with 4 in the same build -- DESIGN 4.14)
   if (glu) {
     if (N >= 4096) launch_lsm<WT, 2, true, NORM>(xp, wp, bp, yp, M, N, K, na, st);       // 4 weight rows per wave
     else launch_lsm<WT, 1, true, NORM>(xp, wp, bp, yp, M, N, K, na, st);
@@ -297,6 +398,8 @@ __global__ __launch_bounds__(256) void linear_gdn_out_kernel(const bf16_t* __res
   const piece_t* wrow = WT::row(w, (size_t)row, K);
   float wscale = 1.f;
   if constexpr (WT::SCALED) wscale = WT::scale(w, __builtin_amdgcn_readfirstlane(row));
+  const unsigned int* wsrow = nullptr;             // (mxfp4: the row's block scales)
+  if constexpr (WT::PACKED) wsrow = WT::srow(w, (size_t)row, K);
   // ---- conv-state shift of q and k (a few items per workgroup; independent of everything else here) ----
   {
     const int total = M * 2 * ga.Dq;
@@ -325,11 +428,34 @@ __global__ __launch_bounds__(256) void linear_gdn_out_kernel(const bf16_t* __res
 #pragma unroll
   for (int m = 0; m < M; ++m) acc[m] = 0.f;
   bool first = true;
+  constexpr bool AHEAD = WT::PACKED && M > 1;      // (mxfp4: two trips in flight, as in linear_small_m_kernel; K >= 512: every lane has a trip 0)
+  u32x4 qnext = {0u, 0u, 0u, 0u};
+  unsigned int snext = 0;
+  if constexpr (AHEAD) {
+    qnext = WT::load_codes(wrow, 0, lane);
+    snext = WT::load_scales(wsrow, 0, lane);
+  }
   for (int c0 = lane; c0 < nchunk; c0 += 64 * LSM_U) {
     piece_t wvv[LSM_U];
+    unsigned int wsb = 0;                          // (mxfp4: byte u = the block scale of piece u)
+    if constexpr (WT::PACKED) {
+      if constexpr (!AHEAD) {
+        qnext = WT::load_codes(wrow, c0 >> 8, lane);
+        snext = WT::load_scales(wsrow, c0 >> 8, lane);
+      }
+      wvv[0] = qnext.x; wvv[1] = qnext.y; wvv[2] = qnext.z; wvv[3] = qnext.w;
+      wsb = snext;
+      if constexpr (AHEAD) {
+        if (c0 + 64 * LSM_U < nchunk) {
+          qnext = WT::load_codes(wrow, (c0 >> 8) + 1, lane);
+          snext = WT::load_scales(wsrow, (c0 >> 8) + 1, lane);
+        }
+      }
+    } else {
 #pragma unroll
-    for (int u = 0; u < LSM_U; ++u) wvv[u] = __builtin_nontemporal_load(wrow + min(c0 + 64 * u, nchunk - 1));
-    if (first) {                                   // (workgroup-uniform trip count)
+      for (int u = 0; u < LSM_U; ++u) wvv[u] = __builtin_nontemporal_load(wrow + min(c0 + 64 * u, nchunk - 1));
+    }
+    if (first) {                                  // (workgroup-uniform trip count)
       const float wf[4] = {bflo(wv.x), bfhi(wv.x), bflo(wv.y), bfhi(wv.y)};
 #pragma unroll
       for (int i = 0; i < HPW; ++i) {
@@ -352,10 +478,13 @@ __global__ __launch_bounds__(256) void linear_gdn_out_kernel(const bf16_t* __res
     for (int u = 0; u < LSM_U; ++u) {
       const int c = c0 + 64 * u;
       const int cc = min(c, nchunk - 1);
+      float wf[WT::PACKED ? 8 : 1];
+      if constexpr (WT::PACKED) WT::decode(wvv[u], (wsb >> (8 * u)) & 0xffu, wf);
 #pragma unroll
       for (int m = 0; m < M; ++m) {
         const u32x4 xl = c < nchunk ? s_x[m * (LSM_NORM_KMAX / 8) + cc] : u32x4{0u, 0u, 0u, 0u};
-        acc[m] = WT::dot(wvv[u], xl, acc[m]);
+        if constexpr (WT::PACKED) acc[m] = WT::dot(wf, xl, acc[m]);
+        else acc[m] = WT::dot(wvv[u], xl, acc[m]);
       }
     }
   }
@@ -420,6 +549,9 @@ static int gdn_out_linear(const void* o_raw, const void* gate, int64_t gate_ld, 
               "whose first trip holds the gated norm, as in the NORM form)", who, H, K, N, LSM_NORM_KMAX);
   IVL_REQUIRE(gate_ld % 4 == 0 && ((size_t)gate & 7) == 0 && ((size_t)o_raw & 7) == 0, IVL_ERR_INVALID_ARG,
               "%s: o_raw / gate rows must be 8-byte aligned", who);
+  if constexpr (WT::PACKED)                        // (K = H * 256 is a multiple of 32)
+    IVL_REQUIRE(((size_t)w.q & 15) == 0 && ((size_t)w.s & 3) == 0, IVL_ERR_INVALID_ARG,
+                "%s: wq must be 16-byte aligned and sq 4-byte aligned", who);
   GdnOutArgs ga;
   ga.gate = (const bf16_t*)gate; ga.gate_ld = gate_ld; ga.norm_w = (const bf16_t*)norm_weight; ga.eps = eps; ga.H = H;
   ga.proj = (const bf16_t*)proj; ga.proj_ld = proj_ld; ga.col_q = col_q; ga.col_k = col_k;
@@ -470,4 +602,33 @@ extern "C" int ivl_gdn_out_linear_small_m_w8_fwd(const void* o_raw, const void* 
                                                  const void* bias, void* y, int M, int N, int K, void* stream) {
   return gdn_out_linear<WE4m3>(o_raw, gate, gate_ld, norm_weight, eps, H, proj, proj_ld, col_q, col_k, conv_state_q, conv_state_k,
                                W8Arg{(const unsigned char*)wq, scale}, bias, y, M, N, K, stream, "ivl_gdn_out_linear_small_m_w8_fwd");
+}
+
+// ---- the MXFP4 twins: wq uint8 [N,Kp/2] e2m1 codes and sq uint8 [N,Kp/32] e8m0 block scales in the shuffled layout of the header ----
+extern "C" int ivl_linear_small_m_w4_fwd(const void* x, const void* wq, const void* sq, const void* bias, void* y, int M, int N, int K,
+                                         void* stream) {
+  return lsm_dispatch<WMxfp4, false>(x, W4Arg{(const unsigned char*)wq, (const unsigned char*)sq}, bias, y, M, N, K, false, NormArgs{},
+                                     stream, "ivl_linear_small_m_w4_fwd");
+}
+
+extern "C" int ivl_linear_swiglu_small_m_w4_fwd(const void* x, const void* wq, const void* sq, const void* bias, void* y, int M, int I,
+                                                int K, void* stream) {
+  return lsm_dispatch<WMxfp4, false>(x, W4Arg{(const unsigned char*)wq, (const unsigned char*)sq}, bias, y, M, I, K, true, NormArgs{},
+                                     stream, "ivl_linear_swiglu_small_m_w4_fwd");
+}
+
+extern "C" int ivl_norm_linear_small_m_w4_fwd(const void* x, const void* residual, const void* norm_weight, float eps, void* h_out,
+                                              const void* wq, const void* sq, const void* bias, void* y, int M, int N, int K, int glu,
+                                              void* stream) {
+  return norm_linear<WMxfp4>(x, residual, norm_weight, eps, h_out, W4Arg{(const unsigned char*)wq, (const unsigned char*)sq}, bias, y, M,
+                             N, K, glu, stream, "ivl_norm_linear_small_m_w4_fwd");
+}
+
+extern "C" int ivl_gdn_out_linear_small_m_w4_fwd(const void* o_raw, const void* gate, int64_t gate_ld, const void* norm_weight,
+                                                 float eps, int H, const void* proj, int64_t proj_ld, int col_q, int col_k,
+                                                 void* conv_state_q, void* conv_state_k, const void* wq, const void* sq,
+                                                 const void* bias, void* y, int M, int N, int K, void* stream) {
+  return gdn_out_linear<WMxfp4>(o_raw, gate, gate_ld, norm_weight, eps, H, proj, proj_ld, col_q, col_k, conv_state_q, conv_state_k,
+                                W4Arg{(const unsigned char*)wq, (const unsigned char*)sq}, bias, y, M, N, K, stream,
+                                "ivl_gdn_out_linear_small_m_w4_fwd");
 }

@@ -116,13 +116,17 @@ class InfiniteVLTextMLP(nn.Module):
         self._w8_on = False
 
     @torch.no_grad()
-    def quantize_weights_(self) -> "InfiniteVLTextMLP":
-        """Round the fused gate|up weight and down_proj onto the e4m3 x 2^e grid IN PLACE and keep the packed copies."""
+    def quantize_weights_(self, fmt: str = "e4m3") -> "InfiniteVLTextMLP":
+        """Round the fused gate|up weight and down_proj onto the grid of `fmt` ("e4m3" or "mxfp4") IN PLACE and keep the packed copies."""
+        ops.check_packable(self._packed_weights(), fmt)
+        self._w8_gu = ops.PackedWeight.of(self._fused_w, also=(self.gate_proj.weight, self.up_proj.weight), fmt=fmt)
+        self._w8_down = ops.PackedWeight.of(self.down_proj.weight, fmt=fmt)
+        return self
+
+    def _packed_weights(self):
         if self._fused_w is None:
             raise RuntimeError("quantize_weights_: call fuse_() first")
-        self._w8_gu = ops.PackedWeight.of(self._fused_w, also=(self.gate_proj.weight, self.up_proj.weight))
-        self._w8_down = ops.PackedWeight.of(self.down_proj.weight)
-        return self
+        return (self._fused_w, self.down_proj.weight)
 
     @torch.no_grad()
     def fuse_(self) -> "InfiniteVLTextMLP":
@@ -182,6 +186,7 @@ class InfiniteVLTextStack(nn.Module):
         self.rotary_emb = InfiniteVLRotaryEmbedding(config)
         self._w8_lm_head = None                 # ops.PackedWeight of the tied embed_tokens.weight (quantize_weights_(lm_head=True))
         self._w8_on = False
+        self._w8_fmt = None                     # the format of the packed copies: "e4m3" / "mxfp4" (quantize_weights_)
 
     @torch.no_grad()
     def init_weights_(self, seed: int = 0, std: float = 0.02) -> "InfiniteVLTextStack":
@@ -218,8 +223,12 @@ class InfiniteVLTextStack(nn.Module):
         return self
 
     @torch.no_grad()
-    def quantize_weights_(self, lm_head: bool = False) -> "InfiniteVLTextStack":
-        """Weight-only e4m3 for the decode step (call after fuse_()).  THIS CHANGES THE MODEL'S WEIGHTS: every
+    def quantize_weights_(self, lm_head: bool = False, fmt: str = "e4m3") -> "InfiniteVLTextStack":
+        """Weight-only e4m3 (fmt="e4m3") or MXFP4 (fmt="mxfp4", DESIGN 4.14: e2m1 codes x one power of two per block
+        of 32 weights, +0.53 byte per weight, ops.quantize_rows_mxfp4; every projection's K must be a multiple of 32, else ValueError
+        before anything is written) for the decode step (call after fuse_()).  Calling it again with another format RE-ROUNDS the
+        already rounded W' onto the new grid: quantise from the original weights for the best 4-bit model.  What follows describes
+        e4m3 and holds for mxfp4 with its grid and bytes.  THIS CHANGES THE MODEL'S WEIGHTS: every
         projection weight -- the fused q|k|v, the attention o_proj, the fused GDN in-projection, the GDN o_proj, the fused gate|up,
         down_proj, and with lm_head=True the tied embed_tokens.weight (the embedding lookup then reads the rounded weight too) --
         is rounded IN PLACE to W' = e4m3 code x 2^e, one power of two per row (ops.quantize_rows_e4m3), and keeps a packed
@@ -227,10 +236,13 @@ class InfiniteVLTextStack(nn.Module):
         Biases, norm and conv weights stay bf16.  From then on every path computes the same function bit for bit whether the
         packed copies are used (decode steps of <= 4 rows stream 1 byte per weight) or not: use_packed_weights() switches.
         Writing the weights afterwards (load_state_dict) makes the packed copies stale -- the next call raises; quantise again."""
+        todo = [w for layer in self.layers for m in (layer.self_attn, layer.mlp) for w in m._packed_weights()]
+        ops.check_packable(todo + ([self.embed_tokens.weight] if lm_head else []), fmt)
         for layer in self.layers:
-            layer.self_attn.quantize_weights_()
-            layer.mlp.quantize_weights_()
-        self._w8_lm_head = ops.PackedWeight.of(self.embed_tokens.weight) if lm_head else None
+            layer.self_attn.quantize_weights_(fmt=fmt)
+            layer.mlp.quantize_weights_(fmt=fmt)
+        self._w8_lm_head = ops.PackedWeight.of(self.embed_tokens.weight, fmt=fmt) if lm_head else None
+        self._w8_fmt = fmt
         return self.use_packed_weights(True)
 
     def use_packed_weights(self, on: bool = True) -> "InfiniteVLTextStack":
@@ -378,6 +390,7 @@ class _Graphed:
     sampler: Optional["Sampler"] = None                 # (GraphedStep has none)
     _captured_controlled = False
     _captured_w8 = False
+    _captured_fmt = None
 
     def _capture(self, tensors: List[torch.Tensor], scope=None):
         """Captures one self._run() into self.graph and returns what it returned.  The cache, `tensors` and the sampler's state
@@ -401,17 +414,22 @@ class _Graphed:
         if self.sampler is not None:
             self.sampler.load_state(saved_smp)          # the warm-up and the capture itself made draws
             self._captured_controlled = self.sampler.controlled
-        self._captured_w8 = self._w8_on()
+        self._captured_w8, self._captured_fmt = self._w8_on(), self._w8_fmt()
         return out
 
     def _w8_on(self) -> bool:
         return bool(getattr(self.model, "_w8_on", False))
 
+    def _w8_fmt(self):
+        """the format of the packed copies in use (None: the bf16 weights)"""
+        return getattr(self.model, "_w8_fmt", None) if self._w8_on() else None
+
     def _stale(self) -> bool:
         """No graph yet, or one captured before the sampler switched to the controlled launch or before the model switched
-        between its bf16 weights and their packed e4m3 copies (use_packed_weights)."""
+        between its bf16 weights and their packed copies (use_packed_weights) or between the formats of the packed copies
+        (quantize_weights_(fmt=): the captured launches are those of one format)."""
         return (self.graph is None or (self.sampler is not None and self.sampler.controlled != self._captured_controlled)
-                or self._w8_on() != self._captured_w8)
+                or self._w8_on() != self._captured_w8 or self._w8_fmt() != self._captured_fmt)
 
     def _run(self):
         """The T = 1 step: forward of every row's token, its next token, positions + 1."""

@@ -150,13 +150,18 @@ class InfiniteVLSelfAttention(nn.Module):
         return ops.linear(attn, self.o_proj.weight, self.o_proj.bias, **ops.w8_kwargs(self._w8_o, self._w8_on)), None
 
     @torch.no_grad()
-    def quantize_weights_(self) -> "InfiniteVLSelfAttention":
-        """Round the fused q|k|v weight and o_proj onto the e4m3 x 2^e grid IN PLACE and keep the packed copies (after fuse_())."""
+    def quantize_weights_(self, fmt: str = "e4m3") -> "InfiniteVLSelfAttention":
+        """Round the fused q|k|v weight and o_proj onto the grid of `fmt` ("e4m3": e4m3 x 2^e per row; "mxfp4": e2m1 x 2^e per
+        block of 32) IN PLACE and keep the packed copies (after fuse_())."""
+        ops.check_packable(self._packed_weights(), fmt)
+        self._w8_qkv = ops.PackedWeight.of(self._fused_w, also=(self.q_proj.weight, self.k_proj.weight, self.v_proj.weight), fmt=fmt)
+        self._w8_o = ops.PackedWeight.of(self.o_proj.weight, fmt=fmt)
+        return self
+
+    def _packed_weights(self):
         if self._fused_w is None:
             raise RuntimeError("quantize_weights_: call fuse_() first")
-        self._w8_qkv = ops.PackedWeight.of(self._fused_w, also=(self.q_proj.weight, self.k_proj.weight, self.v_proj.weight))
-        self._w8_o = ops.PackedWeight.of(self.o_proj.weight)
-        return self
+        return (self._fused_w, self.o_proj.weight)
 
 
 class GatedDeltaNet(nn.Module):
@@ -248,14 +253,18 @@ class GatedDeltaNet(nn.Module):
         return self
 
     @torch.no_grad()
-    def quantize_weights_(self) -> "GatedDeltaNet":
-        """Round the fused q|k|v|g|a|b weight and o_proj onto the e4m3 x 2^e grid IN PLACE and keep the packed copies."""
+    def quantize_weights_(self, fmt: str = "e4m3") -> "GatedDeltaNet":
+        """Round the fused q|k|v|g|a|b weight and o_proj onto the grid of `fmt` ("e4m3" or "mxfp4") IN PLACE and keep the packed copies."""
+        ops.check_packable(self._packed_weights(), fmt)
+        self._w8_in = ops.PackedWeight.of(self._fused_w, also=(self.q_proj.weight, self.k_proj.weight, self.v_proj.weight,
+                                                              self.g_proj.weight, self.a_proj.weight, self.b_proj.weight), fmt=fmt)
+        self._w8_o = ops.PackedWeight.of(self.o_proj.weight, fmt=fmt)
+        return self
+
+    def _packed_weights(self):
         if self._fused_w is None:
             raise RuntimeError("quantize_weights_: call fuse_() first (the Gated DeltaNet needs use_gate)")
-        self._w8_in = ops.PackedWeight.of(self._fused_w, also=(self.q_proj.weight, self.k_proj.weight, self.v_proj.weight,
-                                                              self.g_proj.weight, self.a_proj.weight, self.b_proj.weight))
-        self._w8_o = ops.PackedWeight.of(self.o_proj.weight)
-        return self
+        return (self._fused_w, self.o_proj.weight)
 
     def _gate_params32(self):
         """fp32 copies of A_log / dt_bias for the gate math (std:1294 upcasts them per call); cached and

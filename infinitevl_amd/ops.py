@@ -824,11 +824,12 @@ def gdn_out_linear(o_raw: torch.Tensor, proj: torch.Tensor, col_g: int, col_q: i
     gate = proj.view(B, ld)[:, col_g:]
     if w8 is not None:                                   # the e4m3 twin on the packed copy of `weight` (see `linear`)
         w8.check(weight)
-        _lib.check(_lib.load().ivl_gdn_out_linear_small_m_w8_fwd(
+        fn = _lib.load().ivl_gdn_out_linear_small_m_w4_fwd if w8.fmt == "mxfp4" else _lib.load().ivl_gdn_out_linear_small_m_w8_fwd
+        _lib.check(fn(
             _p(o_raw), ctypes.c_void_p(gate.data_ptr()), ld, _p(norm_weight), float(eps), H, _p(proj), ld, col_q, col_k,
             _p(conv_state_q), _p(conv_state_k), _p(w8.codes), _p(w8.scale), _p(bias) if bias is not None else None, _p(y), B, N, K,
             _stream(o_raw)))
-        W8_CALLS["gdn_out_linear"] += 1
+        w8.count("gdn_out_linear")
         return y
     _lib.check(_lib.load().ivl_gdn_out_linear_small_m_fwd(
         _p(o_raw), ctypes.c_void_p(gate.data_ptr()), ld, _p(norm_weight), float(eps), H, _p(proj), ld, col_q, col_k,
@@ -958,26 +959,140 @@ def dequantize_rows_e4m3(codes: torch.Tensor, scale: torch.Tensor) -> torch.Tens
     return (codes.view(torch.float8_e4m3fn).float() * scale[:, None].float()).to(torch.bfloat16)
 
 
+# ---- weight-only MXFP4 (OCP microscaling FP4) for the same weight streams ---------------------------------------------
+E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)          # the magnitudes of codes 0 .. 7; bit 3 is the sign
+MXFP4_BLOCK = 32                                                 # weights per e8m0 scale
+MXFP4_TILE = 2048                                                # weights per tile of the shuffled layout: rows are padded to it
+W4_CALLS = {"linear": 0, "linear_swiglu": 0, "norm_linear": 0, "gdn_out_linear": 0}      # as W8_CALLS, for the w4 entry points
+PACKED_FORMATS = ("e4m3", "mxfp4")
+
+
+def quantize_rows_mxfp4(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """bf16 [N,K], K % 32 == 0 -> (codes uint8 [N,K/2], e8m0 uint8 [N,K/32], exp int32 [N,K/32]): plain row-major OCP MXFP4 -- element
+    2j of a row in the low nibble of byte j, element 2j + 1 in the high nibble; one scale 2^e, e8m0 = e + 127, per block of 32.
+    e is the SMALLEST exponent with amax(block) <= 6 * 2^e (e = 0 for a zero block), taken from frexp (amax = m 2^x, 0.5 <= m < 1:
+    e = x - 3 up to m = 0.75 = 6 / 8, else x - 2), never from a floating log2.  This rule never saturates: w / 2^e <= 6.  (The OCP
+    reference rule, e = floor(log2 amax) - 2, is one smaller wherever m > 0.75 and then clamps 6 * 2^e < |w| to +-6.)  Codes are
+    RNE(w / 2^e) on the e2m1 grid {0, .5, 1, 1.5, 2, 3, 4, 6}, ties to the even mantissa bit (0.25 -> 0, 0.75 -> 1, 1.25 -> 1,
+    1.75 -> 2, 2.5 -> 2, 3.5 -> 4, 5 -> 4); bit 3 of a code is signbit(w), so -0.0 and negatives that round to zero give 0x8.
+    K % 32 != 0, non-finite weights and |e| > 100 raise ValueError.  Pure torch: CPU and GPU tensors."""
+    if w.dim() != 2 or w.dtype != torch.bfloat16:
+        raise ValueError(f"quantize_rows_mxfp4: a bf16 [N,K] weight is expected; got {w.dtype} {tuple(w.shape)}")
+    N, K = w.shape
+    if K % MXFP4_BLOCK:
+        raise ValueError(f"quantize_rows_mxfp4: K={K} is not a multiple of {MXFP4_BLOCK} (one scale per 32 weights)")
+    wf = w.detach().float().view(N, K // MXFP4_BLOCK, MXFP4_BLOCK)
+    if not bool(torch.isfinite(wf).all()):
+        raise ValueError("quantize_rows_mxfp4: non-finite weights")
+    amax = wf.abs().amax(2)
+    m, x = torch.frexp(amax)
+    exp = torch.where(m <= 0.75, x - 3, x - 2)
+    exp = torch.where(amax == 0, torch.zeros_like(exp), exp).to(torch.int32)
+    if bool((exp.abs() > W8_EXP_LIMIT).any()):
+        raise ValueError(f"quantize_rows_mxfp4: a block scale 2^e with |e| > {W8_EXP_LIMIT}")
+    v = (wf / torch.ldexp(torch.ones_like(amax), exp)[..., None]).abs()          # exact, <= 6
+    idx = ((v > 0.25).to(torch.uint8) + (v >= 0.75) + (v > 1.25) + (v >= 1.75) + (v > 2.5) + (v >= 3.5) + (v > 5.0)).to(torch.uint8)
+    c = (idx | (torch.signbit(wf).to(torch.uint8) << 3)).view(N, K // 2, 2)
+    return c[..., 0] | (c[..., 1] << 4), (exp + 127).to(torch.uint8), exp
+
+
+def dequantize_rows_mxfp4(codes: torch.Tensor, e8m0: torch.Tensor) -> torch.Tensor:
+    """W' = e2m1(code) * 2^(e8m0 - 127) as bf16 [N,K] from plain row-major codes [N,K/2] and scales [N,K/32]: exact (2 significant bits)."""
+    N, Kh = codes.shape
+    c = torch.stack([codes & 15, codes >> 4], -1).view(N, Kh * 2).long()
+    mag = torch.tensor(E2M1_VALUES, dtype=torch.float32, device=codes.device)[c & 7]
+    val = torch.where((c & 8) != 0, -mag, mag).view(N, -1, MXFP4_BLOCK)
+    return torch.ldexp(val, (e8m0.to(torch.int32) - 127)[..., None]).view(N, Kh * 2).to(torch.bfloat16)
+
+
+def mxfp4_shuffle(codes: torch.Tensor, e8m0: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Plain row-major (codes [N,K/2], e8m0 [N,K/32]) -> (wq uint8 [N,Kp/2], sq uint8 [N,Kp/32]), Kp = 2048 ceil(K / 2048): the layout
+    the w4 kernels read (include/ivl_hip.h).  A chunk is 8 consecutive K elements = 4 bytes; the chunk 256t + l + 64u (l in 0..63, u in
+    0..3) goes to byte 1024t + 16l + 4u of its row, the scale of block 64t + g + 16u (g in 0..15) to byte 64t + 4g + u.  Padding:
+    code 0x0, scale byte 127."""
+    N, Kh = codes.shape
+    K = Kh * 2
+    if codes.dtype != torch.uint8 or e8m0.dtype != torch.uint8 or K % MXFP4_BLOCK or tuple(e8m0.shape) != (N, K // MXFP4_BLOCK):
+        raise ValueError(f"mxfp4_shuffle: uint8 codes [N,K/2] and scales [N,K/32], K % 32 == 0, are expected; got "
+                         f"{codes.dtype} {tuple(codes.shape)}, {e8m0.dtype} {tuple(e8m0.shape)}")
+    T = -(-K // MXFP4_TILE)
+    Kp = T * MXFP4_TILE
+    cp = torch.nn.functional.pad(codes, (0, (Kp - K) // 2), value=0).view(N, T, 4, 64, 4)            # [t, u, l, byte]
+    sp = torch.nn.functional.pad(e8m0, (0, (Kp - K) // MXFP4_BLOCK), value=127).view(N, T, 4, 16)    # [t, u, g]
+    return cp.permute(0, 1, 3, 2, 4).reshape(N, Kp // 2).contiguous(), sp.permute(0, 1, 3, 2).reshape(N, Kp // 32).contiguous()
+
+
+def mxfp4_unshuffle(wq: torch.Tensor, sq: torch.Tensor, K: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The inverse of mxfp4_shuffle for a logical row length K (default: the padded length Kp)."""
+    N, Kph = wq.shape
+    Kp = Kph * 2
+    K = Kp if K is None else K
+    if Kp % MXFP4_TILE or tuple(sq.shape) != (N, Kp // MXFP4_BLOCK) or K % MXFP4_BLOCK or not Kp - MXFP4_TILE < K <= Kp:
+        raise ValueError(f"mxfp4_unshuffle: wq {tuple(wq.shape)} / sq {tuple(sq.shape)} are not the shuffled layout of K={K}")
+    T = Kp // MXFP4_TILE
+    codes = wq.view(N, T, 64, 4, 4).permute(0, 1, 3, 2, 4).reshape(N, Kp // 2)
+    e8m0 = sq.view(N, T, 16, 4).permute(0, 1, 3, 2).reshape(N, Kp // MXFP4_BLOCK)
+    return codes[:, :K // 2].contiguous(), e8m0[:, :K // MXFP4_BLOCK].contiguous()
+
+
 class PackedWeight:
-    """The e4m3 copy of a bf16 weight that HOLDS W' = dequantize(codes, scale): codes uint8 [N,K], scale fp32 [N] (powers of two),
-    and what identifies the bf16 weight it was made from -- its data pointer and `_version` (and those of `also`: parameters that
-    are views of a fused weight carry version counters of their own, and load_state_dict writes through THEM).  A packed copy whose
-    weight has moved or been written since is stale: `check` raises, nothing falls back silently."""
+    """The packed copy of a bf16 weight that HOLDS W' = dequantize(packed copy), and what identifies the bf16 weight it was made from
+    -- its data pointer and `_version` (and those of `also`: parameters that are views of a fused weight carry version counters of
+    their own, and load_state_dict writes through THEM).  A packed copy whose weight has moved or been written since is stale:
+    `check` raises, nothing falls back silently.
+      fmt "e4m3" (the default):  codes uint8 [N,K] e4m3fn, scale fp32 [N] (powers of two);
+      fmt "mxfp4":               codes uint8 [N,Kp/2] e2m1 pairs and scale uint8 [N,Kp/32] e8m0 block scales, both in the SHUFFLED
+                                 layout of mxfp4_shuffle (Kp = 2048 ceil(K / 2048)).
+    `shape` is the logical [N,K] of the weight."""
 
-    __slots__ = ("codes", "scale", "exp", "ptr", "version", "_watch")
+    __slots__ = ("codes", "scale", "exp", "ptr", "version", "_watch", "fmt", "shape")
 
-    def __init__(self, weight: torch.Tensor, codes: torch.Tensor, scale: torch.Tensor, exp: Optional[torch.Tensor] = None, also=()):
-        self.codes, self.scale, self.exp = codes.contiguous(), scale.to(torch.float32).contiguous(), exp
+    def __init__(self, weight: torch.Tensor, codes: torch.Tensor, scale: torch.Tensor, exp: Optional[torch.Tensor] = None, also=(),
+                 fmt: str = "e4m3"):
+        if fmt not in PACKED_FORMATS:
+            raise ValueError(f"PackedWeight: fmt must be one of {PACKED_FORMATS} (got {fmt!r})")
+        self.fmt, self.exp = fmt, exp
+        if fmt == "mxfp4":
+            N, K = weight.shape
+            Kp = -(-K // MXFP4_TILE) * MXFP4_TILE
+            if (K % MXFP4_BLOCK or codes.dtype != torch.uint8 or scale.dtype != torch.uint8 or tuple(codes.shape) != (N, Kp // 2)
+                    or tuple(scale.shape) != (N, Kp // MXFP4_BLOCK)):
+                raise ValueError(f"PackedWeight(mxfp4): a weight {tuple(weight.shape)} takes shuffled uint8 codes {(N, Kp // 2)} and "
+                                 f"scales {(N, Kp // MXFP4_BLOCK)}; got {codes.dtype} {tuple(codes.shape)}, {scale.dtype} "
+                                 f"{tuple(scale.shape)}")
+            self.codes, self.scale, self.shape = codes.contiguous(), scale.contiguous(), (N, K)
+        else:
+            self.codes, self.scale = codes.contiguous(), scale.to(torch.float32).contiguous()
+            self.shape = tuple(self.codes.shape)
         self.ptr, self.version = weight.data_ptr(), weight._version
         self._watch = [(t, t.data_ptr(), t._version) for t in also]
 
     @classmethod
-    def of(cls, weight: torch.Tensor, also=()) -> "PackedWeight":
+    def of(cls, weight: torch.Tensor, also=(), fmt: str = "e4m3") -> "PackedWeight":
         """Quantise `weight` (bf16 [N,K], contiguous), write W' back IN PLACE (views and data pointers keep holding) and pack it."""
+        if fmt == "mxfp4":
+            codes, e8m0, exp = quantize_rows_mxfp4(weight)
+            return cls.from_mxfp4(weight, codes, e8m0, also, exp)
+        if fmt != "e4m3":
+            raise ValueError(f"PackedWeight.of: fmt must be one of {PACKED_FORMATS} (got {fmt!r})")
         codes, exp, scale = quantize_rows_e4m3(weight)
         with torch.no_grad():
             weight.copy_(dequantize_rows_e4m3(codes, scale))
         return cls(weight, codes, scale, exp, also)
+
+    @classmethod
+    def from_mxfp4(cls, weight: torch.Tensor, codes: torch.Tensor, e8m0: torch.Tensor, also=(),
+                   exp: Optional[torch.Tensor] = None) -> "PackedWeight":
+        """An existing MXFP4 checkpoint: plain row-major codes [N,K/2] and e8m0 scales [N,K/32] (on weight's device) of a bf16 [N,K]
+        `weight`, which receives W' = dequantize_rows_mxfp4(codes, e8m0) IN PLACE; the codes are shuffled into the kernel layout."""
+        N, K = weight.shape
+        if weight.dtype != torch.bfloat16 or K % MXFP4_BLOCK or tuple(codes.shape) != (N, K // 2) or tuple(e8m0.shape) != (N, K // 32):
+            raise ValueError(f"PackedWeight.from_mxfp4: a bf16 weight [N,K], K % 32 == 0, with codes [N,K/2] and scales [N,K/32] is "
+                             f"expected; got {weight.dtype} {tuple(weight.shape)}, {tuple(codes.shape)}, {tuple(e8m0.shape)}")
+        wq, sq = mxfp4_shuffle(codes.to(weight.device), e8m0.to(weight.device))
+        with torch.no_grad():
+            weight.copy_(dequantize_rows_mxfp4(codes.to(weight.device), e8m0.to(weight.device)))
+        return cls(weight, wq, sq, exp, also, fmt="mxfp4")
 
     def stale(self, weight: torch.Tensor) -> bool:
         return (weight.data_ptr() != self.ptr or weight._version != self.version
@@ -987,10 +1102,24 @@ class PackedWeight:
         if self.stale(weight):
             raise RuntimeError("PackedWeight is stale: the bf16 weight it was quantised from has moved or been written since "
                                "(load_state_dict, an in-place update); call quantize_weights_() again")
-        if tuple(self.codes.shape) != tuple(weight.shape) or self.codes.device != weight.device:
-            raise RuntimeError(f"PackedWeight {tuple(self.codes.shape)} on {self.codes.device} does not belong to a weight "
+        if tuple(self.shape) != tuple(weight.shape) or self.codes.device != weight.device:
+            raise RuntimeError(f"PackedWeight {tuple(self.shape)} on {self.codes.device} does not belong to a weight "
                                f"{tuple(weight.shape)} on {weight.device}")
         return self
+
+    def count(self, entry: str) -> None:
+        (W4_CALLS if self.fmt == "mxfp4" else W8_CALLS)[entry] += 1
+
+
+def check_packable(weights, fmt: str) -> None:
+    """What quantize_weights_ asks before it writes anything: a known format, and for mxfp4 every K a multiple of 32."""
+    if fmt not in PACKED_FORMATS:
+        raise ValueError(f"quantize_weights_: fmt must be one of {PACKED_FORMATS} (got {fmt!r})")
+    if fmt == "mxfp4":
+        bad = [tuple(w.shape) for w in weights if w.shape[-1] % MXFP4_BLOCK]
+        if bad:
+            raise ValueError(f"quantize_weights_(fmt='mxfp4'): K must be a multiple of {MXFP4_BLOCK} (one block scale per 32 weights); "
+                             f"got weights {bad}; nothing was written")
 
 
 def w8_kwargs(packed: Optional[PackedWeight], on: bool) -> dict:
@@ -1013,10 +1142,11 @@ def _prenorm_linear(pn: "PreNorm", weight: torch.Tensor, bias: Optional[torch.Te
     N = weight.shape[0] // 2 if glu else weight.shape[0]
     y = torch.empty(*pn.shape[:-1], N, dtype=torch.bfloat16, device=pn.device)
     if w8 is not None:
-        _lib.check(_lib.load().ivl_norm_linear_small_m_w8_fwd(
+        fn = _lib.load().ivl_norm_linear_small_m_w4_fwd if w8.fmt == "mxfp4" else _lib.load().ivl_norm_linear_small_m_w8_fwd
+        _lib.check(fn(
             _p(pn.x), _p(pn.residual), _p(pn.weight), pn.eps, _p(pn.h) if pn.residual is not None else None,
             _p(w8.codes), _p(w8.scale), _p(bias) if bias is not None else None, _p(y), rows, N, K, 1 if glu else 0, _stream(pn.x)))
-        W8_CALLS["norm_linear"] += 1
+        w8.count("norm_linear")
         pn.done = True
         return y
     _lib.check(_lib.load().ivl_norm_linear_small_m_fwd(
@@ -1057,8 +1187,9 @@ def _linear_swiglu_m256(x: torch.Tensor, w_gate_up: torch.Tensor, rows: int, I: 
 def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, w8: Optional[PackedWeight] = None) -> torch.Tensor:
     """nn.Linear forward.  A single-token decode step (<= 4 rows) is a pure weight stream and goes through
     ivl_linear_small_m_fwd; longer calls are stock library GEMMs (hipBLASLt / rocBLAS through torch), which
-    SURVEY.md 8(d) keeps outside the hot path.  w8: the packed e4m3 copy of `weight` (which then holds W'): the weight stream
-    reads it in place of the bf16 weight -- the same bits, half the bytes; every other path reads `weight` as ever."""
+    SURVEY.md 8(d) keeps outside the hot path.  w8: the packed copy of `weight` (which then holds W'), e4m3 or mxfp4 -- the call
+    dispatches on its format: the weight stream reads it in place of the bf16 weight -- the same bits, a half or a quarter of the
+    bytes; every other path reads `weight` as ever."""
     if w8 is not None:
         w8.check(weight)
     if isinstance(x, PreNorm):
@@ -1075,9 +1206,9 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] =
         N = weight.shape[0]
         y = torch.empty(*x.shape[:-1], N, dtype=torch.bfloat16, device=x.device)
         if w8 is not None:
-            _lib.check(_lib.load().ivl_linear_small_m_w8_fwd(_p(xc), _p(w8.codes), _p(w8.scale), _p(bias) if bias is not None else None,
-                                                             _p(y), rows, N, K, _stream(x)))
-            W8_CALLS["linear"] += 1
+            fn = _lib.load().ivl_linear_small_m_w4_fwd if w8.fmt == "mxfp4" else _lib.load().ivl_linear_small_m_w8_fwd
+            _lib.check(fn(_p(xc), _p(w8.codes), _p(w8.scale), _p(bias) if bias is not None else None, _p(y), rows, N, K, _stream(x)))
+            w8.count("linear")
             return y
         _lib.check(_lib.load().ivl_linear_small_m_fwd(_p(xc), _p(weight), _p(bias) if bias is not None else None,
                                                       _p(y), rows, N, K, _stream(x)))
@@ -1104,9 +1235,9 @@ def linear_swiglu(x: torch.Tensor, w_gate_up: torch.Tensor, w8: Optional[PackedW
         xc = x if x.is_contiguous() else x.contiguous()
         y = torch.empty(*x.shape[:-1], I, dtype=torch.bfloat16, device=x.device)
         if w8 is not None:
-            _lib.check(_lib.load().ivl_linear_swiglu_small_m_w8_fwd(_p(xc), _p(w8.codes), _p(w8.scale), None, _p(y), rows, I, K,
-                                                                    _stream(x)))
-            W8_CALLS["linear_swiglu"] += 1
+            fn = _lib.load().ivl_linear_swiglu_small_m_w4_fwd if w8.fmt == "mxfp4" else _lib.load().ivl_linear_swiglu_small_m_w8_fwd
+            _lib.check(fn(_p(xc), _p(w8.codes), _p(w8.scale), None, _p(y), rows, I, K, _stream(x)))
+            w8.count("linear_swiglu")
             return y
         _lib.check(_lib.load().ivl_linear_swiglu_small_m_fwd(_p(xc), _p(w_gate_up), None, _p(y), rows, I, K, _stream(x)))
         return y

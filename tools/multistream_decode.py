@@ -70,6 +70,12 @@ For information: how far the logits of the rounded random-init model sit from th
 steps (max and rms of the difference beside the rms of the logits).  Nothing is asserted.
 
     python tools/multistream_decode.py --w8 --slots 1,4 [--out profiles/w8_decode.json]
+
+--w4: weight-only MXFP4 (quantize_weights_(lm_head=True, fmt="mxfp4")) beside e4m3 and bf16, in one process: the captured greedy
+step A (bf16 weights) B (e4m3 copies) C (mxfp4 copies), timed A B C A B C per slot count, median of --rounds rounds; then the
+operator table of --w8 with a w4 column (us per call, achieved GB/s of the bytes each format streams, w4 / w8 and w4 / bf16).
+
+    python tools/multistream_decode.py --w4 --slots 1,4 [--out profiles/w4_decode.json]
 """
 import argparse
 import json
@@ -96,6 +102,7 @@ def main():
     ap.add_argument("--beam", action="store_true", help="time the beam search step and the row gather (see above)")
     ap.add_argument("--grammar", action="store_true", help="time the constrained step against the scored one (see above)")
     ap.add_argument("--w8", action="store_true", help="time the step on packed e4m3 weights against the bf16 step (see above)")
+    ap.add_argument("--w4", action="store_true", help="time the step on packed mxfp4 weights against the e4m3 and bf16 steps (see above)")
     args = ap.parse_args()
     import torch
     from infinitevl_amd.cache import MultiStreamCache
@@ -136,6 +143,8 @@ def main():
         return grammar_legs(args, torch, model, cfg, prompts, dev)
     if args.w8:
         return w8_legs(args, torch, model, cfg, prompts, dev)
+    if args.w4:
+        return w4_legs(args, torch, model, cfg, prompts, dev)
 
     # reference: one stream on the existing B = 1 graphed decode step
     c1 = model.allocate_inference_cache(1)
@@ -540,8 +549,12 @@ def grammar_legs(args, torch, model, cfg, prompts, dev):
             f.write(line + "\n")
 
 
-def w8_operator_legs(args, torch, cfg, dev, timed):
-    """every weight stream of a decode token alone: {name: {M: {bf16_us, w8_us, bf16_GBs, w8_GBs}}}"""
+BYTES_PER_WEIGHT = {"bf16": 2.0, "w8": 1.0, "w4": 0.5 + 1.0 / 32}
+
+
+def w8_operator_legs(args, torch, cfg, dev, timed, fmts=("bf16", "w8")):
+    """every weight stream of a decode token alone: {name: {M: {<fmt>_us, <fmt>_GBs, <fmt>_over_bf16 ...}}}; fmts: bf16, w8 (e4m3)
+    and, for --w4, w4 (mxfp4), timed in turn (A B A B / A B C A B C)"""
     from infinitevl_amd import _lib, ops
     lib = _lib.load()
     hd, I, V = cfg.hidden_size, cfg.intermediate_size, cfg.vocab_size
@@ -549,14 +562,20 @@ def w8_operator_legs(args, torch, cfg, dev, timed):
     shapes = [("qkv", 2560, hd, "norm"), ("gdn_in", 12320, hd, "norm"), ("attn_o_proj", hd, 2048, "plain"),
               ("gdn_o_proj", hd, 4096, "plain"), ("gate_up", 2 * I, hd, "norm_glu"), ("down", hd, I, "plain"),
               ("lm_head", V, hd, "plain")]
+    plain = {"bf16": lib.ivl_linear_small_m_fwd, "w8": lib.ivl_linear_small_m_w8_fwd, "w4": lib.ivl_linear_small_m_w4_fwd}
+    normed = {"bf16": lib.ivl_norm_linear_small_m_fwd, "w8": lib.ivl_norm_linear_small_m_w8_fwd, "w4": lib.ivl_norm_linear_small_m_w4_fwd}
     gen = torch.Generator(device=dev).manual_seed(2)
     out = {}
     for name, R, K, form in shapes:
         copies = max(2, -(-(1 << 30) // (R * K * 2)))
         w = (torch.randn(R, K, generator=gen, device=dev) * 0.02).to(torch.bfloat16)
         codes, _, scale = ops.quantize_rows_e4m3(w)
-        wb = ops.dequantize_rows_e4m3(codes, scale)[None].expand(copies, R, K).contiguous()
-        wq = codes[None].expand(copies, R, K).contiguous()
+        # (weights, second operand) per format: the speed of a stream does not depend on the values
+        ws = {"bf16": (ops.dequantize_rows_e4m3(codes, scale)[None].expand(copies, R, K).contiguous(), None),
+              "w8": (codes[None].expand(copies, R, K).contiguous(), scale)}
+        if "w4" in fmts:
+            wq4, sq4 = ops.mxfp4_shuffle(*ops.quantize_rows_mxfp4(w)[:2])
+            ws["w4"] = (wq4[None].expand(copies, *wq4.shape).contiguous(), sq4[None].expand(copies, *sq4.shape).contiguous())
         del w
         N = R // 2 if form == "norm_glu" else R
         nw = torch.ones(K, dtype=torch.bfloat16, device=dev)
@@ -566,41 +585,43 @@ def w8_operator_legs(args, torch, cfg, dev, timed):
             y = torch.empty(M, N, dtype=torch.bfloat16, device=dev)
             state = {"i": 0}
 
-            def call(packed):
+            def call(fmt):
                 i = state["i"] = (state["i"] + 1) % copies
                 st = ops._stream(x)
-                wp = ops._p(wq[i]) if packed else ops._p(wb[i])
+                wt, second = ws[fmt]
+                extra = () if fmt == "bf16" else (ops._p(second[i]) if fmt == "w4" else ops._p(second),)
                 if form == "plain":
-                    rc = (lib.ivl_linear_small_m_w8_fwd(ops._p(x), wp, ops._p(scale), None, ops._p(y), M, N, K, st) if packed else
-                          lib.ivl_linear_small_m_fwd(ops._p(x), wp, None, ops._p(y), M, N, K, st))
+                    rc = plain[fmt](ops._p(x), ops._p(wt[i]), *extra, None, ops._p(y), M, N, K, st)
                 else:
-                    glu = 1 if form == "norm_glu" else 0
-                    rc = (lib.ivl_norm_linear_small_m_w8_fwd(ops._p(x), None, ops._p(nw), 1e-6, None, wp, ops._p(scale), None, ops._p(y),
-                                                             M, N, K, glu, st) if packed else
-                          lib.ivl_norm_linear_small_m_fwd(ops._p(x), None, ops._p(nw), 1e-6, None, wp, None, ops._p(y), M, N, K, glu, st))
+                    rc = normed[fmt](ops._p(x), None, ops._p(nw), 1e-6, None, ops._p(wt[i]), *extra, None, ops._p(y), M, N, K,
+                                     1 if form == "norm_glu" else 0, st)
                 _lib.check(rc)
 
             # `reps` calls in ONE captured graph per leg: from Python a call costs more than the small streams take
             reps = max(8, min(128, 2 * copies))
             graphs = {}
-            for packed in (False, True):
-                call(packed)
+            for fmt in fmts:
+                call(fmt)
                 torch.cuda.synchronize()
-                graphs[packed] = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graphs[packed]):
+                graphs[fmt] = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graphs[fmt]):
                     for _ in range(reps):
-                        call(packed)
-            t = {False: [], True: []}
-            for _ in range(args.rounds):                        # A B A B
-                for packed in (False, True, False, True):
-                    t[packed].append(timed(graphs[packed].replay, 4) / reps)
-            a, b = statistics.median(t[False]), statistics.median(t[True])
+                        call(fmt)
+            t = {fmt: [] for fmt in fmts}
+            for _ in range(args.rounds):                        # A B A B (A B C A B C)
+                for fmt in fmts + fmts:
+                    t[fmt].append(timed(graphs[fmt].replay, 4) / reps)
+            med = {fmt: statistics.median(t[fmt]) for fmt in fmts}
             del graphs
-            row[f"M{M}"] = {"bf16_us": round(1000 * a, 2), "w8_us": round(1000 * b, 2), "w8_over_bf16": round(b / a, 3),
-                            "bf16_GBs": round(R * K * 2 / (a * 1e-3) / 1e9, 1), "w8_GBs": round(R * K / (b * 1e-3) / 1e9, 1)}
+            cell = {f"{fmt}_us": round(1000 * med[fmt], 2) for fmt in fmts}
+            cell.update({f"{fmt}_over_bf16": round(med[fmt] / med["bf16"], 3) for fmt in fmts[1:]})
+            if "w4" in fmts:
+                cell["w4_over_w8"] = round(med["w4"] / med["w8"], 3)
+            cell.update({f"{fmt}_GBs": round(R * K * BYTES_PER_WEIGHT[fmt] / (med[fmt] * 1e-3) / 1e9, 1) for fmt in fmts})
+            row[f"M{M}"] = cell
         out[name] = row
         print(name, row, file=sys.stderr, flush=True)
-        del wb, wq
+        del ws
     return out
 
 
@@ -673,6 +694,69 @@ def w8_legs(args, torch, model, cfg, prompts, dev):
         del decs
     model.use_packed_weights(True)
     res["operators"] = w8_operator_legs(args, torch, cfg, dev, timed)
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+def w4_legs(args, torch, model, cfg, prompts, dev):
+    """bf16 vs e4m3 vs mxfp4: two models of the same weights, one per packed format (a captured step holds the pointers of ITS
+    packed copies); the bf16 leg is the mxfp4 model with use_packed_weights(False)"""
+    from infinitevl_amd.cache import MultiStreamCache
+    from infinitevl_amd.harness import GraphedMultiStreamDecode, InfiniteVLTextStack
+    stream = torch.cuda.current_stream()
+
+    def timed(fn, n):
+        for _ in range(4):
+            fn()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        for _ in range(n):
+            fn()
+        e1.record(stream)
+        e1.synchronize()
+        return e0.elapsed_time(e1) / n
+
+    with torch.device(dev):
+        torch.set_default_dtype(torch.bfloat16)
+        model8 = InfiniteVLTextStack(cfg)
+        torch.set_default_dtype(torch.float32)
+    model8 = model8.to(torch.bfloat16).eval().init_weights_(seed=0).fuse_().quantize_weights_(lm_head=True, fmt="e4m3")
+    model.quantize_weights_(lm_head=True, fmt="mxfp4")
+    legs = (("bf16", model, False), ("w8", model8, True), ("w4", model, True))
+    slots = [int(s) for s in args.slots.split(",")]
+    res = {"tool": "multistream_decode --w4", "layers": cfg.num_hidden_layers, "window": 4096, "steps": args.steps, "rounds": args.rounds,
+           "quantised": "q|k|v, attention o_proj, GDN in-projection, GDN o_proj, gate|up, down_proj, lm_head",
+           "legs": "bf16 = the mxfp4 model's bf16 weights; w8 = e4m3 copies; w4 = mxfp4 copies", "bar": "none asserted"}
+    for n in slots:
+        decs = {}
+        for name, m, on in legs:
+            m.use_packed_weights(on)
+            cache = MultiStreamCache(config=cfg, n_slots=n, device=dev, dtype=torch.bfloat16)
+            dec = GraphedMultiStreamDecode(m, cache)
+            for s in range(n):
+                dec.admit(s, prompts[s])
+            dec.capture()
+            decs[name] = (dec, m, on)
+        times = {k: [] for k in decs}
+        for _ in range(args.rounds):                            # A B C A B C
+            for name in ("bf16", "w8", "w4", "bf16", "w8", "w4"):
+                dec, m, on = decs[name]
+                m.use_packed_weights(on)                        # (a host flag: the step would recapture on a mismatch)
+                times[name].append(timed(dec.step, args.steps))
+        med = {k: statistics.median(v) for k, v in times.items()}
+        res[f"slots{n}"] = dict({f"{k}_ms_per_step": round(v, 4) for k, v in med.items()},
+                                w8_over_bf16=round(med["w8"] / med["bf16"], 4), w4_over_bf16=round(med["w4"] / med["bf16"], 4),
+                                w4_over_w8=round(med["w4"] / med["w8"], 4),
+                                **{f"{k}_spread_ms": [round(min(v), 4), round(max(v), 4)] for k, v in times.items()})
+        print(f"slots{n}: " + " ".join(f"{k} {v:.4f}" for k, v in med.items()) + " ms", file=sys.stderr, flush=True)
+        del decs
+    model.use_packed_weights(True)
+    del model8
+    res["operators"] = w8_operator_legs(args, torch, cfg, dev, timed, fmts=("bf16", "w8", "w4"))
     line = json.dumps(res)
     print(line)
     if args.out:
