@@ -460,6 +460,46 @@ IVL_API int ivl_gdn_out_linear_small_m_w4_fwd(const void* o_raw, const void* gat
                                       void* conv_state_q, void* conv_state_k, const void* wq, const void* sq,
                                       const void* bias, void* y, int M, int N, int K, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * PER-ROW LoRA ADAPTERS on the output of a decode projection, UNMERGED: y[m] += s_a B_a (A_a x[m]) with a = adapter_idx[m] read on
+ * the device, so that every row (decode slot) of a captured step follows its own fine-tune and the base weight -- bf16 or packed --
+ * stays what it is.  Replaces peft's bf16 lora.Linear.forward, `result + lora_B(lora_A(x)) * scaling`, which the reference only
+ * reaches merged (src/llamafactory/model/adapter.py: PeftModel.from_pretrained -> merge_and_unload), at its rounding points:
+ *     t[m,j] = bf16( sum_k A_a[j,k] x[m,k] )        fp32 accumulation (lane l of a wave: the 8-element chunks l + 64 i, i ascending,
+ *                                                     one fmaf per element from 0, then wave_sum)
+ *     d[m,n] = bf16( sum_j B_a[n,j] t[m,j] )        fp32, one fmaf per j, j ascending from 0
+ *     e[m,n] = bf16( scaling[a] * d[m,n] )          one fp32 multiply
+ *     y[m,n] = bf16( y[m,n] + e[m,n] )              one fp32 add, in place
+ *   x [M,K] bf16; y [M,N] bf16 in and out; adapter_idx int32 [M]; scaling fp32 [n_adapters] (alpha / r, or alpha / sqrt r).
+ *   SEGMENTS: a fused weight (q|k|v, the GDN q|k|v|g|a|b, gate|up) has one adapter pair per sub-projection.  Segment i < n_seg owns
+ *   the output columns [seg_col<i>, seg_col<i+1>) -- the nine fields seg_col0 .. seg_col8 are one int[9] by value, entries past
+ *   n_seg unused -- and reads t[m, i R .. i R + R), R the rank capacity of the table:
+ *     A bf16 [n_adapters, n_seg R, K] (the segments' A stacked), B bf16 [n_adapters, N, R] (row n = the B row of n's segment).
+ *   An adapter of rank r < R is stored zero-padded: zero terms add exactly, the result is the rank-r computation bit for bit.
+ *   NOT TOUCHED (no read-modify-write: -0.0 + 0.0 would flip a sign bit): every row m with adapter_idx[m] outside [0, n_adapters)
+ *   -- -1 = no adapter -- and every column in no segment (below seg_col0, from seg_col<n_seg> on).
+ *   NORM group (norm_weight != NULL): x is the raw input of the (residual add +) RMSNorm in front of the projection, and the
+ *   kernel forms xn = bf16(norm_weight * bf16(h rstd)), h = bf16(x + residual) (residual NULL: h = x) itself, with the thread ->
+ *   element mapping and summation order of ivl_add_rmsnorm_fwd / ivl_norm_linear_small_m_fwd: bit-identical rows, no norm launch.
+ *   h is not written (the base launch owns h_out).  512 <= K <= 4096.
+ *   t_ws: bf16 [4, 512] owned by the caller; afterwards t_ws[m*512 + j] = t[m,j] for j < n_seg R of every row WITH an adapter.
+ * Two launches (shrink: one wave per two rows of A and x row; expand-add: one thread per output column); no atomics, a fixed
+ * order: the same bits eager or replayed, and for a row alone or among other rows.  Everything 16-byte aligned.
+ * IVL_ERR_INVALID_ARG: NULL args, x, y, adapter_idx, A, B, scaling or t_ws; a pointer off 16 bytes; N < 1, K < 8, K % 8 != 0;
+ *   n_adapters < 1; n_seg outside 1..8; seg_col not non-decreasing within [0, N]; residual without norm_weight.
+ * IVL_ERR_UNSUPPORTED: M outside 1..4; R not 8, 16, 32 or 64; NORM with K outside [512, 4096].  Checked before any launch.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct ivl_lora_args {
+  const void* x; void* y; const int32_t* adapter_idx;
+  const void* A; const void* B; const float* scaling;
+  int M, N, K, R, n_adapters, n_seg;
+  int seg_col0, seg_col1, seg_col2, seg_col3, seg_col4, seg_col5, seg_col6, seg_col7, seg_col8;
+  /* NORM */
+  const void* residual; const void* norm_weight; float eps;
+  void* t_ws;
+} ivl_lora_args;
+IVL_API int ivl_lora_add_small_m_fwd(const ivl_lora_args* args, void* stream);
+
 /* nn.Linear for the wide projections of a prefill chunk of up to 256 rows: y[M,N] = bf16(x[M,K] W[N,K]^T + bias[N]), or with
  * glu != 0 the SwiGLU MLP head on the fused gate|up weight [2N,K] (N = I):
  *   y[M,I] = bf16( bf16(silu(bf16(x Wg^T + bg))) * bf16(x Wu^T + bu) ),  Wg = w[:I], Wu = w[I:], bias [2I] or NULL

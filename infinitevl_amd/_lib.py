@@ -1,7 +1,7 @@
 """ctypes binding of libivl_hip.so, derived from the C ABI's one declaration: include/ivl_hip.h.
 
 The header is read at import (no library needed): its `#define IVL_*` integers become module attributes, every `struct
-ivl_<x>_args` a ctypes class (`SwaArgs`, `SampleArgs`), and every `IVL_API` prototype an entry of `PROTOTYPES`, which `bind`
+ivl_<x>_args` a ctypes class (`SwaArgs`, `SampleArgs`, `LoraArgs`; all of them in `ARG_STRUCTS`), and every `IVL_API` prototype an entry of `PROTOTYPES`, which `bind`
 applies to a CDLL.
 The library is built in-tree by `__graft_entry__.build()` / `make -C infinitevl_amd/csrc`.
 There is NO fallback: if the shared object is missing, importing an operator raises.
@@ -95,10 +95,12 @@ def parse_header(text: str, structs: dict = None):
 
 if not os.path.exists(HEADER_PATH):
     raise ImportError(f"{HEADER_PATH} not found: the package is used in-tree and reads the C ABI from the header at import.")
-STRUCTS = {}                                                 # {"ivl_swa_args": SwaArgs, "ivl_sample_args": SampleArgs}
+ARG_STRUCTS = {}                                             # every `ivl_<x>_args` struct of the header: {"ivl_swa_args": SwaArgs, ...}
 with open(HEADER_PATH) as _f:
-    CONSTANTS, SwaArgs, PROTOTYPES = parse_header(_f.read(), STRUCTS)
-SampleArgs = STRUCTS["ivl_sample_args"]
+    CONSTANTS, SwaArgs, PROTOTYPES = parse_header(_f.read(), ARG_STRUCTS)
+SampleArgs, LoraArgs = ARG_STRUCTS["ivl_sample_args"], ARG_STRUCTS["ivl_lora_args"]
+# the two wide argument structs (32 fields and more) whose sizes and key offsets tests/test_header_binding_cpu.py pins as numbers
+STRUCTS = {"ivl_swa_args": SwaArgs, "ivl_sample_args": SampleArgs}
 globals().update(CONSTANTS)                                  # IVL_ABI_VERSION, IVL_BF16, ..., IVL_OK, IVL_ERR_*, IVL_GDN_*
 EXPORTED_SYMBOLS = tuple(PROTOTYPES)
 

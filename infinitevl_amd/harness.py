@@ -13,6 +13,7 @@ from __future__ import annotations
 import contextlib
 import inspect
 import math
+import re
 from dataclasses import dataclass, field, fields
 from typing import Dict, List, NamedTuple, Optional, Tuple
 
@@ -114,6 +115,7 @@ class InfiniteVLTextMLP(nn.Module):
         self._fused_w = None
         self._w8_gu = self._w8_down = None  # ops.PackedWeight of the fused gate|up weight and of down_proj (quantize_weights_)
         self._w8_on = False
+        self._lora, self._lora_layer = None, None   # ops.LoraTable with (layer, "gu") and (layer, "down") (enable_adapters)
 
     @torch.no_grad()
     def quantize_weights_(self, fmt: str = "e4m3") -> "InfiniteVLTextMLP":
@@ -137,11 +139,20 @@ class InfiniteVLTextMLP(nn.Module):
         g.data, u.data = self._fused_w[:n], self._fused_w[n:]
         return self
 
+    def lora_projections(self):
+        """as InfiniteVLSelfAttention.lora_projections"""
+        I = self.gate_proj.weight.shape[0]
+        return {(self._lora_layer, "gu"): (self._fused_w, (0, I, 2 * I), ("gate_proj", "up_proj")),
+                (self._lora_layer, "down"): (self.down_proj.weight, (0, self.down_proj.weight.shape[0]), ("down_proj",))}
+
     def forward(self, x):
         if (self._fused_w is not None and x.is_cuda and x.dtype == torch.bfloat16
                 and self.gate_proj.weight.data_ptr() == self._fused_w.data_ptr()):
             w8_gu, w8_down = ops.w8_kwargs(self._w8_gu, self._w8_on), ops.w8_kwargs(self._w8_down, self._w8_on)
-            return ops.linear(ops.linear_swiglu(x, self._fused_w, **w8_gu), self.down_proj.weight, **w8_down)
+            return ops.linear(ops.linear_swiglu(x, self._fused_w, **w8_gu, **ops.lora_kwargs(self._lora, (self._lora_layer, "gu"))),
+                              self.down_proj.weight, **w8_down, **ops.lora_kwargs(self._lora, (self._lora_layer, "down")))
+        if self._lora is not None:
+            raise RuntimeError("adapters are attached (enable_adapters): they ride on the fused bf16 projections only")
         if isinstance(x, ops.PreNorm):
             x = x.materialize()
         return self.down_proj(F.silu(self.gate_proj(x)) * self.up_proj(x))
@@ -187,6 +198,8 @@ class InfiniteVLTextStack(nn.Module):
         self._w8_lm_head = None                 # ops.PackedWeight of the tied embed_tokens.weight (quantize_weights_(lm_head=True))
         self._w8_on = False
         self._w8_fmt = None                     # the format of the packed copies: "e4m3" / "mxfp4" (quantize_weights_)
+        self._lora = None                       # ops.LoraTable of every projection (enable_adapters)
+        self._lora_names = {}                   # {"layers.3.self_attn.q_proj": (key, segment)}
 
     @torch.no_grad()
     def init_weights_(self, seed: int = 0, std: float = 0.02) -> "InfiniteVLTextStack":
@@ -255,6 +268,108 @@ class InfiniteVLTextStack(nn.Module):
             layer.self_attn._w8_on = layer.mlp._w8_on = self._w8_on
         return self
 
+    # ---- per-row LoRA adapters, unmerged ---------------------------------------------------------------------------
+    def _lora_modules(self):
+        for i, layer in enumerate(self.layers):
+            layer.mlp._lora_layer = i
+            yield layer.self_attn
+            yield layer.mlp
+
+    def enable_adapters(self, n_adapters: int, rank: int = 16) -> "InfiniteVLTextStack":
+        """Attach an ops.LoraTable for up to `n_adapters` LoRA adapters of rank <= `rank` (8, 16, 32 or 64) over every projection of
+        the text decoder -- q|k|v and o of the attention layers, q|k|v|g|a|b and o of the Gated DeltaNet layers, gate|up and down --
+        after fuse_().  The base weights, bf16 or packed, are not touched: a row's adapter is added unmerged behind each base
+        projection (ops.lora_add), chosen per row by forward(adapters=).  With the table attached and no adapter named, every row
+        keeps the bits of the model without a table.  enable_adapters(0) detaches it.  A graphed class recaptures when the
+        table is attached, detached or replaced."""
+        if n_adapters == 0:
+            self._lora, self._lora_names = None, {}
+            for m in self._lora_modules():
+                m._lora = None
+            return self
+        if any(getattr(layer.self_attn, "_fused_w", None) is None or layer.mlp._fused_w is None for layer in self.layers):
+            raise RuntimeError("enable_adapters: call fuse_() first (adapters ride on the fused projections)")
+        p_ = next(self.parameters())
+        if p_.dtype != torch.bfloat16:
+            raise RuntimeError(f"enable_adapters: a bf16 model is needed; got {p_.dtype}")
+        table = ops.LoraTable(n_adapters, rank, p_.device)
+        names = {}
+        for m in self._lora_modules():
+            sub = "mlp" if isinstance(m, InfiniteVLTextMLP) else "self_attn"
+            for key, (w, cols, mods) in m.lora_projections().items():
+                table.register(key, w.shape[0], w.shape[1], cols)
+                for seg, mod in enumerate(mods):
+                    names[f"layers.{key[0]}.{sub}.{mod}"] = (key, seg)
+        for m in self._lora_modules():
+            m._lora = table
+        self._lora, self._lora_names = table, names
+        return self
+
+    def _need_lora(self, who: str) -> "ops.LoraTable":
+        if self._lora is None:
+            raise RuntimeError(f"{who}: call enable_adapters(n_adapters, rank) first")
+        return self._lora
+
+    @torch.no_grad()
+    def load_adapter(self, state_dict, alpha: float, rank: int, use_rslora: bool = False) -> "ops.LoraHandle":
+        """Load a LoRA adapter from peft's tensor names (`base_model.model.` + the checkpoint's text prefix +
+        `layers.{i}.self_attn.q_proj.lora_A.weight` [r, K] / `.lora_B.weight` [N, r]; an adapter name between `lora_A` and `weight`
+        is accepted) at a free index of the table.  scaling = alpha / rank, or alpha / sqrt(rank) with use_rslora (peft's
+        LoraConfig).  Keys outside the text decoder's projections -- the vision tower, lm_head, embeddings -- are ignored and
+        listed in the handle's `skipped`."""
+        table = self._need_lora("load_adapter")
+        if isinstance(rank, bool) or not isinstance(rank, int) or not 1 <= rank <= table.R:
+            raise ValueError(f"load_adapter: rank must be an int in [1, {table.R}] (the table's rank capacity); got {rank!r}")
+        pairs, skipped = {}, []
+        for name, t in state_dict.items():
+            m = re.fullmatch(r"(?:base_model\.model\.)?(.*)\.lora_([AB])(?:\.[^.]+)?\.weight", name)
+            short = None
+            if m is not None and not m.group(1).startswith(("visual.", "model.visual.")):
+                for pre in _TEXT_PREFIXES + ("",):
+                    if m.group(1).startswith(pre) and m.group(1)[len(pre):] in self._lora_names:
+                        short = m.group(1)[len(pre):]
+                        break
+            if short is None:
+                skipped.append(name)
+                continue
+            pairs.setdefault(short, {})[m.group(2)] = t
+        tensors = {}
+        for short, ab in pairs.items():
+            if set(ab) != {"A", "B"}:
+                raise KeyError(f"load_adapter: {short} has lora_{'A' if 'A' in ab else 'B'} only")
+            if ab["A"].shape[0] != rank or ab["B"].shape[-1] != rank:
+                raise ValueError(f"load_adapter: {short}: lora_A {tuple(ab['A'].shape)} / lora_B {tuple(ab['B'].shape)} are not of "
+                                 f"rank {rank} (per-module rank patterns are not supported)")
+            key, seg = self._lora_names[short]
+            tensors.setdefault(key, [None] * table.proj[key].n_seg)[seg] = (ab["A"], ab["B"])
+        if not tensors:
+            raise KeyError("load_adapter: no lora_A / lora_B pair of a text projection in the state dict")
+        scaling = float(alpha) / (math.sqrt(rank) if use_rslora else rank)
+        return table.load(tensors, scaling, skipped=tuple(skipped))
+
+    def unload_adapter(self, handle: "ops.LoraHandle") -> None:
+        self._need_lora("unload_adapter").unload(handle)
+
+    @torch.no_grad()
+    def merge_adapter_(self, handle: "ops.LoraHandle") -> "InfiniteVLTextStack":
+        """peft's merge (merge_and_unload of the reference's model/adapter.py) for comparison: W += bf16((B @ A) * scaling) on
+        every targeted projection, IN PLACE.  This writes the weights: packed copies go stale (the next call raises) -- the merged
+        model is a bf16 model."""
+        table = self._need_lora("merge_adapter_")
+        a, R = table.index_of(handle), table.R
+        by_key = {}
+        for m in self._lora_modules():
+            for key, (w, cols, _) in m.lora_projections().items():
+                by_key[key] = w
+        for key, p in table.proj.items():
+            w = by_key[key]
+            for i in range(p.n_seg):
+                c0, c1 = p.seg_cols[i], p.seg_cols[i + 1]
+                A, B = p.A[a, i * R:i * R + handle.rank], p.B[a, c0:c1, :handle.rank]
+                if c1 > c0 and bool(B.any()):
+                    w[c0:c1] += (B @ A) * handle.scaling
+        return self
+
     def set_mma_dtype(self, mma_dtype) -> "InfiniteVLTextStack":
         """Operand format of the mixers' MFMA products: None / "bf16" = the reference's precision; "fp8_e4m3" =
         BASELINE.json configs[4] (e4m3 operands in the Gated DeltaNet chunk scan and the SWA decode step; fp32
@@ -273,9 +388,29 @@ class InfiniteVLTextStack(nn.Module):
     def forward(self, input_ids: Optional[torch.Tensor] = None, inputs_embeds: Optional[torch.Tensor] = None,
                 position_ids: Optional[torch.Tensor] = None, past_key_values: Optional[StaticCachePrealloc] = None,
                 cache_position: Optional[torch.Tensor] = None, logits_to_keep: int = 1,
-                layer_hooks=None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+                layer_hooks=None, adapters=None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
         """layer_hooks = (before_mixer(i), after_mixer(i)) or None: called around the cache-touching part of
-        decoder layer i (used by dist.sequence_parallel_prefill to receive / forward that layer's state)."""
+        decoder layer i (used by dist.sequence_parallel_prefill to receive / forward that layer's state).
+        adapters (after enable_adapters): None = the base model; a handle of load_adapter = that adapter for every row; an int32
+        device tensor [B] = one adapter index per batch row, read on the device (-1 = none; calls of more than 4 rows read it on
+        the host)."""
+        if adapters is not None:
+            table = self._need_lora("forward(adapters=)")
+            if isinstance(adapters, torch.Tensor):
+                B_ = (inputs_embeds if inputs_embeds is not None else input_ids).shape[0]
+                if adapters.dtype != torch.int32 or tuple(adapters.shape) != (B_,):
+                    raise ValueError(f"forward: adapters must be an int32 tensor [{B_}]; got {adapters.dtype} {tuple(adapters.shape)}")
+            else:
+                table.index_of(adapters)
+        if self._lora is not None:
+            self._lora.rows = adapters
+            try:
+                return self._forward(input_ids, inputs_embeds, position_ids, past_key_values, cache_position, logits_to_keep, layer_hooks)
+            finally:
+                self._lora.rows = None
+        return self._forward(input_ids, inputs_embeds, position_ids, past_key_values, cache_position, logits_to_keep, layer_hooks)
+
+    def _forward(self, input_ids, inputs_embeds, position_ids, past_key_values, cache_position, logits_to_keep, layer_hooks):
         if inputs_embeds is None:
             inputs_embeds = self.embed_tokens(input_ids)
         B, T, _ = inputs_embeds.shape
@@ -379,6 +514,35 @@ def load_reference_checkpoint(stack: "InfiniteVLTextStack", path: str) -> List[s
     return skipped
 
 
+@torch.no_grad()
+def load_peft_adapter(model: "InfiniteVLTextStack", path: str) -> "ops.LoraHandle":
+    """Load a peft LoRA adapter directory -- adapter_config.json + adapter_model.safetensors, what the reference's
+    `adapter_name_or_path` names (src/llamafactory/model/adapter.py) -- into the model's adapter table (enable_adapters first) and
+    return its handle.  Refused: DoRA, bias terms, modules_to_save, per-module rank / alpha patterns, a rank above the table's."""
+    import json
+    from safetensors import safe_open
+    with open(_os.path.join(path, "adapter_config.json")) as f:
+        cfg = json.load(f)
+    if cfg.get("peft_type", "LORA") != "LORA":
+        raise ValueError(f"load_peft_adapter: peft_type {cfg.get('peft_type')!r} (LoRA only)")
+    if cfg.get("use_dora"):
+        raise ValueError("load_peft_adapter: use_dora is not supported")
+    if cfg.get("bias", "none") != "none":
+        raise ValueError(f"load_peft_adapter: bias = {cfg['bias']!r} is not supported (bias must be 'none')")
+    for k in ("modules_to_save", "rank_pattern", "alpha_pattern"):
+        if cfg.get(k):
+            raise ValueError(f"load_peft_adapter: {k} = {cfg[k]!r} is not supported")
+    r = cfg.get("r")
+    table = model._need_lora("load_peft_adapter")
+    if isinstance(r, bool) or not isinstance(r, int) or r < 1 or r > table.R:
+        raise ValueError(f"load_peft_adapter: r = {r!r} for a table of rank capacity {table.R} (enable_adapters(n, rank >= r))")
+    tensors = {}
+    with safe_open(_os.path.join(path, "adapter_model.safetensors"), framework="pt", device="cpu") as f:
+        for k in f.keys():
+            tensors[k] = f.get_tensor(k)
+    return model.load_adapter(tensors, alpha=float(cfg.get("lora_alpha", r)), rank=r, use_rslora=bool(cfg.get("use_rslora", False)))
+
+
 def clone_inference_cache(cache: StaticCachePrealloc) -> StaticCachePrealloc:
     """demo:111-160."""
     return cache.clone()
@@ -391,6 +555,8 @@ class _Graphed:
     _captured_controlled = False
     _captured_w8 = False
     _captured_fmt = None
+    _captured_lora = None
+    adapter_ids: Optional[torch.Tensor] = None          # int32 [rows] on the device: one adapter index per row (-1 = none)
 
     def _capture(self, tensors: List[torch.Tensor], scope=None):
         """Captures one self._run() into self.graph and returns what it returned.  The cache, `tensors` and the sampler's state
@@ -415,7 +581,24 @@ class _Graphed:
             self.sampler.load_state(saved_smp)          # the warm-up and the capture itself made draws
             self._captured_controlled = self.sampler.controlled
         self._captured_w8, self._captured_fmt = self._w8_on(), self._w8_fmt()
+        self._captured_lora = self._lora_sig()
         return out
+
+    def _lora_sig(self):
+        """what a capture depends on of the model's adapter table: which table it is, its rank capacity and size"""
+        t = getattr(self.model, "_lora", None)
+        return None if t is None else (id(t), t.R, t.n_adapters)
+
+    def _adapters(self):
+        """the `adapters=` of the captured forward: the per-row ids while a table is attached"""
+        return {"adapters": self.adapter_ids} if getattr(self.model, "_lora", None) is not None and self.adapter_ids is not None else {}
+
+    def _adapter_index(self, who: str, adapter) -> int:
+        if adapter is None:
+            return -1
+        if getattr(self.model, "_lora", None) is None:
+            raise ValueError(f"{who}: an adapter needs a model with enable_adapters()")
+        return self.model._lora.index_of(adapter)
 
     def _w8_on(self) -> bool:
         return bool(getattr(self.model, "_w8_on", False))
@@ -427,14 +610,16 @@ class _Graphed:
     def _stale(self) -> bool:
         """No graph yet, or one captured before the sampler switched to the controlled launch or before the model switched
         between its bf16 weights and their packed copies (use_packed_weights) or between the formats of the packed copies
-        (quantize_weights_(fmt=): the captured launches are those of one format)."""
+        (quantize_weights_(fmt=): the captured launches are those of one format), or before the adapter table was attached,
+        detached or replaced (enable_adapters)."""
         return (self.graph is None or (self.sampler is not None and self.sampler.controlled != self._captured_controlled)
-                or self._w8_on() != self._captured_w8 or self._w8_fmt() != self._captured_fmt)
+                or self._w8_on() != self._captured_w8 or self._w8_fmt() != self._captured_fmt
+                or self._lora_sig() != self._captured_lora)
 
     def _run(self):
         """The T = 1 step: forward of every row's token, its next token, positions + 1."""
         _, lg = self.model(input_ids=self.token, position_ids=self.position_ids, past_key_values=self.cache,
-                           logits_to_keep=1)
+                           logits_to_keep=1, **self._adapters())
         self._next_token(lg[:, -1])
         self.position_ids.add_(1)
         return lg
@@ -889,7 +1074,9 @@ class GraphedDecode(_Graphed):
     Sampler of batch_size rows) the arg-max and the copy are ONE ops.sample_tokens launch on the sampler's table."""
 
     def __init__(self, model: InfiniteVLTextStack, cache: StaticCachePrealloc, batch_size: int, warmup: int = 2,
-                 sampler: Optional["Sampler"] = None):
+                 sampler: Optional["Sampler"] = None, adapters=None):
+        """adapters: None, a handle of model.load_adapter for every row, or a list of one handle / None per row; the ids live in
+        self.adapter_ids (int32 [batch_size] on the device) and may be rewritten between replays."""
         p_ = next(model.parameters())
         if sampler is not None and sampler.n_rows != batch_size:
             raise ValueError(f"GraphedDecode: the sampler has {sampler.n_rows} rows for batch_size {batch_size}")
@@ -900,6 +1087,10 @@ class GraphedDecode(_Graphed):
         self.logits = None
         self.graph: Optional[torch.cuda.CUDAGraph] = None
         self._warmup = warmup
+        per_row = list(adapters) if isinstance(adapters, list) else [adapters] * batch_size
+        if len(per_row) != batch_size:
+            raise ValueError(f"GraphedDecode: {len(per_row)} adapters for batch_size {batch_size}")
+        self.adapter_ids = torch.tensor([self._adapter_index("GraphedDecode", a) for a in per_row], dtype=torch.int32, device=p_.device)
 
     def capture(self) -> None:
         self.cache.ensure_started()
@@ -943,25 +1134,39 @@ class GraphedMultiStreamDecode(_Graphed):
         self._warmup = warmup
         self._live = set()                               # slots between admit and release
         self._fork_plan = None                           # built at the first fork
+        self.adapter_ids = torch.full((self.S,), -1, dtype=torch.int32, device=p_.device)
+        self._slot_adapter = [None] * self.S             # the handles behind adapter_ids (the prefill calls take them)
 
     def capture(self) -> None:
         """Warm up and capture; every slot's ring, state, position and token are restored afterwards."""
         self.logits = self._capture([self.position_ids, self.token])
 
+    def set_adapter(self, slot: int, adapter) -> None:
+        """The slot decodes under `adapter` (a handle of model.load_adapter; None = the base model) from the next step on: one
+        write to adapter_ids between replays, never a recapture."""
+        slot = self._slots("set_adapter", [slot])[0]
+        self.adapter_ids[slot] = self._adapter_index("set_adapter", adapter)
+        self._slot_adapter[slot] = adapter
+
+    def _prefill_adapters(self, slot: int) -> dict:
+        return {"adapters": self._slot_adapter[slot]} if self._slot_adapter[slot] is not None else {}
+
     @torch.no_grad()
     def admit(self, slot: int, inputs_embeds: torch.Tensor, position_ids: Optional[torch.Tensor] = None,
-              sampling: Optional[dict] = None, prompt_ids: Optional[torch.Tensor] = None, grammar=None) -> torch.Tensor:
+              sampling: Optional[dict] = None, prompt_ids: Optional[torch.Tensor] = None, grammar=None, adapter=None) -> torch.Tensor:
         """Start a stream in `slot` with a prompt inputs_embeds [1,T,hidden] (M-RoPE position_ids [3,1,T]; default: text
         positions 0..T-1).  Its first generated token is written to token[slot] and returned.  `sampling`: the keyword
         arguments of Sampler.set for this stream (needs a sampler), applied before that first token is drawn.  `prompt_ids`
         (int64 [T] or [1,T]): the prompt's tokens, marked as seen for the repetition penalty after the row is set and before the
         first token is drawn; that token goes through the same controlled launch as every later one, so it is counted, logged
         and may already end the stream.  `grammar` (a handle of Sampler.load_grammar): the stream starts in the grammar's start
-        state, set after the row's parameters and before the first draw, so the first token is constrained too."""
+        state, set after the row's parameters and before the first draw, so the first token is constrained too.  `adapter`: the stream's LoRA adapter
+        (set_adapter); the prompt is prefilled under it."""
         if sampling is not None and self.sampler is None:
             raise ValueError("admit: sampling parameters need a GraphedMultiStreamDecode built with a sampler")
         self._check_grammar("admit", grammar)
         T = self._check_prompt("admit", inputs_embeds, position_ids, prompt_ids)
+        self.set_adapter(slot, adapter)
         if position_ids is None:
             position_ids = _text_positions(T, inputs_embeds.device)
         if sampling is not None:
@@ -986,7 +1191,7 @@ class GraphedMultiStreamDecode(_Graphed):
         for a in range(0, T, self.PREFILL_CHUNK):
             b = min(T, a + self.PREFILL_CHUNK)
             _, lg = self.model(inputs_embeds=inputs_embeds[:, a:b], position_ids=position_ids[:, :, a:b],
-                               past_key_values=view, logits_to_keep=1)
+                               past_key_values=view, logits_to_keep=1, **self._prefill_adapters(slot))
         return lg
 
     def _draw(self, slot: int, lg: torch.Tensor) -> None:
@@ -1040,13 +1245,16 @@ class GraphedMultiStreamDecode(_Graphed):
             self._live.add(d)
 
     @torch.no_grad()
-    def fork(self, src: int, dsts, sampling=None) -> None:
+    def fork(self, src: int, dsts, sampling=None, adapter="src") -> None:
         """Slots `dsts` become copies of the live slot `src` -- cache rows, pending token, M-RoPE positions and sampler rows in
         one launch -- and live: the branch of the reference's streaming demo (demo:357-398) on the serving path.  `sampling`:
         one dict per destination as in Sampler.fork (temperature / top_k / top_p / seed; the copied state is kept, a seed
-        starts an independent random stream).  In-place writes only, between replays: never a recapture."""
+        starts an independent random stream).  The destinations decode under the source's adapter, or under `adapter` (a handle,
+        or None = the base model) when it is given.  In-place writes only, between replays: never a recapture."""
         src = self._slots("fork", [src])[0]
         dsts = self._slots("fork", dsts)
+        if not isinstance(adapter, str):
+            self._adapter_index("fork", adapter)
         if src in dsts:
             raise ValueError(f"fork: the destination slots {dsts} contain the source slot {src}")
         if src not in self._live:
@@ -1057,6 +1265,8 @@ class GraphedMultiStreamDecode(_Graphed):
         if self.sampler is not None:
             _, _, overrides = self.sampler._check_fork("fork", src, dsts, sampling)
         self._fork_rows(src, dsts)
+        for d in dsts:
+            self.set_adapter(d, self._slot_adapter[src] if isinstance(adapter, str) else adapter)
         if self.sampler is not None:
             self.sampler._forked(src, dsts, overrides)
 
@@ -1102,14 +1312,15 @@ class GraphedMultiStreamDecode(_Graphed):
         if position_ids is None:
             position_ids = self.position_ids[:, slot:slot + 1] + torch.arange(T, device=self.position_ids.device, dtype=torch.int64)
         res = score_sequence(self.model, self.cache.slot_view(slot), inputs_embeds=inputs_embeds, labels=labels,
-                             position_ids=position_ids, chunk=self.PREFILL_CHUNK, next_label=next_label)
+                             position_ids=position_ids, chunk=self.PREFILL_CHUNK, next_label=next_label,
+                             adapters=self._slot_adapter[slot])
         self.token[slot].zero_()
         self.position_ids[:, slot].copy_(position_ids.max() + 1)
         return res
 
     @torch.no_grad()
     def admit_n(self, slots, inputs_embeds: torch.Tensor, position_ids: Optional[torch.Tensor] = None,
-                sampling=None, prompt_ids: Optional[torch.Tensor] = None, grammar=None) -> torch.Tensor:
+                sampling=None, prompt_ids: Optional[torch.Tensor] = None, grammar=None, adapter=None) -> torch.Tensor:
         """Several answers to one prompt (num_return_sequences of the reference's api/chat.py:164): the prompt is prefilled
         ONCE, into slots[0]; its cache and sampler rows are forked to slots[1:] before any token is drawn; then every slot
         draws its own first token from the same logits, in its own sampler row.  `sampling`: one dict of Sampler.set
@@ -1120,6 +1331,8 @@ class GraphedMultiStreamDecode(_Graphed):
         if sampling is not None and self.sampler is None:
             raise ValueError("admit_n: sampling parameters need a GraphedMultiStreamDecode built with a sampler")
         T = self._check_prompt("admit_n", inputs_embeds, position_ids, prompt_ids)
+        for s_ in slots:                                 # (every answer decodes under `adapter`; the prompt is prefilled under it)
+            self.set_adapter(s_, adapter)
         if position_ids is None:
             position_ids = _text_positions(T, inputs_embeds.device)
         checked = None
@@ -1151,7 +1364,7 @@ class GraphedMultiStreamDecode(_Graphed):
 
     @torch.no_grad()
     def load(self, slots, cache: StaticCachePrealloc, row: int = 0, next_position: Optional[int] = None, sampling=None,
-             grammar=None) -> None:
+             grammar=None, adapter=None) -> None:
         """The demo's branch (demo:363-365) on the serving path: the state of row `row` of an external cache -- the B = 1
         StaticCachePrealloc of a running video stream -- goes into `slots` in one launch, and they become live.  The source is
         only read, so questions never pollute the video's history.  Each slot's three M-RoPE positions are set to
@@ -1176,6 +1389,7 @@ class GraphedMultiStreamDecode(_Graphed):
                 self.sampler.set_grammar(s, grammar)
             self.token[s].zero_()
             self.position_ids[:, s].fill_(next_position)
+            self.set_adapter(s, adapter)                 # (the extend that follows runs under it)
             self._live.add(s)
 
     def release(self, slot: int) -> None:
@@ -1186,6 +1400,8 @@ class GraphedMultiStreamDecode(_Graphed):
             self.sampler.reset(slot)
         self.token[slot].zero_()
         self.position_ids[:, slot].zero_()
+        self.adapter_ids[slot] = -1
+        self._slot_adapter[slot] = None
 
     def step(self, graph: bool = True) -> torch.Tensor:
         """One decode step of every slot; the new tokens are left in self.token [S,1] (device).  graph=False runs the
@@ -1308,7 +1524,8 @@ class GraphedBeamDecode(GraphedMultiStreamDecode):
     @torch.no_grad()
     def admit(self, group: int, inputs_embeds: torch.Tensor, position_ids: Optional[torch.Tensor] = None,
               prompt_ids: Optional[torch.Tensor] = None, *, max_new_tokens: int, stop_token_ids=(),
-              repetition_penalty: float = 1.0, length_penalty: float = 1.0, early_stopping: bool = False) -> torch.Tensor:
+              repetition_penalty: float = 1.0, length_penalty: float = 1.0, early_stopping: bool = False,
+              adapter=None) -> torch.Tensor:
         """Start a beam search in `group` with a prompt inputs_embeds [1,T,hidden].  The prompt is prefilled ONCE, into the
         group's first slot; then score, select, gather and commit run on this group alone: the beams' sums start as
         [0, -inf, ...], so every parent is beam 0 and the gather is the fork.  Returns the group's first tokens token[g B:(g+1) B].
@@ -1336,6 +1553,7 @@ class GraphedBeamDecode(GraphedMultiStreamDecode):
         B, s0 = self.B, g * self.B
         for s in range(s0, s0 + B):
             self.sampler.set(s, repetition_penalty=checked["repetition_penalty"])
+            GraphedMultiStreamDecode.set_adapter(self, s, adapter)      # all beams of the group: the in-group gather moves no id
         if B > 1:
             self.sampler.cum_logprob[s0 + 1:s0 + B] = -math.inf
         if prompt_ids is not None:
@@ -1391,7 +1609,7 @@ class GraphedBeamDecode(GraphedMultiStreamDecode):
     def _per_slot(self, *a, **k):
         raise ValueError("GraphedBeamDecode: a slot of a beam group is not a stream of its own (admit / release a group)")
 
-    fork = extend = score = admit_n = load = _per_slot
+    fork = extend = score = admit_n = load = set_adapter = _per_slot
 
 
 IGNORE_INDEX = -100
@@ -1435,7 +1653,7 @@ class ScoreResult(NamedTuple):
 def score_sequence(model: InfiniteVLTextStack, cache: StaticCachePrealloc, *, input_ids: Optional[torch.Tensor] = None,
                    inputs_embeds: Optional[torch.Tensor] = None, labels: torch.Tensor,
                    position_ids: Optional[torch.Tensor] = None, chunk: int = 4096,
-                   next_label: Optional[int] = None) -> ScoreResult:
+                   next_label: Optional[int] = None, adapters=None) -> ScoreResult:
     """Teacher-forced scoring of a sequence that continues whatever `cache` already holds: the log-probability of every label
     under the model, position by position, in constant memory -- perplexity at any depth of a stream, HF's `labels=` loss,
     eval_loss / eval_accuracy, the likelihood of a candidate answer, `echo` + `logprobs`.
@@ -1465,7 +1683,7 @@ def score_sequence(model: InfiniteVLTextStack, cache: StaticCachePrealloc, *, in
         h, _ = model(input_ids=None if input_ids is None else input_ids[:, a:b],
                      inputs_embeds=None if inputs_embeds is None else inputs_embeds[:, a:b],
                      position_ids=None if position_ids is None else position_ids[:, :, a:b],
-                     past_key_values=cache, logits_to_keep=0)
+                     past_key_values=cache, logits_to_keep=0, **({} if adapters is None else {"adapters": adapters}))
         lp, t1 = ops.linear_logprob(h.contiguous(), weight, tg[:, a:b].contiguous(), top1=True)
         logprobs[:, a:b] = lp
         top1[:, a:b] = t1

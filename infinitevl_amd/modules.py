@@ -79,6 +79,7 @@ class InfiniteVLSelfAttention(nn.Module):
         self._fused_w = self._fused_b = None
         self._w8_qkv = self._w8_o = None    # ops.PackedWeight of the fused q|k|v weight and of o_proj (quantize_weights_)
         self._w8_on = False
+        self._lora = None                   # ops.LoraTable with this layer's (layer_idx, "qkv") and (layer_idx, "o") (enable_adapters)
         self.mma_dtype = None           # None = bf16 operands; "fp8_e4m3": single-token decode products on e4m3 (configs[4])
 
     @torch.no_grad()
@@ -107,6 +108,8 @@ class InfiniteVLSelfAttention(nn.Module):
                 output_attentions: bool = False, use_cache: bool = False,
                 cache_position: Optional[torch.LongTensor] = None,
                 position_embeddings: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, **kwargs):
+        if self._lora is not None and not self._fused_ok(hidden_states):
+            raise RuntimeError("adapters are attached (enable_adapters): they ride on the fused bf16 projections only")
         if isinstance(hidden_states, ops.PreNorm) and not self._fused_ok(hidden_states):
             hidden_states = hidden_states.materialize()        # (a not-yet-launched input norm: only the fused q|k|v GEMV runs it)
         bsz, q_len, _ = hidden_states.size()
@@ -122,7 +125,8 @@ class InfiniteVLSelfAttention(nn.Module):
                      and not (self.mma_dtype is not None and q_len * self.num_key_value_groups <= 64))
         if self._fused_ok(hidden_states):
             nq, nkv = self.num_heads * self.head_dim, self.num_key_value_heads * self.head_dim
-            qkv = ops.linear(hidden_states, self._fused_w, self._fused_b, **ops.w8_kwargs(self._w8_qkv, self._w8_on))  # [B,T,nq+2nkv]
+            qkv = ops.linear(hidden_states, self._fused_w, self._fused_b, **ops.w8_kwargs(self._w8_qkv, self._w8_on),
+                             **ops.lora_kwargs(self._lora, (self.layer_idx, "qkv")))                                  # [B,T,nq+2nkv]
             q = qkv[..., :nq].unflatten(-1, (self.num_heads, self.head_dim))
             k = qkv[..., nq:nq + nkv].unflatten(-1, (self.num_key_value_heads, self.head_dim))
             v = qkv[..., nq + nkv:].unflatten(-1, (self.num_key_value_heads, self.head_dim))
@@ -147,7 +151,8 @@ class InfiniteVLSelfAttention(nn.Module):
             attn, _ = ops.swa_attention_interface(self, q.transpose(1, 2), fk, fv, None, scaling=self.scaling,
                                                   sliding_window=self.sliding_window)
         attn = attn.reshape(bsz, q_len, -1)
-        return ops.linear(attn, self.o_proj.weight, self.o_proj.bias, **ops.w8_kwargs(self._w8_o, self._w8_on)), None
+        return ops.linear(attn, self.o_proj.weight, self.o_proj.bias, **ops.w8_kwargs(self._w8_o, self._w8_on),
+                          **ops.lora_kwargs(self._lora, (self.layer_idx, "o"))), None
 
     @torch.no_grad()
     def quantize_weights_(self, fmt: str = "e4m3") -> "InfiniteVLSelfAttention":
@@ -162,6 +167,12 @@ class InfiniteVLSelfAttention(nn.Module):
         if self._fused_w is None:
             raise RuntimeError("quantize_weights_: call fuse_() first")
         return (self._fused_w, self.o_proj.weight)
+
+    def lora_projections(self):
+        """{key: (weight, segment borders, peft module names of the segments)} of the projections an adapter may target"""
+        nq, nkv = self.num_heads * self.head_dim, self.num_key_value_heads * self.head_dim
+        return {(self.layer_idx, "qkv"): (self._fused_w, (0, nq, nq + nkv, nq + 2 * nkv), ("q_proj", "k_proj", "v_proj")),
+                (self.layer_idx, "o"): (self.o_proj.weight, (0, self.o_proj.weight.shape[0]), ("o_proj",))}
 
 
 class GatedDeltaNet(nn.Module):
@@ -226,6 +237,7 @@ class GatedDeltaNet(nn.Module):
         self._gate32 = None
         self._w8_in = self._w8_o = None     # ops.PackedWeight of the fused in-projection and of o_proj (quantize_weights_)
         self._w8_on = False
+        self._lora = None                   # ops.LoraTable with this layer's (layer_idx, "in") and (layer_idx, "o") (enable_adapters)
         self.mma_dtype = None           # None = the reference's bf16 operands; "fp8_e4m3" = BASELINE.json configs[4]
 
     @torch.no_grad()
@@ -266,6 +278,12 @@ class GatedDeltaNet(nn.Module):
             raise RuntimeError("quantize_weights_: call fuse_() first (the Gated DeltaNet needs use_gate)")
         return (self._fused_w, self.o_proj.weight)
 
+    def lora_projections(self):
+        """as InfiniteVLSelfAttention.lora_projections; the padding rows behind b_proj belong to no segment"""
+        cols = list(self._fused_cols) + [self._fused_cols[-1] + self.b_proj.weight.shape[0]]
+        return {(self.layer_idx, "in"): (self._fused_w, tuple(cols), ("q_proj", "k_proj", "v_proj", "g_proj", "a_proj", "b_proj")),
+                (self.layer_idx, "o"): (self.o_proj.weight, (0, self.o_proj.weight.shape[0]), ("o_proj",))}
+
     def _gate_params32(self):
         """fp32 copies of A_log / dt_bias for the gate math (std:1294 upcasts them per call); cached and
         refreshed whenever the parameters are modified in place (e.g. load_state_dict after fuse_)."""
@@ -288,7 +306,8 @@ class GatedDeltaNet(nn.Module):
         Dq, Dk, Dv = H * K, self.key_dim, self.value_dim
         cq, ck, cv, cg, ca, cb = self._fused_cols
         w8_in, w8_o = ops.w8_kwargs(self._w8_in, self._w8_on), ops.w8_kwargs(self._w8_o, self._w8_on)
-        proj = ops.linear(hidden_states, self._fused_w, **w8_in)                      # [B,T,ld]
+        lora_o = ops.lora_kwargs(self._lora, (self.layer_idx, "o"))
+        proj = ops.linear(hidden_states, self._fused_w, **w8_in, **ops.lora_kwargs(self._lora, (self.layer_idx, "in")))   # [B,T,ld]
         ld = proj.shape[-1]
         prev = (None, None, None)
         h0 = None
@@ -305,7 +324,8 @@ class GatedDeltaNet(nn.Module):
         if (T == 1 and layer is not None and prev[0] is not None and h0 is not None and Dk == Dq
                 and h0.data_ptr() == layer.recurrent_state.data_ptr() and K == 128 and V == 256):
             ow, ob = self.o_proj.weight, self.o_proj.bias
-            if (ops._SPLIT_DECODE and B <= 4 and 2 <= H <= 16 and ow.dtype == torch.bfloat16 and ow.is_contiguous() and cg % 4 == 0
+            # (with adapters the o_proj output must exist before lora_add: the one-launch step + ops.linear, bit-equal by the header)
+            if (ops._SPLIT_DECODE and self._lora is None and B <= 4 and 2 <= H <= 16 and ow.dtype == torch.bfloat16 and ow.is_contiguous() and cg % 4 == 0
                     and ld % 4 == 0 and (ob is None or (ob.dtype == torch.bfloat16 and ob.is_contiguous()))):
                 # decode step on 64 workgroups (sequence x head x column quarter); the gated norm and the q / k conv-state shift ride
                 # in the o_proj launch: the same two launches, 4 x the memory parallelism for the 2 MB of state (bit-identical)
@@ -324,7 +344,7 @@ class GatedDeltaNet(nn.Module):
             past_key_values.update(layer_idx=self.layer_idx, key_states=None, value_states=None, conv_state=outs,
                                    recurrent_state=layer.recurrent_state,
                                    cache_kwargs={"op": "set", "delta_len": T, "cache_position": cache_position})
-            return ops.linear(o, self.o_proj.weight, self.o_proj.bias, **w8_o), None
+            return ops.linear(o, self.o_proj.weight, self.o_proj.bias, **w8_o, **lora_o), None
         convs = (self.q_conv1d.weight, self.k_conv1d.weight, self.v_conv1d.weight)
         if mode == "chunk" and Dk == Dq and K == 128 and V == 256 and convs[0].shape[-1] == 4:
             # convs + gates inside the chunk kernel's pre-pass: q / k / v / g / beta never reach HBM, one launch less
@@ -343,7 +363,7 @@ class GatedDeltaNet(nn.Module):
                                    recurrent_state=layer.recurrent_state,
                                    cache_kwargs={"op": "set", "delta_len": T, "cache_position": cache_position})
         o = ops.rmsnorm_swish_gate_strided(o, proj[..., cg:], ld, w, self.norm_eps)
-        return ops.linear(o.reshape(B, T, -1), self.o_proj.weight, self.o_proj.bias, **w8_o), None
+        return ops.linear(o.reshape(B, T, -1), self.o_proj.weight, self.o_proj.bias, **w8_o, **lora_o), None
 
     def forward(self, hidden_states: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
                 past_key_values=None, cache_position: Optional[torch.LongTensor] = None, **kwargs):
@@ -356,6 +376,8 @@ class GatedDeltaNet(nn.Module):
         layer = past_key_values.layers[self.layer_idx] if past_key_values is not None else None
         if self._fused_ok(hidden_states, layer):
             return self._forward_fused(hidden_states, past_key_values, layer, cache_position, mode)
+        if self._lora is not None:
+            raise RuntimeError("adapters are attached (enable_adapters): they ride on the fused bf16 projections only")
         if isinstance(hidden_states, ops.PreNorm):
             hidden_states = hidden_states.materialize()
         use_cache = past_key_values is not None

@@ -1184,12 +1184,17 @@ def _linear_swiglu_m256(x: torch.Tensor, w_gate_up: torch.Tensor, rows: int, I: 
     return y
 
 
-def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, w8: Optional[PackedWeight] = None) -> torch.Tensor:
+def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, w8: Optional[PackedWeight] = None,
+           lora=None) -> torch.Tensor:
     """nn.Linear forward.  A single-token decode step (<= 4 rows) is a pure weight stream and goes through
     ivl_linear_small_m_fwd; longer calls are stock library GEMMs (hipBLASLt / rocBLAS through torch), which
     SURVEY.md 8(d) keeps outside the hot path.  w8: the packed copy of `weight` (which then holds W'), e4m3 or mxfp4 -- the call
     dispatches on its format: the weight stream reads it in place of the bf16 weight -- the same bits, a half or a quarter of the
-    bytes; every other path reads `weight` as ever."""
+    bytes; every other path reads `weight` as ever.  lora: (LoraTable, key, rows) -- the base call as without it, then lora_add on
+    its output (the NORM form reads the PreNorm's x / residual)."""
+    if lora is not None:
+        y = linear(x, weight, bias, w8=w8)
+        return lora_add(y if y.is_contiguous() else y.contiguous(), x, *lora)
     if w8 is not None:
         w8.check(weight)
     if isinstance(x, PreNorm):
@@ -1216,10 +1221,14 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] =
     return torch.nn.functional.linear(x, weight, bias)
 
 
-def linear_swiglu(x: torch.Tensor, w_gate_up: torch.Tensor, w8: Optional[PackedWeight] = None) -> torch.Tensor:
+def linear_swiglu(x: torch.Tensor, w_gate_up: torch.Tensor, w8: Optional[PackedWeight] = None, lora=None) -> torch.Tensor:
     """silu(gate_proj(x)) * up_proj(x) with the fused gate|up weight [2I, K] (std:945).  Decode steps (<= 4 rows)
     apply the gate in the epilogue of the weight-stream kernel, and so does the 256-row kernel of a prefill chunk
-    (ivl_linear_m256_fwd); other calls are a library GEMM + silu_mul.  w8: as in `linear`."""
+    (ivl_linear_m256_fwd); other calls are a library GEMM + silu_mul.  w8: as in `linear`.  lora: (LoraTable, key, rows) with the
+    two segments gate | up -- the plain projection on the fused weight, lora_add, then silu_mul: the header guarantees linear +
+    ivl_silu_mul_fwd == the GLU forms bit for bit, so rows without an adapter keep their bits."""
+    if lora is not None:
+        return silu_mul(linear(x, w_gate_up, w8=w8, lora=lora))
     if w8 is not None:
         w8.check(w_gate_up)
     if isinstance(x, PreNorm):
@@ -1244,6 +1253,227 @@ def linear_swiglu(x: torch.Tensor, w_gate_up: torch.Tensor, w8: Optional[PackedW
     if _m256_swiglu_applies(x, w_gate_up, rows, I, K):
         return _linear_swiglu_m256(x, w_gate_up, rows, I, K)
     return silu_mul(linear(x, w_gate_up))
+
+
+# ---- per-row LoRA adapters over frozen (bf16 or packed) weights, unmerged ---------------------------------------------
+LORA_RANKS = (8, 16, 32, 64)
+LORA_MAX_SEG = 8
+LORA_T_LD = 512                  # row pitch of a t workspace: 8 segments x rank 64
+# calls of lora_add per path (tests read it to know what a call ran on): the HIP entry point / peft's computation through torch
+LORA_CALLS = {"small_m": 0, "torch": 0}
+LoraArgs = _lib.LoraArgs
+
+
+class LoraHandle(NamedTuple):
+    """An adapter loaded into a LoraTable: its index in every registered projection's stacks, its true rank and scaling."""
+    index: int
+    rank: int
+    scaling: float
+    skipped: Tuple[str, ...] = ()          # names of a state dict that load_adapter ignored (vision tower, lm_head)
+
+
+class _LoraProj:
+    """The stacks of one registered projection."""
+
+    def __init__(self, n_adapters: int, R: int, N: int, K: int, seg_cols, device):
+        self.N, self.K, self.seg_cols = N, K, tuple(int(c) for c in seg_cols)
+        self.n_seg = len(self.seg_cols) - 1
+        self.A = torch.zeros(n_adapters, self.n_seg * R, K, dtype=torch.bfloat16, device=device)
+        self.B = torch.zeros(n_adapters, N, R, dtype=torch.bfloat16, device=device)
+        self.t_ws = torch.zeros(4, LORA_T_LD, dtype=torch.bfloat16, device=device)
+
+
+class LoraTable:
+    """The device tables of ivl_lora_add_small_m_fwd as ONE arena for up to `n_adapters` adapters of rank <= R, allocated once (the
+    pattern of FsmTables): per registered projection the A [n_adapters, n_seg R, K] and B [n_adapters, N, R] stacks, the segment
+    borders and a t workspace, and one scaling [n_adapters] for the table.  An adapter occupies ONE index across all registered
+    projections; a projection (or segment) it does not target holds zeros there.  The tensors never move: load() / unload() between
+    two replays of a captured step need no recapture."""
+
+    def __init__(self, n_adapters: int, R: int, device):
+        if isinstance(n_adapters, bool) or not isinstance(n_adapters, int) or n_adapters < 1:
+            raise ValueError(f"LoraTable: n_adapters must be an int >= 1; got {n_adapters!r}")
+        if R not in LORA_RANKS:
+            raise ValueError(f"LoraTable: the rank capacity R must be one of {LORA_RANKS}; got {R!r}")
+        self.n_adapters, self.R, self.device = n_adapters, R, torch.device(device)
+        self.scaling = torch.zeros(n_adapters, dtype=torch.float32, device=self.device)
+        self.proj: Dict[object, _LoraProj] = {}
+        self._slots: List[Optional[LoraHandle]] = [None] * n_adapters
+        self._const: Dict[Tuple[int, int], torch.Tensor] = {}
+        self.rows = None                 # the adapters of the forward in progress: None, a LoraHandle or an int32 device tensor
+
+    def handles(self) -> List[LoraHandle]:
+        return [h for h in self._slots if h is not None]
+
+    def register(self, key, N: int, K: int, seg_cols) -> None:
+        """A projection with N output columns over K inputs; segment i owns the columns [seg_cols[i], seg_cols[i + 1])."""
+        seg_cols = [int(c) for c in seg_cols]
+        if key in self.proj:
+            raise ValueError(f"LoraTable.register: {key!r} is registered already")
+        if self.handles():
+            raise ValueError("LoraTable.register: adapters are loaded; register every projection first")
+        if not 2 <= len(seg_cols) <= LORA_MAX_SEG + 1:
+            raise ValueError(f"LoraTable.register: 1..{LORA_MAX_SEG} segments; got the borders {seg_cols}")
+        if N < 1 or K < 8 or K % 8 or seg_cols[0] < 0 or seg_cols[-1] > N or any(b < a for a, b in zip(seg_cols, seg_cols[1:])):
+            raise ValueError(f"LoraTable.register: N={N} K={K} (a multiple of 8) with non-decreasing borders within [0, N]; got {seg_cols}")
+        self.proj[key] = _LoraProj(self.n_adapters, self.R, N, K, seg_cols, self.device)
+
+    def load(self, tensors: Dict, scaling: float, skipped=()) -> LoraHandle:
+        """tensors: {key: [(A_i [r, K], B_i [n_i, r]) or None for every segment i]} (a key that is missing = not targeted); every pair
+        of one rank r <= R.  Writes the adapter at a free index, zero-padded to R, and returns its handle."""
+        if None not in self._slots:
+            raise ValueError(f"LoraTable.load: all {self.n_adapters} adapter indices are taken")
+        unknown = [k for k in tensors if k not in self.proj]
+        if unknown:
+            raise ValueError(f"LoraTable.load: not registered: {unknown}")
+        rank = None
+        for key, pairs in tensors.items():
+            p = self.proj[key]
+            if len(pairs) != p.n_seg:
+                raise ValueError(f"LoraTable.load: {key!r} has {p.n_seg} segments; got {len(pairs)} entries")
+            for i, pair in enumerate(pairs):
+                if pair is None:
+                    continue
+                A, B = pair
+                n_i = p.seg_cols[i + 1] - p.seg_cols[i]
+                if A.dim() != 2 or B.dim() != 2 or A.shape[1] != p.K or B.shape[0] != n_i or A.shape[0] != B.shape[1]:
+                    raise ValueError(f"LoraTable.load: {key!r} segment {i}: A [r, {p.K}] and B [{n_i}, r] expected; got "
+                                     f"{tuple(A.shape)} and {tuple(B.shape)}")
+                if rank is not None and A.shape[0] != rank:
+                    raise ValueError(f"LoraTable.load: ranks {rank} and {A.shape[0]} in one adapter (no per-module rank pattern)")
+                rank = A.shape[0]
+        if rank is None or not 1 <= rank <= self.R:
+            raise ValueError(f"LoraTable.load: rank {rank} for a table of rank capacity {self.R}")
+        idx = self._slots.index(None)
+        self._zero(idx)
+        for key, pairs in tensors.items():
+            p = self.proj[key]
+            for i, pair in enumerate(pairs):
+                if pair is not None:
+                    A, B = pair
+                    p.A[idx, i * self.R:i * self.R + rank] = A.detach().to(device=self.device, dtype=torch.bfloat16)
+                    p.B[idx, p.seg_cols[i]:p.seg_cols[i + 1], :rank] = B.detach().to(device=self.device, dtype=torch.bfloat16)
+        self.scaling[idx] = float(scaling)
+        self._slots[idx] = h = LoraHandle(idx, rank, float(scaling), tuple(skipped))
+        return h
+
+    def _zero(self, idx: int) -> None:
+        for p in self.proj.values():
+            p.A[idx].zero_()
+            p.B[idx].zero_()
+        self.scaling[idx] = 0.0
+
+    def unload(self, handle: LoraHandle) -> None:
+        """Frees the adapter's index and zeroes its rows: a slot still pointing at it adds zeros until it is given another."""
+        if not isinstance(handle, LoraHandle) or handle.index >= self.n_adapters or self._slots[handle.index] != handle:
+            raise ValueError(f"LoraTable.unload: {handle!r} is not loaded here")
+        self._zero(handle.index)
+        self._slots[handle.index] = None
+
+    def index_of(self, adapter) -> int:
+        """-1 for None, the index of a handle that is loaded here."""
+        if adapter is None:
+            return -1
+        if not isinstance(adapter, LoraHandle) or adapter.index >= self.n_adapters or self._slots[adapter.index] != adapter:
+            raise ValueError(f"LoraTable: {adapter!r} is not an adapter loaded here")
+        return adapter.index
+
+    def rows_of(self, adapter, rows: int) -> torch.Tensor:
+        """An int32 device tensor [rows] that names `adapter` in every row (kept: a captured step may hold its address)."""
+        key = (self.index_of(adapter), rows)
+        if key not in self._const:
+            self._const[key] = torch.full((rows,), key[0], dtype=torch.int32, device=self.device)
+        return self._const[key]
+
+
+def lora_kwargs(table: Optional[LoraTable], key) -> dict:
+    """The `lora=` argument of linear / linear_swiglu for a module's projection `key`: nothing at all unless a table is attached,
+    so an adapter-less model makes the calls it always made.  The rows' adapters are those of the forward in progress (table.rows)."""
+    return {"lora": (table, key, table.rows)} if table is not None else {}
+
+
+def _lora_torch(y: torch.Tensor, x: torch.Tensor, p: _LoraProj, table: LoraTable, rows) -> torch.Tensor:
+    """peft's own computation, y + lora_B(lora_A(x)) * scaling in the dtype of x, per segment, for the rows of each adapter."""
+    M = x.numel() // p.K
+    y2, x2 = y.view(M, p.N), x.reshape(M, p.K)
+    if isinstance(rows, torch.Tensor):
+        if rows.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("lora_add: a call of more than 4 rows reads its adapter indices on the host and cannot be captured "
+                               "(graphed decode with an adapter table serves up to 4 rows per step)")
+        per_row = [int(v) for v in rows.reshape(-1).tolist()]
+        if M % len(per_row):
+            raise ValueError(f"lora_add: {len(per_row)} adapter indices for {M} rows")
+        per_row = [v for v in per_row for _ in range(M // len(per_row))]          # [B] for [B, T, K]: the batch row's, repeated
+    else:
+        per_row = [table.index_of(rows)] * M
+    R = table.R
+    for a in sorted(set(v for v in per_row if 0 <= v < table.n_adapters)):
+        sel = [m for m, v in enumerate(per_row) if v == a]
+        whole = len(sel) == M
+        xa = x2 if whole else x2[sel]
+        s = float(table.scaling[a])
+        for i in range(p.n_seg):
+            c0, c1 = p.seg_cols[i], p.seg_cols[i + 1]
+            if c1 == c0:
+                continue
+            A, B = p.A[a, i * R:(i + 1) * R].to(x.dtype), p.B[a, c0:c1].to(x.dtype)
+            delta = torch.nn.functional.linear(torch.nn.functional.linear(xa, A), B) * s
+            if whole:
+                y2[:, c0:c1] = y2[:, c0:c1] + delta
+            else:
+                y2[sel, c0:c1] = y2[sel, c0:c1] + delta
+    return y
+
+
+def lora_add(y: torch.Tensor, x, table: LoraTable, key, rows) -> torch.Tensor:
+    """y += s_a B_a (A_a x) per row, IN PLACE on the base projection's output y [..., N], for the registered projection `key`.
+    x: the projection's input [..., K], or the PreNorm the base call ran in its prologue (the kernel then forms the normalised
+    row itself, bit-identical to the base launch's).  rows: an int32 device tensor with one adapter index per row (or per batch row
+    of a [B, T, K] input; outside [0, n_adapters) = the row is not touched), or a LoraHandle / None for the whole call.
+    Decode steps (<= 4 rows, bf16, on the device) run ivl_lora_add_small_m_fwd; anything else is peft's computation through torch's
+    library GEMMs, like every M > 4 projection of the package (an index tensor is then read on the host: not capturable)."""
+    p = table.proj.get(key)
+    if p is None:
+        raise ValueError(f"lora_add: the projection {key!r} is not registered in the table")
+    pn = x if isinstance(x, PreNorm) else None
+    shape = pn.shape if pn is not None else x.shape
+    if shape[-1] != p.K or y.shape[-1] != p.N or tuple(y.shape[:-1]) != tuple(shape[:-1]):
+        raise ValueError(f"lora_add: {key!r} is [{p.N}, {p.K}]; got x {tuple(shape)} and y {tuple(y.shape)}")
+    if not y.is_contiguous():
+        raise ValueError("lora_add: y must be contiguous (it is updated in place)")
+    M = y.numel() // p.N
+    dtype = pn.dtype if pn is not None else x.dtype
+    if not (y.is_cuda and 1 <= M <= 4 and dtype == torch.bfloat16 and y.dtype == torch.bfloat16):
+        xt = pn.materialize() if pn is not None else x
+        LORA_CALLS["torch"] += 1
+        return _lora_torch(y, xt, p, table, rows)
+    if not isinstance(rows, torch.Tensor):
+        rows = table.rows_of(rows, M)
+    elif rows.numel() != M:
+        if M % rows.numel():
+            raise ValueError(f"lora_add: {rows.numel()} adapter indices for {M} rows")
+        rows = rows.reshape(-1).repeat_interleave(M // rows.numel())               # on the device
+    if rows.dtype != torch.int32 or not rows.is_cuda or not rows.is_contiguous():
+        raise ValueError("lora_add: rows must be a contiguous int32 tensor on the device")
+    a = LoraArgs()
+    norm = pn is not None and pn._y is None and 512 <= p.K <= 4096
+    if norm:
+        a.x, a.residual, a.norm_weight, a.eps = pn.x.data_ptr(), (pn.residual.data_ptr() if pn.residual is not None else None), \
+            pn.weight.data_ptr(), pn.eps
+        keep = (pn.x, pn.residual, pn.weight)
+    else:
+        xt = pn.materialize() if pn is not None else x
+        xt = xt if xt.is_contiguous() else xt.contiguous()
+        a.x, keep = xt.data_ptr(), (xt,)
+    a.y, a.adapter_idx, a.A, a.B, a.scaling, a.t_ws = y.data_ptr(), rows.data_ptr(), p.A.data_ptr(), p.B.data_ptr(), \
+        table.scaling.data_ptr(), p.t_ws.data_ptr()
+    a.M, a.N, a.K, a.R, a.n_adapters, a.n_seg = M, p.N, p.K, table.R, table.n_adapters, p.n_seg
+    for i in range(LORA_MAX_SEG + 1):
+        setattr(a, f"seg_col{i}", p.seg_cols[min(i, p.n_seg)])
+    _lib.check(_lib.load().ivl_lora_add_small_m_fwd(ctypes.byref(a), _stream(y)))
+    del keep
+    LORA_CALLS["small_m"] += 1
+    return y
 
 
 def linear_logprob(x: torch.Tensor, weight: torch.Tensor, target: torch.Tensor, bias: Optional[torch.Tensor] = None, *,

@@ -76,6 +76,15 @@ step A (bf16 weights) B (e4m3 copies) C (mxfp4 copies), timed A B C A B C per sl
 operator table of --w8 with a w4 column (us per call, achieved GB/s of the bytes each format streams, w4 / w8 and w4 / bf16).
 
     python tools/multistream_decode.py --w4 --slots 1,4 [--out profiles/w4_decode.json]
+
+--lora: per-slot LoRA adapters, unmerged (InfiniteVLTextStack.enable_adapters), in the captured greedy step.  A: the
+step without a table (what the merged model costs as well); B: a table attached, every slot at -1; C: every slot on a rank-16
+adapter over all ten target modules; D: C over mxfp4 packed weights.  Three models of the same shape (a captured step holds the
+launches of ITS model: no table / table / table + packed copies), timed A B C D per round in one process, median of --rounds
+rounds.  Then ops.lora_add alone on every projection of a decode token (both launches of ivl_lora_add_small_m_fwd, the NORM form
+where the model takes it), M = 1 and M = 4, the calls of a leg captured in one graph: us per call.  Nothing is asserted.
+
+    python tools/multistream_decode.py --lora --slots 1,4 [--out profiles/lora_decode.json]
 """
 import argparse
 import json
@@ -103,6 +112,7 @@ def main():
     ap.add_argument("--grammar", action="store_true", help="time the constrained step against the scored one (see above)")
     ap.add_argument("--w8", action="store_true", help="time the step on packed e4m3 weights against the bf16 step (see above)")
     ap.add_argument("--w4", action="store_true", help="time the step on packed mxfp4 weights against the e4m3 and bf16 steps (see above)")
+    ap.add_argument("--lora", action="store_true", help="time the step with per-slot LoRA adapters against the step without (see above)")
     args = ap.parse_args()
     import torch
     from infinitevl_amd.cache import MultiStreamCache
@@ -145,6 +155,8 @@ def main():
         return w8_legs(args, torch, model, cfg, prompts, dev)
     if args.w4:
         return w4_legs(args, torch, model, cfg, prompts, dev)
+    if args.lora:
+        return lora_legs(args, torch, model, cfg, prompts, dev)
 
     # reference: one stream on the existing B = 1 graphed decode step
     c1 = model.allocate_inference_cache(1)
@@ -757,6 +769,130 @@ def w4_legs(args, torch, model, cfg, prompts, dev):
     model.use_packed_weights(True)
     del model8
     res["operators"] = w8_operator_legs(args, torch, cfg, dev, timed, fmts=("bf16", "w8", "w4"))
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+LORA_RANK = 16
+
+
+def lora_state(torch, model, r, seed, scale=0.02):
+    """a peft state dict of rank r over all ten target modules of every layer"""
+    g = torch.Generator().manual_seed(seed)
+    sd = {}
+    for name in model._lora_names:
+        w = model.get_submodule(name).weight
+        pre = "base_model.model.model.language_model." + name
+        sd[pre + ".lora_A.weight"] = (torch.randn(r, w.shape[1], generator=g) * scale).to(torch.bfloat16)
+        sd[pre + ".lora_B.weight"] = (torch.randn(w.shape[0], r, generator=g) * scale).to(torch.bfloat16)
+    return sd
+
+
+def lora_operator_legs(args, torch, cfg, dev, timed):
+    """ops.lora_add alone on every projection of a decode token: {name: {M1_us, M4_us, ...}} (two launches per call)"""
+    from infinitevl_amd import ops
+    hd, I = cfg.hidden_size, cfg.intermediate_size
+    nq, nkv = cfg.num_attention_heads * cfg.head_dim, cfg.num_key_value_heads * cfg.head_dim
+    H, dk = cfg.num_linear_heads, cfg.linear_head_dim
+    dv = int(dk * cfg.expand_v)
+    gcols = [0, H * dk, 2 * H * dk, 2 * H * dk + H * dv, 2 * H * dk + 2 * H * dv, 2 * H * dk + 2 * H * dv + H, 2 * H * dk + 2 * H * dv + 2 * H]
+    shapes = [("qkv", nq + 2 * nkv, hd, (0, nq, nq + nkv, nq + 2 * nkv), True), ("gdn_in", (gcols[-1] + 7) // 8 * 8, hd, tuple(gcols), True),
+              ("attn_o_proj", hd, nq, (0, hd), False), ("gdn_o_proj", hd, H * dv, (0, hd), False),
+              ("gate_up", 2 * I, hd, (0, I, 2 * I), True), ("down", hd, I, (0, hd), False)]
+    gen = torch.Generator(device=dev).manual_seed(3)
+    out = {}
+    for name, N, K, cols, norm in shapes:
+        t = ops.LoraTable(2, LORA_RANK, dev)
+        t.register(name, N, K, cols)
+        p = t.proj[name]
+        p.A.copy_((torch.randn(p.A.shape, generator=gen, device=dev) * 0.02).to(torch.bfloat16))
+        p.B.copy_((torch.randn(p.B.shape, generator=gen, device=dev) * 0.02).to(torch.bfloat16))
+        t.scaling.fill_(2.0)
+        row = {"N": N, "K": K, "segments": len(cols) - 1, "norm_form": norm,
+               "adapter_bytes": int(p.A[0].numel() + p.B[0].numel()) * 2}
+        nw = torch.ones(K, dtype=torch.bfloat16, device=dev)
+        for M in (1, 4):
+            x = (torch.randn(M, K, generator=gen, device=dev) * 0.5).to(torch.bfloat16)
+            y = torch.zeros(M, N, dtype=torch.bfloat16, device=dev)
+            for leg, idx in (("on", 0), ("off", -1)):
+                rows = torch.full((M,), idx, dtype=torch.int32, device=dev)
+
+                def call():
+                    ops.lora_add(y, ops.PreNorm(x, None, nw, 1e-6) if norm else x, t, name, rows)
+                call()
+                torch.cuda.synchronize()
+                g = torch.cuda.CUDAGraph()
+                reps = 64
+                with torch.cuda.graph(g):
+                    for _ in range(reps):
+                        call()
+                ts = [timed(g.replay, 4) / reps for _ in range(args.rounds)]
+                row[f"M{M}_{leg}_us"] = round(1000 * statistics.median(ts), 2)
+        out[name] = row
+        print(name, row, file=sys.stderr, flush=True)
+    return out
+
+
+def lora_legs(args, torch, model, cfg, prompts, dev):
+    from infinitevl_amd.cache import MultiStreamCache
+    from infinitevl_amd.harness import GraphedMultiStreamDecode, InfiniteVLTextStack
+    stream = torch.cuda.current_stream()
+
+    def timed(fn, n):
+        for _ in range(4):
+            fn()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        for _ in range(n):
+            fn()
+        e1.record(stream)
+        e1.synchronize()
+        return e0.elapsed_time(e1) / n
+
+    def another():
+        with torch.device(dev):
+            torch.set_default_dtype(torch.bfloat16)
+            m = InfiniteVLTextStack(cfg)
+            torch.set_default_dtype(torch.float32)
+        return m.to(torch.bfloat16).eval().init_weights_(seed=0).fuse_()
+
+    model_t = another().enable_adapters(4, LORA_RANK)
+    model_q = another().quantize_weights_(lm_head=True, fmt="mxfp4").enable_adapters(4, LORA_RANK)
+    handles = {id(m): m.load_adapter(lora_state(torch, m, LORA_RANK, 1), alpha=2 * LORA_RANK, rank=LORA_RANK) for m in (model_t, model_q)}
+    legs = (("A_no_table", model, False), ("B_table_all_minus_one", model_t, False), ("C_rank16_every_slot", model_t, True),
+            ("D_rank16_over_mxfp4", model_q, True))
+    slots = [int(s) for s in args.slots.split(",")]
+    n_proj = 4 * cfg.num_hidden_layers
+    res = {"tool": "multistream_decode --lora", "layers": cfg.num_hidden_layers, "window": 4096, "steps": args.steps, "rounds": args.rounds,
+           "rank": LORA_RANK, "target_modules": 10, "form": "two launches per projection (shrink, expand-add)",
+           "launches_added_per_step": {"lora": 2 * n_proj, "silu_mul (gate|up runs as linear + gate)": cfg.num_hidden_layers},
+           "bar": "none asserted; the yardstick of C is A"}
+    for n in slots:
+        decs = {}
+        for name, m, on in legs:
+            cache = MultiStreamCache(config=cfg, n_slots=n, device=dev, dtype=torch.bfloat16)
+            dec = GraphedMultiStreamDecode(m, cache)
+            for s in range(n):
+                dec.admit(s, prompts[s], adapter=handles[id(m)] if on else None)
+            dec.capture()
+            decs[name] = dec
+        times = {k: [] for k in decs}
+        for _ in range(args.rounds):                            # A B C D
+            for name, dec in decs.items():
+                times[name].append(timed(dec.step, args.steps))
+        med = {k: statistics.median(v) for k, v in times.items()}
+        a = med["A_no_table"]
+        res[f"slots{n}"] = dict({f"{k}_ms_per_step": round(v, 4) for k, v in med.items()},
+                                **{f"{k}_over_A": round(v / a, 4) for k, v in med.items() if k != "A_no_table"},
+                                **{f"{k}_spread_ms": [round(min(v), 4), round(max(v), 4)] for k, v in times.items()})
+        print(f"slots{n}: " + " ".join(f"{k} {v:.4f}" for k, v in med.items()) + " ms", file=sys.stderr, flush=True)
+        del decs
+    del model_t, model_q
+    res["operators_us_per_call"] = lora_operator_legs(args, torch, cfg, dev, timed)
     line = json.dumps(res)
     print(line)
     if args.out:
