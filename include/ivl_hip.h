@@ -508,6 +508,41 @@ IVL_API int ivl_lora_add_small_m_fwd(const ivl_lora_args* args, void* stream);
  * 1 <= M <= 256, K % 64 == 0 and K <= 16384, N % 4 == 0, x / W 16-byte aligned: else IVL_ERR_UNSUPPORTED / IVL_ERR_INVALID_ARG. */
 IVL_API int ivl_linear_m256_fwd(const void* x, const void* w, const void* bias, void* y, int M, int N, int K, int glu, void* stream);
 
+/* nn.Linear for a decode step of up to 16 rows (5 to 16 slots of a multi-stream step): y[M,N] = bf16(x[M,K] W[N,K]^T + bias[N]), or
+ * with glu != 0 the SwiGLU MLP head on the fused gate|up weight [2N,K] (N = I), with the formula and rounding points of
+ * ivl_linear_swiglu_small_m_fwd:  y[M,I] = bf16( bf16(silu(bf16(x Wg^T + bg))) * bf16(x Wu^T + bu) ),  bias [2I] or NULL.
+ * A weight stream on v_mfma_f32_16x16x32_bf16: 16 weight rows are the A operand, the (zero-padded) 16 rows of x the B operand; fp32
+ * accumulation, one rounding.  x, bias, y bf16 row-major contiguous.
+ *   ivl_linear_m16_fwd     w  bf16 [N,K] (GLU: [2I,K]);
+ *   ivl_linear_m16_w8_fwd  wq uint8 [N,K] OCP e4m3fn codes + scale fp32 [N] (GLU: [2I,K] / [2I]), W'[n,k] = bf16(float(code) * scale[n]);
+ *   ivl_linear_m16_w4_fwd  wq / sq: the SHUFFLED MXFP4 layout of the *_small_m_w4 twins above, unchanged (uint8 [N,Kp/2] and [N,Kp/32],
+ *                          Kp = 2048 ceil(K / 2048)), W'[n,k] = e2m1(code) * 2^(b - 127).
+ * ONE SUMMATION PLAN for the three, a function of K only -- not of M, not of N, not of the format.  A chunk is 8 consecutive k;
+ * step s = 16t + j (t = tile of 2048 k, j in 0..15) is four MFMAs u = 0..3 whose k-group g in 0..3 holds the chunk
+ * 256t + 4j + g + 64u (chunks past K/8: zeros); the S steps that hold a chunk below K/8 are cut into 8 contiguous slices of
+ * ceil(S / 8) steps, each slice is accumulated from 0 in ascending (s, u) order by one wave of the workgroup that owns the output
+ * columns, and the slices are added in ascending order in fp32 in LDS; then the bias, then the rounding.
+ * No split across workgroups, no atomics, one launch.  THE CONTRACTS:
+ *  1. Determinism: every run gives the same bits, eager or replayed from a graph.
+ *  2. Row independence: row m of y depends on row m of x only -- the same bits for every M, at every row index, whatever the other
+ *     rows hold (NaN, Inf); rows >= M of the B operand are zeros, never read from x and never written to y.  Weight rows past the
+ *     last are neither read nor stored.
+ *  3. Packed equals bf16 on W': ivl_linear_m16_w8_fwd with power-of-two scales, and ivl_linear_m16_w4_fwd, equal ivl_linear_m16_fwd
+ *     called on W' = dequantize(packed copy) bit for bit, plain and GLU: every policy hands the MFMA the bf16 bit pattern of W'
+ *     (exact in bf16 for both formats).  A general e4m3 scale computes the W' above (rounded to bf16) and loses nothing but the name.
+ *  4. GLU equals plain plus gate: the glu != 0 call equals the glu == 0 call on the fused weight (N = 2I) followed by
+ *     ivl_silu_mul_fwd, bit for bit.
+ *  5. NO bit-equality with the small-M (M <= 4) or 256-row kernels: their summation orders differ; the agreement is numerical.
+ * 1 <= M <= 16 (else IVL_ERR_UNSUPPORTED); N >= 1, K >= 32 and K % 32 == 0 -- tails in N are predicated, nothing is padded by the
+ * caller --, x / w (wq) / y 16-byte aligned, scale / sq 4-byte aligned, no NULL x, w, wq, scale, sq or y (else IVL_ERR_INVALID_ARG);
+ * every weight offset is a 32-bit byte offset: R K 2 < 2^32 and R (bytes of a padded row) < 2^32 (else IVL_ERR_UNSUPPORTED).  Every
+ * check runs before anything is launched. */
+IVL_API int ivl_linear_m16_fwd(const void* x, const void* w, const void* bias, void* y, int M, int N, int K, int glu, void* stream);
+IVL_API int ivl_linear_m16_w8_fwd(const void* x, const void* wq, const float* scale, const void* bias, void* y, int M, int N, int K,
+                                  int glu, void* stream);
+IVL_API int ivl_linear_m16_w4_fwd(const void* x, const void* wq, const void* sq, const void* bias, void* y, int M, int N, int K,
+                                  int glu, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Scoring GIVEN tokens under lm_head: the log-probability of target[r] in the distribution of row r, the [M,N] logits never
  * written anywhere.  Replaces logits -> float log_softmax -> gather (HF `labels=`, CrossEntropyLoss(reduction="none") of

@@ -1,0 +1,278 @@
+// y[M,N] = x[M,K] W[N,K]^T (+ bias), bf16 in / fp32 accumulate / bf16 out, for 1 <= M <= 16 rows: the projections of a decode step
+// that advances 5 to 16 slots.  Still a weight stream -- 2 M FLOP per weight element -- but no longer one for fmaf
+// chains: sixteen x rows are exactly one B operand of v_mfma_f32_16x16x32_bf16, so a wave owns a TILE of 16 weight rows (the A operand),
+// streams their K elements once, non-temporally, straight into VGPRs, and one MFMA per 32 k serves all rows of x.
+//
+// THE PLAN is a function of K alone -- not of M, not of N, not of the weight format:
+//   a CHUNK is 8 consecutive k; TILE t of a row is the chunks [256t, 256t + 256); STEP s = 16t + j (j in 0..15) issues four MFMAs
+//   u = 0..3 whose k-group g (the 8 k that lane group g = lane >> 4 feeds) holds chunk 256t + 4j + g + 64u -- of weight row
+//   lane & 15 in the A operand, of x row lane & 15 in the B operand.  That is the order in which the shuffled MXFP4 layout hands a lane
+//   its pieces (position p = 4j + g of tile t: ONE 16-byte load holds the four chunks p + 64u, one dword their four block scales); the
+//   bf16 and e4m3 policies load the same chunks from their row-major rows.  Steps past the row end do not exist (S = the number of
+//   steps with a chunk below K/8); chunks past the row end inside a step are zeros on both operands.
+//   K SPLIT: the S steps are cut into 8 contiguous slices of ceil(S / 8) steps, one per wave of the workgroup that owns the columns;
+//   a wave adds its steps in ascending order, u ascending, from 0, and the partial accumulators meet in LDS in ascending slice order
+//   (fp32), then the bias, then the ONE rounding.  A slice without steps adds zeros.  No split across workgroups, no atomics, no
+//   second launch: the same bits on every run.  (A split by the number of rows -- 1, 2, 4 waves for the wide projections -- was
+//   measured and lost at every one of the model's seven shapes: DESIGN 4.16.)
+//
+// WEIGHT ELEMENT POLICIES (W16Bf16 / W16E4m3 / W16Mxfp4): a policy says where a lane's pieces of a step are and how a piece becomes
+// the bf16 bit pattern of W' (exact for both packed formats); everything behind that -- operands, MFMA sequence, reduction, epilogue
+// -- is the kernel's, so the packed forms equal the bf16 form on W' bit for bit.
+//
+// D = A B^T has the x row on the lane (col = lane & 15) and weight rows 4 (lane >> 4) + reg in its four registers: a lane stores four
+// consecutive output columns of one x row.  Rows M .. 15 of B are zeros: never read from x, never written to y; weight rows past the
+// last are neither read (the row index is clamped) nor stored.  Every output element is its own fp32 sum over k in the plan's order:
+// row m of y depends on row m of x only.
+//
+// x comes straight from L2 in fragment shape (16 rows x 64 B per load instruction): it is at most 16 x 11008 bf16 = 352 KB and is
+// re-read by every tile -- at M = 16 as many bytes as the bf16 weights themselves; a wave of a wide plain projection therefore owns
+// two tiles per x fragment (M16_PAIR), as the GLU form does by construction.  Staging x in LDS was not built.
+#include "ivl_rowwise.h"
+
+namespace ivl {
+
+constexpr int M16_KS = 8;         // the K split: waves of a workgroup, which share one range of output columns
+constexpr int M16_PF = 2;         // steps in flight per wave: 8 weight pieces + 8 x pieces per lane and accumulator
+
+__device__ __forceinline__ bf16x8 m16_frag(u32x4 v) { return __builtin_bit_cast(bf16x8, v); }
+
+struct W16Bf16 {                                   // bf16 [R,K]: four 16-byte pieces per step
+  using arg = const bf16_t*;
+  struct row { unsigned int off; };
+  struct raw { u32x4 p[4]; };
+  static bool null(arg w) { return w == nullptr; }
+  static __device__ __forceinline__ row open(arg, int r, int K) { return row{(unsigned int)r * (unsigned int)K * 2u}; }
+  static __device__ __forceinline__ void load(arg w, row rw, int t, int j, int g, int nchunk, raw& o) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int c = min(256 * t + 4 * j + g + 64 * u, nchunk - 1);
+      o.p[u] = __builtin_nontemporal_load((const u32x4*)((const unsigned char*)w + (rw.off + (unsigned int)c * 16u)));
+    }
+  }
+  static __device__ __forceinline__ u32x4 bits(const raw& o, row, int u) { return o.p[u]; }
+};
+
+struct W16Arg8 { const unsigned char* q; const float* scale; };
+struct W16E4m3 {                                   // e4m3fn codes [R,K] + one fp32 scale per row: four 8-byte pieces per step
+  using arg = W16Arg8;
+  struct row { unsigned int off; float scale; };
+  struct raw { u32x2 p[4]; };
+  static bool null(arg w) { return w.q == nullptr || w.scale == nullptr; }
+  static __device__ __forceinline__ row open(arg w, int r, int K) { return row{(unsigned int)r * (unsigned int)K, w.scale[r]}; }
+  static __device__ __forceinline__ void load(arg w, row rw, int t, int j, int g, int nchunk, raw& o) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int c = min(256 * t + 4 * j + g + 64 * u, nchunk - 1);
+      o.p[u] = __builtin_nontemporal_load((const u32x2*)(w.q + (rw.off + (unsigned int)c * 8u)));
+    }
+  }
+  // W' = bf16(float(code) * scale): v_cvt_pk_f32_fp8 decodes exactly, the product with a power of two is exact and has 4 significant bits
+  static __device__ __forceinline__ u32x4 bits(const raw& o, row rw, int u) {
+    const u32x2 a = o.p[u];
+    const auto w01 = __builtin_amdgcn_cvt_pk_f32_fp8((int)a.x, false), w23 = __builtin_amdgcn_cvt_pk_f32_fp8((int)a.x, true);
+    const auto w45 = __builtin_amdgcn_cvt_pk_f32_fp8((int)a.y, false), w67 = __builtin_amdgcn_cvt_pk_f32_fp8((int)a.y, true);
+    const float s = rw.scale;
+    return u32x4{pack2bf(w01[0] * s, w01[1] * s), pack2bf(w23[0] * s, w23[1] * s), pack2bf(w45[0] * s, w45[1] * s),
+                 pack2bf(w67[0] * s, w67[1] * s)};
+  }
+};
+
+struct W16Arg4 { const unsigned char* q; const unsigned char* s; };
+struct W16Mxfp4 {                                  // the shuffled MXFP4 layout of include/ivl_hip.h: one 16-byte load + one dword per step
+  using arg = W16Arg4;
+  struct row { unsigned int qoff, soff; };
+  struct raw { u32x4 q; unsigned int s; };
+  static bool null(arg w) { return w.q == nullptr || w.s == nullptr; }
+  static __host__ __device__ __forceinline__ int kp(int K) { return (K + 2047) & ~2047; }        // a row is whole tiles of 2048 weights
+  static __device__ __forceinline__ row open(arg, int r, int K) {
+    return row{(unsigned int)r * (unsigned int)(kp(K) >> 1), (unsigned int)r * (unsigned int)(kp(K) >> 5)};
+  }
+  // position p = 4j + g of tile t: codes at byte 1024t + 16p of the row (chunks 256t + p + 64u, u = 0..3), their block scales
+  // (blocks 64t + j + 16u) at byte 64t + 4j of the scale row; a padded row holds whole tiles: no clamp
+  static __device__ __forceinline__ void load(arg w, row rw, int t, int j, int g, int, raw& o) {
+    o.q = __builtin_nontemporal_load((const u32x4*)(w.q + (rw.qoff + (unsigned int)(1024 * t + 16 * (4 * j + g)))));
+    o.s = __builtin_nontemporal_load((const unsigned int*)(w.s + (rw.soff + (unsigned int)(64 * t + 4 * j))));
+  }
+  // v_cvt_scalef32_pk_f32_fp4 decodes two codes and multiplies by 2^(sb - 127), exactly; 2 significant bits
+  static __device__ __forceinline__ u32x4 bits(const raw& o, row, int u) {
+    const unsigned int a = u == 0 ? o.q.x : u == 1 ? o.q.y : u == 2 ? o.q.z : o.q.w;
+    const float s = __builtin_bit_cast(float, ((o.s >> (8 * u)) & 0xffu) << 23);
+    const auto w01 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(a, s, 0), w23 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(a, s, 1);
+    const auto w45 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(a, s, 2), w67 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(a, s, 3);
+    return u32x4{pack2bf(w01[0], w01[1]), pack2bf(w23[0], w23[1]), pack2bf(w45[0], w45[1]), pack2bf(w67[0], w67[1])};
+  }
+};
+
+// steps of a row of K elements: tile t < T - 1 has all 16, the last one those whose first chunk 256t + 4j lies below K / 8
+static __host__ __device__ __forceinline__ int m16_steps(int K) {
+  const int nchunk = K >> 3, T = (nchunk + 255) >> 8, last = nchunk - 256 * (T - 1);
+  const int sl = (last + 3) >> 2;
+  return 16 * (T - 1) + (sl < 16 ? sl : 16);
+}
+// PAIR from 512 tiles on (measured, DESIGN 4.16: the GDN in-projection and lm_head gain 20 %, the N <= 2560 projections lose 25 %)
+static bool m16_pair(int R) { return R >= 8192; }
+
+// N = number of OUTPUT columns (GLU: I; the weight then has 2N rows); per = steps per slice
+// MODE: what a wave owns -- M16_ONE: one tile of 16 weight rows; M16_GLU: the gate tile and the up tile of the same 16 columns;
+// M16_PAIR: two adjacent tiles (32 columns) of a plain projection, which halves the x fragments read per weight byte.  ONE or PAIR is a
+// choice of speed: every output element is the same sum in the same order in both.
+enum { M16_ONE = 0, M16_GLU = 1, M16_PAIR = 2 };
+template <class WT, int MODE>
+__global__ __launch_bounds__(64 * M16_KS) void linear_m16_kernel(const bf16_t* __restrict__ x, typename WT::arg w,
+                                                                   const bf16_t* __restrict__ bias, bf16_t* __restrict__ y, int M, int N,
+                                                                   int K, int per) {
+  constexpr bool GLU = MODE == M16_GLU;
+  constexpr int NA = MODE == M16_ONE ? 1 : 2;      // accumulators (tiles) per wave
+  constexpr int COLS = MODE == M16_PAIR ? 32 : 16; // output columns per wave
+  __shared__ f32x4 s_part[M16_KS][NA][64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int r16 = lane & 15, g = lane >> 4;
+  const int tile = (int)blockIdx.x, slice = wave;
+  const int nchunk = K >> 3;
+  const int n0 = tile * COLS;
+  typename WT::row wr[NA];
+#pragma unroll
+  for (int a = 0; a < NA; ++a)                     // (GLU: a = 1 is the "up" row; PAIR: the row 16 further on)
+    wr[a] = WT::open(w, GLU ? min(n0 + r16, N - 1) + a * N : min(n0 + 16 * a + r16, N - 1), K);
+  const u32x4* xrow = (const u32x4*)(x + (size_t)min(r16, M - 1) * K);
+  const bool mlive = r16 < M;
+  f32x4 acc[NA];
+#pragma unroll
+  for (int a = 0; a < NA; ++a) acc[a] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const u32x4 zero = {0u, 0u, 0u, 0u};
+
+  const int S = m16_steps(K);
+  const int s_end = min(S, (slice + 1) * per);
+  for (int s = slice * per; s < s_end; s += M16_PF) {
+    typename WT::raw wv[M16_PF][NA];
+    u32x4 xv[M16_PF][4];
+#pragma unroll
+    for (int i = 0; i < M16_PF; ++i) {             // (a step past the slice repeats the last one and is masked below)
+      const int ss = min(s + i, s_end - 1), t = ss >> 4, j = ss & 15;
+#pragma unroll
+      for (int a = 0; a < NA; ++a) WT::load(w, wr[a], t, j, g, nchunk, wv[i][a]);
+#pragma unroll
+      for (int u = 0; u < 4; ++u) xv[i][u] = xrow[min(256 * t + 4 * j + g + 64 * u, nchunk - 1)];
+    }
+#pragma unroll
+    for (int i = 0; i < M16_PF; ++i) {
+      const int ss = min(s + i, s_end - 1), t = ss >> 4, j = ss & 15;
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const bool ok = s + i < s_end && 256 * t + 4 * j + g + 64 * u < nchunk;
+        const bf16x8 b = m16_frag(ok && mlive ? xv[i][u] : zero);
+#pragma unroll
+        for (int a = 0; a < NA; ++a)
+          acc[a] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(m16_frag(ok ? WT::bits(wv[i][a], wr[a], u) : zero), b, acc[a], 0, 0, 0);
+      }
+    }
+  }
+
+  if (slice != 0) {                                // slices 1 .. 7 hand over, slice 0 adds them in ascending order
+#pragma unroll
+    for (int a = 0; a < NA; ++a) s_part[slice][a][lane] = acc[a];
+  }
+  __syncthreads();
+  if (slice != 0) return;
+#pragma unroll
+  for (int k = 1; k < M16_KS; ++k)
+#pragma unroll
+    for (int a = 0; a < NA; ++a) acc[a] += s_part[k][a][lane];
+
+  if (!mlive) return;
+#pragma unroll
+  for (int a = 0; a < (GLU ? 1 : NA); ++a) {
+  const int n = n0 + 16 * a + 4 * g;               // this lane: x row r16, output columns n .. n + 3
+  if (n >= N) return;
+  float o[4];
+  if constexpr (GLU) {
+    float gt[4], sg[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int col = min(n + r, N - 1);
+      gt[r] = bf_round(acc[0][r] + (bias != nullptr ? bf2f(bias[col]) : 0.f));                    // gate_proj output
+      o[r] = bf_round(acc[1][r] + (bias != nullptr ? bf2f(bias[N + col]) : 0.f));                 // up_proj output
+    }
+    siluf_n_(gt, sg);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) o[r] = bf_round(sg[r]) * o[r];                                     // = silu_mul_kernel
+  } else {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) o[r] = acc[a][r] + (bias != nullptr ? bf2f(bias[min(n + r, N - 1)]) : 0.f);
+  }
+  bf16_t* yp = y + (size_t)r16 * N + n;
+  if ((N & 3) == 0) {                              // (n is a multiple of 4: the four columns exist and the piece is 8-byte aligned)
+    *(u32x2*)yp = u32x2{pack2bf(o[0], o[1]), pack2bf(o[2], o[3])};
+  } else {
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      if (n + r < N) yp[r] = f2bf(o[r]);
+  }
+  }
+}
+
+// every refusal, before anything is launched; row_bytes: the bytes of a (padded) weight row in the format at hand
+template <class WT>
+static int m16_check(const char* who, const void* x, typename WT::arg wp, const void* y, int M, int N, int K, int glu, size_t row_bytes) {
+  IVL_REQUIRE(x && !WT::null(wp) && y, IVL_ERR_INVALID_ARG, "%s: NULL pointer", who);
+  IVL_REQUIRE(M >= 1 && M <= 16, IVL_ERR_UNSUPPORTED, "%s: M=%d (built for 1..16 rows)", who, M);
+  IVL_REQUIRE(N >= 1, IVL_ERR_INVALID_ARG, "%s: N=%d", who, N);
+  IVL_REQUIRE(K >= 32 && K % 32 == 0, IVL_ERR_INVALID_ARG, "%s: K=%d (one MFMA spans 32 k: K must be a multiple of 32, at least 32)", who, K);
+  const long long R = (long long)(glu ? 2 : 1) * N;
+  // every weight offset is a 32-bit byte offset from the base: ONE bound for the three formats (the plan is theirs in common), and the
+  // padded rows of the format at hand
+  IVL_REQUIRE(R * K * 2 < (1ll << 32) && R * (long long)row_bytes < (1ll << 32), IVL_ERR_UNSUPPORTED,
+              "%s: weight of %lld x %d does not fit 32-bit offsets", who, R, K);
+  return IVL_OK;
+}
+
+template <class WT>
+static int m16_launch(const void* x, typename WT::arg wp, const void* bias, void* y, int M, int N, int K, int glu, void* stream,
+                      const char* who) {
+  const int R = glu ? 2 * N : N;
+  const int per = (m16_steps(K) + M16_KS - 1) / M16_KS;
+  const bool pair = !glu && m16_pair(R);
+  const dim3 grid((N + (pair ? 31 : 15)) / (pair ? 32 : 16)), block(64 * M16_KS);       // one range of output columns per workgroup
+  hipStream_t st = (hipStream_t)stream;
+  const bf16_t *xp = (const bf16_t*)x, *bp = (const bf16_t*)bias;
+  if (glu) hipLaunchKernelGGL((linear_m16_kernel<WT, M16_GLU>), grid, block, 0, st, xp, wp, bp, (bf16_t*)y, M, N, K, per);
+  else if (pair) hipLaunchKernelGGL((linear_m16_kernel<WT, M16_PAIR>), grid, block, 0, st, xp, wp, bp, (bf16_t*)y, M, N, K, per);
+  else hipLaunchKernelGGL((linear_m16_kernel<WT, M16_ONE>), grid, block, 0, st, xp, wp, bp, (bf16_t*)y, M, N, K, per);
+  return check_launch(who);
+}
+
+}  // namespace ivl
+
+using namespace ivl;
+
+extern "C" int ivl_linear_m16_fwd(const void* x, const void* w, const void* bias, void* y, int M, int N, int K, int glu, void* stream) {
+  const char* who = "ivl_linear_m16_fwd";
+  const int rc = m16_check<W16Bf16>(who, x, (const bf16_t*)w, y, M, N, K, glu, (size_t)(K > 0 ? K : 0) * 2);
+  if (rc) return rc;
+  IVL_REQUIRE((((size_t)x | (size_t)w | (size_t)y) & 15) == 0 && ((size_t)bias & 1) == 0, IVL_ERR_INVALID_ARG,
+              "%s: x / w / y must be 16-byte aligned", who);
+  return m16_launch<W16Bf16>(x, (const bf16_t*)w, bias, y, M, N, K, glu, stream, who);
+}
+
+extern "C" int ivl_linear_m16_w8_fwd(const void* x, const void* wq, const float* scale, const void* bias, void* y, int M, int N, int K,
+                                     int glu, void* stream) {
+  const char* who = "ivl_linear_m16_w8_fwd";
+  const W16Arg8 wp{(const unsigned char*)wq, scale};
+  const int rc = m16_check<W16E4m3>(who, x, wp, y, M, N, K, glu, (size_t)(K > 0 ? K : 0));
+  if (rc) return rc;
+  IVL_REQUIRE((((size_t)x | (size_t)wq | (size_t)y) & 15) == 0 && ((size_t)bias & 1) == 0 && ((size_t)scale & 3) == 0,
+              IVL_ERR_INVALID_ARG, "%s: x / wq / y must be 16-byte aligned, scale 4-byte aligned", who);
+  return m16_launch<W16E4m3>(x, wp, bias, y, M, N, K, glu, stream, who);
+}
+
+extern "C" int ivl_linear_m16_w4_fwd(const void* x, const void* wq, const void* sq, const void* bias, void* y, int M, int N, int K,
+                                     int glu, void* stream) {
+  const char* who = "ivl_linear_m16_w4_fwd";
+  const W16Arg4 wp{(const unsigned char*)wq, (const unsigned char*)sq};
+  const int rc = m16_check<W16Mxfp4>(who, x, wp, y, M, N, K, glu, (size_t)(K > 0 ? W16Mxfp4::kp(K) >> 1 : 0));
+  if (rc) return rc;
+  IVL_REQUIRE((((size_t)x | (size_t)wq | (size_t)y) & 15) == 0 && ((size_t)bias & 1) == 0 && ((size_t)sq & 3) == 0,
+              IVL_ERR_INVALID_ARG, "%s: x / wq / y must be 16-byte aligned, sq 4-byte aligned", who);
+  return m16_launch<W16Mxfp4>(x, wp, bias, y, M, N, K, glu, stream, who);
+}

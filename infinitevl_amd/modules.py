@@ -79,6 +79,7 @@ class InfiniteVLSelfAttention(nn.Module):
         self._fused_w = self._fused_b = None
         self._w8_qkv = self._w8_o = None    # ops.PackedWeight of the fused q|k|v weight and of o_proj (quantize_weights_)
         self._w8_on = False
+        self._wide_on = False               # InfiniteVLTextStack.use_wide_decode(): 5..16-row projections on ivl_linear_m16_fwd
         self._lora = None                   # ops.LoraTable with this layer's (layer_idx, "qkv") and (layer_idx, "o") (enable_adapters)
         self.mma_dtype = None           # None = bf16 operands; "fp8_e4m3": single-token decode products on e4m3 (configs[4])
 
@@ -126,7 +127,7 @@ class InfiniteVLSelfAttention(nn.Module):
         if self._fused_ok(hidden_states):
             nq, nkv = self.num_heads * self.head_dim, self.num_key_value_heads * self.head_dim
             qkv = ops.linear(hidden_states, self._fused_w, self._fused_b, **ops.w8_kwargs(self._w8_qkv, self._w8_on),
-                             **ops.lora_kwargs(self._lora, (self.layer_idx, "qkv")))                                  # [B,T,nq+2nkv]
+                             **ops.lora_kwargs(self._lora, (self.layer_idx, "qkv")), **ops.wide_kwargs(self._wide_on))    # [B,T,nq+2nkv]
             q = qkv[..., :nq].unflatten(-1, (self.num_heads, self.head_dim))
             k = qkv[..., nq:nq + nkv].unflatten(-1, (self.num_key_value_heads, self.head_dim))
             v = qkv[..., nq + nkv:].unflatten(-1, (self.num_key_value_heads, self.head_dim))
@@ -152,7 +153,7 @@ class InfiniteVLSelfAttention(nn.Module):
                                                   sliding_window=self.sliding_window)
         attn = attn.reshape(bsz, q_len, -1)
         return ops.linear(attn, self.o_proj.weight, self.o_proj.bias, **ops.w8_kwargs(self._w8_o, self._w8_on),
-                          **ops.lora_kwargs(self._lora, (self.layer_idx, "o"))), None
+                          **ops.lora_kwargs(self._lora, (self.layer_idx, "o")), **ops.wide_kwargs(self._wide_on)), None
 
     @torch.no_grad()
     def quantize_weights_(self, fmt: str = "e4m3") -> "InfiniteVLSelfAttention":
@@ -237,6 +238,7 @@ class GatedDeltaNet(nn.Module):
         self._gate32 = None
         self._w8_in = self._w8_o = None     # ops.PackedWeight of the fused in-projection and of o_proj (quantize_weights_)
         self._w8_on = False
+        self._wide_on = False               # as InfiniteVLSelfAttention._wide_on
         self._lora = None                   # ops.LoraTable with this layer's (layer_idx, "in") and (layer_idx, "o") (enable_adapters)
         self.mma_dtype = None           # None = the reference's bf16 operands; "fp8_e4m3" = BASELINE.json configs[4]
 
@@ -306,8 +308,9 @@ class GatedDeltaNet(nn.Module):
         Dq, Dk, Dv = H * K, self.key_dim, self.value_dim
         cq, ck, cv, cg, ca, cb = self._fused_cols
         w8_in, w8_o = ops.w8_kwargs(self._w8_in, self._w8_on), ops.w8_kwargs(self._w8_o, self._w8_on)
-        lora_o = ops.lora_kwargs(self._lora, (self.layer_idx, "o"))
-        proj = ops.linear(hidden_states, self._fused_w, **w8_in, **ops.lora_kwargs(self._lora, (self.layer_idx, "in")))   # [B,T,ld]
+        kw_o = {**ops.lora_kwargs(self._lora, (self.layer_idx, "o")), **ops.wide_kwargs(self._wide_on)}
+        proj = ops.linear(hidden_states, self._fused_w, **w8_in, **ops.lora_kwargs(self._lora, (self.layer_idx, "in")),
+                          **ops.wide_kwargs(self._wide_on))                                                                 # [B,T,ld]
         ld = proj.shape[-1]
         prev = (None, None, None)
         h0 = None
@@ -344,7 +347,7 @@ class GatedDeltaNet(nn.Module):
             past_key_values.update(layer_idx=self.layer_idx, key_states=None, value_states=None, conv_state=outs,
                                    recurrent_state=layer.recurrent_state,
                                    cache_kwargs={"op": "set", "delta_len": T, "cache_position": cache_position})
-            return ops.linear(o, self.o_proj.weight, self.o_proj.bias, **w8_o, **lora_o), None
+            return ops.linear(o, self.o_proj.weight, self.o_proj.bias, **w8_o, **kw_o), None
         convs = (self.q_conv1d.weight, self.k_conv1d.weight, self.v_conv1d.weight)
         if mode == "chunk" and Dk == Dq and K == 128 and V == 256 and convs[0].shape[-1] == 4:
             # convs + gates inside the chunk kernel's pre-pass: q / k / v / g / beta never reach HBM, one launch less
@@ -363,7 +366,7 @@ class GatedDeltaNet(nn.Module):
                                    recurrent_state=layer.recurrent_state,
                                    cache_kwargs={"op": "set", "delta_len": T, "cache_position": cache_position})
         o = ops.rmsnorm_swish_gate_strided(o, proj[..., cg:], ld, w, self.norm_eps)
-        return ops.linear(o.reshape(B, T, -1), self.o_proj.weight, self.o_proj.bias, **w8_o, **lora_o), None
+        return ops.linear(o.reshape(B, T, -1), self.o_proj.weight, self.o_proj.bias, **w8_o, **kw_o), None
 
     def forward(self, hidden_states: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
                 past_key_values=None, cache_position: Optional[torch.LongTensor] = None, **kwargs):

@@ -1184,14 +1184,67 @@ def _linear_swiglu_m256(x: torch.Tensor, w_gate_up: torch.Tensor, rows: int, I: 
     return y
 
 
+# ---- 16-row weight-stream projections for decode steps of 5 to 16 slots ------------------------------------------------
+# calls that took an ivl_linear_m16* entry point, per weight format (tests read it to know which kernel a call ran on)
+M16_CALLS = {"bf16": 0, "e4m3": 0, "mxfp4": 0}
+M16_ROWS = 16
+
+
+def wide_kwargs(on: bool) -> dict:
+    """The `wide=` argument of linear / linear_swiglu for a module: nothing at all unless the model's use_wide_decode() switch is on."""
+    return {"wide": True} if on else {}
+
+
+def _m16_applies(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], rows: int, K: int) -> bool:
+    """what the dispatch of linear / linear_swiglu asks of a call before it takes the 16-row kernel (rows 5..16 is the caller's)"""
+    return (x.is_cuda and x.dtype == torch.bfloat16 and weight.dtype == torch.bfloat16 and weight.dim() == 2 and weight.is_contiguous()
+            and weight.device == x.device and K >= 32 and K % 32 == 0 and x.shape[-1] == K and weight.shape[0] * K * 2 < (1 << 32)
+            and weight.data_ptr() % 16 == 0 and (not x.is_contiguous() or x.data_ptr() % 16 == 0) and (bias is None or (bias.dtype == torch.bfloat16 and bias.is_contiguous())))
+
+
+def linear_m16(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, *, glu: bool = False,
+               w8: Optional[PackedWeight] = None) -> torch.Tensor:
+    """y = x W^T (+ bias) for 1..16 rows of x on the MFMA weight-stream kernel ivl_linear_m16_fwd; glu=True: `weight` is the fused
+    gate|up weight [2I,K] and y = silu(gate) * up [.., I].  w8: the packed copy of `weight` (e4m3 or mxfp4) -- the packed twin of its
+    format streams it in place of the bf16 weight, the same bits.  The direct entry: the shape rules are the ABI's (1 <= rows <= 16,
+    K % 32 == 0, 16-byte aligned), and a call that breaks them raises; ops.linear / linear_swiglu take this kernel for 5..16 rows
+    under InfiniteVLTextStack.use_wide_decode()."""
+    _need_gpu(x, weight)
+    if w8 is not None:
+        w8.check(weight)
+    if x.dtype != torch.bfloat16 or weight.dtype != torch.bfloat16 or weight.dim() != 2 or not weight.is_contiguous():
+        raise ValueError(f"linear_m16: bf16 x and a contiguous bf16 [N,K] weight are expected; got {x.dtype}, {weight.dtype} "
+                         f"{tuple(weight.shape)}")
+    if bias is not None and (bias.dtype != torch.bfloat16 or not bias.is_contiguous()):
+        raise ValueError("linear_m16: a contiguous bf16 bias is expected")
+    R, K = weight.shape
+    if x.shape[-1] != K or (glu and R % 2):
+        raise ValueError(f"linear_m16: x {tuple(x.shape)} does not meet a weight {tuple(weight.shape)} (glu={glu})")
+    N = R // 2 if glu else R
+    rows = x.numel() // K if K else 0
+    xc = x if x.is_contiguous() else x.contiguous()
+    y = torch.empty(*x.shape[:-1], N, dtype=torch.bfloat16, device=x.device)
+    lib, bp = _lib.load(), _p(bias) if bias is not None else None
+    if w8 is not None:
+        fn = lib.ivl_linear_m16_w4_fwd if w8.fmt == "mxfp4" else lib.ivl_linear_m16_w8_fwd
+        _lib.check(fn(_p(xc), _p(w8.codes), _p(w8.scale), bp, _p(y), rows, N, K, 1 if glu else 0, _stream(x)))
+        M16_CALLS[w8.fmt] += 1
+        return y
+    _lib.check(lib.ivl_linear_m16_fwd(_p(xc), _p(weight), bp, _p(y), rows, N, K, 1 if glu else 0, _stream(x)))
+    M16_CALLS["bf16"] += 1
+    return y
+
+
 def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, w8: Optional[PackedWeight] = None,
-           lora=None) -> torch.Tensor:
+           lora=None, wide: bool = False) -> torch.Tensor:
     """nn.Linear forward.  A single-token decode step (<= 4 rows) is a pure weight stream and goes through
     ivl_linear_small_m_fwd; longer calls are stock library GEMMs (hipBLASLt / rocBLAS through torch), which
     SURVEY.md 8(d) keeps outside the hot path.  w8: the packed copy of `weight` (which then holds W'), e4m3 or mxfp4 -- the call
     dispatches on its format: the weight stream reads it in place of the bf16 weight -- the same bits, a half or a quarter of the
     bytes; every other path reads `weight` as ever.  lora: (LoraTable, key, rows) -- the base call as without it, then lora_add on
-    its output (the NORM form reads the PreNorm's x / residual)."""
+    its output (the NORM form reads the PreNorm's x / residual).  wide: the model's use_wide_decode() switch -- a call of 5..16 rows
+    that meets the shape rules of ivl_linear_m16_fwd takes that kernel (with w8: the packed twin) instead of the library GEMM; calls
+    with a lora table never do."""
     if lora is not None:
         y = linear(x, weight, bias, w8=w8)
         return lora_add(y if y.is_contiguous() else y.contiguous(), x, *lora)
@@ -1218,15 +1271,19 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] =
         _lib.check(_lib.load().ivl_linear_small_m_fwd(_p(xc), _p(weight), _p(bias) if bias is not None else None,
                                                       _p(y), rows, N, K, _stream(x)))
         return y
+    if wide and 4 < rows <= M16_ROWS and _m16_applies(x, weight, bias, rows, K):
+        return linear_m16(x, weight, bias, w8=w8)
     return torch.nn.functional.linear(x, weight, bias)
 
 
-def linear_swiglu(x: torch.Tensor, w_gate_up: torch.Tensor, w8: Optional[PackedWeight] = None, lora=None) -> torch.Tensor:
+def linear_swiglu(x: torch.Tensor, w_gate_up: torch.Tensor, w8: Optional[PackedWeight] = None, lora=None,
+                  wide: bool = False) -> torch.Tensor:
     """silu(gate_proj(x)) * up_proj(x) with the fused gate|up weight [2I, K] (std:945).  Decode steps (<= 4 rows)
     apply the gate in the epilogue of the weight-stream kernel, and so does the 256-row kernel of a prefill chunk
     (ivl_linear_m256_fwd); other calls are a library GEMM + silu_mul.  w8: as in `linear`.  lora: (LoraTable, key, rows) with the
     two segments gate | up -- the plain projection on the fused weight, lora_add, then silu_mul: the header guarantees linear +
-    ivl_silu_mul_fwd == the GLU forms bit for bit, so rows without an adapter keep their bits."""
+    ivl_silu_mul_fwd == the GLU forms bit for bit, so rows without an adapter keep their bits.  wide: as in `linear` (the
+    gate then runs in the epilogue of ivl_linear_m16_fwd)."""
     if lora is not None:
         return silu_mul(linear(x, w_gate_up, w8=w8, lora=lora))
     if w8 is not None:
@@ -1252,6 +1309,8 @@ def linear_swiglu(x: torch.Tensor, w_gate_up: torch.Tensor, w8: Optional[PackedW
         return y
     if _m256_swiglu_applies(x, w_gate_up, rows, I, K):
         return _linear_swiglu_m256(x, w_gate_up, rows, I, K)
+    if wide and 4 < rows <= M16_ROWS and w_gate_up.shape[0] % 2 == 0 and _m16_applies(x, w_gate_up, None, rows, K):
+        return linear_m16(x, w_gate_up, glu=True, w8=w8)
     return silu_mul(linear(x, w_gate_up))
 
 

@@ -85,6 +85,16 @@ rounds.  Then ops.lora_add alone on every projection of a decode token (both lau
 where the model takes it), M = 1 and M = 4, the calls of a leg captured in one graph: us per call.  Nothing is asserted.
 
     python tools/multistream_decode.py --lora --slots 1,4 [--out profiles/lora_decode.json]
+
+--wide: the opt-in 16-row weight-stream projections (InfiniteVLTextStack.use_wide_decode) in the captured greedy step of
+8 and 16 slots (the four prompt lengths, repeated).  A: the switch off -- above four rows every projection is a library GEMM (with
+the package's tunable-op file, as in every mode of this tool) and the SwiGLU gate a launch of its own; B: the switch on, bf16
+weights; C: on, e4m3 copies; D: on, mxfp4 copies (lm_head=True in C and D); three models of the same shape, timed A B C D per
+round with the 4-slot small-M step of the same process as the reference point, median of --rounds rounds of --steps replays: ms
+per captured step (= ms per token per stream) and aggregate tok/s.  Then the seven projection shapes of a decode token alone at
+M = 8 and M = 16: the library, bf16, e4m3, mxfp4 -- us per call and achieved GB/s of weight bytes.  Nothing is asserted.
+
+    python tools/multistream_decode.py --wide --slots 8,16 [--out profiles/wide_decode.json]
 """
 import argparse
 import json
@@ -113,6 +123,7 @@ def main():
     ap.add_argument("--w8", action="store_true", help="time the step on packed e4m3 weights against the bf16 step (see above)")
     ap.add_argument("--w4", action="store_true", help="time the step on packed mxfp4 weights against the e4m3 and bf16 steps (see above)")
     ap.add_argument("--lora", action="store_true", help="time the step with per-slot LoRA adapters against the step without (see above)")
+    ap.add_argument("--wide", action="store_true", help="time the 8- and 16-slot step on the 16-row weight-stream kernel (see above)")
     args = ap.parse_args()
     import torch
     from infinitevl_amd.cache import MultiStreamCache
@@ -157,6 +168,8 @@ def main():
         return w4_legs(args, torch, model, cfg, prompts, dev)
     if args.lora:
         return lora_legs(args, torch, model, cfg, prompts, dev)
+    if args.wide:
+        return wide_legs(args, torch, model, cfg, prompts, dev)
 
     # reference: one stream on the existing B = 1 graphed decode step
     c1 = model.allocate_inference_cache(1)
@@ -769,6 +782,142 @@ def w4_legs(args, torch, model, cfg, prompts, dev):
     model.use_packed_weights(True)
     del model8
     res["operators"] = w8_operator_legs(args, torch, cfg, dev, timed, fmts=("bf16", "w8", "w4"))
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+def wide_operator_legs(args, torch, cfg, dev, timed):
+    """the seven projection shapes of a decode token at M = 8 and M = 16: the library GEMM (torch.nn.functional.linear, + ops.silu_mul
+    for gate|up: what ops.linear / linear_swiglu run with the switch off) against ivl_linear_m16_fwd and its e4m3 / mxfp4 twins, us
+    per call and achieved GB/s of the weight bytes each format streams; A B C D A B C D per round, `reps` calls per captured graph
+    over enough copies of the weight (>= 1 GB of bf16) that no call finds it in a cache"""
+    from infinitevl_amd import ops
+    hd, I, V = cfg.hidden_size, cfg.intermediate_size, cfg.vocab_size
+    shapes = [("qkv", 2560, hd, False), ("gdn_in", 12320, hd, False), ("attn_o_proj", hd, 2048, False), ("gdn_o_proj", hd, 4096, False),
+              ("gate_up", 2 * I, hd, True), ("down", hd, I, False), ("lm_head", V, hd, False)]
+    fmts = ("lib", "bf16", "e4m3", "mxfp4")
+    bytes_per_weight = {"lib": 2.0, "bf16": 2.0, "e4m3": 1.0, "mxfp4": 0.5 + 1.0 / 32}
+    gen = torch.Generator(device=dev).manual_seed(2)
+    out = {}
+    for name, R, K, glu in shapes:
+        copies = max(2, -(-(1 << 30) // (R * K * 2)))
+        ws, packs = [], {"e4m3": [], "mxfp4": []}
+        w0 = (torch.randn(R, K, generator=gen, device=dev) * 0.02).to(torch.bfloat16)
+        for _ in range(copies):                              # (the speed of a stream does not depend on the values: one draw, copied)
+            w = w0.clone()
+            ws.append(w)
+            codes, _, scale = ops.quantize_rows_e4m3(w)
+            packs["e4m3"].append(ops.PackedWeight(w, codes, scale))
+            packs["mxfp4"].append(ops.PackedWeight(w, *ops.mxfp4_shuffle(*ops.quantize_rows_mxfp4(w)[:2]), fmt="mxfp4"))
+        row = {"weight_rows": R, "K": K, "glu": glu, "copies": copies}
+        for M in (8, 16):
+            x = (torch.randn(M, K, generator=gen, device=dev) * 0.5).to(torch.bfloat16)
+            state = {"i": 0}
+
+            def call(fmt):
+                i = state["i"] = (state["i"] + 1) % copies
+                if fmt == "lib":
+                    y = torch.nn.functional.linear(x, ws[i])
+                    return ops.silu_mul(y) if glu else y
+                return ops.linear_m16(x, ws[i], glu=glu, w8=None if fmt == "bf16" else packs[fmt][i])
+
+            reps = max(8, min(128, 2 * copies))
+            graphs = {}
+            with torch.no_grad():
+                for fmt in fmts:
+                    call(fmt)
+                    torch.cuda.synchronize()
+                    graphs[fmt] = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(graphs[fmt]):
+                        for _ in range(reps):
+                            call(fmt)
+            t = {fmt: [] for fmt in fmts}
+            for _ in range(args.rounds):
+                for fmt in fmts + fmts:
+                    t[fmt].append(timed(graphs[fmt].replay, 4) / reps)
+            med = {fmt: statistics.median(t[fmt]) for fmt in fmts}
+            del graphs
+            cell = {f"{fmt}_us": round(1000 * med[fmt], 2) for fmt in fmts}
+            cell.update({f"{fmt}_over_lib": round(med[fmt] / med["lib"], 3) for fmt in fmts[1:]})
+            cell.update({f"{fmt}_GBs": round(R * K * bytes_per_weight[fmt] / (med[fmt] * 1e-3) / 1e9, 1) for fmt in fmts})
+            row[f"M{M}"] = cell
+        out[name] = row
+        print(name, row, file=sys.stderr, flush=True)
+        del ws, packs
+    return out
+
+
+def wide_legs(args, torch, model, cfg, prompts, dev):
+    """A B C D per round in one process.  A: the captured greedy step with the switch off (library GEMMs above four rows: the step as
+    it is without this option); B: use_wide_decode() on the bf16 weights; C: on e4m3 copies; D: on mxfp4 copies (lm_head=True for
+    both).  Three models of the same shape (a captured step holds the pointers of ITS packed copies); the 4-slot small-M step of the
+    bf16 model is timed in every round as the reference point."""
+    from infinitevl_amd.cache import MultiStreamCache
+    from infinitevl_amd.harness import GraphedMultiStreamDecode, InfiniteVLTextStack
+    stream = torch.cuda.current_stream()
+
+    def timed(fn, n):
+        for _ in range(4):
+            fn()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        for _ in range(n):
+            fn()
+        e1.record(stream)
+        e1.synchronize()
+        return e0.elapsed_time(e1) / n
+
+    def packed_model(fmt):
+        with torch.device(dev):
+            torch.set_default_dtype(torch.bfloat16)
+            m = InfiniteVLTextStack(cfg)
+            torch.set_default_dtype(torch.float32)
+        return m.to(torch.bfloat16).eval().init_weights_(seed=0).fuse_().quantize_weights_(lm_head=True, fmt=fmt)
+
+    def decoder(m, wide, n):
+        m.use_wide_decode(wide)
+        dec = GraphedMultiStreamDecode(m, MultiStreamCache(config=cfg, n_slots=n, device=dev, dtype=torch.bfloat16))
+        for s in range(n):
+            dec.admit(s, prompts[s % len(prompts)])
+        dec.capture()
+        return dec
+
+    model8, model4 = packed_model("e4m3"), packed_model("mxfp4")
+    slots = [int(s) for s in args.slots.split(",")]
+    res = {"tool": "multistream_decode --wide", "layers": cfg.num_hidden_layers, "window": 4096, "steps": args.steps, "rounds": args.rounds,
+           "legs": "A = switch off (library GEMMs); B = use_wide_decode, bf16; C = use_wide_decode, e4m3 copies; D = use_wide_decode, "
+                   "mxfp4 copies (lm_head packed in C and D); ref4 = the 4-slot small-M step of the bf16 model", "bar": "none asserted"}
+    ref4 = decoder(model, False, 4)
+    for n in slots:
+        decs = {"A": (decoder(model, False, n), model, False), "B": (decoder(model, True, n), model, True),
+                "C": (decoder(model8, True, n), model8, True), "D": (decoder(model4, True, n), model4, True)}
+        times = {k: [] for k in ("ref4", "A", "B", "C", "D")}
+        for _ in range(args.rounds):
+            model.use_wide_decode(False)
+            times["ref4"].append(timed(ref4.step, args.steps))
+            for name in ("A", "B", "C", "D"):
+                dec, m, wide = decs[name]
+                m.use_wide_decode(wide)                         # (a host flag: the step would recapture on a mismatch)
+                times[name].append(timed(dec.step, args.steps))
+        med = {k: statistics.median(v) for k, v in times.items()}
+        cell = {}
+        for k, v in med.items():
+            rows = 4 if k == "ref4" else n
+            cell[k] = {"ms_per_step": round(v, 4), "aggregate_tok_s": round(1000.0 * rows / v, 1), "ms_per_token_per_stream": round(v, 4),
+                       "spread_ms": [round(min(times[k]), 4), round(max(times[k]), 4)]}
+        cell.update(B_over_A=round(med["B"] / med["A"], 4), C_over_B=round(med["C"] / med["B"], 4), D_over_B=round(med["D"] / med["B"], 4),
+                    D_over_A=round(med["D"] / med["A"], 4))
+        res[f"slots{n}"] = cell
+        print(f"slots{n}: " + " ".join(f"{k} {v:.4f}" for k, v in med.items()) + " ms", file=sys.stderr, flush=True)
+        del decs
+    for m in (model, model8, model4):
+        m.use_wide_decode(False)
+    del ref4, model8, model4
+    res["operators"] = wide_operator_legs(args, torch, cfg, dev, timed)
     line = json.dumps(res)
     print(line)
     if args.out:
