@@ -544,6 +544,42 @@ IVL_API int ivl_linear_m16_w4_fwd(const void* x, const void* wq, const void* sq,
                                   int glu, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * PER-ROW LoRA ADAPTERS FOR 5 TO 16 ROWS (the args, chain, segments, rank padding and NOT TOUCHED rule of
+ * ivl_lora_add_small_m_fwd above, its t order included; t_ws is bf16 [16, 512] here).
+ *
+ * ivl_lora_add_m16_fwd: the two-launch form (shrink on a grid of (ceil(n_seg R / 8), M), expand-add) for 1 <= M <= 16.  There is no
+ * NORM group -- the 5..16-row step materialises its norms: norm_weight != NULL is IVL_ERR_UNSUPPORTED, residual without a norm
+ * weight IVL_ERR_INVALID_ARG as above; M outside 1..16 is IVL_ERR_UNSUPPORTED; every other refusal is the small-M entry's, checked
+ * before any launch.
+ *  L1. Row m of y and of t_ws equals what ivl_lora_add_small_m_fwd writes for that row called alone (M = 1, its x row, y row and
+ *      index), bit for bit: independent of M, of the row's position and of the other rows' contents and adapters.
+ *  L2. A row with an index outside [0, n_adapters) and a column in no segment are not read-modify-written (-0.0 keeps its sign);
+ *      t_ws keeps its contents outside the rows and rank rows of the call.
+ *  L3. The same bits eager or replayed.
+ *
+ * ivl_linear_m16_lora_fwd / _w8_fwd / _w4_fwd: the argument lists of the three ivl_linear_m16* entries plus `lora`.  Two launches:
+ * the shrink of the x rows into lora->t_ws, then the m16 kernel with a LoRA epilogue -- after the LDS combine and the bias the lane
+ * that owns an element forms y0 = bf16(acc + bias) and, where its row has an adapter and its WEIGHT ROW lies in a segment, applies
+ * d, e and the add above; with glu != 0 to the gate row c and the up row I + c, before the gate.
+ *   lora->x, y, M and K must be the call's; lora->N must be the number of weight rows (N, or 2N with glu: the segments live in the
+ *   fused row space); the norm fields must be NULL; lora and every table pointer non-NULL: else IVL_ERR_INVALID_ARG.  The refusals of
+ *   the m16 entries come first and are unchanged; those of ivl_lora_add_m16_fwd follow; all before any launch.
+ *  F1. glu == 0: y and t_ws equal ivl_linear_m16*_fwd(glu = 0) followed by ivl_lora_add_m16_fwd on its output, bit for bit -- in
+ *      both tile modes, with N tails, for every weight format.
+ *  F2. glu != 0: equals the glu == 0 call of the same entry on the fused weight (N -> 2N) followed by ivl_silu_mul_fwd, bit for bit.
+ *  F3. A row without an adapter and a column in no segment carry the bits of ivl_linear_m16*_fwd.
+ *  F4. Contracts 1 to 3 of the m16 block carry over: determinism; row m depends on row m of x and on adapter_idx[m] only; packed
+ *      equals bf16 on W'.
+ * ------------------------------------------------------------------------------------------- */
+IVL_API int ivl_lora_add_m16_fwd(const ivl_lora_args* args, void* stream);
+IVL_API int ivl_linear_m16_lora_fwd(const void* x, const void* w, const void* bias, void* y, int M, int N, int K, int glu,
+                                    const ivl_lora_args* lora, void* stream);
+IVL_API int ivl_linear_m16_lora_w8_fwd(const void* x, const void* wq, const float* scale, const void* bias, void* y, int M, int N,
+                                       int K, int glu, const ivl_lora_args* lora, void* stream);
+IVL_API int ivl_linear_m16_lora_w4_fwd(const void* x, const void* wq, const void* sq, const void* bias, void* y, int M, int N, int K,
+                                       int glu, const ivl_lora_args* lora, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Scoring GIVEN tokens under lm_head: the log-probability of target[r] in the distribution of row r, the [M,N] logits never
  * written anywhere.  Replaces logits -> float log_softmax -> gather (HF `labels=`, CrossEntropyLoss(reduction="none") of
  * scripts/stat_utils/cal_ppl.py:111-124, `echo` + `logprobs` of the OpenAI protocol, likelihood ranking of candidate answers).

@@ -28,7 +28,7 @@
 // x comes straight from L2 in fragment shape (16 rows x 64 B per load instruction): it is at most 16 x 11008 bf16 = 352 KB and is
 // re-read by every tile -- at M = 16 as many bytes as the bf16 weights themselves; a wave of a wide plain projection therefore owns
 // two tiles per x fragment (M16_PAIR), as the GLU form does by construction.  Staging x in LDS was not built.
-#include "ivl_rowwise.h"
+#include "ivl_lora.h"
 
 namespace ivl {
 
@@ -118,10 +118,24 @@ static bool m16_pair(int R) { return R >= 8192; }
 // M16_PAIR: two adjacent tiles (32 columns) of a plain projection, which halves the x fragments read per weight byte.  ONE or PAIR is a
 // choice of speed: every output element is the same sum in the same order in both.
 enum { M16_ONE = 0, M16_GLU = 1, M16_PAIR = 2 };
-template <class WT, int MODE>
+
+// LORA: the per-row adapter's expand-add in the epilogue -- after the LDS combine and the bias, the slice-0 lane that owns
+// x row r16 forms y0 = bf16(acc + bias) of each of its columns and, where adapter_idx[r16] is valid and the column's WEIGHT ROW (GLU:
+// c and I + c of the fused gate|up rows) lies in a segment, replaces it by lora_expand_ on that row of B and t_ws[r16] (written by the
+// shrink launch in front); the gate then runs on the adapted gate and up values.  The tables travel as ONE trailing by-value argument
+// that the LORA = false instantiations do not have: their signature, and their code, are what they were.
+struct M16Lora {
+  const int* idx; const bf16_t* B; const float* scaling; const bf16_t* t_ws;
+  int n_adapters, n_seg, R, rows;                  // rows: weight rows = the N of the adapter tables
+  LoraSegs segs;
+};
+template <class T> __device__ __forceinline__ const T& m16_first(const T& t) { return t; }
+
+template <class WT, int MODE, bool LORA = false, class... LP>
 __global__ __launch_bounds__(64 * M16_KS) void linear_m16_kernel(const bf16_t* __restrict__ x, typename WT::arg w,
                                                                    const bf16_t* __restrict__ bias, bf16_t* __restrict__ y, int M, int N,
-                                                                   int K, int per) {
+                                                                   int K, int per, LP... lp) {
+  static_assert(sizeof...(LP) == (LORA ? 1 : 0), "the LoRA tables are the one trailing argument of the LORA form");
   constexpr bool GLU = MODE == M16_GLU;
   constexpr int NA = MODE == M16_ONE ? 1 : 2;      // accumulators (tiles) per wave
   constexpr int COLS = MODE == M16_PAIR ? 32 : 16; // output columns per wave
@@ -181,6 +195,21 @@ __global__ __launch_bounds__(64 * M16_KS) void linear_m16_kernel(const bf16_t* _
     for (int a = 0; a < NA; ++a) acc[a] += s_part[k][a][lane];
 
   if (!mlive) return;
+  // LORA: v = acc + bias of weight row `row` -> bf16(v), or the adapted value where the row of x has an adapter and `row` a segment
+  [[maybe_unused]] auto adapt = [&](float v, int row) -> float {
+    if constexpr (LORA) {
+      const M16Lora& L = m16_first(lp...);
+      v = bf_round(v);
+      const int ad = L.idx[r16];
+      if ((unsigned int)ad >= (unsigned int)L.n_adapters) return v;               // a row without an adapter: the base bits
+      const int seg = lora_seg_of_(row, L.n_seg, L.segs);
+      if (seg < 0) return v;                                                      // a column in no segment
+      return lora_expand_(v, (const u32x4*)(L.B + ((size_t)ad * L.rows + row) * L.R),
+                          (const u32x4*)(L.t_ws + r16 * LORA_T_LD + seg * L.R), L.R >> 3, L.scaling[ad]);
+    } else {
+      return v;
+    }
+  };
 #pragma unroll
   for (int a = 0; a < (GLU ? 1 : NA); ++a) {
   const int n = n0 + 16 * a + 4 * g;               // this lane: x row r16, output columns n .. n + 3
@@ -191,8 +220,13 @@ __global__ __launch_bounds__(64 * M16_KS) void linear_m16_kernel(const bf16_t* _
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int col = min(n + r, N - 1);
+      if constexpr (LORA) {
+        gt[r] = adapt(acc[0][r] + (bias != nullptr ? bf2f(bias[col]) : 0.f), col);
+        o[r] = adapt(acc[1][r] + (bias != nullptr ? bf2f(bias[N + col]) : 0.f), N + col);
+      } else {
       gt[r] = bf_round(acc[0][r] + (bias != nullptr ? bf2f(bias[col]) : 0.f));                    // gate_proj output
       o[r] = bf_round(acc[1][r] + (bias != nullptr ? bf2f(bias[N + col]) : 0.f));                 // up_proj output
+      }
     }
     siluf_n_(gt, sg);
 #pragma unroll
@@ -200,6 +234,10 @@ __global__ __launch_bounds__(64 * M16_KS) void linear_m16_kernel(const bf16_t* _
   } else {
 #pragma unroll
     for (int r = 0; r < 4; ++r) o[r] = acc[a][r] + (bias != nullptr ? bf2f(bias[min(n + r, N - 1)]) : 0.f);
+    if constexpr (LORA) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) o[r] = adapt(o[r], min(n + r, N - 1));
+    }
   }
   bf16_t* yp = y + (size_t)r16 * N + n;
   if ((N & 3) == 0) {                              // (n is a multiple of 4: the four columns exist and the piece is 8-byte aligned)
@@ -227,18 +265,46 @@ static int m16_check(const char* who, const void* x, typename WT::arg wp, const 
   return IVL_OK;
 }
 
-template <class WT>
+// LP: nothing, or the M16Lora of the LORA form
+template <class WT, class... LP>
 static int m16_launch(const void* x, typename WT::arg wp, const void* bias, void* y, int M, int N, int K, int glu, void* stream,
-                      const char* who) {
+                      const char* who, LP... lp) {
+  constexpr bool LORA = sizeof...(LP) != 0;
   const int R = glu ? 2 * N : N;
   const int per = (m16_steps(K) + M16_KS - 1) / M16_KS;
   const bool pair = !glu && m16_pair(R);
   const dim3 grid((N + (pair ? 31 : 15)) / (pair ? 32 : 16)), block(64 * M16_KS);       // one range of output columns per workgroup
   hipStream_t st = (hipStream_t)stream;
   const bf16_t *xp = (const bf16_t*)x, *bp = (const bf16_t*)bias;
-  if (glu) hipLaunchKernelGGL((linear_m16_kernel<WT, M16_GLU>), grid, block, 0, st, xp, wp, bp, (bf16_t*)y, M, N, K, per);
-  else if (pair) hipLaunchKernelGGL((linear_m16_kernel<WT, M16_PAIR>), grid, block, 0, st, xp, wp, bp, (bf16_t*)y, M, N, K, per);
-  else hipLaunchKernelGGL((linear_m16_kernel<WT, M16_ONE>), grid, block, 0, st, xp, wp, bp, (bf16_t*)y, M, N, K, per);
+  if (glu) hipLaunchKernelGGL((linear_m16_kernel<WT, M16_GLU, LORA, LP...>), grid, block, 0, st, xp, wp, bp, (bf16_t*)y, M, N, K, per, lp...);
+  else if (pair) hipLaunchKernelGGL((linear_m16_kernel<WT, M16_PAIR, LORA, LP...>), grid, block, 0, st, xp, wp, bp, (bf16_t*)y, M, N, K, per, lp...);
+  else hipLaunchKernelGGL((linear_m16_kernel<WT, M16_ONE, LORA, LP...>), grid, block, 0, st, xp, wp, bp, (bf16_t*)y, M, N, K, per, lp...);
+  return check_launch(who);
+}
+
+// The LORA form of an entry: the refusals that tie `lora` to the base call (after the base entry's own), those of the LoRA entries,
+// then the shrink of the x rows into lora->t_ws and the m16 kernel with the LoRA epilogue.
+static int m16_lora_check(const char* who, const ivl_lora_args* lora, const void* x, const void* y, int M, int N, int K, int glu,
+                          M16Lora& L) {
+  IVL_REQUIRE(lora != nullptr, IVL_ERR_INVALID_ARG, "%s: NULL lora", who);
+  IVL_REQUIRE(lora->adapter_idx && lora->A && lora->B && lora->scaling && lora->t_ws, IVL_ERR_INVALID_ARG,
+              "%s: NULL pointer in lora (adapter_idx, A, B, scaling and t_ws are all required)", who);
+  IVL_REQUIRE(lora->x == x && lora->y == y && lora->M == M && lora->K == K, IVL_ERR_INVALID_ARG,
+              "%s: lora->x, y, M=%d and K=%d must be the call's (M=%d, K=%d)", who, lora->M, lora->K, M, K);
+  IVL_REQUIRE(lora->N == (glu ? 2 * N : N), IVL_ERR_INVALID_ARG, "%s: lora->N=%d must be the number of weight rows, %d", who, lora->N,
+              glu ? 2 * N : N);
+  IVL_REQUIRE(lora->norm_weight == nullptr && lora->residual == nullptr, IVL_ERR_INVALID_ARG,
+              "%s: the norm fields of lora must be NULL (no NORM group)", who);
+  const int rc = lora_check(who, lora, 16, false, L.segs);
+  if (rc != IVL_OK) return rc;
+  L.idx = (const int*)lora->adapter_idx; L.B = (const bf16_t*)lora->B; L.scaling = lora->scaling; L.t_ws = (const bf16_t*)lora->t_ws;
+  L.n_adapters = lora->n_adapters; L.n_seg = lora->n_seg; L.R = lora->R; L.rows = lora->N;
+  return IVL_OK;
+}
+
+static int m16_lora_shrink(const char* who, const ivl_lora_args* lora, void* stream) {
+  lora_launch_shrink((const bf16_t*)lora->x, (const int*)lora->adapter_idx, (const bf16_t*)lora->A, (bf16_t*)lora->t_ws, lora->M, lora->K,
+                     lora->n_seg * lora->R, lora->n_adapters, (hipStream_t)stream);
   return check_launch(who);
 }
 
@@ -275,4 +341,46 @@ extern "C" int ivl_linear_m16_w4_fwd(const void* x, const void* wq, const void* 
   IVL_REQUIRE((((size_t)x | (size_t)wq | (size_t)y) & 15) == 0 && ((size_t)bias & 1) == 0 && ((size_t)sq & 3) == 0,
               IVL_ERR_INVALID_ARG, "%s: x / wq / y must be 16-byte aligned, sq 4-byte aligned", who);
   return m16_launch<W16Mxfp4>(x, wp, bias, y, M, N, K, glu, stream, who);
+}
+
+// ---- the LORA forms: the argument lists above plus the adapter tables; two launches (shrink, then the kernel with the LoRA epilogue)
+extern "C" int ivl_linear_m16_lora_fwd(const void* x, const void* w, const void* bias, void* y, int M, int N, int K, int glu,
+                                       const ivl_lora_args* lora, void* stream) {
+  const char* who = "ivl_linear_m16_lora_fwd";
+  int rc = m16_check<W16Bf16>(who, x, (const bf16_t*)w, y, M, N, K, glu, (size_t)(K > 0 ? K : 0) * 2);
+  if (rc) return rc;
+  IVL_REQUIRE((((size_t)x | (size_t)w | (size_t)y) & 15) == 0 && ((size_t)bias & 1) == 0, IVL_ERR_INVALID_ARG,
+              "%s: x / w / y must be 16-byte aligned", who);
+  M16Lora L;
+  if ((rc = m16_lora_check(who, lora, x, y, M, N, K, glu, L)) != IVL_OK) return rc;
+  if ((rc = m16_lora_shrink("ivl_linear_m16_lora_fwd (shrink)", lora, stream)) != IVL_OK) return rc;
+  return m16_launch<W16Bf16>(x, (const bf16_t*)w, bias, y, M, N, K, glu, stream, who, L);
+}
+
+extern "C" int ivl_linear_m16_lora_w8_fwd(const void* x, const void* wq, const float* scale, const void* bias, void* y, int M, int N,
+                                          int K, int glu, const ivl_lora_args* lora, void* stream) {
+  const char* who = "ivl_linear_m16_lora_w8_fwd";
+  const W16Arg8 wp{(const unsigned char*)wq, scale};
+  int rc = m16_check<W16E4m3>(who, x, wp, y, M, N, K, glu, (size_t)(K > 0 ? K : 0));
+  if (rc) return rc;
+  IVL_REQUIRE((((size_t)x | (size_t)wq | (size_t)y) & 15) == 0 && ((size_t)bias & 1) == 0 && ((size_t)scale & 3) == 0,
+              IVL_ERR_INVALID_ARG, "%s: x / wq / y must be 16-byte aligned, scale 4-byte aligned", who);
+  M16Lora L;
+  if ((rc = m16_lora_check(who, lora, x, y, M, N, K, glu, L)) != IVL_OK) return rc;
+  if ((rc = m16_lora_shrink("ivl_linear_m16_lora_w8_fwd (shrink)", lora, stream)) != IVL_OK) return rc;
+  return m16_launch<W16E4m3>(x, wp, bias, y, M, N, K, glu, stream, who, L);
+}
+
+extern "C" int ivl_linear_m16_lora_w4_fwd(const void* x, const void* wq, const void* sq, const void* bias, void* y, int M, int N, int K,
+                                          int glu, const ivl_lora_args* lora, void* stream) {
+  const char* who = "ivl_linear_m16_lora_w4_fwd";
+  const W16Arg4 wp{(const unsigned char*)wq, (const unsigned char*)sq};
+  int rc = m16_check<W16Mxfp4>(who, x, wp, y, M, N, K, glu, (size_t)(K > 0 ? W16Mxfp4::kp(K) >> 1 : 0));
+  if (rc) return rc;
+  IVL_REQUIRE((((size_t)x | (size_t)wq | (size_t)y) & 15) == 0 && ((size_t)bias & 1) == 0 && ((size_t)sq & 3) == 0,
+              IVL_ERR_INVALID_ARG, "%s: x / wq / y must be 16-byte aligned, sq 4-byte aligned", who);
+  M16Lora L;
+  if ((rc = m16_lora_check(who, lora, x, y, M, N, K, glu, L)) != IVL_OK) return rc;
+  if ((rc = m16_lora_shrink("ivl_linear_m16_lora_w4_fwd (shrink)", lora, stream)) != IVL_OK) return rc;
+  return m16_launch<W16Mxfp4>(x, wp, bias, y, M, N, K, glu, stream, who, L);
 }

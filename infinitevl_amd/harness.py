@@ -116,6 +116,7 @@ class InfiniteVLTextMLP(nn.Module):
         self._w8_gu = self._w8_down = None  # ops.PackedWeight of the fused gate|up weight and of down_proj (quantize_weights_)
         self._w8_on = False
         self._wide_on = False               # InfiniteVLTextStack.use_wide_decode()
+        self._wide_lora = False             # use_wide_decode(adapters=True)
         self._lora, self._lora_layer = None, None   # ops.LoraTable with (layer, "gu") and (layer, "down") (enable_adapters)
 
     @torch.no_grad()
@@ -150,7 +151,7 @@ class InfiniteVLTextMLP(nn.Module):
         if (self._fused_w is not None and x.is_cuda and x.dtype == torch.bfloat16
                 and self.gate_proj.weight.data_ptr() == self._fused_w.data_ptr()):
             w8_gu, w8_down = ops.w8_kwargs(self._w8_gu, self._w8_on), ops.w8_kwargs(self._w8_down, self._w8_on)
-            wide = ops.wide_kwargs(self._wide_on)
+            wide = ops.wide_kwargs(self._wide_on, self._wide_lora)
             return ops.linear(ops.linear_swiglu(x, self._fused_w, **w8_gu, **ops.lora_kwargs(self._lora, (self._lora_layer, "gu")), **wide),
                               self.down_proj.weight, **w8_down, **ops.lora_kwargs(self._lora, (self._lora_layer, "down")), **wide)
         if self._lora is not None:
@@ -201,6 +202,7 @@ class InfiniteVLTextStack(nn.Module):
         self._w8_on = False
         self._w8_fmt = None                     # the format of the packed copies: "e4m3" / "mxfp4" (quantize_weights_)
         self._wide_on = False                   # use_wide_decode(): projections of 5..16 rows on ivl_linear_m16_fwd
+        self._wide_lora = False                 # use_wide_decode(adapters=True): also while an adapter table is attached
         self._lora = None                      # ops.LoraTable of every projection (enable_adapters)
         self._lora_names = {}                   # {"layers.3.self_attn.q_proj": (key, segment)}
 
@@ -271,17 +273,24 @@ class InfiniteVLTextStack(nn.Module):
             layer.self_attn._w8_on = layer.mlp._w8_on = self._w8_on
         return self
 
-    def use_wide_decode(self, on: bool = True) -> "InfiniteVLTextStack":
+    def use_wide_decode(self, on: bool = True, adapters: bool = False) -> "InfiniteVLTextStack":
         """Opt in (after fuse_(); off by default) to the 16-row weight-stream kernel for decode steps of 5 to 16 slots:
         while it is on, every projection of this model -- q|k|v, the GDN in-projection, both o_proj, gate|up with its SwiGLU gate,
         down_proj and the tied lm_head -- that is called with 5..16 rows of bf16 on the device (K % 32 == 0) runs on
         ivl_linear_m16_fwd instead of the library GEMM, and with use_packed_weights(True) on the packed twin of the copies' format:
         one fixed summation order per output element, so a stream's logits are the same bits alone or among neighbours, in any slot,
-        eager or replayed, packed or not.  Calls of 1..4 rows, of more than 16 rows, and every call while an adapter table is
-        attached (enable_adapters) keep their paths.  Call it before a capture: a graphed class recaptures when the switch changed."""
+        eager or replayed, packed or not.  Calls of 1..4 rows and of more than 16 rows keep their paths, and so does every call
+        while an adapter table is attached (enable_adapters) unless adapters=True: then the 5..16-row projections
+        under a table run on the kernel too, each row's adapter added behind it by ivl_lora_add_m16_fwd (or, with
+        ops._LORA_FUSED, in the epilogue of ivl_linear_m16_lora_fwd and its packed twins: the same bits) with the indices read on
+        the device, so GraphedMultiStreamDecode serves 5 to 16 slots with one adapter per slot; lm_head, which has no adapter,
+        takes the kernel again.  Call it before a capture: a graphed class recaptures when either
+        switch changed."""
         self._wide_on = bool(on)
+        self._wide_lora = self._wide_on and bool(adapters)
         for layer in self.layers:
             layer.self_attn._wide_on = layer.mlp._wide_on = self._wide_on
+            layer.self_attn._wide_lora = layer.mlp._wide_lora = self._wide_lora
         return self
 
     # ---- per-row LoRA adapters, unmerged (DESIGN 4.15) ---------------------------------------------------------------------------
@@ -477,7 +486,7 @@ class InfiniteVLTextStack(nn.Module):
         if logits_to_keep:
             logits = ops.linear(h[:, -logits_to_keep:, :], self.embed_tokens.weight,  # tied lm_head (std:2091-2092)
                                 **ops.w8_kwargs(self._w8_lm_head, self._w8_on),
-                                **ops.wide_kwargs(self._wide_on and self._lora is None))       # (a model with an adapter table: no 16-row kernel)
+                                **ops.wide_kwargs(self._wide_on and (self._lora is None or self._wide_lora)))   # (under an adapter table: only with adapters=True)
         return h, logits
 
 
@@ -573,6 +582,7 @@ class _Graphed:
     _captured_w8 = False
     _captured_fmt = None
     _captured_wide = False
+    _captured_wide_lora = False
     _captured_lora = None
     adapter_ids: Optional[torch.Tensor] = None          # int32 [rows] on the device: one adapter index per row (-1 = none)
 
@@ -599,7 +609,7 @@ class _Graphed:
             self.sampler.load_state(saved_smp)          # the warm-up and the capture itself made draws
             self._captured_controlled = self.sampler.controlled
         self._captured_w8, self._captured_fmt = self._w8_on(), self._w8_fmt()
-        self._captured_wide = self._wide_on()
+        self._captured_wide, self._captured_wide_lora = self._wide_on(), self._wide_lora_on()
         self._captured_lora = self._lora_sig()
         return out
 
@@ -625,6 +635,10 @@ class _Graphed:
     def _wide_on(self) -> bool:
         return bool(getattr(self.model, "_wide_on", False))
 
+    def _wide_lora_on(self) -> bool:
+        """the `adapters` half of the pair use_wide_decode(on, adapters): a capture holds the launches of one setting of both"""
+        return bool(getattr(self.model, "_wide_lora", False))
+
     def _w8_fmt(self):
         """the format of the packed copies in use (None: the bf16 weights)"""
         return getattr(self.model, "_w8_fmt", None) if self._w8_on() else None
@@ -633,10 +647,11 @@ class _Graphed:
         """No graph yet, or one captured before the sampler switched to the controlled launch or before the model switched
         between its bf16 weights and their packed copies (use_packed_weights) or between the formats of the packed copies
         (quantize_weights_(fmt=): the captured launches are those of one format), or before the adapter table was attached,
-        detached or replaced (enable_adapters), or before the 16-row projection kernel was switched on or off (use_wide_decode)."""
+        detached or replaced (enable_adapters), or before the 16-row projection kernel was switched on or off, for calls without
+        or under an adapter table (use_wide_decode(on, adapters))."""
         return (self.graph is None or (self.sampler is not None and self.sampler.controlled != self._captured_controlled)
                 or self._w8_on() != self._captured_w8 or self._w8_fmt() != self._captured_fmt
-                or self._wide_on() != self._captured_wide
+                or (self._wide_on(), self._wide_lora_on()) != (self._captured_wide, self._captured_wide_lora)
                 or self._lora_sig() != self._captured_lora)
 
     def _run(self):

@@ -1190,9 +1190,12 @@ M16_CALLS = {"bf16": 0, "e4m3": 0, "mxfp4": 0}
 M16_ROWS = 16
 
 
-def wide_kwargs(on: bool) -> dict:
-    """The `wide=` argument of linear / linear_swiglu for a module: nothing at all unless the model's use_wide_decode() switch is on."""
-    return {"wide": True} if on else {}
+def wide_kwargs(on: bool, adapters: bool = False) -> dict:
+    """The `wide=` argument of linear / linear_swiglu for a module: nothing at all unless the model's use_wide_decode() switch is on;
+    adapters: its `adapters=True` extension to calls under an adapter table (`wide_lora=`)."""
+    if not on:
+        return {}
+    return {"wide": True, "wide_lora": True} if adapters else {"wide": True}
 
 
 def _m16_applies(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], rows: int, K: int) -> bool:
@@ -1235,8 +1238,60 @@ def linear_m16(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tenso
     return y
 
 
+# the adapter of a 5..16-row call under use_wide_decode(adapters=True): True = in the epilogue of the base launch
+# (ivl_linear_m16_lora*_fwd), False = the composition linear_m16 + lora_add(wide=True) (+ silu_mul).  The same bits (contracts F1 / F2 of
+# include/ivl_hip.h); which one is the default is a measurement: in the captured 36-layer step the fused form came out
+# 0.3 to 1.3 % SLOWER than the composition at 8 and at 16 slots (its epilogue runs on one wave of eight), so the composition is the
+# default.  Both stay: F1 / F2 tie them together, and the tests and tools/multistream_decode.py --wide-lora run both.
+_LORA_FUSED = False
+
+
+def _linear_wide_lora(x, weight: torch.Tensor, bias: Optional[torch.Tensor], w8: Optional["PackedWeight"], lora, glu: bool):
+    """linear / linear_swiglu with a lora table under use_wide_decode(adapters=True): the 5..16-row call, or None where the call is
+    not one (1..4 rows, more than 16, not bf16 on the device): the caller's path of always then runs.  A PreNorm input is materialised
+    once and shared by the base call and the adapter."""
+    table, key, rows_idx = lora
+    shape = x.shape
+    K = weight.shape[-1]
+    rows = 1
+    for d in shape[:-1]:
+        rows *= int(d)
+    if not (4 < rows <= M16_ROWS and weight.is_cuda and weight.dtype == torch.bfloat16 and x.dtype == torch.bfloat16 and shape[-1] == K):
+        return None
+    if isinstance(x, PreNorm):
+        x = x.materialize()
+    if glu and weight.shape[0] % 2:
+        return None
+    if w8 is not None:
+        w8.check(weight)
+    p = table.proj.get(key)
+    fused = (_LORA_FUSED and p is not None and p.N == weight.shape[0] and p.K == K and _m16_applies(x, weight, bias, rows, K))
+    if not fused:
+        if _m16_applies(x, weight, bias, rows, K):
+            y = linear_m16(x, weight, bias, w8=w8)
+        else:
+            y = linear(x, weight, bias, w8=w8)
+        y = lora_add(y if y.is_contiguous() else y.contiguous(), x, table, key, rows_idx, wide=True)
+        return silu_mul(y) if glu else y
+    xc = x if x.is_contiguous() else x.contiguous()
+    N = weight.shape[0] // 2 if glu else weight.shape[0]
+    y = torch.empty(*shape[:-1], N, dtype=torch.bfloat16, device=x.device)
+    idx = _lora_rows(table, rows_idx, rows)
+    a = _lora_args(table, p, xc, y, idx, rows, p.t_ws16)
+    lib, bp, g = _lib.load(), _p(bias) if bias is not None else None, 1 if glu else 0
+    if w8 is not None:
+        fn = lib.ivl_linear_m16_lora_w4_fwd if w8.fmt == "mxfp4" else lib.ivl_linear_m16_lora_w8_fwd
+        _lib.check(fn(_p(xc), _p(w8.codes), _p(w8.scale), bp, _p(y), rows, N, K, g, ctypes.byref(a), _stream(x)))
+        M16_CALLS[w8.fmt] += 1
+    else:
+        _lib.check(lib.ivl_linear_m16_lora_fwd(_p(xc), _p(weight), bp, _p(y), rows, N, K, g, ctypes.byref(a), _stream(x)))
+        M16_CALLS["bf16"] += 1
+    LORA_CALLS["m16_fused"] += 1
+    return y
+
+
 def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, w8: Optional[PackedWeight] = None,
-           lora=None, wide: bool = False) -> torch.Tensor:
+           lora=None, wide: bool = False, wide_lora: bool = False) -> torch.Tensor:
     """nn.Linear forward.  A single-token decode step (<= 4 rows) is a pure weight stream and goes through
     ivl_linear_small_m_fwd; longer calls are stock library GEMMs (hipBLASLt / rocBLAS through torch), which
     SURVEY.md 8(d) keeps outside the hot path.  w8: the packed copy of `weight` (which then holds W'), e4m3 or mxfp4 -- the call
@@ -1244,8 +1299,14 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] =
     bytes; every other path reads `weight` as ever.  lora: (LoraTable, key, rows) -- the base call as without it, then lora_add on
     its output (the NORM form reads the PreNorm's x / residual).  wide: the model's use_wide_decode() switch -- a call of 5..16 rows
     that meets the shape rules of ivl_linear_m16_fwd takes that kernel (with w8: the packed twin) instead of the library GEMM; calls
-    with a lora table never do."""
+    with a lora table do so only with wide_lora (use_wide_decode(adapters=True)): then the adapter follows the base call as
+    lora_add(wide=True) (ivl_lora_add_m16_fwd) or, with _LORA_FUSED on, rides in the base kernel's epilogue
+    (ivl_linear_m16_lora*_fwd) -- the same bits."""
     if lora is not None:
+        if wide and wide_lora:
+            y = _linear_wide_lora(x, weight, bias, w8, lora, False)
+            if y is not None:
+                return y
         y = linear(x, weight, bias, w8=w8)
         return lora_add(y if y.is_contiguous() else y.contiguous(), x, *lora)
     if w8 is not None:
@@ -1277,14 +1338,19 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] =
 
 
 def linear_swiglu(x: torch.Tensor, w_gate_up: torch.Tensor, w8: Optional[PackedWeight] = None, lora=None,
-                  wide: bool = False) -> torch.Tensor:
+                  wide: bool = False, wide_lora: bool = False) -> torch.Tensor:
     """silu(gate_proj(x)) * up_proj(x) with the fused gate|up weight [2I, K] (std:945).  Decode steps (<= 4 rows)
     apply the gate in the epilogue of the weight-stream kernel, and so does the 256-row kernel of a prefill chunk
     (ivl_linear_m256_fwd); other calls are a library GEMM + silu_mul.  w8: as in `linear`.  lora: (LoraTable, key, rows) with the
     two segments gate | up -- the plain projection on the fused weight, lora_add, then silu_mul: the header guarantees linear +
     ivl_silu_mul_fwd == the GLU forms bit for bit, so rows without an adapter keep their bits.  wide: as in `linear` (the
-    gate then runs in the epilogue of ivl_linear_m16_fwd)."""
+    gate then runs in the epilogue of ivl_linear_m16_fwd; with wide_lora and a table: linear_m16 on the fused weight, lora_add,
+    silu_mul, or with _LORA_FUSED on the gate behind the adapter in the epilogue of ivl_linear_m16_lora*_fwd: no silu_mul launch)."""
     if lora is not None:
+        if wide and wide_lora:
+            y = _linear_wide_lora(x, w_gate_up, None, w8, lora, True)
+            if y is not None:
+                return y
         return silu_mul(linear(x, w_gate_up, w8=w8, lora=lora))
     if w8 is not None:
         w8.check(w_gate_up)
@@ -1319,7 +1385,9 @@ LORA_RANKS = (8, 16, 32, 64)
 LORA_MAX_SEG = 8
 LORA_T_LD = 512                  # row pitch of a t workspace: 8 segments x rank 64
 # calls of lora_add per path (tests read it to know what a call ran on): the HIP entry point / peft's computation through torch
-LORA_CALLS = {"small_m": 0, "torch": 0}
+# m16 / m16_fused: the 5..16-row forms of use_wide_decode(adapters=True) -- ivl_lora_add_m16_fwd behind a base call / the adapter in
+# the epilogue of ivl_linear_m16_lora*_fwd
+LORA_CALLS = {"small_m": 0, "torch": 0, "m16": 0, "m16_fused": 0}
 LoraArgs = _lib.LoraArgs
 
 
@@ -1340,6 +1408,7 @@ class _LoraProj:
         self.A = torch.zeros(n_adapters, self.n_seg * R, K, dtype=torch.bfloat16, device=device)
         self.B = torch.zeros(n_adapters, N, R, dtype=torch.bfloat16, device=device)
         self.t_ws = torch.zeros(4, LORA_T_LD, dtype=torch.bfloat16, device=device)
+        self.t_ws16 = torch.zeros(M16_ROWS, LORA_T_LD, dtype=torch.bfloat16, device=device)     # the 5..16-row forms' 
 
 
 class LoraTable:
@@ -1457,8 +1526,9 @@ def _lora_torch(y: torch.Tensor, x: torch.Tensor, p: _LoraProj, table: LoraTable
     y2, x2 = y.view(M, p.N), x.reshape(M, p.K)
     if isinstance(rows, torch.Tensor):
         if rows.is_cuda and torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("lora_add: a call of more than 4 rows reads its adapter indices on the host and cannot be captured "
-                               "(graphed decode with an adapter table serves up to 4 rows per step)")
+            raise RuntimeError("lora_add: this call reads its adapter indices on the host and cannot be captured: graphed decode "
+                               "with an adapter table serves up to 4 rows per step, and 5..16 rows after "
+                               "use_wide_decode(adapters=True)")
         per_row = [int(v) for v in rows.reshape(-1).tolist()]
         if M % len(per_row):
             raise ValueError(f"lora_add: {len(per_row)} adapter indices for {M} rows")
@@ -1484,13 +1554,41 @@ def _lora_torch(y: torch.Tensor, x: torch.Tensor, p: _LoraProj, table: LoraTable
     return y
 
 
-def lora_add(y: torch.Tensor, x, table: LoraTable, key, rows) -> torch.Tensor:
+def _lora_rows(table: LoraTable, rows, M: int) -> torch.Tensor:
+    """the int32 device tensor [M] of a call's adapter indices (never read on the host)"""
+    if not isinstance(rows, torch.Tensor):
+        rows = table.rows_of(rows, M)
+    elif rows.numel() != M:
+        if M % rows.numel():
+            raise ValueError(f"lora_add: {rows.numel()} adapter indices for {M} rows")
+        rows = rows.reshape(-1).repeat_interleave(M // rows.numel())               # on the device
+    if rows.dtype != torch.int32 or not rows.is_cuda or not rows.is_contiguous():
+        raise ValueError("lora_add: rows must be a contiguous int32 tensor on the device")
+    return rows
+
+
+def _lora_args(table: LoraTable, p: _LoraProj, x: Optional[torch.Tensor], y: torch.Tensor, rows: torch.Tensor, M: int,
+               t_ws: torch.Tensor) -> "LoraArgs":
+    """ivl_lora_args of a call without the NORM group (x None: the caller fills x and the norm fields)"""
+    a = LoraArgs()
+    if x is not None:
+        a.x = x.data_ptr()
+    a.y, a.adapter_idx, a.A, a.B, a.scaling, a.t_ws = y.data_ptr(), rows.data_ptr(), p.A.data_ptr(), p.B.data_ptr(), \
+        table.scaling.data_ptr(), t_ws.data_ptr()
+    a.M, a.N, a.K, a.R, a.n_adapters, a.n_seg = M, p.N, p.K, table.R, table.n_adapters, p.n_seg
+    for i in range(LORA_MAX_SEG + 1):
+        setattr(a, f"seg_col{i}", p.seg_cols[min(i, p.n_seg)])
+    return a
+
+
+def lora_add(y: torch.Tensor, x, table: LoraTable, key, rows, wide: bool = False) -> torch.Tensor:
     """y += s_a B_a (A_a x) per row, IN PLACE on the base projection's output y [..., N], for the registered projection `key`.
     x: the projection's input [..., K], or the PreNorm the base call ran in its prologue (the kernel then forms the normalised
     row itself, bit-identical to the base launch's).  rows: an int32 device tensor with one adapter index per row (or per batch row
     of a [B, T, K] input; outside [0, n_adapters) = the row is not touched), or a LoraHandle / None for the whole call.
     Decode steps (<= 4 rows, bf16, on the device) run ivl_lora_add_small_m_fwd; anything else is peft's computation through torch's
-    library GEMMs, like every M > 4 projection of the package (an index tensor is then read on the host: not capturable)."""
+    library GEMMs, like every M > 4 projection of the package (an index tensor is then read on the host: not capturable).
+    wide=True (use_wide_decode(adapters=True)): a call of 5..16 rows runs ivl_lora_add_m16_fwd, the indices staying on the device."""
     p = table.proj.get(key)
     if p is None:
         raise ValueError(f"lora_add: the projection {key!r} is not registered in the table")
@@ -1502,19 +1600,19 @@ def lora_add(y: torch.Tensor, x, table: LoraTable, key, rows) -> torch.Tensor:
         raise ValueError("lora_add: y must be contiguous (it is updated in place)")
     M = y.numel() // p.N
     dtype = pn.dtype if pn is not None else x.dtype
+    if wide and y.is_cuda and 4 < M <= M16_ROWS and dtype == torch.bfloat16 and y.dtype == torch.bfloat16:
+        xt = pn.materialize() if pn is not None else x
+        xt = xt if xt.is_contiguous() else xt.contiguous()
+        a = _lora_args(table, p, xt, y, _lora_rows(table, rows, M), M, p.t_ws16)
+        _lib.check(_lib.load().ivl_lora_add_m16_fwd(ctypes.byref(a), _stream(y)))
+        LORA_CALLS["m16"] += 1
+        return y
     if not (y.is_cuda and 1 <= M <= 4 and dtype == torch.bfloat16 and y.dtype == torch.bfloat16):
         xt = pn.materialize() if pn is not None else x
         LORA_CALLS["torch"] += 1
         return _lora_torch(y, xt, p, table, rows)
-    if not isinstance(rows, torch.Tensor):
-        rows = table.rows_of(rows, M)
-    elif rows.numel() != M:
-        if M % rows.numel():
-            raise ValueError(f"lora_add: {rows.numel()} adapter indices for {M} rows")
-        rows = rows.reshape(-1).repeat_interleave(M // rows.numel())               # on the device
-    if rows.dtype != torch.int32 or not rows.is_cuda or not rows.is_contiguous():
-        raise ValueError("lora_add: rows must be a contiguous int32 tensor on the device")
-    a = LoraArgs()
+    rows = _lora_rows(table, rows, M)
+    a = _lora_args(table, p, None, y, rows, M, p.t_ws)
     norm = pn is not None and pn._y is None and 512 <= p.K <= 4096
     if norm:
         a.x, a.residual, a.norm_weight, a.eps = pn.x.data_ptr(), (pn.residual.data_ptr() if pn.residual is not None else None), \
@@ -1524,11 +1622,6 @@ def lora_add(y: torch.Tensor, x, table: LoraTable, key, rows) -> torch.Tensor:
         xt = pn.materialize() if pn is not None else x
         xt = xt if xt.is_contiguous() else xt.contiguous()
         a.x, keep = xt.data_ptr(), (xt,)
-    a.y, a.adapter_idx, a.A, a.B, a.scaling, a.t_ws = y.data_ptr(), rows.data_ptr(), p.A.data_ptr(), p.B.data_ptr(), \
-        table.scaling.data_ptr(), p.t_ws.data_ptr()
-    a.M, a.N, a.K, a.R, a.n_adapters, a.n_seg = M, p.N, p.K, table.R, table.n_adapters, p.n_seg
-    for i in range(LORA_MAX_SEG + 1):
-        setattr(a, f"seg_col{i}", p.seg_cols[min(i, p.n_seg)])
     _lib.check(_lib.load().ivl_lora_add_small_m_fwd(ctypes.byref(a), _stream(y)))
     del keep
     LORA_CALLS["small_m"] += 1

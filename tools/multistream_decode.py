@@ -95,6 +95,15 @@ per captured step (= ms per token per stream) and aggregate tok/s.  Then the sev
 M = 8 and M = 16: the library, bf16, e4m3, mxfp4 -- us per call and achieved GB/s of weight bytes.  Nothing is asserted.
 
     python tools/multistream_decode.py --wide --slots 8,16 [--out profiles/wide_decode.json]
+
+--wide-lora: per-slot LoRA adapters in the 8- and 16-slot step on the 16-row kernel (use_wide_decode(True, adapters=True), DESIGN
+4.17).  A: the wide step, no table; B: a table attached, every slot at -1; C: every slot on a rank-16 adapter over all ten target
+modules, the adapter in the epilogue of the base launch (ops._LORA_FUSED = True) -- once with ONE adapter shared by all slots, once
+with one adapter per slot; C': the same as the composition linear_m16 + lora_add (+ silu_mul) (_LORA_FUSED = False); D: C over
+mxfp4 copies.  Legs interleaved per round in one process, median of --rounds rounds of --steps replays.  Then the six adapted
+projections of a decode token alone at M = 8 and 16: the base call, fused, composed -- us per call.  Nothing is asserted.
+
+    python tools/multistream_decode.py --wide-lora --slots 8,16 [--out profiles/wide_lora_decode.json]
 """
 import argparse
 import json
@@ -124,6 +133,8 @@ def main():
     ap.add_argument("--w4", action="store_true", help="time the step on packed mxfp4 weights against the e4m3 and bf16 steps (see above)")
     ap.add_argument("--lora", action="store_true", help="time the step with per-slot LoRA adapters against the step without (see above)")
     ap.add_argument("--wide", action="store_true", help="time the 8- and 16-slot step on the 16-row weight-stream kernel (see above)")
+    ap.add_argument("--wide-lora", dest="wide_lora", action="store_true",
+                    help="time per-slot adapters in the 8- and 16-slot step on the 16-row kernel, fused against composed (see above)")
     args = ap.parse_args()
     import torch
     from infinitevl_amd.cache import MultiStreamCache
@@ -168,6 +179,8 @@ def main():
         return w4_legs(args, torch, model, cfg, prompts, dev)
     if args.lora:
         return lora_legs(args, torch, model, cfg, prompts, dev)
+    if args.wide_lora:
+        return wide_lora_legs(args, torch, model, cfg, prompts, dev)
     if args.wide:
         return wide_legs(args, torch, model, cfg, prompts, dev)
 
@@ -1042,6 +1055,144 @@ def lora_legs(args, torch, model, cfg, prompts, dev):
         del decs
     del model_t, model_q
     res["operators_us_per_call"] = lora_operator_legs(args, torch, cfg, dev, timed)
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+def wide_lora_operator_legs(args, torch, cfg, dev, timed):
+    """the six adapted projections of a decode token alone at M = 8 and 16 on the 16-row kernel: the base call without a table,
+    the adapter fused into its epilogue, and the composition base + lora_add(wide=True) (+ silu_mul) -- us per call, 64 calls per graph"""
+    from infinitevl_amd import ops
+    hd, I = cfg.hidden_size, cfg.intermediate_size
+    nq, nkv = cfg.num_attention_heads * cfg.head_dim, cfg.num_key_value_heads * cfg.head_dim
+    H, dk = cfg.num_linear_heads, cfg.linear_head_dim
+    dv = int(dk * cfg.expand_v)
+    gcols = [0, H * dk, 2 * H * dk, 2 * H * dk + H * dv, 2 * H * dk + 2 * H * dv, 2 * H * dk + 2 * H * dv + H, 2 * H * dk + 2 * H * dv + 2 * H]
+    shapes = [("qkv", nq + 2 * nkv, hd, (0, nq, nq + nkv, nq + 2 * nkv), False), ("gdn_in", (gcols[-1] + 7) // 8 * 8, hd, tuple(gcols), False),
+              ("attn_o_proj", hd, nq, (0, hd), False), ("gdn_o_proj", hd, H * dv, (0, hd), False),
+              ("gate_up", 2 * I, hd, (0, I, 2 * I), True), ("down", hd, I, (0, hd), False)]
+    gen = torch.Generator(device=dev).manual_seed(3)
+    out = {}
+    was = ops._LORA_FUSED
+    for name, N, K, cols, glu in shapes:
+        t = ops.LoraTable(16, LORA_RANK, dev)
+        t.register(name, N, K, cols)
+        p = t.proj[name]
+        p.A.copy_((torch.randn(p.A.shape, generator=gen, device=dev) * 0.02).to(torch.bfloat16))
+        p.B.copy_((torch.randn(p.B.shape, generator=gen, device=dev) * 0.02).to(torch.bfloat16))
+        t.scaling.fill_(2.0)
+        w = (torch.randn(N, K, generator=gen, device=dev) * K ** -0.5).to(torch.bfloat16)
+        row = {"N": N, "K": K, "segments": len(cols) - 1, "glu": glu}
+        for M in (8, 16):
+            x = (torch.randn(M, K, generator=gen, device=dev) * 0.5).to(torch.bfloat16)
+            rows = (torch.arange(M, dtype=torch.int32, device=dev) % 16).contiguous()
+            fn = ops.linear_swiglu if glu else ops.linear
+            for leg, fused, kw in (("base", True, {}), ("fused", True, {"lora": (t, name, rows), "wide_lora": True}),
+                                   ("composed", False, {"lora": (t, name, rows), "wide_lora": True})):
+                ops._LORA_FUSED = fused
+                try:
+                    fn(x, w, wide=True, **kw)
+                    torch.cuda.synchronize()
+                    g = torch.cuda.CUDAGraph()
+                    reps = 64
+                    with torch.cuda.graph(g):
+                        for _ in range(reps):
+                            fn(x, w, wide=True, **kw)
+                finally:
+                    ops._LORA_FUSED = was
+                ts = [timed(g.replay, 4) / reps for _ in range(args.rounds)]
+                row[f"M{M}_{leg}_us"] = round(1000 * statistics.median(ts), 2)
+        out[name] = row
+        print(name, row, file=sys.stderr, flush=True)
+    return out
+
+
+def wide_lora_legs(args, torch, model, cfg, prompts, dev):
+    from infinitevl_amd import ops
+    from infinitevl_amd.cache import MultiStreamCache
+    from infinitevl_amd.harness import GraphedMultiStreamDecode, InfiniteVLTextStack
+    stream = torch.cuda.current_stream()
+
+    def timed(fn, n):
+        for _ in range(4):
+            fn()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        for _ in range(n):
+            fn()
+        e1.record(stream)
+        e1.synchronize()
+        return e0.elapsed_time(e1) / n
+
+    def another():
+        with torch.device(dev):
+            torch.set_default_dtype(torch.bfloat16)
+            m = InfiniteVLTextStack(cfg)
+            torch.set_default_dtype(torch.float32)
+        return m.to(torch.bfloat16).eval().init_weights_(seed=0).fuse_()
+
+    model.use_wide_decode(True)
+    model_t = another().enable_adapters(16, LORA_RANK).use_wide_decode(True, adapters=True)
+    model_q = another().quantize_weights_(lm_head=True, fmt="mxfp4").enable_adapters(16, LORA_RANK).use_wide_decode(True, adapters=True)
+    handles = {id(m): [m.load_adapter(lora_state(torch, m, LORA_RANK, 1 + i), alpha=2 * LORA_RANK, rank=LORA_RANK) for i in range(16)]
+               for m in (model_t, model_q)}
+    slots = [int(s) for s in args.slots.split(",")]
+    L = cfg.num_hidden_layers
+    res = {"tool": "multistream_decode --wide-lora", "layers": L, "window": 4096, "steps": args.steps, "rounds": args.rounds,
+           "rank": LORA_RANK, "target_modules": 10,
+           "legs": "A = wide step, no table; B = table, every slot -1 (fused form); C = every slot on an adapter, fused into the base "
+                   "launch's epilogue (shared: one adapter for all slots; per_slot: one each); C' = the same as linear_m16 + lora_add "
+                   "(+ silu_mul); D = C over mxfp4 copies",
+           "launches_added_per_step": {"fused": 4 * L, "composed": 2 * 4 * L + L},
+           "bar": "none asserted; the yardsticks of C are A and C'"}
+    was = ops._LORA_FUSED
+
+    def decoder(m, n, fused):
+        ops._LORA_FUSED = fused                                  # (read when the step is captured)
+        try:
+            dec = GraphedMultiStreamDecode(m, MultiStreamCache(config=cfg, n_slots=n, device=dev, dtype=torch.bfloat16))
+            for s in range(n):
+                dec.admit(s, prompts[s % len(prompts)])
+            dec.capture()
+        finally:
+            ops._LORA_FUSED = was
+        return dec
+
+    def assign(dec, m, how, n):
+        for s in range(n):
+            dec.set_adapter(s, None if how == "none" else handles[id(m)][0 if how == "shared" else s])
+
+    try:
+        for n in slots:
+            dA, dF, dC, dQ = decoder(model, n, True), decoder(model_t, n, True), decoder(model_t, n, False), decoder(model_q, n, True)
+            legs = [("A", dA, model, None), ("B", dF, model_t, "none"), ("C_shared", dF, model_t, "shared"), ("C_per_slot", dF, model_t, "per_slot"),
+                    ("Cprime_shared", dC, model_t, "shared"), ("Cprime_per_slot", dC, model_t, "per_slot"),
+                    ("D_shared", dQ, model_q, "shared"), ("D_per_slot", dQ, model_q, "per_slot")]
+            times = {k: [] for k, _, _, _ in legs}
+            for _ in range(args.rounds):
+                for name, dec, m, how in legs:
+                    if how is not None:
+                        assign(dec, m, how, n)                   # one write per slot between replays: no recapture
+                    times[name].append(timed(dec.step, args.steps))
+            assert dF.graph is not None and not dF._stale() and not dC._stale()
+            med = {k: statistics.median(v) for k, v in times.items()}
+            cell = {k: {"ms_per_step": round(v, 4), "aggregate_tok_s": round(1000.0 * n / v, 1),
+                        "spread_ms": [round(min(times[k]), 4), round(max(times[k]), 4)]} for k, v in med.items()}
+            cell.update({f"{k}_over_A": round(v / med["A"], 4) for k, v in med.items() if k != "A"})
+            cell.update(C_over_Cprime_shared=round(med["C_shared"] / med["Cprime_shared"], 4),
+                        C_over_Cprime_per_slot=round(med["C_per_slot"] / med["Cprime_per_slot"], 4))
+            res[f"slots{n}"] = cell
+            print(f"slots{n}: " + " ".join(f"{k} {v:.4f}" for k, v in med.items()) + " ms", file=sys.stderr, flush=True)
+            del dA, dF, dC, dQ, legs
+    finally:
+        ops._LORA_FUSED = was
+        model.use_wide_decode(False)
+    del model_t, model_q
+    res["operators_us_per_call"] = wide_lora_operator_legs(args, torch, cfg, dev, timed)
     line = json.dumps(res)
     print(line)
     if args.out:
