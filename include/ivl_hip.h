@@ -543,6 +543,34 @@ IVL_API int ivl_linear_m16_w8_fwd(const void* x, const void* wq, const float* sc
 IVL_API int ivl_linear_m16_w4_fwd(const void* x, const void* wq, const void* sq, const void* bias, void* y, int M, int N, int K,
                                   int glu, void* stream);
 
+/* nn.Linear for a decode step of up to 64 rows (17 to 63 slots of a multi-stream step): the three entries above with the row bound
+ * moved -- the same argument lists, formulas, rounding points, weight formats and layouts (the same packed copies: no new layout and
+ * no second copy).  The 64 rows of x are XT = ceil(M / 16) B operands of v_mfma_f32_16x16x32_bf16; a lane's weight piece is loaded
+ * and decoded to the bf16 pattern of W' once and is the A operand of all XT.
+ * THE SUMMATION PLAN IS THAT OF THE 16-ROW ENTRIES, UNCHANGED: the chunks, tiles and steps s = 16t + j, the four MFMAs u = 0..3 with
+ * chunk 256t + 4j + g + 64u, the 8 contiguous slices of ceil(S / 8) steps, each accumulated from 0 in ascending (s, u), the eight
+ * partials added in fp32 in ascending slice order, then the bias, then the one rounding.  Which wave computes which slice of which
+ * (weight tile, x tile) is a choice of speed; the value of an output element is not.  No split across workgroups, no atomics, one
+ * launch, no scratch.  THE CONTRACTS:
+ *  C1. Determinism: every run gives the same bits, eager or replayed from a graph.
+ *  C2. Row m of an M-row call equals ivl_linear_m16_fwd / _w8_fwd / _w4_fwd called on row m alone (M = 1), bit for bit, plain and
+ *      GLU: a row depends on its own row of x only -- the same bits for every M, at every row index, whatever the other rows hold
+ *      (NaN, Inf).
+ *  C3. Packed equals bf16 on W': contract 3 of the 16-row entries, on the same terms.
+ *  C4. GLU equals plain plus gate: the glu != 0 call equals the glu == 0 call on the fused weight (N = 2I) followed by
+ *      ivl_silu_mul_fwd, bit for bit.
+ *  C5. Rows M .. 16 XT - 1 of the B operands are zeros: never read from x, never written to y.  Weight rows past the last are
+ *      neither read nor stored.
+ * 1 <= M <= 64 (else IVL_ERR_UNSUPPORTED); every other refusal is that of the 16-row entry of the same format, with the same code:
+ * N >= 1, K >= 32 and K % 32 == 0, alignment, no NULL pointer (IVL_ERR_INVALID_ARG); 32-bit weight byte offsets
+ * (IVL_ERR_UNSUPPORTED).  Every check runs before anything is launched.  There is no LoRA form: ivl_linear_m16_lora*_fwd stop at 16
+ * rows. */
+IVL_API int ivl_linear_m64_fwd(const void* x, const void* w, const void* bias, void* y, int M, int N, int K, int glu, void* stream);
+IVL_API int ivl_linear_m64_w8_fwd(const void* x, const void* wq, const float* scale, const void* bias, void* y, int M, int N, int K,
+                                  int glu, void* stream);
+IVL_API int ivl_linear_m64_w4_fwd(const void* x, const void* wq, const void* sq, const void* bias, void* y, int M, int N, int K,
+                                  int glu, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * PER-ROW LoRA ADAPTERS FOR 5 TO 16 ROWS (the args, chain, segments, rank padding and NOT TOUCHED rule of
  * ivl_lora_add_small_m_fwd above, its t order included; t_ws is bf16 [16, 512] here).

@@ -117,6 +117,7 @@ class InfiniteVLTextMLP(nn.Module):
         self._w8_on = False
         self._wide_on = False               # InfiniteVLTextStack.use_wide_decode()
         self._wide_lora = False             # use_wide_decode(adapters=True)
+        self._wide_rows = 16                # use_wide_decode(max_rows=)
         self._lora, self._lora_layer = None, None   # ops.LoraTable with (layer, "gu") and (layer, "down") (enable_adapters)
 
     @torch.no_grad()
@@ -151,7 +152,7 @@ class InfiniteVLTextMLP(nn.Module):
         if (self._fused_w is not None and x.is_cuda and x.dtype == torch.bfloat16
                 and self.gate_proj.weight.data_ptr() == self._fused_w.data_ptr()):
             w8_gu, w8_down = ops.w8_kwargs(self._w8_gu, self._w8_on), ops.w8_kwargs(self._w8_down, self._w8_on)
-            wide = ops.wide_kwargs(self._wide_on, self._wide_lora)
+            wide = ops.wide_kwargs(self._wide_on, self._wide_lora, self._wide_rows)
             return ops.linear(ops.linear_swiglu(x, self._fused_w, **w8_gu, **ops.lora_kwargs(self._lora, (self._lora_layer, "gu")), **wide),
                               self.down_proj.weight, **w8_down, **ops.lora_kwargs(self._lora, (self._lora_layer, "down")), **wide)
         if self._lora is not None:
@@ -203,6 +204,7 @@ class InfiniteVLTextStack(nn.Module):
         self._w8_fmt = None                     # the format of the packed copies: "e4m3" / "mxfp4" (quantize_weights_)
         self._wide_on = False                   # use_wide_decode(): projections of 5..16 rows on ivl_linear_m16_fwd
         self._wide_lora = False                 # use_wide_decode(adapters=True): also while an adapter table is attached
+        self._wide_rows = 16                    # use_wide_decode(max_rows=): projections of 17..max_rows rows on ivl_linear_m64_fwd
         self._lora = None                      # ops.LoraTable of every projection (enable_adapters)
         self._lora_names = {}                   # {"layers.3.self_attn.q_proj": (key, segment)}
 
@@ -273,7 +275,7 @@ class InfiniteVLTextStack(nn.Module):
             layer.self_attn._w8_on = layer.mlp._w8_on = self._w8_on
         return self
 
-    def use_wide_decode(self, on: bool = True, adapters: bool = False) -> "InfiniteVLTextStack":
+    def use_wide_decode(self, on: bool = True, adapters: bool = False, max_rows: int = 16) -> "InfiniteVLTextStack":
         """Opt in (after fuse_(); off by default) to the 16-row weight-stream kernel for decode steps of 5 to 16 slots:
         while it is on, every projection of this model -- q|k|v, the GDN in-projection, both o_proj, gate|up with its SwiGLU gate,
         down_proj and the tied lm_head -- that is called with 5..16 rows of bf16 on the device (K % 32 == 0) runs on
@@ -284,13 +286,25 @@ class InfiniteVLTextStack(nn.Module):
         under a table run on the kernel too, each row's adapter added behind it by ivl_lora_add_m16_fwd (or, with
         ops._LORA_FUSED, in the epilogue of ivl_linear_m16_lora_fwd and its packed twins: the same bits) with the indices read on
         the device, so GraphedMultiStreamDecode serves 5 to 16 slots with one adapter per slot; lm_head, which has no adapter,
-        takes the kernel again.  Call it before a capture: a graphed class recaptures when either
-        switch changed."""
+        takes the kernel again.
+        max_rows (an int in 16..64): with the default 16 nothing else changes -- calls of 17 and more rows keep the
+        library path.  With max_rows = R > 16 every such projection call of 17..R rows runs on ivl_linear_m64_fwd (with
+        use_packed_weights(True): on the packed twin), whose summation plan is the 16-row kernel's: a stream's logits stay the
+        same bits when the 17th stream is admitted, and the packed copies are streamed past 16 slots too.  Rows 5..16 stay on the
+        16-row kernel, rows 1..4 on the small-M kernels.  LoRA past 16 rows is out of scope: a call of more than 16 rows under an
+        adapter table keeps the library + adapter path in every setting, adapters=True included, and so does lm_head while a
+        table is attached.  Whether R > 16 pays is a measurement per slot count and format: measured, it does up to
+        24 slots on e4m3 copies and up to 32 slots on mxfp4 copies, and not on bf16 weights.
+        Call it before a capture: a graphed class recaptures when any of the three changed."""
+        if isinstance(max_rows, bool) or not isinstance(max_rows, int) or not 16 <= max_rows <= ops.M64_ROWS:
+            raise ValueError(f"use_wide_decode: max_rows={max_rows!r} (an int in 16..{ops.M64_ROWS} is expected)")
         self._wide_on = bool(on)
         self._wide_lora = self._wide_on and bool(adapters)
+        self._wide_rows = max_rows if self._wide_on else 16
         for layer in self.layers:
             layer.self_attn._wide_on = layer.mlp._wide_on = self._wide_on
             layer.self_attn._wide_lora = layer.mlp._wide_lora = self._wide_lora
+            layer.self_attn._wide_rows = layer.mlp._wide_rows = self._wide_rows
         return self
 
     # ---- per-row LoRA adapters, unmerged (DESIGN 4.15) ---------------------------------------------------------------------------
@@ -486,7 +500,8 @@ class InfiniteVLTextStack(nn.Module):
         if logits_to_keep:
             logits = ops.linear(h[:, -logits_to_keep:, :], self.embed_tokens.weight,  # tied lm_head (std:2091-2092)
                                 **ops.w8_kwargs(self._w8_lm_head, self._w8_on),
-                                **ops.wide_kwargs(self._wide_on and (self._lora is None or self._wide_lora)))   # (under an adapter table: only with adapters=True)
+                                **ops.wide_kwargs(self._wide_on and (self._lora is None or self._wide_lora),     # (under an adapter table: only with adapters=True,
+                                                  max_rows=self._wide_rows if self._lora is None else 16))        # and never past 16 rows)
         return h, logits
 
 
@@ -583,6 +598,7 @@ class _Graphed:
     _captured_fmt = None
     _captured_wide = False
     _captured_wide_lora = False
+    _captured_wide_rows = 16
     _captured_lora = None
     adapter_ids: Optional[torch.Tensor] = None          # int32 [rows] on the device: one adapter index per row (-1 = none)
 
@@ -610,6 +626,7 @@ class _Graphed:
             self._captured_controlled = self.sampler.controlled
         self._captured_w8, self._captured_fmt = self._w8_on(), self._w8_fmt()
         self._captured_wide, self._captured_wide_lora = self._wide_on(), self._wide_lora_on()
+        self._captured_wide_rows = self._wide_rows()
         self._captured_lora = self._lora_sig()
         return out
 
@@ -639,6 +656,10 @@ class _Graphed:
         """the `adapters` half of the pair use_wide_decode(on, adapters): a capture holds the launches of one setting of both"""
         return bool(getattr(self.model, "_wide_lora", False))
 
+    def _wide_rows(self) -> int:
+        """use_wide_decode(max_rows=): a capture holds the launches of one row bound"""
+        return int(getattr(self.model, "_wide_rows", 16))
+
     def _w8_fmt(self):
         """the format of the packed copies in use (None: the bf16 weights)"""
         return getattr(self.model, "_w8_fmt", None) if self._w8_on() else None
@@ -648,10 +669,11 @@ class _Graphed:
         between its bf16 weights and their packed copies (use_packed_weights) or between the formats of the packed copies
         (quantize_weights_(fmt=): the captured launches are those of one format), or before the adapter table was attached,
         detached or replaced (enable_adapters), or before the 16-row projection kernel was switched on or off, for calls without
-        or under an adapter table (use_wide_decode(on, adapters))."""
+        or under an adapter table (use_wide_decode(on, adapters)), or before its row bound changed (max_rows)."""
         return (self.graph is None or (self.sampler is not None and self.sampler.controlled != self._captured_controlled)
                 or self._w8_on() != self._captured_w8 or self._w8_fmt() != self._captured_fmt
                 or (self._wide_on(), self._wide_lora_on()) != (self._captured_wide, self._captured_wide_lora)
+                or self._wide_rows() != self._captured_wide_rows
                 or self._lora_sig() != self._captured_lora)
 
     def _run(self):

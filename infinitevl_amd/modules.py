@@ -81,6 +81,7 @@ class InfiniteVLSelfAttention(nn.Module):
         self._w8_on = False
         self._wide_on = False               # InfiniteVLTextStack.use_wide_decode(): 5..16-row projections on ivl_linear_m16_fwd
         self._wide_lora = False             # use_wide_decode(adapters=True): also under an adapter table (ivl_linear_m16_lora_fwd)
+        self._wide_rows = 16                # use_wide_decode(max_rows=): 17..max_rows rows on ivl_linear_m64_fwd
         self._lora = None                   # ops.LoraTable with this layer's (layer_idx, "qkv") and (layer_idx, "o") (enable_adapters)
         self.mma_dtype = None           # None = bf16 operands; "fp8_e4m3": single-token decode products on e4m3 (configs[4])
 
@@ -128,7 +129,7 @@ class InfiniteVLSelfAttention(nn.Module):
         if self._fused_ok(hidden_states):
             nq, nkv = self.num_heads * self.head_dim, self.num_key_value_heads * self.head_dim
             qkv = ops.linear(hidden_states, self._fused_w, self._fused_b, **ops.w8_kwargs(self._w8_qkv, self._w8_on),
-                             **ops.lora_kwargs(self._lora, (self.layer_idx, "qkv")), **ops.wide_kwargs(self._wide_on, self._wide_lora))    # [B,T,nq+2nkv]
+                             **ops.lora_kwargs(self._lora, (self.layer_idx, "qkv")), **ops.wide_kwargs(self._wide_on, self._wide_lora, self._wide_rows))    # [B,T,nq+2nkv]
             q = qkv[..., :nq].unflatten(-1, (self.num_heads, self.head_dim))
             k = qkv[..., nq:nq + nkv].unflatten(-1, (self.num_key_value_heads, self.head_dim))
             v = qkv[..., nq + nkv:].unflatten(-1, (self.num_key_value_heads, self.head_dim))
@@ -154,7 +155,7 @@ class InfiniteVLSelfAttention(nn.Module):
                                                   sliding_window=self.sliding_window)
         attn = attn.reshape(bsz, q_len, -1)
         return ops.linear(attn, self.o_proj.weight, self.o_proj.bias, **ops.w8_kwargs(self._w8_o, self._w8_on),
-                          **ops.lora_kwargs(self._lora, (self.layer_idx, "o")), **ops.wide_kwargs(self._wide_on, self._wide_lora)), None
+                          **ops.lora_kwargs(self._lora, (self.layer_idx, "o")), **ops.wide_kwargs(self._wide_on, self._wide_lora, self._wide_rows)), None
 
     @torch.no_grad()
     def quantize_weights_(self, fmt: str = "e4m3") -> "InfiniteVLSelfAttention":
@@ -241,6 +242,7 @@ class GatedDeltaNet(nn.Module):
         self._w8_on = False
         self._wide_on = False               # as InfiniteVLSelfAttention._wide_on
         self._wide_lora = False             # as InfiniteVLSelfAttention._wide_lora
+        self._wide_rows = 16                # as InfiniteVLSelfAttention._wide_rows
         self._lora = None                   # ops.LoraTable with this layer's (layer_idx, "in") and (layer_idx, "o") (enable_adapters)
         self.mma_dtype = None           # None = the reference's bf16 operands; "fp8_e4m3" = BASELINE.json configs[4]
 
@@ -310,9 +312,9 @@ class GatedDeltaNet(nn.Module):
         Dq, Dk, Dv = H * K, self.key_dim, self.value_dim
         cq, ck, cv, cg, ca, cb = self._fused_cols
         w8_in, w8_o = ops.w8_kwargs(self._w8_in, self._w8_on), ops.w8_kwargs(self._w8_o, self._w8_on)
-        kw_o = {**ops.lora_kwargs(self._lora, (self.layer_idx, "o")), **ops.wide_kwargs(self._wide_on, self._wide_lora)}
+        kw_o = {**ops.lora_kwargs(self._lora, (self.layer_idx, "o")), **ops.wide_kwargs(self._wide_on, self._wide_lora, self._wide_rows)}
         proj = ops.linear(hidden_states, self._fused_w, **w8_in, **ops.lora_kwargs(self._lora, (self.layer_idx, "in")),
-                          **ops.wide_kwargs(self._wide_on, self._wide_lora))                                                                 # [B,T,ld]
+                          **ops.wide_kwargs(self._wide_on, self._wide_lora, self._wide_rows))                                                                 # [B,T,ld]
         ld = proj.shape[-1]
         prev = (None, None, None)
         h0 = None

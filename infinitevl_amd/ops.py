@@ -1190,12 +1190,16 @@ M16_CALLS = {"bf16": 0, "e4m3": 0, "mxfp4": 0}
 M16_ROWS = 16
 
 
-def wide_kwargs(on: bool, adapters: bool = False) -> dict:
+def wide_kwargs(on: bool, adapters: bool = False, max_rows: int = 16) -> dict:
     """The `wide=` argument of linear / linear_swiglu for a module: nothing at all unless the model's use_wide_decode() switch is on;
-    adapters: its `adapters=True` extension to calls under an adapter table (`wide_lora=`)."""
+    adapters: its `adapters=True` extension to calls under an adapter table (`wide_lora=`); max_rows: its `max_rows=` extension to
+    calls of 17..max_rows rows (`wide_rows=`) -- absent at the default 16."""
     if not on:
         return {}
-    return {"wide": True, "wide_lora": True} if adapters else {"wide": True}
+    kw = {"wide": True, "wide_lora": True} if adapters else {"wide": True}
+    if max_rows > M16_ROWS:
+        kw["wide_rows"] = int(max_rows)
+    return kw
 
 
 def _m16_applies(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], rows: int, K: int) -> bool:
@@ -1235,6 +1239,44 @@ def linear_m16(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tenso
         return y
     _lib.check(lib.ivl_linear_m16_fwd(_p(xc), _p(weight), bp, _p(y), rows, N, K, 1 if glu else 0, _stream(x)))
     M16_CALLS["bf16"] += 1
+    return y
+
+
+# ---- 64-row weight-stream projections for decode steps of 17 to 63 slots -----------------------------------------------
+# calls that took an ivl_linear_m64* entry point, per weight format
+M64_CALLS = {"bf16": 0, "e4m3": 0, "mxfp4": 0}
+M64_ROWS = 64
+
+
+def linear_m64(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, *, glu: bool = False,
+               w8: Optional[PackedWeight] = None) -> torch.Tensor:
+    """linear_m16 for 1..64 rows of x, on ivl_linear_m64_fwd and its packed twins: the same arguments, formats and summation plan, so
+    row m of the result is bit for bit linear_m16 on that row alone (contract C2 of include/ivl_hip.h).  The direct entry: the shape
+    rules are the ABI's (1 <= rows <= 64, K % 32 == 0, 16-byte aligned), and a call that breaks them raises; ops.linear /
+    linear_swiglu take this kernel for 17..max_rows rows under InfiniteVLTextStack.use_wide_decode(max_rows=)."""
+    _need_gpu(x, weight)
+    if w8 is not None:
+        w8.check(weight)
+    if x.dtype != torch.bfloat16 or weight.dtype != torch.bfloat16 or weight.dim() != 2 or not weight.is_contiguous():
+        raise ValueError(f"linear_m64: bf16 x and a contiguous bf16 [N,K] weight are expected; got {x.dtype}, {weight.dtype} "
+                         f"{tuple(weight.shape)}")
+    if bias is not None and (bias.dtype != torch.bfloat16 or not bias.is_contiguous()):
+        raise ValueError("linear_m64: a contiguous bf16 bias is expected")
+    R, K = weight.shape
+    if x.shape[-1] != K or (glu and R % 2):
+        raise ValueError(f"linear_m64: x {tuple(x.shape)} does not meet a weight {tuple(weight.shape)} (glu={glu})")
+    N = R // 2 if glu else R
+    rows = x.numel() // K if K else 0
+    xc = x if x.is_contiguous() else x.contiguous()
+    y = torch.empty(*x.shape[:-1], N, dtype=torch.bfloat16, device=x.device)
+    lib, bp = _lib.load(), _p(bias) if bias is not None else None
+    if w8 is not None:
+        fn = lib.ivl_linear_m64_w4_fwd if w8.fmt == "mxfp4" else lib.ivl_linear_m64_w8_fwd
+        _lib.check(fn(_p(xc), _p(w8.codes), _p(w8.scale), bp, _p(y), rows, N, K, 1 if glu else 0, _stream(x)))
+        M64_CALLS[w8.fmt] += 1
+        return y
+    _lib.check(lib.ivl_linear_m64_fwd(_p(xc), _p(weight), bp, _p(y), rows, N, K, 1 if glu else 0, _stream(x)))
+    M64_CALLS["bf16"] += 1
     return y
 
 
@@ -1291,7 +1333,7 @@ def _linear_wide_lora(x, weight: torch.Tensor, bias: Optional[torch.Tensor], w8:
 
 
 def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, w8: Optional[PackedWeight] = None,
-           lora=None, wide: bool = False, wide_lora: bool = False) -> torch.Tensor:
+           lora=None, wide: bool = False, wide_lora: bool = False, wide_rows: int = M16_ROWS) -> torch.Tensor:
     """nn.Linear forward.  A single-token decode step (<= 4 rows) is a pure weight stream and goes through
     ivl_linear_small_m_fwd; longer calls are stock library GEMMs (hipBLASLt / rocBLAS through torch), which
     SURVEY.md 8(d) keeps outside the hot path.  w8: the packed copy of `weight` (which then holds W'), e4m3 or mxfp4 -- the call
@@ -1301,7 +1343,9 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] =
     that meets the shape rules of ivl_linear_m16_fwd takes that kernel (with w8: the packed twin) instead of the library GEMM; calls
     with a lora table do so only with wide_lora (use_wide_decode(adapters=True)): then the adapter follows the base call as
     lora_add(wide=True) (ivl_lora_add_m16_fwd) or, with _LORA_FUSED on, rides in the base kernel's epilogue
-    (ivl_linear_m16_lora*_fwd) -- the same bits."""
+    (ivl_linear_m16_lora*_fwd) -- the same bits.  wide_rows: use_wide_decode(max_rows=) -- with wide, a call of 17..wide_rows rows
+    without a lora table takes ivl_linear_m64_fwd (with w8: the packed twin) on the same shape rules; a call of more than 16 rows
+    under a lora table keeps the library path in every setting."""
     if lora is not None:
         if wide and wide_lora:
             y = _linear_wide_lora(x, weight, bias, w8, lora, False)
@@ -1334,18 +1378,20 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] =
         return y
     if wide and 4 < rows <= M16_ROWS and _m16_applies(x, weight, bias, rows, K):
         return linear_m16(x, weight, bias, w8=w8)
+    if wide and M16_ROWS < rows <= min(wide_rows, M64_ROWS) and _m16_applies(x, weight, bias, rows, K):
+        return linear_m64(x, weight, bias, w8=w8)
     return torch.nn.functional.linear(x, weight, bias)
 
 
 def linear_swiglu(x: torch.Tensor, w_gate_up: torch.Tensor, w8: Optional[PackedWeight] = None, lora=None,
-                  wide: bool = False, wide_lora: bool = False) -> torch.Tensor:
+                  wide: bool = False, wide_lora: bool = False, wide_rows: int = M16_ROWS) -> torch.Tensor:
     """silu(gate_proj(x)) * up_proj(x) with the fused gate|up weight [2I, K] (std:945).  Decode steps (<= 4 rows)
     apply the gate in the epilogue of the weight-stream kernel, and so does the 256-row kernel of a prefill chunk
     (ivl_linear_m256_fwd); other calls are a library GEMM + silu_mul.  w8: as in `linear`.  lora: (LoraTable, key, rows) with the
     two segments gate | up -- the plain projection on the fused weight, lora_add, then silu_mul: the header guarantees linear +
     ivl_silu_mul_fwd == the GLU forms bit for bit, so rows without an adapter keep their bits.  wide: as in `linear` (the
     gate then runs in the epilogue of ivl_linear_m16_fwd; with wide_lora and a table: linear_m16 on the fused weight, lora_add,
-    silu_mul, or with _LORA_FUSED on the gate behind the adapter in the epilogue of ivl_linear_m16_lora*_fwd: no silu_mul launch)."""
+    silu_mul, or with _LORA_FUSED on the gate behind the adapter in the epilogue of ivl_linear_m16_lora*_fwd: no silu_mul launch).  wide_rows: as in `linear` (the gate in the epilogue of ivl_linear_m64_fwd)."""
     if lora is not None:
         if wide and wide_lora:
             y = _linear_wide_lora(x, w_gate_up, None, w8, lora, True)
@@ -1377,6 +1423,9 @@ def linear_swiglu(x: torch.Tensor, w_gate_up: torch.Tensor, w8: Optional[PackedW
         return _linear_swiglu_m256(x, w_gate_up, rows, I, K)
     if wide and 4 < rows <= M16_ROWS and w_gate_up.shape[0] % 2 == 0 and _m16_applies(x, w_gate_up, None, rows, K):
         return linear_m16(x, w_gate_up, glu=True, w8=w8)
+    if (wide and M16_ROWS < rows <= min(wide_rows, M64_ROWS) and w_gate_up.shape[0] % 2 == 0
+            and _m16_applies(x, w_gate_up, None, rows, K)):
+        return linear_m64(x, w_gate_up, glu=True, w8=w8)
     return silu_mul(linear(x, w_gate_up))
 
 

@@ -96,6 +96,14 @@ M = 8 and M = 16: the library, bf16, e4m3, mxfp4 -- us per call and achieved GB/
 
     python tools/multistream_decode.py --wide --slots 8,16 [--out profiles/wide_decode.json]
 
+--wide --wide-rows 64: the opt-in 64-row weight-stream projections (use_wide_decode(max_rows=64)) in the captured greedy
+step of 17 to 63 slots.  A: use_wide_decode(True) as it is without max_rows -- the library GEMMs above 16 rows, which is also what
+max_rows=16 gives; B: max_rows=64 on the bf16 weights; C: on e4m3 copies; D: on mxfp4 copies.  The same process, the same rounds,
+the same reference point; the operator table is at M = 32 and M = 64 against the library (+ silu_mul for gate|up).  Nothing is
+asserted.
+
+    python tools/multistream_decode.py --wide --wide-rows 64 --slots 24,32,48,63 [--out profiles/wide64_decode.json]
+
 --wide-lora: per-slot LoRA adapters in the 8- and 16-slot step on the 16-row kernel (use_wide_decode(True, adapters=True), DESIGN
 4.17).  A: the wide step, no table; B: a table attached, every slot at -1; C: every slot on a rank-16 adapter over all ten target
 modules, the adapter in the epilogue of the base launch (ops._LORA_FUSED = True) -- once with ONE adapter shared by all slots, once
@@ -133,6 +141,8 @@ def main():
     ap.add_argument("--w4", action="store_true", help="time the step on packed mxfp4 weights against the e4m3 and bf16 steps (see above)")
     ap.add_argument("--lora", action="store_true", help="time the step with per-slot LoRA adapters against the step without (see above)")
     ap.add_argument("--wide", action="store_true", help="time the 8- and 16-slot step on the 16-row weight-stream kernel (see above)")
+    ap.add_argument("--wide-rows", dest="wide_rows", type=int, default=16,
+                    help="with --wide: use_wide_decode(max_rows=); above 16 the legs are those of the 64-row kernel (see above)")
     ap.add_argument("--wide-lora", dest="wide_lora", action="store_true",
                     help="time per-slot adapters in the 8- and 16-slot step on the 16-row kernel, fused against composed (see above)")
     args = ap.parse_args()
@@ -804,7 +814,8 @@ def w4_legs(args, torch, model, cfg, prompts, dev):
 
 
 def wide_operator_legs(args, torch, cfg, dev, timed):
-    """the seven projection shapes of a decode token at M = 8 and M = 16: the library GEMM (torch.nn.functional.linear, + ops.silu_mul
+    """the seven projection shapes of a decode token at M = 8 and M = 16 (--wide-rows above 16: M = 32 and M = 64, on ivl_linear_m64_fwd
+    and its twins): the library GEMM (torch.nn.functional.linear, + ops.silu_mul
     for gate|up: what ops.linear / linear_swiglu run with the switch off) against ivl_linear_m16_fwd and its e4m3 / mxfp4 twins, us
     per call and achieved GB/s of the weight bytes each format streams; A B C D A B C D per round, `reps` calls per captured graph
     over enough copies of the weight (>= 1 GB of bf16) that no call finds it in a cache"""
@@ -813,6 +824,7 @@ def wide_operator_legs(args, torch, cfg, dev, timed):
     shapes = [("qkv", 2560, hd, False), ("gdn_in", 12320, hd, False), ("attn_o_proj", hd, 2048, False), ("gdn_o_proj", hd, 4096, False),
               ("gate_up", 2 * I, hd, True), ("down", hd, I, False), ("lm_head", V, hd, False)]
     fmts = ("lib", "bf16", "e4m3", "mxfp4")
+    Ms, kernel = ((8, 16), ops.linear_m16) if args.wide_rows <= 16 else ((32, 64), ops.linear_m64)
     bytes_per_weight = {"lib": 2.0, "bf16": 2.0, "e4m3": 1.0, "mxfp4": 0.5 + 1.0 / 32}
     gen = torch.Generator(device=dev).manual_seed(2)
     out = {}
@@ -827,7 +839,7 @@ def wide_operator_legs(args, torch, cfg, dev, timed):
             packs["e4m3"].append(ops.PackedWeight(w, codes, scale))
             packs["mxfp4"].append(ops.PackedWeight(w, *ops.mxfp4_shuffle(*ops.quantize_rows_mxfp4(w)[:2]), fmt="mxfp4"))
         row = {"weight_rows": R, "K": K, "glu": glu, "copies": copies}
-        for M in (8, 16):
+        for M in Ms:
             x = (torch.randn(M, K, generator=gen, device=dev) * 0.5).to(torch.bfloat16)
             state = {"i": 0}
 
@@ -836,7 +848,7 @@ def wide_operator_legs(args, torch, cfg, dev, timed):
                 if fmt == "lib":
                     y = torch.nn.functional.linear(x, ws[i])
                     return ops.silu_mul(y) if glu else y
-                return ops.linear_m16(x, ws[i], glu=glu, w8=None if fmt == "bf16" else packs[fmt][i])
+                return kernel(x, ws[i], glu=glu, w8=None if fmt == "bf16" else packs[fmt][i])
 
             reps = max(8, min(128, 2 * copies))
             graphs = {}
@@ -868,7 +880,8 @@ def wide_legs(args, torch, model, cfg, prompts, dev):
     """A B C D per round in one process.  A: the captured greedy step with the switch off (library GEMMs above four rows: the step as
     it is without this option); B: use_wide_decode() on the bf16 weights; C: on e4m3 copies; D: on mxfp4 copies (lm_head=True for
     both).  Three models of the same shape (a captured step holds the pointers of ITS packed copies); the 4-slot small-M step of the
-    bf16 model is timed in every round as the reference point."""
+    bf16 model is timed in every round as the reference point.  --wide-rows R above 16: A is use_wide_decode(True) -- the library
+    above 16 rows --, and B, C, D are use_wide_decode(True, max_rows=R)."""
     from infinitevl_amd.cache import MultiStreamCache
     from infinitevl_amd.harness import GraphedMultiStreamDecode, InfiniteVLTextStack
     stream = torch.cuda.current_stream()
@@ -892,7 +905,7 @@ def wide_legs(args, torch, model, cfg, prompts, dev):
         return m.to(torch.bfloat16).eval().init_weights_(seed=0).fuse_().quantize_weights_(lm_head=True, fmt=fmt)
 
     def decoder(m, wide, n):
-        m.use_wide_decode(wide)
+        m.use_wide_decode(**wide)
         dec = GraphedMultiStreamDecode(m, MultiStreamCache(config=cfg, n_slots=n, device=dev, dtype=torch.bfloat16))
         for s in range(n):
             dec.admit(s, prompts[s % len(prompts)])
@@ -901,20 +914,27 @@ def wide_legs(args, torch, model, cfg, prompts, dev):
 
     model8, model4 = packed_model("e4m3"), packed_model("mxfp4")
     slots = [int(s) for s in args.slots.split(",")]
+    R = args.wide_rows
+    off, base, on = {"on": False}, ({"on": False} if R <= 16 else {"on": True}), ({"on": True} if R <= 16 else {"on": True, "max_rows": R})
     res = {"tool": "multistream_decode --wide", "layers": cfg.num_hidden_layers, "window": 4096, "steps": args.steps, "rounds": args.rounds,
            "legs": "A = switch off (library GEMMs); B = use_wide_decode, bf16; C = use_wide_decode, e4m3 copies; D = use_wide_decode, "
                    "mxfp4 copies (lm_head packed in C and D); ref4 = the 4-slot small-M step of the bf16 model", "bar": "none asserted"}
-    ref4 = decoder(model, False, 4)
+    if R > 16:
+        res.update(tool=f"multistream_decode --wide --wide-rows {R}", wide_rows=R,
+                   legs=f"A = use_wide_decode(True): the library GEMMs above 16 rows (= max_rows=16); B = max_rows={R}, bf16; C = max_rows={R}, "
+                        f"e4m3 copies; D = max_rows={R}, mxfp4 copies (lm_head packed in C and D); ref4 = the 4-slot small-M step of the "
+                        "bf16 model")
+    ref4 = decoder(model, off, 4)
     for n in slots:
-        decs = {"A": (decoder(model, False, n), model, False), "B": (decoder(model, True, n), model, True),
-                "C": (decoder(model8, True, n), model8, True), "D": (decoder(model4, True, n), model4, True)}
+        decs = {"A": (decoder(model, base, n), model, base), "B": (decoder(model, on, n), model, on),
+                "C": (decoder(model8, on, n), model8, on), "D": (decoder(model4, on, n), model4, on)}
         times = {k: [] for k in ("ref4", "A", "B", "C", "D")}
         for _ in range(args.rounds):
             model.use_wide_decode(False)
             times["ref4"].append(timed(ref4.step, args.steps))
             for name in ("A", "B", "C", "D"):
                 dec, m, wide = decs[name]
-                m.use_wide_decode(wide)                         # (a host flag: the step would recapture on a mismatch)
+                m.use_wide_decode(**wide)                       # (a host flag: the step would recapture on a mismatch)
                 times[name].append(timed(dec.step, args.steps))
         med = {k: statistics.median(v) for k, v in times.items()}
         cell = {}
@@ -923,7 +943,7 @@ def wide_legs(args, torch, model, cfg, prompts, dev):
             cell[k] = {"ms_per_step": round(v, 4), "aggregate_tok_s": round(1000.0 * rows / v, 1), "ms_per_token_per_stream": round(v, 4),
                        "spread_ms": [round(min(times[k]), 4), round(max(times[k]), 4)]}
         cell.update(B_over_A=round(med["B"] / med["A"], 4), C_over_B=round(med["C"] / med["B"], 4), D_over_B=round(med["D"] / med["B"], 4),
-                    D_over_A=round(med["D"] / med["A"], 4))
+                    C_over_A=round(med["C"] / med["A"], 4), D_over_A=round(med["D"] / med["A"], 4))
         res[f"slots{n}"] = cell
         print(f"slots{n}: " + " ".join(f"{k} {v:.4f}" for k, v in med.items()) + " ms", file=sys.stderr, flush=True)
         del decs
