@@ -803,6 +803,60 @@ typedef struct ivl_sample_args {
 
 IVL_API int ivl_sample_rows_fwd(const ivl_sample_args* args, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * ADJUSTMENT: logit bias, frequency / presence penalties and min-p inside the same one launch -- `logit_bias`,
+ * `frequency_penalty` and `presence_penalty` of the OpenAI chat-completion protocol the reference's api/ serves, and HF's
+ * MinPLogitsWarper.  ivl_sample_args is unchanged: the group is a second struct, handed to a second entry point beside it.
+ *   min_p fp32 [S]: 0 = off for the row; NULL = off for all rows;
+ *   freq_penalty, pres_penalty fp32 [S]: f and p of the row; NULL = 0;
+ *   count int32 [S, count_ld], count_ld >= V: c_i = how often token i has been GENERATED in row s (the prompt's tokens are marked
+ *     in `seen` and not counted: the OpenAI / vLLM convention);
+ *   bias_idx int32 [S]: the row's bias table b, outside [0, n_bias) = no bias;
+ *   bias_mask uint32 [n_bias, bias_mask_ld], bias_mask_ld*32 >= V: bit (i & 31) of word (i >> 5) of row b = token i has a bias in
+ *     table b (the layout of `seen`);  bias_val fp32 [n_bias, bias_ld], bias_ld >= V: that bias.
+ * Per row s:
+ *   ADJ-0 off is identity.  adj == NULL, or every field of it NULL / 0: every output is bit-equal to ivl_sample_rows_fwd(args)
+ *      (it IS that call).  A row whose min_p is 0, whose f and p are 0 and whose bias_idx is out of range gets the bits of the call
+ *      without the group; its counts are still kept when count != NULL (ADJ-4).
+ *   ADJ-1 the adjusted row.  x' = the bf16 row after step B (the repetition penalty, rounded to bf16), c_i = count[s*count_ld + i].
+ *        an element whose seen bit is set, with c_i > 0 and (f, p) != (0, 0):   t = x' - RN(RN(f * (float)c_i) + p)
+ *        an element whose bit is set in bias_mask row b:                         t = RN(t + bias_val[b*bias_ld + i])
+ *        then                                                                    x'' = bf16_rne(t)
+ *      plain fp32 operations in this order, each rounded once to nearest even, no fused multiply-add; (float)c_i rounds to
+ *      nearest even above 2^24.  A NaN result counts as -inf (step 1) and +-inf behave as IEEE says: a bias of -inf bans a
+ *      token, +inf forces it (several forced tokens: the lowest index, or a draw among them by step 4's weights of 1).  An element
+ *      touched by neither keeps the bits of x' (nothing is read, modified and written back; -0 stays what it is).  count is read
+ *      only where the seen bit is set: a count word under a clear seen bit never influences a result.  Bits and words at or
+ *      beyond V and other rows and tables are never read or written.
+ *   ADJ-2 what follows.  Steps 1-6, the scores L1-L3 and the constraint F1-F5 run on x'' exactly as they run on x' without the
+ *      group: every output is, bit for bit, what ivl_sample_rows_fwd writes for the row x'' with rep_penalty == 1 and the same
+ *      seen / state tensors.  THE SCORED DISTRIBUTION IS THE ADJUSTED ONE: logprob, the top-N list and cum_logprob are those of
+ *      x'' (HF's processed scores behind all its logits processors, in front of the warpers).
+ *   ADJ-3 min-p (MinPLogitsWarper behind temperature, top-k and top-p, min_tokens_to_keep = 1).  With q_i the Q40 integer of
+ *      step 4 at the row's temperature and qmin = (u64)(min_p * 2^40) (the product is exact in fp32):
+ *        P' = {i in P : q_i >= qmin};
+ *      the maximum (q = 2^40) always survives; min_p above 1 acts as 1, below 0 or NaN as 0.  Z_P, n_kept, prob and the walk of
+ *      step 6 are over P'.  The rule is evaluated element by element where the weight is; a greedy row ignores it.
+ *   ADJ-4 bookkeeping.  The one lane that writes the token, in step C:  count[s*count_ld + token] += 1.  A finished row (step A)
+ *      and a dead end in front of the draw (F5) touch nothing.
+ * THE FORM: with a group that is on, the launch takes at least the controlled form, then the scoring or the constrained form
+ * by the rule of ivl_sample_rows_fwd; the kernels launched without the group are the ones they were.  Penalties inside a beam
+ * search are not served: score_only with adj is refused.
+ * Refused before anything is launched, after the checks of ivl_sample_rows_fwd (IVL_ERR_INVALID_ARG): count without seen or
+ * with count_ld < V; freq_penalty or pres_penalty without count; bias_idx with bias_mask or bias_val NULL, n_bias < 1,
+ * bias_mask_ld*32 < V or bias_ld < V; score_only != 0.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct ivl_sample_adj_args {
+  const float* min_p;
+  const float* freq_penalty; const float* pres_penalty;
+  int32_t* count; int64_t count_ld;
+  const int32_t* bias_idx;
+  const uint32_t* bias_mask; int64_t bias_mask_ld;
+  const float* bias_val; int64_t bias_ld; int n_bias;
+} ivl_sample_adj_args;
+
+IVL_API int ivl_sample_rows_adj_fwd(const ivl_sample_args* args, const ivl_sample_adj_args* adj, void* stream);
+
 /* Sets the bits of ids[0..n) (int64, device) in ONE row of a seen bitmap: the prompt's tokens, before the first draw.  Ids outside
  * [0, V) are ignored, duplicates are fine; n == 0 is a no-op.  seen_row NULL, V < 1, n < 0 or ids NULL with n > 0:
  * IVL_ERR_INVALID_ARG. */

@@ -1,7 +1,7 @@
 """ctypes binding of libivl_hip.so, derived from the C ABI's one declaration: include/ivl_hip.h.
 
 The header is read at import (no library needed): its `#define IVL_*` integers become module attributes, every `struct
-ivl_<x>_args` a ctypes class (`SwaArgs`, `SampleArgs`, `LoraArgs`; all of them in `ARG_STRUCTS`), and every `IVL_API` prototype an entry of `PROTOTYPES`, which `bind`
+ivl_<x>_args` a ctypes class (`SwaArgs`, `SampleArgs`, `LoraArgs` in `ARG_STRUCTS`; a companion group such as `SampleAdjArgs` in `GROUP_STRUCTS`), and every `IVL_API` prototype an entry of `PROTOTYPES`, which `bind`
 applies to a CDLL.
 The library is built in-tree by `__graft_entry__.build()` / `make -C infinitevl_amd/csrc`.
 There is NO fallback: if the shared object is missing, importing an operator raises.
@@ -60,14 +60,16 @@ def _int_expr(expr: str, where: str) -> int:
         raise ImportError(f"ivl_hip.h: {where}: not an integer expression: {expr!r}") from None
 
 
-def parse_header(text: str, structs: dict = None):
+def parse_header(text: str, structs: dict = None, groups: dict = None):
     """(constants {name: int}, the SwaArgs class, prototypes {name: (restype, [argument types])}) of a header text.  `structs`,
-    when given, receives every `typedef struct ivl_<x>_args` of the header as {"ivl_<x>_args": its ctypes class}."""
+    when given, receives every `typedef struct ivl_<x>_args` of the header that some entry point takes as its FIRST parameter
+    as {"ivl_<x>_args": its ctypes class}; `groups`, when given, the others: a companion group, which only ever rides beside
+    another struct (ivl_sample_adj_args beside ivl_sample_args)."""
     text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
     defines = re.findall(r"^[ \t]*#[ \t]*define[ \t]+(IVL_\w+)[ \t]+(\S[^\n]*)", text, re.M)     # (the include guard has no value)
     consts = {name: _int_expr(expr, "#define " + name) for name, expr in defines if name != "IVL_API"}
     text = re.sub(r"^[ \t]*#[^\n]*", " ", text, flags=re.M)
-    structs = {} if structs is None else structs
+    out, structs = structs, {}
     for tag, body in re.findall(r"typedef\s+struct\s+(ivl_\w+_args)\s*\{(.*?)\}\s*\1\s*;", text, re.S):
         fields = []
         for decl in filter(None, (d.strip() for d in body.split(";"))):
@@ -81,8 +83,10 @@ def parse_header(text: str, structs: dict = None):
         raise ImportError("ivl_hip.h: struct ivl_swa_args not found")
     known = {**_C_TYPES, **{f"const {tag}*": POINTER(cls) for tag, cls in structs.items()}}
     protos = {}
+    first = set()
     for ret, name, params in re.findall(r"\bIVL_API\s+" + _DECL + r"(\w+)\s*\(([^()]*)\)\s*;", text, re.S):
         types = []
+        first.update(re.findall(r"^\s*const\s+(ivl_\w+_args)\s*\*", params))
         for param in ([] if params.strip() == "void" else params.split(",")):
             m = re.fullmatch(_DECL + r"\w+", param.strip(), re.S)
             types.append(_ctype(m.group(1) if m else param, name, known))
@@ -90,15 +94,22 @@ def parse_header(text: str, structs: dict = None):
     if len(protos) != len(re.findall(r"\bIVL_API\b", text)):
         raise ImportError(f"ivl_hip.h: only {len(protos)} of its IVL_API declarations are readable prototypes (the last one "
                           f"read: {list(protos)[-1:]})")
+    # (the rule is read off the prototypes: an entry point that took a companion group first would move it to `structs`)
+    for tag, cls in structs.items():
+        into = out if tag in first else groups
+        if into is not None:
+            into[tag] = cls
     return consts, structs["ivl_swa_args"], protos
 
 
 if not os.path.exists(HEADER_PATH):
     raise ImportError(f"{HEADER_PATH} not found: the package is used in-tree and reads the C ABI from the header at import.")
-ARG_STRUCTS = {}                                             # every `ivl_<x>_args` struct of the header: {"ivl_swa_args": SwaArgs, ...}
+ARG_STRUCTS = {}                                             # every `ivl_<x>_args` struct an entry point takes first: {"ivl_swa_args": SwaArgs, ...}
+GROUP_STRUCTS = {}                                           # the companion groups: {"ivl_sample_adj_args": SampleAdjArgs}
 with open(HEADER_PATH) as _f:
-    CONSTANTS, SwaArgs, PROTOTYPES = parse_header(_f.read(), ARG_STRUCTS)
+    CONSTANTS, SwaArgs, PROTOTYPES = parse_header(_f.read(), ARG_STRUCTS, GROUP_STRUCTS)
 SampleArgs, LoraArgs = ARG_STRUCTS["ivl_sample_args"], ARG_STRUCTS["ivl_lora_args"]
+SampleAdjArgs = GROUP_STRUCTS["ivl_sample_adj_args"]
 # the two wide argument structs (32 fields and more) whose sizes and key offsets tests/test_header_binding_cpu.py pins as numbers
 STRUCTS = {"ivl_swa_args": SwaArgs, "ivl_sample_args": SampleArgs}
 globals().update(CONSTANTS)                                  # IVL_ABI_VERSION, IVL_BF16, ..., IVL_OK, IVL_ERR_*, IVL_GDN_*

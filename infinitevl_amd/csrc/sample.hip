@@ -45,6 +45,11 @@
 // comes through the same helper, and it is ANDed into the `valid` mask of smp_load: a disallowed token is absent from every pass,
 // exactly as the elements in front of and behind the row are.  Pass 1 counts |A| beside the maximum (it takes V's place in top-k's
 // switch and in the length of the top-N list); the lane that writes the token then advances the state by three dependent loads.
+//
+// Adjusted (ivl_sample_rows_adj_fwd with a group that is on; twins of the controlled, scoring and constrained forms, which are
+// compiled without a line of it): frequency / presence penalties over a row of counts of the generated tokens and a logit-bias
+// table per row, added where smp_load has re-keyed the tile and rounded back to bf16 -- nothing behind the key changes -- and
+// min-p as one more predicate on the Q40 weight where passes 5 and 6 evaluate it.  The lane that writes the token counts it.
 #include "ivl_common.h"
 
 #include <type_traits>
@@ -189,6 +194,66 @@ struct SmpPenFsm : SmpPen {
 __device__ __forceinline__ unsigned smp_load(const SmpRow& r, const SmpPenFsm& pen, long long j, unsigned (&key)[8]) {
   unsigned valid = smp_load(r, static_cast<const SmpPen&>(pen), j, key);
   if (pen.allow) valid &= smp_seen_bits(r, pen.allow, j);
+  return valid;
+}
+
+// The adjusted forms (ADJ-1 of include/ivl_hip.h): the constrained form's view, then the additive adjustments of the row -- the
+// frequency / presence penalty on the seen elements that have been generated (count > 0) and the row's logit-bias table -- in
+// plain fp32, each operation rounded once, and one rounding back to bf16.  cbits: the row's seen bitmap, NULL when (f, p) ==
+// (0, 0); bbits / bval: the row's bias bitmap and values, NULL without a table (all uniform per workgroup: nothing is fetched
+// then).  A count word is read only under a set seen bit, a bias value only under a set bias bit, both only inside the row.
+// The arithmetic starts from the VALUE of the key: a NaN arrives as -inf and -0 as +0, and every result they can reach lies in
+// the same key class as the one reached from the bits themselves (anything with a NaN is a NaN = -inf; -inf plus or minus
+// anything is -inf or a NaN; a zero of either sign plus t is t, or a zero).  An untouched element keeps its key.  A penalised
+// element whose penalty sums to zero (f c + p == 0) IS touched and re-keyed from its value: it keeps its key class, not its
+// bits (-0 comes out as +0, the same key), which is all that the passes can see.
+struct SmpPenAdj : SmpPenFsm {
+  const unsigned char* cbits;
+  const int* cnt;
+  float f, p;
+  const unsigned char* bbits;
+  const float* bval;
+};
+__device__ __forceinline__ unsigned smp_bf16_rne(float y) {
+  unsigned u = __float_as_uint(y);
+  if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (u >> 16) | 0x40u;
+  u += 0x7FFFu + ((u >> 16) & 1u);
+  return u >> 16;
+}
+__device__ __forceinline__ unsigned smp_load(const SmpRow& r, const SmpPenAdj& pen, long long j, unsigned (&key)[8]) {
+  const unsigned valid = smp_load(r, static_cast<const SmpPenFsm&>(pen), j, key);
+  if (pen.cbits || pen.bbits) {                  // uniform per workgroup
+    const unsigned pm = pen.cbits ? smp_seen_bits(r, pen.cbits, j) & valid : 0u;
+    const unsigned bm = pen.bbits ? smp_seen_bits(r, pen.bbits, j) & valid : 0u;
+    if ((pm | bm) != 0u) {
+      // The tile's loads leave together, one wait for all: an element without a bit reads the word of the tile's LOWEST set
+      // bit in its place (a word the row may read, the same line) -- a load under a branch per element would wait for each
+      // of them in turn, in every pass (measured: the sampled operator at V = 151936, 4 rows, 481 us that way).
+      const long long i0 = j * 8 - r.off;
+      int c[8] = {};
+      float bv[8] = {};
+      if (pm != 0u) {
+        const int lo = __ffs((int)pm) - 1;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) c[e] = pen.cnt[i0 + ((pm >> e & 1u) ? e : lo)];
+      }
+      if (bm != 0u) {
+        const int lo = __ffs((int)bm) - 1;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) bv[e] = pen.bval[i0 + ((bm >> e & 1u) ? e : lo)];
+      }
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const bool pe = (pm >> e & 1u) && c[e] > 0, be = (bm >> e & 1u) != 0u;
+        if (pe || be) {
+          float t = smp_key_value(key[e]);
+          if (pe) t = __fsub_rn(t, __fadd_rn(__fmul_rn(pen.f, (float)c[e]), pen.p));
+          if (be) t = __fadd_rn(t, bv[e]);
+          key[e] = smp_key(smp_bf16_rne(t));
+        }
+      }
+    }
+  }
   return valid;
 }
 
@@ -522,6 +587,27 @@ struct SmpFsm {
   const int* trans;
 };
 
+// The adjustment group of ivl_sample_adj_args; every pointer may be NULL (off)
+struct SmpAdj {
+  const float* min_p;
+  const float* freq;
+  const float* pres;
+  int* count;
+  long long count_ld;
+  const int* bias_idx;
+  const unsigned* bias_mask;
+  long long bias_mask_ld;
+  const float* bias_val;
+  long long bias_ld;
+  int n_bias;
+};
+
+// ADJ-4, by the one lane that wrote the token, beside smp_after (the passes' reads of the row's counts lie in front of it, as
+// their reads of `seen` do)
+__device__ __forceinline__ void smp_adj_after(const SmpAdj& a, long long s, long long tok) {
+  if (a.count) a.count[s * a.count_ld + tok] += 1;
+}
+
 // A dead end in front of the draw (F5: no such state, or a state that allows nothing), by every thread of the workgroup: step
 // A's outputs and done = 3; the counter, seen, n_new, the history, the scores' sums and rings and the state stay as they are
 __device__ __forceinline__ void smp_fsm_dead(const SmpCtl& c, const SmpLp& lp, long long s, long long* token, long long token_stride,
@@ -549,7 +635,8 @@ __device__ __forceinline__ void smp_fsm_after(const SmpFsm& f, const SmpCtl& c, 
 }
 
 // CTL: no type (the control-free form, with the parameter list it always had), SmpCtl, SmpCtl and SmpLp, or these two and
-// SmpScore (the score-only form: steps A, B, L1 and L3, nothing committed) or SmpFsm (the constrained form)
+// SmpScore (the score-only form: steps A, B, L1 and L3, nothing committed) or SmpFsm (the constrained form); SmpAdj behind
+// SmpCtl, SmpCtl and SmpLp, or these two and SmpFsm: the adjusted twin of that form
 struct SmpScore {};
 template <typename T, typename... U> constexpr bool smp_has = (std::is_same<T, U>::value || ...);
 // the group of type T among the kernel's trailing parameters
@@ -564,9 +651,10 @@ sample_rows_kernel(const bf16_t* __restrict__ logits, long long ld, int V, const
                    const int* __restrict__ top_k, const float* __restrict__ top_p, const long long* __restrict__ seed,
                    long long* __restrict__ counter, long long* __restrict__ token, long long token_stride,
                    int* __restrict__ n_kept, float* __restrict__ prob, const CTL... ctl_) {
-  constexpr bool kCtl = sizeof...(CTL) >= 1, kLp = sizeof...(CTL) >= 2, kScore = smp_has<SmpScore, CTL...>;
-  constexpr bool kFsm = smp_has<SmpFsm, CTL...>;
-  typename std::conditional<kFsm, SmpPenFsm, typename std::conditional<kCtl, SmpPen, SmpNoPen>::type>::type pen;
+  constexpr bool kCtl = smp_has<SmpCtl, CTL...>, kLp = smp_has<SmpLp, CTL...>, kScore = smp_has<SmpScore, CTL...>;
+  constexpr bool kFsm = smp_has<SmpFsm, CTL...>, kAdj = smp_has<SmpAdj, CTL...>;
+  typename std::conditional<kAdj, SmpPenAdj, typename std::conditional<kFsm, SmpPenFsm,
+      typename std::conditional<kCtl, SmpPen, SmpNoPen>::type>::type>::type pen;
   [[maybe_unused]] int fsm_q = -1;                      // the row's state, read once: the lane that advances it writes last
   [[maybe_unused]] bool lp_on = true;                   // (the constrained form is launched with the score group off, too)
   if constexpr (kCtl) {
@@ -604,6 +692,18 @@ sample_rows_kernel(const bf16_t* __restrict__ logits, long long ld, int V, const
         return;
       }
       pen.allow = fsm_q >= 0 ? (const unsigned char*)(f.mask + (long long)fsm_q * f.mask_ld) : nullptr;
+    }
+    if constexpr (kAdj) {
+      const SmpAdj& a = smp_get<SmpAdj>(ctl_...);
+      if constexpr (!kFsm) pen.allow = nullptr;
+      pen.f = a.freq ? a.freq[s] : 0.f;
+      pen.p = a.pres ? a.pres[s] : 0.f;
+      pen.cnt = a.count ? a.count + s * a.count_ld : nullptr;
+      pen.cbits = pen.cnt && (pen.f != 0.f || pen.p != 0.f) ? (const unsigned char*)(ctl.seen + s * ctl.seen_ld) : nullptr;
+      const int b = a.bias_idx ? a.bias_idx[s] : -1;
+      const bool biased = b >= 0 && b < a.n_bias;
+      pen.bbits = biased ? (const unsigned char*)(a.bias_mask + (long long)b * a.bias_mask_ld) : nullptr;
+      pen.bval = biased ? a.bias_val + (long long)b * a.bias_ld : nullptr;
     }
   }
   __shared__ u64 hist[SMP_BINS];
@@ -700,12 +800,19 @@ sample_rows_kernel(const bf16_t* __restrict__ logits, long long ld, int V, const
       if constexpr (kLp)
         smp_lp_after(smp_get<SmpLp>(ctl_...), smp_get<SmpCtl>(ctl_...), s, nrow, mkey, mkey, smp_key_value(mkey), lse, lpl);
       if constexpr (kCtl && !kScore) smp_after(smp_get<SmpCtl>(ctl_...), s, (long long)midx);
+      if constexpr (kAdj) smp_adj_after(smp_get<SmpAdj>(ctl_...), s, (long long)midx);
       if constexpr (kFsm) smp_fsm_after(smp_get<SmpFsm>(ctl_...), smp_get<SmpCtl>(ctl_...), s, fsm_q, (long long)midx);
     }
     return;
   }
   const float xm = smp_key_value(mkey);
   const float c = 1.44269504088896341f / tau;
+  [[maybe_unused]] u64 qmin = 0ull;                     // ADJ-3: a kept element's weight is at least (u64)(min_p 2^40); above 1 as 1
+  if constexpr (kAdj) {
+    const SmpAdj& a = smp_get<SmpAdj>(ctl_...);
+    const float mp = a.min_p ? a.min_p[s] : 0.f;
+    qmin = mp > 0.f ? (mp < 1.f ? (u64)(mp * 0x1p40f) : SMP_ONE) : 0ull;
+  }
 
   // ---- top-k: the bin where the count from the top reaches k, then the key inside it
   unsigned tk = 0u;
@@ -818,7 +925,14 @@ sample_rows_kernel(const bf16_t* __restrict__ logits, long long ld, int V, const
       const unsigned valid = smp_load(r, pen, j, key);
 #pragma unroll
       for (int e = 0; e < 8; ++e)
-        if ((valid >> e & 1u) && key[e] >= t) { ++cnt; mass += smp_weight(key[e], mkey, xm, c); }
+        if ((valid >> e & 1u) && key[e] >= t) {
+          if constexpr (kAdj) {
+            const u64 w = smp_weight(key[e], mkey, xm, c);
+            if (w >= qmin) { ++cnt; mass += w; }
+          } else {
+            ++cnt; mass += smp_weight(key[e], mkey, xm, c);
+          }
+        }
     }
   }
   mass = smp_wave_sum(mass);
@@ -862,6 +976,7 @@ sample_rows_kernel(const bf16_t* __restrict__ logits, long long ld, int V, const
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       q[e] = ((valid >> e & 1u) && key[e] >= t) ? smp_weight(key[e], mkey, xm, c) : 0ull;
+      if constexpr (kAdj) q[e] = q[e] >= qmin ? q[e] : 0ull;
       m += q[e];
     }
     const u64 incl = smp_wave_incl_scan(m, lane);
@@ -888,6 +1003,7 @@ sample_rows_kernel(const bf16_t* __restrict__ logits, long long ld, int V, const
           smp_lp_after(smp_get<SmpLp>(ctl_...), smp_get<SmpCtl>(ctl_...), s, nrow, ke, mkey, xm, lse, lpl);
         }
         if constexpr (kCtl) smp_after(smp_get<SmpCtl>(ctl_...), s, j * 8 - r.off + e);
+        if constexpr (kAdj) smp_adj_after(smp_get<SmpAdj>(ctl_...), s, j * 8 - r.off + e);
         if constexpr (kFsm) smp_fsm_after(smp_get<SmpFsm>(ctl_...), smp_get<SmpCtl>(ctl_...), s, fsm_q, j * 8 - r.off + e);
       }
       return;
@@ -907,7 +1023,7 @@ token_mark_kernel(unsigned* __restrict__ seen_row, long long V, const long long*
 
 }  // namespace ivl
 
-// one launch statement for the five forms: the groups G follow the twelve parameters that every form takes
+// one launch statement for the five forms and their three adjusted twins: the groups G follow the twelve parameters that every form takes
 template <typename... G>
 static void sample_rows_launch(const ivl_sample_args& a, void* stream, const G&... g) {
   using namespace ivl;
@@ -917,10 +1033,10 @@ static void sample_rows_launch(const ivl_sample_args& a, void* stream, const G&.
                      (int*)a.n_kept, a.prob, g...);
 }
 
-// Checks in the order base, controls, scores, constraint; then the form rule of include/ivl_hip.h, written once.
-extern "C" int ivl_sample_rows_fwd(const ivl_sample_args* args, void* stream) {
+// Checks in the order base, controls, scores, constraint, adjustment; then the form rule of include/ivl_hip.h, written once.
+// adj == NULL: ivl_sample_rows_fwd, whose five launches stand as they were.
+static int sample_rows(const ivl_sample_args* args, const ivl_sample_adj_args* adj, void* stream, const char* fn) {
   using namespace ivl;
-  static const char fn[] = "ivl_sample_rows_fwd";
   IVL_REQUIRE(args, IVL_ERR_INVALID_ARG, "%s: NULL args", fn);
   const ivl_sample_args& a = *args;
   const bool score = a.score_only != 0;
@@ -966,6 +1082,44 @@ extern "C" int ivl_sample_rows_fwd(const ivl_sample_args* args, void* stream) {
                 (long long)a.mask_ld, a.V);
     IVL_REQUIRE(a.n_states >= 1, IVL_ERR_INVALID_ARG, "%s: n_states=%d", fn, a.n_states);
   }
+  // ---- adjustment
+  bool adjusted = false;
+  if (adj) {
+    const ivl_sample_adj_args& j = *adj;
+    IVL_REQUIRE(!j.count || a.seen, IVL_ERR_INVALID_ARG, "%s: count needs seen", fn);
+    IVL_REQUIRE(!j.count || j.count_ld >= (int64_t)a.V, IVL_ERR_INVALID_ARG, "%s: count_ld=%lld below V=%d", fn, (long long)j.count_ld,
+                a.V);
+    IVL_REQUIRE(!(j.freq_penalty || j.pres_penalty) || j.count, IVL_ERR_INVALID_ARG, "%s: freq_penalty and pres_penalty need count",
+                fn);
+    if (j.bias_idx) {
+      IVL_REQUIRE(j.bias_mask, IVL_ERR_INVALID_ARG, "%s: bias_idx needs bias_mask", fn);
+      IVL_REQUIRE(j.bias_val, IVL_ERR_INVALID_ARG, "%s: bias_idx needs bias_val", fn);
+      IVL_REQUIRE(j.n_bias >= 1, IVL_ERR_INVALID_ARG, "%s: n_bias=%d", fn, j.n_bias);
+      IVL_REQUIRE(j.bias_mask_ld * 32 >= (int64_t)a.V, IVL_ERR_INVALID_ARG, "%s: bias_mask_ld=%lld words hold fewer than V=%d bits",
+                  fn, (long long)j.bias_mask_ld, a.V);
+      IVL_REQUIRE(j.bias_ld >= (int64_t)a.V, IVL_ERR_INVALID_ARG, "%s: bias_ld=%lld below V=%d", fn, (long long)j.bias_ld, a.V);
+    }
+    IVL_REQUIRE(!score, IVL_ERR_INVALID_ARG, "%s: score_only takes no adjustment group", fn);
+    adjusted = j.min_p || j.freq_penalty || j.pres_penalty || j.count || j.bias_idx;      // else ADJ-0: the call without the group
+  }
+  if (adjusted) {
+    const ivl_sample_adj_args& j = *adj;
+    const SmpCtl c = {a.rep_penalty, a.seen, a.seen_ld, (const long long*)a.stop_ids, a.n_stop, (const long long*)a.budget,
+                      (const long long*)a.fill, (long long*)a.n_new, a.done, (long long*)a.history, a.hist_ld};
+    const SmpLp l = {a.logprob, a.n_top, (long long*)a.top_ids, a.top_logprobs, a.cum_logprob, a.lp_history,
+                     (long long*)a.top_hist_ids, a.top_hist_lp};
+    const SmpFsm f = {a.fsm_state, a.fsm_mask, a.mask_ld, a.n_states, (const long long*)a.fsm_desc, a.fsm_cls, a.fsm_trans};
+    const SmpAdj d = {j.min_p, j.freq_penalty, j.pres_penalty, j.count, j.count_ld, j.bias_idx, j.bias_mask, j.bias_mask_ld,
+                      j.bias_val, j.bias_ld, j.n_bias};
+    // at least the controlled form, then the scoring or the constrained one by the rule below
+    if (a.fsm_state)
+      sample_rows_launch(a, stream, c, l, f, d);
+    else if (a.logprob || a.n_top > 0 || a.top_ids || a.top_logprobs || a.cum_logprob || ring)
+      sample_rows_launch(a, stream, c, l, d);
+    else
+      sample_rows_launch(a, stream, c, d);
+    return check_launch(fn);
+  }
   // ---- the device structs, each filled here and nowhere else, in the order of their fields (the score-only form reads seen
   //      and done and writes neither)
   const SmpCtl c = {a.rep_penalty, a.seen, a.seen_ld, (const long long*)a.stop_ids, a.n_stop, (const long long*)a.budget,
@@ -985,6 +1139,14 @@ extern "C" int ivl_sample_rows_fwd(const ivl_sample_args* args, void* stream) {
   else
     sample_rows_launch(a, stream);
   return check_launch(fn);
+}
+
+extern "C" int ivl_sample_rows_fwd(const ivl_sample_args* args, void* stream) {
+  return sample_rows(args, nullptr, stream, "ivl_sample_rows_fwd");
+}
+
+extern "C" int ivl_sample_rows_adj_fwd(const ivl_sample_args* args, const ivl_sample_adj_args* adj, void* stream) {
+  return sample_rows(args, adj, stream, "ivl_sample_rows_adj_fwd");
 }
 
 extern "C" int ivl_token_mark_fwd(uint32_t* seen_row, int64_t V, const int64_t* ids, int64_t n, void* stream) {

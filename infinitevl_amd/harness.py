@@ -750,13 +750,16 @@ class _RowField(NamedTuple):
     name: str                   # the attribute
     dtype: torch.dtype
     shape: Tuple[str, ...]      # after the row, as named extents: "words" of the seen bitmap (vocab_size), "max_stop", "history",
-    #                             "top" (logprobs >= 1), "ring" (history, of a sampler with score rings).  The tensor exists when
-    #                             every extent is non-zero
+    #                             "top" (logprobs >= 1), "ring" (history, of a sampler with score rings), "vocab" (vocab_size).
+    #                             The tensor exists when every extent is non-zero
     init: float                 # of a fresh row, and what set() clears a state tensor to
     state: bool = False         # a step changes it (state() saves it); else a parameter
     kw: Optional[str] = None    # the keyword under which ops.sample_tokens takes it; None: positional
     score: bool = False         # ... and only in a sampler built with logprobs
     grammar: bool = False       # ... and only in a sampler built with grammar_states
+    penalties: bool = False     # ... and only in a sampler built with penalties=True
+    bias: bool = False          # ... and only in a sampler built with bias_tables
+    cleared: bool = False       # set() puts it back to `init` although no step changes it (state() does not save it)
 
 
 def _stop_ids(who: str, ids, at_most: Optional[int] = None) -> List[int]:
@@ -820,7 +823,15 @@ class Sampler:
     recapture is involved: load_grammar() puts a grammar.TokenFsm into the arena, set_grammar() points a row at it, and the
     kernel restricts the row's draw to the tokens its state allows and advances the state with the token it emits.  A grammar
     loaded and set between two replays of a captured step is obeyed by the next one.  A row whose state allows nothing ends with
-    done code 3.  Fork and state() follow the table: a forked row continues from its parent's grammar state."""
+    done code 3.  Fork and state() follow the table: a forked row continues from its parent's grammar state.
+
+    Adjustments (`frequency_penalty` / `presence_penalty` / `logit_bias` of the reference's api/protocol.py, HF's
+    MinPLogitsWarper): a sampler built with `penalties=True` (and vocab_size) holds min_p, freq_penalty and pres_penalty per row
+    and `count` (int32 [n_rows, vocab_size]: how often the row GENERATED each token; the prompt's tokens, mark(), are seen but
+    not counted); one built with `bias_tables` > 0 owns an ops.BiasTables arena of that many {token: bias} tables and one more
+    per-row tensor, `bias_idx` (-1 = no bias): load_logit_bias() fills a table, set_logit_bias() points a row at it.  Either
+    uses the adjusted form of the launch (ivl_sample_rows_adj_fwd) from construction on, so parameters, tables and a row's
+    table change between replays without a recapture.  The scores of such a sampler are those of the adjusted distribution."""
 
     # THE list of the per-row tensors: each is an attribute of its name, [n_rows, *shape], or None when the sampler does not hold
     # it.  row_tensors() (so every fork and beam gather), state() / load_state(), what set() clears and the keywords of
@@ -847,14 +858,21 @@ class Sampler:
         _RowField("top_hist_ids", torch.int64, ("ring", "top"), -1, state=True, kw="top_hist_ids", score=True),
         _RowField("top_hist_lp", torch.float32, ("ring", "top"), -math.inf, state=True, kw="top_hist_lp", score=True),
         _RowField("fsm_state", torch.int32, (), -1, state=True, kw="fsm_state", grammar=True),      # -1 = unconstrained
+        _RowField("min_p", torch.float32, (), 0.0, kw="min_p", penalties=True),
+        _RowField("freq_penalty", torch.float32, (), 0.0, kw="freq_penalty", penalties=True),
+        _RowField("pres_penalty", torch.float32, (), 0.0, kw="pres_penalty", penalties=True),
+        _RowField("count", torch.int32, ("vocab",), 0, state=True, kw="count", penalties=True),     # of the GENERATED tokens
+        _RowField("bias_idx", torch.int32, (), -1, kw="bias_idx", bias=True, cleared=True),         # -1 = no bias
     )
 
     def __init__(self, n_rows: int, device, vocab_size: Optional[int] = None, max_stop: int = 8, history: int = 0,
                  logprobs: Optional[int] = None, *, score_rings: bool = True, grammar_states: int = 0,
-                 grammar_slots: Optional[int] = None, grammar_trans: Optional[int] = None):
+                 grammar_slots: Optional[int] = None, grammar_trans: Optional[int] = None, penalties: bool = False,
+                 bias_tables: int = 0):
         """score_rings=False: no per-token score rings (lp_history, top_hist_ids, top_hist_lp) beside the token history.
         grammar_states: the states of all grammars loaded at a time; grammar_slots: how many grammars (default: one per row);
-        grammar_trans: their transition entries, n_states x n_classes each (default: 256 per state)."""
+        grammar_trans: their transition entries, n_states x n_classes each (default: 256 per state).  penalties: min-p and the
+        frequency / presence penalties with the rows' counts; bias_tables: how many logit-bias tables at a time (both: vocab_size)."""
         if n_rows < 1:
             raise ValueError(f"Sampler: n_rows must be >= 1; got {n_rows}")
         if vocab_size is not None and (isinstance(vocab_size, bool) or not isinstance(vocab_size, int) or vocab_size < 1):
@@ -871,18 +889,27 @@ class Sampler:
             raise ValueError("Sampler: grammar_slots and grammar_trans need grammar_states > 0")
         if grammar_states > 0 and vocab_size is None:
             raise ValueError("Sampler: grammar_states needs vocab_size (the allowed-token bitmaps)")
+        if not isinstance(penalties, bool):
+            raise ValueError(f"Sampler: penalties must be a bool; got {penalties!r}")
+        if isinstance(bias_tables, bool) or not isinstance(bias_tables, int) or bias_tables < 0:
+            raise ValueError(f"Sampler: bias_tables must be an int >= 0; got {bias_tables!r}")
+        if (penalties or bias_tables > 0) and vocab_size is None:
+            raise ValueError("Sampler: penalties and bias_tables need vocab_size (the rows' counts, the bias tables)")
         self.n_rows = int(n_rows)
+        self.penalties = penalties
+        self.biases = ops.BiasTables(device, vocab_size, bias_tables) if bias_tables else None      # the arena of the bias tables
         # the arena of the grammars' tables (its own checks refuse what is left of the three sizes)
         self.grammars = ops.FsmTables(device, vocab_size, grammar_states, n_rows if grammar_slots is None else grammar_slots,
                                       256 * grammar_states if grammar_trans is None else grammar_trans) if grammar_states else None
         self.vocab_size, self.max_stop, self.history_len, self.n_logprobs = vocab_size, max_stop, history, logprobs
         self.controlled = vocab_size is not None or history > 0 or logprobs is not None      # (a grammar needs vocab_size)
         extent = {"words": (vocab_size + 31) // 32 if vocab_size is not None else 0, "max_stop": max_stop, "history": history,
-                  "top": logprobs or 0, "ring": history if score_rings else 0}
+                  "top": logprobs or 0, "ring": history if score_rings else 0, "vocab": vocab_size or 0}
         self._fields = []                                # the entries of _TABLE this sampler holds, in the table's order
         for f in self._TABLE:
             shape = [extent[e] for e in f.shape]
-            held = all(shape) and (logprobs is not None or not f.score) and (self.grammars is not None or not f.grammar)
+            held = all(shape) and (logprobs is not None or not f.score) and (self.grammars is not None or not f.grammar) and \
+                (penalties or not f.penalties) and (self.biases is not None or not f.bias)
             setattr(self, f.name, torch.full((n_rows, *shape), f.init, dtype=f.dtype, device=device) if held else None)
             if held:
                 self._fields.append(f)
@@ -932,6 +959,18 @@ class Sampler:
             fill_token = p["fill_token"]
             if isinstance(fill_token, bool) or not isinstance(fill_token, int) or not 0 <= fill_token < 2 ** 63:
                 raise ValueError(f"{who}: fill_token must be an int >= 0; got {fill_token!r}")
+        for k in ("min_p", "frequency_penalty", "presence_penalty"):
+            if k not in p:
+                continue
+            if isinstance(p[k], bool) or not isinstance(p[k], (int, float)):
+                raise ValueError(f"{who}: {k} must be a number; got {p[k]!r}")
+            p[k] = v = float(p[k])
+            if k == "min_p" and not 0.0 <= v <= 1.0:
+                raise ValueError(f"{who}: min_p must be in [0, 1] (0 = off); got {v}")
+            if k != "min_p" and not math.isfinite(v):
+                raise ValueError(f"{who}: {k} must be finite; got {v}")
+            if v != 0.0 and not self.penalties:
+                raise ValueError(f"{who}: {k} needs a Sampler built with penalties=True")
         return p
 
     def _write(self, row: int, p: dict) -> None:
@@ -954,14 +993,21 @@ class Sampler:
             self.budget[row] = -1 if p["max_new_tokens"] is None else p["max_new_tokens"]
         if "fill_token" in p:
             self.fill[row] = p["fill_token"]
+        if self.penalties:
+            for k, t in (("min_p", self.min_p), ("frequency_penalty", self.freq_penalty), ("presence_penalty", self.pres_penalty)):
+                if k in p:
+                    t[row] = p[k]
         if "stop_token_ids" in p and "max_new_tokens" in p:
             self._ends[row] = bool(p["stop_token_ids"]) or p["max_new_tokens"] is not None
             if self._ends[row]:
                 self.controlled = True
 
     def set(self, row: int, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0,
-            repetition_penalty: float = 1.0, stop_token_ids=(), max_new_tokens: Optional[int] = None, fill_token: int = 0) -> None:
-        """Parameters and a fresh stream for `row`: counter 0, and the row's bitmap, n_new, done, history and scores cleared.
+            repetition_penalty: float = 1.0, stop_token_ids=(), max_new_tokens: Optional[int] = None, fill_token: int = 0,
+            min_p: float = 0.0, frequency_penalty: float = 0.0, presence_penalty: float = 0.0) -> None:
+        """Parameters and a fresh stream for `row`: counter 0, and the row's bitmap, n_new, done, history, scores and counts
+        cleared, and the row without a logit bias (set_logit_bias follows).  min_p in [0, 1] (0 = off), frequency_penalty and
+        presence_penalty finite (0 = off): other values need a sampler built with penalties=True.
         temperature 0 = greedy; top_k 0 and top_p 1 = off; repetition_penalty 1 = off (else finite and > 0: needs a sampler
         built with vocab_size); stop_token_ids: at most max_stop ints >= 0; max_new_tokens: None or an int >= 1; fill_token:
         what the row's token becomes once it is done."""
@@ -969,7 +1015,7 @@ class Sampler:
         given = locals()                                 # every keyword of the signature, by the names of _SET_DEFAULTS
         self._write(row, self._checked("Sampler.set", {k: given[k] for k in self._SET_DEFAULTS}))
         for f in self._fields:
-            if f.state:
+            if f.state or f.cleared:
                 getattr(self, f.name)[row] = f.init
 
     # ---- a row's parameters and state as one row of every tensor: fork ---------------------------------------------------
@@ -1060,6 +1106,29 @@ class Sampler:
             raise ValueError(f"Sampler.grammar_state: row {row} is in state {g}, which no loaded grammar owns")
         return found[1]
 
+    # ---- logit bias -----------------------------------------------------------------------------------------------------------
+    def _bias_arena(self, who: str) -> "ops.BiasTables":
+        if self.biases is None:
+            raise ValueError(f"Sampler.{who}: needs a Sampler built with bias_tables > 0")
+        return self.biases
+
+    def load_logit_bias(self, bias: dict) -> "ops.BiasHandle":
+        """Puts a {token id: bias} dict (`logit_bias` of the chat-completion protocol; -inf bans a token, +inf forces it) into a
+        free table of the sampler's arena (between replays: no recapture); ValueError when every table is taken."""
+        return self._bias_arena("load_logit_bias").load(bias)
+
+    def unload_logit_bias(self, handle: "ops.BiasHandle") -> None:
+        """Frees the table.  A row that still points at it is not biased from its next draw on."""
+        self._bias_arena("unload_logit_bias").unload(handle)
+
+    def set_logit_bias(self, row: int, handle: Optional["ops.BiasHandle"]) -> None:
+        """`row` draws under the bias table `handle` from its next draw on; None: no bias.  Call it after set(), which clears
+        the row to no bias."""
+        row, arena = self._row(row), self._bias_arena("set_logit_bias")
+        if handle is not None and handle not in arena.handles():
+            raise ValueError(f"Sampler.set_logit_bias: {handle!r} is not loaded in this sampler")
+        self.bias_idx[row] = -1 if handle is None else handle.index
+
     def _stateful(self):
         return {f.name: getattr(self, f.name) for f in self._fields if f.state}
 
@@ -1119,6 +1188,8 @@ class Sampler:
                 del kw["rep_penalty"]                    # the penalty reads the bitmap: without one the launch takes neither
             if self.grammars is not None:
                 kw["fsm"] = self.grammars
+            if self.biases is not None:
+                kw["bias"] = self.biases
         return ops.sample_tokens(logits, self.temperature[sl], self.top_k[sl], self.top_p[sl], self.seed[sl], self.counter[sl],
                                  out=out, **kw)
 
@@ -1213,7 +1284,8 @@ class GraphedMultiStreamDecode(_Graphed):
 
     @torch.no_grad()
     def admit(self, slot: int, inputs_embeds: torch.Tensor, position_ids: Optional[torch.Tensor] = None,
-              sampling: Optional[dict] = None, prompt_ids: Optional[torch.Tensor] = None, grammar=None, adapter=None) -> torch.Tensor:
+              sampling: Optional[dict] = None, prompt_ids: Optional[torch.Tensor] = None, grammar=None, adapter=None,
+              logit_bias=None) -> torch.Tensor:
         """Start a stream in `slot` with a prompt inputs_embeds [1,T,hidden] (M-RoPE position_ids [3,1,T]; default: text
         positions 0..T-1).  Its first generated token is written to token[slot] and returned.  `sampling`: the keyword
         arguments of Sampler.set for this stream (needs a sampler), applied before that first token is drawn.  `prompt_ids`
@@ -1221,10 +1293,12 @@ class GraphedMultiStreamDecode(_Graphed):
         first token is drawn; that token goes through the same controlled launch as every later one, so it is counted, logged
         and may already end the stream.  `grammar` (a handle of Sampler.load_grammar): the stream starts in the grammar's start
         state, set after the row's parameters and before the first draw, so the first token is constrained too.  `adapter`: the stream's LoRA adapter
-        (set_adapter); the prompt is prefilled under it."""
+        (set_adapter); the prompt is prefilled under it.  `logit_bias` (a handle of Sampler.load_logit_bias): the row's bias
+        table, set before the first draw like the grammar."""
         if sampling is not None and self.sampler is None:
             raise ValueError("admit: sampling parameters need a GraphedMultiStreamDecode built with a sampler")
         self._check_grammar("admit", grammar)
+        self._check_bias("admit", logit_bias)
         T = self._check_prompt("admit", inputs_embeds, position_ids, prompt_ids)
         self.set_adapter(slot, adapter)
         if position_ids is None:
@@ -1233,6 +1307,8 @@ class GraphedMultiStreamDecode(_Graphed):
             self.sampler.set(slot, **sampling)
         if grammar is not None:
             self.sampler.set_grammar(slot, grammar)
+        if logit_bias is not None:
+            self.sampler.set_logit_bias(slot, logit_bias)
         if prompt_ids is not None:
             self.sampler.mark(slot, prompt_ids.to(inputs_embeds.device))
         self.cache.admit(slot)
@@ -1266,6 +1342,12 @@ class GraphedMultiStreamDecode(_Graphed):
             raise ValueError(f"{who}: a grammar needs a GraphedMultiStreamDecode whose sampler was built with grammar_states")
         if grammar is not None and grammar not in self.sampler.grammars.handles():
             raise ValueError(f"{who}: {grammar!r} is not loaded in the sampler (Sampler.load_grammar)")
+
+    def _check_bias(self, who: str, logit_bias) -> None:
+        if logit_bias is not None and (self.sampler is None or self.sampler.biases is None):
+            raise ValueError(f"{who}: a logit_bias needs a GraphedMultiStreamDecode whose sampler was built with bias_tables")
+        if logit_bias is not None and logit_bias not in self.sampler.biases.handles():
+            raise ValueError(f"{who}: {logit_bias!r} is not loaded in the sampler (Sampler.load_logit_bias)")
 
     def _check_prompt(self, who: str, inputs_embeds, position_ids, prompt_ids) -> int:
         if prompt_ids is not None and self.sampler is None:
@@ -1380,14 +1462,17 @@ class GraphedMultiStreamDecode(_Graphed):
 
     @torch.no_grad()
     def admit_n(self, slots, inputs_embeds: torch.Tensor, position_ids: Optional[torch.Tensor] = None,
-                sampling=None, prompt_ids: Optional[torch.Tensor] = None, grammar=None, adapter=None) -> torch.Tensor:
+                sampling=None, prompt_ids: Optional[torch.Tensor] = None, grammar=None, adapter=None,
+                logit_bias=None) -> torch.Tensor:
         """Several answers to one prompt (num_return_sequences of the reference's api/chat.py:164): the prompt is prefilled
         ONCE, into slots[0]; its cache and sampler rows are forked to slots[1:] before any token is drawn; then every slot
         draws its own first token from the same logits, in its own sampler row.  `sampling`: one dict of Sampler.set
         keyword arguments per slot (e.g. one seed each); every slot ends up as admit(slot, ..., sampling=that dict,
-        prompt_ids=prompt_ids) would leave it.  `grammar`: every slot starts in that grammar's start state.  Returns token[slots]."""
+        prompt_ids=prompt_ids) would leave it.  `grammar`: every slot starts in that grammar's start state; `logit_bias`: every slot
+        draws under that bias table.  Returns token[slots]."""
         slots = self._slots("admit_n", slots)
         self._check_grammar("admit_n", grammar)
+        self._check_bias("admit_n", logit_bias)
         if sampling is not None and self.sampler is None:
             raise ValueError("admit_n: sampling parameters need a GraphedMultiStreamDecode built with a sampler")
         T = self._check_prompt("admit_n", inputs_embeds, position_ids, prompt_ids)
@@ -1404,6 +1489,8 @@ class GraphedMultiStreamDecode(_Graphed):
             self.sampler.set(first, **sampling[0])
         if grammar is not None:
             self.sampler.set_grammar(first, grammar)    # (it travels to the other slots with the row)
+        if logit_bias is not None:
+            self.sampler.set_logit_bias(first, logit_bias)
         if prompt_ids is not None:
             self.sampler.mark(first, prompt_ids.to(inputs_embeds.device))
         self.cache.admit(first)
@@ -1424,15 +1511,16 @@ class GraphedMultiStreamDecode(_Graphed):
 
     @torch.no_grad()
     def load(self, slots, cache: StaticCachePrealloc, row: int = 0, next_position: Optional[int] = None, sampling=None,
-             grammar=None, adapter=None) -> None:
+             grammar=None, adapter=None, logit_bias=None) -> None:
         """The demo's branch (demo:363-365) on the serving path: the state of row `row` of an external cache -- the B = 1
         StaticCachePrealloc of a running video stream -- goes into `slots` in one launch, and they become live.  The source is
         only read, so questions never pollute the video's history.  Each slot's three M-RoPE positions are set to
         `next_position` (default: the source's length); `sampling`: one dict of Sampler.set keyword arguments per slot, applied
         as in admit; `grammar`: every slot is put into that grammar's start state, for the draw of the extend that follows.
-        No token is pending afterwards: extend(slot, question) follows."""
+        `logit_bias`: every slot draws under that bias table.  No token is pending afterwards: extend(slot, question) follows."""
         slots = self._slots("load", slots)
         self._check_grammar("load", grammar)
+        self._check_bias("load", logit_bias)
         if sampling is not None:
             if self.sampler is None:
                 raise ValueError("load: sampling parameters need a GraphedMultiStreamDecode built with a sampler")
@@ -1447,6 +1535,8 @@ class GraphedMultiStreamDecode(_Graphed):
                 self.sampler.set(s, **sampling[i])
             if grammar is not None:
                 self.sampler.set_grammar(s, grammar)
+            if logit_bias is not None:
+                self.sampler.set_logit_bias(s, logit_bias)
             self.token[s].zero_()
             self.position_ids[:, s].fill_(next_position)
             self.set_adapter(s, adapter)                 # (the extend that follows runs under it)
@@ -1514,6 +1604,9 @@ class GraphedBeamDecode(GraphedMultiStreamDecode):
                  max_stop: int = 1, warmup: int = 2, sampler: Optional["Sampler"] = None):
         """sampler: the slots' sampler, where the caller wants to keep it (default: built here); it must be what this class
         builds -- n_slots rows, vocab_size, max_stop 0, history, logprobs = K, no score rings -- and hold no grammars."""
+        if sampler is not None and (sampler.penalties or sampler.biases is not None):
+            raise ValueError("GraphedBeamDecode: the sampler was built with penalties or bias_tables: they are not part of beam "
+                             "search (a beam's candidates come from the score-only launch, which takes no adjustment group)")
         if sampler is not None and sampler.grammars is not None:
             raise ValueError("GraphedBeamDecode: the sampler was built with grammar_states: constrained beam search is not "
                              "supported (a beam's candidates come from the score-only launch, which reads no grammar)")

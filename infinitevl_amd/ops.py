@@ -25,7 +25,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from ._lib import IVL_BF16, IVL_F32, IVL_FP8_E4M3, SampleArgs, SwaArgs
+from ._lib import IVL_BF16, IVL_F32, IVL_FP8_E4M3, SampleAdjArgs, SampleArgs, SwaArgs
 
 _DT_CODE = {torch.bfloat16: IVL_BF16, torch.float32: IVL_F32}
 _MMA_CODE = {None: IVL_BF16, "bf16": IVL_BF16, torch.bfloat16: IVL_BF16, "fp8": IVL_FP8_E4M3, "fp8_e4m3": IVL_FP8_E4M3,
@@ -1930,7 +1930,9 @@ def sample_tokens(logits: torch.Tensor, temperature: torch.Tensor, top_k: torch.
                   top_ids: Optional[torch.Tensor] = None, top_logprobs: Optional[torch.Tensor] = None,
                   cum_logprob: Optional[torch.Tensor] = None, lp_history: Optional[torch.Tensor] = None,
                   top_hist_ids: Optional[torch.Tensor] = None, top_hist_lp: Optional[torch.Tensor] = None,
-                  fsm_state: Optional[torch.Tensor] = None, fsm=None) -> torch.Tensor:
+                  fsm_state: Optional[torch.Tensor] = None, fsm=None, min_p: Optional[torch.Tensor] = None,
+                  freq_penalty: Optional[torch.Tensor] = None, pres_penalty: Optional[torch.Tensor] = None,
+                  count: Optional[torch.Tensor] = None, bias_idx: Optional[torch.Tensor] = None, bias=None) -> torch.Tensor:
     """One next token per row of lm_head logits [S,V] or [S,1,V] (bf16, last dim contiguous) in one launch: temperature,
     top-k, top-p and the draw, per row (ivl_sample_rows_fwd states the semantics; HF generate's warpers + multinomial,
     api/chat.py:160-162 of the reference).  temperature / top_k / top_p / seed / counter: [S] fp32 / int32 / fp32 / int64 /
@@ -1958,7 +1960,16 @@ def sample_tokens(logits: torch.Tensor, temperature: torch.Tensor, top_k: torch.
     kernel with the token it emits; `fsm`: an FsmTables, or any holder of mask int32 [n_states, mask_ld] (mask_ld * 32 >= V),
     desc int64 [n_states, 2], cls int32 and trans int32 (flat), with mask_ld and n_states.  A row in state q draws from the
     tokens of q's bitmap alone, and its scores are those of the distribution over them.  Needs `done` (3 = a dead end).  With
-    fsm_state given the launch is the constrained form; the two come together."""
+    fsm_state given the launch is the constrained form; the two come together.
+
+    The keyword-only adjustments (ADJUSTMENT of ivl_sample_rows_adj_fwd; logit_bias / frequency_penalty / presence_penalty
+    of the reference's api/protocol.py, HF's MinPLogitsWarper), each optional: min_p [S] fp32 (0 = off); freq_penalty and
+    pres_penalty [S] fp32 with count [S,C] int32, C >= V (how often each token was generated in the row; needs `seen`, and the
+    kernel adds the token it emits); bias_idx [S] int32 (a table of `bias`, or anything outside [0, n_bias) for none) with
+    `bias`: a BiasTables, or any holder of mask int32 [n_bias, mask_ld] (mask_ld * 32 >= V) and val fp32 [n_bias, ld]
+    (ld >= V) with n_bias, mask_ld and ld.  With none of them given the call is ivl_sample_rows_fwd as before; with any it is
+    ivl_sample_rows_adj_fwd (SAMPLE_ADJ_CALLS counts these), the adjusted twin of the controlled, scoring or constrained form,
+    and the scores are those of the adjusted distribution."""
     if logits.dim() == 3 and logits.shape[1] == 1:
         logits = logits[:, 0]
     if logits.dim() != 2 or logits.dtype != torch.bfloat16 or logits.shape[0] < 1 or logits.shape[1] < 1:
@@ -2040,6 +2051,38 @@ def sample_tokens(logits: torch.Tensor, temperature: torch.Tensor, top_k: torch.
                              f"[{n_states}, 2]; got {tuple(fsm.mask.shape)} and {tuple(fsm.desc.shape)}")
         if mask_ld * 32 < V:
             raise ValueError(f"sample_tokens: fsm.mask has {mask_ld} words per state for V = {V} (needs {(V + 31) // 32})")
+    adjusted = any(t is not None for t in (min_p, freq_penalty, pres_penalty, count, bias_idx, bias))
+    for name, t, dt in (("min_p", min_p, torch.float32), ("freq_penalty", freq_penalty, torch.float32),
+                        ("pres_penalty", pres_penalty, torch.float32), ("bias_idx", bias_idx, torch.int32)):
+        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != dt or tuple(t.shape) != (S,) or not t.is_contiguous()):
+            raise ValueError(f"sample_tokens: {name} must be a contiguous {dt} tensor of [{S}]; got "
+                             f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+    if count is not None:
+        if not isinstance(count, torch.Tensor):
+            raise ValueError(f"sample_tokens: count must be an int32 tensor of [{S},n]; got {type(count).__name__}")
+        if count.dtype != torch.int32 or count.dim() != 2 or count.shape[0] != S or count.stride(1) != 1 or (
+                S > 1 and count.stride(0) < count.shape[1]):
+            raise ValueError(f"sample_tokens: count must be an int32 tensor of [{S},n] with contiguous rows; got {count.dtype} "
+                             f"{tuple(count.shape)} strides {count.stride()}")
+        if count.shape[1] < V:
+            raise ValueError(f"sample_tokens: count has {count.shape[1]} entries per row for V = {V}")
+        if seen is None:
+            raise ValueError("sample_tokens: count needs the seen bitmap")
+    if (freq_penalty is not None or pres_penalty is not None) and count is None:
+        raise ValueError("sample_tokens: freq_penalty and pres_penalty need count")
+    if (bias_idx is None) != (bias is None):
+        raise ValueError("sample_tokens: bias_idx and bias come together")
+    if bias is not None:
+        n_bias, bias_mask_ld, bias_ld = int(bias.n_bias), int(bias.mask_ld), int(bias.ld)
+        for name, t, dt in (("mask", bias.mask, torch.int32), ("val", bias.val, torch.float32)):
+            if not isinstance(t, torch.Tensor) or t.dtype != dt or not t.is_contiguous():
+                raise ValueError(f"sample_tokens: bias.{name} must be a contiguous {dt} tensor")
+        if n_bias < 1 or tuple(bias.mask.shape) != (n_bias, bias_mask_ld) or tuple(bias.val.shape) != (n_bias, bias_ld):
+            raise ValueError(f"sample_tokens: bias.mask must be [n_bias, mask_ld] = [{n_bias}, {bias_mask_ld}] and bias.val "
+                             f"[{n_bias}, {bias_ld}]; got {tuple(bias.mask.shape)} and {tuple(bias.val.shape)}")
+        if bias_mask_ld * 32 < V or bias_ld < V:
+            raise ValueError(f"sample_tokens: bias.mask has {bias_mask_ld} words and bias.val {bias_ld} entries per table for "
+                             f"V = {V} (needs {(V + 31) // 32} and {V})")
     if out is None:
         out = torch.empty(S, dtype=torch.int64, device=logits.device)
     if out.dtype != torch.int64 or tuple(out.shape) not in ((S,), (S, 1)):
@@ -2054,8 +2097,94 @@ def sample_tokens(logits: torch.Tensor, temperature: torch.Tensor, top_k: torch.
     a = _sample_args(logits, tensors, token_stride=out.stride(0) if S > 1 else 1, n_stop=n_stop, hist_ld=hist_ld, n_top=n_top)
     if fsm is not None:
         a.mask_ld, a.n_states = mask_ld, n_states
-    _lib.check(_lib.load().ivl_sample_rows_fwd(ctypes.byref(a), _stream(logits)))
+    if not adjusted:
+        _lib.check(_lib.load().ivl_sample_rows_fwd(ctypes.byref(a), _stream(logits)))
+        return out
+    adj = dict(min_p=min_p, freq_penalty=freq_penalty, pres_penalty=pres_penalty, count=count, bias_idx=bias_idx)
+    if bias is not None:
+        adj.update(bias_mask=bias.mask, bias_val=bias.val)
+    _need_gpu(logits, *adj.values())
+    j = SampleAdjArgs()
+    for name, t in adj.items():
+        if t is not None:
+            setattr(j, name, t.data_ptr())
+    if count is not None:
+        j.count_ld = count.stride(0) if S > 1 else count.shape[1]
+    if bias is not None:
+        j.bias_mask_ld, j.bias_ld, j.n_bias = bias_mask_ld, bias_ld, n_bias
+    SAMPLE_ADJ_CALLS["adj"] += 1
+    _lib.check(_lib.load().ivl_sample_rows_adj_fwd(ctypes.byref(a), ctypes.byref(j), _stream(logits)))
     return out
+
+
+SAMPLE_ADJ_CALLS = {"adj": 0}       # calls of sample_tokens that went to ivl_sample_rows_adj_fwd (tests and tools read it)
+
+
+class BiasHandle(NamedTuple):
+    """A logit-bias table loaded into a BiasTables: `index` is what a row's bias_idx holds; `ids` are the biased tokens;
+    `serial` counts the arena's loads, so the handle of an unloaded table never equals that of a later load into its place."""
+    index: int
+    ids: Tuple[int, ...]
+    serial: int
+
+
+class BiasTables:
+    """The device tables of ivl_sample_adj_args' logit bias as ONE arena, allocated once: `n_tables` tables over vocab_size
+    tokens, each a bitmap row of `mask` int32 [n, ceil(V/32)] (the layout of `seen`) and a row of `val` fp32 [n, V].  load()
+    writes a {token id: bias} dict into a free table; unload() clears its bitmap, so a row that still points at it is not
+    biased.  The tensors never move: a captured step obeys a table that was loaded after its capture.  mask / val with n_bias,
+    mask_ld and ld are what ops.sample_tokens(bias=) takes."""
+
+    def __init__(self, device, vocab_size: int, n_tables: int):
+        for name, v in (("vocab_size", vocab_size), ("n_tables", n_tables)):
+            if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+                raise ValueError(f"BiasTables: {name} must be an int >= 1; got {v!r}")
+        self.vocab_size, self.n_bias = vocab_size, n_tables
+        self.mask_ld, self.ld = (vocab_size + 31) // 32, vocab_size
+        self.mask = torch.zeros(n_tables, self.mask_ld, dtype=torch.int32, device=device)
+        self.val = torch.zeros(n_tables, vocab_size, dtype=torch.float32, device=device)
+        self._slots: List[Optional[BiasHandle]] = [None] * n_tables
+        self._loads = 0
+
+    def handles(self) -> List["BiasHandle"]:
+        return [h for h in self._slots if h is not None]
+
+    def load(self, bias: dict) -> "BiasHandle":
+        """Writes {token id: bias} (ids in [0, vocab_size), values floats; -inf bans a token, +inf forces it, NaN is refused)
+        into a free table and returns its handle.  ValueError: a bad entry, or no table left."""
+        if not isinstance(bias, dict):
+            raise ValueError(f"BiasTables.load: a dict of token id -> bias is expected; got {type(bias).__name__}")
+        ids, vals = [], []
+        for k, v in bias.items():
+            if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 0 <= int(k) < self.vocab_size:
+                raise ValueError(f"BiasTables.load: token id {k!r} is not an int in [0, {self.vocab_size})")
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or v != v:
+                raise ValueError(f"BiasTables.load: the bias of token {k} must be a number that is not NaN; got {v!r}")
+            ids.append(int(k))
+            vals.append(float(v))
+        if None not in self._slots:
+            raise ValueError(f"BiasTables.load: all {self.n_bias} tables are taken")
+        slot = self._slots.index(None)
+        dev = self.mask.device
+        idx = np.asarray(ids, dtype=np.int64)
+        words = np.zeros(self.mask_ld, dtype=np.uint32)
+        np.bitwise_or.at(words, idx >> 5, np.uint32(1) << (idx & 31).astype(np.uint32))
+        row = np.zeros(self.vocab_size, dtype=np.float32)
+        with np.errstate(over="ignore"):
+            row[idx] = np.asarray(vals, dtype=np.float64).astype(np.float32)
+        self.val[slot] = torch.from_numpy(row).to(dev)
+        self.mask[slot] = torch.from_numpy(words.view(np.int32)).to(dev)
+        self._loads += 1
+        self._slots[slot] = h = BiasHandle(slot, tuple(sorted(ids)), self._loads)
+        return h
+
+    def unload(self, handle: "BiasHandle") -> None:
+        """Frees the table; it biases nothing from now on."""
+        if not isinstance(handle, BiasHandle) or handle.index >= len(self._slots) or self._slots[handle.index] != handle:
+            raise ValueError(f"BiasTables.unload: {handle!r} is not loaded here")
+        self.mask[handle.index].zero_()
+        self.val[handle.index].zero_()
+        self._slots[handle.index] = None
 
 
 class FsmHandle(NamedTuple):

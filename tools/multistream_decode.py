@@ -112,6 +112,17 @@ mxfp4 copies.  Legs interleaved per round in one process, median of --rounds rou
 projections of a decode token alone at M = 8 and 16: the base call, fused, composed -- us per call.  Nothing is asserted.
 
     python tools/multistream_decode.py --wide-lora --slots 8,16 [--out profiles/wide_lora_decode.json]
+
+--adjust: the cost of the adjustment group (Sampler(penalties=True, bias_tables=), ivl_sample_rows_adj_fwd: DESIGN 4.19) in the
+captured 4-slot step.  A: the sampled, controlled step of --generation (0.7 / 50 / 0.9, repetition penalty 1.3, two stop ids, a
+budget, a 256-entry history, the bitmap about 5 % full); B: the same with min_p 0.05, frequency_penalty 0.5 and
+presence_penalty 0.5 on every slot and every slot under a 300-entry logit-bias table.  Both legs generate 64 tokens per row
+first; that state (bitmap, counts, counters) is saved and put back in front of every timed run, outside the timed region, so
+each run starts from 64 generated tokens per row.  Timed A B A B, median of --rounds rounds of --steps replays.  Then the
+operator alone on 4 rows of the model's vocabulary, with the group, with an all-off group (the adjusted kernel, nothing on) and
+without.  No bar is asserted: B - A is reported beside the 2 % of A that DESIGN 4.8 grants the sampling launch as a whole.
+
+    python tools/multistream_decode.py --adjust [--out profiles/adjust_decode.json]
 """
 import argparse
 import json
@@ -145,6 +156,8 @@ def main():
                     help="with --wide: use_wide_decode(max_rows=); above 16 the legs are those of the 64-row kernel (see above)")
     ap.add_argument("--wide-lora", dest="wide_lora", action="store_true",
                     help="time per-slot adapters in the 8- and 16-slot step on the 16-row kernel, fused against composed (see above)")
+    ap.add_argument("--adjust", action="store_true",
+                    help="time the 4-slot controlled step with and without penalties, min-p and a logit-bias table (see above)")
     args = ap.parse_args()
     import torch
     from infinitevl_amd.cache import MultiStreamCache
@@ -171,6 +184,8 @@ def main():
                 _, lg = model(inputs_embeds=x[:, a:b], position_ids=pid, past_key_values=cache)
         return lg
 
+    if args.adjust:
+        return adjust_legs(args, torch, model, cfg, prompts, dev)
     if args.sampling:
         return sampling_legs(args, torch, model, cfg, prompts, dev)
     if args.generation:
@@ -409,6 +424,106 @@ def generation_legs(args, torch, model, cfg, prompts, dev):
             op[f"S{S}_{pname}_controls_penalty_off_us"] = round(1000 * timed(lambda: r1.sample(lg, tok), 200), 2)
             op[f"S{S}_{pname}_controls_us"] = round(1000 * timed(lambda: ctl.sample(lg, tok), 200), 2)
             op[f"S{S}_{pname}_controls_rows_still_live"] = bool((ctl.poll()[0] == 0).all() and (r1.poll()[0] == 0).all())
+    res["operator_V%d" % V] = op
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+ADJUST = {"min_p": 0.05, "frequency_penalty": 0.5, "presence_penalty": 0.5}
+BIAS_ENTRIES = 300
+GENERATED = 64
+
+
+def adjust_legs(args, torch, model, cfg, prompts, dev):
+    from infinitevl_amd.cache import MultiStreamCache
+    from infinitevl_amd.harness import GraphedMultiStreamDecode, Sampler
+    stream = torch.cuda.current_stream()
+    V, n = cfg.vocab_size, 4
+
+    def timed(fn, k, before=None):
+        for _ in range(4):
+            fn()
+        if before is not None:
+            before()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        for _ in range(k):
+            fn()
+        e1.record(stream)
+        e1.synchronize()
+        return e0.elapsed_time(e1) / k
+
+    def seen_ids(s):
+        g = torch.Generator().manual_seed(100 + s)
+        return torch.randperm(V, generator=g)[:int(SEEN_FRACTION * V)].to(dev)
+
+    def bias_table(seed):
+        g = torch.Generator().manual_seed(seed)
+        ids = torch.randperm(V, generator=g)[:BIAS_ENTRIES].tolist()
+        vals = (torch.randn(BIAS_ENTRIES, generator=g) * 2.0).tolist()
+        return dict(zip(ids, vals))
+
+    def controls(s, **more):
+        return dict(SAMPLED, seed=s + 1, stop_token_ids=[V - 1 - s, V - 9 - s], **CONTROLS, **more)
+
+    res = {"tool": "multistream_decode --adjust", "layers": cfg.num_hidden_layers, "window": 4096, "slots": n, "steps": args.steps,
+           "rounds": args.rounds, "sampled": SAMPLED, "controls": dict(CONTROLS, stop_ids=2, history=HISTORY, seen_fraction=SEEN_FRACTION),
+           "group": dict(ADJUST, bias_entries=BIAS_ENTRIES, generated_tokens_per_row=GENERATED)}
+    legs, samplers, restore = {}, {}, {}
+    for name in ("controlled", "adjusted"):
+        cache = MultiStreamCache(config=cfg, n_slots=n, device=dev, dtype=torch.bfloat16)
+        on = name == "adjusted"
+        smp = Sampler(n, dev, vocab_size=V, history=HISTORY, penalties=on, bias_tables=1 if on else 0)
+        dec = GraphedMultiStreamDecode(model, cache, sampler=smp)
+        table = smp.load_logit_bias(bias_table(7)) if on else None
+        for s in range(n):
+            dec.admit(s, prompts[s], sampling=controls(s, **(ADJUST if on else {})), prompt_ids=seen_ids(s),
+                      **({"logit_bias": table} if on else {}))
+        dec.capture()
+        for _ in range(GENERATED - 1):                          # (admit drew the first token)
+            dec.step()
+        state = smp.state()
+        legs[name], samplers[name], restore[name] = dec.step, smp, (lambda smp=smp, state=state: smp.load_state(state))
+    times = {k: [] for k in legs}
+    for _ in range(args.rounds):                                # A B A B
+        for _ in range(2):
+            for name in ("controlled", "adjusted"):
+                times[name].append(timed(legs[name], args.steps, restore[name]))
+    a, b = statistics.median(times["controlled"]), statistics.median(times["adjusted"])
+    for name, t in (("controlled", a), ("adjusted", b)):
+        done, n_new = samplers[name].poll()
+        res[name] = {"ms_per_step": round(t, 4), "spread_ms": [round(min(times[name]), 4), round(max(times[name]), 4)],
+                     "rows_still_live": bool((done == 0).all()), "tokens_per_row_at_the_end": n_new.tolist()}
+    res["adjusted_minus_controlled_us"] = round(1000 * (b - a), 1)
+    res["allowance_us"] = round(1000 * 0.02 * a, 1)
+    res["within_allowance"] = bool(b - a <= 0.02 * a)
+    # the operator alone, back to back on one stream (launch-bound figures include the launch gap)
+    gen = torch.Generator(device=dev).manual_seed(1)
+    lg = (torch.randn(n, V, generator=gen, device=dev) * 3.0).to(torch.bfloat16)
+    tok = torch.zeros(n, 1, dtype=torch.int64, device=dev)
+    op = {}
+    for pname, kw in (("kernel_greedy", {}), ("sampled", SAMPLED)):
+        ctl = Sampler(n, dev, vocab_size=V, history=HISTORY)
+        off = Sampler(n, dev, vocab_size=V, history=HISTORY, penalties=True, bias_tables=1)
+        adj = Sampler(n, dev, vocab_size=V, history=HISTORY, penalties=True, bias_tables=1)
+        table = adj.load_logit_bias(bias_table(7))
+        states = {}
+        for tag, smp in (("controls", ctl), ("all_off_group", off), ("group", adj)):
+            for s in range(n):
+                smp.set(s, seed=s, stop_token_ids=[V - 1 - s, V - 9 - s], **CONTROLS, **kw, **(ADJUST if smp is adj else {}))
+                smp.mark(s, seen_ids(s))
+                if smp is adj:
+                    smp.set_logit_bias(s, table)
+            for _ in range(GENERATED):
+                smp.sample(lg, tok)
+            states[tag] = smp.state()
+            op[f"S{n}_{pname}_{tag}_us"] = round(1000 * timed(lambda smp=smp: smp.sample(lg, tok), 200,
+                                                              lambda smp=smp, tag=tag: smp.load_state(states[tag])), 2)
+            op[f"S{n}_{pname}_{tag}_rows_still_live"] = bool((smp.poll()[0] == 0).all())
     res["operator_V%d" % V] = op
     line = json.dumps(res)
     print(line)
