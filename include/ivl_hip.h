@@ -264,6 +264,31 @@ IVL_API int ivl_swa_fwd(const ivl_swa_args* args, void* stream);
  * B = 1 ivl_swa_fwd of that row.  Other shapes: IVL_ERR_UNSUPPORTED; NULL pos_rows: IVL_ERR_INVALID_ARG. */
 IVL_API int ivl_swa_decode_rows_fwd(const ivl_swa_args* args, const int64_t* pos_rows, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Per-row HOLD of a multi-stream step.  `frozen`: device int32 [B], read when the launch RUNS (at replay); row b is frozen when
+ * frozen[b] != 0.  frozen == NULL means "no row is frozen": the call IS its twin without the argument, same kernels, same bits.
+ * The three entry points that take it -- ivl_gdn_decode_step_rows_fwd, ivl_swa_decode_rows_hold_fwd, ivl_rows_advance_fwd -- keep:
+ *   HOLD-1 a frozen row is untouched.  No byte of what the row owns is written: its GDN recurrent state, its three conv states, its
+ *          K / V ring row, pos_rows[b], its three M-RoPE positions.  Nothing of it needs to be read (it may hold NaN or inf).  The
+ *          outputs of that row (y, o, and the logits computed from them) are unspecified.
+ *   HOLD-2 running rows do not notice.  Every output and every state byte of a running row is bit-equal to the same call with
+ *          frozen == NULL, and so to the call in which the frozen rows hold anything at all (a row depends on its own row only).
+ *   HOLD-3 graph.  The mask is read on the device; changing it between replays of a captured call needs no recapture, and the same
+ *          bits result eager or replayed.
+ * The sampling launch's `done` (int32 [S]) has exactly this layout: a decoder may pass it as the mask, so that a row that ends (codes
+ * 1, 2, 3) freezes on the next replay with no host involved; code 4 is "held by the host" (to the sampling kernels: a finished row).
+ * ------------------------------------------------------------------------------------------- */
+/* ivl_swa_decode_rows_fwd with the hold mask: same scope, argument rules, split count, grids and merge.  The attention workgroups
+ * of a frozen row leave at once, its combine blocks skip the merge and the o store, and with append_new its slots
+ * (pos_rows[b] + t) % C are not written. */
+IVL_API int ivl_swa_decode_rows_hold_fwd(const ivl_swa_args* args, const int64_t* pos_rows, const int32_t* frozen, void* stream);
+
+/* The counters of a multi-stream step, one launch: pos_rows[s] += delta (int64 [S]) and position_ids[a * pid_stride + s] += delta
+ * for a = 0, 1, 2 (int64 [3, S], row stride pid_stride >= S) where row s runs.  Either pointer may be NULL (that counter is left
+ * alone).  S < 1 or pid_stride < S: IVL_ERR_INVALID_ARG. */
+IVL_API int ivl_rows_advance_fwd(int64_t* pos_rows, int64_t* position_ids, int64_t pid_stride, const int32_t* frozen, int S,
+                                 int64_t delta, void* stream);
+
 /* Append the T new tokens to the ring (slot (pos+t) % C) -- after ivl_swa_fwd of the same call.
  * Replaces the tail copy-back of std:146-172.  k_new,v_new bf16 with the strides given.  With rope_cos / rope_sin
  * (same meaning as in ivl_swa_args) the keys are rotated on the way into the ring. */
@@ -353,6 +378,14 @@ IVL_API int ivl_gdn_decode_step_fwd(const void* proj, int64_t ld, int col_q, int
                             void* conv_state_q, void* conv_state_k, void* conv_state_v, const float* A_log,
                             const float* dt_bias, const void* norm_weight, float eps, void* state, int state_dtype,
                             void* y, int B, int H, int K, int V, float scale, void* stream);
+
+/* ivl_gdn_decode_step_fwd with the hold mask (HOLD-1..3 above): the workgroups of a frozen row leave before their first state load;
+ * the row's recurrent state and conv states are neither read nor written and its y is not written.  Same argument rules. */
+IVL_API int ivl_gdn_decode_step_rows_fwd(const void* proj, int64_t ld, int col_q, int col_k, int col_v, int col_g, int col_a,
+                            int col_b, const void* conv_wq, const void* conv_wk, const void* conv_wv,
+                            void* conv_state_q, void* conv_state_k, void* conv_state_v, const float* A_log,
+                            const float* dt_bias, const void* norm_weight, float eps, void* state, int state_dtype,
+                            void* y, int B, int H, int K, int V, float scale, const int32_t* frozen, void* stream);
 
 /* The same step on 4 x as many workgroups (round 5): a workgroup = (sequence, head, quarter of the 256 value columns); the delta
  * rule is column-local, so the quarters exchange nothing.  What spans a head moves into the NEXT launch
@@ -698,7 +731,8 @@ IVL_API int ivl_linear_logprob_m256_fwd(const void* x, const void* w, const void
  *       else done[s] = 2 if budget[s] >= 0 and n_new[s] >= budget[s] (after the increment).  A stop id wins over the budget.
  *   D bounds.  Bits at or above V in a row's last word, the words between ceil(V/32) and seen_ld and other rows are never
  *     modified and never influence a result; nothing outside a row's seen_ld words is read.
- * done codes: 0 running, 1 ended on a stop id, 2 ended on its budget, 3 a dead end of the constraint; the host clears done[s] to
+ * done codes: 0 running, 1 ended on a stop id, 2 ended on its budget, 3 a dead end of the constraint, 4 held by the host (never
+ * written by a kernel; a decoder with holds sets and clears it between replays); the host clears done[s] to
  * restart a row.
  *
  * SCORES: the scores of what the call generates, inside the same one launch: the log-probability of the token, the

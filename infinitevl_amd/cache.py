@@ -585,6 +585,8 @@ class MultiStreamSlidingLayer(StaticSlidingWindowLayerPrealloc):
         super().__init__(**kw)
         self._pos_rows = torch.zeros(self.batch_size, dtype=torch.int64, device=self.device)
         self._lengths = [0] * self.batch_size
+        self._frozen = None                  # MultiStreamCache.enable_holds: the hold mask, device int32 [n_slots]
+        self._hold_advance = True            # False: the owner of the cache advances _pos_rows itself (one ops.rows_advance)
 
     def attend(self, q, k_new, v_new, scaling, window, mma_dtype=None, rope=None):
         B, T, Hkv, D = k_new.shape
@@ -595,6 +597,13 @@ class MultiStreamSlidingLayer(StaticSlidingWindowLayerPrealloc):
             raise ValueError("MultiStreamCache: the fp8 decode step is not supported (bf16 only)")
         if B != self.batch_size:
             raise ValueError(f"MultiStreamCache has {self.batch_size} slots, but got B={B}")
+        if self._frozen is not None:         # hold mode: a frozen row keeps its ring row and its position
+            o = ops.swa_forward(q, k_new, v_new, window=window, scaling=scaling, k_cache=self._buf_keys,
+                                v_cache=self._buf_values, pos_rows=self._pos_rows, rope=rope, append=True, frozen=self._frozen)
+            if self._advances_counter and self._hold_advance:
+                ops.rows_advance(self._pos_rows, None, self._frozen, 1)
+            self.advance(1)
+            return o
         o = ops.swa_forward(q, k_new, v_new, window=window, scaling=scaling, k_cache=self._buf_keys,
                             v_cache=self._buf_values, pos_rows=self._pos_rows, rope=rope, append=True)
         if self._advances_counter:
@@ -667,15 +676,44 @@ class MultiStreamCache(StaticCachePrealloc):
     def pos_rows(self) -> torch.Tensor:
         return self._sliding()[0]._pos_rows
 
+    # ---- per-slot hold (include/ivl_hip.h, HOLD-1..3) ---------------------------------------------------------------------
+    hold_mask: Optional[torch.Tensor] = None
+
+    def enable_holds(self, frozen: torch.Tensor, advance: bool = True) -> None:
+        """Decode steps on this cache read `frozen` (device int32 [n_slots]) at replay: a slot with frozen[s] != 0 sits the step
+        out -- its GDN states, ring row and position stay as they are, and its outputs are unspecified.  The mask is kept for the
+        life of the cache (a captured graph holds its address): the same tensor object may be given again, another one is
+        refused.  advance=False: the caller advances pos_rows itself (ops.rows_advance, with its other per-slot counters).
+        From here on the host no longer knows how far a slot went: sync_lengths() reads the positions back."""
+        if not torch.is_tensor(frozen) or frozen.dtype != torch.int32 or tuple(frozen.shape) != (self.n_slots,) or \
+                not frozen.is_contiguous() or frozen.device != self.pos_rows.device:
+            raise ValueError(f"MultiStreamCache.enable_holds: frozen must be a contiguous int32 [{self.n_slots}] tensor on "
+                             f"{self.pos_rows.device}")
+        if self.hold_mask is not None and self.hold_mask is not frozen:
+            raise ValueError("MultiStreamCache.enable_holds: the cache already keeps another mask (a graph holds its address)")
+        self.hold_mask = frozen
+        for layer in self._sliding():
+            layer._frozen, layer._hold_advance = frozen, bool(advance)
+
+    def sync_lengths(self):
+        """Rewrites the host mirror slot_lengths from pos_rows (one read-back; it waits for the steps queued so far) and returns
+        it.  In hold mode this is the only way the host learns a slot's length; without a mask the mirror is already right."""
+        if self.hold_mask is not None:
+            self.slot_lengths[:] = [int(n) for n in self.pos_rows.cpu().tolist()]
+        return self.slot_lengths
+
     @property
     def slot_lengths(self):
+        """The host mirror of pos_rows.  With a hold mask (enable_holds) it is stale until sync_lengths() rewrites it."""
         return self._sliding()[0]._lengths
 
     def get_seq_length(self, layer_idx: int = 0, *a, slot: Optional[int] = None, **k) -> int:
+        """The length of slot `slot`.  With a hold mask it is read back from the device (sync_lengths): the host mirror
+        `slot_lengths` counts every replay for every slot and is stale between two syncs."""
         if slot is None:
             raise ValueError("MultiStreamCache: the slots have different lengths; pass position_ids to the forward "
                              "(or get_seq_length(slot=...))")
-        return int(self.slot_lengths[slot])
+        return int(self.sync_lengths()[slot])
 
     def _check_slot(self, slot: int) -> int:
         slot = int(slot)
@@ -691,6 +729,7 @@ class MultiStreamCache(StaticCachePrealloc):
             if isinstance(layer, StaticLinearLayerPrealloc):
                 for t in layer.carried_tensors():
                     t[slot].zero_()
+        self.sync_lengths()
         self.pos_rows[slot:slot + 1].zero_()
         self.slot_lengths[slot] = 0
 
@@ -773,6 +812,7 @@ class MultiStreamCache(StaticCachePrealloc):
         """Slots `dsts` become copies of slot `src`: every carried tensor of every layer and the ring position, in ONE launch
         (ops.RowCopyPlan).  In-place writes only: valid between replays of a captured graph."""
         src, dsts = self._check_slot(src), self._check_dsts(dsts)
+        self.sync_lengths()
         self._plan("fork").run(src, dsts)
         for d in dsts:
             self.slot_lengths[d] = self.slot_lengths[src]
@@ -786,6 +826,9 @@ class MultiStreamCache(StaticCachePrealloc):
         if isinstance(row, bool) or not isinstance(row, int) or not 0 <= row < n_rows:
             raise ValueError(f"MultiStreamCache.load: row must be an int in [0, {n_rows}); got {row!r}")
         cache.ensure_started()
+        self.sync_lengths()
+        if isinstance(cache, MultiStreamCache):
+            cache.sync_lengths()
         self._plan("load", cache).run(row, dsts)
         n = self._other_length(cache, row)
         for d in dsts:
@@ -803,7 +846,7 @@ class MultiStreamCache(StaticCachePrealloc):
         if isinstance(row, bool) or not isinstance(row, int) or not 0 <= row < n_rows:
             raise ValueError(f"MultiStreamCache.store: row must be an int in [0, {n_rows}); got {row!r}")
         self._plan("store", cache).run(slot, [row])
-        n = int(self.slot_lengths[slot])
+        n = int(self.sync_lengths()[slot])
         if isinstance(cache, MultiStreamCache):
             cache.slot_lengths[row] = n
             return
@@ -817,7 +860,7 @@ class MultiStreamCache(StaticCachePrealloc):
         """A B = 1 StaticCachePrealloc whose tensors alias row `slot` (ring, conv and recurrent states, position): a prompt
         runs through the unchanged stack forward on it (chunked GDN, 128 / 256-row attention, in-place state)."""
         slot = self._check_slot(slot)
-        n = self.slot_lengths[slot]
+        n = self.sync_lengths()[slot]
         layers = []
         for layer in self.layers:
             if isinstance(layer, MultiStreamSlidingLayer):
@@ -841,5 +884,6 @@ class MultiStreamCache(StaticCachePrealloc):
             layers.append(v)
         view = _retype(self, StaticCachePrealloc)      # the aggregate's own bookkeeping, with per-slot layers
         view.layers = layers
+        view.hold_mask = None                          # (a B = 1 prefill on the view is never masked)
         view._share_position_counter()
         return view

@@ -227,6 +227,19 @@ __global__ void counter_add_kernel(long long* c, long long delta) {
   if (threadIdx.x == 0 && blockIdx.x == 0) *c += delta;
 }
 
+// per-row counters of a multi-stream step (ivl_rows_advance_fwd): thread s owns row s; a frozen row writes nothing
+__global__ __launch_bounds__(256) void rows_advance_kernel(long long* __restrict__ pos_rows, long long* __restrict__ pid, long long pid_stride,
+                                                          const int32_t* __restrict__ frozen, int S, long long delta) {
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= S) return;
+  if (frozen != nullptr && frozen[s] != 0) return;
+  if (pos_rows != nullptr) pos_rows[s] += delta;
+  if (pid != nullptr) {
+#pragma unroll
+    for (int a = 0; a < 3; ++a) pid[a * pid_stride + s] += delta;
+  }
+}
+
 }  // namespace ivl
 
 using namespace ivl;
@@ -343,4 +356,15 @@ extern "C" int ivl_counter_add(int64_t* counter, int64_t delta, void* stream) {
   IVL_REQUIRE(counter, IVL_ERR_INVALID_ARG, "ivl_counter_add: NULL counter");
   hipLaunchKernelGGL(counter_add_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (long long*)counter, (long long)delta);
   return check_launch("ivl_counter_add");
+}
+
+extern "C" int ivl_rows_advance_fwd(int64_t* pos_rows, int64_t* position_ids, int64_t pid_stride, const int32_t* frozen, int S, int64_t delta,
+                                    void* stream) {
+  IVL_REQUIRE(S >= 1, IVL_ERR_INVALID_ARG, "ivl_rows_advance_fwd: S=%d", S);
+  IVL_REQUIRE(position_ids == nullptr || pid_stride >= S, IVL_ERR_INVALID_ARG, "ivl_rows_advance_fwd: pid_stride=%lld < S=%d",
+              (long long)pid_stride, S);
+  if (pos_rows == nullptr && position_ids == nullptr) return IVL_OK;      // nothing to advance
+  hipLaunchKernelGGL(rows_advance_kernel, dim3((S + 255) / 256), dim3(256), 0, (hipStream_t)stream, (long long*)pos_rows,
+                     (long long*)position_ids, (long long)pid_stride, frozen, S, (long long)delta);
+  return check_launch("ivl_rows_advance_fwd");
 }

@@ -53,6 +53,16 @@ __global__ __launch_bounds__(256, 2) void swa_rows_decode_kernel(const long long
 #undef SWA_ROWS
 }
 
+// the same with a per-row hold mask (frozen: int32[B], ivl_swa_decode_rows_hold_fwd): `frozen` follows the struct, the running rows'
+// workgroups execute the body above
+__global__ __launch_bounds__(256, 2) void swa_rows_hold_decode_kernel(const long long* pos_dev, SwaParams p, const int32_t* frozen) {
+  constexpr bool PACK = true;
+  constexpr int QG = 1;
+#define SWA_ROWS 2
+#include "swa_fwd_body.inc"
+#undef SWA_ROWS
+}
+
 // ------------------------------------------------------------------------------------------------------------------
 // Prefill kernel (T > 64 query rows per head): 8 compute wavefronts = 4 row groups x 2 key halves on v_mfma_f32_32x32x16_bf16,
 // plus 4 loader wavefronts.
@@ -747,8 +757,9 @@ struct AppendArgs {
 };
 // token t of the call -> slot (pos + t) % C ; only the last min(T, C) tokens are written
 // ROWS (ivl_swa_decode_rows_fwd): a.pos_dev is an int64[B], batch row b appends at its own pos_dev[b]
-template <bool ROWS = false>
-__device__ __forceinline__ void ring_append(const AppendArgs& a, long long block, long long nblocks) {
+// ROWS == 2 (ivl_swa_decode_rows_hold_fwd): the same, and the slots of a row with frozen[b] != 0 are not written
+template <int ROWS = 0>
+__device__ __forceinline__ void ring_append(const AppendArgs& a, long long block, long long nblocks, const int32_t* frozen = nullptr) {
   const long long pos = ROWS ? 0 : (a.pos_dev ? *a.pos_dev : a.pos);
   const int t_first = a.T > a.C ? a.T - a.C : 0;
   const int nt = a.T - t_first;
@@ -760,6 +771,9 @@ __device__ __forceinline__ void ring_append(const AppendArgs& a, long long block
     const long long bt = divmod_idx(idx >> 4, a.Hkv, hk);          // SWA_D / 8 = 16 pieces per row
     const int b = (int)divmod_idx(bt, nt, tt);
     tt += t_first;
+    if constexpr (ROWS == 2) {
+      if (frozen[b] != 0) continue;
+    }
     const int pos_slot = ROWS ? mod_pos(a.pos_dev[b], a.C) : pos_slot0;
     const int slot = (int)(((unsigned int)pos_slot + (unsigned int)tt) % (unsigned int)a.C);      // (pos + tt) % C; pos_slot, tt < 2^31
     const long long src = (long long)b * a.kn_sb + (long long)tt * a.kn_st + (long long)hk * a.kn_sh + ch * 8;
@@ -816,6 +830,28 @@ __global__ __launch_bounds__(256) void swa_rows_combine_wide_kernel(const float*
                                                                    bf16_t* __restrict__ o, int B, int rows_per_b, int nsplit, AppendArgs ap) {
 #define SWA_WIDE 1
 #define SWA_ROWS 1
+#include "swa_combine_body.inc"
+#undef SWA_ROWS
+#undef SWA_WIDE
+}
+
+// the hold forms of the two pos_rows combine kernels (frozen: int32[B])
+template <int NS>
+__global__ __launch_bounds__(256) void swa_rows_hold_combine_kernel(const float* __restrict__ part_o, const float* __restrict__ part_ml,
+                                                                   bf16_t* __restrict__ o, int B, int rows_per_b, int nsplit, AppendArgs ap,
+                                                                   const int32_t* __restrict__ frozen) {
+  constexpr bool BF16P = false;
+#define SWA_WIDE 0
+#define SWA_ROWS 2
+#include "swa_combine_body.inc"
+#undef SWA_ROWS
+#undef SWA_WIDE
+}
+__global__ __launch_bounds__(256) void swa_rows_hold_combine_wide_kernel(const float* __restrict__ part_o, const float* __restrict__ part_ml,
+                                                                        bf16_t* __restrict__ o, int B, int rows_per_b, int nsplit, AppendArgs ap,
+                                                                        const int32_t* __restrict__ frozen) {
+#define SWA_WIDE 1
+#define SWA_ROWS 2
 #include "swa_combine_body.inc"
 #undef SWA_ROWS
 #undef SWA_WIDE
@@ -927,7 +963,13 @@ static swa_combine_fn swa_combine_for(int nsplit, bool rows, bool bf16p) {
   if (bf16p) return nsplit <= 4 ? swa_combine_kernel<4, true> : nsplit <= 8 ? swa_combine_kernel<8, true> : swa_combine_kernel<16, true>;
   return nsplit <= 4 ? swa_combine_kernel<4, false> : nsplit <= 8 ? swa_combine_kernel<8, false> : swa_combine_kernel<16, false>;
 }
-static int swa_combine_append(const SwaParams& p, bool rows, bool bf16p, bool append, hipStream_t st) {
+typedef void (*swa_hold_combine_fn)(const float*, const float*, bf16_t*, int, int, int, AppendArgs, const int32_t*);
+static swa_hold_combine_fn swa_hold_combine_for(int nsplit) {
+  if (nsplit > 16) return swa_rows_hold_combine_wide_kernel;
+  return nsplit <= 4 ? swa_rows_hold_combine_kernel<4> : nsplit <= 8 ? swa_rows_hold_combine_kernel<8> : swa_rows_hold_combine_kernel<16>;
+}
+// `frozen` != nullptr (with rows): the hold twins of the pos_rows combine kernels on the same grid
+static int swa_combine_append(const SwaParams& p, bool rows, bool bf16p, bool append, hipStream_t st, const int32_t* frozen = nullptr) {
   AppendArgs ap;
   ap.first_block = -1;
   const int append_blocks = !append ? 0 : swa_append_args(ap, p.k_new, p.kn_sb, p.kn_st, p.kn_sh, p.v_new, p.vn_sb, p.vn_st, p.vn_sh, p.k_cache,
@@ -937,6 +979,11 @@ static int swa_combine_append(const SwaParams& p, bool rows, bool bf16p, bool ap
     const int blocks = p.nsplit > 16 ? (int)(nrows > 4096 ? 4096 : nrows)        // wide: one workgroup per row
                                      : blocks256(nrows * 64, 4096);              // one wavefront per row
     if (append_blocks > 0) ap.first_block = blocks;
+    if (frozen != nullptr) {
+      hipLaunchKernelGGL(swa_hold_combine_for(p.nsplit), dim3(blocks + append_blocks), dim3(256), 0, st, p.part_o, p.part_ml, p.o, p.B,
+                         p.T * p.Hq, p.nsplit, ap, frozen);
+      return check_launch("ivl_swa_decode_rows_hold_fwd(combine)");
+    }
     hipLaunchKernelGGL(swa_combine_for(p.nsplit, rows, bf16p), dim3(blocks + append_blocks), dim3(256), 0, st, p.part_o, p.part_ml, p.o,
                        p.B, p.T * p.Hq, p.nsplit, ap);
     return check_launch(rows ? "ivl_swa_decode_rows_fwd(combine)" : "ivl_swa_fwd(combine)");
@@ -1044,36 +1091,47 @@ extern "C" int ivl_swa_fwd(const ivl_swa_args* a, void* stream) {
   return swa_combine_append(p, false, prefill, a->append_new != 0, st);
 }
 
-extern "C" int ivl_swa_decode_rows_fwd(const ivl_swa_args* a, const int64_t* pos_rows, void* stream) {
-  static const char fn[] = "ivl_swa_decode_rows_fwd";
+// rules + launches of both pos_rows forms; frozen == nullptr IS ivl_swa_decode_rows_fwd
+static int swa_decode_rows_launch(const char* fn, const ivl_swa_args* a, const int64_t* pos_rows, const int32_t* frozen, void* stream) {
   // (a NULL struct is refused first, by the shared rule behind this one)
-  IVL_REQUIRE(a == nullptr || pos_rows != nullptr, IVL_ERR_INVALID_ARG, "ivl_swa_decode_rows_fwd: NULL pos_rows");
+  IVL_REQUIRE(a == nullptr || pos_rows != nullptr, IVL_ERR_INVALID_ARG, "%s: NULL pos_rows", fn);
   if (const int rc = swa_check_pointers(a, fn); rc != IVL_OK) return rc;
   IVL_REQUIRE(a->B > 0 && a->T > 0 && a->Hq > 0 && a->Hkv > 0, IVL_ERR_INVALID_ARG,
-              "ivl_swa_decode_rows_fwd: bad sizes B=%d T=%d Hq=%d Hkv=%d", a->B, a->T, a->Hq, a->Hkv);
+              "%s: bad sizes B=%d T=%d Hq=%d Hkv=%d", fn, a->B, a->T, a->Hq, a->Hkv);
   if (const int rc = swa_check_heads(a, fn); rc != IVL_OK) return rc;
   IVL_REQUIRE(a->cache_capacity > 0 && a->k_cache && a->v_cache, IVL_ERR_UNSUPPORTED,
-              "ivl_swa_decode_rows_fwd: needs a ring cache (cache_capacity=%d)", a->cache_capacity);
-  IVL_REQUIRE(a->T_new == a->T, IVL_ERR_UNSUPPORTED, "ivl_swa_decode_rows_fwd: needs T_new == T (got %d, %d)", a->T_new, a->T);
+              "%s: needs a ring cache (cache_capacity=%d)", fn, a->cache_capacity);
+  IVL_REQUIRE(a->T_new == a->T, IVL_ERR_UNSUPPORTED, "%s: needs T_new == T (got %d, %d)", fn, a->T_new, a->T);
   const int G = a->Hq / a->Hkv;
   IVL_REQUIRE((long long)a->T * G <= SWA_QT && G <= 16, IVL_ERR_UNSUPPORTED,
-              "ivl_swa_decode_rows_fwd: packed decode rows only: T * Hq/Hkv = %lld > %d", (long long)a->T * G, SWA_QT);
-  IVL_REQUIRE(a->mma_dtype == IVL_BF16, IVL_ERR_UNSUPPORTED, "ivl_swa_decode_rows_fwd: mma_dtype must be IVL_BF16 (got %d)",
+              "%s: packed decode rows only: T * Hq/Hkv = %lld > %d", fn, (long long)a->T * G, SWA_QT);
+  IVL_REQUIRE(a->mma_dtype == IVL_BF16, IVL_ERR_UNSUPPORTED, "%s: mma_dtype must be IVL_BF16 (got %d)", fn,
               a->mma_dtype);
   if (const int rc = swa_check_rope_tables(a, fn); rc != IVL_OK) return rc;
   IVL_REQUIRE(a->rope_cos == nullptr || swa_rope_sections_ok(a->rope_s0, a->rope_s1), IVL_ERR_UNSUPPORTED,
-              "ivl_swa_decode_rows_fwd: mrope sections must be multiples of 8 (got %d, %d)", a->rope_s0, a->rope_s1);
+              "%s: mrope sections must be multiples of 8 (got %d, %d)", fn, a->rope_s0, a->rope_s1);
   if (const int rc = swa_check_key_rows(a, fn, ""); rc != IVL_OK) return rc;
   const int nsplit = swa_pack_nsplit(a);
-  IVL_REQUIRE(nsplit > 1, IVL_ERR_UNSUPPORTED, "ivl_swa_decode_rows_fwd: single-split shape (window %d)", a->window);
+  IVL_REQUIRE(nsplit > 1, IVL_ERR_UNSUPPORTED, "%s: single-split shape (window %d)", fn, a->window);
   SwaParams p = swa_params(a, nsplit);
   p.pos = 0; p.pos_dev = (const long long*)pos_rows;
   if (const int rc = swa_carve_partials(a, fn, p); rc != IVL_OK) return rc;
   p.n_qtiles = 1;
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(swa_rows_decode_kernel, dim3(a->Hkv * a->B * nsplit), dim3(256), 0, st, p.pos_dev, p);
+  if (frozen != nullptr) hipLaunchKernelGGL(swa_rows_hold_decode_kernel, dim3(a->Hkv * a->B * nsplit), dim3(256), 0, st, p.pos_dev, p, frozen);
+  else hipLaunchKernelGGL(swa_rows_decode_kernel, dim3(a->Hkv * a->B * nsplit), dim3(256), 0, st, p.pos_dev, p);
   if (const int rc = check_launch(fn); rc != IVL_OK) return rc;
-  return swa_combine_append(p, true, false, a->append_new != 0, st);
+  return swa_combine_append(p, true, false, a->append_new != 0, st, frozen);
+}
+
+extern "C" int ivl_swa_decode_rows_fwd(const ivl_swa_args* a, const int64_t* pos_rows, void* stream) {
+  return swa_decode_rows_launch("ivl_swa_decode_rows_fwd", a, pos_rows, nullptr, stream);
+}
+
+// ivl_swa_decode_rows_fwd with a per-row hold mask (HOLD-1..3 in ivl_hip.h): the same split count, grid and merge; the workgroups,
+// combine blocks and ring slots of a row with frozen[b] != 0 do nothing
+extern "C" int ivl_swa_decode_rows_hold_fwd(const ivl_swa_args* a, const int64_t* pos_rows, const int32_t* frozen, void* stream) {
+  return swa_decode_rows_launch("ivl_swa_decode_rows_hold_fwd", a, pos_rows, frozen, stream);
 }
 
 extern "C" int ivl_swa_cache_append(const void* k_new, const void* v_new, int64_t kn_sb, int64_t kn_st, int64_t kn_sh,

@@ -1,11 +1,16 @@
 // Bodies of the split-KV combine kernels (swa.hip), included inside the kernel functions that share them: SWA_WIDE 0 the
 // templated combine (NS, BF16P in scope), SWA_WIDE 1 the wide one; SWA_ROWS 1 (ivl_swa_decode_rows_fwd) appends every batch
-// row at its own position (ring_append<true>).  Textual inclusion keeps the generated code of the pre-existing combine kernels
+// row at its own position (ring_append<1>); SWA_ROWS 2 (ivl_swa_decode_rows_hold_fwd, `frozen` in scope) also skips the merge, the o
+// store and the ring slots of a frozen batch row.  Textual inclusion keeps the generated code of the pre-existing combine kernels
 // exactly what it was when the bodies were written inside them.
 // Expects: part_o, part_ml, o, B, rows_per_b, nsplit, ap in scope, SWA_WIDE and SWA_ROWS defined.
 #if SWA_WIDE
   if (ap.first_block >= 0 && (int)blockIdx.x >= ap.first_block) {
+#if SWA_ROWS == 2
+    ring_append<2>(ap, (long long)blockIdx.x - ap.first_block, (long long)gridDim.x - ap.first_block, frozen);
+#else
     ring_append<SWA_ROWS>(ap, (long long)blockIdx.x - ap.first_block, (long long)gridDim.x - ap.first_block);
+#endif
     return;
   }
   // one WORKGROUP per row: wave w merges the splits 16w .. 16w + 15 (all 16 partial rows requested at once: one memory
@@ -16,6 +21,9 @@
   for (long long r = blockIdx.x; r < (long long)B * rows_per_b; r += ncb) {
     int rr_;
     const long long b = divmod_idx(r, rows_per_b, rr_), rr = rr_;
+#if SWA_ROWS == 2
+    if (frozen[b] != 0) continue;        // uniform over the row's workgroup / wavefront: its partials were never written
+#endif
     const bool on = lane < nsplit;
     const float2 ml = *(const float2*)(part_ml + ((b * nsplit + (on ? lane : 0)) * rows_per_b + rr) * 2);
     float2 ov[16];
@@ -49,7 +57,11 @@
   }
 #else
   if (ap.first_block >= 0 && (int)blockIdx.x >= ap.first_block) {
+#if SWA_ROWS == 2
+    ring_append<2>(ap, (long long)blockIdx.x - ap.first_block, (long long)gridDim.x - ap.first_block, frozen);
+#else
     ring_append<SWA_ROWS>(ap, (long long)blockIdx.x - ap.first_block, (long long)gridDim.x - ap.first_block);
+#endif
     return;
   }
   const int ncb = ap.first_block >= 0 ? ap.first_block : (int)gridDim.x;       // combine blocks
@@ -59,6 +71,9 @@
   for (long long r = wid; r < (long long)B * rows_per_b; r += nw) {
     int rr_;
     const long long b = divmod_idx(r, rows_per_b, rr_), rr = rr_;
+#if SWA_ROWS == 2
+    if (frozen[b] != 0) continue;        // uniform over the row's workgroup / wavefront: its partials were never written
+#endif
     float ms[NS], ls[NS];
     float2 ov[NS];
 #pragma unroll

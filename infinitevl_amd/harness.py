@@ -809,6 +809,9 @@ class Sampler:
     built without either samples exactly as before, until a row is given stop ids or a budget -- set that before the step is
     captured (the graphed classes recapture when they see the switch).  The kernel keeps n_new (tokens generated) and done
     (0 running, 1 stop id, 2 budget) per row; a finished row gets its fill token until it is set or reset again.
+    done code 4 = held by the host: no kernel writes it; GraphedMultiStreamDecode(holds=True).hold() sets it and resume() clears
+    it, and to the sampling launch it is a finished row.  With holds `done` is also the step's hold mask (HOLD-1..3 in
+    include/ivl_hip.h): a row with done != 0 keeps its cache rows and positions from the next replay on.
 
     Scores (`logprobs` / `top_logprobs` of the reference's api/protocol.py, output_scores of HF generate): a sampler built
     with `logprobs` = 0 (the emitted token's log-probability) or 1..20 (that plus the N most likely alternatives) uses the
@@ -848,7 +851,7 @@ class Sampler:
         _RowField("budget", torch.int64, (), -1, kw="budget"),
         _RowField("fill", torch.int64, (), 0, kw="fill"),
         _RowField("n_new", torch.int64, (), 0, state=True, kw="n_new"),             # tokens generated
-        _RowField("done", torch.int32, (), 0, state=True, kw="done"),               # 0 running, 1 stop id, 2 budget
+        _RowField("done", torch.int32, (), 0, state=True, kw="done"),               # 0 running, 1 stop id, 2 budget, 3 dead end, 4 held
         _RowField("history", torch.int64, ("history",), 0, state=True, kw="history"),
         _RowField("logprob", torch.float32, (), 0.0, state=True, kw="logprob", score=True),
         _RowField("cum_logprob", torch.float64, (), 0.0, state=True, kw="cum_logprob", score=True),
@@ -998,9 +1001,30 @@ class Sampler:
                 if k in p:
                     t[row] = p[k]
         if "stop_token_ids" in p and "max_new_tokens" in p:
-            self._ends[row] = bool(p["stop_token_ids"]) or p["max_new_tokens"] is not None
-            if self._ends[row]:
-                self.controlled = True
+            self._note_ends(row, bool(p["stop_token_ids"]) or p["max_new_tokens"] is not None)
+
+    def _note_ends(self, row: int, ends: bool) -> None:
+        """the host's note of whether `row` has a stop id or a budget (run_until_done watches such rows; the first one switches
+        the sampler to the controlled launch)"""
+        self._ends[row] = ends
+        if ends:
+            self.controlled = True
+
+    _UNCHANGED = object()
+
+    def set_ends(self, row: int, max_new_tokens=_UNCHANGED, stop_token_ids=_UNCHANGED) -> None:
+        """What ends `row` from here on, the rest of the row left as it is: its budget (None or an int >= 1, counted against
+        n_new) and / or its stop ids, each checked as in set(); one that is not given stays.  The host's note follows from what
+        the row then has (one read-back of the row's budget and stop ids)."""
+        row = self._row(row)
+        given = {k: v for k, v in (("max_new_tokens", max_new_tokens), ("stop_token_ids", stop_token_ids)) if v is not self._UNCHANGED}
+        if not given:
+            return
+        p = self._checked("Sampler.set_ends", given)
+        if p.get("stop_token_ids") and self.stop_ids is None:
+            raise ValueError("Sampler.set_ends: stop_token_ids need a Sampler built with max_stop > 0")
+        self._write(row, p)
+        self._note_ends(row, int(self.budget[row]) >= 0 or (self.stop_ids is not None and bool((self.stop_ids[row] >= 0).any())))
 
     def set(self, row: int, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0,
             repetition_penalty: float = 1.0, stop_token_ids=(), max_new_tokens: Optional[int] = None, fill_token: int = 0,
@@ -1146,7 +1170,7 @@ class Sampler:
 
     def poll(self) -> Tuple[torch.Tensor, torch.Tensor]:
         """(done, n_new) of every row on the host, int64 [n_rows] each, in one copy (it waits for the steps queued so far).
-        done: 0 running, 1 stop id, 2 budget, 3 a dead end of the row's grammar."""
+        done: 0 running, 1 stop id, 2 budget, 3 a dead end of the row's grammar, 4 held by the host (hold / resume)."""
         both = torch.stack([self.done.to(torch.int64), self.n_new]).cpu()
         return both[0], both[1]
 
@@ -1245,12 +1269,30 @@ class GraphedMultiStreamDecode(_Graphed):
     top-k / top-p and its own random stream in one ops.sample_tokens launch (a slot left at temperature 0 stays greedy).
     A slot's whole state is one row of every tensor, so a stream also branches: fork() copies a live slot into others in one
     launch, load() brings in the state of an external stream cache, extend() feeds a live slot more prompt tokens, and
-    admit_n() prefills a prompt once for several independently sampled answers -- all between replays, never a recapture."""
+    admit_n() prefills a prompt once for several independently sampled answers -- all between replays, never a recapture.
+
+    holds=True (needs a sampler in its controlled form; fixed at construction): a slot's state is exactly the tokens it was
+    given.  The captured step reads the sampler's `done` as its hold mask (HOLD-1..3 in include/ivl_hip.h): a slot that ended on
+    a stop id, its budget or a dead end keeps its GDN states, ring row, position and M-RoPE positions from the next replay on,
+    with no host involved; hold(slot) / resume(slot) make a live slot sit steps out (a stream waiting for its next frame) and
+    extend() on a finished slot starts the next turn of a conversation.  The host mirror of the slots' lengths is then rewritten
+    from the device where a length is read (MultiStreamCache.sync_lengths)."""
 
     PREFILL_CHUNK = 4096
+    _UNCHANGED = Sampler._UNCHANGED                      # extend(max_new_tokens=, stop_token_ids=): keep what the row has
+    HELD = 4                                             # the done code of a slot held by the host
 
     def __init__(self, model: InfiniteVLTextStack, cache: MultiStreamCache, warmup: int = 2,
-                 sampler: Optional["Sampler"] = None):
+                 sampler: Optional["Sampler"] = None, holds: bool = False):
+        if holds and (sampler is None or not sampler.controlled):
+            raise ValueError("GraphedMultiStreamDecode: holds=True needs a sampler in its controlled form (built with vocab_size, "
+                             "history or logprobs): its `done` is the step's hold mask")
+        if holds:
+            bad = [i for i, l in enumerate(model.layers) if hasattr(l.self_attn, "holds_ok") and not l.self_attn.holds_ok(cache.layers[i].dtype)]
+            if bad:
+                raise ValueError(f"GraphedMultiStreamDecode: holds=True needs GDN layers that take the masked one-launch step (a "
+                                 f"fuse_()d bf16 stack with 128 x 256 heads on a bf16 cache); layers {bad} do not")
+        self.holds = bool(holds)
         if sampler is not None and sampler.n_rows != cache.n_slots:
             raise ValueError(f"GraphedMultiStreamDecode: the sampler has {sampler.n_rows} rows for {cache.n_slots} slots")
         self.sampler = sampler
@@ -1267,10 +1309,62 @@ class GraphedMultiStreamDecode(_Graphed):
         self._fork_plan = None                           # built at the first fork
         self.adapter_ids = torch.full((self.S,), -1, dtype=torch.int32, device=p_.device)
         self._slot_adapter = [None] * self.S             # the handles behind adapter_ids (the prefill calls take them)
+        self._held = set()                               # slots between hold and resume
+        self._parked = None
+        if self.holds:
+            self._parked = torch.zeros(self.S, 1, dtype=torch.int64, device=p_.device)      # the pending token of a held slot
+            cache.enable_holds(sampler.done, advance=False)                                  # (_run advances both counters)
 
     def capture(self) -> None:
         """Warm up and capture; every slot's ring, state, position and token are restored afterwards."""
         self.logits = self._capture([self.position_ids, self.token])
+
+    def _run(self):
+        """In hold mode: forward of every running row's token, ONE ops.rows_advance for pos_rows and the three M-RoPE positions,
+        then the draw.  The counters move before the draw because the mask is the sampler's `done`: the row whose token ends it
+        in this step did run this step (its ring took the token), so it is advanced under the mask the forward saw."""
+        if not self.holds:
+            return super()._run()
+        _, lg = self.model(input_ids=self.token, position_ids=self.position_ids, past_key_values=self.cache,
+                           logits_to_keep=1, **self._adapters())
+        ops.rows_advance(self.cache.pos_rows, self.position_ids, self.sampler.done, 1)
+        self._next_token(lg[:, -1])
+        return lg
+
+    def _unhold(self, slot: int) -> None:
+        """A held slot that gets a new stream is no longer held: the host's code leaves its row with the note (a row that is
+        set afresh clears it anyway)."""
+        if slot in self._held:
+            self._held.discard(slot)
+            self.sampler.done[slot] = 0
+
+    def _need_holds(self, who: str) -> None:
+        if not self.holds:
+            raise ValueError(f"{who}: needs a GraphedMultiStreamDecode built with holds=True")
+
+    def hold(self, slot: int) -> None:
+        """The live, running slot `slot` sits out the steps from the next replay on (done code 4): its pending token is parked,
+        its state, position and sampler row stay as they are.  Between replays; never a recapture."""
+        self._need_holds("hold")
+        slot = self._slots("hold", [slot])[0]
+        if slot not in self._live:
+            raise ValueError(f"hold: slot {slot} holds no stream (admit or load it first)")
+        code = int(self.sampler.done[slot])
+        if code != 0:
+            raise ValueError(f"hold: slot {slot} is not running (done code {code})")
+        self._parked[slot].copy_(self.token[slot])
+        self.sampler.done[slot] = self.HELD
+        self._held.add(slot)
+
+    def resume(self, slot: int) -> None:
+        """The held slot `slot` runs again from the next replay on, with the token it was held with."""
+        self._need_holds("resume")
+        slot = self._slots("resume", [slot])[0]
+        if slot not in self._held:
+            raise ValueError(f"resume: slot {slot} is not held")
+        self.token[slot].copy_(self._parked[slot])
+        self.sampler.done[slot] = 0
+        self._held.discard(slot)
 
     def set_adapter(self, slot: int, adapter) -> None:
         """The slot decodes under `adapter` (a handle of model.load_adapter; None = the base model) from the next step on: one
@@ -1313,6 +1407,7 @@ class GraphedMultiStreamDecode(_Graphed):
             self.sampler.mark(slot, prompt_ids.to(inputs_embeds.device))
         self.cache.admit(slot)
         self._live.add(slot)
+        self._unhold(slot)
         lg = self._prefill(slot, inputs_embeds, position_ids)
         self.admit_logits = lg                          # [1,1,vocab]: what the latest admission's first token was taken from
         self._draw(slot, lg)
@@ -1381,10 +1476,15 @@ class GraphedMultiStreamDecode(_Graphed):
         return self._fork_plan
 
     def _fork_rows(self, src: int, dsts: List[int]) -> None:
+        self.cache.sync_lengths()
         self._row_plan().run(src, dsts)
         for d in dsts:
             self.cache.slot_lengths[d] = self.cache.slot_lengths[src]
             self._live.add(d)
+            self._held.discard(d)
+            if src in self._held:                        # a frozen row is copied as it is, code and parked token included
+                self._parked[d].copy_(self._parked[src])
+                self._held.add(d)
 
     @torch.no_grad()
     def fork(self, src: int, dsts, sampling=None, adapter="src") -> None:
@@ -1414,17 +1514,36 @@ class GraphedMultiStreamDecode(_Graphed):
 
     @torch.no_grad()
     def extend(self, slot: int, inputs_embeds: torch.Tensor, position_ids: Optional[torch.Tensor] = None,
-               prompt_ids: Optional[torch.Tensor] = None, grammar=None) -> torch.Tensor:
+               prompt_ids: Optional[torch.Tensor] = None, grammar=None, max_new_tokens=_UNCHANGED,
+               stop_token_ids=_UNCHANGED) -> torch.Tensor:
         """Continue the live slot `slot` with more prompt tokens inputs_embeds [1,T,hidden] -- a question, the next video
         frame -- on its B = 1 view.  position_ids [3,1,T]; default: each of the slot's three positions counts on from
         position_ids[:, slot].  The slot's next token is drawn from the last logits (in the sampler's launch, after
         `prompt_ids` were marked as seen) and REPLACES the pending one, which was never fed to the model.  admit_logits is set.
-        `grammar`: the slot goes to that grammar's start state before the draw (default: it stays in the state it is in)."""
+        `grammar`: the slot goes to that grammar's start state before the draw (default: it stays in the state it is in).
+        `max_new_tokens` (None or an int >= 1) / `stop_token_ids`: the row's budget / stop ids from here on (default: unchanged).
+        With holds=True, on a slot that is frozen (finished or held) this starts the NEXT TURN where the state stopped: done, n_new
+        and cum_logprob are cleared, so tokens(slot) and the score rings hold the new answer only; seen, count, the random counter
+        and the grammar state stay.  The token that ended the last turn was never fed to the model; it belongs in inputs_embeds
+        if the conversation's template has it."""
         slot = self._slots("extend", [slot])[0]
         if slot not in self._live:
             raise ValueError(f"extend: slot {slot} holds no stream (admit or load it first)")
         self._check_grammar("extend", grammar)
         T = self._check_prompt("extend", inputs_embeds, position_ids, prompt_ids)
+        ends = {k: v for k, v in (("max_new_tokens", max_new_tokens), ("stop_token_ids", stop_token_ids)) if v is not Sampler._UNCHANGED}
+        if ends and self.sampler is None:
+            raise ValueError("extend: max_new_tokens / stop_token_ids need a GraphedMultiStreamDecode built with a sampler")
+        if ends:
+            self.sampler._checked("extend", ends)       # (refused before anything is written)
+        if self.holds and int(self.sampler.done[slot]) != 0:
+            self.sampler.done[slot] = 0
+            self.sampler.n_new[slot] = 0
+            if self.sampler.cum_logprob is not None:
+                self.sampler.cum_logprob[slot] = 0.0
+            self._held.discard(slot)                     # (the draw below replaces the parked token too)
+        if ends:
+            self.sampler.set_ends(slot, **ends)
         if grammar is not None:
             self.sampler.set_grammar(slot, grammar)
         if position_ids is None:
@@ -1495,6 +1614,7 @@ class GraphedMultiStreamDecode(_Graphed):
             self.sampler.mark(first, prompt_ids.to(inputs_embeds.device))
         self.cache.admit(first)
         self._live.add(first)
+        self._unhold(first)
         lg = self._prefill(first, inputs_embeds, position_ids)
         self.admit_logits = lg
         self.position_ids[:, first].fill_(int(position_ids.max()) + 1)
@@ -1541,11 +1661,13 @@ class GraphedMultiStreamDecode(_Graphed):
             self.position_ids[:, s].fill_(next_position)
             self.set_adapter(s, adapter)                 # (the extend that follows runs under it)
             self._live.add(s)
+            self._unhold(s)
 
     def release(self, slot: int) -> None:
         """End the stream in `slot`: its state is zeroed (the slot keeps computing on zeros until the next admit)."""
         self.cache.release(slot)
         self._live.discard(slot)
+        self._held.discard(slot)
         if self.sampler is not None:
             self.sampler.reset(slot)
         self.token[slot].zero_()
@@ -1563,7 +1685,7 @@ class GraphedMultiStreamDecode(_Graphed):
         if self._stale():
             self.capture()
         self.graph.replay()
-        self.cache.advance(1)
+        self.cache.advance(1)                            # (with holds the per-slot mirror is rewritten by cache.sync_lengths())
         return self.token
 
     def _replay_until(self, finished, max_steps: int, poll_every: int) -> None:
@@ -1582,10 +1704,11 @@ class GraphedMultiStreamDecode(_Graphed):
         """Replay up to `max_steps` steps without a host round trip per token: the sampler's done flags are polled every
         `poll_every` steps, and the loop ends once every live slot that has a stop id or a budget is done (or at max_steps; it
         runs to max_steps when no live slot has either).  Returns {slot: the slot's generated tokens} of the live slots, from
-        the sampler's history.  A finished slot keeps computing on its fill token until it is released."""
+        the sampler's history.  A finished slot keeps computing on its fill token until it is released (with holds=True it
+        freezes where it ended instead, and held slots are not waited for)."""
         if self.sampler is None or self.sampler.history is None:
             raise ValueError("run_until_done: needs a sampler built with history > 0")
-        watched = [s for s in sorted(self._live) if self.sampler._ends[s]]
+        watched = [s for s in sorted(self._live) if self.sampler._ends[s] and s not in self._held]
         self._replay_until(lambda: bool(watched) and bool((self.sampler.poll()[0][watched] != 0).all()), max_steps, poll_every)
         return {s: self.sampler.tokens(s) for s in sorted(self._live)}
 
@@ -1601,9 +1724,12 @@ class GraphedBeamDecode(GraphedMultiStreamDecode):
     ivl_beam_select_fwd in include/ivl_hip.h states the semantics and the differences from HF."""
 
     def __init__(self, model: InfiniteVLTextStack, cache: MultiStreamCache, num_beams: int, vocab_size: int, history: int,
-                 max_stop: int = 1, warmup: int = 2, sampler: Optional["Sampler"] = None):
+                 max_stop: int = 1, warmup: int = 2, sampler: Optional["Sampler"] = None, holds: bool = False):
         """sampler: the slots' sampler, where the caller wants to keep it (default: built here); it must be what this class
-        builds -- n_slots rows, vocab_size, max_stop 0, history, logprobs = K, no score rings -- and hold no grammars."""
+        builds -- n_slots rows, vocab_size, max_stop 0, history, logprobs = K, no score rings -- and hold no grammars.
+        holds: refused (a beam's rows are gathered every step; a group that is done is already skipped)."""
+        if holds:
+            raise ValueError("GraphedBeamDecode: holds=True is not supported (per-slot holds are GraphedMultiStreamDecode's)")
         if sampler is not None and (sampler.penalties or sampler.biases is not None):
             raise ValueError("GraphedBeamDecode: the sampler was built with penalties or bias_tables: they are not part of beam "
                              "search (a beam's candidates come from the score-only launch, which takes no adjustment group)")

@@ -178,6 +178,11 @@ class InfiniteVLSelfAttention(nn.Module):
                 (self.layer_idx, "o"): (self.o_proj.weight, (0, self.o_proj.weight.shape[0]), ("o_proj",))}
 
 
+_HOLD_REFUSAL = ("the cache keeps a hold mask (MultiStreamCache.enable_holds), and this Gated DeltaNet call does not reach the masked "
+                 "one-launch step: it would overwrite the states of frozen slots.  Holds need a fuse_()d bf16 stack with 128 x 256 "
+                 "heads on a bf16 cache, and T = 1 steps (a prompt runs on MultiStreamCache.slot_view)")
+
+
 class GatedDeltaNet(nn.Module):
     """Gated DeltaNet mixer (std:1116-1347): q/k/v short convs, gates, delta-rule kernel, gated norm."""
 
@@ -298,6 +303,13 @@ class GatedDeltaNet(nn.Module):
             self._gate32 = (key, self.A_log.detach().float().contiguous(), self.dt_bias.detach().float().contiguous())
         return self._gate32[1], self._gate32[2]
 
+    def holds_ok(self, cache_dtype: torch.dtype = torch.bfloat16) -> bool:
+        """Whether a T = 1 step of this layer on a bf16 cache reaches the masked one-launch step (ops.gdn_decode_step(frozen=)):
+        the fused bf16 projection (fuse_()), 128 x 256 heads, as many key as query heads."""
+        return (self._fused_w is not None and self._fused_w.dtype == torch.bfloat16 and cache_dtype == torch.bfloat16
+                and self.q_proj.weight.data_ptr() == self._fused_w.data_ptr() and self.q_conv1d.weight.dtype == torch.bfloat16
+                and self.key_dim == self.num_heads * self.head_dim and self.head_dim == 128 and self.head_v_dim == 256)
+
     def _fused_ok(self, x: torch.Tensor, layer) -> bool:
         return (self._fused_w is not None and x.dtype == torch.bfloat16 and self._fused_w.dtype == torch.bfloat16
                 and self.q_proj.weight.data_ptr() == self._fused_w.data_ptr()
@@ -328,11 +340,14 @@ class GatedDeltaNet(nn.Module):
         A32, dt32 = self._gate_params32()
         w = self.o_norm.weight
         w = w if w.dtype == torch.bfloat16 else w.to(torch.bfloat16)
+        frozen = getattr(past_key_values, "hold_mask", None)
         if (T == 1 and layer is not None and prev[0] is not None and h0 is not None and Dk == Dq
                 and h0.data_ptr() == layer.recurrent_state.data_ptr() and K == 128 and V == 256):
             ow, ob = self.o_proj.weight, self.o_proj.bias
+            # hold mode (MultiStreamCache.enable_holds): the one-launch step takes the per-row mask at every slot count (the split
+            # form has no mask; the two forms are bit-equal by the header)
             # (with adapters the o_proj output must exist before lora_add: the one-launch step + ops.linear, bit-equal by the header)
-            if (ops._SPLIT_DECODE and self._lora is None and B <= 4 and 2 <= H <= 16 and ow.dtype == torch.bfloat16 and ow.is_contiguous() and cg % 4 == 0
+            if (ops._SPLIT_DECODE and frozen is None and self._lora is None and B <= 4 and 2 <= H <= 16 and ow.dtype == torch.bfloat16 and ow.is_contiguous() and cg % 4 == 0
                     and ld % 4 == 0 and (ob is None or (ob.dtype == torch.bfloat16 and ob.is_contiguous()))):
                 # decode step on 64 workgroups (sequence x head x column quarter); the gated norm and the q / k conv-state shift ride
                 # in the o_proj launch: the same two launches, 4 x the memory parallelism for the 2 MB of state (bit-identical)
@@ -347,11 +362,13 @@ class GatedDeltaNet(nn.Module):
             # decode step: convs + gates + delta rule + gated norm in ONE launch, cache tensors updated in place
             o = ops.gdn_decode_step(proj, (cq, ck, cv, cg, ca, cb),
                                     (self.q_conv1d.weight, self.k_conv1d.weight, self.v_conv1d.weight), outs, A32, dt32,
-                                    w, self.norm_eps, layer.recurrent_state, H, K, V, K ** -0.5)
+                                    w, self.norm_eps, layer.recurrent_state, H, K, V, K ** -0.5, frozen=frozen)
             past_key_values.update(layer_idx=self.layer_idx, key_states=None, value_states=None, conv_state=outs,
                                    recurrent_state=layer.recurrent_state,
                                    cache_kwargs={"op": "set", "delta_len": T, "cache_position": cache_position})
             return ops.linear(o, self.o_proj.weight, self.o_proj.bias, **w8_o, **kw_o), None
+        if frozen is not None:
+            raise RuntimeError(_HOLD_REFUSAL)
         convs = (self.q_conv1d.weight, self.k_conv1d.weight, self.v_conv1d.weight)
         if mode == "chunk" and Dk == Dq and K == 128 and V == 256 and convs[0].shape[-1] == 4:
             # convs + gates inside the chunk kernel's pre-pass: q / k / v / g / beta never reach HBM, one launch less
@@ -385,6 +402,8 @@ class GatedDeltaNet(nn.Module):
             return self._forward_fused(hidden_states, past_key_values, layer, cache_position, mode)
         if self._lora is not None:
             raise RuntimeError("adapters are attached (enable_adapters): they ride on the fused bf16 projections only")
+        if getattr(past_key_values, "hold_mask", None) is not None:
+            raise RuntimeError(_HOLD_REFUSAL)
         if isinstance(hidden_states, ops.PreNorm):
             hidden_states = hidden_states.materialize()
         use_cache = past_key_values is not None

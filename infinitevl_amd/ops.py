@@ -768,21 +768,67 @@ def gdn_prologue(proj: torch.Tensor, cols, conv_weights, conv_states_in, conv_st
 
 
 def gdn_decode_step(proj: torch.Tensor, cols, conv_weights, conv_states, A_log32, dt_bias32, norm_weight, eps: float,
-                    state: torch.Tensor, H: int, K: int, V: int, scale: float) -> torch.Tensor:
+                    state: torch.Tensor, H: int, K: int, V: int, scale: float,
+                    frozen: Optional[torch.Tensor] = None) -> torch.Tensor:
     """One new token per sequence through the GDN mixer core in ONE launch (convs + gates + delta rule + gated
     norm).  proj [B,1,ld] bf16; cols = (col_q, col_k, col_v, col_g, col_a, col_b); conv_states 3 x [B,D,4] bf16 and
-    state [B,H,K,V] are updated in place.  Returns y [B,1,H*V] bf16 (the o_proj input)."""
+    state [B,H,K,V] are updated in place.  Returns y [B,1,H*V] bf16 (the o_proj input).
+    `frozen` (device int32 [B], ivl_gdn_decode_step_rows_fwd): a row with frozen[b] != 0 keeps its states and its y row is
+    unspecified; the mask is read at replay."""
     _need_gpu(proj, state)
     B, T, ld = proj.shape
     assert T == 1 and proj.is_contiguous() and proj.dtype == torch.bfloat16 and state.is_contiguous()
-    y = torch.empty(B, 1, H * V, dtype=torch.bfloat16, device=proj.device)
     wq, wk, wv = conv_weights
     sq, sk, sv = conv_states
+    if frozen is not None:
+        _check_frozen("gdn_decode_step", frozen, B, proj)
+        y = torch.empty(B, 1, H * V, dtype=torch.bfloat16, device=proj.device)
+        HOLD_CALLS["gdn_decode_step"] += 1
+        _lib.check(_lib.load().ivl_gdn_decode_step_rows_fwd(
+            _p(proj), ld, cols[0], cols[1], cols[2], cols[3], cols[4], cols[5], _p(wq), _p(wk), _p(wv), _p(sq), _p(sk), _p(sv),
+            _p(A_log32), _p(dt_bias32), _p(norm_weight), float(eps), _p(state), _DT_CODE[state.dtype], _p(y), B, H, K, V,
+            float(scale), _p(frozen), _stream(proj)))
+        return y
+    y = torch.empty(B, 1, H * V, dtype=torch.bfloat16, device=proj.device)
     _lib.check(_lib.load().ivl_gdn_decode_step_fwd(
         _p(proj), ld, cols[0], cols[1], cols[2], cols[3], cols[4], cols[5], _p(wq), _p(wk), _p(wv), _p(sq), _p(sk), _p(sv),
         _p(A_log32), _p(dt_bias32), _p(norm_weight), float(eps), _p(state), _DT_CODE[state.dtype], _p(y), B, H, K, V,
         float(scale), _stream(proj)))
     return y
+
+
+# calls that took a hold entry point (frozen=), per operator (tests read it to know which kernel a call ran on)
+HOLD_CALLS = {"gdn_decode_step": 0, "swa_forward": 0, "rows_advance": 0}
+
+
+def _check_frozen(who: str, frozen: torch.Tensor, B: int, like: torch.Tensor) -> None:
+    if frozen.dtype != torch.int32 or tuple(frozen.shape) != (B,) or not frozen.is_contiguous() or frozen.device != like.device:
+        raise ValueError(f"{who}: frozen must be a contiguous int32 [B] = [{B}] tensor on {like.device}; got {frozen.dtype} "
+                         f"{tuple(frozen.shape)} on {frozen.device}")
+
+
+def rows_advance(pos_rows: Optional[torch.Tensor], position_ids: Optional[torch.Tensor], frozen: Optional[torch.Tensor],
+                 delta: int = 1) -> None:
+    """pos_rows[s] += delta (int64 [S]) and position_ids[:, s] += delta (int64 [3, S] or [3, S, 1]) where frozen[s] == 0, in one
+    launch (ivl_rows_advance_fwd); either tensor may be None, frozen=None advances every row."""
+    ref = pos_rows if pos_rows is not None else position_ids
+    if ref is None:
+        return
+    _need_gpu(ref)
+    S = pos_rows.shape[0] if pos_rows is not None else position_ids.shape[1]
+    stride = 0
+    if pos_rows is not None and (pos_rows.dtype != torch.int64 or pos_rows.dim() != 1 or not pos_rows.is_contiguous()):
+        raise ValueError(f"rows_advance: pos_rows must be a contiguous int64 [S] tensor; got {pos_rows.dtype} {tuple(pos_rows.shape)}")
+    if position_ids is not None:
+        if position_ids.dtype != torch.int64 or position_ids.shape[0] != 3 or position_ids.numel() != 3 * S or \
+                not position_ids.is_contiguous():
+            raise ValueError(f"rows_advance: position_ids must be a contiguous int64 [3, S] = [3, {S}] tensor; got "
+                             f"{position_ids.dtype} {tuple(position_ids.shape)}")
+        stride = S
+    if frozen is not None:
+        _check_frozen("rows_advance", frozen, S, ref)
+    HOLD_CALLS["rows_advance"] += 1
+    _lib.check(_lib.load().ivl_rows_advance_fwd(_p(pos_rows), _p(position_ids), stride, _p(frozen), S, int(delta), _stream(ref)))
 
 
 # The GDN decode step on 64 workgroups + gated norm / conv-state shift in the o_proj launch (gdn_decode_split + gdn_out_linear):
@@ -1765,7 +1811,7 @@ def swa_forward(
     k_cache: Optional[torch.Tensor] = None, v_cache: Optional[torch.Tensor] = None,
     pos: int = 0, pos_dev: Optional[torch.Tensor] = None, n_query: Optional[int] = None,
     layout: str = "bthd", mma_dtype=None, rope=None, append: bool = False, pos_min: int = 0, pos_min_holds_in_graph: bool = False,
-    pos_rows: Optional[torch.Tensor] = None,
+    pos_rows: Optional[torch.Tensor] = None, frozen: Optional[torch.Tensor] = None,
 ) -> torch.Tensor:
     """Sliding-window GQA attention over (ring cache ++ new keys); returns o [B,T,Hq,d] bf16.
 
@@ -1782,8 +1828,10 @@ def swa_forward(
     unless `pos_min_holds_in_graph` says the bound holds for every replay (the kernel micro-benchmarks replay one position).
     `pos_rows` (device int64 [B]): one ring position per batch row -- independent streams in the rows of one cache
     (ivl_swa_decode_rows_fwd).  Row b attends as this call would at B = 1 with pos = pos_rows[b]; pos_rows is not advanced.
-    Packed decode steps only (ring cache, T_new == T, T * Hq/Hkv <= 64, bf16); excludes pos / pos_dev / pos_min."""
-    _need_gpu(q, k_new, v_new, k_cache, v_cache, pos_dev, pos_rows)
+    Packed decode steps only (ring cache, T_new == T, T * Hq/Hkv <= 64, bf16); excludes pos / pos_dev / pos_min.
+    `frozen` (device int32 [B], with pos_rows only; ivl_swa_decode_rows_hold_fwd): a row with frozen[b] != 0 keeps its ring row
+    and its o rows are unspecified; the mask is read at replay."""
+    _need_gpu(q, k_new, v_new, k_cache, v_cache, pos_dev, pos_rows, frozen)
     if q.dtype != torch.bfloat16 or k_new.dtype != torch.bfloat16 or v_new.dtype != torch.bfloat16:
         raise ValueError("swa_forward is built for bf16")
     if layout == "bhtd":
@@ -1805,6 +1853,10 @@ def swa_forward(
                              f"(got T={T}, T_new={T_new}, Hq/Hkv={Hq // Hkv})")
         if mma_code(mma_dtype) != IVL_BF16:
             raise ValueError("swa_forward: pos_rows runs in bf16 only (no fp8 decode step)")
+    if frozen is not None:
+        if pos_rows is None:
+            raise ValueError("swa_forward: frozen goes with pos_rows")
+        _check_frozen("swa_forward", frozen, B, q)
     if q.stride(-1) != 1:
         q = q.contiguous()
     if k_new.stride(-1) != 1 or v_new.stride() != k_new.stride():
@@ -1847,7 +1899,10 @@ def swa_forward(
     if rope is not None:
         cos, sin, sec = _rope_args(rope, B, T, d)
         a.rope_cos, a.rope_sin, a.rope_s0, a.rope_s1 = cos.data_ptr(), sin.data_ptr(), int(sec[0]), int(sec[1])
-    if pos_rows is not None:
+    if frozen is not None:
+        HOLD_CALLS["swa_forward"] += 1
+        _lib.check(lib.ivl_swa_decode_rows_hold_fwd(ctypes.byref(a), pos_rows.data_ptr(), frozen.data_ptr(), _stream(q)))
+    elif pos_rows is not None:
         _lib.check(lib.ivl_swa_decode_rows_fwd(ctypes.byref(a), pos_rows.data_ptr(), _stream(q)))
     else:
         _lib.check(lib.ivl_swa_fwd(ctypes.byref(a), _stream(q)))

@@ -123,6 +123,16 @@ operator alone on 4 rows of the model's vocabulary, with the group, with an all-
 without.  No bar is asserted: B - A is reported beside the 2 % of A that DESIGN 4.8 grants the sampling launch as a whole.
 
     python tools/multistream_decode.py --adjust [--out profiles/adjust_decode.json]
+
+--holds: the cost of the per-slot hold in the captured step, at 4 slots and at 16 slots (use_wide_decode on).
+Every leg draws greedily through a controlled sampler (vocabulary bitmap, 64-entry history, no stop id or budget: no row ends on
+its own).  A: a holds=False decoder, the step as it is without the option; B: holds=True, nothing frozen; C: holds=True, every
+second slot finished (done = 2); D: all but slot 0 finished.  Timed A B C D per round in one process, median of --rounds rounds
+of --steps replays.  Gate (asserted in the exit code): C and D are no slower than B beyond 2 % -- a frozen row may only remove
+work.  B against A is reported beside the project's 2 % allowance, not gated: in hold mode a GDN layer takes the one-launch
+step with the mask at every slot count.
+
+    python tools/multistream_decode.py --holds [--slots 4,16] [--out profiles/holds_decode.json]
 """
 import argparse
 import json
@@ -158,6 +168,8 @@ def main():
                     help="time per-slot adapters in the 8- and 16-slot step on the 16-row kernel, fused against composed (see above)")
     ap.add_argument("--adjust", action="store_true",
                     help="time the 4-slot controlled step with and without penalties, min-p and a logit-bias table (see above)")
+    ap.add_argument("--holds", action="store_true",
+                    help="time the step with the per-slot hold mask: off, on, half and all but one slot frozen (see above)")
     args = ap.parse_args()
     import torch
     from infinitevl_amd.cache import MultiStreamCache
@@ -184,6 +196,8 @@ def main():
                 _, lg = model(inputs_embeds=x[:, a:b], position_ids=pid, past_key_values=cache)
         return lg
 
+    if args.holds:
+        raise SystemExit(holds_legs(args, torch, model, cfg, prompts, dev))      # exit code 1: the gate failed
     if args.adjust:
         return adjust_legs(args, torch, model, cfg, prompts, dev)
     if args.sampling:
@@ -1072,6 +1086,74 @@ def wide_legs(args, torch, model, cfg, prompts, dev):
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
             f.write(line + "\n")
+
+
+def holds_legs(args, torch, model, cfg, prompts, dev):
+    """A B C D per round in one process (see the module docstring).  Returns 1 when C or D is slower than B beyond 2 %."""
+    from infinitevl_amd import ops
+    from infinitevl_amd.cache import MultiStreamCache
+    from infinitevl_amd.harness import GraphedMultiStreamDecode, Sampler
+    stream = torch.cuda.current_stream()
+    V = cfg.vocab_size
+
+    def timed(fn, n):
+        for _ in range(4):
+            fn()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        for _ in range(n):
+            fn()
+        e1.record(stream)
+        e1.synchronize()
+        return e0.elapsed_time(e1) / n
+
+    def decoder(n, holds, finished):
+        smp = Sampler(n, dev, vocab_size=V, history=64)
+        dec = GraphedMultiStreamDecode(model, MultiStreamCache(config=cfg, n_slots=n, device=dev, dtype=torch.bfloat16), sampler=smp,
+                                       **({"holds": True} if holds else {}))
+        for s in range(n):
+            dec.admit(s, prompts[s % len(prompts)])
+        dec.capture()
+        for s in finished:
+            smp.done[s] = 2
+        return dec
+
+    slots = [int(s) for s in args.slots.split(",")] if args.slots != "1,2,4" else [4, 16]
+    res = {"tool": "multistream_decode --holds", "layers": cfg.num_hidden_layers, "window": 4096, "steps": args.steps, "rounds": args.rounds,
+           "legs": "A = holds=False; B = holds=True, nothing frozen; C = holds=True, every second slot finished; D = holds=True, all but "
+                   "slot 0 finished (use_wide_decode on above 4 slots)",
+           "gate": "C and D ms_per_step <= 1.02 x B", "report_only": "B over A, beside the 2 % allowance"}
+    ok = True
+    for n in slots:
+        model.use_wide_decode(n > 4)
+        before = dict(ops.HOLD_CALLS)
+        decs = {"A": decoder(n, False, []), "B": decoder(n, True, []), "C": decoder(n, True, list(range(1, n, 2))),
+                "D": decoder(n, True, list(range(1, n)))}
+        assert all(ops.HOLD_CALLS[k] > before[k] for k in before)
+        times = {k: [] for k in decs}
+        for _ in range(args.rounds):
+            for name, dec in decs.items():
+                times[name].append(timed(dec.step, args.steps))
+        med = {k: statistics.median(v) for k, v in times.items()}
+        cell = {k: {"ms_per_step": round(v, 4), "spread_ms": [round(min(times[k]), 4), round(max(times[k]), 4)]} for k, v in med.items()}
+        for name, want in (("A", [0] * n), ("B", [0] * n), ("C", [0, 2] * (n // 2)), ("D", [0] + [2] * (n - 1))):
+            assert decs[name].sampler.poll()[0].tolist() == want, (name, "a row ended on its own")
+        cell.update(B_over_A=round(med["B"] / med["A"], 4), B_minus_A_us=round(1000 * (med["B"] - med["A"]), 1),
+                    allowance_us=round(1000 * 0.02 * med["A"], 1), B_within_allowance=bool(med["B"] <= 1.02 * med["A"]),
+                    C_over_B=round(med["C"] / med["B"], 4), D_over_B=round(med["D"] / med["B"], 4),
+                    gate_passed=bool(med["C"] <= 1.02 * med["B"] and med["D"] <= 1.02 * med["B"]))
+        ok = ok and cell["gate_passed"]
+        res[f"slots{n}"] = cell
+        print(f"slots{n}: " + " ".join(f"{k} {v:.4f}" for k, v in med.items()) + " ms", file=sys.stderr, flush=True)
+        del decs
+    model.use_wide_decode(False)
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+    return 0 if ok else 1
 
 
 LORA_RANK = 16
