@@ -15,6 +15,9 @@ struct W16Bf16 {                                   // bf16 [R,K]: four 16-byte p
   struct row { unsigned int off; };
   struct raw { u32x4 p[4]; };
   static bool null(arg w) { return w == nullptr; }
+  static size_t row_bytes(int K) { return (size_t)K * 2; }
+  static bool aligned(arg w) { return ((size_t)w & 15) == 0; }
+  static const char* misaligned() { return "%s: x / w / y must be 16-byte aligned"; }
   static __device__ __forceinline__ row open(arg, int r, int K) { return row{(unsigned int)r * (unsigned int)K * 2u}; }
   static __device__ __forceinline__ void load(arg w, row rw, int t, int j, int g, int nchunk, raw& o) {
 #pragma unroll
@@ -32,6 +35,9 @@ struct W16E4m3 {                                   // e4m3fn codes [R,K] + one f
   struct row { unsigned int off; float scale; };
   struct raw { u32x2 p[4]; };
   static bool null(arg w) { return w.q == nullptr || w.scale == nullptr; }
+  static size_t row_bytes(int K) { return (size_t)K; }
+  static bool aligned(arg w) { return ((size_t)w.q & 15) == 0 && ((size_t)w.scale & 3) == 0; }
+  static const char* misaligned() { return "%s: x / wq / y must be 16-byte aligned, scale 4-byte aligned"; }
   static __device__ __forceinline__ row open(arg w, int r, int K) { return row{(unsigned int)r * (unsigned int)K, w.scale[r]}; }
   static __device__ __forceinline__ void load(arg w, row rw, int t, int j, int g, int nchunk, raw& o) {
 #pragma unroll
@@ -58,6 +64,9 @@ struct W16Mxfp4 {                                  // the shuffled MXFP4 layout 
   struct raw { u32x4 q; unsigned int s; };
   static bool null(arg w) { return w.q == nullptr || w.s == nullptr; }
   static __host__ __device__ __forceinline__ int kp(int K) { return (K + 2047) & ~2047; }        // a row is whole tiles of 2048 weights
+  static size_t row_bytes(int K) { return (size_t)(kp(K) >> 1); }
+  static bool aligned(arg w) { return ((size_t)w.q & 15) == 0 && ((size_t)w.s & 3) == 0; }
+  static const char* misaligned() { return "%s: x / wq / y must be 16-byte aligned, sq 4-byte aligned"; }
   static __device__ __forceinline__ row open(arg, int r, int K) {
     return row{(unsigned int)r * (unsigned int)(kp(K) >> 1), (unsigned int)r * (unsigned int)(kp(K) >> 5)};
   }
@@ -84,10 +93,13 @@ static __host__ __device__ __forceinline__ int m16_steps(int K) {
   return 16 * (T - 1) + (sl < 16 ? sl : 16);
 }
 
-// every refusal, before anything is launched; max_rows: 16, or the 64 of linear_m64.hip; row_bytes: the bytes of a (padded) weight row in the format at hand
-template <class WT>
-static int m16_check(const char* who, const void* x, typename WT::arg wp, const void* y, int M, int N, int K, int glu, size_t row_bytes,
-                     int max_rows = 16) {
+// An entry point of either kernel, whatever the format: every refusal in ONE order and before anything is launched -- NULL, the rows
+// (max_rows: 16, or the 64 of linear_m64.hip), N, K, the 32-bit offsets, the alignment that the format asks -- then launch(): the
+// kernel's launch, behind the LoRA refusals and the shrink launch where the entry has an adapter.  What differs between the formats
+// is the policy's: null(), row_bytes(K) (the bytes of a padded weight row), aligned() and the text of misaligned().
+template <class WT, class Launch>
+static int m16_entry(const char* who, const void* x, typename WT::arg wp, const void* bias, const void* y, int M, int N, int K, int glu,
+                     int max_rows, Launch launch) {
   IVL_REQUIRE(x && !WT::null(wp) && y, IVL_ERR_INVALID_ARG, "%s: NULL pointer", who);
   IVL_REQUIRE(M >= 1 && M <= max_rows, IVL_ERR_UNSUPPORTED, "%s: M=%d (built for 1..%d rows)", who, M, max_rows);
   IVL_REQUIRE(N >= 1, IVL_ERR_INVALID_ARG, "%s: N=%d", who, N);
@@ -95,9 +107,10 @@ static int m16_check(const char* who, const void* x, typename WT::arg wp, const 
   const long long R = (long long)(glu ? 2 : 1) * N;
   // every weight offset is a 32-bit byte offset from the base: ONE bound for the three formats (the plan is theirs in common), and the
   // padded rows of the format at hand
-  IVL_REQUIRE(R * K * 2 < (1ll << 32) && R * (long long)row_bytes < (1ll << 32), IVL_ERR_UNSUPPORTED,
+  IVL_REQUIRE(R * K * 2 < (1ll << 32) && R * (long long)WT::row_bytes(K) < (1ll << 32), IVL_ERR_UNSUPPORTED,
               "%s: weight of %lld x %d does not fit 32-bit offsets", who, R, K);
-  return IVL_OK;
+  IVL_REQUIRE((((size_t)x | (size_t)y) & 15) == 0 && ((size_t)bias & 1) == 0 && WT::aligned(wp), IVL_ERR_INVALID_ARG, WT::misaligned(), who);
+  return launch();
 }
 
 }  // namespace ivl

@@ -218,79 +218,57 @@ static int m16_lora_shrink(const char* who, const ivl_lora_args* lora, void* str
   return check_launch(who);
 }
 
+// the entries of a format: name, policy, weight argument; the LORA forms also name their shrink launch
+template <class WT>
+static int m16_fwd(const char* who, const void* x, typename WT::arg wp, const void* bias, void* y, int M, int N, int K, int glu,
+                   void* stream) {
+  return m16_entry<WT>(who, x, wp, bias, y, M, N, K, glu, 16, [&] { return m16_launch<WT>(x, wp, bias, y, M, N, K, glu, stream, who); });
+}
+
+template <class WT>
+static int m16_lora_fwd(const char* who, const char* shrink, const void* x, typename WT::arg wp, const void* bias, void* y, int M, int N,
+                        int K, int glu, const ivl_lora_args* lora, void* stream) {
+  return m16_entry<WT>(who, x, wp, bias, y, M, N, K, glu, 16, [&] {
+    M16Lora L;
+    int rc = m16_lora_check(who, lora, x, y, M, N, K, glu, L);
+    if (rc == IVL_OK) rc = m16_lora_shrink(shrink, lora, stream);
+    return rc != IVL_OK ? rc : m16_launch<WT>(x, wp, bias, y, M, N, K, glu, stream, who, L);
+  });
+}
+
 }  // namespace ivl
 
 using namespace ivl;
 
 extern "C" int ivl_linear_m16_fwd(const void* x, const void* w, const void* bias, void* y, int M, int N, int K, int glu, void* stream) {
-  const char* who = "ivl_linear_m16_fwd";
-  const int rc = m16_check<W16Bf16>(who, x, (const bf16_t*)w, y, M, N, K, glu, (size_t)(K > 0 ? K : 0) * 2);
-  if (rc) return rc;
-  IVL_REQUIRE((((size_t)x | (size_t)w | (size_t)y) & 15) == 0 && ((size_t)bias & 1) == 0, IVL_ERR_INVALID_ARG,
-              "%s: x / w / y must be 16-byte aligned", who);
-  return m16_launch<W16Bf16>(x, (const bf16_t*)w, bias, y, M, N, K, glu, stream, who);
+  return m16_fwd<W16Bf16>("ivl_linear_m16_fwd", x, (const bf16_t*)w, bias, y, M, N, K, glu, stream);
 }
 
 extern "C" int ivl_linear_m16_w8_fwd(const void* x, const void* wq, const float* scale, const void* bias, void* y, int M, int N, int K,
                                      int glu, void* stream) {
-  const char* who = "ivl_linear_m16_w8_fwd";
-  const W16Arg8 wp{(const unsigned char*)wq, scale};
-  const int rc = m16_check<W16E4m3>(who, x, wp, y, M, N, K, glu, (size_t)(K > 0 ? K : 0));
-  if (rc) return rc;
-  IVL_REQUIRE((((size_t)x | (size_t)wq | (size_t)y) & 15) == 0 && ((size_t)bias & 1) == 0 && ((size_t)scale & 3) == 0,
-              IVL_ERR_INVALID_ARG, "%s: x / wq / y must be 16-byte aligned, scale 4-byte aligned", who);
-  return m16_launch<W16E4m3>(x, wp, bias, y, M, N, K, glu, stream, who);
+  return m16_fwd<W16E4m3>("ivl_linear_m16_w8_fwd", x, {(const unsigned char*)wq, scale}, bias, y, M, N, K, glu, stream);
 }
 
 extern "C" int ivl_linear_m16_w4_fwd(const void* x, const void* wq, const void* sq, const void* bias, void* y, int M, int N, int K,
                                      int glu, void* stream) {
-  const char* who = "ivl_linear_m16_w4_fwd";
-  const W16Arg4 wp{(const unsigned char*)wq, (const unsigned char*)sq};
-  const int rc = m16_check<W16Mxfp4>(who, x, wp, y, M, N, K, glu, (size_t)(K > 0 ? W16Mxfp4::kp(K) >> 1 : 0));
-  if (rc) return rc;
-  IVL_REQUIRE((((size_t)x | (size_t)wq | (size_t)y) & 15) == 0 && ((size_t)bias & 1) == 0 && ((size_t)sq & 3) == 0,
-              IVL_ERR_INVALID_ARG, "%s: x / wq / y must be 16-byte aligned, sq 4-byte aligned", who);
-  return m16_launch<W16Mxfp4>(x, wp, bias, y, M, N, K, glu, stream, who);
+  return m16_fwd<W16Mxfp4>("ivl_linear_m16_w4_fwd", x, {(const unsigned char*)wq, (const unsigned char*)sq}, bias, y, M, N, K, glu, stream);
 }
 
 // ---- the LORA forms: the argument lists above plus the adapter tables; two launches (shrink, then the kernel with the LoRA epilogue)
 extern "C" int ivl_linear_m16_lora_fwd(const void* x, const void* w, const void* bias, void* y, int M, int N, int K, int glu,
                                        const ivl_lora_args* lora, void* stream) {
-  const char* who = "ivl_linear_m16_lora_fwd";
-  int rc = m16_check<W16Bf16>(who, x, (const bf16_t*)w, y, M, N, K, glu, (size_t)(K > 0 ? K : 0) * 2);
-  if (rc) return rc;
-  IVL_REQUIRE((((size_t)x | (size_t)w | (size_t)y) & 15) == 0 && ((size_t)bias & 1) == 0, IVL_ERR_INVALID_ARG,
-              "%s: x / w / y must be 16-byte aligned", who);
-  M16Lora L;
-  if ((rc = m16_lora_check(who, lora, x, y, M, N, K, glu, L)) != IVL_OK) return rc;
-  if ((rc = m16_lora_shrink("ivl_linear_m16_lora_fwd (shrink)", lora, stream)) != IVL_OK) return rc;
-  return m16_launch<W16Bf16>(x, (const bf16_t*)w, bias, y, M, N, K, glu, stream, who, L);
+  return m16_lora_fwd<W16Bf16>("ivl_linear_m16_lora_fwd", "ivl_linear_m16_lora_fwd (shrink)", x, (const bf16_t*)w, bias, y, M, N, K, glu,
+                               lora, stream);
 }
 
 extern "C" int ivl_linear_m16_lora_w8_fwd(const void* x, const void* wq, const float* scale, const void* bias, void* y, int M, int N,
                                           int K, int glu, const ivl_lora_args* lora, void* stream) {
-  const char* who = "ivl_linear_m16_lora_w8_fwd";
-  const W16Arg8 wp{(const unsigned char*)wq, scale};
-  int rc = m16_check<W16E4m3>(who, x, wp, y, M, N, K, glu, (size_t)(K > 0 ? K : 0));
-  if (rc) return rc;
-  IVL_REQUIRE((((size_t)x | (size_t)wq | (size_t)y) & 15) == 0 && ((size_t)bias & 1) == 0 && ((size_t)scale & 3) == 0,
-              IVL_ERR_INVALID_ARG, "%s: x / wq / y must be 16-byte aligned, scale 4-byte aligned", who);
-  M16Lora L;
-  if ((rc = m16_lora_check(who, lora, x, y, M, N, K, glu, L)) != IVL_OK) return rc;
-  if ((rc = m16_lora_shrink("ivl_linear_m16_lora_w8_fwd (shrink)", lora, stream)) != IVL_OK) return rc;
-  return m16_launch<W16E4m3>(x, wp, bias, y, M, N, K, glu, stream, who, L);
+  return m16_lora_fwd<W16E4m3>("ivl_linear_m16_lora_w8_fwd", "ivl_linear_m16_lora_w8_fwd (shrink)", x, {(const unsigned char*)wq, scale},
+                               bias, y, M, N, K, glu, lora, stream);
 }
 
 extern "C" int ivl_linear_m16_lora_w4_fwd(const void* x, const void* wq, const void* sq, const void* bias, void* y, int M, int N, int K,
                                           int glu, const ivl_lora_args* lora, void* stream) {
-  const char* who = "ivl_linear_m16_lora_w4_fwd";
-  const W16Arg4 wp{(const unsigned char*)wq, (const unsigned char*)sq};
-  int rc = m16_check<W16Mxfp4>(who, x, wp, y, M, N, K, glu, (size_t)(K > 0 ? W16Mxfp4::kp(K) >> 1 : 0));
-  if (rc) return rc;
-  IVL_REQUIRE((((size_t)x | (size_t)wq | (size_t)y) & 15) == 0 && ((size_t)bias & 1) == 0 && ((size_t)sq & 3) == 0,
-              IVL_ERR_INVALID_ARG, "%s: x / wq / y must be 16-byte aligned, sq 4-byte aligned", who);
-  M16Lora L;
-  if ((rc = m16_lora_check(who, lora, x, y, M, N, K, glu, L)) != IVL_OK) return rc;
-  if ((rc = m16_lora_shrink("ivl_linear_m16_lora_w4_fwd (shrink)", lora, stream)) != IVL_OK) return rc;
-  return m16_launch<W16Mxfp4>(x, wp, bias, y, M, N, K, glu, stream, who, L);
+  return m16_lora_fwd<W16Mxfp4>("ivl_linear_m16_lora_w4_fwd", "ivl_linear_m16_lora_w4_fwd (shrink)", x,
+                                {(const unsigned char*)wq, (const unsigned char*)sq}, bias, y, M, N, K, glu, lora, stream);
 }

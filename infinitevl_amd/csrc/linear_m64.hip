@@ -217,37 +217,27 @@ static int m64_launch(const void* x, typename WT::arg wp, const void* bias, void
   return check_launch(who);
 }
 
+template <class WT>
+static int m64_fwd(const char* who, const void* x, typename WT::arg wp, const void* bias, void* y, int M, int N, int K, int glu,
+                   void* stream) {
+  return m16_entry<WT>(who, x, wp, bias, y, M, N, K, glu, 16 * M64_XT,
+                       [&] { return m64_launch<WT>(x, wp, bias, y, M, N, K, glu, stream, who); });
+}
+
 }  // namespace ivl
 
 using namespace ivl;
 
 extern "C" int ivl_linear_m64_fwd(const void* x, const void* w, const void* bias, void* y, int M, int N, int K, int glu, void* stream) {
-  const char* who = "ivl_linear_m64_fwd";
-  const int rc = m16_check<W16Bf16>(who, x, (const bf16_t*)w, y, M, N, K, glu, (size_t)(K > 0 ? K : 0) * 2, 16 * M64_XT);
-  if (rc) return rc;
-  IVL_REQUIRE((((size_t)x | (size_t)w | (size_t)y) & 15) == 0 && ((size_t)bias & 1) == 0, IVL_ERR_INVALID_ARG,
-              "%s: x / w / y must be 16-byte aligned", who);
-  return m64_launch<W16Bf16>(x, (const bf16_t*)w, bias, y, M, N, K, glu, stream, who);
+  return m64_fwd<W16Bf16>("ivl_linear_m64_fwd", x, (const bf16_t*)w, bias, y, M, N, K, glu, stream);
 }
 
 extern "C" int ivl_linear_m64_w8_fwd(const void* x, const void* wq, const float* scale, const void* bias, void* y, int M, int N, int K,
                                      int glu, void* stream) {
-  const char* who = "ivl_linear_m64_w8_fwd";
-  const W16Arg8 wp{(const unsigned char*)wq, scale};
-  const int rc = m16_check<W16E4m3>(who, x, wp, y, M, N, K, glu, (size_t)(K > 0 ? K : 0), 16 * M64_XT);
-  if (rc) return rc;
-  IVL_REQUIRE((((size_t)x | (size_t)wq | (size_t)y) & 15) == 0 && ((size_t)bias & 1) == 0 && ((size_t)scale & 3) == 0,
-              IVL_ERR_INVALID_ARG, "%s: x / wq / y must be 16-byte aligned, scale 4-byte aligned", who);
-  return m64_launch<W16E4m3>(x, wp, bias, y, M, N, K, glu, stream, who);
+  return m64_fwd<W16E4m3>("ivl_linear_m64_w8_fwd", x, {(const unsigned char*)wq, scale}, bias, y, M, N, K, glu, stream);
 }
 
 extern "C" int ivl_linear_m64_w4_fwd(const void* x, const void* wq, const void* sq, const void* bias, void* y, int M, int N, int K,
                                      int glu, void* stream) {
-  const char* who = "ivl_linear_m64_w4_fwd";
-  const W16Arg4 wp{(const unsigned char*)wq, (const unsigned char*)sq};
-  const int rc = m16_check<W16Mxfp4>(who, x, wp, y, M, N, K, glu, (size_t)(K > 0 ? W16Mxfp4::kp(K) >> 1 : 0), 16 * M64_XT);
-  if (rc) return rc;
-  IVL_REQUIRE((((size_t)x | (size_t)wq | (size_t)y) & 15) == 0 && ((size_t)bias & 1) == 0 && ((size_t)sq & 3) == 0,
-              IVL_ERR_INVALID_ARG, "%s: x / wq / y must be 16-byte aligned, sq 4-byte aligned", who);
-  return m64_launch<W16Mxfp4>(x, wp, bias, y, M, N, K, glu, stream, who);
+  return m64_fwd<W16Mxfp4>("ivl_linear_m64_w4_fwd", x, {(const unsigned char*)wq, (const unsigned char*)sq}, bias, y, M, N, K, glu, stream);
 }

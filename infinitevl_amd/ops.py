@@ -868,18 +868,9 @@ def gdn_out_linear(o_raw: torch.Tensor, proj: torch.Tensor, col_g: int, col_q: i
     assert T == 1 and o_raw.is_contiguous() and weight.is_contiguous() and weight.dtype == torch.bfloat16
     y = torch.empty(B, 1, N, dtype=torch.bfloat16, device=o_raw.device)
     gate = proj.view(B, ld)[:, col_g:]
-    if w8 is not None:                                   # the e4m3 twin on the packed copy of `weight` (see `linear`)
-        w8.check(weight)
-        fn = _lib.load().ivl_gdn_out_linear_small_m_w4_fwd if w8.fmt == "mxfp4" else _lib.load().ivl_gdn_out_linear_small_m_w8_fwd
-        _lib.check(fn(
-            _p(o_raw), ctypes.c_void_p(gate.data_ptr()), ld, _p(norm_weight), float(eps), H, _p(proj), ld, col_q, col_k,
-            _p(conv_state_q), _p(conv_state_k), _p(w8.codes), _p(w8.scale), _p(bias) if bias is not None else None, _p(y), B, N, K,
-            _stream(o_raw)))
-        w8.count("gdn_out_linear")
-        return y
-    _lib.check(_lib.load().ivl_gdn_out_linear_small_m_fwd(
-        _p(o_raw), ctypes.c_void_p(gate.data_ptr()), ld, _p(norm_weight), float(eps), H, _p(proj), ld, col_q, col_k,
-        _p(conv_state_q), _p(conv_state_k), _p(weight), _p(bias) if bias is not None else None, _p(y), B, N, K, _stream(o_raw)))
+    _weight_call("gdn_out_small_m", weight, w8,
+                 (_p(o_raw), ctypes.c_void_p(gate.data_ptr()), ld, _p(norm_weight), float(eps), H, _p(proj), ld, col_q, col_k,
+                  _p(conv_state_q), _p(conv_state_k)), (_p(bias), _p(y), B, N, K, _stream(o_raw)), entry="gdn_out_linear")
     return y
 
 
@@ -1174,11 +1165,42 @@ def w8_kwargs(packed: Optional[PackedWeight], on: bool) -> dict:
     return {"w8": packed} if on and packed is not None else {}
 
 
+# ---- projection dispatch: every projection entry point, by kernel family and weight format.  The names are literal: a
+# grep for a symbol finds this table, and the table names the one caller of the family.
+ENTRY_POINTS = {
+    "small_m": {"bf16": "ivl_linear_small_m_fwd", "e4m3": "ivl_linear_small_m_w8_fwd", "mxfp4": "ivl_linear_small_m_w4_fwd"},
+    "swiglu_small_m": {"bf16": "ivl_linear_swiglu_small_m_fwd", "e4m3": "ivl_linear_swiglu_small_m_w8_fwd",
+                       "mxfp4": "ivl_linear_swiglu_small_m_w4_fwd"},
+    "norm_small_m": {"bf16": "ivl_norm_linear_small_m_fwd", "e4m3": "ivl_norm_linear_small_m_w8_fwd",
+                     "mxfp4": "ivl_norm_linear_small_m_w4_fwd"},
+    "gdn_out_small_m": {"bf16": "ivl_gdn_out_linear_small_m_fwd", "e4m3": "ivl_gdn_out_linear_small_m_w8_fwd",
+                        "mxfp4": "ivl_gdn_out_linear_small_m_w4_fwd"},
+    "m16": {"bf16": "ivl_linear_m16_fwd", "e4m3": "ivl_linear_m16_w8_fwd", "mxfp4": "ivl_linear_m16_w4_fwd"},
+    "m64": {"bf16": "ivl_linear_m64_fwd", "e4m3": "ivl_linear_m64_w8_fwd", "mxfp4": "ivl_linear_m64_w4_fwd"},
+    "m16_lora": {"bf16": "ivl_linear_m16_lora_fwd", "e4m3": "ivl_linear_m16_lora_w8_fwd", "mxfp4": "ivl_linear_m16_lora_w4_fwd"},
+}
+
+
+def _weight_call(family: str, weight: torch.Tensor, w8: Optional[PackedWeight], lead: tuple, tail: tuple, *, entry: Optional[str] = None,
+                 calls: Optional[dict] = None) -> None:
+    """One launch of `family` on `weight` -- or, with w8, on its packed copy through the twin of its format (the same bits): the entry
+    point's arguments are `lead`, the weight's (w, or codes and scale), `tail`.  Counts the call once it was accepted: a packed one
+    under `entry` in W8_CALLS / W4_CALLS, any one under its format in `calls` (M16_CALLS / M64_CALLS)."""
+    if w8 is None:
+        fmt, w = "bf16", (_p(weight),)
+    else:
+        fmt, w = w8.check(weight).fmt, (_p(w8.codes), _p(w8.scale))
+    _lib.check(getattr(_lib.load(), ENTRY_POINTS[family][fmt])(*lead, *w, *tail))
+    if entry is not None and w8 is not None:
+        w8.count(entry)
+    if calls is not None:
+        calls[fmt] += 1
+
+
 def _prenorm_linear(pn: "PreNorm", weight: torch.Tensor, bias: Optional[torch.Tensor], glu: bool,
                     w8: Optional[PackedWeight] = None) -> Optional[torch.Tensor]:
-    """The fused launch when it applies (decode step, bf16, K <= 4096), else None.  w8: the e4m3 twin on the packed copy."""
-    if w8 is not None:
-        w8.check(weight)
+    """The fused launch when it applies (decode step, bf16, K <= 4096), else None.  w8: the packed twin on the packed copy (the
+    ladder has checked it against the weight)."""
     K = weight.shape[-1]
     rows = pn.numel() // K if K else 0
     if not (pn.is_cuda and 1 <= rows <= 4 and pn.dtype == torch.bfloat16 and weight.dtype == torch.bfloat16 and weight.dim() == 2
@@ -1187,17 +1209,9 @@ def _prenorm_linear(pn: "PreNorm", weight: torch.Tensor, bias: Optional[torch.Te
         return None
     N = weight.shape[0] // 2 if glu else weight.shape[0]
     y = torch.empty(*pn.shape[:-1], N, dtype=torch.bfloat16, device=pn.device)
-    if w8 is not None:
-        fn = _lib.load().ivl_norm_linear_small_m_w4_fwd if w8.fmt == "mxfp4" else _lib.load().ivl_norm_linear_small_m_w8_fwd
-        _lib.check(fn(
-            _p(pn.x), _p(pn.residual), _p(pn.weight), pn.eps, _p(pn.h) if pn.residual is not None else None,
-            _p(w8.codes), _p(w8.scale), _p(bias) if bias is not None else None, _p(y), rows, N, K, 1 if glu else 0, _stream(pn.x)))
-        w8.count("norm_linear")
-        pn.done = True
-        return y
-    _lib.check(_lib.load().ivl_norm_linear_small_m_fwd(
-        _p(pn.x), _p(pn.residual), _p(pn.weight), pn.eps, _p(pn.h) if pn.residual is not None else None,
-        _p(weight), _p(bias) if bias is not None else None, _p(y), rows, N, K, 1 if glu else 0, _stream(pn.x)))
+    _weight_call("norm_small_m", weight, w8,
+                 (_p(pn.x), _p(pn.residual), _p(pn.weight), pn.eps, _p(pn.h) if pn.residual is not None else None),
+                 (_p(bias), _p(y), rows, N, K, 1 if glu else 0, _stream(pn.x)), entry="norm_linear")
     pn.done = True
     return y
 
@@ -1255,6 +1269,28 @@ def _m16_applies(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Ten
             and weight.data_ptr() % 16 == 0 and (not x.is_contiguous() or x.data_ptr() % 16 == 0) and (bias is None or (bias.dtype == torch.bfloat16 and bias.is_contiguous())))
 
 
+def _linear_rows(who: str, family: str, calls: dict, x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], glu: bool,
+                 w8: Optional[PackedWeight]) -> torch.Tensor:
+    """the body of linear_m16 / linear_m64.  The rows are not checked here: the ABI's refusal is what raises."""
+    _need_gpu(x, weight)
+    if w8 is not None:
+        w8.check(weight)
+    if x.dtype != torch.bfloat16 or weight.dtype != torch.bfloat16 or weight.dim() != 2 or not weight.is_contiguous():
+        raise ValueError(f"{who}: bf16 x and a contiguous bf16 [N,K] weight are expected; got {x.dtype}, {weight.dtype} "
+                         f"{tuple(weight.shape)}")
+    if bias is not None and (bias.dtype != torch.bfloat16 or not bias.is_contiguous()):
+        raise ValueError(f"{who}: a contiguous bf16 bias is expected")
+    R, K = weight.shape
+    if x.shape[-1] != K or (glu and R % 2):
+        raise ValueError(f"{who}: x {tuple(x.shape)} does not meet a weight {tuple(weight.shape)} (glu={glu})")
+    N = R // 2 if glu else R
+    rows = x.numel() // K if K else 0
+    xc = x if x.is_contiguous() else x.contiguous()
+    y = torch.empty(*x.shape[:-1], N, dtype=torch.bfloat16, device=x.device)
+    _weight_call(family, weight, w8, (_p(xc),), (_p(bias), _p(y), rows, N, K, 1 if glu else 0, _stream(x)), calls=calls)
+    return y
+
+
 def linear_m16(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, *, glu: bool = False,
                w8: Optional[PackedWeight] = None) -> torch.Tensor:
     """y = x W^T (+ bias) for 1..16 rows of x on the MFMA weight-stream kernel ivl_linear_m16_fwd; glu=True: `weight` is the fused
@@ -1262,30 +1298,7 @@ def linear_m16(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tenso
     format streams it in place of the bf16 weight, the same bits.  The direct entry: the shape rules are the ABI's (1 <= rows <= 16,
     K % 32 == 0, 16-byte aligned), and a call that breaks them raises; ops.linear / linear_swiglu take this kernel for 5..16 rows
     under InfiniteVLTextStack.use_wide_decode()."""
-    _need_gpu(x, weight)
-    if w8 is not None:
-        w8.check(weight)
-    if x.dtype != torch.bfloat16 or weight.dtype != torch.bfloat16 or weight.dim() != 2 or not weight.is_contiguous():
-        raise ValueError(f"linear_m16: bf16 x and a contiguous bf16 [N,K] weight are expected; got {x.dtype}, {weight.dtype} "
-                         f"{tuple(weight.shape)}")
-    if bias is not None and (bias.dtype != torch.bfloat16 or not bias.is_contiguous()):
-        raise ValueError("linear_m16: a contiguous bf16 bias is expected")
-    R, K = weight.shape
-    if x.shape[-1] != K or (glu and R % 2):
-        raise ValueError(f"linear_m16: x {tuple(x.shape)} does not meet a weight {tuple(weight.shape)} (glu={glu})")
-    N = R // 2 if glu else R
-    rows = x.numel() // K if K else 0
-    xc = x if x.is_contiguous() else x.contiguous()
-    y = torch.empty(*x.shape[:-1], N, dtype=torch.bfloat16, device=x.device)
-    lib, bp = _lib.load(), _p(bias) if bias is not None else None
-    if w8 is not None:
-        fn = lib.ivl_linear_m16_w4_fwd if w8.fmt == "mxfp4" else lib.ivl_linear_m16_w8_fwd
-        _lib.check(fn(_p(xc), _p(w8.codes), _p(w8.scale), bp, _p(y), rows, N, K, 1 if glu else 0, _stream(x)))
-        M16_CALLS[w8.fmt] += 1
-        return y
-    _lib.check(lib.ivl_linear_m16_fwd(_p(xc), _p(weight), bp, _p(y), rows, N, K, 1 if glu else 0, _stream(x)))
-    M16_CALLS["bf16"] += 1
-    return y
+    return _linear_rows("linear_m16", "m16", M16_CALLS, x, weight, bias, glu, w8)
 
 
 # ---- 64-row weight-stream projections for decode steps of 17 to 63 slots (DESIGN 4.18) -----------------------------------------------
@@ -1300,30 +1313,7 @@ def linear_m64(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tenso
     row m of the result is bit for bit linear_m16 on that row alone (contract C2 of include/ivl_hip.h).  The direct entry: the shape
     rules are the ABI's (1 <= rows <= 64, K % 32 == 0, 16-byte aligned), and a call that breaks them raises; ops.linear /
     linear_swiglu take this kernel for 17..max_rows rows under InfiniteVLTextStack.use_wide_decode(max_rows=)."""
-    _need_gpu(x, weight)
-    if w8 is not None:
-        w8.check(weight)
-    if x.dtype != torch.bfloat16 or weight.dtype != torch.bfloat16 or weight.dim() != 2 or not weight.is_contiguous():
-        raise ValueError(f"linear_m64: bf16 x and a contiguous bf16 [N,K] weight are expected; got {x.dtype}, {weight.dtype} "
-                         f"{tuple(weight.shape)}")
-    if bias is not None and (bias.dtype != torch.bfloat16 or not bias.is_contiguous()):
-        raise ValueError("linear_m64: a contiguous bf16 bias is expected")
-    R, K = weight.shape
-    if x.shape[-1] != K or (glu and R % 2):
-        raise ValueError(f"linear_m64: x {tuple(x.shape)} does not meet a weight {tuple(weight.shape)} (glu={glu})")
-    N = R // 2 if glu else R
-    rows = x.numel() // K if K else 0
-    xc = x if x.is_contiguous() else x.contiguous()
-    y = torch.empty(*x.shape[:-1], N, dtype=torch.bfloat16, device=x.device)
-    lib, bp = _lib.load(), _p(bias) if bias is not None else None
-    if w8 is not None:
-        fn = lib.ivl_linear_m64_w4_fwd if w8.fmt == "mxfp4" else lib.ivl_linear_m64_w8_fwd
-        _lib.check(fn(_p(xc), _p(w8.codes), _p(w8.scale), bp, _p(y), rows, N, K, 1 if glu else 0, _stream(x)))
-        M64_CALLS[w8.fmt] += 1
-        return y
-    _lib.check(lib.ivl_linear_m64_fwd(_p(xc), _p(weight), bp, _p(y), rows, N, K, 1 if glu else 0, _stream(x)))
-    M64_CALLS["bf16"] += 1
-    return y
+    return _linear_rows("linear_m64", "m64", M64_CALLS, x, weight, bias, glu, w8)
 
 
 # the adapter of a 5..16-row call under use_wide_decode(adapters=True): True = in the epilogue of the base launch
@@ -1350,8 +1340,6 @@ def _linear_wide_lora(x, weight: torch.Tensor, bias: Optional[torch.Tensor], w8:
         x = x.materialize()
     if glu and weight.shape[0] % 2:
         return None
-    if w8 is not None:
-        w8.check(weight)
     p = table.proj.get(key)
     fused = (_LORA_FUSED and p is not None and p.N == weight.shape[0] and p.K == K and _m16_applies(x, weight, bias, rows, K))
     if not fused:
@@ -1366,113 +1354,78 @@ def _linear_wide_lora(x, weight: torch.Tensor, bias: Optional[torch.Tensor], w8:
     y = torch.empty(*shape[:-1], N, dtype=torch.bfloat16, device=x.device)
     idx = _lora_rows(table, rows_idx, rows)
     a = _lora_args(table, p, xc, y, idx, rows, p.t_ws16)
-    lib, bp, g = _lib.load(), _p(bias) if bias is not None else None, 1 if glu else 0
-    if w8 is not None:
-        fn = lib.ivl_linear_m16_lora_w4_fwd if w8.fmt == "mxfp4" else lib.ivl_linear_m16_lora_w8_fwd
-        _lib.check(fn(_p(xc), _p(w8.codes), _p(w8.scale), bp, _p(y), rows, N, K, g, ctypes.byref(a), _stream(x)))
-        M16_CALLS[w8.fmt] += 1
-    else:
-        _lib.check(lib.ivl_linear_m16_lora_fwd(_p(xc), _p(weight), bp, _p(y), rows, N, K, g, ctypes.byref(a), _stream(x)))
-        M16_CALLS["bf16"] += 1
+    _weight_call("m16_lora", weight, w8, (_p(xc),), (_p(bias), _p(y), rows, N, K, 1 if glu else 0, ctypes.byref(a), _stream(x)),
+                 calls=M16_CALLS)
     LORA_CALLS["m16_fused"] += 1
     return y
 
 
-def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, w8: Optional[PackedWeight] = None,
-           lora=None, wide: bool = False, wide_lora: bool = False, wide_rows: int = M16_ROWS) -> torch.Tensor:
-    """nn.Linear forward.  A single-token decode step (<= 4 rows) is a pure weight stream and goes through
-    ivl_linear_small_m_fwd; longer calls are stock library GEMMs (hipBLASLt / rocBLAS through torch), which
-    SURVEY.md 8(d) keeps outside the hot path.  w8: the packed copy of `weight` (which then holds W'), e4m3 or mxfp4 -- the call
-    dispatches on its format: the weight stream reads it in place of the bf16 weight -- the same bits, a half or a quarter of the
-    bytes; every other path reads `weight` as ever.  lora: (LoraTable, key, rows) -- the base call as without it, then lora_add on
-    its output (the NORM form reads the PreNorm's x / residual).  wide: the model's use_wide_decode() switch -- a call of 5..16 rows
-    that meets the shape rules of ivl_linear_m16_fwd takes that kernel (with w8: the packed twin) instead of the library GEMM; calls
-    with a lora table do so only with wide_lora (use_wide_decode(adapters=True)): then the adapter follows the base call as
-    lora_add(wide=True) (ivl_lora_add_m16_fwd) or, with _LORA_FUSED on, rides in the base kernel's epilogue
-    (ivl_linear_m16_lora*_fwd) -- the same bits.  wide_rows: use_wide_decode(max_rows=) -- with wide, a call of 17..wide_rows rows
-    without a lora table takes ivl_linear_m64_fwd (with w8: the packed twin) on the same shape rules; a call of more than 16 rows
-    under a lora table keeps the library path in every setting."""
+def _project(x, weight: torch.Tensor, bias: Optional[torch.Tensor], glu: bool, w8: Optional[PackedWeight], lora, wide: bool,
+             wide_lora: bool, wide_rows: int) -> torch.Tensor:
+    """THE ladder of linear (glu False) and linear_swiglu (glu True: `weight` is the fused gate|up weight, bias None): the routes in
+    the order in which they are tried, each with its predicate -- the table of DESIGN 4.21, which tests/test_gpu_routes.py pins."""
     if lora is not None:
+        # an adapter table: the 5..16-row forms under wide + wide_lora; else the base call WITHOUT the wide flags (so 5..16 rows take
+        # the library path), the adapter on the plain projection, and the gate behind it (linear + ivl_silu_mul_fwd == the GLU forms
+        # bit for bit, so rows without an adapter keep their bits)
         if wide and wide_lora:
-            y = _linear_wide_lora(x, weight, bias, w8, lora, False)
+            y = _linear_wide_lora(x, weight, bias, w8, lora, glu)
             if y is not None:
                 return y
         y = linear(x, weight, bias, w8=w8)
-        return lora_add(y if y.is_contiguous() else y.contiguous(), x, *lora)
+        y = lora_add(y if y.is_contiguous() else y.contiguous(), x, *lora)
+        return silu_mul(y) if glu else y
     if w8 is not None:
         w8.check(weight)
-    if isinstance(x, PreNorm):
-        y = _prenorm_linear(x, weight, bias, False, w8)
+    if isinstance(x, PreNorm):               # the fused norm launch first; else the norm runs once, here
+        y = _prenorm_linear(x, weight, bias, glu, w8)
         if y is not None:
             return y
         x = x.materialize()
-    K = weight.shape[-1]
+    R, K = weight.shape[0], weight.shape[-1]
+    N = R // 2 if glu else R
     rows = x.numel() // K if K else 0
-    if (x.is_cuda and 1 <= rows <= 4 and x.dtype == torch.bfloat16 and weight.dtype == torch.bfloat16
-            and weight.dim() == 2 and weight.is_contiguous() and K % 8 == 0
-            and (bias is None or (bias.dtype == torch.bfloat16 and bias.is_contiguous()))):
+    # small-M: the plain form passes a bias and asks a 2-D weight and a contiguous bf16 bias; the GLU form passes none and asks neither
+    if (x.is_cuda and 1 <= rows <= 4 and x.dtype == torch.bfloat16 and weight.dtype == torch.bfloat16 and weight.is_contiguous()
+            and K % 8 == 0 and (glu or (weight.dim() == 2 and (bias is None or (bias.dtype == torch.bfloat16 and bias.is_contiguous()))))):
         xc = x if x.is_contiguous() else x.contiguous()
-        N = weight.shape[0]
         y = torch.empty(*x.shape[:-1], N, dtype=torch.bfloat16, device=x.device)
-        if w8 is not None:
-            fn = _lib.load().ivl_linear_small_m_w4_fwd if w8.fmt == "mxfp4" else _lib.load().ivl_linear_small_m_w8_fwd
-            _lib.check(fn(_p(xc), _p(w8.codes), _p(w8.scale), _p(bias) if bias is not None else None, _p(y), rows, N, K, _stream(x)))
-            w8.count("linear")
-            return y
-        _lib.check(_lib.load().ivl_linear_small_m_fwd(_p(xc), _p(weight), _p(bias) if bias is not None else None,
-                                                      _p(y), rows, N, K, _stream(x)))
+        _weight_call("swiglu_small_m" if glu else "small_m", weight, w8, (_p(xc),), (_p(bias), _p(y), rows, N, K, _stream(x)),
+                     entry="linear_swiglu" if glu else "linear")
         return y
-    if wide and 4 < rows <= M16_ROWS and _m16_applies(x, weight, bias, rows, K):
-        return linear_m16(x, weight, bias, w8=w8)
-    if wide and M16_ROWS < rows <= min(wide_rows, M64_ROWS) and _m16_applies(x, weight, bias, rows, K):
-        return linear_m64(x, weight, bias, w8=w8)
-    return torch.nn.functional.linear(x, weight, bias)
+    if glu and _m256_swiglu_applies(x, weight, rows, N, K):        # GLU only (see _m256_swiglu_applies), in front of the wide routes
+        return _linear_swiglu_m256(x, weight, rows, N, K)
+    if (wide and 4 < rows <= max(M16_ROWS, min(wide_rows, M64_ROWS)) and not (glu and R % 2)
+            and _m16_applies(x, weight, bias, rows, K)):
+        return (linear_m16 if rows <= M16_ROWS else linear_m64)(x, weight, bias, glu=glu, w8=w8)
+    # the library GEMM (hipBLASLt / rocBLAS through torch), which SURVEY.md 8(d) keeps outside the hot path; the GLU form reaches it
+    # through linear() with neither w8 nor the wide flags
+    return silu_mul(linear(x, weight)) if glu else torch.nn.functional.linear(x, weight, bias)
+
+
+def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, w8: Optional[PackedWeight] = None,
+           lora=None, wide: bool = False, wide_lora: bool = False, wide_rows: int = M16_ROWS) -> torch.Tensor:
+    """nn.Linear forward.  Which kernel a call takes is the ladder of DESIGN 4.21 (_project): a decode step of <= 4 rows is a pure
+    weight stream (ivl_linear_small_m_fwd, or the fused norm launch for a PreNorm input); longer calls are library GEMMs unless the
+    model's use_wide_decode() switch is on.  w8: the packed copy of `weight` (which then holds W'), e4m3 or mxfp4 -- the weight
+    stream reads it in place of the bf16 weight through the twin of its format: the same bits, a half or a quarter of the bytes;
+    every other path reads `weight` as ever.  lora: (LoraTable, key, rows) -- the base call as without it, then lora_add on its
+    output (the NORM form reads the PreNorm's x / residual).  wide: use_wide_decode() -- a call of 5..16 rows that meets
+    _m16_applies takes ivl_linear_m16_fwd; with a lora table only under wide_lora (use_wide_decode(adapters=True)): the adapter
+    then follows as lora_add(wide=True) or, with _LORA_FUSED on, rides in the epilogue of ivl_linear_m16_lora*_fwd -- the same
+    bits.  wide_rows: use_wide_decode(max_rows=) -- a call of 17..wide_rows rows without a lora table takes ivl_linear_m64_fwd; more
+    than 16 rows under a lora table keep the library path in every setting."""
+    return _project(x, weight, bias, False, w8, lora, wide, wide_lora, wide_rows)
 
 
 def linear_swiglu(x: torch.Tensor, w_gate_up: torch.Tensor, w8: Optional[PackedWeight] = None, lora=None,
                   wide: bool = False, wide_lora: bool = False, wide_rows: int = M16_ROWS) -> torch.Tensor:
-    """silu(gate_proj(x)) * up_proj(x) with the fused gate|up weight [2I, K] (std:945).  Decode steps (<= 4 rows)
-    apply the gate in the epilogue of the weight-stream kernel, and so does the 256-row kernel of a prefill chunk
-    (ivl_linear_m256_fwd); other calls are a library GEMM + silu_mul.  w8: as in `linear`.  lora: (LoraTable, key, rows) with the
-    two segments gate | up -- the plain projection on the fused weight, lora_add, then silu_mul: the header guarantees linear +
-    ivl_silu_mul_fwd == the GLU forms bit for bit, so rows without an adapter keep their bits.  wide: as in `linear` (the
-    gate then runs in the epilogue of ivl_linear_m16_fwd; with wide_lora and a table: linear_m16 on the fused weight, lora_add,
-    silu_mul, or with _LORA_FUSED on the gate behind the adapter in the epilogue of ivl_linear_m16_lora*_fwd: no silu_mul launch).  wide_rows: as in `linear` (the gate in the epilogue of ivl_linear_m64_fwd)."""
-    if lora is not None:
-        if wide and wide_lora:
-            y = _linear_wide_lora(x, w_gate_up, None, w8, lora, True)
-            if y is not None:
-                return y
-        return silu_mul(linear(x, w_gate_up, w8=w8, lora=lora))
-    if w8 is not None:
-        w8.check(w_gate_up)
-    if isinstance(x, PreNorm):
-        y = _prenorm_linear(x, w_gate_up, None, True, w8)
-        if y is not None:
-            return y
-        x = x.materialize()
-    K = w_gate_up.shape[-1]
-    I = w_gate_up.shape[0] // 2
-    rows = x.numel() // K
-    if (x.is_cuda and 1 <= rows <= 4 and x.dtype == torch.bfloat16 and w_gate_up.dtype == torch.bfloat16
-            and w_gate_up.is_contiguous() and K % 8 == 0):
-        xc = x if x.is_contiguous() else x.contiguous()
-        y = torch.empty(*x.shape[:-1], I, dtype=torch.bfloat16, device=x.device)
-        if w8 is not None:
-            fn = _lib.load().ivl_linear_swiglu_small_m_w4_fwd if w8.fmt == "mxfp4" else _lib.load().ivl_linear_swiglu_small_m_w8_fwd
-            _lib.check(fn(_p(xc), _p(w8.codes), _p(w8.scale), None, _p(y), rows, I, K, _stream(x)))
-            w8.count("linear_swiglu")
-            return y
-        _lib.check(_lib.load().ivl_linear_swiglu_small_m_fwd(_p(xc), _p(w_gate_up), None, _p(y), rows, I, K, _stream(x)))
-        return y
-    if _m256_swiglu_applies(x, w_gate_up, rows, I, K):
-        return _linear_swiglu_m256(x, w_gate_up, rows, I, K)
-    if wide and 4 < rows <= M16_ROWS and w_gate_up.shape[0] % 2 == 0 and _m16_applies(x, w_gate_up, None, rows, K):
-        return linear_m16(x, w_gate_up, glu=True, w8=w8)
-    if (wide and M16_ROWS < rows <= min(wide_rows, M64_ROWS) and w_gate_up.shape[0] % 2 == 0
-            and _m16_applies(x, w_gate_up, None, rows, K)):
-        return linear_m64(x, w_gate_up, glu=True, w8=w8)
-    return silu_mul(linear(x, w_gate_up))
+    """silu(gate_proj(x)) * up_proj(x) with the fused gate|up weight [2I, K] (std:945), on the same ladder as `linear` (DESIGN
+    4.21) with the same arguments: the gate runs in the epilogue of the small-M, 16-row and 64-row kernels and of the 256-row kernel
+    of a prefill chunk (ivl_linear_m256_fwd); other calls are a library GEMM + silu_mul.  lora: the table's projection has the two
+    segments gate | up; the adapter is added to the plain projection on the fused weight and the gate follows (silu_mul, or with
+    _LORA_FUSED on the epilogue of ivl_linear_m16_lora*_fwd: no silu_mul launch)."""
+    return _project(x, w_gate_up, None, True, w8, lora, wide, wide_lora, wide_rows)
 
 
 # ---- per-row LoRA adapters over frozen (bf16 or packed) weights, unmerged (DESIGN 4.15) ---------------------------------------------

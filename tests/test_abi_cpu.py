@@ -61,6 +61,30 @@ def test_dynamic_symbol_table_is_exactly_the_header():
     assert "getenv" not in src, "no environment knobs on the launch path"
 
 
+def test_projection_entry_table_is_sound():
+    """ops.ENTRY_POINTS (family x weight format -> symbol): every name is declared, a packed twin has its family's bf16 prototype with
+    the one weight pointer replaced by two (codes, scale), and every exported projection symbol is in the table exactly once."""
+    from ctypes import c_void_p
+    from infinitevl_amd import _lib, ops
+    assert set(ops.ENTRY_POINTS) == {"small_m", "swiglu_small_m", "norm_small_m", "gdn_out_small_m", "m16", "m64", "m16_lora"}
+    names = []
+    for family, by_fmt in ops.ENTRY_POINTS.items():
+        assert tuple(by_fmt) == ("bf16",) + tuple(ops.PACKED_FORMATS), family
+        names += by_fmt.values()
+        assert all(n in _lib.PROTOTYPES for n in by_fmt.values()), (family, by_fmt)
+        ret, args = _lib.PROTOTYPES[by_fmt["bf16"]]
+        twins = {(ret, tuple(args[:i]) + (c_void_p, c_void_p) + tuple(args[i + 1:])) for i, a in enumerate(args) if a is c_void_p}
+        for fmt in ops.PACKED_FORMATS:
+            r, a = _lib.PROTOTYPES[by_fmt[fmt]]
+            assert (r, tuple(a)) in twins, (family, fmt, a, args)
+    assert len(names) == len(set(names)) == 21
+    exported = {n for n in _lib.PROTOTYPES if re.fullmatch(r"ivl_\w*linear\w*", n) and "m256" not in n and "logprob" not in n}
+    assert exported == set(names), exported ^ set(names)
+    src = open(os.path.join(ROOT, "infinitevl_amd", "ops.py")).read()
+    for n in names:
+        assert src.count(f'"{n}"') == 1 and src.count(n + "(") == 0, f"{n}: named in the table, called through it"
+
+
 def test_argument_validation_returns_codes(lib):
     from infinitevl_amd import _lib
     rc = lib.ivl_short_conv_fwd(None, None, None, None, None, 1, 1, 8, 4, 1, None)

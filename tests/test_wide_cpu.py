@@ -82,6 +82,31 @@ def test_refusals_come_before_any_launch(lib):
     assert w4_(p, p, p, None, p, 5, 1 << 22, 32, 0, None) == UNS and b"32-bit offsets" in lib.ivl_last_error(), "padded mxfp4 rows"
 
 
+def test_a_call_that_breaks_several_rules_is_refused_for_the_first_of_them(lib):
+    """the order of the refusals -- NULL, rows, N, K, offsets, alignment -- through all nine entries of the two kernels"""
+    from infinitevl_amd import _lib
+    p, odd16 = ctypes.c_void_p(0x1000), ctypes.c_void_p(0x1008)
+    INV, UNS = _lib.IVL_ERR_INVALID_ARG, _lib.IVL_ERR_UNSUPPORTED
+    seen = 0
+    for family, max_rows in (("ivl_linear_m16", 16), ("ivl_linear_m64", 64), ("ivl_linear_m16_lora", 16)):
+        for suffix, n_weight in (("_fwd", 1), ("_w8_fwd", 2), ("_w4_fwd", 2)):
+            name = family + suffix
+            fn = getattr(lib, name)
+            tail = (None, None) if "lora" in name else (None,)             # (lora,) stream
+            assert len(_lib.PROTOTYPES[name][1]) == 1 + n_weight + 6 + len(tail)
+
+            def call(x, M, K):
+                return fn(x, *([p] * n_weight), None, p, M, 16, K, 0, *tail)
+
+            assert call(None, 0, 48) == INV and lib.ivl_last_error() == f"{name}: NULL pointer".encode(), name
+            assert call(p, 0, 48) == UNS and lib.ivl_last_error() == f"{name}: M=0 (built for 1..{max_rows} rows)".encode(), name
+            assert call(odd16, 5, 48) == INV, name
+            err = lib.ivl_last_error()
+            assert err.startswith(f"{name}: K=48 (".encode()) and b"multiple of 32" in err and b"aligned" not in err, (name, err)
+            seen += 1
+    assert seen == 9
+
+
 # ---- the plan -------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("K", wide.KS_PLAN)
 def test_plan_is_a_permutation_of_the_chunks_plus_padding(K):
