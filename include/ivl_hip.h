@@ -897,6 +897,60 @@ IVL_API int ivl_sample_rows_adj_fwd(const ivl_sample_args* args, const ivl_sampl
 IVL_API int ivl_token_mark_fwd(uint32_t* seen_row, int64_t V, const int64_t* ids, int64_t n, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * TOKEN BANS: `no_repeat_ngram_size`, `bad_words_ids` and `min_new_tokens` of HF generate -- the logits processors that set
+ * scores to -inf in front of the warpers -- as ONE small launch in front of the sampling launch.  It writes bf16 -inf into the
+ * rows of `logits` IN PLACE; the sampling entry points are unchanged and see the edited rows.
+ *   logits bf16 [S, ld], ld >= V; done int32 [S], may be NULL;
+ *   n_new int64 [S] and history int64 [S, hist_ld]: the ring of the row's generated tokens that ivl_sample_rows_fwd keeps;
+ *   ctx int64 [S, ctx_ld] and n_ctx int64 [S]: a second ring of the same rule, the tokens in front of them (the prompt), n_ctx of
+ *     them pushed so far; may be NULL;
+ *   ngram int32 [S]: the row's n-gram size g, <= 0 = off; NULL = off for all rows;
+ *   min_new int64 [S] with stop_ids int64 [S, n_stop]; NULL = off;
+ *   ban_idx int32 [S]: the row's sequence table b, outside [0, n_tables) = none; NULL = none for all rows;
+ *   ban_seq int64 [n_tables, n_seq, seq_ld]: a sequence of m <= seq_ld tokens occupies the LAST m columns of its row; the first
+ *     negative entry from the right ends it; a row whose last column is negative is unused.
+ * THE ROW'S SEQUENCE seq[0 .. L): the c = min(n_ctx[s], ctx_ld) newest entries of the context ring, oldest first (c = 0 when ctx
+ * is NULL or n_ctx[s] < 0), then the h = min(n_new[s], hist_ld) newest entries of the history ring, oldest first; L = c + h.
+ * Entry number i of a ring sits at i % ld.  The window is what the rings hold: a token that has been overwritten no longer counts.
+ * An id outside [0, V) in a ring or a table equals nothing, not even itself: a prefix that holds one never matches.
+ * Per row s:
+ *   BAN-0 finished rows and rows that are off.  A row with done[s] != 0 is not touched, and nothing of it beyond done[s] is read
+ *      (step A of the sampling launch, HOLD-1..3).  A row with ngram <= 0, ban_idx out of range and n_new >= min_new has no byte
+ *      written, and neither its rings nor any table are read.
+ *   BAN-1 n-gram rule (NoRepeatNGramLogitsProcessor), g = ngram[s] >= 1.  For every i in [0, L - g]: if seq[i .. i+g-2] equals the
+ *      last g - 1 tokens of seq, token seq[i+g-1] is banned.  g = 1 bans every token of seq; L < g bans nothing.
+ *   BAN-2 sequence rule (NoBadWordsLogitsProcessor), for every used row of table b: t is its last token, the m - 1 tokens in
+ *      front of it the prefix.  If m - 1 <= L and the prefix equals the last m - 1 tokens of seq, t is banned; m = 1 always bans
+ *      t.  (HF skips a sequence that is LONGER than the ids so far, one token too early: its prefix may fit.  Here a prefix that
+ *      fits is matched.)
+ *   BAN-3 minimum length rule (MinNewTokensLengthLogitsProcessor).  While n_new[s] < min_new[s], every entry of stop_ids[s, :]
+ *      in [0, V) is banned.
+ *   BAN-4 the edit.  Banned: logits[s*ld + t] = bf16 -inf (0xFF80), for 0 <= t < V only -- no id is used as an address before it
+ *      is known to lie in [0, V).  Every other element keeps its bits (NaN payloads, -0); columns V..ld and other rows are never
+ *      written.  A ban is a 2-byte store to the element itself, never a read-modify-write of the word around it, and the row is
+ *      not read: the call is idempotent.  A row's result depends on that row's inputs alone: the same bits eager or replayed,
+ *      alone or as any row of a larger call.
+ *   BAN-5 composition.  The sampling launch that follows runs step 1, the scores L1-L3, the adjustments ADJ-1..3 and the
+ *      constraint on the edited row; a row that is banned entirely follows the all -inf rules it has.
+ * Refused before anything is launched (IVL_ERR_INVALID_ARG): NULL args or logits; S < 1, V < 1, ld < V; ngram or ban_idx
+ * without n_new and history or with hist_ld < 1; ctx without n_ctx or with ctx_ld < 1; ban_idx without ban_seq or with
+ * n_tables, n_seq or seq_ld < 1 or seq_ld > 16; min_new without n_new or stop_ids or with n_stop outside 1..16.
+ * IVL_ERR_UNSUPPORTED: V >= 2^23; with ngram or ban_idx, hist_ld + ctx_ld > 12288 (the window the kernel stages).
+ * ------------------------------------------------------------------------------------------- */
+typedef struct ivl_ban_args {
+  void* logits; int64_t ld; int S, V;
+  const int32_t* done;
+  const int64_t* n_new; const int64_t* history; int64_t hist_ld;
+  const int64_t* ctx; int64_t ctx_ld; const int64_t* n_ctx;
+  const int32_t* ngram;
+  const int64_t* min_new; const int64_t* stop_ids; int n_stop;
+  const int32_t* ban_idx;
+  const int64_t* ban_seq; int n_tables, n_seq, seq_ld;
+} ivl_ban_args;
+
+IVL_API int ivl_token_ban_fwd(const ivl_ban_args* args, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Row fork: row `src_row` of every tensor of a table goes to a set of rows of the partner tensors, in one launch.  The state of
  * a stream (ring rows, conv and recurrent states, position, sampler rows) is one row each of many tensors: this is the clone of
  * the reference's streaming demo (inference_examples/demo_streaming_inference.py:357-398) and the fan-out behind

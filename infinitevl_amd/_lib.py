@@ -1,7 +1,8 @@
 """ctypes binding of libivl_hip.so, derived from the C ABI's one declaration: include/ivl_hip.h.
 
 The header is read at import (no library needed): its `#define IVL_*` integers become module attributes, every `struct
-ivl_<x>_args` a ctypes class (`SwaArgs`, `SampleArgs`, `LoraArgs` in `ARG_STRUCTS`; a companion group such as `SampleAdjArgs` in `GROUP_STRUCTS`), and every `IVL_API` prototype an entry of `PROTOTYPES`, which `bind`
+ivl_<x>_args` a ctypes class (`SwaArgs`, `SampleArgs`, `LoraArgs` in `ARG_STRUCTS`; a companion group such as `SampleAdjArgs` in `GROUP_STRUCTS`;
+the struct of an in-place edit such as `BanArgs` in `EDIT_STRUCTS`), and every `IVL_API` prototype an entry of `PROTOTYPES`, which `bind`
 applies to a CDLL.
 The library is built in-tree by `__graft_entry__.build()` / `make -C infinitevl_amd/csrc`.
 There is NO fallback: if the shared object is missing, importing an operator raises.
@@ -60,16 +61,18 @@ def _int_expr(expr: str, where: str) -> int:
         raise ImportError(f"ivl_hip.h: {where}: not an integer expression: {expr!r}") from None
 
 
-def parse_header(text: str, structs: dict = None, groups: dict = None):
+def parse_header(text: str, structs: dict = None, groups: dict = None, edits: dict = None):
     """(constants {name: int}, the SwaArgs class, prototypes {name: (restype, [argument types])}) of a header text.  `structs`,
     when given, receives every `typedef struct ivl_<x>_args` of the header that some entry point takes as its FIRST parameter
     as {"ivl_<x>_args": its ctypes class}; `groups`, when given, the others: a companion group, which only ever rides beside
-    another struct (ivl_sample_adj_args beside ivl_sample_args)."""
+    another struct (ivl_sample_adj_args beside ivl_sample_args).  A struct whose FIRST member is a writable pointer (`void* logits`
+    of ivl_ban_args: its entry point edits that buffer in place and computes nothing else) is neither: it goes to `edits`, when
+    given, whoever takes it."""
     text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
     defines = re.findall(r"^[ \t]*#[ \t]*define[ \t]+(IVL_\w+)[ \t]+(\S[^\n]*)", text, re.M)     # (the include guard has no value)
     consts = {name: _int_expr(expr, "#define " + name) for name, expr in defines if name != "IVL_API"}
     text = re.sub(r"^[ \t]*#[^\n]*", " ", text, flags=re.M)
-    out, structs = structs, {}
+    out, structs, writable = structs, {}, set()
     for tag, body in re.findall(r"typedef\s+struct\s+(ivl_\w+_args)\s*\{(.*?)\}\s*\1\s*;", text, re.S):
         fields = []
         for decl in filter(None, (d.strip() for d in body.split(";"))):
@@ -77,6 +80,8 @@ def parse_header(text: str, structs: dict = None, groups: dict = None):
             if m is None:
                 raise ImportError(f"ivl_hip.h: {tag}: cannot read the field declaration {decl!r}")
             fields += [(name, _ctype(m.group(1), f"{tag}.{name}", _C_TYPES)) for name in re.split(r"\s*,\s*", m.group(2))]
+        if re.match(r"\s*(?!const\b)\w[\w\s]*\*", body):
+            writable.add(tag)
         cls = "".join(w.capitalize() for w in tag.split("_")[1:])                                  # ivl_swa_args -> SwaArgs
         structs[tag] = type(cls, (Structure,), {"_fields_": fields, "__doc__": f"struct {tag} (include/ivl_hip.h)."})
     if "ivl_swa_args" not in structs:
@@ -96,7 +101,7 @@ def parse_header(text: str, structs: dict = None, groups: dict = None):
                           f"read: {list(protos)[-1:]})")
     # (the rule is read off the prototypes: an entry point that took a companion group first would move it to `structs`)
     for tag, cls in structs.items():
-        into = out if tag in first else groups
+        into = edits if tag in writable else out if tag in first else groups
         if into is not None:
             into[tag] = cls
     return consts, structs["ivl_swa_args"], protos
@@ -106,10 +111,12 @@ if not os.path.exists(HEADER_PATH):
     raise ImportError(f"{HEADER_PATH} not found: the package is used in-tree and reads the C ABI from the header at import.")
 ARG_STRUCTS = {}                                             # every `ivl_<x>_args` struct an entry point takes first: {"ivl_swa_args": SwaArgs, ...}
 GROUP_STRUCTS = {}                                           # the companion groups: {"ivl_sample_adj_args": SampleAdjArgs}
+EDIT_STRUCTS = {}                                            # the structs of in-place edits: {"ivl_ban_args": BanArgs}
 with open(HEADER_PATH) as _f:
-    CONSTANTS, SwaArgs, PROTOTYPES = parse_header(_f.read(), ARG_STRUCTS, GROUP_STRUCTS)
+    CONSTANTS, SwaArgs, PROTOTYPES = parse_header(_f.read(), ARG_STRUCTS, GROUP_STRUCTS, EDIT_STRUCTS)
 SampleArgs, LoraArgs = ARG_STRUCTS["ivl_sample_args"], ARG_STRUCTS["ivl_lora_args"]
 SampleAdjArgs = GROUP_STRUCTS["ivl_sample_adj_args"]
+BanArgs = EDIT_STRUCTS["ivl_ban_args"]
 # the two wide argument structs (32 fields and more) whose sizes and key offsets tests/test_header_binding_cpu.py pins as numbers
 STRUCTS = {"ivl_swa_args": SwaArgs, "ivl_sample_args": SampleArgs}
 globals().update(CONSTANTS)                                  # IVL_ABI_VERSION, IVL_BF16, ..., IVL_OK, IVL_ERR_*, IVL_GDN_*

@@ -750,7 +750,8 @@ class _RowField(NamedTuple):
     name: str                   # the attribute
     dtype: torch.dtype
     shape: Tuple[str, ...]      # after the row, as named extents: "words" of the seen bitmap (vocab_size), "max_stop", "history",
-    #                             "top" (logprobs >= 1), "ring" (history, of a sampler with score rings), "vocab" (vocab_size).
+    #                             "top" (logprobs >= 1), "ring" (history, of a sampler with score rings), "vocab" (vocab_size),
+    #                             "context" (ban_context).
     #                             The tensor exists when every extent is non-zero
     init: float                 # of a fresh row, and what set() clears a state tensor to
     state: bool = False         # a step changes it (state() saves it); else a parameter
@@ -759,6 +760,7 @@ class _RowField(NamedTuple):
     grammar: bool = False       # ... and only in a sampler built with grammar_states
     penalties: bool = False     # ... and only in a sampler built with penalties=True
     bias: bool = False          # ... and only in a sampler built with bias_tables
+    bans: bool = False          # ... and only in a sampler built with bans=True
     cleared: bool = False       # set() puts it back to `init` although no step changes it (state() does not save it)
 
 
@@ -834,7 +836,18 @@ class Sampler:
     not counted); one built with `bias_tables` > 0 owns an ops.BiasTables arena of that many {token: bias} tables and one more
     per-row tensor, `bias_idx` (-1 = no bias): load_logit_bias() fills a table, set_logit_bias() points a row at it.  Either
     uses the adjusted form of the launch (ivl_sample_rows_adj_fwd) from construction on, so parameters, tables and a row's
-    table change between replays without a recapture.  The scores of such a sampler are those of the adjusted distribution."""
+    table change between replays without a recapture.  The scores of such a sampler are those of the adjusted distribution.
+
+    Token bans (`no_repeat_ngram_size` / `bad_words_ids` / `min_new_tokens` of HF generate): a sampler built with `bans=True`
+    (and history > 0) holds ngram and min_new per row, a second ring `ctx` of the last `ban_context` tokens that mark() was given
+    (the prompt) with its count n_ctx, and, with `ban_tables` > 0, an ops.BanTables arena and one more per-row tensor, `ban_idx`
+    (-1 = no table): load_bad_words() fills a table, set_bad_words() points a row at it.  sample() then launches
+    ops.ban_tokens (ivl_token_ban_fwd, BAN-0..5) on the same rows directly in front of ops.sample_tokens: the banned tokens of
+    a row become -inf IN the logits it is given, and everything the sampling launch does -- scores and adjustments included --
+    runs on the edited row.  Parameters, tables and a row's table change between replays without a recapture.  THE ROW'S
+    SEQUENCE is "context in mark() order, then this turn's generated tokens" and the window is what the two rings hold: a token
+    that has been overwritten no longer counts, and when a live slot is extended mid-answer that order is not the chronological
+    one (the new prompt tokens stand in front of the answer's).  None of these rows is handed to ops.sample_tokens."""
 
     # THE list of the per-row tensors: each is an attribute of its name, [n_rows, *shape], or None when the sampler does not hold
     # it.  row_tensors() (so every fork and beam gather), state() / load_state(), what set() clears and the keywords of
@@ -866,16 +879,26 @@ class Sampler:
         _RowField("pres_penalty", torch.float32, (), 0.0, kw="pres_penalty", penalties=True),
         _RowField("count", torch.int32, ("vocab",), 0, state=True, kw="count", penalties=True),     # of the GENERATED tokens
         _RowField("bias_idx", torch.int32, (), -1, kw="bias_idx", bias=True, cleared=True),         # -1 = no bias
+        # the rows of ops.ban_tokens (kw None: ops.sample_tokens never sees them)
+        _RowField("ngram", torch.int32, (), 0, bans=True),                                          # 0 = off
+        _RowField("min_new", torch.int64, (), 0, bans=True),
+        _RowField("ban_idx", torch.int32, (), -1, bans=True, cleared=True),                         # -1 = no table
+        _RowField("ctx", torch.int64, ("context",), 0, bans=True),                                  # the ring mark() pushes into
+        _RowField("n_ctx", torch.int64, (), 0, bans=True, cleared=True),                            # tokens pushed so far
     )
 
     def __init__(self, n_rows: int, device, vocab_size: Optional[int] = None, max_stop: int = 8, history: int = 0,
                  logprobs: Optional[int] = None, *, score_rings: bool = True, grammar_states: int = 0,
                  grammar_slots: Optional[int] = None, grammar_trans: Optional[int] = None, penalties: bool = False,
-                 bias_tables: int = 0):
+                 bias_tables: int = 0, bans: bool = False, ban_context: int = 256, ban_tables: int = 0, ban_seqs: int = 64,
+                 ban_len: int = 8):
         """score_rings=False: no per-token score rings (lp_history, top_hist_ids, top_hist_lp) beside the token history.
         grammar_states: the states of all grammars loaded at a time; grammar_slots: how many grammars (default: one per row);
         grammar_trans: their transition entries, n_states x n_classes each (default: 256 per state).  penalties: min-p and the
-        frequency / presence penalties with the rows' counts; bias_tables: how many logit-bias tables at a time (both: vocab_size)."""
+        frequency / presence penalties with the rows' counts; bias_tables: how many logit-bias tables at a time (both: vocab_size).
+        bans: the token bans in front of the sampling launch (needs history > 0); ban_context: the length of the context ring
+        (0: none, the bans see the generated tokens alone); ban_tables: how many bad-words tables at a time, each of up to
+        ban_seqs sequences of up to ban_len tokens."""
         if n_rows < 1:
             raise ValueError(f"Sampler: n_rows must be >= 1; got {n_rows}")
         if vocab_size is not None and (isinstance(vocab_size, bool) or not isinstance(vocab_size, int) or vocab_size < 1):
@@ -898,8 +921,22 @@ class Sampler:
             raise ValueError(f"Sampler: bias_tables must be an int >= 0; got {bias_tables!r}")
         if (penalties or bias_tables > 0) and vocab_size is None:
             raise ValueError("Sampler: penalties and bias_tables need vocab_size (the rows' counts, the bias tables)")
+        if not isinstance(bans, bool):
+            raise ValueError(f"Sampler: bans must be a bool; got {bans!r}")
+        for name, v in (("ban_context", ban_context), ("ban_tables", ban_tables)):
+            if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+                raise ValueError(f"Sampler: {name} must be an int >= 0; got {v!r}")
+        if bans and history < 1:
+            raise ValueError("Sampler: bans=True needs history > 0 (the ring of generated tokens the bans are decided from)")
+        if not bans and ban_tables > 0:
+            raise ValueError("Sampler: ban_tables needs bans=True")
+        if bans and history + ban_context > ops.BAN_WINDOW:
+            raise ValueError(f"Sampler: history + ban_context = {history} + {ban_context} tokens; the bans stage at most "
+                             f"{ops.BAN_WINDOW}")
         self.n_rows = int(n_rows)
         self.penalties = penalties
+        self.bans = bans
+        self.bad_words = ops.BanTables(device, ban_tables, ban_seqs, ban_len) if ban_tables else None    # the arena of the tables
         self.biases = ops.BiasTables(device, vocab_size, bias_tables) if bias_tables else None      # the arena of the bias tables
         # the arena of the grammars' tables (its own checks refuse what is left of the three sizes)
         self.grammars = ops.FsmTables(device, vocab_size, grammar_states, n_rows if grammar_slots is None else grammar_slots,
@@ -907,12 +944,13 @@ class Sampler:
         self.vocab_size, self.max_stop, self.history_len, self.n_logprobs = vocab_size, max_stop, history, logprobs
         self.controlled = vocab_size is not None or history > 0 or logprobs is not None      # (a grammar needs vocab_size)
         extent = {"words": (vocab_size + 31) // 32 if vocab_size is not None else 0, "max_stop": max_stop, "history": history,
-                  "top": logprobs or 0, "ring": history if score_rings else 0, "vocab": vocab_size or 0}
+                  "top": logprobs or 0, "ring": history if score_rings else 0, "vocab": vocab_size or 0,
+                  "context": ban_context}
         self._fields = []                                # the entries of _TABLE this sampler holds, in the table's order
         for f in self._TABLE:
             shape = [extent[e] for e in f.shape]
             held = all(shape) and (logprobs is not None or not f.score) and (self.grammars is not None or not f.grammar) and \
-                (penalties or not f.penalties) and (self.biases is not None or not f.bias)
+                (penalties or not f.penalties) and (self.biases is not None or not f.bias) and (bans or not f.bans)
             setattr(self, f.name, torch.full((n_rows, *shape), f.init, dtype=f.dtype, device=device) if held else None)
             if held:
                 self._fields.append(f)
@@ -974,6 +1012,15 @@ class Sampler:
                 raise ValueError(f"{who}: {k} must be finite; got {v}")
             if v != 0.0 and not self.penalties:
                 raise ValueError(f"{who}: {k} needs a Sampler built with penalties=True")
+        for k, top in (("no_repeat_ngram_size", 2 ** 31), ("min_new_tokens", 2 ** 63)):
+            if k not in p:
+                continue
+            if isinstance(p[k], bool) or not isinstance(p[k], int) or not 0 <= p[k] < top:
+                raise ValueError(f"{who}: {k} must be an int >= 0 (0 = off); got {p[k]!r}")
+            if p[k] != 0 and not self.bans:
+                raise ValueError(f"{who}: {k} needs a Sampler built with bans=True")
+            if p[k] != 0 and k == "min_new_tokens" and self.stop_ids is None:
+                raise ValueError(f"{who}: min_new_tokens needs a Sampler built with max_stop > 0 (it bans the row's stop ids)")
         return p
 
     def _write(self, row: int, p: dict) -> None:
@@ -998,6 +1045,10 @@ class Sampler:
             self.fill[row] = p["fill_token"]
         if self.penalties:
             for k, t in (("min_p", self.min_p), ("frequency_penalty", self.freq_penalty), ("presence_penalty", self.pres_penalty)):
+                if k in p:
+                    t[row] = p[k]
+        if self.bans:
+            for k, t in (("no_repeat_ngram_size", self.ngram), ("min_new_tokens", self.min_new)):
                 if k in p:
                     t[row] = p[k]
         if "stop_token_ids" in p and "max_new_tokens" in p:
@@ -1028,10 +1079,14 @@ class Sampler:
 
     def set(self, row: int, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0,
             repetition_penalty: float = 1.0, stop_token_ids=(), max_new_tokens: Optional[int] = None, fill_token: int = 0,
-            min_p: float = 0.0, frequency_penalty: float = 0.0, presence_penalty: float = 0.0) -> None:
+            min_p: float = 0.0, frequency_penalty: float = 0.0, presence_penalty: float = 0.0, no_repeat_ngram_size: int = 0,
+            min_new_tokens: int = 0) -> None:
         """Parameters and a fresh stream for `row`: counter 0, and the row's bitmap, n_new, done, history, scores and counts
-        cleared, and the row without a logit bias (set_logit_bias follows).  min_p in [0, 1] (0 = off), frequency_penalty and
-        presence_penalty finite (0 = off): other values need a sampler built with penalties=True.
+        cleared, and the row without a logit bias (set_logit_bias follows), without a bad-words table (set_bad_words follows)
+        and with an empty context ring (mark follows).  min_p in [0, 1] (0 = off), frequency_penalty and
+        presence_penalty finite (0 = off): other values need a sampler built with penalties=True.  no_repeat_ngram_size and
+        min_new_tokens: ints >= 0 (0 = off; min_new_tokens bans the row's stop ids while n_new is below it): other values need
+        a sampler built with bans=True.
         temperature 0 = greedy; top_k 0 and top_p 1 = off; repetition_penalty 1 = off (else finite and > 0: needs a sampler
         built with vocab_size); stop_token_ids: at most max_stop ints >= 0; max_new_tokens: None or an int >= 1; fill_token:
         what the row's token becomes once it is done."""
@@ -1081,13 +1136,52 @@ class Sampler:
 
     def mark(self, row: int, ids: torch.Tensor) -> None:
         """Mark the prompt's tokens `ids` (int64 [T] or [1,T], on the sampler's device) as seen by `row`: after set(), before
-        the row's first draw."""
+        the row's first draw.  A sampler with a context ring (bans=True, ban_context > 0) also appends them to the row's ring,
+        in the order given; one with neither a bitmap nor a ring refuses."""
         row = self._row(row)
-        if self.seen is None:
-            raise ValueError("Sampler.mark: needs a Sampler built with vocab_size (the bitmap of seen tokens)")
+        if self.seen is None and self.ctx is None:
+            raise ValueError("Sampler.mark: needs a Sampler built with vocab_size (the bitmap of seen tokens) or with bans=True "
+                             "and ban_context > 0 (the context ring)")
         if ids.dtype != torch.int64 or not (ids.dim() == 1 or (ids.dim() == 2 and ids.shape[0] == 1)):
             raise ValueError(f"Sampler.mark: ids must be int64 [T] or [1,T]; got {ids.dtype} {tuple(ids.shape)}")
-        ops.mark_tokens(self.seen[row], ids, self.vocab_size)
+        if self.seen is not None:
+            ops.mark_tokens(self.seen[row], ids, self.vocab_size)
+        if self.ctx is not None:
+            self._push_context(row, ids.reshape(-1))
+
+    def _push_context(self, row: int, ids: torch.Tensor) -> None:
+        """Appends ids (int64 [T], on the sampler's device) to the row's context ring: entry number i sits at i % ban_context.
+        Device work only (no read-back of n_ctx)."""
+        T, C = ids.shape[0], self.ctx.shape[1]
+        if T == 0:
+            return
+        first = max(T - C, 0)                            # of more than a ring's length only the last ban_context survive
+        at = (self.n_ctx[row] + torch.arange(first, T, device=ids.device, dtype=torch.int64)) % C
+        self.ctx[row].index_copy_(0, at, ids[first:])
+        self.n_ctx[row] += T
+
+    # ---- bad words ------------------------------------------------------------------------------------------------------------
+    def _ban_arena(self, who: str) -> "ops.BanTables":
+        if self.bad_words is None:
+            raise ValueError(f"Sampler.{who}: needs a Sampler built with bans=True and ban_tables > 0")
+        return self.bad_words
+
+    def load_bad_words(self, seqs) -> "ops.BanHandle":
+        """Puts a list of token-id lists (`bad_words_ids` of HF generate) into a free table of the sampler's arena (between
+        replays: no recapture); ValueError when every table is taken."""
+        return self._ban_arena("load_bad_words").load(seqs)
+
+    def unload_bad_words(self, handle: "ops.BanHandle") -> None:
+        """Frees the table.  A row that still points at it has nothing banned by it from its next draw on."""
+        self._ban_arena("unload_bad_words").unload(handle)
+
+    def set_bad_words(self, row: int, handle: Optional["ops.BanHandle"]) -> None:
+        """`row` draws under the bad-words table `handle` from its next draw on; None: no table.  Call it after set(), which
+        clears the row to no table."""
+        row, arena = self._row(row), self._ban_arena("set_bad_words")
+        if handle is not None and handle not in arena.handles():
+            raise ValueError(f"Sampler.set_bad_words: {handle!r} is not loaded in this sampler")
+        self.ban_idx[row] = -1 if handle is None else handle.index
 
     # ---- constrained decoding ------------------------------------------------------------------------------------------------
     def _arena(self, who: str) -> "ops.FsmTables":
@@ -1214,6 +1308,13 @@ class Sampler:
                 kw["fsm"] = self.grammars
             if self.biases is not None:
                 kw["bias"] = self.biases
+        if self.bans:                                    # the banned tokens of these rows become -inf in `logits` itself
+            ban = {"ctx": self.ctx[sl], "n_ctx": self.n_ctx[sl]} if self.ctx is not None else {}
+            if self.stop_ids is not None:
+                ban.update(min_new=self.min_new[sl], stop_ids=self.stop_ids[sl])
+            if self.bad_words is not None:
+                ban.update(ban_idx=self.ban_idx[sl], words=self.bad_words)
+            ops.ban_tokens(logits, n_new=self.n_new[sl], history=self.history[sl], done=self.done[sl], ngram=self.ngram[sl], **ban)
         return ops.sample_tokens(logits, self.temperature[sl], self.top_k[sl], self.top_p[sl], self.seed[sl], self.counter[sl],
                                  out=out, **kw)
 
@@ -1379,7 +1480,7 @@ class GraphedMultiStreamDecode(_Graphed):
     @torch.no_grad()
     def admit(self, slot: int, inputs_embeds: torch.Tensor, position_ids: Optional[torch.Tensor] = None,
               sampling: Optional[dict] = None, prompt_ids: Optional[torch.Tensor] = None, grammar=None, adapter=None,
-              logit_bias=None) -> torch.Tensor:
+              logit_bias=None, bad_words=None) -> torch.Tensor:
         """Start a stream in `slot` with a prompt inputs_embeds [1,T,hidden] (M-RoPE position_ids [3,1,T]; default: text
         positions 0..T-1).  Its first generated token is written to token[slot] and returned.  `sampling`: the keyword
         arguments of Sampler.set for this stream (needs a sampler), applied before that first token is drawn.  `prompt_ids`
@@ -1388,11 +1489,13 @@ class GraphedMultiStreamDecode(_Graphed):
         and may already end the stream.  `grammar` (a handle of Sampler.load_grammar): the stream starts in the grammar's start
         state, set after the row's parameters and before the first draw, so the first token is constrained too.  `adapter`: the stream's LoRA adapter
         (set_adapter); the prompt is prefilled under it.  `logit_bias` (a handle of Sampler.load_logit_bias): the row's bias
-        table, set before the first draw like the grammar."""
+        table, set before the first draw like the grammar.  `bad_words` (a handle of Sampler.load_bad_words): the row's table of
+        banned sequences, set before the first draw too."""
         if sampling is not None and self.sampler is None:
             raise ValueError("admit: sampling parameters need a GraphedMultiStreamDecode built with a sampler")
         self._check_grammar("admit", grammar)
         self._check_bias("admit", logit_bias)
+        self._check_bad_words("admit", bad_words)
         T = self._check_prompt("admit", inputs_embeds, position_ids, prompt_ids)
         self.set_adapter(slot, adapter)
         if position_ids is None:
@@ -1403,6 +1506,8 @@ class GraphedMultiStreamDecode(_Graphed):
             self.sampler.set_grammar(slot, grammar)
         if logit_bias is not None:
             self.sampler.set_logit_bias(slot, logit_bias)
+        if bad_words is not None:
+            self.sampler.set_bad_words(slot, bad_words)
         if prompt_ids is not None:
             self.sampler.mark(slot, prompt_ids.to(inputs_embeds.device))
         self.cache.admit(slot)
@@ -1443,6 +1548,12 @@ class GraphedMultiStreamDecode(_Graphed):
             raise ValueError(f"{who}: a logit_bias needs a GraphedMultiStreamDecode whose sampler was built with bias_tables")
         if logit_bias is not None and logit_bias not in self.sampler.biases.handles():
             raise ValueError(f"{who}: {logit_bias!r} is not loaded in the sampler (Sampler.load_logit_bias)")
+
+    def _check_bad_words(self, who: str, bad_words) -> None:
+        if bad_words is not None and (self.sampler is None or self.sampler.bad_words is None):
+            raise ValueError(f"{who}: bad_words need a GraphedMultiStreamDecode whose sampler was built with bans=True and ban_tables")
+        if bad_words is not None and bad_words not in self.sampler.bad_words.handles():
+            raise ValueError(f"{who}: {bad_words!r} is not loaded in the sampler (Sampler.load_bad_words)")
 
     def _check_prompt(self, who: str, inputs_embeds, position_ids, prompt_ids) -> int:
         if prompt_ids is not None and self.sampler is None:
@@ -1524,7 +1635,8 @@ class GraphedMultiStreamDecode(_Graphed):
         `max_new_tokens` (None or an int >= 1) / `stop_token_ids`: the row's budget / stop ids from here on (default: unchanged).
         With holds=True, on a slot that is frozen (finished or held) this starts the NEXT TURN where the state stopped: done, n_new
         and cum_logprob are cleared, so tokens(slot) and the score rings hold the new answer only; seen, count, the random counter
-        and the grammar state stay.  The token that ended the last turn was never fed to the model; it belongs in inputs_embeds
+        and the grammar state stay; a sampler with a context ring (bans=True) gets the finished answer, tokens(slot), appended to
+        the ring first, so the next turn's bans still see it.  The token that ended the last turn was never fed to the model; it belongs in inputs_embeds
         if the conversation's template has it."""
         slot = self._slots("extend", [slot])[0]
         if slot not in self._live:
@@ -1537,6 +1649,8 @@ class GraphedMultiStreamDecode(_Graphed):
         if ends:
             self.sampler._checked("extend", ends)       # (refused before anything is written)
         if self.holds and int(self.sampler.done[slot]) != 0:
+            if self.sampler.bans and self.sampler.ctx is not None:       # the next turn's bans still see the finished answer
+                self.sampler._push_context(slot, self.sampler.tokens(slot).to(self.sampler.ctx.device))
             self.sampler.done[slot] = 0
             self.sampler.n_new[slot] = 0
             if self.sampler.cum_logprob is not None:
@@ -1582,16 +1696,17 @@ class GraphedMultiStreamDecode(_Graphed):
     @torch.no_grad()
     def admit_n(self, slots, inputs_embeds: torch.Tensor, position_ids: Optional[torch.Tensor] = None,
                 sampling=None, prompt_ids: Optional[torch.Tensor] = None, grammar=None, adapter=None,
-                logit_bias=None) -> torch.Tensor:
+                logit_bias=None, bad_words=None) -> torch.Tensor:
         """Several answers to one prompt (num_return_sequences of the reference's api/chat.py:164): the prompt is prefilled
         ONCE, into slots[0]; its cache and sampler rows are forked to slots[1:] before any token is drawn; then every slot
         draws its own first token from the same logits, in its own sampler row.  `sampling`: one dict of Sampler.set
         keyword arguments per slot (e.g. one seed each); every slot ends up as admit(slot, ..., sampling=that dict,
         prompt_ids=prompt_ids) would leave it.  `grammar`: every slot starts in that grammar's start state; `logit_bias`: every slot
-        draws under that bias table.  Returns token[slots]."""
+        draws under that bias table; `bad_words`: and under that table of banned sequences.  Returns token[slots]."""
         slots = self._slots("admit_n", slots)
         self._check_grammar("admit_n", grammar)
         self._check_bias("admit_n", logit_bias)
+        self._check_bad_words("admit_n", bad_words)
         if sampling is not None and self.sampler is None:
             raise ValueError("admit_n: sampling parameters need a GraphedMultiStreamDecode built with a sampler")
         T = self._check_prompt("admit_n", inputs_embeds, position_ids, prompt_ids)
@@ -1610,6 +1725,8 @@ class GraphedMultiStreamDecode(_Graphed):
             self.sampler.set_grammar(first, grammar)    # (it travels to the other slots with the row)
         if logit_bias is not None:
             self.sampler.set_logit_bias(first, logit_bias)
+        if bad_words is not None:
+            self.sampler.set_bad_words(first, bad_words)
         if prompt_ids is not None:
             self.sampler.mark(first, prompt_ids.to(inputs_embeds.device))
         self.cache.admit(first)
@@ -1625,22 +1742,24 @@ class GraphedMultiStreamDecode(_Graphed):
                     self.sampler._ends[d] = self.sampler._ends[first]
                     if checked is not None:
                         self.sampler._write(d, checked[i + 1])
-        for s in slots:
-            self._draw(s, lg)
+        bans = self.sampler is not None and self.sampler.bans
+        for s in slots:                                  # (a slot's bans are written into the logits it draws from: one copy each)
+            self._draw(s, lg.clone() if bans else lg)
         return self.token[slots]
 
     @torch.no_grad()
     def load(self, slots, cache: StaticCachePrealloc, row: int = 0, next_position: Optional[int] = None, sampling=None,
-             grammar=None, adapter=None, logit_bias=None) -> None:
+             grammar=None, adapter=None, logit_bias=None, bad_words=None) -> None:
         """The demo's branch (demo:363-365) on the serving path: the state of row `row` of an external cache -- the B = 1
         StaticCachePrealloc of a running video stream -- goes into `slots` in one launch, and they become live.  The source is
         only read, so questions never pollute the video's history.  Each slot's three M-RoPE positions are set to
         `next_position` (default: the source's length); `sampling`: one dict of Sampler.set keyword arguments per slot, applied
         as in admit; `grammar`: every slot is put into that grammar's start state, for the draw of the extend that follows.
-        `logit_bias`: every slot draws under that bias table.  No token is pending afterwards: extend(slot, question) follows."""
+        `logit_bias`: every slot draws under that bias table; `bad_words`: and under that table of banned sequences.  No token is pending afterwards: extend(slot, question) follows."""
         slots = self._slots("load", slots)
         self._check_grammar("load", grammar)
         self._check_bias("load", logit_bias)
+        self._check_bad_words("load", bad_words)
         if sampling is not None:
             if self.sampler is None:
                 raise ValueError("load: sampling parameters need a GraphedMultiStreamDecode built with a sampler")
@@ -1657,6 +1776,8 @@ class GraphedMultiStreamDecode(_Graphed):
                 self.sampler.set_grammar(s, grammar)
             if logit_bias is not None:
                 self.sampler.set_logit_bias(s, logit_bias)
+            if bad_words is not None:
+                self.sampler.set_bad_words(s, bad_words)
             self.token[s].zero_()
             self.position_ids[:, s].fill_(next_position)
             self.set_adapter(s, adapter)                 # (the extend that follows runs under it)
@@ -1733,6 +1854,9 @@ class GraphedBeamDecode(GraphedMultiStreamDecode):
         if sampler is not None and (sampler.penalties or sampler.biases is not None):
             raise ValueError("GraphedBeamDecode: the sampler was built with penalties or bias_tables: they are not part of beam "
                              "search (a beam's candidates come from the score-only launch, which takes no adjustment group)")
+        if sampler is not None and sampler.bans:
+            raise ValueError("GraphedBeamDecode: the sampler was built with bans=True: token bans are not part of beam search (a "
+                             "beam's candidates come from the score-only launch, with no ban launch in front of it)")
         if sampler is not None and sampler.grammars is not None:
             raise ValueError("GraphedBeamDecode: the sampler was built with grammar_states: constrained beam search is not "
                              "supported (a beam's candidates come from the score-only launch, which reads no grammar)")

@@ -2298,6 +2298,147 @@ def mark_tokens(seen_row: torch.Tensor, ids: torch.Tensor, vocab_size: int) -> N
 
 
 # ---------------------------------------------------------------------------------------------
+# token bans: no_repeat_ngram_size, bad_words_ids, min_new_tokens in front of the sampling launch
+# ---------------------------------------------------------------------------------------------
+BAN_CALLS = {"ban": 0}              # calls of ban_tokens that went to ivl_token_ban_fwd (tests and tools read it)
+BAN_WINDOW = 12288                  # tokens of history + context a call may stage (ivl_token_ban_fwd)
+
+
+class BanHandle(NamedTuple):
+    """A list of banned sequences loaded into a BanTables: `index` is what a row's ban_idx holds; `serial` counts the arena's
+    loads, so the handle of an unloaded table never equals that of a later load into its place."""
+    index: int
+    serial: int
+
+
+class BanTables:
+    """The device tables of ivl_ban_args' sequence rule as ONE arena, allocated once: `n_tables` tables of up to `n_seq`
+    sequences of up to `max_len` tokens, `seq` int64 [n_tables, n_seq, max_len], a sequence right-aligned in its row and -1
+    everywhere else (`bad_words_ids` of HF generate, one table per request).  load() writes a list of token-id lists into a free
+    table; unload() fills it with -1, so a row that still points at it has nothing banned.  The tensor never moves: a captured
+    step obeys a table that was loaded after its capture.  seq with n_tables, n_seq and seq_ld is what
+    ops.ban_tokens(words=) takes."""
+
+    def __init__(self, device, n_tables: int, n_seq: int = 64, max_len: int = 8):
+        for name, v in (("n_tables", n_tables), ("n_seq", n_seq), ("max_len", max_len)):
+            if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+                raise ValueError(f"BanTables: {name} must be an int >= 1; got {v!r}")
+        if max_len > 16:
+            raise ValueError(f"BanTables: max_len must be at most 16; got {max_len}")
+        self.n_tables, self.n_seq, self.seq_ld = n_tables, n_seq, max_len
+        self.seq = torch.full((n_tables, n_seq, max_len), -1, dtype=torch.int64, device=device)
+        self._slots: List[Optional[BanHandle]] = [None] * n_tables
+        self._loads = 0
+
+    def handles(self) -> List["BanHandle"]:
+        return [h for h in self._slots if h is not None]
+
+    def load(self, seqs) -> "BanHandle":
+        """Writes a list of token-id lists (each 1..max_len ints >= 0, at most n_seq of them) into a free table and returns
+        its handle.  ValueError: an empty list, a bad sequence or id, or no table left."""
+        if isinstance(seqs, (str, bytes, dict)) or not hasattr(seqs, "__iter__"):
+            raise ValueError(f"BanTables.load: a list of token-id lists is expected; got {type(seqs).__name__}")
+        seqs = list(seqs)
+        if not seqs or len(seqs) > self.n_seq:
+            raise ValueError(f"BanTables.load: 1 to {self.n_seq} sequences are expected; got {len(seqs)}")
+        rows = np.full((self.n_seq, self.seq_ld), -1, dtype=np.int64)
+        for r, q in enumerate(seqs):
+            if isinstance(q, (str, bytes, dict)) or not hasattr(q, "__iter__"):
+                raise ValueError(f"BanTables.load: sequence {r} is not a list of token ids: {q!r}")
+            q = list(q)
+            if not 1 <= len(q) <= self.seq_ld:
+                raise ValueError(f"BanTables.load: sequence {r} has {len(q)} tokens (1 to {self.seq_ld})")
+            for t in q:
+                if isinstance(t, bool) or not isinstance(t, (int, np.integer)) or not 0 <= int(t) < 2 ** 63:
+                    raise ValueError(f"BanTables.load: token id {t!r} of sequence {r} is not an int >= 0")
+            rows[r, self.seq_ld - len(q):] = [int(t) for t in q]
+        if None not in self._slots:
+            raise ValueError(f"BanTables.load: all {self.n_tables} tables are taken")
+        slot = self._slots.index(None)
+        self.seq[slot] = torch.from_numpy(rows).to(self.seq.device)
+        self._loads += 1
+        self._slots[slot] = h = BanHandle(slot, self._loads)
+        return h
+
+    def unload(self, handle: "BanHandle") -> None:
+        """Frees the table; it bans nothing from now on."""
+        if not isinstance(handle, BanHandle) or not 0 <= handle.index < len(self._slots) or self._slots[handle.index] != handle:
+            raise ValueError(f"BanTables.unload: {handle!r} is not loaded here")
+        self.seq[handle.index].fill_(-1)
+        self._slots[handle.index] = None
+
+
+def ban_tokens(logits: torch.Tensor, *, n_new: torch.Tensor, history: Optional[torch.Tensor] = None,
+               done: Optional[torch.Tensor] = None, ctx: Optional[torch.Tensor] = None, n_ctx: Optional[torch.Tensor] = None,
+               ngram: Optional[torch.Tensor] = None, min_new: Optional[torch.Tensor] = None,
+               stop_ids: Optional[torch.Tensor] = None, ban_idx: Optional[torch.Tensor] = None, words=None) -> torch.Tensor:
+    """Writes bf16 -inf over the banned tokens of every row of lm_head logits [S,V] or [S,1,V] (bf16, last dim contiguous) IN
+    PLACE, in one launch in front of ops.sample_tokens, and returns `logits` (ivl_token_ban_fwd states the semantics, BAN-0 to
+    BAN-5; HF generate's NoRepeatNGram, NoBadWords and MinNewTokensLength logits processors).  The row's sequence is the
+    context ring ctx [S,C] int64 with n_ctx [S] int64 (the tokens pushed so far; optional), then the ring history [S,H] int64
+    with n_new [S] int64 that ops.sample_tokens keeps; H + C <= BAN_WINDOW.  ngram [S] int32: no_repeat_ngram_size per row
+    (0 = off).  min_new [S] int64 with stop_ids [S,n] int64 (n <= 16): while n_new < min_new the row's stop ids are banned.
+    ban_idx [S] int32 (a table of `words`, or anything outside [0, n_tables) for none) with `words`: a BanTables, or any
+    holder of seq int64 [n_tables, n_seq, seq_ld] with n_tables, n_seq and seq_ld.  done [S] int32: a row that is finished is
+    not touched.  A row with every rule off has no byte written."""
+    given = logits
+    if logits.dim() == 3 and logits.shape[1] == 1:
+        logits = logits[:, 0]
+    if logits.dim() != 2 or logits.dtype != torch.bfloat16 or logits.shape[0] < 1 or logits.shape[1] < 1:
+        raise ValueError(f"ban_tokens: logits must be bf16 [S,V] or [S,1,V]; got {logits.dtype} {tuple(logits.shape)}")
+    S, V = logits.shape
+    if logits.stride(1) != 1 or (S > 1 and logits.stride(0) < V):
+        raise ValueError(f"ban_tokens: the last dim of logits must be contiguous and the rows apart (strides {logits.stride()})")
+    for name, t, dt in (("n_new", n_new, torch.int64), ("n_ctx", n_ctx, torch.int64), ("min_new", min_new, torch.int64),
+                        ("done", done, torch.int32), ("ngram", ngram, torch.int32), ("ban_idx", ban_idx, torch.int32)):
+        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != dt or tuple(t.shape) != (S,) or not t.is_contiguous()):
+            raise ValueError(f"ban_tokens: {name} must be a contiguous {dt} tensor of [{S}]; got "
+                             f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+    for name, t in (("history", history), ("ctx", ctx), ("stop_ids", stop_ids)):
+        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or t.dim() != 2 or t.shape[0] != S
+                              or t.shape[1] < 1 or not t.is_contiguous()):
+            raise ValueError(f"ban_tokens: {name} must be a contiguous int64 tensor of [{S},n], n >= 1; got "
+                             f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+    if n_new is None:
+        raise ValueError("ban_tokens: n_new is needed")
+    if (ngram is not None or ban_idx is not None) and history is None:
+        raise ValueError("ban_tokens: ngram and ban_idx need history")
+    if (ctx is None) != (n_ctx is None):
+        raise ValueError("ban_tokens: ctx and n_ctx come together")
+    if min_new is not None and stop_ids is None:
+        raise ValueError("ban_tokens: min_new needs stop_ids")
+    if min_new is not None and stop_ids.shape[1] > 16:
+        raise ValueError(f"ban_tokens: stop_ids must be [{S},n] with 1 <= n <= 16; got {tuple(stop_ids.shape)}")
+    if (ban_idx is None) != (words is None):
+        raise ValueError("ban_tokens: ban_idx and words come together")
+    a = _lib.BanArgs(ld=logits.stride(0) if S > 1 else V, S=S, V=V)
+    if words is not None:
+        a.n_tables, a.n_seq, a.seq_ld = int(words.n_tables), int(words.n_seq), int(words.seq_ld)
+        seq = words.seq
+        if not isinstance(seq, torch.Tensor) or seq.dtype != torch.int64 or not seq.is_contiguous() or \
+                tuple(seq.shape) != (a.n_tables, a.n_seq, a.seq_ld) or a.n_tables < 1 or a.n_seq < 1 or not 1 <= a.seq_ld <= 16:
+            raise ValueError(f"ban_tokens: words.seq must be a contiguous int64 tensor of [n_tables, n_seq, seq_ld] = "
+                             f"[{a.n_tables}, {a.n_seq}, {a.seq_ld}], each >= 1 and seq_ld <= 16; got "
+                             f"{getattr(seq, 'dtype', type(seq))} {tuple(getattr(seq, 'shape', ()))}")
+    window = (history.shape[1] if history is not None else 0) + (ctx.shape[1] if ctx is not None else 0)
+    if (ngram is not None or ban_idx is not None) and window > BAN_WINDOW:
+        raise ValueError(f"ban_tokens: history and ctx hold {window} tokens per row (at most {BAN_WINDOW})")
+    tensors = dict(logits=logits, done=done, n_new=n_new, history=history, ctx=ctx, n_ctx=n_ctx, ngram=ngram, min_new=min_new,
+                   stop_ids=stop_ids if min_new is not None else None, ban_idx=ban_idx,
+                   ban_seq=words.seq if words is not None else None)
+    _need_gpu(*tensors.values())
+    for name, t in tensors.items():
+        if t is not None:
+            setattr(a, name, t.data_ptr())
+    a.hist_ld = history.shape[1] if history is not None else 0
+    a.ctx_ld = ctx.shape[1] if ctx is not None else 0
+    a.n_stop = stop_ids.shape[1] if min_new is not None else 0
+    BAN_CALLS["ban"] += 1
+    _lib.check(_lib.load().ivl_token_ban_fwd(ctypes.byref(a), _stream(logits)))
+    return given
+
+
+# ---------------------------------------------------------------------------------------------
 # row fork: one row of many tensors to other rows, one launch
 # ---------------------------------------------------------------------------------------------
 def _byte_extent(t: torch.Tensor) -> Tuple[int, int]:

@@ -133,6 +133,16 @@ work.  B against A is reported beside the project's 2 % allowance, not gated: in
 step with the mask at every slot count.
 
     python tools/multistream_decode.py --holds [--slots 4,16] [--out profiles/holds_decode.json]
+
+--bans: the cost of the ban launch in front of the sampling launch (ivl_token_ban_fwd) in the captured 4-slot
+step.  A: the sampled, controlled step of --adjust's leg A (a sampler built without bans); B: the same with a sampler built with
+bans=True (a 256-entry context ring, one table) and every row off; C: every slot with no_repeat_ngram_size 3, min_new_tokens
+above what any run reaches and a table of 8 sequences of 2 to 4 tokens.  Every leg generates 64 tokens per row first; that state
+is saved and put back in front of every timed run, outside the timed region.  Timed A B C A B C, median of --rounds rounds of
+--steps replays.  No bar is asserted: B - A and C - A are reported beside the 2 % of A of the project's allowance and beside
+the spread of A's own runs.
+
+    python tools/multistream_decode.py --bans [--out profiles/bans_decode.json]
 """
 import argparse
 import json
@@ -170,6 +180,8 @@ def main():
                     help="time the 4-slot controlled step with and without penalties, min-p and a logit-bias table (see above)")
     ap.add_argument("--holds", action="store_true",
                     help="time the step with the per-slot hold mask: off, on, half and all but one slot frozen (see above)")
+    ap.add_argument("--bans", action="store_true",
+                    help="time the 4-slot controlled step without the ban launch, with it and every row off, and with every rule on (see above)")
     args = ap.parse_args()
     import torch
     from infinitevl_amd.cache import MultiStreamCache
@@ -200,6 +212,8 @@ def main():
         raise SystemExit(holds_legs(args, torch, model, cfg, prompts, dev))      # exit code 1: the gate failed
     if args.adjust:
         return adjust_legs(args, torch, model, cfg, prompts, dev)
+    if args.bans:
+        return bans_legs(args, torch, model, cfg, prompts, dev)
     if args.sampling:
         return sampling_legs(args, torch, model, cfg, prompts, dev)
     if args.generation:
@@ -538,6 +552,94 @@ def adjust_legs(args, torch, model, cfg, prompts, dev):
             op[f"S{n}_{pname}_{tag}_us"] = round(1000 * timed(lambda smp=smp: smp.sample(lg, tok), 200,
                                                               lambda smp=smp, tag=tag: smp.load_state(states[tag])), 2)
             op[f"S{n}_{pname}_{tag}_rows_still_live"] = bool((smp.poll()[0] == 0).all())
+    res["operator_V%d" % V] = op
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+BANS = {"no_repeat_ngram_size": 3, "min_new_tokens": 1 << 30}
+BAN_CONTEXT = 256
+BAN_SEQUENCES = 8
+
+
+def bans_legs(args, torch, model, cfg, prompts, dev):
+    from infinitevl_amd import ops
+    from infinitevl_amd.cache import MultiStreamCache
+    from infinitevl_amd.harness import GraphedMultiStreamDecode, Sampler
+    stream = torch.cuda.current_stream()
+    V, n = cfg.vocab_size, 4
+
+    def timed(fn, k, before):
+        for _ in range(4):
+            fn()
+        before()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        for _ in range(k):
+            fn()
+        e1.record(stream)
+        e1.synchronize()
+        return e0.elapsed_time(e1) / k
+
+    def seen_ids(s):
+        g = torch.Generator().manual_seed(100 + s)
+        return torch.randperm(V, generator=g)[:int(SEEN_FRACTION * V)].to(dev)
+
+    g = torch.Generator().manual_seed(9)
+    words = [torch.randint(0, V, (2 + i % 3,), generator=g).tolist() for i in range(BAN_SEQUENCES)]
+    names = ("controlled", "bans_off", "bans_on")
+    res = {"tool": "multistream_decode --bans", "layers": cfg.num_hidden_layers, "window": 4096, "slots": n, "steps": args.steps,
+           "rounds": args.rounds, "sampled": SAMPLED, "controls": dict(CONTROLS, stop_ids=2, history=HISTORY, seen_fraction=SEEN_FRACTION),
+           "bans": dict(BANS, ban_context=BAN_CONTEXT, sequences=BAN_SEQUENCES, generated_tokens_per_row=GENERATED)}
+    legs, samplers, restore, launches = {}, {}, {}, {}
+    for name in names:
+        cache = MultiStreamCache(config=cfg, n_slots=n, device=dev, dtype=torch.bfloat16)
+        extra = {} if name == "controlled" else dict(bans=True, ban_context=BAN_CONTEXT, ban_tables=1, ban_seqs=BAN_SEQUENCES, ban_len=4)
+        smp = Sampler(n, dev, vocab_size=V, history=HISTORY, **extra)
+        dec = GraphedMultiStreamDecode(model, cache, sampler=smp)
+        on = name == "bans_on"
+        table = smp.load_bad_words(words) if on else None
+        before = ops.BAN_CALLS["ban"]
+        for s in range(n):
+            dec.admit(s, prompts[s], sampling=dict(SAMPLED, seed=s + 1, stop_token_ids=[V - 1 - s, V - 9 - s], **CONTROLS,
+                                                   **(BANS if on else {})), prompt_ids=seen_ids(s),
+                      **({"bad_words": table} if on else {}))
+        dec.capture()
+        launches[name] = ops.BAN_CALLS["ban"] - before
+        for _ in range(GENERATED - 1):                          # (admit drew the first token)
+            dec.step()
+        state = smp.state()
+        legs[name], samplers[name], restore[name] = dec.step, smp, (lambda smp=smp, state=state: smp.load_state(state))
+    times = {k: [] for k in legs}
+    for _ in range(args.rounds):                                # A B C A B C
+        for _ in range(2):
+            for name in names:
+                times[name].append(timed(legs[name], args.steps, restore[name]))
+    med = {k: statistics.median(v) for k, v in times.items()}
+    a = med["controlled"]
+    for name in names:
+        done, n_new = samplers[name].poll()
+        res[name] = {"ms_per_step": round(med[name], 4), "spread_ms": [round(min(times[name]), 4), round(max(times[name]), 4)],
+                     "ban_launches_issued_eagerly": launches[name], "rows_still_live": bool((done == 0).all()),
+                     "tokens_per_row_at_the_end": n_new.tolist()}
+    res["allowance_us"] = round(1000 * 0.02 * a, 1)
+    res["step_noise_us"] = round(1000 * (max(times["controlled"]) - min(times["controlled"])), 1)
+    for name in names[1:]:
+        res[f"{name}_minus_controlled_us"] = round(1000 * (med[name] - a), 1)
+        res[f"{name}_within_allowance"] = bool(med[name] - a <= 0.02 * a)
+    # the ban launch alone on 4 rows of the model's vocabulary, back to back on one stream (the figure includes the launch gap)
+    gen = torch.Generator(device=dev).manual_seed(1)
+    lg = (torch.randn(n, V, generator=gen, device=dev) * 3.0).to(torch.bfloat16)
+    op = {}
+    for name in names[1:]:
+        smp = samplers[name]
+        sl = dict(n_new=smp.n_new, history=smp.history, done=smp.done, ngram=smp.ngram, ctx=smp.ctx, n_ctx=smp.n_ctx,
+                  min_new=smp.min_new, stop_ids=smp.stop_ids, ban_idx=smp.ban_idx, words=smp.bad_words)
+        op[f"S{n}_{name}_us"] = round(1000 * timed(lambda sl=sl: ops.ban_tokens(lg, **sl), 200, lambda: None), 2)
     res["operator_V%d" % V] = op
     line = json.dumps(res)
     print(line)
