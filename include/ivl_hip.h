@@ -951,6 +951,43 @@ typedef struct ivl_ban_args {
 IVL_API int ivl_token_ban_fwd(const ivl_ban_args* args, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * GUIDANCE ON PAIRED ROWS: `guidance_scale` with `negative_prompt_ids` of HF generate (UnbatchedClassifierFreeGuidanceLogits-
+ * Processor) and visual contrastive decoding (VCD: cd_alpha, cd_beta) -- the one logits processor that needs TWO rows.  A guided
+ * stream is a leader row r (the real prompt) and its partner row p = partner[r] (the negative prompt).  ivl_logit_guide_fwd is ONE
+ * small launch in front of the bans and the sampling launch; it rewrites the leader's row of `logits` IN PLACE from both rows.
+ * ivl_rows_follow_fwd is one launch behind the sampling launch; it keeps the partner on the leader's tokens.
+ *   logits bf16 [S, ld], ld >= V, rows at any alignment, as in the sampling launch;
+ *   partner int32 [S]; scale fp32 [S]; cut fp32 [S]: ln(beta) of the plausibility rule, -inf = off (the host takes the
+ *     logarithm); done int32 [S], may be NULL.
+ *   GUIDE-0 which rows are guided.  Row r is guided when p = partner[r] lies in [0, S), p != r, partner[p] is not itself in
+ *      [0, S) other than p (a partner is never a leader), scale[r] is finite, and done is NULL or done[r] == 0.  Any other row is
+ *      OFF: no byte of it is written and nothing of it beyond those table entries is read; it keeps its bits whatever they are.
+ *   GUIDE-1 log-partitions.  c = row r, u = row p, a NaN read as -inf.  mc, mu: the row maxima.  Lc, Lu: the log-partitions as
+ *      the scoring form of the sampling launch computes its lse (L1): Z = the INTEGER sum of the Q40 weights at temperature 1,
+ *      2^40 exactly at the maximum, L = logf((float)Z * 2^-40).  An integer sum does not depend on the order of the reduction.
+ *   GUIDE-2 the combination, in fp32, one rounding per operation: dc = c(v) - mc, du = u(v) - mu; lc = dc - Lc, lu = du - Lu;
+ *      y = fmaf(s, lc - lu, lu), s = scale[r]; out(v) = bf16_rne(y).  This is HF's uncond + s (cond - uncond) on log-softmaxes;
+ *      with s = 1 + alpha it is VCD's (1 + alpha) c - alpha u up to a constant per row, which is kept so that what runs behind
+ *      it (the repetition penalty) sees HF's values.
+ *   GUIDE-3 infinities and the cut.  c(v) = -inf: out(v) = -inf.  u(v) = -inf with c(v) finite: out(v) = lc (HF produces a NaN
+ *      there).  dc < cut[r]: out(v) = -inf -- VCD's adaptive plausibility constraint p_c(v) >= beta max p_c.  The leader's
+ *      maximum always survives, whatever cut[r] holds.
+ *   GUIDE-4 the edit.  Only elements [0, V) of guided leader rows are written; columns V..ld, partner rows and off rows keep
+ *      every bit.  A row's result depends on its two input rows alone: the same bits eager or replayed, in any pair of row
+ *      positions, among any neighbours.  The call is NOT idempotent: it is meant for freshly written logits.
+ *   GUIDE-5 composition.  The bans and every form of the sampling launch run on the edited row: scores and logprobs are those
+ *      of the guided distribution.
+ * ivl_rows_follow_fwd: token int64, row s at token[s * token_stride]; done int32 [S], may be NULL.  For every row p that is the
+ * partner of a valid leader r (GUIDE-0 without the done and scale clauses): token[p * stride] = token[r * stride], and
+ * done[p] = done[r] if done is given.  If several leaders name p the lowest r wins.  Every other element is untouched.
+ * Refused before anything is launched (IVL_ERR_INVALID_ARG): NULL logits, partner, scale, cut or token; S < 1, V < 1, ld < V,
+ * token_stride < 1.  IVL_ERR_UNSUPPORTED: V >= 2^23 or S > 63.
+ * ------------------------------------------------------------------------------------------- */
+IVL_API int ivl_logit_guide_fwd(void* logits, int64_t ld, int S, int V, const int32_t* partner, const float* scale,
+                                const float* cut, const int32_t* done, void* stream);
+IVL_API int ivl_rows_follow_fwd(int64_t* token, int64_t token_stride, int32_t* done, const int32_t* partner, int S, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Row fork: row `src_row` of every tensor of a table goes to a set of rows of the partner tensors, in one launch.  The state of
  * a stream (ring rows, conv and recurrent states, position, sampler rows) is one row each of many tensors: this is the clone of
  * the reference's streaming demo (inference_examples/demo_streaming_inference.py:357-398) and the fan-out behind

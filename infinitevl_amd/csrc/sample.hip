@@ -51,46 +51,18 @@
 // table per row, added where smp_load has re-keyed the tile and rounded back to bf16 -- nothing behind the key changes -- and
 // min-p as one more predicate on the Q40 weight where passes 5 and 6 evaluate it.  The lane that writes the token counts it.
 #include "ivl_common.h"
+#include "ivl_logits.h"
 
 #include <type_traits>
 
 namespace ivl {
 
-typedef unsigned long long u64;
-
+// (the key, the Q40 weight, the log-partition, the bf16 rounding, the wave sum and the tile view of a row: ivl_logits.h,
+// shared with the guidance launch of guide.hip)
 constexpr int SMP_THREADS = 1024;
 constexpr int SMP_WAVES = SMP_THREADS / 64;
 constexpr int SMP_BINS = 4096;                 // coarse level: key >> 4
 constexpr int SMP_SUB = 16;                    // keys per coarse bin
-constexpr unsigned SMP_KEY_NINF = 0x007Fu;     // key of -inf (and of NaN): the lowest key that occurs
-constexpr u64 SMP_ONE = 1ull << 40;            // weight of the maximum
-
-// bf16 bits -> a 16-bit key whose unsigned order is the numeric order; NaN counts as -inf, -0 as +0
-__device__ __forceinline__ unsigned smp_key(unsigned b) {
-  if ((b & 0x7FFFu) > 0x7F80u) b = 0xFF80u;
-  if (b == 0x8000u) b = 0u;
-  return (b & 0x8000u) ? (~b & 0xFFFFu) : (b | 0x8000u);
-}
-__device__ __forceinline__ float smp_key_value(unsigned k) {
-  const unsigned b = (k & 0x8000u) ? (k & 0x7FFFu) : (~k & 0xFFFFu);
-  return __uint_as_float(b << 16);
-}
-
-// Q40 weight of a key: 2^40 exactly at the maximum (also m = +-inf), 0 for -inf below it and below 2^-40
-__device__ __forceinline__ u64 smp_weight(unsigned key, unsigned mkey, float xm, float c) {
-  if (key == mkey) return SMP_ONE;
-  if (key <= SMP_KEY_NINF) return 0ull;
-  const float a = (smp_key_value(key) - xm) * c;
-  if (!(a > -41.f)) return 0ull;               // also a NaN (0 x inf at a temperature outside what the host admits)
-  return (u64)(__builtin_amdgcn_exp2f(a) * 0x1p40f);
-}
-
-struct SmpRow {
-  const u32x4* base;     // 16-byte boundary at or below the row start
-  long long nt;          // tiles of 8 elements
-  int off;               // row element 0 is element `off` of tile 0
-  int V;
-};
 
 // The repetition penalty of the controlled form: the row's bitmap of seen tokens as bytes (bit i & 7 of byte i >> 3 = bit i & 31 of
 // word i >> 5) and the row's r; bits == NULL when r == 1 (uniform per workgroup: nothing is fetched then).  SmpNoPen: the
@@ -214,12 +186,6 @@ struct SmpPenAdj : SmpPenFsm {
   const unsigned char* bbits;
   const float* bval;
 };
-__device__ __forceinline__ unsigned smp_bf16_rne(float y) {
-  unsigned u = __float_as_uint(y);
-  if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (u >> 16) | 0x40u;
-  u += 0x7FFFu + ((u >> 16) & 1u);
-  return u >> 16;
-}
 __device__ __forceinline__ unsigned smp_load(const SmpRow& r, const SmpPenAdj& pen, long long j, unsigned (&key)[8]) {
   const unsigned valid = smp_load(r, static_cast<const SmpPenFsm&>(pen), j, key);
   if (pen.cbits || pen.bbits) {                  // uniform per workgroup
@@ -257,11 +223,6 @@ __device__ __forceinline__ unsigned smp_load(const SmpRow& r, const SmpPenAdj& p
   return valid;
 }
 
-__device__ __forceinline__ u64 smp_wave_sum(u64 v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 __device__ __forceinline__ u64 smp_wave_incl_scan(u64 v, int lane) {
 #pragma unroll
   for (int o = 1; o < 64; o <<= 1) {
@@ -390,13 +351,6 @@ struct SmpLpLds {
 };
 struct SmpNoLds {};
 
-// lp of a key: (x' - m) - lse in fp32; -lse at the maximum (also m = +-inf), -inf for -inf < m
-__device__ __forceinline__ float smp_lp(unsigned key, unsigned mkey, float xm, float lse) {
-  if (key == mkey) return -lse;
-  if (key <= SMP_KEY_NINF) return -__builtin_inff();
-  return (smp_key_value(key) - xm) - lse;
-}
-
 // Passes L1-L3, by every thread of the workgroup, while `hist`, `sub`, `wsum` and the sh_ words are free; returns lse and leaves
 // the min(n_top, nrow) survivors in L.cand (nrow: the tokens of the row, V or a constrained row's |A|).  Ends on a barrier.
 // counted: hist already holds the row's coarse counts (pass 1 made them for top-k, whose scan only read them).
@@ -439,7 +393,7 @@ __device__ __forceinline__ float smp_lp_phase(const SmpRow& r, const PEN& pen, i
   u64 Z1 = 0ull;
 #pragma unroll
   for (int w = 0; w < SMP_WAVES; ++w) Z1 += wsum[w];
-  const float lse = logf((float)Z1 * 0x1p-40f);        // 2^40 <= Z1 < 2^63: the conversion rounds to nearest even, the scaling is exact
+  const float lse = smp_lse(Z1);
   if (nsel == 0u) { __syncthreads(); return lse; }
   __syncthreads();                                     // wsum has been read by every thread
   // ---- the bin where the count from the top reaches nsel, then L2: the key inside it
@@ -720,11 +674,7 @@ sample_rows_kernel(const bf16_t* __restrict__ logits, long long ld, int V, const
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const long long s = blockIdx.x;
   const bf16_t* row = logits + s * ld;
-  SmpRow r;
-  r.off = (int)(((uintptr_t)row & 15u) >> 1);
-  r.base = (const u32x4*)(row - r.off);
-  r.V = V;
-  r.nt = ((long long)r.off + V + 7) >> 3;
+  const SmpRow r = smp_row(row, V);
 
   float tau = 0.f, p = 1.f;                             // the score-only form has no sampling parameters: it takes the greedy
   int k = 0;                                            // row's path to the scores and writes no token

@@ -761,6 +761,7 @@ class _RowField(NamedTuple):
     penalties: bool = False     # ... and only in a sampler built with penalties=True
     bias: bool = False          # ... and only in a sampler built with bias_tables
     bans: bool = False          # ... and only in a sampler built with bans=True
+    guidance: bool = False      # ... and only in a sampler built with guidance=True
     cleared: bool = False       # set() puts it back to `init` although no step changes it (state() does not save it)
 
 
@@ -847,7 +848,18 @@ class Sampler:
     runs on the edited row.  Parameters, tables and a row's table change between replays without a recapture.  THE ROW'S
     SEQUENCE is "context in mark() order, then this turn's generated tokens" and the window is what the two rings hold: a token
     that has been overwritten no longer counts, and when a live slot is extended mid-answer that order is not the chronological
-    one (the new prompt tokens stand in front of the answer's).  None of these rows is handed to ops.sample_tokens."""
+    one (the new prompt tokens stand in front of the answer's).  None of these rows is handed to ops.sample_tokens.
+
+    Guidance (`guidance_scale` with `negative_prompt_ids` of HF generate; cd_alpha / cd_beta of visual contrastive decoding):
+    a sampler built with `guidance=True` holds guide_partner (-1 = not guided), guide_scale and guide_cut per row.
+    set_guidance(row, partner, scale, plausibility) makes `row` the LEADER of a guided stream whose negative stream runs in
+    the row `partner`.  sample() over all rows then launches ops.guide_logits (ivl_logit_guide_fwd, GUIDE-0..5) in front of
+    the bans -- the leader's logits row becomes bf16(lu + s (lc - lu)) of the two rows' log-softmaxes IN the logits it is given,
+    and bans, adjustments, scores and the draw run on the edited row -- and ops.rows_follow behind the draw: the partner's
+    token and done code become the leader's.  Scale, cut and pairing change between replays without a recapture.  The
+    single-row form of sample() launches neither: whoever draws one row of a pair guides and copies himself
+    (GraphedMultiStreamDecode.admit_guided).  The partner's own row stays an ordinary row: leave it greedy, without stop ids or a
+    budget.  A sampler built without `guidance` launches what it always did."""
 
     # THE list of the per-row tensors: each is an attribute of its name, [n_rows, *shape], or None when the sampler does not hold
     # it.  row_tensors() (so every fork and beam gather), state() / load_state(), what set() clears and the keywords of
@@ -885,20 +897,25 @@ class Sampler:
         _RowField("ban_idx", torch.int32, (), -1, bans=True, cleared=True),                         # -1 = no table
         _RowField("ctx", torch.int64, ("context",), 0, bans=True),                                  # the ring mark() pushes into
         _RowField("n_ctx", torch.int64, (), 0, bans=True, cleared=True),                            # tokens pushed so far
+        # the rows of ops.guide_logits / ops.rows_follow (kw None: ops.sample_tokens never sees them)
+        _RowField("guide_partner", torch.int32, (), -1, guidance=True, cleared=True),               # -1 = the row is not guided
+        _RowField("guide_scale", torch.float32, (), 1.0, guidance=True),
+        _RowField("guide_cut", torch.float32, (), -math.inf, guidance=True),                        # ln(beta); -inf = off
     )
 
     def __init__(self, n_rows: int, device, vocab_size: Optional[int] = None, max_stop: int = 8, history: int = 0,
                  logprobs: Optional[int] = None, *, score_rings: bool = True, grammar_states: int = 0,
                  grammar_slots: Optional[int] = None, grammar_trans: Optional[int] = None, penalties: bool = False,
                  bias_tables: int = 0, bans: bool = False, ban_context: int = 256, ban_tables: int = 0, ban_seqs: int = 64,
-                 ban_len: int = 8):
+                 ban_len: int = 8, guidance: bool = False):
         """score_rings=False: no per-token score rings (lp_history, top_hist_ids, top_hist_lp) beside the token history.
         grammar_states: the states of all grammars loaded at a time; grammar_slots: how many grammars (default: one per row);
         grammar_trans: their transition entries, n_states x n_classes each (default: 256 per state).  penalties: min-p and the
         frequency / presence penalties with the rows' counts; bias_tables: how many logit-bias tables at a time (both: vocab_size).
         bans: the token bans in front of the sampling launch (needs history > 0); ban_context: the length of the context ring
         (0: none, the bans see the generated tokens alone); ban_tables: how many bad-words tables at a time, each of up to
-        ban_seqs sequences of up to ban_len tokens."""
+        ban_seqs sequences of up to ban_len tokens.  guidance: the guidance launch in front of the bans and the follow launch behind
+        the draw (set_guidance)."""
         if n_rows < 1:
             raise ValueError(f"Sampler: n_rows must be >= 1; got {n_rows}")
         if vocab_size is not None and (isinstance(vocab_size, bool) or not isinstance(vocab_size, int) or vocab_size < 1):
@@ -933,8 +950,15 @@ class Sampler:
         if bans and history + ban_context > ops.BAN_WINDOW:
             raise ValueError(f"Sampler: history + ban_context = {history} + {ban_context} tokens; the bans stage at most "
                              f"{ops.BAN_WINDOW}")
+        if not isinstance(guidance, bool):
+            raise ValueError(f"Sampler: guidance must be a bool; got {guidance!r}")
+        if guidance and n_rows > ops.GUIDE_ROWS:
+            raise ValueError(f"Sampler: guidance=True serves at most {ops.GUIDE_ROWS} rows; got {n_rows}")
         self.n_rows = int(n_rows)
         self.penalties = penalties
+        self.guidance = guidance
+        self._partner = {}                               # {leader row: partner row} (host copy of guide_partner)
+        self._guide_params = {}                          # {leader row: (guidance_scale, plausibility)} as they were given
         self.bans = bans
         self.bad_words = ops.BanTables(device, ban_tables, ban_seqs, ban_len) if ban_tables else None    # the arena of the tables
         self.biases = ops.BiasTables(device, vocab_size, bias_tables) if bias_tables else None      # the arena of the bias tables
@@ -950,7 +974,8 @@ class Sampler:
         for f in self._TABLE:
             shape = [extent[e] for e in f.shape]
             held = all(shape) and (logprobs is not None or not f.score) and (self.grammars is not None or not f.grammar) and \
-                (penalties or not f.penalties) and (self.biases is not None or not f.bias) and (bans or not f.bans)
+                (penalties or not f.penalties) and (self.biases is not None or not f.bias) and (bans or not f.bans) and \
+                (guidance or not f.guidance)
             setattr(self, f.name, torch.full((n_rows, *shape), f.init, dtype=f.dtype, device=device) if held else None)
             if held:
                 self._fields.append(f)
@@ -1096,6 +1121,8 @@ class Sampler:
         for f in self._fields:
             if f.state or f.cleared:
                 getattr(self, f.name)[row] = f.init
+        self._partner.pop(row, None)                     # (guide_partner is cleared: the row leads no pair; set_guidance follows)
+        self._guide_params.pop(row, None)
 
     # ---- a row's parameters and state as one row of every tensor: fork ---------------------------------------------------
     def row_tensors(self) -> List[torch.Tensor]:
@@ -1125,6 +1152,7 @@ class Sampler:
         of temperature / top_k / top_p / seed, checked as in set() and applied WITHOUT clearing the copied state; a given
         seed restarts that row's counter at 0 (an independent random stream over the same history)."""
         src, dsts, overrides = self._check_fork("Sampler.fork", src, dsts, sampling)
+        self._refuse_guided("Sampler.fork", [src, *dsts])
         if self._fork_plan is None:
             self._fork_plan = ops.RowCopyPlan([(t, t) for t in self.row_tensors()])
         self._fork_plan.run(src, dsts)
@@ -1182,6 +1210,71 @@ class Sampler:
         if handle is not None and handle not in arena.handles():
             raise ValueError(f"Sampler.set_bad_words: {handle!r} is not loaded in this sampler")
         self.ban_idx[row] = -1 if handle is None else handle.index
+
+    # ---- guidance ------------------------------------------------------------------------------------------------------------
+    def guided_role(self, row: int) -> Optional[str]:
+        """"leader" / "partner" of a row that belongs to a guided pair, else None (host)."""
+        return "leader" if row in self._partner else "partner" if row in self._partner.values() else None
+
+    def leader_of(self, row: int) -> Optional[int]:
+        """The leader whose partner `row` is, else None (host)."""
+        return next((r for r, p in self._partner.items() if p == row), None)
+
+    def _refuse_guided(self, who: str, rows) -> None:
+        for r in rows:
+            role = self.guided_role(r)
+            if role is not None:
+                raise ValueError(f"{who}: row {r} is the {role} of a guided pair (a copied row would carry the partner index "
+                                 f"verbatim); clear_guidance or release the pair first")
+
+    def _checked_guidance(self, who: str, guidance_scale, plausibility) -> Tuple[float, float]:
+        """(scale, cut = ln(beta)) as the fp32 values the launch gets; no device work."""
+        for name, v in (("guidance_scale", guidance_scale), ("plausibility", plausibility)):
+            if isinstance(v, bool) or not isinstance(v, (int, float)):
+                raise ValueError(f"{who}: {name} must be a number; got {v!r}")
+        s, beta = float(guidance_scale), float(plausibility)
+        if not (math.isfinite(s) and math.isfinite(float(torch.tensor(s, dtype=torch.float32)))):
+            raise ValueError(f"{who}: guidance_scale must be finite (in fp32); got {guidance_scale!r}")
+        if not 0.0 <= beta < 1.0:
+            raise ValueError(f"{who}: plausibility (beta: a token survives when p(v) >= beta max p) must be in [0, 1); got "
+                             f"{plausibility!r}")
+        return s, (math.log(beta) if beta > 0.0 else -math.inf)
+
+    def set_guidance(self, row: int, partner: int, guidance_scale: float, plausibility: float = 0.0) -> None:
+        """`row` leads a guided stream whose negative stream runs in the row `partner`, from the next sample() over all rows on:
+        out = uncond + guidance_scale (cond - uncond) on log-softmaxes (HF's guidance_scale; VCD's 1 + cd_alpha), and with
+        plausibility = beta in (0, 1) a token whose probability under the leader's row is below beta times the largest is
+        dropped (VCD's cd_beta; 0 = off).  Called again on a leader with the same partner it changes the two numbers.
+        Refused: a non-finite scale, beta outside [0, 1), a partner out of range or equal to the row, a partner that is a
+        leader or already someone's partner, a leader that is someone's partner."""
+        if not self.guidance:
+            raise ValueError("Sampler.set_guidance: needs a Sampler built with guidance=True")
+        row = self._row(row)
+        s, cut = self._checked_guidance("Sampler.set_guidance", guidance_scale, plausibility)
+        if isinstance(partner, bool) or not isinstance(partner, int) or not 0 <= partner < self.n_rows or partner == row:
+            raise ValueError(f"Sampler.set_guidance: partner must be an int in [0, {self.n_rows}) other than the row {row}; got "
+                             f"{partner!r}")
+        if partner in self._partner:
+            raise ValueError(f"Sampler.set_guidance: row {partner} leads a pair itself (a partner is never a leader)")
+        if self.leader_of(partner) not in (None, row):
+            raise ValueError(f"Sampler.set_guidance: row {partner} is already the partner of row {self.leader_of(partner)}")
+        if self.leader_of(row) is not None:
+            raise ValueError(f"Sampler.set_guidance: row {row} is the partner of row {self.leader_of(row)} (a partner is never a "
+                             f"leader)")
+        self.guide_scale[row] = s
+        self.guide_cut[row] = cut
+        self.guide_partner[row] = partner
+        self._partner[row] = partner
+        self._guide_params[row] = (float(guidance_scale), float(plausibility))
+
+    def clear_guidance(self, row: int) -> None:
+        """`row` leads no pair from its next draw on; its former partner is an ordinary row again."""
+        if not self.guidance:
+            raise ValueError("Sampler.clear_guidance: needs a Sampler built with guidance=True")
+        row = self._row(row)
+        self.guide_partner[row] = -1
+        self._partner.pop(row, None)
+        self._guide_params.pop(row, None)
 
     # ---- constrained decoding ------------------------------------------------------------------------------------------------
     def _arena(self, who: str) -> "ops.FsmTables":
@@ -1308,6 +1401,9 @@ class Sampler:
                 kw["fsm"] = self.grammars
             if self.biases is not None:
                 kw["bias"] = self.biases
+        guided = self.guidance and row is None           # (one row of a pair alone: whoever draws it guides and copies himself)
+        if guided:                                       # a leader's row becomes the guided logits in `logits` itself
+            ops.guide_logits(logits, partner=self.guide_partner, scale=self.guide_scale, cut=self.guide_cut, done=self.done)
         if self.bans:                                    # the banned tokens of these rows become -inf in `logits` itself
             ban = {"ctx": self.ctx[sl], "n_ctx": self.n_ctx[sl]} if self.ctx is not None else {}
             if self.stop_ids is not None:
@@ -1315,8 +1411,11 @@ class Sampler:
             if self.bad_words is not None:
                 ban.update(ban_idx=self.ban_idx[sl], words=self.bad_words)
             ops.ban_tokens(logits, n_new=self.n_new[sl], history=self.history[sl], done=self.done[sl], ngram=self.ngram[sl], **ban)
-        return ops.sample_tokens(logits, self.temperature[sl], self.top_k[sl], self.top_p[sl], self.seed[sl], self.counter[sl],
-                                 out=out, **kw)
+        out = ops.sample_tokens(logits, self.temperature[sl], self.top_k[sl], self.top_p[sl], self.seed[sl], self.counter[sl],
+                                out=out, **kw)
+        if guided:                                       # the partners take their leaders' tokens and done codes
+            ops.rows_follow(out, self.guide_partner, self.done)
+        return out
 
 
 # the names and defaults of set()'s keywords are stated once, in its signature: set() and admit_n read them from here
@@ -1412,6 +1511,7 @@ class GraphedMultiStreamDecode(_Graphed):
         self._slot_adapter = [None] * self.S             # the handles behind adapter_ids (the prefill calls take them)
         self._held = set()                               # slots between hold and resume
         self._parked = None
+        self._guide_scratch = self._guide_pair = None    # [2,vocab] bf16 and its partner table: a pair's eager first draw
         if self.holds:
             self._parked = torch.zeros(self.S, 1, dtype=torch.int64, device=p_.device)      # the pending token of a held slot
             cache.enable_holds(sampler.done, advance=False)                                  # (_run advances both counters)
@@ -1445,27 +1545,34 @@ class GraphedMultiStreamDecode(_Graphed):
 
     def hold(self, slot: int) -> None:
         """The live, running slot `slot` sits out the steps from the next replay on (done code 4): its pending token is parked,
-        its state, position and sampler row stay as they are.  Between replays; never a recapture."""
+        its state, position and sampler row stay as they are.  Between replays; never a recapture.  The leader of a guided
+        pair takes its partner along (both tokens and both done codes); a partner is not held on its own."""
         self._need_holds("hold")
         slot = self._slots("hold", [slot])[0]
+        self._refuse_pair("hold", [slot], leader_ok=True)
         if slot not in self._live:
             raise ValueError(f"hold: slot {slot} holds no stream (admit or load it first)")
         code = int(self.sampler.done[slot])
         if code != 0:
             raise ValueError(f"hold: slot {slot} is not running (done code {code})")
-        self._parked[slot].copy_(self.token[slot])
-        self.sampler.done[slot] = self.HELD
-        self._held.add(slot)
+        for s in (slot, self._pair(slot)):
+            if s is not None:
+                self._parked[s].copy_(self.token[s])
+                self.sampler.done[s] = self.HELD
+                self._held.add(s)
 
     def resume(self, slot: int) -> None:
         """The held slot `slot` runs again from the next replay on, with the token it was held with."""
         self._need_holds("resume")
         slot = self._slots("resume", [slot])[0]
+        self._refuse_pair("resume", [slot], leader_ok=True)
         if slot not in self._held:
             raise ValueError(f"resume: slot {slot} is not held")
-        self.token[slot].copy_(self._parked[slot])
-        self.sampler.done[slot] = 0
-        self._held.discard(slot)
+        for s in (slot, self._pair(slot)):               # (a guided pair was held together)
+            if s is not None:
+                self.token[s].copy_(self._parked[s])
+                self.sampler.done[s] = 0
+                self._held.discard(s)
 
     def set_adapter(self, slot: int, adapter) -> None:
         """The slot decodes under `adapter` (a handle of model.load_adapter; None = the base model) from the next step on: one
@@ -1490,13 +1597,22 @@ class GraphedMultiStreamDecode(_Graphed):
         state, set after the row's parameters and before the first draw, so the first token is constrained too.  `adapter`: the stream's LoRA adapter
         (set_adapter); the prompt is prefilled under it.  `logit_bias` (a handle of Sampler.load_logit_bias): the row's bias
         table, set before the first draw like the grammar.  `bad_words` (a handle of Sampler.load_bad_words): the row's table of
-        banned sequences, set before the first draw too."""
+        banned sequences, set before the first draw too.  Refused on a slot of a guided pair: release the pair's leader first."""
+        self._refuse_pair("admit", [slot])
+        lg = self._start("admit", slot, inputs_embeds, position_ids, sampling, prompt_ids, grammar, adapter, logit_bias, bad_words)
+        self._draw(slot, lg)
+        return self.token[slot]
+
+    def _start(self, who: str, slot: int, inputs_embeds, position_ids, sampling, prompt_ids, grammar, adapter, logit_bias, bad_words,
+               then=None) -> torch.Tensor:
+        """An admission up to the first draw: the checks, the slot's sampler row (`then`, when given, runs once it is set), the
+        prompt's prefill and the slot's next M-RoPE position.  Returns the prompt's last logits [1,1,vocab] (admit_logits)."""
         if sampling is not None and self.sampler is None:
-            raise ValueError("admit: sampling parameters need a GraphedMultiStreamDecode built with a sampler")
-        self._check_grammar("admit", grammar)
-        self._check_bias("admit", logit_bias)
-        self._check_bad_words("admit", bad_words)
-        T = self._check_prompt("admit", inputs_embeds, position_ids, prompt_ids)
+            raise ValueError(f"{who}: sampling parameters need a GraphedMultiStreamDecode built with a sampler")
+        self._check_grammar(who, grammar)
+        self._check_bias(who, logit_bias)
+        self._check_bad_words(who, bad_words)
+        T = self._check_prompt(who, inputs_embeds, position_ids, prompt_ids)
         self.set_adapter(slot, adapter)
         if position_ids is None:
             position_ids = _text_positions(T, inputs_embeds.device)
@@ -1508,6 +1624,8 @@ class GraphedMultiStreamDecode(_Graphed):
             self.sampler.set_logit_bias(slot, logit_bias)
         if bad_words is not None:
             self.sampler.set_bad_words(slot, bad_words)
+        if then is not None:
+            then()
         if prompt_ids is not None:
             self.sampler.mark(slot, prompt_ids.to(inputs_embeds.device))
         self.cache.admit(slot)
@@ -1515,9 +1633,88 @@ class GraphedMultiStreamDecode(_Graphed):
         self._unhold(slot)
         lg = self._prefill(slot, inputs_embeds, position_ids)
         self.admit_logits = lg                          # [1,1,vocab]: what the latest admission's first token was taken from
-        self._draw(slot, lg)
         self.position_ids[:, slot].fill_(int(position_ids.max()) + 1)        # the next M-RoPE text position
+        return lg
+
+    # ---- guided pairs -------------------------------------------------------------------------------------------------------
+    def _pair(self, slot: int) -> Optional[int]:
+        """The partner slot of the leader `slot`, else None."""
+        return self.sampler._partner.get(slot) if self.sampler is not None else None
+
+    def _refuse_pair(self, who: str, slots, leader_ok: bool = False) -> None:
+        """ValueError when one of `slots` belongs to a guided pair (leader_ok: only when it is a partner)."""
+        if self.sampler is None:
+            return
+        for s in slots:
+            role = self.sampler.guided_role(s) if isinstance(s, int) and not isinstance(s, bool) else None
+            if role == "partner":
+                raise ValueError(f"{who}: slot {s} is the partner of the guided slot {self.sampler.leader_of(s)}: it follows its "
+                                 f"leader (call this on the leader, or release the leader first)")
+            if role == "leader" and not leader_ok:
+                raise ValueError(f"{who}: slot {s} leads a guided pair (with slot {self._pair(s)}): not supported for a guided "
+                                 f"stream; release it first")
+
+    def _draw_guided(self, slot: int, partner: int, lg: torch.Tensor, lgn: torch.Tensor) -> None:
+        """token[slot] from the guided combination of the two prompts' last logits lg, lgn [1,1,vocab], in the leader's sampler
+        row; the partner takes the same token and the leader's done code.  The pair is guided on a [2,vocab] scratch of this
+        class, rows (leader, partner), with the leader's scale and cut: the first token is guided as every later one."""
+        smp, V = self.sampler, lg.shape[-1]
+        if self._guide_scratch is None or self._guide_scratch.shape[1] != V:
+            self._guide_scratch = torch.empty(2, V, dtype=torch.bfloat16, device=lg.device)
+            self._guide_pair = torch.tensor([1, -1], dtype=torch.int32, device=lg.device)
+        g = self._guide_scratch
+        g[0].copy_(lg[0, -1])
+        g[1].copy_(lgn[0, -1])
+        ops.guide_logits(g, partner=self._guide_pair, scale=torch.cat([smp.guide_scale[slot:slot + 1], smp.guide_scale.new_ones(1)]),
+                         cut=torch.cat([smp.guide_cut[slot:slot + 1], smp.guide_cut.new_full((1,), -math.inf)]))
+        self.admit_logits = g[0:1].unsqueeze(1)          # (the guided row, as the leader's draw sees it before its bans)
+        smp.sample(g[0:1], self.token[slot:slot + 1], row=slot)
+        self.token[partner].copy_(self.token[slot])
+        smp.done[partner:partner + 1].copy_(smp.done[slot:slot + 1])
+
+    @torch.no_grad()
+    def admit_guided(self, slot: int, partner: int, inputs_embeds: torch.Tensor, negative_embeds: torch.Tensor, *,
+                     guidance_scale: float, plausibility: float = 0.0, position_ids: Optional[torch.Tensor] = None,
+                     negative_position_ids: Optional[torch.Tensor] = None, sampling: Optional[dict] = None,
+                     prompt_ids: Optional[torch.Tensor] = None, grammar=None, adapter=None, logit_bias=None,
+                     bad_words=None) -> torch.Tensor:
+        """Start a GUIDED stream in the two slots `slot` (the leader: the prompt inputs_embeds, and the sampler row that
+        `sampling`, `prompt_ids`, `grammar`, `logit_bias` and `bad_words` configure, as in admit) and `partner` (the negative
+        prompt negative_embeds [1,Tn,hidden]: the question without the image, a distorted frame, or just the last token; its
+        sampler row is set greedy, without stop ids or a budget).  Needs a sampler built with guidance=True.  Every step then
+        draws the leader's token from bf16(lu + guidance_scale (lc - lu)) of the two slots' log-softmaxes (HF's guidance_scale
+        with negative_prompt_ids; with guidance_scale = 1 + cd_alpha and plausibility = cd_beta visual contrastive decoding) and
+        feeds it to BOTH slots, inside the captured step and with no recapture.  Both prompts are prefilled eagerly (under
+        `adapter`), the first token is guided too, and it is written to token[slot] and token[partner] and returned."""
+        if self.sampler is None or not self.sampler.guidance:
+            raise ValueError("admit_guided: needs a GraphedMultiStreamDecode whose sampler was built with guidance=True")
+        slot, partner = self._slots("admit_guided", [slot, partner])
+        self._refuse_pair("admit_guided", [slot, partner])
+        self.sampler._checked_guidance("admit_guided", guidance_scale, plausibility)
+        if sampling is not None:
+            self.sampler._checked("admit_guided", sampling)                  # (refused before anything is written)
+        self._check_prompt("admit_guided", inputs_embeds, position_ids, prompt_ids)
+        self._check_prompt("admit_guided", negative_embeds, negative_position_ids, None)
+        self._check_grammar("admit_guided", grammar)
+        self._check_bias("admit_guided", logit_bias)
+        self._check_bad_words("admit_guided", bad_words)
+        self.sampler.set(partner)                        # greedy, no stop ids, no budget: the partner follows its leader
+        lgn = self._start("admit_guided", partner, negative_embeds, negative_position_ids, None, None, None, adapter, None, None)
+        lg = self._start("admit_guided", slot, inputs_embeds, position_ids, sampling, prompt_ids, grammar, adapter, logit_bias,
+                         bad_words, then=lambda: self.sampler.set_guidance(slot, partner, guidance_scale, plausibility))
+        self._draw_guided(slot, partner, lg, lgn)
         return self.token[slot]
+
+    def set_guidance(self, slot: int, guidance_scale: Optional[float] = None, plausibility: Optional[float] = None) -> None:
+        """The guided slot `slot` draws under another guidance_scale and / or plausibility from the next step on (None: as it
+        is): two writes to the sampler's table between replays, never a recapture."""
+        slot = self._slots("set_guidance", [slot])[0]
+        partner = self._pair(slot)
+        if partner is None:
+            raise ValueError(f"set_guidance: slot {slot} leads no guided pair (admit_guided starts one)")
+        s, beta = self.sampler._guide_params[slot]
+        self.sampler.set_guidance(slot, partner, s if guidance_scale is None else guidance_scale,
+                                  beta if plausibility is None else plausibility)
 
     def _prefill(self, slot: int, inputs_embeds: torch.Tensor, position_ids: torch.Tensor) -> torch.Tensor:
         """Runs prompt tokens through the stack on the slot's B = 1 view, in calls of PREFILL_CHUNK; the last call's logits."""
@@ -1612,6 +1809,7 @@ class GraphedMultiStreamDecode(_Graphed):
             raise ValueError(f"fork: the destination slots {dsts} contain the source slot {src}")
         if src not in self._live:
             raise ValueError(f"fork: slot {src} holds no stream (admit or load it first)")
+        self._refuse_pair("fork", [src, *dsts])
         if sampling is not None and self.sampler is None:
             raise ValueError("fork: sampling parameters need a GraphedMultiStreamDecode built with a sampler")
         overrides = None
@@ -1626,7 +1824,8 @@ class GraphedMultiStreamDecode(_Graphed):
     @torch.no_grad()
     def extend(self, slot: int, inputs_embeds: torch.Tensor, position_ids: Optional[torch.Tensor] = None,
                prompt_ids: Optional[torch.Tensor] = None, grammar=None, max_new_tokens=_UNCHANGED,
-               stop_token_ids=_UNCHANGED) -> torch.Tensor:
+               stop_token_ids=_UNCHANGED, negative_embeds: Optional[torch.Tensor] = None,
+               negative_position_ids: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Continue the live slot `slot` with more prompt tokens inputs_embeds [1,T,hidden] -- a question, the next video
         frame -- on its B = 1 view.  position_ids [3,1,T]; default: each of the slot's three positions counts on from
         position_ids[:, slot].  The slot's next token is drawn from the last logits (in the sampler's launch, after
@@ -1637,12 +1836,25 @@ class GraphedMultiStreamDecode(_Graphed):
         and cum_logprob are cleared, so tokens(slot) and the score rings hold the new answer only; seen, count, the random counter
         and the grammar state stay; a sampler with a context ring (bans=True) gets the finished answer, tokens(slot), appended to
         the ring first, so the next turn's bans still see it.  The token that ended the last turn was never fed to the model; it belongs in inputs_embeds
-        if the conversation's template has it."""
+        if the conversation's template has it.
+        The leader of a guided pair needs `negative_embeds` [1,Tn,hidden] (negative_position_ids [3,1,Tn]; default: counting on
+        from the partner's positions): the partner's half of the new prompt.  Both halves are prefilled, the next token is
+        guided and goes to both slots, and a frozen partner starts its next turn with its leader.  A partner is not extended
+        on its own, and a slot that leads no pair takes no negative_embeds."""
         slot = self._slots("extend", [slot])[0]
         if slot not in self._live:
             raise ValueError(f"extend: slot {slot} holds no stream (admit or load it first)")
+        self._refuse_pair("extend", [slot], leader_ok=True)
+        partner = self._pair(slot)
+        if (partner is None) != (negative_embeds is None):
+            raise ValueError(f"extend: slot {slot} leads a guided pair with slot {partner}: negative_embeds (the partner's half of "
+                             f"the prompt) is required" if partner is not None else
+                             f"extend: negative_embeds is for the leader of a guided pair; slot {slot} leads none")
+        if negative_embeds is None and negative_position_ids is not None:
+            raise ValueError("extend: negative_position_ids come with negative_embeds")
         self._check_grammar("extend", grammar)
         T = self._check_prompt("extend", inputs_embeds, position_ids, prompt_ids)
+        Tn = self._check_prompt("extend", negative_embeds, negative_position_ids, None) if partner is not None else 0
         ends = {k: v for k, v in (("max_new_tokens", max_new_tokens), ("stop_token_ids", stop_token_ids)) if v is not Sampler._UNCHANGED}
         if ends and self.sampler is None:
             raise ValueError("extend: max_new_tokens / stop_token_ids need a GraphedMultiStreamDecode built with a sampler")
@@ -1656,6 +1868,9 @@ class GraphedMultiStreamDecode(_Graphed):
             if self.sampler.cum_logprob is not None:
                 self.sampler.cum_logprob[slot] = 0.0
             self._held.discard(slot)                     # (the draw below replaces the parked token too)
+            if partner is not None:                      # (it froze with its leader; its own row counts nothing that is read)
+                self.sampler.done[partner] = 0
+                self._held.discard(partner)
         if ends:
             self.sampler.set_ends(slot, **ends)
         if grammar is not None:
@@ -1666,7 +1881,15 @@ class GraphedMultiStreamDecode(_Graphed):
             self.sampler.mark(slot, prompt_ids.to(inputs_embeds.device))
         lg = self._prefill(slot, inputs_embeds, position_ids)
         self.admit_logits = lg
-        self._draw(slot, lg)
+        if partner is None:
+            self._draw(slot, lg)
+        else:
+            if negative_position_ids is None:
+                negative_position_ids = self.position_ids[:, partner:partner + 1] + \
+                    torch.arange(Tn, device=self.position_ids.device, dtype=torch.int64)
+            lgn = self._prefill(partner, negative_embeds, negative_position_ids)
+            self._draw_guided(slot, partner, lg, lgn)
+            self.position_ids[:, partner].copy_(negative_position_ids.max() + 1)
         self.position_ids[:, slot].copy_(position_ids.max() + 1)
         return self.token[slot]
 
@@ -1681,6 +1904,7 @@ class GraphedMultiStreamDecode(_Graphed):
         Ranking candidate answers by likelihood without polluting the stream: fork(src, dsts) -> score(dst, candidate) for
         each -> release(dst); `src` is only read by the fork."""
         slot = self._slots("score", [slot])[0]
+        self._refuse_pair("score", [slot])
         if slot not in self._live:
             raise ValueError(f"score: slot {slot} holds no stream (admit or load it first)")
         T = self._check_prompt("score", inputs_embeds, position_ids, None)
@@ -1704,6 +1928,7 @@ class GraphedMultiStreamDecode(_Graphed):
         prompt_ids=prompt_ids) would leave it.  `grammar`: every slot starts in that grammar's start state; `logit_bias`: every slot
         draws under that bias table; `bad_words`: and under that table of banned sequences.  Returns token[slots]."""
         slots = self._slots("admit_n", slots)
+        self._refuse_pair("admit_n", slots)
         self._check_grammar("admit_n", grammar)
         self._check_bias("admit_n", logit_bias)
         self._check_bad_words("admit_n", bad_words)
@@ -1757,6 +1982,7 @@ class GraphedMultiStreamDecode(_Graphed):
         as in admit; `grammar`: every slot is put into that grammar's start state, for the draw of the extend that follows.
         `logit_bias`: every slot draws under that bias table; `bad_words`: and under that table of banned sequences.  No token is pending afterwards: extend(slot, question) follows."""
         slots = self._slots("load", slots)
+        self._refuse_pair("load", slots)
         self._check_grammar("load", grammar)
         self._check_bias("load", logit_bias)
         self._check_bad_words("load", bad_words)
@@ -1785,7 +2011,13 @@ class GraphedMultiStreamDecode(_Graphed):
             self._unhold(s)
 
     def release(self, slot: int) -> None:
-        """End the stream in `slot`: its state is zeroed (the slot keeps computing on zeros until the next admit)."""
+        """End the stream in `slot`: its state is zeroed (the slot keeps computing on zeros until the next admit).  The leader
+        of a guided pair releases both slots and clears the pair; a partner is refused (release its leader)."""
+        self._refuse_pair("release", [slot], leader_ok=True)
+        partner = self._pair(slot)
+        if partner is not None:
+            self.sampler.clear_guidance(slot)
+            self.release(partner)
         self.cache.release(slot)
         self._live.discard(slot)
         self._held.discard(slot)
@@ -1857,6 +2089,9 @@ class GraphedBeamDecode(GraphedMultiStreamDecode):
         if sampler is not None and sampler.bans:
             raise ValueError("GraphedBeamDecode: the sampler was built with bans=True: token bans are not part of beam search (a "
                              "beam's candidates come from the score-only launch, with no ban launch in front of it)")
+        if sampler is not None and sampler.guidance:
+            raise ValueError("GraphedBeamDecode: the sampler was built with guidance=True: guidance is not part of beam search (a "
+                             "beam's rows are gathered every step; a pair of slots would not stay a pair)")
         if sampler is not None and sampler.grammars is not None:
             raise ValueError("GraphedBeamDecode: the sampler was built with grammar_states: constrained beam search is not "
                              "supported (a beam's candidates come from the score-only launch, which reads no grammar)")

@@ -2439,6 +2439,75 @@ def ban_tokens(logits: torch.Tensor, *, n_new: torch.Tensor, history: Optional[t
 
 
 # ---------------------------------------------------------------------------------------------
+# guidance on paired rows: classifier-free guidance / contrastive decoding in front of the sampling launch
+# ---------------------------------------------------------------------------------------------
+GUIDE_CALLS = {"guide": 0, "follow": 0}     # calls that went to ivl_logit_guide_fwd / ivl_rows_follow_fwd (tests and tools read it)
+GUIDE_ROWS = 63                             # rows of either launch
+
+
+def _guide_rows(who: str, S: int, **tables) -> None:
+    """The per-row tables of the guidance launches: contiguous [S] tensors of their dtype (None = not given)."""
+    if S > GUIDE_ROWS:
+        raise ValueError(f"{who}: {S} rows (at most {GUIDE_ROWS})")
+    for name, (t, dt) in tables.items():
+        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != dt or tuple(t.shape) != (S,) or not t.is_contiguous()):
+            raise ValueError(f"{who}: {name} must be a contiguous {dt} tensor of [{S}]; got "
+                             f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+
+
+def guide_logits(logits: torch.Tensor, *, partner: torch.Tensor, scale: torch.Tensor, cut: torch.Tensor,
+                 done: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Rewrites every guided leader row of lm_head logits [S,V] or [S,1,V] (bf16, last dim contiguous) IN PLACE from the row and
+    its partner's, in one launch in front of ops.ban_tokens and ops.sample_tokens, and returns `logits` (ivl_logit_guide_fwd
+    states the semantics, GUIDE-0 to GUIDE-5): out = bf16(lu + s (lc - lu)) on the two rows' log-softmaxes -- `guidance_scale`
+    with `negative_prompt_ids` of HF generate, and with s = 1 + cd_alpha and cut = ln(cd_beta) visual contrastive decoding.
+    partner [S] int32: row r's partner row, anything outside [0, S) or r itself = the row is not guided; scale [S] fp32: s;
+    cut [S] fp32: ln(beta) of the plausibility rule (an element more than that below the leader's maximum becomes -inf), -inf =
+    off; done [S] int32: a row that is finished is not touched.  Partner rows and rows that are off keep every bit.  The call is
+    not idempotent: it is meant for freshly written logits."""
+    given = logits
+    if logits.dim() == 3 and logits.shape[1] == 1:
+        logits = logits[:, 0]
+    if logits.dim() != 2 or logits.dtype != torch.bfloat16 or logits.shape[0] < 1 or logits.shape[1] < 1:
+        raise ValueError(f"guide_logits: logits must be bf16 [S,V] or [S,1,V]; got {logits.dtype} {tuple(logits.shape)}")
+    S, V = logits.shape
+    if logits.stride(1) != 1 or (S > 1 and logits.stride(0) < V):
+        raise ValueError(f"guide_logits: the last dim of logits must be contiguous and the rows apart (strides {logits.stride()})")
+    if V >= 2 ** 23:
+        raise ValueError(f"guide_logits: {V} tokens (below 2^23 only)")
+    if partner is None or scale is None or cut is None:
+        raise ValueError("guide_logits: partner, scale and cut are needed")
+    _guide_rows("guide_logits", S, partner=(partner, torch.int32), scale=(scale, torch.float32), cut=(cut, torch.float32),
+                done=(done, torch.int32))
+    _need_gpu(logits, partner, scale, cut, done)
+    GUIDE_CALLS["guide"] += 1
+    _lib.check(_lib.load().ivl_logit_guide_fwd(_p(logits), logits.stride(0) if S > 1 else V, S, V, _p(partner), _p(scale), _p(cut),
+                                               _p(done) if done is not None else None, _stream(logits)))
+    return given
+
+
+def rows_follow(token: torch.Tensor, partner: torch.Tensor, done: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Behind the sampling launch: the partner row of every leader (partner [S] int32, as in guide_logits, whatever the leader's
+    scale and done code) takes the leader's token -- token int64 [S] or [S,1], edited in place and returned -- and, when done
+    [S] int32 is given, the leader's done code (ivl_rows_follow_fwd): the partner's stream stays "negative prompt + the leader's
+    tokens" and ends with it.  One launch; every other element is untouched.  If several leaders name one partner the lowest
+    leader wins."""
+    if not isinstance(token, torch.Tensor) or token.dtype != torch.int64 or token.dim() not in (1, 2) or token.shape[0] < 1 or \
+            (token.dim() == 2 and token.shape[1] != 1) or token.stride(0) < 1:
+        raise ValueError(f"rows_follow: token must be int64 [S] or [S,1]; got {getattr(token, 'dtype', type(token))} "
+                         f"{tuple(getattr(token, 'shape', ()))}")
+    S = token.shape[0]
+    if partner is None:
+        raise ValueError("rows_follow: partner is needed")
+    _guide_rows("rows_follow", S, partner=(partner, torch.int32), done=(done, torch.int32))
+    _need_gpu(token, partner, done)
+    GUIDE_CALLS["follow"] += 1
+    _lib.check(_lib.load().ivl_rows_follow_fwd(_p(token), token.stride(0), _p(done) if done is not None else None, _p(partner), S,
+                                               _stream(token)))
+    return token
+
+
+# ---------------------------------------------------------------------------------------------
 # row fork: one row of many tensors to other rows, one launch
 # ---------------------------------------------------------------------------------------------
 def _byte_extent(t: torch.Tensor) -> Tuple[int, int]:

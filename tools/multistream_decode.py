@@ -143,6 +143,16 @@ is saved and put back in front of every timed run, outside the timed region.  Ti
 the spread of A's own runs.
 
     python tools/multistream_decode.py --bans [--out profiles/bans_decode.json]
+
+--guidance: the cost of guidance on paired slots (ivl_logit_guide_fwd in front of the sampling launch,
+ivl_rows_follow_fwd behind it) in the captured 4-slot step.  A: the sampled, controlled step of --adjust's leg A (a sampler built
+without guidance: what the parent commit runs); B: the same with a sampler built with guidance=True and every row off; C: two
+guided pairs (slots 0 <- 1 and 2 <- 3, guidance_scale 1.5, plausibility 0.1; the leaders sampled and controlled as in A, the
+partners greedy).  Every leg generates 64 tokens per row first; that state is saved and put back in front of every timed run,
+outside the timed region.  Timed A B C A B C, median of --rounds rounds of --steps replays.  No bar is asserted: B - A and
+C - A are reported beside the 2 % of A of the project's allowance and beside the spread of A's own runs.
+
+    python tools/multistream_decode.py --guidance [--out profiles/guidance_decode.json]
 """
 import argparse
 import json
@@ -182,6 +192,8 @@ def main():
                     help="time the step with the per-slot hold mask: off, on, half and all but one slot frozen (see above)")
     ap.add_argument("--bans", action="store_true",
                     help="time the 4-slot controlled step without the ban launch, with it and every row off, and with every rule on (see above)")
+    ap.add_argument("--guidance", action="store_true",
+                    help="time the 4-slot controlled step without the guidance launches, with them and every row off, and with two guided pairs (see above)")
     args = ap.parse_args()
     import torch
     from infinitevl_amd.cache import MultiStreamCache
@@ -214,6 +226,8 @@ def main():
         return adjust_legs(args, torch, model, cfg, prompts, dev)
     if args.bans:
         return bans_legs(args, torch, model, cfg, prompts, dev)
+    if args.guidance:
+        return guidance_legs(args, torch, model, cfg, prompts, dev)
     if args.sampling:
         return sampling_legs(args, torch, model, cfg, prompts, dev)
     if args.generation:
@@ -640,6 +654,94 @@ def bans_legs(args, torch, model, cfg, prompts, dev):
         sl = dict(n_new=smp.n_new, history=smp.history, done=smp.done, ngram=smp.ngram, ctx=smp.ctx, n_ctx=smp.n_ctx,
                   min_new=smp.min_new, stop_ids=smp.stop_ids, ban_idx=smp.ban_idx, words=smp.bad_words)
         op[f"S{n}_{name}_us"] = round(1000 * timed(lambda sl=sl: ops.ban_tokens(lg, **sl), 200, lambda: None), 2)
+    res["operator_V%d" % V] = op
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+GUIDANCE = {"guidance_scale": 1.5, "plausibility": 0.1}
+
+
+def guidance_legs(args, torch, model, cfg, prompts, dev):
+    from infinitevl_amd import ops
+    from infinitevl_amd.cache import MultiStreamCache
+    from infinitevl_amd.harness import GraphedMultiStreamDecode, Sampler
+    stream = torch.cuda.current_stream()
+    V, n = cfg.vocab_size, 4
+
+    def timed(fn, k, before):
+        for _ in range(4):
+            fn()
+        before()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        for _ in range(k):
+            fn()
+        e1.record(stream)
+        e1.synchronize()
+        return e0.elapsed_time(e1) / k
+
+    def seen_ids(s):
+        g = torch.Generator().manual_seed(100 + s)
+        return torch.randperm(V, generator=g)[:int(SEEN_FRACTION * V)].to(dev)
+
+    def sampling(s):
+        return dict(SAMPLED, seed=s + 1, stop_token_ids=[V - 1 - s, V - 9 - s], **CONTROLS)
+
+    names = ("controlled", "guidance_off", "guided_pairs")
+    res = {"tool": "multistream_decode --guidance", "layers": cfg.num_hidden_layers, "window": 4096, "slots": n, "steps": args.steps,
+           "rounds": args.rounds, "sampled": SAMPLED, "controls": dict(CONTROLS, stop_ids=2, history=HISTORY, seen_fraction=SEEN_FRACTION),
+           "guidance": dict(GUIDANCE, pairs=[[0, 1], [2, 3]], generated_tokens_per_row=GENERATED)}
+    legs, samplers, restore, launches = {}, {}, {}, {}
+    for name in names:
+        cache = MultiStreamCache(config=cfg, n_slots=n, device=dev, dtype=torch.bfloat16)
+        smp = Sampler(n, dev, vocab_size=V, history=HISTORY, **({} if name == "controlled" else {"guidance": True}))
+        dec = GraphedMultiStreamDecode(model, cache, sampler=smp)
+        before = dict(ops.GUIDE_CALLS)
+        if name == "guided_pairs":
+            for s in (0, 2):
+                dec.admit_guided(s, s + 1, prompts[s], prompts[s + 1], sampling=sampling(s), prompt_ids=seen_ids(s), **GUIDANCE)
+        else:
+            for s in range(n):
+                dec.admit(s, prompts[s], sampling=sampling(s), prompt_ids=seen_ids(s))
+        dec.capture()
+        launches[name] = {k: ops.GUIDE_CALLS[k] - before[k] for k in before}
+        for _ in range(GENERATED - 1):                          # (the admission drew the first token)
+            dec.step()
+        state = smp.state()
+        legs[name], samplers[name], restore[name] = dec.step, smp, (lambda smp=smp, state=state: smp.load_state(state))
+    times = {k: [] for k in legs}
+    for _ in range(args.rounds):                                # A B C A B C
+        for _ in range(2):
+            for name in names:
+                times[name].append(timed(legs[name], args.steps, restore[name]))
+    med = {k: statistics.median(v) for k, v in times.items()}
+    a = med["controlled"]
+    for name in names:
+        done, n_new = samplers[name].poll()
+        res[name] = {"ms_per_step": round(med[name], 4), "spread_ms": [round(min(times[name]), 4), round(max(times[name]), 4)],
+                     "guide_launches_issued_eagerly": launches[name], "rows_still_live": bool((done == 0).all()),
+                     "tokens_per_row_at_the_end": n_new.tolist()}
+    res["allowance_us"] = round(1000 * 0.02 * a, 1)
+    res["step_noise_us"] = round(1000 * (max(times["controlled"]) - min(times["controlled"])), 1)
+    for name in names[1:]:
+        res[f"{name}_minus_controlled_us"] = round(1000 * (med[name] - a), 1)
+        res[f"{name}_within_allowance"] = bool(med[name] - a <= 0.02 * a)
+    # the two launches alone on 4 rows of the model's vocabulary, back to back on one stream (the figures include the launch gap;
+    # the guidance launch rewrites its own output again and again: the values drift, the work per element does not)
+    gen = torch.Generator(device=dev).manual_seed(1)
+    lg = (torch.randn(n, V, generator=gen, device=dev) * 3.0).to(torch.bfloat16)
+    tok = torch.zeros(n, 1, dtype=torch.int64, device=dev)
+    op = {}
+    for name in names[1:]:
+        smp = samplers[name]
+        kw = dict(partner=smp.guide_partner, scale=smp.guide_scale, cut=smp.guide_cut, done=smp.done)
+        op[f"S{n}_{name}_guide_us"] = round(1000 * timed(lambda kw=kw: ops.guide_logits(lg, **kw), 200, lambda: None), 2)
+        op[f"S{n}_{name}_follow_us"] = round(1000 * timed(lambda smp=smp: ops.rows_follow(tok, smp.guide_partner), 200, lambda: None), 2)
     res["operator_V%d" % V] = op
     line = json.dumps(res)
     print(line)
