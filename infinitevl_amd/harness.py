@@ -23,6 +23,7 @@ import torch.nn.functional as F
 
 from . import ops
 from .cache import MultiStreamCache, StaticCachePrealloc
+from .ops import _is_int
 
 import os as _os
 
@@ -756,20 +757,25 @@ class _RowField(NamedTuple):
     init: float                 # of a fresh row, and what set() clears a state tensor to
     state: bool = False         # a step changes it (state() saves it); else a parameter
     kw: Optional[str] = None    # the keyword under which ops.sample_tokens takes it; None: positional
-    score: bool = False         # ... and only in a sampler built with logprobs
-    grammar: bool = False       # ... and only in a sampler built with grammar_states
-    penalties: bool = False     # ... and only in a sampler built with penalties=True
-    bias: bool = False          # ... and only in a sampler built with bias_tables
-    bans: bool = False          # ... and only in a sampler built with bans=True
-    guidance: bool = False      # ... and only in a sampler built with guidance=True
+    needs: Optional[str] = None  # ... and only in a sampler built with that feature: "score" (logprobs), "grammar" (grammar_states),
+    #                             "penalties", "bias" (bias_tables), "bans", "guidance"
     cleared: bool = False       # set() puts it back to `init` although no step changes it (state() does not save it)
+
+
+class _RowOption(NamedTuple):
+    """One per-row option of a Sampler that is a handle into a table arena (Sampler._OPTIONS)."""
+    name: str                   # the keyword of admit / admit_n / load / extend, and the stem of load_<name>, unload_<name>, set_<name>
+    arena: str                  # the sampler's attribute that holds the arena (None: built without it)
+    field: str                  # the row tensor that names the row's table (-1 = none)
+    built: str                  # "Sampler.<method>: needs a Sampler built with <built>"
+    asks: str                   # "<who>: <asks> a GraphedMultiStreamDecode whose sampler was built with <built_dec>"
+    built_dec: str
 
 
 def _stop_ids(who: str, ids, at_most: Optional[int] = None) -> List[int]:
     """`ids` as a list of ints in [0, 2^63), at most `at_most` of them (None: the caller bounds their number)."""
     stop = list(ids)
-    if (at_most is not None and len(stop) > at_most) or \
-            any(isinstance(t, bool) or not isinstance(t, int) or not 0 <= t < 2 ** 63 for t in stop):
+    if (at_most is not None and len(stop) > at_most) or any(not _is_int(t, 0, 2 ** 63) for t in stop):
         raise ValueError(f"{who}: stop_token_ids must be {'' if at_most is None else f'at most {at_most} '}ints >= 0; got {ids!r}")
     return stop
 
@@ -878,30 +884,43 @@ class Sampler:
         _RowField("n_new", torch.int64, (), 0, state=True, kw="n_new"),             # tokens generated
         _RowField("done", torch.int32, (), 0, state=True, kw="done"),               # 0 running, 1 stop id, 2 budget, 3 dead end, 4 held
         _RowField("history", torch.int64, ("history",), 0, state=True, kw="history"),
-        _RowField("logprob", torch.float32, (), 0.0, state=True, kw="logprob", score=True),
-        _RowField("cum_logprob", torch.float64, (), 0.0, state=True, kw="cum_logprob", score=True),
-        _RowField("top_ids", torch.int64, ("top",), -1, state=True, kw="top_ids", score=True),
-        _RowField("top_logprob", torch.float32, ("top",), -math.inf, state=True, kw="top_logprobs", score=True),
-        _RowField("lp_history", torch.float32, ("ring",), 0.0, state=True, kw="lp_history", score=True),
-        _RowField("top_hist_ids", torch.int64, ("ring", "top"), -1, state=True, kw="top_hist_ids", score=True),
-        _RowField("top_hist_lp", torch.float32, ("ring", "top"), -math.inf, state=True, kw="top_hist_lp", score=True),
-        _RowField("fsm_state", torch.int32, (), -1, state=True, kw="fsm_state", grammar=True),      # -1 = unconstrained
-        _RowField("min_p", torch.float32, (), 0.0, kw="min_p", penalties=True),
-        _RowField("freq_penalty", torch.float32, (), 0.0, kw="freq_penalty", penalties=True),
-        _RowField("pres_penalty", torch.float32, (), 0.0, kw="pres_penalty", penalties=True),
-        _RowField("count", torch.int32, ("vocab",), 0, state=True, kw="count", penalties=True),     # of the GENERATED tokens
-        _RowField("bias_idx", torch.int32, (), -1, kw="bias_idx", bias=True, cleared=True),         # -1 = no bias
+        _RowField("logprob", torch.float32, (), 0.0, state=True, kw="logprob", needs="score"),
+        _RowField("cum_logprob", torch.float64, (), 0.0, state=True, kw="cum_logprob", needs="score"),
+        _RowField("top_ids", torch.int64, ("top",), -1, state=True, kw="top_ids", needs="score"),
+        _RowField("top_logprob", torch.float32, ("top",), -math.inf, state=True, kw="top_logprobs", needs="score"),
+        _RowField("lp_history", torch.float32, ("ring",), 0.0, state=True, kw="lp_history", needs="score"),
+        _RowField("top_hist_ids", torch.int64, ("ring", "top"), -1, state=True, kw="top_hist_ids", needs="score"),
+        _RowField("top_hist_lp", torch.float32, ("ring", "top"), -math.inf, state=True, kw="top_hist_lp", needs="score"),
+        _RowField("fsm_state", torch.int32, (), -1, state=True, kw="fsm_state", needs="grammar"),           # -1 = unconstrained
+        _RowField("min_p", torch.float32, (), 0.0, kw="min_p", needs="penalties"),
+        _RowField("freq_penalty", torch.float32, (), 0.0, kw="freq_penalty", needs="penalties"),
+        _RowField("pres_penalty", torch.float32, (), 0.0, kw="pres_penalty", needs="penalties"),
+        _RowField("count", torch.int32, ("vocab",), 0, state=True, kw="count", needs="penalties"),          # of the GENERATED tokens
+        _RowField("bias_idx", torch.int32, (), -1, kw="bias_idx", needs="bias", cleared=True),              # -1 = no bias
         # the rows of ops.ban_tokens (kw None: ops.sample_tokens never sees them)
-        _RowField("ngram", torch.int32, (), 0, bans=True),                                          # 0 = off
-        _RowField("min_new", torch.int64, (), 0, bans=True),
-        _RowField("ban_idx", torch.int32, (), -1, bans=True, cleared=True),                         # -1 = no table
-        _RowField("ctx", torch.int64, ("context",), 0, bans=True),                                  # the ring mark() pushes into
-        _RowField("n_ctx", torch.int64, (), 0, bans=True, cleared=True),                            # tokens pushed so far
+        _RowField("ngram", torch.int32, (), 0, needs="bans"),                                               # 0 = off
+        _RowField("min_new", torch.int64, (), 0, needs="bans"),
+        _RowField("ban_idx", torch.int32, (), -1, needs="bans", cleared=True),                              # -1 = no table
+        _RowField("ctx", torch.int64, ("context",), 0, needs="bans"),                                       # the ring mark() pushes into
+        _RowField("n_ctx", torch.int64, (), 0, needs="bans", cleared=True),                                 # tokens pushed so far
         # the rows of ops.guide_logits / ops.rows_follow (kw None: ops.sample_tokens never sees them)
-        _RowField("guide_partner", torch.int32, (), -1, guidance=True, cleared=True),               # -1 = the row is not guided
-        _RowField("guide_scale", torch.float32, (), 1.0, guidance=True),
-        _RowField("guide_cut", torch.float32, (), -math.inf, guidance=True),                        # ln(beta); -inf = off
+        _RowField("guide_partner", torch.int32, (), -1, needs="guidance", cleared=True),                    # -1 = the row is not guided
+        _RowField("guide_scale", torch.float32, (), 1.0, needs="guidance"),
+        _RowField("guide_cut", torch.float32, (), -math.inf, needs="guidance"),                             # ln(beta); -inf = off
     )
+
+    # THE list of the per-row options that are handles: _arena(), load_* / unload_* / set_*, check_options() and apply_options()
+    # follow from here, and so does every refusal of GraphedMultiStreamDecode that names one.
+    _OPTIONS = {o.name: o for o in (
+        _RowOption("grammar", "grammars", "fsm_state", "grammar_states > 0", "a grammar needs", "grammar_states"),
+        _RowOption("logit_bias", "biases", "bias_idx", "bias_tables > 0", "a logit_bias needs", "bias_tables"),
+        _RowOption("bad_words", "bad_words", "ban_idx", "bans=True and ban_tables > 0", "bad_words need", "bans=True and ban_tables"),
+    )}
+
+    # set()'s keywords that are one value in the row of one tensor: keyword -> field (_write)
+    _PLAIN = {"temperature": "temperature", "top_k": "top_k", "top_p": "top_p", "repetition_penalty": "rep_penalty",
+              "fill_token": "fill", "min_p": "min_p", "frequency_penalty": "freq_penalty", "presence_penalty": "pres_penalty",
+              "no_repeat_ngram_size": "ngram", "min_new_tokens": "min_new"}
 
     def __init__(self, n_rows: int, device, vocab_size: Optional[int] = None, max_stop: int = 8, history: int = 0,
                  logprobs: Optional[int] = None, *, score_rings: bool = True, grammar_states: int = 0,
@@ -918,15 +937,15 @@ class Sampler:
         the draw (set_guidance)."""
         if n_rows < 1:
             raise ValueError(f"Sampler: n_rows must be >= 1; got {n_rows}")
-        if vocab_size is not None and (isinstance(vocab_size, bool) or not isinstance(vocab_size, int) or vocab_size < 1):
+        if vocab_size is not None and not _is_int(vocab_size, 1):
             raise ValueError(f"Sampler: vocab_size must be an int >= 1; got {vocab_size!r}")
-        if isinstance(max_stop, bool) or not isinstance(max_stop, int) or not 0 <= max_stop <= 16:
+        if not _is_int(max_stop, 0, 17):
             raise ValueError(f"Sampler: max_stop must be an int in [0, 16]; got {max_stop!r}")
-        if isinstance(history, bool) or not isinstance(history, int) or history < 0:
+        if not _is_int(history, 0):
             raise ValueError(f"Sampler: history must be an int >= 0; got {history!r}")
-        if logprobs is not None and (isinstance(logprobs, bool) or not isinstance(logprobs, int) or not 0 <= logprobs <= 20):
+        if logprobs is not None and not _is_int(logprobs, 0, 21):
             raise ValueError(f"Sampler: logprobs must be None or an int in [0, 20]; got {logprobs!r}")
-        if isinstance(grammar_states, bool) or not isinstance(grammar_states, int) or grammar_states < 0:
+        if not _is_int(grammar_states, 0):
             raise ValueError(f"Sampler: grammar_states must be an int >= 0; got {grammar_states!r}")
         if grammar_states == 0 and (grammar_slots is not None or grammar_trans is not None):
             raise ValueError("Sampler: grammar_slots and grammar_trans need grammar_states > 0")
@@ -934,14 +953,14 @@ class Sampler:
             raise ValueError("Sampler: grammar_states needs vocab_size (the allowed-token bitmaps)")
         if not isinstance(penalties, bool):
             raise ValueError(f"Sampler: penalties must be a bool; got {penalties!r}")
-        if isinstance(bias_tables, bool) or not isinstance(bias_tables, int) or bias_tables < 0:
+        if not _is_int(bias_tables, 0):
             raise ValueError(f"Sampler: bias_tables must be an int >= 0; got {bias_tables!r}")
         if (penalties or bias_tables > 0) and vocab_size is None:
             raise ValueError("Sampler: penalties and bias_tables need vocab_size (the rows' counts, the bias tables)")
         if not isinstance(bans, bool):
             raise ValueError(f"Sampler: bans must be a bool; got {bans!r}")
         for name, v in (("ban_context", ban_context), ("ban_tables", ban_tables)):
-            if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+            if not _is_int(v, 0):
                 raise ValueError(f"Sampler: {name} must be an int >= 0; got {v!r}")
         if bans and history < 1:
             raise ValueError("Sampler: bans=True needs history > 0 (the ring of generated tokens the bans are decided from)")
@@ -970,12 +989,12 @@ class Sampler:
         extent = {"words": (vocab_size + 31) // 32 if vocab_size is not None else 0, "max_stop": max_stop, "history": history,
                   "top": logprobs or 0, "ring": history if score_rings else 0, "vocab": vocab_size or 0,
                   "context": ban_context}
+        on = {"score": logprobs is not None, "grammar": self.grammars is not None, "penalties": penalties,
+              "bias": self.biases is not None, "bans": bans, "guidance": guidance}
         self._fields = []                                # the entries of _TABLE this sampler holds, in the table's order
         for f in self._TABLE:
             shape = [extent[e] for e in f.shape]
-            held = all(shape) and (logprobs is not None or not f.score) and (self.grammars is not None or not f.grammar) and \
-                (penalties or not f.penalties) and (self.biases is not None or not f.bias) and (bans or not f.bans) and \
-                (guidance or not f.guidance)
+            held = all(shape) and (f.needs is None or on[f.needs])
             setattr(self, f.name, torch.full((n_rows, *shape), f.init, dtype=f.dtype, device=device) if held else None)
             if held:
                 self._fields.append(f)
@@ -998,7 +1017,7 @@ class Sampler:
                 raise ValueError(f"{who}: temperature must be finite and >= 0; got {temperature}")
         if "top_k" in p:
             top_k = p["top_k"]
-            if isinstance(top_k, bool) or not isinstance(top_k, int) or not 0 <= top_k < 2 ** 31:
+            if not _is_int(top_k, 0, 2 ** 31):
                 raise ValueError(f"{who}: top_k must be an int >= 0 (0 = off); got {top_k!r}")
         if "top_p" in p:
             p["top_p"] = top_p = float(p["top_p"])
@@ -1006,7 +1025,7 @@ class Sampler:
                 raise ValueError(f"{who}: top_p must be in (0, 1]; got {top_p}")
         if "seed" in p:
             seed = p["seed"]
-            if isinstance(seed, bool) or not isinstance(seed, int) or not -2 ** 63 <= seed < 2 ** 64:
+            if not _is_int(seed, -2 ** 63, 2 ** 64):
                 raise ValueError(f"{who}: seed must be a 64-bit int; got {seed!r}")
         if "repetition_penalty" in p:
             p["repetition_penalty"] = repetition_penalty = float(p["repetition_penalty"])
@@ -1023,7 +1042,7 @@ class Sampler:
                 raise ValueError(f"{who}: max_new_tokens must be None or an int >= 1; got {max_new_tokens!r}")
         if "fill_token" in p:
             fill_token = p["fill_token"]
-            if isinstance(fill_token, bool) or not isinstance(fill_token, int) or not 0 <= fill_token < 2 ** 63:
+            if not _is_int(fill_token, 0, 2 ** 63):
                 raise ValueError(f"{who}: fill_token must be an int >= 0; got {fill_token!r}")
         for k in ("min_p", "frequency_penalty", "presence_penalty"):
             if k not in p:
@@ -1040,7 +1059,7 @@ class Sampler:
         for k, top in (("no_repeat_ngram_size", 2 ** 31), ("min_new_tokens", 2 ** 63)):
             if k not in p:
                 continue
-            if isinstance(p[k], bool) or not isinstance(p[k], int) or not 0 <= p[k] < top:
+            if not _is_int(p[k], 0, top):
                 raise ValueError(f"{who}: {k} must be an int >= 0 (0 = off); got {p[k]!r}")
             if p[k] != 0 and not self.bans:
                 raise ValueError(f"{who}: {k} needs a Sampler built with bans=True")
@@ -1051,31 +1070,16 @@ class Sampler:
     def _write(self, row: int, p: dict) -> None:
         """Writes the checked parameters `p` into `row` and leaves the row's state alone, except that a seed restarts its
         counter.  The host's note of a stop id or a budget follows when `p` holds both."""
-        if "temperature" in p:
-            self.temperature[row] = p["temperature"]
-        if "top_k" in p:
-            self.top_k[row] = p["top_k"]
-        if "top_p" in p:
-            self.top_p[row] = p["top_p"]
+        for k, name in self._PLAIN.items():             # (a sampler without the field was refused every value but "off")
+            if k in p and getattr(self, name) is not None:
+                getattr(self, name)[row] = p[k]
         if "seed" in p:
             self.seed[row] = p["seed"] - 2 ** 64 if p["seed"] >= 2 ** 63 else p["seed"]
             self.counter[row] = 0
-        if "repetition_penalty" in p:
-            self.rep_penalty[row] = p["repetition_penalty"]
         if "stop_token_ids" in p and self.stop_ids is not None:
             _write_stop_ids(self.stop_ids, row, p["stop_token_ids"])
         if "max_new_tokens" in p:
             self.budget[row] = -1 if p["max_new_tokens"] is None else p["max_new_tokens"]
-        if "fill_token" in p:
-            self.fill[row] = p["fill_token"]
-        if self.penalties:
-            for k, t in (("min_p", self.min_p), ("frequency_penalty", self.freq_penalty), ("presence_penalty", self.pres_penalty)):
-                if k in p:
-                    t[row] = p[k]
-        if self.bans:
-            for k, t in (("no_repeat_ngram_size", self.ngram), ("min_new_tokens", self.min_new)):
-                if k in p:
-                    t[row] = p[k]
         if "stop_token_ids" in p and "max_new_tokens" in p:
             self._note_ends(row, bool(p["stop_token_ids"]) or p["max_new_tokens"] is not None)
 
@@ -1188,28 +1192,64 @@ class Sampler:
         self.ctx[row].index_copy_(0, at, ids[first:])
         self.n_ctx[row] += T
 
-    # ---- bad words ------------------------------------------------------------------------------------------------------------
-    def _ban_arena(self, who: str) -> "ops.BanTables":
-        if self.bad_words is None:
-            raise ValueError(f"Sampler.{who}: needs a Sampler built with bans=True and ban_tables > 0")
-        return self.bad_words
+    # ---- the options that are handles (_OPTIONS) ------------------------------------------------------------------------------
+    def _arena(self, option: str, who: str):
+        """The arena of `option`, for the method `who`; ValueError in a sampler built without it."""
+        o = self._OPTIONS[option]
+        if getattr(self, o.arena) is None:
+            raise ValueError(f"Sampler.{who}: needs a Sampler built with {o.built}")
+        return getattr(self, o.arena)
+
+    def _point(self, option: str, row: int, handle, at=lambda h: -1 if h is None else h.index) -> None:
+        """The body of set_<option>: the row's `field` becomes at(handle), of a handle that is None or loaded in this sampler."""
+        row, arena = self._row(row), self._arena(option, f"set_{option}")
+        if handle is not None and handle not in arena.handles():
+            raise ValueError(f"Sampler.set_{option}: {handle!r} is not loaded in this sampler")
+        getattr(self, self._OPTIONS[option].field)[row] = at(handle)
+
+    @classmethod
+    def _lacks(cls, who: str, option: str) -> ValueError:
+        o = cls._OPTIONS[option]
+        return ValueError(f"{who}: {o.asks} a GraphedMultiStreamDecode whose sampler was built with {o.built_dec}")
+
+    def check_options(self, who: str, *, grammar=None, logit_bias=None, bad_words=None) -> None:
+        """Refuses, as the decoder's method `who`, a handle whose arena this sampler lacks or that is not loaded in it.  No device
+        work and no writes."""
+        for name, handle in (("grammar", grammar), ("logit_bias", logit_bias), ("bad_words", bad_words)):
+            arena = getattr(self, self._OPTIONS[name].arena)
+            if handle is not None and arena is None:
+                raise self._lacks(who, name)
+            if handle is not None and handle not in arena.handles():
+                raise ValueError(f"{who}: {handle!r} is not loaded in the sampler (Sampler.load_{name})")
+
+    def apply_options(self, row: int, *, sampling: Optional[dict] = None, grammar=None, logit_bias=None, bad_words=None, then=None,
+                      prompt_ids: Optional[torch.Tensor] = None) -> None:
+        """A row's setup in THE order every admission uses: set(**sampling) -> set_grammar -> set_logit_bias -> set_bad_words ->
+        then() -> mark(prompt_ids); what is None is left out.  The order carries meaning: set() clears fsm_state, bias_idx, ban_idx
+        and the context ring (and the row's pairing), so the handles, `then` (set_guidance) and the prompt's tokens come after it."""
+        if sampling is not None:
+            self.set(row, **sampling)
+        for name, handle in (("grammar", grammar), ("logit_bias", logit_bias), ("bad_words", bad_words)):
+            if handle is not None:
+                getattr(self, f"set_{name}")(row, handle)
+        if then is not None:
+            then()
+        if prompt_ids is not None:
+            self.mark(row, prompt_ids)
 
     def load_bad_words(self, seqs) -> "ops.BanHandle":
         """Puts a list of token-id lists (`bad_words_ids` of HF generate) into a free table of the sampler's arena (between
         replays: no recapture); ValueError when every table is taken."""
-        return self._ban_arena("load_bad_words").load(seqs)
+        return self._arena("bad_words", "load_bad_words").load(seqs)
 
     def unload_bad_words(self, handle: "ops.BanHandle") -> None:
         """Frees the table.  A row that still points at it has nothing banned by it from its next draw on."""
-        self._ban_arena("unload_bad_words").unload(handle)
+        self._arena("bad_words", "unload_bad_words").unload(handle)
 
     def set_bad_words(self, row: int, handle: Optional["ops.BanHandle"]) -> None:
         """`row` draws under the bad-words table `handle` from its next draw on; None: no table.  Call it after set(), which
         clears the row to no table."""
-        row, arena = self._row(row), self._ban_arena("set_bad_words")
-        if handle is not None and handle not in arena.handles():
-            raise ValueError(f"Sampler.set_bad_words: {handle!r} is not loaded in this sampler")
-        self.ban_idx[row] = -1 if handle is None else handle.index
+        self._point("bad_words", row, handle)
 
     # ---- guidance ------------------------------------------------------------------------------------------------------------
     def guided_role(self, row: int) -> Optional[str]:
@@ -1251,7 +1291,7 @@ class Sampler:
             raise ValueError("Sampler.set_guidance: needs a Sampler built with guidance=True")
         row = self._row(row)
         s, cut = self._checked_guidance("Sampler.set_guidance", guidance_scale, plausibility)
-        if isinstance(partner, bool) or not isinstance(partner, int) or not 0 <= partner < self.n_rows or partner == row:
+        if not _is_int(partner, 0, self.n_rows) or partner == row:
             raise ValueError(f"Sampler.set_guidance: partner must be an int in [0, {self.n_rows}) other than the row {row}; got "
                              f"{partner!r}")
         if partner in self._partner:
@@ -1277,38 +1317,29 @@ class Sampler:
         self._guide_params.pop(row, None)
 
     # ---- constrained decoding ------------------------------------------------------------------------------------------------
-    def _arena(self, who: str) -> "ops.FsmTables":
-        if self.grammars is None:
-            raise ValueError(f"Sampler.{who}: needs a Sampler built with grammar_states > 0")
-        return self.grammars
-
     def load_grammar(self, fsm) -> "ops.FsmHandle":
         """Puts a grammar.TokenFsm into the sampler's arena (between replays: no recapture); ValueError when it is full."""
-        return self._arena("load_grammar").load(fsm)
+        return self._arena("grammar", "load_grammar").load(fsm)
 
     def unload_grammar(self, handle: "ops.FsmHandle") -> None:
         """Frees the grammar's room.  A row still in one of its states meets a dead end (done code 3) at its next draw."""
-        self._arena("unload_grammar").unload(handle)
+        self._arena("grammar", "unload_grammar").unload(handle)
 
     def set_grammar(self, row: int, handle: Optional["ops.FsmHandle"], state: Optional[int] = None) -> None:
         """`row` continues under the grammar `handle`, from its start state or from the local `state`; None: unconstrained.
         Call it after set(), which clears the row to unconstrained."""
-        row, arena = self._row(row), self._arena("set_grammar")
-        if handle is None:
-            if state is not None:
+        def at(h):
+            if h is None and state is not None:
                 raise ValueError("Sampler.set_grammar: a state needs a grammar")
-            self.fsm_state[row] = -1
-            return
-        if handle not in arena.handles():
-            raise ValueError(f"Sampler.set_grammar: {handle!r} is not loaded in this sampler")
-        local = handle.start if state is None else state
-        if isinstance(local, bool) or not isinstance(local, int) or not 0 <= local < handle.n_states:
-            raise ValueError(f"Sampler.set_grammar: state must be in [0, {handle.n_states}); got {state!r}")
-        self.fsm_state[row] = handle.base + local
+            local = None if h is None else h.start if state is None else state
+            if h is not None and not _is_int(local, 0, h.n_states):
+                raise ValueError(f"Sampler.set_grammar: state must be in [0, {h.n_states}); got {state!r}")
+            return -1 if h is None else h.base + local
+        self._point("grammar", row, handle, at)
 
     def grammar_state(self, row: int) -> Optional[int]:
         """The row's state, local to its grammar (host; it waits for the steps queued so far); None: the row is unconstrained."""
-        row, arena = self._row(row), self._arena("grammar_state")
+        row, arena = self._row(row), self._arena("grammar", "grammar_state")
         g = int(self.fsm_state[row].item())
         if g < 0:
             return None
@@ -1318,27 +1349,19 @@ class Sampler:
         return found[1]
 
     # ---- logit bias -----------------------------------------------------------------------------------------------------------
-    def _bias_arena(self, who: str) -> "ops.BiasTables":
-        if self.biases is None:
-            raise ValueError(f"Sampler.{who}: needs a Sampler built with bias_tables > 0")
-        return self.biases
-
     def load_logit_bias(self, bias: dict) -> "ops.BiasHandle":
         """Puts a {token id: bias} dict (`logit_bias` of the chat-completion protocol; -inf bans a token, +inf forces it) into a
         free table of the sampler's arena (between replays: no recapture); ValueError when every table is taken."""
-        return self._bias_arena("load_logit_bias").load(bias)
+        return self._arena("logit_bias", "load_logit_bias").load(bias)
 
     def unload_logit_bias(self, handle: "ops.BiasHandle") -> None:
         """Frees the table.  A row that still points at it is not biased from its next draw on."""
-        self._bias_arena("unload_logit_bias").unload(handle)
+        self._arena("logit_bias", "unload_logit_bias").unload(handle)
 
     def set_logit_bias(self, row: int, handle: Optional["ops.BiasHandle"]) -> None:
         """`row` draws under the bias table `handle` from its next draw on; None: no bias.  Call it after set(), which clears
         the row to no bias."""
-        row, arena = self._row(row), self._bias_arena("set_logit_bias")
-        if handle is not None and handle not in arena.handles():
-            raise ValueError(f"Sampler.set_logit_bias: {handle!r} is not loaded in this sampler")
-        self.bias_idx[row] = -1 if handle is None else handle.index
+        self._point("logit_bias", row, handle)
 
     def _stateful(self):
         return {f.name: getattr(self, f.name) for f in self._fields if f.state}
@@ -1599,35 +1622,41 @@ class GraphedMultiStreamDecode(_Graphed):
         table, set before the first draw like the grammar.  `bad_words` (a handle of Sampler.load_bad_words): the row's table of
         banned sequences, set before the first draw too.  Refused on a slot of a guided pair: release the pair's leader first."""
         self._refuse_pair("admit", [slot])
-        lg = self._start("admit", slot, inputs_embeds, position_ids, sampling, prompt_ids, grammar, adapter, logit_bias, bad_words)
-        self._draw(slot, lg)
+        self._check_request("admit", inputs_embeds, position_ids, prompt_ids, sampling, "Sampler.set", grammar=grammar,
+                            logit_bias=logit_bias, bad_words=bad_words)
+        self._setup_row(slot, adapter, sampling=sampling, grammar=grammar, logit_bias=logit_bias, bad_words=bad_words,
+                        prompt_ids=prompt_ids)
+        self._draw(slot, self._prompt_in(slot, inputs_embeds, position_ids))
         return self.token[slot]
 
-    def _start(self, who: str, slot: int, inputs_embeds, position_ids, sampling, prompt_ids, grammar, adapter, logit_bias, bad_words,
-               then=None) -> torch.Tensor:
-        """An admission up to the first draw: the checks, the slot's sampler row (`then`, when given, runs once it is set), the
-        prompt's prefill and the slot's next M-RoPE position.  Returns the prompt's last logits [1,1,vocab] (admit_logits)."""
+    # ---- an admission = check the whole request, set the row up, put the prompt in --------------------------------------------
+    def _check_request(self, who: str, inputs_embeds, position_ids, prompt_ids, sampling=None, set_who: Optional[str] = None,
+                       **options) -> Optional[int]:
+        """Everything of a request that can be refused short of its slots, with nothing written: `sampling` without a sampler
+        (and, with `set_who`, the values of that one dict as the method `set_who` refuses them), the handles in `options`
+        (grammar, logit_bias, bad_words) and, where inputs_embeds is given, the prompt, whose length T is returned."""
         if sampling is not None and self.sampler is None:
             raise ValueError(f"{who}: sampling parameters need a GraphedMultiStreamDecode built with a sampler")
-        self._check_grammar(who, grammar)
-        self._check_bias(who, logit_bias)
-        self._check_bad_words(who, bad_words)
-        T = self._check_prompt(who, inputs_embeds, position_ids, prompt_ids)
+        for name, handle in options.items():
+            if handle is not None and self.sampler is None:
+                raise Sampler._lacks(who, name)
+        if self.sampler is not None:
+            self.sampler.check_options(who, **options)
+        if sampling is not None and set_who is not None:
+            self.sampler._checked(set_who, sampling)
+        return None if inputs_embeds is None else self._check_prompt(who, inputs_embeds, position_ids, prompt_ids)
+
+    def _setup_row(self, slot: int, adapter, prompt_ids: Optional[torch.Tensor] = None, **options) -> None:
+        """Row setup of a checked request, no prefill: the slot's adapter, then its sampler row (Sampler.apply_options)."""
         self.set_adapter(slot, adapter)
+        if self.sampler is not None:
+            self.sampler.apply_options(slot, prompt_ids=None if prompt_ids is None else prompt_ids.to(self.token.device), **options)
+
+    def _prompt_in(self, slot: int, inputs_embeds: torch.Tensor, position_ids: Optional[torch.Tensor]) -> torch.Tensor:
+        """Prompt in: the slot becomes live (and is no longer held), the prompt is prefilled in chunks, and the slot's three
+        M-RoPE positions are the next text position.  Returns the prompt's last logits [1,1,vocab] (admit_logits)."""
         if position_ids is None:
-            position_ids = _text_positions(T, inputs_embeds.device)
-        if sampling is not None:
-            self.sampler.set(slot, **sampling)
-        if grammar is not None:
-            self.sampler.set_grammar(slot, grammar)
-        if logit_bias is not None:
-            self.sampler.set_logit_bias(slot, logit_bias)
-        if bad_words is not None:
-            self.sampler.set_bad_words(slot, bad_words)
-        if then is not None:
-            then()
-        if prompt_ids is not None:
-            self.sampler.mark(slot, prompt_ids.to(inputs_embeds.device))
+            position_ids = _text_positions(inputs_embeds.shape[1], inputs_embeds.device)
         self.cache.admit(slot)
         self._live.add(slot)
         self._unhold(slot)
@@ -1691,18 +1720,16 @@ class GraphedMultiStreamDecode(_Graphed):
         slot, partner = self._slots("admit_guided", [slot, partner])
         self._refuse_pair("admit_guided", [slot, partner])
         self.sampler._checked_guidance("admit_guided", guidance_scale, plausibility)
-        if sampling is not None:
-            self.sampler._checked("admit_guided", sampling)                  # (refused before anything is written)
-        self._check_prompt("admit_guided", inputs_embeds, position_ids, prompt_ids)
+        self._check_request("admit_guided", inputs_embeds, position_ids, prompt_ids, sampling, "admit_guided", grammar=grammar,
+                            logit_bias=logit_bias, bad_words=bad_words)
         self._check_prompt("admit_guided", negative_embeds, negative_position_ids, None)
-        self._check_grammar("admit_guided", grammar)
-        self._check_bias("admit_guided", logit_bias)
-        self._check_bad_words("admit_guided", bad_words)
         self.sampler.set(partner)                        # greedy, no stop ids, no budget: the partner follows its leader
-        lgn = self._start("admit_guided", partner, negative_embeds, negative_position_ids, None, None, None, adapter, None, None)
-        lg = self._start("admit_guided", slot, inputs_embeds, position_ids, sampling, prompt_ids, grammar, adapter, logit_bias,
-                         bad_words, then=lambda: self.sampler.set_guidance(slot, partner, guidance_scale, plausibility))
-        self._draw_guided(slot, partner, lg, lgn)
+        self._setup_row(partner, adapter)
+        lgn = self._prompt_in(partner, negative_embeds, negative_position_ids)
+        self._setup_row(slot, adapter, sampling=sampling, grammar=grammar, logit_bias=logit_bias, bad_words=bad_words,
+                        then=lambda: self.sampler.set_guidance(slot, partner, guidance_scale, plausibility),
+                        prompt_ids=prompt_ids)
+        self._draw_guided(slot, partner, self._prompt_in(slot, inputs_embeds, position_ids), lgn)
         return self.token[slot]
 
     def set_guidance(self, slot: int, guidance_scale: Optional[float] = None, plausibility: Optional[float] = None) -> None:
@@ -1734,24 +1761,6 @@ class GraphedMultiStreamDecode(_Graphed):
         else:
             self.sampler.sample(lg[:, -1], self.token[slot:slot + 1], row=slot)
 
-    def _check_grammar(self, who: str, grammar) -> None:
-        if grammar is not None and (self.sampler is None or self.sampler.grammars is None):
-            raise ValueError(f"{who}: a grammar needs a GraphedMultiStreamDecode whose sampler was built with grammar_states")
-        if grammar is not None and grammar not in self.sampler.grammars.handles():
-            raise ValueError(f"{who}: {grammar!r} is not loaded in the sampler (Sampler.load_grammar)")
-
-    def _check_bias(self, who: str, logit_bias) -> None:
-        if logit_bias is not None and (self.sampler is None or self.sampler.biases is None):
-            raise ValueError(f"{who}: a logit_bias needs a GraphedMultiStreamDecode whose sampler was built with bias_tables")
-        if logit_bias is not None and logit_bias not in self.sampler.biases.handles():
-            raise ValueError(f"{who}: {logit_bias!r} is not loaded in the sampler (Sampler.load_logit_bias)")
-
-    def _check_bad_words(self, who: str, bad_words) -> None:
-        if bad_words is not None and (self.sampler is None or self.sampler.bad_words is None):
-            raise ValueError(f"{who}: bad_words need a GraphedMultiStreamDecode whose sampler was built with bans=True and ban_tables")
-        if bad_words is not None and bad_words not in self.sampler.bad_words.handles():
-            raise ValueError(f"{who}: {bad_words!r} is not loaded in the sampler (Sampler.load_bad_words)")
-
     def _check_prompt(self, who: str, inputs_embeds, position_ids, prompt_ids) -> int:
         if prompt_ids is not None and self.sampler is None:
             raise ValueError(f"{who}: prompt_ids need a GraphedMultiStreamDecode built with a sampler")
@@ -1764,8 +1773,7 @@ class GraphedMultiStreamDecode(_Graphed):
 
     def _slots(self, who: str, slots) -> List[int]:
         slots = list(slots)
-        if not slots or len(set(slots)) != len(slots) or \
-                any(isinstance(s, bool) or not isinstance(s, int) or not 0 <= s < self.S for s in slots):
+        if not slots or len(set(slots)) != len(slots) or any(not _is_int(s, 0, self.S) for s in slots):
             raise ValueError(f"{who}: slots must be distinct ints in [0, {self.S}), at least one; got {slots!r}")
         return slots
 
@@ -1810,8 +1818,7 @@ class GraphedMultiStreamDecode(_Graphed):
         if src not in self._live:
             raise ValueError(f"fork: slot {src} holds no stream (admit or load it first)")
         self._refuse_pair("fork", [src, *dsts])
-        if sampling is not None and self.sampler is None:
-            raise ValueError("fork: sampling parameters need a GraphedMultiStreamDecode built with a sampler")
+        self._check_request("fork", None, None, None, sampling)
         overrides = None
         if self.sampler is not None:
             _, _, overrides = self.sampler._check_fork("fork", src, dsts, sampling)
@@ -1820,6 +1827,26 @@ class GraphedMultiStreamDecode(_Graphed):
             self.set_adapter(d, self._slot_adapter[src] if isinstance(adapter, str) else adapter)
         if self.sampler is not None:
             self.sampler._forked(src, dsts, overrides)
+
+    def _counting_on(self, slot: int, T: int) -> torch.Tensor:
+        """The default position_ids [3,1,T] of extend and score: each of the slot's three positions counts on from where it is."""
+        return self.position_ids[:, slot:slot + 1] + torch.arange(T, device=self.position_ids.device, dtype=torch.int64)
+
+    def _next_turn(self, slot: int, partner: Optional[int]) -> None:
+        """A frozen slot (holds=True: finished or held) starts its next turn where its state stopped: done, n_new and cum_logprob
+        are cleared, the finished answer goes into the context ring the next turn's bans read, and the slot is no longer held (the
+        draw that follows replaces the parked token too).  A partner froze with its leader; its own row counts nothing that is read."""
+        smp = self.sampler
+        if smp.bans and smp.ctx is not None:
+            smp._push_context(slot, smp.tokens(slot).to(smp.ctx.device))
+        smp.done[slot] = 0
+        smp.n_new[slot] = 0
+        if smp.cum_logprob is not None:
+            smp.cum_logprob[slot] = 0.0
+        self._held.discard(slot)
+        if partner is not None:
+            smp.done[partner] = 0
+            self._held.discard(partner)
 
     @torch.no_grad()
     def extend(self, slot: int, inputs_embeds: torch.Tensor, position_ids: Optional[torch.Tensor] = None,
@@ -1852,8 +1879,7 @@ class GraphedMultiStreamDecode(_Graphed):
                              f"extend: negative_embeds is for the leader of a guided pair; slot {slot} leads none")
         if negative_embeds is None and negative_position_ids is not None:
             raise ValueError("extend: negative_position_ids come with negative_embeds")
-        self._check_grammar("extend", grammar)
-        T = self._check_prompt("extend", inputs_embeds, position_ids, prompt_ids)
+        T = self._check_request("extend", inputs_embeds, position_ids, prompt_ids, grammar=grammar)
         Tn = self._check_prompt("extend", negative_embeds, negative_position_ids, None) if partner is not None else 0
         ends = {k: v for k, v in (("max_new_tokens", max_new_tokens), ("stop_token_ids", stop_token_ids)) if v is not Sampler._UNCHANGED}
         if ends and self.sampler is None:
@@ -1861,22 +1887,13 @@ class GraphedMultiStreamDecode(_Graphed):
         if ends:
             self.sampler._checked("extend", ends)       # (refused before anything is written)
         if self.holds and int(self.sampler.done[slot]) != 0:
-            if self.sampler.bans and self.sampler.ctx is not None:       # the next turn's bans still see the finished answer
-                self.sampler._push_context(slot, self.sampler.tokens(slot).to(self.sampler.ctx.device))
-            self.sampler.done[slot] = 0
-            self.sampler.n_new[slot] = 0
-            if self.sampler.cum_logprob is not None:
-                self.sampler.cum_logprob[slot] = 0.0
-            self._held.discard(slot)                     # (the draw below replaces the parked token too)
-            if partner is not None:                      # (it froze with its leader; its own row counts nothing that is read)
-                self.sampler.done[partner] = 0
-                self._held.discard(partner)
+            self._next_turn(slot, partner)
         if ends:
             self.sampler.set_ends(slot, **ends)
         if grammar is not None:
             self.sampler.set_grammar(slot, grammar)
         if position_ids is None:
-            position_ids = self.position_ids[:, slot:slot + 1] + torch.arange(T, device=self.position_ids.device, dtype=torch.int64)
+            position_ids = self._counting_on(slot, T)
         if prompt_ids is not None:
             self.sampler.mark(slot, prompt_ids.to(inputs_embeds.device))
         lg = self._prefill(slot, inputs_embeds, position_ids)
@@ -1885,8 +1902,7 @@ class GraphedMultiStreamDecode(_Graphed):
             self._draw(slot, lg)
         else:
             if negative_position_ids is None:
-                negative_position_ids = self.position_ids[:, partner:partner + 1] + \
-                    torch.arange(Tn, device=self.position_ids.device, dtype=torch.int64)
+                negative_position_ids = self._counting_on(partner, Tn)
             lgn = self._prefill(partner, negative_embeds, negative_position_ids)
             self._draw_guided(slot, partner, lg, lgn)
             self.position_ids[:, partner].copy_(negative_position_ids.max() + 1)
@@ -1909,7 +1925,7 @@ class GraphedMultiStreamDecode(_Graphed):
             raise ValueError(f"score: slot {slot} holds no stream (admit or load it first)")
         T = self._check_prompt("score", inputs_embeds, position_ids, None)
         if position_ids is None:
-            position_ids = self.position_ids[:, slot:slot + 1] + torch.arange(T, device=self.position_ids.device, dtype=torch.int64)
+            position_ids = self._counting_on(slot, T)
         res = score_sequence(self.model, self.cache.slot_view(slot), inputs_embeds=inputs_embeds, labels=labels,
                              position_ids=position_ids, chunk=self.PREFILL_CHUNK, next_label=next_label,
                              adapters=self._slot_adapter[slot])
@@ -1929,44 +1945,22 @@ class GraphedMultiStreamDecode(_Graphed):
         draws under that bias table; `bad_words`: and under that table of banned sequences.  Returns token[slots]."""
         slots = self._slots("admit_n", slots)
         self._refuse_pair("admit_n", slots)
-        self._check_grammar("admit_n", grammar)
-        self._check_bias("admit_n", logit_bias)
-        self._check_bad_words("admit_n", bad_words)
-        if sampling is not None and self.sampler is None:
-            raise ValueError("admit_n: sampling parameters need a GraphedMultiStreamDecode built with a sampler")
-        T = self._check_prompt("admit_n", inputs_embeds, position_ids, prompt_ids)
-        for s_ in slots:                                 # (every answer decodes under `adapter`; the prompt is prefilled under it)
-            self.set_adapter(s_, adapter)
-        if position_ids is None:
-            position_ids = _text_positions(T, inputs_embeds.device)
+        self._check_request("admit_n", inputs_embeds, position_ids, prompt_ids, sampling, grammar=grammar, logit_bias=logit_bias,
+                            bad_words=bad_words)
         checked = None
-        if sampling is not None:
+        if sampling is not None:                         # (every slot's dict, before slots[0] is touched)
             sampling = _sampling_dicts("admit_n", sampling, len(slots), "slot", tuple(Sampler._SET_DEFAULTS))
             checked = [self.sampler._checked("admit_n", {**Sampler._SET_DEFAULTS, **d}) for d in sampling]
         first, rest = slots[0], slots[1:]
-        if sampling is not None:
-            self.sampler.set(first, **sampling[0])
-        if grammar is not None:
-            self.sampler.set_grammar(first, grammar)    # (it travels to the other slots with the row)
-        if logit_bias is not None:
-            self.sampler.set_logit_bias(first, logit_bias)
-        if bad_words is not None:
-            self.sampler.set_bad_words(first, bad_words)
-        if prompt_ids is not None:
-            self.sampler.mark(first, prompt_ids.to(inputs_embeds.device))
-        self.cache.admit(first)
-        self._live.add(first)
-        self._unhold(first)
-        lg = self._prefill(first, inputs_embeds, position_ids)
-        self.admit_logits = lg
-        self.position_ids[:, first].fill_(int(position_ids.max()) + 1)
+        self._setup_row(first, adapter, sampling=None if sampling is None else sampling[0], grammar=grammar, logit_bias=logit_bias,
+                        bad_words=bad_words, prompt_ids=prompt_ids)
+        for s_ in rest:                                  # (every answer decodes under `adapter`; the prompt is prefilled under it)
+            self.set_adapter(s_, adapter)
+        lg = self._prompt_in(first, inputs_embeds, position_ids)
         if rest:
             self._fork_rows(first, rest)                # the marked bitmap and the fresh state travel with the row
-            if self.sampler is not None:
-                for i, d in enumerate(rest):
-                    self.sampler._ends[d] = self.sampler._ends[first]
-                    if checked is not None:
-                        self.sampler._write(d, checked[i + 1])
+            if self.sampler is not None:                # (the host's notes, then each slot's own parameters: as after a fork)
+                self.sampler._forked(first, rest, [{}] * len(rest) if checked is None else checked[1:])
         bans = self.sampler is not None and self.sampler.bans
         for s in slots:                                  # (a slot's bans are written into the logits it draws from: one copy each)
             self._draw(s, lg.clone() if bans else lg)
@@ -1983,30 +1977,21 @@ class GraphedMultiStreamDecode(_Graphed):
         `logit_bias`: every slot draws under that bias table; `bad_words`: and under that table of banned sequences.  No token is pending afterwards: extend(slot, question) follows."""
         slots = self._slots("load", slots)
         self._refuse_pair("load", slots)
-        self._check_grammar("load", grammar)
-        self._check_bias("load", logit_bias)
-        self._check_bad_words("load", bad_words)
+        self._check_request("load", None, None, None, sampling, grammar=grammar, logit_bias=logit_bias, bad_words=bad_words)
         if sampling is not None:
-            if self.sampler is None:
-                raise ValueError("load: sampling parameters need a GraphedMultiStreamDecode built with a sampler")
             sampling = _sampling_dicts("load", sampling, len(slots), "slot")      # (the keys: set() checks them, slot by slot)
-        if next_position is not None and (isinstance(next_position, bool) or not isinstance(next_position, int) or next_position < 0):
+            for d in sampling:                           # (the values: before anything is written)
+                self.sampler._checked("Sampler.set", d)
+        if next_position is not None and not _is_int(next_position, 0):
             raise ValueError(f"load: next_position must be None or an int >= 0; got {next_position!r}")
         self.cache.load(slots, cache, row)
         if next_position is None:
             next_position = self.cache.slot_lengths[slots[0]]
         for i, s in enumerate(slots):
-            if sampling is not None:
-                self.sampler.set(s, **sampling[i])
-            if grammar is not None:
-                self.sampler.set_grammar(s, grammar)
-            if logit_bias is not None:
-                self.sampler.set_logit_bias(s, logit_bias)
-            if bad_words is not None:
-                self.sampler.set_bad_words(s, bad_words)
+            self._setup_row(s, adapter, sampling=None if sampling is None else sampling[i], grammar=grammar, logit_bias=logit_bias,
+                            bad_words=bad_words)         # (the extend that follows runs under the adapter)
             self.token[s].zero_()
             self.position_ids[:, s].fill_(next_position)
-            self.set_adapter(s, adapter)                 # (the extend that follows runs under it)
             self._live.add(s)
             self._unhold(s)
 
@@ -2095,13 +2080,13 @@ class GraphedBeamDecode(GraphedMultiStreamDecode):
         if sampler is not None and sampler.grammars is not None:
             raise ValueError("GraphedBeamDecode: the sampler was built with grammar_states: constrained beam search is not "
                              "supported (a beam's candidates come from the score-only launch, which reads no grammar)")
-        if isinstance(num_beams, bool) or not isinstance(num_beams, int) or not 1 <= num_beams <= 8:
+        if not _is_int(num_beams, 1, 9):
             raise ValueError(f"GraphedBeamDecode: num_beams must be an int in [1, 8]; got {num_beams!r}")
         if cache.n_slots % num_beams:
             raise ValueError(f"GraphedBeamDecode: the cache's {cache.n_slots} slots are no multiple of num_beams = {num_beams}")
-        if isinstance(history, bool) or not isinstance(history, int) or history < 1:
+        if not _is_int(history, 1):
             raise ValueError(f"GraphedBeamDecode: history must be an int >= 1; got {history!r}")
-        if isinstance(max_stop, bool) or not isinstance(max_stop, int) or not 0 <= max_stop <= 16:
+        if not _is_int(max_stop, 0, 17):
             raise ValueError(f"GraphedBeamDecode: max_stop must be an int in [0, 16]; got {max_stop!r}")
         K = ops.beam_width(num_beams, max_stop)          # refuses K > 20
         device = next(model.parameters()).device
@@ -2128,7 +2113,7 @@ class GraphedBeamDecode(GraphedMultiStreamDecode):
         self._gather_plan = None
 
     def _group(self, who: str, group) -> int:
-        if isinstance(group, bool) or not isinstance(group, int) or not 0 <= group < self.G:
+        if not _is_int(group, 0, self.G):
             raise ValueError(f"{who}: group must be an int in [0, {self.G}); got {group!r}")
         return group
 
@@ -2175,7 +2160,7 @@ class GraphedBeamDecode(GraphedMultiStreamDecode):
         if ops.beam_width(self.B, len(stop)) > self.K:
             raise ValueError(f"admit: {len(stop)} stop ids need K = {ops.beam_width(self.B, len(stop))} candidates per beam; this "
                              f"decoder was built with max_stop = {self.max_stop} (K = {self.K})")
-        if isinstance(max_new_tokens, bool) or not isinstance(max_new_tokens, int) or max_new_tokens < 1:
+        if not _is_int(max_new_tokens, 1):
             raise ValueError(f"admit: max_new_tokens must be an int >= 1; got {max_new_tokens!r}")
         if max_new_tokens > self.L:
             raise ValueError(f"admit: max_new_tokens = {max_new_tokens} exceeds the token history of {self.L} a hypothesis is "
@@ -2229,7 +2214,7 @@ class GraphedBeamDecode(GraphedMultiStreamDecode):
         """The n best finished hypotheses of `group` as (tokens int64 [len] on the host, score, sum of log-probabilities), best
         first, ties to the earlier insertion."""
         g = self._group("result", group)
-        if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+        if not _is_int(n, 1):
             raise ValueError(f"result: n must be an int >= 1; got {n!r}")
         nh = int(self.beam["n_hyp"][g].item())
         score, sums = self.beam["hyp_score"][g].cpu(), self.beam["hyp_sum"][g].cpu()
@@ -2302,7 +2287,7 @@ def score_sequence(model: InfiniteVLTextStack, cache: StaticCachePrealloc, *, in
     all when that is None; -100 entries (and anything else outside the vocabulary) are not scored.  The cache advances by T."""
     if (input_ids is None) == (inputs_embeds is None):
         raise ValueError("score_sequence: exactly one of input_ids and inputs_embeds")
-    if isinstance(chunk, bool) or not isinstance(chunk, int) or chunk < 1:
+    if not _is_int(chunk, 1):
         raise ValueError(f"score_sequence: chunk must be an int >= 1; got {chunk!r}")
     src = input_ids if inputs_embeds is None else inputs_embeds
     B, T = int(src.shape[0]), int(src.shape[1])

@@ -62,6 +62,46 @@ def _need_gpu(*ts: torch.Tensor) -> None:
                 "There is deliberately no CPU fallback in the product path.")
 
 
+def _is_int(v, lo: int, hi: Optional[int] = None) -> bool:
+    """`v` is an int (a bool is not one) with lo <= v, and v < hi where `hi` is given."""
+    return isinstance(v, int) and not isinstance(v, bool) and lo <= v and (hi is None or v < hi)
+
+
+class _TableSlots:
+    """The slot list of a table arena (LoraTable, BiasTables, FsmTables, BanTables): _slots[i] is the handle loaded at place i or
+    None.  The arena keeps its tensors, what load() checks and what unload() clears."""
+
+    def _init_slots(self, n: int, handle: type, at: str = "index") -> None:
+        """n free places for handles of the type `handle`, whose field `at` names their place."""
+        self._slots, self._handle, self._at = [None] * n, handle, at
+        self._loads = 0                  # loads so far: the serial of a handle type that carries one
+
+    def handles(self) -> list:
+        return [h for h in self._slots if h is not None]
+
+    def _free_slot(self, noun: str) -> int:
+        """The first free place; ValueError "<arena>.load: all N <noun> are taken" when there is none."""
+        if None not in self._slots:
+            raise ValueError(f"{type(self).__name__}.load: all {len(self._slots)} {noun} are taken")
+        return self._slots.index(None)
+
+    def _serial(self) -> int:
+        self._loads += 1
+        return self._loads
+
+    def _loaded(self, handle) -> bool:
+        """`handle` is of this arena's type and is what its place holds now."""
+        at = getattr(handle, self._at) if isinstance(handle, self._handle) else -1
+        return 0 <= at < len(self._slots) and self._slots[at] == handle
+
+    def _unload_slot(self, handle) -> int:
+        """Frees the place of `handle` and returns it; ValueError "<arena>.unload: ... is not loaded here" when it is not loaded."""
+        if not self._loaded(handle):
+            raise ValueError(f"{type(self).__name__}.unload: {handle!r} is not loaded here")
+        self._slots[getattr(handle, self._at)] = None
+        return getattr(handle, self._at)
+
+
 # ---------------------------------------------------------------------------------------------
 # workspace: one growable scratch buffer per (device, tag)
 # ---------------------------------------------------------------------------------------------
@@ -1459,7 +1499,7 @@ class _LoraProj:
         self.t_ws16 = torch.zeros(M16_ROWS, LORA_T_LD, dtype=torch.bfloat16, device=device)     # the 5..16-row forms' 
 
 
-class LoraTable:
+class LoraTable(_TableSlots):
     """The device tables of ivl_lora_add_small_m_fwd as ONE arena for up to `n_adapters` adapters of rank <= R, allocated once (the
     pattern of FsmTables): per registered projection the A [n_adapters, n_seg R, K] and B [n_adapters, N, R] stacks, the segment
     borders and a t workspace, and one scaling [n_adapters] for the table.  An adapter occupies ONE index across all registered
@@ -1467,19 +1507,16 @@ class LoraTable:
     two replays of a captured step need no recapture."""
 
     def __init__(self, n_adapters: int, R: int, device):
-        if isinstance(n_adapters, bool) or not isinstance(n_adapters, int) or n_adapters < 1:
+        if not _is_int(n_adapters, 1):
             raise ValueError(f"LoraTable: n_adapters must be an int >= 1; got {n_adapters!r}")
         if R not in LORA_RANKS:
             raise ValueError(f"LoraTable: the rank capacity R must be one of {LORA_RANKS}; got {R!r}")
         self.n_adapters, self.R, self.device = n_adapters, R, torch.device(device)
         self.scaling = torch.zeros(n_adapters, dtype=torch.float32, device=self.device)
         self.proj: Dict[object, _LoraProj] = {}
-        self._slots: List[Optional[LoraHandle]] = [None] * n_adapters
+        self._init_slots(n_adapters, LoraHandle)
         self._const: Dict[Tuple[int, int], torch.Tensor] = {}
         self.rows = None                 # the adapters of the forward in progress: None, a LoraHandle or an int32 device tensor
-
-    def handles(self) -> List[LoraHandle]:
-        return [h for h in self._slots if h is not None]
 
     def register(self, key, N: int, K: int, seg_cols) -> None:
         """A projection with N output columns over K inputs; segment i owns the columns [seg_cols[i], seg_cols[i + 1])."""
@@ -1497,8 +1534,7 @@ class LoraTable:
     def load(self, tensors: Dict, scaling: float, skipped=()) -> LoraHandle:
         """tensors: {key: [(A_i [r, K], B_i [n_i, r]) or None for every segment i]} (a key that is missing = not targeted); every pair
         of one rank r <= R.  Writes the adapter at a free index, zero-padded to R, and returns its handle."""
-        if None not in self._slots:
-            raise ValueError(f"LoraTable.load: all {self.n_adapters} adapter indices are taken")
+        idx = self._free_slot("adapter indices")
         unknown = [k for k in tensors if k not in self.proj]
         if unknown:
             raise ValueError(f"LoraTable.load: not registered: {unknown}")
@@ -1520,7 +1556,6 @@ class LoraTable:
                 rank = A.shape[0]
         if rank is None or not 1 <= rank <= self.R:
             raise ValueError(f"LoraTable.load: rank {rank} for a table of rank capacity {self.R}")
-        idx = self._slots.index(None)
         self._zero(idx)
         for key, pairs in tensors.items():
             p = self.proj[key]
@@ -1541,16 +1576,13 @@ class LoraTable:
 
     def unload(self, handle: LoraHandle) -> None:
         """Frees the adapter's index and zeroes its rows: a slot still pointing at it adds zeros until it is given another."""
-        if not isinstance(handle, LoraHandle) or handle.index >= self.n_adapters or self._slots[handle.index] != handle:
-            raise ValueError(f"LoraTable.unload: {handle!r} is not loaded here")
-        self._zero(handle.index)
-        self._slots[handle.index] = None
+        self._zero(self._unload_slot(handle))
 
     def index_of(self, adapter) -> int:
         """-1 for None, the index of a handle that is loaded here."""
         if adapter is None:
             return -1
-        if not isinstance(adapter, LoraHandle) or adapter.index >= self.n_adapters or self._slots[adapter.index] != adapter:
+        if not self._loaded(adapter):
             raise ValueError(f"LoraTable: {adapter!r} is not an adapter loaded here")
         return adapter.index
 
@@ -2136,7 +2168,7 @@ class BiasHandle(NamedTuple):
     serial: int
 
 
-class BiasTables:
+class BiasTables(_TableSlots):
     """The device tables of ivl_sample_adj_args' logit bias as ONE arena, allocated once: `n_tables` tables over vocab_size
     tokens, each a bitmap row of `mask` int32 [n, ceil(V/32)] (the layout of `seen`) and a row of `val` fp32 [n, V].  load()
     writes a {token id: bias} dict into a free table; unload() clears its bitmap, so a row that still points at it is not
@@ -2145,17 +2177,13 @@ class BiasTables:
 
     def __init__(self, device, vocab_size: int, n_tables: int):
         for name, v in (("vocab_size", vocab_size), ("n_tables", n_tables)):
-            if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+            if not _is_int(v, 1):
                 raise ValueError(f"BiasTables: {name} must be an int >= 1; got {v!r}")
         self.vocab_size, self.n_bias = vocab_size, n_tables
         self.mask_ld, self.ld = (vocab_size + 31) // 32, vocab_size
         self.mask = torch.zeros(n_tables, self.mask_ld, dtype=torch.int32, device=device)
         self.val = torch.zeros(n_tables, vocab_size, dtype=torch.float32, device=device)
-        self._slots: List[Optional[BiasHandle]] = [None] * n_tables
-        self._loads = 0
-
-    def handles(self) -> List["BiasHandle"]:
-        return [h for h in self._slots if h is not None]
+        self._init_slots(n_tables, BiasHandle)
 
     def load(self, bias: dict) -> "BiasHandle":
         """Writes {token id: bias} (ids in [0, vocab_size), values floats; -inf bans a token, +inf forces it, NaN is refused)
@@ -2170,9 +2198,7 @@ class BiasTables:
                 raise ValueError(f"BiasTables.load: the bias of token {k} must be a number that is not NaN; got {v!r}")
             ids.append(int(k))
             vals.append(float(v))
-        if None not in self._slots:
-            raise ValueError(f"BiasTables.load: all {self.n_bias} tables are taken")
-        slot = self._slots.index(None)
+        slot = self._free_slot("tables")
         dev = self.mask.device
         idx = np.asarray(ids, dtype=np.int64)
         words = np.zeros(self.mask_ld, dtype=np.uint32)
@@ -2182,17 +2208,14 @@ class BiasTables:
             row[idx] = np.asarray(vals, dtype=np.float64).astype(np.float32)
         self.val[slot] = torch.from_numpy(row).to(dev)
         self.mask[slot] = torch.from_numpy(words.view(np.int32)).to(dev)
-        self._loads += 1
-        self._slots[slot] = h = BiasHandle(slot, tuple(sorted(ids)), self._loads)
+        self._slots[slot] = h = BiasHandle(slot, tuple(sorted(ids)), self._serial())
         return h
 
     def unload(self, handle: "BiasHandle") -> None:
         """Frees the table; it biases nothing from now on."""
-        if not isinstance(handle, BiasHandle) or handle.index >= len(self._slots) or self._slots[handle.index] != handle:
-            raise ValueError(f"BiasTables.unload: {handle!r} is not loaded here")
-        self.mask[handle.index].zero_()
-        self.val[handle.index].zero_()
-        self._slots[handle.index] = None
+        at = self._unload_slot(handle)
+        self.mask[at].zero_()
+        self.val[at].zero_()
 
 
 class FsmHandle(NamedTuple):
@@ -2205,7 +2228,7 @@ class FsmHandle(NamedTuple):
     trans_len: int
 
 
-class FsmTables:
+class FsmTables(_TableSlots):
     """The device tables of ivl_sample_args' constraint group as ONE arena for several grammars (grammar.TokenFsm), allocated once: room
     for `states` states in all, `grammars` grammars at a time (one class table of vocab_size entries each) and `trans`
     transition entries (a grammar takes n_states x n_classes of them).  load() writes a grammar at a free range, its transition
@@ -2215,20 +2238,17 @@ class FsmTables:
 
     def __init__(self, device, vocab_size: int, states: int, grammars: int, trans: int, mask_ld: Optional[int] = None):
         for name, v in (("vocab_size", vocab_size), ("states", states), ("grammars", grammars), ("trans", trans)):
-            if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+            if not _is_int(v, 1):
                 raise ValueError(f"FsmTables: {name} must be an int >= 1; got {v!r}")
         words = (vocab_size + 31) // 32
-        if mask_ld is not None and (isinstance(mask_ld, bool) or not isinstance(mask_ld, int) or mask_ld < words):
+        if mask_ld is not None and not _is_int(mask_ld, words):
             raise ValueError(f"FsmTables: mask_ld must be an int >= {words} (the words of vocab_size {vocab_size}); got {mask_ld!r}")
         self.vocab_size, self.n_states, self.mask_ld = vocab_size, states, words if mask_ld is None else mask_ld
         self.mask = torch.zeros(states, self.mask_ld, dtype=torch.int32, device=device)
         self.desc = torch.zeros(states, 2, dtype=torch.int64, device=device)
         self.cls = torch.zeros(grammars * vocab_size, dtype=torch.int32, device=device)
         self.trans = torch.full((trans,), -2, dtype=torch.int32, device=device)
-        self._slots: List[Optional[FsmHandle]] = [None] * grammars
-
-    def handles(self) -> List[FsmHandle]:
-        return [h for h in self._slots if h is not None]
+        self._init_slots(grammars, FsmHandle, "slot")
 
     @staticmethod
     def _first_fit(taken, need: int, room: int) -> Optional[int]:
@@ -2253,7 +2273,7 @@ class FsmTables:
                              f"{sum(h.n_states for h in held)} of {self.n_states} states and {sum(h.trans_len for h in held)} of "
                              f"{self.trans.shape[0]} transition entries are taken; this grammar needs {n} states and {n_trans} "
                              f"entries, each in one piece")
-        slot = self._slots.index(None)
+        slot = self._free_slot("grammars")
         dev = self.mask.device
         t = fsm.trans.astype(np.int32)
         self.trans[off:off + n_trans] = torch.from_numpy(np.where(t >= 0, t + base, t).astype(np.int32).reshape(-1)).to(dev)
@@ -2267,11 +2287,9 @@ class FsmTables:
 
     def unload(self, handle: FsmHandle) -> None:
         """Frees the grammar's ranges; its states allow nothing from now on."""
-        if handle.slot >= len(self._slots) or self._slots[handle.slot] != handle:
-            raise ValueError(f"FsmTables.unload: {handle!r} is not loaded here")
+        self._unload_slot(handle)
         self.mask[handle.base:handle.base + handle.n_states].zero_()
         self.trans[handle.trans_off:handle.trans_off + handle.trans_len] = -2
-        self._slots[handle.slot] = None
 
     def local(self, state: int) -> Optional[Tuple[FsmHandle, int]]:
         """(handle, local state) of a global state, or None where no loaded grammar owns it."""
@@ -2311,7 +2329,7 @@ class BanHandle(NamedTuple):
     serial: int
 
 
-class BanTables:
+class BanTables(_TableSlots):
     """The device tables of ivl_ban_args' sequence rule as ONE arena, allocated once: `n_tables` tables of up to `n_seq`
     sequences of up to `max_len` tokens, `seq` int64 [n_tables, n_seq, max_len], a sequence right-aligned in its row and -1
     everywhere else (`bad_words_ids` of HF generate, one table per request).  load() writes a list of token-id lists into a free
@@ -2321,17 +2339,13 @@ class BanTables:
 
     def __init__(self, device, n_tables: int, n_seq: int = 64, max_len: int = 8):
         for name, v in (("n_tables", n_tables), ("n_seq", n_seq), ("max_len", max_len)):
-            if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+            if not _is_int(v, 1):
                 raise ValueError(f"BanTables: {name} must be an int >= 1; got {v!r}")
         if max_len > 16:
             raise ValueError(f"BanTables: max_len must be at most 16; got {max_len}")
         self.n_tables, self.n_seq, self.seq_ld = n_tables, n_seq, max_len
         self.seq = torch.full((n_tables, n_seq, max_len), -1, dtype=torch.int64, device=device)
-        self._slots: List[Optional[BanHandle]] = [None] * n_tables
-        self._loads = 0
-
-    def handles(self) -> List["BanHandle"]:
-        return [h for h in self._slots if h is not None]
+        self._init_slots(n_tables, BanHandle)
 
     def load(self, seqs) -> "BanHandle":
         """Writes a list of token-id lists (each 1..max_len ints >= 0, at most n_seq of them) into a free table and returns
@@ -2352,20 +2366,14 @@ class BanTables:
                 if isinstance(t, bool) or not isinstance(t, (int, np.integer)) or not 0 <= int(t) < 2 ** 63:
                     raise ValueError(f"BanTables.load: token id {t!r} of sequence {r} is not an int >= 0")
             rows[r, self.seq_ld - len(q):] = [int(t) for t in q]
-        if None not in self._slots:
-            raise ValueError(f"BanTables.load: all {self.n_tables} tables are taken")
-        slot = self._slots.index(None)
+        slot = self._free_slot("tables")
         self.seq[slot] = torch.from_numpy(rows).to(self.seq.device)
-        self._loads += 1
-        self._slots[slot] = h = BanHandle(slot, self._loads)
+        self._slots[slot] = h = BanHandle(slot, self._serial())
         return h
 
     def unload(self, handle: "BanHandle") -> None:
         """Frees the table; it bans nothing from now on."""
-        if not isinstance(handle, BanHandle) or not 0 <= handle.index < len(self._slots) or self._slots[handle.index] != handle:
-            raise ValueError(f"BanTables.unload: {handle!r} is not loaded here")
-        self.seq[handle.index].fill_(-1)
-        self._slots[handle.index] = None
+        self.seq[self._unload_slot(handle)].fill_(-1)
 
 
 def ban_tokens(logits: torch.Tensor, *, n_new: torch.Tensor, history: Optional[torch.Tensor] = None,
@@ -2584,14 +2592,14 @@ class RowCopyPlan:
 
     def check_rows(self, src_row, dst_rows) -> int:
         """Validates the rows of a run (no device work) and returns the destination mask."""
-        if isinstance(src_row, bool) or not isinstance(src_row, int) or not 0 <= src_row < self.n_src_rows:
+        if not _is_int(src_row, 0, self.n_src_rows):
             raise ValueError(f"RowCopyPlan.run: src_row must be an int in [0, {self.n_src_rows}); got {src_row!r}")
         dst_rows = list(dst_rows)
         if not dst_rows:
             raise ValueError("RowCopyPlan.run: dst_rows is empty")
         mask = 0
         for r in dst_rows:
-            if isinstance(r, bool) or not isinstance(r, int) or not 0 <= r < self.n_dst_rows:
+            if not _is_int(r, 0, self.n_dst_rows):
                 raise ValueError(f"RowCopyPlan.run: dst_rows must be ints in [0, {self.n_dst_rows}); got {r!r}")
             if mask >> r & 1:
                 raise ValueError(f"RowCopyPlan.run: row {r} is repeated in dst_rows {dst_rows}")
@@ -2696,9 +2704,9 @@ class RowGatherPlan:
 def beam_width(num_beams: int, n_stop: int) -> int:
     """K of a beam step: the candidates every beam offers and the length of the walk, max(2, 1 + n_stop) * num_beams -- enough
     for the first K ranked candidates to hold num_beams that are no stop id.  ValueError above 20 (the scoring launch's limit)."""
-    if isinstance(num_beams, bool) or not isinstance(num_beams, int) or not 1 <= num_beams <= 8:
+    if not _is_int(num_beams, 1, 9):
         raise ValueError(f"beam_width: num_beams must be an int in [1, 8]; got {num_beams!r}")
-    if isinstance(n_stop, bool) or not isinstance(n_stop, int) or n_stop < 0:
+    if not _is_int(n_stop, 0):
         raise ValueError(f"beam_width: n_stop must be an int >= 0; got {n_stop!r}")
     K = max(2, 1 + n_stop) * num_beams
     if K > 20:
@@ -2714,7 +2722,7 @@ _BEAM_GROUP = (("length_penalty", torch.float64, 1), ("early_stopping", torch.in
 
 
 def _beam_check(who: str, G: int, B: int, L: int, group_mask, st: dict, names) -> int:
-    if isinstance(group_mask, bool) or not isinstance(group_mask, int) or not 0 <= group_mask < (1 << G):
+    if not _is_int(group_mask, 0, (1 << G)):
         raise ValueError(f"{who}: group_mask must be an int in [0, 2^{G}); got {group_mask!r}")
     for name, dt, nd in _BEAM_GROUP:
         if name not in names:
@@ -2734,7 +2742,7 @@ def beam_select(B: int, group_mask: int, top_ids: torch.Tensor, top_logprobs: to
     state["parent"] / ["next_token"] / ["next_score"] [G,B], the hypothesis tables state["n_hyp"], ["hyp_score"], ["hyp_sum"],
     ["hyp_len"], ["hyp_tokens"] and state["beam_done"].  S = G * B slots; n_new [S] int64, history [S,L] int64, stop_ids [G,n]
     int64 or None; state also holds length_penalty [G] float64 and early_stopping [G] int32."""
-    if isinstance(B, bool) or not isinstance(B, int) or not 1 <= B <= 8:
+    if not _is_int(B, 1, 9):
         raise ValueError(f"beam_select: B must be an int in [1, 8]; got {B!r}")
     if top_ids.dim() != 2 or top_ids.shape[0] % B or not 1 <= top_ids.shape[1] <= 20:
         raise ValueError(f"beam_select: top_ids must be [G*{B},K] with 1 <= K <= 20; got {tuple(top_ids.shape)}")
@@ -2772,7 +2780,7 @@ def beam_commit(B: int, group_mask: int, token: torch.Tensor, seen: Optional[tor
     (ivl_beam_commit_fwd): token [S] or [S,1] int64 <- state["next_token"], the token's bit of seen [S,W] int32 (or None), its
     place in history [S,L], n_new += 1, cum_logprob <- state["next_score"]; a group whose n_new reaches state["budget"] files
     its beams as hypotheses and ends with beam_done = 2 and state["parent"] = the identity."""
-    if isinstance(B, bool) or not isinstance(B, int) or not 1 <= B <= 8:
+    if not _is_int(B, 1, 9):
         raise ValueError(f"beam_commit: B must be an int in [1, 8]; got {B!r}")
     if history.dim() != 2 or history.shape[0] % B or history.shape[1] < 1:
         raise ValueError(f"beam_commit: history must be [G*{B},L]; got {tuple(history.shape)}")
@@ -2786,7 +2794,7 @@ def beam_commit(B: int, group_mask: int, token: torch.Tensor, seen: Optional[tor
             raise ValueError(f"beam_commit: {name} must be a contiguous {dt} tensor of {list(want)}; got {t.dtype} {tuple(t.shape)}")
     V = 0
     if seen is not None:
-        if isinstance(vocab_size, bool) or not isinstance(vocab_size, int) or vocab_size < 1:
+        if not _is_int(vocab_size, 1):
             raise ValueError(f"beam_commit: seen needs vocab_size, an int >= 1; got {vocab_size!r}")
         V = vocab_size
         if seen.dtype != torch.int32 or tuple(seen.shape[:1]) != (S,) or seen.dim() != 2 or not seen.is_contiguous() or \

@@ -535,3 +535,53 @@ def test_graphed_decode_batch_two_with_controls():
     assert runs[0][0] == runs[1][0]
     for k_ in runs[0][1]:
         assert torch.equal(runs[0][1][k_], runs[1][1][k_]), k_
+
+
+def _bytes_equal(a, b):
+    return a.shape == b.shape and a.dtype == b.dtype and torch.equal(a.contiguous().flatten().view(torch.uint8),
+                                                                      b.contiguous().flatten().view(torch.uint8))
+
+
+def test_admit_n_equals_admit_with_every_option_on():
+    """admit_n(slots, ...) leaves every slot as admit(slot, ...) with that slot's dict would: sampling, prompt_ids, a grammar, a
+    bias table and a bad-words table at once, on a sampler with every per-row option but guidance.  Tokens of the admission and of
+    6 graphed steps, the sampler's state and every tensor a slot owns (cache rows, token, positions, sampler rows), byte for byte."""
+    from infinitevl_amd.cache import MultiStreamCache
+    from infinitevl_amd.grammar import TokenFsm
+    from infinitevl_amd.harness import GraphedMultiStreamDecode, Sampler
+    stack, hc = _small()
+    V = hc.vocab_size
+    x, ids = _prompt(hc, 37, 21)
+    fsm = TokenFsm.from_edges(V, 2, [(0, list(range(0, V, 2)), 1), (1, list(range(V)), 0)])   # every state allows >= V/2 tokens
+    dicts = [dict(temperature=0.8, top_k=40, top_p=0.95, seed=5, repetition_penalty=1.2, min_p=0.01, frequency_penalty=0.3,
+                  no_repeat_ngram_size=2, max_new_tokens=4, fill_token=3),
+             dict(repetition_penalty=1.4, presence_penalty=0.5, min_new_tokens=3, stop_token_ids=[8, 9]),
+             dict(temperature=1.3, seed=-9, top_k=0, min_p=0.02, no_repeat_ngram_size=3)]
+    runs = []
+    for n_way in (True, False):
+        cache = MultiStreamCache(config=hc, n_slots=4, device=DEV, dtype=torch.bfloat16)
+        smp = Sampler(4, DEV, vocab_size=V, history=32, logprobs=2, grammar_states=8, penalties=True, bias_tables=2, bans=True,
+                      ban_context=16, ban_tables=2, ban_seqs=8, ban_len=4)
+        dec = GraphedMultiStreamDecode(stack, cache, sampler=smp)
+        opts = dict(prompt_ids=ids, grammar=smp.load_grammar(fsm), logit_bias=smp.load_logit_bias({5: -INF, 12: 2.0, 100: -1.5}),
+                    bad_words=smp.load_bad_words([[7], [20, 22], [1, 2, 3, 4]]))
+        if n_way:
+            dec.admit_n([0, 1, 2], x, sampling=dicts, **opts)
+        else:
+            for slot in range(3):
+                dec.admit(slot, x, sampling=dicts[slot], **opts)
+        toks = [dec.token[:3, 0].tolist()]
+        for _ in range(6):
+            dec.step()
+            toks.append(dec.token[:3, 0].tolist())
+        torch.cuda.synchronize()
+        runs.append((toks, _state(smp), [t[:3].cpu() for t in dec._slot_tensors()]))
+    (toks_n, st_n, rows_n), (toks_1, st_1, rows_1) = runs
+    assert not (st_n["done"][:3] == 3).any() and st_n["done"][0].item() == 2, "no row meets a dead end; row 0 spends its budget"
+    assert toks_n == toks_1
+    assert set(st_n) == set(st_1)
+    for k_ in st_n:
+        assert _bytes_equal(st_n[k_], st_1[k_]), k_
+    assert len(rows_n) == len(rows_1)
+    for i, (a, b) in enumerate(zip(rows_n, rows_1)):
+        assert _bytes_equal(a, b), i
