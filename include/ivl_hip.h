@@ -263,6 +263,20 @@ IVL_API int ivl_swa_fwd(const ivl_swa_args* args, void* stream);
  * combine with the append folded in), with the split count of ivl_swa_fwd: a row's output and ring are bit-identical to a
  * B = 1 ivl_swa_fwd of that row.  Other shapes: IVL_ERR_UNSUPPORTED; NULL pos_rows: IVL_ERR_INVALID_ARG. */
 IVL_API int ivl_swa_decode_rows_fwd(const ivl_swa_args* args, const int64_t* pos_rows, void* stream);
+/* ivl_swa_fwd with ONE RING POSITION PER BATCH ROW for every T >= 1: a T-token frame for each of B independent streams in one call.
+ * pos_rows: device int64[B], never written.  args->pos, pos_dev and pos_min are ignored; the 256-row form of a full ring is never
+ * taken.  Scope: a ring cache, T_new == T, mma_dtype IVL_BF16; fused rope and append_new as in ivl_swa_fwd.  Workspace:
+ * ivl_swa_workspace_bytes(B, T, Hq, d).  The launch plan is ivl_swa_fwd's for the same B, T, Hq, Hkv, window and capacity (form,
+ * split count, rope pre-pass, combine with the append folded in; the stand-alone append launch when there is one split): packed
+ * shapes (T * Hq/Hkv <= 64) run the launches of ivl_swa_decode_rows_fwd, T <= 64 the 64-row kernel, longer calls the 128-row kernel,
+ * each reading pos_rows[b] where its twin reads the scalar position.
+ *   ROWS-1 row b's rows of o and its ring row are bit-equal to row b of ivl_swa_fwd on the same arguments with every row at
+ *          pos = pos_rows[b].
+ *   ROWS-2 a row depends on its own row only (its q, keys, ring row and position): what the other rows hold changes no bit of it.
+ *   ROWS-3 the positions are read when the launch RUNS: one captured call serves every step, the same bits eager or replayed.
+ *   ROWS-4 with append_new and T > cache_capacity only the last cache_capacity tokens of a row reach its ring, as in ivl_swa_fwd.
+ * Refusals are ivl_swa_decode_rows_fwd's minus the packing rule. */
+IVL_API int ivl_swa_rows_fwd(const ivl_swa_args* args, const int64_t* pos_rows, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Per-row HOLD of a multi-stream step.  `frozen`: device int32 [B], read when the launch RUNS (at replay); row b is frozen when

@@ -579,7 +579,8 @@ def _retype(obj, cls):
 class MultiStreamSlidingLayer(StaticSlidingWindowLayerPrealloc):
     """Sliding layer of a MultiStreamCache: row b of the ring belongs to slot b, which has its own position
     `_pos_rows[b]` (device int64 [n_slots], shared by all sliding layers of the cache; `_lengths` is its host mirror).
-    Decode steps of one token only: a prompt is prefilled on MultiStreamCache.slot_view."""
+    A call of T tokens gives every slot T tokens: one for a decode step (the only form that reads a hold mask), a frame for
+    T > 1 (ops.swa_forward_rows).  A prompt of one slot alone is prefilled on MultiStreamCache.slot_view."""
 
     def __init__(self, **kw):
         super().__init__(**kw)
@@ -590,13 +591,22 @@ class MultiStreamSlidingLayer(StaticSlidingWindowLayerPrealloc):
 
     def attend(self, q, k_new, v_new, scaling, window, mma_dtype=None, rope=None):
         B, T, Hkv, D = k_new.shape
-        if T != 1:
-            raise ValueError(f"MultiStreamCache decodes one token per slot and step (got T={T}); prefill a slot through "
-                             "MultiStreamCache.slot_view(slot)")
         if mma_dtype is not None and ops.mma_code(mma_dtype) != ops.IVL_BF16:
             raise ValueError("MultiStreamCache: the fp8 decode step is not supported (bf16 only)")
         if B != self.batch_size:
             raise ValueError(f"MultiStreamCache has {self.batch_size} slots, but got B={B}")
+        if T != 1:
+            if not q.is_cuda:
+                raise ValueError(f"MultiStreamCache: a frame step (T={T} tokens for every slot) runs on the GPU only; one slot alone "
+                                 "is prefilled through MultiStreamCache.slot_view(slot)")
+            # a frame step: T tokens for EVERY slot (ivl_swa_rows_fwd).  The hold mask is not read: a held or finished slot takes the
+            # tokens too, as extend() on a finished slot does (the GDN chunk kernels have no per-slot mask either)
+            o = ops.swa_forward_rows(q, k_new, v_new, window=window, scaling=scaling, k_cache=self._buf_keys,
+                                     v_cache=self._buf_values, pos_rows=self._pos_rows, rope=rope, append=True)
+            if self._advances_counter:
+                self._pos_rows.add_(T)
+            self.advance(T)
+            return o
         if self._frozen is not None:         # hold mode: a frozen row keeps its ring row and its position
             o = ops.swa_forward(q, k_new, v_new, window=window, scaling=scaling, k_cache=self._buf_keys,
                                 v_cache=self._buf_values, pos_rows=self._pos_rows, rope=rope, append=True, frozen=self._frozen)

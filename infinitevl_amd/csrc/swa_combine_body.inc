@@ -1,5 +1,5 @@
 // Bodies of the split-KV combine kernels (swa.hip), included inside the kernel functions that share them: SWA_WIDE 0 the
-// templated combine (NS, BF16P in scope), SWA_WIDE 1 the wide one; SWA_ROWS 1 (ivl_swa_decode_rows_fwd) appends every batch
+// templated combine (NS, BF16P in scope), SWA_WIDE 1 the wide one; SWA_ROWS 1 (ivl_swa_decode_rows_fwd, ivl_swa_rows_fwd) appends every batch
 // row at its own position (ring_append<1>); SWA_ROWS 2 (ivl_swa_decode_rows_hold_fwd, `frozen` in scope) also skips the merge, the o
 // store and the ring slots of a frozen batch row.  Textual inclusion keeps the generated code of the pre-existing combine kernels
 // exactly what it was when the bodies were written inside them.

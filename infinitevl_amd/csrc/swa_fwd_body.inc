@@ -1,6 +1,6 @@
 // Body of the 64-row attention kernel (swa.hip), included inside the kernel functions that share it: swa_fwd_kernel<PACK, QG>
-// (SWA_ROWS 0: pos_dev is a scalar position, or NULL for p.pos) and swa_rows_decode_kernel (SWA_ROWS 1: pos_dev is an int64[B],
-// one ring position per batch row; SWA_ROWS 2, swa_rows_hold_decode_kernel: the same with `frozen` (int32[B]) in scope -- the
+// (SWA_ROWS 0: pos_dev is a scalar position, or NULL for p.pos), swa_rows_decode_kernel and swa_rows_fwd_kernel (SWA_ROWS 1: pos_dev
+// is an int64[B], one ring position per batch row; PACK = true resp. false; SWA_ROWS 2, swa_rows_hold_decode_kernel: the same with `frozen` (int32[B]) in scope -- the
 // workgroups of a frozen batch row leave before their first load, ahead of every barrier).  Textual inclusion keeps the generated code of swa_fwd_kernel exactly what it was when the
 // body was written inside it (a __forceinline__ device function is inlined later in the optimisation pipeline and changes it).
 // Expects: PACK, QG (compile-time), pos_dev, p (SwaParams) in scope, SWA_ROWS defined.  The tile phases are attn_tile64.h's.

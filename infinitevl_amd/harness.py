@@ -746,6 +746,71 @@ class GraphedStep(_Graphed):
         return self.hidden, self.logits
 
 
+class GraphedMultiStreamStep(_Graphed):
+    """The GraphedStep of a MultiStreamCache: ONE captured forward feeds a frame of T tokens to EVERY slot -- the weights are
+    streamed once for all S streams, each slot attends at its own ring position (ops.swa_forward_rows).  Static buffers
+    inputs_embeds [S,T,hidden] and position_ids [3,S,T]; the positions advance by T inside the graph as in GraphedStep (a
+    caller whose frames are not text-like overwrites them through step()).  Streams join and leave between replays (admit /
+    release on the cache or on a GraphedMultiStreamDecode over it) without a recapture; an idle slot computes on zeros.  Every
+    slot takes the frame: a hold mask on the cache is not read (the GDN chunk kernels have no per-slot mask).  bf16 only, no
+    adapter table (prefill adapters read their indices on the host)."""
+
+    def __init__(self, model: InfiniteVLTextStack, cache: MultiStreamCache, T: int, logits_to_keep: int = 1, warmup: int = 2):
+        if not isinstance(cache, MultiStreamCache):
+            raise ValueError(f"GraphedMultiStreamStep: needs a MultiStreamCache (got {type(cache).__name__}); a "
+                             "StaticCachePrealloc steps through GraphedStep")
+        if not _is_int(T, 1, 1 << 30):
+            raise ValueError(f"GraphedMultiStreamStep: T must be an int >= 1; got {T!r}")
+        if any(getattr(l.self_attn, "mma_dtype", None) is not None for l in model.layers):
+            raise ValueError("GraphedMultiStreamStep: the fp8 paths are not supported (bf16 only)")
+        self.model, self.cache, self.T, self.S = model, cache, int(T), cache.n_slots
+        self._refuse_adapters()
+        p_ = next(model.parameters())
+        self.inputs_embeds = torch.zeros(self.S, self.T, model.config.hidden_size, dtype=p_.dtype, device=p_.device)
+        self.position_ids = torch.zeros(3, self.S, self.T, dtype=torch.int64, device=p_.device)
+        self.logits_to_keep = logits_to_keep
+        self.graph: Optional[torch.cuda.CUDAGraph] = None
+        self.hidden = self.logits = None
+        self._warmup = warmup
+        self._sync: Optional[torch.Tensor] = None
+
+    def _refuse_adapters(self) -> None:
+        if getattr(self.model, "_lora", None) is not None:
+            raise ValueError("GraphedMultiStreamStep: a model with an adapter table attached (enable_adapters) is not supported: "
+                             "prefill adapters read their indices on the host")
+
+    def _run(self):
+        h, lg = self.model(inputs_embeds=self.inputs_embeds, position_ids=self.position_ids, past_key_values=self.cache,
+                           logits_to_keep=self.logits_to_keep)
+        self.position_ids.add_(self.T)
+        return h, lg
+
+    def capture(self) -> None:
+        """Warm up on a side stream and capture; every slot's ring, state and position and both buffers are restored."""
+        self._refuse_adapters()
+        self.cache.ensure_started()
+        if self._sync is None:               # the graph owns the flag words of its single-launch GDN calls (ops.gdn_sync_scope)
+            self._sync = ops.new_gdn_sync_area(self.inputs_embeds.device)
+        self.hidden, self.logits = self._capture([self.position_ids, self.inputs_embeds], ops.gdn_sync_scope(self._sync))
+
+    def step(self, inputs_embeds: Optional[torch.Tensor] = None, position_ids: Optional[torch.Tensor] = None, graph: bool = True):
+        """Copies what it is given into the static buffers, replays, returns (hidden [S,T,hidden], logits [S,keep,vocab]).
+        graph=False runs the same step eagerly (the reference the captured graph is checked against)."""
+        if inputs_embeds is not None:
+            self.inputs_embeds.copy_(inputs_embeds)
+        if position_ids is not None:
+            self.position_ids.copy_(position_ids)
+        if not graph:
+            with torch.no_grad():
+                return self._run()
+        if self._stale():
+            self.capture()
+        self.graph.replay()
+        self.cache.advance(self.T)           # (with holds the per-slot mirror is rewritten by cache.sync_lengths())
+        ops.gdn_sync_check(self.inputs_embeds.device)
+        return self.hidden, self.logits
+
+
 class _RowField(NamedTuple):
     """One per-row tensor of a Sampler (Sampler._TABLE)."""
     name: str                   # the attribute
@@ -1908,6 +1973,43 @@ class GraphedMultiStreamDecode(_Graphed):
             self.position_ids[:, partner].copy_(negative_position_ids.max() + 1)
         self.position_ids[:, slot].copy_(position_ids.max() + 1)
         return self.token[slot]
+
+    @torch.no_grad()
+    def extend_frames(self, stepper: "GraphedMultiStreamStep", inputs_embeds: torch.Tensor,
+                      position_ids: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """extend() for EVERY slot at once: inputs_embeds [S,T,hidden] -- the next video frame of every stream -- goes through ONE
+        replay of `stepper` (a GraphedMultiStreamStep of T tokens on the same cache), which streams the weights once for all
+        slots.  position_ids [3,S,T]; default: each slot's three positions count on from position_ids[:, slot] (computed on the
+        device).  Every slot's next token is drawn from logits[:, -1] in one sampling launch (argmax without a sampler) and
+        REPLACES its pending one; position_ids[:, s] becomes slot s's maximum + 1; admit_logits is set.  No host read-back.
+        Every slot takes the frame (an idle slot computes on zeros, its token is ignored).  Not with holds=True (the frame step
+        reads no mask) and not while the sampler has a guided pair (a pair's halves take different prompts)."""
+        who = "extend_frames"
+        if self.holds:
+            raise ValueError(f"{who}: holds=True is not supported (the frame step reads no hold mask: a frozen slot would take the frame)")
+        if self.sampler is not None and self.sampler._partner:
+            raise ValueError(f"{who}: the sampler has a guided pair (rows {sorted(self.sampler._partner.items())}); a pair is "
+                             f"extended slot by slot with extend(negative_embeds=)")
+        if not isinstance(stepper, GraphedMultiStreamStep) or stepper.cache is not self.cache:
+            raise ValueError(f"{who}: needs a GraphedMultiStreamStep on this decoder's cache")
+        T = stepper.T
+        want = (self.S, T, self.model.config.hidden_size)
+        if not torch.is_tensor(inputs_embeds) or tuple(inputs_embeds.shape) != want:
+            raise ValueError(f"{who}: inputs_embeds must be [S,T,hidden] = {list(want)}; got "
+                             f"{list(inputs_embeds.shape) if torch.is_tensor(inputs_embeds) else type(inputs_embeds).__name__}")
+        if position_ids is not None and tuple(position_ids.shape) != (3, self.S, T):
+            raise ValueError(f"{who}: position_ids must be [3,{self.S},{T}]; got {tuple(position_ids.shape)}")
+        dev = self.position_ids.device
+        if position_ids is None:
+            position_ids = self.position_ids + torch.arange(T, device=dev, dtype=torch.int64)
+        else:
+            position_ids = position_ids.to(device=dev, dtype=torch.int64)
+        nxt = position_ids.amax(dim=(0, 2)) + 1                          # [S]
+        _, lg = stepper.step(inputs_embeds, position_ids)
+        self.admit_logits = lg
+        self._next_token(lg[:, -1])
+        self.position_ids.copy_(nxt.view(1, self.S, 1).expand(3, self.S, 1))
+        return self.token
 
     @torch.no_grad()
     def score(self, slot: int, inputs_embeds: torch.Tensor, labels: torch.Tensor, position_ids: Optional[torch.Tensor] = None,

@@ -180,7 +180,7 @@ class InfiniteVLSelfAttention(nn.Module):
 
 _HOLD_REFUSAL = ("the cache keeps a hold mask (MultiStreamCache.enable_holds), and this Gated DeltaNet call does not reach the masked "
                  "one-launch step: it would overwrite the states of frozen slots.  Holds need a fuse_()d bf16 stack with 128 x 256 "
-                 "heads on a bf16 cache, and T = 1 steps (a prompt runs on MultiStreamCache.slot_view)")
+                 "heads on a bf16 cache (a call of T > 1 tokens reads no mask: every slot takes them)")
 
 
 class GatedDeltaNet(nn.Module):
@@ -367,7 +367,7 @@ class GatedDeltaNet(nn.Module):
                                    recurrent_state=layer.recurrent_state,
                                    cache_kwargs={"op": "set", "delta_len": T, "cache_position": cache_position})
             return ops.linear(o, self.o_proj.weight, self.o_proj.bias, **w8_o, **kw_o), None
-        if frozen is not None:
+        if frozen is not None and T == 1:      # (a frame step, T > 1, does not read the mask: every slot takes the tokens)
             raise RuntimeError(_HOLD_REFUSAL)
         convs = (self.q_conv1d.weight, self.k_conv1d.weight, self.v_conv1d.weight)
         if mode == "chunk" and Dk == Dq and K == 128 and V == 256 and convs[0].shape[-1] == 4:
@@ -402,7 +402,7 @@ class GatedDeltaNet(nn.Module):
             return self._forward_fused(hidden_states, past_key_values, layer, cache_position, mode)
         if self._lora is not None:
             raise RuntimeError("adapters are attached (enable_adapters): they ride on the fused bf16 projections only")
-        if getattr(past_key_values, "hold_mask", None) is not None:
+        if getattr(past_key_values, "hold_mask", None) is not None and q_len == 1:
             raise RuntimeError(_HOLD_REFUSAL)
         if isinstance(hidden_states, ops.PreNorm):
             hidden_states = hidden_states.materialize()

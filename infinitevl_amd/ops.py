@@ -1894,6 +1894,64 @@ def swa_forward(
     return o
 
 
+ROWS_STEP_CALLS = 0            # calls of swa_forward_rows (tests and tools read it to know that a frame step ran on ivl_swa_rows_fwd)
+
+
+def swa_forward_rows(
+    q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor, *, window: Optional[int], scaling: float,
+    k_cache: torch.Tensor, v_cache: torch.Tensor, pos_rows: torch.Tensor, rope=None, append: bool = False,
+    layout: str = "bthd",
+) -> torch.Tensor:
+    """swa_forward with one ring position per batch row for every T >= 1 (ivl_swa_rows_fwd): a T-token frame for each of B
+    independent streams in the rows of one ring cache; returns o [B,T,Hq,d] bf16.  Layout and stride rules as swa_forward.
+    `pos_rows` (device int64 [B]) is read when the launch runs and is not advanced.  Row b's output and ring row are
+    bit-equal to row b of swa_forward on the same tensors with every row at pos_rows[b] (ROWS-1 in include/ivl_hip.h).
+    Ring cache, T_new == T, bf16; `rope` and `append` as in swa_forward."""
+    _need_gpu(q, k_new, v_new, k_cache, v_cache, pos_rows)
+    if q.dtype != torch.bfloat16 or k_new.dtype != torch.bfloat16 or v_new.dtype != torch.bfloat16:
+        raise ValueError("swa_forward_rows is built for bf16")
+    if layout == "bhtd":
+        q, k_new, v_new = q.transpose(1, 2), k_new.transpose(1, 2), v_new.transpose(1, 2)
+    B, T, Hq, d = q.shape
+    T_new, Hkv = k_new.shape[1], k_new.shape[2]
+    if pos_rows.dtype != torch.int64 or tuple(pos_rows.shape) != (B,) or not pos_rows.is_contiguous():
+        raise ValueError(f"swa_forward_rows: pos_rows must be a contiguous int64 [B] = [{B}] tensor; got {pos_rows.dtype} "
+                         f"{tuple(pos_rows.shape)}")
+    if k_cache is None or v_cache is None:
+        raise ValueError("swa_forward_rows: pos_rows needs a ring cache (k_cache / v_cache)")
+    if T_new != T:
+        raise ValueError(f"swa_forward_rows: needs T_new == T (got T={T}, T_new={T_new})")
+    if q.stride(-1) != 1:
+        q = q.contiguous()
+    if k_new.stride(-1) != 1 or v_new.stride() != k_new.stride():
+        k_new, v_new = k_new.contiguous(), v_new.contiguous()
+    assert k_cache.is_contiguous() and v_cache.is_contiguous() and k_cache.dtype == torch.bfloat16
+    assert tuple(k_cache.shape[:2]) == (B, Hkv) and k_cache.shape[3] == d and tuple(v_cache.shape) == tuple(k_cache.shape)
+    C = k_cache.shape[2]
+    o = torch.empty(B, T, Hq, d, dtype=torch.bfloat16, device=q.device)
+    lib = _lib.load()
+    ws = get_workspace(lib.ivl_swa_workspace_bytes(B, T, Hq, d), q.device, "swa")
+    a = SwaArgs()
+    a.q, a.k_new, a.v_new, a.k_cache, a.v_cache, a.o = (q.data_ptr(), k_new.data_ptr(), v_new.data_ptr(), k_cache.data_ptr(),
+                                                         v_cache.data_ptr(), o.data_ptr())
+    a.q_sb, a.q_st, a.q_sh = q.stride(0), q.stride(1), q.stride(2)
+    a.kn_sb, a.kn_st, a.kn_sh = k_new.stride(0), k_new.stride(1), k_new.stride(2)
+    a.B, a.T, a.T_new, a.Hq, a.Hkv, a.d = B, T, T_new, Hq, Hkv, d
+    a.cache_capacity = C
+    a.window = int(window) if window is not None else 0
+    a.scaling = float(scaling)
+    a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+    a.mma_dtype = IVL_BF16
+    a.append_new = int(bool(append))
+    if rope is not None:
+        cos, sin, sec = _rope_args(rope, B, T, d)
+        a.rope_cos, a.rope_sin, a.rope_s0, a.rope_s1 = cos.data_ptr(), sin.data_ptr(), int(sec[0]), int(sec[1])
+    global ROWS_STEP_CALLS
+    ROWS_STEP_CALLS += 1
+    _lib.check(lib.ivl_swa_rows_fwd(ctypes.byref(a), pos_rows.data_ptr(), _stream(q)))
+    return o
+
+
 def _rope_args(rope, B: int, T: int, d: int):
     cos, sin, sec = rope
     if cos.dtype != torch.bfloat16 or not cos.is_contiguous():

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Experiment: per-kernel durations INSIDE the real streaming step, measured live with torch.profiler (roctracer /
 rocprofiler-sdk activity records of hipGraph replays) instead of an external rocprofv3 run.
-usage: step_profile.py [steps=4] [layers=36]"""
+usage: step_profile.py [steps=4] [layers=36] [slots=0]
+slots = 0: the B = 1 GraphedStep of the benchmark; slots = S >= 1: one GraphedMultiStreamStep tick over S slots (a 256-token frame for
+every slot: tools/multistream_frames.py's B)"""
 import collections
 import json
 import os
@@ -17,9 +19,11 @@ from torch.profiler import ProfilerActivity, profile  # noqa: E402
 def main():
     steps = int(sys.argv[1]) if len(sys.argv) > 1 else 4
     layers = int(sys.argv[2]) if len(sys.argv) > 2 else 36
+    slots = int(sys.argv[3]) if len(sys.argv) > 3 else 0
     import infinitevl_amd
     infinitevl_amd.load_library()
-    from infinitevl_amd.harness import GraphedStep, InfiniteVLTextConfig, InfiniteVLTextStack
+    from infinitevl_amd.cache import MultiStreamCache
+    from infinitevl_amd.harness import GraphedMultiStreamStep, GraphedStep, InfiniteVLTextConfig, InfiniteVLTextStack
     dev = torch.device("cuda", 0)
     cfg = InfiniteVLTextConfig(sliding_window=4096, num_hidden_layers=layers)
     with torch.device(dev):
@@ -29,10 +33,12 @@ def main():
     model = model.to(torch.bfloat16).eval()
     model.init_weights_(seed=0)
     model.fuse_()
-    cache = model.allocate_inference_cache(1)
     T = 256
-    x = (torch.randn(1, T, cfg.hidden_size, device=dev) * 0.02).to(torch.bfloat16)
-    step = GraphedStep(model, cache, 1, T, logits_to_keep=1)
+    x = (torch.randn(max(slots, 1), T, cfg.hidden_size, device=dev) * 0.02).to(torch.bfloat16)
+    if slots:
+        step = GraphedMultiStreamStep(model, MultiStreamCache(config=cfg, n_slots=slots, device=dev, dtype=torch.bfloat16), T)
+    else:
+        step = GraphedStep(model, model.allocate_inference_cache(1), 1, T, logits_to_keep=1)
     step.capture()
     for _ in range(20):
         step.step(x)
@@ -47,7 +53,7 @@ def main():
             agg[ev.name.split("(")[0]].append(ev.device_time if hasattr(ev, "device_time") else ev.cuda_time)
     rows = sorted(((n, len(v), sum(v) / len(v), sum(v)) for n, v in agg.items()), key=lambda r: -r[3])
     out = [{"kernel": n[:120], "launches": c, "avg_us": a, "total_us": t} for n, c, a, t in rows[:40]]
-    print(json.dumps({"steps": steps, "kernels": out}, indent=1))
+    print(json.dumps({"steps": steps, "slots": slots, "kernels": out}, indent=1))
 
 
 if __name__ == "__main__":
