@@ -1,5 +1,5 @@
-// The 64-key tile of the lane-owns-a-row attention formulation, once: swa_fwd_kernel / swa_rows_decode_kernel (swa.hip through
-// swa_fwd_body.inc) and vision_attn_kernel (vision_attn.hip) are the same tile loop around different masks; swa_decode_fp8_kernel
+// The 64-key tile of the lane-owns-a-row attention formulation, once: swa_fwd_kernel (swa.hip, every position mode) and
+// vision_attn_kernel (vision_attn.hip) are the same tile loop around different masks; swa_decode_fp8_kernel
 // shares the group butterflies and the epilogue.
 //   S^T = K Q^T      A = K tile rows (keys)       B = Q^T            -> lane (g, l15) owns query row l15 of its 16-row group
 //   O^T = V^T P^T    A = V^T (LDS transpose read) B = P^T (in regs)  -> the same lane owns that row's O

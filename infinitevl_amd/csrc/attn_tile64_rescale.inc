@@ -1,5 +1,5 @@
 // Online softmax of the 64-key attention tile, part 2 (part 1: tile64_probs, attn_tile64.h): the row's running state takes the
-// tile's probabilities `t`.  Included inside the per-query-group loop of the tile loops of swa_fwd_body.inc and vision_attn_kernel.
+// tile's probabilities `t`.  Included inside the per-query-group loop of the tile loops of swa_fwd_kernel and vision_attn_kernel.
 // A text fragment and not a function: as a __forceinline__ template that holds oacc[qg] by reference the branch is inlined late
 // and vision_attn_kernel<128, 2> goes from 253 to 256 VGPRs with scratch (so did the whole phase as one function).
 // Expects in scope: qg, t (Tile64Probs), m_run[QG], l_run[QG], oacc[QG][NDT], pf[QG][2].

@@ -36,40 +36,276 @@ struct SwaParams {
   const bf16_t* rcos; const bf16_t* rsin; int rs0, rs1;
 };
 
-// QG = 16-row query groups per wave; only QG = 1 is instantiated (decode / T <= 64 calls), longer calls run swa_prefill_kernel.
-template <bool PACK, int QG>
-__global__ __launch_bounds__(256, 2) void swa_fwd_kernel(const long long* pos_dev, SwaParams p) {   // (pos_dev: see swa_prefill_kernel)
-#define SWA_ROWS 0
-#include "swa_fwd_body.inc"
-#undef SWA_ROWS
-}
+// Where a workgroup reads its ring position is a MODE of each kernel family: a trailing pack of tag types on ONE template.
+//   (empty)     pos_dev is a scalar position, or NULL for p.pos
+//   PerRow      pos_dev is an int64[B], one ring position per batch row (ivl_swa_decode_rows_fwd, ivl_swa_rows_fwd)
+//   PerRowHold  PerRow with a hold mask, frozen int32[B] (ivl_swa_decode_rows_hold_fwd): the attention workgroups, the merge rows and
+//               the ring slots of a batch row with frozen[b] != 0 do nothing
+// A pack of types and not a trailing non-type parameter: with the empty pack the scalar-position kernels keep the demangled names
+// that bench.py and the committed profiles look up (ivl::swa_fwd_kernel<true, 1>, ivl::swa_combine_kernel<8, true>).
+// Every instantiation takes a trailing `frozen` (nullptr unless PerRowHold), so a family has one pointer type and one launch
+// statement; it follows the struct, behind the preloaded dwords.
+// A template and not a shared body function, as measured: a templated kernel with the body written in it compiles to the
+// instruction stream the hand-written kernel had, line for line; a __forceinline__ body function is inlined later in the
+// optimisation pipeline and changes it (swa_prefill_kernel: 8,165 -> 8,253 lines of assembly).  Table: DESIGN.md 4.26.
+struct PerRow {};
+struct PerRowHold {};
+template <typename... MODE>
+constexpr int swa_rows_mode = (std::is_same<PerRowHold, MODE>::value || ...) ? 2 : (std::is_same<PerRow, MODE>::value || ...) ? 1 : 0;
 
-// packed decode step with one ring position per batch row (pos_rows: int64[B], ivl_swa_decode_rows_fwd)
-__global__ __launch_bounds__(256, 2) void swa_rows_decode_kernel(const long long* pos_dev, SwaParams p) {
-  constexpr bool PACK = true;
-  constexpr int QG = 1;
-#define SWA_ROWS 1
-#include "swa_fwd_body.inc"
-#undef SWA_ROWS
-}
+// The 64-row kernel.  QG = 16-row query groups per wave; only QG = 1 is instantiated (decode / T <= 64 calls), longer calls run
+// swa_prefill_kernel.  PACK: the rows of a workgroup are the (token, head-in-group) pairs of one kv head (decode steps).  The
+// workgroups of a frozen batch row leave before their first load, ahead of every barrier.  The tile phases are attn_tile64.h's.
+template <bool PACK, int QG, typename... MODE>
+__global__ __launch_bounds__(256, 2) void swa_fwd_kernel(const long long* pos_dev, SwaParams p, const int32_t* frozen) {   // (pos_dev: see swa_prefill_kernel)
+  constexpr int ROWS = swa_rows_mode<MODE...>;
+  __shared__ __attribute__((aligned(16))) unsigned char smem[SWA_LDS_BYTES];
+  constexpr int QT = SWA_QT * QG;      // query rows per workgroup
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int l15 = lane & 15, g = lane >> 4;
+  const int G = p.Hq / p.Hkv;
+  // 1-D grid with an XCD-aware (bijective) remap: hardware block id i runs on XCD i % 8; logical ids are
+  // ordered (b, split, kv-head, head-in-group, q-tile) so the workgroups that read the SAME K/V range are
+  // consecutive and therefore land on the same XCD / L2 (they re-read each K/V tile up to 8 x n_qtiles times).
+  const int heads_y = PACK ? p.Hkv : p.Hq;
+  int bx, rest;                      // q-tile, and (b * nsplit + split) * heads_y + head
+  {
+    const int nwg = gridDim.x, xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
+    const int qn = nwg >> 3, rn = nwg & 7;
+    if (rn == 0 && qn % p.n_qtiles == 0) {
+      // every XCD owns whole (batch, split, head) rows.  Inside an XCD the workgroups are issued heaviest first
+      // (the work of a q-tile grows with its index: causal / window not yet full), so the long workgroups no
+      // longer form the tail.  When all of them are co-resident (<= 2 per CU) the upper half goes first in
+      // descending order and the lower half follows in ascending order: a heavy one shares its CU with a light one.
+      const int hx = qn / p.n_qtiles;                       // rows per XCD
+      const int r = slot / hx, half = (p.n_qtiles + 1) >> 1;
+      bx = qn > 64 ? p.n_qtiles - 1 - r : (r < half ? p.n_qtiles - 1 - r : r - half);
+      rest = xcd * hx + slot % hx;
+    } else {
+      const int lid = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + slot;
+      bx = lid % p.n_qtiles;
+      rest = lid / p.n_qtiles;
+    }
+  }
+  const int by = rest % heads_y;                         // q head (or kv head when PACK); heads of one group adjacent
+  const int bz = rest / heads_y;                         // b * nsplit + split
+  const int b = bz / p.nsplit, split = bz % p.nsplit;
+  const int hk = PACK ? by : by / G;
+  if constexpr (ROWS == 2) {
+    if (frozen[b] != 0) return;        // workgroup-uniform (HOLD-1): no q / ring read, no partial written
+  }
+  IVL_T(tr_start);
+#ifdef IVL_TRACE
+  const long long rt_start = (long long)__builtin_amdgcn_s_memrealtime();
+#endif
+  IVL_TVAR(tr_b1); IVL_TVAR(tr_st); IVL_TVAR(tr_qk); IVL_TVAR(tr_sm); IVL_TVAR(tr_pv);
 
-// a call of up to 64 tokens that does not pack, one ring position per batch row (ivl_swa_rows_fwd): the rows twin of swa_fwd_kernel<false, 1>
-__global__ __launch_bounds__(256, 2) void swa_rows_fwd_kernel(const long long* pos_dev, SwaParams p) {
-  constexpr bool PACK = false;
-  constexpr int QG = 1;
-#define SWA_ROWS 1
-#include "swa_fwd_body.inc"
-#undef SWA_ROWS
-}
+  const long long pos = ROWS ? pos_dev[b] : (pos_dev ? *pos_dev : p.pos);
+  const int n_ring = p.C > 0 ? (int)(pos < (long long)p.C ? pos : (long long)p.C) : 0;
+  const int n_extra = p.T_new - p.T;
+  const int n_prev = n_ring + n_extra;
+  const int S = n_prev + p.T;
+  const int s0 = p.C > 0 ? mod_pos(pos - n_ring, p.C) : 0;      // ring slot of call-local key 0
 
-// the packed step with a per-row hold mask (frozen: int32[B], ivl_swa_decode_rows_hold_fwd): `frozen` follows the struct, the running rows'
-// workgroups execute the body above
-__global__ __launch_bounds__(256, 2) void swa_rows_hold_decode_kernel(const long long* pos_dev, SwaParams p, const int32_t* frozen) {
-  constexpr bool PACK = true;
-  constexpr int QG = 1;
-#define SWA_ROWS 2
-#include "swa_fwd_body.inc"
-#undef SWA_ROWS
+  // ---- rows of this workgroup / wave / lane ----------------------------------------------------
+  const int total_rows = PACK ? p.T * G : p.T;
+  const int tile_row0 = bx * QT;
+  int t_row[QG], hq[QG], hi[QG], lo[QG];
+  bool row_ok[QG];
+#pragma unroll
+  for (int qg = 0; qg < QG; ++qg) {
+    const int row = tile_row0 + (wave * QG + qg) * 16 + l15;
+    row_ok[qg] = row < total_rows;
+    t_row[qg] = PACK ? row / G : row;
+    hq[qg] = PACK ? hk * G + row % G : by;
+    hi[qg] = n_prev + t_row[qg];
+    lo[qg] = p.W > 0 ? max(0, n_prev + t_row[qg] - p.W + 1) : 0;
+  }
+
+  // band extremes over the rows of THIS wave (rows are consecutive; lo/hi are monotone in the row index)
+  int w_lo_max, w_hi_min;
+  {
+    const int wr0 = tile_row0 + wave * 16 * QG;
+    const int wr1 = min(wr0 + 16 * QG - 1, total_rows - 1);
+    const int t_first = PACK ? wr0 / G : wr0;
+    const int t_last = PACK ? max(wr1, wr0) / G : max(wr1, wr0);
+    w_hi_min = n_prev + t_first;
+    w_lo_max = p.W > 0 ? max(0, n_prev + t_last - p.W + 1) : 0;
+  }
+
+  // workgroup key-tile range
+  const int last_row = min(tile_row0 + QT, total_rows) - 1;
+  const int t_min = PACK ? tile_row0 / G : tile_row0;
+  const int t_max = PACK ? last_row / G : last_row;
+  const int lo_min = p.W > 0 ? max(0, n_prev + t_min - p.W + 1) : 0;
+  const int kt0 = lo_min / SWA_KT, kt1 = (n_prev + t_max) / SWA_KT + 1;
+  const int per = (kt1 - kt0 + p.nsplit - 1) / p.nsplit;
+  const int kt_begin = kt0 + split * per;
+  const int kt_end = min(kt1, kt_begin + per);
+
+  // ---- Q fragments (B operand of S^T = K Q^T): lane = query row, k-slots 8g..8g+7 of each 32-chunk ----
+  u32x4 qf[QG][4];
+#pragma unroll
+  for (int qg = 0; qg < QG; ++qg) {
+    const bf16_t* qp = p.q + (long long)b * p.q_sb + (long long)t_row[qg] * p.q_st + (long long)hq[qg] * p.q_sh;
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+      if (row_ok[qg]) qf[qg][ks] = *(const u32x4*)(qp + 32 * ks + 8 * g);
+      else qf[qg][ks] = u32x4{0u, 0u, 0u, 0u};
+    }
+  }
+
+  const long long rplane = (long long)p.B * p.T * SWA_D;
+  if (p.rcos != nullptr) {
+#pragma unroll
+    for (int qg = 0; qg < QG; ++qg) {
+      const long long row_off = ((long long)b * p.T + min(t_row[qg], p.T - 1)) * SWA_D;
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) rope_pair(qf[qg][ks], qf[qg][ks + 2], p.rcos, p.rsin, rplane, row_off, 32 * ks + 8 * g, p.rs0, p.rs1);
+    }
+  }
+  float m_run[QG], l_run[QG];
+  f32x4 oacc[QG][8];
+#pragma unroll
+  for (int qg = 0; qg < QG; ++qg) {
+    m_run[qg] = -INFINITY;
+    l_run[qg] = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) oacc[qg][i] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+
+  // ---- staging: thread -> rows (tid>>4) + 16 i, 16-byte chunk tid&15 ------------------------------
+  const int srow = tid >> 4, schunk = tid & 15;
+  u32x4 kreg[4], vreg[4];
+  // per-(batch, kv-head) base pointers; rows are addressed with 32-bit element offsets from them
+  const bf16_t* kb_ring = p.C > 0 ? p.k_cache + (((long long)b * p.Hkv + hk) * p.C) * SWA_D + schunk * 8 : p.k_new;
+  const bf16_t* vb_ring = p.C > 0 ? p.v_cache + (((long long)b * p.Hkv + hk) * p.C) * SWA_D + schunk * 8 : p.v_new;
+  const bf16_t* kb_new = p.k_new + (long long)b * p.kn_sb + (long long)hk * p.kn_sh + schunk * 8;
+  const bf16_t* vb_new = p.v_new + (long long)b * p.kn_sb + (long long)hk * p.kn_sh + schunk * 8;
+  const unsigned int kn_st32 = (unsigned int)p.kn_st;
+  // the call's new keys arrive un-rotated when the rope is fused: thread (row, 16-byte chunk) fetches the partner chunk
+  // (channels +-64) and the row's cos / sin and rotates its chunk in place (only the few tiles that hold new keys pay this)
+  auto rope_new_key = [&](u32x4& kv, int jn /* index among the new keys */) {
+    const int lo_ch = (schunk & 7) * 8;                    // channel block of the "lo" half of the pair
+    const u32x4 part = *(const u32x4*)(kb_new - schunk * 8 + (unsigned int)jn * kn_st32 + (schunk ^ 8) * 8);
+    u32x4 lo = schunk < 8 ? kv : part, hi = schunk < 8 ? part : kv;
+    rope_pair(lo, hi, p.rcos, p.rsin, rplane, ((long long)b * p.T + jn) * SWA_D, lo_ch, p.rs0, p.rs1);
+    kv = schunk < 8 ? lo : hi;
+  };
+  auto load_tile = [&](int kt) {
+    const int j0 = kt * SWA_KT;
+    const int slot0 = s0 + j0;
+    if (j0 + SWA_KT <= n_ring && (slot0 + SWA_KT <= p.C || slot0 >= p.C)) {
+      // wave-uniform fast path (almost every tile of a full window): 64 consecutive ring slots, no wrap inside
+      const unsigned int off = (unsigned int)((slot0 >= p.C ? slot0 - p.C : slot0) + srow) * SWA_D;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        kreg[i] = *(const u32x4*)(kb_ring + off + 16 * i * SWA_D);
+        vreg[i] = *(const u32x4*)(vb_ring + off + 16 * i * SWA_D);
+      }
+      return;
+    }
+    if (j0 >= n_ring && j0 + SWA_KT <= S) {
+      // wave-uniform fast path: 64 keys of this call
+      const unsigned int off = (unsigned int)(j0 - n_ring + srow) * kn_st32;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        kreg[i] = *(const u32x4*)(kb_new + off + 16 * i * kn_st32);
+        vreg[i] = *(const u32x4*)(vb_new + off + 16 * i * kn_st32);
+      }
+      if (p.rcos != nullptr) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) rope_new_key(kreg[i], j0 - n_ring + srow + 16 * i);
+      }
+      return;
+    }
+    // generic tile (ring wrap, ring/new seam or tail).  Branch-free per row: every row issues its two 16-byte
+    // loads (clamped address); a conditional load per row would serialise one memory round trip per row.
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int j = j0 + srow + 16 * i;
+      const int jc = min(j, S - 1);
+      const bool in_ring = jc < n_ring;
+      int slot = s0 + jc;
+      slot = slot >= p.C ? slot - p.C : slot;
+      const unsigned int off = in_ring ? (unsigned int)slot * SWA_D : (unsigned int)(jc - n_ring) * kn_st32;
+      const bf16_t* kp = (in_ring ? kb_ring : kb_new) + off;
+      const bf16_t* vp = (in_ring ? vb_ring : vb_new) + off;
+      kreg[i] = *(const u32x4*)kp;
+      vreg[i] = *(const u32x4*)vp;
+      if (p.rcos != nullptr && !in_ring) rope_new_key(kreg[i], jc - n_ring);
+    }
+    if (j0 + SWA_KT > S) {          // wave-uniform: tail tile, rows >= S are zeroed
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        if (j0 + srow + 16 * i >= S) {
+          kreg[i] = u32x4{0u, 0u, 0u, 0u};
+          vreg[i] = u32x4{0u, 0u, 0u, 0u};
+        }
+    }
+  };
+  if (kt_begin < kt_end) load_tile(kt_begin);
+  const float sc = p.scaling * LOG2E;
+  IVL_T(tr_loop);
+
+  for (int kt = kt_begin; kt < kt_end; ++kt) {
+    IVL_T(tr0);
+    __syncthreads();
+    IVL_T(tr1);
+    tile64_stage<SWA_VSTRIDE>(smem, srow, schunk, kreg, vreg);
+    __syncthreads();
+    IVL_T(tr2);
+
+    f32x4 sacc[QG][4];
+    tile64_qk<4, QG>(smem, l15, g, qf, sacc);
+    // next tile's global loads are issued behind the first MFMA batch (their address arithmetic no longer
+    // delays it); they have the softmax + PV phases to land before the stage store of the next iteration
+    if (kt + 1 < kt_end) load_tile(kt + 1);
+    IVL_T(tr3);
+    // ---- band mask + online softmax (lane-local rows) -----------------------------------------
+    // Interior tiles (every key visible to every row of this wave) skip the per-element band test.
+    const int jbase = kt * SWA_KT + 4 * g;
+    const bool interior = kt * SWA_KT >= w_lo_max && kt * SWA_KT + SWA_KT - 1 <= w_hi_min;
+    u32x4 pf[QG][2];
+#pragma unroll
+    for (int qg = 0; qg < QG; ++qg) {
+      if (!interior) {
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int j = jbase + 16 * mt + r;
+            const bool vis = row_ok[qg] && j >= lo[qg] && j <= hi[qg];
+            sacc[qg][mt][r] = vis ? sacc[qg][mt][r] : -INFINITY;
+          }
+      }
+      const Tile64Probs t = tile64_probs<true>(sacc[qg][0], sacc[qg][1], sacc[qg][2], sacc[qg][3], sc, m_run[qg]);
+#include "attn_tile64_rescale.inc"      // a snippet, shared with vision_attn_kernel: as a function it does change the code of both
+    }
+    IVL_T(tr4);
+    tile64_pv<8, QG, SWA_VSTRIDE>(smem, l15, g, pf, oacc);
+    IVL_T(tr5);
+    IVL_TACC(tr_b1, tr1, tr0); IVL_TACC(tr_st, tr2, tr1); IVL_TACC(tr_qk, tr3, tr2); IVL_TACC(tr_sm, tr4, tr3); IVL_TACC(tr_pv, tr5, tr4);
+  }
+  IVL_T(tr_end);
+
+  // ---- epilogue: lane owns its rows, d = 16 mt2 + 4g + r ----------------------------------------
+#pragma unroll
+  for (int qg = 0; qg < QG; ++qg) {
+    if (!row_ok[qg]) continue;
+    if (p.nsplit == 1) {
+      tile64_store_row<8, true>(p.o + (((long long)b * p.T + t_row[qg]) * p.Hq + hq[qg]) * SWA_D + 4 * g, oacc[qg], l_run[qg]);
+    } else {
+      const long long prow = (((long long)b * p.nsplit + split) * p.T + t_row[qg]) * p.Hq + hq[qg];
+      tile64_store_partial(p.part_o + prow * SWA_D + 4 * g, p.part_ml + prow * 2, g, oacc[qg], m_run[qg], l_run[qg]);
+    }
+  }
+  IVL_T(tr_fin);
+  IVL_TOUT(32, tr_loop - tr_start); IVL_TOUT(33, tr_b1); IVL_TOUT(34, tr_st); IVL_TOUT(35, tr_qk); IVL_TOUT(36, tr_sm);
+#ifdef IVL_TRACE
+  IVL_TOUT(41, (long long)__builtin_amdgcn_s_memrealtime() - rt_start);
+#endif
+  IVL_TOUT(37, tr_pv); IVL_TOUT(38, tr_fin - tr_end); IVL_TOUT(39, tr_fin - tr_start); IVL_TOUT(40, kt_end - kt_begin);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -120,17 +356,439 @@ static_assert(PF_ML_OFF + 128 * 8 <= P8_LDS_BYTES, "merge image must fit the K/V
 // `pos_dev` (= p.pos_dev) is a parameter of its own IN FRONT of the struct: leading scalar / pointer parameters are preloaded into
 // SGPRs at wave launch (Makefile: -amdgpu-kernarg-preload-count; a by-value struct is not), and the position load is the head of
 // the kernel's start-up chain (kernarg -> position -> tile addresses -> first DMA): it no longer waits for the kernarg s_load.
-__global__ __launch_bounds__(P8_THREADS, 1) void swa_prefill_kernel(const long long* pos_dev, SwaParams p) {
-#define SWA_ROWS 0
-#include "swa_prefill_body.inc"
-#undef SWA_ROWS
-}
+// MODE = PerRow (ivl_swa_rows_fwd with T > 64): b is workgroup-uniform, so everything derived from the row's position stays in
+// SGPRs as well.  (`frozen` is the family's trailing parameter; no hold form of this kernel is instantiated.)
+template <typename... MODE>
+__global__ __launch_bounds__(P8_THREADS, 1) void swa_prefill_kernel(const long long* pos_dev, SwaParams p, const int32_t* frozen) {
+  constexpr int ROWS = swa_rows_mode<MODE...>;
+  __shared__ __attribute__((aligned(16))) unsigned char smem[P8_LDS_BYTES];
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int l31 = lane & 31, hi5 = lane >> 5, l15 = lane & 15;
+  const bool loader = wave >= 8;
+  const int rg = wave & 3, kh = (wave >> 2) & 1;
+  int bx, rest;
+  {
+    const int nwg = gridDim.x, xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
+    const int qn = nwg >> 3, rn = nwg & 7;
+    if (rn == 0 && qn % p.n_qtiles == 0) {
+      const int hx = qn / p.n_qtiles;
+      const int r = slot / hx, half = (p.n_qtiles + 1) >> 1;
+      bx = qn > 32 ? p.n_qtiles - 1 - r : (r < half ? p.n_qtiles - 1 - r : r - half);
+      rest = xcd * hx + slot % hx;
+    } else {
+      const int lid = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + slot;
+      bx = lid % p.n_qtiles;
+      rest = lid / p.n_qtiles;
+    }
+  }
+  const int G = p.Hq / p.Hkv;
+  const int hq = rest % p.Hq, bz = rest / p.Hq;
+  const int b = bz / p.nsplit, split = bz % p.nsplit;
+  const int hk = hq / G;
+  IVL_T(tr_start);
 
-// the same with one ring position per batch row (pos_dev: int64[B], ivl_swa_rows_fwd with T > 64)
-__global__ __launch_bounds__(P8_THREADS, 1) void swa_rows_prefill_kernel(const long long* pos_dev, SwaParams p) {
-#define SWA_ROWS 1
-#include "swa_prefill_body.inc"
-#undef SWA_ROWS
+  // the position comes through a vector load (the pointer is not provably read-only): everything derived from it -- ring geometry,
+  // tile kinds, DMA addresses, the dead-tile tests -- must live in SGPRs, or every test on it becomes a lane-mask operation and
+  // every address a 64-bit VALU chain (measured: 480-1,060 cycles per tile for the four DMA pieces of a wave)
+  const long long pos_v = ROWS ? pos_dev[b] : (pos_dev ? *pos_dev : p.pos);
+  const long long pos = (long long)(((unsigned long long)(unsigned int)__builtin_amdgcn_readfirstlane((unsigned int)((unsigned long long)pos_v >> 32)) << 32) |
+                                    (unsigned long long)(unsigned int)__builtin_amdgcn_readfirstlane((unsigned int)pos_v));
+  const int n_ring = p.C > 0 ? (int)(pos < (long long)p.C ? pos : (long long)p.C) : 0;
+  const int n_prev = n_ring + (p.T_new - p.T);
+  const int S = n_prev + p.T;
+  const int s0 = __builtin_amdgcn_readfirstlane(p.C > 0 ? mod_pos(pos - n_ring, p.C) : 0);
+
+  const int tile_row0 = bx * PF_QT;
+  const int last_row = min(tile_row0 + PF_QT, p.T) - 1;
+  const int lo_min = p.W > 0 ? max(0, n_prev + tile_row0 - p.W + 1) : 0;
+  const int kt0 = lo_min / SWA_KT, kt1 = (n_prev + last_row) / SWA_KT + 1;
+  const int per = __builtin_amdgcn_readfirstlane((kt1 - kt0 + p.nsplit - 1) / p.nsplit);
+  const int kt_begin = kt0 + split * per;
+  const int kt_end = min(kt1, kt_begin + per);
+  const int n = max(kt_end - kt_begin, 0);            // workgroup-uniform
+
+  // ---- staging (loader waves 8-11): loader L takes the 4-row chunks c = L + 4 j (j < 4) of both images: 8 DMA pieces per tile ----
+  const int r_in = lane >> 4, pp = lane & 15;
+  const unsigned int k_piece = (unsigned int)((pp ^ (4 * (wave & 3) + r_in)) << 4);                 // source byte offset inside the row
+  const unsigned int v_piece = (unsigned int)(((((pp >> 2) ^ r_in) << 2) | (pp & 3)) << 4);
+  const int chunk0 = wave & 3;                                                                      // + 4 j
+  const unsigned int lds_base = (unsigned int)(size_t)smem;
+  const long long ring_off = p.C > 0 ? (((long long)b * p.Hkv + hk) * p.C) * SWA_D : 0;
+  const bf16_t* const k_ring = p.C > 0 ? p.k_cache + ring_off : p.k_new;
+  const bf16_t* const v_ring = p.C > 0 ? p.v_cache + ring_off : p.v_new;
+  const bf16_t* const k_newb = p.k_new + (long long)b * p.kn_sb + (long long)hk * p.kn_sh;
+  const bf16_t* const v_newb = p.v_new + (long long)b * p.vn_sb + (long long)hk * p.vn_sh;
+  const unsigned int kn_st32 = (unsigned int)p.kn_st, vn_st32 = (unsigned int)p.vn_st;
+  const bool rope_keys = p.rcos != nullptr;             // the call's keys arrive un-rotated (short single-split calls only)
+  auto dma_piece = [&](const unsigned char* base_u, unsigned int voff, unsigned int dst) __attribute__((always_inline)) {
+    const unsigned long long bu = (unsigned long long)base_u;
+    const unsigned char* const base = (const unsigned char*)(((unsigned long long)(unsigned int)__builtin_amdgcn_readfirstlane((unsigned int)(bu >> 32)) << 32) |
+                                                             (unsigned long long)(unsigned int)__builtin_amdgcn_readfirstlane((unsigned int)bu));
+    unsigned int keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep) : "v"(voff), "s"(dst), "s"(base) : "memory");
+  };
+  // tile kinds, monotone in kt: [0, kt_ring_end) lie wholly in the ring (all but the one that holds the wrap point are 64 consecutive
+  // slots), [kt_new_begin, kt_new_end) wholly in the call's keys; the rest (wrap, ring / new seam, tail) take the register path
+  const int kt_ring_end = n_ring / SWA_KT, kt_new_begin = (n_ring + SWA_KT - 1) / SWA_KT, kt_new_end = S / SWA_KT;
+  const int kt_wrap = (p.C > 0 && s0 + n_ring > p.C) ? (p.C - s0) / SWA_KT : -1;       // the tile with slots on both sides of the wrap
+  const bool wrap_aligned = p.C > 0 && (p.C - s0) % SWA_KT == 0;                         // ... unless the wrap falls on a tile boundary
+  // tile kt of the call into stage `st`; returns the number of DMA instructions this wave issued (0, 4 or 8)
+  auto stage_tile = [&](int kt, int st) __attribute__((always_inline)) -> int {
+    const int j0 = kt * SWA_KT, slot0 = s0 + j0;
+    const bool ring_fast = kt < kt_ring_end && (kt != kt_wrap || wrap_aligned);
+    const bool new_fast = kt >= kt_new_begin && kt < kt_new_end;
+    int issued = 0;
+#pragma unroll
+    for (int isv = 0; isv < 2; ++isv) {
+      const unsigned int img = lds_base + (unsigned int)st * P8_STAGE + (isv ? (unsigned int)P8_IMG : 0u);
+      const unsigned int piece = isv ? v_piece : k_piece;
+      const unsigned int st32 = isv ? vn_st32 : kn_st32;
+      const bf16_t* const rb = isv ? v_ring : k_ring;
+      const bf16_t* const nb = isv ? v_newb : k_newb;
+      if (ring_fast) {
+        const unsigned char* src = (const unsigned char*)(rb + (long long)(slot0 >= p.C ? slot0 - p.C : slot0) * SWA_D);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) dma_piece(src + (chunk0 + 4 * j) * 1024, (unsigned int)(r_in * 256) + piece, img + 1024u * (chunk0 + 4 * j));
+        issued += 4;
+      } else if (new_fast && !(isv == 0 && rope_keys)) {
+        const unsigned char* src = (const unsigned char*)(nb + (long long)(j0 - n_ring) * st32);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          dma_piece(src + (long long)(chunk0 + 4 * j) * 4 * st32 * 2, (unsigned int)r_in * st32 * 2 + piece, img + 1024u * (chunk0 + 4 * j));
+        issued += 4;
+      } else {
+        // register path (ring wrap, ring / new seam, tail, un-rotated keys): clamped loads from both sources, rows past the end
+        // are zero, the call's keys are rotated; written with the lane -> (row, piece) map of a DMA piece
+        u32x4 r[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int jk = j0 + 4 * (chunk0 + 4 * j) + r_in;
+          const int jc = min(jk, S - 1);
+          int slot = s0 + min(jc, max(n_ring - 1, 0));
+          slot = slot >= p.C ? slot - p.C : slot;
+          const u32x4 a0 = *(const u32x4*)((const unsigned char*)(rb + (unsigned int)slot * SWA_D) + piece);
+          const u32x4 c0 = *(const u32x4*)((const unsigned char*)(nb + (unsigned int)max(jc - n_ring, 0) * st32) + piece);
+          u32x4 val = jc < n_ring ? a0 : c0;
+          if (isv == 0 && rope_keys && jc >= n_ring) {
+            const int jn = jc - n_ring;
+            const u32x4 part = *(const u32x4*)((const unsigned char*)(nb + (unsigned int)jn * st32) + (piece ^ 128u));
+            const bool is_lo = piece < 128u;
+            u32x4 lo = is_lo ? val : part, hi = is_lo ? part : val;
+            rope_pair(lo, hi, p.rcos, p.rsin, (long long)p.B * p.T * SWA_D, ((long long)b * p.T + jn) * SWA_D, (int)((piece & 127u) >> 1), p.rs0, p.rs1);
+            val = is_lo ? lo : hi;
+          }
+          r[j] = jk < S ? val : u32x4{0u, 0u, 0u, 0u};
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) *(u32x4*)(smem + st * P8_STAGE + (isv ? P8_IMG : 0) + 1024 * (chunk0 + 4 * j) + 16 * lane) = r[j];
+      }
+    }
+    return issued;
+  };
+
+  if (loader) {
+    // ---- loader wavefronts: per tile  [request tile t + 2 over tile t - 1] | vmcnt: tile t + 1 has landed | barrier ---------------
+    auto land = [&](int fly) __attribute__((always_inline)) {            // `fly` younger DMA instructions may stay in flight
+      __builtin_amdgcn_sched_barrier(0);
+      if (fly == 8) asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+      else if (fly == 4) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+      else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+      __builtin_amdgcn_sched_barrier(0);
+    };
+    // The rotated key half reads K(t + 1) during tile t, i.e. BEHIND the barrier that ends tile t - 1: the loaders arrive at the
+    // barrier that ends tile t with tile t + 2 landed (not t + 1), which takes a request distance of three tiles and FOUR stages
+    // (tile t + 3 goes into the stage tile t - 1 left at the previous barrier).  [A three-stage version that awaited tile t + 1
+    // only passed every single-process test and failed 4 of 12 two-process runs: the DMA of tile t + 1 was usually, not always,
+    // complete when the rotated half read it.]
+    if (n > 0) stage_tile(kt_begin, 0);
+    if (n > 1) stage_tile(kt_begin + 1, 1);
+    const int fly2 = n > 2 ? stage_tile(kt_begin + 2, 2) : 0;
+    land(fly2);                                                           // tiles 0 and 1 are in LDS: the compute waves start
+#pragma nounroll
+    for (int t = 0; t < n; ++t) {
+      const int fly = t + 3 < n ? stage_tile(kt_begin + t + 3, (t + 3) & 3) : 0;
+      land(fly);                                                          // tile t + 2 has landed
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();                                                      // the three barriers of the merge epilogue
+    __syncthreads();
+    __syncthreads();
+    return;
+  }
+
+  // ---- compute-side set-up ----------------------------------------------------------------------------------------------------
+  const int row = tile_row0 + 32 * rg + l31;
+  const bool row_ok = row < p.T;
+  const int band_hi = n_prev + row;
+  const int band_lo = p.W > 0 ? max(0, n_prev + row - p.W + 1) : 0;
+  const int wr0 = tile_row0 + 32 * rg, wr1 = max(min(wr0 + 31, p.T - 1), wr0);
+  const int w_hi_min = n_prev + wr0, w_hi_max = n_prev + wr1;
+  const int w_lo_min = p.W > 0 ? max(0, n_prev + wr0 - p.W + 1) : 0;
+  const int w_lo_max = p.W > 0 ? max(0, n_prev + wr1 - p.W + 1) : 0;
+  u32x4 qf[8];
+  {
+    const bf16_t* qp = p.q + (long long)b * p.q_sb + (long long)min(row, p.T - 1) * p.q_st + (long long)hq * p.q_sh;
+#pragma unroll
+    for (int kd = 0; kd < 8; ++kd) qf[kd] = *(const u32x4*)(qp + 16 * kd + 8 * hi5);
+  }
+  if (p.rcos != nullptr) {
+    const long long row_off = ((long long)b * p.T + min(row, p.T - 1)) * SWA_D;
+    const long long plane = (long long)p.B * p.T * SWA_D;
+    u32x4 c1[4], n1[4], c2[4], n2[4];
+#pragma unroll
+    for (int kd = 0; kd < 4; ++kd) {
+      const int c0 = 16 * kd + 8 * hi5;
+      const int sec = c0 < p.rs0 ? 0 : (c0 < p.rs0 + p.rs1 ? 1 : 2);
+      const long long off = sec * plane + row_off + c0;
+      c1[kd] = *(const u32x4*)(p.rcos + off); n1[kd] = *(const u32x4*)(p.rsin + off);
+      c2[kd] = *(const u32x4*)(p.rcos + off + 64); n2[kd] = *(const u32x4*)(p.rsin + off + 64);
+    }
+#pragma unroll
+    for (int kd = 0; kd < 4; ++kd) rope_apply(qf[kd], qf[kd + 4], c1[kd], n1[kd], c2[kd], n2[kd]);
+  }
+  if (!row_ok) {
+#pragma unroll
+    for (int kd = 0; kd < 8; ++kd) qf[kd] = u32x4{0u, 0u, 0u, 0u};
+  }
+
+  float m_run = -INFINITY, l_run = 0.f;
+  f32x16 oacc[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) oacc[i][r] = 0.f;
+  const float sc = p.scaling * LOG2E;
+  const unsigned int k_base = (unsigned int)((32 * kh + l31) * 256 + ((l15 >> 1) << 5) + ((hi5 ^ (l15 & 1)) << 4));
+  const unsigned int v_base = (unsigned int)(P8_IMG + (32 * kh + 4 * hi5 + (l15 >> 2)) * 256 + ((l15 >> 2) << 6) + 32 * ((lane >> 4) & 1) + 8 * (l15 & 3));
+  unsigned int ak[8], av[4];
+#pragma unroll
+  for (int kd = 0; kd < 8; ++kd) ak[kd] = k_base ^ (unsigned int)(kd << 5);
+#pragma unroll
+  for (int mt = 0; mt < 4; ++mt) av[mt] = v_base ^ (unsigned int)(mt << 6);
+
+  auto is_dead = [&](int kt) __attribute__((always_inline)) {                // no row of the wave sees any of its 32 keys of tile kt
+    const int kbeg = kt * SWA_KT + 32 * kh;
+    return kbeg > w_hi_max || kbeg + 31 < w_lo_min;
+  };
+  auto qk = [&](int st, f32x16& s) __attribute__((always_inline)) {
+    const unsigned int so = (unsigned int)st * P8_STAGE;
+    u32x4 fr[8];
+#pragma unroll
+    for (int kd = 0; kd < 8; ++kd) fr[kd] = *(const u32x4*)(smem + (ak[kd] + so));
+#pragma unroll
+    for (int r = 0; r < 16; ++r) s[r] = 0.f;
+#pragma unroll
+    for (int kd = 0; kd < 8; ++kd) s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_mfma(fr[kd]), as_mfma(qf[kd]), s, 0, 0, 0);
+  };
+  // band mask, running exponent reference, rescale.  LAZY reference: m_run is the exponent reference of the row, not its exact
+  // running maximum.  It follows the maximum only when some row of the wave has outgrown it by more than 2^8 (always on a row's
+  // first visible tile: -inf + 8 = -inf); until then the probabilities are 2^(s - m_run) <= 2^8 -- exact in fp32 and of the same
+  // relative precision in bf16 -- and the accumulators need no rescale: 33 v_pk_mul_f32 per wave and tile behind a wave-uniform
+  // branch that is taken a handful of times per call.  (m, l, O) stay consistent: the merge of the key halves and the split-KV
+  // combine use m_run as the partial's reference.  The first reader of the MFMA results is an instruction the compiler sees
+  // (hazard wait states: see swa_fwd_kernel).
+  auto row_max = [&](int kt, f32x16& s) __attribute__((always_inline)) {
+    const int kbeg = kt * SWA_KT + 32 * kh;
+    const bool interior = kbeg >= w_lo_max && kbeg + 31 <= w_hi_min;
+    if (!interior) {
+      const int jb = kbeg + 4 * hi5;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int j = jb + (r & 3) + 8 * (r >> 2);
+        const bool vis = row_ok && j >= band_lo && j <= band_hi;
+        s[r] = vis ? s[r] : -INFINITY;
+      }
+    }
+    float rmax = vmax2(__builtin_fmaxf(s[0], s[1]), s[2]);       // first reader of the MFMA results: compiler-visible (hazard wait states)
+    rmax = vmax3(rmax, s[3], s[4]);
+    rmax = vmax3(rmax, s[5], s[6]);
+    rmax = vmax3(rmax, s[7], s[8]);
+    rmax = vmax3(rmax, s[9], s[10]);
+    rmax = vmax3(rmax, s[11], s[12]);
+    rmax = vmax3(rmax, s[13], s[14]);
+    rmax = vmax2(rmax, s[15]);
+    auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(rmax), __float_as_uint(rmax), false, false);
+    rmax = vmax2(__uint_as_float(sw[0]), __uint_as_float(sw[1])) * sc;
+    const float m_new = vmax2(m_run, rmax);
+    if (__any(m_new > m_run + 8.0f)) {
+      const float m_u = m_new == -INFINITY ? 0.f : m_new;
+      const float alpha = __builtin_amdgcn_exp2f(m_run - m_u);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) oacc[i] *= alpha;
+      l_run *= alpha;
+      m_run = m_new;
+    }
+  };
+  auto exps = [&](f32x16& s, u32x4 (&pf)[2]) __attribute__((always_inline)) {
+    const float m_use = m_run == -INFINITY ? 0.f : m_run;
+    float rsum = 0.f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const float pv = __builtin_amdgcn_exp2f(__builtin_fmaf(s[r], sc, -m_use));
+      s[r] = pv;
+      rsum += pv;
+    }
+    l_run += rsum;
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks)
+      pf[ks] = u32x4{pack2bf(s[8 * ks + 0], s[8 * ks + 1]), pack2bf(s[8 * ks + 2], s[8 * ks + 3]),
+                     pack2bf(s[8 * ks + 4], s[8 * ks + 5]), pack2bf(s[8 * ks + 6], s[8 * ks + 7])};
+  };
+  auto pv = [&](int st, const u32x4 (&pf)[2]) __attribute__((always_inline)) {
+    const unsigned int so = (unsigned int)st * P8_STAGE;
+    u32x4 fv[2][4];
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+      for (int mt = 0; mt < 4; ++mt) {
+        const unsigned char* vp = smem + (av[mt] + so) + 16 * ks * 256;
+        const s16x4 a0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)vp);
+        const s16x4 a1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(vp + 8 * 256));
+        u32x2 w0, w1;
+        __builtin_memcpy(&w0, &a0, 8);
+        __builtin_memcpy(&w1, &a1, 8);
+        fv[ks][mt] = u32x4{w0.x, w0.y, w1.x, w1.y};
+      }
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+      for (int mt = 0; mt < 4; ++mt) oacc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_mfma(fv[ks][mt]), as_mfma(pf[ks]), oacc[mt], 0, 0, 0);
+  };
+  // the barrier that ends a tile: nobody reads the current tile any more; the loaders arrive with the next tile in LDS
+  auto tile_barrier = [&]() __attribute__((always_inline)) {
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  tile_barrier();                              // tiles 0 and 1 are in LDS
+
+  IVL_T(tr_loop);
+  IVL_TVAR(tr_c1); IVL_TVAR(tr_st); IVL_TVAR(tr_c2); IVL_TVAR(tr_w);
+  f32x16 sA;
+  u32x4 pA[2];
+  int st = 0;                                  // stage of tile t = t % 3
+  if (kh == 0) {
+    // key half 0:  QK^T(t) | row max | exponentials | PV(t) | barrier
+#pragma nounroll
+    for (int t = 0; t < n; ++t) {
+      const int kt = kt_begin + t;
+      const bool dead = is_dead(kt);
+      IVL_T(t0);
+      if (!dead) {
+        qk(st, sA);
+        row_max(kt, sA);
+      }
+      IVL_T(t1);
+      IVL_T(t2);
+      if (!dead) {
+        exps(sA, pA);
+        pv(st, pA);
+      }
+      IVL_T(t3);
+      tile_barrier();
+      IVL_T(t4);
+      IVL_TACC(tr_c1, t1, t0); IVL_TACC(tr_st, t2, t1); IVL_TACC(tr_c2, t3, t2); IVL_TACC(tr_w, t4, t3);
+      st = (st + 1) & 3;
+    }
+  } else {
+    // key half 1, rotated:  row max(t) | exponentials | PV(t) | QK^T(t + 1) | barrier
+    // (tile t + 1 is complete since the barrier that ended tile t - 1: the loaders run three tiles ahead)
+    __builtin_amdgcn_s_setprio(1);               // the second-dispatched half loses the VALU arbitration against its SIMD partner
+    if (n > 0 && !is_dead(kt_begin)) qk(0, sA);
+#pragma nounroll
+    for (int t = 0; t < n; ++t) {
+      const int kt = kt_begin + t;
+      const bool dead = is_dead(kt);
+      IVL_T(t0);
+      if (!dead) row_max(kt, sA);
+      IVL_T(t1);
+      const int st1 = (st + 1) & 3;
+      IVL_T(t2);
+      if (!dead) {
+        exps(sA, pA);
+        pv(st, pA);
+      }
+      if (t + 1 < n && !is_dead(kt + 1)) qk(st1, sA);       // (the scores of tile t are packed in pA by now)
+      IVL_T(t3);
+      tile_barrier();
+      IVL_T(t4);
+      IVL_TACC(tr_c1, t1, t0); IVL_TACC(tr_st, t2, t1); IVL_TACC(tr_c2, t3, t2); IVL_TACC(tr_w, t4, t3);
+      st = st1;
+    }
+  }
+  IVL_T(tr_end);
+
+  // ---- merge the two key halves of every row group through LDS (the K/V stages are free behind the next barrier), then whole-row
+  //      stores by the 512 compute threads: 256 B of bf16 per row, into o or into the split's partial rows ----------------------------
+  {
+    auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(l_run), __float_as_uint(l_run), false, false);
+    l_run = __uint_as_float(sw[0]) + __uint_as_float(sw[1]);
+  }
+  __syncthreads();
+  unsigned char* oimg = smem + rg * 32 * PF_OSTRIDE + l31 * PF_OSTRIDE + 16 * hi5;      // + 128 mt + 32 q : d = 32 mt + 8 q + 4 hi
+  float* ml = (float*)(smem + PF_ML_OFF) + (rg * 32 + l31) * 2;
+  if (kh == 1) {
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+        *(f32x4*)(oimg + 128 * mt + 32 * q) = f32x4{oacc[mt][4 * q], oacc[mt][4 * q + 1], oacc[mt][4 * q + 2], oacc[mt][4 * q + 3]};
+    if (hi5 == 0) {
+      ml[0] = m_run;
+      ml[1] = l_run;
+    }
+  }
+  __syncthreads();
+  if (kh == 0) {
+    const float m1 = ml[0], l1 = ml[1];
+    const float m = vmax2(m_run, m1);
+    const float mu = m == -INFINITY ? 0.f : m;
+    const float a0 = __builtin_amdgcn_exp2f(m_run - mu), a1 = __builtin_amdgcn_exp2f(m1 - mu);
+    const float l = l_run * a0 + l1 * a1;
+    const float inv = l > 0.f ? 1.0f / l : 0.f;      // normalised rows also for the split-KV partials (stored in bf16)
+    const float w0 = a0 * inv, w1 = a1 * inv;
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const f32x4 o1 = *(const f32x4*)(oimg + 128 * mt + 32 * q);
+        f32x4 o;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = oacc[mt][4 * q + e] * w0 + o1[e] * w1;
+        *(f32x4*)(oimg + 128 * mt + 32 * q) = o;
+      }
+    if (hi5 == 0) {
+      ml[0] = m;
+      ml[1] = l;
+    }
+  }
+  __syncthreads();
+  {
+    bf16_t* const dst = p.nsplit == 1 ? p.o : (bf16_t*)p.part_o;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int idx = tid + 512 * i, r = idx >> 4, c = idx & 15;       // row, 8-channel piece
+      const int t = tile_row0 + r;
+      if (t < p.T) {
+        const unsigned char* src = smem + r * PF_OSTRIDE + c * 32;
+        const f32x4 x = *(const f32x4*)src, y = *(const f32x4*)(src + 16);
+        const long long orow = p.nsplit == 1 ? ((long long)b * p.T + t) * p.Hq + hq
+                                             : (((long long)b * p.nsplit + split) * p.T + t) * p.Hq + hq;
+        store_out16(dst + orow * SWA_D + 8 * c,
+                    u32x4{pack2bf(x[0], x[1]), pack2bf(x[2], x[3]), pack2bf(y[0], y[1]), pack2bf(y[2], y[3])});
+      }
+    }
+    if (p.nsplit > 1 && tid < PF_QT && tile_row0 + tid < p.T) {
+      const long long prow = (((long long)b * p.nsplit + split) * p.T + tile_row0 + tid) * p.Hq + hq;
+      *(float2*)(p.part_ml + prow * 2) = *(const float2*)(smem + PF_ML_OFF + tid * 8);
+    }
+  }
+  IVL_T(tr_fin);
+  IVL_TOUT(32, tr_loop - tr_start); IVL_TOUT(38, tr_fin - tr_end); IVL_TOUT(39, tr_fin - tr_start); IVL_TOUT(40, kt_end - kt_begin);
+  IVL_TOUT(47, tr_end - tr_loop); IVL_TOUT(42, 2);
+  IVL_TOUT(33, tr_c1); IVL_TOUT(34, tr_st); IVL_TOUT(35, tr_c2); IVL_TOUT(36, tr_w);
+  IVL_TOUT_AT(256, 50, tr_c1); IVL_TOUT_AT(256, 51, tr_st); IVL_TOUT_AT(256, 52, tr_c2); IVL_TOUT_AT(256, 53, tr_w);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -386,83 +1044,121 @@ __device__ __forceinline__ void ring_append(const AppendArgs& a, long long block
 // issued before the first use (template on the split count so the loop is fully unrolled)
 // BF16P (partials of swa_prefill_kernel): part_o holds NORMALISED rows O_s / l_s in bf16 (half the round trip of the
 // split-KV partials, which is 17 MB per launch in fp32 at the bench shape); the merge weights are then w_s l_s.
-template <int NS, bool BF16P>
+// MODE: PerRow appends every batch row at its own position; PerRowHold also skips the merge, the o store and the ring slots of a
+// frozen batch row (its partials were never written).
+template <int NS, bool BF16P, typename... MODE>
 __global__ __launch_bounds__(256) void swa_combine_kernel(const float* __restrict__ part_o, const float* __restrict__ part_ml,
-                                                         bf16_t* __restrict__ o, int B, int rows_per_b, int nsplit, AppendArgs ap) {
-#define SWA_WIDE 0
-#define SWA_ROWS 0
-#include "swa_combine_body.inc"
-#undef SWA_ROWS
-#undef SWA_WIDE
-}
-template <int NS>
-__global__ __launch_bounds__(256) void swa_rows_combine_kernel(const float* __restrict__ part_o, const float* __restrict__ part_ml,
-                                                              bf16_t* __restrict__ o, int B, int rows_per_b, int nsplit, AppendArgs ap) {
-  constexpr bool BF16P = false;
-#define SWA_WIDE 0
-#define SWA_ROWS 1
-#include "swa_combine_body.inc"
-#undef SWA_ROWS
-#undef SWA_WIDE
-}
-// the rows combine over the bf16 partials of swa_rows_prefill_kernel (ivl_swa_rows_fwd with T > 64)
-template <int NS>
-__global__ __launch_bounds__(256) void swa_rows_combine_bf16p_kernel(const float* __restrict__ part_o, const float* __restrict__ part_ml,
-                                                                    bf16_t* __restrict__ o, int B, int rows_per_b, int nsplit, AppendArgs ap) {
-  constexpr bool BF16P = true;
-#define SWA_WIDE 0
-#define SWA_ROWS 1
-#include "swa_combine_body.inc"
-#undef SWA_ROWS
-#undef SWA_WIDE
+                                                         bf16_t* __restrict__ o, int B, int rows_per_b, int nsplit, AppendArgs ap,
+                                                         const int32_t* __restrict__ frozen) {
+  constexpr int ROWS = swa_rows_mode<MODE...>;
+  if (ap.first_block >= 0 && (int)blockIdx.x >= ap.first_block) {
+    ring_append<ROWS>(ap, (long long)blockIdx.x - ap.first_block, (long long)gridDim.x - ap.first_block, frozen);
+    return;
+  }
+  const int ncb = ap.first_block >= 0 ? ap.first_block : (int)gridDim.x;       // combine blocks
+  const int lane = threadIdx.x & 63;
+  const long long wid = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const long long nw = ((long long)ncb * blockDim.x) >> 6;
+  for (long long r = wid; r < (long long)B * rows_per_b; r += nw) {
+    int rr_;
+    const long long b = divmod_idx(r, rows_per_b, rr_), rr = rr_;
+    if constexpr (ROWS == 2) {
+      if (frozen[b] != 0) continue;        // uniform over the row's wavefront
+    }
+    float ms[NS], ls[NS];
+    float2 ov[NS];
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+      const bool on = s < nsplit;
+      const long long pr = (b * nsplit + (on ? s : 0)) * rows_per_b + rr;
+      const float2 ml = *(const float2*)(part_ml + pr * 2);
+      ms[s] = on ? ml.x : -INFINITY;
+      ls[s] = on ? ml.y : 0.f;
+      if (BF16P) {
+        const unsigned int w2 = *(const unsigned int*)((const bf16_t*)part_o + pr * SWA_D + 2 * lane);
+        ov[s] = float2{bflo(w2), bfhi(w2)};
+      } else {
+        ov[s] = *(const float2*)(part_o + pr * SWA_D + 2 * lane);
+      }
+    }
+    float m = -INFINITY;
+#pragma unroll
+    for (int s = 0; s < NS; ++s) m = fmaxf(m, ms[s]);
+    float l = 0.f, a0 = 0.f, a1 = 0.f;
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+      float w = ms[s] == -INFINITY ? 0.f : exp2f(ms[s] - m);
+      if (BF16P) w *= ls[s];
+      l = BF16P ? l + w : fmaf(w, ls[s], l);
+      a0 = fmaf(w, ov[s].x, a0);
+      a1 = fmaf(w, ov[s].y, a1);
+    }
+    const float inv = l > 0.f ? 1.0f / l : 0.f;
+    *(unsigned int*)(o + r * SWA_D + 2 * lane) = pack2bf(a0 * inv, a1 * inv);
+  }
 }
 
 // merge up to 64 split-KV partials (packed decode): one wavefront per (b, t, head) row.  Lane s first owns split s
 // (its running max / sum -> weight 2^(m_s - m)), then the wave walks the splits with the weights broadcast by
 // v_readlane while every lane accumulates its 2 d-values; loads are issued 8 splits at a time.
+// (a kernel of its own, not a flag of swa_combine_kernel: the two merges share the append branch and nothing else.)
+template <typename... MODE>
 __global__ __launch_bounds__(256) void swa_combine_wide_kernel(const float* __restrict__ part_o, const float* __restrict__ part_ml,
-                                                              bf16_t* __restrict__ o, int B, int rows_per_b, int nsplit, AppendArgs ap) {
-#define SWA_WIDE 1
-#define SWA_ROWS 0
-#include "swa_combine_body.inc"
-#undef SWA_ROWS
-#undef SWA_WIDE
-}
-__global__ __launch_bounds__(256) void swa_rows_combine_wide_kernel(const float* __restrict__ part_o, const float* __restrict__ part_ml,
-                                                                   bf16_t* __restrict__ o, int B, int rows_per_b, int nsplit, AppendArgs ap) {
-#define SWA_WIDE 1
-#define SWA_ROWS 1
-#include "swa_combine_body.inc"
-#undef SWA_ROWS
-#undef SWA_WIDE
+                                                              bf16_t* __restrict__ o, int B, int rows_per_b, int nsplit, AppendArgs ap,
+                                                              const int32_t* __restrict__ frozen) {
+  constexpr int ROWS = swa_rows_mode<MODE...>;
+  if (ap.first_block >= 0 && (int)blockIdx.x >= ap.first_block) {
+    ring_append<ROWS>(ap, (long long)blockIdx.x - ap.first_block, (long long)gridDim.x - ap.first_block, frozen);
+    return;
+  }
+  // one WORKGROUP per row: wave w merges the splits 16w .. 16w + 15 (all 16 partial rows requested at once: one memory
+  // round trip instead of nsplit / 8), the four partial sums meet in LDS
+  __shared__ float2 red[4][64];
+  const int ncb = ap.first_block >= 0 ? ap.first_block : (int)gridDim.x;       // combine blocks
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (long long r = blockIdx.x; r < (long long)B * rows_per_b; r += ncb) {
+    int rr_;
+    const long long b = divmod_idx(r, rows_per_b, rr_), rr = rr_;
+    if constexpr (ROWS == 2) {
+      if (frozen[b] != 0) continue;        // uniform over the row's workgroup
+    }
+    const bool on = lane < nsplit;
+    const float2 ml = *(const float2*)(part_ml + ((b * nsplit + (on ? lane : 0)) * rows_per_b + rr) * 2);
+    float2 ov[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      const int s2 = min(16 * wave + j, nsplit - 1);
+      ov[j] = *(const float2*)(part_o + ((b * nsplit + s2) * rows_per_b + rr) * SWA_D + 2 * lane);
+    }
+    const float ms = on ? ml.x : -INFINITY;
+    float m = ms;
+#pragma unroll
+    for (int ofs = 32; ofs > 0; ofs >>= 1) m = fmaxf(m, __shfl_xor(m, ofs, 64));
+    const float w = ms == -INFINITY ? 0.f : exp2f(ms - m);
+    const float l = wave_sum(w * (on ? ml.y : 0.f));
+    float a0 = 0.f, a1 = 0.f;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      const int s2 = 16 * wave + j;
+      const float ws = s2 < nsplit ? __shfl(w, s2, 64) : 0.f;
+      a0 = fmaf(ws, ov[j].x, a0);
+      a1 = fmaf(ws, ov[j].y, a1);
+    }
+    red[wave][lane] = float2{a0, a1};
+    __syncthreads();
+    if (wave == 0) {
+      const float2 p1 = red[1][lane], p2 = red[2][lane], p3 = red[3][lane];
+      const float inv = l > 0.f ? 1.0f / l : 0.f;
+      *(unsigned int*)(o + r * SWA_D + 2 * lane) = pack2bf((a0 + p1.x + p2.x + p3.x) * inv, (a1 + p1.y + p2.y + p3.y) * inv);
+    }
+    __syncthreads();
+  }
 }
 
-// the hold forms of the two pos_rows combine kernels (frozen: int32[B])
-template <int NS>
-__global__ __launch_bounds__(256) void swa_rows_hold_combine_kernel(const float* __restrict__ part_o, const float* __restrict__ part_ml,
-                                                                   bf16_t* __restrict__ o, int B, int rows_per_b, int nsplit, AppendArgs ap,
-                                                                   const int32_t* __restrict__ frozen) {
-  constexpr bool BF16P = false;
-#define SWA_WIDE 0
-#define SWA_ROWS 2
-#include "swa_combine_body.inc"
-#undef SWA_ROWS
-#undef SWA_WIDE
-}
-__global__ __launch_bounds__(256) void swa_rows_hold_combine_wide_kernel(const float* __restrict__ part_o, const float* __restrict__ part_ml,
-                                                                        bf16_t* __restrict__ o, int B, int rows_per_b, int nsplit, AppendArgs ap,
-                                                                        const int32_t* __restrict__ frozen) {
-#define SWA_WIDE 1
-#define SWA_ROWS 2
-#include "swa_combine_body.inc"
-#undef SWA_ROWS
-#undef SWA_WIDE
-}
-
-// stand-alone ring append (ivl_swa_cache_append, and ivl_swa_fwd with append_new when no combine launch follows)
-__global__ __launch_bounds__(256) void swa_cache_append_kernel(AppendArgs ap) { ring_append(ap, blockIdx.x, gridDim.x); }
-// its rows form (ivl_swa_rows_fwd with append_new and one split): ap.pos_dev is an int64[B]
-__global__ __launch_bounds__(256) void swa_rows_cache_append_kernel(AppendArgs ap) { ring_append<1>(ap, blockIdx.x, gridDim.x); }
+// stand-alone ring append (ivl_swa_cache_append, and ivl_swa_fwd with append_new when no combine launch follows); MODE = PerRow
+// (ivl_swa_rows_fwd with append_new and one split): ap.pos_dev is an int64[B]
+template <typename... MODE>
+__global__ __launch_bounds__(256) void swa_cache_append_kernel(AppendArgs ap) { ring_append<swa_rows_mode<MODE...>>(ap, blockIdx.x, gridDim.x); }
 
 static int swa_base_nsplit(int B, int T, int Hq) {
   const bool prefill = T > SWA_QT;
@@ -560,22 +1256,19 @@ static int swa_append_args(AppendArgs& ap, const bf16_t* k_new, long long kn_sb,
 // What follows the attention launch: the merge of the split-KV partials (p.nsplit > 1) with the ring append (`append`) in the
 // blocks behind the combine blocks, or the stand-alone append launch when there is nothing to merge.  `rows`: the pos_rows forms;
 // `bf16p`: the partials are swa_prefill_kernel's.  The append uses the (possibly rotated-copy) keys of p.
-typedef void (*swa_combine_fn)(const float*, const float*, bf16_t*, int, int, int, AppendArgs);
-static swa_combine_fn swa_combine_for(int nsplit, bool rows, bool bf16p) {
-  if (nsplit > 16) return rows ? swa_rows_combine_wide_kernel : swa_combine_wide_kernel;
-  if (rows && bf16p)
-    return nsplit <= 4 ? swa_rows_combine_bf16p_kernel<4> : nsplit <= 8 ? swa_rows_combine_bf16p_kernel<8> : swa_rows_combine_bf16p_kernel<16>;
-  if (rows) return nsplit <= 4 ? swa_rows_combine_kernel<4> : nsplit <= 8 ? swa_rows_combine_kernel<8> : swa_rows_combine_kernel<16>;
-  if (bf16p) return nsplit <= 4 ? swa_combine_kernel<4, true> : nsplit <= 8 ? swa_combine_kernel<8, true> : swa_combine_kernel<16, true>;
-  return nsplit <= 4 ? swa_combine_kernel<4, false> : nsplit <= 8 ? swa_combine_kernel<8, false> : swa_combine_kernel<16, false>;
+// `frozen` != nullptr (with rows): the hold instances on the same grid; they merge the packed step's fp32 partials only.
+typedef void (*swa_combine_fn)(const float*, const float*, bf16_t*, int, int, int, AppendArgs, const int32_t*);
+template <bool BF16P, typename... MODE>
+static swa_combine_fn swa_combine_of(int nsplit) {
+  if (nsplit > 16) return swa_combine_wide_kernel<MODE...>;
+  return nsplit <= 4 ? swa_combine_kernel<4, BF16P, MODE...> : nsplit <= 8 ? swa_combine_kernel<8, BF16P, MODE...> : swa_combine_kernel<16, BF16P, MODE...>;
 }
-typedef void (*swa_hold_combine_fn)(const float*, const float*, bf16_t*, int, int, int, AppendArgs, const int32_t*);
-static swa_hold_combine_fn swa_hold_combine_for(int nsplit) {
-  if (nsplit > 16) return swa_rows_hold_combine_wide_kernel;
-  return nsplit <= 4 ? swa_rows_hold_combine_kernel<4> : nsplit <= 8 ? swa_rows_hold_combine_kernel<8> : swa_rows_hold_combine_kernel<16>;
+static swa_combine_fn swa_combine_for(int nsplit, bool rows, bool bf16p, bool hold) {
+  if (hold) return swa_combine_of<false, PerRowHold>(nsplit);
+  if (rows) return bf16p ? swa_combine_of<true, PerRow>(nsplit) : swa_combine_of<false, PerRow>(nsplit);
+  return bf16p ? swa_combine_of<true>(nsplit) : swa_combine_of<false>(nsplit);
 }
-// `frozen` != nullptr (with rows): the hold twins of the pos_rows combine kernels on the same grid
-static int swa_combine_append(const SwaParams& p, bool rows, bool bf16p, bool append, hipStream_t st, const int32_t* frozen = nullptr) {
+static int swa_combine_append(const SwaParams& p, bool rows, bool bf16p, bool append, hipStream_t st, const int32_t* frozen) {
   AppendArgs ap;
   ap.first_block = -1;
   const int append_blocks = !append ? 0 : swa_append_args(ap, p.k_new, p.kn_sb, p.kn_st, p.kn_sh, p.v_new, p.vn_sb, p.vn_st, p.vn_sh, p.k_cache,
@@ -585,19 +1278,15 @@ static int swa_combine_append(const SwaParams& p, bool rows, bool bf16p, bool ap
     const int blocks = p.nsplit > 16 ? (int)(nrows > 4096 ? 4096 : nrows)        // wide: one workgroup per row
                                      : blocks256(nrows * 64, 4096);              // one wavefront per row
     if (append_blocks > 0) ap.first_block = blocks;
-    if (frozen != nullptr) {
-      hipLaunchKernelGGL(swa_hold_combine_for(p.nsplit), dim3(blocks + append_blocks), dim3(256), 0, st, p.part_o, p.part_ml, p.o, p.B,
-                         p.T * p.Hq, p.nsplit, ap, frozen);
-      return check_launch("ivl_swa_decode_rows_hold_fwd(combine)");
-    }
-    hipLaunchKernelGGL(swa_combine_for(p.nsplit, rows, bf16p), dim3(blocks + append_blocks), dim3(256), 0, st, p.part_o, p.part_ml, p.o,
-                       p.B, p.T * p.Hq, p.nsplit, ap);
-    return check_launch(rows ? "ivl_swa_decode_rows_fwd / ivl_swa_rows_fwd(combine)" : "ivl_swa_fwd(combine)");
+    hipLaunchKernelGGL(swa_combine_for(p.nsplit, rows, bf16p, frozen != nullptr), dim3(blocks + append_blocks), dim3(256), 0, st, p.part_o,
+                       p.part_ml, p.o, p.B, p.T * p.Hq, p.nsplit, ap, frozen);
+    return check_launch(frozen != nullptr ? "ivl_swa_decode_rows_hold_fwd(combine)"
+                        : rows            ? "ivl_swa_decode_rows_fwd / ivl_swa_rows_fwd(combine)"
+                                          : "ivl_swa_fwd(combine)");
   }
   if (append_blocks > 0) {                     // one split (the packed pos_rows forms always have splits to merge: ivl_swa_rows_fwd only)
     ap.first_block = 0;
-    if (rows) hipLaunchKernelGGL(swa_rows_cache_append_kernel, dim3(append_blocks), dim3(256), 0, st, ap);
-    else hipLaunchKernelGGL(swa_cache_append_kernel, dim3(append_blocks), dim3(256), 0, st, ap);
+    hipLaunchKernelGGL((rows ? swa_cache_append_kernel<PerRow> : swa_cache_append_kernel<>), dim3(append_blocks), dim3(256), 0, st, ap);
     return check_launch(rows ? "ivl_swa_rows_fwd(append)" : "ivl_swa_fwd(append)");
   }
   return IVL_OK;
@@ -617,11 +1306,13 @@ extern "C" size_t ivl_swa_workspace_bytes(int B, int T, int Hq, int d) {
   return (size_t)B * ns * T * Hq * (SWA_D + 2) * sizeof(float) + rot + 256;
 }
 
-// The launch plan of a call that passed its entry point's rules (`fn`: ivl_swa_fwd, or ivl_swa_rows_fwd with pos_rows != nullptr):
-// the form, the split count, the rope pre-pass rule and the combine depend on B, T, Hq, Hkv, W and C only, never on a position, so a
-// pos_rows call runs the workgroups and the merge of ivl_swa_fwd on the same arguments (ROWS-1); the rows kernels differ from
-// their twins in where a workgroup reads its position.
-static int swa_plan_launch(const char* fn, const ivl_swa_args* a, const long long* pos_rows, void* stream) {
+// The launch plan of a call that passed its entry point's rules (`fn`: ivl_swa_fwd, or one of the three pos_rows entry points with
+// pos_rows != nullptr; `frozen` != nullptr: ivl_swa_decode_rows_hold_fwd, a packed shape by its rules): the form, the split count, the
+// rope pre-pass rule and the combine depend on B, T, Hq, Hkv, W and C only, never on a position, so a pos_rows call runs the
+// workgroups and the merge of ivl_swa_fwd on the same arguments (ROWS-1); the PerRow instances differ from the scalar ones in where
+// a workgroup reads its position.
+typedef void (*swa_attn_fn)(const long long*, SwaParams, const int32_t*);
+static int swa_plan_launch(const char* fn, const ivl_swa_args* a, const long long* pos_rows, const int32_t* frozen, void* stream) {
   const bool per_row = pos_rows != nullptr;
   const int G = a->Hq / a->Hkv;
   const bool pack = (long long)a->T * G <= SWA_QT && G <= 16;
@@ -670,17 +1361,17 @@ static int swa_plan_launch(const char* fn, const ivl_swa_args* a, const long lon
   }
   p.n_qtiles = prefill ? (rows + PF_QT - 1) / PF_QT : (rows + SWA_QT - 1) / SWA_QT;
   dim3 grid(p.n_qtiles * (pack ? a->Hkv : a->Hq) * a->B * nsplit);
-  if (per_row) {                         // (bf16 only: the entry point's rule)
-    if (prefill) hipLaunchKernelGGL(swa_rows_prefill_kernel, grid, dim3(P8_THREADS), 0, st, p.pos_dev, p);
-    else if (pack) hipLaunchKernelGGL(swa_rows_decode_kernel, grid, dim3(256), 0, st, p.pos_dev, p);
-    else hipLaunchKernelGGL(swa_rows_fwd_kernel, grid, dim3(256), 0, st, p.pos_dev, p);
-  } else if (prefill) hipLaunchKernelGGL(swa_prefill_kernel, grid, dim3(P8_THREADS), 0, st, p.pos_dev, p);
-  else if (pack && a->mma_dtype == IVL_FP8_E4M3)
+  if (pack && a->mma_dtype == IVL_FP8_E4M3) {          // (ivl_swa_fwd only: the pos_rows entry points take bf16)
     hipLaunchKernelGGL(swa_decode_fp8_kernel, dim3(a->Hkv * a->B * nsplit), dim3(256), 0, st, p.pos_dev, p);
-  else if (pack) hipLaunchKernelGGL((swa_fwd_kernel<true, 1>), grid, dim3(256), 0, st, p.pos_dev, p);
-  else hipLaunchKernelGGL((swa_fwd_kernel<false, 1>), grid, dim3(256), 0, st, p.pos_dev, p);
+  } else {
+    const swa_attn_fn kernel = prefill  ? (per_row ? swa_prefill_kernel<PerRow> : swa_prefill_kernel<>)
+                               : !pack  ? (per_row ? swa_fwd_kernel<false, 1, PerRow> : swa_fwd_kernel<false, 1>)
+                               : frozen ? swa_fwd_kernel<true, 1, PerRowHold>
+                                        : (per_row ? swa_fwd_kernel<true, 1, PerRow> : swa_fwd_kernel<true, 1>);
+    hipLaunchKernelGGL(kernel, grid, dim3(prefill ? P8_THREADS : 256), 0, st, p.pos_dev, p, frozen);
+  }
   if (const int rc = check_launch(fn); rc != IVL_OK) return rc;
-  return swa_combine_append(p, per_row, prefill, a->append_new != 0, st);
+  return swa_combine_append(p, per_row, prefill, a->append_new != 0, st, frozen);
 }
 
 extern "C" int ivl_swa_fwd(const ivl_swa_args* a, void* stream) {
@@ -709,11 +1400,13 @@ extern "C" int ivl_swa_fwd(const ivl_swa_args* a, void* stream) {
     const size_t need = ivl_swa_ring256_workspace_bytes(a->B, a->T, a->Hq, a->Hkv, a->d, a->cache_capacity);
     if (need != 0 && a->workspace != nullptr && a->workspace_bytes >= need) return swa_ring256_launch(a, (hipStream_t)stream);
   }
-  return swa_plan_launch(fn, a, nullptr, stream);
+  return swa_plan_launch(fn, a, nullptr, nullptr, stream);
 }
 
-// rules + launches of both pos_rows forms; frozen == nullptr IS ivl_swa_decode_rows_fwd
-static int swa_decode_rows_launch(const char* fn, const ivl_swa_args* a, const int64_t* pos_rows, const int32_t* frozen, void* stream) {
+// The three pos_rows entry points: one rule list, then the launch plan.  `packed_step` (ivl_swa_decode_rows_fwd and its hold form: a
+// decode step) adds the packing rule and, last, the rule that the shape has splits to merge; frozen == nullptr in the hold form IS
+// ivl_swa_decode_rows_fwd.  Never the ring256 form.
+static int swa_rows_entry(const char* fn, const ivl_swa_args* a, const int64_t* pos_rows, const int32_t* frozen, bool packed_step, void* stream) {
   // (a NULL struct is refused first, by the shared rule behind this one)
   IVL_REQUIRE(a == nullptr || pos_rows != nullptr, IVL_ERR_INVALID_ARG, "%s: NULL pos_rows", fn);
   if (const int rc = swa_check_pointers(a, fn); rc != IVL_OK) return rc;
@@ -724,56 +1417,31 @@ static int swa_decode_rows_launch(const char* fn, const ivl_swa_args* a, const i
               "%s: needs a ring cache (cache_capacity=%d)", fn, a->cache_capacity);
   IVL_REQUIRE(a->T_new == a->T, IVL_ERR_UNSUPPORTED, "%s: needs T_new == T (got %d, %d)", fn, a->T_new, a->T);
   const int G = a->Hq / a->Hkv;
-  IVL_REQUIRE((long long)a->T * G <= SWA_QT && G <= 16, IVL_ERR_UNSUPPORTED,
+  IVL_REQUIRE(!packed_step || ((long long)a->T * G <= SWA_QT && G <= 16), IVL_ERR_UNSUPPORTED,
               "%s: packed decode rows only: T * Hq/Hkv = %lld > %d", fn, (long long)a->T * G, SWA_QT);
   IVL_REQUIRE(a->mma_dtype == IVL_BF16, IVL_ERR_UNSUPPORTED, "%s: mma_dtype must be IVL_BF16 (got %d)", fn,
               a->mma_dtype);
   if (const int rc = swa_check_rope_tables(a, fn); rc != IVL_OK) return rc;
   IVL_REQUIRE(a->rope_cos == nullptr || swa_rope_sections_ok(a->rope_s0, a->rope_s1), IVL_ERR_UNSUPPORTED,
               "%s: mrope sections must be multiples of 8 (got %d, %d)", fn, a->rope_s0, a->rope_s1);
-  if (const int rc = swa_check_key_rows(a, fn, ""); rc != IVL_OK) return rc;
-  const int nsplit = swa_pack_nsplit(a);
-  IVL_REQUIRE(nsplit > 1, IVL_ERR_UNSUPPORTED, "%s: single-split shape (window %d)", fn, a->window);
-  SwaParams p = swa_params(a, nsplit);
-  p.pos = 0; p.pos_dev = (const long long*)pos_rows;
-  if (const int rc = swa_carve_partials(a, fn, p); rc != IVL_OK) return rc;
-  p.n_qtiles = 1;
-  hipStream_t st = (hipStream_t)stream;
-  if (frozen != nullptr) hipLaunchKernelGGL(swa_rows_hold_decode_kernel, dim3(a->Hkv * a->B * nsplit), dim3(256), 0, st, p.pos_dev, p, frozen);
-  else hipLaunchKernelGGL(swa_rows_decode_kernel, dim3(a->Hkv * a->B * nsplit), dim3(256), 0, st, p.pos_dev, p);
-  if (const int rc = check_launch(fn); rc != IVL_OK) return rc;
-  return swa_combine_append(p, true, false, a->append_new != 0, st, frozen);
+  if (const int rc = swa_check_key_rows(a, fn, packed_step ? "" : " (split the call)"); rc != IVL_OK) return rc;
+  IVL_REQUIRE(!packed_step || swa_pack_nsplit(a) > 1, IVL_ERR_UNSUPPORTED, "%s: single-split shape (window %d)", fn, a->window);
+  return swa_plan_launch(fn, a, (const long long*)pos_rows, frozen, stream);
 }
 
 extern "C" int ivl_swa_decode_rows_fwd(const ivl_swa_args* a, const int64_t* pos_rows, void* stream) {
-  return swa_decode_rows_launch("ivl_swa_decode_rows_fwd", a, pos_rows, nullptr, stream);
+  return swa_rows_entry("ivl_swa_decode_rows_fwd", a, pos_rows, nullptr, true, stream);
 }
 
 // ivl_swa_decode_rows_fwd with a per-row hold mask (HOLD-1..3 in ivl_hip.h): the same split count, grid and merge; the workgroups,
 // combine blocks and ring slots of a row with frozen[b] != 0 do nothing
 extern "C" int ivl_swa_decode_rows_hold_fwd(const ivl_swa_args* a, const int64_t* pos_rows, const int32_t* frozen, void* stream) {
-  return swa_decode_rows_launch("ivl_swa_decode_rows_hold_fwd", a, pos_rows, frozen, stream);
+  return swa_rows_entry("ivl_swa_decode_rows_hold_fwd", a, pos_rows, frozen, true, stream);
 }
 
-// ivl_swa_fwd with one ring position per batch row, every T >= 1 (ROWS-1..4 in ivl_hip.h): ivl_swa_decode_rows_fwd's rules minus the
-// packing rule, then ivl_swa_fwd's launch plan on the rows kernels (never the ring256 form)
+// ivl_swa_fwd with one ring position per batch row, every T >= 1 (ROWS-1..4 in ivl_hip.h): ivl_swa_fwd's launch plan on the PerRow kernels
 extern "C" int ivl_swa_rows_fwd(const ivl_swa_args* a, const int64_t* pos_rows, void* stream) {
-  static const char fn[] = "ivl_swa_rows_fwd";
-  IVL_REQUIRE(a == nullptr || pos_rows != nullptr, IVL_ERR_INVALID_ARG, "%s: NULL pos_rows", fn);
-  if (const int rc = swa_check_pointers(a, fn); rc != IVL_OK) return rc;
-  IVL_REQUIRE(a->B > 0 && a->T > 0 && a->Hq > 0 && a->Hkv > 0, IVL_ERR_INVALID_ARG,
-              "%s: bad sizes B=%d T=%d Hq=%d Hkv=%d", fn, a->B, a->T, a->Hq, a->Hkv);
-  if (const int rc = swa_check_heads(a, fn); rc != IVL_OK) return rc;
-  IVL_REQUIRE(a->cache_capacity > 0 && a->k_cache && a->v_cache, IVL_ERR_UNSUPPORTED,
-              "%s: needs a ring cache (cache_capacity=%d)", fn, a->cache_capacity);
-  IVL_REQUIRE(a->T_new == a->T, IVL_ERR_UNSUPPORTED, "%s: needs T_new == T (got %d, %d)", fn, a->T_new, a->T);
-  IVL_REQUIRE(a->mma_dtype == IVL_BF16, IVL_ERR_UNSUPPORTED, "%s: mma_dtype must be IVL_BF16 (got %d)", fn,
-              a->mma_dtype);
-  if (const int rc = swa_check_rope_tables(a, fn); rc != IVL_OK) return rc;
-  IVL_REQUIRE(a->rope_cos == nullptr || swa_rope_sections_ok(a->rope_s0, a->rope_s1), IVL_ERR_UNSUPPORTED,
-              "%s: mrope sections must be multiples of 8 (got %d, %d)", fn, a->rope_s0, a->rope_s1);
-  if (const int rc = swa_check_key_rows(a, fn, " (split the call)"); rc != IVL_OK) return rc;
-  return swa_plan_launch(fn, a, (const long long*)pos_rows, stream);
+  return swa_rows_entry("ivl_swa_rows_fwd", a, pos_rows, nullptr, false, stream);
 }
 
 extern "C" int ivl_swa_cache_append(const void* k_new, const void* v_new, int64_t kn_sb, int64_t kn_st, int64_t kn_sh,
@@ -792,6 +1460,6 @@ extern "C" int ivl_swa_cache_append(const void* k_new, const void* v_new, int64_
                                      Hkv, cache_capacity, pos, (const long long*)pos_dev, (const bf16_t*)rope_cos, (const bf16_t*)rope_sin,
                                      rope_s0, rope_s1);
   ap.first_block = 0;
-  hipLaunchKernelGGL(swa_cache_append_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, ap);
+  hipLaunchKernelGGL(swa_cache_append_kernel<>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, ap);
   return check_launch("ivl_swa_cache_append");
 }

@@ -1791,6 +1791,49 @@ SWA_RING256 = os.environ.get("IVL_SWA_RING256", "1") != "0"
 SWA_RING256_CALLS = 0          # calls that took it (tests read this to know which kernel a product-path call ran on)
 
 
+def _swa_args(who: str, q, k_new, v_new, k_cache, v_cache, *, layout, window, scaling, mma_dtype, rope, append, rules=None):
+    """The host marshalling of swa_forward and swa_forward_rows (`who` names the caller in the messages): dtype and layout checks,
+    the caller's own refusals (`rules(B, T, T_new, Hq, Hkv)`, between the shapes and the stride fix-ups), stride fix-ups, ring
+    asserts, the output tensor and an SwaArgs with every field set but the position fields and the workspace.
+    Returns (args, o, keep); `keep` holds the tensors whose pointers the struct carries, for the caller to hold until the launch."""
+    if q.dtype != torch.bfloat16 or k_new.dtype != torch.bfloat16 or v_new.dtype != torch.bfloat16:
+        raise ValueError(f"{who} is built for bf16")
+    if layout == "bhtd":
+        q, k_new, v_new = q.transpose(1, 2), k_new.transpose(1, 2), v_new.transpose(1, 2)
+    B, T, Hq, d = q.shape
+    T_new, Hkv = k_new.shape[1], k_new.shape[2]
+    if rules is not None:
+        rules(B, T, T_new, Hq, Hkv)
+    if q.stride(-1) != 1:
+        q = q.contiguous()
+    if k_new.stride(-1) != 1 or v_new.stride() != k_new.stride():
+        k_new, v_new = k_new.contiguous(), v_new.contiguous()
+    C = 0
+    if k_cache is not None:
+        assert k_cache.is_contiguous() and v_cache.is_contiguous() and k_cache.dtype == torch.bfloat16
+        assert tuple(k_cache.shape[:2]) == (B, Hkv) and k_cache.shape[3] == d
+        C = k_cache.shape[2]
+    o = torch.empty(B, T, Hq, d, dtype=torch.bfloat16, device=q.device)
+    a = SwaArgs()
+    a.q, a.k_new, a.v_new, a.k_cache, a.v_cache, a.o = (q.data_ptr(), k_new.data_ptr(), v_new.data_ptr(),
+                                                         k_cache.data_ptr() if C else None,
+                                                         v_cache.data_ptr() if C else None, o.data_ptr())
+    a.q_sb, a.q_st, a.q_sh = q.stride(0), q.stride(1), q.stride(2)
+    a.kn_sb, a.kn_st, a.kn_sh = k_new.stride(0), k_new.stride(1), k_new.stride(2)
+    a.B, a.T, a.T_new, a.Hq, a.Hkv, a.d = B, T, T_new, Hq, Hkv, d
+    a.cache_capacity = C
+    a.window = int(window) if window is not None else 0
+    a.scaling = float(scaling)
+    a.mma_dtype = mma_code(mma_dtype)
+    a.append_new = int(bool(append) and C > 0)
+    keep = [q, k_new, v_new]
+    if rope is not None:
+        cos, sin, sec = _rope_args(rope, B, T, d)
+        a.rope_cos, a.rope_sin, a.rope_s0, a.rope_s1 = cos.data_ptr(), sin.data_ptr(), int(sec[0]), int(sec[1])
+        keep += [cos, sin]
+    return a, o, keep
+
+
 def swa_forward(
     q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor, *, window: Optional[int], scaling: float,
     k_cache: Optional[torch.Tensor] = None, v_cache: Optional[torch.Tensor] = None,
@@ -1817,41 +1860,31 @@ def swa_forward(
     `frozen` (device int32 [B], with pos_rows only; ivl_swa_decode_rows_hold_fwd): a row with frozen[b] != 0 keeps its ring row
     and its o rows are unspecified; the mask is read at replay."""
     _need_gpu(q, k_new, v_new, k_cache, v_cache, pos_dev, pos_rows, frozen)
-    if q.dtype != torch.bfloat16 or k_new.dtype != torch.bfloat16 or v_new.dtype != torch.bfloat16:
-        raise ValueError("swa_forward is built for bf16")
-    if layout == "bhtd":
-        q, k_new, v_new = q.transpose(1, 2), k_new.transpose(1, 2), v_new.transpose(1, 2)
-    B, T, Hq, d = q.shape
-    T_new, Hkv = k_new.shape[1], k_new.shape[2]
-    if n_query is not None:
-        assert n_query == T
-    if pos_rows is not None:
-        if pos_dev is not None or pos != 0 or pos_min != 0:
-            raise ValueError("swa_forward: pos_rows excludes pos / pos_dev / pos_min")
-        if pos_rows.dtype != torch.int64 or tuple(pos_rows.shape) != (B,) or not pos_rows.is_contiguous():
-            raise ValueError(f"swa_forward: pos_rows must be a contiguous int64 [B] = [{B}] tensor; got {pos_rows.dtype} "
-                             f"{tuple(pos_rows.shape)}")
-        if k_cache is None:
-            raise ValueError("swa_forward: pos_rows needs a ring cache (k_cache / v_cache)")
-        if T_new != T or T * (Hq // Hkv) > 64:
-            raise ValueError(f"swa_forward: pos_rows serves packed decode steps only: T_new == T and T * Hq/Hkv <= 64 "
-                             f"(got T={T}, T_new={T_new}, Hq/Hkv={Hq // Hkv})")
-        if mma_code(mma_dtype) != IVL_BF16:
-            raise ValueError("swa_forward: pos_rows runs in bf16 only (no fp8 decode step)")
-    if frozen is not None:
-        if pos_rows is None:
-            raise ValueError("swa_forward: frozen goes with pos_rows")
-        _check_frozen("swa_forward", frozen, B, q)
-    if q.stride(-1) != 1:
-        q = q.contiguous()
-    if k_new.stride(-1) != 1 or v_new.stride() != k_new.stride():
-        k_new, v_new = k_new.contiguous(), v_new.contiguous()
-    C = 0
-    if k_cache is not None:
-        assert k_cache.is_contiguous() and v_cache.is_contiguous() and k_cache.dtype == torch.bfloat16
-        assert tuple(k_cache.shape[:2]) == (B, Hkv) and k_cache.shape[3] == d
-        C = k_cache.shape[2]
-    o = torch.empty(B, T, Hq, d, dtype=torch.bfloat16, device=q.device)
+
+    def rules(B, T, T_new, Hq, Hkv):
+        if n_query is not None:
+            assert n_query == T
+        if pos_rows is not None:
+            if pos_dev is not None or pos != 0 or pos_min != 0:
+                raise ValueError("swa_forward: pos_rows excludes pos / pos_dev / pos_min")
+            if pos_rows.dtype != torch.int64 or tuple(pos_rows.shape) != (B,) or not pos_rows.is_contiguous():
+                raise ValueError(f"swa_forward: pos_rows must be a contiguous int64 [B] = [{B}] tensor; got {pos_rows.dtype} "
+                                 f"{tuple(pos_rows.shape)}")
+            if k_cache is None:
+                raise ValueError("swa_forward: pos_rows needs a ring cache (k_cache / v_cache)")
+            if T_new != T or T * (Hq // Hkv) > 64:
+                raise ValueError(f"swa_forward: pos_rows serves packed decode steps only: T_new == T and T * Hq/Hkv <= 64 "
+                                 f"(got T={T}, T_new={T_new}, Hq/Hkv={Hq // Hkv})")
+            if mma_code(mma_dtype) != IVL_BF16:
+                raise ValueError("swa_forward: pos_rows runs in bf16 only (no fp8 decode step)")
+        if frozen is not None:
+            if pos_rows is None:
+                raise ValueError("swa_forward: frozen goes with pos_rows")
+            _check_frozen("swa_forward", frozen, B, q)
+
+    a, o, keep = _swa_args("swa_forward", q, k_new, v_new, k_cache, v_cache, layout=layout, window=window, scaling=scaling,
+                           mma_dtype=mma_dtype, rope=rope, append=append, rules=rules)
+    B, T, T_new, Hq, Hkv, d, C = a.B, a.T, a.T_new, a.Hq, a.Hkv, a.d, a.cache_capacity
     lib = _lib.load()
     nbytes = lib.ivl_swa_workspace_bytes(B, T, Hq, d)
     pos_min = int(pos_min) if pos_dev is not None else int(pos)
@@ -1865,25 +1898,10 @@ def swa_forward(
             SWA_RING256_CALLS += 1
         nbytes = max(nbytes, n256)
     ws = get_workspace(nbytes, q.device, "swa")
-    a = SwaArgs()
-    a.q, a.k_new, a.v_new, a.k_cache, a.v_cache, a.o = (q.data_ptr(), k_new.data_ptr(), v_new.data_ptr(),
-                                                         k_cache.data_ptr() if C else None,
-                                                         v_cache.data_ptr() if C else None, o.data_ptr())
-    a.q_sb, a.q_st, a.q_sh = q.stride(0), q.stride(1), q.stride(2)
-    a.kn_sb, a.kn_st, a.kn_sh = k_new.stride(0), k_new.stride(1), k_new.stride(2)
-    a.B, a.T, a.T_new, a.Hq, a.Hkv, a.d = B, T, T_new, Hq, Hkv, d
-    a.cache_capacity = C
-    a.window = int(window) if window is not None else 0
+    a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
     a.pos = int(pos)
     a.pos_dev = pos_dev.data_ptr() if pos_dev is not None else None
-    a.scaling = float(scaling)
-    a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
-    a.mma_dtype = mma_code(mma_dtype)
-    a.append_new = int(bool(append) and C > 0)
     a.pos_min = pos_min
-    if rope is not None:
-        cos, sin, sec = _rope_args(rope, B, T, d)
-        a.rope_cos, a.rope_sin, a.rope_s0, a.rope_s1 = cos.data_ptr(), sin.data_ptr(), int(sec[0]), int(sec[1])
     if frozen is not None:
         HOLD_CALLS["swa_forward"] += 1
         _lib.check(lib.ivl_swa_decode_rows_hold_fwd(ctypes.byref(a), pos_rows.data_ptr(), frozen.data_ptr(), _stream(q)))
@@ -1891,6 +1909,7 @@ def swa_forward(
         _lib.check(lib.ivl_swa_decode_rows_fwd(ctypes.byref(a), pos_rows.data_ptr(), _stream(q)))
     else:
         _lib.check(lib.ivl_swa_fwd(ctypes.byref(a), _stream(q)))
+    del keep                   # (held until here: the launches are issued)
     return o
 
 
@@ -1908,47 +1927,26 @@ def swa_forward_rows(
     bit-equal to row b of swa_forward on the same tensors with every row at pos_rows[b] (ROWS-1 in include/ivl_hip.h).
     Ring cache, T_new == T, bf16; `rope` and `append` as in swa_forward."""
     _need_gpu(q, k_new, v_new, k_cache, v_cache, pos_rows)
-    if q.dtype != torch.bfloat16 or k_new.dtype != torch.bfloat16 or v_new.dtype != torch.bfloat16:
-        raise ValueError("swa_forward_rows is built for bf16")
-    if layout == "bhtd":
-        q, k_new, v_new = q.transpose(1, 2), k_new.transpose(1, 2), v_new.transpose(1, 2)
-    B, T, Hq, d = q.shape
-    T_new, Hkv = k_new.shape[1], k_new.shape[2]
-    if pos_rows.dtype != torch.int64 or tuple(pos_rows.shape) != (B,) or not pos_rows.is_contiguous():
-        raise ValueError(f"swa_forward_rows: pos_rows must be a contiguous int64 [B] = [{B}] tensor; got {pos_rows.dtype} "
-                         f"{tuple(pos_rows.shape)}")
-    if k_cache is None or v_cache is None:
-        raise ValueError("swa_forward_rows: pos_rows needs a ring cache (k_cache / v_cache)")
-    if T_new != T:
-        raise ValueError(f"swa_forward_rows: needs T_new == T (got T={T}, T_new={T_new})")
-    if q.stride(-1) != 1:
-        q = q.contiguous()
-    if k_new.stride(-1) != 1 or v_new.stride() != k_new.stride():
-        k_new, v_new = k_new.contiguous(), v_new.contiguous()
-    assert k_cache.is_contiguous() and v_cache.is_contiguous() and k_cache.dtype == torch.bfloat16
-    assert tuple(k_cache.shape[:2]) == (B, Hkv) and k_cache.shape[3] == d and tuple(v_cache.shape) == tuple(k_cache.shape)
-    C = k_cache.shape[2]
-    o = torch.empty(B, T, Hq, d, dtype=torch.bfloat16, device=q.device)
+
+    def rules(B, T, T_new, Hq, Hkv):
+        if pos_rows.dtype != torch.int64 or tuple(pos_rows.shape) != (B,) or not pos_rows.is_contiguous():
+            raise ValueError(f"swa_forward_rows: pos_rows must be a contiguous int64 [B] = [{B}] tensor; got {pos_rows.dtype} "
+                             f"{tuple(pos_rows.shape)}")
+        if k_cache is None or v_cache is None:
+            raise ValueError("swa_forward_rows: pos_rows needs a ring cache (k_cache / v_cache)")
+        if T_new != T:
+            raise ValueError(f"swa_forward_rows: needs T_new == T (got T={T}, T_new={T_new})")
+
+    a, o, keep = _swa_args("swa_forward_rows", q, k_new, v_new, k_cache, v_cache, layout=layout, window=window, scaling=scaling,
+                           mma_dtype=None, rope=rope, append=append, rules=rules)
+    assert tuple(v_cache.shape) == tuple(k_cache.shape)
     lib = _lib.load()
-    ws = get_workspace(lib.ivl_swa_workspace_bytes(B, T, Hq, d), q.device, "swa")
-    a = SwaArgs()
-    a.q, a.k_new, a.v_new, a.k_cache, a.v_cache, a.o = (q.data_ptr(), k_new.data_ptr(), v_new.data_ptr(), k_cache.data_ptr(),
-                                                         v_cache.data_ptr(), o.data_ptr())
-    a.q_sb, a.q_st, a.q_sh = q.stride(0), q.stride(1), q.stride(2)
-    a.kn_sb, a.kn_st, a.kn_sh = k_new.stride(0), k_new.stride(1), k_new.stride(2)
-    a.B, a.T, a.T_new, a.Hq, a.Hkv, a.d = B, T, T_new, Hq, Hkv, d
-    a.cache_capacity = C
-    a.window = int(window) if window is not None else 0
-    a.scaling = float(scaling)
+    ws = get_workspace(lib.ivl_swa_workspace_bytes(a.B, a.T, a.Hq, a.d), q.device, "swa")
     a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
-    a.mma_dtype = IVL_BF16
-    a.append_new = int(bool(append))
-    if rope is not None:
-        cos, sin, sec = _rope_args(rope, B, T, d)
-        a.rope_cos, a.rope_sin, a.rope_s0, a.rope_s1 = cos.data_ptr(), sin.data_ptr(), int(sec[0]), int(sec[1])
     global ROWS_STEP_CALLS
     ROWS_STEP_CALLS += 1
     _lib.check(lib.ivl_swa_rows_fwd(ctypes.byref(a), pos_rows.data_ptr(), _stream(q)))
+    del keep                   # (held until here: the launches are issued)
     return o
 
 

@@ -128,6 +128,59 @@ def test_packed_shape_equals_the_decode_rows_call():
         assert torch.equal(o1, o2) and torch.equal(k1, k2) and torch.equal(v1, v2), rope is not None
 
 
+@pytest.mark.parametrize("append", [False, True])
+@pytest.mark.parametrize("use_rope", [False, True])
+@pytest.mark.parametrize("T", [1, 4])
+def test_packed_rows_forms_share_one_launch_plan(T, use_rope, append):
+    """On a packed shape the three pos_rows entry points run ONE launch plan, the pack branch of ivl_swa_fwd's: ivl_swa_decode_rows_fwd,
+    ivl_swa_rows_fwd and ivl_swa_decode_rows_hold_fwd under a mask of zeros give the same bits in o and in both rings, and every row
+    is the B = 1 scalar-position call at its position, bit for bit.  With row 1 held its ring row keeps its bits and rows 0 and 2 do
+    not notice.  Ring of 95 under window 96 (3 splits); the rows: an empty ring row, a half-full one, a wrapped one."""
+    from infinitevl_amd import ops
+    C, positions = 95, [0, 40, 200]
+    B = len(positions)
+    g = torch.Generator().manual_seed(40 + T)
+    kc, vc = (torch.randn(B, HKV, C, D, generator=g).to(BF).to(DEV) for _ in range(2))
+    q = torch.randn(B, T, HQ, D, generator=g).to(BF).to(DEV)
+    k, v = (torch.randn(B, T, HKV, D, generator=g).to(BF).to(DEV) for _ in range(2))
+    pos_rows = torch.tensor(positions, dtype=torch.int64, device=DEV)
+    pid = (pos_rows[None, :, None] + torch.arange(T, device=DEV)[None, None, :]).expand(3, B, T) + \
+        torch.tensor([0, 3, 11], device=DEV)[:, None, None]
+    cos, sin = frames.rope_tables(pid)
+    kw = dict(window=C + 1, scaling=SCALE, append=append)
+    names = ("o", "k ring", "v ring")
+
+    def run(fn, **extra):
+        kr, vr = kc.clone(), vc.clone()
+        o = fn(q, k, v, k_cache=kr, v_cache=vr, pos_rows=pos_rows, rope=(cos, sin, frames.SECTIONS) if use_rope else None, **kw, **extra)
+        torch.cuda.synchronize()
+        return o, kr, vr
+
+    calls, holds = ops.ROWS_STEP_CALLS, ops.HOLD_CALLS["swa_forward"]
+    dec = run(ops.swa_forward)                                                                   # ivl_swa_decode_rows_fwd
+    rows = run(ops.swa_forward_rows)                                                             # ivl_swa_rows_fwd
+    hold0 = run(ops.swa_forward, frozen=torch.zeros(B, dtype=torch.int32, device=DEV))           # ivl_swa_decode_rows_hold_fwd
+    assert ops.ROWS_STEP_CALLS == calls + 1 and ops.HOLD_CALLS["swa_forward"] == holds + 1
+    assert pos_rows.tolist() == positions
+    for what, a, b_, c in zip(names, dec, rows, hold0):
+        assert torch.equal(words(a), words(b_)), (what, "ivl_swa_rows_fwd")
+        assert torch.equal(words(a), words(c)), (what, "ivl_swa_decode_rows_hold_fwd")
+    for b, p in enumerate(positions):                                                            # the B = 1 call with a scalar position
+        kr, vr = kc[b:b + 1].clone(), vc[b:b + 1].clone()
+        rope1 = (cos[:, b:b + 1].contiguous(), sin[:, b:b + 1].contiguous(), frames.SECTIONS) if use_rope else None
+        o1 = ops.swa_forward(q[b:b + 1], k[b:b + 1], v[b:b + 1], k_cache=kr, v_cache=vr, pos=p, rope=rope1, **kw)
+        torch.cuda.synchronize()
+        for what, got, ref in zip(names, dec, (o1, kr, vr)):
+            assert torch.equal(words(got[b]), words(ref[0])), (what, b, p)
+        slots = torch.tensor([(p + t) % C for t in range(T)], device=DEV)
+        assert torch.equal(dec[2][b][:, slots], vc[b][:, slots]) == (not append), (b, p)         # the append took its slots, or none
+    held = run(ops.swa_forward, frozen=torch.tensor([0, 1, 0], dtype=torch.int32, device=DEV))
+    assert torch.equal(words(held[1][1]), words(kc[1])) and torch.equal(words(held[2][1]), words(vc[1]))      # HOLD-1
+    for b in (0, 2):                                                                             # HOLD-2
+        for what, got, ref in zip(names, held, dec):
+            assert torch.equal(words(got[b]), words(ref[b])), (what, b)
+
+
 @pytest.mark.parametrize("name", ["c", "d"])
 def test_rows_against_the_oracle(name):
     from infinitevl_amd import ops
