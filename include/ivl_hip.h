@@ -133,6 +133,25 @@ IVL_API int ivl_gdn_chunk_fused_fwd(const void* proj, int64_t ld, int col_q, int
                             const float* dt_bias, void* o, const void* h0, int h0_dtype, void* ht, int ht_dtype, int B,
                             int T, int H, int K, int V, int conv_width, float scale, int mma_dtype, void* workspace,
                             size_t workspace_bytes, void* sync, void* stream);
+/* ivl_gdn_chunk_fused_fwd with A TOKEN COUNT PER BATCH ROW: row b takes the first n_b = clamp(n_rows[b], 0, T) tokens of its T rows
+ * of proj and nothing else of them touches its states.  n_rows: device int32 [B], never read on the host (each workgroup reads its
+ * row's count as it starts).  Scope: mma_dtype IVL_BF16, K = 128, V = 256, conv width 4, one segment (T <= 4096), states updated in
+ * place (each s*_out and ht aliases its input -- ht with h0's dtype -- or is NULL); other shapes IVL_ERR_UNSUPPORTED, other
+ * arguments IVL_ERR_INVALID_ARG.  Always the two-launch form (no sync area: a workgroup that has left is never waited for).
+ * n_rows == NULL: the call IS ivl_gdn_chunk_fused_fwd with sync = NULL, same kernels, same bits.
+ *   RAG-1 for every row b, o[b, :n_b], the recurrent state and the three conv states (also for n_b of 1, 2 or 3, where old and new
+ *         inputs mix in a conv state) are bit-equal to row b of ivl_gdn_chunk_fused_fwd(sync = NULL) on the same arguments with the
+ *         same B and T = n_b.
+ *   RAG-2 a row depends on its own first n_b tokens only.  Tokens t >= n_b of proj are never read (they may hold NaN); o[b, n_b:] is
+ *         unspecified; what other rows hold, or how long they are, changes no bit of row b.
+ *   RAG-3 for n_b = 0 no byte the row owns is written and none is read (its states may hold NaN).
+ *   RAG-4 the counts are read when the launch RUNS: one captured call serves every tick, the same bits eager or replayed. */
+IVL_API int ivl_gdn_chunk_fused_rows_fwd(const void* proj, int64_t ld, int col_q, int col_k, int col_v, int col_a, int col_b,
+                                 const void* wq, const void* wk, const void* wv, const void* sq_in, const void* sk_in,
+                                 const void* sv_in, void* sq_out, void* sk_out, void* sv_out, const float* A_log,
+                                 const float* dt_bias, void* o, const void* h0, int h0_dtype, void* ht, int ht_dtype, int B,
+                                 int T, int H, int K, int V, int conv_width, float scale, int mma_dtype, void* workspace,
+                                 size_t workspace_bytes, const int32_t* n_rows, void* stream);
 /* Status of the single-launch forms on the CURRENT device: IVL_OK or IVL_ERR_SYNC (ivl_last_error(): which wait, head, chunk).
  * sync == NULL: what the kernels of ANY area have reported so far through the host-visible status slots -- no stream work,
  *   callable at any time, also during capture (a failure shows up once the failing kernel has run: check after a
@@ -277,6 +296,22 @@ IVL_API int ivl_swa_decode_rows_fwd(const ivl_swa_args* args, const int64_t* pos
  *   ROWS-4 with append_new and T > cache_capacity only the last cache_capacity tokens of a row reach its ring, as in ivl_swa_fwd.
  * Refusals are ivl_swa_decode_rows_fwd's minus the packing rule. */
 IVL_API int ivl_swa_rows_fwd(const ivl_swa_args* args, const int64_t* pos_rows, void* stream);
+/* ivl_swa_rows_fwd with A TOKEN COUNT PER BATCH ROW: row b brings n_b = clamp(n_rows[b], 0, T) tokens, the first n_b of its T.  n_rows:
+ * device int32 [B], never read on the host.  Same arguments, same rules, same launch plan (which reads no length); n_rows == NULL IS
+ * ivl_swa_rows_fwd.  Scope: the unpacked forms, T * Hq/Hkv > 64 (a packed shape is IVL_ERR_UNSUPPORTED: the decode step has its hold
+ * twin).  Causality keeps a query t < n_b from the keys of tokens >= n_b, so the valid rows attend as before; what changes: with
+ * append_new only tokens t < n_b go to slots (pos_rows[b] + t) % C (the last C of them when n_b > C); query tiles wholly at or beyond
+ * n_b, and their rows of the merge, do nothing.
+ *   RAG-5  o[b, :n_b] is bit-equal to ivl_swa_rows_fwd on the same arguments with ZEROS in q, k_new and v_new at the tokens t >= n_b
+ *          (which is what the kernels compute, without reading them; with other finite values there the 128-row kernel of
+ *          ivl_swa_rows_fwd may move a row's lazily updated softmax reference when a neighbouring row of its wavefront outgrows its
+ *          own -- the same value up to the rounding of the rescale).  o[b, n_b:] is unspecified.
+ *   RAG-6  row b's ring row is bit-equal to its ring row after ivl_swa_rows_fwd with T = n_b (rope tables of the same positions).
+ *   RAG-7  with n_b = 0 no byte of the row's ring row is written or read.
+ *   RAG-8  pos_rows is never written.
+ *   RAG-9  q / k_new / v_new at t >= n_b and unread ring slots may hold NaN.
+ *   RAG-10 the counts are read when the launch RUNS: one captured call serves every tick, the same bits eager or replayed. */
+IVL_API int ivl_swa_rows_n_fwd(const ivl_swa_args* args, const int64_t* pos_rows, const int32_t* n_rows, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Per-row HOLD of a multi-stream step.  `frozen`: device int32 [B], read when the launch RUNS (at replay); row b is frozen when

@@ -589,18 +589,26 @@ class MultiStreamSlidingLayer(StaticSlidingWindowLayerPrealloc):
         self._frozen = None                  # MultiStreamCache.enable_holds: the hold mask, device int32 [n_slots]
         self._hold_advance = True            # False: the owner of the cache advances _pos_rows itself (one ops.rows_advance)
 
-    def attend(self, q, k_new, v_new, scaling, window, mma_dtype=None, rope=None):
+    def attend(self, q, k_new, v_new, scaling, window, mma_dtype=None, rope=None, frame_lengths=None):
         B, T, Hkv, D = k_new.shape
         if mma_dtype is not None and ops.mma_code(mma_dtype) != ops.IVL_BF16:
             raise ValueError("MultiStreamCache: the fp8 decode step is not supported (bf16 only)")
         if B != self.batch_size:
             raise ValueError(f"MultiStreamCache has {self.batch_size} slots, but got B={B}")
+        if frame_lengths is not None:
+            # a ragged frame step: slot b brings its first frame_lengths[b] tokens (ivl_swa_rows_n_fwd) and moves on by as many -- a
+            # device add, capturable.  The host mirror is the caller's to advance: only it knows the counts (advance_rows)
+            o = ops.swa_forward_rows(q, k_new, v_new, window=window, scaling=scaling, k_cache=self._buf_keys, v_cache=self._buf_values,
+                                     pos_rows=self._pos_rows, rope=rope, append=True, n_rows=frame_lengths)
+            if self._advances_counter:
+                self._pos_rows.add_(frame_lengths)
+            return o
         if T != 1:
             if not q.is_cuda:
                 raise ValueError(f"MultiStreamCache: a frame step (T={T} tokens for every slot) runs on the GPU only; one slot alone "
                                  "is prefilled through MultiStreamCache.slot_view(slot)")
             # a frame step: T tokens for EVERY slot (ivl_swa_rows_fwd).  The hold mask is not read: a held or finished slot takes the
-            # tokens too, as extend() on a finished slot does (the GDN chunk kernels have no per-slot mask either)
+            # tokens too, as extend() on a finished slot does (a slot that brings fewer tokens, or none: frame_lengths, above)
             o = ops.swa_forward_rows(q, k_new, v_new, window=window, scaling=scaling, k_cache=self._buf_keys,
                                      v_cache=self._buf_values, pos_rows=self._pos_rows, rope=rope, append=True)
             if self._advances_counter:
@@ -704,6 +712,14 @@ class MultiStreamCache(StaticCachePrealloc):
         self.hold_mask = frozen
         for layer in self._sliding():
             layer._frozen, layer._hold_advance = frozen, bool(advance)
+
+    def advance_rows(self, lengths) -> None:
+        """Host-side bookkeeping of one ragged frame step (forward(frame_lengths=)): slot s moved on by lengths[s] tokens."""
+        for s, n in enumerate(lengths):
+            self.slot_lengths[s] += int(n)
+        for layer in self.layers:
+            if not isinstance(layer, MultiStreamSlidingLayer):
+                layer.advance(0)             # (started; a GDN layer keeps no per-slot length)
 
     def sync_lengths(self):
         """Rewrites the host mirror slot_lengths from pos_rows (one read-back; it waits for the steps queued so far) and returns

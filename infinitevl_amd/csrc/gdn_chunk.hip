@@ -274,6 +274,10 @@ __device__ __forceinline__ void conv4_silu(const u32x4* xr, const u32x4* w, u32x
 // workgroup are launched one after the other -- and arrived at B1 later than wave 1 does with both jobs.)
 // The conv state of k is read by BOTH workgroups of chunk 0 and written (possibly in place) by the k side: the q side raises
 // `kread` once its loads of the old state have returned, the k side writes the new state at its very end, behind that word.
+// INVARIANT the rows mode rests on (gdn_chunk_prepare_rows_kernel below calls this body with T = the row's token count and pf.proj
+// moved forward by b * (T_call - T) rows): every use of T as a STRIDE has the form base + (b * T + t) * row_stride on a buffer the
+// wrapper re-bases (today: pf.proj only), and nt_seg is used for the record base (bh * nt_seg + ci) and nothing else.  A new
+// T-strided buffer, or a new use of nt_seg, must be added to the wrapper as well.
 template <bool F8, bool FUSED, bool DEV, int ROLE, bool LOOPED = false>
 __device__ __forceinline__ void gdn_chunk_prepare_body(
     unsigned char* smem, const int ci, const int bh,
@@ -883,6 +887,25 @@ __global__ __launch_bounds__(512, 2) void gdn_chunk_prepare_kernel(
   extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
   gdn_chunk_prepare_body<F8, FUSED, false, 0>(smem, (int)blockIdx.x, (int)blockIdx.y, q, k, g, beta, pf, ws, T, H, t_seg0, nt_seg, l2norm, nullptr,
                                               nullptr, nullptr);
+}
+
+// ---- a token count per batch row (ivl_gdn_chunk_fused_rows_fwd; two-launch fused form, one segment) ----------------------------
+// The bodies take ONE number T for two things: the row stride of the buffers (b * T rows in front of batch row b) and the tokens that
+// count (the valid rows of a chunk, the clamped loads, "the last chunk", the conv-state carry-out, the final-state store).  The rows
+// mode runs the SAME bodies with T = n = clamp(n_rows[b], 0, T) and hands them batch-row bases moved forward by b * (T - n) rows, so
+// that b * n rows further on the body stands at the row's true first token: every address it forms is the one the plain kernel
+// forms for a call of T = n tokens on this row (RAG-1), nothing at or beyond token n is addressed (RAG-2), and the pre-existing
+// instantiations are the code they were.  b is workgroup-uniform: the count (rows_count_, ivl_common.h) lives in SGPRs.
+template <bool F8>
+__global__ __launch_bounds__(512, 2) void gdn_chunk_prepare_rows_kernel(PrepFused pf, unsigned char* __restrict__ ws, int T, int H, int nt_seg,
+                                                                        const int32_t* __restrict__ n_rows) {
+  extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
+  const int ci = (int)blockIdx.x, b = (int)blockIdx.y / H;
+  const int n = rows_count_(n_rows, b, T);
+  if (ci * GC >= n) return;                    // a chunk at or beyond ceil(n / 64), every chunk of a row with n = 0 (RAG-3): before the first load
+  pf.proj += (long long)b * (T - n) * pf.ld;
+  gdn_chunk_prepare_body<F8, true, false, 0>(smem, ci, (int)blockIdx.y, nullptr, nullptr, nullptr, nullptr, pf, ws, n, H, 0, nt_seg, 1, nullptr, nullptr,
+                                             nullptr);
 }
 
 // ==================================================================================================
@@ -1665,6 +1688,9 @@ __device__ __forceinline__ void scan_role(int w, int& role, int& idx) {
 
 // One scan workgroup: batch*head bx, column slab by.  SYNC (single-launch form): the records are written by pre-pass
 // workgroups of the SAME launch; `sync` -> ScanSync tells the loader waves where to wait for them.
+// INVARIANT the rows mode rests on (gdn_chunk_scan_rows_kernel below calls this body with T and nt_seg = the row's token and chunk
+// counts and re-based ws, o and sv.v): T is a STRIDE only as base + (b * T + t) * row_stride on sv.v (V waves, loaders) and o, and
+// nt_seg a stride only in ws_bh = ws + bh * nt_seg records.  A new T- or nt_seg-strided address must be added to the wrapper as well.
 template <int NCW, bool F8, bool VCONV, int SYNC>
 __device__ __forceinline__ void gdn_chunk_scan_body(
     unsigned char* smem, const int bx, const int by,
@@ -2012,6 +2038,20 @@ __global__ __launch_bounds__(64 * (2 * NCW + SCAN_NL + SCAN_NV)) void gdn_chunk_
                                              nt_seg, scale, ScanSync{});
 }
 
+template <int NCW, bool F8>
+__global__ __launch_bounds__(64 * (2 * NCW + SCAN_NL + SCAN_NV)) void gdn_chunk_scan_rows_kernel(
+    const unsigned char* __restrict__ ws, bf16_t* __restrict__ o, ScanV sv, const void* h0, int h0_dtype, void* ht, int ht_dtype,
+    int T, int H, int nt_seg, float scale, const int32_t* __restrict__ n_rows) {
+  extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
+  const int bh = (int)blockIdx.x, b = bh / H;
+  const int n = rows_count_(n_rows, b, T);
+  if (n == 0) return;                          // RAG-3: no state read, none written; the whole workgroup, ahead of every barrier
+  const int nt = (n + GC - 1) / GC;            // the row's chunks: the scan's steps, its "last chunk", its records (row bh at bh * nt_seg)
+  sv.v += (long long)b * (T - n) * sv.ld;
+  gdn_chunk_scan_body<NCW, F8, true, 0>(smem, bh, (int)blockIdx.y, ws + (size_t)bh * (nt_seg - nt) * Rec<F8>::STRIDE,
+                                        o + (size_t)b * (T - n) * H * GV, sv, h0, h0_dtype, ht, ht_dtype, n, H, 0, nt, scale, ScanSync{});
+}
+
 // Single launch of the fused call at small grids (the benchmark's streaming step: 2 x 64 pre-pass + 128 scan workgroups on 256
 // CUs).  The first blocks are pre-pass workgroups (waves 8-11 leave at once), the rest scan workgroups; both kinds need no more
 // than one CU each.  The scan side waits for the pre-pass side (scan_wait_records) without a second launch -- one launch
@@ -2232,6 +2272,9 @@ static void gdn_chunk_init_device() {
     (void)hipFuncSetAttribute((const void*)gdn_chunk_prepare_kernel<true, true>, attr, P_BYTES);
     scan_set_attr<4, false, false>(); scan_set_attr<2, false, false>(); scan_set_attr<4, true, false>(); scan_set_attr<2, true, false>();
     scan_set_attr<4, false, true>(); scan_set_attr<2, false, true>(); scan_set_attr<4, true, true>(); scan_set_attr<2, true, true>();
+    (void)hipFuncSetAttribute((const void*)gdn_chunk_prepare_rows_kernel<false>, attr, P_BYTES);
+    (void)hipFuncSetAttribute((const void*)gdn_chunk_scan_rows_kernel<2, false>, attr, scan_lds_bytes(2, false));
+    (void)hipFuncSetAttribute((const void*)gdn_chunk_scan_rows_kernel<4, false>, attr, scan_lds_bytes(4, false));
     const int lds16 = scan_lds_bytes(2, false);
     (void)hipFuncSetAttribute((const void*)gdn_chunk_single_kernel<false, 0>, attr, lds16);
     (void)hipFuncSetAttribute((const void*)gdn_chunk_single_kernel<false, 1>, attr, lds16);
@@ -2421,31 +2464,87 @@ extern "C" int ivl_gdn_chunk_fwd(const void* q, const void* k, const void* v, co
                                  (unsigned char*)workspace, nullptr, (hipStream_t)stream);
 }
 
+// the argument rules the fused entry points share (`who`: the entry point's name in the error text)
+static int gdn_fused_check(const char* who, const void* proj, int64_t ld, int col_q, int col_k, int col_v, int col_a, int col_b, const void* wq,
+                           const void* wk, const void* wv, const float* A_log, const float* dt_bias, const void* o, const void* h0, int h0_dtype,
+                           const void* ht, int ht_dtype, int B, int T, int H, int K, int V, int conv_width, int mma_dtype,
+                           const void* workspace, size_t workspace_bytes) {
+  IVL_REQUIRE(proj && wq && wk && wv && A_log && dt_bias && o, IVL_ERR_INVALID_ARG, "%s: NULL pointer", who);
+  IVL_REQUIRE(B > 0 && T > 0 && H > 0, IVL_ERR_INVALID_ARG, "%s: B,T,H must be positive (%d,%d,%d)", who, B, T, H);
+  IVL_REQUIRE(K == GK && V == GV && conv_width == 4, IVL_ERR_UNSUPPORTED, "%s: built for K=128, V=256, conv width 4 (got %d,%d,%d)", who, K, V,
+              conv_width);
+  IVL_REQUIRE((long long)T * ld < (1LL << 31), IVL_ERR_UNSUPPORTED,
+              "%s: T * ld = %lld elements exceeds the 32-bit row addressing of the pre-pass (split the call)", who, (long long)T * ld);
+  IVL_REQUIRE(ld % 8 == 0 && col_q % 8 == 0 && col_k % 8 == 0 && col_v % 8 == 0 && col_q >= 0 && col_k >= 0 && col_v >= 0 &&
+                  col_a >= 0 && col_b >= 0 && col_a + H <= ld && col_b + H <= ld,
+              IVL_ERR_INVALID_ARG, "%s: projection columns must be 16-byte aligned and inside the row (ld=%lld)", who, (long long)ld);
+  IVL_REQUIRE((h0 == nullptr || h0_dtype == IVL_F32 || h0_dtype == IVL_BF16) &&
+              (ht == nullptr || ht_dtype == IVL_F32 || ht_dtype == IVL_BF16),
+              IVL_ERR_INVALID_ARG, "%s: state dtype must be IVL_F32 or IVL_BF16", who);
+  IVL_REQUIRE(mma_dtype == IVL_BF16 || mma_dtype == IVL_FP8_E4M3, IVL_ERR_INVALID_ARG, "%s: mma_dtype must be IVL_BF16 or IVL_FP8_E4M3 (got %d)",
+              who, mma_dtype);
+  const size_t need = ivl_gdn_chunk_workspace_bytes(B, T, H, K, V);
+  IVL_REQUIRE(workspace != nullptr && workspace_bytes >= need, IVL_ERR_WORKSPACE, "%s: workspace %zu bytes < required %zu", who, workspace_bytes,
+              need);
+  return IVL_OK;
+}
+
+// A token count per batch row (include/ivl_hip.h, RAG-1..4): always the two launches, one segment, the counts read by the workgroups.
+extern "C" int ivl_gdn_chunk_fused_rows_fwd(const void* proj, int64_t ld, int col_q, int col_k, int col_v, int col_a, int col_b,
+                                            const void* wq, const void* wk, const void* wv, const void* sq_in, const void* sk_in,
+                                            const void* sv_in, void* sq_out, void* sk_out, void* sv_out, const float* A_log,
+                                            const float* dt_bias, void* o, const void* h0, int h0_dtype, void* ht, int ht_dtype, int B,
+                                            int T, int H, int K, int V, int conv_width, float scale, int mma_dtype, void* workspace,
+                                            size_t workspace_bytes, const int32_t* n_rows, void* stream) {
+  if (n_rows == nullptr)
+    return ivl_gdn_chunk_fused_fwd(proj, ld, col_q, col_k, col_v, col_a, col_b, wq, wk, wv, sq_in, sk_in, sv_in, sq_out, sk_out, sv_out, A_log,
+                                   dt_bias, o, h0, h0_dtype, ht, ht_dtype, B, T, H, K, V, conv_width, scale, mma_dtype, workspace,
+                                   workspace_bytes, nullptr, stream);
+  const char* who = "ivl_gdn_chunk_fused_rows_fwd";
+  if (const int rc = gdn_fused_check(who, proj, ld, col_q, col_k, col_v, col_a, col_b, wq, wk, wv, A_log, dt_bias, o, h0, h0_dtype, ht, ht_dtype,
+                                     B, T, H, K, V, conv_width, mma_dtype, workspace, workspace_bytes);
+      rc != IVL_OK)
+    return rc;
+  IVL_REQUIRE(mma_dtype == IVL_BF16, IVL_ERR_UNSUPPORTED, "%s: per-row token counts run the bf16 products only (mma_dtype %d)", who, mma_dtype);
+  IVL_REQUIRE(T <= G_SEG_CHUNKS * GC, IVL_ERR_UNSUPPORTED, "%s: one segment only, T <= %d (got %d)", who, G_SEG_CHUNKS * GC, T);
+  // a row of fewer than T tokens keeps what it does not rewrite only when every state is updated in place
+  IVL_REQUIRE((sq_out == nullptr || sq_out == sq_in) && (sk_out == nullptr || sk_out == sk_in) && (sv_out == nullptr || sv_out == sv_in) &&
+                  (ht == nullptr || (ht == h0 && ht_dtype == h0_dtype)),
+              IVL_ERR_INVALID_ARG, "%s: every conv state output and ht must alias its input or be NULL", who);
+  gdn_chunk_init_device();
+  PrepFused pf;
+  pf.proj = (const bf16_t*)proj; pf.ld = ld;
+  pf.col_q = col_q; pf.col_k = col_k; pf.col_v = col_v; pf.col_a = col_a; pf.col_b = col_b;
+  pf.w[0] = (const bf16_t*)wq; pf.w[1] = (const bf16_t*)wk; pf.w[2] = (const bf16_t*)wv;
+  pf.st_in[0] = (const bf16_t*)sq_in; pf.st_in[1] = (const bf16_t*)sk_in; pf.st_in[2] = (const bf16_t*)sv_in;
+  pf.st_out[0] = (bf16_t*)sq_out; pf.st_out[1] = (bf16_t*)sk_out; pf.st_out[2] = (bf16_t*)sv_out;
+  pf.A_log = A_log; pf.dt_bias = dt_bias;
+  ScanV sv;
+  sv.v = pf.proj; sv.ld = ld; sv.col0 = col_v; sv.w = pf.w[2]; sv.st_in = pf.st_in[2]; sv.st_out = pf.st_out[2];
+  const int NT = (T + GC - 1) / GC;
+  hipStream_t st = (hipStream_t)stream;
+  unsigned char* wsb = (unsigned char*)workspace;
+  hipLaunchKernelGGL((gdn_chunk_prepare_rows_kernel<false>), dim3(NT, B * H), dim3(512), P_BYTES, st, pf, wsb, T, H, NT, n_rows);
+  if (const int rc = check_launch("ivl_gdn_chunk_fused_rows_fwd(prepare)"); rc != IVL_OK) return rc;
+  if (B * H * 4 <= 128)                        // the column split of ivl_gdn_chunk_fused_fwd for the same B and H
+    hipLaunchKernelGGL((gdn_chunk_scan_rows_kernel<2, false>), dim3(B * H, 8), dim3(64 * (2 * 2 + SCAN_NL + SCAN_NV)), scan_lds_bytes(2, false), st,
+                       wsb, (bf16_t*)o, sv, h0, h0_dtype, ht, ht_dtype, T, H, NT, scale, n_rows);
+  else
+    hipLaunchKernelGGL((gdn_chunk_scan_rows_kernel<4, false>), dim3(B * H, 4), dim3(64 * (2 * 4 + SCAN_NL + SCAN_NV)), scan_lds_bytes(4, false), st,
+                       wsb, (bf16_t*)o, sv, h0, h0_dtype, ht, ht_dtype, T, H, NT, scale, n_rows);
+  return check_launch("ivl_gdn_chunk_fused_rows_fwd(scan)");
+}
+
 extern "C" int ivl_gdn_chunk_fused_fwd(const void* proj, int64_t ld, int col_q, int col_k, int col_v, int col_a, int col_b,
                                        const void* wq, const void* wk, const void* wv, const void* sq_in, const void* sk_in,
                                        const void* sv_in, void* sq_out, void* sk_out, void* sv_out, const float* A_log,
                                        const float* dt_bias, void* o, const void* h0, int h0_dtype, void* ht, int ht_dtype, int B,
                                        int T, int H, int K, int V, int conv_width, float scale, int mma_dtype, void* workspace,
                                        size_t workspace_bytes, void* sync, void* stream) {
-  IVL_REQUIRE(proj && wq && wk && wv && A_log && dt_bias && o, IVL_ERR_INVALID_ARG, "ivl_gdn_chunk_fused_fwd: NULL pointer");
-  IVL_REQUIRE(B > 0 && T > 0 && H > 0, IVL_ERR_INVALID_ARG, "ivl_gdn_chunk_fused_fwd: B,T,H must be positive (%d,%d,%d)", B, T, H);
-  IVL_REQUIRE(K == GK && V == GV && conv_width == 4, IVL_ERR_UNSUPPORTED,
-              "ivl_gdn_chunk_fused_fwd: built for K=128, V=256, conv width 4 (got %d,%d,%d)", K, V, conv_width);
-  IVL_REQUIRE((long long)T * ld < (1LL << 31), IVL_ERR_UNSUPPORTED,
-              "ivl_gdn_chunk_fused_fwd: T * ld = %lld elements exceeds the 32-bit row addressing of the pre-pass (split the call)",
-              (long long)T * ld);
-  IVL_REQUIRE(ld % 8 == 0 && col_q % 8 == 0 && col_k % 8 == 0 && col_v % 8 == 0 && col_q >= 0 && col_k >= 0 && col_v >= 0 &&
-                  col_a >= 0 && col_b >= 0 && col_a + H <= ld && col_b + H <= ld,
-              IVL_ERR_INVALID_ARG, "ivl_gdn_chunk_fused_fwd: projection columns must be 16-byte aligned and inside the row (ld=%lld)",
-              (long long)ld);
-  IVL_REQUIRE((h0 == nullptr || h0_dtype == IVL_F32 || h0_dtype == IVL_BF16) &&
-              (ht == nullptr || ht_dtype == IVL_F32 || ht_dtype == IVL_BF16),
-              IVL_ERR_INVALID_ARG, "ivl_gdn_chunk_fused_fwd: state dtype must be IVL_F32 or IVL_BF16");
-  IVL_REQUIRE(mma_dtype == IVL_BF16 || mma_dtype == IVL_FP8_E4M3, IVL_ERR_INVALID_ARG,
-              "ivl_gdn_chunk_fused_fwd: mma_dtype must be IVL_BF16 or IVL_FP8_E4M3 (got %d)", mma_dtype);
-  const size_t need = ivl_gdn_chunk_workspace_bytes(B, T, H, K, V);
-  IVL_REQUIRE(workspace != nullptr && workspace_bytes >= need, IVL_ERR_WORKSPACE,
-              "ivl_gdn_chunk_fused_fwd: workspace %zu bytes < required %zu", workspace_bytes, need);
+  if (const int rc = gdn_fused_check("ivl_gdn_chunk_fused_fwd", proj, ld, col_q, col_k, col_v, col_a, col_b, wq, wk, wv, A_log, dt_bias, o, h0,
+                                     h0_dtype, ht, ht_dtype, B, T, H, K, V, conv_width, mma_dtype, workspace, workspace_bytes);
+      rc != IVL_OK)
+    return rc;
   IVL_REQUIRE(sync == nullptr || ((size_t)sync & 15) == 0, IVL_ERR_INVALID_ARG, "ivl_gdn_chunk_fused_fwd: sync area must be 16-byte aligned");
   gdn_chunk_init_device();
   if (sync != nullptr) {

@@ -173,6 +173,14 @@ __device__ __forceinline__ long long divmod_idx(long long x, int d, int& rem) {
 #define IVL_TOUT(slot, value) ((void)0)
 #endif
 
+// The token count of batch row b in a call with a count per row (ivl_gdn_chunk_fused_rows_fwd, ivl_swa_rows_n_fwd: n_rows is a device
+// int32 [B]), clamped to [0, T] on the device.  Where b is workgroup-uniform the value goes through v_readfirstlane into SGPRs.
+// rows_clamp_ is the one spelling of the clamp; rows_count_ is for a workgroup-uniform b only.
+__device__ __forceinline__ int rows_clamp_(int n, int T) { return n < 0 ? 0 : (n > T ? T : n); }
+__device__ __forceinline__ int rows_count_(const int32_t* __restrict__ n_rows, int b, int T) {
+  return rows_clamp_(__builtin_amdgcn_readfirstlane(n_rows[b]), T);
+}
+
 // ---- host side -------------------------------------------------------------------------------
 void set_error(const char* fmt, ...);
 int check_launch(const char* what);

@@ -48,10 +48,18 @@ struct SwaParams {
 // A template and not a shared body function, as measured: a templated kernel with the body written in it compiles to the
 // instruction stream the hand-written kernel had, line for line; a __forceinline__ body function is inlined later in the
 // optimisation pipeline and changes it (swa_prefill_kernel: 8,165 -> 8,253 lines of assembly).  Table: DESIGN.md 4.26.
+//   PerRowN     PerRow with a token count per row, n_rows int32[B] in the `frozen` slot (ivl_swa_rows_n_fwd, unpacked forms): row b is
+//               the call with zeros in q, k_new and v_new at tokens t >= n_b = clamp(n_rows[b], 0, T), none of which is read -- the
+//               geometry (tiles, splits, dead-tile tests) stays that of T, so the valid rows keep their bits (RAG-5); query tiles
+//               wholly at or beyond n_b leave at once, rows t >= n_b are neither stored nor merged, only tokens t < n_b are appended
 struct PerRow {};
 struct PerRowHold {};
+struct PerRowN {};
 template <typename... MODE>
-constexpr int swa_rows_mode = (std::is_same<PerRowHold, MODE>::value || ...) ? 2 : (std::is_same<PerRow, MODE>::value || ...) ? 1 : 0;
+constexpr int swa_rows_mode = (std::is_same<PerRowN, MODE>::value || ...)      ? 3
+                              : (std::is_same<PerRowHold, MODE>::value || ...) ? 2
+                              : (std::is_same<PerRow, MODE>::value || ...)     ? 1
+                                                                               : 0;
 
 // The 64-row kernel.  QG = 16-row query groups per wave; only QG = 1 is instantiated (decode / T <= 64 calls), longer calls run
 // swa_prefill_kernel.  PACK: the rows of a workgroup are the (token, head-in-group) pairs of one kv head (decode steps).  The
@@ -94,6 +102,12 @@ __global__ __launch_bounds__(256, 2) void swa_fwd_kernel(const long long* pos_de
   if constexpr (ROWS == 2) {
     if (frozen[b] != 0) return;        // workgroup-uniform (HOLD-1): no q / ring read, no partial written
   }
+  int Tn = p.T;                        // PerRowN: the tokens of this batch row that exist
+  if constexpr (ROWS == 3) {
+    static_assert(!PACK, "token counts per row: the unpacked forms");
+    Tn = rows_count_(frozen, b, p.T);
+    if (bx * QT >= Tn) return;         // workgroup-uniform: a query tile wholly at or beyond n_b (every tile when n_b = 0, RAG-7)
+  }
   IVL_T(tr_start);
 #ifdef IVL_TRACE
   const long long rt_start = (long long)__builtin_amdgcn_s_memrealtime();
@@ -104,7 +118,7 @@ __global__ __launch_bounds__(256, 2) void swa_fwd_kernel(const long long* pos_de
   const int n_ring = p.C > 0 ? (int)(pos < (long long)p.C ? pos : (long long)p.C) : 0;
   const int n_extra = p.T_new - p.T;
   const int n_prev = n_ring + n_extra;
-  const int S = n_prev + p.T;
+  const int S = n_prev + (ROWS == 3 ? Tn : p.T);               // keys that exist (PerRowN: the tail of the call reads as zeros, unread)
   const int s0 = p.C > 0 ? mod_pos(pos - n_ring, p.C) : 0;      // ring slot of call-local key 0
 
   // ---- rows of this workgroup / wave / lane ----------------------------------------------------
@@ -150,7 +164,7 @@ __global__ __launch_bounds__(256, 2) void swa_fwd_kernel(const long long* pos_de
     const bf16_t* qp = p.q + (long long)b * p.q_sb + (long long)t_row[qg] * p.q_st + (long long)hq[qg] * p.q_sh;
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
-      if (row_ok[qg]) qf[qg][ks] = *(const u32x4*)(qp + 32 * ks + 8 * g);
+      if (row_ok[qg] && (ROWS != 3 || t_row[qg] < Tn)) qf[qg][ks] = *(const u32x4*)(qp + 32 * ks + 8 * g);
       else qf[qg][ks] = u32x4{0u, 0u, 0u, 0u};
     }
   }
@@ -159,7 +173,7 @@ __global__ __launch_bounds__(256, 2) void swa_fwd_kernel(const long long* pos_de
   if (p.rcos != nullptr) {
 #pragma unroll
     for (int qg = 0; qg < QG; ++qg) {
-      const long long row_off = ((long long)b * p.T + min(t_row[qg], p.T - 1)) * SWA_D;
+      const long long row_off = ((long long)b * p.T + min(t_row[qg], (ROWS == 3 ? Tn : p.T) - 1)) * SWA_D;
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) rope_pair(qf[qg][ks], qf[qg][ks + 2], p.rcos, p.rsin, rplane, row_off, 32 * ks + 8 * g, p.rs0, p.rs1);
     }
@@ -292,7 +306,7 @@ __global__ __launch_bounds__(256, 2) void swa_fwd_kernel(const long long* pos_de
   // ---- epilogue: lane owns its rows, d = 16 mt2 + 4g + r ----------------------------------------
 #pragma unroll
   for (int qg = 0; qg < QG; ++qg) {
-    if (!row_ok[qg]) continue;
+    if (!row_ok[qg] || (ROWS == 3 && t_row[qg] >= Tn)) continue;
     if (p.nsplit == 1) {
       tile64_store_row<8, true>(p.o + (((long long)b * p.T + t_row[qg]) * p.Hq + hq[qg]) * SWA_D + 4 * g, oacc[qg], l_run[qg]);
     } else {
@@ -385,6 +399,11 @@ __global__ __launch_bounds__(P8_THREADS, 1) void swa_prefill_kernel(const long l
   const int hq = rest % p.Hq, bz = rest / p.Hq;
   const int b = bz / p.nsplit, split = bz % p.nsplit;
   const int hk = hq / G;
+  int Tn = p.T;                        // PerRowN: the tokens of this batch row that exist (SGPR)
+  if constexpr (ROWS == 3) {
+    Tn = rows_count_(frozen, b, p.T);
+    if (bx * PF_QT >= Tn) return;      // the whole workgroup, ahead of every barrier: a query tile wholly at or beyond n_b
+  }
   IVL_T(tr_start);
 
   // the position comes through a vector load (the pointer is not provably read-only): everything derived from it -- ring geometry,
@@ -395,7 +414,7 @@ __global__ __launch_bounds__(P8_THREADS, 1) void swa_prefill_kernel(const long l
                                     (unsigned long long)(unsigned int)__builtin_amdgcn_readfirstlane((unsigned int)pos_v));
   const int n_ring = p.C > 0 ? (int)(pos < (long long)p.C ? pos : (long long)p.C) : 0;
   const int n_prev = n_ring + (p.T_new - p.T);
-  const int S = n_prev + p.T;
+  const int S = n_prev + (ROWS == 3 ? Tn : p.T);        // keys that exist (PerRowN: behind them the call reads as zeros, unread)
   const int s0 = __builtin_amdgcn_readfirstlane(p.C > 0 ? mod_pos(pos - n_ring, p.C) : 0);
 
   const int tile_row0 = bx * PF_QT;
@@ -528,12 +547,12 @@ __global__ __launch_bounds__(P8_THREADS, 1) void swa_prefill_kernel(const long l
   const int w_lo_max = p.W > 0 ? max(0, n_prev + wr1 - p.W + 1) : 0;
   u32x4 qf[8];
   {
-    const bf16_t* qp = p.q + (long long)b * p.q_sb + (long long)min(row, p.T - 1) * p.q_st + (long long)hq * p.q_sh;
+    const bf16_t* qp = p.q + (long long)b * p.q_sb + (long long)min(row, (ROWS == 3 ? Tn : p.T) - 1) * p.q_st + (long long)hq * p.q_sh;
 #pragma unroll
     for (int kd = 0; kd < 8; ++kd) qf[kd] = *(const u32x4*)(qp + 16 * kd + 8 * hi5);
   }
   if (p.rcos != nullptr) {
-    const long long row_off = ((long long)b * p.T + min(row, p.T - 1)) * SWA_D;
+    const long long row_off = ((long long)b * p.T + min(row, (ROWS == 3 ? Tn : p.T) - 1)) * SWA_D;
     const long long plane = (long long)p.B * p.T * SWA_D;
     u32x4 c1[4], n1[4], c2[4], n2[4];
 #pragma unroll
@@ -547,7 +566,7 @@ __global__ __launch_bounds__(P8_THREADS, 1) void swa_prefill_kernel(const long l
 #pragma unroll
     for (int kd = 0; kd < 4; ++kd) rope_apply(qf[kd], qf[kd + 4], c1[kd], n1[kd], c2[kd], n2[kd]);
   }
-  if (!row_ok) {
+  if (!row_ok || (ROWS == 3 && row >= Tn)) {
 #pragma unroll
     for (int kd = 0; kd < 8; ++kd) qf[kd] = u32x4{0u, 0u, 0u, 0u};
   }
@@ -770,7 +789,7 @@ __global__ __launch_bounds__(P8_THREADS, 1) void swa_prefill_kernel(const long l
     for (int i = 0; i < 4; ++i) {
       const int idx = tid + 512 * i, r = idx >> 4, c = idx & 15;       // row, 8-channel piece
       const int t = tile_row0 + r;
-      if (t < p.T) {
+      if (t < (ROWS == 3 ? Tn : p.T)) {
         const unsigned char* src = smem + r * PF_OSTRIDE + c * 32;
         const f32x4 x = *(const f32x4*)src, y = *(const f32x4*)(src + 16);
         const long long orow = p.nsplit == 1 ? ((long long)b * p.T + t) * p.Hq + hq
@@ -779,7 +798,7 @@ __global__ __launch_bounds__(P8_THREADS, 1) void swa_prefill_kernel(const long l
                     u32x4{pack2bf(x[0], x[1]), pack2bf(x[2], x[3]), pack2bf(y[0], y[1]), pack2bf(y[2], y[3])});
       }
     }
-    if (p.nsplit > 1 && tid < PF_QT && tile_row0 + tid < p.T) {
+    if (p.nsplit > 1 && tid < PF_QT && tile_row0 + tid < (ROWS == 3 ? Tn : p.T)) {
       const long long prow = (((long long)b * p.nsplit + split) * p.T + tile_row0 + tid) * p.Hq + hq;
       *(float2*)(p.part_ml + prow * 2) = *(const float2*)(smem + PF_ML_OFF + tid * 8);
     }
@@ -970,29 +989,45 @@ __global__ __launch_bounds__(256, 2) void swa_decode_fp8_kernel(const long long*
 // [B,T,H,128]) and the attention kernel runs on rotated data.  Rotating inside the attention kernel repeats the work in every
 // split and every q head of a kv group: at the step shape (8 splits) the q rope alone cost every workgroup 128 KB of
 // cos / sin traffic and ~5 us per launch; the pre-pass costs one ~2 us launch.  Same arithmetic (rope_pair): bit-identical.
+// The body is a macro, not a function or a template: written into the kernel it compiles to the code the kernel had.  Tried: a
+// __forceinline__ body moved six instructions of the old kernel; a `template <typename... MODE>` kernel with the trailing n_rows of
+// the other families (the way of DESIGN.md 4.26) kept its 677 instructions but changed 72 of them (the extra kernel argument moves
+// the preloaded SGPRs), and made the plain kernel a template instance under another symbol.  SKIP_: the statement in front of a token's loads -- empty, or the PerRowN rule: tokens t >= n_rows[b] are neither
+// read nor written (the attention kernel reads none of them).
+#define IVL_SWA_ROPE_PREPASS_BODY(SKIP_)                                                                                          \
+  const int HT = Hq + Hkv;                                                                                                        \
+  const long long total = (long long)B * T * HT * 8;               /* (row, head, channel-block pair c, c + 8) */                 \
+  const long long plane = (long long)B * T * SWA_D;                                                                               \
+  for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) { \
+    const int c = (int)(idx & 7);                                                                                                 \
+    int h, t;                                                                                                                     \
+    const long long bt = divmod_idx(idx >> 3, HT, h);                                                                             \
+    const int b = (int)divmod_idx(bt, T, t);                                                                                      \
+    SKIP_                                                                                                                         \
+    const bool is_q = h < Hq;                                                                                                     \
+    const bf16_t* src = is_q ? q + (long long)b * q_sb + (long long)t * q_st + (long long)h * q_sh                                \
+                             : k + (long long)b * k_sb + (long long)t * k_st + (long long)(h - Hq) * k_sh;                        \
+    u32x4 lo = *(const u32x4*)(src + 8 * c), hi = *(const u32x4*)(src + 8 * c + 64);                                              \
+    rope_pair(lo, hi, rcos, rsin, plane, bt * SWA_D, 8 * c, rs0, rs1);                                                            \
+    bf16_t* dst = is_q ? q_out + (bt * Hq + h) * SWA_D : k_out + (bt * Hkv + (h - Hq)) * SWA_D;                                   \
+    store_out16(dst + 8 * c, lo);                                                                                                 \
+    store_out16(dst + 8 * c + 64, hi);                                                                                            \
+  }
 __global__ __launch_bounds__(256) void swa_rope_prepass_kernel(const bf16_t* __restrict__ q, long long q_sb, long long q_st, long long q_sh,
                                                               const bf16_t* __restrict__ k, long long k_sb, long long k_st, long long k_sh,
                                                               bf16_t* __restrict__ q_out, bf16_t* __restrict__ k_out, int B, int T, int Hq,
                                                               int Hkv, const bf16_t* __restrict__ rcos, const bf16_t* __restrict__ rsin,
                                                               int rs0, int rs1) {
-  const int HT = Hq + Hkv;
-  const long long total = (long long)B * T * HT * 8;               // (row, head, channel-block pair c, c + 8)
-  const long long plane = (long long)B * T * SWA_D;
-  for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
-    const int c = (int)(idx & 7);
-    int h, t;
-    const long long bt = divmod_idx(idx >> 3, HT, h);
-    const int b = (int)divmod_idx(bt, T, t);
-    const bool is_q = h < Hq;
-    const bf16_t* src = is_q ? q + (long long)b * q_sb + (long long)t * q_st + (long long)h * q_sh
-                             : k + (long long)b * k_sb + (long long)t * k_st + (long long)(h - Hq) * k_sh;
-    u32x4 lo = *(const u32x4*)(src + 8 * c), hi = *(const u32x4*)(src + 8 * c + 64);
-    rope_pair(lo, hi, rcos, rsin, plane, bt * SWA_D, 8 * c, rs0, rs1);
-    bf16_t* dst = is_q ? q_out + (bt * Hq + h) * SWA_D : k_out + (bt * Hkv + (h - Hq)) * SWA_D;
-    store_out16(dst + 8 * c, lo);
-    store_out16(dst + 8 * c + 64, hi);
-  }
+  IVL_SWA_ROPE_PREPASS_BODY((void)b;)
 }
+__global__ __launch_bounds__(256) void swa_rope_prepass_rows_kernel(const bf16_t* __restrict__ q, long long q_sb, long long q_st, long long q_sh,
+                                                                   const bf16_t* __restrict__ k, long long k_sb, long long k_st, long long k_sh,
+                                                                   bf16_t* __restrict__ q_out, bf16_t* __restrict__ k_out, int B, int T, int Hq,
+                                                                   int Hkv, const bf16_t* __restrict__ rcos, const bf16_t* __restrict__ rsin,
+                                                                   int rs0, int rs1, const int32_t* __restrict__ n_rows) {
+  IVL_SWA_ROPE_PREPASS_BODY(if (t >= rows_clamp_(n_rows[b], T)) continue;)
+}
+#undef IVL_SWA_ROPE_PREPASS_BODY
 
 // Ring append folded into the combine launch (ivl_swa_args.append_new): the blocks behind the combine blocks copy the
 // call's tokens into the ring.  The attention kernel has finished by then (stream order), so no reader of the old
@@ -1007,6 +1042,7 @@ struct AppendArgs {
 // token t of the call -> slot (pos + t) % C ; only the last min(T, C) tokens are written
 // ROWS (ivl_swa_decode_rows_fwd): a.pos_dev is an int64[B], batch row b appends at its own pos_dev[b]
 // ROWS == 2 (ivl_swa_decode_rows_hold_fwd): the same, and the slots of a row with frozen[b] != 0 are not written
+// ROWS == 3 (ivl_swa_rows_n_fwd): `frozen` holds the rows' token counts; row b appends the last min(n_b, C) of its first n_b tokens
 template <int ROWS = 0>
 __device__ __forceinline__ void ring_append(const AppendArgs& a, long long block, long long nblocks, const int32_t* frozen = nullptr) {
   const long long pos = ROWS ? 0 : (a.pos_dev ? *a.pos_dev : a.pos);
@@ -1019,7 +1055,13 @@ __device__ __forceinline__ void ring_append(const AppendArgs& a, long long block
     int hk, tt;
     const long long bt = divmod_idx(idx >> 4, a.Hkv, hk);          // SWA_D / 8 = 16 pieces per row
     const int b = (int)divmod_idx(bt, nt, tt);
-    tt += t_first;
+    if constexpr (ROWS == 3) {         // the row's own count (in the `frozen` slot): the last min(n_b, C) of its first n_b tokens
+      const int nb = rows_clamp_(frozen[b], a.T);
+      tt += nb > a.C ? nb - a.C : 0;
+      if (tt >= nb) continue;
+    } else {
+      tt += t_first;
+    }
     if constexpr (ROWS == 2) {
       if (frozen[b] != 0) continue;
     }
@@ -1064,6 +1106,10 @@ __global__ __launch_bounds__(256) void swa_combine_kernel(const float* __restric
     const long long b = divmod_idx(r, rows_per_b, rr_), rr = rr_;
     if constexpr (ROWS == 2) {
       if (frozen[b] != 0) continue;        // uniform over the row's wavefront
+    }
+    if constexpr (ROWS == 3) {             // rows of tokens t >= n_b have no partials (ap.T is set for every PerRowN launch)
+      const int t = rr_ / (rows_per_b / ap.T);       // rows_per_b = T * Hq: row rr_ = t * Hq + head
+      if (t >= rows_clamp_(frozen[b], ap.T)) continue;
     }
     float ms[NS], ls[NS];
     float2 ov[NS];
@@ -1122,6 +1168,10 @@ __global__ __launch_bounds__(256) void swa_combine_wide_kernel(const float* __re
     if constexpr (ROWS == 2) {
       if (frozen[b] != 0) continue;        // uniform over the row's workgroup
     }
+    if constexpr (ROWS == 3) {
+      const int t = rr_ / (rows_per_b / ap.T);       // rows_per_b = T * Hq: row rr_ = t * Hq + head
+      if (t >= rows_clamp_(frozen[b], ap.T)) continue;
+    }
     const bool on = lane < nsplit;
     const float2 ml = *(const float2*)(part_ml + ((b * nsplit + (on ? lane : 0)) * rows_per_b + rr) * 2);
     float2 ov[16];
@@ -1159,6 +1209,10 @@ __global__ __launch_bounds__(256) void swa_combine_wide_kernel(const float* __re
 // (ivl_swa_rows_fwd with append_new and one split): ap.pos_dev is an int64[B]
 template <typename... MODE>
 __global__ __launch_bounds__(256) void swa_cache_append_kernel(AppendArgs ap) { ring_append<swa_rows_mode<MODE...>>(ap, blockIdx.x, gridDim.x); }
+// ... of a PerRowN call with one split: the counts ride behind the struct
+__global__ __launch_bounds__(256) void swa_cache_append_n_kernel(AppendArgs ap, const int32_t* __restrict__ n_rows) {
+  ring_append<3>(ap, blockIdx.x, gridDim.x, n_rows);
+}
 
 static int swa_base_nsplit(int B, int T, int Hq) {
   const bool prefill = T > SWA_QT;
@@ -1263,14 +1317,17 @@ static swa_combine_fn swa_combine_of(int nsplit) {
   if (nsplit > 16) return swa_combine_wide_kernel<MODE...>;
   return nsplit <= 4 ? swa_combine_kernel<4, BF16P, MODE...> : nsplit <= 8 ? swa_combine_kernel<8, BF16P, MODE...> : swa_combine_kernel<16, BF16P, MODE...>;
 }
-static swa_combine_fn swa_combine_for(int nsplit, bool rows, bool bf16p, bool hold) {
+static swa_combine_fn swa_combine_for(int nsplit, bool rows, bool bf16p, bool hold, bool counts) {
+  if (counts) return bf16p ? swa_combine_of<true, PerRowN>(nsplit) : swa_combine_of<false, PerRowN>(nsplit);
   if (hold) return swa_combine_of<false, PerRowHold>(nsplit);
   if (rows) return bf16p ? swa_combine_of<true, PerRow>(nsplit) : swa_combine_of<false, PerRow>(nsplit);
   return bf16p ? swa_combine_of<true>(nsplit) : swa_combine_of<false>(nsplit);
 }
-static int swa_combine_append(const SwaParams& p, bool rows, bool bf16p, bool append, hipStream_t st, const int32_t* frozen) {
+// `counts`: `frozen` holds the token counts of a PerRowN call, not a hold mask
+static int swa_combine_append(const SwaParams& p, bool rows, bool bf16p, bool append, hipStream_t st, const int32_t* frozen, bool counts) {
   AppendArgs ap;
   ap.first_block = -1;
+  ap.T = p.T;                                  // (read by the PerRowN merge also when nothing is appended)
   const int append_blocks = !append ? 0 : swa_append_args(ap, p.k_new, p.kn_sb, p.kn_st, p.kn_sh, p.v_new, p.vn_sb, p.vn_st, p.vn_sh, p.k_cache,
                                                           p.v_cache, p.B, p.T, p.Hkv, p.C, p.pos, p.pos_dev, p.rcos, p.rsin, p.rs0, p.rs1);
   if (p.nsplit > 1) {
@@ -1278,14 +1335,19 @@ static int swa_combine_append(const SwaParams& p, bool rows, bool bf16p, bool ap
     const int blocks = p.nsplit > 16 ? (int)(nrows > 4096 ? 4096 : nrows)        // wide: one workgroup per row
                                      : blocks256(nrows * 64, 4096);              // one wavefront per row
     if (append_blocks > 0) ap.first_block = blocks;
-    hipLaunchKernelGGL(swa_combine_for(p.nsplit, rows, bf16p, frozen != nullptr), dim3(blocks + append_blocks), dim3(256), 0, st, p.part_o,
-                       p.part_ml, p.o, p.B, p.T * p.Hq, p.nsplit, ap, frozen);
-    return check_launch(frozen != nullptr ? "ivl_swa_decode_rows_hold_fwd(combine)"
+    hipLaunchKernelGGL(swa_combine_for(p.nsplit, rows, bf16p, frozen != nullptr && !counts, counts), dim3(blocks + append_blocks), dim3(256), 0,
+                       st, p.part_o, p.part_ml, p.o, p.B, p.T * p.Hq, p.nsplit, ap, frozen);
+    return check_launch(counts            ? "ivl_swa_rows_n_fwd(combine)"
+                        : frozen != nullptr ? "ivl_swa_decode_rows_hold_fwd(combine)"
                         : rows            ? "ivl_swa_decode_rows_fwd / ivl_swa_rows_fwd(combine)"
                                           : "ivl_swa_fwd(combine)");
   }
   if (append_blocks > 0) {                     // one split (the packed pos_rows forms always have splits to merge: ivl_swa_rows_fwd only)
     ap.first_block = 0;
+    if (counts) {
+      hipLaunchKernelGGL(swa_cache_append_n_kernel, dim3(append_blocks), dim3(256), 0, st, ap, frozen);
+      return check_launch("ivl_swa_rows_n_fwd(append)");
+    }
     hipLaunchKernelGGL((rows ? swa_cache_append_kernel<PerRow> : swa_cache_append_kernel<>), dim3(append_blocks), dim3(256), 0, st, ap);
     return check_launch(rows ? "ivl_swa_rows_fwd(append)" : "ivl_swa_fwd(append)");
   }
@@ -1312,7 +1374,9 @@ extern "C" size_t ivl_swa_workspace_bytes(int B, int T, int Hq, int d) {
 // workgroups and the merge of ivl_swa_fwd on the same arguments (ROWS-1); the PerRow instances differ from the scalar ones in where
 // a workgroup reads its position.
 typedef void (*swa_attn_fn)(const long long*, SwaParams, const int32_t*);
-static int swa_plan_launch(const char* fn, const ivl_swa_args* a, const long long* pos_rows, const int32_t* frozen, void* stream) {
+// `n_rows` != nullptr (ivl_swa_rows_n_fwd, an unpacked shape by its rules): the PerRowN instances on the same grids -- the plan reads no length.
+static int swa_plan_launch(const char* fn, const ivl_swa_args* a, const long long* pos_rows, const int32_t* frozen, const int32_t* n_rows,
+                           void* stream) {
   const bool per_row = pos_rows != nullptr;
   const int G = a->Hq / a->Hkv;
   const bool pack = (long long)a->T * G <= SWA_QT && G <= 16;
@@ -1351,9 +1415,14 @@ static int swa_plan_launch(const char* fn, const ivl_swa_args* a, const long lon
                 "%s: workspace %zu bytes < required %zu (rope pre-pass)", fn, a->workspace_bytes, n_part + (n_q + n_k) * sizeof(bf16_t));
     bf16_t* q_rot = (bf16_t*)((unsigned char*)a->workspace + n_part);
     bf16_t* k_rot = q_rot + n_q;
-    hipLaunchKernelGGL(swa_rope_prepass_kernel, dim3(blocks256((long long)a->B * a->T * (a->Hq + a->Hkv) * 8, 2048)), dim3(256), 0, st, p.q,
-                       p.q_sb, p.q_st, p.q_sh, p.k_new, p.kn_sb, p.kn_st, p.kn_sh, q_rot, k_rot, a->B, a->T, a->Hq, a->Hkv, p.rcos, p.rsin,
-                       p.rs0, p.rs1);
+    if (n_rows != nullptr)
+      hipLaunchKernelGGL(swa_rope_prepass_rows_kernel, dim3(blocks256((long long)a->B * a->T * (a->Hq + a->Hkv) * 8, 2048)), dim3(256), 0, st, p.q,
+                         p.q_sb, p.q_st, p.q_sh, p.k_new, p.kn_sb, p.kn_st, p.kn_sh, q_rot, k_rot, a->B, a->T, a->Hq, a->Hkv, p.rcos, p.rsin,
+                         p.rs0, p.rs1, n_rows);
+    else
+      hipLaunchKernelGGL(swa_rope_prepass_kernel, dim3(blocks256((long long)a->B * a->T * (a->Hq + a->Hkv) * 8, 2048)), dim3(256), 0, st, p.q,
+                         p.q_sb, p.q_st, p.q_sh, p.k_new, p.kn_sb, p.kn_st, p.kn_sh, q_rot, k_rot, a->B, a->T, a->Hq, a->Hkv, p.rcos, p.rsin,
+                         p.rs0, p.rs1);
     if (const int rc = check_launch(per_row ? "ivl_swa_rows_fwd(rope pre-pass)" : "ivl_swa_fwd(rope pre-pass)"); rc != IVL_OK) return rc;
     p.q = q_rot; p.q_sb = (long long)a->T * a->Hq * SWA_D; p.q_st = (long long)a->Hq * SWA_D; p.q_sh = SWA_D;
     p.k_new = k_rot; p.kn_sb = (long long)a->T * a->Hkv * SWA_D; p.kn_st = (long long)a->Hkv * SWA_D; p.kn_sh = SWA_D;
@@ -1364,14 +1433,15 @@ static int swa_plan_launch(const char* fn, const ivl_swa_args* a, const long lon
   if (pack && a->mma_dtype == IVL_FP8_E4M3) {          // (ivl_swa_fwd only: the pos_rows entry points take bf16)
     hipLaunchKernelGGL(swa_decode_fp8_kernel, dim3(a->Hkv * a->B * nsplit), dim3(256), 0, st, p.pos_dev, p);
   } else {
-    const swa_attn_fn kernel = prefill  ? (per_row ? swa_prefill_kernel<PerRow> : swa_prefill_kernel<>)
+    const swa_attn_fn kernel = n_rows   ? (prefill ? swa_prefill_kernel<PerRowN> : swa_fwd_kernel<false, 1, PerRowN>)
+                               : prefill  ? (per_row ? swa_prefill_kernel<PerRow> : swa_prefill_kernel<>)
                                : !pack  ? (per_row ? swa_fwd_kernel<false, 1, PerRow> : swa_fwd_kernel<false, 1>)
                                : frozen ? swa_fwd_kernel<true, 1, PerRowHold>
                                         : (per_row ? swa_fwd_kernel<true, 1, PerRow> : swa_fwd_kernel<true, 1>);
-    hipLaunchKernelGGL(kernel, grid, dim3(prefill ? P8_THREADS : 256), 0, st, p.pos_dev, p, frozen);
+    hipLaunchKernelGGL(kernel, grid, dim3(prefill ? P8_THREADS : 256), 0, st, p.pos_dev, p, n_rows ? n_rows : frozen);
   }
   if (const int rc = check_launch(fn); rc != IVL_OK) return rc;
-  return swa_combine_append(p, per_row, prefill, a->append_new != 0, st, frozen);
+  return swa_combine_append(p, per_row, prefill, a->append_new != 0, st, n_rows ? n_rows : frozen, n_rows != nullptr);
 }
 
 extern "C" int ivl_swa_fwd(const ivl_swa_args* a, void* stream) {
@@ -1400,13 +1470,14 @@ extern "C" int ivl_swa_fwd(const ivl_swa_args* a, void* stream) {
     const size_t need = ivl_swa_ring256_workspace_bytes(a->B, a->T, a->Hq, a->Hkv, a->d, a->cache_capacity);
     if (need != 0 && a->workspace != nullptr && a->workspace_bytes >= need) return swa_ring256_launch(a, (hipStream_t)stream);
   }
-  return swa_plan_launch(fn, a, nullptr, nullptr, stream);
+  return swa_plan_launch(fn, a, nullptr, nullptr, nullptr, stream);
 }
 
 // The three pos_rows entry points: one rule list, then the launch plan.  `packed_step` (ivl_swa_decode_rows_fwd and its hold form: a
 // decode step) adds the packing rule and, last, the rule that the shape has splits to merge; frozen == nullptr in the hold form IS
 // ivl_swa_decode_rows_fwd.  Never the ring256 form.
-static int swa_rows_entry(const char* fn, const ivl_swa_args* a, const int64_t* pos_rows, const int32_t* frozen, bool packed_step, void* stream) {
+static int swa_rows_entry(const char* fn, const ivl_swa_args* a, const int64_t* pos_rows, const int32_t* frozen, const int32_t* n_rows,
+                          bool packed_step, void* stream) {
   // (a NULL struct is refused first, by the shared rule behind this one)
   IVL_REQUIRE(a == nullptr || pos_rows != nullptr, IVL_ERR_INVALID_ARG, "%s: NULL pos_rows", fn);
   if (const int rc = swa_check_pointers(a, fn); rc != IVL_OK) return rc;
@@ -1426,22 +1497,32 @@ static int swa_rows_entry(const char* fn, const ivl_swa_args* a, const int64_t* 
               "%s: mrope sections must be multiples of 8 (got %d, %d)", fn, a->rope_s0, a->rope_s1);
   if (const int rc = swa_check_key_rows(a, fn, packed_step ? "" : " (split the call)"); rc != IVL_OK) return rc;
   IVL_REQUIRE(!packed_step || swa_pack_nsplit(a) > 1, IVL_ERR_UNSUPPORTED, "%s: single-split shape (window %d)", fn, a->window);
-  return swa_plan_launch(fn, a, (const long long*)pos_rows, frozen, stream);
+  // token counts per row: the unpacked forms only (the decode step has its hold twin)
+  IVL_REQUIRE(n_rows == nullptr || !((long long)a->T * G <= SWA_QT && G <= 16), IVL_ERR_UNSUPPORTED,
+              "%s: packed shapes (T * Hq/Hkv = %lld <= %d) take no token counts: hold the row (ivl_swa_decode_rows_hold_fwd)", fn,
+              (long long)a->T * G, SWA_QT);
+  return swa_plan_launch(fn, a, (const long long*)pos_rows, frozen, n_rows, stream);
 }
 
 extern "C" int ivl_swa_decode_rows_fwd(const ivl_swa_args* a, const int64_t* pos_rows, void* stream) {
-  return swa_rows_entry("ivl_swa_decode_rows_fwd", a, pos_rows, nullptr, true, stream);
+  return swa_rows_entry("ivl_swa_decode_rows_fwd", a, pos_rows, nullptr, nullptr, true, stream);
 }
 
 // ivl_swa_decode_rows_fwd with a per-row hold mask (HOLD-1..3 in ivl_hip.h): the same split count, grid and merge; the workgroups,
 // combine blocks and ring slots of a row with frozen[b] != 0 do nothing
 extern "C" int ivl_swa_decode_rows_hold_fwd(const ivl_swa_args* a, const int64_t* pos_rows, const int32_t* frozen, void* stream) {
-  return swa_rows_entry("ivl_swa_decode_rows_hold_fwd", a, pos_rows, frozen, true, stream);
+  return swa_rows_entry("ivl_swa_decode_rows_hold_fwd", a, pos_rows, frozen, nullptr, true, stream);
 }
 
 // ivl_swa_fwd with one ring position per batch row, every T >= 1 (ROWS-1..4 in ivl_hip.h): ivl_swa_fwd's launch plan on the PerRow kernels
 extern "C" int ivl_swa_rows_fwd(const ivl_swa_args* a, const int64_t* pos_rows, void* stream) {
-  return swa_rows_entry("ivl_swa_rows_fwd", a, pos_rows, nullptr, false, stream);
+  return swa_rows_entry("ivl_swa_rows_fwd", a, pos_rows, nullptr, nullptr, false, stream);
+}
+
+// ivl_swa_rows_fwd with a token count per batch row (RAG-5..10 in ivl_hip.h): the same rules and launch plan on the PerRowN kernels;
+// n_rows == nullptr IS ivl_swa_rows_fwd
+extern "C" int ivl_swa_rows_n_fwd(const ivl_swa_args* a, const int64_t* pos_rows, const int32_t* n_rows, void* stream) {
+  return swa_rows_entry(n_rows ? "ivl_swa_rows_n_fwd" : "ivl_swa_rows_fwd", a, pos_rows, nullptr, n_rows, false, stream);
 }
 
 extern "C" int ivl_swa_cache_append(const void* k_new, const void* v_new, int64_t kn_sb, int64_t kn_st, int64_t kn_sh,

@@ -428,8 +428,11 @@ class InfiniteVLTextStack(nn.Module):
     def forward(self, input_ids: Optional[torch.Tensor] = None, inputs_embeds: Optional[torch.Tensor] = None,
                 position_ids: Optional[torch.Tensor] = None, past_key_values: Optional[StaticCachePrealloc] = None,
                 cache_position: Optional[torch.Tensor] = None, logits_to_keep: int = 1,
-                layer_hooks=None, adapters=None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
-        """layer_hooks = (before_mixer(i), after_mixer(i)) or None: called around the cache-touching part of
+                layer_hooks=None, adapters=None, frame_lengths: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+        """frame_lengths (device int32 [B], on a MultiStreamCache; read by the kernels when they run): a ragged frame step -- slot b
+        takes the first frame_lengths[b] of its T tokens and nothing else of its row touches its state; 0 = the slot sits the call out.
+        hidden[b, n_b:] is unspecified; with logits_to_keep = 1 the logits are those of each slot's last valid token.
+        layer_hooks = (before_mixer(i), after_mixer(i)) or None: called around the cache-touching part of
         decoder layer i (used by dist.sequence_parallel_prefill to receive / forward that layer's state).
         adapters (after enable_adapters): None = the base model; a handle of load_adapter = that adapter for every row; an int32
         device tensor [B] = one adapter index per batch row, read on the device (-1 = none; calls of more than 4 rows read it on
@@ -445,12 +448,17 @@ class InfiniteVLTextStack(nn.Module):
         if self._lora is not None:
             self._lora.rows = adapters
             try:
-                return self._forward(input_ids, inputs_embeds, position_ids, past_key_values, cache_position, logits_to_keep, layer_hooks)
+                return self._forward(input_ids, inputs_embeds, position_ids, past_key_values, cache_position, logits_to_keep, layer_hooks,
+                                     frame_lengths)
             finally:
                 self._lora.rows = None
-        return self._forward(input_ids, inputs_embeds, position_ids, past_key_values, cache_position, logits_to_keep, layer_hooks)
+        return self._forward(input_ids, inputs_embeds, position_ids, past_key_values, cache_position, logits_to_keep, layer_hooks, frame_lengths)
 
-    def _forward(self, input_ids, inputs_embeds, position_ids, past_key_values, cache_position, logits_to_keep, layer_hooks):
+    def _forward(self, input_ids, inputs_embeds, position_ids, past_key_values, cache_position, logits_to_keep, layer_hooks,
+                 frame_lengths=None):
+        if frame_lengths is not None and logits_to_keep not in (0, 1):
+            raise ValueError(f"forward: frame_lengths goes with logits_to_keep 0 or 1 (got {logits_to_keep})")
+        ragged = {} if frame_lengths is None else {"frame_lengths": frame_lengths}
         if inputs_embeds is None:
             inputs_embeds = self.embed_tokens(input_ids)
         B, T, _ = inputs_embeds.shape
@@ -484,7 +492,7 @@ class InfiniteVLTextStack(nn.Module):
                 layer_hooks[0](layer.self_attn.layer_idx)
             attn, _ = layer.self_attn(hidden_states=y, position_ids=position_ids, past_key_values=past_key_values,
                                       use_cache=past_key_values is not None, cache_position=cache_position,
-                                      position_embeddings=position_embeddings)
+                                      position_embeddings=position_embeddings, **ragged)
             if layer_hooks is not None:
                 layer_hooks[1](layer.self_attn.layer_idx)
             if isinstance(y, ops.PreNorm) and not y.done:
@@ -499,7 +507,10 @@ class InfiniteVLTextStack(nn.Module):
             _, h = self.norm.add_and_norm(pend, resid)
         logits = None
         if logits_to_keep:
-            logits = ops.linear(h[:, -logits_to_keep:, :], self.embed_tokens.weight,  # tied lm_head (std:2091-2092)
+            last = h[:, -logits_to_keep:, :]
+            if frame_lengths is not None:        # each slot's last valid token: a device gather (row 0 for a slot that sat the call out)
+                last = h[torch.arange(B, device=h.device), (frame_lengths.to(torch.int64) - 1).clamp_(0, T - 1)][:, None, :]
+            logits = ops.linear(last, self.embed_tokens.weight,  # tied lm_head (std:2091-2092)
                                 **ops.w8_kwargs(self._w8_lm_head, self._w8_on),
                                 **ops.wide_kwargs(self._wide_on and (self._lora is None or self._wide_lora),     # (under an adapter table: only with adapters=True,
                                                   max_rows=self._wide_rows if self._lora is None else 16))        # and never past 16 rows)
@@ -752,8 +763,9 @@ class GraphedMultiStreamStep(_Graphed):
     inputs_embeds [S,T,hidden] and position_ids [3,S,T]; the positions advance by T inside the graph as in GraphedStep (a
     caller whose frames are not text-like overwrites them through step()).  Streams join and leave between replays (admit /
     release on the cache or on a GraphedMultiStreamDecode over it) without a recapture; an idle slot computes on zeros.  Every
-    slot takes the frame: a hold mask on the cache is not read (the GDN chunk kernels have no per-slot mask).  bf16 only, no
-    adapter table (prefill adapters read their indices on the host)."""
+    slot takes the frame: a hold mask on the cache is not read.  bf16 only, no adapter table (prefill adapters read their indices
+    on the host).  Slots that bring fewer than T tokens, or none: GraphedRaggedStep."""
+    ragged = False
 
     def __init__(self, model: InfiniteVLTextStack, cache: MultiStreamCache, T: int, logits_to_keep: int = 1, warmup: int = 2):
         if not isinstance(cache, MultiStreamCache):
@@ -793,9 +805,13 @@ class GraphedMultiStreamStep(_Graphed):
             self._sync = ops.new_gdn_sync_area(self.inputs_embeds.device)
         self.hidden, self.logits = self._capture([self.position_ids, self.inputs_embeds], ops.gdn_sync_scope(self._sync))
 
-    def step(self, inputs_embeds: Optional[torch.Tensor] = None, position_ids: Optional[torch.Tensor] = None, graph: bool = True):
+    def step(self, inputs_embeds: Optional[torch.Tensor] = None, position_ids: Optional[torch.Tensor] = None, lengths=None,
+             graph: bool = True):
         """Copies what it is given into the static buffers, replays, returns (hidden [S,T,hidden], logits [S,keep,vocab]).
-        graph=False runs the same step eagerly (the reference the captured graph is checked against)."""
+        graph=False runs the same step eagerly (the reference the captured graph is checked against).  `lengths`: a
+        GraphedRaggedStep's."""
+        if lengths is not None:
+            raise ValueError("GraphedMultiStreamStep.step: lengths= needs a ragged stepper (GraphedRaggedStep); here every slot takes T tokens")
         if inputs_embeds is not None:
             self.inputs_embeds.copy_(inputs_embeds)
         if position_ids is not None:
@@ -808,6 +824,74 @@ class GraphedMultiStreamStep(_Graphed):
         self.graph.replay()
         self.cache.advance(self.T)           # (with holds the per-slot mirror is rewritten by cache.sync_lengths())
         ops.gdn_sync_check(self.inputs_embeds.device)
+        return self.hidden, self.logits
+
+
+class GraphedRaggedStep(GraphedMultiStreamStep):
+    """GraphedMultiStreamStep with a token count per slot: slot s takes the first lengths[s] of its T tokens (0 <= lengths[s] <= T)
+    and nothing else of its row of the static buffer touches its state -- dynamic-resolution frames, a camera that skips a tick
+    (0: the slot sits the step out, bit for bit), a question on one slot while the others receive video.  The counts live in the
+    static buffer `lengths` (device int32 [S], initialised to T) that the captured forward reads (forward(frame_lengths=): the
+    chunk-form GDN call and sliding-window attention with a count per row, include/ivl_hip.h RAG-1..10); changing them between
+    replays never recaptures.  In the graph position_ids += lengths[None, :, None]; logits (logits_to_keep = 1) are those of each
+    slot's last valid token; hidden[s, lengths[s]:] is unspecified.  The GDN call is always the two-launch form."""
+    ragged = True
+
+    def __init__(self, model: InfiniteVLTextStack, cache: MultiStreamCache, T: int, logits_to_keep: int = 1, warmup: int = 2):
+        super().__init__(model, cache, T, logits_to_keep=logits_to_keep, warmup=warmup)
+        if logits_to_keep not in (0, 1):
+            raise ValueError(f"GraphedRaggedStep: logits_to_keep must be 0 or 1 (the last valid token of each slot); got {logits_to_keep!r}")
+        G = model.config.num_attention_heads // model.config.num_key_value_heads
+        if self.T * G <= 64 and G <= 16:
+            raise ValueError(f"GraphedRaggedStep: T * Hq/Hkv = {self.T * G} <= 64 is a packed attention shape, and sliding-window attention "
+                             f"takes token counts on the unpacked forms only (ivl_swa_rows_n_fwd); T must be above {64 // G}.  A slot that "
+                             "sits a one-token step out is held (GraphedMultiStreamDecode(holds=True))")
+        dev = self.inputs_embeds.device
+        self.lengths = torch.full((self.S,), self.T, dtype=torch.int32, device=dev)
+        # the counts of a tick go through a pinned host tensor: the copy is queued behind the previous replay, the host does not wait
+        self._lengths_host = torch.empty(self.S, dtype=torch.int32, pin_memory=dev.type == "cuda")
+        self._lengths_copied: Optional[torch.cuda.Event] = None
+
+    def _run(self):
+        h, lg = self.model(inputs_embeds=self.inputs_embeds, position_ids=self.position_ids, past_key_values=self.cache,
+                           logits_to_keep=self.logits_to_keep, frame_lengths=self.lengths)
+        self.position_ids.add_(self.lengths[None, :, None])
+        return h, lg
+
+    def check_lengths(self, lengths) -> List[int]:
+        """`lengths` as S ints in 0..T (None: every slot takes T)"""
+        if lengths is None:
+            return [self.T] * self.S
+        n = list(lengths)
+        if len(n) != self.S or any(not _is_int(v, 0, self.T + 1) for v in n):
+            raise ValueError(f"GraphedRaggedStep: lengths must be {self.S} ints in 0..{self.T}; got {lengths!r}")
+        return n
+
+    def step(self, inputs_embeds: Optional[torch.Tensor] = None, position_ids: Optional[torch.Tensor] = None, lengths=None,
+             graph: bool = True):
+        """As GraphedMultiStreamStep.step; `lengths`: a host list of S ints (None: T for every slot), copied into the static buffer.
+        The host mirror cache.slot_lengths advances per slot; nothing is read back."""
+        n = self.check_lengths(lengths)
+        if self._lengths_copied is not None:
+            self._lengths_copied.synchronize()       # the previous tick's copy has read the staging tensor (long done: a tick is ms)
+        self._lengths_host.copy_(torch.tensor(n, dtype=torch.int32))
+        self.lengths.copy_(self._lengths_host, non_blocking=True)
+        if self.lengths.is_cuda:
+            self._lengths_copied = torch.cuda.Event()
+            self._lengths_copied.record()
+        if inputs_embeds is not None:
+            self.inputs_embeds.copy_(inputs_embeds)
+        if position_ids is not None:
+            self.position_ids.copy_(position_ids)
+        if not graph:
+            with torch.no_grad():
+                out = self._run()
+            self.cache.advance_rows(n)
+            return out
+        if self._stale():
+            self.capture()
+        self.graph.replay()
+        self.cache.advance_rows(n)
         return self.hidden, self.logits
 
 
@@ -1976,17 +2060,22 @@ class GraphedMultiStreamDecode(_Graphed):
 
     @torch.no_grad()
     def extend_frames(self, stepper: "GraphedMultiStreamStep", inputs_embeds: torch.Tensor,
-                      position_ids: Optional[torch.Tensor] = None) -> torch.Tensor:
+                      position_ids: Optional[torch.Tensor] = None, lengths=None) -> torch.Tensor:
         """extend() for EVERY slot at once: inputs_embeds [S,T,hidden] -- the next video frame of every stream -- goes through ONE
         replay of `stepper` (a GraphedMultiStreamStep of T tokens on the same cache), which streams the weights once for all
         slots.  position_ids [3,S,T]; default: each slot's three positions count on from position_ids[:, slot] (computed on the
         device).  Every slot's next token is drawn from logits[:, -1] in one sampling launch (argmax without a sampler) and
         REPLACES its pending one; position_ids[:, s] becomes slot s's maximum + 1; admit_logits is set.  No host read-back.
-        Every slot takes the frame (an idle slot computes on zeros, its token is ignored).  Not with holds=True (the frame step
-        reads no mask) and not while the sampler has a guided pair (a pair's halves take different prompts)."""
+        Without `lengths` every slot takes the frame (an idle slot computes on zeros, its token is ignored).  Not with holds=True (the
+        frame step reads no hold mask; a slot sits a tick out through lengths=, below) and not while the sampler has a guided pair (a
+        pair's halves take different prompts).
+        `lengths` (a host list of S ints in 0..T; needs a GraphedRaggedStep): slot s takes its first lengths[s] tokens; default
+        positions count on over the valid tokens only; a slot with 0 tokens keeps its pending token, its three positions and its
+        sampler row untouched.  All positive: the one sampling launch; otherwise one draw per slot that took tokens."""
         who = "extend_frames"
         if self.holds:
-            raise ValueError(f"{who}: holds=True is not supported (the frame step reads no hold mask: a frozen slot would take the frame)")
+            raise ValueError(f"{who}: holds=True is not supported (the frame step reads no hold mask: a frozen slot would take the frame; "
+                             f"without holds, a GraphedRaggedStep and lengths= let a slot sit a tick out)")
         if self.sampler is not None and self.sampler._partner:
             raise ValueError(f"{who}: the sampler has a guided pair (rows {sorted(self.sampler._partner.items())}); a pair is "
                              f"extended slot by slot with extend(negative_embeds=)")
@@ -1999,16 +2088,35 @@ class GraphedMultiStreamDecode(_Graphed):
                              f"{list(inputs_embeds.shape) if torch.is_tensor(inputs_embeds) else type(inputs_embeds).__name__}")
         if position_ids is not None and tuple(position_ids.shape) != (3, self.S, T):
             raise ValueError(f"{who}: position_ids must be [3,{self.S},{T}]; got {tuple(position_ids.shape)}")
+        if lengths is not None and not stepper.ragged:
+            raise ValueError(f"{who}: lengths= needs a ragged stepper (GraphedRaggedStep); this one gives every slot T tokens")
+        n = stepper.check_lengths(lengths) if lengths is not None else None
         dev = self.position_ids.device
         if position_ids is None:
             position_ids = self.position_ids + torch.arange(T, device=dev, dtype=torch.int64)
         else:
             position_ids = position_ids.to(device=dev, dtype=torch.int64)
-        nxt = position_ids.amax(dim=(0, 2)) + 1                          # [S]
-        _, lg = stepper.step(inputs_embeds, position_ids)
+        if n is None:
+            nxt = position_ids.amax(dim=(0, 2)) + 1                      # [S]
+            _, lg = stepper.step(inputs_embeds, position_ids)
+            self.admit_logits = lg
+            self._next_token(lg[:, -1])
+            self.position_ids.copy_(nxt.view(1, self.S, 1).expand(3, self.S, 1))
+            return self.token
+        # ragged: the maximum over a slot's VALID tokens; a slot without any keeps its three positions (the host knows the counts)
+        _, lg = stepper.step(inputs_embeds, position_ids, lengths=n)
+        nv = stepper.lengths.to(torch.int64)                             # the counts the step just queued (pinned, non-blocking): no other copy
+        valid = torch.arange(T, device=dev)[None, None, :] < nv[None, :, None]
+        nxt = torch.where(valid, position_ids, torch.iinfo(torch.int64).min).amax(dim=(0, 2)) + 1
         self.admit_logits = lg
-        self._next_token(lg[:, -1])
-        self.position_ids.copy_(nxt.view(1, self.S, 1).expand(3, self.S, 1))
+        if all(v > 0 for v in n):
+            self._next_token(lg[:, -1])
+        else:
+            for slot, v in enumerate(n):
+                if v > 0:
+                    self._draw(slot, lg[slot:slot + 1])
+        took = (nv > 0).view(1, self.S, 1)
+        self.position_ids.copy_(torch.where(took, nxt.view(1, self.S, 1).expand(3, self.S, 1), self.position_ids))
         return self.token
 
     @torch.no_grad()

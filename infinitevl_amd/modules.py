@@ -143,7 +143,12 @@ class InfiniteVLSelfAttention(nn.Module):
                 ops.apply_mrope_inplace(q, k, cos, sin, sec)                                  # std:1057-1064
         rope = (cos, sin, sec) if fuse_rope else None
 
-        if isinstance(layer, StaticSlidingWindowLayerPrealloc):
+        frame_lengths = kwargs.get("frame_lengths")       # a ragged frame step: device int32 [B], tokens per slot (MultiStreamCache only)
+        if frame_lengths is not None and not hasattr(layer, "_pos_rows"):
+            raise ValueError("frame_lengths needs a MultiStreamCache (one ring position per slot)")
+        if frame_lengths is not None:
+            attn = layer.attend(q, k, v, self.scaling, self.sliding_window, mma_dtype=self.mma_dtype, rope=rope, frame_lengths=frame_lengths)
+        elif isinstance(layer, StaticSlidingWindowLayerPrealloc):
             attn = layer.attend(q, k, v, self.scaling, self.sliding_window, mma_dtype=self.mma_dtype, rope=rope)   # std:1067-1108 fused
         elif layer is None:
             attn = ops.swa_forward(q, k, v, window=self.sliding_window, scaling=self.scaling, rope=rope)
@@ -316,7 +321,7 @@ class GatedDeltaNet(nn.Module):
                 and (layer is None or (isinstance(layer, StaticLinearLayerPrealloc) and layer.dtype == torch.bfloat16))
                 and self.q_conv1d.weight.dtype == torch.bfloat16)
 
-    def _forward_fused(self, hidden_states: torch.Tensor, past_key_values, layer, cache_position, mode: str):
+    def _forward_fused(self, hidden_states: torch.Tensor, past_key_values, layer, cache_position, mode: str, frame_lengths=None):
         """One projection GEMM -> one prologue launch (3 convs + gate math) -> delta-rule kernel (state in place)
         -> gated norm reading its gate from the projection buffer -> o_proj."""
         B, T, _ = hidden_states.shape
@@ -341,7 +346,7 @@ class GatedDeltaNet(nn.Module):
         w = self.o_norm.weight
         w = w if w.dtype == torch.bfloat16 else w.to(torch.bfloat16)
         frozen = getattr(past_key_values, "hold_mask", None)
-        if (T == 1 and layer is not None and prev[0] is not None and h0 is not None and Dk == Dq
+        if (T == 1 and frame_lengths is None and layer is not None and prev[0] is not None and h0 is not None and Dk == Dq
                 and h0.data_ptr() == layer.recurrent_state.data_ptr() and K == 128 and V == 256):
             ow, ob = self.o_proj.weight, self.o_proj.bias
             # hold mode (MultiStreamCache.enable_holds): the one-launch step takes the per-row mask at every slot count (the split
@@ -370,7 +375,15 @@ class GatedDeltaNet(nn.Module):
         if frozen is not None and T == 1:      # (a frame step, T > 1, does not read the mask: every slot takes the tokens)
             raise RuntimeError(_HOLD_REFUSAL)
         convs = (self.q_conv1d.weight, self.k_conv1d.weight, self.v_conv1d.weight)
-        if mode == "chunk" and Dk == Dq and K == 128 and V == 256 and convs[0].shape[-1] == 4:
+        if frame_lengths is not None:
+            # a ragged frame step: slot b takes its first frame_lengths[b] tokens (ops.gdn_chunk_fused(n_rows=): states in place, the
+            # chunk kernels at every T -- the recurrent kernel of short calls has no per-row count)
+            if not (layer is not None and prev[0] is not None and h0 is not None and Dk == Dq and K == 128 and V == 256
+                    and convs[0].shape[-1] == 4 and self.mma_dtype is None):
+                raise ValueError("frame_lengths needs the fused bf16 Gated DeltaNet call on a cache with history (128 x 256 heads, conv width 4)")
+            o = ops.gdn_chunk_fused(proj, (cq, ck, cv, ca, cb), convs, outs, outs, A32, dt32, H, K, V, initial_state=layer.recurrent_state,
+                                    final_state_out=layer.recurrent_state, n_rows=frame_lengths)
+        elif mode == "chunk" and Dk == Dq and K == 128 and V == 256 and convs[0].shape[-1] == 4:
             # convs + gates inside the chunk kernel's pre-pass: q / k / v / g / beta never reach HBM, one launch less
             o = ops.gdn_chunk_fused(proj, (cq, ck, cv, ca, cb), convs, prev, outs, A32, dt32, H, K, V,
                                     initial_state=h0, final_state_out=layer.recurrent_state if layer is not None else None,
@@ -399,7 +412,9 @@ class GatedDeltaNet(nn.Module):
 
         layer = past_key_values.layers[self.layer_idx] if past_key_values is not None else None
         if self._fused_ok(hidden_states, layer):
-            return self._forward_fused(hidden_states, past_key_values, layer, cache_position, mode)
+            return self._forward_fused(hidden_states, past_key_values, layer, cache_position, mode, kwargs.get("frame_lengths"))
+        if kwargs.get("frame_lengths") is not None:
+            raise ValueError("frame_lengths needs the fused bf16 Gated DeltaNet call (fuse_(), a bf16 cache)")
         if self._lora is not None:
             raise RuntimeError("adapters are attached (enable_adapters): they ride on the fused bf16 projections only")
         if getattr(past_key_values, "hold_mask", None) is not None and q_len == 1:

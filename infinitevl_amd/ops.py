@@ -486,12 +486,24 @@ def gdn_sync_reset(device=None) -> None:
         torch.cuda.synchronize(device)
 
 
+RAGGED_CALLS = 0               # calls of gdn_chunk_fused / swa_forward_rows with n_rows (tests and tools read it: the ragged kernels ran)
+
+
+def _n_rows(n_rows: torch.Tensor, B: int, like: torch.Tensor) -> torch.Tensor:
+    """The per-row token counts of a ragged call: a device int32 [B], read by the kernels when the launch runs (never here)."""
+    assert n_rows.dtype == torch.int32 and n_rows.is_contiguous() and tuple(n_rows.shape) == (B,) and n_rows.device == like.device, \
+        (n_rows.dtype, tuple(n_rows.shape), n_rows.device)
+    return n_rows
+
+
 def gdn_chunk_fused(proj: torch.Tensor, cols, conv_weights, conv_states_in, conv_states_out, A_log32, dt_bias32,
-                    H: int, K: int, V: int, scale=None, initial_state=None, final_state_out=None, mma_dtype=None):
+                    H: int, K: int, V: int, scale=None, initial_state=None, final_state_out=None, mma_dtype=None, n_rows=None):
     """Chunked gated delta rule with its front end (3 short convs + SiLU + gate math) inside the pre-pass: one call from
     the fused projection output to the mixer core's output (std:1253-1323).  proj [B,T,ld] bf16; cols = (col_q, col_k,
     col_v, col_a, col_b); conv_weights 3 x [D,1,4] bf16; conv_states_in / _out 3 x ([B,D,4] bf16 or None; out may alias in).
-    Returns o [B,T,H,V] bf16; the final recurrent state is written into `final_state_out` when given."""
+    Returns o [B,T,H,V] bf16; the final recurrent state is written into `final_state_out` when given.
+    n_rows (device int32 [B]): row b takes its first n_rows[b] tokens only (ivl_gdn_chunk_fused_rows_fwd, RAG-1..4: states in
+    place, o[b, n_b:] unspecified, always two launches)."""
     _need_gpu(proj)
     B, T, ld = proj.shape
     assert proj.is_contiguous() and proj.dtype == torch.bfloat16
@@ -507,12 +519,16 @@ def gdn_chunk_fused(proj: torch.Tensor, cols, conv_weights, conv_states_in, conv
             assert s.is_contiguous() and tuple(s.shape) == (B, H, K, V), (s.shape, (B, H, K, V))
     wq, wk, wv = conv_weights
     si, so = conv_states_in, conv_states_out
-    _lib.check(lib.ivl_gdn_chunk_fused_fwd(
-        _p(proj), ld, cols[0], cols[1], cols[2], cols[3], cols[4], _p(wq), _p(wk), _p(wv),
-        _p(si[0]), _p(si[1]), _p(si[2]), _p(so[0]), _p(so[1]), _p(so[2]), _p(A_log32), _p(dt_bias32), _p(o),
-        *_pd(h0), *_pd(ht),
-        B, T, H, K, V, wq.shape[-1], float(K ** -0.5 if scale is None else scale), mma_code(mma_dtype), _p(ws), ws.numel(),
-        _p(area) if _GDN_SINGLE_LAUNCH else None, _stream(proj)))
+    args = (_p(proj), ld, cols[0], cols[1], cols[2], cols[3], cols[4], _p(wq), _p(wk), _p(wv),
+            _p(si[0]), _p(si[1]), _p(si[2]), _p(so[0]), _p(so[1]), _p(so[2]), _p(A_log32), _p(dt_bias32), _p(o),
+            *_pd(h0), *_pd(ht),
+            B, T, H, K, V, wq.shape[-1], float(K ** -0.5 if scale is None else scale), mma_code(mma_dtype), _p(ws), ws.numel())
+    if n_rows is None:
+        _lib.check(lib.ivl_gdn_chunk_fused_fwd(*args, _p(area) if _GDN_SINGLE_LAUNCH else None, _stream(proj)))
+    else:
+        global RAGGED_CALLS
+        RAGGED_CALLS += 1
+        _lib.check(lib.ivl_gdn_chunk_fused_rows_fwd(*args, _p(_n_rows(n_rows, B, proj)), _stream(proj)))
     return o
 
 
@@ -1919,14 +1935,16 @@ ROWS_STEP_CALLS = 0            # calls of swa_forward_rows (tests and tools read
 def swa_forward_rows(
     q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor, *, window: Optional[int], scaling: float,
     k_cache: torch.Tensor, v_cache: torch.Tensor, pos_rows: torch.Tensor, rope=None, append: bool = False,
-    layout: str = "bthd",
+    layout: str = "bthd", n_rows: Optional[torch.Tensor] = None,
 ) -> torch.Tensor:
     """swa_forward with one ring position per batch row for every T >= 1 (ivl_swa_rows_fwd): a T-token frame for each of B
     independent streams in the rows of one ring cache; returns o [B,T,Hq,d] bf16.  Layout and stride rules as swa_forward.
     `pos_rows` (device int64 [B]) is read when the launch runs and is not advanced.  Row b's output and ring row are
     bit-equal to row b of swa_forward on the same tensors with every row at pos_rows[b] (ROWS-1 in include/ivl_hip.h).
-    Ring cache, T_new == T, bf16; `rope` and `append` as in swa_forward."""
-    _need_gpu(q, k_new, v_new, k_cache, v_cache, pos_rows)
+    Ring cache, T_new == T, bf16; `rope` and `append` as in swa_forward.
+    `n_rows` (device int32 [B], read when the launch runs; ivl_swa_rows_n_fwd, RAG-5..10): row b brings its first n_rows[b] tokens
+    only -- the others are neither read nor appended and their rows of o are unspecified.  Unpacked shapes (T * Hq/Hkv > 64)."""
+    _need_gpu(q, k_new, v_new, k_cache, v_cache, pos_rows, n_rows)
 
     def rules(B, T, T_new, Hq, Hkv):
         if pos_rows.dtype != torch.int64 or tuple(pos_rows.shape) != (B,) or not pos_rows.is_contiguous():
@@ -1945,7 +1963,12 @@ def swa_forward_rows(
     a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
     global ROWS_STEP_CALLS
     ROWS_STEP_CALLS += 1
-    _lib.check(lib.ivl_swa_rows_fwd(ctypes.byref(a), pos_rows.data_ptr(), _stream(q)))
+    if n_rows is None:
+        _lib.check(lib.ivl_swa_rows_fwd(ctypes.byref(a), pos_rows.data_ptr(), _stream(q)))
+    else:
+        global RAGGED_CALLS
+        RAGGED_CALLS += 1
+        _lib.check(lib.ivl_swa_rows_n_fwd(ctypes.byref(a), pos_rows.data_ptr(), _p(_n_rows(n_rows, a.B, q)), _stream(q)))
     del keep                   # (held until here: the launches are issued)
     return o
 
